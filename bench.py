@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: region-crops/sec embedded + all-pairs cosine (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N rank processes itself
 (fresh children, before this process imports torch or touches a GPU) and relays rank 0's JSON
@@ -31,8 +31,15 @@ of the table BASELINE.md section 4 specifies for its config and GPU count.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the bf16 MFMA GEMM,
 gemm_bf16_tn_*): algorithmic GEMM FLOPs of a step / the GEMM kernels' summed duration,
-measured with HIP events on the launch stream inside the timed region.  `cpu_baseline`
-(N = 1 only) times the oracle's reference-shaped path on the host cores on bounded samples.
+measured with HIP events on the launch stream inside the timed region.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds everything else
+the line can carry, each after the timed steps: `cpu_baseline` (N = 1 only: the oracle's
+reference-shaped path on the host cores on bounded samples), parity against the oracle (C5:
+`labels_equal_oracle`), the secondary legs of the N = 1 line (C4 share, last layer pruned, from
+host arrays, through process_regions), the box probe and `result_digest`.
+
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -81,11 +88,18 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-from-host", action="store_true", help="skip the secondary PCIe-inclusive measurement (value_from_host)")
     ap.add_argument("--no-c4-share", action="store_true", help="skip the secondary 8192-crop C4-share measurement of the N = 1 line")
-    ap.add_argument("--headline-only", action="store_true", help="= --no-cpu-baseline --no-from-host --no-c4-share (profiler passes)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: = --no-cpu-baseline --no-from-host --no-c4-share, and no clock probe")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the CPU baseline, the oracle checks, the secondary "
+                    "legs, the box probe and the result digest (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (f32 / f64, <= 64 MB "
+                    "in all: larger outputs as a fixed seeded sample of rows)")
     ap.add_argument("--force-dist", action="store_true", help="create the torch.distributed process group (nccl = RCCL on a GPU box) at "
                     "WORLD_SIZE = 1 too and run every collective of the N > 1 path through it: the one-GPU rehearsal of the multi-GPU code")
     ap.add_argument("--timeout", type=float, default=570.0, help="seconds the self-started multi-rank run may take before every rank is stopped (0: unbounded)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1 (it writes what the last timed step returned)")
+    return args
 
 
 def free_port() -> int:
@@ -287,7 +301,7 @@ def c3_inputs(n, dev):
 
 def main():
     args = parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_from_host = args.no_c4_share = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.timeout))
@@ -431,12 +445,18 @@ def main():
     elapsed_local = time.perf_counter() - t0
     prof = eng.profile_read()
     eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        outputs = {"embeddings_f32": e32, "embeddings_bf16": e16, "cosine": sim}
+        if c5 is not None:
+            outputs.update(page_matrix=c5["S"], labels=np.asarray(c5["labels"]), n_clusters=np.asarray(c5["k"]))
+        dump_outputs(args.dump_outputs, outputs)
     per_rank = mdist.all_gather_floats(elapsed_local, dev)
     startup_by_rank = mdist.all_gather_floats(startup_s, dev)
-    # which class of box every rank ran on: outside the timed region.  --headline-only (the profiler passes) skips
-    # the clock probe: its 0.5 s of GEMM launches would be folded into the kernel statistics of the step
-    box = box_probe(eng, dev, clock=not args.headline_only)
-    box_by_rank = {k: mdist.all_gather_floats(v if v is not None else float("nan"), dev) for k, v in box.items()}
+    if args.full:
+        # which class of box every rank ran on: outside the timed region.  --headline-only (the profiler passes) skips
+        # the clock probe: its 0.5 s of GEMM launches would be folded into the kernel statistics of the step
+        box = box_probe(eng, dev, clock=not args.headline_only)
+        box_by_rank = {k: mdist.all_gather_floats(v if v is not None else float("nan"), dev) for k, v in box.items()}
     elapsed = max(per_rank)
     steps = max(args.steps, 1)
     gather_ms = None
@@ -514,11 +534,6 @@ def main():
             },
             "ms_per_step_by_rank": [t * 1e3 / steps for t in per_rank],
             "startup_s_by_rank": startup_by_rank,
-            "box": {**{k: v[0] for k, v in box_by_rank.items()}, "by_rank": box_by_rank,
-                    "what": "hbm_copy_gbs: device-to-device copy of 1 GiB (read + written bytes / HIP-event time, ~50 ms of copies): boxes of this "
-                            "pool stream at ~3.9 or ~5.5 TB/s in K1 and differ up to 30 % on the HBM-bound kernels; gemm_clock_ghz: s_memtime / "
-                            "s_memrealtime of one stamped launch of the QKV-shaped GEMM after 0.5 s of the product kernel (mme_gemm_stamps)"},
-            "result_digest": result_digest(e32, table[: n * world], c5),
             "allgather_ms": gather_ms,
             "allgather_host_ms": gather_host_s[0] * 1e3 / steps if use_dist else None,
             "allgather_bytes": float(n) * world * 768 * 2 if use_dist else None,
@@ -531,6 +546,12 @@ def main():
             "roofline": roofline,
             "from_profile": rec,
         }
+        if args.full:
+            out["box"] = {**{k: v[0] for k, v in box_by_rank.items()}, "by_rank": box_by_rank,
+                          "what": "hbm_copy_gbs: device-to-device copy of 1 GiB (read + written bytes / HIP-event time, ~50 ms of copies): boxes of this "
+                                  "pool stream at ~3.9 or ~5.5 TB/s in K1 and differ up to 30 % on the HBM-bound kernels; gemm_clock_ghz: s_memtime / "
+                                  "s_memrealtime of one stamped launch of the QKV-shaped GEMM after 0.5 s of the product kernel (mme_gemm_stamps)"}
+            out["result_digest"] = result_digest(e32, table[: n * world], c5)
         parity = None
         labels_equal = None
         if world == 1 and config == "c2" and not args.no_cpu_baseline:
@@ -661,11 +682,13 @@ def main_tilevit(args, rank, world, local, use_dist):
     eng.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, e32, _ = eng.tile_vit_forward(pv, ids, nt)
+        _, e32, e16 = eng.tile_vit_forward(pv, ids, nt)
     fence()
     elapsed_local = time.perf_counter() - t0
     prof = eng.profile_read()
     eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings_f32": e32, "embeddings_bf16": e16})
     per_rank = mdist.all_gather_floats(elapsed_local, dev)
     elapsed = max(per_rank)
     steps = max(args.steps, 1)
@@ -727,6 +750,33 @@ def main_tilevit(args, rank, world, local, use_dist):
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 63_000_000  # the .npy headers fit in the rest of 64 MB
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every output of the last timed step as out_dir/<name>.npy, float64 kept as float64, everything else
+    as float32 (bf16 widens exactly; integers go to float64).  At most 64 MB in all: taken smallest first, an output
+    larger than its even share of what is left keeps a fixed sample of its rows (numpy default_rng(0), sorted), so that
+    runs with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    tensors = {k: v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v)) for k, v in outputs.items()}
+    wide = {k: torch.float64 if t.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32 for k, t in tensors.items()}
+    left = DUMP_BYTES
+    for i, name in enumerate(sorted(tensors, key=lambda k: tensors[k].numel() * wide[k].itemsize)):
+        t = tensors[name]
+        share = left // (len(tensors) - i)
+        if t.numel() * wide[name].itemsize > share and t.dim() > 0:
+            row_bytes = t[0].numel() * wide[name].itemsize
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], max(1, share // row_bytes), replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.to(wide[name]).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
 
 
 def box_probe(eng, dev, clock=True):

@@ -12,17 +12,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs /root/reference (build container only)")
 
 
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
 
-
-def pytest_collection_modifyitems(config, items):
-    have_ref = os.path.isdir("/root/reference/deprecated_package")
-    skip_ref = pytest.mark.skip(reason="/root/reference not present (GPU box)")
-    for item in items:
-        if "reference" in item.keywords and not have_ref:
-            item.add_marker(skip_ref)

@@ -28,6 +28,8 @@ Fixtures written
   vit_cases.npz          transformers.ViTModel (seeded synthetic weights) hidden states / embeddings
   crops/*.png            a few bundled region crops (data) incl. the 16 crops of config C1
   crops_expected.npz     Pillow resize + MllamaImageProcessorPil outputs for those crops
+  bundled_crop_sizes_hw.npy, bundled_crop_names.json
+                         (height, width) and file name of every bundled region crop (output/region_images), sorted by name
   tile_vit_cases.npz     transformers MllamaVisionModel (560 / 14 / 1280-d / 32 + 8 layers, seeded weights) rows per tile grid
                          (run separately: `make_golden.py --only-tile-vit`, ~15 min of CPU)
   query_cases.json       a brute-force store queried through the REAL safe_query (wrc:73-95): ids / distances
@@ -829,6 +831,7 @@ def main():
     # crop sizes of the whole bundled set (for the C3 workload shape): int-truncated bbox sizes
     all_sizes = np.array([[sizes[f][1], sizes[f][0]] for f in allf], dtype=np.int32)
     np.save(os.path.join(HERE, "bundled_crop_sizes_hw.npy"), all_sizes)
+    json.dump(allf, open(os.path.join(HERE, "bundled_crop_names.json"), "w"), indent=0)
     print("crops:", len(picked), "fixtures written to", HERE)
 
 

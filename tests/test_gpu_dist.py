@@ -31,7 +31,7 @@ def _free_port():
 def _bench(*argv, force):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MME_DIST_BACKEND", "MME_FORCE_DIST")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--headline-only", *argv]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--headline-only", *argv]
     if force:
         cmd.append("--force-dist")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)

@@ -194,28 +194,31 @@ def test_resize_matches_live_pillow_on_synthetic_shapes():
         assert np.array_equal(opre.pil_bilinear_resize_u8(img, nh, nw), ref), (h, w)
 
 
-@pytest.mark.reference
 def test_bundled_crop_sizes_equal_int_bbox(golden_dir):
-    """every bundled crop's pixel size equals the int()-truncated bbox."""
-    from PIL import Image
-
+    """every bundled crop's pixel size equals the int()-truncated bbox.  The crops' file names and
+    (height, width) are data fixtures (bundled_crop_names.json, bundled_crop_sizes_hw.npy, both in sorted-name order),
+    read by make_golden.py off the reference's output/region_images."""
     pages = json.load(open(os.path.join(golden_dir, "region_table.json")))
-    crop_dir = "/root/reference/deprecated_package/output/region_images"
+    names = json.load(open(os.path.join(golden_dir, "bundled_crop_names.json")))
+    hw = np.load(os.path.join(golden_dir, "bundled_crop_sizes_hw.npy"))
+    size = {f: (int(w), int(h)) for f, (h, w) in zip(names, hw)}
+    assert len(size) == len(names) == len(hw) == 1862
     checked = 0
     for p in pages:
         stem = os.path.splitext(p["name"])[0]
         for i, (box, cname) in enumerate(zip(p["boxes"], p["class_names"])):
-            f = os.path.join(crop_dir, f"{stem}_region{i}_{cname}.png")
-            if not os.path.exists(f):
+            f = f"{stem}_region{i}_{cname}.png"
+            if f not in size:
                 continue
             x0, y0, x1, y1 = opre.crop_box_int(box)
-            assert Image.open(f).size == (x1 - x0, y1 - y0)
+            assert size[f] == (x1 - x0, y1 - y0)
             checked += 1
     assert checked == 1862
 
 
-def _pin_crops(files):
-    """worker: oracle.preprocess_crop vs transformers' Mllama processor (live) on a slice of the bundled crops"""
+def _pin_crops(crops):
+    """worker: oracle.preprocess_crop vs transformers' Mllama processor (live) on a slice of the crops; a crop is a PNG
+    path or (index, height, width) of seeded synthetic pixels"""
     from PIL import Image
     from threadpoolctl import threadpool_limits
     from transformers.models.mllama.image_processing_pil_mllama import MllamaImageProcessorPil
@@ -224,33 +227,40 @@ def _pin_crops(files):
     proc = MllamaImageProcessorPil(size={"height": 224, "width": 224}, max_image_tiles=1, image_mean=list(opre.CLIP_MEAN),
                                    image_std=list(opre.CLIP_STD))
     bad = []
-    for f in files:
-        im = Image.open(f)
+    for c in crops:
+        if isinstance(c, str):
+            im, label = Image.open(c), os.path.basename(c)
+        else:
+            k, h, w = c
+            im, label = Image.fromarray(np.random.default_rng([7, k]).integers(0, 256, (h, w, 3), dtype=np.uint8)), f"shape {k}: {h} x {w}"
         want = proc(images=[im], return_tensors="np")["pixel_values"][0, 0, 0]
         a = np.array(im.convert("RGB"))
         nh, nw = opre.fit_to_canvas(*a.shape[:2])
         if not (np.array_equal(opre.preprocess_crop(a), want)
                 and np.array_equal(opre.pil_bilinear_resize_u8(a, nh, nw), np.array(im.convert("RGB").resize((nw, nh), resample=Image.BILINEAR)))):
-            bad.append(os.path.basename(f))
-    return len(files), bad
+            bad.append(label)
+    return len(crops), bad
 
 
-@pytest.mark.reference
-def test_oracle_preprocessing_is_bit_exact_on_every_bundled_crop():
-    """north_star: "on the bundled newspaper_images set".  All 1862 crops under the reference's output/region_images
-    (178 MB, cannot travel) through oracle.preprocess_crop / pil_bilinear_resize_u8 against live Pillow and live
-    transformers MllamaImageProcessorPil: bit-exact f32 pixel values and bit-exact resized bytes, every crop.
-    (The GPU-side K1 check uses the 24 committed crops plus the bundled size distribution; this pins the checker.)"""
+def test_oracle_preprocessing_is_bit_exact_on_every_bundled_crop(golden_dir):
+    """north_star: "on the bundled newspaper_images set".  oracle.preprocess_crop / pil_bilinear_resize_u8 against live
+    Pillow and live transformers MllamaImageProcessorPil: bit-exact f32 pixel values and bit-exact resized bytes, on
+    every one of the 1862 bundled crop shapes (bundled_crop_sizes_hw.npy, seeded synthetic pixels: the crops themselves
+    are 178 MB) and on the committed bundled crops (tests/golden/crops) as they are.
+    (The GPU-side K1 check uses the committed crops plus the bundled size distribution; this pins the checker.)"""
     import multiprocessing as mp
 
-    crop_dir = "/root/reference/deprecated_package/output/region_images"
+    hw = np.load(os.path.join(golden_dir, "bundled_crop_sizes_hw.npy"))
+    assert len(hw) == 1862
+    crop_dir = os.path.join(golden_dir, "crops")
     files = sorted(os.path.join(crop_dir, f) for f in os.listdir(crop_dir) if f.endswith(".png"))
-    assert len(files) == 1862
+    assert len(files) == 24
+    crops = files + [(k, int(h), int(w)) for k, (h, w) in enumerate(hw)]
     workers = 6
-    parts = [files[k::workers] for k in range(workers)]
+    parts = [crops[k::workers] for k in range(workers)]
     with mp.get_context("fork").Pool(workers) as pool:
         results = pool.map(_pin_crops, parts)
-    assert sum(n for n, _ in results) == 1862
+    assert sum(n for n, _ in results) == len(crops)
     assert [b for _, bad in results for b in bad] == []
 
 
