@@ -115,7 +115,8 @@ int mme_set_ln_fusion(mme_ctx* ctx, int mode);
 /* K5 (attention of the ViT-B/16 forward, transformers modeling_vit.py:164-189).
  *   1 (default) fast form: the exponentials of a query row are taken against the maximum over its first 32 keys instead
  *     of its row maximum -- softmax is invariant to that choice, only the range differs -- which lets the scores leave
- *     the matrix pipe ready for exp2.  A row whose sum leaves [1, 2^100) raises a per-launch guard word and the
+ *     the matrix pipe ready for exp2.  A row whose sum leaves [1, 2^100), or whose unnormalised output O is not finite
+ *     (p v past f32's range while the sum is in range: a bf16 |v| >= 2^28), raises a per-launch guard word and the
  *     launch is redone by the exact kernel (the decision is taken on the device; the call stays asynchronous), so
  *     every finite input gets the exact algorithm's result;
  *   0 exact form only (row maximum first), as the reference computes it.
@@ -131,9 +132,11 @@ int mme_set_ln_fusion(mme_ctx* ctx, int mode);
  * and mode 0 is the setting for a checkpoint that trips the guard routinely.
  * The same switch governs the tile-ViT encoder's attention (mme_tile_vit_forward; attention_tiles.hip), whose fast form
  * differs: the reference point of a row starts as the maximum over its first 32 keys and is RE-CENTRED from the row sum after
- * every 128-key tile (a sum past 2^60 moves the reference by the sum's exponent: exact powers of two), so the guard fires only
- * when a score jumps ~67 log2 units (46 nats of q.k / sqrt(d)) above everything the row met before within one tile -- the sum
- * is then inf / NaN and that layer's launch is redone by the exact kernel (one guard word per layer, 40 for the full tower). */
+ * every 128-key tile (a sum past 2^60 moves the reference by the sum's exponent: exact powers of two), so the range is left
+ * only when a score jumps ~60+ log2 units above everything the row met before within one tile.  The guard is checked once per
+ * row after the last key: a final sum not below 2^100 (inf / NaN included) or an O accumulator that is not finite (a jump of
+ * ~67 with |v| > 1, less with a larger |v|: O overflows while re-centring keeps the sum in range) redoes that layer's launch
+ * by the exact kernel (one guard word per layer, 40 for the full tower: mme_attention_redone_n). */
 int mme_set_attention_mode(mme_ctx* ctx, int mode);
 /* Order in which the kernels of an encoder pass walk the rows of the activations.  1 (default) zig-zag: consecutive kernels
  * walk in opposite directions, so a consumer starts on the rows its producer wrote last -- what is still in the 256 MiB
@@ -150,6 +153,21 @@ int mme_set_forward_pruning(mme_ctx* ctx, int on);
 /* Diagnostic (synchronises the device): flags[l] != 0 when the attention launch of layer l of the LAST encoder pass
  * raised its guard and was redone by the exact kernel. */
 int mme_attention_redone(mme_ctx* ctx, int32_t flags[12]);
+/* As mme_attention_redone for the first `count` (1..64) layers of the last pass: 12 for the ViT-B/16 forward, the
+ * tower's local + global layer count (40 in the full tower) after mme_tile_vit_forward. */
+int mme_attention_redone_n(mme_ctx* ctx, int count, int32_t* flags);
+/* ONE attention launch on a caller's activation, exactly as the forward makes it under the current
+ * mme_set_attention_mode (0 exact; 1 fast, then the exact kernel with run_if = guard; 2 the re-run forced).  Synchronous.
+ *   kind 0 (K5):       qkv_dev bf16 [n*197][2304] = Q | K | V, head h at columns 64h of each part -> out_dev bf16 [n*197][768];
+ *                      only_block -1 (every query block) or 0..6 (only queries 32b..32b+31 are computed and stored, as the
+ *                      pruned last layer does); reverse 0 / 1 (the walk order of the blocks; results are bit-identical).
+ *   kind 1 (tile-ViT): qkv_dev bf16 [n*6432][3840], 16 heads of 80 -> out_dev bf16 [n*6432][1280]; ntiles_host int32[n],
+ *                      the tiles each image uses (1..4: the padding mask); only_block must be -1 and reverse 0.
+ * Q carries dh^-0.5 log2(e) already (as after mme_load_vit / mme_load_tile_vit): the scores are base-2 logits.
+ * *redone = 1 when the fast form's guard was raised and the exact kernel redid the launch (always in mode 2, never in
+ * mode 0).  The launch has a guard word of its own: what mme_attention_redone reports for the last pass is unchanged. */
+int mme_attention_apply(mme_ctx* ctx, int kind, const uint16_t* qkv_dev, int n, const int32_t* ntiles_host, int only_block,
+                        int reverse, uint16_t* out_dev, int32_t* redone, void* stream);
 
 /* ---- K0: cut the bounding boxes of one decoded page on the device ----------
  * Replaces DocLayoutDetector.get_region_image (doclayout_detector.py:165-194), which re-opens

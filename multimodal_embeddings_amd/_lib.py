@@ -78,6 +78,9 @@ EXPORTS = {
     "mme_set_ln_fusion": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_attention_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_attention_redone": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_attention_redone_n": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "mme_attention_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.POINTER(C.c_int32), C.c_void_p]),
     "mme_set_forward_pruning": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_tile_order": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -311,11 +314,40 @@ class Engine:
         bit-identical embeddings, 6 % less work; off by default (see mme.h)."""
         self._check(self.lib.mme_set_forward_pruning(self.h, int(bool(on))), "mme_set_forward_pruning")
 
-    def attention_redone(self):
-        """Layers of the LAST encoder pass whose attention launch raised the fast form's guard (list of 12 ints)."""
-        flags = (C.c_int32 * 12)()
-        self._check(self.lib.mme_attention_redone(self.h, flags), "mme_attention_redone")
+    def attention_redone(self, count: int = 12):
+        """Layers of the LAST encoder pass whose attention launch raised the fast form's guard (list of `count` ints:
+        12 for the ViT-B/16 forward, the tower's layer count after `tile_vit_forward`)."""
+        flags = (C.c_int32 * int(count))()
+        self._check(self.lib.mme_attention_redone_n(self.h, int(count), flags), "mme_attention_redone_n")
         return list(flags)
+
+    # (tokens, heads, head dim) of the attention kinds mme_attention_apply takes
+    _ATTN_KINDS = {0: (197, 12, 64), 1: (6432, 16, 80)}
+
+    def attention(self, qkv, kind: int, ntiles=None, only_block: int = -1, reverse: bool = False, out=None):
+        """ONE attention launch under the current attention mode (mme_attention_apply; synchronous).  qkv bf16 CUDA
+        [n * T, 3 * H * dh] = Q | K | V with Q pre-scaled by dh^-0.5 log2(e); kind 0 = ViT-B/16 (T 197, 12 x 64), kind 1 =
+        tile-ViT (T 6432, 16 x 80, `ntiles` = tiles per image, 1..4).  -> (out bf16 [n * T, H * dh], redone: bool)."""
+        t = self.torch
+        if kind not in self._ATTN_KINDS:
+            raise MmeError(f"attention: kind {kind} (0 = ViT-B/16, 1 = tile-ViT)")
+        T, H, dh = self._ATTN_KINDS[kind]
+        if qkv.dtype != t.bfloat16 or not qkv.is_contiguous() or qkv.dim() != 2 or qkv.shape[1] != 3 * H * dh or qkv.shape[0] % T:
+            raise MmeError(f"attention: qkv must be a contiguous bf16 [n * {T}, {3 * H * dh}] tensor")
+        n = qkv.shape[0] // T
+        if out is None:
+            out = t.empty((n * T, H * dh), dtype=t.bfloat16, device=qkv.device)
+        if out.dtype != t.bfloat16 or not out.is_contiguous() or tuple(out.shape) != (n * T, H * dh):
+            raise MmeError(f"attention: out must be a contiguous bf16 [{n * T}, {H * dh}] tensor")
+        nt = None
+        if ntiles is not None:
+            nt = np.ascontiguousarray(np.asarray(ntiles).reshape(-1), dtype=np.int32)
+            if nt.shape[0] != n:
+                raise MmeError(f"attention: {nt.shape[0]} tile counts for {n} images")
+        redone = C.c_int32(0)
+        self._check(self.lib.mme_attention_apply(self.h, int(kind), qkv.data_ptr(), n, None if nt is None else nt.ctypes.data, int(only_block),
+                                                 int(bool(reverse)), out.data_ptr(), C.byref(redone), self._stream()), "mme_attention_apply")
+        return out, bool(redone.value)
 
     def set_chunk(self, crops: int):
         self._check(self.lib.mme_set_chunk(self.h, int(crops)), "mme_set_chunk")

@@ -234,9 +234,11 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 // those start from accumulators holding -c: K.Q^T - c leaves the matrix pipe ready for exp2 -- no subtraction,
                 // no scale (Q arrives pre-multiplied by dh^-0.5 log2 e: folded into W_q at load time), no 112-entry
                 // maximum chain on the critical path.  5 vector instructions per score become 3.5.
-                // Range: the sum is >= 1 (the tile-0 maximum contributes exp2(0)); a row whose true maximum exceeds c by
-                // more than ~100 (raw scores 550 apart) would overflow -- such a row raises `guard` and the launch is redone
-                // by the exact kernel (launch_attention), so every finite input gets the exact algorithm's result.
+                // Range: the sum is >= 1 (the tile-0 maximum contributes exp2(0)).  A row raises `guard`, and the launch is
+                // redone by the exact kernel (launch_attention), when its sum is not below 2^100 (a true maximum ~100 above c:
+                // raw scores 550 apart; inf and NaN included) or when an accumulator of O is not finite (a product p v past
+                // f32's range with the sum still in range: p < 2^100 and a bf16 |v| >= 2^28).  So every finite input gets the
+                // exact algorithm's result.
                 bf16x8 kf[2][2][4];
                 auto read_k = [&](int kt, bf16x8 (&dst)[4]) {
 #pragma unroll
@@ -318,8 +320,20 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 pv_step(std::integral_constant<int, 12>{});
                 float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
                 sum += other_half(sum);
-                // !(sum < 2^100) also catches inf and NaN; one lane's word per offending row is enough
-                if (guard && !(sum < guard_limit) && q < VIT_T) *guard = 1;  // guard_limit = 2^100 (0.5 in the forced-re-run test mode)
+                // O overflow: the total of this lane's 32 accumulators is finite iff all of them are (inf / NaN never turn
+                // finite again; a total that overflows from finite terms only costs a needless re-run).  Once per item,
+                // after the key loop
+                float ot;
+                {
+                    f32x16 t = o[0] + o[1];
+#pragma unroll
+                    for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+                        for (int e = 0; e < w; ++e) t[e] += t[e + w];
+                    ot = t[0];
+                }
+                // !(sum < 2^100) also catches inf and NaN, !(ot - ot == 0) an inf / NaN total; one lane's word per offending row is enough
+                if (guard && (!(sum < guard_limit) || !(ot - ot == 0.f)) && q < VIT_T) *guard = 1;  // guard_limit = 2^100 (0.5 in the forced-re-run test mode)
                 inv = __builtin_amdgcn_rcpf(sum);
             } else if constexpr (PIPE == 1) {
                 // The kernel is bound by vector-ALU and matrix issue per SIMD, not by HBM (stamped build: a wave's

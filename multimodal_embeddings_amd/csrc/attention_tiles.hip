@@ -301,10 +301,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles(const bf16_t* __restric
 //   * NO running maximum: softmax(s) = exp2(s - c) / sum for ANY c; the maximum only buys range.  c starts as the maximum
 //     over the query's first 32 keys and is re-centred from the ROW SUM: after every 128-key tile, a query whose sum passed
 //     2^60 moves its reference by the sum's exponent (O and the sum scale by an exact power of two, the -ref block moves
-//     with it).  So ref >= (largest score so far) - 60 after every tile, and a probability overflows only if a score
-//     jumps more than ~67 log2 units (46 nats of q.k / sqrt(d)) above everything the query met before within one tile:
-//     then the sum is inf / NaN, the lane raises `guard`, and the exact kernel above -- launched right behind with
-//     run_if = guard -- redoes the launch.  Every finite input gets a correct result; ordinary inputs never re-run.
+//     with it).  So ref >= (largest score so far) - 60 after every tile, and the range can only be left when a score
+//     jumps ~60+ log2 units above everything the query met before within one tile.  Guarded, once after the key loop: a
+//     row whose final sum is not below 2^100 (inf / NaN included) OR whose O accumulators are not all finite (p |v| past
+//     f32's range while the sum stays finite: a jump of ~67 with |v| > 1, or less with a larger |v|; recentre() then
+//     brings the sum back into range but O stays inf) raises `guard`, and the exact kernel above -- launched right behind
+//     with run_if = guard -- redoes the launch.  Every finite input gets a correct result; ordinary inputs never re-run.
 //   * software pipeline per wave over 32-key sub-tiles: the five S^T MFMAs of sub-tile k+1 are issued around the
 //     exponentials of sub-tile k (two score blocks alive), then the six P.V MFMAs of sub-tile k with their transposed V
 //     reads; no stagger between the wave groups, two LDS buffers, one barrier per 128-key tile.
@@ -461,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles_fast(const bf16_t* __re
         const float l = row_sum();
         if (__ballot(l > 0x1p60f) != 0) {
             const int ex = l > 0x1p60f ? __builtin_amdgcn_frexp_expf(l) : 0;  // l = f * 2^ex, f in [0.5, 1)
-            const float down = __builtin_amdgcn_ldexpf(1.0f, -ex);           // inf / NaN sums: guard at the end
+            const float down = __builtin_amdgcn_ldexpf(1.0f, -ex);           // inf / NaN sums and O: guard at the end
 #pragma unroll
             for (int db = 0; db < 3; ++db)
 #pragma unroll
@@ -598,8 +600,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles_fast(const bf16_t* __re
     if (!wave_active) return;
 
     const float l = row_sum();
-    // !(l < limit) also catches inf and NaN; the sum is >= ~0.5 by construction (the reference key contributes 1)
-    if (guard && !(l < guard_limit) && q < TV_T) *guard = 1;  // guard_limit = 2^100 (0.25 in the forced-re-run test mode)
+    // O overflow: the total of this lane's 48 accumulators is finite iff all of them are (inf / NaN never turn finite again,
+    // recentre() included; a total that overflows from finite terms only costs a needless re-run)
+    float ot;
+    {
+        f32x16 t = o[0] + o[1] + o[2];
+#pragma unroll
+        for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+            for (int e = 0; e < w; ++e) t[e] += t[e + w];
+        ot = t[0];
+    }
+    // !(l < limit) also catches inf and NaN, !(ot - ot == 0) an inf / NaN total; the sum is >= ~0.5 by construction (the
+    // reference key contributes 1)
+    if (guard && (!(l < guard_limit) || !(ot - ot == 0.f)) && q < TV_T) *guard = 1;  // guard_limit = 2^100 (0.25 in the forced-re-run test mode)
     const float inv = __builtin_amdgcn_rcpf(l);
     if (q < TV_T) {
         bf16_t* op = out + ((size_t)img * TV_T + q) * TV_D + head * TV_DH;

@@ -240,8 +240,9 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, s));
     }
-    // one guard word per layer for the attention kernel's fast form (attention.hip): zero = no row left its range
-    if (c->attn_mode) HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, 64 * sizeof(int), s));
+    // one guard word per layer for the attention kernel's fast form (attention.hip): zero = no row left its range (zeroed
+    // in mode 0 too, so that mme_attention_redone reports this pass and not an earlier one)
+    HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, 64 * sizeof(int), s));
     // LayerNorm statistics of the residual stream x for the GEMM that folds the LayerNorm in.  Mode 2: the GEMM
     // that WROTE x (EPI_BIAS_RES_STATS) left per-slice partial sums; finishing them reads 96 bytes per row
     // instead of the 1536-byte row.  Rows of a ragged last row tile, launches that ran the 128 x 128 kernel and
@@ -550,7 +551,7 @@ void mme_destroy(mme_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (void* p : c->allocs) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard};
+    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->lut) (void)hipFree(c->lut);
@@ -666,6 +667,53 @@ int mme_attention_redone(mme_ctx* c, int32_t flags[12]) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());
     HIP_TRY(c, hipMemcpy(flags, c->attn_guard.p, VIT_L * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MME_OK;
+}
+
+int mme_attention_redone_n(mme_ctx* c, int count, int32_t* flags) {
+    if (!c || !flags) return fail(c, MME_E_ARG, "mme_attention_redone_n: null argument");
+    if (count < 1 || count > 64) return fail(c, MME_E_ARG, "mme_attention_redone_n: count %d outside 1..64", count);
+    for (int l = 0; l < count; ++l) flags[l] = 0;
+    if (!c->attn_guard.p) return MME_OK;  // no pass has run yet
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy(flags, c->attn_guard.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MME_OK;
+}
+
+int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const int32_t* ntiles_host, int only_block, int reverse,
+                        uint16_t* out, int32_t* redone, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!qkv || !out || !redone) return fail(c, MME_E_ARG, "mme_attention_apply: null argument");
+    if (kind != 0 && kind != 1) return fail(c, MME_E_ARG, "mme_attention_apply: kind %d (0 = ViT-B/16, 1 = tile-ViT)", kind);
+    const int n_max = kind == 0 ? 1 << 20 : 4096;
+    if (n <= 0 || n > n_max) return fail(c, MME_E_ARG, "mme_attention_apply: n = %d outside 1..%d", n, n_max);
+    if (kind == 0) {
+        if (only_block < -1 || only_block > 6) return fail(c, MME_E_ARG, "mme_attention_apply: only_block %d outside -1..6", only_block);
+        if (reverse != 0 && reverse != 1) return fail(c, MME_E_ARG, "mme_attention_apply: reverse must be 0 or 1");
+    } else {
+        if (only_block != -1 || reverse != 0) return fail(c, MME_E_ARG, "mme_attention_apply: kind 1 takes only_block = -1 and reverse = 0");
+        if (!ntiles_host) return fail(c, MME_E_ARG, "mme_attention_apply: kind 1 needs ntiles_host");
+        for (int i = 0; i < n; ++i)
+            if (ntiles_host[i] < 1 || ntiles_host[i] > 4) return fail(c, MME_E_ARG, "mme_attention_apply: image %d uses %d tiles (1..4)", i, ntiles_host[i]);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure(c, c->attn_apply, (16 + (size_t)n) * sizeof(int32_t)))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    int* guard = (int*)c->attn_apply.p;
+    int32_t* nt_dev = (int32_t*)c->attn_apply.p + 16;
+    HIP_TRY(c, hipMemsetAsync(guard, 0, sizeof(int), s));
+    if (kind == 0) {
+        HIP_TRY(c, launch_attention(qkv, out, n, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2, only_block, reverse != 0));
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(nt_dev, ntiles_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, launch_attention_tiles(qkv, out, nt_dev, n, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2));
+    }
+    int32_t g = 0;
+    HIP_TRY(c, hipMemcpyAsync(&g, guard, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    *redone = g != 0;
     return MME_OK;
 }
 

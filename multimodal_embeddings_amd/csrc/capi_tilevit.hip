@@ -185,7 +185,7 @@ int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* a
             int rg;
             if ((rg = ensure(c, c->attn_guard, 64 * sizeof(int)))) return rg;
         }
-        if (c->attn_mode) HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, 64 * sizeof(int), s));
+        HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, 64 * sizeof(int), s));  // mode 0 too: the flags describe THIS pass
         const int64_t npatch = (int64_t)m * TTILES * TGRID * TGRID;
         {
             Timed tm(c, s, KC_PRE);

@@ -177,12 +177,20 @@ def test_fast_attention_form_tracks_its_range_and_falls_back_to_the_exact_kernel
         eng.load_tile_vit(w, geom)
         pv, ids, mask, nt = _prep(eng, arrays)
         out = {}
+        n_layers = geom.num_layers + geom.num_global_layers
         for mode in ((0, 1, 2) if scale == 1.0 else (0, 1)):
             eng.set_attention_mode(mode)
             hidden, _, _ = eng.tile_vit_forward(pv, ids, nt, want_hidden=True)
             torch.cuda.synchronize()
             out[mode] = hidden.cpu().numpy()
             assert np.isfinite(out[mode]).all(), (scale, mode)
+            # one guard word per layer of the tower; the words past the last layer stay zero
+            flags = eng.attention_redone(n_layers + 2)
+            assert flags[n_layers:] == [0, 0], (scale, mode, flags)
+            if scale == 1.0 and mode == 1:
+                assert flags[:n_layers] == [0] * n_layers, flags  # ordinary weights: the fast form stands in every layer
+            if mode == 2:
+                assert flags[:n_layers] == [1] * n_layers, flags  # forced: every layer redone
         cos = _token_cos(out[1].reshape(-1, out[1].shape[-1]), out[0].reshape(-1, out[0].shape[-1]))
         assert cos.min() >= 1 - 1e-4, (scale, float(cos.min()))
         bitwise.append(bool(np.array_equal(out[0], out[1])))
