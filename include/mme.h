@@ -28,8 +28,8 @@ extern "C" {
 /* Bumped whenever an export changes its signature, the meaning of an argument or the size of a caller-owned array.
  * 2 (round 3): mme_profile_read_sync takes the capacity of the caller's arrays (the class count is no longer part of
  *    the ABI); mme_set_ln_fusion's argument is a MODE (0 / 1 / 2, it was on / off in version 1); mme_tile_vit_weights
- *    carries the save point of the intermediate states; the experiment switches MME_GEMM_DEBUG / MME_ATTN_DEBUG exist
- *    only in a -DMME_DIAG build; new exports mme_is_diag_build, mme_set_attention_mode, mme_attention_redone,
+ *    carries the save point of the intermediate states; the experiment switches exist only in a
+ *    -DMME_DIAG build; new exports mme_is_diag_build, mme_set_attention_mode, mme_attention_redone,
  *    mme_set_tile_order, mme_set_forward_pruning.  A binder checks `mme_abi_version() == MME_ABI_VERSION` right after dlopen. */
 #define MME_ABI_VERSION 2
 
@@ -49,8 +49,7 @@ typedef struct mme_ctx mme_ctx;
  * (deprecated_package/embedder.py:42-84): one context per visible GPU. */
 int mme_abi_version(void);
 /* 1 when the library was built with -DMME_DIAG (libmme_diag.so): only then are the experiment switches of DESIGN.md
- * 4.5 (MME_GEMM_DEBUG, MME_GEMM_GN / RB / GRID / MIN256, MME_ATTN_BUFS / PIPE / DEBUG, MME_K1_VWIN / HBAND) read from
- * the environment.  The production library ignores them. */
+ * 4.5 (MME_ATTN_DEBUG, MME_TATTN_DEBUG) read from the environment.  The production library ignores them. */
 int mme_is_diag_build(void);
 int mme_create(int device, mme_ctx** out);
 void mme_destroy(mme_ctx* ctx);
@@ -97,10 +96,10 @@ int mme_set_normalisation(mme_ctx* ctx, const float mean[3], const float std[3])
 int mme_set_chunk(mme_ctx* ctx, int crops_per_pass);
 
 /* Tuning / test knob: which MFMA GEMM tiling serves K2/K4/K6/K7/K9.  0 = by shape (default),
- * 1 = 128x128 tiles, 3 = 256x256 ping-pong kernel with a 3-deep activation ring (2 is accepted and
- * means 3), 4 / 6 / 5 = variant 3 with 4 / 6 / 8 of a lane's 16 output stores deferred into the next
- * tile's first K-tile (4 is the default for large problems).  Results are bit-identical across
- * variants (same MFMA instruction, same K order per output element). */
+ * 1 = 128x128 tiles, 3 = 256x256 ping-pong kernel with a 3-deep activation ring, 4 = variant 3 with
+ * 4 of a lane's 16 output stores deferred into the next tile's first K-tile (the default for large
+ * problems).  2 is accepted and means 3; 5 and 6 are accepted and mean 4.  Results are bit-identical
+ * across variants (same MFMA instruction, same K order per output element). */
 int mme_set_gemm_variant(mme_ctx* ctx, int variant);
 
 /* LayerNorm folding: LN1 / LN2 are folded into the QKV / fc1 GEMMs
@@ -342,7 +341,8 @@ int mme_gemm_bench(mme_ctx* ctx, int M, int N, int K, int epilogue, int variant,
 int mme_gemm_stamps(mme_ctx* ctx, int M, int N, int K, uint64_t* stamps_host);
 
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
- * its stamped build once.  stamps_host uint64[B workgroups][8 waves][8]: s_memtime cycles summed over the 12 head
+ * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,
+ * timed with its guarded exact re-run).  stamps_host uint64[B workgroups][8 waves][8]: s_memtime cycles summed over the 12 head
  * iterations of the wave -- [0] wait for its own requests, [1] workgroup barrier, [2] issue of the next head's
  * requests (K/V LDS-DMA on wave 7, Q prefetch on the others), [3] S^T = K.Q^T, [4] softmax, [5] O^T = V^T.P^T,
  * [6] hand-over + output stores; [7] heads processed.  Wave 7 (staging only) carries in [5] / [6] the s_memtime cycles and

@@ -37,6 +37,9 @@ constexpr int QKV_LD = 3 * VIT_D * 2;  // 4608-byte rows of the fused QKV activa
 constexpr int NPIECE = 25;             // 25 x 8 rows = 200 >= 197
 constexpr int ATTN_SHARE_FAST = 0 + 16 * 8 + 256 * 8;  // K/V pieces of the next head requested by the computing waves (dma_head: a + 16 b + 256 c)
 constexpr int ATTN_SHARE_EXACT = 0 + 16 * 8 + 256 * 8;
+// the computing waves request at most the 2 x 25 pieces of a head; the staging wave takes the rest (dma_head)
+constexpr bool share_fits(int share) { return 3 * ((share & 15) + ((share >> 4) & 15)) + (share >> 8) <= 2 * NPIECE; }
+static_assert(share_fits(ATTN_SHARE_FAST) && share_fits(ATTN_SHARE_EXACT), "ATTN_SHARE_*");
 // NB = LDS buffers (heads in flight + 1): two buffers of 224 rows (7 key tiles of 32).  (A three-buffer geometry of 208
 // rows, two heads in flight, measured 3 % slower in round 2 and is gone.)
 template <int NB> struct AttnGeom {
@@ -496,12 +499,8 @@ hipError_t launch_attention(const void* qkv, void* out, int B, hipStream_t s, in
         if (B * d >= 512) break;
     }
     const int nblk = B * hsplit, grid = nblk < 256 ? nblk : 256;  // persistent: one workgroup per CU walks its blocks
-    const char* pipe_env = diag_env("MME_ATTN_PIPE");  // 1: the exact kernel only (A/B)
-    const bool fast = guard != nullptr && !(pipe_env && atoi(pipe_env) == 1);
-    const char* share_env = diag_env("MME_ATTN_SHARE");  // K/V pieces requested by the computing waves (dma_head)
-    int share = share_env ? atoi(share_env) : (fast ? ATTN_SHARE_FAST : ATTN_SHARE_EXACT);
-    if (share < 0 || 3 * ((share & 15) + ((share >> 4) & 15)) + (share >> 8) > 2 * NPIECE) return hipErrorInvalidValue;
-    if (reverse) share |= 1 << 17;
+    const bool fast = guard != nullptr;
+    const int share = (fast ? ATTN_SHARE_FAST : ATTN_SHARE_EXACT) | (reverse ? 1 << 17 : 0);
     if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
     if (fast) {
         // FAST kernel, then the exact kernel on the same launch geometry, which returns at once unless a row of the fast
@@ -519,21 +518,17 @@ hipError_t launch_attention(const void* qkv, void* out, int B, hipStream_t s, in
     return hipGetLastError();
 }
 
-// diagnostic: the stamped build (two buffers, one workgroup per crop); stamps = uint64[B][8 waves][8], zeroed by the caller
-hipError_t launch_attention_stamped(const void* qkv, void* out, int B, unsigned long long* stamps, hipStream_t s) {
+// diagnostic: the stamped build of the fast or the exact form (two buffers, one workgroup per crop); stamps = uint64[B][8 waves][8],
+// zeroed by the caller
+hipError_t launch_attention_stamped(const void* qkv, void* out, int B, bool fast, unsigned long long* stamps, hipStream_t s) {
     const int dbg = diag_env("MME_ATTN_DEBUG") ? atoi(diag_env("MME_ATTN_DEBUG")) : 0;
     if (B <= 0) return hipSuccess;
-    const char* pipe_env = diag_env("MME_ATTN_PIPE");
-    const bool fast = !(pipe_env && atoi(pipe_env) == 1);
-    const char* share_env = diag_env("MME_ATTN_SHARE");
-    const int share = share_env ? atoi(share_env) : (fast ? ATTN_SHARE_FAST : ATTN_SHARE_EXACT);
-    if (share < 0 || 3 * ((share & 15) + ((share >> 4) & 15)) + (share >> 8) > 2 * NPIECE) return hipErrorInvalidValue;
     if (!fast) {
         if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, true>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, share, (const int*)nullptr);
+        hipLaunchKernelGGL((attn_fwd_t197<2, true>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_EXACT, (const int*)nullptr);
     } else {
         if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true, 2>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, true, 2>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, share, (const int*)nullptr);
+        hipLaunchKernelGGL((attn_fwd_t197<2, true, 2>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_FAST, (const int*)nullptr);
     }
     return hipGetLastError();
 }

@@ -214,8 +214,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     // Zig-zag: consecutive kernels of the pass walk the rows in OPPOSITE directions, so a consumer starts on the rows its
     // producer wrote last -- what is still in the 256 MiB Infinity Cache of a 1.2-5 GB activation -- instead of on the rows
     // written first and long evicted.  Tile order only: results are bit-identical (tests).  dir flips at every producer.
-    const char* zz_env = diag_env("MME_ZIGZAG");
-    const int zigzag = zz_env ? atoi(zz_env) : c->zigzag;  // 0 off, 1 every kernel alternates, 2 only the attention walks backwards
+    const int zigzag = c->zigzag;  // 0 off, 1 every kernel alternates, 2 only the attention walks backwards
     int dir = 0;
     auto next_dir = [&]() { if (zigzag == 1) dir ^= 1; return dir; };
     {
@@ -421,8 +420,8 @@ struct K1Plan {
     int count[3] = {0, 0, 0};
     int kv_max = 0;  // largest K1Layout::kv of the batch (LDS of the vertical pass)
 };
-// MME_K1_HBAND (KiB): tuning switch for the LDS budget of classes 0 and 1
-static const int kHLds = (diag_env("MME_K1_HBAND") && atoi(diag_env("MME_K1_HBAND")) >= 4 ? atoi(diag_env("MME_K1_HBAND")) : 32) * 1024;
+// LDS budget of classes 0 and 1
+constexpr int kHLds = 32 * 1024;
 
 void plan_crop(mme_ctx* c, K1Plan& p, int i, CropDesc& d) {
     d.tmp_off = 0;
@@ -496,9 +495,7 @@ int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const 
     if ((r = run_h_pass(c, plan, pix, n, s, "mme_preprocess"))) return r;
     Timed t(c, s, KC_PRE);
     if ((r = launch_h_pass(c, plan, pix, n, s, "mme_preprocess"))) return r;
-    NormAffine aff = c->norm_aff;
-    if (diag_env("MME_K1_TABLE")) aff.exact = 0;  // A/B (diagnostic build): the table form of the patch emitter
-    HIP_TRY(c, launch_resize_v_patchify(pix, (const uint8_t*)c->tmp.p, (const CropDesc*)c->crops.p, n, c->lut, aff, patches, any_resize,
+    HIP_TRY(c, launch_resize_v_patchify(pix, (const uint8_t*)c->tmp.p, (const CropDesc*)c->crops.p, n, c->lut, c->norm_aff, patches, any_resize,
                                         (const uint8_t*)c->htab.p, plan.kv_max, s));
     return MME_OK;
 }
@@ -641,7 +638,7 @@ int mme_set_normalisation(mme_ctx* c, const float mean[3], const float stdv[3]) 
 
 int mme_set_gemm_variant(mme_ctx* c, int variant) {
     if (!c) return MME_E_ARG;
-    if (variant < 0 || variant > 6) return fail(c, MME_E_ARG, "mme_set_gemm_variant: 0 (auto), 1 (128x128), 2 (256x256, 2-slot ring), 3 (256x256, 3-deep activation ring), 4 / 5 (3 with 4 / 8 of a lane's 16 stores deferred)");
+    if (variant < 0 || variant > 6) return fail(c, MME_E_ARG, "mme_set_gemm_variant: 0 (auto), 1 (128x128), 3 (256x256, 3-deep activation ring), 4 (3 with 4 of a lane's 16 stores deferred); 2 means 3, 5 and 6 mean 4");
     c->gemm_variant = variant;
     return MME_OK;
 }
@@ -1338,17 +1335,18 @@ int mme_attention_stamps(mme_ctx* c, int B, int iters, double* avg_ms, uint64_t*
             if (rc) break;
         }
         hipStream_t s = nullptr;
-        if (launch_attention(Q, O, B, s, (int*)G) != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: launch"); break; }
+        int* guard = c->attn_mode ? (int*)G : nullptr;  // mode 0: the exact kernel alone
+        if (launch_attention(Q, O, B, s, guard, c->attn_mode == 2) != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: launch"); break; }
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, s);
-        for (int i = 0; i < iters; ++i) (void)launch_attention(Q, O, B, s, (int*)G);
+        for (int i = 0; i < iters; ++i) (void)launch_attention(Q, O, B, s, guard, c->attn_mode == 2);
         (void)hipEventRecord(e1, s);
         if (hipEventSynchronize(e1) != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: kernel failed"); break; }
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         *avg_ms = ms / iters;
         (void)hipMemset(ST, 0, st_bytes);
-        if (launch_attention_stamped(Q, O, B, (unsigned long long*)ST, s) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: stamped launch"); break; }
+        if (launch_attention_stamped(Q, O, B, guard != nullptr, (unsigned long long*)ST, s) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: stamped launch"); break; }
         (void)hipMemcpy(stamps_host, ST, st_bytes, hipMemcpyDeviceToHost);
     } while (0);
     if (e0) (void)hipEventDestroy(e0);

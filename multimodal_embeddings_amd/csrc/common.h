@@ -11,9 +11,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-// Experiment switches -- environment variables that change the tiling or (MME_GEMM_DEBUG, MME_ATTN_DEBUG) produce wrong
-// results on purpose -- exist only in the diagnostic build (`python -m multimodal_embeddings_amd.build --diag` ->
-// libmme_diag.so, -DMME_DIAG): a stray variable in a user's environment cannot change what libmme.so computes.
+// Experiment switches -- environment variables that select ablations of the stamped kernel builds (MME_ATTN_DEBUG,
+// MME_TATTN_DEBUG) and produce wrong results on purpose -- exist only in the diagnostic build (`python -m
+// multimodal_embeddings_amd.build --diag` -> libmme_diag.so, -DMME_DIAG): a stray variable in a user's environment cannot
+// change what libmme.so computes.
 #include <stdlib.h>
 #ifdef MME_DIAG
 static inline const char* diag_env(const char* name) { return getenv(name); }

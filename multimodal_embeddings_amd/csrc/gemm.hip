@@ -15,8 +15,6 @@
 //     accumulator holds 4 consecutive n per lane -> 8-byte bf16x4 / 16-byte f32x4 stores and
 //     bias / residual vector loads.
 //   * XCD-aware bijective tile order: consecutive tiles share the A row panel in one XCD's L2.
-#include <cstdlib>
-
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
@@ -121,21 +119,22 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_128(GemmArgs g) {
 
 }  // namespace
 
-hipError_t launch_gemm256r(int epilogue, const GemmArgs& g, hipStream_t s, int defer);
+hipError_t launch_gemm256r(int epilogue, const GemmArgs& g, hipStream_t s, bool defer);
 
 // variant: 0 = choose by shape, 1 = 128x128 tiles, 3 = 256x256 ping-pong kernel with a 3-deep activation ring (all 160 KiB
-// of LDS), 4 / 6 / 5 = variant 3 with 4 / 6 / 8 of a lane's 16 stores deferred into the next tile's first K-tile (2 is
-// accepted for old callers and means 3: the 2-slot-ring kernel it named was folded into gemm256r.hip)
+// of LDS), 4 = variant 3 with 4 of a lane's 16 stores deferred into the next tile's first K-tile.  Accepted for old
+// callers: 2 means 3 (the 2-slot-ring kernel it named was folded into gemm256r.hip); 5 and 6 mean 4 (their deeper
+// deferrals, 8 and 6 stores, measured slower than 4)
 static int resolve_variant(const GemmArgs& g, int variant) {
     if (variant == 0) {
         const int64_t tiles256 = (int64_t)((g.M + 255) / 256) * ((g.N + 255) / 256);
-        // 128 tiles: measured on whole embed calls of 16..256 crops (tools/bench_small.py; MME_GEMM_MIN256 sweeps it): with the
-        // threshold at 256, calls of 64 / 96 crops ran their 150- / 225-tile GEMMs on the 128 x 128 kernel and took 11 % / 9 %
-        // longer (that kernel also leaves no LayerNorm partial sums: one more pass over x per LayerNorm)
-        static const int min256 = diag_env("MME_GEMM_MIN256") ? atoi(diag_env("MME_GEMM_MIN256")) : 128;
-        variant = tiles256 >= min256 ? 4 : 1;
+        // 128 tiles: measured on whole embed calls of 16..256 crops (tools/bench_small.py): with the threshold at 256, calls
+        // of 64 / 96 crops ran their 150- / 225-tile GEMMs on the 128 x 128 kernel and took 11 % / 9 % longer (that kernel
+        // also leaves no LayerNorm partial sums: one more pass over x per LayerNorm)
+        variant = tiles256 >= 128 ? 4 : 1;
     }
     if (variant == 2) variant = 3;
+    if (variant == 5 || variant == 6) variant = 4;
     if (g.K < 128) variant = 1;  // the 256 kernel streams two K-tiles ahead
     return variant;
 }
@@ -146,13 +145,11 @@ hipError_t launch_gemm(int epilogue, const GemmArgs& g, hipStream_t s, int varia
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     const bool automatic = variant == 0;
     variant = resolve_variant(g, variant);
-    if (variant >= 3 && variant <= 6) {
-        int defer = variant == 3 ? 0 : (variant == 4 ? 4 : (variant == 5 ? 8 : 6));
+    if (variant == 3 || variant == 4) {
         // f32 out (K9): the deferred row block LOSES there -- interleaved A/B on the [8192 x 65536] block, 20 launches per arm,
         // four rounds: 0.911 ms without, 1.00 ms with (tools/k9_ab.py; the mid-round figure that favoured it had measured the
         // undeferred arm first, cold).  The bf16 epilogues keep it (-3.4 % of the forward's GEMM time, tools/ab_step.py).
-        if (automatic && epilogue == EPI_F32) defer = 0;
-        return launch_gemm256r(epilogue, g, s, defer);
+        return launch_gemm256r(epilogue, g, s, variant == 4 && !(automatic && epilogue == EPI_F32));
     }
     if (g.K <= 0 || (g.K % BK) != 0) return hipErrorInvalidValue;
     const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);

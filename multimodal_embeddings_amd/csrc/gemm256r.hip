@@ -11,8 +11,6 @@
 // (A(t+1) was issued during tile t-1, B_lo(t+1) in its q3) and leaves the six newest pieces --
 // A(t+2) and B_lo(t+2) -- in flight: every A piece has 1.5-1.75 K-tiles to land, B_hi three
 // phases instead of one.
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -35,20 +33,20 @@ constexpr int LDS_BYTES = 3 * ASLOT + 2 * BSLOT;
 // sync + prologue issue, epilogue body, rest); 16 words per wave go to `stamps` (layout: mme.h,
 // mme_gemm_stamps).  No stamp executes in the product kernel.
 //
-// DEFER (variants 4 and 5): the output write of a 256 x 256 bf16 tile is a fixed ~8 k cycles of store ISSUE per CU
+// DEFER (variant 4): the output write of a 256 x 256 bf16 tile is a fixed ~8 k cycles of store ISSUE per CU
 // (~16 B/clk/CU) during which the matrix pipe idles.  With DEFER an interior tile stores only the upper half
 // of each wave tile at once; the packed lower half (8 x 16 B per lane, 32 VGPRs -- the K loop has that many
 // to spare) is issued one store per phase inside the first K-tiles of the workgroup's NEXT tile, behind
 // that phase's LDS-DMA request, where the other wave group's MFMAs cover it.  vmcnt counts stores, in order:
 // the counted wait of such a K-tile leaves nine operations in flight instead of six.
-// NDEF = 16-byte stores per lane that are deferred (0, 4, 6 or 8 of the 16), issued one or two per phase of the
-// next tile's first K-tile.
+// NDEF = 16-byte stores per lane that are deferred (0 or 4 of the 16), issued one per phase of the next tile's first
+// K-tile.
 template <int EPI, bool STAMP = false, int NDEF = 0>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tiles_m, int tiles_n, int gn, int dbg,
-                                                             unsigned long long* stamps = nullptr, int rb = 0) {
+__global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tiles_m, int tiles_n, int gn,
+                                                             unsigned long long* stamps = nullptr) {
     constexpr bool DEFER = NDEF > 0;
-        static_assert(NDEF == 0 || NDEF == 4 || NDEF == 6 || NDEF == 8, "NDEF");
-    static_assert(!DEFER || epi_has_fast_path<EPI>() || (EPI == EPI_F32 && NDEF == 4), "DEFER needs a 16-byte fast-path epilogue");
+    static_assert(NDEF == 0 || NDEF == 4, "NDEF");
+    static_assert(!DEFER || epi_has_fast_path<EPI>() || EPI == EPI_F32, "DEFER needs a 16-byte fast-path epilogue");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -78,23 +76,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
         TileCtx c;
         // ids are ordered (column group, row panel, column in group): an XCD's contiguous id range
         // stays inside one group of `gn` column tiles, whose weight rows then live in its L2
-        // rb > 0: the row panels are cut into blocks of rb and the column groups alternate INSIDE a block, so the second
-        // group re-reads a block of A panels (rb x 256 rows) a few hundred tiles after the first read it -- from the
-        // Infinity Cache -- instead of after the whole activation matrix has streamed through
         const int id = xcd_remap(tile, ntiles);
-        const int rbs = rb > 0 ? rb : tiles_m;
-        const int per_blk = rbs * tiles_n;
-        const int blk = id / per_blk, idb = id - blk * per_blk;
-        const int rows_blk = min(rbs, tiles_m - blk * rbs);
-        const int gsz = rows_blk * gn;
-        const int grp = idb / gsz, rem = idb - grp * gsz;
+        const int gsz = tiles_m * gn;
+        const int grp = id / gsz, rem = id - grp * gsz;
         const int gw = min(gn, tiles_n - grp * gn);
-        const int tm_f = blk * rbs + rem / gw, tn = grp * gn + (rem - (rem / gw) * gw);
+        const int tm_f = rem / gw, tn = grp * gn + (rem - (rem / gw) * gw);
         const int tm = g.reverse_m ? tiles_m - 1 - tm_f : tm_f;
         c.m0 = tm * TM;
         c.n0 = tn * TN;
-        c.Ag = (const char*)g.A + (size_t)((dbg & 3) == 2 ? 0 : c.m0) * ldb;
-        c.Wg = (const char*)g.W + (size_t)((dbg & 3) == 2 ? 0 : c.n0) * ldb;
+        c.Ag = (const char*)g.A + (size_t)c.m0 * ldb;
+        c.Wg = (const char*)g.W + (size_t)c.n0 * ldb;
         c.mrem = g.M - 1 - c.m0;  // rows past the matrix edge re-read the last row
         c.nrem = g.N - 1 - c.n0;
         return c;
@@ -151,19 +142,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
     bf16_t* pend_base = nullptr;
     const int pend_lo0 = fr * (int)g.ldo + row16_col(0, fq), pend_lo1 = fr * (int)g.ldo + row16_col(2, fq);
     auto pend_store = [&](auto idx_tag) {
-        constexpr int IDX = decltype(idx_tag)::value;  // (i - (8 - NDEF / 2)) * 2 + (jp >> 1)
-        if constexpr (DEFER && IDX < NDEF) {
+        constexpr int IDX = decltype(idx_tag)::value;  // (i - 6) * 2 + (jp >> 1)
+        if constexpr (DEFER) {
             if constexpr (EPI == EPI_F32) {  // f32 out: the four column tiles j = IDX of the last row block (i = 7)
                 float* fb = (float*)pend_base;
                 *(uint4*)(fb + (int64_t)(7 * 16 + fr) * g.ldf + IDX * 16 + fq * 4) = pend[IDX];
             } else {
-                *(uint4*)(pend_base + (int64_t)(8 - NDEF / 2 + (IDX >> 1)) * 16 * g.ldo + ((IDX & 1) ? pend_lo1 : pend_lo0)) = pend[IDX];
+                *(uint4*)(pend_base + (int64_t)(6 + (IDX >> 1)) * 16 * g.ldo + ((IDX & 1) ? pend_lo1 : pend_lo0)) = pend[IDX];
             }
         }
     };
-    // pending stores issued in phase q of the carrying K-tile: 4 -> 1,1,1,1   6 -> 2,2,1,1   8 -> 2,2,2,2
-    constexpr int PQ0 = NDEF >= 6 ? 2 : 1, PQ1 = NDEF >= 6 ? 2 : 1, PQ2 = NDEF >= 8 ? 2 : 1;
-    constexpr int PQ_BEFORE_WAIT = PQ0 + PQ1 + PQ2;
 
     while (true) {
         const int m0 = cx.m0, n0 = cx.n0, mrem = cx.mrem, nrem = cx.nrem;
@@ -220,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
             constexpr int PS = decltype(ps_tag)::value;
             // K-tiles t+1 / t+2 of the stream: past the end of this tile they are the next tile's first ones
             const bool nt1 = t + 1 >= nk, nt2 = t + 2 >= nk;
-            const bool has1 = (!nt1 || has_next) && (dbg & 3) != 1, has2 = (!nt2 || has_next) && (dbg & 3) != 1;
+            const bool has1 = !nt1 || has_next, has2 = !nt2 || has_next;
             const char* w1 = nt1 ? nx.Wg + (size_t)(t + 1 - nk) * (TK * 2) : Wg + (size_t)(t + 1) * (TK * 2);
             const char* w2 = nt2 ? nx.Wg + (size_t)(t + 2 - nk) * (TK * 2) : Wg + (size_t)(t + 2) * (TK * 2);
             const char* a2 = nt2 ? nx.Ag + (size_t)(t + 2 - nk) * (TK * 2) : Ag + (size_t)(t + 2) * (TK * 2);
@@ -230,10 +218,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
             __builtin_amdgcn_sched_barrier(0);
             READ_A(a_cur, 0)
             if (has1) stage(w1, nrem1, 128, B_RING + b_nxt + HALF);
-            if constexpr (PS >= 0) {
-                pend_store(std::integral_constant<int, 0>{});
-                if constexpr (PQ0 > 1) pend_store(std::integral_constant<int, 1>{});
-            }
+            if constexpr (PS >= 0) pend_store(std::integral_constant<int, 0>{});
             S_BARRIER();
             STAMP_IV(0)
             MFMA_QUAD(0, 0)
@@ -242,10 +227,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
             /* q1 */
             READ_B(b_cur, 2)
             if (has2) stage(a2, mrem2, 0, a_nx2);
-            if constexpr (PS >= 0) {
-                pend_store(std::integral_constant<int, PQ0>{});
-                if constexpr (PQ1 > 1) pend_store(std::integral_constant<int, PQ0 + 1>{});
-            }
+            if constexpr (PS >= 0) pend_store(std::integral_constant<int, 1>{});
             S_BARRIER();
             STAMP_IV(2)
             MFMA_QUAD(0, 2)
@@ -254,10 +236,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
             /* q2 */
             READ_A(a_cur, 4)
             if (has2) stage(a2, mrem2, 128, a_nx2 + HALF);
-            if constexpr (PS >= 0) {
-                pend_store(std::integral_constant<int, PQ0 + PQ1>{});
-                if constexpr (PQ2 > 1) pend_store(std::integral_constant<int, PQ0 + PQ1 + 1>{});
-            }
+            if constexpr (PS >= 0) pend_store(std::integral_constant<int, 2>{});
             S_BARRIER();
             STAMP_IV(4)
             MFMA_QUAD(4, 2)
@@ -267,13 +246,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
             const unsigned long long st_w0 = st_on ? __builtin_amdgcn_s_memtime() : 0;
             if (has2) {
                 stage(w2, nrem2, 0, B_RING + b_cur);
-                // leave in flight: A(t+2) and B_lo(t+2) (six pieces) -- and the deferred stores issued among them
-                if constexpr (PS >= 0 && PQ_BEFORE_WAIT == 6) {
-                    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                } else if constexpr (PS >= 0 && PQ_BEFORE_WAIT == 5) {
-                    asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-                } else if constexpr (PS >= 0) {
-                    static_assert(PS < 0 || PQ_BEFORE_WAIT == 3, "counted wait");
+                // leave in flight: A(t+2) and B_lo(t+2) (six pieces) -- and the three deferred stores issued among them
+                if constexpr (PS >= 0) {
                     asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
                 } else {
                     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -282,10 +256,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             if (st_on) st_wait += __builtin_amdgcn_s_memtime() - st_w0;
-            if constexpr (PS >= 0) {
-                pend_store(std::integral_constant<int, PQ_BEFORE_WAIT>{});
-                if constexpr (NDEF - PQ_BEFORE_WAIT > 1) pend_store(std::integral_constant<int, PQ_BEFORE_WAIT + 1>{});
-            }
+            if constexpr (PS >= 0) pend_store(std::integral_constant<int, 3>{});
             S_BARRIER();
             STAMP_IV(6)
             MFMA_QUAD(4, 0)
@@ -329,7 +300,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (DEFER && i == 7) {
-                        pend[j < (DEFER ? NDEF : 1) ? j : 0] = __builtin_bit_cast(uint4, acc[i][j]);
+                        pend[DEFER ? j : 0] = __builtin_bit_cast(uint4, acc[i][j]);
                     } else {
                         *(f32x4*)(fb + (int64_t)i * 16 * g.ldf + lo + j * 16) = acc[i][j];
                     }
@@ -410,8 +381,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
                 if (pend_base != nullptr) {
                     pend_store(std::integral_constant<int, 0>{}); pend_store(std::integral_constant<int, 1>{});
                     pend_store(std::integral_constant<int, 2>{}); pend_store(std::integral_constant<int, 3>{});
-                    pend_store(std::integral_constant<int, 4>{}); pend_store(std::integral_constant<int, 5>{});
-                    pend_store(std::integral_constant<int, 6>{}); pend_store(std::integral_constant<int, 7>{});
                 }
             }
             break;
@@ -438,32 +407,23 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
 #undef K_TILE
 }
 
-template <int EPI, int DEFER = 0>
-hipError_t launch256r(const GemmArgs& g, hipStream_t s) {
-    const int smem = LDS_BYTES;
-    if (hipError_t e = ensure_dynamic_lds((const void*)gemm_bf16_tn_256r<EPI, false, DEFER>, smem); e != hipSuccess) return e;
+// column-group width of the tile order: the group's weight rows (gn x 256 x K bf16) should stay resident in one
+// XCD's 4 MiB L2 next to the streaming A panels and output lines; never split below 3 tiles
+// (PMC, fc1 4096 crops: L2-miss fetch 15.4 GB at gn = 12 -> 6.2 GB at gn = 6, same time)
+int column_group(int K, int tiles_n) {
+    int gn = (int)((2400 * 1024) / ((size_t)TN * K * 2));
+    if (gn < 3) gn = 3;
+    return gn > tiles_n ? tiles_n : gn;
+}
+
+template <int EPI, int NDEF, bool STAMP = false>
+hipError_t launch256r(const GemmArgs& g, hipStream_t s, unsigned long long* stamps = nullptr) {
+    if (hipError_t e = ensure_dynamic_lds((const void*)gemm_bf16_tn_256r<EPI, STAMP, NDEF>, LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (g.M + TM - 1) / TM, tiles_n = (g.N + TN - 1) / TN;
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < 256 ? ntiles : 256;  // one workgroup per CU
-    static const int dbg = [] {  // timing experiments only: 1 = no K-loop loads, 2 = every tile reads tile 0 (wrong results!)
-        const int v = diag_env("MME_GEMM_DEBUG") ? atoi(diag_env("MME_GEMM_DEBUG")) : 0;
-        if (v) fprintf(stderr, "libmme: MME_GEMM_DEBUG=%d -- GEMM RESULTS ARE INVALID (timing experiment mode)\n", v);
-        return v;
-    }();
-    static const int gn_env = diag_env("MME_GEMM_GN") ? atoi(diag_env("MME_GEMM_GN")) : 0;
-    // column-group width: the group's weight rows (gn x 256 x K bf16) should stay resident in one
-    // XCD's 4 MiB L2 next to the streaming A panels and output lines; never split below 3 tiles
-    // (PMC, fc1 4096 crops: L2-miss fetch 15.4 GB at gn = 12 -> 6.2 GB at gn = 6, same time)
-    int gn = gn_env > 0 ? gn_env : (int)((2400 * 1024) / ((size_t)TN * g.K * 2));
-    if (gn < 3) gn = 3;
-    if (gn > tiles_n) gn = tiles_n;
-    // MME_GEMM_RB: row-panel block of the tile order (0 = one block: column group outermost, the default); read per launch for A/B runs
-    const char* rb_env = diag_env("MME_GEMM_RB");
-    // measured at 4096 crops: 16 -> -0.4 % GEMM time (8 / 32: +-0) but +5 % requests leaving the L2 (the weight group is
-    // re-fetched per block; FETCH_SIZE counts Infinity-Cache hits too) -- inside the noise, so the default stays 0
-    const int rb = rb_env ? atoi(rb_env) : 0;
-    hipLaunchKernelGGL((gemm_bf16_tn_256r<EPI, false, DEFER>), dim3(grid), dim3(512), smem, s, g, tiles_m, tiles_n, gn, dbg,
-                       (unsigned long long*)nullptr, rb);
+    hipLaunchKernelGGL((gemm_bf16_tn_256r<EPI, STAMP, NDEF>), dim3(grid), dim3(512), LDS_BYTES, s, g, tiles_m, tiles_n,
+                       column_group(g.K, tiles_n), stamps);
     return hipGetLastError();
 }
 
@@ -472,67 +432,23 @@ hipError_t launch256r(const GemmArgs& g, hipStream_t s) {
 // diagnostic launch of the stamped build (bias epilogue only): stamps = uint64[256 * 2 * 16], zeroed by the caller
 hipError_t launch_gemm256r_stamped(const GemmArgs& g, unsigned long long* stamps, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0 || g.K < 2 * TK || (g.K % TK) != 0) return hipErrorInvalidValue;
-    hipError_t e = ensure_dynamic_lds((const void*)gemm_bf16_tn_256r<EPI_BIAS, true>, LDS_BYTES);
-    if (e != hipSuccess) return e;
-    const int tiles_m = (g.M + TM - 1) / TM, tiles_n = (g.N + TN - 1) / TN;
-    const int ntiles = tiles_m * tiles_n;
-    int gn = (int)((2400 * 1024) / ((size_t)TN * g.K * 2));
-    gn = gn < 3 ? 3 : gn;
-    gn = gn > tiles_n ? tiles_n : gn;
-    // MME_GEMM_GRID: run the stamped build on fewer workgroups (does the epilogue's store cost depend on how
-    // many CUs store at the same time?)
-    int grid = ntiles < 256 ? ntiles : 256;
-    if (diag_env("MME_GEMM_GRID") && atoi(diag_env("MME_GEMM_GRID")) > 0 && atoi(diag_env("MME_GEMM_GRID")) < grid) grid = atoi(diag_env("MME_GEMM_GRID"));
-    hipLaunchKernelGGL((gemm_bf16_tn_256r<EPI_BIAS, true>), dim3(grid), dim3(512), LDS_BYTES, s, g, tiles_m, tiles_n, gn, 0, stamps);
-    return hipGetLastError();
+    return launch256r<EPI_BIAS, 0, true>(g, s, stamps);
 }
 
-hipError_t launch_gemm256r(int epilogue, const GemmArgs& g, hipStream_t s, int defer) {
+hipError_t launch_gemm256r(int epilogue, const GemmArgs& g, hipStream_t s, bool defer) {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     if (g.K <= 0 || (g.K % TK) != 0) return hipErrorInvalidValue;
     if (g.K < 2 * TK) return hipErrorInvalidValue;  // the cross-tile stream looks two K-tiles ahead (launch_gemm routes K = 64 to the 128 x 128 kernel)
-    if (defer == 8) {
-        switch (epilogue) {
-            case EPI_BIAS: return launch256r<EPI_BIAS, 8>(g, s);
-            case EPI_BIAS_GELU: return launch256r<EPI_BIAS_GELU, 8>(g, s);
-            case EPI_BIAS_RES: return launch256r<EPI_BIAS_RES, 8>(g, s);
-            case EPI_BIAS_RES_STATS: return launch256r<EPI_BIAS_RES_STATS, 8>(g, s);
-            case EPI_LN_BIAS: return launch256r<EPI_LN_BIAS, 8>(g, s);
-            case EPI_LN_BIAS_GELU: return launch256r<EPI_LN_BIAS_GELU, 8>(g, s);
-            default: break;  // the other epilogues have no deferred form
-        }
-    } else if (defer == 6) {
-        switch (epilogue) {
-            case EPI_BIAS: return launch256r<EPI_BIAS, 6>(g, s);
-            case EPI_BIAS_GELU: return launch256r<EPI_BIAS_GELU, 6>(g, s);
-            case EPI_BIAS_RES: return launch256r<EPI_BIAS_RES, 6>(g, s);
-            case EPI_BIAS_RES_STATS: return launch256r<EPI_BIAS_RES_STATS, 6>(g, s);
-            case EPI_LN_BIAS: return launch256r<EPI_LN_BIAS, 6>(g, s);
-            case EPI_LN_BIAS_GELU: return launch256r<EPI_LN_BIAS_GELU, 6>(g, s);
-            default: break;
-        }
-    } else if (defer == 4) {
-        if (epilogue == EPI_F32) return launch256r<EPI_F32, 4>(g, s);
-        switch (epilogue) {
-            case EPI_BIAS: return launch256r<EPI_BIAS, 4>(g, s);
-            case EPI_BIAS_GELU: return launch256r<EPI_BIAS_GELU, 4>(g, s);
-            case EPI_BIAS_RES: return launch256r<EPI_BIAS_RES, 4>(g, s);
-            case EPI_BIAS_RES_STATS: return launch256r<EPI_BIAS_RES_STATS, 4>(g, s);
-            case EPI_LN_BIAS: return launch256r<EPI_LN_BIAS, 4>(g, s);
-            case EPI_LN_BIAS_GELU: return launch256r<EPI_LN_BIAS_GELU, 4>(g, s);
-            default: break;
-        }
-    }
     switch (epilogue) {
-        case EPI_BIAS: return launch256r<EPI_BIAS>(g, s);
-        case EPI_BIAS_GELU: return launch256r<EPI_BIAS_GELU>(g, s);
-        case EPI_BIAS_RES: return launch256r<EPI_BIAS_RES>(g, s);
-        case EPI_BIAS_RES_STATS: return launch256r<EPI_BIAS_RES_STATS>(g, s);
-        case EPI_PATCH: return launch256r<EPI_PATCH>(g, s);
-        case EPI_F32: return launch256r<EPI_F32>(g, s);
-        case EPI_LN_BIAS: return launch256r<EPI_LN_BIAS>(g, s);
-        case EPI_LN_BIAS_GELU: return launch256r<EPI_LN_BIAS_GELU>(g, s);
-        case EPI_TOPK: return launch256r<EPI_TOPK>(g, s);
+        case EPI_BIAS: return defer ? launch256r<EPI_BIAS, 4>(g, s) : launch256r<EPI_BIAS, 0>(g, s);
+        case EPI_BIAS_GELU: return defer ? launch256r<EPI_BIAS_GELU, 4>(g, s) : launch256r<EPI_BIAS_GELU, 0>(g, s);
+        case EPI_BIAS_RES: return defer ? launch256r<EPI_BIAS_RES, 4>(g, s) : launch256r<EPI_BIAS_RES, 0>(g, s);
+        case EPI_BIAS_RES_STATS: return defer ? launch256r<EPI_BIAS_RES_STATS, 4>(g, s) : launch256r<EPI_BIAS_RES_STATS, 0>(g, s);
+        case EPI_LN_BIAS: return defer ? launch256r<EPI_LN_BIAS, 4>(g, s) : launch256r<EPI_LN_BIAS, 0>(g, s);
+        case EPI_LN_BIAS_GELU: return defer ? launch256r<EPI_LN_BIAS_GELU, 4>(g, s) : launch256r<EPI_LN_BIAS_GELU, 0>(g, s);
+        case EPI_F32: return defer ? launch256r<EPI_F32, 4>(g, s) : launch256r<EPI_F32, 0>(g, s);
+        case EPI_PATCH: return launch256r<EPI_PATCH, 0>(g, s);  // no deferred form
+        case EPI_TOPK: return launch256r<EPI_TOPK, 0>(g, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -83,8 +83,8 @@ hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, h
 // reverse: walk the crops from the last one down (same results; zig-zag order of consecutive kernels, forward_chunk)
 hipError_t launch_attention(const void* qkv, void* out, int B, hipStream_t s, int* guard = nullptr, bool force_redo = false, int only_block = -1,
                             bool reverse = false);
-// diagnostic: stamped build, stamps uint64[B][8][8]
-hipError_t launch_attention_stamped(const void* qkv, void* out, int B, unsigned long long* stamps, hipStream_t s);
+// diagnostic: stamped build of the fast or the exact form, stamps uint64[B][8][8]
+hipError_t launch_attention_stamped(const void* qkv, void* out, int B, bool fast, unsigned long long* stamps, hipStream_t s);
 
 struct CropDesc {  // one per crop, built on the host by capi
     int64_t src_off;   // byte offset into pix

@@ -23,7 +23,6 @@
 // The fixed-point sums are exact in 32-bit unsigned arithmetic: triangle weights are >= 0 and sum to 2^22 +- n/2, so
 // 255 * sum + 2^21 < 2^31, and v_mad_u32_u24 multiplies an 8-bit pixel by a < 2^24 coefficient exactly.
 // Contraction is disabled so no fused multiply-add changes a rounding of the f64 coefficient arithmetic.
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -309,7 +308,7 @@ __global__ __launch_bounds__(RESIZE ? 512 : 256, RESIZE ? 8 : 1) void resize_v_p
         rows_chunk = max(window_bytes / pitch, 1);
         dma_range_to_lds<NT>((const uint4*)(src + (int64_t)r0 * pitch), (char*)window, (min(r0 + rows_chunk, r1) - r0) * (pitch >> 4), tid);
     }
-    const bool affine = RESIZE && aff.exact;  // the all-224 x 224 instantiation is an HBM-bound stream: its table form measured 5 % faster (tools/k1_ab.py)
+    const bool affine = RESIZE && aff.exact;  // the all-224 x 224 instantiation is an HBM-bound stream: its table form measured 5 % faster (profiles/round3_k1_ab.txt)
     if (!affine)
         for (int i = tid; i < 768; i += NT) slut[i] = lut[i];
     if (nout > 0) {
@@ -563,14 +562,13 @@ hipError_t launch_resize_h(const uint8_t* pix, uint8_t* tmp, const CropDesc* cro
 hipError_t launch_resize_v_patchify(const uint8_t* pix, const uint8_t* tmp, const CropDesc* crops, int n, const float* lut, const NormAffine& aff,
                                     void* patches, bool any_resize, const uint8_t* tab, int kv_max, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    // the LDS window is only needed when some crop is resized or partially fills the canvas; the
+    // the LDS window (16 KiB per chunk) is only needed when some crop is resized or partially fills the canvas; the
     // all-224x224 batch keeps the small footprint (more workgroups per CU for a pure stream)
-    static const int win_kb = diag_env("MME_K1_VWIN") ? atoi(diag_env("MME_K1_VWIN")) : 16;  // tuning switch (KiB per chunk)
+    constexpr int window = 16 * 1024;
     const int kvs = kv_max < 4 ? 4 : ((kv_max + 3) & ~3);
     if (kvs > MAX_TAPS) return hipErrorInvalidValue;
     const int kk_bytes = VIT_PATCH * kvs * (int)sizeof(int);
     if (any_resize) {
-        const int window = (win_kb < 1 ? 1 : (win_kb > 96 ? 96 : win_kb)) * 1024;
         const int smem = kk_bytes + window + DMA_SLACK;
         if (hipError_t e = ensure_dynamic_lds((const void*)resize_v_patchify<true>, smem); e != hipSuccess) return e;
         hipLaunchKernelGGL(resize_v_patchify<true>, dim3(n * VIT_GRID), dim3(512), smem, s, pix, tmp, crops, lut, (bf16_t*)patches, tab, window, kvs, aff);

@@ -346,7 +346,7 @@ def test_gemm_variants_bit_identical_and_race_free(engine, golden_dir):
     pix, offs, hw = _pack(arrays)
     engine.set_gemm_variant(1)
     e1, _ = engine.embed(pix, offs, hw)
-    for variant in (2, 3, 4, 5):  # 4 / 5: a quarter / half of each tile's stores deferred into the next tile's K loop
+    for variant in (2, 3, 4, 5):  # 4: a quarter of each tile's stores deferred into the next tile's K loop; 5 means 4
         engine.set_gemm_variant(variant)
         for _ in range(3):
             e2, _ = engine.embed(pix, offs, hw)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""A/B of whole embed steps in ONE process, interleaved rounds (guide rule 24): GEMM variants x attention buffers.
+"""A/B of whole embed steps in ONE process, interleaved rounds (guide rule 24): GEMM variants x LayerNorm modes x
+attention forms x tile orders.
 
-    python tools/ab_step.py [--crops 4096] [--rounds 4]
+    python tools/ab_step.py [--crops 4096] [--rounds 4] [--arms 4:2:0,4:2:1]
 """
 import argparse
 import os
@@ -9,10 +10,6 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _diag import use_diag_library
-
-use_diag_library()  # the MME_* experiment switches below exist only in libmme_diag.so
 import numpy as np
 import torch
 
@@ -24,7 +21,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--crops", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=4)
-    ap.add_argument("--arms", default="4:2:2:1,4:2:2:2", help="gemm_variant:attention_buffers:ln_mode:attention_form (1 exact, 2 fast):gemm_rb:attention_dma_share, comma separated")
+    ap.add_argument("--arms", default="4:2:0,4:2:1", help="gemm_variant:ln_mode:attention_mode (0 exact, 1 fast):tile_order (default 0), comma separated")
     args = ap.parse_args()
     n = args.crops
     eng = Engine(0)
@@ -40,15 +37,9 @@ def main():
     for r in range(args.rounds + 1):
         for a in arms:
             eng.set_gemm_variant(a[0])
-            os.environ["MME_ATTN_BUFS"] = str(a[1])
-            eng.set_ln_fusion(a[2] if len(a) > 2 else 2)
-            os.environ["MME_ATTN_PIPE"] = str(a[3] if len(a) > 3 else 2)
-            os.environ["MME_GEMM_RB"] = str(a[4] if len(a) > 4 else 0)
-            os.environ["MME_ZIGZAG"] = str(a[6]) if len(a) > 6 else "0"
-            if len(a) > 5:
-                os.environ["MME_ATTN_SHARE"] = str(a[5])
-            else:
-                os.environ.pop("MME_ATTN_SHARE", None)
+            eng.set_ln_fusion(a[1] if len(a) > 1 else 2)
+            eng.set_attention_mode(a[2] if len(a) > 2 else 1)
+            eng.set_tile_order(a[3] if len(a) > 3 else 0)
             eng.profile(True)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -67,7 +58,7 @@ def main():
                 print(f"arm {a}: embeddings differ from arm {arms[0]} (max 1-cos {float((1.0 - (ref * e32).sum(dim=1)).max()):.3e})", flush=True)
     for a in arms:
         t = sorted(times[a])
-        print(f"gemm variant {a[0]} attn bufs {a[1]} ln mode {a[2] if len(a) > 2 else 2} attn pipe {a[3] if len(a) > 3 else 1} gemm rb {a[4] if len(a) > 4 else 0} attn share {a[5] if len(a) > 5 else 'default'} zigzag {a[6] if len(a) > 6 else 0}: ms/step min {t[0]:.2f} med {t[len(t) // 2]:.2f} | "
+        print(f"gemm variant {a[0]} ln mode {a[1] if len(a) > 1 else 2} attention mode {a[2] if len(a) > 2 else 1} tile order {a[3] if len(a) > 3 else 0}: ms/step min {t[0]:.2f} med {t[len(t) // 2]:.2f} | "
               + " ".join(f"{k} {v:.2f}" for k, v in kern[a].items()), flush=True)
 
 

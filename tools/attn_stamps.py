@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from _diag import use_diag_library
 
-use_diag_library()  # the MME_* experiment switches below exist only in libmme_diag.so
+use_diag_library()  # MME_ATTN_DEBUG exists only in libmme_diag.so
 import numpy as np
 
 from multimodal_embeddings_amd._lib import Engine
@@ -18,15 +18,11 @@ NAMES = ["wait own", "barrier", "issue next", "S^T", "softmax", "P.V", "handover
 def main():
     eng = Engine(0)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-    shares = [v for v in (sys.argv[4].split(",") if len(sys.argv) > 4 else [""])]
-    for pipe, share in [(int(v), sh) for v in (sys.argv[3].split(",") if len(sys.argv) > 3 else ["1", "2"]) for sh in shares]:
-        os.environ["MME_ATTN_PIPE"] = str(pipe)
-        if share != "":
-            os.environ["MME_ATTN_SHARE"] = share
-            print(f"=== K/V pieces requested by each computing wave: {share}")
+    for mode in [int(v) for v in (sys.argv[3].split(",") if len(sys.argv) > 3 else ["0", "1"])]:
+        eng.set_attention_mode(mode)
         for dbg in [int(v) for v in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["0"])]:
             os.environ["MME_ATTN_DEBUG"] = str(dbg)
-            print(f"--- kernel form {pipe} (1 exact row maximum, 2 fast / reference point from key tile 0); MME_ATTN_DEBUG={dbg} "
+            print(f"--- attention mode {mode} (0 exact row maximum, 1 fast / reference point from key tile 0); MME_ATTN_DEBUG={dbg} "
                   "(exact stamped build only: 1 no K re-reads, 2 no K/V requests after head 0, 4 no max, 8 no exp)")
             report(eng, B)
 

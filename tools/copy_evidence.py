@@ -23,7 +23,7 @@ def main():
             open(os.path.join(dst, f"{tag}_{tool}.txt"), "w").writelines(keep)
     for name in ("bench_c2.json", "bench_c3.json", "bench_c4_1gpu.json", "bench_c5.json", "bench_tilevit.json", "bench_c4_nccl_world1.json",
                  "bench_c5_nccl_world1.json", "bench_gloo_2ranks_1gpu.json", "bench_gloo_2ranks_1gpu_c5.json",
-                 "bench_from_host.log", "gemm_stamps.log", "attn_stamps.log", "attn_ab.log", "k1_ab.log", "tattn_ablations.log", "host_copy_probe.log"):
+                 "bench_from_host.log", "gemm_stamps.log", "attn_stamps.log", "attn_ab.log", "tattn_ablations.log", "host_copy_probe.log"):
         f = os.path.join(src, name)
         if os.path.exists(f):
             lines = [l for l in open(f, errors="replace") if "amdgpu.ids" not in l]
