@@ -87,6 +87,26 @@ typedef struct {
 
 int mme_load_vit(mme_ctx* ctx, const mme_vit_weights* w);
 
+/* The same load from a checkpoint's OWN element type, prepared on the device.  Replaces the `torch_dtype=bfloat16` read of
+ * `from_pretrained` (embedder.py:75-80) for a checkpoint on local disk: every tensor pointer of `w` (and of its layer
+ * array) points at HOST elements of `dtype` -- the struct fields keep their `const float*` type, cast the pointers.  The
+ * raw bytes are copied to a device staging buffer (freed before the call returns, not part of the context) and kernels
+ * produce every buffer mme_load_vit produces on the host -- convert, scale the query rows, round to bf16, fold the
+ * LayerNorms with their f64 column sums in the host's k order -- BIT-IDENTICAL to mme_load_vit on the same values widened
+ * to f32 (mme_weights_fingerprint compares two contexts).  A bf16 checkpoint is never inflated to f32 on the host.
+ * Same validation and error texts as mme_load_vit.  Synchronises `stream` before returning: the host tensors may be
+ * released right after. */
+enum { MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2 };
+int mme_load_vit_as(mme_ctx* ctx, const mme_vit_weights* w, int dtype, void* stream);
+
+/* Diagnostic (synchronises the device): one 64-bit word per prepared weight buffer of the context, in the order the
+ * loaders created them (the ViT buffers of mme_load_vit[_as], then the tile-ViT buffers of mme_load_tile_vit[_as], when
+ * loaded in that order).  The word is a position-dependent checksum of the buffer's bytes -- the sum over its 32-bit words
+ * of word * odd_hash(word index) mod 2^64, reduced on the device -- so two contexts hold the same prepared weights exactly
+ * when their words agree, without running a forward.  Writes at most `cap` words to out_host; returns the number of
+ * buffers (>= 0, call with cap = 0 to size the array) or MME_E_*. */
+int mme_weights_fingerprint(mme_ctx* ctx, int cap, uint64_t* out_host);
+
 /* Pixel normalisation constants of the image processor (per channel; default CLIP).
  * Replaces the `image_mean` / `image_std` of the checkpoint's preprocessor_config. */
 int mme_set_normalisation(mme_ctx* ctx, const float mean[3], const float std[3]);
@@ -403,6 +423,9 @@ typedef struct {
 } mme_tile_vit_weights;
 
 int mme_load_tile_vit(mme_ctx* ctx, const mme_tile_vit_weights* w);
+/* As mme_load_vit_as: every tensor pointer of `w` and of its layers points at host elements of `dtype` (MME_DT_*), prepared
+ * on the device bit-identically to mme_load_tile_vit.  The scalar gates stay `float` by value; tanh stays on the host. */
+int mme_load_tile_vit_as(mme_ctx* ctx, const mme_tile_vit_weights* w, int dtype, void* stream);
 
 /* pixel_values_dev f32 [n, 4, 3, 560, 560] (what mme_preprocess_tiles writes), aspect_ids_host / num_tiles_host int32[n]
  * (its other two outputs).  Any of the three outputs may be NULL:

@@ -72,6 +72,8 @@ EXPORTS = {
     "mme_destroy": (None, [C.c_void_p]),
     "mme_last_error": (C.c_char_p, [C.c_void_p]),
     "mme_load_vit": (C.c_int, [C.c_void_p, C.POINTER(_Weights)]),
+    "mme_load_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_Weights), C.c_int, C.c_void_p]),
+    "mme_weights_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "mme_set_normalisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mme_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
@@ -104,6 +106,7 @@ EXPORTS = {
     "mme_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mme_load_tile_vit": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights)]),
+    "mme_load_tile_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights), C.c_int, C.c_void_p]),
     "mme_tile_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_comm_unique_id": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mme_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -268,6 +271,93 @@ class Engine:
         W.layer = layers
         self._check(self.lib.mme_load_tile_vit(self.h, C.byref(W)), "mme_load_tile_vit")
         self.tile_features = geom.output_dim
+
+    # ---- weights from a checkpoint, in the file's own dtype, prepared on the device (mme_load_*_as) ------------
+    @staticmethod
+    def _ckpt_ptr(ckpt, name):
+        t = ckpt.tensors[name]
+        if not t.is_contiguous() or t.device.type != "cpu":
+            raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
+        return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))  # elements of ckpt.dtype behind the struct's float*
+
+    def load_vit_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "vit_b16")` -> this context: the raw f32 / bf16 / f16 bytes go to the device
+        and are converted, scaled and LayerNorm-folded there, bit-identically to `load_vit` on the same values."""
+        if ckpt.encoder != "vit_b16":
+            raise MmeError(f"load_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        arr = lambda name: self._ckpt_ptr(ckpt, name)  # noqa: E731
+        layers = (_Layer * 12)()
+        for i in range(12):
+            p = f"layers.{i}."
+            L = layers[i]
+            L.ln1_g, L.ln1_b = arr(p + "layernorm_before.weight"), arr(p + "layernorm_before.bias")
+            L.q_w, L.q_b = arr(p + "attention.q_proj.weight"), arr(p + "attention.q_proj.bias")
+            L.k_w, L.k_b = arr(p + "attention.k_proj.weight"), arr(p + "attention.k_proj.bias")
+            L.v_w, L.v_b = arr(p + "attention.v_proj.weight"), arr(p + "attention.v_proj.bias")
+            L.o_w, L.o_b = arr(p + "attention.o_proj.weight"), arr(p + "attention.o_proj.bias")
+            L.ln2_g, L.ln2_b = arr(p + "layernorm_after.weight"), arr(p + "layernorm_after.bias")
+            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
+            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+        g = ckpt.geometry
+        W = _Weights(g.image_size, g.patch_size, g.hidden_size, g.num_layers, g.num_heads, g.intermediate_size, float(g.layer_norm_eps))
+        W.cls_token = arr("embeddings.cls_token")
+        W.pos_emb = arr("embeddings.position_embeddings")
+        W.patch_w = arr("embeddings.patch_embeddings.projection.weight")
+        W.patch_b = arr("embeddings.patch_embeddings.projection.bias")
+        W.lnf_g, W.lnf_b = arr("layernorm.weight"), arr("layernorm.bias")
+        W.layer = layers
+        self._check(self.lib.mme_load_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_vit_as")
+
+    def load_tile_vit_checkpoint(self, ckpt, geometry=None):
+        """`checkpoint.read_checkpoint(dir, "mllama_tiles")` -> the tile-ViT encoder of this context, prepared on the device.
+        `geometry` overrides the checkpoint's (the save point of the intermediate states is not in the file)."""
+        if ckpt.encoder != "mllama_tiles":
+            raise MmeError(f"load_tile_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        geom = geometry or ckpt.geometry
+        arr = lambda name: self._ckpt_ptr(ckpt, name)  # noqa: E731
+        gate = lambda name: float(ckpt.tensors[name].float().reshape(-1)[0])  # noqa: E731
+        L = geom.num_layers + geom.num_global_layers
+        layers = (_TileLayer * L)()
+        for i in range(L):
+            gated = i >= geom.num_layers
+            p = f"global_transformer.layers.{i - geom.num_layers}." if gated else f"transformer.layers.{i}."
+            X = layers[i]
+            X.ln1_g, X.ln1_b = arr(p + "input_layernorm.weight"), arr(p + "input_layernorm.bias")
+            X.q_w, X.k_w, X.v_w, X.o_w = (arr(p + f"self_attn.{n}_proj.weight") for n in "qkvo")
+            X.ln2_g, X.ln2_b = arr(p + "post_attention_layernorm.weight"), arr(p + "post_attention_layernorm.bias")
+            X.fc1_w, X.fc1_b, X.fc2_w, X.fc2_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias"), arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+            X.gated = int(gated)
+            X.gate_attn = gate(p + "gate_attn") if gated else 0.0
+            X.gate_ffn = gate(p + "gate_ffn") if gated else 0.0
+        W = _TileWeights()
+        W.image_size, W.patch_size, W.hidden, W.heads, W.mlp = geom.image_size, geom.patch_size, geom.hidden_size, geom.num_heads, geom.intermediate_size
+        W.max_tiles, W.aspect_ratios, W.layers, W.global_layers = geom.max_num_tiles, geom.max_aspect_ratio_id + 1, geom.num_layers, geom.num_global_layers
+        W.n_intermediate = len(geom.intermediate_layers)
+        for k, v in enumerate(geom.intermediate_layers):
+            W.intermediate[k] = int(v)
+        W.intermediate_save_point = {"after": 0, "before": 1}[geom.intermediate_save_point]
+        W.norm_eps = float(geom.norm_eps)
+        W.pos_gate = gate("gated_positional_embedding.gate")
+        W.pre_gate = gate("pre_tile_positional_embedding.gate")
+        W.post_gate = gate("post_tile_positional_embedding.gate")
+        W.class_embedding, W.patch_w = arr("class_embedding"), arr("patch_embedding.weight")
+        W.pos_emb, W.tile_pos_emb = arr("gated_positional_embedding.embedding"), arr("gated_positional_embedding.tile_embedding.weight")
+        W.pre_emb, W.post_emb = arr("pre_tile_positional_embedding.embedding.weight"), arr("post_tile_positional_embedding.embedding.weight")
+        W.ln_pre_g, W.ln_pre_b = arr("layernorm_pre.weight"), arr("layernorm_pre.bias")
+        W.ln_post_g, W.ln_post_b = arr("layernorm_post.weight"), arr("layernorm_post.bias")
+        W.layer = layers
+        self._check(self.lib.mme_load_tile_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_tile_vit_as")
+        self.tile_features = geom.output_dim
+
+    def weights_fingerprint(self) -> tuple:
+        """One 64-bit checksum per prepared weight buffer of this context, in creation order (mme_weights_fingerprint):
+        equal tuples = the same prepared weights, without running a forward."""
+        n = self.lib.mme_weights_fingerprint(self.h, 0, None)
+        self._check(min(n, 0), "mme_weights_fingerprint")
+        out = (C.c_uint64 * max(n, 1))()
+        rc = self.lib.mme_weights_fingerprint(self.h, n, out)
+        self._check(min(rc, 0), "mme_weights_fingerprint")
+        return tuple(int(out[i]) for i in range(n))
 
     def tile_vit_forward(self, pixel_values, aspect_ratio_ids, num_tiles, want_hidden=False, want_f32=True, want_bf16=True):
         """pixel_values f32 CUDA [n, 4, 3, 560, 560] (+ ids / tile counts, as `preprocess_tiles` returns them) ->

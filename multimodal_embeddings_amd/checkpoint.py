@@ -1,0 +1,366 @@
+"""Read an encoder checkpoint from a LOCAL directory (host only; nothing here touches the network or a GPU).
+
+The reference names its encoder and lets `from_pretrained` fetch it (deprecated_package/embedder.py:73-82).  This engine
+never fetches: `read_checkpoint(path, encoder)` takes a directory that is already on disk --
+
+    config.json  [+ preprocessor_config.json]
+    model.safetensors  |  model.safetensors.index.json + shards  |  pytorch_model.bin
+
+-- checks that its configuration is the geometry the library is built for, maps the tensor names to the canonical ones
+(`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
+bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
+bytes to the device, where they are converted and folded (csrc/weight_prep.hip).
+
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|mllama_tiles]
+
+prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
+"""
+from __future__ import annotations
+
+import json
+import logging
+import os
+import re
+from dataclasses import dataclass, field
+
+from . import config
+from ._lib import MmeError
+from .weights import TILE_VIT, VIT_B16, TileViTGeometry, ViTGeometry, tile_vit_tensor_specs, vit_tensor_specs
+
+logger = logging.getLogger("multimodal_embeddings_amd")
+
+ENCODERS = ("vit_b16", "mllama_tiles")
+SUPPORTED_ASPECT_RATIOS = [[1, 1], [1, 2], [1, 3], [1, 4], [2, 1], [2, 2], [3, 1], [4, 1]]
+_DTYPE_IDS = {"float32": 0, "bfloat16": 1, "float16": 2}  # include/mme.h MME_DT_*
+_warned_resize_rule = False
+
+
+@dataclass
+class Checkpoint:
+    encoder: str
+    tensors: dict            # canonical name -> contiguous torch tensor in the file's own dtype (shape as the specs list it)
+    dtype: str               # "float32" | "bfloat16" | "float16"
+    geometry: object         # ViTGeometry | TileViTGeometry
+    image_mean: tuple | None = None
+    image_std: tuple | None = None
+    source: list = field(default_factory=list)  # files read
+
+    @property
+    def dtype_id(self) -> int:
+        return _DTYPE_IDS[self.dtype]
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors.values())
+
+
+# ---- the decision RegionEmbedder takes on `model_name` (no GPU needed) ---------------------------------------------------
+def resolve_model_source(model_name, weights=None, allow_synthetic: bool = True) -> str:
+    """-> "weights" (the caller's dict wins), "checkpoint" (`model_name` is an existing directory) or "synthetic"
+    (seeded weights; one WARNING says so, except for config.DEFAULT_MODEL_NAME, which says it itself).  With
+    `allow_synthetic=False` a name that is no directory raises."""
+    if weights is not None:
+        return "weights"
+    if isinstance(model_name, (str, os.PathLike)) and os.path.isdir(model_name):
+        return "checkpoint"
+    if not allow_synthetic:
+        raise MmeError(f"model_name={model_name!r} is not a local checkpoint directory; this engine never fetches "
+                       "(pass a directory holding config.json + model.safetensors, or weights=...)")
+    if model_name == config.DEFAULT_MODEL_NAME:
+        return "synthetic"
+    logger.warning(f"model_name={model_name!r} is not a local checkpoint directory and this engine never fetches: the encoder runs on "
+                   "SEEDED SYNTHETIC weights (pass a checkpoint directory, or allow_synthetic=False to make this an error)")
+    return "synthetic"
+
+
+# ---- names --------------------------------------------------------------------------------------------------------------
+_VIT_LEGACY = (
+    (re.compile(r"^encoder\.layer\.(\d+)\.attention\.attention\.query\.(weight|bias)$"), r"layers.\1.attention.q_proj.\2"),
+    (re.compile(r"^encoder\.layer\.(\d+)\.attention\.attention\.key\.(weight|bias)$"), r"layers.\1.attention.k_proj.\2"),
+    (re.compile(r"^encoder\.layer\.(\d+)\.attention\.attention\.value\.(weight|bias)$"), r"layers.\1.attention.v_proj.\2"),
+    (re.compile(r"^encoder\.layer\.(\d+)\.attention\.output\.dense\.(weight|bias)$"), r"layers.\1.attention.o_proj.\2"),
+    (re.compile(r"^encoder\.layer\.(\d+)\.intermediate\.dense\.(weight|bias)$"), r"layers.\1.mlp.fc1.\2"),
+    (re.compile(r"^encoder\.layer\.(\d+)\.output\.dense\.(weight|bias)$"), r"layers.\1.mlp.fc2.\2"),
+    (re.compile(r"^encoder\.layer\.(\d+)\.(layernorm_before|layernorm_after)\.(weight|bias)$"), r"layers.\1.\2.\3"),
+)
+
+
+def canonical_vit_name(key: str):
+    """Checkpoint key -> canonical name, or None for a key the encoder does not use (pooler, classifier)."""
+    if key.startswith("vit."):
+        key = key[4:]
+    if key.startswith(("pooler.", "classifier.")):
+        return None
+    for pat, rep in _VIT_LEGACY:
+        if pat.match(key):
+            return pat.sub(rep, key)
+    return key
+
+
+def canonical_tile_name(key: str):
+    """Checkpoint key -> canonical name, or None for a key outside the vision tower."""
+    for prefix in ("model.vision_model.", "vision_model."):
+        if key.startswith(prefix):
+            return key[len(prefix):]
+    if key.startswith(("model.", "language_model.", "multi_modal_projector.", "lm_head.")):
+        return None
+    return key
+
+
+# ---- configuration ------------------------------------------------------------------------------------------------------
+def _load_json(path):
+    with open(path, "r", encoding="utf-8") as f:
+        return json.load(f)
+
+
+def _expect(cfg: dict, fld: str, built, where: str, default=None):
+    found = cfg.get(fld, default)
+    same = found == built
+    if isinstance(built, float) and isinstance(found, (int, float)):
+        same = abs(float(found) - built) <= 1e-12 * max(1.0, abs(built))
+    if not same:
+        raise MmeError(f"{where}: {fld} = {found!r}, but this library is built for {fld} = {built!r}")
+
+
+def _vit_geometry(cfg: dict, where: str) -> ViTGeometry:
+    g = VIT_B16
+    for fld, built in (("image_size", g.image_size), ("patch_size", g.patch_size), ("hidden_size", g.hidden_size),
+                       ("num_hidden_layers", g.num_layers), ("num_attention_heads", g.num_heads), ("intermediate_size", g.intermediate_size),
+                       ("num_channels", g.num_channels)):
+        _expect(cfg, fld, built, where, default=built if fld == "num_channels" else None)
+    _expect(cfg, "hidden_act", "gelu", where)
+    _expect(cfg, "qkv_bias", True, where, default=True)
+    return ViTGeometry(layer_norm_eps=float(cfg.get("layer_norm_eps", g.layer_norm_eps)))
+
+
+def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
+    g = TILE_VIT
+    for fld, built in (("image_size", g.image_size), ("patch_size", g.patch_size), ("hidden_size", g.hidden_size),
+                       ("attention_heads", g.num_heads), ("intermediate_size", g.intermediate_size), ("max_num_tiles", g.max_num_tiles)):
+        _expect(cfg, fld, built, where)
+    _expect(cfg, "num_channels", g.num_channels, where, default=g.num_channels)
+    _expect(cfg, "hidden_act", "gelu", where)
+    ratios = cfg.get("supported_aspect_ratios")
+    if [list(r) for r in (ratios or [])] != SUPPORTED_ASPECT_RATIOS:
+        raise MmeError(f"{where}: supported_aspect_ratios = {ratios!r}, but this library is built for supported_aspect_ratios = {SUPPORTED_ASPECT_RATIOS!r}")
+    for fld in ("num_hidden_layers", "num_global_layers", "intermediate_layers_indices"):
+        if fld not in cfg:
+            raise MmeError(f"{where}: {fld} is missing")
+    return TileViTGeometry(num_layers=int(cfg["num_hidden_layers"]), num_global_layers=int(cfg["num_global_layers"]),
+                           intermediate_layers=tuple(int(v) for v in cfg["intermediate_layers_indices"]),
+                           norm_eps=float(cfg.get("norm_eps", g.norm_eps)))
+
+
+def _read_preprocessor(path: str, encoder: str):
+    """preprocessor_config.json -> (mean, std) or (None, None); raises for what K1 cannot honour."""
+    global _warned_resize_rule
+    pc = _load_json(path)
+    where = os.path.basename(path)
+    if pc.get("do_rescale", True) is not True:
+        raise MmeError(f"{where}: do_rescale = {pc.get('do_rescale')!r}; K1 always rescales by 1/255")
+    rf = pc.get("rescale_factor", 1.0 / 255.0)
+    if abs(float(rf) - 1.0 / 255.0) > 1e-9:
+        raise MmeError(f"{where}: rescale_factor = {rf!r}; K1 rescales by 1/255 = {1.0 / 255.0!r}")
+    if pc.get("do_normalize", True) is not True:
+        raise MmeError(f"{where}: do_normalize = {pc.get('do_normalize')!r}; K1 always normalises with image_mean / image_std")
+    resample = pc.get("resample", 2)
+    if resample != 2:
+        raise MmeError(f"{where}: resample = {resample!r}; K1 resizes with Pillow BILINEAR (resample = 2) only")
+    if encoder == "mllama_tiles":
+        size = pc.get("size", {"height": 560, "width": 560})
+        if not isinstance(size, dict) or size.get("height") != 560 or size.get("width") != 560:
+            raise MmeError(f"{where}: size = {size!r}; the tile encoder is built for size = 560 x 560")
+        tiles = pc.get("max_image_tiles", 4)
+        if tiles != 4:
+            raise MmeError(f"{where}: max_image_tiles = {tiles!r}; the tile encoder is built for max_image_tiles = 4")
+    elif "Mllama" not in str(pc.get("image_processor_type", "")) and not _warned_resize_rule:
+        _warned_resize_rule = True
+        logger.warning(f"{where}: image_processor_type = {pc.get('image_processor_type')!r} does not use Mllama's fit-and-pad resize; K1 keeps the "
+                       "aspect-preserving fit into 224 x 224 with zero padding (this encoder's contract, DESIGN.md) and applies only the "
+                       "checkpoint's image_mean / image_std")
+    mean, std = pc.get("image_mean"), pc.get("image_std")
+    if mean is None or std is None:
+        return None, None
+    if len(mean) != 3 or len(std) != 3:
+        raise MmeError(f"{where}: image_mean / image_std must have three channels, got {mean!r} / {std!r}")
+    return tuple(float(v) for v in mean), tuple(float(v) for v in std)
+
+
+# ---- tensors ------------------------------------------------------------------------------------------------------------
+def _read_tensors(path: str, canonical, wanted: set):
+    """-> ({canonical name: torch tensor}, {canonical name: key in the file}, [files read]); reads only the keys that map
+    to a wanted name."""
+    import torch
+
+    single = os.path.join(path, "model.safetensors")
+    index = os.path.join(path, "model.safetensors.index.json")
+    legacy = os.path.join(path, "pytorch_model.bin")
+    out, keys, files = {}, {}, []
+
+    def take(name, key, tensor):
+        if name in out:
+            raise MmeError(f"{path}: the keys {keys[name]!r} and {key!r} both name the tensor {name!r}")
+        out[name], keys[name] = tensor, key
+
+    if os.path.exists(single) or os.path.exists(index):
+        from safetensors import safe_open
+
+        if os.path.exists(single):
+            shards = {single: None}
+        else:
+            files.append(index)
+            shards = {}
+            for key, shard in _load_json(index)["weight_map"].items():
+                if canonical(key) in wanted:
+                    shards.setdefault(os.path.join(path, shard), []).append(key)
+        for shard, shard_keys in shards.items():
+            if not os.path.exists(shard):
+                raise MmeError(f"{shard} is named by {os.path.basename(index)} and missing")
+            files.append(shard)
+            with safe_open(shard, framework="pt", device="cpu") as f:
+                for key in (f.keys() if shard_keys is None else shard_keys):
+                    name = canonical(key)
+                    if name in wanted:
+                        take(name, key, f.get_tensor(key))
+    elif os.path.exists(legacy):
+        files.append(legacy)
+        try:
+            sd = torch.load(legacy, map_location="cpu", weights_only=True, mmap=True)
+        except (RuntimeError, ValueError):  # a file saved without the zip container cannot be mapped
+            sd = torch.load(legacy, map_location="cpu", weights_only=True)
+        if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
+            sd = sd["state_dict"]
+        for key, tensor in sd.items():
+            name = canonical(key)
+            if name in wanted and isinstance(tensor, torch.Tensor):
+                take(name, key, tensor)
+    else:
+        raise MmeError(f"{path}: no model.safetensors, model.safetensors.index.json or pytorch_model.bin")
+    return out, keys, files
+
+
+def _unify_dtype(tensors: dict, keys: dict):
+    """All tensors in ONE of f32 / bf16 / f16: the dtype that holds most elements, when every other tensor converts to it
+    exactly; else everything f32 (exact for all three)."""
+    import torch
+
+    names = {torch.float32: "float32", torch.bfloat16: "bfloat16", torch.float16: "float16"}
+    count = {}
+    for name, t in tensors.items():
+        if t.dtype not in names:
+            raise MmeError(f"tensor {keys[name]!r} has dtype {t.dtype}; supported: float32, bfloat16, float16")
+        count[t.dtype] = count.get(t.dtype, 0) + t.numel()
+    major = max(count, key=lambda d: count[d])
+    if len(count) > 1 and major != torch.float32:
+        for t in tensors.values():
+            if t.dtype != major and not torch.equal(t.to(major).to(t.dtype), t):
+                major = torch.float32
+                break
+    return {n: (t if t.dtype == major else t.to(major)).contiguous() for n, t in tensors.items()}, names[major]
+
+
+def read_checkpoint(path, encoder: str = "vit_b16") -> Checkpoint:
+    """Directory -> Checkpoint (see the module docstring).  Raises MmeError naming the file, field or key at fault."""
+    path = os.fspath(path)
+    if encoder not in ENCODERS:
+        raise ValueError(f"encoder must be one of {ENCODERS}")
+    if not os.path.isdir(path):
+        raise MmeError(f"{path!r} is not a local checkpoint directory; this engine never fetches")
+    cfg_path = os.path.join(path, "config.json")
+    if not os.path.exists(cfg_path):
+        raise MmeError(f"{cfg_path} is missing")
+    cfg = _load_json(cfg_path)
+    source = [cfg_path]
+    if encoder == "vit_b16":
+        geometry = _vit_geometry(cfg, "config.json")
+        specs = [(n, s) for n, s, _ in vit_tensor_specs(geometry)]
+        canonical = canonical_vit_name
+    else:
+        where = "config.json"
+        if "vision_config" in cfg:  # a whole Mllama model
+            cfg, where = cfg["vision_config"], "config.json: vision_config"
+        geometry = _tile_geometry(cfg, where)
+        specs = [(n, s) for n, s, _, _ in tile_vit_tensor_specs(geometry)]
+        canonical = canonical_tile_name
+    tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs})
+    source += files
+    for name, shape in specs:
+        if name not in tensors:
+            raise MmeError(f"{path}: tensor {name!r} is missing from the checkpoint")
+        if tuple(tensors[name].shape) != tuple(shape):
+            raise MmeError(f"{path}: tensor {keys[name]!r} has shape {tuple(tensors[name].shape)}, expected {tuple(shape)}")
+    tensors, dtype = _unify_dtype({n: tensors[n] for n, _ in specs}, keys)
+    mean = std = None
+    pre_path = os.path.join(path, "preprocessor_config.json")
+    if os.path.exists(pre_path):
+        mean, std = _read_preprocessor(pre_path, encoder)
+        source.append(pre_path)
+    return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source)
+
+
+def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = "float32", geometry=None, image_mean=None, image_std=None,
+                    image_processor_type: str = "MllamaImageProcessor") -> str:
+    """The inverse of `read_checkpoint` for a canonical-name dict of f32 arrays (weights.make_vit_weights /
+    make_tile_vit_weights): writes config.json + model.safetensors in `dtype` (and preprocessor_config.json when a mean /
+    std is given) into `path`.  What the tests and tools/bench_load.py load from; also how seeded weights become a
+    directory another tool can read."""
+    import numpy as np
+    import torch
+    from safetensors.torch import save_file
+
+    tdt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}[dtype]
+    os.makedirs(path, exist_ok=True)
+    if encoder == "vit_b16":
+        g = geometry or VIT_B16
+        cfg = {"architectures": ["ViTModel"], "model_type": "vit", "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels,
+               "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
+               "intermediate_size": g.intermediate_size, "hidden_act": "gelu", "qkv_bias": True, "layer_norm_eps": g.layer_norm_eps, "dtype": dtype}
+    elif encoder == "mllama_tiles":
+        g = geometry or TILE_VIT
+        cfg = {"architectures": ["MllamaVisionModel"], "model_type": "mllama_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,
+               "num_channels": g.num_channels, "hidden_size": g.hidden_size, "attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
+               "hidden_act": "gelu", "max_num_tiles": g.max_num_tiles, "supported_aspect_ratios": SUPPORTED_ASPECT_RATIOS,
+               "num_hidden_layers": g.num_layers, "num_global_layers": g.num_global_layers,
+               "intermediate_layers_indices": list(g.intermediate_layers), "norm_eps": g.norm_eps, "dtype": dtype}
+    else:
+        raise ValueError(f"encoder must be one of {ENCODERS}")
+    with open(os.path.join(path, "config.json"), "w", encoding="utf-8") as f:
+        json.dump(cfg, f, indent=1)
+    save_file({k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(tdt).contiguous() for k, v in weights.items()},
+              os.path.join(path, "model.safetensors"), metadata={"format": "pt"})
+    if image_mean is not None:
+        pc = {"image_processor_type": image_processor_type, "do_rescale": True, "rescale_factor": 1.0 / 255.0, "do_normalize": True, "resample": 2,
+              "image_mean": [float(v) for v in image_mean], "image_std": [float(v) for v in image_std]}
+        if encoder == "mllama_tiles":
+            pc.update({"size": {"height": 560, "width": 560}, "max_image_tiles": 4})
+        with open(os.path.join(path, "preprocessor_config.json"), "w", encoding="utf-8") as f:
+            json.dump(pc, f, indent=1)
+    return os.fspath(path)
+
+
+def main(argv=None) -> int:
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="python -m multimodal_embeddings_amd.checkpoint", description="what a load of this checkpoint directory would find")
+    ap.add_argument("directory")
+    ap.add_argument("--encoder", choices=ENCODERS, default="vit_b16")
+    a = ap.parse_args(argv)
+    try:
+        ck = read_checkpoint(a.directory, a.encoder)
+    except MmeError as e:
+        print(f"cannot load: {e}")
+        return 1
+    print(f"encoder     {ck.encoder}")
+    print(f"dtype       {ck.dtype}")
+    print(f"geometry    {ck.geometry}")
+    print(f"image_mean  {ck.image_mean}")
+    print(f"image_std   {ck.image_std}")
+    print(f"tensors     {len(ck.tensors)}")
+    print(f"bytes       {ck.nbytes}")
+    for f in ck.source:
+        print(f"read        {f}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -62,6 +62,7 @@ int upload_f32(mme_ctx* c, const float* src, size_t n, float** dst) {
     hipError_t e = hipMalloc(&p, n * sizeof(float));
     if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
     c->allocs.push_back(p);
+    c->alloc_bytes.push_back(n * sizeof(float));
     HIP_TRY(c, hipMemcpy(p, src, n * sizeof(float), hipMemcpyHostToDevice));
     *dst = (float*)p;
     return MME_OK;
@@ -79,6 +80,7 @@ int upload_bf16(mme_ctx* c, const float* const* srcs, const size_t* rows, int ns
     hipError_t e = hipMalloc(&p, total * 2);
     if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
     c->allocs.push_back(p);
+    c->alloc_bytes.push_back(total * 2);
     HIP_TRY(c, hipMemcpy(p, h.data(), total * 2, hipMemcpyHostToDevice));
     *dst = (bf16_t*)p;
     return MME_OK;
@@ -114,6 +116,7 @@ int upload_folded(mme_ctx* c, const float* const* ws, const float* const* bs, co
     hipError_t e = hipMalloc(&p, hw.size() * 2);
     if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
     c->allocs.push_back(p);
+    c->alloc_bytes.push_back(hw.size() * 2);
     HIP_TRY(c, hipMemcpy(p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
     *wf = (bf16_t*)p;
     int r;
@@ -125,6 +128,18 @@ int upload_f32_cat(mme_ctx* c, const float* const* srcs, const size_t* n, int ns
     std::vector<float> h;
     for (int i = 0; i < nsrc; ++i) h.insert(h.end(), srcs[i], srcs[i] + n[i]);
     return upload_f32(c, h.data(), h.size(), dst);
+}
+
+int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who) {
+    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
+    if (w->image_size != VIT_IMG || w->patch_size != VIT_PATCH || w->hidden != VIT_D || w->layers != VIT_L ||
+        w->heads != VIT_H || w->mlp != VIT_F)
+        return fail(c, MME_E_ARG, "%s: only ViT-B/16 @224 geometry (224/16/768/12/12/3072) is built; got %d/%d/%d/%d/%d/%d", who,
+                    w->image_size, w->patch_size, w->hidden, w->layers, w->heads, w->mlp);
+    if (!w->cls_token || !w->pos_emb || !w->patch_w || !w->patch_b || !w->lnf_g || !w->lnf_b || !w->layer)
+        return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
+    if (c->loaded) return fail(c, MME_E_STATE, "%s: weights already loaded; create a new context", who);
+    return MME_OK;
 }
 
 int ensure_workspace(mme_ctx* c) {
@@ -563,17 +578,10 @@ void mme_destroy(mme_ctx* c) {
 const char* mme_last_error(const mme_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 
 int mme_load_vit(mme_ctx* c, const mme_vit_weights* w) {
-    if (!c || !w) return fail(c, MME_E_ARG, "mme_load_vit: null argument");
-    if (w->image_size != VIT_IMG || w->patch_size != VIT_PATCH || w->hidden != VIT_D || w->layers != VIT_L ||
-        w->heads != VIT_H || w->mlp != VIT_F)
-        return fail(c, MME_E_ARG, "mme_load_vit: only ViT-B/16 @224 geometry (224/16/768/12/12/3072) is built; got %d/%d/%d/%d/%d/%d",
-                    w->image_size, w->patch_size, w->hidden, w->layers, w->heads, w->mlp);
-    if (!w->cls_token || !w->pos_emb || !w->patch_w || !w->patch_b || !w->lnf_g || !w->lnf_b || !w->layer)
-        return fail(c, MME_E_ARG, "mme_load_vit: null tensor pointer");
-    if (c->loaded) return fail(c, MME_E_STATE, "mme_load_vit: weights already loaded; create a new context");
+    int r;
+    if ((r = validate_vit_weights(c, w, "mme_load_vit"))) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     c->ln_eps = w->ln_eps;
-    int r;
     if ((r = upload_f32(c, w->cls_token, VIT_D, &c->cls))) return r;
     if ((r = upload_f32(c, w->pos_emb, (size_t)VIT_T * VIT_D, &c->pos))) return r;
     if ((r = upload_f32(c, w->patch_b, VIT_D, &c->patch_b))) return r;

@@ -54,11 +54,7 @@ int upload_scaled_f32(mme_ctx* c, const float* src, size_t n, float scale, float
     return upload_f32(c, h.data(), n, dst);
 }
 
-}  // namespace
-
-extern "C" {
-
-int mme_load_tile_vit(mme_ctx* c, const mme_tile_vit_weights* w) {
+int validate_tile_weights(mme_ctx* c, const mme_tile_vit_weights* w) {
     if (!c || !w) return fail(c, MME_E_ARG, "mme_load_tile_vit: null argument");
     if (w->image_size != 560 || w->patch_size != 14 || w->hidden != TD || w->heads != TH || w->mlp != TF || w->max_tiles != TTILES ||
         w->aspect_ratios != TARATIOS)
@@ -76,6 +72,11 @@ int mme_load_tile_vit(mme_ctx* c, const mme_tile_vit_weights* w) {
         !w->ln_post_g || !w->ln_post_b || !w->layer)
         return fail(c, MME_E_ARG, "mme_load_tile_vit: null tensor pointer");
     if (c->tv) return fail(c, MME_E_STATE, "mme_load_tile_vit: tile-ViT weights already loaded; create a new context");
+    return MME_OK;
+}
+
+// the context's tower record with the layer counts of `w` (the prepared buffers follow)
+int new_tile_dev(mme_ctx* c, const mme_tile_vit_weights* w) {
     HIP_TRY(c, hipSetDevice(c->device));
     TileVitDev* t = new (std::nothrow) TileVitDev();
     if (!t) return fail(c, MME_E_NOMEM, "mme_load_tile_vit: out of host memory");
@@ -86,7 +87,18 @@ int mme_load_tile_vit(mme_ctx* c, const mme_tile_vit_weights* w) {
     for (int k = 0; k < t->ni; ++k) t->inter_after[k] = w->intermediate[k];
     t->save_before = w->intermediate_save_point;
     t->eps = w->norm_eps;
+    return MME_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mme_load_tile_vit(mme_ctx* c, const mme_tile_vit_weights* w) {
     int r;
+    if ((r = validate_tile_weights(c, w))) return r;
+    if ((r = new_tile_dev(c, w))) return r;
+    TileVitDev* t = c->tv;
     // gates are applied here, once: the kernels add plain tables
     const float g_pos = std::tanh(w->pos_gate), g_pre = std::tanh(w->pre_gate), g_post = std::tanh(w->post_gate);
     if ((r = upload_f32(c, w->class_embedding, TD, &t->cls))) return r;
@@ -139,6 +151,121 @@ int mme_load_tile_vit(mme_ctx* c, const mme_tile_vit_weights* w) {
         if ((r = upload_scaled_f32(c, a.fc2_b, TD, gf, &Ld.fc2_b))) return r;
     }
     return MME_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+struct TileStaged {
+    const void *cls, *patch_w, *pos, *tilepos, *pre, *post, *lnpre_g, *lnpre_b, *lnpost_g, *lnpost_b;
+    struct Layer {
+        const void *ln1_g, *ln1_b, *q_w, *k_w, *v_w, *o_w, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+    };
+    std::vector<Layer> layer;
+};
+
+// one walk over the checkpoint's tensors (WeightStage: sizes the staging buffer when dry, copies afterwards)
+void stage_tile(WeightStage& st, const mme_tile_vit_weights* w, TileStaged& d) {
+    const size_t D = TD, F = TF;
+    d.cls = st.put(w->class_embedding, D);
+    d.patch_w = st.put(w->patch_w, D * TPDIM);
+    d.pos = st.put(w->pos_emb, (size_t)TTOK * D);
+    d.tilepos = st.put(w->tile_pos_emb, (size_t)TARATIOS * TTILES * TTOK * D);
+    d.pre = st.put(w->pre_emb, (size_t)TARATIOS * TTILES * D);
+    d.post = st.put(w->post_emb, (size_t)TARATIOS * TTILES * D);
+    d.lnpre_g = st.put(w->ln_pre_g, D); d.lnpre_b = st.put(w->ln_pre_b, D);
+    d.lnpost_g = st.put(w->ln_post_g, D); d.lnpost_b = st.put(w->ln_post_b, D);
+    const int L = w->layers + w->global_layers;
+    d.layer.resize(L);
+    for (int l = 0; l < L; ++l) {
+        const mme_tile_layer& a = w->layer[l];
+        TileStaged::Layer& X = d.layer[l];
+        X.ln1_g = st.put(a.ln1_g, D); X.ln1_b = st.put(a.ln1_b, D);
+        X.q_w = st.put(a.q_w, D * D); X.k_w = st.put(a.k_w, D * D); X.v_w = st.put(a.v_w, D * D); X.o_w = st.put(a.o_w, D * D);
+        X.ln2_g = st.put(a.ln2_g, D); X.ln2_b = st.put(a.ln2_b, D);
+        X.fc1_w = st.put(a.fc1_w, F * D); X.fc1_b = st.put(a.fc1_b, F);
+        X.fc2_w = st.put(a.fc2_w, D * F); X.fc2_b = st.put(a.fc2_b, D);
+    }
+}
+
+// mme_load_tile_vit's sequence of uploads, buffer for buffer, by the kernels of weight_prep.hip
+int prepare_tile(mme_ctx* c, int dt, const mme_tile_vit_weights* w, const TileStaged& d, hipStream_t s) {
+    TileVitDev* t = c->tv;
+    int r;
+    const size_t D = TD, F = TF;
+    const float g_pos = std::tanh(w->pos_gate), g_pre = std::tanh(w->pre_gate), g_post = std::tanh(w->post_gate);
+    if ((r = prep_table(c, dt, d.cls, D, 1.f, false, &t->cls, s))) return r;
+    if ((r = prep_table(c, dt, d.pos, (size_t)TTOK * D, 1.0f - g_pos, true, &t->pos, s))) return r;
+    if ((r = prep_table(c, dt, d.tilepos, (size_t)TARATIOS * TTILES * TTOK * D, g_pos, true, &t->tilepos, s))) return r;
+    if ((r = prep_table(c, dt, d.pre, (size_t)TARATIOS * TTILES * D, g_pre, true, &t->pre, s))) return r;
+    if ((r = prep_table(c, dt, d.post, (size_t)TARATIOS * TTILES * D, g_post, true, &t->post, s))) return r;
+    if ((r = prep_table(c, dt, d.lnpre_g, D, 1.f, false, &t->lnpre_g, s))) return r;
+    if ((r = prep_table(c, dt, d.lnpre_b, D, 1.f, false, &t->lnpre_b, s))) return r;
+    if ((r = prep_table(c, dt, d.lnpost_g, D, 1.f, false, &t->lnpost_g, s))) return r;
+    if ((r = prep_table(c, dt, d.lnpost_b, D, 1.f, false, &t->lnpost_b, s))) return r;
+    {
+        void* p;
+        if ((r = alloc_weight(c, F * sizeof(float), &p))) return r;
+        HIP_TRY(c, hipMemsetAsync(p, 0, F * sizeof(float), s));
+        t->zeros = (float*)p;
+        if ((r = alloc_weight(c, D * TPDIMP * 2, &p))) return r;
+        HIP_TRY(c, launch_wp_pad(dt, d.patch_w, TD, TPDIM, TPDIMP, p, s));
+        t->patch_w = (bf16_t*)p;
+    }
+    const int L = w->layers + w->global_layers;
+    t->layer.resize(L);
+    const size_t rD[3] = {D, D, D}, rF[1] = {F};
+    const float qsc = 0.11180339887498949f * 1.44269504088896341f;  // mme_load_tile_vit: 80^-0.5 log2(e)
+    for (int l = 0; l < L; ++l) {
+        const mme_tile_layer& a = w->layer[l];
+        const TileStaged::Layer& X = d.layer[l];
+        TileLayerDev& Ld = t->layer[l];
+        const float ga = a.gated ? std::tanh(a.gate_attn) : 1.0f, gf = a.gated ? std::tanh(a.gate_ffn) : 1.0f;
+        const WpFoldSrc fq[3] = {{X.q_w, nullptr, qsc, 1}, {X.k_w, nullptr, 1.f, 0}, {X.v_w, nullptr, 1.f, 0}};
+        if ((r = prep_folded(c, dt, fq, rD, 3, D, X.ln1_g, X.ln1_b, &Ld.qkv_wf, &Ld.qkv_cs, &Ld.qkv_bf, s))) return r;
+        if ((r = prep_bf16(c, dt, &X.o_w, rD, 1, D, &Ld.o_w, ga, ga != 1.0f, s))) return r;
+        const WpFoldSrc f1[1] = {{X.fc1_w, X.fc1_b, 1.f, 0}};
+        if ((r = prep_folded(c, dt, f1, rF, 1, D, X.ln2_g, X.ln2_b, &Ld.fc1_wf, &Ld.fc1_cs, &Ld.fc1_bf, s))) return r;
+        if ((r = prep_bf16(c, dt, &X.fc2_w, rD, 1, F, &Ld.fc2_w, gf, gf != 1.0f, s))) return r;
+        if ((r = prep_table(c, dt, X.fc2_b, D, gf, true, &Ld.fc2_b, s))) return r;
+    }
+    return MME_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mme_load_tile_vit_as(mme_ctx* c, const mme_tile_vit_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_tile_weights(c, w))) return r;
+    if (dtype < MME_DT_F32 || dtype > MME_DT_F16)
+        return fail(c, MME_E_ARG, "mme_load_tile_vit_as: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", dtype);
+    for (int l = 0; l < w->layers + w->global_layers; ++l) {
+        const mme_tile_layer& a = w->layer[l];
+        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.k_w, a.v_w, a.o_w, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+        for (const float* p : all)
+            if (!p) return fail(c, MME_E_ARG, "mme_load_tile_vit: layer %d has a null tensor pointer", l);
+    }
+    if ((r = new_tile_dev(c, w))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    WeightStage st(dtype, s);
+    TileStaged d;
+    stage_tile(st, w, d);
+    if ((r = st.reserve(c))) return r;
+    stage_tile(st, w, d);
+    if (st.err != hipSuccess) {
+        r = fail(c, MME_E_HIP, "mme_load_tile_vit_as: copying the checkpoint's bytes to the device: %s", hipGetErrorString(st.err));
+    } else {
+        r = prepare_tile(c, dtype, w, d, s);
+    }
+    if (r == MME_OK) {
+        hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) r = fail(c, MME_E_HIP, "mme_load_tile_vit_as: weight preparation: %s", hipGetErrorString(e));
+    }
+    st.release();
+    return r;
 }
 
 int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* aspect_ids_host, const int32_t* num_tiles_host, int n,

@@ -45,6 +45,7 @@ struct mme_ctx {
     int neigh_mode = 0;  // K12: 0 by size, 1 cosine block through the workspace, 2 fused candidate lists
     // weights
     std::vector<void*> allocs;
+    std::vector<size_t> alloc_bytes;  // size of allocs[i] (mme_weights_fingerprint)
     float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
     bf16_t* patch_w = nullptr;
     LayerDev layer[VIT_L];
@@ -86,6 +87,36 @@ int upload_bf16(mme_ctx* c, const float* const* srcs, const size_t* rows, int ns
 int upload_folded(mme_ctx* c, const float* const* ws, const float* const* bs, const size_t* rows, int nsrc, size_t cols, const float* gamma,
                   const float* beta, bf16_t** wf, float** cs, float** bf);
 void tile_vit_free(mme_ctx* c);
+// argument checks shared by mme_load_vit and mme_load_vit_as (`who` names the f32 loader in the messages of both)
+int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who);
+
+// ---- device-side weight preparation (weight_prep.hip): the upload_* helpers above, from staged device bytes of `dt` ----
+// hipMalloc registered in c->allocs / c->alloc_bytes
+int alloc_weight(mme_ctx* c, size_t bytes, void** out);
+// The checkpoint's bytes on the device for the duration of one load.  Two walks over the tensors with the same calls:
+// the first (dry) sizes the buffer, reserve() allocates it, the second copies and returns the device addresses
+// (16-byte aligned).  release() waits for the stream and frees: nothing of it stays in the context.
+struct WeightStage {
+    char* base = nullptr;
+    size_t total = 0, used = 0, esz;
+    bool dry = true;
+    hipStream_t s;
+    hipError_t err = hipSuccess;
+    WeightStage(int dt, hipStream_t s_) : esz(dt == MME_DT_F32 ? 4 : 2), s(s_) {}
+    int reserve(mme_ctx* c);
+    const void* put(const void* host, size_t n);
+    void release();
+};
+// dt -> f32 table, `scaled`: every value times `scale` first (upload_f32 / upload_scaled_f32)
+int prep_table(mme_ctx* c, int dt, const void* src, size_t n, float scale, bool scaled, float** dst, hipStream_t s);
+// upload_f32_cat; the first part times `scale0` when `scaled0`
+int prep_table_cat(mme_ctx* c, int dt, const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst, hipStream_t s);
+// upload_bf16; the first part times `scale0` when `scaled0`
+int prep_bf16(mme_ctx* c, int dt, const void* const* srcs, const size_t* rows, int nsrc, size_t cols, bf16_t** dst, float scale0, bool scaled0,
+              hipStream_t s);
+// upload_folded
+int prep_folded(mme_ctx* c, int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf,
+                float** cs, float** bf, hipStream_t s);
 
 struct Timed {
     mme_ctx* c;

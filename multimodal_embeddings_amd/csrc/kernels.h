@@ -214,3 +214,21 @@ hipError_t launch_tile_ln_post(void* x, const float* g, const float* b, const fl
 hipError_t launch_tile_output(const void* x, const void* inter, int ni, int64_t inter_stride, float* hidden, int64_t out_rows, hipStream_t s);
 hipError_t launch_tile_pool(const void* x, const void* inter, int ni, int64_t inter_stride, int n, float* emb_f32, void* emb_bf16, hipStream_t s);
 hipError_t launch_attention_tiles(const void* qkv, void* out, const int32_t* ntiles_dev, int n, hipStream_t s, int* guard = nullptr, bool force_redo = false);
+
+// ---- device-side weight preparation (weight_prep.hip).  dt = MME_DT_* (include/mme.h); sources are device addresses,
+// 16-byte aligned, of elements of that type.
+// `count` elements (a multiple of 8) -> f32 table or bf16 (round to nearest even) at dst (16-byte aligned);
+// `scaled`: every value times `scale` (in f32) first
+hipError_t launch_wp_convert(int dt, const void* src, size_t count, float scale, bool scaled, bool out_bf16, void* dst, hipStream_t s);
+// [rows, cols] -> bf16 [rows, cols_padded] with zero columns behind (cols, cols_padded multiples of 4)
+hipError_t launch_wp_pad(int dt, const void* src, int rows, int cols, int cols_padded, void* dst_bf16, hipStream_t s);
+struct WpFoldSrc {
+    const void* w;  // [rows, cols]
+    const void* b;  // [rows] or null: no bias
+    float scale;
+    int scaled;     // weights and bias times `scale`, rounded to f32, before anything else (the query rows)
+};
+// LayerNorm folding of up to three row blocks (rows[i] multiples of 64; cols a multiple of 64, <= 1280):
+// wf bf16 [sum rows, cols], cs / bf f32 [sum rows]; sums over k ascending in f64, a row per thread
+hipError_t launch_wp_fold(int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, int cols, const void* gamma, const void* beta, void* wf, float* cs,
+                          float* bf, hipStream_t s);

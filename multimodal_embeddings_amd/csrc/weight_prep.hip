@@ -1,0 +1,581 @@
+// Device-side weight preparation: what the host loops of capi.hip (upload_bf16, upload_folded, upload_f32_cat) and
+// capi_tilevit.hip (upload_scaled_f32, the patch-weight padding) compute, restated as kernels over a staged copy of the
+// checkpoint's own bytes (f32, bf16 or f16).  Every kernel keeps the operations of its host loop and their order, so the
+// prepared buffers are bit-identical to the host path's (tests/test_gpu_checkpoint.py compares their fingerprints):
+//   convert  dtype -> f32 (exact), optional f32 scale, -> f32 table or -> bf16 (round to nearest even, NaN kept quiet);
+//            the parts of a concatenated buffer (Q | K | V) are one launch each into their slice of it
+//   pad      [rows, cols] -> bf16 [rows, cols_padded], zero columns behind
+//   fold     LayerNorm folding: W' = bf16(w * gamma), colsum = sum_k W', bias' = b + sum_k w * beta; the two sums run over k
+//            ASCENDING in one f64 accumulator per output row (a row per thread; a tree reduction would change the order)
+//   fingerprint  position-dependent 64-bit checksum of a buffer's bytes (integer adds: the reduction order is free)
+// No fast-math and no flushing of f32 subnormals in this file: the results must match IEEE host arithmetic.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "ctx.h"
+
+namespace {
+
+constexpr int WP_THREADS = 256;
+constexpr int WP_MAX_BLOCKS = 2048;
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+// f32_to_bf16_rne of capi.hip, bit for bit
+__device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN stays NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+
+// eight consecutive elements of `dt` from a 16-byte aligned address -> f32 (exact for all three types)
+template <int DT>
+__device__ __forceinline__ void load8(const void* base, size_t elem, float v[8]) {
+    if (DT == MME_DT_F32) {
+        const f32x4* p = (const f32x4*)((const float*)base + elem);
+        const f32x4 a = p[0], b = p[1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = a[j];
+            v[4 + j] = b[j];
+        }
+    } else {
+        const u32x4 r = *(const u32x4*)((const uint16_t*)base + elem);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t lo = r[j] & 0xffffu, hi = r[j] >> 16;
+            if (DT == MME_DT_BF16) {
+                v[2 * j] = __uint_as_float(lo << 16);
+                v[2 * j + 1] = __uint_as_float(hi << 16);
+            } else {
+                const uint16_t l16 = (uint16_t)lo, h16 = (uint16_t)hi;
+                _Float16 hl, hh;
+                __builtin_memcpy(&hl, &l16, 2);
+                __builtin_memcpy(&hh, &h16, 2);
+                v[2 * j] = (float)hl;
+                v[2 * j + 1] = (float)hh;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ u32x4 pack8_bf16(const float v[8]) {
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = bf16_rne_bits(v[2 * j]) | (bf16_rne_bits(v[2 * j + 1]) << 16);
+    return o;
+}
+
+struct ConvertArgs {
+    const void* src;
+    unsigned long long chunks;  // of 8 elements
+    float scale;
+    int scaled;    // multiply by `scale` (the host loops skip the multiplication where the factor is 1)
+    int out_bf16;  // else an f32 table
+    void* dst;
+};
+
+template <int DT>
+__global__ __launch_bounds__(WP_THREADS) void convert_kernel(ConvertArgs a) {
+    for (unsigned long long c = (unsigned long long)blockIdx.x * WP_THREADS + threadIdx.x; c < a.chunks; c += (unsigned long long)gridDim.x * WP_THREADS) {
+        float v[8];
+        load8<DT>(a.src, (size_t)c * 8, v);
+        if (a.scaled) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = v[j] * a.scale;
+        }
+        if (a.out_bf16) {
+            ((u32x4*)a.dst)[c] = pack8_bf16(v);
+        } else {
+            f32x4 lo, hi;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                lo[j] = v[j];
+                hi[j] = v[4 + j];
+            }
+            ((f32x4*)a.dst)[2 * c] = lo;
+            ((f32x4*)a.dst)[2 * c + 1] = hi;
+        }
+    }
+}
+
+// [rows, cols] -> bf16 [rows, colsp]; four elements per thread (cols % 4 == 0, colsp % 4 == 0: a row of 588 16-bit
+// elements starts 8-byte aligned only)
+template <int DT>
+__global__ __launch_bounds__(WP_THREADS) void pad_kernel(const void* src, int rows, int cols, int colsp, uint16_t* dst) {
+    const int q = colsp / 4;
+    const long long total = (long long)rows * q;
+    for (long long i = (long long)blockIdx.x * WP_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * WP_THREADS) {
+        const int r = (int)(i / q), k = (int)(i % q) * 4;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (k < cols) {
+            const size_t e = (size_t)r * cols + k;
+            if (DT == MME_DT_F32) {
+                const f32x4 a = *(const f32x4*)((const float*)src + e);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = a[j];
+            } else {
+                const uint2 w = *(const uint2*)((const uint16_t*)src + e);
+                const uint32_t h[4] = {w.x & 0xffffu, w.x >> 16, w.y & 0xffffu, w.y >> 16};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (DT == MME_DT_BF16) {
+                        v[j] = __uint_as_float(h[j] << 16);
+                    } else {
+                        const uint16_t b = (uint16_t)h[j];
+                        _Float16 x;
+                        __builtin_memcpy(&x, &b, 2);
+                        v[j] = (float)x;
+                    }
+                }
+            }
+        }
+        uint2 o;
+        o.x = bf16_rne_bits(v[0]) | (bf16_rne_bits(v[1]) << 16);
+        o.y = bf16_rne_bits(v[2]) | (bf16_rne_bits(v[3]) << 16);
+        *(uint2*)(dst + (size_t)r * colsp + k) = o;
+    }
+}
+
+// ---- fold --------------------------------------------------------------------------------------------------------------
+// One wave per 64 output rows, a row per thread.  The [64 rows x 64 k] tile comes through LDS: coalesced 16-byte global
+// loads (a row's 64 k are 128 / 256 contiguous bytes), converted and scaled on the way in, then every thread walks ITS row
+// k ascending with 16-byte LDS reads (rows padded by one access width).  The rounded W' goes back through LDS the same way
+// so that the global stores are 16 bytes wide as well.
+constexpr int FOLD_ROWS = 64, FOLD_KT = 64, FOLD_MAXK = 1280;
+constexpr int FOLD_WLD = FOLD_KT + 4;  // f32 row pitch: 272 bytes
+constexpr int FOLD_QLD = FOLD_KT + 8;  // bf16 row pitch: 144 bytes
+
+struct FoldArgs {
+    WpFoldSrc src[3];
+    int rows_end[3];  // running total of rows
+    int nsrc, cols;
+    const void *gamma, *beta;
+    uint16_t* wf;
+    float *cs, *bf;
+};
+
+template <int DT>
+__global__ __launch_bounds__(FOLD_ROWS) void fold_kernel(FoldArgs a) {
+    __shared__ __attribute__((aligned(16))) float w_s[FOLD_ROWS * FOLD_WLD];
+    __shared__ __attribute__((aligned(16))) uint16_t q_s[FOLD_ROWS * FOLD_QLD];
+    __shared__ __attribute__((aligned(16))) float g_s[FOLD_MAXK];
+    __shared__ __attribute__((aligned(16))) float b_s[FOLD_MAXK];
+    const int tid = threadIdx.x, row0 = blockIdx.x * FOLD_ROWS, K = a.cols;
+    int i = 0, first = 0;
+    if (a.nsrc > 1 && row0 >= a.rows_end[0]) { i = 1; first = a.rows_end[0]; }
+    if (a.nsrc > 2 && row0 >= a.rows_end[1]) { i = 2; first = a.rows_end[1]; }
+    const WpFoldSrc S = a.src[i];
+    const int lrow0 = row0 - first;  // the block's first row inside its source (sources hold whole blocks of rows)
+    for (int c = tid; c < K / 8; c += FOLD_ROWS) {
+        float v[8];
+        load8<DT>(a.gamma, (size_t)c * 8, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g_s[c * 8 + j] = v[j];
+        load8<DT>(a.beta, (size_t)c * 8, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b_s[c * 8 + j] = v[j];
+    }
+    double s = 0.0, t = 0.0;
+    for (int k0 = 0; k0 < K; k0 += FOLD_KT) {
+        __syncthreads();  // the previous tile has been read (and g_s / b_s are there)
+#pragma unroll
+        for (int it = 0; it < FOLD_ROWS * FOLD_KT / 8 / FOLD_ROWS; ++it) {
+            const int c = it * FOLD_ROWS + tid, r = c >> 3, k8 = (c & 7) * 8;
+            float v[8];
+            load8<DT>(S.w, (size_t)(lrow0 + r) * K + k0 + k8, v);
+            if (S.scaled) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = v[j] * S.scale;  // rounded to f32 HERE, before gamma (as the host's qw_s)
+            }
+            f32x4 lo, hi;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                lo[j] = v[j];
+                hi[j] = v[4 + j];
+            }
+            *(f32x4*)&w_s[r * FOLD_WLD + k8] = lo;
+            *(f32x4*)&w_s[r * FOLD_WLD + k8 + 4] = hi;
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int k8 = 0; k8 < FOLD_KT; k8 += 8) {
+            const f32x4 lo = *(const f32x4*)&w_s[tid * FOLD_WLD + k8], hi = *(const f32x4*)&w_s[tid * FOLD_WLD + k8 + 4];
+            float q[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float w = j < 4 ? lo[j] : hi[j - 4];
+                const uint32_t qb = bf16_rne_bits(w * g_s[k0 + k8 + j]);
+                q[j] = __uint_as_float(qb << 16);
+                s += (double)q[j];
+                t += (double)w * (double)b_s[k0 + k8 + j];
+            }
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (__float_as_uint(q[2 * j]) >> 16) | (__float_as_uint(q[2 * j + 1]) & 0xffff0000u);
+            *(u32x4*)&q_s[tid * FOLD_QLD + k8] = o;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < FOLD_ROWS * FOLD_KT / 8 / FOLD_ROWS; ++it) {
+            const int c = it * FOLD_ROWS + tid, r = c >> 3, k8 = (c & 7) * 8;
+            *(u32x4*)(a.wf + (size_t)(row0 + r) * K + k0 + k8) = *(const u32x4*)&q_s[r * FOLD_QLD + k8];
+        }
+    }
+    double b = 0.0;
+    if (S.b) {
+        float bv;
+        const size_t e = (size_t)lrow0 + tid;
+        if (DT == MME_DT_F32) {
+            bv = ((const float*)S.b)[e];
+        } else if (DT == MME_DT_BF16) {
+            bv = __uint_as_float((uint32_t)((const uint16_t*)S.b)[e] << 16);
+        } else {
+            bv = (float)((const _Float16*)S.b)[e];
+        }
+        if (S.scaled) bv = bv * S.scale;
+        b = (double)bv;
+    }
+    a.cs[row0 + tid] = (float)s;
+    a.bf[row0 + tid] = (float)(b + t);
+}
+
+// ---- fingerprint ---------------------------------------------------------------------------------------------------------
+struct FpBuf {
+    const void* p;
+    unsigned long long bytes;
+};
+
+__device__ __forceinline__ unsigned long long odd_hash(unsigned long long x) {  // splitmix64 finaliser, forced odd
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return (x ^ (x >> 31)) | 1ull;
+}
+
+constexpr int FP_BLOCKS = 64;
+
+// grid (FP_BLOCKS, buffers): out[b] += sum over the buffer's 32-bit words of word * odd_hash(word index), mod 2^64
+__global__ __launch_bounds__(WP_THREADS) void fingerprint_kernel(const FpBuf* bufs, unsigned long long* out) {
+    __shared__ unsigned long long part[WP_THREADS / 64];
+    const FpBuf B = bufs[blockIdx.y];
+    const unsigned long long words = B.bytes / 4, vecs = words / 4;
+    unsigned long long acc = 0;
+    for (unsigned long long v = (unsigned long long)blockIdx.x * WP_THREADS + threadIdx.x; v < vecs; v += (unsigned long long)FP_BLOCKS * WP_THREADS) {
+        const u32x4 w = ((const u32x4*)B.p)[v];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc += (unsigned long long)w[j] * odd_hash(4 * v + j);
+    }
+    if (blockIdx.x == 0) {
+        const unsigned long long wi = vecs * 4 + threadIdx.x;  // at most three whole words behind the last 16 bytes
+        if (threadIdx.x < 4 && wi < words) acc += (unsigned long long)((const uint32_t*)B.p)[wi] * odd_hash(wi);
+        if (threadIdx.x == 4 && (B.bytes & 3)) {  // and at most three bytes behind the last word
+            uint32_t w = 0;
+            for (unsigned k = 0; k < (B.bytes & 3); ++k) w |= (uint32_t)((const uint8_t*)B.p)[words * 4 + k] << (8 * k);
+            acc += (unsigned long long)w * odd_hash(words);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0;
+        for (int k = 0; k < WP_THREADS / 64; ++k) sum += part[k];
+        if (sum) atomicAdd(out + blockIdx.y, sum);
+    }
+}
+
+int grid_for(unsigned long long items) {
+    unsigned long long b = (items + WP_THREADS - 1) / WP_THREADS;
+    return (int)(b < 1 ? 1 : (b > WP_MAX_BLOCKS ? WP_MAX_BLOCKS : b));
+}
+
+}  // namespace
+
+hipError_t launch_wp_convert(int dt, const void* src, size_t count, float scale, bool scaled, bool out_bf16, void* dst, hipStream_t s) {
+    if (dt < MME_DT_F32 || dt > MME_DT_F16 || count % 8 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+    if (!count) return hipSuccess;
+    ConvertArgs a{};
+    a.src = src;
+    a.chunks = count / 8;
+    a.scale = scale;
+    a.scaled = scaled;
+    a.out_bf16 = out_bf16;
+    a.dst = dst;
+    const int grid = grid_for(a.chunks);
+    if (dt == MME_DT_F32) convert_kernel<MME_DT_F32><<<grid, WP_THREADS, 0, s>>>(a);
+    else if (dt == MME_DT_BF16) convert_kernel<MME_DT_BF16><<<grid, WP_THREADS, 0, s>>>(a);
+    else convert_kernel<MME_DT_F16><<<grid, WP_THREADS, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_wp_pad(int dt, const void* src, int rows, int cols, int cols_padded, void* dst_bf16, hipStream_t s) {
+    if (dt < MME_DT_F32 || dt > MME_DT_F16 || rows < 1 || cols < 4 || cols % 4 || cols_padded % 4 || cols_padded < cols || ((uintptr_t)src & 15))
+        return hipErrorInvalidValue;
+    const int grid = grid_for((unsigned long long)rows * (cols_padded / 4));
+    if (dt == MME_DT_F32) pad_kernel<MME_DT_F32><<<grid, WP_THREADS, 0, s>>>(src, rows, cols, cols_padded, (uint16_t*)dst_bf16);
+    else if (dt == MME_DT_BF16) pad_kernel<MME_DT_BF16><<<grid, WP_THREADS, 0, s>>>(src, rows, cols, cols_padded, (uint16_t*)dst_bf16);
+    else pad_kernel<MME_DT_F16><<<grid, WP_THREADS, 0, s>>>(src, rows, cols, cols_padded, (uint16_t*)dst_bf16);
+    return hipGetLastError();
+}
+
+hipError_t launch_wp_fold(int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, int cols, const void* gamma, const void* beta, void* wf, float* cs,
+                          float* bf, hipStream_t s) {
+    if (nsrc < 1 || nsrc > 3 || dt < MME_DT_F32 || dt > MME_DT_F16 || cols < FOLD_KT || cols % FOLD_KT || cols > FOLD_MAXK) return hipErrorInvalidValue;
+    if (((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15)) return hipErrorInvalidValue;
+    FoldArgs a{};
+    int total = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        if (rows[i] == 0 || rows[i] % FOLD_ROWS || ((uintptr_t)srcs[i].w & 15)) return hipErrorInvalidValue;
+        a.src[i] = srcs[i];
+        total += (int)rows[i];
+        a.rows_end[i] = total;
+    }
+    a.nsrc = nsrc;
+    a.cols = cols;
+    a.gamma = gamma;
+    a.beta = beta;
+    a.wf = (uint16_t*)wf;
+    a.cs = cs;
+    a.bf = bf;
+    const int grid = total / FOLD_ROWS;
+    if (dt == MME_DT_F32) fold_kernel<MME_DT_F32><<<grid, FOLD_ROWS, 0, s>>>(a);
+    else if (dt == MME_DT_BF16) fold_kernel<MME_DT_BF16><<<grid, FOLD_ROWS, 0, s>>>(a);
+    else fold_kernel<MME_DT_F16><<<grid, FOLD_ROWS, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// ---- the upload helpers of capi.hip, from staged device bytes ----------------------------------------------------------------
+int alloc_weight(mme_ctx* c, size_t bytes, void** out) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
+    c->allocs.push_back(p);
+    c->alloc_bytes.push_back(bytes);
+    *out = p;
+    return MME_OK;
+}
+
+int WeightStage::reserve(mme_ctx* c) {
+    hipError_t e = hipMalloc((void**)&base, used ? used : 16);
+    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc(%zu) for the staged checkpoint bytes: %s", used, hipGetErrorString(e));
+    total = used;
+    used = 0;
+    dry = false;
+    return MME_OK;
+}
+
+const void* WeightStage::put(const void* host, size_t n) {
+    const size_t bytes = n * esz, off = used;
+    used += (bytes + 15) & ~(size_t)15;
+    if (dry || err != hipSuccess) return nullptr;
+    if (used > total) {
+        err = hipErrorInvalidValue;
+        return nullptr;
+    }
+    err = hipMemcpyAsync(base + off, host, bytes, hipMemcpyHostToDevice, s);
+    return base + off;
+}
+
+void WeightStage::release() {
+    if (base) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(base);
+    }
+    base = nullptr;
+}
+
+int prep_table(mme_ctx* c, int dt, const void* src, size_t n, float scale, bool scaled, float** dst, hipStream_t s) {
+    void* p;
+    int r;
+    if ((r = alloc_weight(c, n * sizeof(float), &p))) return r;
+    HIP_TRY(c, launch_wp_convert(dt, src, n, scale, scaled, false, p, s));
+    *dst = (float*)p;
+    return MME_OK;
+}
+
+int prep_table_cat(mme_ctx* c, int dt, const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst, hipStream_t s) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += n[i];
+    void* p;
+    int r;
+    if ((r = alloc_weight(c, total * sizeof(float), &p))) return r;
+    size_t o = 0;
+    for (int i = 0; i < nsrc; ++i) {  // only the first part may carry a factor (the query bias): one launch per part
+        HIP_TRY(c, launch_wp_convert(dt, srcs[i], n[i], scale0, scaled0 && i == 0, false, (float*)p + o, s));
+        o += n[i];
+    }
+    *dst = (float*)p;
+    return MME_OK;
+}
+
+int prep_bf16(mme_ctx* c, int dt, const void* const* srcs, const size_t* rows, int nsrc, size_t cols, bf16_t** dst, float scale0, bool scaled0,
+              hipStream_t s) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += rows[i] * cols;
+    void* p;
+    int r;
+    if ((r = alloc_weight(c, total * 2, &p))) return r;
+    size_t o = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        const size_t n = rows[i] * cols;
+        HIP_TRY(c, launch_wp_convert(dt, srcs[i], n, scale0, scaled0 && i == 0, true, (uint16_t*)p + o, s));
+        o += n;
+    }
+    *dst = (bf16_t*)p;
+    return MME_OK;
+}
+
+int prep_folded(mme_ctx* c, int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf,
+                float** cs, float** bf, hipStream_t s) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += rows[i];
+    void *pw, *pc, *pb;
+    int r;
+    if ((r = alloc_weight(c, total * cols * 2, &pw))) return r;
+    if ((r = alloc_weight(c, total * sizeof(float), &pc))) return r;
+    if ((r = alloc_weight(c, total * sizeof(float), &pb))) return r;
+    HIP_TRY(c, launch_wp_fold(dt, srcs, rows, nsrc, (int)cols, gamma, beta, pw, (float*)pc, (float*)pb, s));
+    *wf = (bf16_t*)pw;
+    *cs = (float*)pc;
+    *bf = (float*)pb;
+    return MME_OK;
+}
+
+namespace {
+
+struct VitStaged {
+    const void *cls, *pos, *patch_w, *patch_b, *lnf_g, *lnf_b;
+    struct Layer {
+        const void *ln1_g, *ln1_b, *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *o_w, *o_b, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+    } layer[VIT_L];
+};
+
+// one walk over the checkpoint's tensors: sizes the staging buffer when `st` is dry, copies into it afterwards
+void stage_vit(WeightStage& st, const mme_vit_weights* w, VitStaged& d) {
+    const size_t D = VIT_D, F = VIT_F;
+    d.cls = st.put(w->cls_token, D);
+    d.pos = st.put(w->pos_emb, (size_t)VIT_T * D);
+    d.patch_w = st.put(w->patch_w, D * D);
+    d.patch_b = st.put(w->patch_b, D);
+    d.lnf_g = st.put(w->lnf_g, D);
+    d.lnf_b = st.put(w->lnf_b, D);
+    for (int l = 0; l < VIT_L; ++l) {
+        const mme_vit_layer& a = w->layer[l];
+        VitStaged::Layer& L = d.layer[l];
+        L.ln1_g = st.put(a.ln1_g, D); L.ln1_b = st.put(a.ln1_b, D);
+        L.q_w = st.put(a.q_w, D * D); L.q_b = st.put(a.q_b, D);
+        L.k_w = st.put(a.k_w, D * D); L.k_b = st.put(a.k_b, D);
+        L.v_w = st.put(a.v_w, D * D); L.v_b = st.put(a.v_b, D);
+        L.o_w = st.put(a.o_w, D * D); L.o_b = st.put(a.o_b, D);
+        L.ln2_g = st.put(a.ln2_g, D); L.ln2_b = st.put(a.ln2_b, D);
+        L.fc1_w = st.put(a.fc1_w, F * D); L.fc1_b = st.put(a.fc1_b, F);
+        L.fc2_w = st.put(a.fc2_w, D * F); L.fc2_b = st.put(a.fc2_b, D);
+    }
+}
+
+// mme_load_vit's sequence of uploads, buffer for buffer (mme_weights_fingerprint reports them in this order)
+int prepare_vit(mme_ctx* c, int dt, const VitStaged& d, hipStream_t s) {
+    int r;
+    const size_t D = VIT_D, F = VIT_F;
+    if ((r = prep_table(c, dt, d.cls, D, 1.f, false, &c->cls, s))) return r;
+    if ((r = prep_table(c, dt, d.pos, (size_t)VIT_T * D, 1.f, false, &c->pos, s))) return r;
+    if ((r = prep_table(c, dt, d.patch_b, D, 1.f, false, &c->patch_b, s))) return r;
+    if ((r = prep_table(c, dt, d.lnf_g, D, 1.f, false, &c->lnf_g, s))) return r;
+    if ((r = prep_table(c, dt, d.lnf_b, D, 1.f, false, &c->lnf_b, s))) return r;
+    const size_t rD[3] = {D, D, D}, rF[1] = {F};
+    if ((r = prep_bf16(c, dt, &d.patch_w, rD, 1, D, &c->patch_w, 1.f, false, s))) return r;
+    const float sc = 0.125f * 1.44269504088896341f;  // mme_load_vit: dh^-0.5 log2(e), folded into the query projection
+    for (int l = 0; l < VIT_L; ++l) {
+        const VitStaged::Layer& a = d.layer[l];
+        LayerDev& L = c->layer[l];
+        if ((r = prep_table(c, dt, a.ln1_g, D, 1.f, false, &L.ln1_g, s))) return r;
+        if ((r = prep_table(c, dt, a.ln1_b, D, 1.f, false, &L.ln1_b, s))) return r;
+        if ((r = prep_table(c, dt, a.ln2_g, D, 1.f, false, &L.ln2_g, s))) return r;
+        if ((r = prep_table(c, dt, a.ln2_b, D, 1.f, false, &L.ln2_b, s))) return r;
+        const void* qkv[3] = {a.q_w, a.k_w, a.v_w};
+        if ((r = prep_bf16(c, dt, qkv, rD, 3, D, &L.qkv_w, sc, true, s))) return r;
+        const void* qkvb[3] = {a.q_b, a.k_b, a.v_b};
+        if ((r = prep_table_cat(c, dt, qkvb, rD, 3, sc, true, &L.qkv_b, s))) return r;
+        const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
+        if ((r = prep_folded(c, dt, fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf, s))) return r;
+        if ((r = prep_bf16(c, dt, &a.o_w, rD, 1, D, &L.o_w, 1.f, false, s))) return r;
+        if ((r = prep_table(c, dt, a.o_b, D, 1.f, false, &L.o_b, s))) return r;
+        if ((r = prep_bf16(c, dt, &a.fc1_w, rF, 1, D, &L.fc1_w, 1.f, false, s))) return r;
+        if ((r = prep_table(c, dt, a.fc1_b, F, 1.f, false, &L.fc1_b, s))) return r;
+        const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
+        if ((r = prep_folded(c, dt, f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf, s))) return r;
+        if ((r = prep_bf16(c, dt, &a.fc2_w, rD, 1, F, &L.fc2_w, 1.f, false, s))) return r;
+        if ((r = prep_table(c, dt, a.fc2_b, D, 1.f, false, &L.fc2_b, s))) return r;
+    }
+    return MME_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mme_load_vit_as(mme_ctx* c, const mme_vit_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_vit_weights(c, w, "mme_load_vit"))) return r;
+    if (dtype < MME_DT_F32 || dtype > MME_DT_F16)
+        return fail(c, MME_E_ARG, "mme_load_vit_as: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", dtype);
+    for (int l = 0; l < VIT_L; ++l) {
+        const mme_vit_layer& a = w->layer[l];
+        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+        for (const float* p : all)
+            if (!p) return fail(c, MME_E_ARG, "mme_load_vit: layer %d has a null tensor pointer", l);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->ln_eps = w->ln_eps;
+    hipStream_t s = (hipStream_t)stream;
+    WeightStage st(dtype, s);
+    VitStaged d{};
+    stage_vit(st, w, d);
+    if ((r = st.reserve(c))) return r;
+    stage_vit(st, w, d);
+    if (st.err != hipSuccess) {
+        r = fail(c, MME_E_HIP, "mme_load_vit_as: copying the checkpoint's bytes to the device: %s", hipGetErrorString(st.err));
+    } else {
+        r = prepare_vit(c, dtype, d, s);
+    }
+    if (r == MME_OK) {
+        hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) r = fail(c, MME_E_HIP, "mme_load_vit_as: weight preparation: %s", hipGetErrorString(e));
+    }
+    st.release();
+    if (r == MME_OK) c->loaded = true;
+    return r;
+}
+
+int mme_weights_fingerprint(mme_ctx* c, int cap, uint64_t* out) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return fail(c, MME_E_ARG, "mme_weights_fingerprint: null argument or negative capacity");
+    const int n = (int)c->allocs.size();
+    if (n == 0 || cap == 0) return n;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize());
+    std::vector<FpBuf> h(n);
+    for (int i = 0; i < n; ++i) h[i] = FpBuf{c->allocs[i], (unsigned long long)c->alloc_bytes[i]};
+    void* ws = nullptr;
+    const size_t tab = (size_t)n * sizeof(FpBuf), res = (size_t)n * sizeof(unsigned long long);
+    hipError_t e = hipMalloc(&ws, tab + res);
+    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "mme_weights_fingerprint: hipMalloc: %s", hipGetErrorString(e));
+    std::vector<unsigned long long> sums(n);
+    e = hipMemcpy(ws, h.data(), tab, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset((char*)ws + tab, 0, res);
+    if (e == hipSuccess) {
+        fingerprint_kernel<<<dim3(FP_BLOCKS, n), WP_THREADS>>>((const FpBuf*)ws, (unsigned long long*)((char*)ws + tab));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(sums.data(), (char*)ws + tab, res, hipMemcpyDeviceToHost);
+    (void)hipFree(ws);
+    if (e != hipSuccess) return fail(c, MME_E_HIP, "mme_weights_fingerprint: %s", hipGetErrorString(e));
+    for (int i = 0; i < n && i < cap; ++i) out[i] = sums[i];
+    return n;
+}
+
+}  // extern "C"

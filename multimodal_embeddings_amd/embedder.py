@@ -112,11 +112,24 @@ class RegionEmbedder:
 
     def __init__(self, model_name=config.DEFAULT_MODEL_NAME, device=None, gpu_count=None, *, weights=None,
                  seed: int = 1, pool: str = "cls", chunk: int | None = None, engine: Engine | None = None, devices=None,
-                 encoder: str = "vit_b16", geometry=None, prune_last_layer: bool | None = None):
+                 encoder: str = "vit_b16", geometry=None, prune_last_layer: bool | None = None, allow_synthetic: bool = True):
+        """`model_name`: a LOCAL checkpoint directory (config.json + model.safetensors | shards | pytorch_model.bin, optionally
+        preprocessor_config.json) is read once (checkpoint.read_checkpoint), loaded into every context in the file's own dtype
+        and its image_mean / image_std applied; `self.checkpoint` keeps it.  Any other name is never fetched: the encoder runs
+        on seeded synthetic weights with one WARNING, or raises with `allow_synthetic=False`.  `weights=` (a dict) wins."""
         import torch
+
+        from .checkpoint import read_checkpoint, resolve_model_source
 
         self.torch = torch
         self.model_name = model_name
+        self.checkpoint = None
+        if encoder not in ("vit_b16", "mllama_tiles"):
+            raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+        # a caller's engine carries its own weights
+        source = "weights" if engine is not None else resolve_model_source(model_name, weights, allow_synthetic)
+        if source == "checkpoint":
+            self.checkpoint = read_checkpoint(model_name, encoder)
         if engine is not None:
             dev_list = [engine.device]
         elif devices is not None:  # explicit device indices (may repeat: several contexts on one GPU)
@@ -141,11 +154,22 @@ class RegionEmbedder:
         self.gpu_count = len(dev_list)
         self.devices = [f"cuda:{d}" for d in dev_list]
         self.device = torch.device(self.devices[0])
-        if encoder not in ("vit_b16", "mllama_tiles"):
-            raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
         self.encoder = encoder
         if engine is not None:
             self.engines = [engine]
+        elif self.checkpoint is not None:
+            ck = self.checkpoint
+            self.engines = []
+            for d in dev_list:  # read once, loaded into every context
+                e = Engine(d)
+                if encoder == "mllama_tiles":
+                    geom = ck.geometry if geometry is None else geometry
+                    e.load_tile_vit_checkpoint(ck, geom)
+                else:
+                    e.load_vit_checkpoint(ck)
+                if ck.image_mean is not None:
+                    e.set_normalisation(ck.image_mean, ck.image_std)
+                self.engines.append(e)
         else:
             if encoder == "mllama_tiles":
                 from .weights import make_tile_vit_weights
