@@ -360,6 +360,79 @@ int mme_gemm_bench(mme_ctx* ctx, int M, int N, int K, int epilogue, int variant,
  * [13] / [14] x 100 MHz is the clock the chip held (the call runs ~0.5 s of the product kernel first). */
 int mme_gemm_stamps(mme_ctx* ctx, int M, int N, int K, uint64_t* stamps_host);
 
+/* Diagnostic: ONE launch of the MFMA GEMM  C[M,N] = A[M,K] . W[N,K]^T  with one fused epilogue on the CALLER's device
+ * operands, exactly as the encoder pass makes it, then a stream synchronise (tests/test_gpu_gemm.py compares every
+ * output element with float64).  Every pointer is device memory; a field the chosen epilogue does not read is ignored.
+ *   epilogue  0 out = bf16(acc + bias[n])                      1 out = bf16(gelu(acc + bias[n]))
+ *             2 out = bf16(acc + bias[n] + res[m,n])           (res has out's layout; res == out is the forward's in-place form)
+ *             3 patch embed: row m = (crop b = m / 196, patch p = m % 196) -> out row b*197 + 1 + p,
+ *               out = bf16(acc + bias[n] + pos[(1 + p) * N + n]); rows b*197 are not written.  M % 196 == 0.
+ *               With ln_part set, the 256 x 256 kernel also leaves the partial sums of 8 below at those OUTPUT rows.
+ *             4 outf[m * ldf + n] = acc (f32)
+ *             5 out = bf16(rstd[m] * (acc - mean[m] * colsum[n]) + bias[n]), (mean, rstd) = ln_stats[2m], [2m + 1]
+ *             6 as 5, then gelu
+ *             8 as 2; the 256 x 256 kernel (*ran_256 = 1) also writes, for every row of an INTERIOR 256-row tile,
+ *               ln_part[(0 * N/64 + slice) * ln_part_rows + m] = sum and [(1 * N/64 + slice) * ...] = sum of squares of
+ *               the ROUNDED outputs of row m over columns 64 slice .. 64 slice + 63 (f32).  Other rows carry no promise.
+ *             (7, the candidate-list epilogue of mme_neighbours, is refused.)
+ *   variant   as mme_set_gemm_variant (0 = by shape); K = 64 always runs the 128 x 128 kernel.  reverse_m 0 / 1: the
+ *             256 x 256 kernel walks the row panels upwards / downwards (same results).
+ * Preconditions (anything else returns MME_E_ARG with a message and launches nothing): M, N >= 1; K >= 64, K % 64 == 0;
+ * A, W 16-byte aligned; epilogues with a bf16 output: N % 4 == 0, bias and out 16-byte aligned, ldo >= N, ldo % 8 == 0;
+ * res 16-byte aligned and either == out or not overlapping it; pos 16-byte aligned with pos_rows >= 197; outf with
+ * ldf >= N, 16-byte aligned when ldf % 4 == 0 (4-byte otherwise); ln_stats 8-byte, colsum 16-byte aligned; planes:
+ * N % 64 == 0, ln_part_rows >= M (epilogue 8) or >= M / 196 * 197 (epilogue 3), ln_part_floats >= 2 * N/64 * ln_part_rows.
+ * *ran_256 = 1 when the 256 x 256 kernel ran (and, for epilogue 8, the planes were written), 0 for the 128 x 128 one. */
+typedef struct mme_gemm_apply_args {
+    int32_t epilogue, variant, reverse_m;
+    int32_t M, N, K;
+    const uint16_t* A;      /* bf16 [M, K] */
+    const uint16_t* W;      /* bf16 [N, K] */
+    const float* bias;      /* [N] */
+    uint16_t* out;          /* bf16, row pitch ldo elements */
+    int64_t ldo;
+    const uint16_t* res;    /* bf16, row pitch ldo */
+    const float* pos;       /* [pos_rows, N] */
+    int64_t pos_rows;
+    float* outf;            /* f32, row pitch ldf elements */
+    int64_t ldf;
+    const float* ln_stats;  /* [M, 2] */
+    const float* colsum;    /* [N] */
+    float* ln_part;         /* [2][N / 64][ln_part_rows] */
+    int64_t ln_part_rows;
+    int64_t ln_part_floats; /* capacity of ln_part in floats */
+} mme_gemm_apply_args;
+int mme_gemm_apply(mme_ctx* ctx, const mme_gemm_apply_args* args, int32_t* ran_256, void* stream);
+
+/* Diagnostic: ONE launch of a row kernel of the ViT-B/16 forward on the caller's device buffers, synchronous.
+ *   op 0 layernorm_rows          y[r] = bf16(LayerNorm(x[r]) * gamma + beta), r < rows; bf16 rows of 768, f32 two-pass statistics
+ *      1 ln_stats_rows           stats[2r], [2r + 1] = (mean, rstd) of x[r], r < rows, the same two-pass arithmetic
+ *      2 ln_stats_canonical_rows the same statistics in the canonical one-pass order (gemm_epilogue.h) of rows
+ *                                row0, row0 + stride, ... < row1 of x bf16 [*, d]; stats is indexed by the row itself
+ *      3 ln_finish_rows          stats of rows [0, rows) from the planes part [2][d / 64][part_rows] an epilogue-8 / -3 GEMM left
+ *      4 cls_rows                x[b * 197] = bf16(cls + pos[0 .. 767]), b < B (x bf16 [B * 197, 768])
+ *      5 pool_ln_l2              LayerNorm (gamma, beta) of row b * 197 + tok, then x / max(||x||, 1e-12) -> emb_f32 [B, 768]
+ *                                and / or emb_bf16 [B, 768] (either may be NULL, not both)
+ * Preconditions (else MME_E_ARG, nothing launched): the pointers the op reads or writes non-null, bf16 / f32 vectors
+ * 16-byte aligned, stats 8-byte aligned; ops 0, 1, 4, 5: d == 768; ops 2, 3: d % 64 == 0, d <= 2048; op 2: 0 <= row0 <=
+ * row1, stride >= 1; op 3: rows <= part_rows, part_floats >= 2 * d/64 * part_rows; op 5: 0 <= tok <= 196; rows, B >= 0. */
+typedef struct mme_rowop_apply_args {
+    uint16_t* x;            /* bf16 input rows (op 4: the rows written) */
+    uint16_t* y;            /* op 0 output */
+    const float* gamma;
+    const float* beta;
+    float* stats;           /* [*, 2] (mean, rstd) */
+    const float* part;
+    const float* cls;
+    const float* pos;
+    float* emb_f32;
+    uint16_t* emb_bf16;
+    int64_t rows, row0, row1, stride, part_rows, part_floats;
+    int32_t d, B, tok;
+    float eps;
+} mme_rowop_apply_args;
+int mme_rowop_apply(mme_ctx* ctx, int op, const mme_rowop_apply_args* args, void* stream);
+
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
  * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,
  * timed with its guarded exact re-run).  stamps_host uint64[B workgroups][8 waves][8]: s_memtime cycles summed over the 12 head

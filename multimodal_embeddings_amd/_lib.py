@@ -65,6 +65,21 @@ class _TileWeights(C.Structure):
     ]
 
 
+class _GemmApplyArgs(C.Structure):  # mme_gemm_apply_args
+    _fields_ = [
+        ("epilogue", C.c_int32), ("variant", C.c_int32), ("reverse_m", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("res", C.c_void_p),
+        ("pos", C.c_void_p), ("pos_rows", C.c_int64), ("outf", C.c_void_p), ("ldf", C.c_int64), ("ln_stats", C.c_void_p),
+        ("colsum", C.c_void_p), ("ln_part", C.c_void_p), ("ln_part_rows", C.c_int64), ("ln_part_floats", C.c_int64),
+    ]
+
+
+class _RowopApplyArgs(C.Structure):  # mme_rowop_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("x", "y", "gamma", "beta", "stats", "part", "cls", "pos", "emb_f32", "emb_bf16")] + [
+        (n, C.c_int64) for n in ("rows", "row0", "row1", "stride", "part_rows", "part_floats")] + [
+        ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("eps", C.c_float)]
+
+
 EXPORTS = {
     "mme_abi_version": (C.c_int, []),
     "mme_is_diag_build": (C.c_int, []),
@@ -105,6 +120,8 @@ EXPORTS = {
     "mme_set_neighbour_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mme_gemm_apply": (C.c_int, [C.c_void_p, C.POINTER(_GemmApplyArgs), C.POINTER(C.c_int32), C.c_void_p]),
+    "mme_rowop_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_RowopApplyArgs), C.c_void_p]),
     "mme_load_tile_vit": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights)]),
     "mme_load_tile_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights), C.c_int, C.c_void_p]),
     "mme_tile_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -438,6 +455,47 @@ class Engine:
         self._check(self.lib.mme_attention_apply(self.h, int(kind), qkv.data_ptr(), n, None if nt is None else nt.ctypes.data, int(only_block),
                                                  int(bool(reverse)), out.data_ptr(), C.byref(redone), self._stream()), "mme_attention_apply")
         return out, bool(redone.value)
+
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else int(t.data_ptr())
+
+    def gemm_apply(self, epilogue: int, A, W, *, M=None, N=None, K=None, variant: int = 0, reverse_m: int = 0, bias=None, out=None, ldo=None,
+                   res=None, pos=None, outf=None, ldf=None, ln_stats=None, colsum=None, ln_part=None, ln_part_rows: int = 0) -> bool:
+        """ONE GEMM launch with one epilogue on the caller's CUDA tensors (mme_gemm_apply; synchronous): A bf16 [M, K],
+        W bf16 [N, K]; the other tensors as include/mme.h describes them, `out` / `res` / `outf` possibly views into larger
+        buffers with row pitch `ldo` / `ldf` (default N).  M, N, K default to the operands' shapes.  -> True when the
+        256 x 256 kernel ran.  Nothing is checked here: the library validates every argument and raises MmeError."""
+        a = _GemmApplyArgs()
+        a.epilogue, a.variant, a.reverse_m = int(epilogue), int(variant), int(reverse_m)
+        a.M = int(A.shape[0] if M is None else M)
+        a.N = int(W.shape[0] if N is None else N)
+        a.K = int(A.shape[1] if K is None else K)
+        a.A, a.W, a.bias, a.out, a.res, a.pos = (self._ptr(t) for t in (A, W, bias, out, res, pos))
+        a.outf, a.ln_stats, a.colsum, a.ln_part = (self._ptr(t) for t in (outf, ln_stats, colsum, ln_part))
+        a.ldo = int(a.N if ldo is None else ldo)
+        a.ldf = int(a.N if ldf is None else ldf)
+        a.pos_rows = 0 if pos is None else int(pos.shape[0])
+        a.ln_part_rows = int(ln_part_rows)
+        a.ln_part_floats = 0 if ln_part is None else int(ln_part.numel())
+        ran = C.c_int32(-1)
+        self._check(self.lib.mme_gemm_apply(self.h, C.byref(a), C.byref(ran), self._stream()), "mme_gemm_apply")
+        return bool(ran.value)
+
+    ROWOPS = {"layernorm": 0, "ln_stats": 1, "ln_stats_canonical": 2, "ln_finish": 3, "cls_rows": 4, "pool_ln_l2": 5}
+
+    def rowop_apply(self, op, *, x=None, y=None, gamma=None, beta=None, stats=None, part=None, cls=None, pos=None, emb_f32=None, emb_bf16=None,
+                    rows: int = 0, row0: int = 0, row1: int = 0, stride: int = 1, part_rows: int = 0, d: int = 768, B: int = 0, tok: int = 0,
+                    eps: float = 1e-12):
+        """ONE launch of a row kernel of the forward on the caller's CUDA tensors (mme_rowop_apply; synchronous).  op: a name
+        of ROWOPS or its code; which tensors and sizes each op reads is in include/mme.h.  The library validates."""
+        a = _RowopApplyArgs()
+        a.x, a.y, a.gamma, a.beta, a.stats = (self._ptr(t) for t in (x, y, gamma, beta, stats))
+        a.part, a.cls, a.pos, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (part, cls, pos, emb_f32, emb_bf16))
+        a.rows, a.row0, a.row1, a.stride, a.part_rows = int(rows), int(row0), int(row1), int(stride), int(part_rows)
+        a.part_floats = 0 if part is None else int(part.numel())
+        a.d, a.B, a.tok, a.eps = int(d), int(B), int(tok), float(eps)
+        self._check(self.lib.mme_rowop_apply(self.h, int(self.ROWOPS.get(op, op)), C.byref(a), self._stream()), "mme_rowop_apply")
 
     def set_chunk(self, crops: int):
         self._check(self.lib.mme_set_chunk(self.h, int(crops)), "mme_set_chunk")

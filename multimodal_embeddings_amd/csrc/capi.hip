@@ -1274,6 +1274,138 @@ int mme_gemm_stamps(mme_ctx* c, int M, int N, int K, uint64_t* stamps_host) {
     return gemm_bench_impl(c, M, N, K, EPI_BIAS, 3, 150, &ms, stamps_host);
 }
 
+// ---- single launches on caller-owned operands (tests/test_gpu_gemm.py): every assumption of the kernels is checked here,
+// so that a bad argument is an MME_E_ARG and never a launch
+static bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+int mme_gemm_apply(mme_ctx* c, const mme_gemm_apply_args* a, int32_t* ran_256, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a || !ran_256) return fail(c, MME_E_ARG, "mme_gemm_apply: null argument");
+    const int epi = a->epilogue;
+    if (epi == EPI_TOPK) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 7 (candidate lists) is not served here; mme_neighbours runs it");
+    if (epi < 0 || epi > EPI_BIAS_RES_STATS) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue %d outside 0..6, 8", epi);
+    if (a->variant < 0 || a->variant > 6) return fail(c, MME_E_ARG, "mme_gemm_apply: variant %d outside 0..6", a->variant);
+    if (a->reverse_m != 0 && a->reverse_m != 1) return fail(c, MME_E_ARG, "mme_gemm_apply: reverse_m must be 0 or 1");
+    const int64_t M = a->M, N = a->N, K = a->K;
+    if (M < 1 || M > (1 << 24) || N < 1 || N > (1 << 20)) return fail(c, MME_E_ARG, "mme_gemm_apply: M = %d outside 1..2^24 or N = %d outside 1..2^20", a->M, a->N);
+    if (K < 64 || K > (1 << 16) || (K % 64) != 0) return fail(c, MME_E_ARG, "mme_gemm_apply: K = %d must be a multiple of 64 in 64..65536", a->K);
+    if (!a->A || !a->W) return fail(c, MME_E_ARG, "mme_gemm_apply: null operand (A or W)");
+    if (!aligned_to(a->A, 16) || !aligned_to(a->W, 16)) return fail(c, MME_E_ARG, "mme_gemm_apply: A and W must be 16-byte aligned");
+    const bool patch = epi == EPI_PATCH, res = epi == EPI_BIAS_RES || epi == EPI_BIAS_RES_STATS;
+    const bool ln = epi == EPI_LN_BIAS || epi == EPI_LN_BIAS_GELU;
+    if (patch && (M % VIT_NP) != 0) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 3 needs M %% %d == 0 (M = %d)", VIT_NP, a->M);
+    const int64_t out_rows = patch ? M / VIT_NP * VIT_T : M;
+    if (epi == EPI_F32) {
+        if (!a->outf) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 4 needs outf");
+        if (a->ldf < N || a->ldf > (1 << 24)) return fail(c, MME_E_ARG, "mme_gemm_apply: ldf = %lld outside N..2^24", (long long)a->ldf);
+        if (!aligned_to(a->outf, (a->ldf % 4) == 0 ? 16 : 4))
+            return fail(c, MME_E_ARG, "mme_gemm_apply: outf must be 16-byte aligned when ldf %% 4 == 0 (4-byte otherwise)");
+    } else {
+        if ((N % 4) != 0) return fail(c, MME_E_ARG, "mme_gemm_apply: a bf16 output needs N %% 4 == 0 (N = %d)", a->N);
+        if (!a->bias || !a->out) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue %d needs bias and out", epi);
+        if (!aligned_to(a->bias, 16) || !aligned_to(a->out, 16)) return fail(c, MME_E_ARG, "mme_gemm_apply: bias and out must be 16-byte aligned");
+        if (a->ldo < N || a->ldo > (1 << 24) || (a->ldo % 8) != 0) return fail(c, MME_E_ARG, "mme_gemm_apply: ldo = %lld must be a multiple of 8 in N..2^24", (long long)a->ldo);
+    }
+    if (res) {
+        if (!a->res) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue %d needs res", epi);
+        if (!aligned_to(a->res, 16)) return fail(c, MME_E_ARG, "mme_gemm_apply: res must be 16-byte aligned");
+        const uintptr_t o0 = (uintptr_t)a->out, r0 = (uintptr_t)a->res, span = (uintptr_t)(((out_rows - 1) * a->ldo + N) * 2);
+        if (r0 != o0 && r0 < o0 + span && o0 < r0 + span) return fail(c, MME_E_ARG, "mme_gemm_apply: res must be out itself or not overlap it");
+    }
+    if (patch) {
+        if (!a->pos) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 3 needs pos");
+        if (!aligned_to(a->pos, 16)) return fail(c, MME_E_ARG, "mme_gemm_apply: pos must be 16-byte aligned");
+        if (a->pos_rows < VIT_T) return fail(c, MME_E_ARG, "mme_gemm_apply: pos must hold [%d, N] (pos_rows = %lld)", VIT_T, (long long)a->pos_rows);
+    }
+    if (ln) {
+        if (!a->ln_stats || !a->colsum) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue %d needs ln_stats and colsum", epi);
+        if (!aligned_to(a->ln_stats, 8) || !aligned_to(a->colsum, 16)) return fail(c, MME_E_ARG, "mme_gemm_apply: ln_stats must be 8-byte and colsum 16-byte aligned");
+    }
+    const bool planes = epi == EPI_BIAS_RES_STATS || (patch && a->ln_part);
+    if (planes) {
+        if (!a->ln_part) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 8 needs ln_part");
+        if (!aligned_to(a->ln_part, 4)) return fail(c, MME_E_ARG, "mme_gemm_apply: ln_part must be 4-byte aligned");
+        if ((N % 64) != 0) return fail(c, MME_E_ARG, "mme_gemm_apply: partial-sum planes need N %% 64 == 0 (N = %d)", a->N);
+        if (a->ln_part_rows < out_rows) return fail(c, MME_E_ARG, "mme_gemm_apply: ln_part_rows = %lld is below the %lld output rows", (long long)a->ln_part_rows, (long long)out_rows);
+        if (a->ln_part_rows > ((int64_t)1 << 32) || a->ln_part_floats < 2 * (N / 64) * a->ln_part_rows)
+            return fail(c, MME_E_ARG, "mme_gemm_apply: ln_part holds %lld floats, [2][%lld][%lld] needs %lld", (long long)a->ln_part_floats, (long long)(N / 64),
+                        (long long)a->ln_part_rows, (long long)(2 * (N / 64) * a->ln_part_rows));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    GemmArgs g{};
+    g.A = a->A; g.W = a->W; g.M = a->M; g.N = a->N; g.K = a->K;
+    g.reverse_m = a->reverse_m;
+    if (epi == EPI_F32) {
+        g.outf = a->outf; g.ldf = a->ldf;
+    } else {
+        g.bias = a->bias; g.out = a->out; g.ldo = a->ldo;
+    }
+    if (res) g.res = a->res;
+    if (patch) g.pos = a->pos;
+    if (ln) { g.ln_stats = a->ln_stats; g.colsum = a->colsum; }
+    if (planes) { g.ln_part = a->ln_part; g.ln_part_rows = a->ln_part_rows; }
+    hipStream_t s = (hipStream_t)stream;
+    *ran_256 = gemm_runs_256(g, a->variant) ? 1 : 0;
+    HIP_TRY(c, launch_gemm(epi, g, s, a->variant));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_rowop_apply: null argument");
+    if (op < 0 || op > 5) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d outside 0..5", op);
+    const bool fixed_d = op == 0 || op == 1 || op == 4 || op == 5;
+    if (fixed_d && a->d != VIT_D) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d is built for d == %d (d = %d)", op, VIT_D, a->d);
+    if (!fixed_d && (a->d <= 0 || (a->d % 64) != 0 || a->d > 2048)) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d needs d %% 64 == 0, d <= 2048 (d = %d)", op, a->d);
+    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    const bool stats_ok = a->stats && aligned_to(a->stats, 8);
+    const char* bad = nullptr;
+    switch (op) {
+        case 0:
+            if (!vec(a->x) || !vec(a->y) || !vec(a->gamma) || !vec(a->beta)) bad = "x, y, gamma, beta non-null and 16-byte aligned";
+            else if (a->rows < 0) bad = "rows >= 0";
+            break;
+        case 1:
+            if (!vec(a->x) || !stats_ok) bad = "x non-null and 16-byte aligned, stats non-null and 8-byte aligned";
+            else if (a->rows < 0) bad = "rows >= 0";
+            break;
+        case 2:
+            if (!vec(a->x) || !stats_ok) bad = "x non-null and 16-byte aligned, stats non-null and 8-byte aligned";
+            else if (a->row0 < 0 || a->row1 < a->row0 || a->stride < 1) bad = "0 <= row0 <= row1 and stride >= 1";
+            break;
+        case 3:
+            if (!a->part || !aligned_to(a->part, 4) || !stats_ok) bad = "part non-null and 4-byte aligned, stats non-null and 8-byte aligned";
+            else if (a->rows < 0 || a->rows > a->part_rows) bad = "0 <= rows <= part_rows";
+            else if (a->part_rows > ((int64_t)1 << 32) || a->part_floats < 2 * (int64_t)(a->d / 64) * a->part_rows) bad = "part_floats >= 2 * d/64 * part_rows";
+            break;
+        case 4:
+            if (!vec(a->x) || !vec(a->cls) || !vec(a->pos)) bad = "x, cls, pos non-null and 16-byte aligned";
+            else if (a->B < 0) bad = "B >= 0";
+            break;
+        default:
+            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
+            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
+            else if (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
+            else if (a->B < 0) bad = "B >= 0";
+            else if (a->tok < 0 || a->tok >= VIT_T) bad = "0 <= tok <= 196";
+            break;
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d needs %s", op, bad);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    switch (op) {
+        case 0: HIP_TRY(c, launch_layernorm(a->x, a->gamma, a->beta, a->y, a->rows, a->eps, s)); break;
+        case 1: HIP_TRY(c, launch_ln_stats(a->x, a->rows, a->eps, a->stats, s)); break;
+        case 2: HIP_TRY(c, launch_ln_stats_canonical(a->x, a->row0, a->row1, a->d, a->eps, a->stats, s, a->stride)); break;
+        case 3: HIP_TRY(c, launch_ln_finish(a->part, a->part_rows, a->rows, a->d, a->eps, a->stats, s)); break;
+        case 4: HIP_TRY(c, launch_cls_rows(a->x, a->cls, a->pos, a->B, s)); break;
+        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, a->tok, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
 // ---- the one collective (RCCL over xGMI) -------------------------------------------------------------------
 #define RCCL_TRY(c, expr)                                                                           \
     do {                                                                                            \
