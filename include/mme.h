@@ -57,10 +57,17 @@ const char* mme_last_error(const mme_ctx* ctx); /* ctx may be NULL: creation err
 
 /* ---- encoder weights --------------------------------------------------------------
  * Replaces `MllamaForConditionalGeneration.from_pretrained(...)` (embedder.py:75-80) for
- * the re-scoped ViT-B/16 encoder.  Host f32 tensors in Hugging Face ViT layout
+ * the re-scoped ViT/16 encoder (ViT-S, ViT-B or ViT-L at 224 pixels).  Host f32 tensors in Hugging Face ViT layout
  * (transformers models/vit/modeling_vit.py): Linear weights are [out, in]; the patch
  * projection is [hidden, 3*patch*patch] in (c, ky, kx) order.  Values are rounded to
- * bf16 on upload (the reference runs the encoder in bf16, embedder.py:78). */
+ * bf16 on upload (the reference runs the encoder in bf16, embedder.py:78).
+ * Supported geometries: image_size 224, patch_size 16, heads of 64 (heads == hidden / 64), hidden 384, 768 or 1024,
+ * mlp a multiple of 64 up to 8192, 1..64 layers, any ln_eps.  Anything else is MME_E_ARG with a text that names the
+ * field, the value found and the supported values; nothing in the context changes then.
+ * A context runs the geometry of its LAST successful load, ViT-B/16 (224/16/768/12/12/3072) before any: a second load
+ * replaces the first whatever the two geometries are (the old weight buffers are freed once the device has drained, the
+ * activation workspace regrows on the next pass).  A load that fails after validation leaves the context without
+ * weights. */
 typedef struct {
     const float *ln1_g, *ln1_b;
     const float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *o_w, *o_b;
@@ -71,10 +78,10 @@ typedef struct {
 typedef struct {
     int32_t image_size;  /* 224 */
     int32_t patch_size;  /* 16  */
-    int32_t hidden;      /* 768 */
-    int32_t layers;      /* 12  */
-    int32_t heads;       /* 12  */
-    int32_t mlp;         /* 3072 */
+    int32_t hidden;      /* 384, 768 or 1024 */
+    int32_t layers;      /* 1..64 */
+    int32_t heads;       /* hidden / 64 */
+    int32_t mlp;         /* multiple of 64, <= 8192 */
     float ln_eps;        /* 1e-12 */
     const float* cls_token; /* [hidden] */
     const float* pos_emb;   /* [1 + (image/patch)^2, hidden] */
@@ -86,6 +93,9 @@ typedef struct {
 } mme_vit_weights;
 
 int mme_load_vit(mme_ctx* ctx, const mme_vit_weights* w);
+/* out[6] = image_size, patch_size, hidden, layers, heads, mlp of the context's encoder: what the last load brought,
+ * ViT-B/16 before any.  mme_vit_forward / mme_embed write rows of `hidden`. */
+int mme_vit_geometry(mme_ctx* ctx, int32_t out[6]);
 
 /* The same load from a checkpoint's OWN element type, prepared on the device.  Replaces the `torch_dtype=bfloat16` read of
  * `from_pretrained` (embedder.py:75-80) for a checkpoint on local disk: every tensor pointer of `w` (and of its layer
@@ -112,7 +122,10 @@ int mme_weights_fingerprint(mme_ctx* ctx, int cap, uint64_t* out_host);
 int mme_set_normalisation(mme_ctx* ctx, const float mean[3], const float std[3]);
 
 /* Rows of the internal activation workspace = crops per encoder pass (default 4096: one pass
- * for the headline batch; 11.6 GB of workspace; larger passes lose less to tile quantisation). */
+ * for the headline batch; 11.6 GiB of workspace at ViT-B/16; larger passes lose less to tile quantisation).
+ * The workspace is 197 * crops * (12 * hidden + 2 * mlp + 8 * (1 + hidden / 64)) bytes, plus 301 056 bytes of patch
+ * rows per crop in mme_embed: at 4096 crops 6.2 GB for ViT-S/16, 12.5 GB (11.6 GiB) for ViT-B/16 and 16.6 GB for
+ * ViT-L/16. */
 int mme_set_chunk(mme_ctx* ctx, int crops_per_pass);
 
 /* Tuning / test knob: which MFMA GEMM tiling serves K2/K4/K6/K7/K9.  0 = by shape (default),
@@ -131,7 +144,7 @@ int mme_set_gemm_variant(mme_ctx* ctx, int variant);
  *   0 separate LayerNorm kernel (A/B, tests). */
 int mme_set_ln_fusion(mme_ctx* ctx, int mode);
 
-/* K5 (attention of the ViT-B/16 forward, transformers modeling_vit.py:164-189).
+/* K5 (attention of the ViT/16 forward, transformers modeling_vit.py:164-189).
  *   1 (default) fast form: the exponentials of a query row are taken against the maximum over its first 32 keys instead
  *     of its row maximum -- softmax is invariant to that choice, only the range differs -- which lets the scores leave
  *     the matrix pipe ready for exp2.  A row whose sum leaves [1, 2^100), or whose unnormalised output O is not finite
@@ -170,14 +183,16 @@ int mme_set_tile_order(mme_ctx* ctx, int mode);
  * (bench.py reports the pruned rate separately); applies to the LayerNorm-folded modes (mme_set_ln_fusion 1 / 2). */
 int mme_set_forward_pruning(mme_ctx* ctx, int on);
 /* Diagnostic (synchronises the device): flags[l] != 0 when the attention launch of layer l of the LAST encoder pass
- * raised its guard and was redone by the exact kernel. */
+ * raised its guard and was redone by the exact kernel.  Writes min(12, layers) words (mme_vit_geometry): the whole of a
+ * ViT-S or ViT-B pass; mme_attention_redone_n reads the 24 of ViT-L. */
 int mme_attention_redone(mme_ctx* ctx, int32_t flags[12]);
-/* As mme_attention_redone for the first `count` (1..64) layers of the last pass: 12 for the ViT-B/16 forward, the
+/* As mme_attention_redone for the first `count` (1..64) layers of the last pass: the layer count of the ViT forward, the
  * tower's local + global layer count (40 in the full tower) after mme_tile_vit_forward. */
 int mme_attention_redone_n(mme_ctx* ctx, int count, int32_t* flags);
 /* ONE attention launch on a caller's activation, exactly as the forward makes it under the current
  * mme_set_attention_mode (0 exact; 1 fast, then the exact kernel with run_if = guard; 2 the re-run forced).  Synchronous.
- *   kind 0 (K5):       qkv_dev bf16 [n*197][2304] = Q | K | V, head h at columns 64h of each part -> out_dev bf16 [n*197][768];
+ *   kind 0 (K5):       at the context's geometry (mme_vit_geometry; ViT-B/16 when nothing is loaded):
+ *                      qkv_dev bf16 [n*197][3*hidden] = Q | K | V, head h at columns 64h of each part -> out_dev bf16 [n*197][hidden];
  *                      only_block -1 (every query block) or 0..6 (only queries 32b..32b+31 are computed and stored, as the
  *                      pruned last layer does); reverse 0 / 1 (the walk order of the blocks; results are bit-identical).
  *   kind 1 (tile-ViT): qkv_dev bf16 [n*6432][3840], 16 heads of 80 -> out_dev bf16 [n*6432][1280]; ntiles_host int32[n],
@@ -219,7 +234,8 @@ int mme_nms_boxes(mme_ctx* ctx, const double* boxes, const double* scores, const
  * Replaces, per crop, `processor(images=[image])` (embedder.py:117-121; transformers
  * image_processing_pil_mllama.py:483-541 with tile 224, one tile): aspect-preserving
  * Pillow-BILINEAR fit (bit-exact incl. the per-pass uint8 rounding), zero pad right/
- * bottom BEFORE normalisation, x/255, (x-mean)/std, im2col to [196, 768] in (c,ky,kx).
+ * bottom BEFORE normalisation, x/255, (x-mean)/std, im2col to [196, 768] in (c,ky,kx)
+ * (768 = 3 * 16 * 16, the patch row: the same at every hidden size).
  *   pix_dev     uint8 RGB HWC pixels of all crops, concatenated; the allocation must
  *               extend at least 16 bytes past the last pixel (rows are read in words)
  *   offs_host   int64[n]   byte offset of crop i inside pix_dev
@@ -404,17 +420,18 @@ typedef struct mme_gemm_apply_args {
 } mme_gemm_apply_args;
 int mme_gemm_apply(mme_ctx* ctx, const mme_gemm_apply_args* args, int32_t* ran_256, void* stream);
 
-/* Diagnostic: ONE launch of a row kernel of the ViT-B/16 forward on the caller's device buffers, synchronous.
- *   op 0 layernorm_rows          y[r] = bf16(LayerNorm(x[r]) * gamma + beta), r < rows; bf16 rows of 768, f32 two-pass statistics
+/* Diagnostic: ONE launch of a row kernel of the ViT forward on the caller's device buffers, synchronous.
+ *   op 0 layernorm_rows          y[r] = bf16(LayerNorm(x[r]) * gamma + beta), r < rows; bf16 rows of d, f32 two-pass statistics
  *      1 ln_stats_rows           stats[2r], [2r + 1] = (mean, rstd) of x[r], r < rows, the same two-pass arithmetic
  *      2 ln_stats_canonical_rows the same statistics in the canonical one-pass order (gemm_epilogue.h) of rows
  *                                row0, row0 + stride, ... < row1 of x bf16 [*, d]; stats is indexed by the row itself
  *      3 ln_finish_rows          stats of rows [0, rows) from the planes part [2][d / 64][part_rows] an epilogue-8 / -3 GEMM left
- *      4 cls_rows                x[b * 197] = bf16(cls + pos[0 .. 767]), b < B (x bf16 [B * 197, 768])
- *      5 pool_ln_l2              LayerNorm (gamma, beta) of row b * 197 + tok, then x / max(||x||, 1e-12) -> emb_f32 [B, 768]
- *                                and / or emb_bf16 [B, 768] (either may be NULL, not both)
+ *      4 cls_rows                x[b * 197] = bf16(cls + pos[0 .. d - 1]), b < B (x bf16 [B * 197, d])
+ *      5 pool_ln_l2              LayerNorm (gamma, beta) of row b * 197 + tok, then x / max(||x||, 1e-12) -> emb_f32 [B, d]
+ *                                and / or emb_bf16 [B, d] (either may be NULL, not both)
  * Preconditions (else MME_E_ARG, nothing launched): the pointers the op reads or writes non-null, bf16 / f32 vectors
- * 16-byte aligned, stats 8-byte aligned; ops 0, 1, 4, 5: d == 768; ops 2, 3: d % 64 == 0, d <= 2048; op 2: 0 <= row0 <=
+ * 16-byte aligned, stats 8-byte aligned; ops 0, 1, 4, 5: d == 384, d == 768 or d == 1024 (one instantiation per
+ * supported width); ops 2, 3: d % 64 == 0, d <= 2048; op 2: 0 <= row0 <=
  * row1, stride >= 1; op 3: rows <= part_rows, part_floats >= 2 * d/64 * part_rows; op 5: 0 <= tok <= 196; rows, B >= 0. */
 typedef struct mme_rowop_apply_args {
     uint16_t* x;            /* bf16 input rows (op 4: the rows written) */
@@ -435,8 +452,8 @@ int mme_rowop_apply(mme_ctx* ctx, int op, const mme_rowop_apply_args* args, void
 
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
  * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,
- * timed with its guarded exact re-run).  stamps_host uint64[B workgroups][8 waves][8]: s_memtime cycles summed over the 12 head
- * iterations of the wave -- [0] wait for its own requests, [1] workgroup barrier, [2] issue of the next head's
+ * timed with its guarded exact re-run).  stamps_host uint64[B workgroups][8 waves][8]: s_memtime cycles summed over the head
+ * iterations of the wave (the context's head count: 12 for ViT-B/16) -- [0] wait for its own requests, [1] workgroup barrier, [2] issue of the next head's
  * requests (K/V LDS-DMA on wave 7, Q prefetch on the others), [3] S^T = K.Q^T, [4] softmax, [5] O^T = V^T.P^T,
  * [6] hand-over + output stores; [7] heads processed.  Wave 7 (staging only) carries in [5] / [6] the s_memtime cycles and
  * s_memrealtime ticks (100 MHz) of the whole workgroup: [5] / [6] x 100 MHz = the clock the chip held. */

@@ -87,6 +87,7 @@ EXPORTS = {
     "mme_destroy": (None, [C.c_void_p]),
     "mme_last_error": (C.c_char_p, [C.c_void_p]),
     "mme_load_vit": (C.c_int, [C.c_void_p, C.POINTER(_Weights)]),
+    "mme_vit_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_load_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_Weights), C.c_int, C.c_void_p]),
     "mme_weights_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "mme_set_normalisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -216,14 +217,11 @@ class Engine:
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- weights ---------------------------------------------------------------------------------
-    def load_vit(self, w: dict, eps: float = 1e-12):
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            self._keep.append(a)
-            return _fp(a)
-
-        layers = (_Layer * 12)()
-        for i in range(12):
+    @staticmethod
+    def _vit_struct(geom, arr):
+        """mme_vit_weights (+ its layer array, which the caller keeps alive) for `geom`, tensor pointers from arr(name)."""
+        layers = (_Layer * geom.num_layers)()
+        for i in range(geom.num_layers):
             p = f"layers.{i}."
             L = layers[i]
             L.ln1_g, L.ln1_b = arr(p + "layernorm_before.weight"), arr(p + "layernorm_before.bias")
@@ -234,15 +232,57 @@ class Engine:
             L.ln2_g, L.ln2_b = arr(p + "layernorm_after.weight"), arr(p + "layernorm_after.bias")
             L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
             L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        W = _Weights(224, 16, 768, 12, 12, 3072, float(eps))
+        W = _Weights(geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
+                     float(geom.layer_norm_eps))
         W.cls_token = arr("embeddings.cls_token")
         W.pos_emb = arr("embeddings.position_embeddings")
         W.patch_w = arr("embeddings.patch_embeddings.projection.weight")
         W.patch_b = arr("embeddings.patch_embeddings.projection.bias")
         W.lnf_g, W.lnf_b = arr("layernorm.weight"), arr("layernorm.bias")
         W.layer = layers
+        return W, layers
+
+    def load_vit(self, w: dict, eps: float | None = None, geom=None):
+        """Canonical-name dict of f32 arrays (weights.vit_tensor_specs) -> this context, replacing what it held.  The
+        geometry is `geom` (a weights.ViTGeometry) or, by default, read off the tensor shapes (heads of 64); every tensor's
+        shape is checked against it here, the geometry itself against the supported set by the library.  `eps` overrides
+        the geometry's layer_norm_eps."""
+        import dataclasses
+
+        from .weights import infer_vit_geometry, vit_tensor_specs
+
+        if geom is None:
+            geom = infer_vit_geometry(w)
+        if eps is not None:
+            geom = dataclasses.replace(geom, layer_norm_eps=float(eps))
+        for name, shape, _ in vit_tensor_specs(geom):
+            if name not in w:
+                raise MmeError(f"load_vit: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"load_vit: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32)
+            keep.append(a)
+            return _fp(a)
+
+        W, layers = self._vit_struct(geom, arr)
         self._check(self.lib.mme_load_vit(self.h, C.byref(W)), "mme_load_vit")
-        self._keep.clear()
+
+    def vit_geometry(self):
+        """The weights.ViTGeometry this context runs (mme_vit_geometry): that of its last load, ViT-B/16 before any.
+        layer_norm_eps is not reported by the library and keeps the dataclass default."""
+        from .weights import ViTGeometry
+
+        g = (C.c_int32 * 6)()
+        self._check(self.lib.mme_vit_geometry(self.h, g), "mme_vit_geometry")
+        return ViTGeometry(image_size=g[0], patch_size=g[1], hidden_size=g[2], num_layers=g[3], num_heads=g[4], intermediate_size=g[5])
+
+    @property
+    def embed_dim(self) -> int:
+        """Width of the rows `vit_forward` / `embed` return."""
+        return self.vit_geometry().hidden_size
 
     def load_tile_vit(self, w: dict, geom=None):
         """Hugging Face `MllamaVisionModel` state dict (f32 arrays) -> the tile-ViT encoder of this context."""
@@ -298,31 +338,12 @@ class Engine:
         return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))  # elements of ckpt.dtype behind the struct's float*
 
     def load_vit_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "vit_b16")` -> this context: the raw f32 / bf16 / f16 bytes go to the device
-        and are converted, scaled and LayerNorm-folded there, bit-identically to `load_vit` on the same values."""
-        if ckpt.encoder != "vit_b16":
+        """`checkpoint.read_checkpoint(dir, "vit_b16" | "vit")` -> this context, at the checkpoint's geometry: the raw f32 /
+        bf16 / f16 bytes go to the device and are converted, scaled and LayerNorm-folded there, bit-identically to
+        `load_vit` on the same values.  Replaces what the context held."""
+        if ckpt.encoder not in ("vit_b16", "vit"):
             raise MmeError(f"load_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        arr = lambda name: self._ckpt_ptr(ckpt, name)  # noqa: E731
-        layers = (_Layer * 12)()
-        for i in range(12):
-            p = f"layers.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "layernorm_before.weight"), arr(p + "layernorm_before.bias")
-            L.q_w, L.q_b = arr(p + "attention.q_proj.weight"), arr(p + "attention.q_proj.bias")
-            L.k_w, L.k_b = arr(p + "attention.k_proj.weight"), arr(p + "attention.k_proj.bias")
-            L.v_w, L.v_b = arr(p + "attention.v_proj.weight"), arr(p + "attention.v_proj.bias")
-            L.o_w, L.o_b = arr(p + "attention.o_proj.weight"), arr(p + "attention.o_proj.bias")
-            L.ln2_g, L.ln2_b = arr(p + "layernorm_after.weight"), arr(p + "layernorm_after.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        g = ckpt.geometry
-        W = _Weights(g.image_size, g.patch_size, g.hidden_size, g.num_layers, g.num_heads, g.intermediate_size, float(g.layer_norm_eps))
-        W.cls_token = arr("embeddings.cls_token")
-        W.pos_emb = arr("embeddings.position_embeddings")
-        W.patch_w = arr("embeddings.patch_embeddings.projection.weight")
-        W.patch_b = arr("embeddings.patch_embeddings.projection.bias")
-        W.lnf_g, W.lnf_b = arr("layernorm.weight"), arr("layernorm.bias")
-        W.layer = layers
+        W, layers = self._vit_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
         self._check(self.lib.mme_load_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_vit_as")
 
     def load_tile_vit_checkpoint(self, ckpt, geometry=None):
@@ -423,22 +444,25 @@ class Engine:
 
     def attention_redone(self, count: int = 12):
         """Layers of the LAST encoder pass whose attention launch raised the fast form's guard (list of `count` ints:
-        12 for the ViT-B/16 forward, the tower's layer count after `tile_vit_forward`)."""
+        `vit_geometry().num_layers` for the ViT forward -- 12 for ViT-B/16 --, the tower's layer count after `tile_vit_forward`)."""
         flags = (C.c_int32 * int(count))()
         self._check(self.lib.mme_attention_redone_n(self.h, int(count), flags), "mme_attention_redone_n")
         return list(flags)
 
-    # (tokens, heads, head dim) of the attention kinds mme_attention_apply takes
-    _ATTN_KINDS = {0: (197, 12, 64), 1: (6432, 16, 80)}
+    # (tokens, heads, head dim) of the attention kinds mme_attention_apply takes; kind 0 runs at the context's geometry
+    _ATTN_KINDS = {0: (197, None, 64), 1: (6432, 16, 80)}
 
     def attention(self, qkv, kind: int, ntiles=None, only_block: int = -1, reverse: bool = False, out=None):
         """ONE attention launch under the current attention mode (mme_attention_apply; synchronous).  qkv bf16 CUDA
-        [n * T, 3 * H * dh] = Q | K | V with Q pre-scaled by dh^-0.5 log2(e); kind 0 = ViT-B/16 (T 197, 12 x 64), kind 1 =
+        [n * T, 3 * H * dh] = Q | K | V with Q pre-scaled by dh^-0.5 log2(e); kind 0 = the ViT of this context (T 197, H x 64
+        with H = 6, 12 or 16 as loaded; 12 before any load), kind 1 =
         tile-ViT (T 6432, 16 x 80, `ntiles` = tiles per image, 1..4).  -> (out bf16 [n * T, H * dh], redone: bool)."""
         t = self.torch
         if kind not in self._ATTN_KINDS:
-            raise MmeError(f"attention: kind {kind} (0 = ViT-B/16, 1 = tile-ViT)")
+            raise MmeError(f"attention: kind {kind} (0 = ViT/16, 1 = tile-ViT)")
         T, H, dh = self._ATTN_KINDS[kind]
+        if H is None:
+            H = self.vit_geometry().num_heads
         if qkv.dtype != t.bfloat16 or not qkv.is_contiguous() or qkv.dim() != 2 or qkv.shape[1] != 3 * H * dh or qkv.shape[0] % T:
             raise MmeError(f"attention: qkv must be a contiguous bf16 [n * {T}, {3 * H * dh}] tensor")
         n = qkv.shape[0] // T
@@ -559,7 +583,8 @@ class Engine:
         t = self.torch
         offs, hw = self._crop_tables(offs, hw)
         n = len(offs)
-        patches = t.empty((n * 196, 768), dtype=t.bfloat16, device=pix.device)
+        g = self.vit_geometry()
+        patches = t.empty((n * g.num_patches, g.patch_dim), dtype=t.bfloat16, device=pix.device)
         self._check(self.lib.mme_preprocess(self.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, patches.data_ptr(), self._stream()), "mme_preprocess")
         return patches
 
@@ -579,9 +604,10 @@ class Engine:
 
     def vit_forward(self, patches, pool_token: int = 0, want_f32: bool = True, want_bf16: bool = True):
         t = self.torch
-        n = patches.shape[0] // 196
-        e32 = t.empty((n, 768), dtype=t.float32, device=patches.device) if want_f32 else None
-        e16 = t.empty((n, 768), dtype=t.bfloat16, device=patches.device) if want_bf16 else None
+        g = self.vit_geometry()
+        n, d = patches.shape[0] // g.num_patches, g.hidden_size
+        e32 = t.empty((n, d), dtype=t.float32, device=patches.device) if want_f32 else None
+        e16 = t.empty((n, d), dtype=t.bfloat16, device=patches.device) if want_bf16 else None
         self._check(self.lib.mme_vit_forward(self.h, patches.data_ptr(), n, int(pool_token), e32.data_ptr() if want_f32 else None,
                                              e16.data_ptr() if want_bf16 else None, self._stream()), "mme_vit_forward")
         return e32, e16
@@ -590,8 +616,8 @@ class Engine:
         t = self.torch
         offs, hw = self._crop_tables(offs, hw)
         n = len(offs)
-        e32 = out_f32 if out_f32 is not None else (t.empty((n, 768), dtype=t.float32, device=pix.device) if want_f32 else None)
-        e16 = out_bf16 if out_bf16 is not None else (t.empty((n, 768), dtype=t.bfloat16, device=pix.device) if want_bf16 else None)
+        e32 = out_f32 if out_f32 is not None else (t.empty((n, self.embed_dim), dtype=t.float32, device=pix.device) if want_f32 else None)
+        e16 = out_bf16 if out_bf16 is not None else (t.empty((n, self.embed_dim), dtype=t.bfloat16, device=pix.device) if want_bf16 else None)
         self._check(self.lib.mme_embed(self.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, int(pool_token),
                                        e32.data_ptr() if e32 is not None else None, e16.data_ptr() if e16 is not None else None,
                                        self._stream()), "mme_embed")

@@ -6,12 +6,13 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
     config.json  [+ preprocessor_config.json]
     model.safetensors  |  model.safetensors.index.json + shards  |  pytorch_model.bin
 
--- checks that its configuration is the geometry the library is built for, maps the tensor names to the canonical ones
+-- checks that its configuration is a geometry the library is built for ("vit_b16": exactly ViT-B/16; "vit": any of the
+supported ViT/16 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
 bytes to the device, where they are converted and folded (csrc/weight_prep.hip).
 
-    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|mllama_tiles]
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|mllama_tiles]
 
 prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
 """
@@ -25,11 +26,12 @@ from dataclasses import dataclass, field
 
 from . import config
 from ._lib import MmeError
-from .weights import TILE_VIT, VIT_B16, TileViTGeometry, ViTGeometry, tile_vit_tensor_specs, vit_tensor_specs
+from .weights import TILE_VIT, VIT_B16, TileViTGeometry, ViTGeometry, tile_vit_tensor_specs, vit_geometry_problem, vit_tensor_specs
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "mllama_tiles")
+ENCODERS = ("vit_b16", "vit", "mllama_tiles")
+VIT_ENCODERS = ("vit_b16", "vit")  # one loader, one tensor layout; "vit" takes its geometry from config.json
 SUPPORTED_ASPECT_RATIOS = [[1, 1], [1, 2], [1, 3], [1, 4], [2, 1], [2, 2], [3, 1], [4, 1]]
 _DTYPE_IDS = {"float32": 0, "bfloat16": 1, "float16": 2}  # include/mme.h MME_DT_*
 _warned_resize_rule = False
@@ -131,6 +133,25 @@ def _vit_geometry(cfg: dict, where: str) -> ViTGeometry:
     _expect(cfg, "hidden_act", "gelu", where)
     _expect(cfg, "qkv_bias", True, where, default=True)
     return ViTGeometry(layer_norm_eps=float(cfg.get("layer_norm_eps", g.layer_norm_eps)))
+
+
+def _vit_family_geometry(cfg: dict, where: str) -> ViTGeometry:
+    """config.json of any ViT/16 @224 the engine runs (weights.SUPPORTED_VIT); a field outside the set is refused with the
+    field, the value found and the supported values."""
+    b = VIT_B16
+    for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
+        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
+            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
+    g = ViTGeometry(image_size=cfg["image_size"], patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels),
+                    hidden_size=cfg["hidden_size"], num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"],
+                    intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
+    bad = vit_geometry_problem(g)
+    if bad:
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    _expect(cfg, "hidden_act", "gelu", where)
+    _expect(cfg, "qkv_bias", True, where, default=True)
+    return g
 
 
 def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
@@ -271,8 +292,8 @@ def read_checkpoint(path, encoder: str = "vit_b16") -> Checkpoint:
         raise MmeError(f"{cfg_path} is missing")
     cfg = _load_json(cfg_path)
     source = [cfg_path]
-    if encoder == "vit_b16":
-        geometry = _vit_geometry(cfg, "config.json")
+    if encoder in VIT_ENCODERS:
+        geometry = _vit_geometry(cfg, "config.json") if encoder == "vit_b16" else _vit_family_geometry(cfg, "config.json")
         specs = [(n, s) for n, s, _ in vit_tensor_specs(geometry)]
         canonical = canonical_vit_name
     else:
@@ -310,7 +331,7 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
 
     tdt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}[dtype]
     os.makedirs(path, exist_ok=True)
-    if encoder == "vit_b16":
+    if encoder in VIT_ENCODERS:
         g = geometry or VIT_B16
         cfg = {"architectures": ["ViTModel"], "model_type": "vit", "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels,
                "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,

@@ -1,11 +1,13 @@
-// K5: fused multi-head self-attention for ViT-B/16 (T = 197 tokens, 12 heads, dh = 64).
+// K5: fused multi-head self-attention for ViT/16 @224 (T = 197 tokens, dh = 64; H = 6, 12 or 16 heads: ViT-S, -B, -L).
 //
 // Restates transformers models/vit/modeling_vit.py:164-189 (softmax(Q K^T / 8) V, softmax in
 // f32).  T is short, so there is no online softmax: the whole 32 x 224 score strip of a query
 // block lives in accumulator registers.
 //
-// One 8-wave workgroup per CU, PERSISTENT: it walks its blocks (a block = the 12 heads of one crop; 12 / hsplit heads
-// for small batches) as one stream of (crop, head) items:
+// One 8-wave workgroup per CU, PERSISTENT: it walks its blocks (a block = the H heads of one crop; H / hsplit heads
+// for small batches) as one stream of (crop, head) items.  H is a template parameter: it enters only the row strides of
+// the activation (3 * 64 H in, 64 H out) and the item -> (crop, head) map, so an item's arithmetic, LDS image and
+// scaling are the same at every width, and the 12-head instantiation is the code it was when H was a constant:
 //   * K and V of item i+1 stream into the second LDS buffer by LDS-DMA (global_load_lds, no VGPR round trip) while
 //     item i is computed, and the Q fragments of item i+1 are prefetched into registers -- across crop boundaries too:
 //     after the workgroup's first item no memory latency is exposed.  One barrier per item.
@@ -33,7 +35,11 @@
 namespace {
 
 constexpr int ROWB = VIT_DH * 2;       // 128-byte K/V rows in LDS
-constexpr int QKV_LD = 3 * VIT_D * 2;  // 4608-byte rows of the fused QKV activation
+template <int H> struct AttnRows {
+    static_assert(H == 6 || H == 12 || H == 16, "attention: 6, 12 or 16 heads of 64");
+    static constexpr int D = H * VIT_DH;    // row of the output, and of each of Q | K | V
+    static constexpr int QKV_LD = 3 * D * 2;  // bytes per row of the fused QKV activation (4608 at 12 heads)
+};
 constexpr int NPIECE = 25;             // 25 x 8 rows = 200 >= 197
 constexpr int ATTN_SHARE_FAST = 0 + 16 * 8 + 256 * 8;  // K/V pieces of the next head requested by the computing waves (dma_head: a + 16 b + 256 c)
 constexpr int ATTN_SHARE_EXACT = 0 + 16 * 8 + 256 * 8;
@@ -72,23 +78,24 @@ __device__ __forceinline__ float other_half(float x) {
 // exponentials taken from key tile 0 (see there), guarded; the exact form re-runs a launch whose guard was raised.
 // run_if: when given, the whole launch returns at once unless *run_if != 0 (the conditional exact re-run).
 // share: K/V pieces of the next head the COMPUTING waves request (encoding: dma_head); the staging wave takes the rest
-template <int NB, bool STAMP, int PIPE>
+template <int NB, bool STAMP, int PIPE, int H>
 __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, const int nblk, const int hsplit,
                                           unsigned long long* stamps, const int dbg_arg, int* __restrict__ guard, const int share,
                                           const float guard_limit, const int only_block) {
     // ablation switches of the STAMPED build only (results invalid): 1 no K re-reads, 2 no K/V requests after the
     // first head, 4 no maximum, 8 no exponentials
     const int dbg = STAMP ? dbg_arg : 0;
+    constexpr int QKV_LD = AttnRows<H>::QKV_LD, D = AttnRows<H>::D;
     constexpr int TROWS = AttnGeom<NB>::TROWS, KV_BYTES = AttnGeom<NB>::KV_BYTES, BUF_BYTES = AttnGeom<NB>::BUF_BYTES;
     extern __shared__ __attribute__((aligned(16))) char lds[];  // NB x (K | V)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // A block = hpw = 12 / hsplit heads of one crop (hsplit blocks share a crop: small batches would otherwise leave
-    // most CUs idle and serialise 12 heads on one).  The workgroup is PERSISTENT: it walks the blocks blockIdx.x,
+    // A block = hpw = H / hsplit heads of one crop (hsplit blocks share a crop: small batches would otherwise leave
+    // most CUs idle and serialise H heads on one).  The workgroup is PERSISTENT: it walks the blocks blockIdx.x,
     // blockIdx.x + gridDim.x, ... as ONE stream of (crop, head) items, so that the K/V requests and the Q prefetch of
     // a crop's first head ride under the previous crop's last head -- one exposed memory latency per workgroup
     // instead of one per crop (16 per CU at 4096 crops: ~3 % of the launch).
-    const int hpw = VIT_H / hsplit;
+    const int hpw = H / hsplit;
     const int nloc = blockIdx.x < nblk ? (nblk - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
     const int n_items = nloc * hpw;
     if (n_items == 0) return;
@@ -130,7 +137,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
             const int row = pp * 8 + (lane >> 3);
             const int slot = lane & 7;
             const int chunk = isv ? (slot ^ (((row >> 1) & 1) << 2)) : (slot ^ ((row >> 1) & 7));
-            const char* src = hb + (size_t)min(row, VIT_T - 1) * QKV_LD + (isv ? 2 : 1) * VIT_D * 2 + chunk * 16;
+            const char* src = hb + (size_t)min(row, VIT_T - 1) * QKV_LD + (isv ? 2 : 1) * D * 2 + chunk * 16;
             // LDS-DMA through inline asm, so that hipcc does not know these loads write LDS: told through the builtin it
             // orders every later LDS read behind them with `s_waitcnt vmcnt(0)` -- in the middle of the head iteration,
             // where that also waits for the Q prefetch and the previous head's stores.  The ordering that is needed
@@ -438,7 +445,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks];
             }
             // o[db][4*rg + j] = O[q][32db + 8rg + 4hh + j]: pair the lane halves into 16-byte stores
-            bf16_t* op = out + ((size_t)b * VIT_T + min(q, VIT_T - 1)) * VIT_D + h * VIT_DH;
+            bf16_t* op = out + ((size_t)b * VIT_T + min(q, VIT_T - 1)) * D + h * VIT_DH;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -478,57 +485,86 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
 }
 
 // run_if: when given, the whole launch returns at once unless *run_if != 0 (the conditional exact re-run behind FAST)
-template <int NB, bool STAMP = false, int PIPE = 1>
+template <int NB, bool STAMP = false, int PIPE = 1, int H = VIT_H>
 __global__ __launch_bounds__(512, 2) void attn_fwd_t197(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int nblk, int hsplit,
                                                          unsigned long long* stamps = nullptr, int dbg_arg = 0, int* __restrict__ guard = nullptr,
                                                          int share = 0, const int* __restrict__ run_if = nullptr, float guard_limit = 1.2676506e30f,
                                                          int only_block = -1) {
     if (run_if && *(const volatile int*)run_if == 0) return;  // uniform: every wave of every workgroup takes the same way
-    attn_body<NB, STAMP, PIPE>(qkv, out, nblk, hsplit, stamps, dbg_arg, guard, share, guard_limit, only_block);
+    attn_body<NB, STAMP, PIPE, H>(qkv, out, nblk, hsplit, stamps, dbg_arg, guard, share, guard_limit, only_block);
 }
 
 }  // namespace
 
-hipError_t launch_attention(const void* qkv, void* out, int B, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
-    if (only_block < -1 || only_block > 6) return hipErrorInvalidValue;
-    if (B <= 0) return hipSuccess;
-    // blocks of 12 / hsplit heads: enough of them for every CU (one workgroup fits per CU: 112 KiB of LDS)
+namespace {
+
+template <int H>
+hipError_t launch_attention_heads(const void* qkv, void* out, int B, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
+    // blocks of H / hsplit heads: enough of them for every CU (one workgroup fits per CU: 112 KiB of LDS); the divisors of H
     int hsplit = 1;
-    for (int d : {1, 2, 3, 4, 6, 12}) {
+    for (int d = 1; d <= H; ++d) {
+        if (H % d) continue;
         hsplit = d;
         if (B * d >= 512) break;
     }
     const int nblk = B * hsplit, grid = nblk < 256 ? nblk : 256;  // persistent: one workgroup per CU walks its blocks
     const bool fast = guard != nullptr;
     const int share = (fast ? ATTN_SHARE_FAST : ATTN_SHARE_EXACT) | (reverse ? 1 << 17 : 0);
-    if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
+    if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, false, 1, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
     if (fast) {
         // FAST kernel, then the exact kernel on the same launch geometry, which returns at once unless a row of the fast
         // kernel left the range its reference point covers (*guard raised; guard is zeroed by the caller per pass)
-        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, false, 2>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, false, 2>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
+        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, false, 2, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
+        hipLaunchKernelGGL((attn_fwd_t197<2, false, 2, H>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
                            (unsigned long long*)nullptr, 0, guard, share, (const int*)nullptr, force_redo ? 0.5f : 1.2676506e30f, only_block);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
+        hipLaunchKernelGGL((attn_fwd_t197<2, false, 1, H>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
                            (unsigned long long*)nullptr, 0, (int*)nullptr, ATTN_SHARE_EXACT | (reverse ? 1 << 17 : 0), (const int*)guard, 1.2676506e30f, only_block);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((attn_fwd_t197<2>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
+    hipLaunchKernelGGL((attn_fwd_t197<2, false, 1, H>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
                        (unsigned long long*)nullptr, 0, (int*)nullptr, share, (const int*)nullptr, 1.2676506e30f, only_block);
     return hipGetLastError();
 }
 
+}  // namespace
+
+hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
+    if (only_block < -1 || only_block > 6) return hipErrorInvalidValue;
+    if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // no other instantiation, and no stand-in
+    if (B <= 0) return hipSuccess;
+    switch (heads) {
+        case 6: return launch_attention_heads<6>(qkv, out, B, s, guard, force_redo, only_block, reverse);
+        case 16: return launch_attention_heads<16>(qkv, out, B, s, guard, force_redo, only_block, reverse);
+        default: return launch_attention_heads<12>(qkv, out, B, s, guard, force_redo, only_block, reverse);
+    }
+}
+
 // diagnostic: the stamped build of the fast or the exact form (two buffers, one workgroup per crop); stamps = uint64[B][8 waves][8],
 // zeroed by the caller
-hipError_t launch_attention_stamped(const void* qkv, void* out, int B, bool fast, unsigned long long* stamps, hipStream_t s) {
-    const int dbg = diag_env("MME_ATTN_DEBUG") ? atoi(diag_env("MME_ATTN_DEBUG")) : 0;
-    if (B <= 0) return hipSuccess;
+namespace {
+
+template <int H>
+hipError_t launch_attention_stamped_heads(const void* qkv, void* out, int B, bool fast, unsigned long long* stamps, int dbg, hipStream_t s) {
     if (!fast) {
-        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, true>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_EXACT, (const int*)nullptr);
+        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true, 1, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
+        hipLaunchKernelGGL((attn_fwd_t197<2, true, 1, H>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_EXACT, (const int*)nullptr);
     } else {
-        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true, 2>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, true, 2>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_FAST, (const int*)nullptr);
+        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true, 2, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
+        hipLaunchKernelGGL((attn_fwd_t197<2, true, 2, H>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_FAST, (const int*)nullptr);
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_attention_stamped(const void* qkv, void* out, int B, int heads, bool fast, unsigned long long* stamps, hipStream_t s) {
+    const int dbg = diag_env("MME_ATTN_DEBUG") ? atoi(diag_env("MME_ATTN_DEBUG")) : 0;
+    if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;
+    if (B <= 0) return hipSuccess;
+    switch (heads) {
+        case 6: return launch_attention_stamped_heads<6>(qkv, out, B, fast, stamps, dbg, s);
+        case 16: return launch_attention_stamped_heads<16>(qkv, out, B, fast, stamps, dbg, s);
+        default: return launch_attention_stamped_heads<12>(qkv, out, B, fast, stamps, dbg, s);
+    }
 }

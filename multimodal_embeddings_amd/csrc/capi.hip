@@ -132,29 +132,66 @@ int upload_f32_cat(mme_ctx* c, const float* const* srcs, const size_t* n, int ns
 
 int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who) {
     if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
-    if (w->image_size != VIT_IMG || w->patch_size != VIT_PATCH || w->hidden != VIT_D || w->layers != VIT_L ||
-        w->heads != VIT_H || w->mlp != VIT_F)
-        return fail(c, MME_E_ARG, "%s: only ViT-B/16 @224 geometry (224/16/768/12/12/3072) is built; got %d/%d/%d/%d/%d/%d", who,
-                    w->image_size, w->patch_size, w->hidden, w->layers, w->heads, w->mlp);
+    // every refusal names the field, the value found and what is supported
+    if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
+    if (w->patch_size != VIT_PATCH) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: %d", who, w->patch_size, VIT_PATCH);
+    if (!vit_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 384, 768, 1024", who, w->hidden);
+    if (w->heads * VIT_DH != w->hidden)
+        return fail(c, MME_E_ARG, "%s: heads = %d at hidden = %d; supported: heads of %d, heads = hidden / %d = %d", who, w->heads, w->hidden, VIT_DH, VIT_DH,
+                    w->hidden / VIT_DH);
+    if (w->mlp < 64 || (w->mlp % 64) != 0 || w->mlp > VIT_MAX_F)
+        return fail(c, MME_E_ARG, "%s: mlp = %d; supported: multiples of 64 up to %d", who, w->mlp, VIT_MAX_F);
+    if (w->layers < 1 || w->layers > VIT_MAX_L) return fail(c, MME_E_ARG, "%s: layers = %d; supported: 1..%d", who, w->layers, VIT_MAX_L);
     if (!w->cls_token || !w->pos_emb || !w->patch_w || !w->patch_b || !w->lnf_g || !w->lnf_b || !w->layer)
         return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
-    if (c->loaded) return fail(c, MME_E_STATE, "%s: weights already loaded; create a new context", who);
+    for (int l = 0; l < w->layers; ++l) {
+        const mme_vit_layer& a = w->layer[l];
+        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+        for (const float* p : all)
+            if (!p) return fail(c, MME_E_ARG, "%s: layer %d has a null tensor pointer", who, l);
+    }
     return MME_OK;
 }
 
+int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->loaded = false;
+    if (c->vit_alloc_hi > c->vit_alloc_lo) {
+        HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
+        for (size_t i = c->vit_alloc_lo; i < c->vit_alloc_hi; ++i) (void)hipFree(c->allocs[i]);
+        c->allocs.erase(c->allocs.begin() + c->vit_alloc_lo, c->allocs.begin() + c->vit_alloc_hi);
+        c->alloc_bytes.erase(c->alloc_bytes.begin() + c->vit_alloc_lo, c->alloc_bytes.begin() + c->vit_alloc_hi);
+    }
+    c->vit_alloc_lo = c->vit_alloc_hi = c->allocs.size();
+    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp};
+    c->ln_eps = w->ln_eps;
+    c->layer.assign((size_t)w->layers, LayerDev{});
+    return MME_OK;
+}
+
+void end_vit_load(mme_ctx* c, bool ok) {
+    c->vit_alloc_hi = c->allocs.size();
+    c->loaded = ok;
+}
+
+// The workspace follows the chunk AND the geometry: a context that was reloaded with a wider encoder regrows it
+// (ensure() never shrinks a buffer, so going back to a narrower one keeps what is there).
 int ensure_workspace(mme_ctx* c) {
-    if (c->ws_chunk == c->chunk) return MME_OK;
+    const int D = c->geom.hidden, F = c->geom.mlp;
+    if (c->ws_chunk == c->chunk && c->ws_hidden == D && c->ws_mlp == F) return MME_OK;
     const size_t rows = (size_t)c->chunk * VIT_T;
     int r;
-    if ((r = ensure(c, c->x, rows * VIT_D * 2))) return r;
-    if ((r = ensure(c, c->hbuf, rows * VIT_D * 2))) return r;
-    if ((r = ensure(c, c->qkv, rows * 3 * VIT_D * 2))) return r;
-    if ((r = ensure(c, c->att, rows * VIT_D * 2))) return r;
-    if ((r = ensure(c, c->mlp, rows * VIT_F * 2))) return r;
+    if ((r = ensure(c, c->x, rows * D * 2))) return r;
+    if ((r = ensure(c, c->hbuf, rows * D * 2))) return r;
+    if ((r = ensure(c, c->qkv, rows * 3 * D * 2))) return r;
+    if ((r = ensure(c, c->att, rows * D * 2))) return r;
+    if ((r = ensure(c, c->mlp, rows * F * 2))) return r;
     if ((r = ensure(c, c->stats, rows * 2 * sizeof(float)))) return r;
-    if ((r = ensure(c, c->lnpart, rows * 2 * (VIT_D / 64) * sizeof(float)))) return r;
-    if ((r = ensure(c, c->attn_guard, 64 * sizeof(int)))) return r;
+    if ((r = ensure(c, c->lnpart, rows * 2 * (D / 64) * sizeof(float)))) return r;
+    if ((r = ensure(c, c->attn_guard, VIT_MAX_L * sizeof(int)))) return r;
     c->ws_chunk = c->chunk;
+    c->ws_hidden = D;
+    c->ws_mlp = F;
     return MME_OK;
 }
 
@@ -225,6 +262,12 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
 
 int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
     const int M = n * VIT_T;
+    const int D = c->geom.hidden, F = c->geom.mlp, NL = c->geom.layers;  // the geometry of the loaded weights
+    // The epilogues leave the LayerNorm partial planes from their interior-tile code only, and at a width that is no
+    // multiple of the 256-column tile (384) the last column tile of every row panel is no interior tile: its two slices
+    // would be missing.  There mode 2 takes mode 1's statistics pass over x, which sums in the same canonical order:
+    // the same bits, one more read of x per LayerNorm.
+    const bool planes = c->ln_mode == 2 && (D % 256) == 0;
     GemmArgs g{};
     // Zig-zag: consecutive kernels of the pass walk the rows in OPPOSITE directions, so a consumer starts on the rows its
     // producer wrote last -- what is still in the 256 MiB Infinity Cache of a 1.2-5 GB activation -- instead of on the rows
@@ -237,13 +280,13 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         g.A = patches;
         g.W = c->patch_w;
         g.M = n * VIT_NP;
-        g.N = VIT_D;
-        g.K = VIT_D;
+        g.N = D;
+        g.K = VIT_PATCH_DIM;
         g.bias = c->patch_b;
         g.pos = c->pos;
         g.out = c->x.p;
-        g.ldo = VIT_D;
-        if (c->ln_mode == 2) {  // the 256 x 256 kernel leaves the LayerNorm partial sums of the token rows it writes
+        g.ldo = D;
+        if (planes) {  // the 256 x 256 kernel leaves the LayerNorm partial sums of the token rows it writes
             g.ln_part = (float*)c->lnpart.p;
             g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
         }
@@ -252,62 +295,62 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     const GemmArgs patch_args = g;
     {
         Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, s));
+        HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, D, s));
     }
     // one guard word per layer for the attention kernel's fast form (attention.hip): zero = no row left its range (zeroed
     // in mode 0 too, so that mme_attention_redone reports this pass and not an earlier one)
-    HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, 64 * sizeof(int), s));
+    HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, VIT_MAX_L * sizeof(int), s));
     // LayerNorm statistics of the residual stream x for the GEMM that folds the LayerNorm in.  Mode 2: the GEMM
     // that WROTE x (EPI_BIAS_RES_STATS) left per-slice partial sums; finishing them reads 96 bytes per row
-    // instead of the 1536-byte row.  Rows of a ragged last row tile, launches that ran the 128 x 128 kernel and
+    // instead of the 1536-byte row (ViT-B/16).  Rows of a ragged last row tile, launches that ran the 128 x 128 kernel and
     // the first LayerNorm of the pass take the stand-alone kernel, which sums in the same canonical order.
     auto stats_from_x = [&](int64_t row0) -> int {
         Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, row0, M, VIT_D, c->ln_eps, (float*)c->stats.p, s));
+        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, row0, M, D, c->ln_eps, (float*)c->stats.p, s));
         return MME_OK;
     };
     auto stats_after = [&](const GemmArgs& producer) -> int {
-        if (c->ln_mode != 2 || !gemm_runs_256(producer, c->gemm_variant)) return stats_from_x(0);
+        if (!planes || !gemm_runs_256(producer, c->gemm_variant)) return stats_from_x(0);
         const int64_t interior = (int64_t)(M / 256) * 256;
         {
             Timed t(c, s, KC_LN);
-            HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, producer.ln_part_rows, interior, VIT_D, c->ln_eps, (float*)c->stats.p, s));
+            HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, producer.ln_part_rows, interior, D, c->ln_eps, (float*)c->stats.p, s));
         }
         return interior < M ? stats_from_x(interior) : MME_OK;
     };
-    const int res_epi = c->ln_mode == 2 ? EPI_BIAS_RES_STATS : EPI_BIAS_RES;
+    const int res_epi = planes ? EPI_BIAS_RES_STATS : EPI_BIAS_RES;
     int r;
-    if (c->ln_mode == 2 && gemm_runs_256(patch_args, c->gemm_variant)) {
+    if (planes && gemm_runs_256(patch_args, c->gemm_variant)) {
         // first LayerNorm of the pass: the patch-embed epilogue left the partial sums of every token row an INTERIOR tile
         // wrote (patch rows [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th
         // row) and the rows of the ragged last tile take the stand-alone kernel, same canonical order
         const int64_t interior = (int64_t)(patch_args.M / 256) * 256;                      // patch rows
         const int64_t t_int = interior ? interior - 1 + (interior - 1) / VIT_NP + 2 : 0;   // one past the last token row they map to
         Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, patch_args.ln_part_rows, t_int, VIT_D, c->ln_eps, (float*)c->stats.p, s));
-        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, 0, t_int, VIT_D, c->ln_eps, (float*)c->stats.p, s, VIT_T));  // [CLS] rows below t_int
-        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, t_int, M, VIT_D, c->ln_eps, (float*)c->stats.p, s));
+        HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, patch_args.ln_part_rows, t_int, D, c->ln_eps, (float*)c->stats.p, s));
+        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, 0, t_int, D, c->ln_eps, (float*)c->stats.p, s, VIT_T));  // [CLS] rows below t_int
+        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, t_int, M, D, c->ln_eps, (float*)c->stats.p, s));
     } else if (c->ln_mode != 0 && (r = stats_from_x(0))) {
         return r;
     }
-    for (int l = 0; l < VIT_L; ++l) {
+    for (int l = 0; l < NL; ++l) {
         const LayerDev& L = c->layer[l];
         if (c->ln_mode != 0) {  // LN1 folded into the QKV GEMM: x is read once, nothing normalised is written
             Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
-            g.A = c->x.p; g.W = L.qkv_wf; g.M = M; g.N = 3 * VIT_D; g.K = VIT_D;
-            g.bias = L.qkv_bf; g.colsum = L.qkv_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->qkv.p; g.ldo = 3 * VIT_D;
+            g.A = c->x.p; g.W = L.qkv_wf; g.M = M; g.N = 3 * D; g.K = D;
+            g.bias = L.qkv_bf; g.colsum = L.qkv_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->qkv.p; g.ldo = 3 * D;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(EPI_LN_BIAS, g, s, c->gemm_variant));
         } else {
             {
                 Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_layernorm(c->x.p, L.ln1_g, L.ln1_b, c->hbuf.p, M, c->ln_eps, s));
+                HIP_TRY(c, launch_layernorm(c->x.p, L.ln1_g, L.ln1_b, c->hbuf.p, M, D, c->ln_eps, s));
             }
             Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
-            g.A = c->hbuf.p; g.W = L.qkv_w; g.M = M; g.N = 3 * VIT_D; g.K = VIT_D;
-            g.bias = L.qkv_b; g.out = c->qkv.p; g.ldo = 3 * VIT_D;
+            g.A = c->hbuf.p; g.W = L.qkv_w; g.M = M; g.N = 3 * D; g.K = D;
+            g.bias = L.qkv_b; g.out = c->qkv.p; g.ldo = 3 * D;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(EPI_BIAS, g, s, c->gemm_variant));
         }
@@ -315,16 +358,16 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         // (K8 pools token `pool_token`), so the query block that holds it is the only one attended, and o_proj, LayerNorm,
         // fc1 and fc2 run on the n gathered rows instead of n x 197.  Same kernels, same per-row arithmetic: the
         // embeddings are bit-identical to the full pass (tests/test_gpu_parity.py).
-        const bool pruned = c->prune_last && l + 1 == VIT_L && c->ln_mode != 0;
+        const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0;
         {
             Timed t(c, s, KC_ATTN);
-            HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
+            HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
                                         pruned ? pool_token / 32 : -1, zigzag == 2 ? true : next_dir() != 0));
         }
         if (pruned) {
-            bf16_t* att_p = (bf16_t*)c->hbuf.p;          // [n, 768] gathered attention rows
-            bf16_t* x_p = att_p + (size_t)n * VIT_D;      // [n, 768] gathered residual rows (hbuf holds rows x 768: n x 197 of them)
-            const size_t rowb = (size_t)VIT_D * 2, pitch = (size_t)VIT_T * rowb;
+            bf16_t* att_p = (bf16_t*)c->hbuf.p;          // [n, D] gathered attention rows
+            bf16_t* x_p = att_p + (size_t)n * D;      // [n, D] gathered residual rows (hbuf holds rows x D: n x 197 of them)
+            const size_t rowb = (size_t)D * 2, pitch = (size_t)VIT_T * rowb;
             {
                 Timed t(c, s, KC_POOL);
                 HIP_TRY(c, hipMemcpy2DAsync(att_p, rowb, (const char*)c->att.p + (size_t)pool_token * rowb, pitch, rowb, n, hipMemcpyDeviceToDevice, s));
@@ -333,23 +376,23 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             {
                 Timed t(c, s, KC_GEMM);
                 g = GemmArgs{};
-                g.A = att_p; g.W = L.o_w; g.M = n; g.N = VIT_D; g.K = VIT_D;
-                g.bias = L.o_b; g.out = x_p; g.res = x_p; g.ldo = VIT_D;
+                g.A = att_p; g.W = L.o_w; g.M = n; g.N = D; g.K = D;
+                g.bias = L.o_b; g.out = x_p; g.res = x_p; g.ldo = D;
                 HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
             }
             {
                 Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_ln_stats_canonical(x_p, 0, n, VIT_D, c->ln_eps, (float*)c->stats.p, s));
+                HIP_TRY(c, launch_ln_stats_canonical(x_p, 0, n, D, c->ln_eps, (float*)c->stats.p, s));
             }
             {
                 Timed t(c, s, KC_GEMM);
                 g = GemmArgs{};
-                g.A = x_p; g.W = L.fc1_wf; g.M = n; g.N = VIT_F; g.K = VIT_D;
-                g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = VIT_F;
+                g.A = x_p; g.W = L.fc1_wf; g.M = n; g.N = F; g.K = D;
+                g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = F;
                 HIP_TRY(c, launch_gemm(EPI_LN_BIAS_GELU, g, s, c->gemm_variant));
                 g = GemmArgs{};
-                g.A = c->mlp.p; g.W = L.fc2_w; g.M = n; g.N = VIT_D; g.K = VIT_F;
-                g.bias = L.fc2_b; g.out = x_p; g.res = x_p; g.ldo = VIT_D;
+                g.A = c->mlp.p; g.W = L.fc2_w; g.M = n; g.N = D; g.K = F;
+                g.bias = L.fc2_b; g.out = x_p; g.res = x_p; g.ldo = D;
                 HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
             }
             {   // back into the residual stream, where the pooling kernel reads the row
@@ -361,8 +404,8 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         {
             Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
-            g.A = c->att.p; g.W = L.o_w; g.M = M; g.N = VIT_D; g.K = VIT_D;
-            g.bias = L.o_b; g.out = c->x.p; g.res = c->x.p; g.ldo = VIT_D;
+            g.A = c->att.p; g.W = L.o_w; g.M = M; g.N = D; g.K = D;
+            g.bias = L.o_b; g.out = c->x.p; g.res = c->x.p; g.ldo = D;
             g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(res_epi, g, s, c->gemm_variant));
@@ -371,28 +414,28 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             if ((r = stats_after(g))) return r;
             Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
-            g.A = c->x.p; g.W = L.fc1_wf; g.M = M; g.N = VIT_F; g.K = VIT_D;
-            g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = VIT_F;
+            g.A = c->x.p; g.W = L.fc1_wf; g.M = M; g.N = F; g.K = D;
+            g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = F;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(EPI_LN_BIAS_GELU, g, s, c->gemm_variant));
         } else {
             {
                 Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_layernorm(c->x.p, L.ln2_g, L.ln2_b, c->hbuf.p, M, c->ln_eps, s));
+                HIP_TRY(c, launch_layernorm(c->x.p, L.ln2_g, L.ln2_b, c->hbuf.p, M, D, c->ln_eps, s));
             }
             Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
-            g.A = c->hbuf.p; g.W = L.fc1_w; g.M = M; g.N = VIT_F; g.K = VIT_D;
-            g.bias = L.fc1_b; g.out = c->mlp.p; g.ldo = VIT_F;
+            g.A = c->hbuf.p; g.W = L.fc1_w; g.M = M; g.N = F; g.K = D;
+            g.bias = L.fc1_b; g.out = c->mlp.p; g.ldo = F;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(EPI_BIAS_GELU, g, s, c->gemm_variant));
         }
-        const bool last = l + 1 == VIT_L;  // the final LayerNorm touches the pooled row only (K8)
+        const bool last = l + 1 == NL;  // the final LayerNorm touches the pooled row only (K8)
         {
             Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
-            g.A = c->mlp.p; g.W = L.fc2_w; g.M = M; g.N = VIT_D; g.K = VIT_F;
-            g.bias = L.fc2_b; g.out = c->x.p; g.res = c->x.p; g.ldo = VIT_D;
+            g.A = c->mlp.p; g.W = L.fc2_w; g.M = M; g.N = D; g.K = F;
+            g.bias = L.fc2_b; g.out = c->x.p; g.res = c->x.p; g.ldo = D;
             g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(last ? EPI_BIAS_RES : res_epi, g, s, c->gemm_variant));
@@ -401,7 +444,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     }
     {
         Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, c->ln_eps, emb_f32, emb_bf16, s));
+        HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
     }
     return MME_OK;
 }
@@ -577,61 +620,74 @@ void mme_destroy(mme_ctx* c) {
 
 const char* mme_last_error(const mme_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 
+int mme_vit_geometry(mme_ctx* c, int32_t out[6]) {
+    if (!c || !out) return fail(c, MME_E_ARG, "mme_vit_geometry: null argument");
+    const int32_t g[6] = {VIT_IMG, VIT_PATCH, c->geom.hidden, c->geom.layers, c->geom.heads, c->geom.mlp};
+    for (int i = 0; i < 6; ++i) out[i] = g[i];
+    return MME_OK;
+}
+
+static int load_vit_host(mme_ctx* c, const mme_vit_weights* w);
+
 int mme_load_vit(mme_ctx* c, const mme_vit_weights* w) {
     int r;
     if ((r = validate_vit_weights(c, w, "mme_load_vit"))) return r;
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->ln_eps = w->ln_eps;
-    if ((r = upload_f32(c, w->cls_token, VIT_D, &c->cls))) return r;
-    if ((r = upload_f32(c, w->pos_emb, (size_t)VIT_T * VIT_D, &c->pos))) return r;
-    if ((r = upload_f32(c, w->patch_b, VIT_D, &c->patch_b))) return r;
-    if ((r = upload_f32(c, w->lnf_g, VIT_D, &c->lnf_g))) return r;
-    if ((r = upload_f32(c, w->lnf_b, VIT_D, &c->lnf_b))) return r;
+    if ((r = begin_vit_load(c, w))) return r;
+    r = load_vit_host(c, w);
+    end_vit_load(c, r == MME_OK);
+    return r;
+}
+
+// the host loops of mme_load_vit (f32 in, converted / scaled / folded on the CPU, one upload per buffer)
+static int load_vit_host(mme_ctx* c, const mme_vit_weights* w) {
+    int r;
+    const size_t D = (size_t)w->hidden, F = (size_t)w->mlp;
+    if ((r = upload_f32(c, w->cls_token, D, &c->cls))) return r;
+    if ((r = upload_f32(c, w->pos_emb, (size_t)VIT_T * D, &c->pos))) return r;
+    if ((r = upload_f32(c, w->patch_b, D, &c->patch_b))) return r;
+    if ((r = upload_f32(c, w->lnf_g, D, &c->lnf_g))) return r;
+    if ((r = upload_f32(c, w->lnf_b, D, &c->lnf_b))) return r;
     {
         const float* s[1] = {w->patch_w};
-        const size_t rows[1] = {VIT_D};
-        if ((r = upload_bf16(c, s, rows, 1, VIT_D, &c->patch_w))) return r;
+        const size_t rows[1] = {D};
+        if ((r = upload_bf16(c, s, rows, 1, VIT_PATCH_DIM, &c->patch_w))) return r;
     }
-    for (int l = 0; l < VIT_L; ++l) {
+    for (int l = 0; l < w->layers; ++l) {
         const mme_vit_layer& a = w->layer[l];
-        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
-        for (const float* p : all)
-            if (!p) return fail(c, MME_E_ARG, "mme_load_vit: layer %d has a null tensor pointer", l);
         LayerDev& L = c->layer[l];
-        if ((r = upload_f32(c, a.ln1_g, VIT_D, &L.ln1_g))) return r;
-        if ((r = upload_f32(c, a.ln1_b, VIT_D, &L.ln1_b))) return r;
-        if ((r = upload_f32(c, a.ln2_g, VIT_D, &L.ln2_g))) return r;
-        if ((r = upload_f32(c, a.ln2_b, VIT_D, &L.ln2_b))) return r;
+        if ((r = upload_f32(c, a.ln1_g, D, &L.ln1_g))) return r;
+        if ((r = upload_f32(c, a.ln1_b, D, &L.ln1_b))) return r;
+        if ((r = upload_f32(c, a.ln2_g, D, &L.ln2_g))) return r;
+        if ((r = upload_f32(c, a.ln2_b, D, &L.ln2_b))) return r;
         // The attention kernel takes its scores in log2 units straight from the matrix pipe (attention.hip, PRESCALED):
         // dh^-0.5 * log2(e) is folded into the query projection here, once, BEFORE the rounding to bf16 that the upload
         // applies anyway -- softmax(q.k / 8) = exp2(q'.k - c) / sum with q' = (W_q' x + b_q'), W_q' = sc W_q, b_q' = sc b_q.
         const float sc = 0.125f * 1.44269504088896341f;
-        std::vector<float> qw_s((size_t)VIT_D * VIT_D), qb_s(VIT_D);
+        std::vector<float> qw_s((size_t)D * D), qb_s(D);
         for (size_t i = 0; i < qw_s.size(); ++i) qw_s[i] = a.q_w[i] * sc;
-        for (int i = 0; i < VIT_D; ++i) qb_s[i] = a.q_b[i] * sc;
+        for (size_t i = 0; i < D; ++i) qb_s[i] = a.q_b[i] * sc;
         const float* qkv[3] = {qw_s.data(), a.k_w, a.v_w};
-        const size_t r3[3] = {VIT_D, VIT_D, VIT_D};
-        if ((r = upload_bf16(c, qkv, r3, 3, VIT_D, &L.qkv_w))) return r;
+        const size_t r3[3] = {D, D, D};
+        if ((r = upload_bf16(c, qkv, r3, 3, D, &L.qkv_w))) return r;
         const float* qkvb[3] = {qb_s.data(), a.k_b, a.v_b};
         if ((r = upload_f32_cat(c, qkvb, r3, 3, &L.qkv_b))) return r;
-        if ((r = upload_folded(c, qkv, qkvb, r3, 3, VIT_D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
+        if ((r = upload_folded(c, qkv, qkvb, r3, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
         const float* o[1] = {a.o_w};
-        const size_t r1[1] = {VIT_D};
-        if ((r = upload_bf16(c, o, r1, 1, VIT_D, &L.o_w))) return r;
-        if ((r = upload_f32(c, a.o_b, VIT_D, &L.o_b))) return r;
+        const size_t r1[1] = {D};
+        if ((r = upload_bf16(c, o, r1, 1, D, &L.o_w))) return r;
+        if ((r = upload_f32(c, a.o_b, D, &L.o_b))) return r;
         const float* f1[1] = {a.fc1_w};
-        const size_t rf1[1] = {VIT_F};
-        if ((r = upload_bf16(c, f1, rf1, 1, VIT_D, &L.fc1_w))) return r;
-        if ((r = upload_f32(c, a.fc1_b, VIT_F, &L.fc1_b))) return r;
+        const size_t rf1[1] = {F};
+        if ((r = upload_bf16(c, f1, rf1, 1, D, &L.fc1_w))) return r;
+        if ((r = upload_f32(c, a.fc1_b, F, &L.fc1_b))) return r;
         {
             const float* f1b[1] = {a.fc1_b};
-            if ((r = upload_folded(c, f1, f1b, rf1, 1, VIT_D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf))) return r;
+            if ((r = upload_folded(c, f1, f1b, rf1, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf))) return r;
         }
         const float* f2[1] = {a.fc2_w};
-        if ((r = upload_bf16(c, f2, r1, 1, VIT_F, &L.fc2_w))) return r;
-        if ((r = upload_f32(c, a.fc2_b, VIT_D, &L.fc2_b))) return r;
+        if ((r = upload_bf16(c, f2, r1, 1, F, &L.fc2_w))) return r;
+        if ((r = upload_f32(c, a.fc2_b, D, &L.fc2_b))) return r;
     }
-    c->loaded = true;
     return MME_OK;
 }
 
@@ -667,11 +723,12 @@ int mme_set_attention_mode(mme_ctx* c, int mode) {
 
 int mme_attention_redone(mme_ctx* c, int32_t flags[12]) {
     if (!c || !flags) return fail(c, MME_E_ARG, "mme_attention_redone: null argument");
-    for (int l = 0; l < VIT_L; ++l) flags[l] = 0;
+    const int nl = c->geom.layers < 12 ? c->geom.layers : 12;  // the first min(12, layers) words; mme_attention_redone_n for more
+    for (int l = 0; l < nl; ++l) flags[l] = 0;
     if (!c->attn_guard.p) return MME_OK;  // no pass has run yet
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(flags, c->attn_guard.p, VIT_L * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(flags, c->attn_guard.p, nl * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MME_OK;
 }
 
@@ -690,7 +747,7 @@ int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const 
                         uint16_t* out, int32_t* redone, void* stream) {
     if (!c) return MME_E_ARG;
     if (!qkv || !out || !redone) return fail(c, MME_E_ARG, "mme_attention_apply: null argument");
-    if (kind != 0 && kind != 1) return fail(c, MME_E_ARG, "mme_attention_apply: kind %d (0 = ViT-B/16, 1 = tile-ViT)", kind);
+    if (kind != 0 && kind != 1) return fail(c, MME_E_ARG, "mme_attention_apply: kind %d (0 = ViT/16 at the context's geometry, 1 = tile-ViT)", kind);
     const int n_max = kind == 0 ? 1 << 20 : 4096;
     if (n <= 0 || n > n_max) return fail(c, MME_E_ARG, "mme_attention_apply: n = %d outside 1..%d", n, n_max);
     if (kind == 0) {
@@ -710,7 +767,7 @@ int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const 
     int32_t* nt_dev = (int32_t*)c->attn_apply.p + 16;
     HIP_TRY(c, hipMemsetAsync(guard, 0, sizeof(int), s));
     if (kind == 0) {
-        HIP_TRY(c, launch_attention(qkv, out, n, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2, only_block, reverse != 0));
+        HIP_TRY(c, launch_attention(qkv, out, n, c->geom.heads, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2, only_block, reverse != 0));
     } else {
         HIP_TRY(c, hipMemcpyAsync(nt_dev, ntiles_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(c, launch_attention_tiles(qkv, out, nt_dev, n, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2));
@@ -752,7 +809,7 @@ int mme_preprocess(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const in
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
         if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));
-        int r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_D, s);
+        int r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_PATCH_DIM, s);
         if (r) return r;
     }
     return MME_OK;
@@ -770,9 +827,9 @@ int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, 
     hipStream_t s = (hipStream_t)stream;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_D, m, pool_token,
-                          emb_f32 ? emb_f32 + (size_t)s0 * VIT_D : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * VIT_D : nullptr, s);
+        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_PATCH_DIM, m, pool_token,
+                          emb_f32 ? emb_f32 + (size_t)s0 * c->geom.hidden : nullptr,
+                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * c->geom.hidden : nullptr, s);
         if (r) return r;
     }
     return MME_OK;
@@ -788,15 +845,15 @@ int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t
     HIP_TRY(c, hipSetDevice(c->device));
     int r = ensure_workspace(c);
     if (r) return r;
-    if ((r = ensure(c, c->patches, (size_t)c->chunk * VIT_NP * VIT_D * 2))) return r;
+    if ((r = ensure(c, c->patches, (size_t)c->chunk * VIT_NP * VIT_PATCH_DIM * 2))) return r;
     hipStream_t s = (hipStream_t)stream;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
         if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));  // crop tables are reused per chunk
         r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)c->patches.p, s);
         if (r) return r;
-        r = forward_chunk(c, (const bf16_t*)c->patches.p, m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * VIT_D : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * VIT_D : nullptr, s);
+        r = forward_chunk(c, (const bf16_t*)c->patches.p, m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * c->geom.hidden : nullptr,
+                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * c->geom.hidden : nullptr, s);
         if (r) return r;
     }
     return MME_OK;
@@ -1356,7 +1413,7 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
     if (!a) return fail(c, MME_E_ARG, "mme_rowop_apply: null argument");
     if (op < 0 || op > 5) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d outside 0..5", op);
     const bool fixed_d = op == 0 || op == 1 || op == 4 || op == 5;
-    if (fixed_d && a->d != VIT_D) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d is built for d == %d (d = %d)", op, VIT_D, a->d);
+    if (fixed_d && !vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
     if (!fixed_d && (a->d <= 0 || (a->d % 64) != 0 || a->d > 2048)) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d needs d %% 64 == 0, d <= 2048 (d = %d)", op, a->d);
     auto vec = [](const void* p) { return p && aligned_to(p, 16); };
     const bool stats_ok = a->stats && aligned_to(a->stats, 8);
@@ -1395,12 +1452,12 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     switch (op) {
-        case 0: HIP_TRY(c, launch_layernorm(a->x, a->gamma, a->beta, a->y, a->rows, a->eps, s)); break;
-        case 1: HIP_TRY(c, launch_ln_stats(a->x, a->rows, a->eps, a->stats, s)); break;
+        case 0: HIP_TRY(c, launch_layernorm(a->x, a->gamma, a->beta, a->y, a->rows, a->d, a->eps, s)); break;
+        case 1: HIP_TRY(c, launch_ln_stats(a->x, a->rows, a->d, a->eps, a->stats, s)); break;
         case 2: HIP_TRY(c, launch_ln_stats_canonical(a->x, a->row0, a->row1, a->d, a->eps, a->stats, s, a->stride)); break;
         case 3: HIP_TRY(c, launch_ln_finish(a->part, a->part_rows, a->rows, a->d, a->eps, a->stats, s)); break;
-        case 4: HIP_TRY(c, launch_cls_rows(a->x, a->cls, a->pos, a->B, s)); break;
-        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, a->tok, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+        case 4: HIP_TRY(c, launch_cls_rows(a->x, a->cls, a->pos, a->B, a->d, s)); break;
+        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
@@ -1455,7 +1512,8 @@ int mme_allgather(mme_ctx* c, void* comm, const uint16_t* shard, int64_t rows, i
 int mme_attention_stamps(mme_ctx* c, int B, int iters, double* avg_ms, uint64_t* stamps_host) {
     if (!c || !avg_ms || !stamps_host || B <= 0 || iters < 1) return fail(c, MME_E_ARG, "mme_attention_stamps: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t rows = (size_t)B * VIT_T, q_bytes = rows * 3 * VIT_D * 2, o_bytes = rows * VIT_D * 2, st_bytes = (size_t)B * 64 * sizeof(uint64_t);
+    const int heads = c->geom.heads;
+    const size_t D = (size_t)c->geom.hidden, rows = (size_t)B * VIT_T, q_bytes = rows * 3 * D * 2, o_bytes = rows * D * 2, st_bytes = (size_t)B * 64 * sizeof(uint64_t);
     void *Q = nullptr, *O = nullptr, *ST = nullptr, *G = nullptr;
     int rc = MME_OK;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1476,17 +1534,17 @@ int mme_attention_stamps(mme_ctx* c, int B, int iters, double* avg_ms, uint64_t*
         }
         hipStream_t s = nullptr;
         int* guard = c->attn_mode ? (int*)G : nullptr;  // mode 0: the exact kernel alone
-        if (launch_attention(Q, O, B, s, guard, c->attn_mode == 2) != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: launch"); break; }
+        if (launch_attention(Q, O, B, heads, s, guard, c->attn_mode == 2) != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: launch"); break; }
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, s);
-        for (int i = 0; i < iters; ++i) (void)launch_attention(Q, O, B, s, guard, c->attn_mode == 2);
+        for (int i = 0; i < iters; ++i) (void)launch_attention(Q, O, B, heads, s, guard, c->attn_mode == 2);
         (void)hipEventRecord(e1, s);
         if (hipEventSynchronize(e1) != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: kernel failed"); break; }
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         *avg_ms = ms / iters;
         (void)hipMemset(ST, 0, st_bytes);
-        if (launch_attention_stamped(Q, O, B, guard != nullptr, (unsigned long long*)ST, s) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: stamped launch"); break; }
+        if (launch_attention_stamped(Q, O, B, heads, guard != nullptr, (unsigned long long*)ST, s) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { rc = fail(c, MME_E_HIP, "mme_attention_stamps: stamped launch"); break; }
         (void)hipMemcpy(stamps_host, ST, st_bytes, hipMemcpyDeviceToHost);
     } while (0);
     if (e0) (void)hipEventDestroy(e0);

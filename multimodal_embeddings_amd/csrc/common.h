@@ -25,8 +25,11 @@ static inline const char* diag_env(const char*) { return nullptr; }
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 
-// ViT-B/16 @224 geometry (BASELINE.json north_star); fixed at compile time so every
-// index computation folds to constants.
+// ViT/16 @224 geometry.  What every supported encoder shares is fixed at compile time, so that the index computations
+// of the attention kernel, the patch emitter and the patch-embed epilogue fold to constants: 197 tokens of 16 x 16
+// patches, heads of 64.  Width, depth, head count and MLP size belong to the weights a context was loaded with
+// (ctx.h, VitGeom); the row kernels and the attention kernel are instantiated per supported width (384, 768, 1024 =
+// 6, 12, 16 heads).  VIT_D / VIT_H / VIT_F / VIT_L are ViT-B/16, the geometry of a context before any load.
 constexpr int VIT_D = 768;
 constexpr int VIT_T = 197;
 constexpr int VIT_NP = 196;
@@ -37,6 +40,11 @@ constexpr int VIT_L = 12;
 constexpr int VIT_GRID = 14;
 constexpr int VIT_PATCH = 16;
 constexpr int VIT_IMG = 224;
+constexpr int VIT_PATCH_DIM = 3 * VIT_PATCH * VIT_PATCH;  // im2col row of one patch: K of the patch-embed GEMM (768 at every width)
+constexpr int VIT_MAX_L = 64;                             // the guard-word table of a pass (ctx.h, attn_guard)
+constexpr int VIT_MAX_F = 8192;
+// the widths the row kernels and the attention kernel are instantiated for
+constexpr bool vit_width_built(int d) { return d == 384 || d == 768 || d == 1024; }
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 

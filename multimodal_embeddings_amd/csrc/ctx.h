@@ -25,6 +25,13 @@ struct LayerDev {
     float *qkv_cs, *qkv_bf, *fc1_cs, *fc1_bf;
 };
 
+// The ViT/16 @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
+// Supported set (validate_vit_weights): image 224, patch 16, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
+// <= 8192, 1..64 layers.
+struct VitGeom {
+    int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
+};
+
 enum KClass { KC_PRE = 0, KC_GEMM = 1, KC_LN = 2, KC_ATTN = 3, KC_POOL = 4, KC_COS = 5, KC_PAGE = 6, KC_CLUSTER = 7, KC_NEIGH = 8, KC_COMM = 9 };
 
 struct EventPair {
@@ -46,13 +53,15 @@ struct mme_ctx {
     // weights
     std::vector<void*> allocs;
     std::vector<size_t> alloc_bytes;  // size of allocs[i] (mme_weights_fingerprint)
+    size_t vit_alloc_lo = 0, vit_alloc_hi = 0;  // allocs[lo, hi): the ViT weights (a second mme_load_vit* frees exactly these)
+    VitGeom geom;
     float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
     bf16_t* patch_w = nullptr;
-    LayerDev layer[VIT_L];
+    std::vector<LayerDev> layer;  // geom.layers of them
     float* lut = nullptr;  // [3,256]
     NormAffine norm_aff{};  // the same mapping as one fma per value where that is bit-exact after the bf16 rounding (set_lut)
     // workspace (sized for `chunk` crops)
-    int ws_chunk = 0;
+    int ws_chunk = 0, ws_hidden = 0, ws_mlp = 0;  // what the workspace below was sized for
     DevBuf attn_guard;      // int[64]: one guard word per layer of a pass (attention.hip, FAST form)
     DevBuf attn_apply;      // mme_attention_apply: its own guard word (int 0), the tile counts from int 16 on
     bool prune_last = false;  // mme_set_forward_pruning
@@ -87,8 +96,14 @@ int upload_bf16(mme_ctx* c, const float* const* srcs, const size_t* rows, int ns
 int upload_folded(mme_ctx* c, const float* const* ws, const float* const* bs, const size_t* rows, int nsrc, size_t cols, const float* gamma,
                   const float* beta, bf16_t** wf, float** cs, float** bf);
 void tile_vit_free(mme_ctx* c);
-// argument checks shared by mme_load_vit and mme_load_vit_as (`who` names the f32 loader in the messages of both)
+// argument checks shared by mme_load_vit and mme_load_vit_as (`who` names the f32 loader in the messages of both): the
+// geometry against the supported set, every tensor pointer.  Touches nothing in the context but its error text.
 int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who);
+// A load replaces what the context held: begin frees the previous ViT weights (after the device has drained), takes the
+// new geometry and leaves the context unloaded; end marks the buffers allocated since as the ViT weights and, when
+// `ok`, the context as loaded.  A load that fails in between leaves the context without weights.
+int begin_vit_load(mme_ctx* c, const mme_vit_weights* w);
+void end_vit_load(mme_ctx* c, bool ok);
 
 // ---- device-side weight preparation (weight_prep.hip): the upload_* helpers above, from staged device bytes of `dt` ----
 // hipMalloc registered in c->allocs / c->alloc_bytes

@@ -57,10 +57,11 @@ hipError_t launch_gemm(int epilogue, const GemmArgs& g, hipStream_t s, int varia
 // diagnostic: stamped build of the 3-deep-ring 256x256 kernel (bias epilogue), stamps uint64[256 * 2 * 16]
 hipError_t launch_gemm256r_stamped(const GemmArgs& g, unsigned long long* stamps, hipStream_t s);
 
-// LayerNorm over rows of 768 bf16 (f32 statistics), bf16 out.
-hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, float eps, hipStream_t s);
-// per-row LayerNorm statistics of bf16 rows of 768: stats[row] = (mean, rstd)
-hipError_t launch_ln_stats(const void* x, int64_t rows, float eps, float* stats, hipStream_t s);
+// LayerNorm over bf16 rows of d (f32 statistics), bf16 out.  d: a width the row kernels are instantiated for (384, 768,
+// 1024; common.h vit_width_built), as for launch_ln_stats, launch_cls_rows and launch_pool; else hipErrorInvalidValue
+hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, float eps, hipStream_t s);
+// per-row LayerNorm statistics of bf16 rows of d: stats[row] = (mean, rstd)
+hipError_t launch_ln_stats(const void* x, int64_t rows, int d, float eps, float* stats, hipStream_t s);
 // the same statistics in the CANONICAL summation order shared with the EPI_BIAS_RES_STATS epilogue, for rows
 // [row0, row1) of bf16 rows of `d` (d % 64 == 0, d <= 2048): one pass over x
 // rows row0, row0 + stride, ... < row1
@@ -69,22 +70,23 @@ hipError_t launch_ln_stats_canonical(const void* x, int64_t row0, int64_t row1, 
 hipError_t launch_ln_finish(const float* part, int64_t part_rows, int64_t rows, int d, float eps, float* stats, hipStream_t s);
 // true when launch_gemm(variant) runs the 256 x 256 kernel (whose fast-path epilogue writes the partial planes)
 bool gemm_runs_256(const GemmArgs& g, int variant);
-// x[b*197 + 0, :] = bf16(cls + pos[0])
-hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, hipStream_t s);
-// final LayerNorm on row b*197+tok, L2 normalise, write f32 and/or bf16
-hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tok, float eps,
+// x[b*197 + 0, :] = bf16(cls + pos[0]), rows of d
+hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, int d, hipStream_t s);
+// final LayerNorm on row b*197+tok of d values, L2 normalise, write f32 and/or bf16 [B, d]
+hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps,
                        float* emb_f32, void* emb_bf16, hipStream_t s);
 // f32 [rows,d] -> L2-normalised bf16 [rows,d]
 hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, hipStream_t s);
-// fused multi-head attention, T=197, dh=64, 12 heads; qkv [B*197, 2304] -> out [B*197, 768]
+// fused multi-head attention, T=197, dh=64, `heads` = 6, 12 or 16 (one instantiation each; anything else is
+// hipErrorInvalidValue); qkv [B*197, 3*64*heads] -> out [B*197, 64*heads]
 // guard: device int, zero before the launch; non-null selects the FAST kernel + the conditional exact re-run (attention.hip)
 // force_redo: the fast kernel raises the guard for every row (test of the re-run path)
 // only_block >= 0: compute and store that query block of 32 only (0..6)
 // reverse: walk the crops from the last one down (same results; zig-zag order of consecutive kernels, forward_chunk)
-hipError_t launch_attention(const void* qkv, void* out, int B, hipStream_t s, int* guard = nullptr, bool force_redo = false, int only_block = -1,
-                            bool reverse = false);
+hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard = nullptr, bool force_redo = false,
+                            int only_block = -1, bool reverse = false);
 // diagnostic: stamped build of the fast or the exact form, stamps uint64[B][8][8]
-hipError_t launch_attention_stamped(const void* qkv, void* out, int B, bool fast, unsigned long long* stamps, hipStream_t s);
+hipError_t launch_attention_stamped(const void* qkv, void* out, int B, int heads, bool fast, unsigned long long* stamps, hipStream_t s);
 
 struct CropDesc {  // one per crop, built on the host by capi
     int64_t src_off;   // byte offset into pix

@@ -400,7 +400,7 @@ __global__ __launch_bounds__(RESIZE ? 512 : 256, RESIZE ? 8 : 1) void resize_v_p
     }
     __syncthreads();
     // 14 patches x 768 values (im2col order (c, ky, kx))
-    bf16_t* out = patches + ((int64_t)crop * VIT_NP + py * VIT_GRID) * VIT_D;
+    bf16_t* out = patches + ((int64_t)crop * VIT_NP + py * VIT_GRID) * VIT_PATCH_DIM;
     if (affine) {
         // A thread emits 8 consecutive kx of one (patch, ky) for ALL three channels: 24 contiguous canvas bytes (8-byte
         // aligned: (16 px + 8 half) * 3) as three 8-byte LDS reads, every byte converted in place (v_cvt_f32_ubyteN) and
@@ -422,19 +422,19 @@ __global__ __launch_bounds__(RESIZE ? 512 : 256, RESIZE ? 8 : 1) void resize_v_p
                     o[ch][j] = (bf16_t)fmaf(v, aff.a[ch], aff.b[ch]);
                 }
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) *(bf16x8*)(out + (int64_t)px * VIT_D + ch * 256 + ky * 16 + kx0) = o[ch];
+            for (int ch = 0; ch < 3; ++ch) *(bf16x8*)(out + (int64_t)px * VIT_PATCH_DIM + ch * 256 + ky * 16 + kx0) = o[ch];
         }
         return;
     }
     // table form: a thread emits 8 consecutive kx of one (patch, c, ky)
-    for (int e = tid; e < VIT_GRID * VIT_D / 8; e += NT) {
-        const int px = e / (VIT_D / 8), q = e - px * (VIT_D / 8);
+    for (int e = tid; e < VIT_GRID * VIT_PATCH_DIM / 8; e += NT) {
+        const int px = e / (VIT_PATCH_DIM / 8), q = e - px * (VIT_PATCH_DIM / 8);
         const int ch = q >> 5, ky = (q >> 1) & 15, kx0 = (q & 1) * 8;
         const uint8_t* cp = canvas + ky * ROW + (px * VIT_PATCH + kx0) * 3 + ch;
         bf16x8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (bf16_t)slut[ch * 256 + cp[j * 3]];
-        *(bf16x8*)(out + (int64_t)px * VIT_D + q * 8) = o;
+        *(bf16x8*)(out + (int64_t)px * VIT_PATCH_DIM + q * 8) = o;
     }
 }
 

@@ -1,80 +1,98 @@
 // Row-wise HBM-bound kernels of the ViT forward: LayerNorm (K3), [CLS] row initialisation,
 // and final-LayerNorm + pooling + L2 normalisation (K8).
 //
-// One 64-lane wave owns one 768-wide row: 3 x 8-byte (bf16x4) loads per lane, statistics
+// One 64-lane wave owns one D-wide row: 3 x 8-byte (bf16x4) loads per lane at D = 768, statistics
 // in f32 registers, two wave reductions (mean, then centred variance -- the same two-pass
 // form torch's LayerNorm uses, transformers modeling_vit.py:261-262,348), 8-byte stores.
+// Instantiated per supported width (RowShape): 768 = 3 x 4 values per lane (the ViT-B/16 code as it always was),
+// 1024 = 4 x 4, 384 = 3 x 2 (4-byte accesses: 384 is no multiple of the 256 values a wave covers with 8-byte ones).
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace {
 
+// a row of D values over 64 lanes: NT accesses of V consecutive values per lane, access t at column t * 64 V + lane * V
+template <int D> struct RowShape {
+    static_assert(D == 384 || D == 768 || D == 1024, "row kernels: widths 384, 768 and 1024");
+    static constexpr int V = (D % 256) == 0 ? 4 : 2;
+    static constexpr int NT = D / (64 * V);
+    static constexpr int PER_LANE = D / 64;
+    typedef __attribute__((ext_vector_type(V))) __bf16 bvec;
+    typedef __attribute__((ext_vector_type(V))) float fvec;
+};
+
+template <int D>
 __global__ __launch_bounds__(256) void layernorm_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, bf16_t* __restrict__ y,
                                                       int64_t rows, float eps) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const bf16_t* xr = x + row * VIT_D;
-    float v[12];
+    const bf16_t* xr = x + row * D;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
+    float v[NV];
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const bf16x4 p = *(const bf16x4*)(xr + t * 256 + lane * 4);
+    for (int t = 0; t < NT; ++t) {
+        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[t * 4 + j] = (float)p[j];
+        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
     }
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / VIT_D);
+    for (int j = 0; j < NV; ++j) s += v[j];
+    const float mean = wave_sum(s) * (1.0f / D);
     float q = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
+    for (int j = 0; j < NV; ++j) {
         v[j] -= mean;
         q += v[j] * v[j];
     }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / VIT_D) + eps);
-    bf16_t* yr = y + row * VIT_D;
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+    bf16_t* yr = y + row * D;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const int c = t * 256 + lane * 4;
-        const f32x4 gv = *(const f32x4*)(gamma + c);
-        const f32x4 bv = *(const f32x4*)(beta + c);
-        bf16x4 o;
+    for (int t = 0; t < NT; ++t) {
+        const int c = t * 64 * V + lane * V;
+        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
+        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
+        typename RS::bvec o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16_t)(v[t * 4 + j] * rstd * gv[j] + bv[j]);
-        *(bf16x4*)(yr + c) = o;
+        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(v[t * V + j] * rstd * gv[j] + bv[j]);
+        *(typename RS::bvec*)(yr + c) = o;
     }
 }
 
-// LayerNorm statistics only (mean, rstd) of bf16 rows of 768: the normalisation itself is
+// LayerNorm statistics only (mean, rstd) of bf16 rows of D: the normalisation itself is
 // folded into the GEMM that consumes the row (EPI_LN_*), so the residual stream is read once
 // and nothing is written back but 8 bytes per row.  Same two-pass f32 arithmetic as
 // layernorm_rows, so the folded path sees the statistics LayerNorm would have used.
+template <int D>
 __global__ __launch_bounds__(256) void ln_stats_rows(const bf16_t* __restrict__ x, int64_t rows, float eps, float* __restrict__ stats) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const bf16_t* xr = x + row * VIT_D;
-    float v[12];
+    const bf16_t* xr = x + row * D;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
+    float v[NV];
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const bf16x4 p = *(const bf16x4*)(xr + t * 256 + lane * 4);
+    for (int t = 0; t < NT; ++t) {
+        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[t * 4 + j] = (float)p[j];
+        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
     }
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / VIT_D);
+    for (int j = 0; j < NV; ++j) s += v[j];
+    const float mean = wave_sum(s) * (1.0f / D);
     float q = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
+    for (int j = 0; j < NV; ++j) {
         const float d = v[j] - mean;
         q += d * d;
     }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / VIT_D) + eps);
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
     if (lane == 0) *(float2*)(stats + 2 * row) = make_float2(mean, rstd);
 }
 
@@ -128,78 +146,84 @@ __global__ __launch_bounds__(256) void ln_finish_rows(const float* __restrict__ 
     *(float2*)(stats + 2 * row) = ln_finish_row(S, Q, d, eps);
 }
 
+template <int D>
 __global__ __launch_bounds__(256) void cls_rows(bf16_t* __restrict__ x, const float* __restrict__ cls,
                                                 const float* __restrict__ pos, int B) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
-    bf16_t* xr = x + (int64_t)b * VIT_T * VIT_D;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT;
+    bf16_t* xr = x + (int64_t)b * VIT_T * D;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const int c = t * 256 + lane * 4;
-        const f32x4 a = *(const f32x4*)(cls + c);
-        const f32x4 p = *(const f32x4*)(pos + c);
-        bf16x4 o;
+    for (int t = 0; t < NT; ++t) {
+        const int c = t * 64 * V + lane * V;
+        const typename RS::fvec a = *(const typename RS::fvec*)(cls + c);
+        const typename RS::fvec p = *(const typename RS::fvec*)(pos + c);
+        typename RS::bvec o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16_t)(a[j] + p[j]);
-        *(bf16x4*)(xr + c) = o;
+        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(a[j] + p[j]);
+        *(typename RS::bvec*)(xr + c) = o;
     }
 }
 
 // K8: restates last_pooling (deprecated_package/embedder.py:17-34) for one fixed token
 // index per sequence, after the final LayerNorm of that row only (the other 196 rows of
 // the last hidden state are never read by the reference's pooling).
+template <int D>
 __global__ __launch_bounds__(256) void pool_ln_l2(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
                                                   const float* __restrict__ beta, int B, int tok, float eps,
                                                   float* __restrict__ emb_f32, bf16_t* __restrict__ emb_bf16) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
-    const bf16_t* xr = x + ((int64_t)b * VIT_T + tok) * VIT_D;
-    float v[12];
+    const bf16_t* xr = x + ((int64_t)b * VIT_T + tok) * D;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
+    float v[NV];
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const bf16x4 p = *(const bf16x4*)(xr + t * 256 + lane * 4);
+    for (int t = 0; t < NT; ++t) {
+        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[t * 4 + j] = (float)p[j];
+        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
     }
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / VIT_D);
+    for (int j = 0; j < NV; ++j) s += v[j];
+    const float mean = wave_sum(s) * (1.0f / D);
     float q = 0.f;
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
+    for (int j = 0; j < NV; ++j) {
         v[j] -= mean;
         q += v[j] * v[j];
     }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / VIT_D) + eps);
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
     float n2 = 0.f;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const int c = t * 256 + lane * 4;
-        const f32x4 gv = *(const f32x4*)(gamma + c);
-        const f32x4 bv = *(const f32x4*)(beta + c);
+    for (int t = 0; t < NT; ++t) {
+        const int c = t * 64 * V + lane * V;
+        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
+        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[t * 4 + j] = v[t * 4 + j] * rstd * gv[j] + bv[j];
-            n2 += v[t * 4 + j] * v[t * 4 + j];
+        for (int j = 0; j < V; ++j) {
+            v[t * V + j] = v[t * V + j] * rstd * gv[j] + bv[j];
+            n2 += v[t * V + j] * v[t * V + j];
         }
     }
     // torch.nn.functional.normalize: x / max(||x||_2, 1e-12)
     const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const int c = t * 256 + lane * 4;
-        f32x4 o;
-        bf16x4 ob;
+    for (int t = 0; t < NT; ++t) {
+        const int c = t * 64 * V + lane * V;
+        typename RS::fvec o;
+        typename RS::bvec ob;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = v[t * 4 + j] * inv;
+        for (int j = 0; j < V; ++j) {
+            o[j] = v[t * V + j] * inv;
             ob[j] = (bf16_t)o[j];
         }
-        if (emb_f32) *(f32x4*)(emb_f32 + (int64_t)b * VIT_D + c) = o;
-        if (emb_bf16) *(bf16x4*)(emb_bf16 + (int64_t)b * VIT_D + c) = ob;
+        if (emb_f32) *(typename RS::fvec*)(emb_f32 + (int64_t)b * D + c) = o;
+        if (emb_bf16) *(typename RS::bvec*)(emb_bf16 + (int64_t)b * D + c) = ob;
     }
 }
 
@@ -235,16 +259,26 @@ hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, h
     return hipGetLastError();
 }
 
-hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, float eps, hipStream_t s) {
+// the instantiation of a row kernel for width d (384, 768, 1024); any other width is an error, never another kernel
+#define ROW_KERNEL_BY_WIDTH(d, kernel, grid, s, ...)                                                          \
+    switch (d) {                                                                                              \
+        case 384: hipLaunchKernelGGL(kernel<384>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
+        case 768: hipLaunchKernelGGL(kernel<768>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
+        case 1024: hipLaunchKernelGGL(kernel<1024>, grid, dim3(256), 0, s, __VA_ARGS__); break;               \
+        default: return hipErrorInvalidValue;                                                                 \
+    }
+
+hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, float eps, hipStream_t s) {
+    if (!vit_width_built(d)) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(layernorm_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const bf16_t*)x, gamma, beta,
-                       (bf16_t*)y, rows, eps);
+    ROW_KERNEL_BY_WIDTH(d, layernorm_rows, dim3((unsigned)((rows + 3) / 4)), s, (const bf16_t*)x, gamma, beta, (bf16_t*)y, rows, eps)
     return hipGetLastError();
 }
 
-hipError_t launch_ln_stats(const void* x, int64_t rows, float eps, float* stats, hipStream_t s) {
+hipError_t launch_ln_stats(const void* x, int64_t rows, int d, float eps, float* stats, hipStream_t s) {
+    if (!vit_width_built(d)) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ln_stats_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const bf16_t*)x, rows, eps, stats);
+    ROW_KERNEL_BY_WIDTH(d, ln_stats_rows, dim3((unsigned)((rows + 3) / 4)), s, (const bf16_t*)x, rows, eps, stats)
     return hipGetLastError();
 }
 
@@ -263,16 +297,17 @@ hipError_t launch_ln_finish(const float* part, int64_t part_rows, int64_t rows, 
     return hipGetLastError();
 }
 
-hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, hipStream_t s) {
+hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, int d, hipStream_t s) {
+    if (!vit_width_built(d)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(cls_rows, dim3((B + 3) / 4), dim3(256), 0, s, (bf16_t*)x, cls, pos, B);
+    ROW_KERNEL_BY_WIDTH(d, cls_rows, dim3((B + 3) / 4), s, (bf16_t*)x, cls, pos, B)
     return hipGetLastError();
 }
 
-hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tok, float eps, float* emb_f32,
+hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32,
                        void* emb_bf16, hipStream_t s) {
+    if (!vit_width_built(d)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pool_ln_l2, dim3((B + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, B, tok, eps, emb_f32,
-                       (bf16_t*)emb_bf16);
+    ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tok, eps, emb_f32, (bf16_t*)emb_bf16)
     return hipGetLastError();
 }

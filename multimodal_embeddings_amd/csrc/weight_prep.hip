@@ -452,19 +452,21 @@ struct VitStaged {
     const void *cls, *pos, *patch_w, *patch_b, *lnf_g, *lnf_b;
     struct Layer {
         const void *ln1_g, *ln1_b, *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *o_w, *o_b, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
-    } layer[VIT_L];
+    };
+    std::vector<Layer> layer;  // one per layer of the checkpoint
 };
 
 // one walk over the checkpoint's tensors: sizes the staging buffer when `st` is dry, copies into it afterwards
 void stage_vit(WeightStage& st, const mme_vit_weights* w, VitStaged& d) {
-    const size_t D = VIT_D, F = VIT_F;
+    const size_t D = (size_t)w->hidden, F = (size_t)w->mlp;
+    d.layer.resize((size_t)w->layers);
     d.cls = st.put(w->cls_token, D);
     d.pos = st.put(w->pos_emb, (size_t)VIT_T * D);
-    d.patch_w = st.put(w->patch_w, D * D);
+    d.patch_w = st.put(w->patch_w, D * VIT_PATCH_DIM);
     d.patch_b = st.put(w->patch_b, D);
     d.lnf_g = st.put(w->lnf_g, D);
     d.lnf_b = st.put(w->lnf_b, D);
-    for (int l = 0; l < VIT_L; ++l) {
+    for (int l = 0; l < w->layers; ++l) {
         const mme_vit_layer& a = w->layer[l];
         VitStaged::Layer& L = d.layer[l];
         L.ln1_g = st.put(a.ln1_g, D); L.ln1_b = st.put(a.ln1_b, D);
@@ -481,16 +483,16 @@ void stage_vit(WeightStage& st, const mme_vit_weights* w, VitStaged& d) {
 // mme_load_vit's sequence of uploads, buffer for buffer (mme_weights_fingerprint reports them in this order)
 int prepare_vit(mme_ctx* c, int dt, const VitStaged& d, hipStream_t s) {
     int r;
-    const size_t D = VIT_D, F = VIT_F;
+    const size_t D = (size_t)c->geom.hidden, F = (size_t)c->geom.mlp;
     if ((r = prep_table(c, dt, d.cls, D, 1.f, false, &c->cls, s))) return r;
     if ((r = prep_table(c, dt, d.pos, (size_t)VIT_T * D, 1.f, false, &c->pos, s))) return r;
     if ((r = prep_table(c, dt, d.patch_b, D, 1.f, false, &c->patch_b, s))) return r;
     if ((r = prep_table(c, dt, d.lnf_g, D, 1.f, false, &c->lnf_g, s))) return r;
     if ((r = prep_table(c, dt, d.lnf_b, D, 1.f, false, &c->lnf_b, s))) return r;
     const size_t rD[3] = {D, D, D}, rF[1] = {F};
-    if ((r = prep_bf16(c, dt, &d.patch_w, rD, 1, D, &c->patch_w, 1.f, false, s))) return r;
+    if ((r = prep_bf16(c, dt, &d.patch_w, rD, 1, VIT_PATCH_DIM, &c->patch_w, 1.f, false, s))) return r;
     const float sc = 0.125f * 1.44269504088896341f;  // mme_load_vit: dh^-0.5 log2(e), folded into the query projection
-    for (int l = 0; l < VIT_L; ++l) {
+    for (int l = 0; l < c->geom.layers; ++l) {
         const VitStaged::Layer& a = d.layer[l];
         LayerDev& L = c->layer[l];
         if ((r = prep_table(c, dt, a.ln1_g, D, 1.f, false, &L.ln1_g, s))) return r;
@@ -524,19 +526,15 @@ int mme_load_vit_as(mme_ctx* c, const mme_vit_weights* w, int dtype, void* strea
     if ((r = validate_vit_weights(c, w, "mme_load_vit"))) return r;
     if (dtype < MME_DT_F32 || dtype > MME_DT_F16)
         return fail(c, MME_E_ARG, "mme_load_vit_as: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", dtype);
-    for (int l = 0; l < VIT_L; ++l) {
-        const mme_vit_layer& a = w->layer[l];
-        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
-        for (const float* p : all)
-            if (!p) return fail(c, MME_E_ARG, "mme_load_vit: layer %d has a null tensor pointer", l);
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->ln_eps = w->ln_eps;
+    if ((r = begin_vit_load(c, w))) return r;
     hipStream_t s = (hipStream_t)stream;
     WeightStage st(dtype, s);
-    VitStaged d{};
+    VitStaged d;
     stage_vit(st, w, d);
-    if ((r = st.reserve(c))) return r;
+    if ((r = st.reserve(c))) {
+        end_vit_load(c, false);
+        return r;
+    }
     stage_vit(st, w, d);
     if (st.err != hipSuccess) {
         r = fail(c, MME_E_HIP, "mme_load_vit_as: copying the checkpoint's bytes to the device: %s", hipGetErrorString(st.err));
@@ -548,7 +546,7 @@ int mme_load_vit_as(mme_ctx* c, const mme_vit_weights* w, int dtype, void* strea
         if (e != hipSuccess) r = fail(c, MME_E_HIP, "mme_load_vit_as: weight preparation: %s", hipGetErrorString(e));
     }
     st.release();
-    if (r == MME_OK) c->loaded = true;
+    end_vit_load(c, r == MME_OK);
     return r;
 }
 

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import config
 from ._lib import Engine, MmeError  # noqa: F401
-from .weights import make_vit_weights
+from .weights import TILE_VIT, VIT_B16, make_vit_weights
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
@@ -116,7 +116,11 @@ class RegionEmbedder:
         """`model_name`: a LOCAL checkpoint directory (config.json + model.safetensors | shards | pytorch_model.bin, optionally
         preprocessor_config.json) is read once (checkpoint.read_checkpoint), loaded into every context in the file's own dtype
         and its image_mean / image_std applied; `self.checkpoint` keeps it.  Any other name is never fetched: the encoder runs
-        on seeded synthetic weights with one WARNING, or raises with `allow_synthetic=False`.  `weights=` (a dict) wins."""
+        on seeded synthetic weights with one WARNING, or raises with `allow_synthetic=False`.  `weights=` (a dict) wins.
+        `encoder`: "vit_b16" (exactly ViT-B/16), "vit" (any ViT/16 @224 of the supported family -- ViT-S, -B, -L widths,
+        weights.SUPPORTED_VIT: a checkpoint directory brings its own geometry in config.json, seeded weights take
+        `geometry=`, e.g. weights.VIT_L16, a `weights=` dict is sized by its tensors) or "mllama_tiles".  `self.embed_dim`
+        is the width of the vectors this object returns."""
         import torch
 
         from .checkpoint import read_checkpoint, resolve_model_source
@@ -124,8 +128,11 @@ class RegionEmbedder:
         self.torch = torch
         self.model_name = model_name
         self.checkpoint = None
-        if encoder not in ("vit_b16", "mllama_tiles"):
-            raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+        if encoder not in ("vit_b16", "vit", "mllama_tiles"):
+            raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16), 'vit' (the ViT/16 family: ViT-S, -B and -L widths) "
+                             "or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+        if encoder == "vit_b16" and geometry is not None:
+            raise ValueError("encoder='vit_b16' is ViT-B/16 only; pass encoder='vit' with geometry=")
         # a caller's engine carries its own weights
         source = "weights" if engine is not None else resolve_model_source(model_name, weights, allow_synthetic)
         if source == "checkpoint":
@@ -175,6 +182,8 @@ class RegionEmbedder:
                 from .weights import make_tile_vit_weights
 
                 w = weights if weights is not None else (make_tile_vit_weights(seed + 1, geometry) if geometry else make_tile_vit_weights(seed + 1))
+            elif encoder == "vit" and geometry is not None:
+                w = weights if weights is not None else make_vit_weights(seed, geometry)
             else:
                 w = weights if weights is not None else make_vit_weights(seed)
             self.engines = []
@@ -182,8 +191,10 @@ class RegionEmbedder:
                 e = Engine(d)
                 if encoder == "mllama_tiles":
                     e.load_tile_vit(w, geometry)
+                elif encoder == "vit":
+                    e.load_vit(w, geom=geometry)
                 else:
-                    e.load_vit(w)
+                    e.load_vit(w, geom=VIT_B16)
                 self.engines.append(e)
         self.engine = self.engines[0]
         if chunk:
@@ -191,7 +202,7 @@ class RegionEmbedder:
                 e.set_chunk(chunk)
         if prune_last_layer is None:  # default: on for the contexts this object created, a caller's engine stays as it is
             prune_last_layer = engine is None
-        if prune_last_layer and encoder == "vit_b16":
+        if prune_last_layer and encoder in ("vit_b16", "vit"):
             # only the pooled token's row of the last layer is computed past its attention (mme_set_forward_pruning): callers of
             # this class only ever receive pooled vectors, and those are bit-identical, 6 % sooner.  The benchmark's headline
             # drives the Engine directly and times the whole forward; `prune_last_layer=False` restores that here.
@@ -199,7 +210,9 @@ class RegionEmbedder:
                 e.set_forward_pruning(True)
         if pool not in ("cls", "last"):
             raise ValueError("pool must be 'cls' or 'last'")
-        self.pool_token = 0 if pool == "cls" else 196
+        self.pool_token = 0 if pool == "cls" else 196  # the last of the 197 tokens (the same at every width)
+        # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
+        self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
         self._group_crops = 16 * config.BATCH_SIZE
 
     # -- device-resident API -------------------------------------------------------------------
@@ -221,7 +234,7 @@ class RegionEmbedder:
         return host.to(device, non_blocking=True), offs, hw
 
     def embed_packed(self, pix, offs, hw, want_f32=True, want_bf16=True):
-        """Packed crops already in HBM -> (f32 [n,768], bf16 [n,768]) CUDA tensors."""
+        """Packed crops already in HBM -> (f32 [n, embed_dim], bf16 [n, embed_dim]) CUDA tensors."""
         return self.engine.embed(pix, offs, hw, self.pool_token, want_f32=want_f32, want_bf16=want_bf16)
 
     def embed_uniform(self, crops):
@@ -533,7 +546,7 @@ class RegionEmbedder:
         `batch_size` keeps the reference's meaning "images per GPU per batch", except that a device pass here
         carries 16 of the reference's one-image forwards per unit of it (256 crops at the default 16)."""
         if not image_paths:
-            return (np.zeros((0, 768), dtype=np.float32), np.zeros(0, dtype=bool)) if as_array else []
+            return (np.zeros((0, getattr(self, "embed_dim", config.EMBED_DIM)), dtype=np.float32), np.zeros(0, dtype=bool)) if as_array else []
         self._rows_as_array = bool(as_array) and getattr(self, "encoder", "vit_b16") != "mllama_tiles"
         self._group_crops = 16 * max(1, int(batch_size))
         embeddings = [None] * len(image_paths)
@@ -552,7 +565,7 @@ class RegionEmbedder:
                 embeddings[i] = row
         if as_array:
             ok = np.array([row is not None for row in embeddings], dtype=bool)
-            width = next((len(row) for row in embeddings if row is not None), 768)
+            width = next((len(row) for row in embeddings if row is not None), getattr(self, "embed_dim", config.EMBED_DIM))
             arr = np.zeros((len(embeddings), width), dtype=np.float32)
             for i, row in enumerate(embeddings):
                 if row is not None:
@@ -561,7 +574,7 @@ class RegionEmbedder:
         return embeddings
 
     def embed(self, region):
-        """north_star `embed(region) -> vec`: one crop -> float32[768] (raises on failure)."""
+        """north_star `embed(region) -> vec`: one crop -> float32[embed_dim] (raises on failure)."""
         out = self.get_image_embeddings([region], is_query=True)
         if out[0] is None:
             raise MmeError("embed(region) failed; see log")

@@ -122,7 +122,7 @@ class RegionProcessor:
         return t.from_numpy(np.require(arr, requirements=["C", "W"])).to(dev)
 
     def embed_page_regions(self, page, int_boxes):
-        """page: path | PIL image | uint8[H,W,3]; int_boxes int32[n,4] -> float32 CUDA tensor [n, 768].
+        """page: path | PIL image | uint8[H,W,3]; int_boxes int32[n,4] -> float32 CUDA tensor [n, embed_dim].
 
         Boxes of zero or negative size (which make the reference's PNG save fail, :115-117) raise."""
         pix, offs, hw = self.embedder.engine.crop_boxes(self._page_to_device(page), int_boxes)

@@ -1,4 +1,4 @@
-"""Deterministic synthetic ViT-B/16 weights (SURVEY.md §8d "Synthetic inputs").
+"""Deterministic synthetic ViT/16 weights: ViT-B/16 by default, any `ViTGeometry` (SURVEY.md §8d "Synthetic inputs").
 
 The reference loads pretrained weights by NAME over the network
 (deprecated_package/embedder.py:75-79), which is unavailable offline, so the
@@ -32,7 +32,8 @@ _MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 @dataclass(frozen=True)
 class ViTGeometry:
-    """ViT-B/16 @224 (transformers ViTConfig defaults)."""
+    """A ViT/16 @224 encoder; the defaults are ViT-B/16 (transformers ViTConfig defaults).  What the engine runs is
+    `SUPPORTED_VIT` below (checked by `check_vit_geometry`, and again by the library when the weights are loaded)."""
 
     image_size: int = 224
     patch_size: int = 16
@@ -65,6 +66,55 @@ class ViTGeometry:
 
 
 VIT_B16 = ViTGeometry()
+VIT_S16 = ViTGeometry(hidden_size=384, num_layers=12, num_heads=6, intermediate_size=1536)
+VIT_L16 = ViTGeometry(hidden_size=1024, num_layers=24, num_heads=16, intermediate_size=4096)
+
+# the geometries the engine is built for (csrc/common.h, csrc/capi.hip validate_vit_weights)
+SUPPORTED_VIT = {"image_size": (224,), "patch_size": (16,), "num_channels": (3,), "hidden_size": (384, 768, 1024), "head_dim": (64,),
+                 "intermediate_size": "a multiple of 64 up to 8192", "num_layers": "1..64"}
+
+
+def vit_geometry_problem(geom: ViTGeometry):
+    """None when the engine runs `geom`, else (field, value found, supported values as text) of the first field outside
+    the supported set."""
+    for fld in ("image_size", "patch_size", "num_channels", "hidden_size"):
+        if getattr(geom, fld) not in SUPPORTED_VIT[fld]:
+            return fld, getattr(geom, fld), ", ".join(str(v) for v in SUPPORTED_VIT[fld])
+    if geom.num_heads * 64 != geom.hidden_size:
+        return "num_heads", geom.num_heads, f"{geom.hidden_size // 64} at hidden_size {geom.hidden_size} (heads of 64)"
+    F = geom.intermediate_size
+    if F < 64 or F % 64 or F > 8192:
+        return "intermediate_size", F, SUPPORTED_VIT["intermediate_size"]
+    if not 1 <= geom.num_layers <= 64:
+        return "num_layers", geom.num_layers, SUPPORTED_VIT["num_layers"]
+    return None
+
+
+def vit_flops_per_crop(geom: ViTGeometry = VIT_B16) -> int:
+    """FLOP of one crop's forward as DESIGN.md §4 counts them (2 per multiply-add; LayerNorm, softmax and GELU excluded):
+    the patch embedding (196 x patch_dim x D) and, per layer, the four projections and the two MLP matrices on 197 tokens
+    plus the two attention products.  DESIGN's figure for ViT-B/16, 35 126 083 584 (bench.py prices its headline with it),
+    holds 4 (197^2 - 1) D per layer for the attention products -- 36 864 FLOP, one part in a million, below the plain
+    4 x 197^2 x D; this function keeps DESIGN's count at every width so that the fractions of nominal it feeds compare
+    with the recorded ones."""
+    D, F, L, T = geom.hidden_size, geom.intermediate_size, geom.num_layers, geom.seq_len
+    return 2 * geom.num_patches * geom.patch_dim * D + L * (2 * T * D * (4 * D + 2 * F) + 4 * (T * T - 1) * D)
+
+
+def infer_vit_geometry(w: dict, eps: float = 1e-12) -> ViTGeometry:
+    """The geometry of a canonical-name weight dict (vit_tensor_specs), read off its tensor shapes; heads of 64."""
+    D = int(np.shape(w["embeddings.patch_embeddings.projection.weight"])[0])
+    patch = int(np.shape(w["embeddings.patch_embeddings.projection.weight"])[-1])
+    tokens = int(np.shape(w["embeddings.position_embeddings"])[-2])
+    grid = int(round((tokens - 1) ** 0.5))
+    layers = 0
+    while f"layers.{layers}.mlp.fc1.weight" in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError("the weight dict holds no 'layers.0.mlp.fc1.weight'")
+    F = int(np.shape(w["layers.0.mlp.fc1.weight"])[0])
+    return ViTGeometry(image_size=grid * patch, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
+                       layer_norm_eps=float(eps))
 
 
 def _splitmix64(x: np.ndarray) -> np.ndarray:
