@@ -100,10 +100,11 @@ int mme_vit_geometry(mme_ctx* ctx, int32_t out[6]);
 /* The same load from a checkpoint's OWN element type, prepared on the device.  Replaces the `torch_dtype=bfloat16` read of
  * `from_pretrained` (embedder.py:75-80) for a checkpoint on local disk: every tensor pointer of `w` (and of its layer
  * array) points at HOST elements of `dtype` -- the struct fields keep their `const float*` type, cast the pointers.  The
- * raw bytes are copied to a device staging buffer (freed before the call returns, not part of the context) and kernels
- * produce every buffer mme_load_vit produces on the host -- convert, scale the query rows, round to bf16, fold the
- * LayerNorms with their f64 column sums in the host's k order -- BIT-IDENTICAL to mme_load_vit on the same values widened
- * to f32 (mme_weights_fingerprint compares two contexts).  A bf16 checkpoint is never inflated to f32 on the host.
+ * raw bytes are copied to a device staging buffer (freed before the call returns, not part of the context).  The two loaders
+ * run ONE sequence of prepared buffers with two preparers: mme_load_vit's host loops, and here kernels with the same
+ * operations in the same order -- convert, scale the query rows, round to bf16, fold the LayerNorms with their f64 column
+ * sums over k ascending -- so the buffers are BIT-IDENTICAL to mme_load_vit's on the same values widened to f32
+ * (mme_weights_fingerprint compares two contexts).  A bf16 checkpoint is never inflated to f32 on the host.
  * Same validation and error texts as mme_load_vit.  Synchronises `stream` before returning: the host tensors may be
  * released right after. */
 enum { MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2 };

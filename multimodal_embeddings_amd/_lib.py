@@ -284,76 +284,10 @@ class Engine:
         """Width of the rows `vit_forward` / `embed` return."""
         return self.vit_geometry().hidden_size
 
-    def load_tile_vit(self, w: dict, geom=None):
-        """Hugging Face `MllamaVisionModel` state dict (f32 arrays) -> the tile-ViT encoder of this context."""
-        from .weights import TILE_VIT
-
-        geom = geom or TILE_VIT
-        keep = []
-
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            keep.append(a)
-            return _fp(a)
-
-        L = geom.num_layers + geom.num_global_layers
-        layers = (_TileLayer * L)()
-        for i in range(L):
-            gated = i >= geom.num_layers
-            p = f"global_transformer.layers.{i - geom.num_layers}." if gated else f"transformer.layers.{i}."
-            X = layers[i]
-            X.ln1_g, X.ln1_b = arr(p + "input_layernorm.weight"), arr(p + "input_layernorm.bias")
-            X.q_w, X.k_w, X.v_w, X.o_w = (arr(p + f"self_attn.{n}_proj.weight") for n in "qkvo")
-            X.ln2_g, X.ln2_b = arr(p + "post_attention_layernorm.weight"), arr(p + "post_attention_layernorm.bias")
-            X.fc1_w, X.fc1_b, X.fc2_w, X.fc2_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias"), arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-            X.gated = int(gated)
-            X.gate_attn = float(w[p + "gate_attn"][0]) if gated else 0.0
-            X.gate_ffn = float(w[p + "gate_ffn"][0]) if gated else 0.0
-        W = _TileWeights()
-        W.image_size, W.patch_size, W.hidden, W.heads, W.mlp = geom.image_size, geom.patch_size, geom.hidden_size, geom.num_heads, geom.intermediate_size
-        W.max_tiles, W.aspect_ratios, W.layers, W.global_layers = geom.max_num_tiles, geom.max_aspect_ratio_id + 1, geom.num_layers, geom.num_global_layers
-        W.n_intermediate = len(geom.intermediate_layers)
-        for k, v in enumerate(geom.intermediate_layers):
-            W.intermediate[k] = int(v)
-        W.intermediate_save_point = {"after": 0, "before": 1}[geom.intermediate_save_point]
-        W.norm_eps = float(geom.norm_eps)
-        W.pos_gate = float(w["gated_positional_embedding.gate"][0])
-        W.pre_gate = float(w["pre_tile_positional_embedding.gate"][0])
-        W.post_gate = float(w["post_tile_positional_embedding.gate"][0])
-        W.class_embedding, W.patch_w = arr("class_embedding"), arr("patch_embedding.weight")
-        W.pos_emb, W.tile_pos_emb = arr("gated_positional_embedding.embedding"), arr("gated_positional_embedding.tile_embedding.weight")
-        W.pre_emb, W.post_emb = arr("pre_tile_positional_embedding.embedding.weight"), arr("post_tile_positional_embedding.embedding.weight")
-        W.ln_pre_g, W.ln_pre_b = arr("layernorm_pre.weight"), arr("layernorm_pre.bias")
-        W.ln_post_g, W.ln_post_b = arr("layernorm_post.weight"), arr("layernorm_post.bias")
-        W.layer = layers
-        self._check(self.lib.mme_load_tile_vit(self.h, C.byref(W)), "mme_load_tile_vit")
-        self.tile_features = geom.output_dim
-
-    # ---- weights from a checkpoint, in the file's own dtype, prepared on the device (mme_load_*_as) ------------
     @staticmethod
-    def _ckpt_ptr(ckpt, name):
-        t = ckpt.tensors[name]
-        if not t.is_contiguous() or t.device.type != "cpu":
-            raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
-        return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))  # elements of ckpt.dtype behind the struct's float*
-
-    def load_vit_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "vit_b16" | "vit")` -> this context, at the checkpoint's geometry: the raw f32 /
-        bf16 / f16 bytes go to the device and are converted, scaled and LayerNorm-folded there, bit-identically to
-        `load_vit` on the same values.  Replaces what the context held."""
-        if ckpt.encoder not in ("vit_b16", "vit"):
-            raise MmeError(f"load_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        W, layers = self._vit_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
-        self._check(self.lib.mme_load_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_vit_as")
-
-    def load_tile_vit_checkpoint(self, ckpt, geometry=None):
-        """`checkpoint.read_checkpoint(dir, "mllama_tiles")` -> the tile-ViT encoder of this context, prepared on the device.
-        `geometry` overrides the checkpoint's (the save point of the intermediate states is not in the file)."""
-        if ckpt.encoder != "mllama_tiles":
-            raise MmeError(f"load_tile_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        geom = geometry or ckpt.geometry
-        arr = lambda name: self._ckpt_ptr(ckpt, name)  # noqa: E731
-        gate = lambda name: float(ckpt.tensors[name].float().reshape(-1)[0])  # noqa: E731
+    def _tile_struct(geom, arr, gate):
+        """mme_tile_vit_weights (+ its layer array, which the caller keeps alive) for `geom`: tensor pointers from arr(name),
+        the scalar gates from gate(name)."""
         L = geom.num_layers + geom.num_global_layers
         layers = (_TileLayer * L)()
         for i in range(L):
@@ -384,6 +318,50 @@ class Engine:
         W.ln_pre_g, W.ln_pre_b = arr("layernorm_pre.weight"), arr("layernorm_pre.bias")
         W.ln_post_g, W.ln_post_b = arr("layernorm_post.weight"), arr("layernorm_post.bias")
         W.layer = layers
+        return W, layers
+
+    def load_tile_vit(self, w: dict, geom=None):
+        """Hugging Face `MllamaVisionModel` state dict (f32 arrays) -> the tile-ViT encoder of this context."""
+        from .weights import TILE_VIT
+
+        geom = geom or TILE_VIT
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32)
+            keep.append(a)
+            return _fp(a)
+
+        W, layers = self._tile_struct(geom, arr, lambda name: float(w[name][0]))
+        self._check(self.lib.mme_load_tile_vit(self.h, C.byref(W)), "mme_load_tile_vit")
+        self.tile_features = geom.output_dim
+
+    # ---- weights from a checkpoint, in the file's own dtype, prepared on the device (mme_load_*_as) ------------
+    @staticmethod
+    def _ckpt_ptr(ckpt, name):
+        t = ckpt.tensors[name]
+        if not t.is_contiguous() or t.device.type != "cpu":
+            raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
+        return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))  # elements of ckpt.dtype behind the struct's float*
+
+    def load_vit_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "vit_b16" | "vit")` -> this context, at the checkpoint's geometry: the raw f32 /
+        bf16 / f16 bytes go to the device and are converted, scaled and LayerNorm-folded there, bit-identically to
+        `load_vit` on the same values.  Replaces what the context held."""
+        if ckpt.encoder not in ("vit_b16", "vit"):
+            raise MmeError(f"load_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        W, layers = self._vit_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
+        self._check(self.lib.mme_load_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_vit_as")
+
+    def load_tile_vit_checkpoint(self, ckpt, geometry=None):
+        """`checkpoint.read_checkpoint(dir, "mllama_tiles")` -> the tile-ViT encoder of this context, prepared on the device.
+        `geometry` overrides the checkpoint's (the save point of the intermediate states is not in the file)."""
+        if ckpt.encoder != "mllama_tiles":
+            raise MmeError(f"load_tile_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        geom = geometry or ckpt.geometry
+        arr = lambda name: self._ckpt_ptr(ckpt, name)  # noqa: E731
+        gate = lambda name: float(ckpt.tensors[name].float().reshape(-1)[0])  # noqa: E731
+        W, layers = self._tile_struct(geom, arr, gate)
         self._check(self.lib.mme_load_tile_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_tile_vit_as")
         self.tile_features = geom.output_dim
 

@@ -10,7 +10,7 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
 supported ViT/16 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
-bytes to the device, where they are converted and folded (csrc/weight_prep.hip).
+bytes to the device, where they are converted and folded (csrc/weight_load.hip: DevPrep; kernels in csrc/weight_prep.hip).
 
     python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|mllama_tiles]
 

@@ -1,4 +1,4 @@
-// C ABI (include/mme.h): context, weight upload, workspace and the launch sequences.
+// C ABI (include/mme.h): context, workspace and the launch sequences (weight loading: weight_load.hip).
 // No exceptions cross the boundary; every failure sets ctx->err and returns a code.
 #include "../../include/mme.h"
 
@@ -47,131 +47,6 @@ int ensure(mme_ctx* c, DevBuf& b, size_t bytes) {
     if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
     b.bytes = bytes;
     return MME_OK;
-}
-
-uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-int upload_f32(mme_ctx* c, const float* src, size_t n, float** dst) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, n * sizeof(float));
-    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
-    c->allocs.push_back(p);
-    c->alloc_bytes.push_back(n * sizeof(float));
-    HIP_TRY(c, hipMemcpy(p, src, n * sizeof(float), hipMemcpyHostToDevice));
-    *dst = (float*)p;
-    return MME_OK;
-}
-
-// concatenates up to three [rows_i, cols] f32 matrices row-wise, converts to bf16, uploads
-int upload_bf16(mme_ctx* c, const float* const* srcs, const size_t* rows, int nsrc, size_t cols, bf16_t** dst, float scale) {
-    size_t total = 0;
-    for (int i = 0; i < nsrc; ++i) total += rows[i] * cols;
-    std::vector<uint16_t> h(total);
-    size_t o = 0;
-    for (int i = 0; i < nsrc; ++i)
-        for (size_t k = 0; k < rows[i] * cols; ++k) h[o++] = f32_to_bf16_rne(scale == 1.0f ? srcs[i][k] : srcs[i][k] * scale);
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, total * 2);
-    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
-    c->allocs.push_back(p);
-    c->alloc_bytes.push_back(total * 2);
-    HIP_TRY(c, hipMemcpy(p, h.data(), total * 2, hipMemcpyHostToDevice));
-    *dst = (bf16_t*)p;
-    return MME_OK;
-}
-
-// LayerNorm folding for `y = W . LN(x) + b`:  W'[n,k] = bf16(W[n,k] * gamma[k]),
-// colsum[n] = sum_k W'[n,k] (of the ROUNDED values, so that r*(W'x - mu*colsum) is exact algebra),
-// b'[n] = b[n] + sum_k W[n,k] * beta[k].  Sums in f64 on the host.
-int upload_folded(mme_ctx* c, const float* const* ws, const float* const* bs, const size_t* rows, int nsrc, size_t cols,
-                  const float* gamma, const float* beta, bf16_t** wf, float** cs, float** bf) {
-    size_t total = 0;
-    for (int i = 0; i < nsrc; ++i) total += rows[i];
-    std::vector<uint16_t> hw(total * cols);
-    std::vector<float> hcs(total), hbf(total);
-    size_t o = 0;
-    for (int i = 0; i < nsrc; ++i)
-        for (size_t n = 0; n < rows[i]; ++n, ++o) {
-            double s = 0.0, t = 0.0;
-            for (size_t k = 0; k < cols; ++k) {
-                const float w = ws[i][n * cols + k];
-                const uint16_t q = f32_to_bf16_rne(w * gamma[k]);
-                hw[o * cols + k] = q;
-                uint32_t u = (uint32_t)q << 16;
-                float wq;
-                memcpy(&wq, &u, 4);
-                s += (double)wq;
-                t += (double)w * (double)beta[k];
-            }
-            hcs[o] = (float)s;
-            hbf[o] = (float)((bs[i] ? (double)bs[i][n] : 0.0) + t);
-        }
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, hw.size() * 2);
-    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
-    c->allocs.push_back(p);
-    c->alloc_bytes.push_back(hw.size() * 2);
-    HIP_TRY(c, hipMemcpy(p, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
-    *wf = (bf16_t*)p;
-    int r;
-    if ((r = upload_f32(c, hcs.data(), hcs.size(), cs))) return r;
-    return upload_f32(c, hbf.data(), hbf.size(), bf);
-}
-
-int upload_f32_cat(mme_ctx* c, const float* const* srcs, const size_t* n, int nsrc, float** dst) {
-    std::vector<float> h;
-    for (int i = 0; i < nsrc; ++i) h.insert(h.end(), srcs[i], srcs[i] + n[i]);
-    return upload_f32(c, h.data(), h.size(), dst);
-}
-
-int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who) {
-    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
-    // every refusal names the field, the value found and what is supported
-    if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
-    if (w->patch_size != VIT_PATCH) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: %d", who, w->patch_size, VIT_PATCH);
-    if (!vit_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 384, 768, 1024", who, w->hidden);
-    if (w->heads * VIT_DH != w->hidden)
-        return fail(c, MME_E_ARG, "%s: heads = %d at hidden = %d; supported: heads of %d, heads = hidden / %d = %d", who, w->heads, w->hidden, VIT_DH, VIT_DH,
-                    w->hidden / VIT_DH);
-    if (w->mlp < 64 || (w->mlp % 64) != 0 || w->mlp > VIT_MAX_F)
-        return fail(c, MME_E_ARG, "%s: mlp = %d; supported: multiples of 64 up to %d", who, w->mlp, VIT_MAX_F);
-    if (w->layers < 1 || w->layers > VIT_MAX_L) return fail(c, MME_E_ARG, "%s: layers = %d; supported: 1..%d", who, w->layers, VIT_MAX_L);
-    if (!w->cls_token || !w->pos_emb || !w->patch_w || !w->patch_b || !w->lnf_g || !w->lnf_b || !w->layer)
-        return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
-    for (int l = 0; l < w->layers; ++l) {
-        const mme_vit_layer& a = w->layer[l];
-        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
-        for (const float* p : all)
-            if (!p) return fail(c, MME_E_ARG, "%s: layer %d has a null tensor pointer", who, l);
-    }
-    return MME_OK;
-}
-
-int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->loaded = false;
-    if (c->vit_alloc_hi > c->vit_alloc_lo) {
-        HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
-        for (size_t i = c->vit_alloc_lo; i < c->vit_alloc_hi; ++i) (void)hipFree(c->allocs[i]);
-        c->allocs.erase(c->allocs.begin() + c->vit_alloc_lo, c->allocs.begin() + c->vit_alloc_hi);
-        c->alloc_bytes.erase(c->alloc_bytes.begin() + c->vit_alloc_lo, c->alloc_bytes.begin() + c->vit_alloc_hi);
-    }
-    c->vit_alloc_lo = c->vit_alloc_hi = c->allocs.size();
-    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp};
-    c->ln_eps = w->ln_eps;
-    c->layer.assign((size_t)w->layers, LayerDev{});
-    return MME_OK;
-}
-
-void end_vit_load(mme_ctx* c, bool ok) {
-    c->vit_alloc_hi = c->allocs.size();
-    c->loaded = ok;
 }
 
 // The workspace follows the chunk AND the geometry: a context that was reloaded with a wider encoder regrows it
@@ -624,70 +499,6 @@ int mme_vit_geometry(mme_ctx* c, int32_t out[6]) {
     if (!c || !out) return fail(c, MME_E_ARG, "mme_vit_geometry: null argument");
     const int32_t g[6] = {VIT_IMG, VIT_PATCH, c->geom.hidden, c->geom.layers, c->geom.heads, c->geom.mlp};
     for (int i = 0; i < 6; ++i) out[i] = g[i];
-    return MME_OK;
-}
-
-static int load_vit_host(mme_ctx* c, const mme_vit_weights* w);
-
-int mme_load_vit(mme_ctx* c, const mme_vit_weights* w) {
-    int r;
-    if ((r = validate_vit_weights(c, w, "mme_load_vit"))) return r;
-    if ((r = begin_vit_load(c, w))) return r;
-    r = load_vit_host(c, w);
-    end_vit_load(c, r == MME_OK);
-    return r;
-}
-
-// the host loops of mme_load_vit (f32 in, converted / scaled / folded on the CPU, one upload per buffer)
-static int load_vit_host(mme_ctx* c, const mme_vit_weights* w) {
-    int r;
-    const size_t D = (size_t)w->hidden, F = (size_t)w->mlp;
-    if ((r = upload_f32(c, w->cls_token, D, &c->cls))) return r;
-    if ((r = upload_f32(c, w->pos_emb, (size_t)VIT_T * D, &c->pos))) return r;
-    if ((r = upload_f32(c, w->patch_b, D, &c->patch_b))) return r;
-    if ((r = upload_f32(c, w->lnf_g, D, &c->lnf_g))) return r;
-    if ((r = upload_f32(c, w->lnf_b, D, &c->lnf_b))) return r;
-    {
-        const float* s[1] = {w->patch_w};
-        const size_t rows[1] = {D};
-        if ((r = upload_bf16(c, s, rows, 1, VIT_PATCH_DIM, &c->patch_w))) return r;
-    }
-    for (int l = 0; l < w->layers; ++l) {
-        const mme_vit_layer& a = w->layer[l];
-        LayerDev& L = c->layer[l];
-        if ((r = upload_f32(c, a.ln1_g, D, &L.ln1_g))) return r;
-        if ((r = upload_f32(c, a.ln1_b, D, &L.ln1_b))) return r;
-        if ((r = upload_f32(c, a.ln2_g, D, &L.ln2_g))) return r;
-        if ((r = upload_f32(c, a.ln2_b, D, &L.ln2_b))) return r;
-        // The attention kernel takes its scores in log2 units straight from the matrix pipe (attention.hip, PRESCALED):
-        // dh^-0.5 * log2(e) is folded into the query projection here, once, BEFORE the rounding to bf16 that the upload
-        // applies anyway -- softmax(q.k / 8) = exp2(q'.k - c) / sum with q' = (W_q' x + b_q'), W_q' = sc W_q, b_q' = sc b_q.
-        const float sc = 0.125f * 1.44269504088896341f;
-        std::vector<float> qw_s((size_t)D * D), qb_s(D);
-        for (size_t i = 0; i < qw_s.size(); ++i) qw_s[i] = a.q_w[i] * sc;
-        for (size_t i = 0; i < D; ++i) qb_s[i] = a.q_b[i] * sc;
-        const float* qkv[3] = {qw_s.data(), a.k_w, a.v_w};
-        const size_t r3[3] = {D, D, D};
-        if ((r = upload_bf16(c, qkv, r3, 3, D, &L.qkv_w))) return r;
-        const float* qkvb[3] = {qb_s.data(), a.k_b, a.v_b};
-        if ((r = upload_f32_cat(c, qkvb, r3, 3, &L.qkv_b))) return r;
-        if ((r = upload_folded(c, qkv, qkvb, r3, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
-        const float* o[1] = {a.o_w};
-        const size_t r1[1] = {D};
-        if ((r = upload_bf16(c, o, r1, 1, D, &L.o_w))) return r;
-        if ((r = upload_f32(c, a.o_b, D, &L.o_b))) return r;
-        const float* f1[1] = {a.fc1_w};
-        const size_t rf1[1] = {F};
-        if ((r = upload_bf16(c, f1, rf1, 1, D, &L.fc1_w))) return r;
-        if ((r = upload_f32(c, a.fc1_b, F, &L.fc1_b))) return r;
-        {
-            const float* f1b[1] = {a.fc1_b};
-            if ((r = upload_folded(c, f1, f1b, rf1, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf))) return r;
-        }
-        const float* f2[1] = {a.fc2_w};
-        if ((r = upload_bf16(c, f2, r1, 1, F, &L.fc2_w))) return r;
-        if ((r = upload_f32(c, a.fc2_b, D, &L.fc2_b))) return r;
-    }
     return MME_OK;
 }
 

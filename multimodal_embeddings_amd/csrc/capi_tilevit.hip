@@ -27,8 +27,7 @@ struct TileVitDev {
     float *cls = nullptr, *pre = nullptr, *pos = nullptr, *tilepos = nullptr, *post = nullptr;
     float *lnpre_g = nullptr, *lnpre_b = nullptr, *lnpost_g = nullptr, *lnpost_b = nullptr, *zeros = nullptr;
     bf16_t* patch_w = nullptr;
-    std::vector<TileLayerDev> layer;
-    std::vector<void*> allocs;
+    std::vector<TileLayerDev> layer;  // the prepared buffers are registered in the context (c->allocs)
     // workspace for `ws_images` images
     int ws_images = 0;
     DevBuf patches, pemb, x, qkv, att, mlp, stats, lnpart, inter, meta;
@@ -37,7 +36,6 @@ struct TileVitDev {
 void tile_vit_free(mme_ctx* c) {
     if (!c->tv) return;
     TileVitDev* t = c->tv;
-    for (void* p : t->allocs) (void)hipFree(p);
     DevBuf* bufs[] = {&t->patches, &t->pemb, &t->x, &t->qkv, &t->att, &t->mlp, &t->stats, &t->lnpart, &t->inter, &t->meta};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -46,13 +44,6 @@ void tile_vit_free(mme_ctx* c) {
 }
 
 namespace {
-
-// upload helpers of capi.hip register their allocations in c->allocs (freed by mme_destroy); fine for these too
-int upload_scaled_f32(mme_ctx* c, const float* src, size_t n, float scale, float** dst) {
-    std::vector<float> h(n);
-    for (size_t i = 0; i < n; ++i) h[i] = src[i] * scale;
-    return upload_f32(c, h.data(), n, dst);
-}
 
 int validate_tile_weights(mme_ctx* c, const mme_tile_vit_weights* w) {
     if (!c || !w) return fail(c, MME_E_ARG, "mme_load_tile_vit: null argument");
@@ -72,6 +63,12 @@ int validate_tile_weights(mme_ctx* c, const mme_tile_vit_weights* w) {
         !w->ln_post_g || !w->ln_post_b || !w->layer)
         return fail(c, MME_E_ARG, "mme_load_tile_vit: null tensor pointer");
     if (c->tv) return fail(c, MME_E_STATE, "mme_load_tile_vit: tile-ViT weights already loaded; create a new context");
+    for (int l = 0; l < w->layers + w->global_layers; ++l) {
+        const mme_tile_layer& a = w->layer[l];
+        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.k_w, a.v_w, a.o_w, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+        for (const float* p : all)
+            if (!p) return fail(c, MME_E_ARG, "mme_load_tile_vit: layer %d has a null tensor pointer", l);
+    }
     return MME_OK;
 }
 
@@ -90,6 +87,85 @@ int new_tile_dev(mme_ctx* c, const mme_tile_vit_weights* w) {
     return MME_OK;
 }
 
+// every tensor of the checkpoint with its element count (the order of the staged bytes)
+template <class Fn>
+void each_tile_tensor(mme_tile_vit_weights& w, std::vector<mme_tile_layer>& layer, Fn&& f) {
+    const size_t D = TD, F = TF;
+    f(w.class_embedding, D);
+    f(w.patch_w, D * TPDIM);
+    f(w.pos_emb, (size_t)TTOK * D);
+    f(w.tile_pos_emb, (size_t)TARATIOS * TTILES * TTOK * D);
+    f(w.pre_emb, (size_t)TARATIOS * TTILES * D);
+    f(w.post_emb, (size_t)TARATIOS * TTILES * D);
+    f(w.ln_pre_g, D); f(w.ln_pre_b, D);
+    f(w.ln_post_g, D); f(w.ln_post_b, D);
+    for (mme_tile_layer& a : layer) {
+        f(a.ln1_g, D); f(a.ln1_b, D);
+        f(a.q_w, D * D); f(a.k_w, D * D); f(a.v_w, D * D); f(a.o_w, D * D);
+        f(a.ln2_g, D); f(a.ln2_b, D);
+        f(a.fc1_w, F * D); f(a.fc1_b, F);
+        f(a.fc2_w, D * F); f(a.fc2_b, D);
+    }
+}
+
+// The prepared buffers of the tower, in the order mme_weights_fingerprint reports them: nine tables, zeros, patch_w, then
+// 9 per layer.  The tanh gates are applied here, once (tanh on the host): the kernels add plain tables.  A gated table
+// and fc2_b are always multiplied, o_w / fc2_w only where the factor is not 1 (the ungated layers).
+template <class P>
+int prepare_tile(mme_ctx* c, P& p, const mme_tile_vit_weights& w) {
+    TileVitDev* t = c->tv;
+    int r;
+    const size_t D = TD, F = TF;
+    const size_t rD[3] = {D, D, D}, rF[1] = {F};
+    auto plain = [&](const float* src, size_t n, float** dst) { return p.table(src, n, 1.f, false, dst); };
+    const float g_pos = std::tanh(w.pos_gate), g_pre = std::tanh(w.pre_gate), g_post = std::tanh(w.post_gate);
+    if ((r = plain(w.class_embedding, D, &t->cls))) return r;
+    if ((r = p.table(w.pos_emb, (size_t)TTOK * D, 1.0f - g_pos, true, &t->pos))) return r;
+    if ((r = p.table(w.tile_pos_emb, (size_t)TARATIOS * TTILES * TTOK * D, g_pos, true, &t->tilepos))) return r;
+    if ((r = p.table(w.pre_emb, (size_t)TARATIOS * TTILES * D, g_pre, true, &t->pre))) return r;
+    if ((r = p.table(w.post_emb, (size_t)TARATIOS * TTILES * D, g_post, true, &t->post))) return r;
+    if ((r = plain(w.ln_pre_g, D, &t->lnpre_g))) return r;
+    if ((r = plain(w.ln_pre_b, D, &t->lnpre_b))) return r;
+    if ((r = plain(w.ln_post_g, D, &t->lnpost_g))) return r;
+    if ((r = plain(w.ln_post_b, D, &t->lnpost_b))) return r;
+    if ((r = p.zeros(F, &t->zeros))) return r;
+    // patch projection [1280, 588] -> [1280, 640] (zero columns: the GEMM's K step is 64)
+    if ((r = p.padded(w.patch_w, TD, TPDIM, TPDIMP, &t->patch_w))) return r;
+    const int L = w.layers + w.global_layers;
+    t->layer.resize(L);
+    // The attention kernels take their scores in log2 units straight from the matrix pipe (attention_tiles.hip):
+    // 80^-0.5 * log2(e) is folded into the query projection here, once, BEFORE the rounding to bf16 (as prepare_vit does)
+    const float qsc = 0.11180339887498949f * 1.44269504088896341f;
+    for (int l = 0; l < L; ++l) {
+        const mme_tile_layer& a = w.layer[l];
+        TileLayerDev& Ld = t->layer[l];
+        // x + tanh(gate) * branch(x): the gate multiplies the branch's LAST linear map (global layers only)
+        const float ga = a.gated ? std::tanh(a.gate_attn) : 1.0f, gf = a.gated ? std::tanh(a.gate_ffn) : 1.0f;
+        const WpFoldSrc fq[3] = {{a.q_w, nullptr, qsc, 1}, {a.k_w, nullptr, 1.f, 0}, {a.v_w, nullptr, 1.f, 0}};
+        if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &Ld.qkv_wf, &Ld.qkv_cs, &Ld.qkv_bf))) return r;
+        const void *o_w = a.o_w, *fc2_w = a.fc2_w;
+        if ((r = p.bf16(&o_w, rD, 1, D, ga, ga != 1.0f, &Ld.o_w))) return r;
+        const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
+        if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &Ld.fc1_wf, &Ld.fc1_cs, &Ld.fc1_bf))) return r;
+        if ((r = p.bf16(&fc2_w, rD, 1, F, gf, gf != 1.0f, &Ld.fc2_w))) return r;
+        if ((r = p.table(a.fc2_b, D, gf, true, &Ld.fc2_b))) return r;
+    }
+    return MME_OK;
+}
+
+template <class P>
+int load_tile(mme_ctx* c, const mme_tile_vit_weights* w, P p) {
+    int r;
+    if ((r = new_tile_dev(c, w))) return r;
+    // the preparer's view of the tensors: the caller's pointers, or where the preparer staged them
+    std::vector<mme_tile_layer> layer(w->layer, w->layer + w->layers + w->global_layers);
+    mme_tile_vit_weights v = *w;
+    v.layer = layer.data();
+    r = p.stage([&](auto& put) { each_tile_tensor(v, layer, put); });
+    if (r == MME_OK) r = prepare_tile(c, p, v);
+    return p.finish(r);
+}
+
 }  // namespace
 
 extern "C" {
@@ -97,175 +173,14 @@ extern "C" {
 int mme_load_tile_vit(mme_ctx* c, const mme_tile_vit_weights* w) {
     int r;
     if ((r = validate_tile_weights(c, w))) return r;
-    if ((r = new_tile_dev(c, w))) return r;
-    TileVitDev* t = c->tv;
-    // gates are applied here, once: the kernels add plain tables
-    const float g_pos = std::tanh(w->pos_gate), g_pre = std::tanh(w->pre_gate), g_post = std::tanh(w->post_gate);
-    if ((r = upload_f32(c, w->class_embedding, TD, &t->cls))) return r;
-    if ((r = upload_scaled_f32(c, w->pos_emb, (size_t)TTOK * TD, 1.0f - g_pos, &t->pos))) return r;
-    if ((r = upload_scaled_f32(c, w->tile_pos_emb, (size_t)TARATIOS * TTILES * TTOK * TD, g_pos, &t->tilepos))) return r;
-    if ((r = upload_scaled_f32(c, w->pre_emb, (size_t)TARATIOS * TTILES * TD, g_pre, &t->pre))) return r;
-    if ((r = upload_scaled_f32(c, w->post_emb, (size_t)TARATIOS * TTILES * TD, g_post, &t->post))) return r;
-    if ((r = upload_f32(c, w->ln_pre_g, TD, &t->lnpre_g))) return r;
-    if ((r = upload_f32(c, w->ln_pre_b, TD, &t->lnpre_b))) return r;
-    if ((r = upload_f32(c, w->ln_post_g, TD, &t->lnpost_g))) return r;
-    if ((r = upload_f32(c, w->ln_post_b, TD, &t->lnpost_b))) return r;
-    {
-        std::vector<float> z(TF, 0.f);
-        if ((r = upload_f32(c, z.data(), TF, &t->zeros))) return r;
-        // patch projection [1280, 588] -> [1280, 640] (zero columns: the GEMM's K step is 64)
-        std::vector<float> pw((size_t)TD * TPDIMP, 0.f);
-        for (int n = 0; n < TD; ++n) memcpy(&pw[(size_t)n * TPDIMP], w->patch_w + (size_t)n * TPDIM, TPDIM * sizeof(float));
-        const float* src[1] = {pw.data()};
-        const size_t rows[1] = {TD};
-        if ((r = upload_bf16(c, src, rows, 1, TPDIMP, &t->patch_w))) return r;
-    }
-    const int L = w->layers + w->global_layers;
-    t->layer.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const mme_tile_layer& a = w->layer[l];
-        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.k_w, a.v_w, a.o_w, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
-        for (const float* p : all)
-            if (!p) return fail(c, MME_E_ARG, "mme_load_tile_vit: layer %d has a null tensor pointer", l);
-        TileLayerDev& Ld = t->layer[l];
-        // x + tanh(gate) * branch(x): the gate multiplies the branch's LAST linear map (global layers only)
-        const float ga = a.gated ? std::tanh(a.gate_attn) : 1.0f, gf = a.gated ? std::tanh(a.gate_ffn) : 1.0f;
-        // The attention kernels take their scores in log2 units straight from the matrix pipe (attention_tiles.hip): 80^-0.5 * log2(e)
-        // is folded into the query projection here, once, BEFORE the rounding to bf16 that the upload applies anyway (as mme_load_vit does)
-        const float qsc = 0.11180339887498949f * 1.44269504088896341f;
-        std::vector<float> qw_s((size_t)TD * TD);
-        for (size_t i = 0; i < qw_s.size(); ++i) qw_s[i] = a.q_w[i] * qsc;
-        const float* qkv[3] = {qw_s.data(), a.k_w, a.v_w};
-        const float* nob[3] = {nullptr, nullptr, nullptr};
-        const size_t r3[3] = {TD, TD, TD};
-        if ((r = upload_folded(c, qkv, nob, r3, 3, TD, a.ln1_g, a.ln1_b, &Ld.qkv_wf, &Ld.qkv_cs, &Ld.qkv_bf))) return r;
-        const float* o[1] = {a.o_w};
-        const size_t r1[1] = {TD};
-        if ((r = upload_bf16(c, o, r1, 1, TD, &Ld.o_w, ga))) return r;
-        const float* f1[1] = {a.fc1_w};
-        const float* f1b[1] = {a.fc1_b};
-        const size_t rf[1] = {TF};
-        if ((r = upload_folded(c, f1, f1b, rf, 1, TD, a.ln2_g, a.ln2_b, &Ld.fc1_wf, &Ld.fc1_cs, &Ld.fc1_bf))) return r;
-        const float* f2[1] = {a.fc2_w};
-        if ((r = upload_bf16(c, f2, r1, 1, TF, &Ld.fc2_w, gf))) return r;
-        if ((r = upload_scaled_f32(c, a.fc2_b, TD, gf, &Ld.fc2_b))) return r;
-    }
-    return MME_OK;
+    return load_tile(c, w, HostPrep{c});
 }
-
-}  // extern "C"
-
-namespace {
-
-struct TileStaged {
-    const void *cls, *patch_w, *pos, *tilepos, *pre, *post, *lnpre_g, *lnpre_b, *lnpost_g, *lnpost_b;
-    struct Layer {
-        const void *ln1_g, *ln1_b, *q_w, *k_w, *v_w, *o_w, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
-    };
-    std::vector<Layer> layer;
-};
-
-// one walk over the checkpoint's tensors (WeightStage: sizes the staging buffer when dry, copies afterwards)
-void stage_tile(WeightStage& st, const mme_tile_vit_weights* w, TileStaged& d) {
-    const size_t D = TD, F = TF;
-    d.cls = st.put(w->class_embedding, D);
-    d.patch_w = st.put(w->patch_w, D * TPDIM);
-    d.pos = st.put(w->pos_emb, (size_t)TTOK * D);
-    d.tilepos = st.put(w->tile_pos_emb, (size_t)TARATIOS * TTILES * TTOK * D);
-    d.pre = st.put(w->pre_emb, (size_t)TARATIOS * TTILES * D);
-    d.post = st.put(w->post_emb, (size_t)TARATIOS * TTILES * D);
-    d.lnpre_g = st.put(w->ln_pre_g, D); d.lnpre_b = st.put(w->ln_pre_b, D);
-    d.lnpost_g = st.put(w->ln_post_g, D); d.lnpost_b = st.put(w->ln_post_b, D);
-    const int L = w->layers + w->global_layers;
-    d.layer.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const mme_tile_layer& a = w->layer[l];
-        TileStaged::Layer& X = d.layer[l];
-        X.ln1_g = st.put(a.ln1_g, D); X.ln1_b = st.put(a.ln1_b, D);
-        X.q_w = st.put(a.q_w, D * D); X.k_w = st.put(a.k_w, D * D); X.v_w = st.put(a.v_w, D * D); X.o_w = st.put(a.o_w, D * D);
-        X.ln2_g = st.put(a.ln2_g, D); X.ln2_b = st.put(a.ln2_b, D);
-        X.fc1_w = st.put(a.fc1_w, F * D); X.fc1_b = st.put(a.fc1_b, F);
-        X.fc2_w = st.put(a.fc2_w, D * F); X.fc2_b = st.put(a.fc2_b, D);
-    }
-}
-
-// mme_load_tile_vit's sequence of uploads, buffer for buffer, by the kernels of weight_prep.hip
-int prepare_tile(mme_ctx* c, int dt, const mme_tile_vit_weights* w, const TileStaged& d, hipStream_t s) {
-    TileVitDev* t = c->tv;
-    int r;
-    const size_t D = TD, F = TF;
-    const float g_pos = std::tanh(w->pos_gate), g_pre = std::tanh(w->pre_gate), g_post = std::tanh(w->post_gate);
-    if ((r = prep_table(c, dt, d.cls, D, 1.f, false, &t->cls, s))) return r;
-    if ((r = prep_table(c, dt, d.pos, (size_t)TTOK * D, 1.0f - g_pos, true, &t->pos, s))) return r;
-    if ((r = prep_table(c, dt, d.tilepos, (size_t)TARATIOS * TTILES * TTOK * D, g_pos, true, &t->tilepos, s))) return r;
-    if ((r = prep_table(c, dt, d.pre, (size_t)TARATIOS * TTILES * D, g_pre, true, &t->pre, s))) return r;
-    if ((r = prep_table(c, dt, d.post, (size_t)TARATIOS * TTILES * D, g_post, true, &t->post, s))) return r;
-    if ((r = prep_table(c, dt, d.lnpre_g, D, 1.f, false, &t->lnpre_g, s))) return r;
-    if ((r = prep_table(c, dt, d.lnpre_b, D, 1.f, false, &t->lnpre_b, s))) return r;
-    if ((r = prep_table(c, dt, d.lnpost_g, D, 1.f, false, &t->lnpost_g, s))) return r;
-    if ((r = prep_table(c, dt, d.lnpost_b, D, 1.f, false, &t->lnpost_b, s))) return r;
-    {
-        void* p;
-        if ((r = alloc_weight(c, F * sizeof(float), &p))) return r;
-        HIP_TRY(c, hipMemsetAsync(p, 0, F * sizeof(float), s));
-        t->zeros = (float*)p;
-        if ((r = alloc_weight(c, D * TPDIMP * 2, &p))) return r;
-        HIP_TRY(c, launch_wp_pad(dt, d.patch_w, TD, TPDIM, TPDIMP, p, s));
-        t->patch_w = (bf16_t*)p;
-    }
-    const int L = w->layers + w->global_layers;
-    t->layer.resize(L);
-    const size_t rD[3] = {D, D, D}, rF[1] = {F};
-    const float qsc = 0.11180339887498949f * 1.44269504088896341f;  // mme_load_tile_vit: 80^-0.5 log2(e)
-    for (int l = 0; l < L; ++l) {
-        const mme_tile_layer& a = w->layer[l];
-        const TileStaged::Layer& X = d.layer[l];
-        TileLayerDev& Ld = t->layer[l];
-        const float ga = a.gated ? std::tanh(a.gate_attn) : 1.0f, gf = a.gated ? std::tanh(a.gate_ffn) : 1.0f;
-        const WpFoldSrc fq[3] = {{X.q_w, nullptr, qsc, 1}, {X.k_w, nullptr, 1.f, 0}, {X.v_w, nullptr, 1.f, 0}};
-        if ((r = prep_folded(c, dt, fq, rD, 3, D, X.ln1_g, X.ln1_b, &Ld.qkv_wf, &Ld.qkv_cs, &Ld.qkv_bf, s))) return r;
-        if ((r = prep_bf16(c, dt, &X.o_w, rD, 1, D, &Ld.o_w, ga, ga != 1.0f, s))) return r;
-        const WpFoldSrc f1[1] = {{X.fc1_w, X.fc1_b, 1.f, 0}};
-        if ((r = prep_folded(c, dt, f1, rF, 1, D, X.ln2_g, X.ln2_b, &Ld.fc1_wf, &Ld.fc1_cs, &Ld.fc1_bf, s))) return r;
-        if ((r = prep_bf16(c, dt, &X.fc2_w, rD, 1, F, &Ld.fc2_w, gf, gf != 1.0f, s))) return r;
-        if ((r = prep_table(c, dt, X.fc2_b, D, gf, true, &Ld.fc2_b, s))) return r;
-    }
-    return MME_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int mme_load_tile_vit_as(mme_ctx* c, const mme_tile_vit_weights* w, int dtype, void* stream) {
     int r;
     if ((r = validate_tile_weights(c, w))) return r;
-    if (dtype < MME_DT_F32 || dtype > MME_DT_F16)
-        return fail(c, MME_E_ARG, "mme_load_tile_vit_as: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", dtype);
-    for (int l = 0; l < w->layers + w->global_layers; ++l) {
-        const mme_tile_layer& a = w->layer[l];
-        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.k_w, a.v_w, a.o_w, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
-        for (const float* p : all)
-            if (!p) return fail(c, MME_E_ARG, "mme_load_tile_vit: layer %d has a null tensor pointer", l);
-    }
-    if ((r = new_tile_dev(c, w))) return r;
-    hipStream_t s = (hipStream_t)stream;
-    WeightStage st(dtype, s);
-    TileStaged d;
-    stage_tile(st, w, d);
-    if ((r = st.reserve(c))) return r;
-    stage_tile(st, w, d);
-    if (st.err != hipSuccess) {
-        r = fail(c, MME_E_HIP, "mme_load_tile_vit_as: copying the checkpoint's bytes to the device: %s", hipGetErrorString(st.err));
-    } else {
-        r = prepare_tile(c, dtype, w, d, s);
-    }
-    if (r == MME_OK) {
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) r = fail(c, MME_E_HIP, "mme_load_tile_vit_as: weight preparation: %s", hipGetErrorString(e));
-    }
-    st.release();
-    return r;
+    if ((r = check_load_dtype(c, dtype, "mme_load_tile_vit_as"))) return r;
+    return load_tile(c, w, DevPrep(c, dtype, stream, "mme_load_tile_vit_as"));
 }
 
 int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* aspect_ids_host, const int32_t* num_tiles_host, int n,

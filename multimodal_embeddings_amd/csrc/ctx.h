@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -26,7 +27,7 @@ struct LayerDev {
 };
 
 // The ViT/16 @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
-// Supported set (validate_vit_weights): image 224, patch 16, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
+// Supported set (validate_vit_weights, weight_load.hip): image 224, patch 16, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
 // <= 8192, 1..64 layers.
 struct VitGeom {
     int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
@@ -88,29 +89,53 @@ int fail(mme_ctx* c, int code, const char* fmt, ...);
     } while (0)
 
 int ensure(mme_ctx* c, DevBuf& b, size_t bytes);
-uint16_t f32_to_bf16_rne(float f);
-int upload_f32(mme_ctx* c, const float* src, size_t n, float** dst);
-// concatenates up to three [rows_i, cols] f32 matrices row-wise, converts to bf16, uploads; `scale` multiplies every value first
-int upload_bf16(mme_ctx* c, const float* const* srcs, const size_t* rows, int nsrc, size_t cols, bf16_t** dst, float scale = 1.0f);
-// LayerNorm folding for `y = W . LN(x) + b` (bs[i] may be null: no bias)
-int upload_folded(mme_ctx* c, const float* const* ws, const float* const* bs, const size_t* rows, int nsrc, size_t cols, const float* gamma,
-                  const float* beta, bf16_t** wf, float** cs, float** bf);
+// f32 -> bf16, round to nearest even, NaN kept quiet (bf16_rne_bits of weight_prep.hip is its device form, bit for bit)
+inline uint16_t f32_to_bf16_rne(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
 void tile_vit_free(mme_ctx* c);
-// argument checks shared by mme_load_vit and mme_load_vit_as (`who` names the f32 loader in the messages of both): the
-// geometry against the supported set, every tensor pointer.  Touches nothing in the context but its error text.
-int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who);
-// A load replaces what the context held: begin frees the previous ViT weights (after the device has drained), takes the
-// new geometry and leaves the context unloaded; end marks the buffers allocated since as the ViT weights and, when
-// `ok`, the context as loaded.  A load that fails in between leaves the context without weights.
-int begin_vit_load(mme_ctx* c, const mme_vit_weights* w);
-void end_vit_load(mme_ctx* c, bool ok);
 
-// ---- device-side weight preparation (weight_prep.hip): the upload_* helpers above, from staged device bytes of `dt` ----
-// hipMalloc registered in c->allocs / c->alloc_bytes
-int alloc_weight(mme_ctx* c, size_t bytes, void** out);
+// ---- weight loading (weight_load.hip) ---------------------------------------------------------------------------------
+// Each encoder's load is ONE sequence of prepared buffers (prepare_vit in weight_load.hip, prepare_tile in
+// capi_tilevit.hip), written against the operations that the two preparers below share.  The sequence reads the caller's
+// weights struct: through HostPrep its pointers are the caller's host f32 tensors, through DevPrep they are the device
+// addresses of the staged checkpoint bytes (elements of `dt`).  Both produce the same bits
+// (tests/test_gpu_checkpoint.py compares the fingerprints):
+//   a factor is applied in f32, and rounded to f32, before anything else, and only where `scaled` says so;
+//   bf16 rounding is nearest-even with NaN kept quiet;
+//   the LayerNorm fold is W' = bf16(w * gamma), colsum = sum_k W' (of the ROUNDED values, so that r * (W'x - mu * colsum)
+//   is exact algebra), bias' = b + sum_k w * beta (a null b counts as 0), both sums over k ascending in one f64
+//   accumulator per row.
+// Both register every prepared buffer in c->allocs / c->alloc_bytes, in creation order.
+int check_load_dtype(mme_ctx* c, int dtype, const char* who);
+
+// The host loops (f32 in): prepared on the CPU, one upload per buffer.  The reference the kernels are tested against.
+struct HostPrep {
+    mme_ctx* c;
+    template <class Walk>
+    int stage(Walk&&) { return MME_OK; }  // the tensors are read where the caller holds them
+    int finish(int r) { return r; }
+    // f32 table; `scaled`: every value times `scale` first
+    int table(const void* src, size_t n, float scale, bool scaled, float** dst);
+    // concatenated f32 table; the first part times `scale0` when `scaled0`
+    int table_cat(const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst);
+    // up to three [rows_i, cols] matrices, row-wise, as bf16; the first part times `scale0` when `scaled0`
+    int bf16(const void* const* srcs, const size_t* rows, int nsrc, size_t cols, float scale0, bool scaled0, bf16_t** dst);
+    // LayerNorm folding for `y = W . LN(x) + b` of up to three row blocks
+    int folded(const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf, float** cs, float** bf);
+    // [rows, cols] -> bf16 [rows, cols_padded], zero columns behind
+    int padded(const void* src, int rows, int cols, int cols_padded, bf16_t** dst);
+    int zeros(size_t n, float** dst);
+};
+
 // The checkpoint's bytes on the device for the duration of one load.  Two walks over the tensors with the same calls:
-// the first (dry) sizes the buffer, reserve() allocates it, the second copies and returns the device addresses
-// (16-byte aligned).  release() waits for the stream and frees: nothing of it stays in the context.
+// the first (dry) sizes the buffer and leaves every pointer as it is, reserve() allocates it, the second copies and
+// returns the device addresses (16-byte aligned).  release() waits for the stream and frees: nothing of it stays in the
+// context.
 struct WeightStage {
     char* base = nullptr;
     size_t total = 0, used = 0, esz;
@@ -122,16 +147,35 @@ struct WeightStage {
     const void* put(const void* host, size_t n);
     void release();
 };
-// dt -> f32 table, `scaled`: every value times `scale` first (upload_f32 / upload_scaled_f32)
-int prep_table(mme_ctx* c, int dt, const void* src, size_t n, float scale, bool scaled, float** dst, hipStream_t s);
-// upload_f32_cat; the first part times `scale0` when `scaled0`
-int prep_table_cat(mme_ctx* c, int dt, const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst, hipStream_t s);
-// upload_bf16; the first part times `scale0` when `scaled0`
-int prep_bf16(mme_ctx* c, int dt, const void* const* srcs, const size_t* rows, int nsrc, size_t cols, bf16_t** dst, float scale0, bool scaled0,
-              hipStream_t s);
-// upload_folded
-int prep_folded(mme_ctx* c, int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf,
-                float** cs, float** bf, hipStream_t s);
+
+// The kernels of weight_prep.hip on staged bytes of `dt` (f32, bf16 or f16): HostPrep's operations, launched on `s`.
+struct DevPrep {
+    mme_ctx* c;
+    int dt;
+    hipStream_t s;
+    const char* who;  // the entry point, for the error texts
+    WeightStage st;
+    DevPrep(mme_ctx* c_, int dt_, void* stream, const char* who_) : c(c_), dt(dt_), s((hipStream_t)stream), who(who_), st(dt_, s) {}
+    // walk(put) calls put(pointer, elements) for every tensor of a weights struct; afterwards the pointers are device addresses
+    template <class Walk>
+    int stage(Walk&& walk) {
+        auto put = [this](const float*& p, size_t n) { p = (const float*)st.put(p, n); };
+        walk(put);
+        int r = st.reserve(c);
+        if (r) return r;
+        walk(put);
+        if (st.err != hipSuccess) return fail(c, MME_E_HIP, "%s: copying the checkpoint's bytes to the device: %s", who, hipGetErrorString(st.err));
+        return MME_OK;
+    }
+    // waits for the preparation, frees the staged bytes
+    int finish(int r);
+    int table(const void* src, size_t n, float scale, bool scaled, float** dst);
+    int table_cat(const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst);
+    int bf16(const void* const* srcs, const size_t* rows, int nsrc, size_t cols, float scale0, bool scaled0, bf16_t** dst);
+    int folded(const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf, float** cs, float** bf);
+    int padded(const void* src, int rows, int cols, int cols_padded, bf16_t** dst);
+    int zeros(size_t n, float** dst);
+};
 
 struct Timed {
     mme_ctx* c;

@@ -1,0 +1,372 @@
+// Weight loading: the two preparers (ctx.h) and the ViT/16 load sequence written once against them.
+//   HostPrep   f32 host tensors, prepared by the loops below and uploaded buffer by buffer (mme_load_vit, mme_load_tile_vit)
+//   DevPrep    the checkpoint's own bytes (f32, bf16 or f16) staged on the device, prepared by the kernels of
+//              weight_prep.hip (mme_load_vit_as, mme_load_tile_vit_as)
+// The host loops are the reference of the kernels: every kernel keeps the operations of its loop and their order, and
+// tests/test_gpu_checkpoint.py holds the two to equal fingerprints.  The tile-ViT sequence is prepare_tile in
+// capi_tilevit.hip, beside the tower's device record.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "ctx.h"
+
+int check_load_dtype(mme_ctx* c, int dtype, const char* who) {
+    if (dtype < MME_DT_F32 || dtype > MME_DT_F16) return fail(c, MME_E_ARG, "%s: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", who, dtype);
+    return MME_OK;
+}
+
+namespace {
+
+// hipMalloc of n elements, registered in c->allocs / c->alloc_bytes: every prepared buffer of both preparers
+template <class T>
+int alloc_weight(mme_ctx* c, size_t n, T** out) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
+    c->allocs.push_back(p);
+    c->alloc_bytes.push_back(n * sizeof(T));
+    *out = (T*)p;
+    return MME_OK;
+}
+
+// ---- HostPrep ------------------------------------------------------------------------------------------------------------
+template <class T>
+int upload(mme_ctx* c, const void* h, size_t n, T** dst) {
+    int r;
+    if ((r = alloc_weight(c, n, dst))) return r;
+    HIP_TRY(c, hipMemcpy(*dst, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return MME_OK;
+}
+
+// dst[i] = src[i] (* scale); the product is rounded to f32 here, before whatever follows
+void copy_scaled(const float* src, size_t n, float scale, bool scaled, float* dst) {
+    if (scaled)
+        for (size_t i = 0; i < n; ++i) dst[i] = src[i] * scale;
+    else
+        memcpy(dst, src, n * sizeof(float));
+}
+
+}  // namespace
+
+int HostPrep::table(const void* src, size_t n, float scale, bool scaled, float** dst) {
+    return scaled ? table_cat(&src, &n, 1, scale, true, dst) : upload(c, src, n, dst);  // a plain table goes up as it is
+}
+
+int HostPrep::table_cat(const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += n[i];
+    std::vector<float> h(total);
+    size_t o = 0;
+    for (int i = 0; i < nsrc; o += n[i], ++i) copy_scaled((const float*)srcs[i], n[i], scale0, scaled0 && i == 0, h.data() + o);
+    return upload(c, h.data(), total, dst);
+}
+
+int HostPrep::bf16(const void* const* srcs, const size_t* rows, int nsrc, size_t cols, float scale0, bool scaled0, bf16_t** dst) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += rows[i] * cols;
+    std::vector<uint16_t> h(total);
+    size_t o = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        const float* src = (const float*)srcs[i];
+        const size_t n = rows[i] * cols;
+        if (scaled0 && i == 0)
+            for (size_t k = 0; k < n; ++k) h[o++] = f32_to_bf16_rne(src[k] * scale0);
+        else
+            for (size_t k = 0; k < n; ++k) h[o++] = f32_to_bf16_rne(src[k]);
+    }
+    return upload(c, h.data(), total, dst);
+}
+
+int HostPrep::folded(const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma_, const void* beta_, bf16_t** wf, float** cs,
+                     float** bf) {
+    const float *gamma = (const float*)gamma_, *beta = (const float*)beta_;
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += rows[i];
+    std::vector<uint16_t> hw(total * cols);
+    std::vector<float> hcs(total), hbf(total);
+    size_t o = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        const float *ws = (const float*)srcs[i].w, *bs = (const float*)srcs[i].b;
+        const float scale = srcs[i].scale;
+        const bool scaled = srcs[i].scaled != 0;
+        for (size_t n = 0; n < rows[i]; ++n, ++o) {
+            double s = 0.0, t = 0.0;
+            for (size_t k = 0; k < cols; ++k) {
+                const float w = scaled ? ws[n * cols + k] * scale : ws[n * cols + k];
+                const uint16_t q = f32_to_bf16_rne(w * gamma[k]);
+                hw[o * cols + k] = q;
+                uint32_t u = (uint32_t)q << 16;
+                float wq;
+                memcpy(&wq, &u, 4);
+                s += (double)wq;
+                t += (double)w * (double)beta[k];
+            }
+            const float b = !bs ? 0.f : (scaled ? bs[n] * scale : bs[n]);
+            hcs[o] = (float)s;
+            hbf[o] = (float)((double)b + t);
+        }
+    }
+    int r;
+    if ((r = upload(c, hw.data(), hw.size(), wf))) return r;
+    if ((r = upload(c, hcs.data(), total, cs))) return r;
+    return upload(c, hbf.data(), total, bf);
+}
+
+int HostPrep::padded(const void* src, int rows, int cols, int cols_padded, bf16_t** dst) {
+    std::vector<uint16_t> h((size_t)rows * cols_padded, 0);  // bf16 +0.0
+    for (int n = 0; n < rows; ++n)
+        for (int k = 0; k < cols; ++k) h[(size_t)n * cols_padded + k] = f32_to_bf16_rne(((const float*)src)[(size_t)n * cols + k]);
+    return upload(c, h.data(), h.size(), dst);
+}
+
+int HostPrep::zeros(size_t n, float** dst) {
+    std::vector<float> z(n, 0.f);
+    return upload(c, z.data(), n, dst);
+}
+
+// ---- DevPrep -------------------------------------------------------------------------------------------------------------
+int WeightStage::reserve(mme_ctx* c) {
+    hipError_t e = hipMalloc((void**)&base, used ? used : 16);
+    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc(%zu) for the staged checkpoint bytes: %s", used, hipGetErrorString(e));
+    total = used;
+    used = 0;
+    dry = false;
+    return MME_OK;
+}
+
+const void* WeightStage::put(const void* host, size_t n) {
+    const size_t bytes = n * esz, off = used;
+    used += (bytes + 15) & ~(size_t)15;
+    if (dry) return host;
+    if (err != hipSuccess) return nullptr;
+    if (used > total) {
+        err = hipErrorInvalidValue;
+        return nullptr;
+    }
+    err = hipMemcpyAsync(base + off, host, bytes, hipMemcpyHostToDevice, s);
+    return base + off;
+}
+
+void WeightStage::release() {
+    if (base) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(base);
+    }
+    base = nullptr;
+}
+
+int DevPrep::finish(int r) {
+    if (r == MME_OK) {
+        hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) r = fail(c, MME_E_HIP, "%s: weight preparation: %s", who, hipGetErrorString(e));
+    }
+    st.release();
+    return r;
+}
+
+int DevPrep::table(const void* src, size_t n, float scale, bool scaled, float** dst) { return table_cat(&src, &n, 1, scale, scaled, dst); }
+
+int DevPrep::table_cat(const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += n[i];
+    int r;
+    if ((r = alloc_weight(c, total, dst))) return r;
+    size_t o = 0;
+    for (int i = 0; i < nsrc; o += n[i], ++i)  // one launch per part into its slice
+        HIP_TRY(c, launch_wp_convert(dt, srcs[i], n[i], scale0, scaled0 && i == 0, false, *dst + o, s));
+    return MME_OK;
+}
+
+int DevPrep::bf16(const void* const* srcs, const size_t* rows, int nsrc, size_t cols, float scale0, bool scaled0, bf16_t** dst) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += rows[i] * cols;
+    int r;
+    if ((r = alloc_weight(c, total, dst))) return r;
+    size_t o = 0;
+    for (int i = 0; i < nsrc; o += rows[i] * cols, ++i)
+        HIP_TRY(c, launch_wp_convert(dt, srcs[i], rows[i] * cols, scale0, scaled0 && i == 0, true, *dst + o, s));
+    return MME_OK;
+}
+
+int DevPrep::folded(const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf, float** cs,
+                    float** bf) {
+    size_t total = 0;
+    for (int i = 0; i < nsrc; ++i) total += rows[i];
+    int r;
+    if ((r = alloc_weight(c, total * cols, wf))) return r;
+    if ((r = alloc_weight(c, total, cs))) return r;
+    if ((r = alloc_weight(c, total, bf))) return r;
+    HIP_TRY(c, launch_wp_fold(dt, srcs, rows, nsrc, (int)cols, gamma, beta, *wf, *cs, *bf, s));
+    return MME_OK;
+}
+
+int DevPrep::padded(const void* src, int rows, int cols, int cols_padded, bf16_t** dst) {
+    int r;
+    if ((r = alloc_weight(c, (size_t)rows * cols_padded, dst))) return r;
+    HIP_TRY(c, launch_wp_pad(dt, src, rows, cols, cols_padded, *dst, s));
+    return MME_OK;
+}
+
+int DevPrep::zeros(size_t n, float** dst) {
+    int r;
+    if ((r = alloc_weight(c, n, dst))) return r;
+    HIP_TRY(c, hipMemsetAsync(*dst, 0, n * sizeof(float), s));
+    return MME_OK;
+}
+
+// ---- ViT/16 --------------------------------------------------------------------------------------------------------------
+namespace {
+
+// argument checks of both ViT loaders (the messages of both name the f32 loader): the geometry against the supported
+// set, every tensor pointer.  Touches nothing in the context but its error text.
+int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w) {
+    const char* who = "mme_load_vit";
+    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
+    // every refusal names the field, the value found and what is supported
+    if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
+    if (w->patch_size != VIT_PATCH) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: %d", who, w->patch_size, VIT_PATCH);
+    if (!vit_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 384, 768, 1024", who, w->hidden);
+    if (w->heads * VIT_DH != w->hidden)
+        return fail(c, MME_E_ARG, "%s: heads = %d at hidden = %d; supported: heads of %d, heads = hidden / %d = %d", who, w->heads, w->hidden, VIT_DH, VIT_DH,
+                    w->hidden / VIT_DH);
+    if (w->mlp < 64 || (w->mlp % 64) != 0 || w->mlp > VIT_MAX_F)
+        return fail(c, MME_E_ARG, "%s: mlp = %d; supported: multiples of 64 up to %d", who, w->mlp, VIT_MAX_F);
+    if (w->layers < 1 || w->layers > VIT_MAX_L) return fail(c, MME_E_ARG, "%s: layers = %d; supported: 1..%d", who, w->layers, VIT_MAX_L);
+    if (!w->cls_token || !w->pos_emb || !w->patch_w || !w->patch_b || !w->lnf_g || !w->lnf_b || !w->layer)
+        return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
+    for (int l = 0; l < w->layers; ++l) {
+        const mme_vit_layer& a = w->layer[l];
+        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+        for (const float* p : all)
+            if (!p) return fail(c, MME_E_ARG, "%s: layer %d has a null tensor pointer", who, l);
+    }
+    return MME_OK;
+}
+
+// A load replaces what the context held: begin frees the previous ViT weights (after the device has drained), takes the
+// new geometry and leaves the context unloaded; end marks the buffers allocated since as the ViT weights and, when
+// `ok`, the context as loaded.  A load that fails in between leaves the context without weights.
+int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->loaded = false;
+    if (c->vit_alloc_hi > c->vit_alloc_lo) {
+        HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
+        for (size_t i = c->vit_alloc_lo; i < c->vit_alloc_hi; ++i) (void)hipFree(c->allocs[i]);
+        c->allocs.erase(c->allocs.begin() + c->vit_alloc_lo, c->allocs.begin() + c->vit_alloc_hi);
+        c->alloc_bytes.erase(c->alloc_bytes.begin() + c->vit_alloc_lo, c->alloc_bytes.begin() + c->vit_alloc_hi);
+    }
+    c->vit_alloc_lo = c->vit_alloc_hi = c->allocs.size();
+    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp};
+    c->ln_eps = w->ln_eps;
+    c->layer.assign((size_t)w->layers, LayerDev{});
+    return MME_OK;
+}
+
+void end_vit_load(mme_ctx* c, bool ok) {
+    c->vit_alloc_hi = c->allocs.size();
+    c->loaded = ok;
+}
+
+// every tensor of the checkpoint with its element count (the order of the staged bytes)
+template <class Fn>
+void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&& f) {
+    const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
+    f(w.cls_token, D);
+    f(w.pos_emb, (size_t)VIT_T * D);
+    f(w.patch_w, D * VIT_PATCH_DIM);
+    f(w.patch_b, D);
+    f(w.lnf_g, D);
+    f(w.lnf_b, D);
+    for (mme_vit_layer& a : layer) {
+        f(a.ln1_g, D); f(a.ln1_b, D);
+        f(a.q_w, D * D); f(a.q_b, D);
+        f(a.k_w, D * D); f(a.k_b, D);
+        f(a.v_w, D * D); f(a.v_b, D);
+        f(a.o_w, D * D); f(a.o_b, D);
+        f(a.ln2_g, D); f(a.ln2_b, D);
+        f(a.fc1_w, F * D); f(a.fc1_b, F);
+        f(a.fc2_w, D * F); f(a.fc2_b, D);
+    }
+}
+
+// The prepared buffers of the ViT/16 encoder, in the order mme_weights_fingerprint reports them: cls, pos, patch_b, lnf_g,
+// lnf_b, patch_w, then 18 per layer.
+template <class P>
+int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
+    int r;
+    const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
+    const size_t rD[3] = {D, D, D}, rF[1] = {F};
+    auto plain = [&](const float* src, size_t n, float** dst) { return p.table(src, n, 1.f, false, dst); };
+    auto plain_bf16 = [&](const float* src, const size_t* rows, size_t cols, bf16_t** dst) {
+        const void* s[1] = {src};
+        return p.bf16(s, rows, 1, cols, 1.f, false, dst);
+    };
+    if ((r = plain(w.cls_token, D, &c->cls))) return r;
+    if ((r = plain(w.pos_emb, (size_t)VIT_T * D, &c->pos))) return r;
+    if ((r = plain(w.patch_b, D, &c->patch_b))) return r;
+    if ((r = plain(w.lnf_g, D, &c->lnf_g))) return r;
+    if ((r = plain(w.lnf_b, D, &c->lnf_b))) return r;
+    if ((r = plain_bf16(w.patch_w, rD, VIT_PATCH_DIM, &c->patch_w))) return r;
+    // The attention kernel takes its scores in log2 units straight from the matrix pipe (attention.hip, PRESCALED):
+    // dh^-0.5 * log2(e) is folded into the query projection here, once, BEFORE the rounding to bf16 that the preparation
+    // applies anyway -- softmax(q.k / 8) = exp2(q'.k - c) / sum with q' = (W_q' x + b_q'), W_q' = sc W_q, b_q' = sc b_q.
+    const float sc = 0.125f * 1.44269504088896341f;
+    for (int l = 0; l < w.layers; ++l) {
+        const mme_vit_layer& a = w.layer[l];
+        LayerDev& L = c->layer[l];
+        if ((r = plain(a.ln1_g, D, &L.ln1_g))) return r;
+        if ((r = plain(a.ln1_b, D, &L.ln1_b))) return r;
+        if ((r = plain(a.ln2_g, D, &L.ln2_g))) return r;
+        if ((r = plain(a.ln2_b, D, &L.ln2_b))) return r;
+        const void* qkv[3] = {a.q_w, a.k_w, a.v_w};
+        if ((r = p.bf16(qkv, rD, 3, D, sc, true, &L.qkv_w))) return r;
+        const void* qkvb[3] = {a.q_b, a.k_b, a.v_b};
+        if ((r = p.table_cat(qkvb, rD, 3, sc, true, &L.qkv_b))) return r;
+        const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
+        if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
+        if ((r = plain_bf16(a.o_w, rD, D, &L.o_w))) return r;
+        if ((r = plain(a.o_b, D, &L.o_b))) return r;
+        if ((r = plain_bf16(a.fc1_w, rF, D, &L.fc1_w))) return r;
+        if ((r = plain(a.fc1_b, F, &L.fc1_b))) return r;
+        const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
+        if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf))) return r;
+        if ((r = plain_bf16(a.fc2_w, rD, F, &L.fc2_w))) return r;
+        if ((r = plain(a.fc2_b, D, &L.fc2_b))) return r;
+    }
+    return MME_OK;
+}
+
+template <class P>
+int load_vit(mme_ctx* c, const mme_vit_weights* w, P p) {
+    int r;
+    if ((r = begin_vit_load(c, w))) return r;
+    // the preparer's view of the tensors: the caller's pointers, or where the preparer staged them
+    std::vector<mme_vit_layer> layer(w->layer, w->layer + w->layers);
+    mme_vit_weights v = *w;
+    v.layer = layer.data();
+    r = p.stage([&](auto& put) { each_vit_tensor(v, layer, put); });
+    if (r == MME_OK) r = prepare_vit(c, p, v);
+    r = p.finish(r);
+    end_vit_load(c, r == MME_OK);
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mme_load_vit(mme_ctx* c, const mme_vit_weights* w) {
+    int r;
+    if ((r = validate_vit_weights(c, w))) return r;
+    return load_vit(c, w, HostPrep{c});
+}
+
+int mme_load_vit_as(mme_ctx* c, const mme_vit_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_vit_weights(c, w))) return r;
+    if ((r = check_load_dtype(c, dtype, "mme_load_vit_as"))) return r;
+    return load_vit(c, w, DevPrep(c, dtype, stream, "mme_load_vit_as"));
+}
+
+}  // extern "C"

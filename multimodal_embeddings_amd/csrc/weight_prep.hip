@@ -1,7 +1,7 @@
-// Device-side weight preparation: what the host loops of capi.hip (upload_bf16, upload_folded, upload_f32_cat) and
-// capi_tilevit.hip (upload_scaled_f32, the patch-weight padding) compute, restated as kernels over a staged copy of the
-// checkpoint's own bytes (f32, bf16 or f16).  Every kernel keeps the operations of its host loop and their order, so the
-// prepared buffers are bit-identical to the host path's (tests/test_gpu_checkpoint.py compares their fingerprints):
+// Device-side weight preparation: the kernels behind DevPrep (ctx.h, weight_load.hip), over a staged copy of the
+// checkpoint's own bytes (f32, bf16 or f16).  Every kernel keeps the operations of HostPrep's loop for the same buffer and
+// their order, so the prepared buffers are bit-identical to the host preparer's (tests/test_gpu_checkpoint.py compares
+// their fingerprints):
 //   convert  dtype -> f32 (exact), optional f32 scale, -> f32 table or -> bf16 (round to nearest even, NaN kept quiet);
 //            the parts of a concatenated buffer (Q | K | V) are one launch each into their slice of it
 //   pad      [rows, cols] -> bf16 [rows, cols_padded], zero columns behind
@@ -23,7 +23,7 @@ constexpr int WP_MAX_BLOCKS = 2048;
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-// f32_to_bf16_rne of capi.hip, bit for bit
+// f32_to_bf16_rne of ctx.h, bit for bit
 __device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
     uint32_t u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN stays NaN
@@ -73,7 +73,7 @@ struct ConvertArgs {
     const void* src;
     unsigned long long chunks;  // of 8 elements
     float scale;
-    int scaled;    // multiply by `scale` (the host loops skip the multiplication where the factor is 1)
+    int scaled;    // multiply by `scale` (the load sequences say where; HostPrep skips the multiplication elsewhere too)
     int out_bf16;  // else an f32 table
     void* dst;
 };
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(FOLD_ROWS) void fold_kernel(FoldArgs a) {
             load8<DT>(S.w, (size_t)(lrow0 + r) * K + k0 + k8, v);
             if (S.scaled) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = v[j] * S.scale;  // rounded to f32 HERE, before gamma (as the host's qw_s)
+                for (int j = 0; j < 8; ++j) v[j] = v[j] * S.scale;  // rounded to f32 HERE, before gamma (as HostPrep::folded)
             }
             f32x4 lo, hi;
 #pragma unroll
@@ -349,206 +349,7 @@ hipError_t launch_wp_fold(int dt, const WpFoldSrc* srcs, const size_t* rows, int
     return hipGetLastError();
 }
 
-// ---- the upload helpers of capi.hip, from staged device bytes ----------------------------------------------------------------
-int alloc_weight(mme_ctx* c, size_t bytes, void** out) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc weights: %s", hipGetErrorString(e));
-    c->allocs.push_back(p);
-    c->alloc_bytes.push_back(bytes);
-    *out = p;
-    return MME_OK;
-}
-
-int WeightStage::reserve(mme_ctx* c) {
-    hipError_t e = hipMalloc((void**)&base, used ? used : 16);
-    if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc(%zu) for the staged checkpoint bytes: %s", used, hipGetErrorString(e));
-    total = used;
-    used = 0;
-    dry = false;
-    return MME_OK;
-}
-
-const void* WeightStage::put(const void* host, size_t n) {
-    const size_t bytes = n * esz, off = used;
-    used += (bytes + 15) & ~(size_t)15;
-    if (dry || err != hipSuccess) return nullptr;
-    if (used > total) {
-        err = hipErrorInvalidValue;
-        return nullptr;
-    }
-    err = hipMemcpyAsync(base + off, host, bytes, hipMemcpyHostToDevice, s);
-    return base + off;
-}
-
-void WeightStage::release() {
-    if (base) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(base);
-    }
-    base = nullptr;
-}
-
-int prep_table(mme_ctx* c, int dt, const void* src, size_t n, float scale, bool scaled, float** dst, hipStream_t s) {
-    void* p;
-    int r;
-    if ((r = alloc_weight(c, n * sizeof(float), &p))) return r;
-    HIP_TRY(c, launch_wp_convert(dt, src, n, scale, scaled, false, p, s));
-    *dst = (float*)p;
-    return MME_OK;
-}
-
-int prep_table_cat(mme_ctx* c, int dt, const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst, hipStream_t s) {
-    size_t total = 0;
-    for (int i = 0; i < nsrc; ++i) total += n[i];
-    void* p;
-    int r;
-    if ((r = alloc_weight(c, total * sizeof(float), &p))) return r;
-    size_t o = 0;
-    for (int i = 0; i < nsrc; ++i) {  // only the first part may carry a factor (the query bias): one launch per part
-        HIP_TRY(c, launch_wp_convert(dt, srcs[i], n[i], scale0, scaled0 && i == 0, false, (float*)p + o, s));
-        o += n[i];
-    }
-    *dst = (float*)p;
-    return MME_OK;
-}
-
-int prep_bf16(mme_ctx* c, int dt, const void* const* srcs, const size_t* rows, int nsrc, size_t cols, bf16_t** dst, float scale0, bool scaled0,
-              hipStream_t s) {
-    size_t total = 0;
-    for (int i = 0; i < nsrc; ++i) total += rows[i] * cols;
-    void* p;
-    int r;
-    if ((r = alloc_weight(c, total * 2, &p))) return r;
-    size_t o = 0;
-    for (int i = 0; i < nsrc; ++i) {
-        const size_t n = rows[i] * cols;
-        HIP_TRY(c, launch_wp_convert(dt, srcs[i], n, scale0, scaled0 && i == 0, true, (uint16_t*)p + o, s));
-        o += n;
-    }
-    *dst = (bf16_t*)p;
-    return MME_OK;
-}
-
-int prep_folded(mme_ctx* c, int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf,
-                float** cs, float** bf, hipStream_t s) {
-    size_t total = 0;
-    for (int i = 0; i < nsrc; ++i) total += rows[i];
-    void *pw, *pc, *pb;
-    int r;
-    if ((r = alloc_weight(c, total * cols * 2, &pw))) return r;
-    if ((r = alloc_weight(c, total * sizeof(float), &pc))) return r;
-    if ((r = alloc_weight(c, total * sizeof(float), &pb))) return r;
-    HIP_TRY(c, launch_wp_fold(dt, srcs, rows, nsrc, (int)cols, gamma, beta, pw, (float*)pc, (float*)pb, s));
-    *wf = (bf16_t*)pw;
-    *cs = (float*)pc;
-    *bf = (float*)pb;
-    return MME_OK;
-}
-
-namespace {
-
-struct VitStaged {
-    const void *cls, *pos, *patch_w, *patch_b, *lnf_g, *lnf_b;
-    struct Layer {
-        const void *ln1_g, *ln1_b, *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *o_w, *o_b, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
-    };
-    std::vector<Layer> layer;  // one per layer of the checkpoint
-};
-
-// one walk over the checkpoint's tensors: sizes the staging buffer when `st` is dry, copies into it afterwards
-void stage_vit(WeightStage& st, const mme_vit_weights* w, VitStaged& d) {
-    const size_t D = (size_t)w->hidden, F = (size_t)w->mlp;
-    d.layer.resize((size_t)w->layers);
-    d.cls = st.put(w->cls_token, D);
-    d.pos = st.put(w->pos_emb, (size_t)VIT_T * D);
-    d.patch_w = st.put(w->patch_w, D * VIT_PATCH_DIM);
-    d.patch_b = st.put(w->patch_b, D);
-    d.lnf_g = st.put(w->lnf_g, D);
-    d.lnf_b = st.put(w->lnf_b, D);
-    for (int l = 0; l < w->layers; ++l) {
-        const mme_vit_layer& a = w->layer[l];
-        VitStaged::Layer& L = d.layer[l];
-        L.ln1_g = st.put(a.ln1_g, D); L.ln1_b = st.put(a.ln1_b, D);
-        L.q_w = st.put(a.q_w, D * D); L.q_b = st.put(a.q_b, D);
-        L.k_w = st.put(a.k_w, D * D); L.k_b = st.put(a.k_b, D);
-        L.v_w = st.put(a.v_w, D * D); L.v_b = st.put(a.v_b, D);
-        L.o_w = st.put(a.o_w, D * D); L.o_b = st.put(a.o_b, D);
-        L.ln2_g = st.put(a.ln2_g, D); L.ln2_b = st.put(a.ln2_b, D);
-        L.fc1_w = st.put(a.fc1_w, F * D); L.fc1_b = st.put(a.fc1_b, F);
-        L.fc2_w = st.put(a.fc2_w, D * F); L.fc2_b = st.put(a.fc2_b, D);
-    }
-}
-
-// mme_load_vit's sequence of uploads, buffer for buffer (mme_weights_fingerprint reports them in this order)
-int prepare_vit(mme_ctx* c, int dt, const VitStaged& d, hipStream_t s) {
-    int r;
-    const size_t D = (size_t)c->geom.hidden, F = (size_t)c->geom.mlp;
-    if ((r = prep_table(c, dt, d.cls, D, 1.f, false, &c->cls, s))) return r;
-    if ((r = prep_table(c, dt, d.pos, (size_t)VIT_T * D, 1.f, false, &c->pos, s))) return r;
-    if ((r = prep_table(c, dt, d.patch_b, D, 1.f, false, &c->patch_b, s))) return r;
-    if ((r = prep_table(c, dt, d.lnf_g, D, 1.f, false, &c->lnf_g, s))) return r;
-    if ((r = prep_table(c, dt, d.lnf_b, D, 1.f, false, &c->lnf_b, s))) return r;
-    const size_t rD[3] = {D, D, D}, rF[1] = {F};
-    if ((r = prep_bf16(c, dt, &d.patch_w, rD, 1, VIT_PATCH_DIM, &c->patch_w, 1.f, false, s))) return r;
-    const float sc = 0.125f * 1.44269504088896341f;  // mme_load_vit: dh^-0.5 log2(e), folded into the query projection
-    for (int l = 0; l < c->geom.layers; ++l) {
-        const VitStaged::Layer& a = d.layer[l];
-        LayerDev& L = c->layer[l];
-        if ((r = prep_table(c, dt, a.ln1_g, D, 1.f, false, &L.ln1_g, s))) return r;
-        if ((r = prep_table(c, dt, a.ln1_b, D, 1.f, false, &L.ln1_b, s))) return r;
-        if ((r = prep_table(c, dt, a.ln2_g, D, 1.f, false, &L.ln2_g, s))) return r;
-        if ((r = prep_table(c, dt, a.ln2_b, D, 1.f, false, &L.ln2_b, s))) return r;
-        const void* qkv[3] = {a.q_w, a.k_w, a.v_w};
-        if ((r = prep_bf16(c, dt, qkv, rD, 3, D, &L.qkv_w, sc, true, s))) return r;
-        const void* qkvb[3] = {a.q_b, a.k_b, a.v_b};
-        if ((r = prep_table_cat(c, dt, qkvb, rD, 3, sc, true, &L.qkv_b, s))) return r;
-        const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
-        if ((r = prep_folded(c, dt, fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf, s))) return r;
-        if ((r = prep_bf16(c, dt, &a.o_w, rD, 1, D, &L.o_w, 1.f, false, s))) return r;
-        if ((r = prep_table(c, dt, a.o_b, D, 1.f, false, &L.o_b, s))) return r;
-        if ((r = prep_bf16(c, dt, &a.fc1_w, rF, 1, D, &L.fc1_w, 1.f, false, s))) return r;
-        if ((r = prep_table(c, dt, a.fc1_b, F, 1.f, false, &L.fc1_b, s))) return r;
-        const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
-        if ((r = prep_folded(c, dt, f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf, s))) return r;
-        if ((r = prep_bf16(c, dt, &a.fc2_w, rD, 1, F, &L.fc2_w, 1.f, false, s))) return r;
-        if ((r = prep_table(c, dt, a.fc2_b, D, 1.f, false, &L.fc2_b, s))) return r;
-    }
-    return MME_OK;
-}
-
-}  // namespace
-
 extern "C" {
-
-int mme_load_vit_as(mme_ctx* c, const mme_vit_weights* w, int dtype, void* stream) {
-    int r;
-    if ((r = validate_vit_weights(c, w, "mme_load_vit"))) return r;
-    if (dtype < MME_DT_F32 || dtype > MME_DT_F16)
-        return fail(c, MME_E_ARG, "mme_load_vit_as: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", dtype);
-    if ((r = begin_vit_load(c, w))) return r;
-    hipStream_t s = (hipStream_t)stream;
-    WeightStage st(dtype, s);
-    VitStaged d;
-    stage_vit(st, w, d);
-    if ((r = st.reserve(c))) {
-        end_vit_load(c, false);
-        return r;
-    }
-    stage_vit(st, w, d);
-    if (st.err != hipSuccess) {
-        r = fail(c, MME_E_HIP, "mme_load_vit_as: copying the checkpoint's bytes to the device: %s", hipGetErrorString(st.err));
-    } else {
-        r = prepare_vit(c, dtype, d, s);
-    }
-    if (r == MME_OK) {
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) r = fail(c, MME_E_HIP, "mme_load_vit_as: weight preparation: %s", hipGetErrorString(e));
-    }
-    st.release();
-    end_vit_load(c, r == MME_OK);
-    return r;
-}
 
 int mme_weights_fingerprint(mme_ctx* c, int cap, uint64_t* out) {
     if (!c || cap < 0 || (cap > 0 && !out)) return fail(c, MME_E_ARG, "mme_weights_fingerprint: null argument or negative capacity");

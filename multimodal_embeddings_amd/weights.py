@@ -69,7 +69,7 @@ VIT_B16 = ViTGeometry()
 VIT_S16 = ViTGeometry(hidden_size=384, num_layers=12, num_heads=6, intermediate_size=1536)
 VIT_L16 = ViTGeometry(hidden_size=1024, num_layers=24, num_heads=16, intermediate_size=4096)
 
-# the geometries the engine is built for (csrc/common.h, csrc/capi.hip validate_vit_weights)
+# the geometries the engine is built for (csrc/common.h, csrc/weight_load.hip validate_vit_weights)
 SUPPORTED_VIT = {"image_size": (224,), "patch_size": (16,), "num_channels": (3,), "hidden_size": (384, 768, 1024), "head_dim": (64,),
                  "intermediate_size": "a multiple of 64 up to 8192", "num_layers": "1..64"}
 

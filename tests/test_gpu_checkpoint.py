@@ -1,8 +1,10 @@
 """Checkpoint directory -> device-side weight preparation (csrc/weight_prep.hip) -> embeddings.
 
-The device path restates the host loops of mme_load_vit / mme_load_tile_vit operation for operation, so everything here
-is EQUALITY: the fingerprints of the prepared buffers (mme_weights_fingerprint) agree word for word with a context loaded
-by the host path from the same values, and the embeddings are bit-equal.  Seed 7: `model_name` used to be ignored, so a
+Each encoder's load is one sequence of buffers (csrc/weight_load.hip, csrc/capi_tilevit.hip) run by two preparers: the host
+loops behind mme_load_vit / mme_load_tile_vit and the kernels behind mme_load_*_as, operation for operation.  So everything
+here is EQUALITY, and it guards the kernels and the host preparer's operations alike: the fingerprints of the prepared
+buffers (mme_weights_fingerprint) agree word for word with a context loaded by the host path from the same values, and
+the embeddings are bit-equal.  Seed 7: `model_name` used to be ignored, so a
 directory of seed-7 weights only gives seed-7 vectors when it is really read."""
 import json
 
