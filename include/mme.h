@@ -527,6 +527,45 @@ int mme_load_tile_vit_as(mme_ctx* ctx, const mme_tile_vit_weights* w, int dtype,
 int mme_tile_vit_forward(mme_ctx* ctx, const float* pixel_values_dev, const int32_t* aspect_ids_host, const int32_t* num_tiles_host, int n,
                          float* hidden_dev, float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
 
+/* Diagnostic: ONE launch of a row kernel of the tile-ViT forward (tilevit.hip) on the caller's device buffers, synchronous;
+ * works on a bare context, no weights loaded (tests/test_gpu_tile_rows.py compares every output element with float64).
+ * Rows are 1280 wide; a padded sequence row is r = (image * 4 + tile) * 1608 + tok, an output row (image * 4 + tile) * 1601 + tok.
+ *   op 0 tile_patchify  pv f32 [tiles, 3, 560, 560] -> patches bf16 [npatch, 640]: patch p = (tile, py, px) of the 40 x 40 grid,
+ *                       element (c, ky, kx), columns 588..639 zero
+ *      1 tile_assemble  x[r] = bf16(LayerNorm(v) * gamma + beta), r < rows, with v = cls + pos[0] + tilepos[a][tile][0] for tok 0,
+ *                       v = pemb[(image * 4 + tile) * 1600 + tok - 1] + pre[a][tile] + pos[tok] + tilepos[a][tile][tok] for
+ *                       1 <= tok <= 1600, a = aid[image]; rows with tok >= 1601 are zero.  pre [aspect_rows, 4, 1280],
+ *                       pos [1601, 1280], tilepos [aspect_rows, 4, 1601, 1280] f32
+ *      2 tile_ln_post   x[r] <- bf16(LayerNorm(x[r]) * gamma + beta + post[aid[image]][tile]), r < rows, in place, every row
+ *      3 tile_output    hidden f32 [out_rows, 1280 * (1 + ni)]: features [0, 1280) = x of the source row (the 7 padding rows of
+ *                       a tile are skipped), feature 1280 + d * ni + k = inter[k * inter_stride + source row * 1280 + d]
+ *      4 tile_pool      row (image * 4) * 1608 of x and of the ni states, all 1280 * (1 + ni) features in that order, divided by
+ *                       max(its L2 norm, 1e-12) -> emb_f32 [n, F] and / or emb_bf16 [n, F] (either may be NULL, not both)
+ * `aid` is DEVICE int32, one entry per image the rows touch; the entry copies it back and refuses a value outside
+ * [0, aspect_rows), aspect_rows (1..9) being the rows of the caller's pre / post / tilepos tables.
+ * Preconditions (else MME_E_ARG with a message, nothing launched): the pointers the op reads or writes non-null and 16-byte
+ * aligned (aid: 4-byte); inter NULL exactly when ni == 0; ni in 0..8; with ni > 1, inter_stride >= the elements one state
+ * needs ((last source row + 1) * 1280) and <= 2^40; npatch, rows, out_rows, n >= 0 (a count of 0 returns MME_OK without a
+ * launch) and <= 2^31 - 1. */
+typedef struct mme_tile_rowop_apply_args {
+    const float* pv;          /* op 0 */
+    uint16_t* patches;        /* op 0 output */
+    const uint16_t* pemb;     /* op 1: bf16 [*, 1280] patch embeddings */
+    const float *cls, *pre, *pos, *tilepos;  /* op 1 */
+    const float *gamma, *beta;               /* ops 1, 2 */
+    const float* post;        /* op 2: [aspect_rows, 4, 1280] */
+    const int32_t* aid;       /* ops 1, 2 */
+    uint16_t* x;              /* op 1 output, op 2 in place, ops 3, 4 input */
+    const uint16_t* inter;    /* ops 3, 4: ni states of inter_stride elements */
+    float* hidden;            /* op 3 output */
+    float* emb_f32;           /* op 4 outputs */
+    uint16_t* emb_bf16;
+    int64_t npatch, rows, out_rows, inter_stride;
+    int32_t n, ni, aspect_rows;
+    float eps;
+} mme_tile_rowop_apply_args;
+int mme_tile_rowop_apply(mme_ctx* ctx, int op, const mme_tile_rowop_apply_args* args, void* stream);
+
 /* ---- multi-GPU: the ONE exchange step of the path ------------------------------------------
  * Replaces the hand-back of per-device results through Python lists by the reference's thread pool
  * (deprecated_package/embedder.py:208-224): every rank embeds its contiguous block of the corpus and the

@@ -80,6 +80,13 @@ class _RowopApplyArgs(C.Structure):  # mme_rowop_apply_args
         ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("eps", C.c_float)]
 
 
+class _TileRowopApplyArgs(C.Structure):  # mme_tile_rowop_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("pv", "patches", "pemb", "cls", "pre", "pos", "tilepos", "gamma", "beta", "post", "aid", "x", "inter", "hidden",
+                                          "emb_f32", "emb_bf16")] + [
+        (n, C.c_int64) for n in ("npatch", "rows", "out_rows", "inter_stride")] + [
+        ("n", C.c_int32), ("ni", C.c_int32), ("aspect_rows", C.c_int32), ("eps", C.c_float)]
+
+
 EXPORTS = {
     "mme_abi_version": (C.c_int, []),
     "mme_is_diag_build": (C.c_int, []),
@@ -126,6 +133,7 @@ EXPORTS = {
     "mme_load_tile_vit": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights)]),
     "mme_load_tile_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights), C.c_int, C.c_void_p]),
     "mme_tile_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_tile_rowop_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_TileRowopApplyArgs), C.c_void_p]),
     "mme_comm_unique_id": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mme_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mme_comm_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -498,6 +506,21 @@ class Engine:
         a.part_floats = 0 if part is None else int(part.numel())
         a.d, a.B, a.tok, a.eps = int(d), int(B), int(tok), float(eps)
         self._check(self.lib.mme_rowop_apply(self.h, int(self.ROWOPS.get(op, op)), C.byref(a), self._stream()), "mme_rowop_apply")
+
+    TILE_ROWOPS = {"patchify": 0, "assemble": 1, "ln_post": 2, "output": 3, "pool": 4}
+
+    def tile_rowop_apply(self, op, *, pv=None, patches=None, pemb=None, cls=None, pre=None, pos=None, tilepos=None, gamma=None, beta=None, post=None,
+                         aid=None, x=None, inter=None, hidden=None, emb_f32=None, emb_bf16=None, npatch: int = 0, rows: int = 0, out_rows: int = 0,
+                         inter_stride: int = 0, n: int = 0, ni: int = 0, aspect_rows: int = 9, eps: float = 1e-5):
+        """ONE launch of a row kernel of the tile-ViT forward on the caller's CUDA tensors (mme_tile_rowop_apply; synchronous).
+        op: a name of TILE_ROWOPS or its code; which tensors and sizes each op reads is in include/mme.h (`aid` is a CUDA
+        int32 tensor).  The library validates."""
+        a = _TileRowopApplyArgs()
+        a.pv, a.patches, a.pemb, a.cls, a.pre, a.pos, a.tilepos, a.gamma = (self._ptr(t) for t in (pv, patches, pemb, cls, pre, pos, tilepos, gamma))
+        a.beta, a.post, a.aid, a.x, a.inter, a.hidden, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (beta, post, aid, x, inter, hidden, emb_f32, emb_bf16))
+        a.npatch, a.rows, a.out_rows, a.inter_stride = int(npatch), int(rows), int(out_rows), int(inter_stride)
+        a.n, a.ni, a.aspect_rows, a.eps = int(n), int(ni), int(aspect_rows), float(eps)
+        self._check(self.lib.mme_tile_rowop_apply(self.h, int(self.TILE_ROWOPS.get(op, op)), C.byref(a), self._stream()), "mme_tile_rowop_apply")
 
     def set_chunk(self, crops: int):
         self._check(self.lib.mme_set_chunk(self.h, int(crops)), "mme_set_chunk")

@@ -331,4 +331,75 @@ int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* a
     return MME_OK;
 }
 
+// ---- single launches of the row kernels on caller-owned buffers (tests/test_gpu_tile_rows.py): as mme_rowop_apply, every
+// assumption of the kernels is checked here, so that a bad argument is an MME_E_ARG and never a launch
+int mme_tile_rowop_apply(mme_ctx* c, int op, const mme_tile_rowop_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_tile_rowop_apply: null argument");
+    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_tile_rowop_apply: op %d outside 0..4", op);
+    auto vec = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
+    const int64_t count_max = 0x7fffffff;
+    const int64_t count = op == 0 ? a->npatch : op == 3 ? a->out_rows : op == 4 ? (int64_t)a->n : a->rows;
+    const char* bad = nullptr;
+    int64_t last_row = 0;  // ops 3, 4: the last row of x and of every state the launch reads
+    switch (op) {
+        case 0:
+            if (!vec(a->pv) || !vec(a->patches)) bad = "pv, patches non-null and 16-byte aligned";
+            else if (count < 0 || count > count_max) bad = "0 <= npatch <= 2^31 - 1";
+            break;
+        case 1:
+            if (!vec(a->pemb) || !vec(a->cls) || !vec(a->pre) || !vec(a->pos) || !vec(a->tilepos) || !vec(a->gamma) || !vec(a->beta) || !vec(a->x))
+                bad = "pemb, cls, pre, pos, tilepos, gamma, beta, x non-null and 16-byte aligned";
+            break;
+        case 2:
+            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta) || !vec(a->post)) bad = "x, gamma, beta, post non-null and 16-byte aligned";
+            break;
+        case 3:
+            if (!vec(a->x) || !vec(a->hidden)) bad = "x, hidden non-null and 16-byte aligned";
+            else if (count < 0 || count > count_max) bad = "0 <= out_rows <= 2^31 - 1";
+            else if (count > 0) last_row = (count - 1) / TTOK * TTOKP + (count - 1) % TTOK;
+            break;
+        default:
+            if (!vec(a->x)) bad = "x non-null and 16-byte aligned";
+            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
+            else if (((uintptr_t)a->emb_f32 & 15) || ((uintptr_t)a->emb_bf16 & 15)) bad = "emb_f32 and emb_bf16 16-byte aligned";
+            else if (count < 0) bad = "n >= 0";
+            else if (count > 0) last_row = (count - 1) * TT;
+            break;
+    }
+    if (!bad && (op == 1 || op == 2)) {
+        if (!a->aid || ((uintptr_t)a->aid & 3)) bad = "aid non-null and 4-byte aligned";
+        else if (count < 0 || count > count_max) bad = "0 <= rows <= 2^31 - 1";
+        else if (a->aspect_rows < 1 || a->aspect_rows > TARATIOS) bad = "aspect_rows in 1..9";
+    }
+    if (!bad && (op == 3 || op == 4)) {
+        if (a->ni < 0 || a->ni > TMAXI) bad = "ni in 0..8";
+        else if ((a->ni == 0) != (a->inter == nullptr)) bad = "inter null exactly when ni == 0";
+        else if (a->inter && !vec(a->inter)) bad = "inter 16-byte aligned";
+        else if (a->ni > 1 && (a->inter_stride < (last_row + 1) * TD || a->inter_stride > ((int64_t)1 << 40)))
+            bad = "inter_stride >= the elements of one state ((last source row + 1) * 1280) and <= 2^40";
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_tile_rowop_apply: op %d needs %s", op, bad);
+    if (count == 0) return MME_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (op == 1 || op == 2) {  // the kernels index the caller's tables by these values
+        std::vector<int32_t> ids((size_t)((count + TT - 1) / TT));
+        HIP_TRY(c, hipMemcpyAsync(ids.data(), a->aid, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        for (size_t i = 0; i < ids.size(); ++i)
+            if (ids[i] < 0 || ids[i] >= a->aspect_rows)
+                return fail(c, MME_E_ARG, "mme_tile_rowop_apply: aid[%lld] = %d outside 0..%d (aspect_rows - 1)", (long long)i, ids[i], a->aspect_rows - 1);
+    }
+    switch (op) {
+        case 0: HIP_TRY(c, launch_tile_patchify(a->pv, a->patches, a->npatch, s)); break;
+        case 1: HIP_TRY(c, launch_tile_assemble(a->pemb, a->cls, a->pre, a->pos, a->tilepos, a->gamma, a->beta, a->aid, a->x, a->rows, a->eps, s)); break;
+        case 2: HIP_TRY(c, launch_tile_ln_post(a->x, a->gamma, a->beta, a->post, a->aid, a->rows, a->eps, s)); break;
+        case 3: HIP_TRY(c, launch_tile_output(a->x, a->inter, a->ni, a->inter_stride, a->hidden, a->out_rows, s)); break;
+        default: HIP_TRY(c, launch_tile_pool(a->x, a->inter, a->ni, a->inter_stride, a->n, a->emb_f32, a->emb_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
 }  // extern "C"

@@ -146,36 +146,44 @@ __global__ __launch_bounds__(256) void tile_output(const bf16_t* __restrict__ x,
 }
 
 // the crop's vector: class token (token 0) of tile 0, all 1280 * (1 + ni) features, L2-normalised (the pooling rule of
-// deprecated_package/embedder.py:17-34: one token row, F.normalize); one workgroup per image
+// deprecated_package/embedder.py:17-34: one token row, F.normalize); one workgroup per image.
+// The row is scaled by 2^-e, e the exponent of its largest magnitude, before it is squared: the sum of squares of a row of
+// 2^60-sized values is beyond the f32 range (unscaled, 1 / inf turns such a row into zeros).  A power of two changes no
+// rounding, so a row whose sum of squares f32 can hold gets the same bits with and without it; the floor of
+// max(||x||, 1e-12) is scaled alike.
 __global__ __launch_bounds__(256) void tile_pool(const bf16_t* __restrict__ x, const bf16_t* __restrict__ inter, int ni, int64_t inter_stride,
                                                  float* __restrict__ emb_f32, bf16_t* __restrict__ emb_bf16) {
-    __shared__ float part[4];
+    __shared__ float part[4], pmax[4];
     const int img = blockIdx.x, tid = threadIdx.x;
     const int64_t row = (int64_t)img * TILES * TOKP;
     const int F = D * (1 + ni);
+    auto feature = [&](int e) -> float {
+        if (e < D) return (float)x[row * D + e];
+        const int d = (e - D) / ni, k = (e - D) - d * ni;
+        return (float)inter[k * inter_stride + row * D + d];
+    };
+    float m = 0.f;
+    for (int e = tid; e < F; e += 256) m = fmaxf(m, fabsf(feature(e)));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) pmax[tid >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]));
+    // 2^-e with e = floor(log2 m) clamped to [-126, 126], straight from m's exponent field (1 for a zero row): the scaled
+    // maximum lies in [1, 4), and 2^-e is itself a normal number
+    const int ex = min(max((int)((__float_as_uint(m) >> 23) & 0xff), 1), 253);
+    const float sc = m > 0.f ? __uint_as_float((uint32_t)(254 - ex) << 23) : 1.0f;
     float n2 = 0.f;
     for (int e = tid; e < F; e += 256) {
-        float v;
-        if (e < D) {
-            v = (float)x[row * D + e];
-        } else {
-            const int d = (e - D) / ni, k = (e - D) - d * ni;
-            v = (float)inter[k * inter_stride + row * D + d];
-        }
+        const float v = feature(e) * sc;
         n2 += v * v;
     }
     n2 = wave_sum(n2);
     if ((tid & 63) == 0) part[tid >> 6] = n2;
     __syncthreads();
-    const float inv = 1.0f / fmaxf(sqrtf(part[0] + part[1] + part[2] + part[3]), 1e-12f);
+    const float inv = 1.0f / fmaxf(sqrtf(part[0] + part[1] + part[2] + part[3]), 1e-12f * sc);
     for (int e = tid; e < F; e += 256) {
-        float v;
-        if (e < D) {
-            v = (float)x[row * D + e];
-        } else {
-            const int d = (e - D) / ni, k = (e - D) - d * ni;
-            v = (float)inter[k * inter_stride + row * D + d];
-        }
+        const float v = feature(e) * sc;
         if (emb_f32) emb_f32[(int64_t)img * F + e] = v * inv;
         if (emb_bf16) emb_bf16[(int64_t)img * F + e] = (bf16_t)(v * inv);
     }

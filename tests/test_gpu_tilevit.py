@@ -236,6 +236,44 @@ def test_full_tower_matches_rows_recorded_from_transformers(golden_dir):
     eng.close()
 
 
+def test_ragged_last_pass_is_bit_identical():
+    """The pass loop of mme_tile_vit_forward: three images of 1, 2 and 4 tiles through the shallow tower in one pass
+    (chunk 3), in passes of 2 and 1 (chunk 2: the last pass is shorter than the workspace, so M, the row count of the
+    partial-sum planes and the stride of the saved intermediate states describe fewer images than the buffers hold) and
+    one image at a time (chunk 1), each with the LayerNorm statistics from a pass over x (mode 1) and from the producing
+    GEMM's partial sums (mode 2).  `hidden`, `emb_f32` and `emb_bf16` are bit-identical across all runs: the statistics
+    follow one canonical order, the GEMM's K loop does not depend on M, attention works per image.  The chunkings run in
+    ascending order because the workspace only grows: chunk 2 then runs in a workspace of exactly 2 images; a last run
+    at chunk 2 in the workspace of 3 covers the other case."""
+    from multimodal_embeddings_amd._lib import Engine
+
+    geom = replace(TILE_VIT, num_layers=1, num_global_layers=1, intermediate_layers=(0,))
+    w = make_tile_vit_weights(5, geom)
+    eng = Engine(0)
+    eng.load_tile_vit(w, geom)
+    rng = np.random.default_rng(4)
+    arrays = [rng.integers(0, 256, s, dtype=np.uint8) for s in [(300, 200, 3), (400, 900, 3), (1000, 1100, 3)]]
+    pv, ids, mask, nt = _prep(eng, arrays)
+    assert nt == [1, 2, 4]
+    first = None
+    for chunk in (1, 2, 3, 2):
+        eng.set_chunk(chunk)
+        for mode in (1, 2):
+            eng.set_ln_fusion(mode)
+            out = eng.tile_vit_forward(pv, ids, nt, want_hidden=True)
+            torch.cuda.synchronize()
+            if first is None:
+                first = [o.clone() for o in out]
+                assert all(bool(torch.isfinite(o.float()).all()) for o in first)
+                assert first[0].shape == (3, 4, 1601, geom.output_dim)
+                continue
+            for name, a, b in zip(("hidden", "emb_f32", "emb_bf16"), first, out):
+                same = a.view(torch.int16 if a.dtype == torch.bfloat16 else torch.int32) == b.view(torch.int16 if b.dtype == torch.bfloat16 else torch.int32)
+                assert bool(same.all()), (f"chunk {chunk}, statistics mode {mode}: {name} differs from chunk 1 / mode 1 in {int((~same).sum())} elements, "
+                                          f"first at {(~same).nonzero()[0].tolist()}")
+    eng.close()
+
+
 def test_bench_config_tilevit_prints_the_contract_line():
     """`bench.py --config tilevit` (a fresh child process): one JSON line with the contract's keys, `roofline` for the attention
     kernel and `roofline_gemm`, both with live HIP-event durations."""
