@@ -117,6 +117,74 @@ int mme_load_vit_as(mme_ctx* ctx, const mme_vit_weights* w, int dtype, void* str
  * when their words agree, without running a forward.  Writes at most `cap` words to out_host; returns the number of
  * buffers (>= 0, call with cap = 0 to size the array) or MME_E_*. */
 int mme_weights_fingerprint(mme_ctx* ctx, int cap, uint64_t* out_host);
+/* odd_hash of the checksum above, for a 64-bit word index x, all arithmetic mod 2^64 (the splitmix64 finaliser, forced odd):
+ *   x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *   odd_hash = (x ^ (x >> 31)) | 1.
+ * The 32-bit words are little-endian; up to three bytes behind the last whole word count as one more word, zero-extended. */
+
+/* Diagnostic (synchronises the device): copies the first min(cap_bytes, size) bytes of prepared buffer `index` to dst_host
+ * and returns the buffer's size in bytes (>= 0; cap_bytes = 0 only sizes it, dst_host may be NULL then).  `index` counts in
+ * the creation order mme_weights_fingerprint reports.  An index outside [0, buffers), a negative cap_bytes or a null
+ * dst_host with cap_bytes > 0 returns MME_E_ARG.  tests/test_gpu_weight_prep.py compares every buffer with float64 from
+ * the model's definition, and relies on this order (D = hidden, F = mlp, T = tokens; f32 unless marked bf16):
+ *   ViT (mme_load_vit[_as]), 6 tables:
+ *     cls [D], pos [197, D], patch_b [D], lnf_g [D], lnf_b [D], patch_w bf16 [D, 768];
+ *   then 18 per layer:
+ *     ln1_g [D], ln1_b [D], ln2_g [D], ln2_b [D],
+ *     qkv_w bf16 [3D, D] and qkv_b [3D]: Q | K | V, the Q rows times f32(dh^-0.5 log2 e) (dh = 64; the LayerNorm-kernel mode),
+ *     qkv_wf bf16 [3D, D], qkv_cs [3D], qkv_bf [3D]: the fold of ln1 (layernorm_before) into Q | K | V, Q scaled,
+ *     o_w bf16 [D, D], o_b [D], fc1_w bf16 [F, D], fc1_b [F],
+ *     fc1_wf bf16 [F, D], fc1_cs [F], fc1_bf [F]: the fold of ln2 (layernorm_after) into fc1,
+ *     fc2_w bf16 [D, F], fc2_b [D].
+ *   Tower (mme_load_tile_vit[_as]), 11 tables:
+ *     cls [1280], pos [1601, 1280] = (1 - tanh pos_gate) pos_emb, tilepos [9, 4 * 1601 * 1280] = tanh(pos_gate) tile_pos_emb,
+ *     pre [9, 4 * 1280] = tanh(pre_gate) pre_emb, post [9, 4 * 1280] = tanh(post_gate) post_emb,
+ *     lnpre_g, lnpre_b, lnpost_g, lnpost_b [1280], zeros [5120], patch_w bf16 [1280, 640] (columns 588..639 zero);
+ *   then 9 per layer, the local stack first:
+ *     qkv_wf bf16 [3840, 1280], qkv_cs [3840], qkv_bf [3840]: the fold of input_layernorm into Q | K | V, the Q rows times
+ *       f32(80^-0.5 log2 e), no biases,
+ *     o_w bf16 [1280, 1280] (global layers: times tanh gate_attn),
+ *     fc1_wf bf16 [5120, 1280], fc1_cs [5120], fc1_bf [5120]: the fold of post_attention_layernorm into fc1,
+ *     fc2_w bf16 [1280, 5120], fc2_b [1280] (global layers: both times tanh gate_ffn).
+ * The fold of LayerNorm (gamma, beta) into y = W x + b:  W' = bf16(w gamma) with w = f32(scale w) on scaled rows,
+ * colsum = f32(sum_k W') of the ROUNDED values, b' = f32(b + sum_k w beta_k), both sums in f64 over k ascending; every
+ * factor (scale, tanh gate) is applied in f32 and rounded to f32 before anything else. */
+int64_t mme_weights_read(mme_ctx* ctx, int index, int64_t cap_bytes, void* dst_host);
+
+/* Diagnostic: ONE launch of a weight-preparation kernel (weight_prep.hip) on the caller's DEVICE buffers, then a stream
+ * synchronise; works on a bare context.  `dtype` (MME_DT_*) is the element type of every source (src, w[i], b[i], gamma, beta).
+ *   op 0 convert  dst[i] = src[i] (times `scale` in f32 when `scaled`), i < count, to an f32 table or, with out_bf16, to
+ *                 bf16 by round-to-nearest-even (a NaN stays a quiet NaN; subnormals are not flushed).  count = 0 returns
+ *                 MME_OK without a launch.
+ *      1 pad      src [rows, cols] -> dst bf16 [rows, cols_padded], columns cols.. = +0.0
+ *      2 fold     the LayerNorm fold described at mme_weights_read of nsrc row blocks w[i] [src_rows[i], cols] with biases
+ *                 b[i] [src_rows[i]] (NULL: no bias), block i times src_scale[i] when src_scaled[i], into
+ *                 wf bf16 [sum rows, cols], cs f32 [sum rows], bf f32 [sum rows]
+ * Preconditions (else MME_E_ARG with a message, nothing launched): dtype 0..2; every pointer the op uses non-null (b[i]
+ * excepted) and 16-byte aligned (b[i]: to its element);
+ *   op 0: 0 <= count <= 2^40, count % 8 == 0;
+ *   op 1: rows >= 1, cols >= 4, cols % 4 == 0, cols_padded % 4 == 0, cols_padded >= cols;
+ *   op 2: nsrc in 1..3; cols % 64 == 0, 64 <= cols <= 1280; every src_rows[i] a non-zero multiple of 64, <= 2^24. */
+typedef struct mme_weight_prep_apply_args {
+    int32_t dtype;
+    int32_t scaled, out_bf16;    /* op 0 */
+    float scale;                 /* op 0 */
+    const void* src;             /* ops 0, 1 */
+    void* dst;                   /* ops 0, 1 */
+    int64_t count;               /* op 0 */
+    int32_t rows, cols_padded;   /* op 1 */
+    int32_t cols;                /* ops 1, 2 */
+    int32_t nsrc;                /* op 2, as everything below */
+    const void* w[3];
+    const void* b[3];
+    int64_t src_rows[3];
+    float src_scale[3];
+    int32_t src_scaled[3];
+    const void *gamma, *beta;
+    uint16_t* wf;
+    float *cs, *bf;
+} mme_weight_prep_apply_args;
+int mme_weight_prep_apply(mme_ctx* ctx, int op, const mme_weight_prep_apply_args* args, void* stream);
 
 /* Pixel normalisation constants of the image processor (per channel; default CLIP).
  * Replaces the `image_mean` / `image_std` of the checkpoint's preprocessor_config. */

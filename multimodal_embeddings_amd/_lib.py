@@ -87,6 +87,15 @@ class _TileRowopApplyArgs(C.Structure):  # mme_tile_rowop_apply_args
         ("n", C.c_int32), ("ni", C.c_int32), ("aspect_rows", C.c_int32), ("eps", C.c_float)]
 
 
+class _WeightPrepApplyArgs(C.Structure):  # mme_weight_prep_apply_args
+    _fields_ = [
+        ("dtype", C.c_int32), ("scaled", C.c_int32), ("out_bf16", C.c_int32), ("scale", C.c_float), ("src", C.c_void_p), ("dst", C.c_void_p),
+        ("count", C.c_int64), ("rows", C.c_int32), ("cols_padded", C.c_int32), ("cols", C.c_int32), ("nsrc", C.c_int32),
+        ("w", C.c_void_p * 3), ("b", C.c_void_p * 3), ("src_rows", C.c_int64 * 3), ("src_scale", C.c_float * 3), ("src_scaled", C.c_int32 * 3),
+        ("gamma", C.c_void_p), ("beta", C.c_void_p), ("wf", C.c_void_p), ("cs", C.c_void_p), ("bf", C.c_void_p),
+    ]
+
+
 EXPORTS = {
     "mme_abi_version": (C.c_int, []),
     "mme_is_diag_build": (C.c_int, []),
@@ -97,6 +106,8 @@ EXPORTS = {
     "mme_vit_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_load_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_Weights), C.c_int, C.c_void_p]),
     "mme_weights_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "mme_weights_read": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "mme_weight_prep_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_WeightPrepApplyArgs), C.c_void_p]),
     "mme_set_normalisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mme_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
@@ -382,6 +393,38 @@ class Engine:
         rc = self.lib.mme_weights_fingerprint(self.h, n, out)
         self._check(min(rc, 0), "mme_weights_fingerprint")
         return tuple(int(out[i]) for i in range(n))
+
+    def weights_read(self, index: int) -> np.ndarray:
+        """The bytes of prepared weight buffer `index` (creation order, named in include/mme.h) as a uint8 array
+        (mme_weights_read; synchronises the device)."""
+        n = int(self.lib.mme_weights_read(self.h, int(index), 0, None))
+        self._check(min(n, 0), "mme_weights_read")
+        out = np.empty(n, dtype=np.uint8)
+        rc = int(self.lib.mme_weights_read(self.h, int(index), n, out.ctypes.data))
+        self._check(min(rc, 0), "mme_weights_read")
+        return out
+
+    WEIGHT_PREP_OPS = {"convert": 0, "pad": 1, "fold": 2}
+
+    def weight_prep_apply(self, op, *, dtype: int = 0, src=None, dst=None, count: int = 0, scale: float = 1.0, scaled: bool = False,
+                          out_bf16: bool = False, rows: int = 0, cols: int = 0, cols_padded: int = 0, w=(), b=(), src_rows=(), src_scale=(),
+                          src_scaled=(), nsrc=None, gamma=None, beta=None, wf=None, cs=None, bf=None):
+        """ONE launch of a weight-preparation kernel on the caller's CUDA tensors (mme_weight_prep_apply; synchronous).  op: a
+        name of WEIGHT_PREP_OPS or its code; dtype an MME_DT_* code (0 f32, 1 bf16, 2 f16) of every source; w / b / src_rows /
+        src_scale / src_scaled are per-source sequences of the fold (b[i] may be None).  The library validates."""
+        a = _WeightPrepApplyArgs()
+        a.dtype, a.scaled, a.out_bf16, a.scale = int(dtype), int(bool(scaled)), int(bool(out_bf16)), float(scale)
+        a.src, a.dst, a.count = self._ptr(src), self._ptr(dst), int(count)
+        a.rows, a.cols, a.cols_padded = int(rows), int(cols), int(cols_padded)
+        a.nsrc = int(len(w) if nsrc is None else nsrc)
+        for i in range(min(len(w), 3)):
+            a.w[i] = self._ptr(w[i])
+            a.b[i] = self._ptr(b[i]) if i < len(b) else None
+            a.src_rows[i] = int(src_rows[i]) if i < len(src_rows) else 0
+            a.src_scale[i] = float(src_scale[i]) if i < len(src_scale) else 1.0
+            a.src_scaled[i] = int(bool(src_scaled[i])) if i < len(src_scaled) else 0
+        a.gamma, a.beta, a.wf, a.cs, a.bf = (self._ptr(t) for t in (gamma, beta, wf, cs, bf))
+        self._check(self.lib.mme_weight_prep_apply(self.h, int(self.WEIGHT_PREP_OPS.get(op, op)), C.byref(a), self._stream()), "mme_weight_prep_apply")
 
     def tile_vit_forward(self, pixel_values, aspect_ratio_ids, num_tiles, want_hidden=False, want_f32=True, want_bf16=True):
         """pixel_values f32 CUDA [n, 4, 3, 560, 560] (+ ids / tile counts, as `preprocess_tiles` returns them) ->

@@ -97,6 +97,14 @@ inline uint16_t f32_to_bf16_rne(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
+// an f32 table value as both preparers store it: a NaN leaves as a quiet NaN (every other value unchanged, bit for bit)
+inline float f32_quiet_nan(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) u |= 0x00400000u;
+    memcpy(&f, &u, 4);
+    return f;
+}
 void tile_vit_free(mme_ctx* c);
 
 // ---- weight loading (weight_load.hip) ---------------------------------------------------------------------------------
@@ -113,7 +121,7 @@ void tile_vit_free(mme_ctx* c);
 // Both register every prepared buffer in c->allocs / c->alloc_bytes, in creation order.
 int check_load_dtype(mme_ctx* c, int dtype, const char* who);
 
-// The host loops (f32 in): prepared on the CPU, one upload per buffer.  The reference the kernels are tested against.
+// The host loops (f32 in): prepared on the CPU, one upload per buffer.  The kernels keep these loops' operations and their order.
 struct HostPrep {
     mme_ctx* c;
     template <class Walk>

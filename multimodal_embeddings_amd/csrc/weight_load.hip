@@ -2,8 +2,8 @@
 //   HostPrep   f32 host tensors, prepared by the loops below and uploaded buffer by buffer (mme_load_vit, mme_load_tile_vit)
 //   DevPrep    the checkpoint's own bytes (f32, bf16 or f16) staged on the device, prepared by the kernels of
 //              weight_prep.hip (mme_load_vit_as, mme_load_tile_vit_as)
-// The host loops are the reference of the kernels: every kernel keeps the operations of its loop and their order, and
-// tests/test_gpu_checkpoint.py holds the two to equal fingerprints.  The tile-ViT sequence is prepare_tile in
+// Every kernel keeps the operations of its host loop and their order: tests/test_gpu_checkpoint.py holds the two to equal
+// fingerprints, tests/test_gpu_weight_prep.py compares what both prepared with float64 from the model's definition.  The tile-ViT sequence is prepare_tile in
 // capi_tilevit.hip, beside the tower's device record.
 #include <hip/hip_runtime.h>
 
@@ -42,15 +42,15 @@ int upload(mme_ctx* c, const void* h, size_t n, T** dst) {
 // dst[i] = src[i] (* scale); the product is rounded to f32 here, before whatever follows
 void copy_scaled(const float* src, size_t n, float scale, bool scaled, float* dst) {
     if (scaled)
-        for (size_t i = 0; i < n; ++i) dst[i] = src[i] * scale;
+        for (size_t i = 0; i < n; ++i) dst[i] = f32_quiet_nan(src[i] * scale);
     else
-        memcpy(dst, src, n * sizeof(float));
+        for (size_t i = 0; i < n; ++i) dst[i] = f32_quiet_nan(src[i]);
 }
 
 }  // namespace
 
 int HostPrep::table(const void* src, size_t n, float scale, bool scaled, float** dst) {
-    return scaled ? table_cat(&src, &n, 1, scale, true, dst) : upload(c, src, n, dst);  // a plain table goes up as it is
+    return table_cat(&src, &n, 1, scale, scaled, dst);
 }
 
 int HostPrep::table_cat(const void* const* srcs, const size_t* n, int nsrc, float scale0, bool scaled0, float** dst) {

@@ -2,7 +2,7 @@
 // checkpoint's own bytes (f32, bf16 or f16).  Every kernel keeps the operations of HostPrep's loop for the same buffer and
 // their order, so the prepared buffers are bit-identical to the host preparer's (tests/test_gpu_checkpoint.py compares
 // their fingerprints):
-//   convert  dtype -> f32 (exact), optional f32 scale, -> f32 table or -> bf16 (round to nearest even, NaN kept quiet);
+//   convert  dtype -> f32 (exact), optional f32 scale, -> f32 table or -> bf16 (round to nearest even); a NaN leaves quiet;
 //            the parts of a concatenated buffer (Q | K | V) are one launch each into their slice of it
 //   pad      [rows, cols] -> bf16 [rows, cols_padded], zero columns behind
 //   fold     LayerNorm folding: W' = bf16(w * gamma), colsum = sum_k W', bias' = b + sum_k w * beta; the two sums run over k
@@ -30,6 +30,8 @@ __device__ __forceinline__ uint32_t bf16_rne_bits(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return u >> 16;
 }
+
+__device__ __forceinline__ uint32_t quiet_nan_bits(uint32_t u) { return (u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) : u; }
 
 // eight consecutive elements of `dt` from a 16-byte aligned address -> f32 (exact for all three types)
 template <int DT>
@@ -90,14 +92,16 @@ __global__ __launch_bounds__(WP_THREADS) void convert_kernel(ConvertArgs a) {
         if (a.out_bf16) {
             ((u32x4*)a.dst)[c] = pack8_bf16(v);
         } else {
-            f32x4 lo, hi;
+            // a NaN leaves as a quiet NaN on this path too (an unscaled f32 or bf16 value is moved by integer operations
+            // only, which would hand a signalling NaN through; f32_quiet_nan of ctx.h is the host form)
+            u32x4 lo, hi;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                lo[j] = v[j];
-                hi[j] = v[4 + j];
+                lo[j] = quiet_nan_bits(__float_as_uint(v[j]));
+                hi[j] = quiet_nan_bits(__float_as_uint(v[4 + j]));
             }
-            ((f32x4*)a.dst)[2 * c] = lo;
-            ((f32x4*)a.dst)[2 * c + 1] = hi;
+            ((u32x4*)a.dst)[2 * c] = lo;
+            ((u32x4*)a.dst)[2 * c + 1] = hi;
         }
     }
 }
@@ -375,6 +379,70 @@ int mme_weights_fingerprint(mme_ctx* c, int cap, uint64_t* out) {
     if (e != hipSuccess) return fail(c, MME_E_HIP, "mme_weights_fingerprint: %s", hipGetErrorString(e));
     for (int i = 0; i < n && i < cap; ++i) out[i] = sums[i];
     return n;
+}
+
+int64_t mme_weights_read(mme_ctx* c, int index, int64_t cap_bytes, void* dst_host) {
+    if (!c) return MME_E_ARG;
+    const int n = (int)c->allocs.size();
+    if (index < 0 || index >= n) return fail(c, MME_E_ARG, "mme_weights_read: index %d outside 0..%d (the context holds %d prepared buffers)", index, n - 1, n);
+    if (cap_bytes < 0 || (cap_bytes > 0 && !dst_host)) return fail(c, MME_E_ARG, "mme_weights_read: negative capacity, or a null destination with cap_bytes > 0");
+    const size_t size = c->alloc_bytes[index], take = (size_t)cap_bytes < size ? (size_t)cap_bytes : size;
+    if (take) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipDeviceSynchronize());
+        HIP_TRY(c, hipMemcpy(dst_host, c->allocs[index], take, hipMemcpyDeviceToHost));
+    }
+    return (int64_t)size;
+}
+
+// ---- single launches of the preparation kernels on caller-owned buffers (tests/test_gpu_weight_prep.py): as
+// mme_rowop_apply, every assumption of the launchers and kernels is checked here, so that a bad argument is an MME_E_ARG
+// and never a launch
+int mme_weight_prep_apply(mme_ctx* c, int op, const mme_weight_prep_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_weight_prep_apply: null argument");
+    if (op < 0 || op > 2) return fail(c, MME_E_ARG, "mme_weight_prep_apply: op %d outside 0..2", op);
+    if (a->dtype < MME_DT_F32 || a->dtype > MME_DT_F16)
+        return fail(c, MME_E_ARG, "mme_weight_prep_apply: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", a->dtype);
+    auto vec = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
+    const size_t esz = a->dtype == MME_DT_F32 ? 4 : 2;
+    const char* bad = nullptr;
+    WpFoldSrc srcs[3] = {};
+    size_t rows[3] = {0, 0, 0};
+    switch (op) {
+        case 0:
+            if (a->count < 0 || a->count > ((int64_t)1 << 40) || (a->count % 8) != 0) bad = "0 <= count <= 2^40, count % 8 == 0";
+            else if (!vec(a->src) || !vec(a->dst)) bad = "src, dst non-null and 16-byte aligned";
+            break;
+        case 1:
+            if (a->rows < 1 || a->cols < 4 || (a->cols % 4) != 0 || (a->cols_padded % 4) != 0 || a->cols_padded < a->cols)
+                bad = "rows >= 1, cols >= 4, cols % 4 == 0, cols_padded % 4 == 0, cols_padded >= cols";
+            else if (!vec(a->src) || !vec(a->dst)) bad = "src, dst non-null and 16-byte aligned";
+            break;
+        default:
+            if (a->nsrc < 1 || a->nsrc > 3) bad = "nsrc in 1..3";
+            else if (a->cols < FOLD_KT || (a->cols % FOLD_KT) != 0 || a->cols > FOLD_MAXK) bad = "cols a multiple of 64, 64 <= cols <= 1280";
+            else if (!vec(a->gamma) || !vec(a->beta) || !vec(a->wf) || !vec(a->cs) || !vec(a->bf)) bad = "gamma, beta, wf, cs, bf non-null and 16-byte aligned";
+            for (int i = 0; !bad && i < a->nsrc; ++i) {
+                if (a->src_rows[i] < FOLD_ROWS || (a->src_rows[i] % FOLD_ROWS) != 0 || a->src_rows[i] > (1 << 24)) bad = "every rows[i] a non-zero multiple of 64, <= 2^24";
+                else if (!vec(a->w[i])) bad = "every w[i] non-null and 16-byte aligned";
+                else if ((uintptr_t)a->b[i] % esz) bad = "every b[i] null or aligned to its element";
+                srcs[i] = WpFoldSrc{a->w[i], a->b[i], a->src_scale[i], a->src_scaled[i] ? 1 : 0};
+                rows[i] = (size_t)a->src_rows[i];
+            }
+            break;
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_weight_prep_apply: op %d needs %s", op, bad);
+    if (op == 0 && a->count == 0) return MME_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    switch (op) {
+        case 0: HIP_TRY(c, launch_wp_convert(a->dtype, a->src, (size_t)a->count, a->scale, a->scaled != 0, a->out_bf16 != 0, a->dst, s)); break;
+        case 1: HIP_TRY(c, launch_wp_pad(a->dtype, a->src, a->rows, a->cols, a->cols_padded, a->dst, s)); break;
+        default: HIP_TRY(c, launch_wp_fold(a->dtype, srcs, rows, a->nsrc, a->cols, a->gamma, a->beta, a->wf, a->cs, a->bf, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
 }
 
 }  // extern "C"

@@ -2,9 +2,10 @@
 
 Each encoder's load is one sequence of buffers (csrc/weight_load.hip, csrc/capi_tilevit.hip) run by two preparers: the host
 loops behind mme_load_vit / mme_load_tile_vit and the kernels behind mme_load_*_as, operation for operation.  So everything
-here is EQUALITY, and it guards the kernels and the host preparer's operations alike: the fingerprints of the prepared
-buffers (mme_weights_fingerprint) agree word for word with a context loaded by the host path from the same values, and
-the embeddings are bit-equal.  Seed 7: `model_name` used to be ignored, so a
+here is EQUALITY between the two preparers: the fingerprints of the prepared buffers (mme_weights_fingerprint) agree word
+for word with a context loaded by the host path from the same values, and the embeddings are bit-equal.  Neither preparer
+is the reference of the other's arithmetic -- they share one sequence: tests/test_gpu_weight_prep.py compares every prepared
+buffer, and the fingerprint itself, with float64 from the model's definition.  Seed 7: `model_name` used to be ignored, so a
 directory of seed-7 weights only gives seed-7 vectors when it is really read."""
 import json
 
