@@ -189,6 +189,12 @@ int mme_weight_prep_apply(mme_ctx* ctx, int op, const mme_weight_prep_apply_args
 /* Pixel normalisation constants of the image processor (per channel; default CLIP).
  * Replaces the `image_mean` / `image_std` of the checkpoint's preprocessor_config. */
 int mme_set_normalisation(mme_ctx* ctx, const float mean[3], const float std[3]);
+/* Which form of the current constants mme_preprocess' patch emitter uses for a batch that is resized (read-only, no
+ * device work; for tests and diagnostics).  *exact = 1: per channel one fma, bf16(fma(u, a[ch], b[ch])), which the host
+ * verified equal to bf16 of the table entry for all 256 u when the constants were set; a / b receive that pair.
+ * *exact = 0: no such pair exists near the rounded slope / offset of some channel, the emitter reads the f32 table; a / b
+ * then hold nothing of meaning.  A batch of 224 x 224 crops only and mme_preprocess_tiles always read the table. */
+int mme_normalisation_form(mme_ctx* ctx, int32_t* exact, float a[3], float b[3]);
 
 /* Rows of the internal activation workspace = crops per encoder pass (default 4096: one pass
  * for the headline batch; 11.6 GiB of workspace at ViT-B/16; larger passes lose less to tile quantisation).

@@ -109,6 +109,7 @@ EXPORTS = {
     "mme_weights_read": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "mme_weight_prep_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_WeightPrepApplyArgs), C.c_void_p]),
     "mme_set_normalisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mme_normalisation_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mme_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_ln_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -448,6 +449,14 @@ class Engine:
         m = (C.c_float * 3)(*mean)
         s = (C.c_float * 3)(*std)
         self._check(self.lib.mme_set_normalisation(self.h, m, s), "mme_set_normalisation")
+
+    def normalisation_form(self):
+        """(exact, a float32[3], b float32[3]) of the current constants (mme_normalisation_form): exact = True when the patch
+        emitter of a resized batch computes bf16(fma(u, a[ch], b[ch])), False when it reads the table (a, b then mean nothing)."""
+        exact = C.c_int32(-1)
+        a, b = np.zeros(3, dtype=np.float32), np.zeros(3, dtype=np.float32)
+        self._check(self.lib.mme_normalisation_form(self.h, C.byref(exact), _fp(a), _fp(b)), "mme_normalisation_form")
+        return bool(exact.value), a, b
 
     def set_gemm_variant(self, variant: int):
         self._check(self.lib.mme_set_gemm_variant(self.h, int(variant)), "mme_set_gemm_variant")

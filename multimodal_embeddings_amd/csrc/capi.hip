@@ -103,8 +103,14 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
     }
     HIP_TRY(c, hipMemcpy(c->lut, h, sizeof h, hipMemcpyHostToDevice));
     // The patch emitter rounds the table value to bf16.  Look for (a, b) per channel with bf16(fma(u, a, b)) == bf16(table[u])
-    // for ALL 256 u: start from the f64-rounded slope / offset and try the f32 neighbours (a few ulps each way).  Found for
-    // the CLIP and the 0.5 / 0.5 constants; when not, the kernel keeps reading the table (exact = 0).
+    // for ALL 256 u: start from the f64-rounded slope / offset and try the f32 neighbours (up to 8 ulps each way, nearest
+    // first, the slope in the outer loop).  The starting pair itself serves the CLIP, the ImageNet, the 0.5 / 0.5 and the
+    // 0 / 1 constants; about one set in twenty needs a neighbour, and about one in a thousand has no pair on some channel
+    // -- a mean within about 1e-5 of u / 255 for some u (0.6, 0.4, 0.5098) makes table[u] 0 or the few bits that the
+    // cancellation in x - mean leaves, which no fma near the rounded pair gives -- and then the kernel keeps reading the table
+    // for all three channels (exact = 0).
+    // tests/test_gpu_normalisation.py restates this search with an exact fma, predicts the form and the pair of each of its
+    // constant sets (all three kinds) and holds both emitters to the oracle bit for bit under them.
     NormAffine aff{};
     aff.exact = 1;
     for (int ch = 0; ch < 3 && aff.exact; ++ch) {
@@ -509,6 +515,16 @@ int mme_set_normalisation(mme_ctx* c, const float mean[3], const float stdv[3]) 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());
     return set_lut(c, mean, stdv);
+}
+
+int mme_normalisation_form(mme_ctx* c, int32_t* exact, float a[3], float b[3]) {
+    if (!c || !exact || !a || !b) return fail(c, MME_E_ARG, "mme_normalisation_form: null argument");
+    *exact = c->norm_aff.exact;
+    for (int i = 0; i < 3; ++i) {
+        a[i] = c->norm_aff.a[i];
+        b[i] = c->norm_aff.b[i];
+    }
+    return MME_OK;
 }
 
 int mme_set_gemm_variant(mme_ctx* c, int variant) {
