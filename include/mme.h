@@ -110,6 +110,43 @@ int mme_vit_geometry(mme_ctx* ctx, int32_t out[6]);
 enum { MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2 };
 int mme_load_vit_as(mme_ctx* ctx, const mme_vit_weights* w, int dtype, void* stream);
 
+/* ---- CLIP ViT/16 image towers ------------------------------------------------------------------------------------------
+ * Replaces `CLIPVisionModelWithProjection.from_pretrained(dir)(pixel_values).image_embeds` (or `CLIPVisionModel`'s
+ * pooler_output when the checkpoint has no projection), L2-normalised, for the towers at this engine's geometry: 224
+ * pixels, patch 16, heads of 64 (clip-vit-base-patch16 and its re-trainings).  The tower is the ViT forward above with
+ * five differences (transformers models/clip/modeling_clip.py):
+ *   - CLIPVisionEmbeddings: the patch convolution has no bias (`bias=False`): vit.patch_b may be NULL and is prepared as a
+ *     table of zeros; vit.cls_token is class_embedding, vit.pos_emb is position_embedding.weight [197, hidden];
+ *   - CLIPVisionTransformer.forward: `hidden_states = self.pre_layrnorm(hidden_states)` over every token row before
+ *     layer 0 (pre_g, pre_b);
+ *   - CLIPMLP: `self.activation_fn = ACT2FN[config.hidden_act]`: "quick_gelu" (act 1, x * sigmoid(1.702 x), activations.py
+ *     QuickGELUActivation) for OpenAI weights, "gelu" (act 0) for the LAION conversions;
+ *   - CLIPEncoderLayer: layer_norm1 / layer_norm2 with `eps=config.layer_norm_eps`, 1e-5 (vit.ln_eps);
+ *   - CLIPVisionTransformer.forward: `pooled_output = self.post_layernorm(last_hidden_state[:, 0, :])` (vit.lnf_g / lnf_b; here
+ *     of token `pool_token`), then CLIPVisionModelWithProjection.forward: `image_embeds = self.visual_projection(
+ *     pooled_output)`, a bias-free Linear [proj_dim, hidden] (proj_w).  The LayerNormed row is rounded to bf16 before the
+ *     projection, as the model does when it runs in bf16.
+ * The attention scale (CLIPAttention: `self.scale = self.head_dim**-0.5`) is folded into the query rows as for the ViT.
+ * mme_vit_forward / mme_embed then write rows of embed_dim = proj_dim, or hidden when proj_dim is 0 (see them below).
+ * Validation as for the ViT loader: geometry from the same supported set, proj_dim 0 or a multiple of 64 up to 1024 (with
+ * proj_w set exactly when it is not 0), act 0 or 1, non-null pre_g / pre_b; a refusal names the field, the value found and
+ * the supported set, and nothing in the context changes.  The ..._as form takes the checkpoint's own element type as the
+ * ViT's does.  Prepared buffers (mme_weights_read): the ViT's 6 + 18 L in their order, patch_b the zero table when NULL,
+ * then pre_g [D], pre_b [D] and, with a projection, proj_w bf16 [proj_dim, D].  A later ViT load on the same context
+ * returns it to the plain ViT form. */
+typedef struct {
+    mme_vit_weights vit;          /* patch_b may be NULL (CLIP: no bias) -> a zero table */
+    const float *pre_g, *pre_b;   /* pre_layrnorm, [hidden] */
+    const float* proj_w;          /* visual_projection.weight [proj_dim, hidden] or NULL */
+    int32_t proj_dim;             /* 0, or a multiple of 64 up to 1024 */
+    int32_t act;                  /* 0 erf-GELU, 1 QuickGELU */
+} mme_clip_weights;
+int mme_load_clip(mme_ctx* ctx, const mme_clip_weights* w);
+int mme_load_clip_as(mme_ctx* ctx, const mme_clip_weights* w, int dtype, void* stream);
+/* out[4] = kind (0 ViT, 1 CLIP), embed_dim (the row width the forward writes), act (0 erf-GELU, 1 QuickGELU), proj_dim (0: none)
+ * of the context's encoder: what the last load brought, {0, 768, 0, 0} before any. */
+int mme_encoder_info(mme_ctx* ctx, int32_t out[4]);
+
 /* Diagnostic (synchronises the device): one 64-bit word per prepared weight buffer of the context, in the order the
  * loaders created them (the ViT buffers of mme_load_vit[_as], then the tile-ViT buffers of mme_load_tile_vit[_as], when
  * loaded in that order).  The word is a position-dependent checksum of the buffer's bytes -- the sum over its 32-bit words
@@ -136,6 +173,9 @@ int mme_weights_fingerprint(mme_ctx* ctx, int cap, uint64_t* out_host);
  *     o_w bf16 [D, D], o_b [D], fc1_w bf16 [F, D], fc1_b [F],
  *     fc1_wf bf16 [F, D], fc1_cs [F], fc1_bf [F]: the fold of ln2 (layernorm_after) into fc1,
  *     fc2_w bf16 [D, F], fc2_b [D].
+ *   CLIP tower (the CLIP loaders): the ViT's 6 + 18 L buffers in that order -- patch_b all +0.0 when the tower has no patch bias,
+ *     ln1 / ln2 = layer_norm1 / layer_norm2, lnf = post_layernorm -- then pre_g [D], pre_b [D] (pre_layrnorm, identical bits) and,
+ *     with a projection, proj_w bf16 [proj_dim, D] (visual_projection.weight, one rounding to nearest even).
  *   Tower (mme_load_tile_vit[_as]), 11 tables:
  *     cls [1280], pos [1601, 1280] = (1 - tanh pos_gate) pos_emb, tilepos [9, 4 * 1601 * 1280] = tanh(pos_gate) tile_pos_emb,
  *     pre [9, 4 * 1280] = tanh(pre_gate) pre_emb, post [9, 4 * 1280] = tanh(post_gate) post_emb,
@@ -339,8 +379,12 @@ int mme_preprocess_tiles(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* of
  * Replaces `model(**inputs, output_hidden_states=True)` + `last_pooling`
  * (embedder.py:124-129, :17-34).  pool_token: 0 = [CLS] (default), 196 = last token
  * (the reference's "last attended token" with an all-ones mask), any 0..196.
- *   emb_f32_dev  float[n, hidden]  L2-normalised (may be NULL)
- *   emb_bf16_dev bf16 [n, hidden]  same vectors rounded to bf16 (may be NULL) */
+ *   emb_f32_dev  float[n, embed_dim]  L2-normalised (may be NULL)
+ *   emb_bf16_dev bf16 [n, embed_dim]  same vectors rounded to bf16 (may be NULL)
+ * embed_dim (mme_encoder_info) is `hidden` for a ViT and for a CLIP tower without projection, else the tower's proj_dim.
+ * After a CLIP load the pass replaces CLIPVisionTransformer.forward + visual_projection (modeling_clip.py): pre_layrnorm
+ * once over x (with the first LayerNorm's statistics from the same launch), QuickGELU epilogues where act is 1, and the
+ * tail post_layernorm of the pooled row -> bf16 -> projection GEMM (f32 out) -> L2. */
 int mme_vit_forward(mme_ctx* ctx, const uint16_t* patches_dev, int n, int pool_token,
                     float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
 
@@ -524,6 +568,35 @@ typedef struct mme_rowop_apply_args {
     float eps;
 } mme_rowop_apply_args;
 int mme_rowop_apply(mme_ctx* ctx, int op, const mme_rowop_apply_args* args, void* stream);
+
+/* Diagnostic: ONE launch of a kernel the CLIP tower adds, on the caller's device buffers, synchronous; works on a bare context.
+ *   op 0 the GEMM of `gemm` with out = bf16(quick_gelu(acc + bias[n])), quick_gelu(x) = x * sigmoid(1.702 x)
+ *        (activations.py QuickGELUActivation); gemm->epilogue is not read; operands and preconditions as epilogue 1 above
+ *      1 the same with the folded LayerNorm first: quick_gelu(rstd[m] * (acc - mean[m] * colsum[n]) + bias[n]), as epilogue 6
+ *      2 pre_ln_rows   x[r] = bf16(LayerNorm(x[r]) * gamma + beta) IN PLACE, r < rows (rows of d; layernorm_rows' arithmetic),
+ *                      and stats[2r], [2r + 1] = (mean, rstd) of the ROUNDED row in the canonical order: the bits op 2 of
+ *                      the row-kernel diagnostic above finds in x afterwards
+ *      3 pool_ln_rows  y[b] = bf16(LayerNorm(x[b * 197 + tok]) * gamma + beta), b < B, y bf16 [B, d]
+ *      4 l2_rows       xf f32 [rows, p] -> xf / max(||xf||, 1e-12) to y_f32 [rows, p] and / or y_bf16 (not both NULL)
+ * Preconditions (else MME_E_ARG, nothing launched): op 0..4; ops 0, 1: `gemm` non-null and what the GEMM diagnostic asks of
+ * epilogues 1 / 6; ops 2, 3: d == 384, 768 or 1024, x / gamma / beta non-null and 16-byte aligned; op 2: stats non-null and
+ * 8-byte aligned, rows >= 0; op 3: y non-null and 16-byte aligned, B >= 0, 0 <= tok <= 196; op 4: p % 64 == 0, 64 <= p <= 1024, xf and the outputs 16-byte aligned. */
+typedef struct mme_clip_apply_args {
+    const mme_gemm_apply_args* gemm; /* ops 0, 1 */
+    uint16_t* x;            /* ops 2 (in place), 3: bf16 rows of d */
+    const float* gamma;
+    const float* beta;
+    float* stats;           /* op 2: [rows, 2] */
+    uint16_t* y;            /* op 3: bf16 [B, d] */
+    const float* xf;        /* op 4 */
+    float* y_f32;
+    uint16_t* y_bf16;
+    int64_t rows;
+    int32_t d, B, tok, p;
+    float eps;
+    int32_t* ran_256;       /* ops 0, 1, optional: set to 1 when the 256 x 256 kernel ran, 0 for the 128 x 128 one */
+} mme_clip_apply_args;
+int mme_clip_apply(mme_ctx* ctx, int op, const mme_clip_apply_args* args, void* stream);
 
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
  * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,

@@ -47,6 +47,11 @@ class _Weights(C.Structure):
     ]
 
 
+class _ClipWeights(C.Structure):  # mme_clip_weights
+    _fields_ = [("vit", _Weights), ("pre_g", C.POINTER(C.c_float)), ("pre_b", C.POINTER(C.c_float)), ("proj_w", C.POINTER(C.c_float)),
+                ("proj_dim", C.c_int32), ("act", C.c_int32)]
+
+
 class _TileLayer(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_float)) for n in ("ln1_g", "ln1_b", "q_w", "k_w", "v_w", "o_w", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")] + [
         ("gate_attn", C.c_float), ("gate_ffn", C.c_float), ("gated", C.c_int32)]
@@ -80,6 +85,12 @@ class _RowopApplyArgs(C.Structure):  # mme_rowop_apply_args
         ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("eps", C.c_float)]
 
 
+class _ClipApplyArgs(C.Structure):  # mme_clip_apply_args
+    _fields_ = [("gemm", C.POINTER(_GemmApplyArgs))] + [(n, C.c_void_p) for n in ("x", "gamma", "beta", "stats", "y", "xf", "y_f32", "y_bf16")] + [
+        ("rows", C.c_int64), ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("p", C.c_int32), ("eps", C.c_float),
+        ("ran_256", C.POINTER(C.c_int32))]
+
+
 class _TileRowopApplyArgs(C.Structure):  # mme_tile_rowop_apply_args
     _fields_ = [(n, C.c_void_p) for n in ("pv", "patches", "pemb", "cls", "pre", "pos", "tilepos", "gamma", "beta", "post", "aid", "x", "inter", "hidden",
                                           "emb_f32", "emb_bf16")] + [
@@ -105,6 +116,10 @@ EXPORTS = {
     "mme_load_vit": (C.c_int, [C.c_void_p, C.POINTER(_Weights)]),
     "mme_vit_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_load_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_Weights), C.c_int, C.c_void_p]),
+    "mme_load_clip": (C.c_int, [C.c_void_p, C.POINTER(_ClipWeights)]),
+    "mme_load_clip_as": (C.c_int, [C.c_void_p, C.POINTER(_ClipWeights), C.c_int, C.c_void_p]),
+    "mme_encoder_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_clip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_ClipApplyArgs), C.c_void_p]),
     "mme_weights_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "mme_weights_read": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "mme_weight_prep_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_WeightPrepApplyArgs), C.c_void_p]),
@@ -299,10 +314,86 @@ class Engine:
         self._check(self.lib.mme_vit_geometry(self.h, g), "mme_vit_geometry")
         return ViTGeometry(image_size=g[0], patch_size=g[1], hidden_size=g[2], num_layers=g[3], num_heads=g[4], intermediate_size=g[5])
 
+    def encoder_info(self) -> dict:
+        """What the last load brought (mme_encoder_info): {"kind": "vit" | "clip", "embed_dim", "hidden_act", "projection_dim"}."""
+        from .weights import CLIP_ACTS
+
+        o = (C.c_int32 * 4)()
+        self._check(self.lib.mme_encoder_info(self.h, o), "mme_encoder_info")
+        return {"kind": ("vit", "clip")[o[0]], "embed_dim": int(o[1]), "hidden_act": CLIP_ACTS[o[2]], "projection_dim": int(o[3]) or None}
+
     @property
     def embed_dim(self) -> int:
-        """Width of the rows `vit_forward` / `embed` return."""
-        return self.vit_geometry().hidden_size
+        """Width of the rows `vit_forward` / `embed` return: the hidden size, or a CLIP tower's projection_dim."""
+        return self.encoder_info()["embed_dim"]
+
+    # ---- CLIP image towers (mme_load_clip*) -----------------------------------------------------------------
+    @staticmethod
+    def _clip_struct(geom, arr):
+        """mme_clip_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.CLIPGeometry), tensor
+        pointers from arr(name) over the names of weights.clip_tensor_specs."""
+        from .weights import CLIP_ACTS
+
+        v = "vision_model."
+        layers = (_Layer * geom.num_layers)()
+        for i in range(geom.num_layers):
+            p = f"{v}encoder.layers.{i}."
+            L = layers[i]
+            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
+            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
+            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
+            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
+            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
+            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
+            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
+            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+        W = _ClipWeights()
+        W.vit = _Weights(geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
+                         float(geom.layer_norm_eps))
+        W.vit.cls_token = arr(v + "embeddings.class_embedding")
+        W.vit.pos_emb = arr(v + "embeddings.position_embedding.weight")
+        W.vit.patch_w = arr(v + "embeddings.patch_embedding.weight")
+        W.vit.patch_b = None  # CLIPVisionEmbeddings: bias=False
+        W.vit.lnf_g, W.vit.lnf_b = arr(v + "post_layernorm.weight"), arr(v + "post_layernorm.bias")
+        W.vit.layer = layers
+        W.pre_g, W.pre_b = arr(v + "pre_layrnorm.weight"), arr(v + "pre_layrnorm.bias")
+        W.proj_w = arr("visual_projection.weight") if geom.projection_dim else None
+        W.proj_dim = int(geom.projection_dim or 0)
+        if geom.hidden_act not in CLIP_ACTS:
+            raise MmeError(f"hidden_act = {geom.hidden_act!r}; supported: {', '.join(CLIP_ACTS)}")
+        W.act = CLIP_ACTS.index(geom.hidden_act)
+        return W, layers
+
+    def load_clip(self, w: dict, geom=None):
+        """`weights.clip_tensor_specs` dict of f32 arrays (the state dict of transformers' CLIPVisionModelWithProjection, or
+        of CLIPVisionModel: no visual_projection) -> this context, replacing what it held.  `geom`: a weights.CLIPGeometry;
+        by default read off the tensor shapes, with QuickGELU and eps 1e-5 (clip-vit-base-patch16's)."""
+        from .weights import clip_tensor_specs, infer_clip_geometry
+
+        if geom is None:
+            geom = infer_clip_geometry(w)
+        for name, shape, _ in clip_tensor_specs(geom):
+            if name not in w:
+                raise MmeError(f"load_clip: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"load_clip: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32)
+            keep.append(a)
+            return _fp(a)
+
+        W, layers = self._clip_struct(geom, arr)
+        self._check(self.lib.mme_load_clip(self.h, C.byref(W)), "mme_load_clip")
+
+    def load_clip_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "clip")` -> this context, prepared on the device from the file's own f32 / bf16 / f16
+        bytes, bit-identically to `load_clip` on the same values.  Replaces what the context held."""
+        if ckpt.encoder != "clip":
+            raise MmeError(f"load_clip_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        W, layers = self._clip_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
+        self._check(self.lib.mme_load_clip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_clip_as")
 
     @staticmethod
     def _tile_struct(geom, arr, gate):
@@ -559,6 +650,34 @@ class Engine:
         a.d, a.B, a.tok, a.eps = int(d), int(B), int(tok), float(eps)
         self._check(self.lib.mme_rowop_apply(self.h, int(self.ROWOPS.get(op, op)), C.byref(a), self._stream()), "mme_rowop_apply")
 
+    CLIP_OPS = {"gemm_qgelu": 0, "gemm_ln_qgelu": 1, "pre_ln": 2, "pool_ln": 3, "l2": 4}
+
+    def clip_apply(self, op, *, A=None, W=None, M=None, N=None, K=None, variant: int = 0, reverse_m: int = 0, bias=None, out=None, ldo=None,
+                   ln_stats=None, colsum=None, x=None, gamma=None, beta=None, stats=None, y=None, xf=None, y_f32=None, y_bf16=None,
+                   rows: int = 0, d: int = 768, B: int = 0, tok: int = 0, p: int = 0, eps: float = 1e-5):
+        """ONE launch of a kernel the CLIP tower adds, on the caller's CUDA tensors (mme_clip_apply; synchronous).  op: a name
+        of CLIP_OPS or its code.  The GEMM ops take A bf16 [M, K], W bf16 [N, K], bias, out (+ ln_stats, colsum) as
+        `gemm_apply`; the row ops the tensors include/mme.h lists.  The library validates.  -> for the GEMM ops, True when the
+        256 x 256 kernel ran; None for the row ops."""
+        code = int(self.CLIP_OPS.get(op, op))
+        a = _ClipApplyArgs()
+        g = None
+        if A is not None or W is not None:
+            g = _GemmApplyArgs()
+            g.variant, g.reverse_m = int(variant), int(reverse_m)
+            g.M = int(A.shape[0] if M is None else M)
+            g.N = int(W.shape[0] if N is None else N)
+            g.K = int(A.shape[1] if K is None else K)
+            g.A, g.W, g.bias, g.out, g.ln_stats, g.colsum = (self._ptr(t) for t in (A, W, bias, out, ln_stats, colsum))
+            g.ldo = int(g.N if ldo is None else ldo)
+            a.gemm = C.pointer(g)
+        a.x, a.gamma, a.beta, a.stats, a.y, a.xf, a.y_f32, a.y_bf16 = (self._ptr(t) for t in (x, gamma, beta, stats, y, xf, y_f32, y_bf16))
+        a.rows, a.d, a.B, a.tok, a.p, a.eps = int(rows), int(d), int(B), int(tok), int(p), float(eps)
+        ran = C.c_int32(-1)
+        a.ran_256 = C.pointer(ran)
+        self._check(self.lib.mme_clip_apply(self.h, code, C.byref(a), self._stream()), "mme_clip_apply")
+        return bool(ran.value) if g is not None else None
+
     TILE_ROWOPS = {"patchify": 0, "assemble": 1, "ln_post": 2, "output": 3, "pool": 4}
 
     def tile_rowop_apply(self, op, *, pv=None, patches=None, pemb=None, cls=None, pre=None, pos=None, tilepos=None, gamma=None, beta=None, post=None,
@@ -658,7 +777,7 @@ class Engine:
     def vit_forward(self, patches, pool_token: int = 0, want_f32: bool = True, want_bf16: bool = True):
         t = self.torch
         g = self.vit_geometry()
-        n, d = patches.shape[0] // g.num_patches, g.hidden_size
+        n, d = patches.shape[0] // g.num_patches, self.embed_dim
         e32 = t.empty((n, d), dtype=t.float32, device=patches.device) if want_f32 else None
         e16 = t.empty((n, d), dtype=t.bfloat16, device=patches.device) if want_bf16 else None
         self._check(self.lib.mme_vit_forward(self.h, patches.data_ptr(), n, int(pool_token), e32.data_ptr() if want_f32 else None,

@@ -7,17 +7,19 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
     model.safetensors  |  model.safetensors.index.json + shards  |  pytorch_model.bin
 
 -- checks that its configuration is a geometry the library is built for ("vit_b16": exactly ViT-B/16; "vit": any of the
-supported ViT/16 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
+supported ViT/16 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "clip": a CLIP image tower of that family,
+`CLIPVisionModel[WithProjection]` or the vision half of a whole `CLIPModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
 bytes to the device, where they are converted and folded (csrc/weight_load.hip: DevPrep; kernels in csrc/weight_prep.hip).
 
-    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|mllama_tiles]
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles]
 
 prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import logging
 import os
@@ -26,11 +28,12 @@ from dataclasses import dataclass, field
 
 from . import config
 from ._lib import MmeError
-from .weights import TILE_VIT, VIT_B16, TileViTGeometry, ViTGeometry, tile_vit_tensor_specs, vit_geometry_problem, vit_tensor_specs
+from .weights import (CLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, TileViTGeometry, ViTGeometry, clip_geometry_problem, clip_tensor_specs,
+                      tile_vit_tensor_specs, vit_geometry_problem, vit_tensor_specs)
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "vit", "mllama_tiles")
+ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles")
 VIT_ENCODERS = ("vit_b16", "vit")  # one loader, one tensor layout; "vit" takes its geometry from config.json
 SUPPORTED_ASPECT_RATIOS = [[1, 1], [1, 2], [1, 3], [1, 4], [2, 1], [2, 2], [3, 1], [4, 1]]
 _DTYPE_IDS = {"float32": 0, "bfloat16": 1, "float16": 2}  # include/mme.h MME_DT_*
@@ -99,6 +102,17 @@ def canonical_vit_name(key: str):
     return key
 
 
+def canonical_clip_name(key: str):
+    """Checkpoint key -> canonical name (`weights.clip_tensor_specs`: the keys of `CLIPVisionModelWithProjection`), or None
+    for what the image tower does not use: the text tower, text_projection, logit_scale, the position_ids buffers."""
+    if key.startswith(("text_model.", "text_projection.")) or key == "logit_scale" or key.endswith(".position_ids"):
+        return None
+    # CLIPVisionModel.save_pretrained of transformers 5 writes the tower's own keys, without the "vision_model." prefix
+    if key.startswith(("embeddings.", "pre_layrnorm.", "encoder.layers.", "post_layernorm.")):
+        return "vision_model." + key
+    return key
+
+
 def canonical_tile_name(key: str):
     """Checkpoint key -> canonical name, or None for a key outside the vision tower."""
     for prefix in ("model.vision_model.", "vision_model."):
@@ -154,6 +168,25 @@ def _vit_family_geometry(cfg: dict, where: str) -> ViTGeometry:
     return g
 
 
+def _clip_geometry(cfg: dict, where: str, projection_dim) -> CLIPGeometry:
+    """The vision configuration of a CLIP checkpoint (CLIPVisionConfig) -> geometry; the same supported set as "vit", plus
+    hidden_act and projection_dim.  `projection_dim` is what the file that holds `cfg` says (a whole CLIP config names it
+    at its top level); whether the checkpoint has a visual_projection at all is decided by its tensors."""
+    b = CLIP_B16
+    for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
+        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
+            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
+    g = CLIPGeometry(image_size=cfg["image_size"], patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels),
+                     hidden_size=cfg["hidden_size"], num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"],
+                     intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)),
+                     projection_dim=projection_dim, hidden_act=cfg.get("hidden_act", b.hidden_act))
+    bad = clip_geometry_problem(g)
+    if bad:
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    return g
+
+
 def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
     g = TILE_VIT
     for fld, built in (("image_size", g.image_size), ("patch_size", g.patch_size), ("hidden_size", g.hidden_size),
@@ -185,7 +218,8 @@ def _read_preprocessor(path: str, encoder: str):
     if pc.get("do_normalize", True) is not True:
         raise MmeError(f"{where}: do_normalize = {pc.get('do_normalize')!r}; K1 always normalises with image_mean / image_std")
     resample = pc.get("resample", 2)
-    if resample != 2:
+    clip_rule = encoder == "clip" and (resample == 3 or pc.get("do_center_crop") or "crop_size" in pc)
+    if resample != 2 and not (encoder == "clip" and resample == 3):
         raise MmeError(f"{where}: resample = {resample!r}; K1 resizes with Pillow BILINEAR (resample = 2) only")
     if encoder == "mllama_tiles":
         size = pc.get("size", {"height": 560, "width": 560})
@@ -194,9 +228,13 @@ def _read_preprocessor(path: str, encoder: str):
         tiles = pc.get("max_image_tiles", 4)
         if tiles != 4:
             raise MmeError(f"{where}: max_image_tiles = {tiles!r}; the tile encoder is built for max_image_tiles = 4")
-    elif "Mllama" not in str(pc.get("image_processor_type", "")) and not _warned_resize_rule:
+    elif ("Mllama" not in str(pc.get("image_processor_type", "")) or clip_rule) and not _warned_resize_rule:
         _warned_resize_rule = True
-        logger.warning(f"{where}: image_processor_type = {pc.get('image_processor_type')!r} does not use Mllama's fit-and-pad resize; K1 keeps the "
+        clip_fields = ""
+        if clip_rule:  # CLIP's own rule: shortest edge to `size` with BICUBIC, then a centre crop
+            named = [f"{k} = {pc[k]!r}" for k in ("resample", "size", "do_center_crop", "crop_size") if k in pc]
+            clip_fields = f" ({', '.join(named)}: the shortest-edge BICUBIC resize and the centre crop are not applied)"
+        logger.warning(f"{where}: image_processor_type = {pc.get('image_processor_type')!r} does not use Mllama's fit-and-pad resize{clip_fields}; K1 keeps the "
                        "aspect-preserving fit into 224 x 224 with zero padding (this encoder's contract, DESIGN.md) and applies only the "
                        "checkpoint's image_mean / image_std")
     mean, std = pc.get("image_mean"), pc.get("image_std")
@@ -296,6 +334,15 @@ def read_checkpoint(path, encoder: str = "vit_b16") -> Checkpoint:
         geometry = _vit_geometry(cfg, "config.json") if encoder == "vit_b16" else _vit_family_geometry(cfg, "config.json")
         specs = [(n, s) for n, s, _ in vit_tensor_specs(geometry)]
         canonical = canonical_vit_name
+    elif encoder == "clip":
+        where, vcfg = "config.json", cfg
+        if "vision_config" in cfg:  # a whole CLIP model: projection_dim sits at the top level
+            vcfg, where = dict(cfg["vision_config"]), "config.json: vision_config"
+            if "projection_dim" in cfg:
+                vcfg["projection_dim"] = cfg["projection_dim"]
+        geometry = _clip_geometry(vcfg, where, vcfg.get("projection_dim"))
+        canonical = canonical_clip_name
+        specs = None  # after the tensors are read: a CLIPVisionModel checkpoint has no visual_projection
     else:
         where = "config.json"
         if "vision_config" in cfg:  # a whole Mllama model
@@ -303,7 +350,16 @@ def read_checkpoint(path, encoder: str = "vit_b16") -> Checkpoint:
         geometry = _tile_geometry(cfg, where)
         specs = [(n, s) for n, s, _, _ in tile_vit_tensor_specs(geometry)]
         canonical = canonical_tile_name
-    tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs})
+    if encoder == "clip":
+        wanted = {n for n, _, _ in clip_tensor_specs(dataclasses.replace(geometry, projection_dim=geometry.projection_dim or 64))}
+        tensors, keys, files = _read_tensors(path, canonical, wanted)
+        if "visual_projection.weight" not in tensors:  # CLIPVisionModel: the embedding is the post_layernorm row
+            geometry = dataclasses.replace(geometry, projection_dim=None)
+        elif geometry.projection_dim is None:
+            raise MmeError(f"{path}: the checkpoint holds {keys['visual_projection.weight']!r} but {where} names no projection_dim")
+        specs = [(n, s) for n, s, _ in clip_tensor_specs(geometry)]
+    else:
+        tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs})
     source += files
     for name, shape in specs:
         if name not in tensors:
@@ -336,6 +392,14 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
         cfg = {"architectures": ["ViTModel"], "model_type": "vit", "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels,
                "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
                "intermediate_size": g.intermediate_size, "hidden_act": "gelu", "qkv_bias": True, "layer_norm_eps": g.layer_norm_eps, "dtype": dtype}
+    elif encoder == "clip":
+        g = geometry or CLIP_B16
+        cfg = {"architectures": ["CLIPVisionModelWithProjection" if g.projection_dim else "CLIPVisionModel"], "model_type": "clip_vision_model",
+               "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size,
+               "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
+               "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "dtype": dtype}
+        if g.projection_dim:
+            cfg["projection_dim"] = g.projection_dim
     elif encoder == "mllama_tiles":
         g = geometry or TILE_VIT
         cfg = {"architectures": ["MllamaVisionModel"], "model_type": "mllama_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,

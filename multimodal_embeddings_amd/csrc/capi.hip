@@ -167,7 +167,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         g.pos = c->pos;
         g.out = c->x.p;
         g.ldo = D;
-        if (planes) {  // the 256 x 256 kernel leaves the LayerNorm partial sums of the token rows it writes
+        if (planes && !c->clip) {  // the 256 x 256 kernel leaves the LayerNorm partial sums of the token rows it writes
             g.ln_part = (float*)c->lnpart.p;
             g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
         }
@@ -200,8 +200,15 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         return interior < M ? stats_from_x(interior) : MME_OK;
     };
     const int res_epi = planes ? EPI_BIAS_RES_STATS : EPI_BIAS_RES;
+    // fc1's activation: erf-GELU, or QuickGELU for a CLIP tower with OpenAI weights
+    const int act_epi = c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, ln_act_epi = c->act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU;
     int r;
-    if (planes && gemm_runs_256(patch_args, c->gemm_variant)) {
+    if (c->clip) {
+        // CLIP: pre_layrnorm over every token row, in place; the same launch leaves the statistics of the rows it wrote,
+        // in the canonical order: the first folded LayerNorm needs neither planes nor another pass over x
+        Timed t(c, s, KC_LN);
+        HIP_TRY(c, launch_pre_ln(c->x.p, c->pre_g, c->pre_b, M, D, c->ln_eps, (float*)c->stats.p, s));
+    } else if (planes && gemm_runs_256(patch_args, c->gemm_variant)) {
         // first LayerNorm of the pass: the patch-embed epilogue left the partial sums of every token row an INTERIOR tile
         // wrote (patch rows [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th
         // row) and the rows of the ragged last tile take the stand-alone kernel, same canonical order
@@ -270,7 +277,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
                 g = GemmArgs{};
                 g.A = x_p; g.W = L.fc1_wf; g.M = n; g.N = F; g.K = D;
                 g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = F;
-                HIP_TRY(c, launch_gemm(EPI_LN_BIAS_GELU, g, s, c->gemm_variant));
+                HIP_TRY(c, launch_gemm(ln_act_epi, g, s, c->gemm_variant));
                 g = GemmArgs{};
                 g.A = c->mlp.p; g.W = L.fc2_w; g.M = n; g.N = D; g.K = F;
                 g.bias = L.fc2_b; g.out = x_p; g.res = x_p; g.ldo = D;
@@ -298,7 +305,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             g.A = c->x.p; g.W = L.fc1_wf; g.M = M; g.N = F; g.K = D;
             g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = F;
             g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(EPI_LN_BIAS_GELU, g, s, c->gemm_variant));
+            HIP_TRY(c, launch_gemm(ln_act_epi, g, s, c->gemm_variant));
         } else {
             {
                 Timed t(c, s, KC_LN);
@@ -309,7 +316,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             g.A = c->hbuf.p; g.W = L.fc1_w; g.M = M; g.N = F; g.K = D;
             g.bias = L.fc1_b; g.out = c->mlp.p; g.ldo = F;
             g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(EPI_BIAS_GELU, g, s, c->gemm_variant));
+            HIP_TRY(c, launch_gemm(act_epi, g, s, c->gemm_variant));
         }
         const bool last = l + 1 == NL;  // the final LayerNorm touches the pooled row only (K8)
         {
@@ -322,6 +329,26 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             HIP_TRY(c, launch_gemm(last ? EPI_BIAS_RES : res_epi, g, s, c->gemm_variant));
         }
         if (c->ln_mode != 0 && !last && (r = stats_after(g))) return r;
+    }
+    if (c->proj_dim) {
+        // CLIP with a projection: post_layernorm of the pooled row, rounded to bf16, times visual_projection, then L2
+        const int P = c->proj_dim;
+        if ((r = ensure(c, c->pooled, (size_t)c->chunk * D * 2))) return r;
+        if ((r = ensure(c, c->projf, (size_t)c->chunk * P * sizeof(float)))) return r;
+        {
+            Timed t(c, s, KC_POOL);
+            HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
+        }
+        {
+            Timed t(c, s, KC_GEMM);
+            g = GemmArgs{};
+            g.A = c->pooled.p; g.W = c->proj_w; g.M = n; g.N = P; g.K = D;
+            g.outf = (float*)c->projf.p; g.ldf = P;
+            HIP_TRY(c, launch_gemm(EPI_F32, g, s, c->gemm_variant));
+        }
+        Timed t(c, s, KC_POOL);
+        HIP_TRY(c, launch_l2_rows((const float*)c->projf.p, n, P, emb_f32, emb_bf16, s));
+        return MME_OK;
     }
     {
         Timed t(c, s, KC_POOL);
@@ -487,7 +514,7 @@ void mme_destroy(mme_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (void* p : c->allocs) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply};
+    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->lut) (void)hipFree(c->lut);
@@ -505,6 +532,15 @@ int mme_vit_geometry(mme_ctx* c, int32_t out[6]) {
     if (!c || !out) return fail(c, MME_E_ARG, "mme_vit_geometry: null argument");
     const int32_t g[6] = {VIT_IMG, VIT_PATCH, c->geom.hidden, c->geom.layers, c->geom.heads, c->geom.mlp};
     for (int i = 0; i < 6; ++i) out[i] = g[i];
+    return MME_OK;
+}
+
+int mme_encoder_info(mme_ctx* c, int32_t out[4]) {
+    if (!c || !out) return fail(c, MME_E_ARG, "mme_encoder_info: null argument");
+    out[0] = c->clip ? 1 : 0;
+    out[1] = embed_dim(c);
+    out[2] = c->act;
+    out[3] = c->proj_dim;
     return MME_OK;
 }
 
@@ -655,8 +691,8 @@ int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, 
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
         r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_PATCH_DIM, m, pool_token,
-                          emb_f32 ? emb_f32 + (size_t)s0 * c->geom.hidden : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * c->geom.hidden : nullptr, s);
+                          emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
+                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
         if (r) return r;
     }
     return MME_OK;
@@ -679,8 +715,8 @@ int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t
         if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));  // crop tables are reused per chunk
         r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)c->patches.p, s);
         if (r) return r;
-        r = forward_chunk(c, (const bf16_t*)c->patches.p, m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * c->geom.hidden : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * c->geom.hidden : nullptr, s);
+        r = forward_chunk(c, (const bf16_t*)c->patches.p, m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
+                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
         if (r) return r;
     }
     return MME_OK;
@@ -1285,6 +1321,69 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
         case 3: HIP_TRY(c, launch_ln_finish(a->part, a->part_rows, a->rows, a->d, a->eps, a->stats, s)); break;
         case 4: HIP_TRY(c, launch_cls_rows(a->x, a->cls, a->pos, a->B, a->d, s)); break;
         default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+// the kernels a CLIP tower adds, one launch each (tests/test_gpu_clip.py)
+int mme_clip_apply(mme_ctx* c, int op, const mme_clip_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_clip_apply: null argument");
+    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_clip_apply: op %d outside 0..4", op);
+    hipStream_t s = (hipStream_t)stream;
+    if (op <= 1) {
+        const mme_gemm_apply_args* ga = a->gemm;
+        if (!ga) return fail(c, MME_E_ARG, "mme_clip_apply: op %d needs gemm", op);
+        if (ga->variant < 0 || ga->variant > 6) return fail(c, MME_E_ARG, "mme_clip_apply: variant %d outside 0..6", ga->variant);
+        if (ga->reverse_m != 0 && ga->reverse_m != 1) return fail(c, MME_E_ARG, "mme_clip_apply: reverse_m must be 0 or 1");
+        const int64_t M = ga->M, N = ga->N, K = ga->K;
+        if (M < 1 || M > (1 << 24) || N < 1 || N > (1 << 20)) return fail(c, MME_E_ARG, "mme_clip_apply: M = %d outside 1..2^24 or N = %d outside 1..2^20", ga->M, ga->N);
+        if (K < 64 || K > (1 << 16) || (K % 64) != 0) return fail(c, MME_E_ARG, "mme_clip_apply: K = %d must be a multiple of 64 in 64..65536", ga->K);
+        if (!ga->A || !ga->W) return fail(c, MME_E_ARG, "mme_clip_apply: null operand (A or W)");
+        if (!aligned_to(ga->A, 16) || !aligned_to(ga->W, 16)) return fail(c, MME_E_ARG, "mme_clip_apply: A and W must be 16-byte aligned");
+        if ((N % 4) != 0) return fail(c, MME_E_ARG, "mme_clip_apply: a bf16 output needs N %% 4 == 0 (N = %d)", ga->N);
+        if (!ga->bias || !ga->out) return fail(c, MME_E_ARG, "mme_clip_apply: op %d needs bias and out", op);
+        if (!aligned_to(ga->bias, 16) || !aligned_to(ga->out, 16)) return fail(c, MME_E_ARG, "mme_clip_apply: bias and out must be 16-byte aligned");
+        if (ga->ldo < N || ga->ldo > (1 << 24) || (ga->ldo % 8) != 0) return fail(c, MME_E_ARG, "mme_clip_apply: ldo = %lld must be a multiple of 8 in N..2^24", (long long)ga->ldo);
+        if (op == 1) {
+            if (!ga->ln_stats || !ga->colsum) return fail(c, MME_E_ARG, "mme_clip_apply: op 1 needs ln_stats and colsum");
+            if (!aligned_to(ga->ln_stats, 8) || !aligned_to(ga->colsum, 16)) return fail(c, MME_E_ARG, "mme_clip_apply: ln_stats must be 8-byte and colsum 16-byte aligned");
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        GemmArgs g{};
+        g.A = ga->A; g.W = ga->W; g.M = ga->M; g.N = ga->N; g.K = ga->K;
+        g.reverse_m = ga->reverse_m;
+        g.bias = ga->bias; g.out = ga->out; g.ldo = ga->ldo;
+        if (op == 1) { g.ln_stats = ga->ln_stats; g.colsum = ga->colsum; }
+        if (a->ran_256) *a->ran_256 = gemm_runs_256(g, ga->variant) ? 1 : 0;
+        HIP_TRY(c, launch_gemm(op == 0 ? EPI_BIAS_QGELU : EPI_LN_BIAS_QGELU, g, s, ga->variant));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return MME_OK;
+    }
+    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    const char* bad = nullptr;
+    if (op == 2 || op == 3) {
+        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_clip_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
+        if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
+        else if (op == 2 && (!a->stats || !aligned_to(a->stats, 8))) bad = "stats non-null and 8-byte aligned";
+        else if (op == 2 && a->rows < 0) bad = "rows >= 0";
+        else if (op == 3 && !vec(a->y)) bad = "y non-null and 16-byte aligned";
+        else if (op == 3 && a->B < 0) bad = "B >= 0";
+        else if (op == 3 && (a->tok < 0 || a->tok >= VIT_T)) bad = "0 <= tok <= 196";
+    } else {
+        if (a->p < 64 || (a->p % 64) != 0 || a->p > 1024) return fail(c, MME_E_ARG, "mme_clip_apply: op 4 needs p %% 64 == 0, 64 <= p <= 1024 (p = %d)", a->p);
+        if (!vec(a->xf)) bad = "xf non-null and 16-byte aligned";
+        else if (!a->y_f32 && !a->y_bf16) bad = "y_f32 or y_bf16";
+        else if (!aligned_to(a->y_f32, 16) || !aligned_to(a->y_bf16, 16)) bad = "y_f32 and y_bf16 16-byte aligned";
+        else if (a->rows < 0) bad = "rows >= 0";
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_clip_apply: op %d needs %s", op, bad);
+    HIP_TRY(c, hipSetDevice(c->device));
+    switch (op) {
+        case 2: HIP_TRY(c, launch_pre_ln(a->x, a->gamma, a->beta, a->rows, a->d, a->eps, a->stats, s)); break;
+        case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->B, a->tok, a->d, a->eps, a->y, s)); break;
+        default: HIP_TRY(c, launch_l2_rows(a->xf, a->rows, a->p, a->y_f32, a->y_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;

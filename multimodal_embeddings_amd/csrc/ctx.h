@@ -59,6 +59,13 @@ struct mme_ctx {
     float *cls = nullptr, *pos = nullptr, *patch_b = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
     bf16_t* patch_w = nullptr;
     std::vector<LayerDev> layer;  // geom.layers of them
+    // CLIP image tower (mme_load_clip*; all off / null after mme_load_vit*): a LayerNorm over every token row before layer 0,
+    // QuickGELU in the MLP, a bias-free projection of the pooled, LayerNormed row
+    bool clip = false;         // the last load was a CLIP load (mme_encoder_info); pre_g / pre_b are set
+    int act = 0;               // 0 erf-GELU, 1 QuickGELU
+    int proj_dim = 0;          // 0: no projection (the embedding is the L2-normalised post_layernorm row)
+    float *pre_g = nullptr, *pre_b = nullptr;
+    bf16_t* proj_w = nullptr;  // [proj_dim, hidden]
     float* lut = nullptr;  // [3,256]
     NormAffine norm_aff{};  // the same mapping as one fma per value where that is bit-exact after the bf16 rounding (set_lut)
     // workspace (sized for `chunk` crops)
@@ -69,6 +76,7 @@ struct mme_ctx {
     int zigzag = 1;           // forward_chunk: 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
+    DevBuf pooled, projf;  // CLIP tail: bf16 [chunk, hidden] post_layernorm rows, f32 [chunk, proj_dim] projected rows
     // host staging for crop tables
     std::vector<CropDesc> h_crops;
     std::vector<HWork> h_work;
@@ -81,6 +89,8 @@ struct mme_ctx {
 };
 
 int fail(mme_ctx* c, int code, const char* fmt, ...);
+// width of the rows mme_vit_forward / mme_embed write
+inline int embed_dim(const mme_ctx* c) { return c->proj_dim ? c->proj_dim : c->geom.hidden; }
 
 #define HIP_TRY(c, expr)                                                                            \
     do {                                                                                            \

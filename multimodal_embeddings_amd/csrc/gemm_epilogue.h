@@ -25,6 +25,21 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + e);  // v_rcp_f32 (1 ulp); __frcp_rn would expand to a full IEEE division
 }
 
+// QuickGELU (transformers activations.py QuickGELUActivation, ACT2FN["quick_gelu"]: x * sigmoid(1.702 x)), the MLP
+// activation of CLIP towers with OpenAI weights (modeling_clip.py CLIPMLP):  x * rcp(1 + exp2(x * f32(-1.702 log2 e))),
+// branch-free, evaluated so that no intermediate leaves the f32 range while the RESULT is still a normal number.  Taken
+// literally, exp2 overflows at x <= -52.1 and v_rcp_f32 flushes its subnormal result from x <= -51.3 on, where the result,
+// |x| 2^-t, is still 4e-37.  So the exponential is taken at half the argument (the factor halved is the same f32, one
+// exponent lower) and squared inside the fma, and 1 + e is carried as 2^-8 (1 + e):
+//   h = exp2(x * C/2),  s = fma(h, h * 2^-8, 2^-8) = 2^-8 (1 + h^2),  y = (x * 2^-8) * rcp(s).
+// The two multiplications by 2^-8 are exact; s stays below 2^125 until the result itself is below 2^-126.  x -> -inf gives
+// s = inf, rcp = 0, y = -0;  x -> +inf gives h = 0, s = 2^-8, y = x.  5 plain VALU ops + exp2 + rcp.
+__device__ __forceinline__ float quick_gelu(float x) {
+    const float h = __builtin_amdgcn_exp2f(x * (float)(-0.851 * 1.4426950408889634));  // exp(-0.851 x)
+    const float s = fmaf(h, h * 0x1p-8f, 0x1p-8f);
+    return (x * 0x1p-8f) * __builtin_amdgcn_rcpf(s);
+}
+
 // ---- LayerNorm statistics in ONE canonical summation order ---------------------------------------------
 // Shared by the EPI_BIAS_RES_STATS epilogue (partial sums while the rounded outputs are still in registers) and
 // by the stand-alone kernels of rowops.hip, so that an embedding does not depend on which of them ran:
@@ -92,7 +107,7 @@ __device__ __forceinline__ void epi_store(const GemmArgs& g, int m, const EpiRow
         }
         return;
     }
-    if (EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU) {
+    if (EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU) {
         const float mu = g.ln_stats[2 * (int64_t)m], rs = g.ln_stats[2 * (int64_t)m + 1];
         const f32x4 sv = *(const f32x4*)(g.colsum + n), bv = *(const f32x4*)(g.bias + n);
 #pragma unroll
@@ -103,6 +118,10 @@ __device__ __forceinline__ void epi_store(const GemmArgs& g, int m, const EpiRow
     if (EPI == EPI_BIAS_GELU || EPI == EPI_LN_BIAS_GELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    }
+    if (EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
     }
     if (EPI == EPI_PATCH) v += *(const f32x4*)(g.pos + (int64_t)er.prow * g.N + n);
     bf16_t* o = (bf16_t*)g.out + er.orow * g.ldo + n;
@@ -163,12 +182,13 @@ template <int EPI, int NDEF = 0, class Between>
 __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&acc)[8][4], int mw, int nw, int fr, int fq,
                                                      Between&& between, uint4* pend = nullptr) {
     static_assert(EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES || EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU ||
-                      EPI == EPI_BIAS_RES_STATS,
+                      EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU,
                   "epilogue_wave_128x64: unsupported epilogue");
     constexpr bool RES = EPI == EPI_BIAS_RES || EPI == EPI_BIAS_RES_STATS;
     constexpr bool STATS = EPI == EPI_BIAS_RES_STATS;
-    constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU;
+    constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU;
     constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_LN_BIAS_GELU;
+    constexpr bool QGELU = EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU;
     // wave-uniform row bases (SGPR pairs) + 32-bit lane offsets: saddr addressing
     const int64_t tile_off = (int64_t)mw * g.ldo + nw;
     const int lo0 = fr * (int)g.ldo + row16_col(0, fq), lo1 = fr * (int)g.ldo + row16_col(2, fq);
@@ -221,6 +241,13 @@ __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&
                 for (int r = 0; r < 4; ++r) {
                     v0[r] = gelu_erf(v0[r]);
                     v1[r] = gelu_erf(v1[r]);
+                }
+            }
+            if (QGELU) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    v0[r] = quick_gelu(v0[r]);
+                    v1[r] = quick_gelu(v1[r]);
                 }
             }
             if (RES) {
@@ -377,5 +404,5 @@ __device__ __forceinline__ void epilogue_wave_patch_128x64(const GemmArgs& g, f3
 template <int EPI>
 constexpr bool epi_has_fast_path() {
     return EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES || EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU ||
-           EPI == EPI_BIAS_RES_STATS;
+           EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU;
 }

@@ -18,7 +18,10 @@ enum GemmEpilogue {
     EPI_TOPK = 7,         // no output matrix: every acc[m,n] >= thr[m] is appended to row m's candidate list (K12)
     // EPI_BIAS_RES that also leaves, per output row and 64-column slice, the LayerNorm partial sums (sum x, sum x^2 of
     // the ROUNDED outputs) in ln_part: the next LayerNorm's statistics then need no pass over the residual stream
-    EPI_BIAS_RES_STATS = 8
+    EPI_BIAS_RES_STATS = 8,
+    // QuickGELU, x * sigmoid(1.702 x), where the erf forms have erf-GELU (CLIP image towers with OpenAI weights)
+    EPI_BIAS_QGELU = 9,     // out = bf16(quick_gelu(acc + bias[n]))                      (fc1, LayerNorm-kernel mode)
+    EPI_LN_BIAS_QGELU = 10  // EPI_LN_BIAS, then QuickGELU                                (fc1)
 };
 
 struct GemmArgs {
@@ -60,6 +63,14 @@ hipError_t launch_gemm256r_stamped(const GemmArgs& g, unsigned long long* stamps
 // LayerNorm over bf16 rows of d (f32 statistics), bf16 out.  d: a width the row kernels are instantiated for (384, 768,
 // 1024; common.h vit_width_built), as for launch_ln_stats, launch_cls_rows and launch_pool; else hipErrorInvalidValue
 hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, float eps, hipStream_t s);
+// the same LayerNorm IN PLACE on rows [0, rows) of x, and stats[row] = (mean, rstd) of the ROUNDED result in the canonical
+// summation order: bit-identical to launch_ln_stats_canonical on x afterwards (CLIP's pre_layrnorm, the statistics source
+// of the pass's first folded LayerNorm)
+hipError_t launch_pre_ln(void* x, const float* gamma, const float* beta, int64_t rows, int d, float eps, float* stats, hipStream_t s);
+// LayerNorm of row b*197+tok of d values -> bf16 [B, d] (launch_pool without its L2 step: CLIP's post_layernorm)
+hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s);
+// f32 [rows, p] -> x / max(||x||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024
+hipError_t launch_l2_rows(const float* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
 // per-row LayerNorm statistics of bf16 rows of d: stats[row] = (mean, rstd)
 hipError_t launch_ln_stats(const void* x, int64_t rows, int d, float eps, float* stats, hipStream_t s);
 // the same statistics in the CANONICAL summation order shared with the EPI_BIAS_RES_STATS epilogue, for rows

@@ -251,6 +251,162 @@ __global__ __launch_bounds__(256) void normalise_rows_f32(const float* __restric
     }
 }
 
+// CLIP's pre_layrnorm (transformers modeling_clip.py, CLIPVisionTransformer.forward: hidden_states = self.pre_layrnorm(
+// hidden_states) before the encoder): LayerNorm(gamma, beta) of every token row IN PLACE, the two-pass f32 arithmetic of
+// layernorm_rows, and in the same launch the (mean, rstd) of the ROUNDED row in the canonical order of gemm_epilogue.h --
+// what ln_stats_canonical_rows would find in x afterwards, bit for bit -- so that the first folded LayerNorm of the pass
+// needs no further pass over x.  The rounded row goes through the wave's own 2 D bytes of LDS to change from the row
+// layout (RowShape) to the canonical one (lane = slice, column group).
+template <int D>
+__global__ __launch_bounds__(256) void pre_ln_rows(bf16_t* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                   int64_t rows, float eps, float* __restrict__ stats) {
+    __shared__ __attribute__((aligned(16))) bf16_t rowbuf[4][D];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+    if (row >= rows) return;  // wave-uniform: no workgroup barrier below
+    bf16_t* xr = x + row * D;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
+    float v[NV];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s += v[j];
+    const float mean = wave_sum(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        v[j] -= mean;
+        q += v[j] * v[j];
+    }
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+    bf16_t* lr = rowbuf[wave];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int c = t * 64 * V + lane * V;
+        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
+        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
+        typename RS::bvec o;
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(v[t * V + j] * rstd * gv[j] + bv[j]);
+        *(typename RS::bvec*)(xr + c) = o;
+        *(typename RS::bvec*)(lr + c) = o;
+    }
+    // the wave reads what its own lanes wrote: LDS operations of one wave complete in order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // as ln_stats_canonical_rows, the row read from LDS
+    constexpr int nslice = D >> 6;
+    const int slice = lane >> 2, grp = lane & 3;
+    float cs[2] = {0.f, 0.f}, cq[2] = {0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int sl = slice + 16 * h;
+        if (sl < nslice) {
+            const bf16_t* sr = lr + sl * 64 + grp * 4;
+            uint2 pk[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pk[j] = *(const uint2*)(sr + j * 16);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ln_accumulate(pk[j], cs[h], cq[h]);
+        }
+        cs[h] += __shfl_xor(cs[h], 1, 64);
+        cq[h] += __shfl_xor(cq[h], 1, 64);
+        cs[h] += __shfl_xor(cs[h], 2, 64);
+        cq[h] += __shfl_xor(cq[h], 2, 64);
+    }
+    double S = 0.0, Q = 0.0;
+    for (int k = 0; k < nslice; ++k) {
+        S += (double)__shfl(k < 16 ? cs[0] : cs[1], 4 * (k & 15), 64);
+        Q += (double)__shfl(k < 16 ? cq[0] : cq[1], 4 * (k & 15), 64);
+    }
+    if (lane == 0) *(float2*)(stats + 2 * row) = ln_finish_row(S, Q, D, eps);
+}
+
+// CLIP's post_layernorm on the pooled row (modeling_clip.py, CLIPVisionTransformer.forward: pooled_output =
+// self.post_layernorm(last_hidden_state[:, 0, :])): pool_ln_l2's LayerNorm of row b * 197 + tok, rounded to bf16 [B, D]
+// for the projection GEMM -- no L2 step, the projected vector is what gets normalised.
+template <int D>
+__global__ __launch_bounds__(256) void pool_ln_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
+                                                    const float* __restrict__ beta, int B, int tok, float eps, bf16_t* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const bf16_t* xr = x + ((int64_t)b * VIT_T + tok) * D;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
+    float v[NV];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s += v[j];
+    const float mean = wave_sum(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        v[j] -= mean;
+        q += v[j] * v[j];
+    }
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int c = t * 64 * V + lane * V;
+        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
+        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
+        typename RS::bvec o;
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(v[t * V + j] * rstd * gv[j] + bv[j]);
+        *(typename RS::bvec*)(y + (int64_t)b * D + c) = o;
+    }
+}
+
+// The L2 step of pool_ln_l2 on its own, for the projected rows of a CLIP tower (modeling_clip.py, CLIPModel.
+// get_image_features callers normalise image_embeds: x / ||x||; here torch.nn.functional.normalize's x / max(||x||, 1e-12)
+// as everywhere in this engine): f32 [rows, p] -> f32 and / or bf16.  One wave per row, p % 64 == 0, p <= 1024: a lane
+// holds columns 4 lane + 256 k .. + 3.
+__global__ __launch_bounds__(256) void l2_rows(const float* __restrict__ x, int64_t rows, int p, float* __restrict__ y_f32,
+                                               bf16_t* __restrict__ y_bf16) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = x + row * p;
+    f32x4 v[4];
+    float n2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane * 4 + k * 256;
+        v[k] = c < p ? *(const f32x4*)(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) n2 += v[k][j] * v[k][j];
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane * 4 + k * 256;
+        if (c >= p) continue;
+        f32x4 o;
+        bf16x4 ob;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = v[k][j] * inv;
+            ob[j] = (bf16_t)o[j];
+        }
+        if (y_f32) *(f32x4*)(y_f32 + row * p + c) = o;
+        if (y_bf16) *(bf16x4*)(y_bf16 + row * p + c) = ob;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, hipStream_t s) {
@@ -309,5 +465,26 @@ hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int
     if (!vit_width_built(d)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
     ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tok, eps, emb_f32, (bf16_t*)emb_bf16)
+    return hipGetLastError();
+}
+
+hipError_t launch_pre_ln(void* x, const float* gamma, const float* beta, int64_t rows, int d, float eps, float* stats, hipStream_t s) {
+    if (!vit_width_built(d)) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
+    ROW_KERNEL_BY_WIDTH(d, pre_ln_rows, dim3((unsigned)((rows + 3) / 4)), s, (bf16_t*)x, gamma, beta, rows, eps, stats)
+    return hipGetLastError();
+}
+
+hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s) {
+    if (!vit_width_built(d)) return hipErrorInvalidValue;
+    if (B <= 0) return hipSuccess;
+    ROW_KERNEL_BY_WIDTH(d, pool_ln_rows, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tok, eps, (bf16_t*)y)
+    return hipGetLastError();
+}
+
+hipError_t launch_l2_rows(const float* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
+    if (p < 64 || (p % 64) != 0 || p > 1024) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(l2_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, p, y_f32, (bf16_t*)y_bf16);
     return hipGetLastError();
 }

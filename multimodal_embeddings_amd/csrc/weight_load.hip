@@ -220,8 +220,7 @@ namespace {
 
 // argument checks of both ViT loaders (the messages of both name the f32 loader): the geometry against the supported
 // set, every tensor pointer.  Touches nothing in the context but its error text.
-int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w) {
-    const char* who = "mme_load_vit";
+int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who = "mme_load_vit", bool bias_free_patch = false) {
     if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
     // every refusal names the field, the value found and what is supported
     if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
@@ -233,7 +232,7 @@ int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w) {
     if (w->mlp < 64 || (w->mlp % 64) != 0 || w->mlp > VIT_MAX_F)
         return fail(c, MME_E_ARG, "%s: mlp = %d; supported: multiples of 64 up to %d", who, w->mlp, VIT_MAX_F);
     if (w->layers < 1 || w->layers > VIT_MAX_L) return fail(c, MME_E_ARG, "%s: layers = %d; supported: 1..%d", who, w->layers, VIT_MAX_L);
-    if (!w->cls_token || !w->pos_emb || !w->patch_w || !w->patch_b || !w->lnf_g || !w->lnf_b || !w->layer)
+    if (!w->cls_token || !w->pos_emb || !w->patch_w || (!w->patch_b && !bias_free_patch) || !w->lnf_g || !w->lnf_b || !w->layer)
         return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
     for (int l = 0; l < w->layers; ++l) {
         const mme_vit_layer& a = w->layer[l];
@@ -260,6 +259,12 @@ int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp};
     c->ln_eps = w->ln_eps;
     c->layer.assign((size_t)w->layers, LayerDev{});
+    // a plain ViT until a CLIP load says otherwise (load_clip sets these after this call; their buffers were freed above)
+    c->clip = false;
+    c->act = 0;
+    c->proj_dim = 0;
+    c->pre_g = c->pre_b = nullptr;
+    c->proj_w = nullptr;
     return MME_OK;
 }
 
@@ -275,7 +280,7 @@ void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&&
     f(w.cls_token, D);
     f(w.pos_emb, (size_t)VIT_T * D);
     f(w.patch_w, D * VIT_PATCH_DIM);
-    f(w.patch_b, D);
+    if (w.patch_b) f(w.patch_b, D);  // CLIP: no bias on the patch projection
     f(w.lnf_g, D);
     f(w.lnf_b, D);
     for (mme_vit_layer& a : layer) {
@@ -304,7 +309,7 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
     };
     if ((r = plain(w.cls_token, D, &c->cls))) return r;
     if ((r = plain(w.pos_emb, (size_t)VIT_T * D, &c->pos))) return r;
-    if ((r = plain(w.patch_b, D, &c->patch_b))) return r;
+    if ((r = w.patch_b ? plain(w.patch_b, D, &c->patch_b) : p.zeros(D, &c->patch_b))) return r;  // CLIP: a zero table
     if ((r = plain(w.lnf_g, D, &c->lnf_g))) return r;
     if ((r = plain(w.lnf_b, D, &c->lnf_b))) return r;
     if ((r = plain_bf16(w.patch_w, rD, VIT_PATCH_DIM, &c->patch_w))) return r;
@@ -352,9 +357,77 @@ int load_vit(mme_ctx* c, const mme_vit_weights* w, P p) {
     return r;
 }
 
+// ---- CLIP image tower: the ViT sequence, then pre_g, pre_b [D] and proj_w bf16 [P, D] -------------------------------------------
+int validate_clip_weights(mme_ctx* c, const mme_clip_weights* w) {
+    const char* who = "mme_load_clip";
+    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
+    int r;
+    if ((r = validate_vit_weights(c, &w->vit, who, true))) return r;
+    if (!w->pre_g || !w->pre_b) return fail(c, MME_E_ARG, "%s: pre_g / pre_b (pre_layrnorm) is a null tensor pointer", who);
+    if (w->act != 0 && w->act != 1) return fail(c, MME_E_ARG, "%s: act = %d; supported: 0 (erf-GELU), 1 (QuickGELU)", who, w->act);
+    if (w->proj_dim != 0 && (w->proj_dim < 64 || (w->proj_dim % 64) != 0 || w->proj_dim > 1024))
+        return fail(c, MME_E_ARG, "%s: proj_dim = %d; supported: 0 (no projection) or a multiple of 64 up to 1024", who, w->proj_dim);
+    if ((w->proj_dim != 0) != (w->proj_w != nullptr))
+        return fail(c, MME_E_ARG, "%s: proj_dim = %d with proj_w %s; supported: both set, or proj_dim = 0 with proj_w NULL", who, w->proj_dim,
+                    w->proj_w ? "set" : "NULL");
+    return MME_OK;
+}
+
+template <class P>
+int prepare_clip(mme_ctx* c, P& p, const mme_clip_weights& w) {
+    int r;
+    const size_t D = (size_t)w.vit.hidden;
+    if ((r = prepare_vit(c, p, w.vit))) return r;
+    if ((r = p.table(w.pre_g, D, 1.f, false, &c->pre_g))) return r;
+    if ((r = p.table(w.pre_b, D, 1.f, false, &c->pre_b))) return r;
+    if (w.proj_w) {
+        const void* s[1] = {w.proj_w};
+        const size_t rows[1] = {(size_t)w.proj_dim};
+        if ((r = p.bf16(s, rows, 1, D, 1.f, false, &c->proj_w))) return r;
+    }
+    return MME_OK;
+}
+
+template <class P>
+int load_clip(mme_ctx* c, const mme_clip_weights* w, P p) {
+    int r;
+    if ((r = begin_vit_load(c, &w->vit))) return r;
+    std::vector<mme_vit_layer> layer(w->vit.layer, w->vit.layer + w->vit.layers);
+    mme_clip_weights v = *w;
+    v.vit.layer = layer.data();
+    r = p.stage([&](auto& put) {
+        each_vit_tensor(v.vit, layer, put);
+        put(v.pre_g, (size_t)v.vit.hidden);
+        put(v.pre_b, (size_t)v.vit.hidden);
+        if (v.proj_w) put(v.proj_w, (size_t)v.proj_dim * v.vit.hidden);
+    });
+    if (r == MME_OK) r = prepare_clip(c, p, v);
+    r = p.finish(r);
+    if (r == MME_OK) {
+        c->clip = true;
+        c->act = w->act;
+        c->proj_dim = w->proj_dim;
+    }
+    end_vit_load(c, r == MME_OK);
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mme_load_clip(mme_ctx* c, const mme_clip_weights* w) {
+    int r;
+    if ((r = validate_clip_weights(c, w))) return r;
+    return load_clip(c, w, HostPrep{c});
+}
+
+int mme_load_clip_as(mme_ctx* c, const mme_clip_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_clip_weights(c, w))) return r;
+    if ((r = check_load_dtype(c, dtype, "mme_load_clip_as"))) return r;
+    return load_clip(c, w, DevPrep(c, dtype, stream, "mme_load_clip_as"));
+}
 
 int mme_load_vit(mme_ctx* c, const mme_vit_weights* w) {
     int r;

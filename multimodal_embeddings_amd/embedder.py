@@ -119,8 +119,11 @@ class RegionEmbedder:
         on seeded synthetic weights with one WARNING, or raises with `allow_synthetic=False`.  `weights=` (a dict) wins.
         `encoder`: "vit_b16" (exactly ViT-B/16), "vit" (any ViT/16 @224 of the supported family -- ViT-S, -B, -L widths,
         weights.SUPPORTED_VIT: a checkpoint directory brings its own geometry in config.json, seeded weights take
-        `geometry=`, e.g. weights.VIT_L16, a `weights=` dict is sized by its tensors) or "mllama_tiles".  `self.embed_dim`
-        is the width of the vectors this object returns."""
+        `geometry=`, e.g. weights.VIT_L16, a `weights=` dict is sized by its tensors), "clip" (a CLIP ViT/16 image tower of
+        the same family: pre-LN, QuickGELU or GELU, visual projection; a checkpoint directory of CLIPVisionModel[WithProjection]
+        or a whole CLIPModel, seeded weights at `geometry=` a weights.CLIPGeometry, default CLIP-B/16, or a `weights=` dict in
+        transformers' names, whose activation `geometry=` names when it is not QuickGELU) or "mllama_tiles".
+        `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim)."""
         import torch
 
         from .checkpoint import read_checkpoint, resolve_model_source
@@ -128,9 +131,9 @@ class RegionEmbedder:
         self.torch = torch
         self.model_name = model_name
         self.checkpoint = None
-        if encoder not in ("vit_b16", "vit", "mllama_tiles"):
-            raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16), 'vit' (the ViT/16 family: ViT-S, -B and -L widths) "
-                             "or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+        if encoder not in ("vit_b16", "vit", "clip", "mllama_tiles"):
+            raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16), 'vit' (the ViT/16 family: ViT-S, -B and -L widths), "
+                             "'clip' (a CLIP ViT/16 image tower of that family) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
         if encoder == "vit_b16" and geometry is not None:
             raise ValueError("encoder='vit_b16' is ViT-B/16 only; pass encoder='vit' with geometry=")
         # a caller's engine carries its own weights
@@ -172,6 +175,8 @@ class RegionEmbedder:
                 if encoder == "mllama_tiles":
                     geom = ck.geometry if geometry is None else geometry
                     e.load_tile_vit_checkpoint(ck, geom)
+                elif encoder == "clip":
+                    e.load_clip_checkpoint(ck)
                 else:
                     e.load_vit_checkpoint(ck)
                 if ck.image_mean is not None:
@@ -182,6 +187,12 @@ class RegionEmbedder:
                 from .weights import make_tile_vit_weights
 
                 w = weights if weights is not None else (make_tile_vit_weights(seed + 1, geometry) if geometry else make_tile_vit_weights(seed + 1))
+            elif encoder == "clip":
+                from .weights import CLIP_B16, make_clip_weights
+
+                w = weights if weights is not None else make_clip_weights(seed, geometry or CLIP_B16)
+                if weights is None and geometry is None:
+                    geometry = CLIP_B16
             elif encoder == "vit" and geometry is not None:
                 w = weights if weights is not None else make_vit_weights(seed, geometry)
             else:
@@ -191,6 +202,8 @@ class RegionEmbedder:
                 e = Engine(d)
                 if encoder == "mllama_tiles":
                     e.load_tile_vit(w, geometry)
+                elif encoder == "clip":
+                    e.load_clip(w, geom=geometry)
                 elif encoder == "vit":
                     e.load_vit(w, geom=geometry)
                 else:
@@ -202,7 +215,7 @@ class RegionEmbedder:
                 e.set_chunk(chunk)
         if prune_last_layer is None:  # default: on for the contexts this object created, a caller's engine stays as it is
             prune_last_layer = engine is None
-        if prune_last_layer and encoder in ("vit_b16", "vit"):
+        if prune_last_layer and encoder in ("vit_b16", "vit", "clip"):
             # only the pooled token's row of the last layer is computed past its attention (mme_set_forward_pruning): callers of
             # this class only ever receive pooled vectors, and those are bit-identical, 6 % sooner.  The benchmark's headline
             # drives the Engine directly and times the whole forward; `prune_last_layer=False` restores that here.

@@ -117,6 +117,115 @@ def infer_vit_geometry(w: dict, eps: float = 1e-12) -> ViTGeometry:
                        layer_norm_eps=float(eps))
 
 
+# ---- CLIP ViT/16 image towers ---------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class CLIPGeometry(ViTGeometry):
+    """A CLIP image tower at the engine's ViT/16 @224 geometry (transformers CLIPVisionConfig): the ViT fields, with
+    layer_norm_eps 1e-5, plus the width of the shared image / text space (`projection_dim`; None: no visual_projection,
+    the embedding is the post_layernorm row) and the MLP activation ("quick_gelu": OpenAI weights, "gelu": LAION
+    conversions).  The defaults are clip-vit-base-patch16."""
+
+    layer_norm_eps: float = 1e-5
+    projection_dim: int | None = 512
+    hidden_act: str = "quick_gelu"
+
+    @property
+    def embed_dim(self) -> int:
+        return self.projection_dim or self.hidden_size
+
+
+CLIP_B16 = CLIPGeometry()
+CLIP_ACTS = ("gelu", "quick_gelu")  # include/mme.h mme_clip_weights.act: the index
+
+
+def clip_geometry_problem(geom: CLIPGeometry):
+    """As `vit_geometry_problem`, with the two CLIP fields: None, or (field, value found, supported values as text)."""
+    bad = vit_geometry_problem(geom)
+    if bad:
+        return bad
+    if geom.hidden_act not in CLIP_ACTS:
+        return "hidden_act", geom.hidden_act, ", ".join(CLIP_ACTS)
+    P = geom.projection_dim
+    if P is not None and (isinstance(P, bool) or not isinstance(P, int) or P < 64 or P % 64 or P > 1024):
+        return "projection_dim", P, "absent, or a multiple of 64 up to 1024"
+    return None
+
+
+def clip_tensor_specs(geom: CLIPGeometry = CLIP_B16):
+    """(name, shape, kind) in a fixed order, Hugging Face `CLIPVisionModelWithProjection` state-dict names
+    (transformers models/clip/modeling_clip.py); kind in {matrix, bias, gamma}.  Without `projection_dim` the list ends
+    at post_layernorm (`CLIPVisionModel`)."""
+    D, F, P = geom.hidden_size, geom.intermediate_size, geom.patch_size
+    v = "vision_model."
+    specs = [
+        (v + "embeddings.class_embedding", (D,), "matrix"),
+        (v + "embeddings.patch_embedding.weight", (D, geom.num_channels, P, P), "matrix"),
+        (v + "embeddings.position_embedding.weight", (geom.seq_len, D), "matrix"),
+        (v + "pre_layrnorm.weight", (D,), "gamma"),
+        (v + "pre_layrnorm.bias", (D,), "bias"),
+    ]
+    for i in range(geom.num_layers):
+        p = f"{v}encoder.layers.{i}."
+        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
+        for n in ("q", "k", "v", "out"):
+            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
+        specs += [
+            (p + "layer_norm2.weight", (D,), "gamma"),
+            (p + "layer_norm2.bias", (D,), "bias"),
+            (p + "mlp.fc1.weight", (F, D), "matrix"),
+            (p + "mlp.fc1.bias", (F,), "bias"),
+            (p + "mlp.fc2.weight", (D, F), "matrix"),
+            (p + "mlp.fc2.bias", (D,), "bias"),
+        ]
+    specs += [(v + "post_layernorm.weight", (D,), "gamma"), (v + "post_layernorm.bias", (D,), "bias")]
+    if geom.projection_dim:
+        specs.append(("visual_projection.weight", (geom.projection_dim, D), "matrix"))
+    return specs
+
+
+def make_clip_weights(seed: int = 1, geom: CLIPGeometry = CLIP_B16, std: float = 0.02) -> dict[str, np.ndarray]:
+    """Seeded synthetic weights of a CLIP image tower, f32 arrays holding bf16-representable values; the generator of
+    `make_vit_weights` on `clip_tensor_specs`.  LayerNorm weights are 1 + 0.25 z and biases 0.1 z (z ~ N(0, 1)): far enough
+    from 1 and 0 that a dropped LayerNorm, or two LayerNorms exchanged, moves the embedding by much more than the bf16
+    path's error.  Matrices N(0, std), the other biases N(0, std)."""
+    out: dict[str, np.ndarray] = {}
+    for tid, (name, shape, kind) in enumerate(clip_tensor_specs(geom)):
+        n = int(np.prod(shape))
+        z = irwin_hall_normal(seed, tid, n)
+        norm = "layer_norm" in name or "layrnorm" in name or "layernorm" in name
+        if kind == "gamma":
+            z = np.float32(1.0) + z * np.float32(0.25)
+        elif kind == "bias" and norm:
+            z = z * np.float32(0.1)
+        else:
+            z = z * np.float32(std)
+        out[name] = round_to_bf16(z).reshape(shape)
+    return out
+
+
+def clip_flops_per_crop(geom: CLIPGeometry = CLIP_B16) -> int:
+    """`vit_flops_per_crop` plus the projection of the pooled row (2 D P); pre_layrnorm, like every LayerNorm, is not counted."""
+    return vit_flops_per_crop(geom) + 2 * geom.hidden_size * (geom.projection_dim or 0)
+
+
+def infer_clip_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quick_gelu") -> CLIPGeometry:
+    """The geometry of a `clip_tensor_specs` weight dict, read off its tensor shapes; heads of 64.  The activation is not in
+    the tensors: `hidden_act` names it."""
+    pw = np.shape(w["vision_model.embeddings.patch_embedding.weight"])
+    D, patch = int(pw[0]), int(pw[-1])
+    tokens = int(np.shape(w["vision_model.embeddings.position_embedding.weight"])[0])
+    grid = int(round((tokens - 1) ** 0.5))
+    layers = 0
+    while f"vision_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError("the weight dict holds no 'vision_model.encoder.layers.0.mlp.fc1.weight'")
+    F = int(np.shape(w["vision_model.encoder.layers.0.mlp.fc1.weight"])[0])
+    P = int(np.shape(w["visual_projection.weight"])[0]) if "visual_projection.weight" in w else None
+    return CLIPGeometry(image_size=grid * patch, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
+                        layer_norm_eps=float(eps), projection_dim=P, hidden_act=hidden_act)
+
+
 def _splitmix64(x: np.ndarray) -> np.ndarray:
     """splitmix64 finaliser on uint64 arrays (wrapping arithmetic)."""
     with np.errstate(over="ignore"):
