@@ -236,6 +236,26 @@ int mme_set_normalisation(mme_ctx* ctx, const float mean[3], const float std[3])
  * then hold nothing of meaning.  A batch of 224 x 224 crops only and mme_preprocess_tiles always read the table. */
 int mme_normalisation_form(mme_ctx* ctx, int32_t* exact, float a[3], float b[3]);
 
+/* How mme_preprocess and mme_embed make the 224 x 224 pixels of a crop (mme_preprocess_tiles ignores it).
+ *   MME_RESIZE_FIT_PAD (0, what a fresh context has): the Mllama rule of one tile -- aspect-preserving fit into
+ *     224 x 224, Pillow BILINEAR, zero pad right / bottom before normalisation (transformers
+ *     image_processing_pil_mllama.py:246-295, 392-429, 483-541).
+ *   MME_RESIZE_CLIP (1): CLIP's own rule, what CLIPImageProcessorPil does -- the short edge becomes 224 and the long
+ *     edge int(224 * long / short) (transformers image_transforms.py:246-310 get_resize_output_image_size, reached from
+ *     image_processing_backends.py:521-570 PilBackend.resize with size = {"shortest_edge": 224}), Pillow BICUBIC
+ *     (libImaging/Resample.c, 8-bit path: a = -0.5, support 2, 22-bit coefficients, a clamp to 0..255 after each
+ *     pass), then the centre crop top = (new_h - 224) / 2, left = (new_w - 224) / 2 (image_processing_backends.py:
+ *     602-617 PilBackend.center_crop -> image_transforms.py:445 center_crop).  No padding ever; the uint8 window is
+ *     bit-equal to Pillow's, only the window is computed.  Normalisation and the patch layout are the same as under rule 0.
+ * A batch of 224 x 224 crops only is the identity under both rules and takes the same kernels.
+ * Any other value is MME_E_ARG; mme_last_error names the value and the supported set.
+ * The rule is a property of how the caller wants pixels made, like mme_set_normalisation: no weight load
+ * (mme_load_vit*, mme_load_clip*, mme_load_tile_vit*) resets or changes it.  Crops stay limited to 1..8000 per side. */
+enum { MME_RESIZE_FIT_PAD = 0, MME_RESIZE_CLIP = 1 };
+int mme_set_resize_rule(mme_ctx* ctx, int rule);
+/* *rule = the current rule (read-only, no device work). */
+int mme_resize_rule(mme_ctx* ctx, int32_t* rule);
+
 /* Rows of the internal activation workspace = crops per encoder pass (default 4096: one pass
  * for the headline batch; 11.6 GiB of workspace at ViT-B/16; larger passes lose less to tile quantisation).
  * The workspace is 197 * crops * (12 * hidden + 2 * mlp + 8 * (1 + hidden / 64)) bytes, plus 301 056 bytes of patch

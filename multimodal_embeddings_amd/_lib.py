@@ -125,6 +125,8 @@ EXPORTS = {
     "mme_weight_prep_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_WeightPrepApplyArgs), C.c_void_p]),
     "mme_set_normalisation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mme_normalisation_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mme_set_resize_rule": (C.c_int, [C.c_void_p, C.c_int]),
+    "mme_resize_rule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_ln_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -548,6 +550,23 @@ class Engine:
         a, b = np.zeros(3, dtype=np.float32), np.zeros(3, dtype=np.float32)
         self._check(self.lib.mme_normalisation_form(self.h, C.byref(exact), _fp(a), _fp(b)), "mme_normalisation_form")
         return bool(exact.value), a, b
+
+    RESIZE_RULES = {"fit_pad": 0, "clip": 1}  # MME_RESIZE_* (include/mme.h)
+
+    def set_resize_rule(self, rule):
+        """How `preprocess` / `embed` make 224 x 224 pixels (mme_set_resize_rule): "fit_pad" (the default: fit, BILINEAR, zero
+        pad) or "clip" (CLIPImageProcessor's shortest-edge BICUBIC resize + centre crop).  An int goes to the library as it is."""
+        if isinstance(rule, str):
+            if rule not in self.RESIZE_RULES:
+                raise MmeError(f"resize rule {rule!r}: supported {sorted(self.RESIZE_RULES)}")
+            rule = self.RESIZE_RULES[rule]
+        self._check(self.lib.mme_set_resize_rule(self.h, int(rule)), "mme_set_resize_rule")
+
+    @property
+    def resize_rule(self) -> str:
+        v = C.c_int32(-1)
+        self._check(self.lib.mme_resize_rule(self.h, C.byref(v)), "mme_resize_rule")
+        return {n: k for k, n in self.RESIZE_RULES.items()}[v.value]
 
     def set_gemm_variant(self, variant: int):
         self._check(self.lib.mme_set_gemm_variant(self.h, int(variant)), "mme_set_gemm_variant")

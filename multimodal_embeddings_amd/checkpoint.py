@@ -205,8 +205,40 @@ def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
                            norm_eps=float(cfg.get("norm_eps", g.norm_eps)))
 
 
-def _read_preprocessor(path: str, encoder: str):
-    """preprocessor_config.json -> (mean, std) or (None, None); raises for what K1 cannot honour."""
+RESIZE_RULES = ("fit_pad", "clip")  # _lib.Engine.RESIZE_RULES / MME_RESIZE_* (include/mme.h)
+CLIP_RULE_ENCODERS = ("vit_b16", "vit", "clip")  # the single-tile encoders K1's "clip" rule feeds
+
+
+def check_resize_rule(resize_rule, encoder: str) -> str:
+    """None -> "fit_pad"; raises for an unknown rule and for "clip" with the tile encoder."""
+    rule = "fit_pad" if resize_rule is None else resize_rule
+    if rule not in RESIZE_RULES:
+        raise MmeError(f"resize_rule = {resize_rule!r}; supported {RESIZE_RULES} (None means 'fit_pad')")
+    if rule == "clip" and encoder not in CLIP_RULE_ENCODERS:
+        raise MmeError(f"resize_rule = 'clip' (shortest-edge BICUBIC resize + centre crop to 224 x 224) feeds the single-tile encoders "
+                       f"{CLIP_RULE_ENCODERS} only; encoder = {encoder!r} has its own multi-tile preprocessing")
+    return rule
+
+
+def _check_clip_rule_fields(pc: dict, where: str):
+    """Under resize_rule = "clip" the file must describe exactly what the kernels do (CLIPImageProcessor's defaults)."""
+    resample = pc.get("resample", 3)
+    if resample != 3:
+        raise MmeError(f"{where}: resample = {resample!r}; resize_rule = 'clip' resizes with Pillow BICUBIC (resample = 3) only")
+    size = pc.get("size", {"shortest_edge": 224})
+    if not (size == {"shortest_edge": 224} or (isinstance(size, int) and not isinstance(size, bool) and size == 224)):
+        raise MmeError(f"{where}: size = {size!r}; resize_rule = 'clip' supports size = {{'shortest_edge': 224}} (or the bare int 224) only")
+    if pc.get("do_resize", True) is False:
+        raise MmeError(f"{where}: do_resize = False; resize_rule = 'clip' always resizes (supported: do_resize = True)")
+    if pc.get("do_center_crop", True) is not True:
+        raise MmeError(f"{where}: do_center_crop = {pc.get('do_center_crop')!r}; resize_rule = 'clip' always centre-crops (supported: do_center_crop = True)")
+    crop = pc.get("crop_size", 224)
+    if not (crop == {"height": 224, "width": 224} or (isinstance(crop, int) and not isinstance(crop, bool) and crop == 224)):
+        raise MmeError(f"{where}: crop_size = {crop!r}; resize_rule = 'clip' supports crop_size = 224 x 224 ({{'height': 224, 'width': 224}} or 224) only")
+
+
+def _read_preprocessor(path: str, encoder: str, resize_rule: str = "fit_pad"):
+    """preprocessor_config.json -> (mean, std) or (None, None); raises for what K1 cannot honour under `resize_rule`."""
     global _warned_resize_rule
     pc = _load_json(path)
     where = os.path.basename(path)
@@ -217,6 +249,9 @@ def _read_preprocessor(path: str, encoder: str):
         raise MmeError(f"{where}: rescale_factor = {rf!r}; K1 rescales by 1/255 = {1.0 / 255.0!r}")
     if pc.get("do_normalize", True) is not True:
         raise MmeError(f"{where}: do_normalize = {pc.get('do_normalize')!r}; K1 always normalises with image_mean / image_std")
+    if resize_rule == "clip":
+        _check_clip_rule_fields(pc, where)
+        return _mean_std(pc, where)
     resample = pc.get("resample", 2)
     clip_rule = encoder == "clip" and (resample == 3 or pc.get("do_center_crop") or "crop_size" in pc)
     if resample != 2 and not (encoder == "clip" and resample == 3):
@@ -237,6 +272,10 @@ def _read_preprocessor(path: str, encoder: str):
         logger.warning(f"{where}: image_processor_type = {pc.get('image_processor_type')!r} does not use Mllama's fit-and-pad resize{clip_fields}; K1 keeps the "
                        "aspect-preserving fit into 224 x 224 with zero padding (this encoder's contract, DESIGN.md) and applies only the "
                        "checkpoint's image_mean / image_std")
+    return _mean_std(pc, where)
+
+
+def _mean_std(pc: dict, where: str):
     mean, std = pc.get("image_mean"), pc.get("image_std")
     if mean is None or std is None:
         return None, None
@@ -318,11 +357,16 @@ def _unify_dtype(tensors: dict, keys: dict):
     return {n: (t if t.dtype == major else t.to(major)).contiguous() for n, t in tensors.items()}, names[major]
 
 
-def read_checkpoint(path, encoder: str = "vit_b16") -> Checkpoint:
-    """Directory -> Checkpoint (see the module docstring).  Raises MmeError naming the file, field or key at fault."""
+def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpoint:
+    """Directory -> Checkpoint (see the module docstring).  Raises MmeError naming the file, field or key at fault.
+
+    `resize_rule` ("fit_pad", the same as None, or "clip") is the rule K1 will run: under "clip" a preprocessor_config.json
+    must describe CLIPImageProcessor's shortest-edge-224 BICUBIC resize and 224 x 224 centre crop exactly, and a directory
+    without one gets CLIP's defaults (the engine's mean / std)."""
     path = os.fspath(path)
     if encoder not in ENCODERS:
         raise ValueError(f"encoder must be one of {ENCODERS}")
+    resize_rule = check_resize_rule(resize_rule, encoder)
     if not os.path.isdir(path):
         raise MmeError(f"{path!r} is not a local checkpoint directory; this engine never fetches")
     cfg_path = os.path.join(path, "config.json")
@@ -370,7 +414,7 @@ def read_checkpoint(path, encoder: str = "vit_b16") -> Checkpoint:
     mean = std = None
     pre_path = os.path.join(path, "preprocessor_config.json")
     if os.path.exists(pre_path):
-        mean, std = _read_preprocessor(pre_path, encoder)
+        mean, std = _read_preprocessor(pre_path, encoder, resize_rule)
         source.append(pre_path)
     return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source)
 
@@ -429,9 +473,11 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m multimodal_embeddings_amd.checkpoint", description="what a load of this checkpoint directory would find")
     ap.add_argument("directory")
     ap.add_argument("--encoder", choices=ENCODERS, default="vit_b16")
+    ap.add_argument("--resize-rule", choices=RESIZE_RULES, default="fit_pad",
+                    help="the rule K1 would run: 'clip' checks preprocessor_config.json against the shortest-edge BICUBIC resize + centre crop")
     a = ap.parse_args(argv)
     try:
-        ck = read_checkpoint(a.directory, a.encoder)
+        ck = read_checkpoint(a.directory, a.encoder, a.resize_rule)
     except MmeError as e:
         print(f"cannot load: {e}")
         return 1

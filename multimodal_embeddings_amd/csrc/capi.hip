@@ -389,6 +389,18 @@ struct K1Plan {
 // LDS budget of classes 0 and 1
 constexpr int kHLds = 32 * 1024;
 
+// The bands of crop i's horizontal pass: source rows [first_row, first_row + nrows) of row_bytes each, whose table takes
+// tab_lds bytes of LDS when it rides beside the band.  Picks the class and appends the bands to it.
+void plan_bands(K1Plan& p, int i, int row_bytes, int tab_lds, int first_row, int nrows) {
+    const int fit = tab_lds < kHLds ? (kHLds - tab_lds) / row_bytes : 0;  // rows that fit beside the table
+    const int cls = fit >= K1_H_RPT ? 0 : (fit >= K1_H_RPT_WIDE ? 1 : 2);
+    int rows = cls == 0 ? (fit & ~(K1_H_RPT - 1)) : K1_H_RPT_WIDE;
+    if (rows > 64) rows = 64;
+    for (int r = 0; r < nrows; r += rows) p.work[cls].push_back(HWork{i, first_row + r, (nrows - r) < rows ? (nrows - r) : rows});
+    const int bb = (rows < nrows ? rows : nrows) * row_bytes + (cls < 2 ? tab_lds : 0);
+    if (bb > p.lds[cls]) p.lds[cls] = bb;
+}
+
 void plan_crop(mme_ctx* c, K1Plan& p, int i, CropDesc& d) {
     d.tmp_off = 0;
     d.tab_off = (int64_t)p.tab_bytes;
@@ -398,15 +410,7 @@ void plan_crop(mme_ctx* c, K1Plan& p, int i, CropDesc& d) {
     if (d.new_w == d.w) return;
     d.tmp_off = (int64_t)p.tmp_bytes;
     p.tmp_bytes += (size_t)d.h * k1_tmp_pitch(d.new_w);
-    const int row_bytes = d.w * 3;
-    const int tab_lds = k1_h_table_lds(d.w, d.new_w);
-    const int fit = tab_lds < kHLds ? (kHLds - tab_lds) / row_bytes : 0;  // rows that fit beside the table
-    const int cls = fit >= K1_H_RPT ? 0 : (fit >= K1_H_RPT_WIDE ? 1 : 2);
-    int rows = cls == 0 ? (fit & ~(K1_H_RPT - 1)) : K1_H_RPT_WIDE;
-    if (rows > 64) rows = 64;
-    for (int r = 0; r < d.h; r += rows) p.work[cls].push_back(HWork{i, r, (d.h - r) < rows ? (d.h - r) : rows});
-    const int bb = (rows < d.h ? rows : d.h) * row_bytes + (cls < 2 ? tab_lds : 0);
-    if (bb > p.lds[cls]) p.lds[cls] = bb;
+    plan_bands(p, i, d.w * 3, k1_h_table_lds(d.w, d.new_w), 0, d.h);
 }
 
 // copies the band lists to the device (class 0 | class 1 | class 2)
@@ -436,6 +440,87 @@ int launch_h_pass(mme_ctx* c, const K1Plan& p, const uint8_t* pix, int n, hipStr
     return MME_OK;
 }
 
+// ---- K1 under MME_RESIZE_CLIP (preprocess_clip.hip) ---------------------------------------------------------------------
+// transformers image_transforms.py get_resize_output_image_size, size = {"shortest_edge": 224}, default_to_square = False:
+// the short edge gets 224, the long edge int(224 * long / short) -- the Python float expression in that order, in f64
+void clip_resized_size(int h, int w, int* nh, int* nw) {
+    const int sh = h <= w ? h : w, lg = h <= w ? w : h;
+    const int nl = (int)((double)(VIT_IMG * (int64_t)lg) / (double)sh);
+    *nh = h <= w ? VIT_IMG : nl;
+    *nw = h <= w ? nl : VIT_IMG;
+}
+// [xmin, xmax) of output coordinate xx (Resample.c precompute_coeffs, BICUBIC: support 2); the device computes the same
+// two expressions in f64 (bicubic_taps_to)
+void clip_window(int in_size, int out_size, int xx, int* xmin, int* xmax) {
+    const double scale = (double)in_size / (double)out_size;
+    const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
+    const double center = (xx + 0.5) * scale;
+    int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
+    *xmin = lo < 0 ? 0 : lo;
+    *xmax = hi > in_size ? in_size : hi;
+}
+// Resample.c's ksize, the upper bound of a window's taps; 1 for an axis that is not filtered
+int clip_ksize(int in_size, int out_size) {
+    if (in_size == out_size) return 1;
+    const double scale = (double)in_size / (double)out_size;
+    return (int)std::ceil(2.0 * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
+}
+
+// Sizes against the 8000 x 8000 limit: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145, so gh <= 37 and kv <= 148 (the
+// vertical pass holds 160); a crop's tables take <= 3584 + 37 * 3584 + 224 * 148 * 4 = 268 800 bytes and its scratch
+// image <= 8000 * 672 = 5 376 000 bytes, both summed in size_t.  The widest class-2 band is 4 * 24000 bytes of LDS.
+void plan_clip_crop(K1Plan& p, int i, ClipCropDesc& d) {
+    clip_resized_size(d.h, d.w, &d.new_h, &d.new_w);
+    d.top = (d.new_h - VIT_IMG) / 2;
+    d.left = (d.new_w - VIT_IMG) / 2;
+    if (d.new_h != d.h) {
+        int a, b, y, z;
+        clip_window(d.h, d.new_h, d.top, &a, &b);
+        clip_window(d.h, d.new_h, d.top + VIT_IMG - 1, &y, &z);
+        d.r0 = a;
+        d.nr = (z > a ? z : a + 1) - a;
+    } else {
+        d.r0 = d.top;
+        d.nr = VIT_IMG;
+    }
+    d.gh = (clip_ksize(d.w, d.new_w) + 3) >> 2;
+    d.kv = (clip_ksize(d.h, d.new_h) + 3) & ~3;
+    if (d.kv > p.kv_max) p.kv_max = d.kv;
+    d.tab_off = (int64_t)p.tab_bytes;
+    p.tab_bytes += (size_t)clip_layout(d.gh, d.kv).bytes;
+    d.tmp_off = (int64_t)p.tmp_bytes;
+    p.tmp_bytes += (size_t)d.nr * (VIT_IMG * 3);
+    plan_bands(p, i, d.w * 3, clip_h_table_lds(d.gh), d.r0, d.nr);
+}
+
+int preprocess_chunk_clip(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches, hipStream_t s) {
+    c->h_clip_crops.resize(n);
+    K1Plan plan;
+    for (int i = 0; i < n; ++i) {
+        ClipCropDesc& d = c->h_clip_crops[i];
+        d.src_off = offs[i];
+        d.h = hw[2 * i];
+        d.w = hw[2 * i + 1];
+        plan_clip_crop(plan, i, d);
+    }
+    int r;
+    if ((r = ensure(c, c->crops, (size_t)n * sizeof(ClipCropDesc)))) return r;
+    HIP_TRY(c, hipMemcpyAsync(c->crops.p, c->h_clip_crops.data(), (size_t)n * sizeof(ClipCropDesc), hipMemcpyHostToDevice, s));
+    if ((r = run_h_pass(c, plan, pix, n, s, "mme_preprocess"))) return r;
+    Timed t(c, s, KC_PRE);
+    const ClipCropDesc* crops = (const ClipCropDesc*)c->crops.p;
+    HIP_TRY(c, launch_clip_tables(crops, n, (uint8_t*)c->htab.p, s));
+    const HWork* work = (const HWork*)c->hwork.p;
+    for (int k = 0; k < 3; ++k) {
+        hipError_t e = launch_clip_resize_h(pix, (uint8_t*)c->tmp.p, crops, work, plan.count[k], plan.lds[k], k, (const uint8_t*)c->htab.p, s);
+        if (e != hipSuccess)
+            return fail(c, MME_E_HIP, "mme_preprocess: BICUBIC horizontal pass, class %d (%s); %d bytes of LDS", k, hipGetErrorString(e), plan.lds[k]);
+        work += plan.count[k];
+    }
+    HIP_TRY(c, launch_clip_v_patchify((const uint8_t*)c->tmp.p, crops, n, c->lut, c->norm_aff, patches, (const uint8_t*)c->htab.p, plan.kv_max, s));
+    return MME_OK;
+}
+
 int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches, hipStream_t s) {
     c->h_crops.resize(n);
     c->h_work.clear();
@@ -445,12 +530,17 @@ int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const 
         const int h = hw[2 * i], w = hw[2 * i + 1];
         if (h <= 0 || w <= 0 || h > 8000 || w > 8000)
             return fail(c, MME_E_ARG, "crop %d has size %dx%d (h x w); supported 1..8000 (embedder.py:110-114 caps at 8000)", i, h, w);
+        if (h != VIT_IMG || w != VIT_IMG) any_resize = true;
+    }
+    // a batch of 224 x 224 crops is the identity under both rules: the lean instantiation below, today's bits and time
+    if (c->resize_rule == MME_RESIZE_CLIP && any_resize) return preprocess_chunk_clip(c, pix, offs, hw, n, patches, s);
+    for (int i = 0; i < n; ++i) {
+        const int h = hw[2 * i], w = hw[2 * i + 1];
         CropDesc& d = c->h_crops[i];
         d.src_off = offs[i];
         d.h = h;
         d.w = w;
         fit_to_canvas(h, w, &d.new_h, &d.new_w);
-        if (h != VIT_IMG || w != VIT_IMG) any_resize = true;
         plan_crop(c, plan, i, d);
     }
     int r;
@@ -551,6 +641,21 @@ int mme_set_normalisation(mme_ctx* c, const float mean[3], const float stdv[3]) 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());
     return set_lut(c, mean, stdv);
+}
+
+int mme_set_resize_rule(mme_ctx* c, int rule) {
+    if (!c) return MME_E_ARG;
+    if (rule != MME_RESIZE_FIT_PAD && rule != MME_RESIZE_CLIP)
+        return fail(c, MME_E_ARG, "mme_set_resize_rule: rule %d; supported %d (MME_RESIZE_FIT_PAD: fit into 224 x 224, BILINEAR, zero pad) and %d "
+                                  "(MME_RESIZE_CLIP: shortest edge 224, BICUBIC, centre crop)", rule, MME_RESIZE_FIT_PAD, MME_RESIZE_CLIP);
+    c->resize_rule = rule;
+    return MME_OK;
+}
+
+int mme_resize_rule(mme_ctx* c, int32_t* rule) {
+    if (!c || !rule) return fail(c, MME_E_ARG, "mme_resize_rule: null argument");
+    *rule = c->resize_rule;
+    return MME_OK;
 }
 
 int mme_normalisation_form(mme_ctx* c, int32_t* exact, float a[3], float b[3]) {

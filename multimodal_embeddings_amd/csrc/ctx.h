@@ -68,6 +68,7 @@ struct mme_ctx {
     bf16_t* proj_w = nullptr;  // [proj_dim, hidden]
     float* lut = nullptr;  // [3,256]
     NormAffine norm_aff{};  // the same mapping as one fma per value where that is bit-exact after the bf16 rounding (set_lut)
+    int resize_rule = MME_RESIZE_FIT_PAD;  // mme_set_resize_rule: how mme_preprocess / mme_embed make 224 x 224 pixels; no load changes it
     // workspace (sized for `chunk` crops)
     int ws_chunk = 0, ws_hidden = 0, ws_mlp = 0;  // what the workspace below was sized for
     DevBuf attn_guard;      // int[64]: one guard word per layer of a pass (attention.hip, FAST form)
@@ -79,6 +80,7 @@ struct mme_ctx {
     DevBuf pooled, projf;  // CLIP tail: bf16 [chunk, hidden] post_layernorm rows, f32 [chunk, proj_dim] projected rows
     // host staging for crop tables
     std::vector<CropDesc> h_crops;
+    std::vector<ClipCropDesc> h_clip_crops;
     std::vector<HWork> h_work;
     // profiling
     bool prof = false;

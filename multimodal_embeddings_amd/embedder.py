@@ -112,7 +112,8 @@ class RegionEmbedder:
 
     def __init__(self, model_name=config.DEFAULT_MODEL_NAME, device=None, gpu_count=None, *, weights=None,
                  seed: int = 1, pool: str = "cls", chunk: int | None = None, engine: Engine | None = None, devices=None,
-                 encoder: str = "vit_b16", geometry=None, prune_last_layer: bool | None = None, allow_synthetic: bool = True):
+                 encoder: str = "vit_b16", geometry=None, prune_last_layer: bool | None = None, allow_synthetic: bool = True,
+                 resize_rule: str | None = None):
         """`model_name`: a LOCAL checkpoint directory (config.json + model.safetensors | shards | pytorch_model.bin, optionally
         preprocessor_config.json) is read once (checkpoint.read_checkpoint), loaded into every context in the file's own dtype
         and its image_mean / image_std applied; `self.checkpoint` keeps it.  Any other name is never fetched: the encoder runs
@@ -123,10 +124,14 @@ class RegionEmbedder:
         the same family: pre-LN, QuickGELU or GELU, visual projection; a checkpoint directory of CLIPVisionModel[WithProjection]
         or a whole CLIPModel, seeded weights at `geometry=` a weights.CLIPGeometry, default CLIP-B/16, or a `weights=` dict in
         transformers' names, whose activation `geometry=` names when it is not QuickGELU) or "mllama_tiles".
-        `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim)."""
+        `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim).
+        `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
+        fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
+        encoders only; a checkpoint's preprocessor_config.json must then describe exactly that rule).  It is set on every
+        engine of this object; None leaves a caller's `engine=` as it is."""
         import torch
 
-        from .checkpoint import read_checkpoint, resolve_model_source
+        from .checkpoint import check_resize_rule, read_checkpoint, resolve_model_source
 
         self.torch = torch
         self.model_name = model_name
@@ -136,10 +141,11 @@ class RegionEmbedder:
                              "'clip' (a CLIP ViT/16 image tower of that family) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
         if encoder == "vit_b16" and geometry is not None:
             raise ValueError("encoder='vit_b16' is ViT-B/16 only; pass encoder='vit' with geometry=")
+        self.resize_rule = check_resize_rule(resize_rule, encoder)
         # a caller's engine carries its own weights
         source = "weights" if engine is not None else resolve_model_source(model_name, weights, allow_synthetic)
         if source == "checkpoint":
-            self.checkpoint = read_checkpoint(model_name, encoder)
+            self.checkpoint = read_checkpoint(model_name, encoder, resize_rule)
         if engine is not None:
             dev_list = [engine.device]
         elif devices is not None:  # explicit device indices (may repeat: several contexts on one GPU)
@@ -210,6 +216,11 @@ class RegionEmbedder:
                     e.load_vit(w, geom=VIT_B16)
                 self.engines.append(e)
         self.engine = self.engines[0]
+        if resize_rule is not None:
+            for e in self.engines:
+                e.set_resize_rule(self.resize_rule)
+        else:  # a caller's engine keeps its rule; this object reports it
+            self.resize_rule = self.engine.resize_rule
         if chunk:
             for e in self.engines:
                 e.set_chunk(chunk)

@@ -3,7 +3,12 @@
 region crops, cycled; pixels synthetic because the crops themselves cannot travel) through the
 on-GPU resize / normalise / patchify (K1) and the embedder.  Prints K1 time, algorithmic bytes,
 GB/s and whole-path crops/s, and checks a sample against the oracle bit-for-bit (patches).
+
+`--resize-rule fit_pad|clip` runs all of that under one rule of mme_set_resize_rule (default fit_pad).  `--resize-rule both`
+alternates K1 under the two rules in one process on the same crops -- two warm-ups each, then five timed runs of each,
+interleaved, one line per run -- and then times one mme_embed step of seeded CLIP-B/16 under each rule.
 """
+import argparse
 import os
 import sys
 import time
@@ -16,7 +21,51 @@ from multimodal_embeddings_amd._lib import Engine
 from multimodal_embeddings_amd.weights import make_vit_weights, round_to_bf16
 
 
+def k1_ms(eng, pix, offs, hw):
+    """kernel time of one mme_preprocess call (the context's event pairs)"""
+    eng.profile(True)
+    eng.preprocess(pix, offs, hw)
+    torch.cuda.synchronize()
+    return eng.profile_read()["preprocess"][0]
+
+
+def both_rules(pix, offs, hw, n):
+    from multimodal_embeddings_amd.weights import make_clip_weights
+
+    eng = Engine(0)
+    eng.load_clip(make_clip_weights(1))
+    rules = ("fit_pad", "clip")
+    for _ in range(2):
+        for rule in rules:
+            eng.set_resize_rule(rule)
+            k1_ms(eng, pix, offs, hw)
+    ms = {r: [] for r in rules}
+    for i in range(5):
+        for rule in rules:
+            eng.set_resize_rule(rule)
+            ms[rule].append(k1_ms(eng, pix, offs, hw))
+            print(f"C3 K1 run {i} rule {rule}: kernels {ms[rule][-1]:.3f} ms")
+    eng.profile(False)
+    for rule in rules:
+        v = ms[rule]
+        print(f"C3 K1 rule {rule}: min {min(v):.3f} median {sorted(v)[2]:.3f} max {max(v):.3f} ms over 5 runs")
+    print(f"C3 K1 ratio clip / fit_pad (medians): {sorted(ms['clip'])[2] / sorted(ms['fit_pad'])[2]:.2f}")
+    for rule in rules:
+        eng.set_resize_rule(rule)
+        for _ in range(2):
+            eng.embed(pix, offs, hw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.embed(pix, offs, hw)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"C3 embed CLIP-B/16 rule {rule}: {dt*1e3:.1f} ms for {n} crops ({n / dt:.0f} crops/s)")
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--resize-rule", choices=("fit_pad", "clip", "both"), default="fit_pad")
+    rule = ap.parse_args().resize_rule
     n = 4096
     sizes = np.load(os.path.join(os.path.dirname(__file__), "..", "tests", "golden", "bundled_crop_sizes_hw.npy"))
     hw = sizes[np.arange(n) % len(sizes)].astype(np.int32)
@@ -26,8 +75,11 @@ def main():
     total = int(offs[-1] + nbytes[-1]) + 16
     g = torch.Generator(device="cuda").manual_seed(0)
     pix = torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda", generator=g)
+    if rule == "both":
+        return both_rules(pix, offs, hw, n)
     eng = Engine(0)
     eng.load_vit(make_vit_weights(seed=1))
+    eng.set_resize_rule(rule)
     eng.profile(True)
     for _ in range(2):
         patches = eng.preprocess(pix, offs, hw)
@@ -62,7 +114,16 @@ def main():
     for i in (0, 1, 17, 500, 1861, 4095):
         h, w = hw[i]
         a = host[offs[i] : offs[i] + nbytes[i]].reshape(h, w, 3)
-        assert np.array_equal(got[i], round_to_bf16(opre.preprocess_to_patches(a))), i
+        if rule == "clip":
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+            from clip_preprocess_reference import clip_window_u8
+
+            lut = opre.normalise_lut()
+            win = clip_window_u8(a)
+            want = opre.patchify(np.stack([lut[ch][win[:, :, ch]] for ch in range(3)]))
+        else:
+            want = opre.preprocess_to_patches(a)
+        assert np.array_equal(got[i], round_to_bf16(want)), i
     print("C3 sample parity: bit-exact")
 
 
