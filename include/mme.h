@@ -147,6 +147,95 @@ int mme_load_clip_as(mme_ctx* ctx, const mme_clip_weights* w, int dtype, void* s
  * of the context's encoder: what the last load brought, {0, 768, 0, 0} before any. */
 int mme_encoder_info(mme_ctx* ctx, int32_t out[4]);
 
+/* ---- CLIP text tower ------------------------------------------------------------------------------------------------------
+ * Replaces `CLIPTextModelWithProjection.from_pretrained(dir)(input_ids).text_embeds` (or `CLIPTextModel`'s pooler_output
+ * when the checkpoint has no text_projection), L2-normalised: the text side of the space a CLIP image tower embeds into
+ * (transformers models/clip/modeling_clip.py, CLIPTextTransformer):
+ *   - CLIPTextEmbeddings: token_embedding[ids] + position_embedding (positions 0..76);
+ *   - CLIPEncoderLayer x layers, pre-LN, under the CAUSAL mask (key j reaches query i only when j <= i): layer_norm1,
+ *     q / k / v, softmax(Q K^T dh^-0.5 + mask) V, out_proj + residual, layer_norm2, fc1, QuickGELU (act 1) or erf-GELU (act 0),
+ *     fc2 + residual;
+ *   - final_layer_norm; the row at the EOS position of each sequence (below); text_projection, a bias-free Linear
+ *     [proj_dim, hidden] (proj_w, or NULL: the embedding is the LayerNormed row); x / max(||x||, 1e-12).
+ * Supported geometry: 77 positions, heads of 64, hidden 512, 768 or 1024 (heads == hidden / 64: 8, 12, 16), mlp a multiple
+ * of 64 up to 8192, 1..64 layers, vocab 3..65536, proj_dim 0 or a multiple of 64 up to 1024 (proj_w set exactly when it is
+ * not 0), act 0 or 1, 0 <= eos_token_id < vocab, any ln_eps.  Anything else is MME_E_ARG naming the field, the value found and
+ * the supported set, and nothing in the context changes.
+ * The tower COEXISTS with the context's image tower: a text load touches nothing of the image side, mme_load_vit* /
+ * mme_load_clip* afterwards touch nothing of the text side, a second text load frees exactly the first one's buffers.
+ * mme_load_clip_text takes host f32 tensors, mme_load_clip_text_as the checkpoint's own f32 / bf16 / f16 elements (cast the
+ * pointers), prepared on the device as mme_load_vit_as does; both run ONE prepare sequence and leave bit-identical buffers.
+ * The LayerNorms of the layers are always folded into the QKV and fc1 GEMMs; the attention scale times log2 e is folded into
+ * the query rows, as for the image towers.
+ * Prepared buffers (mme_weights_read order, behind whatever the context already held; D = hidden, F = mlp, V = vocab):
+ *   tok bf16 [V, D] (token_embedding, one rounding to nearest even), pos [77, D], lnf_g [D], lnf_b [D] (final_layer_norm);
+ *   then 10 per layer: qkv_wf bf16 [3D, D], qkv_cs [3D], qkv_bf [3D] (the fold of layer_norm1 into Q | K | V, the Q rows
+ *   times f32(dh^-0.5 log2 e)), o_w bf16 [D, D], o_b [D], fc1_wf bf16 [F, D], fc1_cs [F], fc1_bf [F] (the fold of
+ *   layer_norm2), fc2_w bf16 [D, F], fc2_b [D];
+ *   then, with a projection, proj_w bf16 [proj_dim, D]. */
+typedef struct {
+    int32_t hidden;         /* 512, 768 or 1024 */
+    int32_t layers;         /* 1..64 */
+    int32_t heads;          /* hidden / 64 */
+    int32_t mlp;            /* multiple of 64, <= 8192 */
+    int32_t vocab;          /* 3..65536 */
+    int32_t max_positions;  /* 77 */
+    int32_t proj_dim;       /* 0, or a multiple of 64 up to 1024 */
+    int32_t act;            /* 0 erf-GELU, 1 QuickGELU */
+    int32_t eos_token_id;   /* 2 selects the legacy rule of mme_text_forward */
+    float ln_eps;           /* 1e-5 */
+    const float* token_emb; /* [vocab, hidden] */
+    const float* pos_emb;   /* [77, hidden] */
+    const float* lnf_g;     /* final_layer_norm */
+    const float* lnf_b;
+    const float* proj_w;    /* text_projection.weight [proj_dim, hidden] or NULL */
+    const mme_vit_layer* layer; /* [layers]: layer_norm1, q/k/v/out_proj, layer_norm2, fc1, fc2 */
+} mme_clip_text_weights;
+int mme_load_clip_text(mme_ctx* ctx, const mme_clip_text_weights* w);
+int mme_load_clip_text_as(mme_ctx* ctx, const mme_clip_text_weights* w, int dtype, void* stream);
+/* out[9] = loaded (0 / 1), hidden, layers, heads, mlp, vocab, proj_dim (0: none), act, eos_token_id of the context's text
+ * tower; all 0 before a text load. */
+int mme_text_info(mme_ctx* ctx, int32_t out[9]);
+/* ids_host int32 [n, 77] (HOST) -> L2-normalised rows of text_embed_dim = proj_dim, or hidden when proj_dim is 0, to the
+ * DEVICE buffers emb_f32 [n, text_embed_dim] and / or emb_bf16 (either may be NULL).  Checked on the host before any launch
+ * (MME_E_ARG naming the sequence; nothing runs): every id in 0..vocab-1, and an EOS position in every sequence, found by
+ * transformers' rule -- eos_token_id == 2 (legacy configurations): the first position of the sequence's largest id; else the
+ * first position equal to eos_token_id, and a sequence without one is refused (transformers pools token 0 there).  Under the
+ * causal mask nothing behind the EOS position reaches its row: the padding's content does not matter.
+ * Works in chunks of MME_TEXT_CHUNK sequences in a workspace of its own (the image pass's buffers are not used); the rows
+ * behind each EOS are computed and ignored.  MME_E_STATE before a text load; n = 0 returns MME_OK.
+ * With mme_profile_enable on, the pass adds its launches to the image pass's kernel classes (token rows: preprocess; the statistics
+ * passes: layernorm; GEMMs: gemm; causal attention: attention; EOS pool-LN and L2: pool): reset the profile between an image step
+ * and a text call to read them apart. */
+#define MME_TEXT_CHUNK 1024
+#define MME_TEXT_TOKENS 77
+int mme_text_forward(mme_ctx* ctx, const int32_t* ids_host, int n, float* emb_f32, uint16_t* emb_bf16, void* stream);
+/* Diagnostic: ONE launch of a kernel the text tower adds, on the caller's DEVICE buffers (ids / eos_pos: HOST, validated and
+ * copied), synchronous; works on a bare context.
+ *   op 0 token rows        x[b*77 + t] = bf16(f32(tok[ids[b*77 + t]]) + pos[t]), b < n; tok bf16 [vocab, d], pos f32 [77, d]
+ *      1 causal attention  qkv bf16 [n*77, 3*64*heads] (Q | K | V, Q pre-scaled by dh^-0.5 log2 e) -> out bf16 [n*77, 64*heads]
+ *      2 EOS pool-LN       y[b] = bf16(LayerNorm(x[b*77 + eos_pos[b]]) * gamma + beta) to y bf16 [n, d] and / or the unrounded
+ *                          values to y_f32 [n, d]
+ * Preconditions (else MME_E_ARG, nothing launched): n >= 0; ops 0, 2: d == 512, 768 or 1024; op 1: heads == 8, 12 or 16; every
+ * pointer the op uses non-null and 16-byte aligned (ids / eos_pos: non-null); op 0: 1 <= vocab <= 65536 and every id in
+ * 0..vocab-1; op 2: every eos_pos in 0..76, y or y_f32. */
+typedef struct mme_text_apply_args {
+    const uint16_t* tok;     /* op 0 */
+    const float* pos;        /* op 0 */
+    const int32_t* ids_host; /* op 0: [n, 77] */
+    uint16_t* x;             /* op 0: out bf16 [n*77, d]; op 2: in */
+    const uint16_t* qkv;     /* op 1 */
+    uint16_t* out;           /* op 1 */
+    const float* gamma;      /* op 2 */
+    const float* beta;
+    const int32_t* eos_pos_host; /* op 2: [n] */
+    uint16_t* y;             /* op 2 */
+    float* y_f32;            /* op 2 */
+    int32_t n, d, heads, vocab;
+    float eps;
+} mme_text_apply_args;
+int mme_text_apply(mme_ctx* ctx, int op, const mme_text_apply_args* args, void* stream);
+
 /* Diagnostic (synchronises the device): one 64-bit word per prepared weight buffer of the context, in the order the
  * loaders created them (the ViT buffers of mme_load_vit[_as], then the tile-ViT buffers of mme_load_tile_vit[_as], when
  * loaded in that order).  The word is a position-dependent checksum of the buffer's bytes -- the sum over its 32-bit words

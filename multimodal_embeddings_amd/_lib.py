@@ -52,6 +52,16 @@ class _ClipWeights(C.Structure):  # mme_clip_weights
                 ("proj_dim", C.c_int32), ("act", C.c_int32)]
 
 
+class _ClipTextWeights(C.Structure):  # mme_clip_text_weights
+    _fields_ = [(n, C.c_int32) for n in ("hidden", "layers", "heads", "mlp", "vocab", "max_positions", "proj_dim", "act", "eos_token_id")] + [
+        ("ln_eps", C.c_float)] + [(n, C.POINTER(C.c_float)) for n in ("token_emb", "pos_emb", "lnf_g", "lnf_b", "proj_w")] + [("layer", C.POINTER(_Layer))]
+
+
+class _TextApplyArgs(C.Structure):  # mme_text_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("tok", "pos", "ids_host", "x", "qkv", "out", "gamma", "beta", "eos_pos_host", "y", "y_f32")] + [
+        ("n", C.c_int32), ("d", C.c_int32), ("heads", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float)]
+
+
 class _TileLayer(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_float)) for n in ("ln1_g", "ln1_b", "q_w", "k_w", "v_w", "o_w", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")] + [
         ("gate_attn", C.c_float), ("gate_ffn", C.c_float), ("gated", C.c_int32)]
@@ -120,6 +130,11 @@ EXPORTS = {
     "mme_load_clip_as": (C.c_int, [C.c_void_p, C.POINTER(_ClipWeights), C.c_int, C.c_void_p]),
     "mme_encoder_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_clip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_ClipApplyArgs), C.c_void_p]),
+    "mme_load_clip_text": (C.c_int, [C.c_void_p, C.POINTER(_ClipTextWeights)]),
+    "mme_load_clip_text_as": (C.c_int, [C.c_void_p, C.POINTER(_ClipTextWeights), C.c_int, C.c_void_p]),
+    "mme_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_text_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_text_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_TextApplyArgs), C.c_void_p]),
     "mme_weights_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "mme_weights_read": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "mme_weight_prep_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_WeightPrepApplyArgs), C.c_void_p]),
@@ -396,6 +411,124 @@ class Engine:
             raise MmeError(f"load_clip_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
         W, layers = self._clip_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
         self._check(self.lib.mme_load_clip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_clip_as")
+
+    # ---- CLIP text tower (mme_load_clip_text*): lives beside the image tower of the same context ----------------------------
+    @staticmethod
+    def _clip_text_struct(geom, arr):
+        """mme_clip_text_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.CLIPTextGeometry),
+        tensor pointers from arr(name) over the names of weights.clip_text_tensor_specs."""
+        from .weights import CLIP_ACTS
+
+        t = "text_model."
+        layers = (_Layer * geom.num_layers)()
+        for i in range(geom.num_layers):
+            p = f"{t}encoder.layers.{i}."
+            L = layers[i]
+            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
+            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
+            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
+            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
+            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
+            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
+            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
+            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+        if geom.hidden_act not in CLIP_ACTS:
+            raise MmeError(f"hidden_act = {geom.hidden_act!r}; supported: {', '.join(CLIP_ACTS)}")
+        W = _ClipTextWeights(geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size, geom.vocab_size,
+                             geom.max_position_embeddings, int(geom.projection_dim or 0), CLIP_ACTS.index(geom.hidden_act), int(geom.eos_token_id),
+                             float(geom.layer_norm_eps))
+        W.token_emb = arr(t + "embeddings.token_embedding.weight")
+        W.pos_emb = arr(t + "embeddings.position_embedding.weight")
+        W.lnf_g, W.lnf_b = arr(t + "final_layer_norm.weight"), arr(t + "final_layer_norm.bias")
+        W.proj_w = arr("text_projection.weight") if geom.projection_dim else None
+        W.layer = layers
+        return W, layers
+
+    def load_clip_text(self, w: dict, geom=None):
+        """`weights.clip_text_tensor_specs` dict of f32 arrays (the state dict of transformers' CLIPTextModelWithProjection, or
+        of CLIPTextModel: no text_projection) -> the text tower of this context, replacing an earlier text tower and nothing
+        else.  `geom`: a weights.CLIPTextGeometry; by default read off the tensor shapes (weights.infer_clip_text_geometry)."""
+        from .weights import clip_text_tensor_specs, infer_clip_text_geometry
+
+        if geom is None:
+            geom = infer_clip_text_geometry(w)
+        for name, shape, _ in clip_text_tensor_specs(geom):
+            if name not in w:
+                raise MmeError(f"load_clip_text: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"load_clip_text: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32)
+            keep.append(a)
+            return _fp(a)
+
+        W, layers = self._clip_text_struct(geom, arr)
+        self._check(self.lib.mme_load_clip_text(self.h, C.byref(W)), "mme_load_clip_text")
+
+    def load_clip_text_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "clip_text")` -> the text tower of this context, prepared on the device from the
+        file's own f32 / bf16 / f16 bytes, bit-identically to `load_clip_text` on the same values."""
+        if ckpt.encoder != "clip_text":
+            raise MmeError(f"load_clip_text_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        W, layers = self._clip_text_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
+        self._check(self.lib.mme_load_clip_text_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_clip_text_as")
+
+    def text_info(self) -> dict:
+        """The text tower of this context (mme_text_info); every number 0 and hidden_act None before a text load."""
+        from .weights import CLIP_ACTS
+
+        o = (C.c_int32 * 9)()
+        self._check(self.lib.mme_text_info(self.h, o), "mme_text_info")
+        return {"loaded": int(o[0]), "hidden_size": int(o[1]), "num_layers": int(o[2]), "num_heads": int(o[3]), "intermediate_size": int(o[4]),
+                "vocab_size": int(o[5]), "projection_dim": int(o[6]) or None, "hidden_act": CLIP_ACTS[o[7]] if o[0] else None,
+                "eos_token_id": int(o[8])}
+
+    @property
+    def text_embed_dim(self) -> int:
+        """Width of the rows `text_forward` returns: the text tower's projection_dim, or its hidden size; 0 before a text load."""
+        i = self.text_info()
+        return int(i["projection_dim"] or i["hidden_size"])
+
+    def text_forward(self, ids, want_f32: bool = True, want_bf16: bool = True):
+        """int token ids [n, 77] (host) -> (f32 [n, text_embed_dim] | None, bf16 | None) CUDA tensors of unit rows
+        (mme_text_forward).  The library checks every id and finds each sequence's EOS position; n = 0 gives empty tensors."""
+        t = self.torch
+        a = np.asarray(ids)
+        if a.ndim != 2 or a.shape[1] != 77 or a.dtype.kind not in "iu":
+            raise MmeError(f"text_forward: ids must be an integer array [n, 77], got {a.dtype} {tuple(a.shape)}")
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise MmeError("text_forward: an id does not fit 32 bits")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        n, d = a.shape[0], self.text_embed_dim
+        dev = t.device("cuda", self.device)
+        e32 = t.empty((n, d), dtype=t.float32, device=dev) if want_f32 else None
+        e16 = t.empty((n, d), dtype=t.bfloat16, device=dev) if want_bf16 else None
+        self._check(self.lib.mme_text_forward(self.h, a.ctypes.data, n, e32.data_ptr() if want_f32 and n else None,
+                                              e16.data_ptr() if want_bf16 and n else None, self._stream()), "mme_text_forward")
+        return e32, e16
+
+    TEXT_OPS = {"token_rows": 0, "attention_causal": 1, "eos_pool_ln": 2}
+
+    def text_apply(self, op, *, tok=None, pos=None, ids=None, x=None, qkv=None, out=None, gamma=None, beta=None, eos_pos=None, y=None, y_f32=None,
+                   n: int = 0, d: int = 512, heads: int = 8, vocab: int = 0, eps: float = 1e-5):
+        """ONE launch of a kernel the text tower adds, on the caller's CUDA tensors (mme_text_apply; synchronous).  op: a name of
+        TEXT_OPS or its code; `ids` [n, 77] and `eos_pos` [n] are host integer arrays.  The library validates."""
+        a = _TextApplyArgs()
+        keep = []
+
+        def host(v):
+            if v is None:
+                return None
+            h = np.ascontiguousarray(np.asarray(v), dtype=np.int32)
+            keep.append(h)
+            return h.ctypes.data
+
+        a.tok, a.pos, a.x, a.qkv, a.out, a.gamma, a.beta, a.y, a.y_f32 = (self._ptr(t) for t in (tok, pos, x, qkv, out, gamma, beta, y, y_f32))
+        a.ids_host, a.eos_pos_host = host(ids), host(eos_pos)
+        a.n, a.d, a.heads, a.vocab, a.eps = int(n), int(d), int(heads), int(vocab), float(eps)
+        self._check(self.lib.mme_text_apply(self.h, int(self.TEXT_OPS.get(op, op)), C.byref(a), self._stream()), "mme_text_apply")
 
     @staticmethod
     def _tile_struct(geom, arr, gate):

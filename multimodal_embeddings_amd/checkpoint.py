@@ -8,12 +8,13 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
 
 -- checks that its configuration is a geometry the library is built for ("vit_b16": exactly ViT-B/16; "vit": any of the
 supported ViT/16 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "clip": a CLIP image tower of that family,
-`CLIPVisionModel[WithProjection]` or the vision half of a whole `CLIPModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
+`CLIPVisionModel[WithProjection]` or the vision half of a whole `CLIPModel`; "clip_text": a CLIP text tower,
+`CLIPTextModel[WithProjection]` or the text half of a whole `CLIPModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
 bytes to the device, where they are converted and folded (csrc/weight_load.hip: DevPrep; kernels in csrc/weight_prep.hip).
 
-    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles]
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text]
 
 prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
 """
@@ -28,12 +29,13 @@ from dataclasses import dataclass, field
 
 from . import config
 from ._lib import MmeError
-from .weights import (CLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, TileViTGeometry, ViTGeometry, clip_geometry_problem, clip_tensor_specs,
-                      tile_vit_tensor_specs, vit_geometry_problem, vit_tensor_specs)
+from .weights import (CLIP_B16, CLIP_TEXT_B, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, TileViTGeometry, ViTGeometry, clip_geometry_problem,
+                      clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem,
+                      vit_tensor_specs)
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles")
+ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text")
 VIT_ENCODERS = ("vit_b16", "vit")  # one loader, one tensor layout; "vit" takes its geometry from config.json
 SUPPORTED_ASPECT_RATIOS = [[1, 1], [1, 2], [1, 3], [1, 4], [2, 1], [2, 2], [3, 1], [4, 1]]
 _DTYPE_IDS = {"float32": 0, "bfloat16": 1, "float16": 2}  # include/mme.h MME_DT_*
@@ -113,6 +115,17 @@ def canonical_clip_name(key: str):
     return key
 
 
+def canonical_clip_text_name(key: str):
+    """Checkpoint key -> canonical name (`weights.clip_text_tensor_specs`: the keys of `CLIPTextModelWithProjection`), or None
+    for what the text tower does not use: the image tower, visual_projection, logit_scale, the position_ids buffers."""
+    if key.startswith(("vision_model.", "visual_projection.")) or key == "logit_scale" or key.endswith(".position_ids"):
+        return None
+    # CLIPTextModel.save_pretrained of transformers 5 writes the tower's own keys, without the "text_model." prefix
+    if key.startswith(("embeddings.", "encoder.layers.", "final_layer_norm.")):
+        return "text_model." + key
+    return key
+
+
 def canonical_tile_name(key: str):
     """Checkpoint key -> canonical name, or None for a key outside the vision tower."""
     for prefix in ("model.vision_model.", "vision_model."):
@@ -181,6 +194,28 @@ def _clip_geometry(cfg: dict, where: str, projection_dim) -> CLIPGeometry:
                      intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)),
                      projection_dim=projection_dim, hidden_act=cfg.get("hidden_act", b.hidden_act))
     bad = clip_geometry_problem(g)
+    if bad:
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    return g
+
+
+def _clip_text_geometry(cfg: dict, where: str, projection_dim) -> CLIPTextGeometry:
+    """The text configuration of a CLIP checkpoint (CLIPTextConfig) -> geometry.  A field the file leaves out has
+    CLIPTextConfig's default (clip-vit-base-patch16's text tower), as transformers reads it."""
+    b = CLIP_TEXT_B
+    fields = {"hidden_size": b.hidden_size, "num_hidden_layers": b.num_layers, "num_attention_heads": b.num_heads, "intermediate_size": b.intermediate_size,
+              "vocab_size": b.vocab_size, "max_position_embeddings": b.max_position_embeddings, "eos_token_id": b.eos_token_id}
+    for fld, default in fields.items():
+        v = cfg.get(fld, default)
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise MmeError(f"{where}: {fld} = {v!r}; an integer is required")
+        fields[fld] = v
+    g = CLIPTextGeometry(hidden_size=fields["hidden_size"], num_layers=fields["num_hidden_layers"], num_heads=fields["num_attention_heads"],
+                         intermediate_size=fields["intermediate_size"], vocab_size=fields["vocab_size"],
+                         max_position_embeddings=fields["max_position_embeddings"], eos_token_id=fields["eos_token_id"], projection_dim=projection_dim,
+                         hidden_act=cfg.get("hidden_act", b.hidden_act), layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
+    bad = clip_text_geometry_problem(g)
     if bad:
         names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
         raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
@@ -387,6 +422,14 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         geometry = _clip_geometry(vcfg, where, vcfg.get("projection_dim"))
         canonical = canonical_clip_name
         specs = None  # after the tensors are read: a CLIPVisionModel checkpoint has no visual_projection
+    elif encoder == "clip_text":
+        where, tcfg = "config.json", cfg
+        if "text_config" in cfg:  # a whole CLIP model: projection_dim sits at the top level
+            tcfg, where = dict(cfg["text_config"]), "config.json: text_config"
+            tcfg["projection_dim"] = cfg.get("projection_dim", CLIP_TEXT_B.projection_dim)  # CLIPConfig's own field and default
+        geometry = _clip_text_geometry(tcfg, where, tcfg.get("projection_dim"))
+        canonical = canonical_clip_text_name
+        specs = None  # after the tensors are read: a CLIPTextModel checkpoint has no text_projection
     else:
         where = "config.json"
         if "vision_config" in cfg:  # a whole Mllama model
@@ -402,6 +445,14 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         elif geometry.projection_dim is None:
             raise MmeError(f"{path}: the checkpoint holds {keys['visual_projection.weight']!r} but {where} names no projection_dim")
         specs = [(n, s) for n, s, _ in clip_tensor_specs(geometry)]
+    elif encoder == "clip_text":
+        wanted = {n for n, _, _ in clip_text_tensor_specs(dataclasses.replace(geometry, projection_dim=geometry.projection_dim or 64))}
+        tensors, keys, files = _read_tensors(path, canonical, wanted)
+        if "text_projection.weight" not in tensors:  # CLIPTextModel: the embedding is the final_layer_norm row at the EOS position
+            geometry = dataclasses.replace(geometry, projection_dim=None)
+        elif geometry.projection_dim is None:
+            raise MmeError(f"{path}: the checkpoint holds {keys['text_projection.weight']!r} but {where} names no projection_dim")
+        specs = [(n, s) for n, s, _ in clip_text_tensor_specs(geometry)]
     else:
         tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs})
     source += files
@@ -413,7 +464,7 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
     tensors, dtype = _unify_dtype({n: tensors[n] for n, _ in specs}, keys)
     mean = std = None
     pre_path = os.path.join(path, "preprocessor_config.json")
-    if os.path.exists(pre_path):
+    if os.path.exists(pre_path) and encoder != "clip_text":  # a text tower reads no pixels
         mean, std = _read_preprocessor(pre_path, encoder, resize_rule)
         source.append(pre_path)
     return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source)
@@ -442,6 +493,14 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
                "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size,
                "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
                "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "dtype": dtype}
+        if g.projection_dim:
+            cfg["projection_dim"] = g.projection_dim
+    elif encoder == "clip_text":
+        g = geometry or CLIP_TEXT_B
+        cfg = {"architectures": ["CLIPTextModelWithProjection" if g.projection_dim else "CLIPTextModel"], "model_type": "clip_text_model",
+               "vocab_size": g.vocab_size, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
+               "intermediate_size": g.intermediate_size, "max_position_embeddings": g.max_position_embeddings, "hidden_act": g.hidden_act,
+               "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "eos_token_id": g.eos_token_id, "dtype": dtype}
         if g.projection_dim:
             cfg["projection_dim"] = g.projection_dim
     elif encoder == "mllama_tiles":

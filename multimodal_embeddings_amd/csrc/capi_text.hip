@@ -1,0 +1,365 @@
+// C ABI of the CLIP text tower (include/mme.h, "CLIP text tower"): transformers' CLIPTextTransformer + text_projection on
+// the GEMM, LayerNorm-folding and statistics machinery of the image path, with its own row kernels (text_tower.hip) and
+// its own causal attention kernel (attention_causal.hip).  The tower lives beside the context's image tower: its record
+// and its workspace are here, its prepared buffers in c->allocs[text_alloc_lo, text_alloc_hi).
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "ctx.h"
+
+struct TextLayerDev {
+    bf16_t *qkv_wf, *o_w, *fc1_wf, *fc2_w;
+    float *qkv_cs, *qkv_bf, *o_b, *fc1_cs, *fc1_bf, *fc2_b;
+};
+
+struct TextDev {
+    bool loaded = false;
+    int hidden = 0, layers = 0, heads = 0, mlp = 0, vocab = 0, proj_dim = 0, act = 0, eos = 0;
+    float eps = 1e-5f;
+    bf16_t* tok = nullptr;
+    float *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
+    bf16_t* proj_w = nullptr;
+    std::vector<TextLayerDev> layer;
+    // workspace of the pass (grown to the largest chunk seen, never shrunk), and the diagnostic's staging of ids / positions
+    DevBuf x, qkv, att, hmlp, stats, pooled, projf, ids, eos_pos, apply_ints;
+};
+
+void text_free(mme_ctx* c) {
+    if (!c->text) return;
+    TextDev* t = c->text;
+    DevBuf* bufs[] = {&t->x, &t->qkv, &t->att, &t->hmlp, &t->stats, &t->pooled, &t->projf, &t->ids, &t->eos_pos, &t->apply_ints};
+    for (DevBuf* b : bufs)
+        if (b->p) (void)hipFree(b->p);
+    delete t;
+    c->text = nullptr;
+}
+
+namespace {
+
+int text_dev(mme_ctx* c, const char* who) {
+    if (c->text) return MME_OK;
+    c->text = new (std::nothrow) TextDev();
+    if (!c->text) return fail(c, MME_E_NOMEM, "%s: out of host memory", who);
+    return MME_OK;
+}
+
+int text_embed_dim(const TextDev* t) { return t->proj_dim ? t->proj_dim : t->hidden; }
+
+// every refusal names the field, the value found and what is supported; touches nothing in the context but its error text
+int validate_text_weights(mme_ctx* c, const mme_clip_text_weights* w) {
+    const char* who = "mme_load_clip_text";
+    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
+    if (!text_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 512, 768, 1024", who, w->hidden);
+    if (w->heads * VIT_DH != w->hidden)
+        return fail(c, MME_E_ARG, "%s: heads = %d at hidden = %d; supported: heads of %d, heads = hidden / %d = %d", who, w->heads, w->hidden, VIT_DH, VIT_DH,
+                    w->hidden / VIT_DH);
+    if (w->max_positions != TXT_T) return fail(c, MME_E_ARG, "%s: max_positions = %d; supported: %d", who, w->max_positions, TXT_T);
+    if (w->mlp < 64 || (w->mlp % 64) != 0 || w->mlp > VIT_MAX_F)
+        return fail(c, MME_E_ARG, "%s: mlp = %d; supported: multiples of 64 up to %d", who, w->mlp, VIT_MAX_F);
+    if (w->layers < 1 || w->layers > VIT_MAX_L) return fail(c, MME_E_ARG, "%s: layers = %d; supported: 1..%d", who, w->layers, VIT_MAX_L);
+    if (w->vocab < 3 || w->vocab > TXT_MAX_VOCAB) return fail(c, MME_E_ARG, "%s: vocab = %d; supported: 3..%d", who, w->vocab, TXT_MAX_VOCAB);
+    if (w->act != 0 && w->act != 1) return fail(c, MME_E_ARG, "%s: act = %d; supported: 0 (erf-GELU), 1 (QuickGELU)", who, w->act);
+    if (w->proj_dim != 0 && (w->proj_dim < 64 || (w->proj_dim % 64) != 0 || w->proj_dim > 1024))
+        return fail(c, MME_E_ARG, "%s: proj_dim = %d; supported: 0 (no projection) or a multiple of 64 up to 1024", who, w->proj_dim);
+    if (w->eos_token_id < 0 || w->eos_token_id >= w->vocab)
+        return fail(c, MME_E_ARG, "%s: eos_token_id = %d; supported: 0..vocab-1 = 0..%d", who, w->eos_token_id, w->vocab - 1);
+    if ((w->proj_dim != 0) != (w->proj_w != nullptr))
+        return fail(c, MME_E_ARG, "%s: proj_dim = %d with proj_w %s; supported: both set, or proj_dim = 0 with proj_w NULL", who, w->proj_dim,
+                    w->proj_w ? "set" : "NULL");
+    if (!w->token_emb || !w->pos_emb || !w->lnf_g || !w->lnf_b || !w->layer) return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
+    for (int l = 0; l < w->layers; ++l) {
+        const mme_vit_layer& a = w->layer[l];
+        const float* all[] = {a.ln1_g, a.ln1_b, a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+        for (const float* p : all)
+            if (!p) return fail(c, MME_E_ARG, "%s: layer %d has a null tensor pointer", who, l);
+    }
+    return MME_OK;
+}
+
+// every tensor of the checkpoint with its element count (the order of the staged bytes)
+template <class Fn>
+void each_text_tensor(mme_clip_text_weights& w, std::vector<mme_vit_layer>& layer, Fn&& f) {
+    const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
+    f(w.token_emb, (size_t)w.vocab * D);
+    f(w.pos_emb, (size_t)TXT_T * D);
+    f(w.lnf_g, D);
+    f(w.lnf_b, D);
+    for (mme_vit_layer& a : layer) {
+        f(a.ln1_g, D); f(a.ln1_b, D);
+        f(a.q_w, D * D); f(a.q_b, D);
+        f(a.k_w, D * D); f(a.k_b, D);
+        f(a.v_w, D * D); f(a.v_b, D);
+        f(a.o_w, D * D); f(a.o_b, D);
+        f(a.ln2_g, D); f(a.ln2_b, D);
+        f(a.fc1_w, F * D); f(a.fc1_b, F);
+        f(a.fc2_w, D * F); f(a.fc2_b, D);
+    }
+    if (w.proj_w) f(w.proj_w, (size_t)w.proj_dim * D);
+}
+
+// The prepared buffers of the text tower, in the order mme_weights_fingerprint reports them: tok, pos, lnf_g, lnf_b, then
+// 10 per layer, then proj_w (include/mme.h).  Only the folded forms exist: there is no LayerNorm-kernel mode for text.
+template <class P>
+int prepare_text(mme_ctx* c, P& p, const mme_clip_text_weights& w) {
+    TextDev* t = c->text;
+    int r;
+    const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
+    const size_t rD[3] = {D, D, D}, rF[1] = {F}, rV[1] = {(size_t)w.vocab};
+    auto plain = [&](const float* src, size_t n, float** dst) { return p.table(src, n, 1.f, false, dst); };
+    auto plain_bf16 = [&](const float* src, const size_t* rows, size_t cols, bf16_t** dst) {
+        const void* s[1] = {src};
+        return p.bf16(s, rows, 1, cols, 1.f, false, dst);
+    };
+    if ((r = plain_bf16(w.token_emb, rV, D, &t->tok))) return r;
+    if ((r = plain(w.pos_emb, (size_t)TXT_T * D, &t->pos))) return r;
+    if ((r = plain(w.lnf_g, D, &t->lnf_g))) return r;
+    if ((r = plain(w.lnf_b, D, &t->lnf_b))) return r;
+    const float sc = 0.125f * 1.44269504088896341f;  // dh^-0.5 * log2(e), folded into the query rows (weight_load.hip, prepare_vit)
+    for (int l = 0; l < w.layers; ++l) {
+        const mme_vit_layer& a = w.layer[l];
+        TextLayerDev& L = t->layer[l];
+        const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
+        if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
+        if ((r = plain_bf16(a.o_w, rD, D, &L.o_w))) return r;
+        if ((r = plain(a.o_b, D, &L.o_b))) return r;
+        const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
+        if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf))) return r;
+        if ((r = plain_bf16(a.fc2_w, rD, F, &L.fc2_w))) return r;
+        if ((r = plain(a.fc2_b, D, &L.fc2_b))) return r;
+    }
+    if (w.proj_w) {
+        const size_t rP[1] = {(size_t)w.proj_dim};
+        if ((r = plain_bf16(w.proj_w, rP, D, &t->proj_w))) return r;
+    }
+    return MME_OK;
+}
+
+// A text load replaces the context's text tower and nothing else: it frees exactly the previous text buffers (after the
+// device has drained), leaves the tower unloaded while it prepares, and marks what it allocated as the new range.
+template <class P>
+int load_text(mme_ctx* c, const mme_clip_text_weights* w, P p, const char* who) {
+    int r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((r = text_dev(c, who))) return r;
+    TextDev* t = c->text;
+    t->loaded = false;
+    if (c->text_alloc_hi > c->text_alloc_lo) HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
+    release_alloc_range(c, c->text_alloc_lo, c->text_alloc_hi, c->vit_alloc_lo, c->vit_alloc_hi);
+    t->hidden = w->hidden; t->layers = w->layers; t->heads = w->heads; t->mlp = w->mlp; t->vocab = w->vocab;
+    t->proj_dim = w->proj_dim; t->act = w->act; t->eos = w->eos_token_id; t->eps = w->ln_eps;
+    t->tok = nullptr; t->pos = t->lnf_g = t->lnf_b = nullptr; t->proj_w = nullptr;
+    t->layer.assign((size_t)w->layers, TextLayerDev{});
+    std::vector<mme_vit_layer> layer(w->layer, w->layer + w->layers);
+    mme_clip_text_weights v = *w;
+    v.layer = layer.data();
+    r = p.stage([&](auto& put) { each_text_tensor(v, layer, put); });
+    if (r == MME_OK) r = prepare_text(c, p, v);
+    r = p.finish(r);
+    c->text_alloc_hi = c->allocs.size();
+    t->loaded = r == MME_OK;
+    return r;
+}
+
+// host side of the pass's input: every id inside the table, and the EOS position of every sequence by transformers' rule
+// (CLIPTextTransformer.forward): eos_token_id == 2 -> argmax of the ids (first of equals), else the first position that
+// holds eos_token_id.  transformers pools position 0 when there is none (argmax of an all-zero mask); here that is an error.
+int scan_ids(mme_ctx* c, const char* who, const int32_t* ids, int n, int vocab, int eos, std::vector<int32_t>& pos) {
+    pos.resize((size_t)n);
+    for (int b = 0; b < n; ++b) {
+        const int32_t* row = ids + (size_t)b * TXT_T;
+        int best = 0, found = -1;
+        for (int t = 0; t < TXT_T; ++t) {
+            if (row[t] < 0 || row[t] >= vocab)
+                return fail(c, MME_E_ARG, "%s: sequence %d, position %d: id = %d; supported: 0..vocab-1 = 0..%d", who, b, t, row[t], vocab - 1);
+            if (row[t] > row[best]) best = t;
+            if (found < 0 && row[t] == eos) found = t;
+        }
+        if (eos == 2) found = best;
+        if (found < 0) return fail(c, MME_E_ARG, "%s: sequence %d holds no eos_token_id = %d: there is no row to pool", who, b, eos);
+        pos[(size_t)b] = found;
+    }
+    return MME_OK;
+}
+
+int text_chunk(mme_ctx* c, TextDev* t, const int32_t* ids_dev, const int32_t* eos_dev, int n, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
+    const int M = n * TXT_T, D = t->hidden, F = t->mlp, NL = t->layers;
+    GemmArgs g{};
+    auto stats = [&]() -> int {
+        Timed tm(c, s, KC_LN);
+        HIP_TRY(c, launch_ln_stats_canonical(t->x.p, 0, M, D, t->eps, (float*)t->stats.p, s));
+        return MME_OK;
+    };
+    int r;
+    {
+        Timed tm(c, s, KC_PRE);
+        HIP_TRY(c, launch_text_token_rows(t->tok, t->pos, ids_dev, t->x.p, n, D, s));
+    }
+    if ((r = stats())) return r;
+    const int ln_act_epi = t->act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU;
+    for (int l = 0; l < NL; ++l) {
+        const TextLayerDev& L = t->layer[l];
+        {
+            Timed tm(c, s, KC_GEMM);  // layer_norm1 folded into Q | K | V
+            g = GemmArgs{};
+            g.A = t->x.p; g.W = L.qkv_wf; g.M = M; g.N = 3 * D; g.K = D;
+            g.bias = L.qkv_bf; g.colsum = L.qkv_cs; g.ln_stats = (const float*)t->stats.p; g.out = t->qkv.p; g.ldo = 3 * D;
+            HIP_TRY(c, launch_gemm(EPI_LN_BIAS, g, s, c->gemm_variant));
+        }
+        {
+            Timed tm(c, s, KC_ATTN);
+            HIP_TRY(c, launch_attention_causal(t->qkv.p, t->att.p, n, t->heads, s));
+        }
+        {
+            Timed tm(c, s, KC_GEMM);
+            g = GemmArgs{};
+            g.A = t->att.p; g.W = L.o_w; g.M = M; g.N = D; g.K = D;
+            g.bias = L.o_b; g.out = t->x.p; g.res = t->x.p; g.ldo = D;
+            HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
+        }
+        if ((r = stats())) return r;
+        {
+            Timed tm(c, s, KC_GEMM);  // layer_norm2 folded into fc1, then the activation
+            g = GemmArgs{};
+            g.A = t->x.p; g.W = L.fc1_wf; g.M = M; g.N = F; g.K = D;
+            g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)t->stats.p; g.out = t->hmlp.p; g.ldo = F;
+            HIP_TRY(c, launch_gemm(ln_act_epi, g, s, c->gemm_variant));
+            g = GemmArgs{};
+            g.A = t->hmlp.p; g.W = L.fc2_w; g.M = M; g.N = D; g.K = F;
+            g.bias = L.fc2_b; g.out = t->x.p; g.res = t->x.p; g.ldo = D;
+            HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
+        }
+        if (l + 1 < NL && (r = stats())) return r;  // final_layer_norm touches the EOS rows only
+    }
+    const int P = t->proj_dim;
+    {
+        Timed tm(c, s, KC_POOL);
+        HIP_TRY(c, launch_text_eos_pool_ln(t->x.p, t->lnf_g, t->lnf_b, eos_dev, n, D, t->eps, P ? t->pooled.p : nullptr, P ? nullptr : (float*)t->projf.p, s));
+    }
+    if (P) {
+        Timed tm(c, s, KC_GEMM);
+        g = GemmArgs{};
+        g.A = t->pooled.p; g.W = t->proj_w; g.M = n; g.N = P; g.K = D;
+        g.outf = (float*)t->projf.p; g.ldf = P;
+        HIP_TRY(c, launch_gemm(EPI_F32, g, s, c->gemm_variant));
+    }
+    Timed tm(c, s, KC_POOL);
+    HIP_TRY(c, launch_l2_rows((const float*)t->projf.p, n, P ? P : D, emb_f32, emb_bf16, s));
+    return MME_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int mme_load_clip_text(mme_ctx* c, const mme_clip_text_weights* w) {
+    int r;
+    if ((r = validate_text_weights(c, w))) return r;
+    return load_text(c, w, HostPrep{c}, "mme_load_clip_text");
+}
+
+int mme_load_clip_text_as(mme_ctx* c, const mme_clip_text_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_text_weights(c, w))) return r;
+    if ((r = check_load_dtype(c, dtype, "mme_load_clip_text_as"))) return r;
+    return load_text(c, w, DevPrep(c, dtype, stream, "mme_load_clip_text_as"), "mme_load_clip_text_as");
+}
+
+int mme_text_info(mme_ctx* c, int32_t out[9]) {
+    if (!c || !out) return fail(c, MME_E_ARG, "mme_text_info: null argument");
+    for (int i = 0; i < 9; ++i) out[i] = 0;
+    const TextDev* t = c->text;
+    if (!t || !t->loaded) return MME_OK;
+    const int32_t v[9] = {1, t->hidden, t->layers, t->heads, t->mlp, t->vocab, t->proj_dim, t->act, t->eos};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return MME_OK;
+}
+
+int mme_text_forward(mme_ctx* c, const int32_t* ids_host, int n, float* emb_f32, uint16_t* emb_bf16, void* stream) {
+    if (!c) return MME_E_ARG;
+    TextDev* t = c->text;
+    if (!t || !t->loaded) return fail(c, MME_E_STATE, "mme_text_forward: call mme_load_clip_text first");
+    if (n < 0 || (n > 0 && !ids_host)) return fail(c, MME_E_ARG, "mme_text_forward: null ids or n<0");
+    if (n == 0) return MME_OK;
+    std::vector<int32_t> eos_pos;
+    int r;
+    if ((r = scan_ids(c, "mme_text_forward", ids_host, n, t->vocab, t->eos, eos_pos))) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int chunk = n < MME_TEXT_CHUNK ? n : MME_TEXT_CHUNK;
+    const size_t rows = (size_t)chunk * TXT_T, D = (size_t)t->hidden, F = (size_t)t->mlp, E = (size_t)text_embed_dim(t);
+    if ((r = ensure(c, t->x, rows * D * 2))) return r;
+    if ((r = ensure(c, t->qkv, rows * 3 * D * 2))) return r;
+    if ((r = ensure(c, t->att, rows * D * 2))) return r;
+    if ((r = ensure(c, t->hmlp, rows * F * 2))) return r;
+    if ((r = ensure(c, t->stats, rows * 2 * sizeof(float)))) return r;
+    if ((r = ensure(c, t->pooled, (size_t)chunk * D * 2))) return r;
+    if ((r = ensure(c, t->projf, (size_t)chunk * (E > D ? E : D) * sizeof(float)))) return r;
+    if ((r = ensure(c, t->ids, (size_t)n * TXT_T * sizeof(int32_t)))) return r;
+    if ((r = ensure(c, t->eos_pos, (size_t)n * sizeof(int32_t)))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(c, hipMemcpyAsync(t->ids.p, ids_host, (size_t)n * TXT_T * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(t->eos_pos.p, eos_pos.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // eos_pos is a local; the caller's ids may be released on return
+    for (int s0 = 0; s0 < n; s0 += MME_TEXT_CHUNK) {
+        const int m = n - s0 < MME_TEXT_CHUNK ? n - s0 : MME_TEXT_CHUNK;
+        r = text_chunk(c, t, (const int32_t*)t->ids.p + (size_t)s0 * TXT_T, (const int32_t*)t->eos_pos.p + s0, m,
+                       emb_f32 ? emb_f32 + (size_t)s0 * E : nullptr, emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * E : nullptr, s);
+        if (r) return r;
+    }
+    return MME_OK;
+}
+
+// the kernels the text tower adds, one launch each (tests/test_gpu_clip_text.py)
+int mme_text_apply(mme_ctx* c, int op, const mme_text_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_text_apply: null argument");
+    if (op < 0 || op > 2) return fail(c, MME_E_ARG, "mme_text_apply: op %d outside 0..2", op);
+    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "mme_text_apply: n = %d outside 0..2^20", a->n);
+    auto vec = [](const void* p) { return p && aligned16(p); };
+    const char* bad = nullptr;
+    if (op != 1 && !text_width_built(a->d)) return fail(c, MME_E_ARG, "mme_text_apply: op %d is built for d == 512, d == 768 and d == 1024 (d = %d)", op, a->d);
+    if (op == 0) {
+        if (!vec(a->tok) || !vec(a->pos) || !vec(a->x) || !a->ids_host) bad = "tok, pos, x non-null and 16-byte aligned, ids_host non-null";
+        else if (a->vocab < 1 || a->vocab > TXT_MAX_VOCAB) bad = "1 <= vocab <= 65536";
+    } else if (op == 1) {
+        if (a->heads != 8 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_text_apply: op 1 is built for heads == 8, 12 and 16 (heads = %d)", a->heads);
+        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv, out non-null and 16-byte aligned";
+    } else {
+        if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta) || !a->eos_pos_host) bad = "x, gamma, beta non-null and 16-byte aligned, eos_pos_host non-null";
+        else if (!a->y && !a->y_f32) bad = "y or y_f32";
+        else if (!aligned16(a->y) || !aligned16(a->y_f32)) bad = "y and y_f32 16-byte aligned";
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_text_apply: op %d needs %s", op, bad);
+    const int n = a->n;
+    if (op == 0)
+        for (size_t i = 0; i < (size_t)n * TXT_T; ++i)
+            if (a->ids_host[i] < 0 || a->ids_host[i] >= a->vocab)
+                return fail(c, MME_E_ARG, "mme_text_apply: op 0: ids_host[%zu] = %d outside 0..vocab-1 = 0..%d", i, a->ids_host[i], a->vocab - 1);
+    if (op == 2)
+        for (int b = 0; b < n; ++b)
+            if (a->eos_pos_host[b] < 0 || a->eos_pos_host[b] >= TXT_T)
+                return fail(c, MME_E_ARG, "mme_text_apply: op 2: eos_pos_host[%d] = %d outside 0..%d", b, a->eos_pos_host[b], TXT_T - 1);
+    if (n == 0) return MME_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int r;
+    if (op != 1) {
+        if ((r = text_dev(c, "mme_text_apply"))) return r;
+        const size_t bytes = (op == 0 ? (size_t)n * TXT_T : (size_t)n) * sizeof(int32_t);
+        if ((r = ensure(c, c->text->apply_ints, bytes))) return r;
+        HIP_TRY(c, hipMemcpyAsync(c->text->apply_ints.p, op == 0 ? a->ids_host : a->eos_pos_host, bytes, hipMemcpyHostToDevice, s));
+    }
+    switch (op) {
+        case 0: HIP_TRY(c, launch_text_token_rows(a->tok, a->pos, (const int32_t*)c->text->apply_ints.p, a->x, n, a->d, s)); break;
+        case 1: HIP_TRY(c, launch_attention_causal(a->qkv, a->out, n, a->heads, s)); break;
+        default:
+            HIP_TRY(c, launch_text_eos_pool_ln(a->x, a->gamma, a->beta, (const int32_t*)c->text->apply_ints.p, n, a->d, a->eps, a->y, a->y_f32, s));
+            break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+}  // extern "C"

@@ -46,6 +46,12 @@ constexpr int VIT_MAX_F = 8192;
 // the widths the row kernels and the attention kernel are instantiated for
 constexpr bool vit_width_built(int d) { return d == 384 || d == 768 || d == 1024; }
 
+// CLIP text tower: 77 tokens (CLIPTextConfig.max_position_embeddings), heads of 64 as above; its row kernels and its
+// causal attention kernel run the widths 512, 768 and 1024 (8, 12, 16 heads).  512 is no width of the image path.
+constexpr int TXT_T = 77;
+constexpr int TXT_MAX_VOCAB = 65536;
+constexpr bool text_width_built(int d) { return d == 512 || d == 768 || d == 1024; }
+
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 
 __device__ __forceinline__ float wave_sum(float v) {

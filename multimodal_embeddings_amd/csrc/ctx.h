@@ -41,6 +41,7 @@ struct EventPair {
 };
 
 struct TileVitDev;  // capi_tilevit.hip
+struct TextDev;     // capi_text.hip
 
 struct mme_ctx {
     int device = 0;
@@ -88,7 +89,27 @@ struct mme_ctx {
     size_t events_used = 0;
     // tile-ViT encoder option
     TileVitDev* tv = nullptr;
+    // CLIP text tower (capi_text.hip): coexists with the image tower; allocs[text_alloc_lo, text_alloc_hi) are its weights
+    TextDev* text = nullptr;
+    size_t text_alloc_lo = 0, text_alloc_hi = 0;
 };
+
+// Frees allocs[lo, hi) (the caller has drained the device) and takes them out of the tables; `other_lo / other_hi`, the
+// range of the tower that stays, moves down with its buffers when it sits behind.  Afterwards lo == hi == allocs.size():
+// the buffers the load creates next are the new range.
+inline void release_alloc_range(mme_ctx* c, size_t& lo, size_t& hi, size_t& other_lo, size_t& other_hi) {
+    const size_t n = hi - lo;
+    if (n) {
+        for (size_t i = lo; i < hi; ++i) (void)hipFree(c->allocs[i]);
+        c->allocs.erase(c->allocs.begin() + lo, c->allocs.begin() + hi);
+        c->alloc_bytes.erase(c->alloc_bytes.begin() + lo, c->alloc_bytes.begin() + hi);
+        if (other_lo >= hi) {
+            other_lo -= n;
+            other_hi -= n;
+        }
+    }
+    lo = hi = c->allocs.size();
+}
 
 int fail(mme_ctx* c, int code, const char* fmt, ...);
 // width of the rows mme_vit_forward / mme_embed write
@@ -118,6 +139,7 @@ inline float f32_quiet_nan(float f) {
     return f;
 }
 void tile_vit_free(mme_ctx* c);
+void text_free(mme_ctx* c);  // the text tower's record and workspace (its weights are in c->allocs)
 
 // ---- weight loading (weight_load.hip) ---------------------------------------------------------------------------------
 // Each encoder's load is ONE sequence of prepared buffers (prepare_vit in weight_load.hip, prepare_tile in

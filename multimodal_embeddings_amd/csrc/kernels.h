@@ -266,6 +266,17 @@ hipError_t launch_tile_output(const void* x, const void* inter, int ni, int64_t 
 hipError_t launch_tile_pool(const void* x, const void* inter, int ni, int64_t inter_stride, int n, float* emb_f32, void* emb_bf16, hipStream_t s);
 hipError_t launch_attention_tiles(const void* qkv, void* out, const int32_t* ntiles_dev, int n, hipStream_t s, int* guard = nullptr, bool force_redo = false);
 
+// ---- CLIP text tower (text_tower.hip, attention_causal.hip): 77 tokens, heads of 64, d = 512, 768 or 1024 (else
+// hipErrorInvalidValue)
+// x[b*77 + t, :] = bf16(f32(tok[ids[b*77 + t], :]) + pos[t, :]); tok bf16 [vocab, d], pos f32 [77, d], ids DEVICE int32 [n*77], each
+// 0 <= id < vocab (the caller validates them on the host)
+hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s);
+// causal attention, T = 77, dh = 64, heads = 8, 12 or 16: qkv [n*77, 3*64*heads] (Q pre-scaled by dh^-0.5 log2 e) -> out [n*77, 64*heads]
+hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads, hipStream_t s);
+// LayerNorm of row b*77 + eos_pos[b] (DEVICE int32 [n], each 0..76) -> y bf16 [n, d] and / or y_f32 [n, d]
+hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
+                                   float* y_f32, hipStream_t s);
+
 // ---- device-side weight preparation (weight_prep.hip).  dt = MME_DT_* (include/mme.h); sources are device addresses,
 // 16-byte aligned, of elements of that type.
 // `count` elements (a multiple of 8) -> f32 table or bf16 (round to nearest even) at dst (16-byte aligned);

@@ -1,0 +1,103 @@
+// Row kernels of the CLIP text tower (transformers models/clip/modeling_clip.py, CLIPTextEmbeddings and the pooling of
+// CLIPTextTransformer.forward): the token rows that open the pass and the LayerNorm of the EOS rows that closes it.
+// One 64-lane wave owns one row of D values, D a multiple of 256 up to 1024 (512, 768, 1024: 8, 12, 16 heads of 64): a lane
+// holds columns 4 lane + 256 k .. + 3.  The sequence length is fixed at 77 (TXT_T, kernels.h) as 197 is for the image tower.
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+// x[b * 77 + t] = bf16(f32(tok[ids[b, t]]) + pos[t]): one f32 add, one rounding to nearest even.  64-bit offsets: a
+// 65536 x 1024 table holds 2^26 values, n * 77 * D passes 2^31 at n = 27 236 (D = 1024).
+__global__ __launch_bounds__(256) void token_rows(const bf16_t* __restrict__ tok, const float* __restrict__ pos, const int32_t* __restrict__ ids,
+                                                  bf16_t* __restrict__ x, int64_t rows, int D) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int t = (int)(row % TXT_T);
+    const bf16_t* tr = tok + (int64_t)ids[row] * D;
+    const float* pr = pos + (int64_t)t * D;
+    bf16_t* xr = x + row * D;
+    for (int c = lane * 4; c < D; c += 256) {
+        const bf16x4 e = *(const bf16x4*)(tr + c);
+        const f32x4 p = *(const f32x4*)(pr + c);
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (bf16_t)((float)e[j] + p[j]);
+        *(bf16x4*)(xr + c) = o;
+    }
+}
+
+// final_layer_norm of row b * 77 + eos_pos[b], the two-pass f32 form of pool_ln_rows (rowops.hip), rounded to bf16
+// [n, D] for the projection GEMM and / or left in f32 [n, D] (a tower without text_projection: the L2 step reads that).
+__global__ __launch_bounds__(256) void eos_pool_ln_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        const int32_t* __restrict__ eos_pos, int n, int D, float eps, bf16_t* __restrict__ y,
+                                                        float* __restrict__ yf) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n) return;
+    const bf16_t* xr = x + ((int64_t)b * TXT_T + eos_pos[b]) * D;
+    const int nk = D >> 8;  // 2, 3 or 4 groups of 256 columns (wave-uniform)
+    float v[4][4];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < nk) {
+            const bf16x4 p = *(const bf16x4*)(xr + k * 256 + lane * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[k][j] = (float)p[j];
+                s += v[k][j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[k][j] = 0.f;
+        }
+    }
+    const float mean = wave_sum(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < nk) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[k][j] -= mean;
+                q += v[k][j] * v[k][j];
+            }
+        }
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < nk) {
+            const int c = k * 256 + lane * 4;
+            const f32x4 gv = *(const f32x4*)(gamma + c);
+            const f32x4 bv = *(const f32x4*)(beta + c);
+            f32x4 o;
+            bf16x4 ob;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = v[k][j] * rstd * gv[j] + bv[j];
+                ob[j] = (bf16_t)o[j];
+            }
+            if (y) *(bf16x4*)(y + (int64_t)b * D + c) = ob;
+            if (yf) *(f32x4*)(yf + (int64_t)b * D + c) = o;
+        }
+}
+
+}  // namespace
+
+hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s) {
+    if (!text_width_built(d)) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    const int64_t rows = (int64_t)n * TXT_T;
+    hipLaunchKernelGGL(token_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const bf16_t*)tok, pos, ids, (bf16_t*)x, rows, d);
+    return hipGetLastError();
+}
+
+hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
+                                   float* y_f32, hipStream_t s) {
+    if (!text_width_built(d)) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(eos_pool_ln_rows, dim3((n + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, eos_pos, n, d, eps, (bf16_t*)y, y_f32);
+    return hipGetLastError();
+}

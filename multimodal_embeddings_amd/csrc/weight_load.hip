@@ -249,13 +249,9 @@ int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who =
 int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     HIP_TRY(c, hipSetDevice(c->device));
     c->loaded = false;
-    if (c->vit_alloc_hi > c->vit_alloc_lo) {
-        HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
-        for (size_t i = c->vit_alloc_lo; i < c->vit_alloc_hi; ++i) (void)hipFree(c->allocs[i]);
-        c->allocs.erase(c->allocs.begin() + c->vit_alloc_lo, c->allocs.begin() + c->vit_alloc_hi);
-        c->alloc_bytes.erase(c->alloc_bytes.begin() + c->vit_alloc_lo, c->alloc_bytes.begin() + c->vit_alloc_hi);
-    }
-    c->vit_alloc_lo = c->vit_alloc_hi = c->allocs.size();
+    if (c->vit_alloc_hi > c->vit_alloc_lo) HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
+    // exactly the image tower's buffers; a text tower loaded behind them keeps its own, its range moves down with them
+    release_alloc_range(c, c->vit_alloc_lo, c->vit_alloc_hi, c->text_alloc_lo, c->text_alloc_hi);
     c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp};
     c->ln_eps = w->ln_eps;
     c->layer.assign((size_t)w->layers, LayerDev{});

@@ -113,7 +113,7 @@ class RegionEmbedder:
     def __init__(self, model_name=config.DEFAULT_MODEL_NAME, device=None, gpu_count=None, *, weights=None,
                  seed: int = 1, pool: str = "cls", chunk: int | None = None, engine: Engine | None = None, devices=None,
                  encoder: str = "vit_b16", geometry=None, prune_last_layer: bool | None = None, allow_synthetic: bool = True,
-                 resize_rule: str | None = None):
+                 resize_rule: str | None = None, text_tower=None, tokenizer=None):
         """`model_name`: a LOCAL checkpoint directory (config.json + model.safetensors | shards | pytorch_model.bin, optionally
         preprocessor_config.json) is read once (checkpoint.read_checkpoint), loaded into every context in the file's own dtype
         and its image_mean / image_std applied; `self.checkpoint` keeps it.  Any other name is never fetched: the encoder runs
@@ -128,7 +128,13 @@ class RegionEmbedder:
         `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
         fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
         encoders only; a checkpoint's preprocessor_config.json must then describe exactly that rule).  It is set on every
-        engine of this object; None leaves a caller's `engine=` as it is."""
+        engine of this object; None leaves a caller's `engine=` as it is.
+        `text_tower`: the CLIP text tower behind `get_text_embeddings`, in the FIRST engine only.  None: nothing is loaded
+        now; the first `get_text_embeddings` loads it if `model_name` is a checkpoint directory that holds one.  True: load
+        now (from that directory, or seeded CLIP_TEXT_B-shaped weights projecting to this object's `embed_dim` beside a seeded
+        image side).  A directory path or a `weights.clip_text_tensor_specs` dict: load that.  False: never.
+        `tokenizer`: a callable str -> list[int] or a transformers tokenizer; by default transformers' CLIPTokenizer is read
+        from the tower's directory on first use (local files only).  Token ids need no tokenizer."""
         import torch
 
         from .checkpoint import check_resize_rule, read_checkpoint, resolve_model_source
@@ -238,6 +244,13 @@ class RegionEmbedder:
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
         self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
         self._group_crops = 16 * config.BATCH_SIZE
+        self._seed = seed
+        self._tokenizer = tokenizer
+        self._text_source = text_tower  # None: look in model_name on first use; False: never
+        self._text_dir = None           # where a default tokenizer is looked for
+        self._text_loaded = False
+        if text_tower is not None and text_tower is not False:
+            self._load_text_tower()
 
     # -- device-resident API -------------------------------------------------------------------
     def pack(self, arrays, device=None):
@@ -604,11 +617,109 @@ class RegionEmbedder:
             raise MmeError("embed(region) failed; see log")
         return np.asarray(out[0], dtype=np.float32)
 
+    # -- text queries (embedder.py:228-254) ------------------------------------------------------------------
+    _NO_TOWER = ("text embeddings need a CLIP text tower: construct RegionEmbedder(..., text_tower=True | a checkpoint directory | a weight "
+                 "dict), or name a checkpoint directory that holds one (a whole CLIPModel); the mmE5 language tower stays out of scope")
+
+    def _load_text_tower(self):
+        """Loads the tower `text_tower=` named into the first engine; NotImplementedError when there is none to load."""
+        from .checkpoint import read_checkpoint
+
+        src = getattr(self, "_text_source", False)
+        eng = self.engines[0]
+        if src is False:
+            raise NotImplementedError(self._NO_TOWER)
+        if isinstance(src, dict):
+            eng.load_clip_text(src)
+        elif isinstance(src, (str, os.PathLike)):
+            eng.load_clip_text_checkpoint(read_checkpoint(src, "clip_text"))
+            self._text_dir = os.fspath(src)
+        elif self.checkpoint is not None:  # None or True beside a checkpoint directory: its own text half
+            try:
+                ck = read_checkpoint(self.model_name, "clip_text")
+            except MmeError as e:
+                if src is None:
+                    raise NotImplementedError(f"{self._NO_TOWER} ({e})") from e
+                raise
+            eng.load_clip_text_checkpoint(ck)
+            self._text_dir = os.fspath(self.model_name)
+        elif src is True:  # seeded, in the space the seeded image side embeds into
+            import dataclasses
+
+            from .weights import CLIP_TEXT_B, make_clip_text_weights
+
+            geom = dataclasses.replace(CLIP_TEXT_B, projection_dim=int(self.embed_dim))
+            eng.load_clip_text(make_clip_text_weights(self._seed + 2, geom), geom)
+        else:
+            raise NotImplementedError(self._NO_TOWER)
+        self._text_loaded = True
+
+    def _tokenize(self, text: str) -> list:
+        """str -> token ids through `tokenizer=` or the lazily loaded CLIPTokenizer of the tower's directory."""
+        tok = getattr(self, "_tokenizer", None)
+        if tok is None:
+            d = getattr(self, "_text_dir", None)
+            hint = "pass tokenizer= (a callable str -> list[int] or a transformers tokenizer); token ids (a sequence of ints) are accepted as they are"
+            if d is None:
+                raise MmeError(f"get_text_embeddings: no tokenizer for a str: {hint}")
+            have = lambda *names: all(os.path.exists(os.path.join(d, n)) for n in names)  # noqa: E731
+            if not (have("vocab.json", "merges.txt") or have("tokenizer.json")):
+                raise MmeError(f"get_text_embeddings: {d!r} holds no CLIP tokenizer files (vocab.json + merges.txt, or tokenizer.json): {hint}")
+            try:
+                from transformers import CLIPTokenizer
+            except ImportError as e:
+                raise MmeError(f"get_text_embeddings: transformers is not installed, so {d!r} cannot be tokenized: {hint}") from e
+            try:
+                tok = CLIPTokenizer.from_pretrained(d, local_files_only=True)  # nothing is ever fetched
+            except Exception as e:  # noqa: BLE001 - whatever the reader raises for missing or broken files
+                raise MmeError(f"get_text_embeddings: {d!r} holds no usable CLIP tokenizer files (vocab.json, merges.txt): {e}; {hint}") from e
+            self._tokenizer = tok
+        if hasattr(tok, "pad_token_id") or hasattr(tok, "encode"):  # a transformers tokenizer
+            ids = tok(text, padding="max_length", max_length=77, truncation=True)["input_ids"]
+        else:
+            ids = tok(text)
+        return [int(v) for v in ids]
+
+    def _text_ids(self, item) -> np.ndarray:
+        """One query -> int32[77]: a str through the tokenizer, ids right-padded with the tower's eos_token_id."""
+        ids = self._tokenize(item) if isinstance(item, str) else item
+        a = np.asarray(ids)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise MmeError(f"get_text_embeddings: token ids must be a 1-D integer sequence, got {a.dtype} {tuple(a.shape)}")
+        if a.shape[0] > 77:
+            raise MmeError(f"get_text_embeddings: {a.shape[0]} token ids; supported: at most 77")
+        row = np.full(77, self.engines[0].text_info()["eos_token_id"], dtype=np.int64)
+        row[: a.shape[0]] = a
+        return row
+
     def get_text_embeddings(self, text):
-        """embedder.py:228-254 is adjacent to the hot path and not part of the metric."""
-        raise NotImplementedError(
-            "text embeddings need the mmE5 language tower, which BASELINE.json re-scopes away (ViT image encoder only)"
-        )
+        """A str, or a 1-D sequence / array of token ids -> list[float] of `text_embed_dim`, unit length; a list of str, or
+        a 2-D int array -> a list of such vectors.  Raises on failure, as the reference's does (embedder.py:228-254).
+        NotImplementedError without a text tower."""
+        engines = getattr(self, "engines", None)
+        if not engines or getattr(self, "_text_source", False) is False:
+            raise NotImplementedError(self._NO_TOWER)
+        if not getattr(self, "_text_loaded", False):
+            self._load_text_tower()
+        single = isinstance(text, str)
+        if not single:
+            a = text if isinstance(text, np.ndarray) else None
+            if a is None and isinstance(text, (list, tuple)) and len(text) and not isinstance(text[0], (str, list, tuple, np.ndarray)):
+                a = np.asarray(text)
+            single = a is not None and a.ndim == 1
+        items = [text] if single else list(text)
+        if not items:
+            return []
+        ids = np.stack([self._text_ids(it) for it in items])
+        e32, _ = engines[0].text_forward(ids, want_f32=True, want_bf16=False)
+        rows = e32.cpu().numpy()
+        out = [[float(v) for v in r] for r in rows]
+        return out[0] if single else out
+
+    @property
+    def text_embed_dim(self) -> int:
+        """Width of the vectors `get_text_embeddings` returns; 0 while no text tower is loaded."""
+        return int(self.engines[0].text_embed_dim)
 
 
 # the reference's class name, so `from embedder import MmE5MllamaEmbedder` call sites port 1:1

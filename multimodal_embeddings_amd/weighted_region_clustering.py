@@ -134,16 +134,27 @@ class RegionCollection:
             "documents": [self.documents[r] for r in rows],
         }
 
-    def query(self, query_embeddings=None, n_results=10, where=None, include=("metadatas", "documents", "distances"), engine=None):
+    def query(self, query_embeddings=None, n_results=10, where=None, include=("metadatas", "documents", "distances"), engine=None, *,
+              query_texts=None, embedder=None):
         """chroma's `Collection.query`: for every query vector the `n_results` nearest stored vectors that pass
         `where`, as lists of lists (one inner list per query), distance ascending.
 
         Exact brute force on the GPU: the candidates that pass `where` and the query vectors are stacked into one
         table of unit bf16 rows; kernel K12 ranks the query rows against it with the queries' own group masked out
         (so a query never returns itself or another query).  Up to 128 results per query come from K12's streaming
-        selection (k + number of queries <= 128); larger requests sort a K9 cosine block."""
+        selection (k + number of queries <= 128); larger requests sort a K9 cosine block.
+
+        `query_texts` (a str, or a list of str / token-id sequences) with `embedder` (a RegionEmbedder that has a CLIP text
+        tower) are embedded by `embedder.get_text_embeddings` and take the same path; the stored vectors must have the
+        tower's width (an image tower and a text tower of one CLIP model share it)."""
         from .cross_compare import to_unit_bf16
 
+        if (query_embeddings is None or len(query_embeddings) == 0) and query_texts is not None and embedder is not None:
+            texts = [query_texts] if isinstance(query_texts, str) else list(query_texts)
+            query_embeddings = embedder.get_text_embeddings(texts) if texts else []
+            stored = next((len(e) for e in self.embeddings if e is not None and len(e) > 0), None)
+            if query_embeddings and stored is not None and len(query_embeddings[0]) != stored:
+                raise ValueError(f"query_texts: the text tower embeds into {len(query_embeddings[0])} dimensions, the stored vectors have {stored}")
         if query_embeddings is None or len(query_embeddings) == 0:
             raise ValueError("query_embeddings is required (text queries need the language tower, which is out of scope)")
         keep = _where_mask(self.metadatas, where)

@@ -226,6 +226,153 @@ def infer_clip_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quick_gel
                         layer_norm_eps=float(eps), projection_dim=P, hidden_act=hidden_act)
 
 
+# ---- CLIP text towers -------------------------------------------------------------------------------------------------
+TEXT_TOKENS = 77  # CLIPTextConfig.max_position_embeddings; fixed at compile time (csrc/common.h TXT_T)
+
+
+@dataclass(frozen=True)
+class CLIPTextGeometry:
+    """A CLIP text tower (transformers CLIPTextConfig) at what the engine runs: 77 positions, heads of 64.  The defaults are
+    clip-vit-base-patch16's text tower.  `projection_dim` None: no text_projection (`CLIPTextModel`), the embedding is the
+    final_layer_norm row at the EOS position.  `eos_token_id` 2 selects transformers' legacy pooling rule (the position of
+    the sequence's largest id)."""
+
+    hidden_size: int = 512
+    num_layers: int = 12
+    num_heads: int = 8
+    intermediate_size: int = 2048
+    vocab_size: int = 49408
+    max_position_embeddings: int = TEXT_TOKENS
+    eos_token_id: int = 49407
+    projection_dim: int | None = 512
+    hidden_act: str = "quick_gelu"
+    layer_norm_eps: float = 1e-5
+
+    @property
+    def embed_dim(self) -> int:
+        return self.projection_dim or self.hidden_size
+
+
+CLIP_TEXT_B = CLIPTextGeometry()
+SUPPORTED_CLIP_TEXT = {"hidden_size": (512, 768, 1024), "max_position_embeddings": (TEXT_TOKENS,), "intermediate_size": "a multiple of 64 up to 8192",
+                       "num_layers": "1..64", "vocab_size": "3..65536", "projection_dim": "absent, or a multiple of 64 up to 1024"}
+
+
+def clip_text_geometry_problem(geom: CLIPTextGeometry):
+    """None when the engine runs `geom`, else (field, value found, supported values as text) of the first field outside the
+    supported set (csrc/capi_text.hip validate_text_weights)."""
+    for fld in ("hidden_size", "max_position_embeddings"):
+        if getattr(geom, fld) not in SUPPORTED_CLIP_TEXT[fld]:
+            return fld, getattr(geom, fld), ", ".join(str(v) for v in SUPPORTED_CLIP_TEXT[fld])
+    if geom.num_heads * 64 != geom.hidden_size:
+        return "num_heads", geom.num_heads, f"{geom.hidden_size // 64} at hidden_size {geom.hidden_size} (heads of 64)"
+    F = geom.intermediate_size
+    if F < 64 or F % 64 or F > 8192:
+        return "intermediate_size", F, SUPPORTED_CLIP_TEXT["intermediate_size"]
+    if not 1 <= geom.num_layers <= 64:
+        return "num_layers", geom.num_layers, SUPPORTED_CLIP_TEXT["num_layers"]
+    if not 3 <= geom.vocab_size <= 65536:
+        return "vocab_size", geom.vocab_size, SUPPORTED_CLIP_TEXT["vocab_size"]
+    if geom.hidden_act not in CLIP_ACTS:
+        return "hidden_act", geom.hidden_act, ", ".join(CLIP_ACTS)
+    P = geom.projection_dim
+    if P is not None and (isinstance(P, bool) or not isinstance(P, int) or P < 64 or P % 64 or P > 1024):
+        return "projection_dim", P, SUPPORTED_CLIP_TEXT["projection_dim"]
+    if isinstance(geom.eos_token_id, bool) or not isinstance(geom.eos_token_id, int) or not 0 <= geom.eos_token_id < geom.vocab_size:
+        return "eos_token_id", geom.eos_token_id, f"0..{geom.vocab_size - 1} (vocab_size - 1)"
+    return None
+
+
+def clip_text_tensor_specs(geom: CLIPTextGeometry = CLIP_TEXT_B):
+    """(name, shape, kind) in a fixed order, the state-dict names of Hugging Face `CLIPTextModelWithProjection`
+    (transformers models/clip/modeling_clip.py); kind in {matrix, bias, gamma}.  Without `projection_dim` the list ends at
+    final_layer_norm (`CLIPTextModel`)."""
+    D, F = geom.hidden_size, geom.intermediate_size
+    t = "text_model."
+    specs = [
+        (t + "embeddings.token_embedding.weight", (geom.vocab_size, D), "matrix"),
+        (t + "embeddings.position_embedding.weight", (geom.max_position_embeddings, D), "matrix"),
+    ]
+    for i in range(geom.num_layers):
+        p = f"{t}encoder.layers.{i}."
+        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
+        for n in ("q", "k", "v", "out"):
+            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
+        specs += [
+            (p + "layer_norm2.weight", (D,), "gamma"),
+            (p + "layer_norm2.bias", (D,), "bias"),
+            (p + "mlp.fc1.weight", (F, D), "matrix"),
+            (p + "mlp.fc1.bias", (F,), "bias"),
+            (p + "mlp.fc2.weight", (D, F), "matrix"),
+            (p + "mlp.fc2.bias", (D,), "bias"),
+        ]
+    specs += [(t + "final_layer_norm.weight", (D,), "gamma"), (t + "final_layer_norm.bias", (D,), "bias")]
+    if geom.projection_dim:
+        specs.append(("text_projection.weight", (geom.projection_dim, D), "matrix"))
+    return specs
+
+
+def make_clip_text_weights(seed: int = 3, geom: CLIPTextGeometry = CLIP_TEXT_B, std: float = 0.02) -> dict[str, np.ndarray]:
+    """Seeded synthetic weights of a CLIP text tower, f32 arrays holding bf16-representable values: the generator and the
+    LayerNorm spread (1 + 0.25 z, 0.1 z) of `make_clip_weights` on `clip_text_tensor_specs`."""
+    out: dict[str, np.ndarray] = {}
+    for tid, (name, shape, kind) in enumerate(clip_text_tensor_specs(geom)):
+        n = int(np.prod(shape))
+        z = irwin_hall_normal(seed, tid, n)
+        if kind == "gamma":
+            z = np.float32(1.0) + z * np.float32(0.25)
+        elif kind == "bias" and "layer_norm" in name:
+            z = z * np.float32(0.1)
+        else:
+            z = z * np.float32(std)
+        out[name] = round_to_bf16(z).reshape(shape)
+    return out
+
+
+def infer_clip_text_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quick_gelu", eos_token_id: int | None = None) -> CLIPTextGeometry:
+    """The geometry of a `clip_text_tensor_specs` weight dict, read off its tensor shapes; heads of 64.  What is not in the
+    tensors is named by the caller: the activation, eps and `eos_token_id` (default: the last id of the table, where CLIP's
+    vocabulary keeps <|endoftext|>)."""
+    V, D = (int(v) for v in np.shape(w["text_model.embeddings.token_embedding.weight"]))
+    T = int(np.shape(w["text_model.embeddings.position_embedding.weight"])[0])
+    layers = 0
+    while f"text_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError("the weight dict holds no 'text_model.encoder.layers.0.mlp.fc1.weight'")
+    F = int(np.shape(w["text_model.encoder.layers.0.mlp.fc1.weight"])[0])
+    P = int(np.shape(w["text_projection.weight"])[0]) if "text_projection.weight" in w else None
+    return CLIPTextGeometry(hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F, vocab_size=V, max_position_embeddings=T,
+                            eos_token_id=V - 1 if eos_token_id is None else int(eos_token_id), projection_dim=P, hidden_act=hidden_act,
+                            layer_norm_eps=float(eps))
+
+
+def clip_text_flops_per_sequence(geom: CLIPTextGeometry = CLIP_TEXT_B) -> int:
+    """FLOP of one sequence's forward counted as `vit_flops_per_crop` counts (2 per multiply-add; LayerNorm, softmax and the
+    activation excluded): per layer the four projections and the two MLP matrices on 77 tokens plus the two attention
+    products over the T (T + 1) / 2 unmasked (query, key) pairs, then the projection of the pooled row.  All 77 rows are
+    counted: the pass computes the rows behind the EOS too."""
+    D, F, L, T = geom.hidden_size, geom.intermediate_size, geom.num_layers, geom.max_position_embeddings
+    return L * (2 * T * D * (4 * D + 2 * F) + 4 * (T * (T + 1) // 2) * D) + 2 * D * (geom.projection_dim or 0)
+
+
+def synthetic_token_ids(n: int, vocab: int, eos: int, seed: int = 0, lengths=None) -> np.ndarray:
+    """int32 [n, 77] BOS-free, right-padded sequences: sequence i holds lengths[i] - 1 hashed ids, none of them `eos`, then
+    `eos` at position lengths[i] - 1 and in every position behind it (the padding CLIP's tokenizer writes).  `lengths`
+    defaults to hashed values in 2..77."""
+    if lengths is None:
+        lengths = 2 + (counter_u64(seed, 0x7100, n) % np.uint64(TEXT_TOKENS - 1)).astype(np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.shape[0] != n or lengths.min() < 1 or lengths.max() > TEXT_TOKENS:
+        raise ValueError(f"lengths must hold {n} values in 1..{TEXT_TOKENS}")
+    out = np.full((n, TEXT_TOKENS), eos, dtype=np.int32)
+    for i in range(n):
+        body = (counter_u64(seed, 0x7101, TEXT_TOKENS, i) % np.uint64(vocab - 1)).astype(np.int64)
+        body += body >= eos  # 0..vocab-1 without eos
+        out[i, : lengths[i] - 1] = body[: lengths[i] - 1]
+    return out
+
+
 def _splitmix64(x: np.ndarray) -> np.ndarray:
     """splitmix64 finaliser on uint64 arrays (wrapping arithmetic)."""
     with np.errstate(over="ignore"):
