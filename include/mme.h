@@ -61,7 +61,8 @@ const char* mme_last_error(const mme_ctx* ctx); /* ctx may be NULL: creation err
  * (transformers models/vit/modeling_vit.py): Linear weights are [out, in]; the patch
  * projection is [hidden, 3*patch*patch] in (c, ky, kx) order.  Values are rounded to
  * bf16 on upload (the reference runs the encoder in bf16, embedder.py:78).
- * Supported geometries: image_size 224, patch_size 16, heads of 64 (heads == hidden / 64), hidden 384, 768 or 1024,
+ * Supported geometries: image_size 224, patch_size 16 or 32 (197 or 50 tokens; pos_emb [197 | 50, hidden], patch_w
+ * [hidden, 768 | 3072]), heads of 64 (heads == hidden / 64), hidden 384, 768 or 1024,
  * mlp a multiple of 64 up to 8192, 1..64 layers, any ln_eps.  Anything else is MME_E_ARG with a text that names the
  * field, the value found and the supported values; nothing in the context changes then.
  * A context runs the geometry of its LAST successful load, ViT-B/16 (224/16/768/12/12/3072) before any: a second load
@@ -77,7 +78,7 @@ typedef struct {
 
 typedef struct {
     int32_t image_size;  /* 224 */
-    int32_t patch_size;  /* 16  */
+    int32_t patch_size;  /* 16 or 32 */
     int32_t hidden;      /* 384, 768 or 1024 */
     int32_t layers;      /* 1..64 */
     int32_t heads;       /* hidden / 64 */
@@ -419,6 +420,8 @@ int mme_attention_redone_n(mme_ctx* ctx, int count, int32_t* flags);
  *                      qkv_dev bf16 [n*197][3*hidden] = Q | K | V, head h at columns 64h of each part -> out_dev bf16 [n*197][hidden];
  *                      only_block -1 (every query block) or 0..6 (only queries 32b..32b+31 are computed and stored, as the
  *                      pruned last layer does); reverse 0 / 1 (the walk order of the blocks; results are bit-identical).
+ *                      This is the 197-token kernel: under a patch-32 context (50 tokens) kind 0 is MME_E_ARG, and
+ *                      mme_vit32_apply op 2 launches that geometry's kernel.
  *   kind 1 (tile-ViT): qkv_dev bf16 [n*6432][3840], 16 heads of 80 -> out_dev bf16 [n*6432][1280]; ntiles_host int32[n],
  *                      the tiles each image uses (1..4: the padding mask); only_block must be -1 and reverse 0.
  * Q carries dh^-0.5 log2(e) already (as after mme_load_vit / mme_load_tile_vit): the scores are base-2 logits.
@@ -465,7 +468,9 @@ int mme_nms_boxes(mme_ctx* ctx, const double* boxes, const double* scores, const
  *   offs_host   int64[n]   byte offset of crop i inside pix_dev
  *   hw_host     int32[n,2] (height, width) of crop i  (int()-truncated bbox size,
  *                          doclayout_detector.py:179)
- *   patches_dev bf16[n*196, 768] */
+ *   patches_dev bf16[n*196, 768]; under a patch-32 context (mme_vit_geometry: patch_size 32) bf16[n*49, 3072], the same
+ *               bytes per crop: K1 writes the patch-16 matrix into an internal staging buffer and a copy kernel permutes
+ *               it (four 16 x 16 patches are one 32 x 32 patch), so every pixel value is the same bit for bit */
 int mme_preprocess(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* offs_host, const int32_t* hw_host,
                    int n, uint16_t* patches_dev, void* stream);
 
@@ -487,7 +492,10 @@ int mme_preprocess_tiles(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* of
 /* ---- K2-K8: ViT forward + pool + L2 normalise -------------------------------------------
  * Replaces `model(**inputs, output_hidden_states=True)` + `last_pooling`
  * (embedder.py:124-129, :17-34).  pool_token: 0 = [CLS] (default), 196 = last token
- * (the reference's "last attended token" with an all-ones mask), any 0..196.
+ * (the reference's "last attended token" with an all-ones mask), any 0..196; under a patch-32 context any 0..49, and
+ * patches_dev is the bf16[n*49, 3072] matrix mme_preprocess writes there.  A patch-32 pass runs its own patch embedding
+ * (f32 GEMM + one row kernel), attention (exact row maximum: mme_set_attention_mode keeps its value, mme_attention_redone
+ * reports zeros) and pooling kernels; every GEMM and LayerNorm form is the patch-16 pass's.
  *   emb_f32_dev  float[n, embed_dim]  L2-normalised (may be NULL)
  *   emb_bf16_dev bf16 [n, embed_dim]  same vectors rounded to bf16 (may be NULL)
  * embed_dim (mme_encoder_info) is `hidden` for a ViT and for a CLIP tower without projection, else the tower's proj_dim.
@@ -706,6 +714,40 @@ typedef struct mme_clip_apply_args {
     int32_t* ran_256;       /* ops 0, 1, optional: set to 1 when the 256 x 256 kernel ran, 0 for the 128 x 128 one */
 } mme_clip_apply_args;
 int mme_clip_apply(mme_ctx* ctx, int op, const mme_clip_apply_args* args, void* stream);
+
+/* Diagnostic: ONE launch of a kernel a patch-32 tower (ViT/32 @224: 49 patches of 32 x 32, 50 tokens) adds, on the caller's
+ * device buffers, synchronous; works on a bare context.  n = crops (B of the pool forms).
+ *   op 0 retile_patches_p32  src bf16 [n * 196, 768] (what K1 writes) -> dst bf16 [n * 49, 3072], conv order (c, ky, kx):
+ *                            dst[b * 49 + PY * 7 + PX][c * 1024 + KY * 32 + KX] =
+ *                            src[b * 196 + (2 PY + KY / 16) * 14 + 2 PX + KX / 16][c * 256 + (KY % 16) * 16 + KX % 16]
+ *      1 embed_rows_t50      acc f32 [n * 49, d] -> x bf16 [n * 50, d]: x[b * 50 + 1 + p] = bf16((acc[b * 49 + p] + bias) + pos[1 + p]),
+ *                            x[b * 50] = bf16(cls + pos[0]); pos f32 [50, d], f32 adds in that order
+ *      2 attn_fwd_t50        qkv bf16 [n * 50, 3 * 64 * heads] (Q | K | V, Q pre-scaled by dh^-0.5 log2 e) -> out bf16 [n * 50, 64 * heads];
+ *                            exact row maximum under every attention mode; only_block 0 / 1: rows 0..31 / 32..49 of every crop only
+ *      3 pool_ln_rows (50)   y[b] = bf16(LayerNorm(x[b * 50 + tok]) * gamma + beta), y bf16 [n, d]
+ *      4 pool_ln_l2 (50)     the same row, LayerNorm then x / max(||x||, 1e-12), to emb_f32 and / or emb_bf16 [n, d]
+ * Preconditions (else MME_E_ARG, nothing launched): op 0..4; 0 <= n <= 2^20; every tensor an op reads or writes non-null
+ * and 16-byte aligned (op 4: one of the two outputs may be NULL); op 0: src != dst; ops 1, 3, 4: d == 384, 768 or 1024;
+ * op 2: heads == 6, 12 or 16, only_block in -1..1; ops 3, 4: 0 <= tok <= 49. */
+typedef struct mme_vit32_apply_args {
+    const uint16_t* src;    /* op 0 */
+    uint16_t* dst;
+    const float* acc;       /* op 1 */
+    const float* bias;
+    const float* pos;
+    const float* cls;
+    uint16_t* x;            /* op 1: out; ops 3, 4: in, bf16 rows of d */
+    const uint16_t* qkv;    /* op 2 */
+    uint16_t* out;
+    const float* gamma;     /* ops 3, 4 */
+    const float* beta;
+    uint16_t* y;            /* op 3 */
+    float* emb_f32;         /* op 4 */
+    uint16_t* emb_bf16;
+    int32_t n, d, heads, only_block, tok;
+    float eps;
+} mme_vit32_apply_args;
+int mme_vit32_apply(mme_ctx* ctx, int op, const mme_vit32_apply_args* args, void* stream);
 
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
  * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,

@@ -101,6 +101,11 @@ class _ClipApplyArgs(C.Structure):  # mme_clip_apply_args
         ("ran_256", C.POINTER(C.c_int32))]
 
 
+class _Vit32ApplyArgs(C.Structure):  # mme_vit32_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "acc", "bias", "pos", "cls", "x", "qkv", "out", "gamma", "beta", "y", "emb_f32", "emb_bf16")] + [
+        (n, C.c_int32) for n in ("n", "d", "heads", "only_block", "tok")] + [("eps", C.c_float)]
+
+
 class _TileRowopApplyArgs(C.Structure):  # mme_tile_rowop_apply_args
     _fields_ = [(n, C.c_void_p) for n in ("pv", "patches", "pemb", "cls", "pre", "pos", "tilepos", "gamma", "beta", "post", "aid", "x", "inter", "hidden",
                                           "emb_f32", "emb_bf16")] + [
@@ -130,6 +135,7 @@ EXPORTS = {
     "mme_load_clip_as": (C.c_int, [C.c_void_p, C.POINTER(_ClipWeights), C.c_int, C.c_void_p]),
     "mme_encoder_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_clip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_ClipApplyArgs), C.c_void_p]),
+    "mme_vit32_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_Vit32ApplyArgs), C.c_void_p]),
     "mme_load_clip_text": (C.c_int, [C.c_void_p, C.POINTER(_ClipTextWeights)]),
     "mme_load_clip_text_as": (C.c_int, [C.c_void_p, C.POINTER(_ClipTextWeights), C.c_int, C.c_void_p]),
     "mme_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -830,6 +836,20 @@ class Engine:
         self._check(self.lib.mme_clip_apply(self.h, code, C.byref(a), self._stream()), "mme_clip_apply")
         return bool(ran.value) if g is not None else None
 
+    VIT32_OPS = {"retile": 0, "embed_rows": 1, "attention": 2, "pool_ln": 3, "pool_ln_l2": 4}
+
+    def vit32_apply(self, op, *, src=None, dst=None, acc=None, bias=None, pos=None, cls=None, x=None, qkv=None, out=None, gamma=None, beta=None,
+                    y=None, emb_f32=None, emb_bf16=None, n: int = 0, d: int = 768, heads: int = 12, only_block: int = -1, tok: int = 0,
+                    eps: float = 1e-5):
+        """ONE launch of a kernel a patch-32 tower adds (ViT/32 @224: 49 patches, 50 tokens), on the caller's CUDA tensors
+        (mme_vit32_apply; synchronous, works on a bare context).  op: a name of VIT32_OPS or its code; `n` = crops; which
+        tensors each op reads is in include/mme.h.  The library validates."""
+        a = _Vit32ApplyArgs()
+        a.src, a.dst, a.acc, a.bias, a.pos, a.cls, a.x = (self._ptr(t) for t in (src, dst, acc, bias, pos, cls, x))
+        a.qkv, a.out, a.gamma, a.beta, a.y, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (qkv, out, gamma, beta, y, emb_f32, emb_bf16))
+        a.n, a.d, a.heads, a.only_block, a.tok, a.eps = int(n), int(d), int(heads), int(only_block), int(tok), float(eps)
+        self._check(self.lib.mme_vit32_apply(self.h, int(self.VIT32_OPS.get(op, op)), C.byref(a), self._stream()), "mme_vit32_apply")
+
     TILE_ROWOPS = {"patchify": 0, "assemble": 1, "ln_post": 2, "output": 3, "pool": 4}
 
     def tile_rowop_apply(self, op, *, pv=None, patches=None, pemb=None, cls=None, pre=None, pos=None, tilepos=None, gamma=None, beta=None, post=None,
@@ -903,7 +923,8 @@ class Engine:
         return [keep[page_offs[p] : page_offs[p] + count[p]].copy() for p in range(pages)]
 
     def preprocess(self, pix, offs, hw):
-        """pix: uint8 CUDA tensor (concatenated HWC crops, >=16 spare bytes at the end)."""
+        """pix: uint8 CUDA tensor (concatenated HWC crops, >=16 spare bytes at the end).  -> bf16 patches of the loaded
+        geometry: [n * 196, 768] at patch 16, [n * 49, 3072] at patch 32 (the same bytes per crop)."""
         t = self.torch
         offs, hw = self._crop_tables(offs, hw)
         n = len(offs)

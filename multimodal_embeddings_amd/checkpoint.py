@@ -7,7 +7,7 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
     model.safetensors  |  model.safetensors.index.json + shards  |  pytorch_model.bin
 
 -- checks that its configuration is a geometry the library is built for ("vit_b16": exactly ViT-B/16; "vit": any of the
-supported ViT/16 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "clip": a CLIP image tower of that family,
+supported ViT/16 and ViT/32 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "clip": a CLIP image tower of that family,
 `CLIPVisionModel[WithProjection]` or the vision half of a whole `CLIPModel`; "clip_text": a CLIP text tower,
 `CLIPTextModel[WithProjection]` or the text half of a whole `CLIPModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
@@ -163,7 +163,7 @@ def _vit_geometry(cfg: dict, where: str) -> ViTGeometry:
 
 
 def _vit_family_geometry(cfg: dict, where: str) -> ViTGeometry:
-    """config.json of any ViT/16 @224 the engine runs (weights.SUPPORTED_VIT); a field outside the set is refused with the
+    """config.json of any ViT/16 or ViT/32 @224 the engine runs (weights.SUPPORTED_VIT); a field outside the set is refused with the
     field, the value found and the supported values."""
     b = VIT_B16
     for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):

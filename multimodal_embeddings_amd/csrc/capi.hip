@@ -53,8 +53,9 @@ int ensure(mme_ctx* c, DevBuf& b, size_t bytes) {
 // (ensure() never shrinks a buffer, so going back to a narrower one keeps what is there).
 int ensure_workspace(mme_ctx* c) {
     const int D = c->geom.hidden, F = c->geom.mlp;
-    if (c->ws_chunk == c->chunk && c->ws_hidden == D && c->ws_mlp == F) return MME_OK;
-    const size_t rows = (size_t)c->chunk * VIT_T;
+    const int T = c->geom.tokens();  // 197, or 50 at patch 32 (a quarter of the rows; ensure() keeps the larger buffers)
+    if (c->ws_chunk == c->chunk && c->ws_hidden == D && c->ws_mlp == F && c->ws_tokens == T) return MME_OK;
+    const size_t rows = (size_t)c->chunk * T;
     int r;
     if ((r = ensure(c, c->x, rows * D * 2))) return r;
     if ((r = ensure(c, c->hbuf, rows * D * 2))) return r;
@@ -67,6 +68,7 @@ int ensure_workspace(mme_ctx* c) {
     c->ws_chunk = c->chunk;
     c->ws_hidden = D;
     c->ws_mlp = F;
+    c->ws_tokens = T;
     return MME_OK;
 }
 
@@ -142,7 +144,9 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
 }
 
 int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
-    const int M = n * VIT_T;
+    const bool t50 = c->geom.t50();  // patch 32: 50 tokens, its own patch embedding, attention and pooling kernels
+    const int T = c->geom.tokens();
+    const int M = n * T;
     const int D = c->geom.hidden, F = c->geom.mlp, NL = c->geom.layers;  // the geometry of the loaded weights
     // The epilogues leave the LayerNorm partial planes from their interior-tile code only, and at a width that is no
     // multiple of the 256-column tile (384) the last column tile of every row panel is no interior tile: its two slices
@@ -156,7 +160,23 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     const int zigzag = c->zigzag;  // 0 off, 1 every kernel alternates, 2 only the attention walks backwards
     int dir = 0;
     auto next_dir = [&]() { if (zigzag == 1) dir ^= 1; return dir; };
-    {
+    if (t50) {
+        // patch 32: the patch-embed GEMM leaves f32 [n * 49, D] in the qkv buffer (dead until layer 0; 196 D n bytes of its
+        // 300 D n), embed_rows_t50 adds bias and position rows, rounds once and writes the [CLS] rows in the same launch
+        {
+            Timed t(c, s, KC_GEMM);
+            g.A = patches;
+            g.W = c->patch_w;
+            g.M = n * c->geom.np();
+            g.N = D;
+            g.K = c->geom.patch_dim();
+            g.outf = (float*)c->qkv.p;
+            g.ldf = D;
+            HIP_TRY(c, launch_gemm(EPI_F32, g, s, c->gemm_variant));
+        }
+        Timed t(c, s, KC_LN);
+        HIP_TRY(c, launch_embed_rows_t50((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
+    } else {
         Timed t(c, s, KC_GEMM);
         g.A = patches;
         g.W = c->patch_w;
@@ -174,7 +194,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         HIP_TRY(c, launch_gemm(EPI_PATCH, g, s, c->gemm_variant));
     }
     const GemmArgs patch_args = g;
-    {
+    if (!t50) {
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, D, s));
     }
@@ -208,7 +228,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         // in the canonical order: the first folded LayerNorm needs neither planes nor another pass over x
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_pre_ln(c->x.p, c->pre_g, c->pre_b, M, D, c->ln_eps, (float*)c->stats.p, s));
-    } else if (planes && gemm_runs_256(patch_args, c->gemm_variant)) {
+    } else if (!t50 && planes && gemm_runs_256(patch_args, c->gemm_variant)) {  // (patch 32: no planes from the f32 epilogue; the canonical pass below gives the same bits)
         // first LayerNorm of the pass: the patch-embed epilogue left the partial sums of every token row an INTERIOR tile
         // wrote (patch rows [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th
         // row) and the rows of the ragged last tile take the stand-alone kernel, same canonical order
@@ -249,13 +269,18 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0;
         {
             Timed t(c, s, KC_ATTN);
-            HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
-                                        pruned ? pool_token / 32 : -1, zigzag == 2 ? true : next_dir() != 0));
+            if (t50) {  // exact kernel only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
+                if (zigzag != 2) next_dir();
+                HIP_TRY(c, launch_attention_t50(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
+            } else {
+                HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
+                                            pruned ? pool_token / 32 : -1, zigzag == 2 ? true : next_dir() != 0));
+            }
         }
         if (pruned) {
             bf16_t* att_p = (bf16_t*)c->hbuf.p;          // [n, D] gathered attention rows
             bf16_t* x_p = att_p + (size_t)n * D;      // [n, D] gathered residual rows (hbuf holds rows x D: n x 197 of them)
-            const size_t rowb = (size_t)D * 2, pitch = (size_t)VIT_T * rowb;
+            const size_t rowb = (size_t)D * 2, pitch = (size_t)T * rowb;
             {
                 Timed t(c, s, KC_POOL);
                 HIP_TRY(c, hipMemcpy2DAsync(att_p, rowb, (const char*)c->att.p + (size_t)pool_token * rowb, pitch, rowb, n, hipMemcpyDeviceToDevice, s));
@@ -294,7 +319,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             g = GemmArgs{};
             g.A = c->att.p; g.W = L.o_w; g.M = M; g.N = D; g.K = D;
             g.bias = L.o_b; g.out = c->x.p; g.res = c->x.p; g.ldo = D;
-            g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
+            g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * T;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(res_epi, g, s, c->gemm_variant));
         }
@@ -324,7 +349,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             g = GemmArgs{};
             g.A = c->mlp.p; g.W = L.fc2_w; g.M = M; g.N = D; g.K = F;
             g.bias = L.fc2_b; g.out = c->x.p; g.res = c->x.p; g.ldo = D;
-            g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
+            g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * T;
             g.reverse_m = next_dir();
             HIP_TRY(c, launch_gemm(last ? EPI_BIAS_RES : res_epi, g, s, c->gemm_variant));
         }
@@ -337,7 +362,8 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         if ((r = ensure(c, c->projf, (size_t)c->chunk * P * sizeof(float)))) return r;
         {
             Timed t(c, s, KC_POOL);
-            HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
+            if (t50) HIP_TRY(c, launch_pool_ln_t50(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
+            else HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
         }
         {
             Timed t(c, s, KC_GEMM);
@@ -352,7 +378,8 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     }
     {
         Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
+        if (t50) HIP_TRY(c, launch_pool_t50(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
+        else HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
     }
     return MME_OK;
 }
@@ -388,6 +415,8 @@ struct K1Plan {
 };
 // LDS budget of classes 0 and 1
 constexpr int kHLds = 32 * 1024;
+// bf16 values of one crop's patch matrix: 196 x 768 = 49 x 3072
+constexpr size_t CROP_VALUES = (size_t)VIT_NP * VIT_PATCH_DIM;
 
 // The bands of crop i's horizontal pass: source rows [first_row, first_row + nrows) of row_bytes each, whose table takes
 // tab_lds bytes of LDS when it rides beside the band.  Picks the class and appends the bands to it.
@@ -604,7 +633,7 @@ void mme_destroy(mme_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (void* p : c->allocs) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf};
+    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->patches32};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->lut) (void)hipFree(c->lut);
@@ -621,7 +650,7 @@ const char* mme_last_error(const mme_ctx* c) { return c ? c->err.c_str() : g_cre
 
 int mme_vit_geometry(mme_ctx* c, int32_t out[6]) {
     if (!c || !out) return fail(c, MME_E_ARG, "mme_vit_geometry: null argument");
-    const int32_t g[6] = {VIT_IMG, VIT_PATCH, c->geom.hidden, c->geom.layers, c->geom.heads, c->geom.mlp};
+    const int32_t g[6] = {VIT_IMG, c->geom.patch, c->geom.hidden, c->geom.layers, c->geom.heads, c->geom.mlp};
     for (int i = 0; i < 6; ++i) out[i] = g[i];
     return MME_OK;
 }
@@ -717,6 +746,7 @@ int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const 
     if (!c) return MME_E_ARG;
     if (!qkv || !out || !redone) return fail(c, MME_E_ARG, "mme_attention_apply: null argument");
     if (kind != 0 && kind != 1) return fail(c, MME_E_ARG, "mme_attention_apply: kind %d (0 = ViT/16 at the context's geometry, 1 = tile-ViT)", kind);
+    if (kind == 0 && c->geom.t50()) return fail(c, MME_E_ARG, "mme_attention_apply: kind 0 is the 197-token kernel and the context holds a patch-32 tower (50 tokens); mme_vit32_apply op 2 launches its kernel");
     const int n_max = kind == 0 ? 1 << 20 : 4096;
     if (n <= 0 || n > n_max) return fail(c, MME_E_ARG, "mme_attention_apply: n = %d outside 1..%d", n, n_max);
     if (kind == 0) {
@@ -774,12 +804,22 @@ int mme_preprocess(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const in
     if (n == 0) return MME_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
+    // patch 32: K1 writes its patch-16 matrix into the staging buffer of one chunk, the retile kernel permutes it into the
+    // caller's [n * 49, 3072]; the bytes per crop are the same
+    const bool t50 = c->geom.t50();
+    int r;
+    if (t50 && (r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
     // the crop tables of successive chunks reuse one device buffer: chunk so that stays ordered
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
         if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));
-        int r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_PATCH_DIM, s);
+        bf16_t* dst = (bf16_t*)patches + (size_t)s0 * CROP_VALUES;
+        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, t50 ? (bf16_t*)c->patches.p : dst, s);
         if (r) return r;
+        if (t50) {
+            Timed t(c, s, KC_PRE);
+            HIP_TRY(c, launch_retile_p32(c->patches.p, dst, m, s));
+        }
     }
     return MME_OK;
 }
@@ -788,7 +828,7 @@ int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, 
     if (!c) return MME_E_ARG;
     if (!c->loaded) return fail(c, MME_E_STATE, "mme_vit_forward: call mme_load_vit first");
     if (n < 0 || (n > 0 && !patches)) return fail(c, MME_E_ARG, "mme_vit_forward: null patches or n<0");
-    if (pool_token < 0 || pool_token >= VIT_T) return fail(c, MME_E_ARG, "mme_vit_forward: pool_token %d outside 0..%d", pool_token, VIT_T - 1);
+    if (pool_token < 0 || pool_token >= c->geom.tokens()) return fail(c, MME_E_ARG, "mme_vit_forward: pool_token %d outside 0..%d", pool_token, c->geom.tokens() - 1);
     if (n == 0) return MME_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     int r = ensure_workspace(c);
@@ -796,7 +836,7 @@ int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, 
     hipStream_t s = (hipStream_t)stream;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * VIT_NP * VIT_PATCH_DIM, m, pool_token,
+        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * CROP_VALUES, m, pool_token,
                           emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
                           emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
         if (r) return r;
@@ -809,19 +849,25 @@ int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t
     if (!c) return MME_E_ARG;
     if (!c->loaded) return fail(c, MME_E_STATE, "mme_embed: call mme_load_vit first");
     if (n < 0 || (n > 0 && (!pix || !offs || !hw))) return fail(c, MME_E_ARG, "mme_embed: null argument or n<0");
-    if (pool_token < 0 || pool_token >= VIT_T) return fail(c, MME_E_ARG, "mme_embed: pool_token %d outside 0..%d", pool_token, VIT_T - 1);
+    if (pool_token < 0 || pool_token >= c->geom.tokens()) return fail(c, MME_E_ARG, "mme_embed: pool_token %d outside 0..%d", pool_token, c->geom.tokens() - 1);
     if (n == 0) return MME_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     int r = ensure_workspace(c);
     if (r) return r;
-    if ((r = ensure(c, c->patches, (size_t)c->chunk * VIT_NP * VIT_PATCH_DIM * 2))) return r;
+    if ((r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
+    const bool t50 = c->geom.t50();  // patch 32: K1 -> retile -> pass
+    if (t50 && (r = ensure(c, c->patches32, (size_t)c->chunk * CROP_VALUES * 2))) return r;
     hipStream_t s = (hipStream_t)stream;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
         if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));  // crop tables are reused per chunk
         r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)c->patches.p, s);
         if (r) return r;
-        r = forward_chunk(c, (const bf16_t*)c->patches.p, m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
+        if (t50) {
+            Timed t(c, s, KC_PRE);
+            HIP_TRY(c, launch_retile_p32(c->patches.p, c->patches32.p, m, s));
+        }
+        r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : c->patches.p), m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
                           emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
         if (r) return r;
     }
@@ -1490,6 +1536,47 @@ int mme_clip_apply(mme_ctx* c, int op, const mme_clip_apply_args* a, void* strea
         case 2: HIP_TRY(c, launch_pre_ln(a->x, a->gamma, a->beta, a->rows, a->d, a->eps, a->stats, s)); break;
         case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->B, a->tok, a->d, a->eps, a->y, s)); break;
         default: HIP_TRY(c, launch_l2_rows(a->xf, a->rows, a->p, a->y_f32, a->y_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+// the kernels a patch-32 tower adds, one launch each (tests/test_gpu_vit32.py)
+int mme_vit32_apply(mme_ctx* c, int op, const mme_vit32_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_vit32_apply: null argument");
+    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_vit32_apply: op %d outside 0..4", op);
+    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "mme_vit32_apply: n = %d outside 0..2^20", a->n);
+    const char* bad = nullptr;
+    if (op == 0) {
+        if (!vec(a->src) || !vec(a->dst)) bad = "src and dst non-null and 16-byte aligned";
+        else if (a->src == a->dst) bad = "src != dst (the permutation is not in place)";
+    } else if (op == 2) {
+        if (a->heads != 6 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_vit32_apply: op 2 is built for heads == 6, 12 and 16 (heads = %d)", a->heads);
+        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv and out non-null and 16-byte aligned";
+        else if (a->only_block < -1 || a->only_block > 1) bad = "only_block in -1..1";
+    } else {
+        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_vit32_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
+        if (op == 1) {
+            if (!vec(a->acc) || !vec(a->bias) || !vec(a->pos) || !vec(a->cls) || !vec(a->x)) bad = "acc, bias, pos, cls, x non-null and 16-byte aligned";
+        } else {
+            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
+            else if (a->tok < 0 || a->tok > 49) bad = "0 <= tok <= 49";
+            else if (op == 3 && !vec(a->y)) bad = "y non-null and 16-byte aligned";
+            else if (op == 4 && !a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
+            else if (op == 4 && (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16))) bad = "emb_f32 and emb_bf16 16-byte aligned";
+        }
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_vit32_apply: op %d needs %s", op, bad);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    switch (op) {
+        case 0: HIP_TRY(c, launch_retile_p32(a->src, a->dst, a->n, s)); break;
+        case 1: HIP_TRY(c, launch_embed_rows_t50(a->acc, a->bias, a->pos, a->cls, a->x, a->n, a->d, s)); break;
+        case 2: HIP_TRY(c, launch_attention_t50(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
+        case 3: HIP_TRY(c, launch_pool_ln_t50(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->y, s)); break;
+        default: HIP_TRY(c, launch_pool_t50(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;

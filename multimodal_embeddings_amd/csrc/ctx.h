@@ -26,11 +26,18 @@ struct LayerDev {
     float *qkv_cs, *qkv_bf, *fc1_cs, *fc1_bf;
 };
 
-// The ViT/16 @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
-// Supported set (validate_vit_weights, weight_load.hip): image 224, patch 16, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
+// The ViT @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
+// Supported set (validate_vit_weights, weight_load.hip): image 224, patch 16 or 32, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
 // <= 8192, 1..64 layers.
+// Patch 16 (197 tokens, the compile-time geometry of common.h) or patch 32 (50 tokens: patch32.hip, attention_t50.hip).
 struct VitGeom {
     int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
+    int patch = VIT_PATCH;
+    int grid() const { return VIT_IMG / patch; }
+    int np() const { return grid() * grid(); }             // patches per crop: 196 or 49
+    int tokens() const { return np() + 1; }                // 197 or 50
+    int patch_dim() const { return 3 * patch * patch; }    // 768 or 3072; np() * patch_dim() is 150 528 for both
+    bool t50() const { return patch == 32; }
 };
 
 enum KClass { KC_PRE = 0, KC_GEMM = 1, KC_LN = 2, KC_ATTN = 3, KC_POOL = 4, KC_COS = 5, KC_PAGE = 6, KC_CLUSTER = 7, KC_NEIGH = 8, KC_COMM = 9 };
@@ -71,13 +78,14 @@ struct mme_ctx {
     NormAffine norm_aff{};  // the same mapping as one fma per value where that is bit-exact after the bf16 rounding (set_lut)
     int resize_rule = MME_RESIZE_FIT_PAD;  // mme_set_resize_rule: how mme_preprocess / mme_embed make 224 x 224 pixels; no load changes it
     // workspace (sized for `chunk` crops)
-    int ws_chunk = 0, ws_hidden = 0, ws_mlp = 0;  // what the workspace below was sized for
+    int ws_chunk = 0, ws_hidden = 0, ws_mlp = 0, ws_tokens = 0;  // what the workspace below was sized for
     DevBuf attn_guard;      // int[64]: one guard word per layer of a pass (attention.hip, FAST form)
     DevBuf attn_apply;      // mme_attention_apply: its own guard word (int 0), the tile counts from int 16 on
     bool prune_last = false;  // mme_set_forward_pruning
     int zigzag = 1;           // forward_chunk: 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
+    DevBuf patches32;      // patch 32: the retiled [chunk * 49, 3072] matrix of mme_embed (`patches` stages K1's patch-16 matrix)
     DevBuf pooled, projf;  // CLIP tail: bf16 [chunk, hidden] post_layernorm rows, f32 [chunk, proj_dim] projected rows
     // host staging for crop tables
     std::vector<CropDesc> h_crops;

@@ -277,6 +277,20 @@ hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads,
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
                                    float* y_f32, hipStream_t s);
 
+// ---- ViT/32 @224 image towers (patch32.hip, attention_t50.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64
+// K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-32 matrix [n * 49, 3072] in conv order (c, ky, kx): a pure copy
+hipError_t launch_retile_p32(const void* patches16, void* patches32, int n, hipStream_t s);
+// acc f32 [n * 49, d] (the patch-embed GEMM under EPI_F32) -> x[b*50 + 1 + p] = bf16((acc + bias) + pos[1 + p]),
+// x[b*50] = bf16(cls + pos[0]); d = 384, 768 or 1024
+hipError_t launch_embed_rows_t50(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int d, hipStream_t s);
+// attention, T = 50, dh = 64, heads = 6, 12 or 16: qkv [n*50, 3*64*heads] (Q pre-scaled) -> out [n*50, 64*heads], exact row
+// maximum; only_block = 0 or 1: that query block of 32 only
+hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
+// launch_pool_ln / launch_pool on row b*50 + tok (0 <= tok <= 49)
+hipError_t launch_pool_ln_t50(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s);
+hipError_t launch_pool_t50(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
+                           hipStream_t s);
+
 // ---- device-side weight preparation (weight_prep.hip).  dt = MME_DT_* (include/mme.h); sources are device addresses,
 // 16-byte aligned, of elements of that type.
 // `count` elements (a multiple of 8) -> f32 table or bf16 (round to nearest even) at dst (16-byte aligned);

@@ -215,7 +215,7 @@ int DevPrep::zeros(size_t n, float** dst) {
     return MME_OK;
 }
 
-// ---- ViT/16 --------------------------------------------------------------------------------------------------------------
+// ---- ViT/16, ViT/32 --------------------------------------------------------------------------------------------------------------
 namespace {
 
 // argument checks of both ViT loaders (the messages of both name the f32 loader): the geometry against the supported
@@ -224,7 +224,7 @@ int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who =
     if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
     // every refusal names the field, the value found and what is supported
     if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
-    if (w->patch_size != VIT_PATCH) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: %d", who, w->patch_size, VIT_PATCH);
+    if (w->patch_size != 16 && w->patch_size != 32) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 16, 32", who, w->patch_size);
     if (!vit_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 384, 768, 1024", who, w->hidden);
     if (w->heads * VIT_DH != w->hidden)
         return fail(c, MME_E_ARG, "%s: heads = %d at hidden = %d; supported: heads of %d, heads = hidden / %d = %d", who, w->heads, w->hidden, VIT_DH, VIT_DH,
@@ -252,7 +252,7 @@ int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     if (c->vit_alloc_hi > c->vit_alloc_lo) HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
     // exactly the image tower's buffers; a text tower loaded behind them keeps its own, its range moves down with them
     release_alloc_range(c, c->vit_alloc_lo, c->vit_alloc_hi, c->text_alloc_lo, c->text_alloc_hi);
-    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp};
+    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp, w->patch_size};
     c->ln_eps = w->ln_eps;
     c->layer.assign((size_t)w->layers, LayerDev{});
     // a plain ViT until a CLIP load says otherwise (load_clip sets these after this call; their buffers were freed above)
@@ -273,9 +273,10 @@ void end_vit_load(mme_ctx* c, bool ok) {
 template <class Fn>
 void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&& f) {
     const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
+    const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size};
     f(w.cls_token, D);
-    f(w.pos_emb, (size_t)VIT_T * D);
-    f(w.patch_w, D * VIT_PATCH_DIM);
+    f(w.pos_emb, (size_t)vg.tokens() * D);
+    f(w.patch_w, D * vg.patch_dim());
     if (w.patch_b) f(w.patch_b, D);  // CLIP: no bias on the patch projection
     f(w.lnf_g, D);
     f(w.lnf_b, D);
@@ -298,17 +299,18 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
     int r;
     const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
     const size_t rD[3] = {D, D, D}, rF[1] = {F};
+    const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size};  // pos [197 | 50, D], patch_w [D, 768 | 3072]
     auto plain = [&](const float* src, size_t n, float** dst) { return p.table(src, n, 1.f, false, dst); };
     auto plain_bf16 = [&](const float* src, const size_t* rows, size_t cols, bf16_t** dst) {
         const void* s[1] = {src};
         return p.bf16(s, rows, 1, cols, 1.f, false, dst);
     };
     if ((r = plain(w.cls_token, D, &c->cls))) return r;
-    if ((r = plain(w.pos_emb, (size_t)VIT_T * D, &c->pos))) return r;
+    if ((r = plain(w.pos_emb, (size_t)vg.tokens() * D, &c->pos))) return r;
     if ((r = w.patch_b ? plain(w.patch_b, D, &c->patch_b) : p.zeros(D, &c->patch_b))) return r;  // CLIP: a zero table
     if ((r = plain(w.lnf_g, D, &c->lnf_g))) return r;
     if ((r = plain(w.lnf_b, D, &c->lnf_b))) return r;
-    if ((r = plain_bf16(w.patch_w, rD, VIT_PATCH_DIM, &c->patch_w))) return r;
+    if ((r = plain_bf16(w.patch_w, rD, (size_t)vg.patch_dim(), &c->patch_w))) return r;
     // The attention kernel takes its scores in log2 units straight from the matrix pipe (attention.hip, PRESCALED):
     // dh^-0.5 * log2(e) is folded into the query projection here, once, BEFORE the rounding to bf16 that the preparation
     // applies anyway -- softmax(q.k / 8) = exp2(q'.k - c) / sum with q' = (W_q' x + b_q'), W_q' = sc W_q, b_q' = sc b_q.

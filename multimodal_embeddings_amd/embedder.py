@@ -118,11 +118,11 @@ class RegionEmbedder:
         preprocessor_config.json) is read once (checkpoint.read_checkpoint), loaded into every context in the file's own dtype
         and its image_mean / image_std applied; `self.checkpoint` keeps it.  Any other name is never fetched: the encoder runs
         on seeded synthetic weights with one WARNING, or raises with `allow_synthetic=False`.  `weights=` (a dict) wins.
-        `encoder`: "vit_b16" (exactly ViT-B/16), "vit" (any ViT/16 @224 of the supported family -- ViT-S, -B, -L widths,
+        `encoder`: "vit_b16" (exactly ViT-B/16), "vit" (any ViT/16 or ViT/32 @224 of the supported family -- ViT-S, -B, -L widths,
         weights.SUPPORTED_VIT: a checkpoint directory brings its own geometry in config.json, seeded weights take
-        `geometry=`, e.g. weights.VIT_L16, a `weights=` dict is sized by its tensors), "clip" (a CLIP ViT/16 image tower of
+        `geometry=`, e.g. weights.VIT_L16 or weights.VIT_B32, a `weights=` dict is sized by its tensors), "clip" (a CLIP ViT/16 or ViT/32 image tower of
         the same family: pre-LN, QuickGELU or GELU, visual projection; a checkpoint directory of CLIPVisionModel[WithProjection]
-        or a whole CLIPModel, seeded weights at `geometry=` a weights.CLIPGeometry, default CLIP-B/16, or a `weights=` dict in
+        or a whole CLIPModel, seeded weights at `geometry=` a weights.CLIPGeometry (weights.CLIP_B32 is clip-vit-base-patch32), default CLIP-B/16, or a `weights=` dict in
         transformers' names, whose activation `geometry=` names when it is not QuickGELU) or "mllama_tiles".
         `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim).
         `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
@@ -240,7 +240,8 @@ class RegionEmbedder:
                 e.set_forward_pruning(True)
         if pool not in ("cls", "last"):
             raise ValueError("pool must be 'cls' or 'last'")
-        self.pool_token = 0 if pool == "cls" else 196  # the last of the 197 tokens (the same at every width)
+        # the last token: 196 of the 197 at patch 16 (the same at every width), 49 of the 50 at patch 32
+        self.pool_token = 0 if pool == "cls" else (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1)
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
         self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
         self._group_crops = 16 * config.BATCH_SIZE

@@ -32,7 +32,7 @@ _MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 @dataclass(frozen=True)
 class ViTGeometry:
-    """A ViT/16 @224 encoder; the defaults are ViT-B/16 (transformers ViTConfig defaults).  What the engine runs is
+    """A ViT/16 or ViT/32 @224 encoder (197 or 50 tokens); the defaults are ViT-B/16 (transformers ViTConfig defaults).  What the engine runs is
     `SUPPORTED_VIT` below (checked by `check_vit_geometry`, and again by the library when the weights are loaded)."""
 
     image_size: int = 224
@@ -68,9 +68,10 @@ class ViTGeometry:
 VIT_B16 = ViTGeometry()
 VIT_S16 = ViTGeometry(hidden_size=384, num_layers=12, num_heads=6, intermediate_size=1536)
 VIT_L16 = ViTGeometry(hidden_size=1024, num_layers=24, num_heads=16, intermediate_size=4096)
+VIT_B32 = ViTGeometry(patch_size=32)  # 7 x 7 patches of 32 x 32, 50 tokens (google/vit-base-patch32-224-in21k)
 
 # the geometries the engine is built for (csrc/common.h, csrc/weight_load.hip validate_vit_weights)
-SUPPORTED_VIT = {"image_size": (224,), "patch_size": (16,), "num_channels": (3,), "hidden_size": (384, 768, 1024), "head_dim": (64,),
+SUPPORTED_VIT = {"image_size": (224,), "patch_size": (16, 32), "num_channels": (3,), "hidden_size": (384, 768, 1024), "head_dim": (64,),
                  "intermediate_size": "a multiple of 64 up to 8192", "num_layers": "1..64"}
 
 
@@ -120,7 +121,7 @@ def infer_vit_geometry(w: dict, eps: float = 1e-12) -> ViTGeometry:
 # ---- CLIP ViT/16 image towers ---------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class CLIPGeometry(ViTGeometry):
-    """A CLIP image tower at the engine's ViT/16 @224 geometry (transformers CLIPVisionConfig): the ViT fields, with
+    """A CLIP image tower at the engine's ViT/16 or ViT/32 @224 geometry (transformers CLIPVisionConfig): the ViT fields, with
     layer_norm_eps 1e-5, plus the width of the shared image / text space (`projection_dim`; None: no visual_projection,
     the embedding is the post_layernorm row) and the MLP activation ("quick_gelu": OpenAI weights, "gelu": LAION
     conversions).  The defaults are clip-vit-base-patch16."""
@@ -135,6 +136,7 @@ class CLIPGeometry(ViTGeometry):
 
 
 CLIP_B16 = CLIPGeometry()
+CLIP_B32 = CLIPGeometry(patch_size=32)  # clip-vit-base-patch32: 768 x 12, MLP 3072, projection 512, quick_gelu, 50 tokens
 CLIP_ACTS = ("gelu", "quick_gelu")  # include/mme.h mme_clip_weights.act: the index
 
 
