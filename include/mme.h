@@ -598,6 +598,56 @@ int mme_neighbours(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const in
  * device's own decision.  Results are identical. */
 int mme_set_neighbour_mode(mme_ctx* ctx, int mode);
 
+/* ---- K14: near-duplicate groups ------------------------------------------------
+ * The connected components of the graph whose edges are the unordered pairs {i, j}, i < j, of rows of the L2-normalised
+ * bf16 table emb_dev[N, d] with group_dev[i] != group_dev[j] (K12's group ids; NULL = every pair is admissible) and an
+ * f32-accumulated cosine s_ij >= min_sim.  Against the float64 dot product s64 of the same bf16 rows, with
+ * delta = 2 * d * 2^-24: s64 >= min_sim + delta is an edge, s64 < min_sim - delta is none, in between either.
+ *
+ * The state is caller-owned device memory behind one struct of pointers; all four calls enqueue on `stream` and never wait
+ * for the device (the cosine blocks go through the K12 workspace, which grows on first use).
+ *   parent      int32[N]   union-find forest, parent[i] <= i
+ *   degree      int32[N]   edges at the row: an OUTPUT as it stands after the scans
+ *   best        uint64[N]  most similar partner among the row's edges as a packed key (mme_duplicates_finish unpacks it)
+ *   page_pairs  int32[P,P] or NULL: edges between page p and page q (page ids from page_of_dev; ids outside 0..P-1 are
+ *               skipped), symmetric, within-page edges on the diagonal.  1 <= P <= 4096
+ *   edges       int32[edge_cap,2] (i < j) and edge_sim float[edge_cap], or NULL with edge_cap = 0: the edge list, in
+ *               arbitrary order.  A list that is full stays a valid, duplicate-free subset of the edges
+ *   counters    int64[2]   [0] edges found (exact, also past edge_cap), [1] edges written to the list (<= edge_cap)
+ * mme_duplicates_init   parent[i] = i, everything else zero.
+ * mme_duplicates_scan   the pairs (i, j) with row0 <= i < row0 + nrows and i < j < N, accumulated into the state: scans over
+ *                       disjoint row ranges that cover [0, N) are one whole run, in any order (nrows = 0 does nothing).
+ *                       page_of_dev int32[N] is read only when the state has page_pairs.
+ * mme_duplicates_merge  dst <- dst and src, two states over the same N rows (row shards of several GPUs, after an all-gather
+ *                       of their states): the forests are united, degrees, page pairs and counters[0] add, best takes the
+ *                       better partner.  Edge lists are NOT merged: dst's list and counters[1] stay as they are.
+ * mme_duplicates_finish labels_dev int32[N]: the smallest row index of the row's component (a singleton labels itself);
+ *                       best_idx_dev int32[N] / best_sim_dev float[N]: the most similar partner, the lower index among
+ *                       bit-equal values, (-1, 0) where degree is 0; summary_dev int64[4]: edges, groups of >= 2 rows,
+ *                       rows in such groups, rows of the largest such group (0 without one).  The state is not changed
+ *                       and may be scanned further.
+ * MME_E_ARG, with the field and the value in mme_last_error, nothing enqueued, state and context usable: d % 64 != 0, a
+ * null pointer, rows outside [0, N], page_pairs with P outside 1..4096 or (scan) without page_of_dev, a NaN min_sim, a
+ * negative edge_cap, merge of states of which one has page_pairs and the other has not.
+ * Profiling classes: the GEMM counts as "cosine", dup_scan and merge as "neighbours", finish as "cluster". */
+typedef struct mme_dup_state {
+    int32_t* parent;
+    int32_t* degree;
+    uint64_t* best;
+    int32_t* page_pairs;
+    int32_t* edges;
+    float* edge_sim;
+    int64_t* counters;
+    int64_t edge_cap;
+    int32_t P;
+} mme_dup_state;
+int mme_duplicates_init(mme_ctx* ctx, const mme_dup_state* state, int N, void* stream);
+int mme_duplicates_scan(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* group_dev, const int32_t* page_of_dev,
+                        float min_sim, int row0, int nrows, const mme_dup_state* state, void* stream);
+int mme_duplicates_merge(mme_ctx* ctx, const mme_dup_state* dst, const mme_dup_state* src, int N, void* stream);
+int mme_duplicates_finish(mme_ctx* ctx, const mme_dup_state* state, int N, int32_t* labels_dev, int32_t* best_idx_dev,
+                          float* best_sim_dev, int64_t* summary_dev, void* stream);
+
 /* Diagnostic: time one MFMA GEMM shape on random bf16 data (allocates its own operands;
  * synchronous).  epilogue 0 bias, 1 bias+GELU, 2 bias+residual, 3 patch-embed, 4 f32 out;
  * variant as mme_set_gemm_variant. */

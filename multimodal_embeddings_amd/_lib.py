@@ -122,6 +122,13 @@ class _WeightPrepApplyArgs(C.Structure):  # mme_weight_prep_apply_args
     ]
 
 
+class _DupState(C.Structure):  # mme_dup_state
+    _fields_ = [
+        ("parent", C.c_void_p), ("degree", C.c_void_p), ("best", C.c_void_p), ("page_pairs", C.c_void_p), ("edges", C.c_void_p),
+        ("edge_sim", C.c_void_p), ("counters", C.c_void_p), ("edge_cap", C.c_int64), ("P", C.c_int32),
+    ]
+
+
 EXPORTS = {
     "mme_abi_version": (C.c_int, []),
     "mme_is_diag_build": (C.c_int, []),
@@ -176,6 +183,11 @@ EXPORTS = {
     "mme_neighbours": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_set_neighbour_mode": (C.c_int, [C.c_void_p, C.c_int]),
+    "mme_duplicates_init": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.c_int, C.c_void_p]),
+    "mme_duplicates_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int,
+                                      C.POINTER(_DupState), C.c_void_p]),
+    "mme_duplicates_merge": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.POINTER(_DupState), C.c_int, C.c_void_p]),
+    "mme_duplicates_finish": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mme_gemm_apply": (C.c_int, [C.c_void_p, C.POINTER(_GemmApplyArgs), C.POINTER(C.c_int32), C.c_void_p]),
@@ -1067,6 +1079,93 @@ class Engine:
                                             int(fetch), int(top_n), int(bool(keep_self)), float(min_sim), float(max_sim),
                                             idx.data_ptr(), sim.data_ptr(), self._stream()), "mme_neighbours")
         return idx, sim
+
+    # ---- K14 near-duplicate groups (mme.h, mme_duplicates_*) ----
+    def _dup_struct(self, state):
+        st = _DupState()
+        for f in ("parent", "degree", "best", "page_pairs", "edges", "edge_sim", "counters"):
+            setattr(st, f, self._ptr(state.get(f)))
+        st.edge_cap, st.P = int(state.get("edge_cap", 0)), int(state.get("pages", 0))
+        return st
+
+    def _i32_rows(self, v, N, what):
+        """optional int32 [N] control vector (CUDA tensor or array) on this engine's device"""
+        if v is None:
+            return None
+        t = self.torch
+        g = v if isinstance(v, t.Tensor) else t.from_numpy(np.ascontiguousarray(v, dtype=np.int32))
+        g = g.to(device=t.device(f"cuda:{self.device}"), dtype=t.int32).contiguous()
+        if g.numel() != N:
+            raise MmeError(f"duplicates: {what} must have one id per row")
+        return g
+
+    def duplicates_init(self, N, pages=0, edge_cap=0):
+        """A fresh state for N rows: a dict of CUDA tensors `parent`, `degree` int32 [N], `best` int64 [N] (packed keys),
+        `counters` int64 [2] (edges found, edges written), `page_pairs` int32 [pages, pages] when pages > 0, `edges`
+        int32 [edge_cap, 2] and `edge_sim` float32 [edge_cap] when edge_cap > 0; plus `N`, `pages`, `edge_cap`."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        N, pages, edge_cap = int(N), int(pages), int(edge_cap)
+        state = {"N": N, "pages": pages, "edge_cap": edge_cap,
+                 "parent": t.empty(max(N, 1), dtype=t.int32, device=dev), "degree": t.empty(max(N, 1), dtype=t.int32, device=dev),
+                 "best": t.empty(max(N, 1), dtype=t.int64, device=dev), "counters": t.empty(2, dtype=t.int64, device=dev)}
+        if pages > 0:
+            state["page_pairs"] = t.empty((pages, pages), dtype=t.int32, device=dev)
+        if edge_cap > 0:
+            state["edges"] = t.zeros((edge_cap, 2), dtype=t.int32, device=dev)
+            state["edge_sim"] = t.zeros(edge_cap, dtype=t.float32, device=dev)
+        self._check(self.lib.mme_duplicates_init(self.h, C.byref(self._dup_struct(state)), N, self._stream()), "mme_duplicates_init")
+        return state
+
+    def duplicates_scan(self, state, emb_bf16, group=None, page_of=None, *, min_sim, row0=0, nrows=None):
+        """Adds the edges (i, j), row0 <= i < row0 + nrows, i < j < N, to `state`.  Scans over disjoint row ranges that
+        cover [0, N) are one whole run, in any order."""
+        t = self.torch
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != t.device(f"cuda:{self.device}"):
+            raise MmeError("duplicates: emb must be a 2-D bfloat16 tensor on this engine's device")
+        N, d = e.shape
+        if N != state["N"]:
+            raise MmeError(f"duplicates: the state was made for {state['N']} rows, emb has {N}")
+        nrows = N - row0 if nrows is None else int(nrows)
+        g, p = self._i32_rows(group, N, "group"), self._i32_rows(page_of, N, "page_of")
+        self._check(self.lib.mme_duplicates_scan(self.h, e.data_ptr(), N, d, self._ptr(g), self._ptr(p), float(min_sim), int(row0), nrows,
+                                                 C.byref(self._dup_struct(state)), self._stream()), "mme_duplicates_scan")
+
+    def duplicates_merge(self, dst, src):
+        """dst <- dst and src (two states over the same rows, e.g. row shards of two GPUs).  Edge lists are not merged."""
+        if dst["N"] != src["N"]:
+            raise MmeError(f"duplicates: merge of states for {dst['N']} and {src['N']} rows")
+        self._check(self.lib.mme_duplicates_merge(self.h, C.byref(self._dup_struct(dst)), C.byref(self._dup_struct(src)), dst["N"], self._stream()),
+                    "mme_duplicates_merge")
+
+    def duplicates_finish(self, state):
+        """The outputs by name, CUDA tensors: labels, degree, best_idx int32 [N], best_sim float32 [N], summary int64 [4]
+        (edges, groups of >= 2 rows, rows in such groups, rows of the largest group), counters int64 [2], and page_pairs /
+        edges / edge_sim where the state has them (edges[:counters[1]] are valid).  The state's own tensors are returned,
+        not copies."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        N = state["N"]
+        out = {"labels": t.empty(N, dtype=t.int32, device=dev), "best_idx": t.empty(N, dtype=t.int32, device=dev),
+               "best_sim": t.empty(N, dtype=t.float32, device=dev), "summary": t.empty(4, dtype=t.int64, device=dev)}
+        self._check(self.lib.mme_duplicates_finish(self.h, C.byref(self._dup_struct(state)), N, self._ptr(out["labels"]) if N else None,
+                                                   self._ptr(out["best_idx"]) if N else None, self._ptr(out["best_sim"]) if N else None,
+                                                   out["summary"].data_ptr(), self._stream()), "mme_duplicates_finish")
+        out["degree"] = state["degree"][:N]
+        out["counters"] = state["counters"]
+        for k in ("page_pairs", "edges", "edge_sim"):
+            if k in state:
+                out[k] = state[k]
+        return out
+
+    def duplicates(self, emb, group=None, page_of=None, pages=0, *, min_sim, rows=None, edge_cap=0):
+        """Near-duplicate groups of the L2-normalised bf16 rows emb[N, d] in one call: init, scan of `rows` = (row0, nrows)
+        (default: all rows), finish.  See duplicates_finish for what comes back."""
+        state = self.duplicates_init(emb.shape[0], pages=pages, edge_cap=edge_cap)
+        row0, nrows = (0, None) if rows is None else rows
+        self.duplicates_scan(state, emb, group, page_of, min_sim=min_sim, row0=row0, nrows=nrows)
+        return self.duplicates_finish(state)
 
     def gemm_bench(self, M, N, K, epilogue=0, variant=0, iters=10):
         """(avg ms, TFLOP/s) for one GEMM shape on random data."""

@@ -4,6 +4,10 @@ Mirrors `create_region_cross_comparison` (deprecated_package/region_compare.py:2
 its HTML / cv2 output (emit JSON instead): the per-region store query
 (:165-170) plus the filter loop (:238-353) run as ONE pass of the K12 kernel
 (`mme_neighbours`: MFMA cosine block + streaming top-k) over every region at once.
+
+`duplicate_groups` answers the question a ranking cannot: which regions are the same thing printed again (a syndicated
+advertisement, a masthead, a reprinted notice) -- the connected components of "cosine >= threshold between regions of
+different pages" over all regions at once (kernel K14, `mme_duplicates_*`), and which pages share such regions.
 """
 from __future__ import annotations
 
@@ -104,4 +108,114 @@ def create_region_cross_comparison(collection, top_n=config.REGION_COMPARE_TOP_N
         os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
         with open(output_path, "w") as fh:
             json.dump({"top_n": top_n, "regions": result}, fh, indent=1)
+    return result
+
+
+def _parent_of(m):
+    return (m or {}).get("parent_image") or (m or {}).get("parent_image_name") or ""
+
+
+def group_table(labels, degree, best_idx, best_sim, ids, metadatas, *, threshold=None, min_size=2, page_pairs=None, image_names=None,
+                edges=None, edge_sim=None, n_edges=None):
+    """The JSON-ready report from K14's arrays; a pure function of its arguments (no GPU).
+
+    labels[i] = smallest row of row i's component, degree[i] = edges at the row, (best_idx, best_sim)[i] = its most similar
+    partner or (-1, 0); ids / metadatas are the rows'.  Components of fewer than `min_size` rows are left out.  Returns
+      {"threshold", "n_regions", "n_edges",
+       "groups": [{"size", "pages": [page names, sorted], "members": [{"id", "parent_image", "type", "area_percentage", "degree",
+                   "best_match": {"id", "score"} or None}, ... in row order]}, ... by size descending, then first member],
+       "page_overlap": {"image_names", "counts"} when page_pairs is given,
+       "edges": {"pairs": [{"a", "b", "score"}, ... sorted by (a, b), a < b as ids], "truncated"} when an edge list is given}
+    n_edges: the number of edges found (default: sum(degree) / 2); an edge list shorter than that is flagged `truncated`."""
+    labels, degree, best_idx = (np.asarray(v).astype(np.int64) for v in (labels, degree, best_idx))
+    best_sim = np.asarray(best_sim, dtype=np.float64)
+    n = len(ids)
+    if not (len(labels) == len(degree) == len(best_idx) == len(best_sim) == len(metadatas) == n):
+        raise ValueError("group_table: labels, degree, best_idx, best_sim, ids and metadatas must have one entry per row")
+    members = {}
+    for r in range(n):
+        members.setdefault(int(labels[r]), []).append(r)
+    groups = []
+    for first, rows in sorted(members.items(), key=lambda kv: (-len(kv[1]), kv[0])):
+        if len(rows) < max(1, int(min_size)):
+            continue
+        out_rows = []
+        for r in rows:
+            m = metadatas[r] or {}
+            b = int(best_idx[r])
+            out_rows.append({"id": ids[r], "parent_image": os.path.basename(_parent_of(m)), "type": m.get("region_type", "unknown"),
+                             "area_percentage": m.get("area_percentage", 0), "degree": int(degree[r]),
+                             "best_match": {"id": ids[b], "score": float(best_sim[r])} if b >= 0 else None})
+        groups.append({"size": len(rows), "pages": sorted({m["parent_image"] for m in out_rows if m["parent_image"]}), "members": out_rows})
+    total = int(degree.sum() // 2) if n_edges is None else int(n_edges)
+    out = {"threshold": None if threshold is None else float(threshold), "n_regions": n, "n_edges": total, "groups": groups}
+    if page_pairs is not None:
+        out["page_overlap"] = {"image_names": list(image_names or []), "counts": np.asarray(page_pairs).astype(np.int64).tolist()}
+    if edges is not None:
+        pairs = []
+        for (a, b), sc in zip(np.asarray(edges).reshape(-1, 2).tolist(), np.asarray(edge_sim, dtype=np.float64).tolist()):
+            x, y = sorted((ids[a], ids[b]))
+            pairs.append({"a": x, "b": y, "score": float(sc)})
+        pairs.sort(key=lambda e: (e["a"], e["b"]))
+        out["edges"] = {"pairs": pairs, "truncated": len(pairs) < total}
+    return out
+
+
+def duplicate_inputs(metadatas, exclude="parent", prefix_length=config.PREFIX_LENGTH):
+    """(group int32[n] or None, page_of int32[n], image_names) of K14 from the rows' metadata; a pure function.
+
+    exclude = "parent": regions of one page are never an edge; "prefix": neither are regions of pages whose file names share
+    their first `prefix_length` characters (scans of one issue); "none": every pair counts.  A row without a parent gets a
+    negative group id of its own and page -1 (not counted in the page overlap)."""
+    if exclude not in ("parent", "prefix", "none"):
+        raise ValueError("exclude must be 'parent', 'prefix' or 'none'")
+    n = len(metadatas)
+    names, page_id, page_of = [], {}, np.empty(n, dtype=np.int32)
+    gid, group = {}, np.empty(n, dtype=np.int32)
+    for r, m in enumerate(metadatas):
+        p = os.path.basename(_parent_of(m))
+        if p and p not in page_id:
+            page_id[p] = len(names)
+            names.append(p)
+        page_of[r] = page_id[p] if p else -1
+        key = p if exclude == "parent" else p[: min(int(prefix_length), len(p))]
+        group[r] = gid.setdefault(key, len(gid)) if key else -(r + 1)
+    return (None if exclude == "none" else group), page_of, names
+
+
+def duplicate_groups(collection, threshold, *, exclude="parent", prefix_length=config.PREFIX_LENGTH, min_size=2, max_edges=0,
+                     engine: Engine | None = None):
+    """Groups of near-duplicate regions: the connected components of "cosine >= threshold" between the regions of the
+    collection (`where={"is_region": ...}`, rows without an embedding left out), pairs chosen by `exclude` (duplicate_inputs)
+    never counting.  One pass of kernel K14 over all regions; returns group_table's dict.
+
+    `threshold` has no default: the right value belongs to the encoder.  `page_overlap` counts, per pair of pages, the edges
+    between them (left out beyond 4096 pages); `max_edges` > 0 adds the edges themselves, up to that many."""
+    all_entries = collection.get(include=["metadatas", "embeddings", "documents"], where={"is_region": {"$eq": True}})
+    have = [r for r, e in enumerate((all_entries or {}).get("embeddings") or []) if e is not None and len(e) > 0]
+    if not have:
+        logger.warning("No regions found in the database. Make sure regions have been processed first.")
+        return group_table([], [], [], [], [], [], threshold=threshold, min_size=min_size)
+    ids = [all_entries["ids"][r] for r in have]
+    metas = [all_entries["metadatas"][r] for r in have]
+    engine = engine or default_engine()
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
+    group, page_of, names = duplicate_inputs(metas, exclude, prefix_length)
+    pages = len(names) if 1 <= len(names) <= 4096 else 0
+    res = engine.duplicates(emb, group, page_of if pages else None, pages, min_sim=float(threshold), edge_cap=int(max_edges))
+    host = {k: v.cpu().numpy() for k, v in res.items()}
+    written = int(host["counters"][1])
+    return group_table(host["labels"], host["degree"], host["best_idx"], host["best_sim"], ids, metas, threshold=threshold, min_size=min_size,
+                       page_pairs=host.get("page_pairs"), image_names=names if pages else None,
+                       edges=host["edges"][:written] if max_edges > 0 else None, edge_sim=host["edge_sim"][:written] if max_edges > 0 else None,
+                       n_edges=int(host["counters"][0]))
+
+
+def create_duplicate_report(collection, threshold, output_path=None, **kwargs):
+    """duplicate_groups, written as one JSON document when `output_path` is given (as create_region_cross_comparison)."""
+    result = duplicate_groups(collection, threshold, **kwargs)
+    if output_path:
+        os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+        with open(output_path, "w") as fh:
+            json.dump(result, fh, indent=1)
     return result
