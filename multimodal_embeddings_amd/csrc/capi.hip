@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "ctx.h"
+#include "encoder_pass.h"
 
 namespace {
 
@@ -64,7 +64,6 @@ int ensure_workspace(mme_ctx* c) {
     if ((r = ensure(c, c->mlp, rows * F * 2))) return r;
     if ((r = ensure(c, c->stats, rows * 2 * sizeof(float)))) return r;
     if ((r = ensure(c, c->lnpart, rows * 2 * (D / 64) * sizeof(float)))) return r;
-    if ((r = ensure(c, c->attn_guard, VIT_MAX_L * sizeof(int)))) return r;
     c->ws_chunk = c->chunk;
     c->ws_hidden = D;
     c->ws_mlp = F;
@@ -153,31 +152,27 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     // would be missing.  There mode 2 takes mode 1's statistics pass over x, which sums in the same canonical order:
     // the same bits, one more read of x per LayerNorm.
     const bool planes = c->ln_mode == 2 && (D % 256) == 0;
+    EncoderPass P{c, s, D, F, c->ln_eps, c->act, c->x.p, c->qkv.p, c->att.p, c->mlp.p, (float*)c->stats.p};
+    P.lnpart = (float*)c->lnpart.p;  // handed to the residual GEMMs in every mode,
+    P.lnpart_rows = (int64_t)c->ws_chunk * T;
+    P.planes = planes;               // used where the epilogues leave all of them
+    P.zigzag = c->zigzag;  // mme_set_tile_order; only this tower alternates the walk (the patch embedding and the tails walk forwards)
     GemmArgs g{};
-    // Zig-zag: consecutive kernels of the pass walk the rows in OPPOSITE directions, so a consumer starts on the rows its
-    // producer wrote last -- what is still in the 256 MiB Infinity Cache of a 1.2-5 GB activation -- instead of on the rows
-    // written first and long evicted.  Tile order only: results are bit-identical (tests).  dir flips at every producer.
-    const int zigzag = c->zigzag;  // 0 off, 1 every kernel alternates, 2 only the attention walks backwards
-    int dir = 0;
-    auto next_dir = [&]() { if (zigzag == 1) dir ^= 1; return dir; };
+    int r;
     if (t50) {
         // patch 32: the patch-embed GEMM leaves f32 [n * 49, D] in the qkv buffer (dead until layer 0; 196 D n bytes of its
         // 300 D n), embed_rows_t50 adds bias and position rows, rounds once and writes the [CLS] rows in the same launch
-        {
-            Timed t(c, s, KC_GEMM);
-            g.A = patches;
-            g.W = c->patch_w;
-            g.M = n * c->geom.np();
-            g.N = D;
-            g.K = c->geom.patch_dim();
-            g.outf = (float*)c->qkv.p;
-            g.ldf = D;
-            HIP_TRY(c, launch_gemm(EPI_F32, g, s, c->gemm_variant));
-        }
+        g.A = patches;
+        g.W = c->patch_w;
+        g.M = n * c->geom.np();
+        g.N = D;
+        g.K = c->geom.patch_dim();
+        g.outf = (float*)c->qkv.p;
+        g.ldf = D;
+        if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_embed_rows_t50((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
     } else {
-        Timed t(c, s, KC_GEMM);
         g.A = patches;
         g.W = c->patch_w;
         g.M = n * VIT_NP;
@@ -188,41 +183,18 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         g.out = c->x.p;
         g.ldo = D;
         if (planes && !c->clip) {  // the 256 x 256 kernel leaves the LayerNorm partial sums of the token rows it writes
-            g.ln_part = (float*)c->lnpart.p;
-            g.ln_part_rows = (int64_t)c->ws_chunk * VIT_T;
+            g.ln_part = P.lnpart;
+            g.ln_part_rows = P.lnpart_rows;
         }
-        HIP_TRY(c, launch_gemm(EPI_PATCH, g, s, c->gemm_variant));
+        if ((r = P.gemm(EPI_PATCH, g))) return r;
     }
     const GemmArgs patch_args = g;
     if (!t50) {
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, D, s));
     }
-    // one guard word per layer for the attention kernel's fast form (attention.hip): zero = no row left its range (zeroed
-    // in mode 0 too, so that mme_attention_redone reports this pass and not an earlier one)
-    HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, VIT_MAX_L * sizeof(int), s));
-    // LayerNorm statistics of the residual stream x for the GEMM that folds the LayerNorm in.  Mode 2: the GEMM
-    // that WROTE x (EPI_BIAS_RES_STATS) left per-slice partial sums; finishing them reads 96 bytes per row
-    // instead of the 1536-byte row (ViT-B/16).  Rows of a ragged last row tile, launches that ran the 128 x 128 kernel and
-    // the first LayerNorm of the pass take the stand-alone kernel, which sums in the same canonical order.
-    auto stats_from_x = [&](int64_t row0) -> int {
-        Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, row0, M, D, c->ln_eps, (float*)c->stats.p, s));
-        return MME_OK;
-    };
-    auto stats_after = [&](const GemmArgs& producer) -> int {
-        if (!planes || !gemm_runs_256(producer, c->gemm_variant)) return stats_from_x(0);
-        const int64_t interior = (int64_t)(M / 256) * 256;
-        {
-            Timed t(c, s, KC_LN);
-            HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, producer.ln_part_rows, interior, D, c->ln_eps, (float*)c->stats.p, s));
-        }
-        return interior < M ? stats_from_x(interior) : MME_OK;
-    };
-    const int res_epi = planes ? EPI_BIAS_RES_STATS : EPI_BIAS_RES;
-    // fc1's activation: erf-GELU, or QuickGELU for a CLIP tower with OpenAI weights
-    const int act_epi = c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, ln_act_epi = c->act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU;
-    int r;
+    if ((r = reset_attn_guards(c, NL, s))) return r;
+    // The first LayerNorm of the pass.  The statistics of every later one come from the block (EncoderPass::stats_after).
     if (c->clip) {
         // CLIP: pre_layrnorm over every token row, in place; the same launch leaves the statistics of the rows it wrote,
         // in the canonical order: the first folded LayerNorm needs neither planes nor another pass over x
@@ -238,45 +210,40 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, patch_args.ln_part_rows, t_int, D, c->ln_eps, (float*)c->stats.p, s));
         HIP_TRY(c, launch_ln_stats_canonical(c->x.p, 0, t_int, D, c->ln_eps, (float*)c->stats.p, s, VIT_T));  // [CLS] rows below t_int
         HIP_TRY(c, launch_ln_stats_canonical(c->x.p, t_int, M, D, c->ln_eps, (float*)c->stats.p, s));
-    } else if (c->ln_mode != 0 && (r = stats_from_x(0))) {
+    } else if (c->ln_mode != 0 && (r = P.stats_from_x(c->x.p, 0, M))) {
         return r;
     }
     for (int l = 0; l < NL; ++l) {
         const LayerDev& L = c->layer[l];
         if (c->ln_mode != 0) {  // LN1 folded into the QKV GEMM: x is read once, nothing normalised is written
-            Timed t(c, s, KC_GEMM);
-            g = GemmArgs{};
-            g.A = c->x.p; g.W = L.qkv_wf; g.M = M; g.N = 3 * D; g.K = D;
-            g.bias = L.qkv_bf; g.colsum = L.qkv_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->qkv.p; g.ldo = 3 * D;
-            g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(EPI_LN_BIAS, g, s, c->gemm_variant));
+            if ((r = P.qkv_ln(L.w, M))) return r;
         } else {
             {
                 Timed t(c, s, KC_LN);
                 HIP_TRY(c, launch_layernorm(c->x.p, L.ln1_g, L.ln1_b, c->hbuf.p, M, D, c->ln_eps, s));
             }
-            Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
             g.A = c->hbuf.p; g.W = L.qkv_w; g.M = M; g.N = 3 * D; g.K = D;
             g.bias = L.qkv_b; g.out = c->qkv.p; g.ldo = 3 * D;
-            g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(EPI_BIAS, g, s, c->gemm_variant));
+            g.reverse_m = P.next_dir();
+            if ((r = P.gemm(EPI_BIAS, g))) return r;
         }
         // Pruned last layer (mme_set_forward_pruning): after the last attention only ONE token row per crop is ever read
-        // (K8 pools token `pool_token`), so the query block that holds it is the only one attended, and o_proj, LayerNorm,
-        // fc1 and fc2 run on the n gathered rows instead of n x 197.  Same kernels, same per-row arithmetic: the
+        // (K8 pools token `pool_token`), so the query block that holds it is the only one attended, and the second half of
+        // the block runs on the n gathered rows instead of n x 197.  Same kernels, same per-row arithmetic: the
         // embeddings are bit-identical to the full pass (tests/test_gpu_parity.py).
         const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0;
         {
             Timed t(c, s, KC_ATTN);
             if (t50) {  // exact kernel only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
-                if (zigzag != 2) next_dir();
+                if (P.zigzag != 2) P.next_dir();
                 HIP_TRY(c, launch_attention_t50(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
             } else {
                 HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
-                                            pruned ? pool_token / 32 : -1, zigzag == 2 ? true : next_dir() != 0));
+                                            pruned ? pool_token / 32 : -1, P.zigzag == 2 ? true : P.next_dir() != 0));
             }
         }
+        const bool last = l + 1 == NL;  // no statistics after the last block: the final LayerNorm touches the pooled row only (K8)
         if (pruned) {
             bf16_t* att_p = (bf16_t*)c->hbuf.p;          // [n, D] gathered attention rows
             bf16_t* x_p = att_p + (size_t)n * D;      // [n, D] gathered residual rows (hbuf holds rows x D: n x 197 of them)
@@ -286,94 +253,47 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
                 HIP_TRY(c, hipMemcpy2DAsync(att_p, rowb, (const char*)c->att.p + (size_t)pool_token * rowb, pitch, rowb, n, hipMemcpyDeviceToDevice, s));
                 HIP_TRY(c, hipMemcpy2DAsync(x_p, rowb, (const char*)c->x.p + (size_t)pool_token * rowb, pitch, rowb, n, hipMemcpyDeviceToDevice, s));
             }
-            {
-                Timed t(c, s, KC_GEMM);
-                g = GemmArgs{};
-                g.A = att_p; g.W = L.o_w; g.M = n; g.N = D; g.K = D;
-                g.bias = L.o_b; g.out = x_p; g.res = x_p; g.ldo = D;
-                HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
-            }
-            {
-                Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_ln_stats_canonical(x_p, 0, n, D, c->ln_eps, (float*)c->stats.p, s));
-            }
-            {
-                Timed t(c, s, KC_GEMM);
-                g = GemmArgs{};
-                g.A = x_p; g.W = L.fc1_wf; g.M = n; g.N = F; g.K = D;
-                g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = F;
-                HIP_TRY(c, launch_gemm(ln_act_epi, g, s, c->gemm_variant));
-                g = GemmArgs{};
-                g.A = c->mlp.p; g.W = L.fc2_w; g.M = n; g.N = D; g.K = F;
-                g.bias = L.fc2_b; g.out = x_p; g.res = x_p; g.ldo = D;
-                HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
-            }
+            EncoderPass G = P;    // the same block on the gathered rows:
+            G.lnpart = nullptr;   // n rows are far below one 256-row panel,
+            G.planes = false;     // so no planes, one canonical statistics pass
+            G.zigzag = G.dir = 0; // and no reversal
+            if ((r = G.after_attention(L.w, n, att_p, x_p, false))) return r;
             {   // back into the residual stream, where the pooling kernel reads the row
                 Timed t(c, s, KC_POOL);
                 HIP_TRY(c, hipMemcpy2DAsync((char*)c->x.p + (size_t)pool_token * rowb, pitch, x_p, rowb, rowb, n, hipMemcpyDeviceToDevice, s));
             }
-            continue;
-        }
-        {
-            Timed t(c, s, KC_GEMM);
-            g = GemmArgs{};
-            g.A = c->att.p; g.W = L.o_w; g.M = M; g.N = D; g.K = D;
-            g.bias = L.o_b; g.out = c->x.p; g.res = c->x.p; g.ldo = D;
-            g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * T;
-            g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(res_epi, g, s, c->gemm_variant));
-        }
-        if (c->ln_mode != 0) {
-            if ((r = stats_after(g))) return r;
-            Timed t(c, s, KC_GEMM);
-            g = GemmArgs{};
-            g.A = c->x.p; g.W = L.fc1_wf; g.M = M; g.N = F; g.K = D;
-            g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)c->stats.p; g.out = c->mlp.p; g.ldo = F;
-            g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(ln_act_epi, g, s, c->gemm_variant));
-        } else {
+        } else if (c->ln_mode != 0) {
+            if ((r = P.after_attention(L.w, M, c->att.p, c->x.p, !last))) return r;
+        } else {  // LayerNorm-kernel mode: the block's residual GEMMs around a LayerNorm launch and the unfolded fc1
+            if ((r = P.residual(c->att.p, L.w.o_w, L.w.o_b, D, M, c->x.p, false))) return r;
             {
                 Timed t(c, s, KC_LN);
                 HIP_TRY(c, launch_layernorm(c->x.p, L.ln2_g, L.ln2_b, c->hbuf.p, M, D, c->ln_eps, s));
             }
-            Timed t(c, s, KC_GEMM);
             g = GemmArgs{};
             g.A = c->hbuf.p; g.W = L.fc1_w; g.M = M; g.N = F; g.K = D;
             g.bias = L.fc1_b; g.out = c->mlp.p; g.ldo = F;
-            g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(act_epi, g, s, c->gemm_variant));
+            g.reverse_m = P.next_dir();
+            if ((r = P.gemm(c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, g))) return r;
+            if ((r = P.residual(c->mlp.p, L.w.fc2_w, L.w.fc2_b, F, M, c->x.p, false))) return r;
         }
-        const bool last = l + 1 == NL;  // the final LayerNorm touches the pooled row only (K8)
-        {
-            Timed t(c, s, KC_GEMM);
-            g = GemmArgs{};
-            g.A = c->mlp.p; g.W = L.fc2_w; g.M = M; g.N = D; g.K = F;
-            g.bias = L.fc2_b; g.out = c->x.p; g.res = c->x.p; g.ldo = D;
-            g.ln_part = (float*)c->lnpart.p; g.ln_part_rows = (int64_t)c->ws_chunk * T;
-            g.reverse_m = next_dir();
-            HIP_TRY(c, launch_gemm(last ? EPI_BIAS_RES : res_epi, g, s, c->gemm_variant));
-        }
-        if (c->ln_mode != 0 && !last && (r = stats_after(g))) return r;
     }
     if (c->proj_dim) {
         // CLIP with a projection: post_layernorm of the pooled row, rounded to bf16, times visual_projection, then L2
-        const int P = c->proj_dim;
+        const int E = c->proj_dim;
         if ((r = ensure(c, c->pooled, (size_t)c->chunk * D * 2))) return r;
-        if ((r = ensure(c, c->projf, (size_t)c->chunk * P * sizeof(float)))) return r;
+        if ((r = ensure(c, c->projf, (size_t)c->chunk * E * sizeof(float)))) return r;
         {
             Timed t(c, s, KC_POOL);
             if (t50) HIP_TRY(c, launch_pool_ln_t50(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
             else HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
         }
-        {
-            Timed t(c, s, KC_GEMM);
-            g = GemmArgs{};
-            g.A = c->pooled.p; g.W = c->proj_w; g.M = n; g.N = P; g.K = D;
-            g.outf = (float*)c->projf.p; g.ldf = P;
-            HIP_TRY(c, launch_gemm(EPI_F32, g, s, c->gemm_variant));
-        }
+        g = GemmArgs{};
+        g.A = c->pooled.p; g.W = c->proj_w; g.M = n; g.N = E; g.K = D;
+        g.outf = (float*)c->projf.p; g.ldf = E;
+        if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_l2_rows((const float*)c->projf.p, n, P, emb_f32, emb_bf16, s));
+        HIP_TRY(c, launch_l2_rows((const float*)c->projf.p, n, E, emb_f32, emb_bf16, s));
         return MME_OK;
     }
     {

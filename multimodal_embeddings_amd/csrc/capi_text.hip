@@ -6,12 +6,7 @@
 #include <new>
 #include <vector>
 
-#include "ctx.h"
-
-struct TextLayerDev {
-    bf16_t *qkv_wf, *o_w, *fc1_wf, *fc2_w;
-    float *qkv_cs, *qkv_bf, *o_b, *fc1_cs, *fc1_bf, *fc2_b;
-};
+#include "encoder_pass.h"
 
 struct TextDev {
     bool loaded = false;
@@ -20,7 +15,7 @@ struct TextDev {
     bf16_t* tok = nullptr;
     float *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr;
     bf16_t* proj_w = nullptr;
-    std::vector<TextLayerDev> layer;
+    std::vector<BlockW> layer;
     // workspace of the pass (grown to the largest chunk seen, never shrunk), and the diagnostic's staging of ids / positions
     DevBuf x, qkv, att, hmlp, stats, pooled, projf, ids, eos_pos, apply_ints;
 };
@@ -118,7 +113,7 @@ int prepare_text(mme_ctx* c, P& p, const mme_clip_text_weights& w) {
     const float sc = 0.125f * 1.44269504088896341f;  // dh^-0.5 * log2(e), folded into the query rows (weight_load.hip, prepare_vit)
     for (int l = 0; l < w.layers; ++l) {
         const mme_vit_layer& a = w.layer[l];
-        TextLayerDev& L = t->layer[l];
+        BlockW& L = t->layer[l];
         const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
         if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
         if ((r = plain_bf16(a.o_w, rD, D, &L.o_w))) return r;
@@ -149,7 +144,7 @@ int load_text(mme_ctx* c, const mme_clip_text_weights* w, P p, const char* who) 
     t->hidden = w->hidden; t->layers = w->layers; t->heads = w->heads; t->mlp = w->mlp; t->vocab = w->vocab;
     t->proj_dim = w->proj_dim; t->act = w->act; t->eos = w->eos_token_id; t->eps = w->ln_eps;
     t->tok = nullptr; t->pos = t->lnf_g = t->lnf_b = nullptr; t->proj_w = nullptr;
-    t->layer.assign((size_t)w->layers, TextLayerDev{});
+    t->layer.assign((size_t)w->layers, BlockW{});
     std::vector<mme_vit_layer> layer(w->layer, w->layer + w->layers);
     mme_clip_text_weights v = *w;
     v.layer = layer.data();
@@ -183,68 +178,39 @@ int scan_ids(mme_ctx* c, const char* who, const int32_t* ids, int n, int vocab, 
 }
 
 int text_chunk(mme_ctx* c, TextDev* t, const int32_t* ids_dev, const int32_t* eos_dev, int n, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
-    const int M = n * TXT_T, D = t->hidden, F = t->mlp, NL = t->layers;
-    GemmArgs g{};
-    auto stats = [&]() -> int {
-        Timed tm(c, s, KC_LN);
-        HIP_TRY(c, launch_ln_stats_canonical(t->x.p, 0, M, D, t->eps, (float*)t->stats.p, s));
-        return MME_OK;
-    };
+    const int M = n * TXT_T, D = t->hidden, NL = t->layers;
+    EncoderPass P{c, s, D, t->mlp, t->eps, t->act, t->x.p, t->qkv.p, t->att.p, t->hmlp.p, (float*)t->stats.p};
+    P.planes = false;    // ln_mode is not consulted: the text tower runs mode 1, one statistics pass over x per LayerNorm,
+    P.lnpart = nullptr;  // and its residual GEMMs are handed no planes
+    P.zigzag = 0;        // every kernel walks the rows forwards
     int r;
     {
         Timed tm(c, s, KC_PRE);
         HIP_TRY(c, launch_text_token_rows(t->tok, t->pos, ids_dev, t->x.p, n, D, s));
     }
-    if ((r = stats())) return r;
-    const int ln_act_epi = t->act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU;
+    if ((r = P.stats_from_x(t->x.p, 0, M))) return r;
     for (int l = 0; l < NL; ++l) {
-        const TextLayerDev& L = t->layer[l];
-        {
-            Timed tm(c, s, KC_GEMM);  // layer_norm1 folded into Q | K | V
-            g = GemmArgs{};
-            g.A = t->x.p; g.W = L.qkv_wf; g.M = M; g.N = 3 * D; g.K = D;
-            g.bias = L.qkv_bf; g.colsum = L.qkv_cs; g.ln_stats = (const float*)t->stats.p; g.out = t->qkv.p; g.ldo = 3 * D;
-            HIP_TRY(c, launch_gemm(EPI_LN_BIAS, g, s, c->gemm_variant));
-        }
+        if ((r = P.qkv_ln(t->layer[l], M))) return r;
         {
             Timed tm(c, s, KC_ATTN);
             HIP_TRY(c, launch_attention_causal(t->qkv.p, t->att.p, n, t->heads, s));
         }
-        {
-            Timed tm(c, s, KC_GEMM);
-            g = GemmArgs{};
-            g.A = t->att.p; g.W = L.o_w; g.M = M; g.N = D; g.K = D;
-            g.bias = L.o_b; g.out = t->x.p; g.res = t->x.p; g.ldo = D;
-            HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
-        }
-        if ((r = stats())) return r;
-        {
-            Timed tm(c, s, KC_GEMM);  // layer_norm2 folded into fc1, then the activation
-            g = GemmArgs{};
-            g.A = t->x.p; g.W = L.fc1_wf; g.M = M; g.N = F; g.K = D;
-            g.bias = L.fc1_bf; g.colsum = L.fc1_cs; g.ln_stats = (const float*)t->stats.p; g.out = t->hmlp.p; g.ldo = F;
-            HIP_TRY(c, launch_gemm(ln_act_epi, g, s, c->gemm_variant));
-            g = GemmArgs{};
-            g.A = t->hmlp.p; g.W = L.fc2_w; g.M = M; g.N = D; g.K = F;
-            g.bias = L.fc2_b; g.out = t->x.p; g.res = t->x.p; g.ldo = D;
-            HIP_TRY(c, launch_gemm(EPI_BIAS_RES, g, s, c->gemm_variant));
-        }
-        if (l + 1 < NL && (r = stats())) return r;  // final_layer_norm touches the EOS rows only
+        // no statistics after the last block: final_layer_norm touches the EOS rows only
+        if ((r = P.after_attention(t->layer[l], M, t->att.p, t->x.p, l + 1 < NL))) return r;
     }
-    const int P = t->proj_dim;
+    const int E = t->proj_dim;
     {
         Timed tm(c, s, KC_POOL);
-        HIP_TRY(c, launch_text_eos_pool_ln(t->x.p, t->lnf_g, t->lnf_b, eos_dev, n, D, t->eps, P ? t->pooled.p : nullptr, P ? nullptr : (float*)t->projf.p, s));
+        HIP_TRY(c, launch_text_eos_pool_ln(t->x.p, t->lnf_g, t->lnf_b, eos_dev, n, D, t->eps, E ? t->pooled.p : nullptr, E ? nullptr : (float*)t->projf.p, s));
     }
-    if (P) {
-        Timed tm(c, s, KC_GEMM);
-        g = GemmArgs{};
-        g.A = t->pooled.p; g.W = t->proj_w; g.M = n; g.N = P; g.K = D;
-        g.outf = (float*)t->projf.p; g.ldf = P;
-        HIP_TRY(c, launch_gemm(EPI_F32, g, s, c->gemm_variant));
+    if (E) {
+        GemmArgs g{};
+        g.A = t->pooled.p; g.W = t->proj_w; g.M = n; g.N = E; g.K = D;
+        g.outf = (float*)t->projf.p; g.ldf = E;
+        if ((r = P.gemm(EPI_F32, g))) return r;
     }
     Timed tm(c, s, KC_POOL);
-    HIP_TRY(c, launch_l2_rows((const float*)t->projf.p, n, P ? P : D, emb_f32, emb_bf16, s));
+    HIP_TRY(c, launch_l2_rows((const float*)t->projf.p, n, E ? E : D, emb_f32, emb_bf16, s));
     return MME_OK;
 }
 

@@ -7,17 +7,12 @@
 #include <new>
 #include <vector>
 
-#include "ctx.h"
+#include "encoder_pass.h"
 
 namespace {
 constexpr int TD = 1280, TF = 5120, TH = 16, TTOK = 1601, TTOKP = 1608, TTILES = 4, TT = TTILES * TTOKP, TGRID = 40;
 constexpr int TPDIM = 588, TPDIMP = 640, TMAXI = 8, TARATIOS = 9;
 }  // namespace
-
-struct TileLayerDev {
-    bf16_t *qkv_wf, *o_w, *fc1_wf, *fc2_w;
-    float *qkv_cs, *qkv_bf, *fc1_cs, *fc1_bf, *fc2_b;
-};
 
 struct TileVitDev {
     int layers = 0, global_layers = 0, ni = 0;
@@ -27,7 +22,7 @@ struct TileVitDev {
     float *cls = nullptr, *pre = nullptr, *pos = nullptr, *tilepos = nullptr, *post = nullptr;
     float *lnpre_g = nullptr, *lnpre_b = nullptr, *lnpost_g = nullptr, *lnpost_b = nullptr, *zeros = nullptr;
     bf16_t* patch_w = nullptr;
-    std::vector<TileLayerDev> layer;  // the prepared buffers are registered in the context (c->allocs)
+    std::vector<BlockW> layer;  // the prepared buffers are registered in the context (c->allocs)
     // workspace for `ws_images` images
     int ws_images = 0;
     DevBuf patches, pemb, x, qkv, att, mlp, stats, lnpart, inter, meta;
@@ -109,7 +104,7 @@ void each_tile_tensor(mme_tile_vit_weights& w, std::vector<mme_tile_layer>& laye
 }
 
 // The prepared buffers of the tower, in the order mme_weights_fingerprint reports them: nine tables, zeros, patch_w, then
-// 9 per layer.  The tanh gates are applied here, once (tanh on the host): the kernels add plain tables.  A gated table
+// 9 per layer (o_b is the shared zeros table).  The tanh gates are applied here, once (tanh on the host): the kernels add plain tables.  A gated table
 // and fc2_b are always multiplied, o_w / fc2_w only where the factor is not 1 (the ungated layers).
 template <class P>
 int prepare_tile(mme_ctx* c, P& p, const mme_tile_vit_weights& w) {
@@ -138,13 +133,14 @@ int prepare_tile(mme_ctx* c, P& p, const mme_tile_vit_weights& w) {
     const float qsc = 0.11180339887498949f * 1.44269504088896341f;
     for (int l = 0; l < L; ++l) {
         const mme_tile_layer& a = w.layer[l];
-        TileLayerDev& Ld = t->layer[l];
+        BlockW& Ld = t->layer[l];
         // x + tanh(gate) * branch(x): the gate multiplies the branch's LAST linear map (global layers only)
         const float ga = a.gated ? std::tanh(a.gate_attn) : 1.0f, gf = a.gated ? std::tanh(a.gate_ffn) : 1.0f;
         const WpFoldSrc fq[3] = {{a.q_w, nullptr, qsc, 1}, {a.k_w, nullptr, 1.f, 0}, {a.v_w, nullptr, 1.f, 0}};
         if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &Ld.qkv_wf, &Ld.qkv_cs, &Ld.qkv_bf))) return r;
         const void *o_w = a.o_w, *fc2_w = a.fc2_w;
         if ((r = p.bf16(&o_w, rD, 1, D, ga, ga != 1.0f, &Ld.o_w))) return r;
+        Ld.o_b = t->zeros;  // the checkpoint has no o_proj bias
         const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
         if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &Ld.fc1_wf, &Ld.fc1_cs, &Ld.fc1_bf))) return r;
         if ((r = p.bf16(&fc2_w, rD, 1, F, gf, gf != 1.0f, &Ld.fc2_w))) return r;
@@ -222,48 +218,31 @@ int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* a
         int32_t* nt_dev = aid_dev + t->ws_images;
         HIP_TRY(c, hipMemcpyAsync(aid_dev, aspect_ids_host + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(nt_dev, num_tiles_host + i0, (size_t)m * 4, hipMemcpyHostToDevice, s));
-        // one guard word per layer for the fast attention form (attention_tiles.hip): zeroed per pass
-        {
-            int rg;
-            if ((rg = ensure(c, c->attn_guard, 64 * sizeof(int)))) return rg;
-        }
-        HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, 64 * sizeof(int), s));  // mode 0 too: the flags describe THIS pass
+        const int L = t->layers + t->global_layers;
+        int r;
+        if ((r = reset_attn_guards(c, L, s))) return r;
         const int64_t npatch = (int64_t)m * TTILES * TGRID * TGRID;
         {
             Timed tm(c, s, KC_PRE);
             HIP_TRY(c, launch_tile_patchify(pixel_values + (size_t)i0 * TTILES * 3 * 560 * 560, t->patches.p, npatch, s));
         }
-        GemmArgs g{};
+        EncoderPass P{c, s, TD, TF, t->eps, /*act: erf-GELU*/ 0, t->x.p, t->qkv.p, t->att.p, t->mlp.p, (float*)t->stats.p};
+        P.lnpart = (float*)t->lnpart.p;  // handed to the residual GEMMs in every mode,
+        P.lnpart_rows = ws_rows;
+        P.planes = c->ln_mode == 2;      // used in mode 2: 1280 is a multiple of the 256-column tile
+        P.zigzag = 0;                    // every kernel walks the rows forwards
         {
-            Timed tm(c, s, KC_GEMM);
+            GemmArgs g{};
             g.A = t->patches.p; g.W = t->patch_w; g.M = (int)npatch; g.N = TD; g.K = TPDIMP; g.bias = t->zeros; g.out = t->pemb.p; g.ldo = TD;
-            HIP_TRY(c, launch_gemm(EPI_BIAS, g, s, c->gemm_variant));
+            if ((r = P.gemm(EPI_BIAS, g))) return r;
         }
         {
             Timed tm(c, s, KC_LN);
             HIP_TRY(c, launch_tile_assemble(t->pemb.p, t->cls, t->pre, t->pos, t->tilepos, t->lnpre_g, t->lnpre_b, aid_dev, t->x.p, M, 1e-5f, s));
         }
-        auto stats_from_x = [&](int64_t row0) -> int {
-            Timed tm(c, s, KC_LN);
-            HIP_TRY(c, launch_ln_stats_canonical(t->x.p, row0, M, TD, t->eps, (float*)t->stats.p, s));
-            return MME_OK;
-        };
-        auto stats_after = [&](const GemmArgs& producer) -> int {
-            if (c->ln_mode != 2 || !gemm_runs_256(producer, c->gemm_variant)) return stats_from_x(0);
-            const int64_t interior = (int64_t)(M / 256) * 256;
-            {
-                Timed tm(c, s, KC_LN);
-                HIP_TRY(c, launch_ln_finish((const float*)t->lnpart.p, producer.ln_part_rows, interior, TD, t->eps, (float*)t->stats.p, s));
-            }
-            return interior < M ? stats_from_x(interior) : MME_OK;
-        };
-        const int res_epi = c->ln_mode == 2 ? EPI_BIAS_RES_STATS : EPI_BIAS_RES;
-        int r;
-        if ((r = stats_from_x(0))) return r;
-        const int L = t->layers + t->global_layers;
+        if ((r = P.stats_from_x(t->x.p, 0, M))) return r;
         int saved = 0;
         for (int l = 0; l < L; ++l) {
-            const TileLayerDev& Ld = t->layer[l];
             // an intermediate state the output concatenates, "before layer l" convention: the state ENTERING local layer l
             if (t->save_before && l < t->layers && saved < t->ni && t->inter_after[saved] == l) {
                 HIP_TRY(c, hipMemcpyAsync((char*)t->inter.p + (size_t)saved * ws_rows * TD * 2, t->x.p, (size_t)M * TD * 2, hipMemcpyDeviceToDevice, s));
@@ -274,47 +253,17 @@ int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* a
                     Timed tm(c, s, KC_LN);
                     HIP_TRY(c, launch_tile_ln_post(t->x.p, t->lnpost_g, t->lnpost_b, t->post, aid_dev, M, 1e-5f, s));
                 }
-                if ((r = stats_from_x(0))) return r;
+                if ((r = P.stats_from_x(t->x.p, 0, M))) return r;
             }
-            {
-                Timed tm(c, s, KC_GEMM);
-                g = GemmArgs{};
-                g.A = t->x.p; g.W = Ld.qkv_wf; g.M = M; g.N = 3 * TD; g.K = TD;
-                g.bias = Ld.qkv_bf; g.colsum = Ld.qkv_cs; g.ln_stats = (const float*)t->stats.p; g.out = t->qkv.p; g.ldo = 3 * TD;
-                HIP_TRY(c, launch_gemm(EPI_LN_BIAS, g, s, c->gemm_variant));
-            }
+            if ((r = P.qkv_ln(t->layer[l], M))) return r;
             {
                 Timed tm(c, s, KC_ATTN);
                 HIP_TRY(c, launch_attention_tiles(t->qkv.p, t->att.p, nt_dev, m, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2));
             }
-            {
-                Timed tm(c, s, KC_GEMM);
-                g = GemmArgs{};
-                g.A = t->att.p; g.W = Ld.o_w; g.M = M; g.N = TD; g.K = TD;
-                g.bias = t->zeros; g.out = t->x.p; g.res = t->x.p; g.ldo = TD;
-                g.ln_part = (float*)t->lnpart.p; g.ln_part_rows = ws_rows;
-                HIP_TRY(c, launch_gemm(res_epi, g, s, c->gemm_variant));
-            }
-            if ((r = stats_after(g))) return r;
-            {
-                Timed tm(c, s, KC_GEMM);
-                g = GemmArgs{};
-                g.A = t->x.p; g.W = Ld.fc1_wf; g.M = M; g.N = TF; g.K = TD;
-                g.bias = Ld.fc1_bf; g.colsum = Ld.fc1_cs; g.ln_stats = (const float*)t->stats.p; g.out = t->mlp.p; g.ldo = TF;
-                HIP_TRY(c, launch_gemm(EPI_LN_BIAS_GELU, g, s, c->gemm_variant));
-            }
             // statistics are needed by the next layer's QKV GEMM, except after the last local layer (layernorm_post
-            // rewrites x first) and after the very last layer
+            // rewrites x first) and after the very last layer: there fc2 takes the plain EPI_BIAS_RES epilogue
             const bool need_stats = l + 1 < L && l + 1 != t->layers;
-            {
-                Timed tm(c, s, KC_GEMM);
-                g = GemmArgs{};
-                g.A = t->mlp.p; g.W = Ld.fc2_w; g.M = M; g.N = TD; g.K = TF;
-                g.bias = Ld.fc2_b; g.out = t->x.p; g.res = t->x.p; g.ldo = TD;
-                g.ln_part = (float*)t->lnpart.p; g.ln_part_rows = ws_rows;
-                HIP_TRY(c, launch_gemm(need_stats ? res_epi : EPI_BIAS_RES, g, s, c->gemm_variant));
-            }
-            if (need_stats && (r = stats_after(g))) return r;
+            if ((r = P.after_attention(t->layer[l], M, t->att.p, t->x.p, need_stats))) return r;
             if (!t->save_before && l < t->layers && saved < t->ni && t->inter_after[saved] == l) {  // "after layer l" convention
                 HIP_TRY(c, hipMemcpyAsync((char*)t->inter.p + (size_t)saved * ws_rows * TD * 2, t->x.p, (size_t)M * TD * 2, hipMemcpyDeviceToDevice, s));
                 ++saved;

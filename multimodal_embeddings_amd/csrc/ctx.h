@@ -17,13 +17,25 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// The ten prepared buffers of one transformer block in the form every tower runs (encoder_pass.h): LayerNorm folded into
+// the consuming GEMM, W' = bf16(W * gamma), colsum = sum_k W', b' = b + W . beta
+struct BlockW {
+    bf16_t* qkv_wf;
+    float *qkv_cs, *qkv_bf;
+    bf16_t* o_w;
+    float* o_b;
+    bf16_t* fc1_wf;
+    float *fc1_cs, *fc1_bf;
+    bf16_t* fc2_w;
+    float* fc2_b;
+};
+
+// a block of the image towers: the folded form, and the unfolded tensors that only the LayerNorm-kernel mode (ln_mode 0) reads
 struct LayerDev {
+    BlockW w;
     float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    bf16_t *qkv_w, *o_w, *fc1_w, *fc2_w;
-    float *qkv_b, *o_b, *fc1_b, *fc2_b;
-    // LayerNorm folded into the consuming GEMM: W' = bf16(W * gamma), colsum = sum_k W', b' = b + W . beta
-    bf16_t *qkv_wf, *fc1_wf;
-    float *qkv_cs, *qkv_bf, *fc1_cs, *fc1_bf;
+    bf16_t *qkv_w, *fc1_w;
+    float *qkv_b, *fc1_b;
 };
 
 // The ViT @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
@@ -79,10 +91,10 @@ struct mme_ctx {
     int resize_rule = MME_RESIZE_FIT_PAD;  // mme_set_resize_rule: how mme_preprocess / mme_embed make 224 x 224 pixels; no load changes it
     // workspace (sized for `chunk` crops)
     int ws_chunk = 0, ws_hidden = 0, ws_mlp = 0, ws_tokens = 0;  // what the workspace below was sized for
-    DevBuf attn_guard;      // int[64]: one guard word per layer of a pass (attention.hip, FAST form)
+    DevBuf attn_guard;      // int[max(64, layers)]: one guard word per layer of a pass (encoder_pass.h, reset_attn_guards)
     DevBuf attn_apply;      // mme_attention_apply: its own guard word (int 0), the tile counts from int 16 on
     bool prune_last = false;  // mme_set_forward_pruning
-    int zigzag = 1;           // forward_chunk: 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
+    int zigzag = 1;           // EncoderPass::zigzag of forward_chunk: 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
     DevBuf patches32;      // patch 32: the retiled [chunk * 49, 3072] matrix of mme_embed (`patches` stages K1's patch-16 matrix)

@@ -1,0 +1,69 @@
+// The launch sequence of one pre-LN transformer block, written once for every tower (encoder_pass.h).
+#include "encoder_pass.h"
+
+int EncoderPass::gemm(int epilogue, const GemmArgs& g) {
+    Timed t(c, s, KC_GEMM);
+    HIP_TRY(c, launch_gemm(epilogue, g, s, c->gemm_variant));
+    return MME_OK;
+}
+
+int EncoderPass::stats_from_x(const void* xr, int64_t row0, int64_t rows) {
+    Timed t(c, s, KC_LN);
+    HIP_TRY(c, launch_ln_stats_canonical(xr, row0, rows, D, eps, stats, s));
+    return MME_OK;
+}
+
+int EncoderPass::stats_after(const GemmArgs& producer, int64_t rows) {
+    if (!planes || !gemm_runs_256(producer, c->gemm_variant)) return stats_from_x(producer.out, 0, rows);
+    const int64_t interior = rows / 256 * 256;
+    {
+        Timed t(c, s, KC_LN);
+        HIP_TRY(c, launch_ln_finish(lnpart, lnpart_rows, interior, D, eps, stats, s));
+    }
+    return interior < rows ? stats_from_x(producer.out, interior, rows) : MME_OK;
+}
+
+int EncoderPass::residual(const void* a, const bf16_t* w, const float* bias, int K, int rows, void* xr, bool stats_next) {
+    GemmArgs g{};
+    g.A = a; g.W = w; g.M = rows; g.N = D; g.K = K;
+    g.bias = bias; g.out = xr; g.res = xr; g.ldo = D;
+    if (lnpart) {
+        g.ln_part = lnpart;
+        g.ln_part_rows = lnpart_rows;
+    }
+    g.reverse_m = next_dir();
+    int r;
+    if ((r = gemm(planes && stats_next ? EPI_BIAS_RES_STATS : EPI_BIAS_RES, g))) return r;
+    return stats_next ? stats_after(g, rows) : MME_OK;
+}
+
+int EncoderPass::qkv_ln(const BlockW& w, int rows) {
+    GemmArgs g{};
+    g.A = x; g.W = w.qkv_wf; g.M = rows; g.N = 3 * D; g.K = D;
+    g.bias = w.qkv_bf; g.colsum = w.qkv_cs; g.ln_stats = stats; g.out = qkv; g.ldo = 3 * D;
+    g.reverse_m = next_dir();
+    return gemm(EPI_LN_BIAS, g);
+}
+
+int EncoderPass::fc1_ln(const BlockW& w, int rows, const void* xr) {
+    GemmArgs g{};
+    g.A = xr; g.W = w.fc1_wf; g.M = rows; g.N = F; g.K = D;
+    g.bias = w.fc1_bf; g.colsum = w.fc1_cs; g.ln_stats = stats; g.out = mlp; g.ldo = F;
+    g.reverse_m = next_dir();
+    return gemm(act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU, g);
+}
+
+int EncoderPass::after_attention(const BlockW& w, int rows, const void* a, void* xr, bool stats_next) {
+    int r;
+    if ((r = residual(a, w.o_w, w.o_b, D, rows, xr, true))) return r;
+    if ((r = fc1_ln(w, rows, xr))) return r;
+    return residual(mlp, w.fc2_w, w.fc2_b, F, rows, xr, stats_next);
+}
+
+int reset_attn_guards(mme_ctx* c, int layers, hipStream_t s) {
+    const size_t bytes = (size_t)(layers > VIT_MAX_L ? layers : VIT_MAX_L) * sizeof(int);
+    int r;
+    if ((r = ensure(c, c->attn_guard, bytes))) return r;
+    HIP_TRY(c, hipMemsetAsync(c->attn_guard.p, 0, bytes, s));
+    return MME_OK;
+}

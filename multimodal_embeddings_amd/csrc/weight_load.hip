@@ -327,15 +327,15 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
         const void* qkvb[3] = {a.q_b, a.k_b, a.v_b};
         if ((r = p.table_cat(qkvb, rD, 3, sc, true, &L.qkv_b))) return r;
         const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
-        if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.qkv_wf, &L.qkv_cs, &L.qkv_bf))) return r;
-        if ((r = plain_bf16(a.o_w, rD, D, &L.o_w))) return r;
-        if ((r = plain(a.o_b, D, &L.o_b))) return r;
+        if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.w.qkv_wf, &L.w.qkv_cs, &L.w.qkv_bf))) return r;
+        if ((r = plain_bf16(a.o_w, rD, D, &L.w.o_w))) return r;
+        if ((r = plain(a.o_b, D, &L.w.o_b))) return r;
         if ((r = plain_bf16(a.fc1_w, rF, D, &L.fc1_w))) return r;
         if ((r = plain(a.fc1_b, F, &L.fc1_b))) return r;
         const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
-        if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.fc1_wf, &L.fc1_cs, &L.fc1_bf))) return r;
-        if ((r = plain_bf16(a.fc2_w, rD, F, &L.fc2_w))) return r;
-        if ((r = plain(a.fc2_b, D, &L.fc2_b))) return r;
+        if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.w.fc1_wf, &L.w.fc1_cs, &L.w.fc1_bf))) return r;
+        if ((r = plain_bf16(a.fc2_w, rD, F, &L.w.fc2_w))) return r;
+        if ((r = plain(a.fc2_b, D, &L.w.fc2_b))) return r;
     }
     return MME_OK;
 }
