@@ -772,7 +772,7 @@ int mme_clip_apply(mme_ctx* ctx, int op, const mme_clip_apply_args* args, void* 
  *                            src[b * 196 + (2 PY + KY / 16) * 14 + 2 PX + KX / 16][c * 256 + (KY % 16) * 16 + KX % 16]
  *      1 embed_rows_t50      acc f32 [n * 49, d] -> x bf16 [n * 50, d]: x[b * 50 + 1 + p] = bf16((acc[b * 49 + p] + bias) + pos[1 + p]),
  *                            x[b * 50] = bf16(cls + pos[0]); pos f32 [50, d], f32 adds in that order
- *      2 attn_fwd_t50        qkv bf16 [n * 50, 3 * 64 * heads] (Q | K | V, Q pre-scaled by dh^-0.5 log2 e) -> out bf16 [n * 50, 64 * heads];
+ *      2 attn_short<50>      qkv bf16 [n * 50, 3 * 64 * heads] (Q | K | V, Q pre-scaled by dh^-0.5 log2 e) -> out bf16 [n * 50, 64 * heads];
  *                            exact row maximum under every attention mode; only_block 0 / 1: rows 0..31 / 32..49 of every crop only
  *      3 pool_ln_rows (50)   y[b] = bf16(LayerNorm(x[b * 50 + tok]) * gamma + beta), y bf16 [n, d]
  *      4 pool_ln_l2 (50)     the same row, LayerNorm then x / max(||x||, 1e-12), to emb_f32 and / or emb_bf16 [n, d]

@@ -29,12 +29,11 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int ROWB = VIT_DH * 2;       // 128-byte K/V rows in LDS
 template <int H> struct AttnRows {
     static_assert(H == 6 || H == 12 || H == 16, "attention: 6, 12 or 16 heads of 64");
     static constexpr int D = H * VIT_DH;    // row of the output, and of each of Q | K | V
@@ -51,25 +50,10 @@ static_assert(share_fits(ATTN_SHARE_FAST) && share_fits(ATTN_SHARE_EXACT), "ATTN
 template <int NB> struct AttnGeom {
     static_assert(NB == 2, "two K/V buffers");
     static constexpr int TROWS = 224;
-    static constexpr int KV_BYTES = TROWS * ROWB;
+    static constexpr int KV_BYTES = TROWS * ATTN_ROWB;
     static constexpr int BUF_BYTES = 2 * KV_BYTES;
     static constexpr int LDS_BYTES = NB * BUF_BYTES;
 };
-
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-#define S_BARRIER() asm volatile("s_barrier" ::: "memory")
-
-// the other half of the wave (lane ^ 32) holds the other keys of this lane's query: exchange by ONE v_permlane32_swap (vector
-// ALU) instead of __shfl_xor's ds_bpermute round trip through the LDS, whose latency sits on the head's critical path
-__device__ __forceinline__ float other_half(float x) {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    // after the swap sw[0] = {lo, lo}, sw[1] = {hi, hi}: the value this lane did not have is the one that differs
-    const float a = __uint_as_float(sw[0]), b = __uint_as_float(sw[1]);
-    return (threadIdx.x & 32) ? a : b;
-}
-
 
 // STAMP: diagnostic build -- every wave accumulates s_memtime intervals between seven points of a head
 // iteration (wait, barrier, request issue, S^T, softmax, P.V, stores) and writes 8 words per wave to `stamps`
@@ -111,7 +95,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
     constexpr int ZROWS = TROWS - 200;
     for (int i = tid; i < NB * ZROWS * 8; i += 512) {
         const int buf = i / (ZROWS * 8), r = (i >> 3) % ZROWS, c = i & 7;
-        *(uint4*)(lds + buf * BUF_BYTES + KV_BYTES + (200 + r) * ROWB + c * 16) = make_uint4(0, 0, 0, 0);
+        *(uint4*)(lds + buf * BUF_BYTES + KV_BYTES + (200 + r) * ATTN_ROWB + c * 16) = make_uint4(0, 0, 0, 0);
     }
 
     // DMA of one head: 25 K pieces + 25 V pieces (8 rows x 128 B each).  An LDS-DMA piece stalls its issuer for
@@ -119,7 +103,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
     // in the FAST form.  The wave without a query block (7) takes most of them; each computing wave requests `share`
     // pieces right after the barrier (pieces w, w + 7, ...), where its SIMD partner's work covers the stall.
     auto dma_head = [&](int it, int buf) {
-        const char* hb = (const char*)qkv + (size_t)item_crop(it) * VIT_T * QKV_LD + item_head(it) * ROWB;
+        const char* hb = (const char*)qkv + (size_t)item_crop(it) * VIT_T * QKV_LD + item_head(it) * ATTN_ROWB;
         char* kdst = lds + buf * BUF_BYTES;
         if ((dbg & 2) && it != 0) return;
         // share = a + 16 b + 256 c: waves 0-2 (the first-dispatched half: they lose the issue arbitration to their SIMD
@@ -134,41 +118,22 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
         for (int p = p_begin; p < p_end; p += p_step) {
             const bool isv = p >= NPIECE;
             const int pp = isv ? p - NPIECE : p;
-            const int row = pp * 8 + (lane >> 3);
-            const int slot = lane & 7;
-            const int chunk = isv ? (slot ^ (((row >> 1) & 1) << 2)) : (slot ^ ((row >> 1) & 7));
-            const char* src = hb + (size_t)min(row, VIT_T - 1) * QKV_LD + (isv ? 2 : 1) * D * 2 + chunk * 16;
-            // LDS-DMA through inline asm, so that hipcc does not know these loads write LDS: told through the builtin it
-            // orders every later LDS read behind them with `s_waitcnt vmcnt(0)` -- in the middle of the head iteration,
-            // where that also waits for the Q prefetch and the previous head's stores.  The ordering that is needed
-            // (pieces landed before the NEXT head reads them) is the counted wait + barrier at the top of the loop.
-            const unsigned dst = (unsigned)(size_t)(LDS_AS char*)(kdst + (isv ? KV_BYTES : 0) + pp * 1024);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-                         : "memory");
+            lds_dma16(kv_piece_src<VIT_T - 1>(hb, QKV_LD, D, isv, pp, lane), kdst + (isv ? KV_BYTES : 0) + pp * 1024);
         }
     };
 
     const int r = lane & 31, hh = lane >> 5;
     const int ksw = (r >> 1) & 7;
-    // transposed-read lane roles: group g of 16 lanes, lane 4q+p supplies row q, cols 4p..4p+3
-    const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-    const int vflag = (tq >> 1) & 1;  // bit 1 of the row this lane addresses: selects the swapped half
-    const int v_row_off = (4 * (g >> 1) + tq) * ROWB + (16 * (g & 1) + 4 * tp) * 2;
-    const int v_off0 = v_row_off + ((0 ^ vflag) << 6), v_off1 = v_row_off + ((1 ^ vflag) << 6);
-    const float sc = 0.125f * 1.44269504088896341f;  // dh^-0.5 * log2(e)
-    // PRESCALED: the Q columns of the QKV projection already carry sc (folded into W_q / b_q when the weights are
-    // uploaded, capi.hip), so a score leaves the matrix pipe in log2 units
-    constexpr bool PRESCALED = true;
+    const int v_off0 = vt_lane_off(lane, 0), v_off1 = vt_lane_off(lane, 1);
+    // The Q columns of the QKV projection carry dh^-0.5 log2 e (folded into W_q / b_q when the weights are uploaded, capi.hip),
+    // so a score leaves the matrix pipe in log2 units
     const int q = wave * 32 + r;                      // this lane's query (waves 0..6)
     // only_block >= 0: only that query block is computed and stored (the last layer when nothing but the pooled token's row
     // is read afterwards, mme_set_forward_pruning); the other waves still take their share of the K/V requests
     const bool active = wave < 7 && (only_block < 0 || wave == only_block);
     // this lane's Q row of an item: 4 x 16 bytes at + ks * 32
     auto q_ptr = [&](int it) {
-        return (const char*)qkv + ((size_t)item_crop(it) * VIT_T + min(q, VIT_T - 1)) * QKV_LD + hh * 16 + item_head(it) * ROWB;
+        return (const char*)qkv + ((size_t)item_crop(it) * VIT_T + min(q, VIT_T - 1)) * QKV_LD + hh * 16 + item_head(it) * ATTN_ROWB;
     };
 
     bf16x8 qf[4], qn[4];
@@ -230,11 +195,50 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
             auto read_v = [&](int i, s16x8 (&dst)[2]) {
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const char* va = Vl + i * 16 * ROWB + (db ? v_off1 : v_off0);
-                    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)va);
-                    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(va + 8 * ROWB));
-                    dst[db] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                    dst[db] = read_vt_frag(Vl + i * 16 * ATTN_ROWB + (db ? v_off1 : v_off0), ATTN_ROWB);
                 }
+            };
+            // P.V of the item: O^T = V^T . P^T in 13 steps of 16 keys, V read one step ahead, the probabilities of step i + 1
+            // computed between the two MFMAs of step i.  prob(kt, e) = P of score s[kt][e], the only thing a form supplies;
+            // returns the row sum (over the f32 P, both lane halves)
+            auto pv_phase = [&](auto prob) {
+                float sum4[4] = {0.f, 0.f, 0.f, 0.f};  // four independent chains: a single one serialises 104 dependent adds
+                // P of step i (16 keys: 8 values per lane), exponentiated, summed and rounded to bf16
+                auto soft = [&](auto i_tag, bf16x8& pf) {
+                    constexpr int I = decltype(i_tag)::value;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        constexpr int kt = I >> 1;
+                        const int e = 8 * (I & 1) + j;
+                        float pv = prob(kt, e);
+                        // of the last tile only keys 192..196 exist: e < 4, and e = 0 alone in the upper lane half
+                        if (kt == 6 && !(e < 4 && e + 4 * hh < VIT_T - 192)) pv = 0.f;
+                        sum4[j & 3] += pv;  // hipcc packs neighbouring chains into v_pk_add_f32: measured better here than 104 single adds (11.29 vs 11.54 ms per step)
+                        pf[j] = (bf16_t)pv;
+                    }
+                };
+#pragma unroll
+                for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.f;
+                bf16x8 pf[2];
+                read_v(0, vf[0]);
+                soft(std::integral_constant<int, 0>{}, pf[0]);
+                auto pv_step = [&](auto i_tag) {
+                    constexpr int I = decltype(i_tag)::value;
+                    if (I + 1 < 13) read_v(I + 1, vf[(I + 1) & 1]);
+                    o[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[I & 1][0]), pf[I & 1], o[0], 0, 0, 0);
+                    if constexpr (I + 1 < 13) soft(std::integral_constant<int, (I + 1 < 13 ? I + 1 : 0)>{}, pf[(I + 1) & 1]);
+                    o[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[I & 1][1]), pf[I & 1], o[1], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                pv_step(std::integral_constant<int, 0>{}); pv_step(std::integral_constant<int, 1>{});
+                pv_step(std::integral_constant<int, 2>{}); pv_step(std::integral_constant<int, 3>{});
+                pv_step(std::integral_constant<int, 4>{}); pv_step(std::integral_constant<int, 5>{});
+                pv_step(std::integral_constant<int, 6>{}); pv_step(std::integral_constant<int, 7>{});
+                pv_step(std::integral_constant<int, 8>{}); pv_step(std::integral_constant<int, 9>{});
+                pv_step(std::integral_constant<int, 10>{}); pv_step(std::integral_constant<int, 11>{});
+                pv_step(std::integral_constant<int, 12>{});
+                const float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
+                return sum + other_half(sum);
             };
             if constexpr (PIPE == 2) {
                 // FAST form.  softmax(s) = exp2(s' - c) / sum for ANY reference point c (s' = score in log2 units): the exact
@@ -250,10 +254,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 // f32's range with the sum still in range: p < 2^100 and a bf16 |v| >= 2^28).  So every finite input gets the
                 // exact algorithm's result.
                 bf16x8 kf[2][2][4];
-                auto read_k = [&](int kt, bf16x8 (&dst)[4]) {
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) dst[ks] = *(const bf16x8*)(Kl + (kt * 32 + r) * ROWB + (((2 * ks + hh) ^ ksw) << 4));
-                };
+                auto read_k = [&](int kt, bf16x8 (&dst)[4]) { read_k_frag(Kl, kt, r, hh, ksw, dst); };
                 read_k(0, kf[0][0]);
                 read_k(1, kf[1][0]);
                 read_k(2, kf[1][1]);
@@ -294,42 +295,8 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 ATTN_STAMP(3)  // S^T
-                float sum4[4] = {0.f, 0.f, 0.f, 0.f};
-                auto soft = [&](auto i_tag, bf16x8& pf) {
-                    constexpr int I = decltype(i_tag)::value;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        constexpr int kt = I >> 1;
-                        const int e = 8 * (I & 1) + j;
-                        float pv = __builtin_amdgcn_exp2f(kt == 0 ? s[kt][e] - mx : s[kt][e]);
-                        if (kt == 6 && !(e < 4 && e + 4 * hh < VIT_T - 192)) pv = 0.f;
-                        sum4[j & 3] += pv;  // hipcc packs neighbouring chains into v_pk_add_f32: measured better here than 104 single adds (11.29 vs 11.54 ms per step)
-                        pf[j] = (bf16_t)pv;
-                    }
-                };
                 ATTN_STAMP(4)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.f;
-                bf16x8 pf[2];
-                read_v(0, vf[0]);
-                soft(std::integral_constant<int, 0>{}, pf[0]);
-                auto pv_step = [&](auto i_tag) {
-                    constexpr int I = decltype(i_tag)::value;
-                    if (I + 1 < 13) read_v(I + 1, vf[(I + 1) & 1]);
-                    o[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[I & 1][0]), pf[I & 1], o[0], 0, 0, 0);
-                    if constexpr (I + 1 < 13) soft(std::integral_constant<int, (I + 1 < 13 ? I + 1 : 0)>{}, pf[(I + 1) & 1]);
-                    o[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[I & 1][1]), pf[I & 1], o[1], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                pv_step(std::integral_constant<int, 0>{}); pv_step(std::integral_constant<int, 1>{});
-                pv_step(std::integral_constant<int, 2>{}); pv_step(std::integral_constant<int, 3>{});
-                pv_step(std::integral_constant<int, 4>{}); pv_step(std::integral_constant<int, 5>{});
-                pv_step(std::integral_constant<int, 6>{}); pv_step(std::integral_constant<int, 7>{});
-                pv_step(std::integral_constant<int, 8>{}); pv_step(std::integral_constant<int, 9>{});
-                pv_step(std::integral_constant<int, 10>{}); pv_step(std::integral_constant<int, 11>{});
-                pv_step(std::integral_constant<int, 12>{});
-                float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
-                sum += other_half(sum);
+                const float sum = pv_phase([&](int kt, int e) { return __builtin_amdgcn_exp2f(kt == 0 ? s[kt][e] - mx : s[kt][e]); });
                 // O overflow: the total of this lane's 32 accumulators is finite iff all of them are (inf / NaN never turn
                 // finite again; a total that overflows from finite terms only costs a needless re-run).  Once per item,
                 // after the key loop
@@ -356,8 +323,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 bf16x8 kf[2][2][4];  // [pair parity][tile of the pair][k step]
                 auto read_k = [&](int kt, bf16x8 (&dst)[4]) {
                     if ((dbg & 1) && kt >= 2) return;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) dst[ks] = *(const bf16x8*)(Kl + (kt * 32 + r) * ROWB + (((2 * ks + hh) ^ ksw) << 4));
+                    read_k_frag(Kl, kt, r, hh, ksw, dst);
                 };
                 read_k(0, kf[0][0]);
                 read_k(1, kf[0][1]);
@@ -399,44 +365,9 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 for (int e = 0; e < 4; ++e)
                     if (e + 4 * hh < VIT_T - 192) mx = fmaxf(mx, s[6][e]);
                 mx = fmaxf(mx, other_half(mx));
-                const float nmx = PRESCALED ? -mx : -mx * sc;
-                float sum4[4] = {0.f, 0.f, 0.f, 0.f};  // four independent chains: a single one serialises 104 dependent adds
-                // P of step i (16 keys: 8 values per lane), exponentiated, summed and rounded to bf16
-                auto soft = [&](auto i_tag, bf16x8& pf) {
-                    constexpr int I = decltype(i_tag)::value;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        constexpr int kt = I >> 1;
-                        const int e = 8 * (I & 1) + j;
-                        float pv = (dbg & 8) ? s[kt][e] : __builtin_amdgcn_exp2f(PRESCALED ? s[kt][e] + nmx : fmaf(s[kt][e], sc, nmx));
-                        if (kt == 6 && !(e < 4 && e + 4 * hh < VIT_T - 192)) pv = 0.f;
-                        sum4[j & 3] += pv;
-                        pf[j] = (bf16_t)pv;
-                    }
-                };
+                const float nmx = -mx;
                 ATTN_STAMP(4)  // maximum
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.f;
-                bf16x8 pf[2];
-                read_v(0, vf[0]);
-                soft(std::integral_constant<int, 0>{}, pf[0]);
-                auto pv_step = [&](auto i_tag) {
-                    constexpr int I = decltype(i_tag)::value;
-                    if (I + 1 < 13) read_v(I + 1, vf[(I + 1) & 1]);
-                    o[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[I & 1][0]), pf[I & 1], o[0], 0, 0, 0);
-                    if constexpr (I + 1 < 13) soft(std::integral_constant<int, (I + 1 < 13 ? I + 1 : 0)>{}, pf[(I + 1) & 1]);
-                    o[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf[I & 1][1]), pf[I & 1], o[1], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                pv_step(std::integral_constant<int, 0>{}); pv_step(std::integral_constant<int, 1>{});
-                pv_step(std::integral_constant<int, 2>{}); pv_step(std::integral_constant<int, 3>{});
-                pv_step(std::integral_constant<int, 4>{}); pv_step(std::integral_constant<int, 5>{});
-                pv_step(std::integral_constant<int, 6>{}); pv_step(std::integral_constant<int, 7>{});
-                pv_step(std::integral_constant<int, 8>{}); pv_step(std::integral_constant<int, 9>{});
-                pv_step(std::integral_constant<int, 10>{}); pv_step(std::integral_constant<int, 11>{});
-                pv_step(std::integral_constant<int, 12>{});
-                float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
-                sum += other_half(sum);
+                const float sum = pv_phase([&](int kt, int e) { return (dbg & 8) ? s[kt][e] : __builtin_amdgcn_exp2f(s[kt][e] + nmx); });
                 inv = __builtin_amdgcn_rcpf(sum);
             }
             ATTN_STAMP(5)  // P.V
@@ -450,22 +381,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int rp = 0; rp < 4; rp += 2) {
-                    uint2 u0, u1;  // row groups rp and rp+1 of this lane
-                    {
-                        bf16x4 t0, t1;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            t0[j] = (bf16_t)(o[db][rp * 4 + j] * inv);
-                            t1[j] = (bf16_t)(o[db][(rp + 1) * 4 + j] * inv);
-                        }
-                        u0 = __builtin_bit_cast(uint2, t0);
-                        u1 = __builtin_bit_cast(uint2, t1);
-                    }
-                    // lower half keeps group rp and receives the upper half's group rp (dims +4..+7);
-                    // upper half keeps group rp+1 and receives the lower half's (dims +0..+3)
-                    const auto ax = __builtin_amdgcn_permlane32_swap(u0.x, u1.x, false, false);
-                    const auto ay = __builtin_amdgcn_permlane32_swap(u0.y, u1.y, false, false);
-                    const uint4 w = make_uint4(ax[0], ay[0], ax[1], ay[1]);
+                    const uint4 w = paired_o(o[db], rp, inv);
                     if (q < VIT_T) *(uint4*)(op + db * 32 + (rp + hh) * 8) = w;
                 }
             ATTN_STAMP(6)  // Q hand-over + stores issued
@@ -498,8 +414,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_t197(const bf16_t* __restrict
 
 namespace {
 
+// f(std::integral_constant<int, heads>) for the head counts the kernel is instantiated for; no other instantiation, and no stand-in
+template <typename F>
+hipError_t with_heads(int heads, F f) {
+    switch (heads) {
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+
 template <int H>
 hipError_t launch_attention_heads(const void* qkv, void* out, int B, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
+    if (B <= 0) return hipSuccess;
     // blocks of H / hsplit heads: enough of them for every CU (one workgroup fits per CU: 112 KiB of LDS); the divisors of H
     int hsplit = 1;
     for (int d = 1; d <= H; ++d) {
@@ -531,13 +459,7 @@ hipError_t launch_attention_heads(const void* qkv, void* out, int B, hipStream_t
 
 hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
     if (only_block < -1 || only_block > 6) return hipErrorInvalidValue;
-    if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // no other instantiation, and no stand-in
-    if (B <= 0) return hipSuccess;
-    switch (heads) {
-        case 6: return launch_attention_heads<6>(qkv, out, B, s, guard, force_redo, only_block, reverse);
-        case 16: return launch_attention_heads<16>(qkv, out, B, s, guard, force_redo, only_block, reverse);
-        default: return launch_attention_heads<12>(qkv, out, B, s, guard, force_redo, only_block, reverse);
-    }
+    return with_heads(heads, [&](auto h) { return launch_attention_heads<decltype(h)::value>(qkv, out, B, s, guard, force_redo, only_block, reverse); });
 }
 
 // diagnostic: the stamped build of the fast or the exact form (two buffers, one workgroup per crop); stamps = uint64[B][8 waves][8],
@@ -546,6 +468,7 @@ namespace {
 
 template <int H>
 hipError_t launch_attention_stamped_heads(const void* qkv, void* out, int B, bool fast, unsigned long long* stamps, int dbg, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
     if (!fast) {
         if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, true, 1, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
         hipLaunchKernelGGL((attn_fwd_t197<2, true, 1, H>), dim3(B), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, B, 1, stamps, dbg, (int*)nullptr, ATTN_SHARE_EXACT, (const int*)nullptr);
@@ -560,11 +483,5 @@ hipError_t launch_attention_stamped_heads(const void* qkv, void* out, int B, boo
 
 hipError_t launch_attention_stamped(const void* qkv, void* out, int B, int heads, bool fast, unsigned long long* stamps, hipStream_t s) {
     const int dbg = diag_env("MME_ATTN_DEBUG") ? atoi(diag_env("MME_ATTN_DEBUG")) : 0;
-    if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;
-    if (B <= 0) return hipSuccess;
-    switch (heads) {
-        case 6: return launch_attention_stamped_heads<6>(qkv, out, B, fast, stamps, dbg, s);
-        case 16: return launch_attention_stamped_heads<16>(qkv, out, B, fast, stamps, dbg, s);
-        default: return launch_attention_stamped_heads<12>(qkv, out, B, fast, stamps, dbg, s);
-    }
+    return with_heads(heads, [&](auto h) { return launch_attention_stamped_heads<decltype(h)::value>(qkv, out, B, fast, stamps, dbg, s); });
 }

@@ -15,7 +15,7 @@
 // to 96 head dims with zeros so that the third 32-row block of O^T is a whole MFMA).
 #include <type_traits>
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 
 namespace {
@@ -30,11 +30,17 @@ constexpr int NBUF = 3;                                                         
 constexpr int QB = 256;                                                                // queries per workgroup
 constexpr int NQB = (TV_T + QB - 1) / QB;                                              // 26
 
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
 __device__ __forceinline__ bool tv_is_pad(int tok_index, int ntile) {
     const int tile = tok_index / TV_TOKP, tok = tok_index - tile * TV_TOKP;
     return tok >= TV_TOK || tile >= ntile;
+}
+
+// Q fragments of both kernels: B operand of S^T = K . Q^T; element j of k-step ks is Q[q][16 ks + 8 hh + j] (queries past the
+// sequence end re-read the last row)
+__device__ __forceinline__ void tv_read_q(const char* base, const int q, const int hh, bf16x8 (&qf)[5]) {
+    const char* qp = base + (size_t)min(q, TV_T - 1) * TV_LD + hh * 16;
+#pragma unroll
+    for (int ks = 0; ks < 5; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 32);
 }
 
 // Schedule (round 2, second cut).  The online softmax works on GRANULES of 64 keys (two per staged tile); every wave
@@ -73,11 +79,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles(const bf16_t* __restric
 
     // Q fragments: B operand of S^T = K . Q^T; element j of k-step ks is Q[q][16 ks + 8 hh + j]
     bf16x8 qf[5];
-    {
-        const char* qp = base + (size_t)min(q, TV_T - 1) * TV_LD + hh * 16;
-#pragma unroll
-        for (int ks = 0; ks < 5; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 32);
-    }
+    tv_read_q(base, q, hh, qf);
 
     // staging: 2560 16-byte chunks per tile (128 rows x (10 of K + 10 of V)); four threads share a row and take chunks
     // q4, q4 + 4, ... q4 + 16 of its 20, so one row offset per thread addresses all five (five NAMED registers: an array
@@ -212,9 +214,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles(const bf16_t* __restric
 #pragma unroll
             for (int db = 0; db < 3; ++db) {
                 const char* va = Vl + (half * 4 + i) * 16 * VROW + v_lane_off + db * 64;
-                const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)va);
-                const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS s16x4*)(va + 8 * VROW));
-                const s16x8 vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                const s16x8 vf = read_vt_frag(va, VROW);
                 o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), pf[i], o[db], 0, 0, 0);
             }
     };
@@ -338,11 +338,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles_fast(const bf16_t* __re
     }
 
     bf16x8 qf[5];
-    {
-        const char* qp = base + (size_t)min(q, TV_T - 1) * TV_LD + hh * 16;
-#pragma unroll
-        for (int ks = 0; ks < 5; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 32);
-    }
+    tv_read_q(base, q, hh, qf);
 
     uint4 stage0, stage1, stage2, stage3, stage4;
     const int srow = tid >> 2, q4 = tid & 3;
@@ -622,16 +618,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_tiles_fast(const bf16_t* __re
 #pragma unroll
             for (int rp = 0; rp < 4; rp += 2) {
                 if (db == 2 && rp == 2) continue;
-                bf16x4 t0, t1;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    t0[j] = (bf16_t)(o[db][rp * 4 + j] * inv);
-                    t1[j] = (bf16_t)(o[db][(rp + 1) * 4 + j] * inv);
-                }
-                const uint2 u0 = __builtin_bit_cast(uint2, t0), u1 = __builtin_bit_cast(uint2, t1);
-                const auto ax = __builtin_amdgcn_permlane32_swap(u0.x, u1.x, false, false);
-                const auto ay = __builtin_amdgcn_permlane32_swap(u0.y, u1.y, false, false);
-                *(uint4*)(op + db * 32 + (rp + hh) * 8) = make_uint4(ax[0], ay[0], ax[1], ay[1]);
+                *(uint4*)(op + db * 32 + (rp + hh) * 8) = paired_o(o[db], rp, inv);
             }
     }
 }

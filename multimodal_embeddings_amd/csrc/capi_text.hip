@@ -1,6 +1,6 @@
 // C ABI of the CLIP text tower (include/mme.h, "CLIP text tower"): transformers' CLIPTextTransformer + text_projection on
 // the GEMM, LayerNorm-folding and statistics machinery of the image path, with its own row kernels (text_tower.hip) and
-// its own causal attention kernel (attention_causal.hip).  The tower lives beside the context's image tower: its record
+// its own causal attention kernel (attention_short.hip).  The tower lives beside the context's image tower: its record
 // and its workspace are here, its prepared buffers in c->allocs[text_alloc_lo, text_alloc_hi).
 #include <cstring>
 #include <new>

@@ -41,7 +41,7 @@ struct LayerDev {
 // The ViT @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
 // Supported set (validate_vit_weights, weight_load.hip): image 224, patch 16 or 32, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
 // <= 8192, 1..64 layers.
-// Patch 16 (197 tokens, the compile-time geometry of common.h) or patch 32 (50 tokens: patch32.hip, attention_t50.hip).
+// Patch 16 (197 tokens, the compile-time geometry of common.h) or patch 32 (50 tokens: patch32.hip, attention_short.hip).
 struct VitGeom {
     int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
     int patch = VIT_PATCH;

@@ -266,7 +266,7 @@ hipError_t launch_tile_output(const void* x, const void* inter, int ni, int64_t 
 hipError_t launch_tile_pool(const void* x, const void* inter, int ni, int64_t inter_stride, int n, float* emb_f32, void* emb_bf16, hipStream_t s);
 hipError_t launch_attention_tiles(const void* qkv, void* out, const int32_t* ntiles_dev, int n, hipStream_t s, int* guard = nullptr, bool force_redo = false);
 
-// ---- CLIP text tower (text_tower.hip, attention_causal.hip): 77 tokens, heads of 64, d = 512, 768 or 1024 (else
+// ---- CLIP text tower (text_tower.hip, attention_short.hip): 77 tokens, heads of 64, d = 512, 768 or 1024 (else
 // hipErrorInvalidValue)
 // x[b*77 + t, :] = bf16(f32(tok[ids[b*77 + t], :]) + pos[t, :]); tok bf16 [vocab, d], pos f32 [77, d], ids DEVICE int32 [n*77], each
 // 0 <= id < vocab (the caller validates them on the host)
@@ -277,7 +277,7 @@ hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads,
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
                                    float* y_f32, hipStream_t s);
 
-// ---- ViT/32 @224 image towers (patch32.hip, attention_t50.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64
+// ---- ViT/32 @224 image towers (patch32.hip, attention_short.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64
 // K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-32 matrix [n * 49, 3072] in conv order (c, ky, kx): a pure copy
 hipError_t launch_retile_p32(const void* patches16, void* patches32, int n, hipStream_t s);
 // acc f32 [n * 49, d] (the patch-embed GEMM under EPI_F32) -> x[b*50 + 1 + p] = bf16((acc + bias) + pos[1 + p]),

@@ -1,5 +1,5 @@
 // ViT/32 @224 (7 x 7 patches of 32 x 32, 50 tokens): the kernels the second image geometry adds beside its attention
-// kernel (attention_t50.hip).  K1, the GEMMs and the 197-token row kernels are untouched and compiled as before.
+// kernel (attention_short.hip).  K1, the GEMMs and the 197-token row kernels are untouched and compiled as before.
 //
 //   retile_patches_p32  K1 writes the bf16 patch-16 matrix [n * 196, 768] under both resize rules and every emitter form;
 //                       this kernel permutes it to the patch-32 matrix [n * 49, 3072] in conv order (c, ky, kx).  A

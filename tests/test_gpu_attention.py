@@ -503,3 +503,21 @@ def test_tile_fast_form_one_tile_jump(eng, start):
             check_sharp(qkv, 1, [4], ref, A, [(0, 0, TV_RANGE_ROWS)], dropped, "spike key dropped")
     assert not failures, "\n".join(failures)
     assert kept > 0, "every case re-ran: the fast form's own output was never checked"
+
+
+# ---- the stamped build (mme_attention_stamps): the only instantiations of K5 no other test launches --------------------
+@pytest.mark.parametrize("mode", [0, 1])
+def test_k5_stamped_build_runs_and_fills_its_slots(eng, mode):
+    """Engine.attention_stamps times the product kernel and runs the stamped build of the same form once (mode 0: the exact
+    kernel, mode 1: the fast one).  Layout (mme.h): [workgroup = crop][wave][slot]; slot 7 = heads processed; waves 0..6
+    compute (slot 3 = S^T, slot 5 = P.V); wave 7 only stages: no S^T, and its slots 5 / 6 carry the workgroup's clock pair."""
+    heads = GEOM[0][1]
+    try:
+        eng.set_attention_mode(mode)
+        _, st = eng.attention_stamps(B=2, iters=1)
+    finally:
+        eng.set_attention_mode(1)
+    assert st.shape == (2, 8, 8)
+    assert (st[:, :, 7] == heads).all(), st[:, :, 7]
+    assert (st[:, :7, 3] > 0).all() and (st[:, :7, 5] > 0).all(), st[:, :7, (3, 5)]
+    assert (st[:, 7, 5] > 0).all() and (st[:, 7, 6] > 0).all() and (st[:, 7, 3] == 0).all(), st[:, 7]

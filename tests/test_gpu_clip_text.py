@@ -1,4 +1,4 @@
-"""The CLIP text tower on the GPU (csrc/text_tower.hip, attention_causal.hip, capi_text.hip): every new kernel one launch at a
+"""The CLIP text tower on the GPU (csrc/text_tower.hip, attention_short.hip, capi_text.hip): every new kernel one launch at a
 time against numpy / float64, the prepared buffers, parity with what transformers returned (tests/golden/clip_text_cases.npz),
 bit identities, coexistence with the image tower, the public interface and the refusals.
 

@@ -6,7 +6,7 @@
 For each crop count n (chunk = n) and each of the two towers: `--warmup` untimed and `--steps` timed calls of mme_embed
 (K1 + the whole forward; at patch 32 K1 -> retile_patches_p32 -> pass), every timed call between its own pair of HIP
 events: median and range.  Then one more call under mme_profile_enable: kernel time by class.  At patch 32 the class
-"attention" is attn_fwd_t50 alone, "preprocess" is K1 + retile_patches_p32 and "layernorm" includes embed_rows_t50; the
+"attention" is attn_short<50> alone, "preprocess" is K1 + retile_patches_p32 and "layernorm" includes embed_rows_t50; the
 two kernels the patch-32 path adds in front of the encoder are also timed alone through mme_vit32_apply (median of
 `--steps` synchronous launches, so each figure includes one launch + synchronise round trip, printed beside it as the
 time of an n = 0 launch), and the f32 patch-embed GEMM [49 n, 3072] x [3072, 768] through mme_gemm_apply, beside the
