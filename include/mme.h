@@ -443,6 +443,46 @@ int mme_attention_apply(mme_ctx* ctx, int kind, const uint16_t* qkv_dev, int n, 
 int mme_crop_boxes(mme_ctx* ctx, const uint8_t* page_dev, int H, int W, const int32_t* boxes_host, int n, uint8_t* pix_dev,
                    const int64_t* offs_host, void* stream);
 
+/* ---- the 8000-pixel cap on the device: Image.resize(..., Image.LANCZOS) of 8-bit RGB, bit for bit ----------
+ * embedder.py:110-114 and :165-168 shrink an image with a side over MAX_IMAGE_HEIGHT_AND_WIDTH = 8000 with Image.LANCZOS
+ * before the processor sees it.  These three entries restate Pillow's libImaging/Resample.c (8-bit path) for that filter:
+ * lanczos(x) = sinc(x) sinc(x / 3) on -3 <= x < 3, support 3 * max(in / out, 1), 22-bit fixed-point coefficients rounded
+ * half away from zero, horizontal pass then vertical pass, each a signed 32-bit sum from 2^21, shifted arithmetically by
+ * 22 and clamped to 0..255; an axis whose size does not change is not filtered.  An image more than 100 times as high as
+ * wide that gets lower is resized vertically first, as PIL/Image.py does it.  Every output byte equals Pillow's (12.2.0).
+ * Accepted per axis: in 1..32768, out 1..8000, in / out <= 16 (ksize <= 97), upscaling included. */
+
+/* The tables of one axis (embedder.py:110-114; Resample.c precompute_coeffs + normalize_coeffs_8bpc, box = whole image).
+ * A pure host function without a context: it runs on a machine without a GPU and may be called from any thread (computed
+ * in f64 with contraction off, calling libm's sin, the function Pillow's own object code calls).
+ *   bounds  int32[out_size][2]      {xmin, n}: output coordinate xx reads source coordinates [xmin, xmin + n)
+ *   coeffs  int32[out_size][ksize]  fixed-point weights of those n coordinates, zero from n on
+ *   *ksize  2 * ceil(3 * max(in / out, 1)) + 1
+ * With bounds and coeffs both null only *ksize is written (size the arrays with it, then call again).  A refusal's text is
+ * mme_last_error(NULL). */
+int mme_lanczos_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int* ksize);
+
+/* Bytes of caller-owned device scratch that mme_lanczos_resize needs for h x w -> new_h x new_w (embedder.py:110-114;
+ * Resample.c ImagingResampleInner's intermediate image): the horizontal pass's image [h][new_w * 3 rounded up to 16]
+ * and both tables (the vertical-first order: three scratch images and four tables of an image at most 327 pixels wide).
+ * Host function without a context, any thread. */
+int mme_lanczos_workspace(int h, int w, int new_h, int new_w, size_t* bytes);
+
+/* dst = Image.fromarray(src).resize((new_w, new_h), Image.LANCZOS) (embedder.py:110-114; Resample.c ImagingResample).
+ *   src_dev   uint8 RGB HWC at ANY byte address, h rows of w pixels, src_pitch_bytes >= 3 * w apart: a box inside a
+ *             larger decoded page is a valid source
+ *   dst_dev   packed [new_h, new_w, 3], any byte address
+ *   work_dev  work_bytes >= mme_lanczos_workspace(...) of device memory, any address, owned by the caller for the
+ *             duration of the work
+ * Threading: the call uses ONLY the caller's workspace and never a buffer of the context, so it cannot meet another
+ * thread in the context's scratch tables; run it on the thread and stream that run mme_embed on its output (the embedder
+ * and the region processor launch it from their consumer thread, on the compute stream, ordered by the events that
+ * already order the pixels).  The tables are made on the host and uploaded by the call, which waits for that upload (and
+ * so for the stream's earlier work); the two kernels are asynchronous on `stream`.
+ * Geometry outside the accepted range is refused with the field, its value and the supported range; nothing is written. */
+int mme_lanczos_resize(mme_ctx* ctx, const uint8_t* src_dev, int64_t src_pitch_bytes, int h, int w, uint8_t* dst_dev, int new_h,
+                       int new_w, void* work_dev, size_t work_bytes, void* stream);
+
 /* ---- K13: merge the detector's grid passes -- class-aware non-maximum suppression ----------
  * Replaces apply_non_max_suppression / calculate_iou (3_combine_grids.py:44-137), the O(n^2) list.index / list.pop loop
  * that turns the boxes of all grid passes of a page into the page's region list: keep the highest-scoring box left (the

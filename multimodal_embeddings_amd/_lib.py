@@ -179,6 +179,10 @@ EXPORTS = {
     "mme_preprocess_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mme_crop_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_lanczos_tables": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "mme_lanczos_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "mme_lanczos_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "mme_nms_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_neighbours": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -248,6 +252,48 @@ def load_library(path: str | None = None):
 
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+LANCZOS_MAX_IN, LANCZOS_MAX_OUT, LANCZOS_MAX_RATIO = 32768, 8000, 16  # what mme_lanczos_resize accepts per axis (include/mme.h)
+
+
+def lanczos_geometry_ok(h: int, w: int, new_h: int, new_w: int) -> bool:
+    """Whether mme_lanczos_resize accepts h x w -> new_h x new_w."""
+    return all(1 <= i <= LANCZOS_MAX_IN and 1 <= o <= LANCZOS_MAX_OUT and i <= LANCZOS_MAX_RATIO * o for i, o in ((h, new_h), (w, new_w)))
+
+
+def check_lanczos_geometry(h: int, w: int, new_h: int, new_w: int):
+    """Raises MmeError naming the field, its value and the supported range, as the library does."""
+    for (iname, i), (oname, o) in ((("h", h), ("new_h", new_h)), (("w", w), ("new_w", new_w))):
+        if not 1 <= i <= LANCZOS_MAX_IN:
+            raise MmeError(f"lanczos_resize: {iname} = {i}; supported 1..{LANCZOS_MAX_IN}")
+        if not 1 <= o <= LANCZOS_MAX_OUT:
+            raise MmeError(f"lanczos_resize: {oname} = {o}; supported 1..{LANCZOS_MAX_OUT}")
+        if i > LANCZOS_MAX_RATIO * o:
+            raise MmeError(f"lanczos_resize: {iname} / {oname} = {i} / {o}; supported: a ratio of at most {LANCZOS_MAX_RATIO}")
+
+
+def lanczos_workspace(h: int, w: int, new_h: int, new_w: int) -> int:
+    """Bytes of device scratch mme_lanczos_resize needs (mme_lanczos_workspace; no GPU needed)."""
+    lib = load_library()
+    n = C.c_size_t(0)
+    if lib.mme_lanczos_workspace(int(h), int(w), int(new_h), int(new_w), C.byref(n)) != 0:
+        raise MmeError(f"mme_lanczos_workspace failed: {lib.mme_last_error(None).decode()}")
+    return int(n.value)
+
+
+def lanczos_tables(in_size: int, out_size: int):
+    """(bounds int32[out, 2] {xmin, n}, coeffs int32[out, ksize]) of one axis: Pillow's own fixed-point LANCZOS tables
+    (mme_lanczos_tables; a host function, no GPU needed)."""
+    lib = load_library()
+    ks = C.c_int(0)
+    if lib.mme_lanczos_tables(int(in_size), int(out_size), None, None, C.byref(ks)) != 0:
+        raise MmeError(f"mme_lanczos_tables failed: {lib.mme_last_error(None).decode()}")
+    bounds = np.zeros((int(out_size), 2), dtype=np.int32)
+    coeffs = np.zeros((int(out_size), ks.value), dtype=np.int32)
+    if lib.mme_lanczos_tables(int(in_size), int(out_size), bounds.ctypes.data, coeffs.ctypes.data, C.byref(ks)) != 0:
+        raise MmeError(f"mme_lanczos_tables failed: {lib.mme_last_error(None).decode()}")
+    return bounds, coeffs
 
 
 class Engine:
@@ -916,6 +962,37 @@ class Engine:
         self._check(self.lib.mme_crop_boxes(self.h, page.data_ptr(), int(page.shape[0]), int(page.shape[1]), b.ctypes.data, n,
                                             pix.data_ptr(), offs.ctypes.data, self._stream()), "mme_crop_boxes")
         return pix, offs, hw
+
+    def lanczos_resize(self, src, new_h: int, new_w: int, out=None, *, pitch=None, work=None):
+        """`Image.fromarray(src).resize((new_w, new_h), Image.LANCZOS)` on the device, bit for bit (mme_lanczos_resize: the
+        8000-pixel cap of embedder.py:110-114).  src: a uint8 CUDA tensor [h, w, 3] whose pixels are 3 bytes apart and whose
+        rows are `pitch` bytes apart (default: the tensor's own row stride, so a box sliced out of a page `page[y0:y1, x0:x1]`
+        is a valid source).  out: a uint8 CUDA buffer of new_h * new_w * 3 elements (any address), made when None.
+        work: caller-owned uint8 CUDA scratch of at least `lanczos_workspace(...)` bytes, made when None.
+        -> out as [new_h, new_w, 3].  Asynchronous on the current stream apart from the upload of the tables."""
+        t = self.torch
+        if not isinstance(src, t.Tensor) or src.dtype != t.uint8 or src.dim() != 3 or src.shape[2] != 3 or not src.is_cuda:
+            raise MmeError("lanczos_resize: src must be a uint8 CUDA tensor [h, w, 3]")
+        h, w = int(src.shape[0]), int(src.shape[1])
+        if h < 1 or w < 1 or src.stride(2) != 1 or src.stride(1) != 3:
+            raise MmeError("lanczos_resize: src must hold at least one pixel, its pixels 3 bytes apart")
+        pitch = int(src.stride(0) if pitch is None else pitch)
+        new_h, new_w = int(new_h), int(new_w)
+        check_lanczos_geometry(h, w, new_h, new_w)
+        if pitch < 3 * w:
+            raise MmeError(f"lanczos_resize: pitch = {pitch}; at least 3 * w = {3 * w} is required")
+        need = lanczos_workspace(h, w, new_h, new_w)
+        if work is None:
+            work = t.empty(need, dtype=t.uint8, device=src.device)
+        elif work.dtype != t.uint8 or not work.is_contiguous() or work.device != src.device or work.numel() < need:
+            raise MmeError(f"lanczos_resize: `work` must be a contiguous uint8 buffer of at least {need} bytes on the source's device")
+        if out is None:
+            out = t.empty((new_h, new_w, 3), dtype=t.uint8, device=src.device)
+        elif out.dtype != t.uint8 or not out.is_contiguous() or out.device != src.device or out.numel() != new_h * new_w * 3:
+            raise MmeError(f"lanczos_resize: `out` must be a contiguous uint8 buffer of {new_h} * {new_w} * 3 elements on the source's device")
+        self._check(self.lib.mme_lanczos_resize(self.h, src.data_ptr(), pitch, h, w, out.data_ptr(), new_h, new_w, work.data_ptr(), int(work.numel()),
+                                                self._stream()), "mme_lanczos_resize")
+        return out.view(new_h, new_w, 3)
 
     def nms_boxes(self, boxes, scores, classes, page_offs, iou_threshold=0.5):
         """K13 (3_combine_grids.py:80-137) over many pages: host arrays in, list of kept page-local index arrays out

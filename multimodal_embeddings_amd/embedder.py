@@ -29,7 +29,7 @@ import os
 import numpy as np
 
 from . import config
-from ._lib import Engine, MmeError  # noqa: F401
+from ._lib import Engine, MmeError, lanczos_geometry_ok, lanczos_workspace  # noqa: F401
 from .weights import TILE_VIT, VIT_B16, make_vit_weights
 
 logger = logging.getLogger("multimodal_embeddings_amd")
@@ -64,6 +64,14 @@ def convert_to_rgb(image):
     return Image.alpha_composite(background, rgba).convert("RGB")
 
 
+def capped_size(h: int, w: int):
+    """(new_h, new_w) of the 8000-pixel cap for an image with a side over it: the reference's own expression
+    (embedder.py:110-114), evaluated as Python evaluates it there.  It gives 7999 for some long sides and 0 for a short
+    side of one pixel (Pillow then raises); neither is "fixed" here."""
+    scale = config.MAX_IMAGE_HEIGHT_AND_WIDTH / max(w, h)
+    return int(h * scale), int(w * scale)
+
+
 def _load_rgb(item):
     """path | PIL.Image | uint8[h,w,3] -> contiguous uint8[h,w,3] (embedder.py:107-114)."""
     from PIL import Image
@@ -89,6 +97,44 @@ def _load_rgb(item):
     if a.shape[0] == 0 or a.shape[1] == 0:
         raise ValueError("empty image")
     return np.ascontiguousarray(a)
+
+
+class _Oversized:
+    """An RGB item over the 8000-pixel cap on its way to the device UNCAPPED: `raw` uint8[h, w, 3] as decoded, and the
+    size the reference's cap gives it.  The consumer thread shrinks it there (Engine.lanczos_resize) before the pass."""
+
+    def __init__(self, raw, new_h, new_w):
+        self.raw, self.new_h, self.new_w = raw, int(new_h), int(new_w)
+        self.shape = (self.new_h, self.new_w, 3)  # of the crop the pass sees
+        self.work = lanczos_workspace(raw.shape[0], raw.shape[1], self.new_h, self.new_w)
+        # what the item takes of a group's packed buffer: the capped image, the raw pixels and the resize's workspace
+        self.nbytes = self.new_h * self.new_w * 3 + int(raw.nbytes) + self.work
+
+
+def _load_for_device(item):
+    """`_load_rgb` for the embed pipelines: the same array for every item but one kind -- an RGB item (a uint8[h, w, 3]
+    array, a PIL / file image of mode "RGB") with a side over the cap whose geometry mme_lanczos_resize accepts comes back
+    as `_Oversized`, uncapped.  Other modes (RGBA resizes premultiplied, P / 1 resize NEAREST), geometry outside the
+    entry's range and a cap that leaves a side of zero pixels (Pillow raises) keep the host path, exactly as before."""
+    from PIL import Image
+
+    cap = config.MAX_IMAGE_HEIGHT_AND_WIDTH
+    if isinstance(item, np.ndarray):
+        a = item
+        if a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3 and min(a.shape[:2]) > 0 and max(a.shape[:2]) > cap:
+            nh, nw = capped_size(a.shape[0], a.shape[1])
+            if lanczos_geometry_ok(a.shape[0], a.shape[1], nh, nw):
+                return _Oversized(np.ascontiguousarray(a), nh, nw)
+        return _load_rgb(item)
+    image = Image.open(item) if isinstance(item, (str, os.PathLike)) else item
+    w, h = image.size
+    if image.mode == "RGB" and max(w, h) > cap:
+        nh, nw = capped_size(h, w)
+        if lanczos_geometry_ok(h, w, nh, nw):
+            raw = np.ascontiguousarray(np.asarray(image))
+            if raw.dtype == np.uint8 and raw.shape == (h, w, 3):
+                return _Oversized(raw, nh, nw)
+    return _load_rgb(image)
 
 
 class _Null:
@@ -271,6 +317,31 @@ class RegionEmbedder:
             hv[o : o + s] = a.reshape(-1)
         return host.to(device, non_blocking=True), offs, hw
 
+    def _pack_mixed(self, arrays, device):
+        """`pack` for a list that may hold device crops (uint8 CUDA tensors [h, w, 3], the capped oversized items of the serial
+        path) beside host arrays: the host arrays travel as `pack` sends them, the device crops are copied into their places."""
+        t = self.torch
+        if not any(isinstance(a, t.Tensor) for a in arrays):
+            return self.pack(arrays, device)
+        hosts = [a if not isinstance(a, t.Tensor) else np.empty((0,) + tuple(a.shape[1:]), dtype=np.uint8) for a in arrays]
+        n = len(arrays)
+        hw = np.array([a.shape[:2] for a in arrays], dtype=np.int32).reshape(n, 2)
+        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+        offs = np.zeros(n, dtype=np.int64)
+        if n > 1:
+            offs[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
+        total = int(offs[-1] + sizes[-1]) + 16
+        host = t.empty(total, dtype=t.uint8, pin_memory=t.cuda.is_available())
+        hv = host.numpy()
+        for a, o, s in zip(hosts, offs, sizes):
+            if a.shape[0]:
+                hv[o : o + s] = a.reshape(-1)
+        pix = host.to(device, non_blocking=True)
+        for a, o, s in zip(arrays, offs, sizes):
+            if isinstance(a, t.Tensor):
+                pix[int(o) : int(o + s)].copy_(a.reshape(-1))
+        return pix, offs, hw
+
     def embed_packed(self, pix, offs, hw, want_f32=True, want_bf16=True):
         """Packed crops already in HBM -> (f32 [n, embed_dim], bf16 [n, embed_dim]) CUDA tensors."""
         return self.engine.embed(pix, offs, hw, self.pool_token, want_f32=want_f32, want_bf16=want_bf16)
@@ -329,7 +400,7 @@ class RegionEmbedder:
 
     def _stage_group(self, pipe, slot, arrays, device):
         """Pack decoded crops into the slot's pinned buffer (16-byte aligned, as `pack`) and start their H2D copy on the
-        input stream.  Returns (device pixels, offs, hw).  The slot's previous occupants are out of the way: the caller
+        input stream.  Returns (device pixels, offs, hw, cap jobs).  The slot's previous occupants are out of the way: the caller
         acquired the slot after the consumer recorded `ev_done[slot]` (the pass that read the device twin)."""
         t = self.torch
         n = len(arrays)
@@ -339,23 +410,38 @@ class RegionEmbedder:
         if n > 1:
             offs[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
         total = int(offs[-1] + sizes[-1]) + 16
+        # An oversized item (_Oversized): `offs` / `hw` point at its CAPPED image, a hole the consumer thread fills on the
+        # device; its raw pixels ride behind the crops (host and device buffer), its workspace behind those (device only).
+        jobs, srcs = [], []  # jobs: (raw offset, h, w, new_h, new_w, capped offset, workspace offset, workspace bytes)
+        for k, a in enumerate(arrays):
+            if isinstance(a, _Oversized):
+                at = (total + 255) // 256 * 256
+                srcs.append((at, a.raw))
+                jobs.append([at, a.raw.shape[0], a.raw.shape[1], a.new_h, a.new_w, int(offs[k]), 0, a.work])
+                total = at + int(a.raw.nbytes)
+        total_dev = total
+        for job in jobs:
+            job[6] = (total_dev + 255) // 256 * 256
+            total_dev = job[6] + job[7]
         first_use = not pipe["used"][slot]  # per pipe state, not per call: a call that left through an exception may have
         pipe["used"][slot] = True           # work in flight on the buffers the next call finds
-        if pipe["pin"][slot] is None or pipe["pin"][slot].numel() < total:
+        if pipe["pin"][slot] is None or pipe["pin"][slot].numel() < total or pipe["dev"][slot].numel() < total_dev:
             if not first_use:  # the buffers about to be dropped may still be read: by the last H2D, by the last pass
                 pipe["ev_in"][slot].synchronize()
                 pipe["ev_done"][slot].synchronize()
-            cap = max(total, 1 << 20)
-            pipe["pin"][slot] = t.empty(cap, dtype=t.uint8, pin_memory=pipe["pinned"])
-            pipe["dev"][slot] = t.empty(cap, dtype=t.uint8, device=device)
+            pipe["pin"][slot] = t.empty(max(total, 1 << 20), dtype=t.uint8, pin_memory=pipe["pinned"])
+            pipe["dev"][slot] = t.empty(max(total_dev, 1 << 20), dtype=t.uint8, device=device)
         elif not first_use:
             pipe["ev_in"][slot].synchronize()  # the last H2D out of this pinned buffer has finished (long ago)
         hv = pipe["pin"][slot].numpy()
+        for at, raw in srcs:
+            hv[at : at + raw.nbytes] = raw.reshape(-1)
 
         def copy_range(lo, hi):  # large numpy copies release the GIL: a few threads fill the buffer side by side
             for k in range(lo, hi):
-                o, sz = int(offs[k]), int(sizes[k])
-                hv[o : o + sz] = arrays[k].reshape(-1)
+                if not isinstance(arrays[k], _Oversized):
+                    o, sz = int(offs[k]), int(sizes[k])
+                    hv[o : o + sz] = arrays[k].reshape(-1)
 
         nbytes = int(sizes.sum())
         workers = min(4, os.cpu_count() or 1, max(1, nbytes >> 26))  # one thread per 64 MB, at most four
@@ -371,7 +457,15 @@ class RegionEmbedder:
                 pipe["in_stream"].wait_event(pipe["ev_done"][slot])  # the pass that read the device twin has run
             pipe["dev"][slot][:total].copy_(pipe["pin"][slot][:total], non_blocking=True)
             pipe["ev_in"][slot].record(pipe["in_stream"])
-        return pipe["dev"][slot][:total], offs, hw
+        return pipe["dev"][slot][:total_dev], offs, hw, jobs
+
+    @staticmethod
+    def _run_cap_jobs(engine, pix, jobs):
+        """The device cap of a staged group's oversized items, on the calling thread's current stream: raw pixels ->
+        LANCZOS -> the hole `offs` points at, each through its own workspace inside `pix`.  The caller is the thread that
+        runs the pass over `pix` next (mme_lanczos_resize uses no buffer of the context)."""
+        for at, h, w, nh, nw, dst, work, work_bytes in jobs:
+            engine.lanczos_resize(pix[at : at + h * w * 3].view(h, w, 3), nh, nw, out=pix[dst : dst + nh * nw * 3], work=pix[work : work + work_bytes])
 
     def _embed_list(self, dev_idx, items):
         """One context's share of a call: [(index, item)] -> [(index, list[float] | None)] (embedder.py:86-139).
@@ -402,7 +496,7 @@ class RegionEmbedder:
         def load(pair):
             i, item = pair
             try:
-                return i, _load_rgb(item)
+                return i, _load_for_device(item)
             except Exception as e:  # embedder.py:135-137
                 logger.error(f"Error processing image {item if isinstance(item, (str, os.PathLike)) else type(item)}: {e}")
                 return i, None
@@ -479,10 +573,11 @@ class RegionEmbedder:
                     if msg[0] == "failed":
                         results.extend((i, None) for i in msg[1])
                         continue
-                    _, slot, idx, (pix, offs, hw) = msg
+                    _, slot, idx, (pix, offs, hw, jobs) = msg
                     n = len(idx)
                     try:
                         compute.wait_event(pipe["ev_in"][slot])
+                        self._run_cap_jobs(engine, pix, jobs)  # this thread, the compute stream: ordered before the pass
                         e32, _ = engine.embed(pix, offs, hw, self.pool_token, want_bf16=False)
                         pipe["ev_done"][slot].record(compute)
                     except Exception as e:  # embedder.py:223-224
@@ -529,16 +624,23 @@ class RegionEmbedder:
         def load(pair):
             i, item = pair
             try:
-                return i, _load_rgb(item)
+                return i, _load_for_device(item)
             except Exception as e:  # embedder.py:135-137
                 logger.error(f"Error processing image {item if isinstance(item, (str, os.PathLike)) else type(item)}: {e}")
                 return i, None
+
+        def cap(a):  # an oversized RGB item is shrunk on the device, by this thread, before it is packed with the others
+            if not isinstance(a, _Oversized):
+                return a
+            with self._on(device):
+                raw = self.torch.from_numpy(a.raw).to(device)
+                return engine.lanczos_resize(raw, a.new_h, a.new_w)
 
         def run(group):
             if not group:
                 return
             try:
-                pix, offs, hw = self.pack([a for _, a in group], device)
+                pix, offs, hw = self._pack_mixed([cap(a) for _, a in group], device)
                 if getattr(self, "encoder", "vit_b16") == "mllama_tiles":  # processor (K1 multi-tile) + vision tower, class token of tile 0 (7680-d)
                     pv, ids, _, nt = engine.preprocess_tiles(pix, offs, hw, 560, 4)
                     _, e32, _ = engine.tile_vit_forward(pv, ids, nt, want_bf16=False)

@@ -125,9 +125,49 @@ class RegionProcessor:
         """page: path | PIL image | uint8[H,W,3]; int_boxes int32[n,4] -> float32 CUDA tensor [n, embed_dim].
 
         Boxes of zero or negative size (which make the reference's PNG save fail, :115-117) raise."""
-        pix, offs, hw = self.embedder.engine.crop_boxes(self._page_to_device(page), int_boxes)
+        pix, offs, hw = self._cut_boxes(self._page_to_device(page), np.asarray(int_boxes, dtype=np.int32).reshape(-1, 4))
         e32, _ = self.embedder.embed_packed(pix, offs, hw, want_bf16=False)
         return e32
+
+    @staticmethod
+    def _crop_sizes(b, page_h, page_w):
+        """(h, w) int32[n, 2] of the crops the boxes `b` become in the packed buffer.  A box with a side over 8000 px is what
+        the reference embeds after its cap (get_region_image -> PNG -> Image.open -> LANCZOS, embedder.py:110-114): it
+        takes the capped size, provided it lies wholly inside the page and mme_lanczos_resize accepts the geometry;
+        otherwise MmeError (the page fails alone, as before)."""
+        from ._lib import lanczos_geometry_ok
+        from .embedder import capped_size
+
+        hw = np.stack([b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]], axis=1).astype(np.int32)
+        for k in np.nonzero(hw.max(axis=1) > config.MAX_IMAGE_HEIGHT_AND_WIDTH)[0]:
+            x0, y0, x1, y1 = (int(v) for v in b[k])
+            h, w = int(hw[k, 0]), int(hw[k, 1])
+            if x0 < 0 or y0 < 0 or x1 > page_w or y1 > page_h:
+                raise MmeError(f"a region is {max(h, w)} px long and reaches outside the page (supported: 8000, or an oversized box inside the page)")
+            nh, nw = capped_size(h, w)
+            if min(h, w) < 1 or not lanczos_geometry_ok(h, w, nh, nw):
+                raise MmeError(f"a region of {h}x{w} px (h x w) caps to {nh}x{nw}, which the device resize does not take")
+            hw[k] = (nh, nw)
+        return hw
+
+    def _cut_boxes(self, page_dev, b, out=None, base: int = 0):
+        """`Engine.crop_boxes` for boxes that may be oversized: K0 cuts the ordinary boxes, and an oversized box inside the
+        page is resized straight out of the device page (pitch = the page's row) into its place in the packed buffer.
+        Called on the thread and stream that run the pass over the buffer (the consumer thread of `process_regions`)."""
+        engine = self.embedder.engine
+        hw = self._crop_sizes(b, int(page_dev.shape[0]), int(page_dev.shape[1]))
+        big = np.nonzero((hw[:, 0] != b[:, 3] - b[:, 1]) | (hw[:, 1] != b[:, 2] - b[:, 0]))[0]
+        if not len(big):
+            return engine.crop_boxes(page_dev, b, out=out, base=base)
+        stand = b.copy()  # K0 lays the buffer out for the capped sizes; what it copies into those places is overwritten below
+        for k in big:
+            stand[k] = (0, 0, hw[k, 1], hw[k, 0])
+        pix, offs, hw_cut = engine.crop_boxes(page_dev, stand, out=out, base=base)
+        for k in big:
+            x0, y0, x1, y1 = (int(v) for v in b[k])
+            nh, nw = int(hw[k, 0]), int(hw[k, 1])
+            engine.lanczos_resize(page_dev[y0:y1, x0:x1], nh, nw, out=pix[int(offs[k]) : int(offs[k]) + nh * nw * 3])
+        return pix, offs, hw_cut
 
     def _page_rows(self, image_path, regions):
         """Rows of one page that will be embedded: (ids, metas, boxes, good) with the reference's warnings (:85-87)."""
@@ -329,9 +369,10 @@ class RegionProcessor:
                         if not good:
                             continue
                         b = boxes[good]
-                        side = np.stack([b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]], axis=1)
-                        if side.max() > 8000:  # mme_crop_boxes' limit (the embedder's own 8000-px cap, embedder.py:110-114)
-                            logger.error(f"Error in batch processing: a region of {image_filename} is {int(side.max())} px long (supported: 8000)")
+                        try:  # an oversized box inside the page takes its capped size (embedder.py:110-114); any other fails the page
+                            side = self._crop_sizes(b, int(arr.shape[0]), int(arr.shape[1]))
+                        except MmeError as e:
+                            logger.error(f"Error in batch processing: {image_filename}: {e}")
                             continue
                         nbytes = int(((side[:, 0].astype(np.int64) * side[:, 1] * 3 + 15) // 16 * 16).sum())
                         if cur is not None and cur["pages"] and (cur["crop_bytes"] + nbytes > self.WAVE_BYTES
@@ -397,7 +438,7 @@ class RegionProcessor:
                         path, ids, metas, good, b, at, shape = page
                         nb = int(shape[0]) * int(shape[1]) * int(shape[2])
                         try:
-                            _, offs, hw = engine.crop_boxes(pipe["arena"][slot][at : at + nb].view(shape), b, out=pipe["pix"], base=base)
+                            _, offs, hw = self._cut_boxes(pipe["arena"][slot][at : at + nb].view(shape), b, out=pipe["pix"], base=base)
                         except (MmeError, ValueError) as e:
                             logger.error(f"Error in batch processing: {e}")  # this page's regions fail, the wave goes on
                             continue
