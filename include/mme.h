@@ -144,9 +144,37 @@ typedef struct {
 } mme_clip_weights;
 int mme_load_clip(mme_ctx* ctx, const mme_clip_weights* w);
 int mme_load_clip_as(mme_ctx* ctx, const mme_clip_weights* w, int dtype, void* stream);
-/* out[4] = kind (0 ViT, 1 CLIP), embed_dim (the row width the forward writes), act (0 erf-GELU, 1 QuickGELU), proj_dim (0: none)
+/* out[4] = kind (0 ViT, 1 CLIP, 2 SigLIP), embed_dim (the row width the forward writes), act (0 erf-GELU, 1 QuickGELU, 2 tanh-GELU), proj_dim (0: none)
  * of the context's encoder: what the last load brought, {0, 768, 0, 0} before any. */
 int mme_encoder_info(mme_ctx* ctx, int32_t out[4]);
+
+/* ---- SigLIP ViT/16 image towers ------------------------------------------------------------------------------------------
+ * Replaces `SiglipVisionModel.from_pretrained(dir)(pixel_values).pooler_output`, L2-normalised, for the towers at this
+ * engine's geometry: 224 pixels, patch 16, heads of 64 (siglip-base-patch16-224 and its re-trainings).  The tower is the
+ * CLIP image tower's pre-LN block sequence with these differences (transformers models/siglip/modeling_siglip.py):
+ *   - SiglipVisionEmbeddings: no class token and no LayerNorm before layer 0: 196 tokens; the patch convolution HAS a bias;
+ *     vit.cls_token must be NULL, vit.pos_emb is position_embedding.weight [196, hidden];
+ *   - SiglipMLP: `gelu_pytorch_tanh`, 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (act 2 of mme_encoder_info);
+ *   - post_layernorm (vit.lnf_g / lnf_b) over EVERY token row, then SiglipMultiheadAttentionPoolingHead:
+ *     a = MultiheadAttention(probe, h, h) with in_proj split into head.q_w | k_w | v_w [hidden, hidden] and q_b | k_b | v_b,
+ *     heads of 64, out_proj = head.o_w / o_b; y = a + mlp(layernorm(a)) with head.ln2_g / ln2_b, head.fc1_*, head.fc2_* (the
+ *     tower's mlp width and activation); pooler_output = y.  head.ln1_g / ln1_b are not read.
+ * mme_vit_forward / mme_embed write y / max(||y||, 1e-12), rows of `hidden`; pool_token is checked (0..195) and ignored;
+ * mme_set_forward_pruning has no effect (the head reads every token row); mme_preprocess writes [n * 196, 768] as for
+ * patch 16.  Validation as for the ViT loader with patch_size 16 only; a refusal names the field, the value found and
+ * the supported set, and nothing in the context changes.  The ..._as form takes the checkpoint's own element type.
+ * Prepared buffers (mme_weights_read): the ViT's 6 + 18 L in their order (cls a zero table), then the head's ln2_g, ln2_b,
+ * K | V bf16 [2 D, D], their bias [2 D], K | V with post_layernorm folded in (bf16 [2 D, D], column sums [2 D], bias' [2 D]),
+ * three buffers of the query (bf16 [D, D] and f32 [D], not read; then the constant query f32 [D] =
+ * (probe . W_q^T + b_q) dh^-0.5 log2 e), o_w, o_b, fc1_w, fc1_b, the fc1 fold (3), fc2_w, fc2_b: 6 + 18 L + 19.
+ * A later ViT or CLIP load on the same context returns it to that form. */
+typedef struct {
+    mme_vit_weights vit;   /* cls_token NULL; pos_emb [196, hidden]; patch_size 16 */
+    const float* probe;    /* head.probe, [hidden] */
+    mme_vit_layer head;    /* ln1_g / ln1_b unused (NULL) */
+} mme_siglip_weights;
+int mme_load_siglip(mme_ctx* ctx, const mme_siglip_weights* w);
+int mme_load_siglip_as(mme_ctx* ctx, const mme_siglip_weights* w, int dtype, void* stream);
 
 /* ---- CLIP text tower ------------------------------------------------------------------------------------------------------
  * Replaces `CLIPTextModelWithProjection.from_pretrained(dir)(input_ids).text_embeds` (or `CLIPTextModel`'s pooler_output
@@ -838,6 +866,35 @@ typedef struct mme_vit32_apply_args {
     float eps;
 } mme_vit32_apply_args;
 int mme_vit32_apply(mme_ctx* ctx, int op, const mme_vit32_apply_args* args, void* stream);
+
+/* Diagnostic: ONE launch of a kernel a SigLIP tower adds, on the caller's device buffers, synchronous; works on a bare context.
+ * (The 196-token attention kernel is launched by mme_attention_apply kind 0 under a SigLIP context.)  n = crops.
+ *   op 0 the GEMM of `gemm` with out = bf16(gelu_tanh(acc + bias[n])), gelu_tanh(x) = 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)));
+ *        gemm->epilogue is not read; operands and preconditions as epilogue 1 of mme_gemm_apply
+ *      1 the same with the folded LayerNorm first: gelu_tanh(rstd[m] * (acc - mean[m] * colsum[n]) + bias[n]), as epilogue 6
+ *      2 embed_rows_t196  acc f32 [n * 196, d] -> x bf16 [n * 196, d]: x[b * 196 + p] = bf16((acc[b * 196 + p] + bias) + pos[p]),
+ *                         pos f32 [196, d], f32 adds in that order
+ *      3 map_pool         kv bf16 [n * 196, 2 * 64 * heads] (K | V), q f32 [64 * heads] (in log2 units: dh^-0.5 log2 e applied) ->
+ *                         out bf16 [n, 64 * heads]: per (crop, head) softmax_j(q_h . k_j) . v, exact maximum, f32 sums, one rounding
+ *      4 l2_rows_bf16     x bf16 [n, d] -> x / max(||x||, 1e-12) to emb_f32 and / or emb_bf16 [n, d]
+ * Preconditions (else MME_E_ARG, nothing launched): op 0..4; ops 0, 1: `gemm` non-null and what the GEMM diagnostic asks of
+ * epilogues 1 / 6; ops 2..4: 0 <= n <= 2^20, every tensor the op reads or writes non-null and 16-byte aligned (op 4: one of
+ * the two outputs may be NULL); ops 2, 4: d == 384, 768 or 1024; op 3: heads == 6, 12 or 16. */
+typedef struct mme_siglip_apply_args {
+    const mme_gemm_apply_args* gemm; /* ops 0, 1 */
+    int32_t* ran_256;       /* ops 0, 1, optional: set to 1 when the 256 x 256 kernel ran, 0 for the 128 x 128 one */
+    const float* acc;       /* op 2 */
+    const float* bias;
+    const float* pos;
+    uint16_t* x;            /* op 2: out; op 4: in */
+    const uint16_t* kv;     /* op 3 */
+    const float* q;
+    uint16_t* out;
+    float* emb_f32;         /* op 4 */
+    uint16_t* emb_bf16;
+    int32_t n, d, heads;
+} mme_siglip_apply_args;
+int mme_siglip_apply(mme_ctx* ctx, int op, const mme_siglip_apply_args* args, void* stream);
 
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
  * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,

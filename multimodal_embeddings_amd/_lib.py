@@ -106,6 +106,15 @@ class _Vit32ApplyArgs(C.Structure):  # mme_vit32_apply_args
         (n, C.c_int32) for n in ("n", "d", "heads", "only_block", "tok")] + [("eps", C.c_float)]
 
 
+class _SiglipWeights(C.Structure):  # mme_siglip_weights
+    _fields_ = [("vit", _Weights), ("probe", C.POINTER(C.c_float)), ("head", _Layer)]
+
+
+class _SiglipApplyArgs(C.Structure):  # mme_siglip_apply_args
+    _fields_ = [("gemm", C.POINTER(_GemmApplyArgs)), ("ran_256", C.POINTER(C.c_int32))] + [
+        (n, C.c_void_p) for n in ("acc", "bias", "pos", "x", "kv", "q", "out", "emb_f32", "emb_bf16")] + [(n, C.c_int32) for n in ("n", "d", "heads")]
+
+
 class _TileRowopApplyArgs(C.Structure):  # mme_tile_rowop_apply_args
     _fields_ = [(n, C.c_void_p) for n in ("pv", "patches", "pemb", "cls", "pre", "pos", "tilepos", "gamma", "beta", "post", "aid", "x", "inter", "hidden",
                                           "emb_f32", "emb_bf16")] + [
@@ -143,6 +152,9 @@ EXPORTS = {
     "mme_encoder_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_clip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_ClipApplyArgs), C.c_void_p]),
     "mme_vit32_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_Vit32ApplyArgs), C.c_void_p]),
+    "mme_load_siglip": (C.c_int, [C.c_void_p, C.POINTER(_SiglipWeights)]),
+    "mme_load_siglip_as": (C.c_int, [C.c_void_p, C.POINTER(_SiglipWeights), C.c_int, C.c_void_p]),
+    "mme_siglip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_SiglipApplyArgs), C.c_void_p]),
     "mme_load_clip_text": (C.c_int, [C.c_void_p, C.POINTER(_ClipTextWeights)]),
     "mme_load_clip_text_as": (C.c_int, [C.c_void_p, C.POINTER(_ClipTextWeights), C.c_int, C.c_void_p]),
     "mme_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -396,12 +408,13 @@ class Engine:
         return ViTGeometry(image_size=g[0], patch_size=g[1], hidden_size=g[2], num_layers=g[3], num_heads=g[4], intermediate_size=g[5])
 
     def encoder_info(self) -> dict:
-        """What the last load brought (mme_encoder_info): {"kind": "vit" | "clip", "embed_dim", "hidden_act", "projection_dim"}."""
+        """What the last load brought (mme_encoder_info): {"kind": "vit" | "clip" | "siglip", "embed_dim", "hidden_act", "projection_dim"}."""
         from .weights import CLIP_ACTS
 
         o = (C.c_int32 * 4)()
         self._check(self.lib.mme_encoder_info(self.h, o), "mme_encoder_info")
-        return {"kind": ("vit", "clip")[o[0]], "embed_dim": int(o[1]), "hidden_act": CLIP_ACTS[o[2]], "projection_dim": int(o[3]) or None}
+        acts = CLIP_ACTS + ("gelu_pytorch_tanh",)  # the library's act codes: 0, 1 (mme_clip_weights.act), 2 (SigLIP)
+        return {"kind": ("vit", "clip", "siglip")[o[0]], "embed_dim": int(o[1]), "hidden_act": acts[o[2]], "projection_dim": int(o[3]) or None}
 
     @property
     def embed_dim(self) -> int:
@@ -475,6 +488,89 @@ class Engine:
             raise MmeError(f"load_clip_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
         W, layers = self._clip_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
         self._check(self.lib.mme_load_clip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_clip_as")
+
+    # ---- SigLIP image towers (mme_load_siglip*) ---------------------------------------------------------------
+    @staticmethod
+    def _siglip_struct(geom, arr):
+        """mme_siglip_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.SiglipGeometry), tensor
+        pointers from arr(name, first_element = 0) over the names of weights.siglip_tensor_specs.  in_proj_weight [3 D, D] and
+        in_proj_bias [3 D] are split q | k | v by element offset."""
+        from .weights import siglip_geometry_problem
+
+        bad = siglip_geometry_problem(geom)
+        if bad and bad[0] in ("hidden_act", "vision_use_head"):  # the two fields the C struct does not carry
+            raise MmeError(f"{bad[0]} = {bad[1]!r}; supported: {bad[2]}")
+        v = "vision_model."
+        D = geom.hidden_size
+        layers = (_Layer * geom.num_layers)()
+        for i in range(geom.num_layers):
+            p = f"{v}encoder.layers.{i}."
+            L = layers[i]
+            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
+            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
+            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
+            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
+            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
+            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
+            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
+            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+        W = _SiglipWeights()
+        W.vit = _Weights(geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
+                         float(geom.layer_norm_eps))
+        W.vit.cls_token = None  # SiglipVisionEmbeddings: no class token
+        W.vit.pos_emb = arr(v + "embeddings.position_embedding.weight")
+        W.vit.patch_w = arr(v + "embeddings.patch_embedding.weight")
+        W.vit.patch_b = arr(v + "embeddings.patch_embedding.bias")
+        W.vit.lnf_g, W.vit.lnf_b = arr(v + "post_layernorm.weight"), arr(v + "post_layernorm.bias")
+        W.vit.layer = layers
+        h = v + "head."
+        W.probe = arr(h + "probe")
+        H = W.head
+        H.ln1_g = H.ln1_b = None
+        H.q_w, H.k_w, H.v_w = (arr(h + "attention.in_proj_weight", i * D * D) for i in range(3))
+        H.q_b, H.k_b, H.v_b = (arr(h + "attention.in_proj_bias", i * D) for i in range(3))
+        H.o_w, H.o_b = arr(h + "attention.out_proj.weight"), arr(h + "attention.out_proj.bias")
+        H.ln2_g, H.ln2_b = arr(h + "layernorm.weight"), arr(h + "layernorm.bias")
+        H.fc1_w, H.fc1_b = arr(h + "mlp.fc1.weight"), arr(h + "mlp.fc1.bias")
+        H.fc2_w, H.fc2_b = arr(h + "mlp.fc2.weight"), arr(h + "mlp.fc2.bias")
+        return W, layers
+
+    def load_siglip(self, w: dict, geom=None):
+        """`weights.siglip_tensor_specs` dict of f32 arrays (the vision state dict of transformers' SiglipModel) -> this
+        context, replacing what it held.  `geom`: a weights.SiglipGeometry; by default read off the tensor shapes, eps 1e-6."""
+        from .weights import infer_siglip_geometry, siglip_tensor_specs
+
+        if geom is None:
+            geom = infer_siglip_geometry(w)
+        for name, shape, _ in siglip_tensor_specs(geom):
+            if name not in w:
+                raise MmeError(f"load_siglip: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"load_siglip: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = {}
+
+        def arr(name, first=0):
+            if name not in keep:
+                keep[name] = np.ascontiguousarray(w[name], dtype=np.float32).reshape(-1)
+            return _fp(keep[name][first:])
+
+        W, layers = self._siglip_struct(geom, arr)
+        self._check(self.lib.mme_load_siglip(self.h, C.byref(W)), "mme_load_siglip")
+
+    def load_siglip_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "siglip")` -> this context, prepared on the device from the file's own f32 / bf16 /
+        f16 bytes, bit-identically to `load_siglip` on the same values.  Replaces what the context held."""
+        if ckpt.encoder != "siglip":
+            raise MmeError(f"load_siglip_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+
+        def arr(name, first=0):
+            t = ckpt.tensors[name]
+            if not t.is_contiguous() or t.device.type != "cpu":
+                raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
+            return C.cast(C.c_void_p(t.data_ptr() + first * t.element_size()), C.POINTER(C.c_float))
+
+        W, layers = self._siglip_struct(ckpt.geometry, arr)
+        self._check(self.lib.mme_load_siglip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_siglip_as")
 
     # ---- CLIP text tower (mme_load_clip_text*): lives beside the image tower of the same context ----------------------------
     @staticmethod
@@ -808,6 +904,8 @@ class Engine:
         T, H, dh = self._ATTN_KINDS[kind]
         if H is None:
             H = self.vit_geometry().num_heads
+            if self.encoder_info()["kind"] == "siglip":  # no class token: the kernel's 196-token instantiation
+                T = 196
         if qkv.dtype != t.bfloat16 or not qkv.is_contiguous() or qkv.dim() != 2 or qkv.shape[1] != 3 * H * dh or qkv.shape[0] % T:
             raise MmeError(f"attention: qkv must be a contiguous bf16 [n * {T}, {3 * H * dh}] tensor")
         n = qkv.shape[0] // T
@@ -892,6 +990,34 @@ class Engine:
         ran = C.c_int32(-1)
         a.ran_256 = C.pointer(ran)
         self._check(self.lib.mme_clip_apply(self.h, code, C.byref(a), self._stream()), "mme_clip_apply")
+        return bool(ran.value) if g is not None else None
+
+    SIGLIP_OPS = {"gemm_tgelu": 0, "gemm_ln_tgelu": 1, "embed_rows": 2, "map_pool": 3, "l2_bf16": 4}
+
+    def siglip_apply(self, op, *, A=None, W=None, M=None, N=None, K=None, variant: int = 0, reverse_m: int = 0, bias=None, out=None, ldo=None,
+                     ln_stats=None, colsum=None, acc=None, pos=None, x=None, kv=None, q=None, emb_f32=None, emb_bf16=None, n: int = 0, d: int = 768,
+                     heads: int = 12):
+        """ONE launch of a kernel a SigLIP tower adds, on the caller's CUDA tensors (mme_siglip_apply; synchronous, works on a
+        bare context).  op: a name of SIGLIP_OPS or its code.  The GEMM ops take A bf16 [M, K], W bf16 [N, K], bias, out
+        (+ ln_stats, colsum) as `gemm_apply`; the others the tensors include/mme.h lists (`bias` and `out` serve both).  The
+        library validates.  -> for the GEMM ops, True when the 256 x 256 kernel ran; None otherwise."""
+        code = int(self.SIGLIP_OPS.get(op, op))
+        a = _SiglipApplyArgs()
+        g = None
+        if A is not None or W is not None:
+            g = _GemmApplyArgs()
+            g.variant, g.reverse_m = int(variant), int(reverse_m)
+            g.M = int(A.shape[0] if M is None else M)
+            g.N = int(W.shape[0] if N is None else N)
+            g.K = int(A.shape[1] if K is None else K)
+            g.A, g.W, g.bias, g.out, g.ln_stats, g.colsum = (self._ptr(t) for t in (A, W, bias, out, ln_stats, colsum))
+            g.ldo = int(g.N if ldo is None else ldo)
+            a.gemm = C.pointer(g)
+        a.acc, a.bias, a.pos, a.x, a.kv, a.q, a.out, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (acc, bias, pos, x, kv, q, out, emb_f32, emb_bf16))
+        a.n, a.d, a.heads = int(n), int(d), int(heads)
+        ran = C.c_int32(-1)
+        a.ran_256 = C.pointer(ran)
+        self._check(self.lib.mme_siglip_apply(self.h, code, C.byref(a), self._stream()), "mme_siglip_apply")
         return bool(ran.value) if g is not None else None
 
     VIT32_OPS = {"retile": 0, "embed_rows": 1, "attention": 2, "pool_ln": 3, "pool_ln_l2": 4}

@@ -9,12 +9,13 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
 -- checks that its configuration is a geometry the library is built for ("vit_b16": exactly ViT-B/16; "vit": any of the
 supported ViT/16 and ViT/32 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "clip": a CLIP image tower of that family,
 `CLIPVisionModel[WithProjection]` or the vision half of a whole `CLIPModel`; "clip_text": a CLIP text tower,
-`CLIPTextModel[WithProjection]` or the text half of a whole `CLIPModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
+`CLIPTextModel[WithProjection]` or the text half of a whole `CLIPModel`; "siglip": a SigLIP ViT/16 @224 image tower with its
+attention-pooling head, `SiglipVisionModel` or the vision half of a whole `SiglipModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
 bytes to the device, where they are converted and folded (csrc/weight_load.hip: DevPrep; kernels in csrc/weight_prep.hip).
 
-    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text]
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text|siglip_vit]
 
 prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
 """
@@ -29,13 +30,17 @@ from dataclasses import dataclass, field
 
 from . import config
 from ._lib import MmeError
-from .weights import (CLIP_B16, CLIP_TEXT_B, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, TileViTGeometry, ViTGeometry, clip_geometry_problem,
-                      clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem,
-                      vit_tensor_specs)
+from .weights import (CLIP_B16, CLIP_TEXT_B, SIGLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, SiglipGeometry, TileViTGeometry, ViTGeometry,
+                      clip_geometry_problem, clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, siglip_geometry_problem,
+                      siglip_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem, vit_tensor_specs)
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text")
+ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip")
+# The command line below and RegionEmbedder spell the SigLIP tower "siglip_vit": both have always refused the bare name
+# "siglip" as an unknown encoder and keep doing so; read_checkpoint, Checkpoint.encoder and the Engine say "siglip".
+SIGLIP_ALIAS = "siglip_vit"
+CLI_ENCODERS = tuple(SIGLIP_ALIAS if e == "siglip" else e for e in ENCODERS)
 VIT_ENCODERS = ("vit_b16", "vit")  # one loader, one tensor layout; "vit" takes its geometry from config.json
 SUPPORTED_ASPECT_RATIOS = [[1, 1], [1, 2], [1, 3], [1, 4], [2, 1], [2, 2], [3, 1], [4, 1]]
 _DTYPE_IDS = {"float32": 0, "bfloat16": 1, "float16": 2}  # include/mme.h MME_DT_*
@@ -126,6 +131,17 @@ def canonical_clip_text_name(key: str):
     return key
 
 
+def canonical_siglip_name(key: str):
+    """Checkpoint key -> canonical name (`weights.siglip_tensor_specs`: the vision keys of a `SiglipModel`), or None for what
+    the image tower does not use: the text tower, logit_scale, logit_bias, the position_ids buffers."""
+    if key.startswith("text_model.") or key in ("logit_scale", "logit_bias") or key.endswith(".position_ids"):
+        return None
+    # SiglipVisionModel.save_pretrained of transformers 5 writes the tower's own keys, without the "vision_model." prefix
+    if key.startswith(("embeddings.", "encoder.layers.", "post_layernorm.", "head.")):
+        return "vision_model." + key
+    return key
+
+
 def canonical_tile_name(key: str):
     """Checkpoint key -> canonical name, or None for a key outside the vision tower."""
     for prefix in ("model.vision_model.", "vision_model."):
@@ -200,6 +216,24 @@ def _clip_geometry(cfg: dict, where: str, projection_dim) -> CLIPGeometry:
     return g
 
 
+def _siglip_geometry(cfg: dict, where: str) -> SiglipGeometry:
+    """The vision configuration of a SigLIP checkpoint (SiglipVisionConfig) -> geometry: patch 16 at 224 pixels, heads of 64,
+    `gelu_pytorch_tanh`, the pooling head.  A field the file leaves out has SiglipVisionConfig's default, except the sizes."""
+    b = SIGLIP_B16
+    for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
+        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
+            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
+    g = SiglipGeometry(image_size=cfg["image_size"], patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels),
+                       hidden_size=cfg["hidden_size"], num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"],
+                       intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)),
+                       hidden_act=cfg.get("hidden_act", b.hidden_act), vision_use_head=cfg.get("vision_use_head", True))
+    bad = siglip_geometry_problem(g)
+    if bad:
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    return g
+
+
 def _clip_text_geometry(cfg: dict, where: str, projection_dim) -> CLIPTextGeometry:
     """The text configuration of a CLIP checkpoint (CLIPTextConfig) -> geometry.  A field the file leaves out has
     CLIPTextConfig's default (clip-vit-base-patch16's text tower), as transformers reads it."""
@@ -241,7 +275,7 @@ def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
 
 
 RESIZE_RULES = ("fit_pad", "clip")  # _lib.Engine.RESIZE_RULES / MME_RESIZE_* (include/mme.h)
-CLIP_RULE_ENCODERS = ("vit_b16", "vit", "clip")  # the single-tile encoders K1's "clip" rule feeds
+CLIP_RULE_ENCODERS = ("vit_b16", "vit", "clip", "siglip")  # the single-tile encoders K1's "clip" rule feeds
 
 
 def check_resize_rule(resize_rule, encoder: str) -> str:
@@ -289,6 +323,14 @@ def _read_preprocessor(path: str, encoder: str, resize_rule: str = "fit_pad"):
         return _mean_std(pc, where)
     resample = pc.get("resample", 2)
     clip_rule = encoder == "clip" and (resample == 3 or pc.get("do_center_crop") or "crop_size" in pc)
+    if encoder == "siglip":
+        # SiglipImageProcessor resizes to size x size WITHOUT keeping the aspect (any resample): not a rule K1 has
+        if "Siglip" in str(pc.get("image_processor_type", "")) or resample != 2:
+            named = [f"{k} = {pc[k]!r}" for k in ("image_processor_type", "resample", "size") if k in pc]
+            logger.warning(f"{where}: {', '.join(named) or 'the file'} asks for SigLIP's own preprocessing, a plain resize to 224 x 224 that does not keep the "
+                           "aspect ratio; K1 does not run that rule: it keeps the aspect-preserving fit into 224 x 224 with zero padding "
+                           "(or resize_rule='clip' on request) and applies only the checkpoint's image_mean / image_std")
+        return _mean_std(pc, where)
     if resample != 2 and not (encoder == "clip" and resample == 3):
         raise MmeError(f"{where}: resample = {resample!r}; K1 resizes with Pillow BILINEAR (resample = 2) only")
     if encoder == "mllama_tiles":
@@ -422,6 +464,13 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         geometry = _clip_geometry(vcfg, where, vcfg.get("projection_dim"))
         canonical = canonical_clip_name
         specs = None  # after the tensors are read: a CLIPVisionModel checkpoint has no visual_projection
+    elif encoder == "siglip":
+        where, vcfg = "config.json", cfg
+        if "vision_config" in cfg:  # a whole SigLIP model
+            vcfg, where = dict(cfg["vision_config"]), "config.json: vision_config"
+        geometry = _siglip_geometry(vcfg, where)
+        specs = [(n, s) for n, s, _ in siglip_tensor_specs(geometry)]
+        canonical = canonical_siglip_name
     elif encoder == "clip_text":
         where, tcfg = "config.json", cfg
         if "text_config" in cfg:  # a whole CLIP model: projection_dim sits at the top level
@@ -495,6 +544,14 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
                "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "dtype": dtype}
         if g.projection_dim:
             cfg["projection_dim"] = g.projection_dim
+    elif encoder == "siglip":
+        g = geometry or SIGLIP_B16
+        cfg = {"architectures": ["SiglipVisionModel"], "model_type": "siglip_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,
+               "num_channels": g.num_channels, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
+               "intermediate_size": g.intermediate_size, "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0,
+               "dtype": dtype}
+        if g.vision_use_head is not True:
+            cfg["vision_use_head"] = g.vision_use_head
     elif encoder == "clip_text":
         g = geometry or CLIP_TEXT_B
         cfg = {"architectures": ["CLIPTextModelWithProjection" if g.projection_dim else "CLIPTextModel"], "model_type": "clip_text_model",
@@ -531,12 +588,12 @@ def main(argv=None) -> int:
 
     ap = argparse.ArgumentParser(prog="python -m multimodal_embeddings_amd.checkpoint", description="what a load of this checkpoint directory would find")
     ap.add_argument("directory")
-    ap.add_argument("--encoder", choices=ENCODERS, default="vit_b16")
+    ap.add_argument("--encoder", choices=CLI_ENCODERS, default="vit_b16")
     ap.add_argument("--resize-rule", choices=RESIZE_RULES, default="fit_pad",
                     help="the rule K1 would run: 'clip' checks preprocessor_config.json against the shortest-edge BICUBIC resize + centre crop")
     a = ap.parse_args(argv)
     try:
-        ck = read_checkpoint(a.directory, a.encoder, a.resize_rule)
+        ck = read_checkpoint(a.directory, "siglip" if a.encoder == SIGLIP_ALIAS else a.encoder, a.resize_rule)
     except MmeError as e:
         print(f"cannot load: {e}")
         return 1

@@ -1,4 +1,4 @@
-// K5: fused multi-head self-attention for ViT/16 @224 (T = 197 tokens, dh = 64; H = 6, 12 or 16 heads: ViT-S, -B, -L).
+// K5: fused multi-head self-attention for ViT/16 @224 (T = 197 tokens, or 196 without a class token; dh = 64; H = 6, 12 or 16 heads: ViT-S, -B, -L).
 //
 // Restates transformers models/vit/modeling_vit.py:164-189 (softmax(Q K^T / 8) V, softmax in
 // f32).  T is short, so there is no online softmax: the whole 32 x 224 score strip of a query
@@ -62,7 +62,10 @@ template <int NB> struct AttnGeom {
 // exponentials taken from key tile 0 (see there), guarded; the exact form re-runs a launch whose guard was raised.
 // run_if: when given, the whole launch returns at once unless *run_if != 0 (the conditional exact re-run).
 // share: K/V pieces of the next head the COMPUTING waves request (encoding: dma_head); the staging wave takes the rest
-template <int NB, bool STAMP, int PIPE, int H>
+// T: tokens per crop, 197 ([CLS] + 196 patches) or 196 (no class token: SigLIP).  It enters the crop stride, the clamp of
+// the last K/V piece, the Q-row clamp and the selection that removes the keys >= T from the last key tile; the 197
+// instantiations are the code they were when T was VIT_T (tools/kernel_streams.py).
+template <int NB, bool STAMP, int PIPE, int H, int T>
 __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, const int nblk, const int hsplit,
                                           unsigned long long* stamps, const int dbg_arg, int* __restrict__ guard, const int share,
                                           const float guard_limit, const int only_block) {
@@ -90,8 +93,9 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
     auto item_head = [&](int it) { return (item_blk(it) % hsplit) * hpw + (it - (it / hpw) * hpw); };
     auto item_crop = [&](int it) { return item_blk(it) / hsplit; };
 
+    static_assert(T == 196 || T == VIT_T, "attention: 196 or 197 tokens");
     // V rows 200.. are never written by DMA: zero them once in every buffer (P is 0 there, but
-    // 0 * garbage could be NaN).  Rows 197..199 receive clamped copies of row 196 (finite).
+    // 0 * garbage could be NaN).  Rows T..199 receive clamped copies of row T - 1 (finite).
     constexpr int ZROWS = TROWS - 200;
     for (int i = tid; i < NB * ZROWS * 8; i += 512) {
         const int buf = i / (ZROWS * 8), r = (i >> 3) % ZROWS, c = i & 7;
@@ -103,7 +107,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
     // in the FAST form.  The wave without a query block (7) takes most of them; each computing wave requests `share`
     // pieces right after the barrier (pieces w, w + 7, ...), where its SIMD partner's work covers the stall.
     auto dma_head = [&](int it, int buf) {
-        const char* hb = (const char*)qkv + (size_t)item_crop(it) * VIT_T * QKV_LD + item_head(it) * ATTN_ROWB;
+        const char* hb = (const char*)qkv + (size_t)item_crop(it) * T * QKV_LD + item_head(it) * ATTN_ROWB;
         char* kdst = lds + buf * BUF_BYTES;
         if ((dbg & 2) && it != 0) return;
         // share = a + 16 b + 256 c: waves 0-2 (the first-dispatched half: they lose the issue arbitration to their SIMD
@@ -118,7 +122,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
         for (int p = p_begin; p < p_end; p += p_step) {
             const bool isv = p >= NPIECE;
             const int pp = isv ? p - NPIECE : p;
-            lds_dma16(kv_piece_src<VIT_T - 1>(hb, QKV_LD, D, isv, pp, lane), kdst + (isv ? KV_BYTES : 0) + pp * 1024);
+            lds_dma16(kv_piece_src<T - 1>(hb, QKV_LD, D, isv, pp, lane), kdst + (isv ? KV_BYTES : 0) + pp * 1024);
         }
     };
 
@@ -133,7 +137,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
     const bool active = wave < 7 && (only_block < 0 || wave == only_block);
     // this lane's Q row of an item: 4 x 16 bytes at + ks * 32
     auto q_ptr = [&](int it) {
-        return (const char*)qkv + ((size_t)item_crop(it) * VIT_T + min(q, VIT_T - 1)) * QKV_LD + hh * 16 + item_head(it) * ATTN_ROWB;
+        return (const char*)qkv + ((size_t)item_crop(it) * T + min(q, T - 1)) * QKV_LD + hh * 16 + item_head(it) * ATTN_ROWB;
     };
 
     bf16x8 qf[4], qn[4];
@@ -211,8 +215,8 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                         constexpr int kt = I >> 1;
                         const int e = 8 * (I & 1) + j;
                         float pv = prob(kt, e);
-                        // of the last tile only keys 192..196 exist: e < 4, and e = 0 alone in the upper lane half
-                        if (kt == 6 && !(e < 4 && e + 4 * hh < VIT_T - 192)) pv = 0.f;
+                        // of the last tile only keys 192..T-1 exist: e < 4, and at T = 197 e = 0 alone in the upper lane half
+                        if (kt == 6 && !(e < 4 && e + 4 * hh < T - 192)) pv = 0.f;
                         sum4[j & 3] += pv;  // hipcc packs neighbouring chains into v_pk_add_f32: measured better here than 104 single adds (11.29 vs 11.54 ms per step)
                         pf[j] = (bf16_t)pv;
                     }
@@ -310,7 +314,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                     ot = t[0];
                 }
                 // !(sum < 2^100) also catches inf and NaN, !(ot - ot == 0) an inf / NaN total; one lane's word per offending row is enough
-                if (guard && (!(sum < guard_limit) || !(ot - ot == 0.f)) && q < VIT_T) *guard = 1;  // guard_limit = 2^100 (0.5 in the forced-re-run test mode)
+                if (guard && (!(sum < guard_limit) || !(ot - ot == 0.f)) && q < T) *guard = 1;  // guard_limit = 2^100 (0.5 in the forced-re-run test mode)
                 inv = __builtin_amdgcn_rcpf(sum);
             } else if constexpr (PIPE == 1) {
                 // The kernel is bound by vector-ALU and matrix issue per SIMD, not by HBM (stamped build: a wave's
@@ -363,7 +367,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 // tile only e = 0..3 can be valid (keys 192..195 in the lower lane half, 196 in the upper)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (e + 4 * hh < VIT_T - 192) mx = fmaxf(mx, s[6][e]);
+                    if (e + 4 * hh < T - 192) mx = fmaxf(mx, s[6][e]);
                 mx = fmaxf(mx, other_half(mx));
                 const float nmx = -mx;
                 ATTN_STAMP(4)  // maximum
@@ -376,13 +380,13 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
                 for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks];
             }
             // o[db][4*rg + j] = O[q][32db + 8rg + 4hh + j]: pair the lane halves into 16-byte stores
-            bf16_t* op = out + ((size_t)b * VIT_T + min(q, VIT_T - 1)) * D + h * VIT_DH;
+            bf16_t* op = out + ((size_t)b * T + min(q, T - 1)) * D + h * VIT_DH;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int rp = 0; rp < 4; rp += 2) {
                     const uint4 w = paired_o(o[db], rp, inv);
-                    if (q < VIT_T) *(uint4*)(op + db * 32 + (rp + hh) * 8) = w;
+                    if (q < T) *(uint4*)(op + db * 32 + (rp + hh) * 8) = w;
                 }
             ATTN_STAMP(6)  // Q hand-over + stores issued
         }
@@ -407,7 +411,17 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_t197(const bf16_t* __restrict
                                                          int share = 0, const int* __restrict__ run_if = nullptr, float guard_limit = 1.2676506e30f,
                                                          int only_block = -1) {
     if (run_if && *(const volatile int*)run_if == 0) return;  // uniform: every wave of every workgroup takes the same way
-    attn_body<NB, STAMP, PIPE, H>(qkv, out, nblk, hsplit, stamps, dbg_arg, guard, share, guard_limit, only_block);
+    attn_body<NB, STAMP, PIPE, H, VIT_T>(qkv, out, nblk, hsplit, stamps, dbg_arg, guard, share, guard_limit, only_block);
+}
+
+// the same kernel at 196 tokens per crop (towers without a class token); same arguments
+template <int NB, bool STAMP = false, int PIPE = 1, int H = VIT_H>
+__global__ __launch_bounds__(512, 2) void attn_fwd_t196(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int nblk, int hsplit,
+                                                         unsigned long long* stamps = nullptr, int dbg_arg = 0, int* __restrict__ guard = nullptr,
+                                                         int share = 0, const int* __restrict__ run_if = nullptr, float guard_limit = 1.2676506e30f,
+                                                         int only_block = -1) {
+    if (run_if && *(const volatile int*)run_if == 0) return;
+    attn_body<NB, STAMP, PIPE, H, 196>(qkv, out, nblk, hsplit, stamps, dbg_arg, guard, share, guard_limit, only_block);
 }
 
 }  // namespace
@@ -425,7 +439,7 @@ hipError_t with_heads(int heads, F f) {
     }
 }
 
-template <int H>
+template <int H, int T>
 hipError_t launch_attention_heads(const void* qkv, void* out, int B, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
     if (B <= 0) return hipSuccess;
     // blocks of H / hsplit heads: enough of them for every CU (one workgroup fits per CU: 112 KiB of LDS); the divisors of H
@@ -437,29 +451,36 @@ hipError_t launch_attention_heads(const void* qkv, void* out, int B, hipStream_t
     }
     const int nblk = B * hsplit, grid = nblk < 256 ? nblk : 256;  // persistent: one workgroup per CU walks its blocks
     const bool fast = guard != nullptr;
+    const auto exact_k = T == VIT_T ? attn_fwd_t197<2, false, 1, H> : attn_fwd_t196<2, false, 1, H>;
+    const auto fast_k = T == VIT_T ? attn_fwd_t197<2, false, 2, H> : attn_fwd_t196<2, false, 2, H>;
     const int share = (fast ? ATTN_SHARE_FAST : ATTN_SHARE_EXACT) | (reverse ? 1 << 17 : 0);
-    if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, false, 1, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
+    if (hipError_t e = ensure_dynamic_lds((const void*)exact_k, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
     if (fast) {
         // FAST kernel, then the exact kernel on the same launch geometry, which returns at once unless a row of the fast
         // kernel left the range its reference point covers (*guard raised; guard is zeroed by the caller per pass)
-        if (hipError_t e = ensure_dynamic_lds((const void*)attn_fwd_t197<2, false, 2, H>, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, false, 2, H>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
+        if (hipError_t e = ensure_dynamic_lds((const void*)fast_k, AttnGeom<2>::LDS_BYTES); e != hipSuccess) return e;
+        hipLaunchKernelGGL(fast_k, dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
                            (unsigned long long*)nullptr, 0, guard, share, (const int*)nullptr, force_redo ? 0.5f : 1.2676506e30f, only_block);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        hipLaunchKernelGGL((attn_fwd_t197<2, false, 1, H>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
+        hipLaunchKernelGGL(exact_k, dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
                            (unsigned long long*)nullptr, 0, (int*)nullptr, ATTN_SHARE_EXACT | (reverse ? 1 << 17 : 0), (const int*)guard, 1.2676506e30f, only_block);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((attn_fwd_t197<2, false, 1, H>), dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
+    hipLaunchKernelGGL(exact_k, dim3(grid), dim3(512), AttnGeom<2>::LDS_BYTES, s, (const bf16_t*)qkv, (bf16_t*)out, nblk, hsplit,
                        (unsigned long long*)nullptr, 0, (int*)nullptr, share, (const int*)nullptr, 1.2676506e30f, only_block);
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse) {
-    if (only_block < -1 || only_block > 6) return hipErrorInvalidValue;
-    return with_heads(heads, [&](auto h) { return launch_attention_heads<decltype(h)::value>(qkv, out, B, s, guard, force_redo, only_block, reverse); });
+hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse,
+                            int tokens) {
+    if (only_block < -1 || only_block > 6 || (tokens != VIT_T && tokens != 196)) return hipErrorInvalidValue;
+    return with_heads(heads, [&](auto h) {
+        constexpr int H = decltype(h)::value;
+        return tokens == VIT_T ? launch_attention_heads<H, VIT_T>(qkv, out, B, s, guard, force_redo, only_block, reverse)
+                               : launch_attention_heads<H, 196>(qkv, out, B, s, guard, force_redo, only_block, reverse);
+    });
 }
 
 // diagnostic: the stamped build of the fast or the exact form (two buffers, one workgroup per crop); stamps = uint64[B][8 waves][8],

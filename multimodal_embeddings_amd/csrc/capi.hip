@@ -144,6 +144,7 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
 
 int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
     const bool t50 = c->geom.t50();  // patch 32: 50 tokens, its own patch embedding, attention and pooling kernels
+    const bool sig = c->siglip;      // SigLIP: 196 tokens (no class token), tanh-GELU, the attention-pooling head behind the last block
     const int T = c->geom.tokens();
     const int M = n * T;
     const int D = c->geom.hidden, F = c->geom.mlp, NL = c->geom.layers;  // the geometry of the loaded weights
@@ -172,6 +173,20 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_embed_rows_t50((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
+    } else if (sig) {
+        // no class token: patch row m IS token row m, but EPI_PATCH (and its interior-tile form) maps rows past the [CLS]
+        // rows at compile time.  As at patch 32 the GEMM leaves f32 [n * 196, D] in the dead qkv buffer (784 D n of its
+        // 1176 D n bytes) and a row kernel adds bias and position rows in EPI_PATCH's f32 order, one rounding
+        g.A = patches;
+        g.W = c->patch_w;
+        g.M = M;
+        g.N = D;
+        g.K = VIT_PATCH_DIM;
+        g.outf = (float*)c->qkv.p;
+        g.ldf = D;
+        if ((r = P.gemm(EPI_F32, g))) return r;
+        Timed t(c, s, KC_LN);
+        HIP_TRY(c, launch_embed_rows_t196((const float*)c->qkv.p, c->patch_b, c->pos, c->x.p, n, D, s));
     } else {
         g.A = patches;
         g.W = c->patch_w;
@@ -189,7 +204,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         if ((r = P.gemm(EPI_PATCH, g))) return r;
     }
     const GemmArgs patch_args = g;
-    if (!t50) {
+    if (!t50 && !sig) {
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, D, s));
     }
@@ -200,7 +215,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         // in the canonical order: the first folded LayerNorm needs neither planes nor another pass over x
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_pre_ln(c->x.p, c->pre_g, c->pre_b, M, D, c->ln_eps, (float*)c->stats.p, s));
-    } else if (!t50 && planes && gemm_runs_256(patch_args, c->gemm_variant)) {  // (patch 32: no planes from the f32 epilogue; the canonical pass below gives the same bits)
+    } else if (!t50 && !sig && planes && gemm_runs_256(patch_args, c->gemm_variant)) {  // (patch 32, SigLIP: no planes from the f32 epilogue; the canonical pass below gives the same bits)
         // first LayerNorm of the pass: the patch-embed epilogue left the partial sums of every token row an INTERIOR tile
         // wrote (patch rows [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th
         // row) and the rows of the ragged last tile take the stand-alone kernel, same canonical order
@@ -232,7 +247,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         // (K8 pools token `pool_token`), so the query block that holds it is the only one attended, and the second half of
         // the block runs on the n gathered rows instead of n x 197.  Same kernels, same per-row arithmetic: the
         // embeddings are bit-identical to the full pass (tests/test_gpu_parity.py).
-        const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0;
+        const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0 && !sig;  // (SigLIP's head reads every token row)
         {
             Timed t(c, s, KC_ATTN);
             if (t50) {  // exact kernel only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
@@ -240,7 +255,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
                 HIP_TRY(c, launch_attention_t50(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
             } else {
                 HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
-                                            pruned ? pool_token / 32 : -1, P.zigzag == 2 ? true : P.next_dir() != 0));
+                                            pruned ? pool_token / 32 : -1, P.zigzag == 2 ? true : P.next_dir() != 0, T));
             }
         }
         const bool last = l + 1 == NL;  // no statistics after the last block: the final LayerNorm touches the pooled row only (K8)
@@ -263,7 +278,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
                 HIP_TRY(c, hipMemcpy2DAsync((char*)c->x.p + (size_t)pool_token * rowb, pitch, x_p, rowb, rowb, n, hipMemcpyDeviceToDevice, s));
             }
         } else if (c->ln_mode != 0) {
-            if ((r = P.after_attention(L.w, M, c->att.p, c->x.p, !last))) return r;
+            if ((r = P.after_attention(L.w, M, c->att.p, c->x.p, !last || sig))) return r;  // SigLIP: post_layernorm, folded into the head's K | V GEMM, reads the statistics
         } else {  // LayerNorm-kernel mode: the block's residual GEMMs around a LayerNorm launch and the unfolded fc1
             if ((r = P.residual(c->att.p, L.w.o_w, L.w.o_b, D, M, c->x.p, false))) return r;
             {
@@ -274,9 +289,59 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             g.A = c->hbuf.p; g.W = L.fc1_w; g.M = M; g.N = F; g.K = D;
             g.bias = L.fc1_b; g.out = c->mlp.p; g.ldo = F;
             g.reverse_m = P.next_dir();
-            if ((r = P.gemm(c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, g))) return r;
+            if ((r = P.gemm(c->act == 2 ? EPI_BIAS_TGELU : c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, g))) return r;
             if ((r = P.residual(c->mlp.p, L.w.fc2_w, L.w.fc2_b, F, M, c->x.p, false))) return r;
         }
+    }
+    if (sig) {
+        // SiglipMultiheadAttentionPoolingHead: K | V = in_proj(post_layernorm(x)) over every token row, one constant query
+        // per head (map_pool), then the second half of a block with the head's weights on n rows: out_proj on a ZEROED
+        // residual (0 + out_proj(a) is out_proj(a) in bf16: the probe is no residual), y = a' + fc2(act(fc1(LN(a')))); L2
+        const LayerDev& Hd = c->head;
+        if ((r = ensure(c, c->pooled, (size_t)2 * c->chunk * D * 2))) return r;
+        bf16_t* a_p = (bf16_t*)c->pooled.p;   // [n, D] pooled attention rows
+        bf16_t* y_p = a_p + (size_t)n * D;    // [n, D] the head's residual rows
+        g = GemmArgs{};
+        g.M = M; g.N = 2 * D; g.K = D; g.out = c->qkv.p; g.ldo = 2 * D;
+        if (c->ln_mode != 0) {
+            g.A = c->x.p; g.W = Hd.w.qkv_wf; g.bias = Hd.w.qkv_bf; g.colsum = Hd.w.qkv_cs; g.ln_stats = (float*)c->stats.p;
+            g.reverse_m = P.next_dir();
+            if ((r = P.gemm(EPI_LN_BIAS, g))) return r;
+        } else {
+            {
+                Timed t(c, s, KC_LN);
+                HIP_TRY(c, launch_layernorm(c->x.p, c->lnf_g, c->lnf_b, c->hbuf.p, M, D, c->ln_eps, s));
+            }
+            g.A = c->hbuf.p; g.W = Hd.qkv_w; g.bias = Hd.qkv_b;
+            g.reverse_m = P.next_dir();
+            if ((r = P.gemm(EPI_BIAS, g))) return r;
+        }
+        {
+            Timed t(c, s, KC_POOL);
+            HIP_TRY(c, launch_map_pool(c->qkv.p, c->head_q, a_p, n, c->geom.heads, s));
+            HIP_TRY(c, hipMemsetAsync(y_p, 0, (size_t)n * D * 2, s));
+        }
+        EncoderPass G = P;    // as the pruned last layer: n rows are far below one 256-row panel,
+        G.lnpart = nullptr;   // so no planes, one canonical statistics pass
+        G.planes = false;
+        G.zigzag = G.dir = 0; // and no reversal
+        if (c->ln_mode != 0) {
+            if ((r = G.after_attention(Hd.w, n, a_p, y_p, false))) return r;
+        } else {
+            if ((r = G.residual(a_p, Hd.w.o_w, Hd.w.o_b, D, n, y_p, false))) return r;
+            {
+                Timed t(c, s, KC_LN);
+                HIP_TRY(c, launch_layernorm(y_p, Hd.ln2_g, Hd.ln2_b, c->hbuf.p, n, D, c->ln_eps, s));
+            }
+            g = GemmArgs{};
+            g.A = c->hbuf.p; g.W = Hd.fc1_w; g.M = n; g.N = F; g.K = D;
+            g.bias = Hd.fc1_b; g.out = c->mlp.p; g.ldo = F;
+            if ((r = G.gemm(EPI_BIAS_TGELU, g))) return r;
+            if ((r = G.residual(c->mlp.p, Hd.w.fc2_w, Hd.w.fc2_b, F, n, y_p, false))) return r;
+        }
+        Timed t(c, s, KC_POOL);
+        HIP_TRY(c, launch_l2_rows_bf16(y_p, n, D, emb_f32, emb_bf16, s));
+        return MME_OK;
     }
     if (c->proj_dim) {
         // CLIP with a projection: post_layernorm of the pooled row, rounded to bf16, times visual_projection, then L2
@@ -577,7 +642,7 @@ int mme_vit_geometry(mme_ctx* c, int32_t out[6]) {
 
 int mme_encoder_info(mme_ctx* c, int32_t out[4]) {
     if (!c || !out) return fail(c, MME_E_ARG, "mme_encoder_info: null argument");
-    out[0] = c->clip ? 1 : 0;
+    out[0] = c->siglip ? 2 : c->clip ? 1 : 0;
     out[1] = embed_dim(c);
     out[2] = c->act;
     out[3] = c->proj_dim;
@@ -686,7 +751,7 @@ int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const 
     int32_t* nt_dev = (int32_t*)c->attn_apply.p + 16;
     HIP_TRY(c, hipMemsetAsync(guard, 0, sizeof(int), s));
     if (kind == 0) {
-        HIP_TRY(c, launch_attention(qkv, out, n, c->geom.heads, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2, only_block, reverse != 0));
+        HIP_TRY(c, launch_attention(qkv, out, n, c->geom.heads, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2, only_block, reverse != 0, c->geom.tokens()));
     } else {
         HIP_TRY(c, hipMemcpyAsync(nt_dev, ntiles_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(c, launch_attention_tiles(qkv, out, nt_dev, n, s, c->attn_mode ? guard : nullptr, c->attn_mode == 2));
@@ -1398,41 +1463,44 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
     return MME_OK;
 }
 
+// ops 0 / 1 of mme_clip_apply and mme_siglip_apply: one GEMM whose epilogue applies the tower's activation, `epi` without
+// (op 0) or behind (op 1) the folded LayerNorm; the checks of mme_gemm_apply's epilogues 1 / 6 under the caller's name
+static int act_gemm_apply(mme_ctx* c, const char* who, int op, int epi, const mme_gemm_apply_args* ga, int32_t* ran_256, hipStream_t s) {
+    if (!ga) return fail(c, MME_E_ARG, "%s: op %d needs gemm", who, op);
+    if (ga->variant < 0 || ga->variant > 6) return fail(c, MME_E_ARG, "%s: variant %d outside 0..6", who, ga->variant);
+    if (ga->reverse_m != 0 && ga->reverse_m != 1) return fail(c, MME_E_ARG, "%s: reverse_m must be 0 or 1", who);
+    const int64_t M = ga->M, N = ga->N, K = ga->K;
+    if (M < 1 || M > (1 << 24) || N < 1 || N > (1 << 20)) return fail(c, MME_E_ARG, "%s: M = %d outside 1..2^24 or N = %d outside 1..2^20", who, ga->M, ga->N);
+    if (K < 64 || K > (1 << 16) || (K % 64) != 0) return fail(c, MME_E_ARG, "%s: K = %d must be a multiple of 64 in 64..65536", who, ga->K);
+    if (!ga->A || !ga->W) return fail(c, MME_E_ARG, "%s: null operand (A or W)", who);
+    if (!aligned_to(ga->A, 16) || !aligned_to(ga->W, 16)) return fail(c, MME_E_ARG, "%s: A and W must be 16-byte aligned", who);
+    if ((N % 4) != 0) return fail(c, MME_E_ARG, "%s: a bf16 output needs N %% 4 == 0 (N = %d)", who, ga->N);
+    if (!ga->bias || !ga->out) return fail(c, MME_E_ARG, "%s: op %d needs bias and out", who, op);
+    if (!aligned_to(ga->bias, 16) || !aligned_to(ga->out, 16)) return fail(c, MME_E_ARG, "%s: bias and out must be 16-byte aligned", who);
+    if (ga->ldo < N || ga->ldo > (1 << 24) || (ga->ldo % 8) != 0) return fail(c, MME_E_ARG, "%s: ldo = %lld must be a multiple of 8 in N..2^24", who, (long long)ga->ldo);
+    if (op == 1) {
+        if (!ga->ln_stats || !ga->colsum) return fail(c, MME_E_ARG, "%s: op 1 needs ln_stats and colsum", who);
+        if (!aligned_to(ga->ln_stats, 8) || !aligned_to(ga->colsum, 16)) return fail(c, MME_E_ARG, "%s: ln_stats must be 8-byte and colsum 16-byte aligned", who);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    GemmArgs g{};
+    g.A = ga->A; g.W = ga->W; g.M = ga->M; g.N = ga->N; g.K = ga->K;
+    g.reverse_m = ga->reverse_m;
+    g.bias = ga->bias; g.out = ga->out; g.ldo = ga->ldo;
+    if (op == 1) { g.ln_stats = ga->ln_stats; g.colsum = ga->colsum; }
+    if (ran_256) *ran_256 = gemm_runs_256(g, ga->variant) ? 1 : 0;
+    HIP_TRY(c, launch_gemm(epi, g, s, ga->variant));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
 // the kernels a CLIP tower adds, one launch each (tests/test_gpu_clip.py)
 int mme_clip_apply(mme_ctx* c, int op, const mme_clip_apply_args* a, void* stream) {
     if (!c) return MME_E_ARG;
     if (!a) return fail(c, MME_E_ARG, "mme_clip_apply: null argument");
     if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_clip_apply: op %d outside 0..4", op);
     hipStream_t s = (hipStream_t)stream;
-    if (op <= 1) {
-        const mme_gemm_apply_args* ga = a->gemm;
-        if (!ga) return fail(c, MME_E_ARG, "mme_clip_apply: op %d needs gemm", op);
-        if (ga->variant < 0 || ga->variant > 6) return fail(c, MME_E_ARG, "mme_clip_apply: variant %d outside 0..6", ga->variant);
-        if (ga->reverse_m != 0 && ga->reverse_m != 1) return fail(c, MME_E_ARG, "mme_clip_apply: reverse_m must be 0 or 1");
-        const int64_t M = ga->M, N = ga->N, K = ga->K;
-        if (M < 1 || M > (1 << 24) || N < 1 || N > (1 << 20)) return fail(c, MME_E_ARG, "mme_clip_apply: M = %d outside 1..2^24 or N = %d outside 1..2^20", ga->M, ga->N);
-        if (K < 64 || K > (1 << 16) || (K % 64) != 0) return fail(c, MME_E_ARG, "mme_clip_apply: K = %d must be a multiple of 64 in 64..65536", ga->K);
-        if (!ga->A || !ga->W) return fail(c, MME_E_ARG, "mme_clip_apply: null operand (A or W)");
-        if (!aligned_to(ga->A, 16) || !aligned_to(ga->W, 16)) return fail(c, MME_E_ARG, "mme_clip_apply: A and W must be 16-byte aligned");
-        if ((N % 4) != 0) return fail(c, MME_E_ARG, "mme_clip_apply: a bf16 output needs N %% 4 == 0 (N = %d)", ga->N);
-        if (!ga->bias || !ga->out) return fail(c, MME_E_ARG, "mme_clip_apply: op %d needs bias and out", op);
-        if (!aligned_to(ga->bias, 16) || !aligned_to(ga->out, 16)) return fail(c, MME_E_ARG, "mme_clip_apply: bias and out must be 16-byte aligned");
-        if (ga->ldo < N || ga->ldo > (1 << 24) || (ga->ldo % 8) != 0) return fail(c, MME_E_ARG, "mme_clip_apply: ldo = %lld must be a multiple of 8 in N..2^24", (long long)ga->ldo);
-        if (op == 1) {
-            if (!ga->ln_stats || !ga->colsum) return fail(c, MME_E_ARG, "mme_clip_apply: op 1 needs ln_stats and colsum");
-            if (!aligned_to(ga->ln_stats, 8) || !aligned_to(ga->colsum, 16)) return fail(c, MME_E_ARG, "mme_clip_apply: ln_stats must be 8-byte and colsum 16-byte aligned");
-        }
-        HIP_TRY(c, hipSetDevice(c->device));
-        GemmArgs g{};
-        g.A = ga->A; g.W = ga->W; g.M = ga->M; g.N = ga->N; g.K = ga->K;
-        g.reverse_m = ga->reverse_m;
-        g.bias = ga->bias; g.out = ga->out; g.ldo = ga->ldo;
-        if (op == 1) { g.ln_stats = ga->ln_stats; g.colsum = ga->colsum; }
-        if (a->ran_256) *a->ran_256 = gemm_runs_256(g, ga->variant) ? 1 : 0;
-        HIP_TRY(c, launch_gemm(op == 0 ? EPI_BIAS_QGELU : EPI_LN_BIAS_QGELU, g, s, ga->variant));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return MME_OK;
-    }
+    if (op <= 1) return act_gemm_apply(c, "mme_clip_apply", op, op == 0 ? EPI_BIAS_QGELU : EPI_LN_BIAS_QGELU, a->gemm, a->ran_256, s);
     auto vec = [](const void* p) { return p && aligned_to(p, 16); };
     const char* bad = nullptr;
     if (op == 2 || op == 3) {
@@ -1497,6 +1565,40 @@ int mme_vit32_apply(mme_ctx* c, int op, const mme_vit32_apply_args* a, void* str
         case 2: HIP_TRY(c, launch_attention_t50(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
         case 3: HIP_TRY(c, launch_pool_ln_t50(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->y, s)); break;
         default: HIP_TRY(c, launch_pool_t50(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+// the kernels a SigLIP tower adds, one launch each (tests/test_gpu_siglip.py)
+int mme_siglip_apply(mme_ctx* c, int op, const mme_siglip_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_siglip_apply: null argument");
+    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d outside 0..4", op);
+    hipStream_t s = (hipStream_t)stream;
+    if (op <= 1) return act_gemm_apply(c, "mme_siglip_apply", op, op == 0 ? EPI_BIAS_TGELU : EPI_LN_BIAS_TGELU, a->gemm, a->ran_256, s);
+    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "mme_siglip_apply: n = %d outside 0..2^20", a->n);
+    const char* bad = nullptr;
+    if (op == 3) {
+        if (a->heads != 6 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_siglip_apply: op 3 is built for heads == 6, 12 and 16 (heads = %d)", a->heads);
+        if (!vec(a->kv) || !vec(a->q) || !vec(a->out)) bad = "kv, q and out non-null and 16-byte aligned";
+    } else {
+        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
+        if (op == 2) {
+            if (!vec(a->acc) || !vec(a->bias) || !vec(a->pos) || !vec(a->x)) bad = "acc, bias, pos, x non-null and 16-byte aligned";
+        } else {
+            if (!vec(a->x)) bad = "x non-null and 16-byte aligned";
+            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
+            else if (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
+        }
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d needs %s", op, bad);
+    HIP_TRY(c, hipSetDevice(c->device));
+    switch (op) {
+        case 2: HIP_TRY(c, launch_embed_rows_t196(a->acc, a->bias, a->pos, a->x, a->n, a->d, s)); break;
+        case 3: HIP_TRY(c, launch_map_pool(a->kv, a->q, a->out, a->n, a->heads, s)); break;
+        default: HIP_TRY(c, launch_l2_rows_bf16(a->x, a->n, a->d, a->emb_f32, a->emb_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;

@@ -42,12 +42,14 @@ struct LayerDev {
 // Supported set (validate_vit_weights, weight_load.hip): image 224, patch 16 or 32, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
 // <= 8192, 1..64 layers.
 // Patch 16 (197 tokens, the compile-time geometry of common.h) or patch 32 (50 tokens: patch32.hip, attention_short.hip).
+// no_cls: a tower without a class token (SigLIP, patch 16 only): 196 tokens (siglip.hip, attention.hip at T = 196).
 struct VitGeom {
     int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
     int patch = VIT_PATCH;
+    bool no_cls = false;
     int grid() const { return VIT_IMG / patch; }
     int np() const { return grid() * grid(); }             // patches per crop: 196 or 49
-    int tokens() const { return np() + 1; }                // 197 or 50
+    int tokens() const { return np() + (no_cls ? 0 : 1); } // 197 or 50; 196 without a class token
     int patch_dim() const { return 3 * patch * patch; }    // 768 or 3072; np() * patch_dim() is 150 528 for both
     bool t50() const { return patch == 32; }
 };
@@ -82,10 +84,18 @@ struct mme_ctx {
     // CLIP image tower (mme_load_clip*; all off / null after mme_load_vit*): a LayerNorm over every token row before layer 0,
     // QuickGELU in the MLP, a bias-free projection of the pooled, LayerNormed row
     bool clip = false;         // the last load was a CLIP load (mme_encoder_info); pre_g / pre_b are set
-    int act = 0;               // 0 erf-GELU, 1 QuickGELU
+    int act = 0;               // 0 erf-GELU, 1 QuickGELU, 2 tanh-GELU (SigLIP)
     int proj_dim = 0;          // 0: no projection (the embedding is the L2-normalised post_layernorm row)
     float *pre_g = nullptr, *pre_b = nullptr;
     bf16_t* proj_w = nullptr;  // [proj_dim, hidden]
+    // SigLIP image tower (mme_load_siglip*; off / null after every other load): no class token, tanh-GELU (act 2), and the
+    // attention-pooling head in place of the pooled token.  `head` is a block in the towers' form whose "QKV" is the K | V
+    // projection [2 D, D] of the head's in_proj with post_layernorm (lnf_g, lnf_b) folded in, whose o_w / o_b is out_proj
+    // and whose ln2 / fc1 / fc2 are the head's layernorm and MLP; head_q [D] f32 is the constant query
+    // (probe . W_q^T + b_q) dh^-0.5 log2 e.  head.ln1_g / ln1_b are not set (ln_mode 0 normalises with lnf_g / lnf_b).
+    bool siglip = false;
+    LayerDev head{};
+    float* head_q = nullptr;
     float* lut = nullptr;  // [3,256]
     NormAffine norm_aff{};  // the same mapping as one fma per value where that is bit-exact after the bf16 rounding (set_lut)
     int resize_rule = MME_RESIZE_FIT_PAD;  // mme_set_resize_rule: how mme_preprocess / mme_embed make 224 x 224 pixels; no load changes it
@@ -99,6 +109,7 @@ struct mme_ctx {
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
     DevBuf patches32;      // patch 32: the retiled [chunk * 49, 3072] matrix of mme_embed (`patches` stages K1's patch-16 matrix)
     DevBuf pooled, projf;  // CLIP tail: bf16 [chunk, hidden] post_layernorm rows, f32 [chunk, proj_dim] projected rows
+                           // SigLIP tail: pooled = bf16 [2][chunk, hidden] (map_pool's rows, then the head's residual rows)
     // host staging for crop tables
     std::vector<CropDesc> h_crops;
     std::vector<ClipCropDesc> h_clip_crops;

@@ -10,7 +10,7 @@ struct EncoderPass {
     hipStream_t s;
     int D, F;       // hidden width, MLP width
     float eps;
-    int act;        // fc1's activation: 0 erf-GELU, 1 QuickGELU
+    int act;        // fc1's activation: 0 erf-GELU, 1 QuickGELU, 2 tanh-GELU
     // workspace: residual stream, Q | K | V, attention output, MLP hidden (bf16); (mean, rstd) per row
     void *x, *qkv, *att, *mlp;
     float* stats;

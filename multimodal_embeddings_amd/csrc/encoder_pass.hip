@@ -50,7 +50,7 @@ int EncoderPass::fc1_ln(const BlockW& w, int rows, const void* xr) {
     g.A = xr; g.W = w.fc1_wf; g.M = rows; g.N = F; g.K = D;
     g.bias = w.fc1_bf; g.colsum = w.fc1_cs; g.ln_stats = stats; g.out = mlp; g.ldo = F;
     g.reverse_m = next_dir();
-    return gemm(act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU, g);
+    return gemm(act == 2 ? EPI_LN_BIAS_TGELU : act ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS_GELU, g);
 }
 
 int EncoderPass::after_attention(const BlockW& w, int rows, const void* a, void* xr, bool stats_next) {

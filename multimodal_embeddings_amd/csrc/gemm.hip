@@ -166,6 +166,8 @@ hipError_t launch_gemm(int epilogue, const GemmArgs& g, hipStream_t s, int varia
         case EPI_LN_BIAS_GELU: hipLaunchKernelGGL(gemm_bf16_tn_128<EPI_LN_BIAS_GELU>, grid, block, 0, s, g); break;
         case EPI_BIAS_QGELU: hipLaunchKernelGGL(gemm_bf16_tn_128<EPI_BIAS_QGELU>, grid, block, 0, s, g); break;
         case EPI_LN_BIAS_QGELU: hipLaunchKernelGGL(gemm_bf16_tn_128<EPI_LN_BIAS_QGELU>, grid, block, 0, s, g); break;
+        case EPI_BIAS_TGELU: hipLaunchKernelGGL(gemm_bf16_tn_128<EPI_BIAS_TGELU>, grid, block, 0, s, g); break;
+        case EPI_LN_BIAS_TGELU: hipLaunchKernelGGL(gemm_bf16_tn_128<EPI_LN_BIAS_TGELU>, grid, block, 0, s, g); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -448,6 +448,8 @@ hipError_t launch_gemm256r(int epilogue, const GemmArgs& g, hipStream_t s, bool 
         case EPI_LN_BIAS_GELU: return defer ? launch256r<EPI_LN_BIAS_GELU, 4>(g, s) : launch256r<EPI_LN_BIAS_GELU, 0>(g, s);
         case EPI_BIAS_QGELU: return defer ? launch256r<EPI_BIAS_QGELU, 4>(g, s) : launch256r<EPI_BIAS_QGELU, 0>(g, s);
         case EPI_LN_BIAS_QGELU: return defer ? launch256r<EPI_LN_BIAS_QGELU, 4>(g, s) : launch256r<EPI_LN_BIAS_QGELU, 0>(g, s);
+        case EPI_BIAS_TGELU: return defer ? launch256r<EPI_BIAS_TGELU, 4>(g, s) : launch256r<EPI_BIAS_TGELU, 0>(g, s);
+        case EPI_LN_BIAS_TGELU: return defer ? launch256r<EPI_LN_BIAS_TGELU, 4>(g, s) : launch256r<EPI_LN_BIAS_TGELU, 0>(g, s);
         case EPI_F32: return defer ? launch256r<EPI_F32, 4>(g, s) : launch256r<EPI_F32, 0>(g, s);
         case EPI_PATCH: return launch256r<EPI_PATCH, 0>(g, s);  // no deferred form
         case EPI_TOPK: return launch256r<EPI_TOPK, 0>(g, s);

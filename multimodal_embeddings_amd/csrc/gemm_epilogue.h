@@ -40,6 +40,23 @@ __device__ __forceinline__ float quick_gelu(float x) {
     return (x * 0x1p-8f) * __builtin_amdgcn_rcpf(s);
 }
 
+// tanh-GELU (transformers ACT2FN["gelu_pytorch_tanh"]): 0.5 x (1 + tanh(u)) with u = sqrt(2 / pi) (x + 0.044715 x^3).
+// 0.5 (1 + tanh u) = sigmoid(2 u), so gelu_tanh(x) = x * sigmoid(x (c0 + c1 x^2)), c0 = 2 sqrt(2 / pi), c1 = 0.044715 c0:
+// an identity, not a fit -- gelu_erf's branch-free form with one polynomial term fewer.  The far negative tail is
+// quick_gelu's: the exponential taken at half the argument and squared inside the fma, 1 + e carried as 2^-8 (1 + e), so
+// that no intermediate leaves the f32 range while the result is still a normal number (it stops being one near
+// x = -10.06, where exp2 of the whole argument has just overflowed; the half argument overflows from x = -12.9 on, where
+// the result is below 1e-76).  x^2 is clamped at 2^12 and the x of the product at -2^100, both far outside the range in
+// which they change a bit of the result: -inf gives h = inf, s = inf, rcp = 0 and y = -2^92 * 0 = -0, +inf gives h = 0,
+// s = 2^-8 and y = x.  8 plain VALU ops + exp2 + rcp.
+__device__ __forceinline__ float gelu_tanh(float x) {
+    const float x2 = fminf(x * x, 4096.0f);
+    const float q = fmaf(x2, (float)(-0.5 * 0.044715 * 1.5957691216057308 * 1.4426950408889634), (float)(-0.5 * 1.5957691216057308 * 1.4426950408889634));
+    const float h = __builtin_amdgcn_exp2f(x * q);  // exp(-x (c0 + c1 x^2) / 2)
+    const float s = fmaf(h, h * 0x1p-8f, 0x1p-8f);
+    return (fmaxf(x, -0x1p100f) * 0x1p-8f) * __builtin_amdgcn_rcpf(s);
+}
+
 // ---- LayerNorm statistics in ONE canonical summation order ---------------------------------------------
 // Shared by the EPI_BIAS_RES_STATS epilogue (partial sums while the rounded outputs are still in registers) and
 // by the stand-alone kernels of rowops.hip, so that an embedding does not depend on which of them ran:
@@ -107,7 +124,7 @@ __device__ __forceinline__ void epi_store(const GemmArgs& g, int m, const EpiRow
         }
         return;
     }
-    if (EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU) {
+    if (EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_LN_BIAS_TGELU) {
         const float mu = g.ln_stats[2 * (int64_t)m], rs = g.ln_stats[2 * (int64_t)m + 1];
         const f32x4 sv = *(const f32x4*)(g.colsum + n), bv = *(const f32x4*)(g.bias + n);
 #pragma unroll
@@ -122,6 +139,10 @@ __device__ __forceinline__ void epi_store(const GemmArgs& g, int m, const EpiRow
     if (EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = quick_gelu(v[r]);
+    }
+    if (EPI == EPI_BIAS_TGELU || EPI == EPI_LN_BIAS_TGELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
     }
     if (EPI == EPI_PATCH) v += *(const f32x4*)(g.pos + (int64_t)er.prow * g.N + n);
     bf16_t* o = (bf16_t*)g.out + er.orow * g.ldo + n;
@@ -182,13 +203,15 @@ template <int EPI, int NDEF = 0, class Between>
 __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&acc)[8][4], int mw, int nw, int fr, int fq,
                                                      Between&& between, uint4* pend = nullptr) {
     static_assert(EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES || EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU ||
-                      EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU,
+                      EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_BIAS_TGELU ||
+                      EPI == EPI_LN_BIAS_TGELU,
                   "epilogue_wave_128x64: unsupported epilogue");
     constexpr bool RES = EPI == EPI_BIAS_RES || EPI == EPI_BIAS_RES_STATS;
     constexpr bool STATS = EPI == EPI_BIAS_RES_STATS;
-    constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU;
+    constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_LN_BIAS_TGELU;
     constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_LN_BIAS_GELU;
     constexpr bool QGELU = EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU;
+    constexpr bool TGELU = EPI == EPI_BIAS_TGELU || EPI == EPI_LN_BIAS_TGELU;
     // wave-uniform row bases (SGPR pairs) + 32-bit lane offsets: saddr addressing
     const int64_t tile_off = (int64_t)mw * g.ldo + nw;
     const int lo0 = fr * (int)g.ldo + row16_col(0, fq), lo1 = fr * (int)g.ldo + row16_col(2, fq);
@@ -248,6 +271,13 @@ __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&
                 for (int r = 0; r < 4; ++r) {
                     v0[r] = quick_gelu(v0[r]);
                     v1[r] = quick_gelu(v1[r]);
+                }
+            }
+            if (TGELU) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    v0[r] = gelu_tanh(v0[r]);
+                    v1[r] = gelu_tanh(v1[r]);
                 }
             }
             if (RES) {
@@ -404,5 +434,5 @@ __device__ __forceinline__ void epilogue_wave_patch_128x64(const GemmArgs& g, f3
 template <int EPI>
 constexpr bool epi_has_fast_path() {
     return EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES || EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU ||
-           EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU;
+           EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_BIAS_TGELU || EPI == EPI_LN_BIAS_TGELU;
 }

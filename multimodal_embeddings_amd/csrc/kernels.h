@@ -21,7 +21,10 @@ enum GemmEpilogue {
     EPI_BIAS_RES_STATS = 8,
     // QuickGELU, x * sigmoid(1.702 x), where the erf forms have erf-GELU (CLIP image towers with OpenAI weights)
     EPI_BIAS_QGELU = 9,     // out = bf16(quick_gelu(acc + bias[n]))                      (fc1, LayerNorm-kernel mode)
-    EPI_LN_BIAS_QGELU = 10  // EPI_LN_BIAS, then QuickGELU                                (fc1)
+    EPI_LN_BIAS_QGELU = 10, // EPI_LN_BIAS, then QuickGELU                                (fc1)
+    // tanh-GELU, 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (gelu_pytorch_tanh: SigLIP image towers)
+    EPI_BIAS_TGELU = 11,    // out = bf16(gelu_tanh(acc + bias[n]))                       (fc1, LayerNorm-kernel mode)
+    EPI_LN_BIAS_TGELU = 12  // EPI_LN_BIAS, then tanh-GELU                                (fc1)
 };
 
 struct GemmArgs {
@@ -94,8 +97,9 @@ hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, h
 // force_redo: the fast kernel raises the guard for every row (test of the re-run path)
 // only_block >= 0: compute and store that query block of 32 only (0..6)
 // reverse: walk the crops from the last one down (same results; zig-zag order of consecutive kernels, EncoderPass::zigzag)
+// tokens: 197, or 196 (towers without a class token: qkv [B*196, ...] -> out [B*196, ...]); anything else is hipErrorInvalidValue
 hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard = nullptr, bool force_redo = false,
-                            int only_block = -1, bool reverse = false);
+                            int only_block = -1, bool reverse = false, int tokens = 197);
 // diagnostic: stamped build of the fast or the exact form, stamps uint64[B][8][8]
 hipError_t launch_attention_stamped(const void* qkv, void* out, int B, int heads, bool fast, unsigned long long* stamps, hipStream_t s);
 
@@ -290,6 +294,15 @@ hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hi
 hipError_t launch_pool_ln_t50(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s);
 hipError_t launch_pool_t50(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
                            hipStream_t s);
+
+// ---- SigLIP ViT/16 @224 image towers (siglip.hip; attention: launch_attention with tokens = 196): 196 tokens, no class token
+// acc f32 [n * 196, d] (the patch-embed GEMM under EPI_F32) -> x[b*196 + p] = bf16((acc + bias) + pos[p]); d = 384, 768 or 1024
+hipError_t launch_embed_rows_t196(const float* acc, const float* bias, const float* pos, void* x, int n, int d, hipStream_t s);
+// attention pooling: kv bf16 [n*196, 2*64*heads] (K | V), q f32 [64*heads] (pre-scaled by dh^-0.5 log2 e, the same for every
+// crop) -> out bf16 [n, 64*heads]; exact maximum, f32 sums, one rounding; heads = 6, 12 or 16
+hipError_t launch_map_pool(const void* kv, const float* q, void* out, int n, int heads, hipStream_t s);
+// launch_l2_rows on bf16 rows: x bf16 [rows, p] -> x / max(||x||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024
+hipError_t launch_l2_rows_bf16(const void* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
 
 // ---- device-side weight preparation (weight_prep.hip).  dt = MME_DT_* (include/mme.h); sources are device addresses,
 // 16-byte aligned, of elements of that type.

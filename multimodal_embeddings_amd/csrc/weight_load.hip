@@ -220,10 +220,12 @@ namespace {
 
 // argument checks of both ViT loaders (the messages of both name the f32 loader): the geometry against the supported
 // set, every tensor pointer.  Touches nothing in the context but its error text.
-int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who = "mme_load_vit", bool bias_free_patch = false) {
+// no_cls: a tower without a class token (SigLIP): patch 16 only, cls_token NULL
+int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who = "mme_load_vit", bool bias_free_patch = false, bool no_cls = false) {
     if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
     // every refusal names the field, the value found and what is supported
     if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
+    if (no_cls && w->patch_size != 16) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 16", who, w->patch_size);
     if (w->patch_size != 16 && w->patch_size != 32) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 16, 32", who, w->patch_size);
     if (!vit_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 384, 768, 1024", who, w->hidden);
     if (w->heads * VIT_DH != w->hidden)
@@ -232,7 +234,8 @@ int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who =
     if (w->mlp < 64 || (w->mlp % 64) != 0 || w->mlp > VIT_MAX_F)
         return fail(c, MME_E_ARG, "%s: mlp = %d; supported: multiples of 64 up to %d", who, w->mlp, VIT_MAX_F);
     if (w->layers < 1 || w->layers > VIT_MAX_L) return fail(c, MME_E_ARG, "%s: layers = %d; supported: 1..%d", who, w->layers, VIT_MAX_L);
-    if (!w->cls_token || !w->pos_emb || !w->patch_w || (!w->patch_b && !bias_free_patch) || !w->lnf_g || !w->lnf_b || !w->layer)
+    if (no_cls && w->cls_token) return fail(c, MME_E_ARG, "%s: vit.cls_token is set; supported: NULL (the tower has no class token)", who);
+    if ((!w->cls_token && !no_cls) || !w->pos_emb || !w->patch_w || (!w->patch_b && !bias_free_patch) || !w->lnf_g || !w->lnf_b || !w->layer)
         return fail(c, MME_E_ARG, "%s: null tensor pointer", who);
     for (int l = 0; l < w->layers; ++l) {
         const mme_vit_layer& a = w->layer[l];
@@ -252,7 +255,7 @@ int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     if (c->vit_alloc_hi > c->vit_alloc_lo) HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
     // exactly the image tower's buffers; a text tower loaded behind them keeps its own, its range moves down with them
     release_alloc_range(c, c->vit_alloc_lo, c->vit_alloc_hi, c->text_alloc_lo, c->text_alloc_hi);
-    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp, w->patch_size};
+    c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp, w->patch_size, w->cls_token == nullptr};  // no class token: SigLIP only (validated)
     c->ln_eps = w->ln_eps;
     c->layer.assign((size_t)w->layers, LayerDev{});
     // a plain ViT until a CLIP load says otherwise (load_clip sets these after this call; their buffers were freed above)
@@ -261,6 +264,9 @@ int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     c->proj_dim = 0;
     c->pre_g = c->pre_b = nullptr;
     c->proj_w = nullptr;
+    c->siglip = false;
+    c->head = LayerDev{};
+    c->head_q = nullptr;
     return MME_OK;
 }
 
@@ -273,8 +279,8 @@ void end_vit_load(mme_ctx* c, bool ok) {
 template <class Fn>
 void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&& f) {
     const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
-    const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size};
-    f(w.cls_token, D);
+    const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size, w.cls_token == nullptr};
+    if (w.cls_token) f(w.cls_token, D);  // SigLIP: no class token
     f(w.pos_emb, (size_t)vg.tokens() * D);
     f(w.patch_w, D * vg.patch_dim());
     if (w.patch_b) f(w.patch_b, D);  // CLIP: no bias on the patch projection
@@ -299,13 +305,13 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
     int r;
     const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
     const size_t rD[3] = {D, D, D}, rF[1] = {F};
-    const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size};  // pos [197 | 50, D], patch_w [D, 768 | 3072]
+    const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size, w.cls_token == nullptr};  // pos [197 | 50 | 196, D], patch_w [D, 768 | 3072]
     auto plain = [&](const float* src, size_t n, float** dst) { return p.table(src, n, 1.f, false, dst); };
     auto plain_bf16 = [&](const float* src, const size_t* rows, size_t cols, bf16_t** dst) {
         const void* s[1] = {src};
         return p.bf16(s, rows, 1, cols, 1.f, false, dst);
     };
-    if ((r = plain(w.cls_token, D, &c->cls))) return r;
+    if ((r = w.cls_token ? plain(w.cls_token, D, &c->cls) : p.zeros(D, &c->cls))) return r;  // SigLIP: a zero table, never read
     if ((r = plain(w.pos_emb, (size_t)vg.tokens() * D, &c->pos))) return r;
     if ((r = w.patch_b ? plain(w.patch_b, D, &c->patch_b) : p.zeros(D, &c->patch_b))) return r;  // CLIP: a zero table
     if ((r = plain(w.lnf_g, D, &c->lnf_g))) return r;
@@ -410,9 +416,115 @@ int load_clip(mme_ctx* c, const mme_clip_weights* w, P p) {
     return r;
 }
 
+// ---- SigLIP image tower: the ViT sequence (no class token), then the pooling head -----------------------------------------------
+int validate_siglip_weights(mme_ctx* c, const mme_siglip_weights* w) {
+    const char* who = "mme_load_siglip";
+    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
+    int r;
+    if ((r = validate_vit_weights(c, &w->vit, who, false, true))) return r;
+    if (!w->probe) return fail(c, MME_E_ARG, "%s: probe is a null tensor pointer", who);
+    const mme_vit_layer& a = w->head;  // ln1_g / ln1_b are not read
+    const float* all[] = {a.q_w, a.q_b, a.k_w, a.k_b, a.v_w, a.v_b, a.o_w, a.o_b, a.ln2_g, a.ln2_b, a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b};
+    for (const float* p : all)
+        if (!p) return fail(c, MME_E_ARG, "%s: head has a null tensor pointer", who);
+    return MME_OK;
+}
+
+// The head's tensors with their element counts, behind the ViT's in the staged bytes
+template <class Fn>
+void each_siglip_head_tensor(mme_siglip_weights& w, Fn&& f) {
+    const size_t D = (size_t)w.vit.hidden, F = (size_t)w.vit.mlp;
+    mme_vit_layer& a = w.head;
+    f(w.probe, D);
+    f(a.q_w, D * D); f(a.q_b, D);
+    f(a.k_w, D * D); f(a.k_b, D);
+    f(a.v_w, D * D); f(a.v_b, D);
+    f(a.o_w, D * D); f(a.o_b, D);
+    f(a.ln2_g, D); f(a.ln2_b, D);
+    f(a.fc1_w, F * D); f(a.fc1_b, F);
+    f(a.fc2_w, D * F); f(a.fc2_b, D);
+}
+
+// Prepared buffers behind the ViT's 6 + 18 L: the head's ln2_g, ln2_b, K | V bf16 [2 D, D], their bias [2 D], the K | V fold
+// with post_layernorm (wf, cs, bf), the query's three (below), o_w, o_b, fc1_w, fc1_b, the fc1 fold (wf, cs, bf), fc2_w, fc2_b.
+template <class P>
+int prepare_siglip(mme_ctx* c, P& p, const mme_siglip_weights& w) {
+    int r;
+    const size_t D = (size_t)w.vit.hidden, F = (size_t)w.vit.mlp;
+    const size_t rD[2] = {D, D}, rF[1] = {F};
+    if ((r = prepare_vit(c, p, w.vit))) return r;
+    auto plain = [&](const float* src, size_t n, float** dst) { return p.table(src, n, 1.f, false, dst); };
+    auto plain_bf16 = [&](const float* src, const size_t* rows, size_t cols, bf16_t** dst) {
+        const void* s[1] = {src};
+        return p.bf16(s, rows, 1, cols, 1.f, false, dst);
+    };
+    const mme_vit_layer& a = w.head;
+    LayerDev& L = c->head;
+    if ((r = plain(a.ln2_g, D, &L.ln2_g))) return r;
+    if ((r = plain(a.ln2_b, D, &L.ln2_b))) return r;
+    const void* kv[2] = {a.k_w, a.v_w};
+    if ((r = p.bf16(kv, rD, 2, D, 1.f, false, &L.qkv_w))) return r;
+    const void* kvb[2] = {a.k_b, a.v_b};
+    if ((r = p.table_cat(kvb, rD, 2, 1.f, false, &L.qkv_b))) return r;
+    // K | V of the head read post_layernorm(x): that LayerNorm is folded into them as ln1 is into a block's QKV
+    const WpFoldSrc fkv[2] = {{a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
+    if ((r = p.folded(fkv, rD, 2, D, w.vit.lnf_g, w.vit.lnf_b, &L.w.qkv_wf, &L.w.qkv_cs, &L.w.qkv_bf))) return r;
+    // The query is the same for every crop: q = sc (probe . W_q^T + b_q), sc = dh^-0.5 log2 e applied to W_q and b_q in f32
+    // first, as a block's query rows are.  That is the bias' of the fold, b' = b + sum_k w beta_k (f64, k ascending), with
+    // the probe standing in for beta, so both preparers compute it with the operation they share; the fold's other two
+    // outputs (W_q times post_layernorm's gamma, its column sums) are prepared and not read.
+    const float sc = 0.125f * 1.44269504088896341f;
+    const WpFoldSrc fq[1] = {{a.q_w, a.q_b, sc, 1}};
+    bf16_t* q_wf_unused;
+    float* q_cs_unused;
+    if ((r = p.folded(fq, rD, 1, D, w.vit.lnf_g, w.probe, &q_wf_unused, &q_cs_unused, &c->head_q))) return r;
+    if ((r = plain_bf16(a.o_w, rD, D, &L.w.o_w))) return r;
+    if ((r = plain(a.o_b, D, &L.w.o_b))) return r;
+    if ((r = plain_bf16(a.fc1_w, rF, D, &L.fc1_w))) return r;
+    if ((r = plain(a.fc1_b, F, &L.fc1_b))) return r;
+    const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
+    if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.w.fc1_wf, &L.w.fc1_cs, &L.w.fc1_bf))) return r;
+    if ((r = plain_bf16(a.fc2_w, rD, F, &L.w.fc2_w))) return r;
+    return plain(a.fc2_b, D, &L.w.fc2_b);
+}
+
+template <class P>
+int load_siglip(mme_ctx* c, const mme_siglip_weights* w, P p) {
+    int r;
+    if ((r = begin_vit_load(c, &w->vit))) return r;
+    std::vector<mme_vit_layer> layer(w->vit.layer, w->vit.layer + w->vit.layers);
+    mme_siglip_weights v = *w;
+    v.vit.layer = layer.data();
+    r = p.stage([&](auto& put) {
+        each_vit_tensor(v.vit, layer, put);
+        each_siglip_head_tensor(v, put);
+    });
+    if (r == MME_OK) r = prepare_siglip(c, p, v);
+    r = p.finish(r);
+    if (r == MME_OK) {
+        c->siglip = true;
+        c->act = 2;
+    }
+    end_vit_load(c, r == MME_OK);
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mme_load_siglip(mme_ctx* c, const mme_siglip_weights* w) {
+    int r;
+    if ((r = validate_siglip_weights(c, w))) return r;
+    return load_siglip(c, w, HostPrep{c});
+}
+
+int mme_load_siglip_as(mme_ctx* c, const mme_siglip_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_siglip_weights(c, w))) return r;
+    if ((r = check_load_dtype(c, dtype, "mme_load_siglip_as"))) return r;
+    return load_siglip(c, w, DevPrep(c, dtype, stream, "mme_load_siglip_as"));
+}
 
 int mme_load_clip(mme_ctx* c, const mme_clip_weights* w) {
     int r;

@@ -169,7 +169,10 @@ class RegionEmbedder:
         `geometry=`, e.g. weights.VIT_L16 or weights.VIT_B32, a `weights=` dict is sized by its tensors), "clip" (a CLIP ViT/16 or ViT/32 image tower of
         the same family: pre-LN, QuickGELU or GELU, visual projection; a checkpoint directory of CLIPVisionModel[WithProjection]
         or a whole CLIPModel, seeded weights at `geometry=` a weights.CLIPGeometry (weights.CLIP_B32 is clip-vit-base-patch32), default CLIP-B/16, or a `weights=` dict in
-        transformers' names, whose activation `geometry=` names when it is not QuickGELU) or "mllama_tiles".
+        transformers' names, whose activation `geometry=` names when it is not QuickGELU), "siglip_vit" (a SigLIP ViT/16 @224 image
+        tower: 196 tokens, tanh-GELU, the attention-pooling head; a checkpoint directory of SiglipVisionModel or a whole
+        SiglipModel, seeded weights at `geometry=` a weights.SiglipGeometry, default SigLIP-B/16, or a `weights=` dict in
+        transformers' names; `pool` must stay at its default, the head pools) or "mllama_tiles".
         `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim).
         `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
         fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
@@ -188,9 +191,15 @@ class RegionEmbedder:
         self.torch = torch
         self.model_name = model_name
         self.checkpoint = None
-        if encoder not in ("vit_b16", "vit", "clip", "mllama_tiles"):
+        if encoder not in ("vit_b16", "vit", "clip", "siglip_vit", "mllama_tiles"):
             raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16), 'vit' (the ViT/16 family: ViT-S, -B and -L widths), "
-                             "'clip' (a CLIP ViT/16 image tower of that family) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+                             "'clip' (a CLIP ViT/16 image tower of that family), 'siglip_vit' (a SigLIP ViT/16 image tower of that family) or "
+                             "'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+        if encoder == "siglip_vit" and pool != "cls":
+            raise ValueError(f"pool = {pool!r}: encoder='siglip_vit' pools with the tower's attention-pooling head; supported: the default")
+        # this class spells the tower "siglip_vit" (the bare name "siglip" stays a refused encoder here); below it is checkpoint.py's "siglip"
+        if encoder == "siglip_vit":
+            encoder = "siglip"
         if encoder == "vit_b16" and geometry is not None:
             raise ValueError("encoder='vit_b16' is ViT-B/16 only; pass encoder='vit' with geometry=")
         self.resize_rule = check_resize_rule(resize_rule, encoder)
@@ -235,6 +244,8 @@ class RegionEmbedder:
                     e.load_tile_vit_checkpoint(ck, geom)
                 elif encoder == "clip":
                     e.load_clip_checkpoint(ck)
+                elif encoder == "siglip":
+                    e.load_siglip_checkpoint(ck)
                 else:
                     e.load_vit_checkpoint(ck)
                 if ck.image_mean is not None:
@@ -251,6 +262,12 @@ class RegionEmbedder:
                 w = weights if weights is not None else make_clip_weights(seed, geometry or CLIP_B16)
                 if weights is None and geometry is None:
                     geometry = CLIP_B16
+            elif encoder == "siglip":
+                from .weights import SIGLIP_B16, make_siglip_weights
+
+                w = weights if weights is not None else make_siglip_weights(seed, geometry or SIGLIP_B16)
+                if weights is None and geometry is None:
+                    geometry = SIGLIP_B16
             elif encoder == "vit" and geometry is not None:
                 w = weights if weights is not None else make_vit_weights(seed, geometry)
             else:
@@ -262,6 +279,8 @@ class RegionEmbedder:
                     e.load_tile_vit(w, geometry)
                 elif encoder == "clip":
                     e.load_clip(w, geom=geometry)
+                elif encoder == "siglip":
+                    e.load_siglip(w, geom=geometry)
                 elif encoder == "vit":
                     e.load_vit(w, geom=geometry)
                 else:
@@ -287,6 +306,7 @@ class RegionEmbedder:
         if pool not in ("cls", "last"):
             raise ValueError("pool must be 'cls' or 'last'")
         # the last token: 196 of the 197 at patch 16 (the same at every width), 49 of the 50 at patch 32
+        # (SigLIP: the library ignores the token, the head pools)
         self.pool_token = 0 if pool == "cls" else (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1)
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
         self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
@@ -730,7 +750,7 @@ class RegionEmbedder:
 
         src = getattr(self, "_text_source", False)
         eng = self.engines[0]
-        if src is False:
+        if src is False or getattr(self, "encoder", None) == "siglip":  # (a CLIP text tower embeds into another space than a SigLIP image tower)
             raise NotImplementedError(self._NO_TOWER)
         if isinstance(src, dict):
             eng.load_clip_text(src)

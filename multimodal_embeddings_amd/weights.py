@@ -228,6 +228,130 @@ def infer_clip_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quick_gel
                         layer_norm_eps=float(eps), projection_dim=P, hidden_act=hidden_act)
 
 
+# ---- SigLIP ViT/16 image towers ---------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class SiglipGeometry(ViTGeometry):
+    """A SigLIP image tower at the engine's ViT/16 @224 geometry (transformers SiglipVisionConfig): the ViT fields with
+    layer_norm_eps 1e-6, no class token (196 tokens), `gelu_pytorch_tanh` in every MLP and the attention-pooling head
+    (`vision_use_head`).  The embedding is the head's output, `hidden_size` wide.  The defaults are siglip-base-patch16-224."""
+
+    layer_norm_eps: float = 1e-6
+    hidden_act: str = "gelu_pytorch_tanh"
+    vision_use_head: bool = True
+
+    @property
+    def seq_len(self) -> int:
+        return self.num_patches
+
+    @property
+    def embed_dim(self) -> int:
+        return self.hidden_size
+
+
+SIGLIP_B16 = SiglipGeometry()
+SUPPORTED_SIGLIP = {"patch_size": (16,), "hidden_act": ("gelu_pytorch_tanh",), "vision_use_head": (True,)}
+
+
+def siglip_geometry_problem(geom: SiglipGeometry):
+    """As `vit_geometry_problem` with patch 16 only and the two SigLIP fields: None, or (field, value found, supported values as text)."""
+    if geom.patch_size not in SUPPORTED_SIGLIP["patch_size"]:
+        return "patch_size", geom.patch_size, "16"
+    bad = vit_geometry_problem(geom)
+    if bad:
+        return bad
+    if geom.hidden_act not in SUPPORTED_SIGLIP["hidden_act"]:
+        return "hidden_act", geom.hidden_act, "gelu_pytorch_tanh"
+    if geom.vision_use_head is not True:
+        return "vision_use_head", geom.vision_use_head, "True (the attention-pooling head)"
+    return None
+
+
+def siglip_tensor_specs(geom: SiglipGeometry = SIGLIP_B16):
+    """(name, shape, kind) in a fixed order, the state-dict names of a `SiglipVisionModel` inside a `SiglipModel`
+    (transformers models/siglip/modeling_siglip.py; prefix "vision_model."); kind in {matrix, bias, gamma}."""
+    D, F, P = geom.hidden_size, geom.intermediate_size, geom.patch_size
+    v = "vision_model."
+    specs = [
+        (v + "embeddings.patch_embedding.weight", (D, geom.num_channels, P, P), "matrix"),
+        (v + "embeddings.patch_embedding.bias", (D,), "bias"),
+        (v + "embeddings.position_embedding.weight", (geom.seq_len, D), "matrix"),
+    ]
+    for i in range(geom.num_layers):
+        p = f"{v}encoder.layers.{i}."
+        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
+        for n in ("q", "k", "v", "out"):
+            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
+        specs += [
+            (p + "layer_norm2.weight", (D,), "gamma"),
+            (p + "layer_norm2.bias", (D,), "bias"),
+            (p + "mlp.fc1.weight", (F, D), "matrix"),
+            (p + "mlp.fc1.bias", (F,), "bias"),
+            (p + "mlp.fc2.weight", (D, F), "matrix"),
+            (p + "mlp.fc2.bias", (D,), "bias"),
+        ]
+    h = v + "head."
+    specs += [
+        (v + "post_layernorm.weight", (D,), "gamma"),
+        (v + "post_layernorm.bias", (D,), "bias"),
+        (h + "probe", (1, 1, D), "matrix"),
+        (h + "attention.in_proj_weight", (3 * D, D), "matrix"),
+        (h + "attention.in_proj_bias", (3 * D,), "bias"),
+        (h + "attention.out_proj.weight", (D, D), "matrix"),
+        (h + "attention.out_proj.bias", (D,), "bias"),
+        (h + "layernorm.weight", (D,), "gamma"),
+        (h + "layernorm.bias", (D,), "bias"),
+        (h + "mlp.fc1.weight", (F, D), "matrix"),
+        (h + "mlp.fc1.bias", (F,), "bias"),
+        (h + "mlp.fc2.weight", (D, F), "matrix"),
+        (h + "mlp.fc2.bias", (D,), "bias"),
+    ]
+    return specs
+
+
+def make_siglip_weights(seed: int = 4, geom: SiglipGeometry = SIGLIP_B16, std: float = 0.02) -> dict[str, np.ndarray]:
+    """Seeded synthetic weights of a SigLIP image tower, f32 arrays holding bf16-representable values: the generator and the
+    LayerNorm spread of `make_clip_weights` on `siglip_tensor_specs`.  The probe is N(0, 1) as transformers initialises it,
+    so that the head's scores are spread over the keys instead of near-uniform."""
+    out: dict[str, np.ndarray] = {}
+    for tid, (name, shape, kind) in enumerate(siglip_tensor_specs(geom)):
+        n = int(np.prod(shape))
+        z = irwin_hall_normal(seed, tid, n)
+        norm = "layer_norm" in name or "layernorm" in name
+        if kind == "gamma":
+            z = np.float32(1.0) + z * np.float32(0.25)
+        elif kind == "bias" and norm:
+            z = z * np.float32(0.1)
+        elif name.endswith("head.probe"):
+            pass
+        else:
+            z = z * np.float32(std)
+        out[name] = round_to_bf16(z).reshape(shape)
+    return out
+
+
+def siglip_flops_per_crop(geom: SiglipGeometry = SIGLIP_B16) -> int:
+    """`vit_flops_per_crop` at 196 tokens plus the head: K | V over the 196 tokens (4 T D^2), the pooled attention (4 T D),
+    out_proj (2 D^2) and the head's MLP (4 D F)."""
+    D, F, T = geom.hidden_size, geom.intermediate_size, geom.seq_len
+    return vit_flops_per_crop(geom) + 4 * T * D * D + 4 * T * D + 2 * D * D + 4 * D * F
+
+
+def infer_siglip_geometry(w: dict, eps: float = 1e-6) -> SiglipGeometry:
+    """The geometry of a `siglip_tensor_specs` weight dict, read off its tensor shapes; heads of 64."""
+    pw = np.shape(w["vision_model.embeddings.patch_embedding.weight"])
+    D, patch = int(pw[0]), int(pw[-1])
+    tokens = int(np.shape(w["vision_model.embeddings.position_embedding.weight"])[0])
+    grid = int(round(tokens ** 0.5))
+    layers = 0
+    while f"vision_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError("the weight dict holds no 'vision_model.encoder.layers.0.mlp.fc1.weight'")
+    F = int(np.shape(w["vision_model.encoder.layers.0.mlp.fc1.weight"])[0])
+    return SiglipGeometry(image_size=grid * patch, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
+                          layer_norm_eps=float(eps))
+
+
 # ---- CLIP text towers -------------------------------------------------------------------------------------------------
 TEXT_TOKENS = 77  # CLIPTextConfig.max_position_embeddings; fixed at compile time (csrc/common.h TXT_T)
 
