@@ -265,6 +265,92 @@ typedef struct mme_text_apply_args {
 } mme_text_apply_args;
 int mme_text_apply(mme_ctx* ctx, int op, const mme_text_apply_args* args, void* stream);
 
+/* ---- SigLIP text tower ----------------------------------------------------------------------------------------------------
+ * Replaces `SiglipTextModel.from_pretrained(dir)(input_ids).pooler_output`, L2-normalised: the text side of the space a SigLIP
+ * image tower embeds into (transformers models/siglip/modeling_siglip.py, SiglipTextTransformer):
+ *   - SiglipTextEmbeddings: token_embedding[ids] + position_embedding (positions 0..63);
+ *   - SiglipEncoderLayer x layers, pre-LN, with NO mask of any kind (the model was trained on padding="max_length" without an
+ *     attention_mask: pad tokens are attended), tanh-GELU (gelu_pytorch_tanh) in the MLP;
+ *   - final_layer_norm; the row at position 63 of every sequence (last_hidden_state[:, -1, :], padding or not); head, a
+ *     Linear [projection_size, hidden] WITH bias; x / max(||x||, 1e-12).
+ * Supported geometry: max_positions 64, heads of 64, hidden 512, 768 or 1024 (heads == hidden / 64), mlp a multiple of 64 up
+ * to 8192, 1..64 layers, vocab 3..262144 (SigLIP 32000, SigLIP 2 256000; every id-to-row offset is 64-bit), projection_size a
+ * multiple of 64 up to 1024, 0 <= pad_token_id < vocab, any ln_eps.  Anything else (so400m's hidden 1152 / heads of 72, 77
+ * positions, ...) is MME_E_ARG naming the field, the value found and the supported set, and nothing in the context changes.
+ * The tower lives in the context's TEXT range: a SigLIP text load replaces a CLIP text load and vice versa, the image tower is
+ * untouched, under whatever image tower the context holds.  Both loaders run the ONE prepare sequence of the text towers and
+ * leave bit-identical buffers (mme_weights_read order): tok bf16 [V, D], pos [64, D], lnf_g [D], lnf_b [D]; 10 per layer as for
+ * the CLIP text tower; head_w bf16 [P, D], head_b [P].
+ * has_logits != 0: logit_scale / logit_bias are SiglipModel's two scalars (mme_siglip_scores); 0: the checkpoint is a bare
+ * SiglipTextModel and the two fields are ignored. */
+typedef struct {
+    int32_t hidden;          /* 512, 768 or 1024 */
+    int32_t layers;          /* 1..64 */
+    int32_t heads;           /* hidden / 64 */
+    int32_t mlp;             /* multiple of 64, <= 8192 */
+    int32_t vocab;           /* 3..262144 */
+    int32_t max_positions;   /* 64 */
+    int32_t projection_size; /* multiple of 64 up to 1024 */
+    int32_t pad_token_id;    /* what a caller pads short sequences with (mme_text_geometry reports it; the pass attends it) */
+    int32_t has_logits;
+    float ln_eps;            /* 1e-6 */
+    float logit_scale;       /* the stored value: scores use exp(logit_scale) */
+    float logit_bias;
+    const float* token_emb;  /* [vocab, hidden] */
+    const float* pos_emb;    /* [64, hidden] */
+    const float* lnf_g;      /* final_layer_norm */
+    const float* lnf_b;
+    const float* head_w;     /* head.weight [projection_size, hidden] */
+    const float* head_b;     /* head.bias [projection_size] */
+    const mme_vit_layer* layer; /* [layers] */
+} mme_siglip_text_weights;
+int mme_load_siglip_text(mme_ctx* ctx, const mme_siglip_text_weights* w);
+int mme_load_siglip_text_as(mme_ctx* ctx, const mme_siglip_text_weights* w, int dtype, void* stream);
+/* out[4] = kind (0 no text tower, 1 CLIP, 2 SigLIP), tokens per sequence (77 or 64: the row length of mme_text_forward's ids),
+ * projection width (0: none), pad id (SigLIP: pad_token_id; CLIP: eos_token_id, which its tokenizer pads with).
+ * mme_text_info's 9 words are unchanged; under a SigLIP tower its act is 2 (tanh-GELU) and its last word is pad_token_id.
+ * mme_text_forward under a SigLIP tower reads ids int32 [n, 64], checks them against the vocabulary only (there is no EOS scan)
+ * and pools position 63. */
+int mme_text_geometry(mme_ctx* ctx, int32_t out[4]);
+/* out_f32[i] = 1 / (1 + exp(-(cos_f32[i] * exp(logit_scale) + logit_bias))), i < m * N, on DEVICE buffers (out_f32 may be
+ * cos_f32): SiglipModel.forward's sigmoid of logits_per_text for a cosine block [m, N] (mme_cosine).  exp(logit_scale) is
+ * formed once on the host in f32.  MME_E_STATE unless the loaded text tower is SigLIP's and brought the two scalars.
+ * Enqueued on `stream`; does not synchronise. */
+int mme_siglip_scores(mme_ctx* ctx, const float* cos_f32, int64_t m, int64_t N, float* out_f32, void* stream);
+/* Diagnostic: ONE launch of a kernel the SigLIP text tower adds, on the caller's DEVICE buffers (ids: HOST, validated and
+ * copied), synchronous; works on a bare context.
+ *   op 0 token rows        x[b*64 + t] = bf16(f32(tok[ids[b*64 + t]]) + pos[t]), b < n; tok bf16 [vocab, d], pos f32 [64, d]
+ *      1 attention         qkv bf16 [n*64, 3*64*heads] (Q | K | V, Q pre-scaled by dh^-0.5 log2 e) -> out bf16 [n*64, 64*heads], no
+ *                          mask; only_block -1 (both query blocks of 32), 0 or 1 (that block only; the other rows of out untouched)
+ *      2 last-row pool-LN  y[b] = bf16(LayerNorm(x[b*64 + 63]) * gamma + beta) to y bf16 [n, d] and / or unrounded to y_f32 [n, d]
+ *      3 bias + L2         y = acc[b] + bias; emb[b] = y / max(||y||, 1e-12); acc f32 [n, p], bias f32 [p] -> emb_f32 and / or emb_bf16
+ *      4 scores            scores[i] = 1 / (1 + exp(-(cos[i] * exp(logit_scale) + logit_bias))), i < count (scores may be cos)
+ * Preconditions (else MME_E_ARG, nothing launched): n >= 0; ops 0, 2: d == 512, 768 or 1024; op 1: heads == 8, 12 or 16,
+ * only_block in -1..1; op 3: p % 64 == 0, 64 <= p <= 1024; every pointer the op uses non-null and 16-byte aligned (ids: non-null;
+ * op 4: 4-byte aligned); op 0: 1 <= vocab <= 262144 and every id in 0..vocab-1; ops 2, 3: at least one output. */
+typedef struct mme_siglip_text_apply_args {
+    const uint16_t* tok;     /* op 0 */
+    const float* pos;        /* op 0 */
+    const int32_t* ids_host; /* op 0: [n, 64] */
+    uint16_t* x;             /* op 0: out bf16 [n*64, d]; op 2: in */
+    const uint16_t* qkv;     /* op 1 */
+    uint16_t* out;           /* op 1 */
+    const float* gamma;      /* op 2 */
+    const float* beta;
+    uint16_t* y;             /* op 2 */
+    float* y_f32;            /* op 2 */
+    const float* acc;        /* op 3 */
+    const float* bias;       /* op 3 */
+    float* emb_f32;          /* op 3 */
+    uint16_t* emb_bf16;      /* op 3 */
+    const float* cos;        /* op 4 */
+    float* scores;           /* op 4 */
+    int64_t count;           /* op 4 */
+    int32_t n, d, heads, vocab, only_block, p;
+    float eps, logit_scale, logit_bias;
+} mme_siglip_text_apply_args;
+int mme_siglip_text_apply(mme_ctx* ctx, int op, const mme_siglip_text_apply_args* args, void* stream);
+
 /* Diagnostic (synchronises the device): one 64-bit word per prepared weight buffer of the context, in the order the
  * loaders created them (the ViT buffers of mme_load_vit[_as], then the tile-ViT buffers of mme_load_tile_vit[_as], when
  * loaded in that order).  The word is a position-dependent checksum of the buffer's bytes -- the sum over its 32-bit words

@@ -62,6 +62,18 @@ class _TextApplyArgs(C.Structure):  # mme_text_apply_args
         ("n", C.c_int32), ("d", C.c_int32), ("heads", C.c_int32), ("vocab", C.c_int32), ("eps", C.c_float)]
 
 
+class _SiglipTextWeights(C.Structure):  # mme_siglip_text_weights
+    _fields_ = [(n, C.c_int32) for n in ("hidden", "layers", "heads", "mlp", "vocab", "max_positions", "projection_size", "pad_token_id", "has_logits")] + [
+        (n, C.c_float) for n in ("ln_eps", "logit_scale", "logit_bias")] + [
+        (n, C.POINTER(C.c_float)) for n in ("token_emb", "pos_emb", "lnf_g", "lnf_b", "head_w", "head_b")] + [("layer", C.POINTER(_Layer))]
+
+
+class _SiglipTextApplyArgs(C.Structure):  # mme_siglip_text_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("tok", "pos", "ids_host", "x", "qkv", "out", "gamma", "beta", "y", "y_f32", "acc", "bias", "emb_f32", "emb_bf16",
+                                          "cos", "scores")] + [("count", C.c_int64)] + [
+        (n, C.c_int32) for n in ("n", "d", "heads", "vocab", "only_block", "p")] + [(n, C.c_float) for n in ("eps", "logit_scale", "logit_bias")]
+
+
 class _TileLayer(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_float)) for n in ("ln1_g", "ln1_b", "q_w", "k_w", "v_w", "o_w", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")] + [
         ("gate_attn", C.c_float), ("gate_ffn", C.c_float), ("gated", C.c_int32)]
@@ -160,6 +172,11 @@ EXPORTS = {
     "mme_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_text_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_text_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_TextApplyArgs), C.c_void_p]),
+    "mme_load_siglip_text": (C.c_int, [C.c_void_p, C.POINTER(_SiglipTextWeights)]),
+    "mme_load_siglip_text_as": (C.c_int, [C.c_void_p, C.POINTER(_SiglipTextWeights), C.c_int, C.c_void_p]),
+    "mme_text_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_siglip_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mme_siglip_text_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_SiglipTextApplyArgs), C.c_void_p]),
     "mme_weights_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "mme_weights_read": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "mme_weight_prep_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_WeightPrepApplyArgs), C.c_void_p]),
@@ -641,9 +658,19 @@ class Engine:
 
         o = (C.c_int32 * 9)()
         self._check(self.lib.mme_text_info(self.h, o), "mme_text_info")
+        acts = tuple(CLIP_ACTS) + ("gelu_pytorch_tanh",)  # EncoderPass::act; 2 under a SigLIP text tower, whose last word is pad_token_id
         return {"loaded": int(o[0]), "hidden_size": int(o[1]), "num_layers": int(o[2]), "num_heads": int(o[3]), "intermediate_size": int(o[4]),
-                "vocab_size": int(o[5]), "projection_dim": int(o[6]) or None, "hidden_act": CLIP_ACTS[o[7]] if o[0] else None,
+                "vocab_size": int(o[5]), "projection_dim": int(o[6]) or None, "hidden_act": acts[o[7]] if o[0] else None,
                 "eos_token_id": int(o[8])}
+
+    TEXT_KINDS = (None, "clip", "siglip")
+
+    def text_geometry(self) -> dict:
+        """What `text_forward` takes and gives under the loaded text tower (mme_text_geometry): kind None | "clip" | "siglip",
+        tokens per sequence (77 | 64; 0 before a text load), projection width (None: none), pad id."""
+        o = (C.c_int32 * 4)()
+        self._check(self.lib.mme_text_geometry(self.h, o), "mme_text_geometry")
+        return {"kind": self.TEXT_KINDS[o[0]], "tokens": int(o[1]), "projection": int(o[2]) or None, "pad_token_id": int(o[3])}
 
     @property
     def text_embed_dim(self) -> int:
@@ -652,12 +679,14 @@ class Engine:
         return int(i["projection_dim"] or i["hidden_size"])
 
     def text_forward(self, ids, want_f32: bool = True, want_bf16: bool = True):
-        """int token ids [n, 77] (host) -> (f32 [n, text_embed_dim] | None, bf16 | None) CUDA tensors of unit rows
-        (mme_text_forward).  The library checks every id and finds each sequence's EOS position; n = 0 gives empty tensors."""
+        """int token ids [n, 77] (host; [n, 64] under a SigLIP text tower) -> (f32 [n, text_embed_dim] | None, bf16 | None) CUDA
+        tensors of unit rows (mme_text_forward).  The library checks every id and finds each sequence's EOS position (CLIP) or
+        pools position 63 (SigLIP); n = 0 gives empty tensors."""
         t = self.torch
         a = np.asarray(ids)
-        if a.ndim != 2 or a.shape[1] != 77 or a.dtype.kind not in "iu":
-            raise MmeError(f"text_forward: ids must be an integer array [n, 77], got {a.dtype} {tuple(a.shape)}")
+        T = self.text_geometry()["tokens"] or 77
+        if a.ndim != 2 or a.shape[1] != T or a.dtype.kind not in "iu":
+            raise MmeError(f"text_forward: ids must be an integer array [n, {T}], got {a.dtype} {tuple(a.shape)}")
         if a.size and (a.min() < -2**31 or a.max() >= 2**31):
             raise MmeError("text_forward: an id does not fit 32 bits")
         a = np.ascontiguousarray(a, dtype=np.int32)
@@ -689,6 +718,114 @@ class Engine:
         a.ids_host, a.eos_pos_host = host(ids), host(eos_pos)
         a.n, a.d, a.heads, a.vocab, a.eps = int(n), int(d), int(heads), int(vocab), float(eps)
         self._check(self.lib.mme_text_apply(self.h, int(self.TEXT_OPS.get(op, op)), C.byref(a), self._stream()), "mme_text_apply")
+
+    # ---- SigLIP text tower (mme_load_siglip_text*): takes the text range of the context, beside whatever image tower it holds ----
+    @staticmethod
+    def _siglip_text_struct(geom, arr, logits):
+        """mme_siglip_text_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.SiglipTextGeometry),
+        tensor pointers from arr(name) over the names of weights.siglip_text_tensor_specs; `logits` (logit_scale, logit_bias) or None."""
+        from .weights import siglip_text_geometry_problem
+
+        bad = siglip_text_geometry_problem(geom)
+        if bad and bad[0] == "hidden_act":  # the struct has no field for it: the library runs tanh-GELU
+            raise MmeError(f"hidden_act = {bad[1]!r}; supported: {bad[2]}")
+        t = "text_model."
+        layers = (_Layer * max(0, int(geom.num_layers)))()
+        for i in range(len(layers)):
+            p = f"{t}encoder.layers.{i}."
+            L = layers[i]
+            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
+            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
+            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
+            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
+            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
+            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
+            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
+            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+        W = _SiglipTextWeights(geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size, geom.vocab_size, geom.max_position_embeddings,
+                               int(geom.projection_size), int(geom.pad_token_id), int(logits is not None), float(geom.layer_norm_eps),
+                               float(logits[0]) if logits else 0.0, float(logits[1]) if logits else 0.0)
+        W.token_emb = arr(t + "embeddings.token_embedding.weight")
+        W.pos_emb = arr(t + "embeddings.position_embedding.weight")
+        W.lnf_g, W.lnf_b = arr(t + "final_layer_norm.weight"), arr(t + "final_layer_norm.bias")
+        W.head_w, W.head_b = arr(t + "head.weight"), arr(t + "head.bias")
+        W.layer = layers
+        return W, layers
+
+    @staticmethod
+    def _siglip_logits(get):
+        """(logit_scale, logit_bias) as floats from get(name) -> a one-value array / tensor or None; None when both are absent."""
+        vals = [get(k) for k in ("logit_scale", "logit_bias")]
+        if vals[0] is None and vals[1] is None:
+            return None
+        if vals[0] is None or vals[1] is None:
+            raise MmeError("load_siglip_text: logit_scale and logit_bias come together (a whole SiglipModel) or not at all")
+        return tuple(float(np.asarray(v.float() if hasattr(v, "float") and not isinstance(v, np.ndarray) else v, dtype=np.float32).reshape(-1)[0]) for v in vals)
+
+    def load_siglip_text(self, w: dict, geom=None):
+        """`weights.siglip_text_tensor_specs` dict of f32 arrays (the text half of transformers' SiglipModel state dict; with
+        `logit_scale` / `logit_bias` beside the tensors, `siglip_scores` works) -> the text tower of this context, replacing an
+        earlier text tower of either kind and nothing else.  `geom`: a weights.SiglipTextGeometry; by default read off the shapes."""
+        from .weights import infer_siglip_text_geometry, siglip_text_tensor_specs
+
+        if geom is None:
+            geom = infer_siglip_text_geometry(w)
+        for name, shape, _ in siglip_text_tensor_specs(geom) if 0 < geom.num_layers <= 64 else ():
+            if name not in w:
+                raise MmeError(f"load_siglip_text: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"load_siglip_text: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32)
+            keep.append(a)
+            return _fp(a)
+
+        W, layers = self._siglip_text_struct(geom, arr, self._siglip_logits(w.get))
+        self._check(self.lib.mme_load_siglip_text(self.h, C.byref(W)), "mme_load_siglip_text")
+
+    def load_siglip_text_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "siglip_text")` -> the text tower of this context, prepared on the device from the
+        file's own f32 / bf16 / f16 bytes, bit-identically to `load_siglip_text` on the same values."""
+        if ckpt.encoder != "siglip_text":
+            raise MmeError(f"load_siglip_text_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        W, layers = self._siglip_text_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name), self._siglip_logits(ckpt.tensors.get))
+        self._check(self.lib.mme_load_siglip_text_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_siglip_text_as")
+
+    def siglip_scores(self, cos, out=None):
+        """f32 CUDA cosine block [m, N] (`cosine`) -> sigmoid(exp(logit_scale) cos + logit_bias), f32 [m, N] (mme_siglip_scores):
+        SiglipModel's probabilities.  `out` may be `cos` (in place).  MmeError unless the loaded text tower is SigLIP's with its two scalars."""
+        t = self.torch
+        if cos.dtype != t.float32 or cos.dim() != 2 or not cos.is_contiguous():
+            raise MmeError(f"siglip_scores: cos must be a contiguous f32 [m, N] tensor, got {cos.dtype} {tuple(cos.shape)}")
+        if out is None:
+            out = t.empty_like(cos)
+        if out.dtype != t.float32 or tuple(out.shape) != tuple(cos.shape) or not out.is_contiguous():
+            raise MmeError("siglip_scores: out must match cos")
+        self._check(self.lib.mme_siglip_scores(self.h, cos.data_ptr() if cos.numel() else None, int(cos.shape[0]), int(cos.shape[1]),
+                                               out.data_ptr() if cos.numel() else None, self._stream()), "mme_siglip_scores")
+        return out
+
+    SIGLIP_TEXT_OPS = {"token_rows": 0, "attention": 1, "last_pool_ln": 2, "bias_l2": 3, "scores": 4}
+
+    def siglip_text_apply(self, op, *, tok=None, pos=None, ids=None, x=None, qkv=None, out=None, gamma=None, beta=None, y=None, y_f32=None, acc=None,
+                          bias=None, emb_f32=None, emb_bf16=None, cos=None, scores=None, count=None, n: int = 0, d: int = 512, heads: int = 8,
+                          vocab: int = 0, only_block: int = -1, p: int = 64, eps: float = 1e-6, logit_scale: float = 0.0, logit_bias: float = 0.0):
+        """ONE launch of a kernel the SigLIP text tower adds, on the caller's CUDA tensors (mme_siglip_text_apply; synchronous,
+        works on a bare context).  op: a name of SIGLIP_TEXT_OPS or its code; `ids` [n, 64] is a host integer array; `count`
+        defaults to cos.numel().  The library validates."""
+        a = _SiglipTextApplyArgs()
+        h = None
+        if ids is not None:
+            h = np.ascontiguousarray(np.asarray(ids), dtype=np.int32)
+            a.ids_host = h.ctypes.data
+        (a.tok, a.pos, a.x, a.qkv, a.out, a.gamma, a.beta, a.y, a.y_f32, a.acc, a.bias, a.emb_f32, a.emb_bf16, a.cos, a.scores) = (
+            self._ptr(t) for t in (tok, pos, x, qkv, out, gamma, beta, y, y_f32, acc, bias, emb_f32, emb_bf16, cos, scores))
+        a.count = int(cos.numel() if count is None and cos is not None else (count or 0))
+        a.n, a.d, a.heads, a.vocab, a.only_block, a.p = int(n), int(d), int(heads), int(vocab), int(only_block), int(p)
+        a.eps, a.logit_scale, a.logit_bias = float(eps), float(logit_scale), float(logit_bias)
+        self._check(self.lib.mme_siglip_text_apply(self.h, int(self.SIGLIP_TEXT_OPS.get(op, op)), C.byref(a), self._stream()), "mme_siglip_text_apply")
 
     @staticmethod
     def _tile_struct(geom, arr, gate):

@@ -15,7 +15,7 @@ attention-pooling head, `SiglipVisionModel` or the vision half of a whole `Sigli
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
 bytes to the device, where they are converted and folded (csrc/weight_load.hip: DevPrep; kernels in csrc/weight_prep.hip).
 
-    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text|siglip_vit]
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text|siglip_vit|siglip_text]
 
 prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
 """
@@ -32,11 +32,12 @@ from . import config
 from ._lib import MmeError
 from .weights import (CLIP_B16, CLIP_TEXT_B, SIGLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, SiglipGeometry, TileViTGeometry, ViTGeometry,
                       clip_geometry_problem, clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, siglip_geometry_problem,
-                      siglip_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem, vit_tensor_specs)
+                      siglip_tensor_specs, siglip_text_geometry_problem, siglip_text_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem,
+                      vit_tensor_specs)
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip")
+ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip", "siglip_text")
 # The command line below and RegionEmbedder spell the SigLIP tower "siglip_vit": both have always refused the bare name
 # "siglip" as an unknown encoder and keep doing so; read_checkpoint, Checkpoint.encoder and the Engine say "siglip".
 SIGLIP_ALIAS = "siglip_vit"
@@ -139,6 +140,17 @@ def canonical_siglip_name(key: str):
     # SiglipVisionModel.save_pretrained of transformers 5 writes the tower's own keys, without the "vision_model." prefix
     if key.startswith(("embeddings.", "encoder.layers.", "post_layernorm.", "head.")):
         return "vision_model." + key
+    return key
+
+
+def canonical_siglip_text_name(key: str):
+    """Checkpoint key -> canonical name (`weights.siglip_text_tensor_specs`: the text keys of a `SiglipModel`, and its two
+    scalars `logit_scale` / `logit_bias`), or None for what the text tower does not use: the image tower, the position_ids buffers."""
+    if key.startswith("vision_model.") or key.endswith(".position_ids"):
+        return None
+    # SiglipTextModel.save_pretrained of transformers 5 writes the tower's own keys, without the "text_model." prefix
+    if key.startswith(("embeddings.", "encoder.layers.", "final_layer_norm.", "head.")):
+        return "text_model." + key
     return key
 
 
@@ -250,6 +262,32 @@ def _clip_text_geometry(cfg: dict, where: str, projection_dim) -> CLIPTextGeomet
                          max_position_embeddings=fields["max_position_embeddings"], eos_token_id=fields["eos_token_id"], projection_dim=projection_dim,
                          hidden_act=cfg.get("hidden_act", b.hidden_act), layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
     bad = clip_text_geometry_problem(g)
+    if bad:
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    return g
+
+
+def _siglip_text_geometry(cfg: dict, where: str):
+    """The text configuration of a SigLIP checkpoint (SiglipTextConfig) -> geometry.  A field the file leaves out has
+    SiglipTextConfig's default (siglip-base-patch16-224's text tower; projection_size: hidden_size), as transformers reads it."""
+    from .weights import SIGLIP_TEXT_B, SiglipTextGeometry
+
+    b = SIGLIP_TEXT_B
+    fields = {"hidden_size": b.hidden_size, "num_hidden_layers": b.num_layers, "num_attention_heads": b.num_heads, "intermediate_size": b.intermediate_size,
+              "vocab_size": b.vocab_size, "max_position_embeddings": b.max_position_embeddings, "pad_token_id": b.pad_token_id}
+    for fld, default in fields.items():
+        v = cfg.get(fld, default)
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise MmeError(f"{where}: {fld} = {v!r}; an integer is required")
+        fields[fld] = v
+    proj = cfg.get("projection_size")
+    g = SiglipTextGeometry(hidden_size=fields["hidden_size"], num_layers=fields["num_hidden_layers"], num_heads=fields["num_attention_heads"],
+                           intermediate_size=fields["intermediate_size"], vocab_size=fields["vocab_size"],
+                           max_position_embeddings=fields["max_position_embeddings"], pad_token_id=fields["pad_token_id"],
+                           projection_size=fields["hidden_size"] if proj is None else proj, hidden_act=cfg.get("hidden_act", b.hidden_act),
+                           layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
+    bad = siglip_text_geometry_problem(g)
     if bad:
         names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
         raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
@@ -479,6 +517,17 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         geometry = _clip_text_geometry(tcfg, where, tcfg.get("projection_dim"))
         canonical = canonical_clip_text_name
         specs = None  # after the tensors are read: a CLIPTextModel checkpoint has no text_projection
+    elif encoder == "siglip_text":
+        where, tcfg = "config.json", cfg
+        if "text_config" in cfg:  # a whole SigLIP model
+            tcfg, where = dict(cfg["text_config"]), "config.json: text_config"
+        elif cfg.get("model_type") == "siglip_vision_model":
+            raise MmeError(f"{path}: config.json has model_type = 'siglip_vision_model': the directory holds no text tower")
+        if "naflex" in str(cfg.get("model_type", "")).lower() or "naflex" in str(tcfg.get("model_type", "")).lower():
+            raise MmeError(f"{where}: model_type = {cfg.get('model_type')!r}; supported: siglip, siglip_text_model (the NaFlex variants are not run)")
+        geometry = _siglip_text_geometry(tcfg, where)
+        canonical = canonical_siglip_text_name
+        specs = None  # after the tensors are read: a SiglipTextModel checkpoint has no logit_scale / logit_bias
     else:
         where = "config.json"
         if "vision_config" in cfg:  # a whole Mllama model
@@ -502,6 +551,19 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         elif geometry.projection_dim is None:
             raise MmeError(f"{path}: the checkpoint holds {keys['text_projection.weight']!r} but {where} names no projection_dim")
         specs = [(n, s) for n, s, _ in clip_text_tensor_specs(geometry)]
+    elif encoder == "siglip_text":
+        from .weights import SIGLIP_LOGIT_KEYS
+
+        specs = [(n, s) for n, s, _ in siglip_text_tensor_specs(geometry)]
+        tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs} | set(SIGLIP_LOGIT_KEYS))
+        have = [k for k in SIGLIP_LOGIT_KEYS if k in tensors]
+        if len(have) == 1:
+            raise MmeError(f"{path}: the checkpoint holds {have[0]!r} without the other of {SIGLIP_LOGIT_KEYS}")
+        for k in have:  # SiglipModel stores them as [1]; kept beside the tower's tensors
+            if tensors[k].numel() != 1:
+                raise MmeError(f"{path}: tensor {keys[k]!r} has shape {tuple(tensors[k].shape)}, expected one value")
+            tensors[k] = tensors[k].reshape(1)
+            specs.append((k, (1,)))
     else:
         tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs})
     source += files
@@ -513,7 +575,7 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
     tensors, dtype = _unify_dtype({n: tensors[n] for n, _ in specs}, keys)
     mean = std = None
     pre_path = os.path.join(path, "preprocessor_config.json")
-    if os.path.exists(pre_path) and encoder != "clip_text":  # a text tower reads no pixels
+    if os.path.exists(pre_path) and encoder not in ("clip_text", "siglip_text"):  # a text tower reads no pixels
         mean, std = _read_preprocessor(pre_path, encoder, resize_rule)
         source.append(pre_path)
     return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source)
@@ -560,6 +622,14 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
                "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "eos_token_id": g.eos_token_id, "dtype": dtype}
         if g.projection_dim:
             cfg["projection_dim"] = g.projection_dim
+    elif encoder == "siglip_text":
+        from .weights import SIGLIP_TEXT_B
+
+        g = geometry or SIGLIP_TEXT_B
+        cfg = {"architectures": ["SiglipTextModel"], "model_type": "siglip_text_model", "vocab_size": g.vocab_size, "hidden_size": g.hidden_size,
+               "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
+               "max_position_embeddings": g.max_position_embeddings, "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps,
+               "attention_dropout": 0.0, "pad_token_id": g.pad_token_id, "projection_size": g.projection_size, "dtype": dtype}
     elif encoder == "mllama_tiles":
         g = geometry or TILE_VIT
         cfg = {"architectures": ["MllamaVisionModel"], "model_type": "mllama_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,

@@ -3,6 +3,10 @@
 //     CLIPAttention under CLIPTextTransformer's causal mask: softmax(Q K^T dh^-0.5 + mask) V with mask[i, j] = -inf for
 //     j > i.  Three waves (77 -> 96 rows).
 //   * <50, false>: the ViT/32 @224 image towers (H = 6, 12 or 16 heads): softmax(Q K^T dh^-0.5) V.  Two waves (50 -> 64).
+//   * <64, false>: the SigLIP text tower (H = 8, 12 or 16 heads), transformers models/siglip/modeling_siglip.py,
+//     SiglipAttention with no mask of any kind (pad tokens are attended).  Two waves, 16 KiB of LDS.  T is a multiple of 32:
+//     there is no padded key and no clamped row -- every LDS row is a token's, kv_piece_src<63> and min(q, 63) clamp nothing,
+//     counts(e) folds to true, every lane stores -- and the last row read is row 64 n - 1 of qkv.
 // The softmax is in f32.  MFMA shapes, LDS images and the LDS-DMA idiom are those of attention.hip (attention_common.h);
 // what differs:
 //   * One workgroup of (T + 31) / 32 waves per (sequence, head) item, persistent over the items blockIdx.x, blockIdx.x +
@@ -140,13 +144,19 @@ __global__ __launch_bounds__(64 * ((T + 31) / 32)) void attn_short(const bf16_t*
     }
 }
 
-hipError_t launch_short(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block, bool causal) {
+enum ShortKind { SHORT_T77_CAUSAL, SHORT_T50, SHORT_T64 };
+
+hipError_t launch_short(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block, ShortKind kind) {
     if (n <= 0) return hipSuccess;
     const int64_t items = (int64_t)n * heads;
     if (items > 0x7fffffff) return hipErrorInvalidValue;
     const int grid = items < 1024 ? (int)items : 1024;  // persistent: up to four workgroups per CU walk the items
-    if (causal) hipLaunchKernelGGL((attn_short<TXT_T, true>), dim3(grid), dim3(192), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
-    else hipLaunchKernelGGL((attn_short<50, false>), dim3(grid), dim3(128), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
+    if (kind == SHORT_T77_CAUSAL)
+        hipLaunchKernelGGL((attn_short<TXT_T, true>), dim3(grid), dim3(192), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
+    else if (kind == SHORT_T50)
+        hipLaunchKernelGGL((attn_short<50, false>), dim3(grid), dim3(128), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
+    else
+        hipLaunchKernelGGL((attn_short<TXT_T64, false>), dim3(grid), dim3(128), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
     return hipGetLastError();
 }
 
@@ -154,11 +164,17 @@ hipError_t launch_short(const void* qkv, void* out, int n, int heads, hipStream_
 
 hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads, hipStream_t s) {
     if (heads != 8 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 512, 768, 1024
-    return launch_short(qkv, out, n, heads, s, -1, true);
+    return launch_short(qkv, out, n, heads, s, -1, SHORT_T77_CAUSAL);
 }
 
 hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block) {
     if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 384, 768, 1024
     if (only_block < -1 || only_block > 1) return hipErrorInvalidValue;
-    return launch_short(qkv, out, n, heads, s, only_block, false);
+    return launch_short(qkv, out, n, heads, s, only_block, SHORT_T50);
+}
+
+hipError_t launch_attention_t64(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block) {
+    if (heads != 8 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 512, 768, 1024
+    if (only_block < -1 || only_block > 1) return hipErrorInvalidValue;
+    return launch_short(qkv, out, n, heads, s, only_block, SHORT_T64);
 }

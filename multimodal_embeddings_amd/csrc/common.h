@@ -50,6 +50,8 @@ constexpr bool vit_width_built(int d) { return d == 384 || d == 768 || d == 1024
 // causal attention kernel run the widths 512, 768 and 1024 (8, 12, 16 heads).  512 is no width of the image path.
 constexpr int TXT_T = 77;
 constexpr int TXT_MAX_VOCAB = 65536;
+constexpr int TXT_T64 = 64;                  // SigLIP text towers: 64 positions
+constexpr int TXT_MAX_VOCAB_SIGLIP = 262144;  // SigLIP 32000, SigLIP 2 256000
 constexpr bool text_width_built(int d) { return d == 512 || d == 768 || d == 1024; }
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }

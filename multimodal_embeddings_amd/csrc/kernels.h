@@ -274,12 +274,22 @@ hipError_t launch_attention_tiles(const void* qkv, void* out, const int32_t* nti
 // hipErrorInvalidValue)
 // x[b*77 + t, :] = bf16(f32(tok[ids[b*77 + t], :]) + pos[t, :]); tok bf16 [vocab, d], pos f32 [77, d], ids DEVICE int32 [n*77], each
 // 0 <= id < vocab (the caller validates them on the host)
-hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s);
+hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s, int tokens = 77);
 // causal attention, T = 77, dh = 64, heads = 8, 12 or 16: qkv [n*77, 3*64*heads] (Q pre-scaled by dh^-0.5 log2 e) -> out [n*77, 64*heads]
 hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads, hipStream_t s);
 // LayerNorm of row b*77 + eos_pos[b] (DEVICE int32 [n], each 0..76) -> y bf16 [n, d] and / or y_f32 [n, d]
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
-                                   float* y_f32, hipStream_t s);
+                                   float* y_f32, hipStream_t s, int tokens = 77);
+// ---- SigLIP text tower (text_tower.hip, attention_short.hip): 64 tokens, no mask, last-token pooling and a head with bias.
+// launch_text_token_rows / launch_text_eos_pool_ln take tokens = 64 (77 or 64, else hipErrorInvalidValue): x rows b*64 + t,
+// pos f32 [64, d], eos_pos 0..63 (the tower pools position 63 of every sequence)
+// attention without a mask, T = 64, dh = 64, heads = 8, 12 or 16: qkv [n*64, 3*64*heads] (Q pre-scaled) -> out [n*64, 64*heads],
+// exact row maximum; only_block = 0 or 1: that query block of 32 only
+hipError_t launch_attention_t64(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
+// acc f32 [rows, p] (the head's GEMM under EPI_F32) + bias [p] -> y / max(||y||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024
+hipError_t launch_bias_l2_rows(const float* acc, const float* bias, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
+// out[i] = 1 / (1 + exp(-(cos[i] * scale + bias))), i < count; out may be cos
+hipError_t launch_siglip_scores(const float* cos, float* out, int64_t count, float scale, float bias, hipStream_t s);
 
 // ---- ViT/32 @224 image towers (patch32.hip, attention_short.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64
 // K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-32 matrix [n * 49, 3072] in conv order (c, ky, kx): a pure copy

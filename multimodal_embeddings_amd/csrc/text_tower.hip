@@ -1,20 +1,24 @@
 // Row kernels of the CLIP text tower (transformers models/clip/modeling_clip.py, CLIPTextEmbeddings and the pooling of
 // CLIPTextTransformer.forward): the token rows that open the pass and the LayerNorm of the EOS rows that closes it.
 // One 64-lane wave owns one row of D values, D a multiple of 256 up to 1024 (512, 768, 1024: 8, 12, 16 heads of 64): a lane
-// holds columns 4 lane + 256 k .. + 3.  The sequence length is fixed at 77 (TXT_T, kernels.h) as 197 is for the image tower.
+// holds columns 4 lane + 256 k .. + 3.  The sequence length T is a template parameter: 77 (TXT_T, CLIP) or 64 (TXT_T64, the
+// SigLIP text tower: transformers models/siglip/modeling_siglip.py, SiglipTextEmbeddings and SiglipTextTransformer's
+// last_hidden_state[:, -1, :] -- eos_pool_ln_rows with every position 63 -- whose head's bias and the L2 step are bias_l2_rows).
+// siglip_scores is SiglipModel.forward's sigmoid(exp(logit_scale) cos + logit_bias) on a cosine block.
 #include "common.h"
 #include "kernels.h"
 
 namespace {
 
-// x[b * 77 + t] = bf16(f32(tok[ids[b, t]]) + pos[t]): one f32 add, one rounding to nearest even.  64-bit offsets: a
-// 65536 x 1024 table holds 2^26 values, n * 77 * D passes 2^31 at n = 27 236 (D = 1024).
+// x[b * T + t] = bf16(f32(tok[ids[b, t]]) + pos[t]): one f32 add, one rounding to nearest even.  64-bit offsets: a
+// 65536 x 1024 table holds 2^26 values (262144 x 1024: 2^28), n * 77 * D passes 2^31 at n = 27 236 (D = 1024).
+template <int T>
 __global__ __launch_bounds__(256) void token_rows(const bf16_t* __restrict__ tok, const float* __restrict__ pos, const int32_t* __restrict__ ids,
                                                   bf16_t* __restrict__ x, int64_t rows, int D) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const int t = (int)(row % TXT_T);
+    const int t = (int)(row % T);
     const bf16_t* tr = tok + (int64_t)ids[row] * D;
     const float* pr = pos + (int64_t)t * D;
     bf16_t* xr = x + row * D;
@@ -28,15 +32,16 @@ __global__ __launch_bounds__(256) void token_rows(const bf16_t* __restrict__ tok
     }
 }
 
-// final_layer_norm of row b * 77 + eos_pos[b], the two-pass f32 form of pool_ln_rows (rowops.hip), rounded to bf16
+// final_layer_norm of row b * T + eos_pos[b], the two-pass f32 form of pool_ln_rows (rowops.hip), rounded to bf16
 // [n, D] for the projection GEMM and / or left in f32 [n, D] (a tower without text_projection: the L2 step reads that).
+template <int T>
 __global__ __launch_bounds__(256) void eos_pool_ln_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         const int32_t* __restrict__ eos_pos, int n, int D, float eps, bf16_t* __restrict__ y,
                                                         float* __restrict__ yf) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n) return;
-    const bf16_t* xr = x + ((int64_t)b * TXT_T + eos_pos[b]) * D;
+    const bf16_t* xr = x + ((int64_t)b * T + eos_pos[b]) * D;
     const int nk = D >> 8;  // 2, 3 or 4 groups of 256 columns (wave-uniform)
     float v[4][4];
     float s = 0.f;
@@ -84,20 +89,91 @@ __global__ __launch_bounds__(256) void eos_pool_ln_rows(const bf16_t* __restrict
         }
 }
 
+// The head of a SigLIP text tower behind its EPI_F32 GEMM, and the L2 step: y = acc + bias formed once in f32, then
+// y / max(||y||, 1e-12) in l2_rows' arithmetic and reduction order (rowops.hip), to f32 and / or bf16.  One wave per row,
+// p % 64 == 0, p <= 1024: a lane holds columns 4 lane + 256 k .. + 3.
+__global__ __launch_bounds__(256) void bias_l2_rows(const float* __restrict__ acc, const float* __restrict__ bias, int64_t rows, int p,
+                                                    float* __restrict__ y_f32, bf16_t* __restrict__ y_bf16) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = acc + row * p;
+    f32x4 v[4];
+    float n2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane * 4 + k * 256;
+        v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < p) {
+            const f32x4 a = *(const f32x4*)(xr + c);
+            const f32x4 bv = *(const f32x4*)(bias + c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[k][j] = a[j] + bv[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) n2 += v[k][j] * v[k][j];
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = lane * 4 + k * 256;
+        if (c >= p) continue;
+        f32x4 o;
+        bf16x4 ob;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = v[k][j] * inv;
+            ob[j] = (bf16_t)o[j];
+        }
+        if (y_f32) *(f32x4*)(y_f32 + row * p + c) = o;
+        if (y_bf16) *(bf16x4*)(y_bf16 + row * p + c) = ob;
+    }
+}
+
+// p = 1 / (1 + exp(-(c * scale + bias))), scale = exp(logit_scale) formed once on the host: one multiply, one add, one exp,
+// one add and one division in f32, in place when out == cos.  Finite for every finite c: z -> -inf gives exp = +inf and
+// p = 0, z -> +inf gives exp = 0 and p = 1; there is no inf - inf and no 0 * inf on the way.
+__global__ __launch_bounds__(256) void siglip_scores(const float* __restrict__ cos, float* __restrict__ out, int64_t count, float scale, float bias) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const float z = cos[i] * scale + bias;
+        out[i] = 1.0f / (1.0f + expf(-z));
+    }
+}
+
 }  // namespace
 
-hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s) {
-    if (!text_width_built(d)) return hipErrorInvalidValue;
+hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s, int tokens) {
+    if (!text_width_built(d) || (tokens != TXT_T && tokens != TXT_T64)) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
-    const int64_t rows = (int64_t)n * TXT_T;
-    hipLaunchKernelGGL(token_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const bf16_t*)tok, pos, ids, (bf16_t*)x, rows, d);
+    const int64_t rows = (int64_t)n * tokens;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (tokens == TXT_T) hipLaunchKernelGGL(token_rows<TXT_T>, grid, dim3(256), 0, s, (const bf16_t*)tok, pos, ids, (bf16_t*)x, rows, d);
+    else hipLaunchKernelGGL(token_rows<TXT_T64>, grid, dim3(256), 0, s, (const bf16_t*)tok, pos, ids, (bf16_t*)x, rows, d);
     return hipGetLastError();
 }
 
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
-                                   float* y_f32, hipStream_t s) {
-    if (!text_width_built(d)) return hipErrorInvalidValue;
+                                   float* y_f32, hipStream_t s, int tokens) {
+    if (!text_width_built(d) || (tokens != TXT_T && tokens != TXT_T64)) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(eos_pool_ln_rows, dim3((n + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, eos_pos, n, d, eps, (bf16_t*)y, y_f32);
+    if (tokens == TXT_T)
+        hipLaunchKernelGGL(eos_pool_ln_rows<TXT_T>, dim3((n + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, eos_pos, n, d, eps, (bf16_t*)y, y_f32);
+    else
+        hipLaunchKernelGGL(eos_pool_ln_rows<TXT_T64>, dim3((n + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, eos_pos, n, d, eps, (bf16_t*)y, y_f32);
+    return hipGetLastError();
+}
+
+hipError_t launch_bias_l2_rows(const float* acc, const float* bias, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
+    if (p < 64 || (p % 64) != 0 || p > 1024) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(bias_l2_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, acc, bias, rows, p, y_f32, (bf16_t*)y_bf16);
+    return hipGetLastError();
+}
+
+hipError_t launch_siglip_scores(const float* cos, float* out, int64_t count, float scale, float bias, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    const int64_t blocks = (count + 255) / 256;
+    hipLaunchKernelGGL(siglip_scores, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, cos, out, count, scale, bias);
     return hipGetLastError();
 }

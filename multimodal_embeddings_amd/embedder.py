@@ -178,10 +178,13 @@ class RegionEmbedder:
         fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
         encoders only; a checkpoint's preprocessor_config.json must then describe exactly that rule).  It is set on every
         engine of this object; None leaves a caller's `engine=` as it is.
-        `text_tower`: the CLIP text tower behind `get_text_embeddings`, in the FIRST engine only.  None: nothing is loaded
+        `text_tower`: the text tower behind `get_text_embeddings` (CLIP's; SigLIP's under encoder="siglip_vit"), in the FIRST engine only.  None: nothing is loaded
         now; the first `get_text_embeddings` loads it if `model_name` is a checkpoint directory that holds one.  True: load
         now (from that directory, or seeded CLIP_TEXT_B-shaped weights projecting to this object's `embed_dim` beside a seeded
         image side).  A directory path or a `weights.clip_text_tensor_specs` dict: load that.  False: never.
+        Under encoder="siglip_vit" the tower is SigLIP's (64 tokens, `weights.siglip_text_tensor_specs`, a whole SiglipModel or
+        a SiglipTextModel directory): True beside seeded or caller's image weights seeds a tower of the image tower's width
+        (SIGLIP_TEXT_B at 768); its projection must equal `embed_dim`.  None beside seeded or vision-only weights loads nothing.
         `tokenizer`: a callable str -> list[int] or a transformers tokenizer; by default transformers' CLIPTokenizer is read
         from the tower's directory on first use (local files only).  Token ids need no tokenizer."""
         import torch
@@ -750,7 +753,9 @@ class RegionEmbedder:
 
         src = getattr(self, "_text_source", False)
         eng = self.engines[0]
-        if src is False or getattr(self, "encoder", None) == "siglip":  # (a CLIP text tower embeds into another space than a SigLIP image tower)
+        if getattr(self, "encoder", None) == "siglip":  # (a CLIP text tower embeds into another space than a SigLIP image tower)
+            return self._load_siglip_text_tower(src, eng)
+        if src is False:
             raise NotImplementedError(self._NO_TOWER)
         if isinstance(src, dict):
             eng.load_clip_text(src)
@@ -777,9 +782,80 @@ class RegionEmbedder:
             raise NotImplementedError(self._NO_TOWER)
         self._text_loaded = True
 
+    _NO_SIGLIP_TOWER = ("text embeddings under encoder='siglip_vit' need a SigLIP text tower: construct RegionEmbedder(..., text_tower=True | a "
+                        "checkpoint directory | a weight dict), or name a checkpoint directory that holds text_model.* (a whole SiglipModel)")
+
+    def _check_siglip_text_width(self, projection: int, where: str):
+        if int(projection) != int(self.embed_dim):
+            raise MmeError(f"text_tower: {where}: projection_size = {projection}; supported: {self.embed_dim}, the embed_dim of the loaded "
+                           "SigLIP image tower (the two towers must embed into one space)")
+
+    def _load_siglip_text_tower(self, src, eng):
+        """The SigLIP branch of `_load_text_tower`: the same sources, the 64-token tower, the width check against the image side."""
+        from .checkpoint import read_checkpoint
+
+        if src is False:
+            raise NotImplementedError(self._NO_SIGLIP_TOWER)
+        if isinstance(src, dict):
+            from .weights import infer_siglip_text_geometry
+
+            self._check_siglip_text_width(infer_siglip_text_geometry(src).projection_size, "the weight dict")
+            eng.load_siglip_text(src)
+        elif isinstance(src, (str, os.PathLike)):
+            ck = read_checkpoint(src, "siglip_text")
+            self._check_siglip_text_width(ck.geometry.projection_size, os.fspath(src))
+            eng.load_siglip_text_checkpoint(ck)
+            self._text_dir = os.fspath(src)
+        elif self.checkpoint is not None:  # None or True beside a checkpoint directory: its own text half
+            try:
+                ck = read_checkpoint(self.model_name, "siglip_text")
+            except MmeError as e:
+                if src is None:  # a vision-only directory
+                    raise NotImplementedError(f"{self._NO_SIGLIP_TOWER} ({e})") from e
+                raise
+            self._check_siglip_text_width(ck.geometry.projection_size, os.fspath(self.model_name))
+            eng.load_siglip_text_checkpoint(ck)
+            self._text_dir = os.fspath(self.model_name)
+        elif src is True:  # seeded, at the width of the image side
+            import dataclasses
+
+            from .weights import SIGLIP_TEXT_B, make_siglip_text_weights
+
+            D = int(self.embed_dim)
+            geom = SIGLIP_TEXT_B if D == SIGLIP_TEXT_B.hidden_size else dataclasses.replace(
+                SIGLIP_TEXT_B, hidden_size=D, num_heads=D // 64, intermediate_size=4 * D, projection_size=D)
+            eng.load_siglip_text(make_siglip_text_weights(self._seed + 2, geom), geom)
+        else:
+            raise NotImplementedError(self._NO_SIGLIP_TOWER)
+        self._text_loaded = True
+
+    def _text_layout(self):
+        """(tokens per sequence, id that right-pads a short sequence) of the first engine's text tower: 77 and the eos_token_id
+        of a CLIP tower, 64 and the pad_token_id of a SigLIP tower."""
+        eng = self.engines[0]
+        geometry = getattr(eng, "text_geometry", None)
+        if geometry is None:  # an engine that knows CLIP towers only
+            return 77, eng.text_info()["eos_token_id"]
+        g = geometry()
+        return g["tokens"] or 77, g["pad_token_id"]
+
     def _tokenize(self, text: str) -> list:
-        """str -> token ids through `tokenizer=` or the lazily loaded CLIPTokenizer of the tower's directory."""
+        """str -> token ids through `tokenizer=` or the lazily loaded tokenizer of the tower's directory (CLIPTokenizer; under a
+        SigLIP tower whatever AutoTokenizer reads from the local files), padded to the tower's token count."""
         tok = getattr(self, "_tokenizer", None)
+        T = self._text_layout()[0]
+        if tok is None and T != 77:
+            d = getattr(self, "_text_dir", None)
+            hint = "pass tokenizer= (a callable str -> list[int] or a transformers tokenizer); token ids (a sequence of ints) are accepted as they are"
+            if d is None:
+                raise MmeError(f"get_text_embeddings: no tokenizer for a str: {hint}")
+            try:
+                from transformers import AutoTokenizer
+
+                tok = AutoTokenizer.from_pretrained(d, local_files_only=True)  # nothing is ever fetched
+            except Exception as e:  # noqa: BLE001 - missing files, or a tokenizer library this machine does not have
+                raise MmeError(f"get_text_embeddings: the libraries here read no SigLIP tokenizer from {d!r}: {e}; {hint}") from e
+            self._tokenizer = tok
         if tok is None:
             d = getattr(self, "_text_dir", None)
             hint = "pass tokenizer= (a callable str -> list[int] or a transformers tokenizer); token ids (a sequence of ints) are accepted as they are"
@@ -798,20 +874,22 @@ class RegionEmbedder:
                 raise MmeError(f"get_text_embeddings: {d!r} holds no usable CLIP tokenizer files (vocab.json, merges.txt): {e}; {hint}") from e
             self._tokenizer = tok
         if hasattr(tok, "pad_token_id") or hasattr(tok, "encode"):  # a transformers tokenizer
-            ids = tok(text, padding="max_length", max_length=77, truncation=True)["input_ids"]
+            ids = tok(text, padding="max_length", max_length=T, truncation=True)["input_ids"]
         else:
             ids = tok(text)
         return [int(v) for v in ids]
 
     def _text_ids(self, item) -> np.ndarray:
-        """One query -> int32[77]: a str through the tokenizer, ids right-padded with the tower's eos_token_id."""
+        """One query -> int32[77] (int32[64] under a SigLIP tower): a str through the tokenizer, ids right-padded with the
+        tower's eos_token_id (SigLIP: its pad_token_id)."""
         ids = self._tokenize(item) if isinstance(item, str) else item
         a = np.asarray(ids)
         if a.ndim != 1 or a.dtype.kind not in "iu":
             raise MmeError(f"get_text_embeddings: token ids must be a 1-D integer sequence, got {a.dtype} {tuple(a.shape)}")
-        if a.shape[0] > 77:
-            raise MmeError(f"get_text_embeddings: {a.shape[0]} token ids; supported: at most 77")
-        row = np.full(77, self.engines[0].text_info()["eos_token_id"], dtype=np.int64)
+        T, pad = self._text_layout()
+        if a.shape[0] > T:
+            raise MmeError(f"get_text_embeddings: {a.shape[0]} token ids; supported: at most {T}")
+        row = np.full(T, pad, dtype=np.int64)
         row[: a.shape[0]] = a
         return row
 
@@ -838,6 +916,37 @@ class RegionEmbedder:
         rows = e32.cpu().numpy()
         out = [[float(v) for v in r] for r in rows]
         return out[0] if single else out
+
+    def siglip_probabilities(self, texts_or_vectors, image_vectors) -> np.ndarray:
+        """SigLIP's zero-shot scores of m texts against N image vectors: sigmoid(exp(logit_scale) cos + logit_bias), f32 [m, N]
+        (SiglipModel.forward's logits_per_text under a sigmoid).  `texts_or_vectors`: what `get_text_embeddings` takes (a list
+        of str or of id sequences, or one of either), or a float array [m, embed_dim] of unit vectors; `image_vectors`: a float
+        array [N, embed_dim] of unit vectors (`get_image_embeddings`).  The cosine block is the engine's bf16 GEMM, the scores
+        its kernel.  MmeError unless the loaded text tower is SigLIP's and came with logit_scale and logit_bias."""
+        engines = getattr(self, "engines", None)
+        if not engines or getattr(self, "_text_source", False) is False:
+            raise NotImplementedError(self._NO_SIGLIP_TOWER)
+        if not getattr(self, "_text_loaded", False):
+            self._load_text_tower()
+        eng, t = engines[0], self.torch
+        a = texts_or_vectors if isinstance(texts_or_vectors, np.ndarray) else None
+        if a is not None and a.dtype.kind == "f":
+            tv = np.atleast_2d(a)
+        else:
+            rows = self.get_text_embeddings(texts_or_vectors)
+            tv = np.atleast_2d(np.asarray(rows, dtype=np.float32))
+        iv = np.atleast_2d(np.asarray(image_vectors, dtype=np.float32))
+        if tv.ndim != 2 or iv.ndim != 2 or tv.shape[1] != iv.shape[1]:
+            raise MmeError(f"siglip_probabilities: text vectors {tuple(tv.shape)} against image vectors {tuple(iv.shape)}")
+        if tv.shape[1] % 64:
+            raise MmeError(f"siglip_probabilities: vectors of {tv.shape[1]} values; supported: a multiple of 64")
+        dev = t.device("cuda", eng.device)
+        with t.cuda.device(dev):
+            tb = t.from_numpy(np.ascontiguousarray(tv, dtype=np.float32)).to(dev).to(t.bfloat16).contiguous()
+            ib = t.from_numpy(np.ascontiguousarray(iv)).to(dev).to(t.bfloat16).contiguous()
+            cos = eng.cosine(tb, ib)
+            p = eng.siglip_scores(cos, out=cos)
+            return p.cpu().numpy()
 
     @property
     def text_embed_dim(self) -> int:

@@ -482,6 +482,154 @@ def clip_text_flops_per_sequence(geom: CLIPTextGeometry = CLIP_TEXT_B) -> int:
     return L * (2 * T * D * (4 * D + 2 * F) + 4 * (T * (T + 1) // 2) * D) + 2 * D * (geom.projection_dim or 0)
 
 
+# ---- SigLIP text towers -----------------------------------------------------------------------------------------------
+SIGLIP_TEXT_TOKENS = 64  # SiglipTextConfig.max_position_embeddings (csrc/common.h TXT_T64)
+SIGLIP_TEXT_ACT = "gelu_pytorch_tanh"
+
+
+@dataclass(frozen=True)
+class SiglipTextGeometry:
+    """A SigLIP text tower (transformers SiglipTextConfig) at what the engine runs: 64 positions, heads of 64, no attention mask,
+    the row at position 63 pooled, a head with bias onto `projection_size`.  The defaults are siglip-base-patch16-224's text
+    tower.  `pad_token_id` is what short sequences are right-padded with (SigLIP's tokenizer: 1; the padding is attended)."""
+
+    hidden_size: int = 768
+    num_layers: int = 12
+    num_heads: int = 12
+    intermediate_size: int = 3072
+    vocab_size: int = 32000
+    max_position_embeddings: int = SIGLIP_TEXT_TOKENS
+    pad_token_id: int = 1
+    projection_size: int = 768
+    hidden_act: str = SIGLIP_TEXT_ACT
+    layer_norm_eps: float = 1e-6
+
+    @property
+    def embed_dim(self) -> int:
+        return self.projection_size
+
+
+SIGLIP_TEXT_B = SiglipTextGeometry()
+SUPPORTED_SIGLIP_TEXT = {"hidden_size": (512, 768, 1024), "max_position_embeddings": (SIGLIP_TEXT_TOKENS,),
+                         "intermediate_size": "a multiple of 64 up to 8192", "num_layers": "1..64", "vocab_size": "3..262144",
+                         "projection_size": "a multiple of 64 up to 1024", "hidden_act": (SIGLIP_TEXT_ACT,)}
+
+
+def siglip_text_geometry_problem(geom: SiglipTextGeometry):
+    """None when the engine runs `geom`, else (field, value found, supported values as text) of the first field outside the
+    supported set (csrc/capi_text.hip validate_siglip_text_weights).  so400m (hidden 1152, heads of 72) stops at hidden_size."""
+    for fld in ("hidden_size", "max_position_embeddings"):
+        if getattr(geom, fld) not in SUPPORTED_SIGLIP_TEXT[fld]:
+            return fld, getattr(geom, fld), ", ".join(str(v) for v in SUPPORTED_SIGLIP_TEXT[fld])
+    if geom.num_heads * 64 != geom.hidden_size:
+        return "num_heads", geom.num_heads, f"{geom.hidden_size // 64} at hidden_size {geom.hidden_size} (heads of 64)"
+    F = geom.intermediate_size
+    if F < 64 or F % 64 or F > 8192:
+        return "intermediate_size", F, SUPPORTED_SIGLIP_TEXT["intermediate_size"]
+    if not 1 <= geom.num_layers <= 64:
+        return "num_layers", geom.num_layers, SUPPORTED_SIGLIP_TEXT["num_layers"]
+    if not 3 <= geom.vocab_size <= 262144:
+        return "vocab_size", geom.vocab_size, SUPPORTED_SIGLIP_TEXT["vocab_size"]
+    if geom.hidden_act not in SUPPORTED_SIGLIP_TEXT["hidden_act"]:
+        return "hidden_act", geom.hidden_act, SIGLIP_TEXT_ACT
+    P = geom.projection_size
+    if isinstance(P, bool) or not isinstance(P, int) or P < 64 or P % 64 or P > 1024:
+        return "projection_size", P, SUPPORTED_SIGLIP_TEXT["projection_size"]
+    if isinstance(geom.pad_token_id, bool) or not isinstance(geom.pad_token_id, int) or not 0 <= geom.pad_token_id < geom.vocab_size:
+        return "pad_token_id", geom.pad_token_id, f"0..{geom.vocab_size - 1} (vocab_size - 1)"
+    return None
+
+
+def siglip_text_tensor_specs(geom: SiglipTextGeometry = SIGLIP_TEXT_B):
+    """(name, shape, kind) in a fixed order, the state-dict names of the text half of a Hugging Face `SiglipModel`
+    (transformers models/siglip/modeling_siglip.py; prefix "text_model."); kind in {matrix, bias, gamma}.  The two scalars
+    `logit_scale` / `logit_bias` of a whole model are not in the list: a weight dict may carry them beside these tensors."""
+    D, F = geom.hidden_size, geom.intermediate_size
+    t = "text_model."
+    specs = [
+        (t + "embeddings.token_embedding.weight", (geom.vocab_size, D), "matrix"),
+        (t + "embeddings.position_embedding.weight", (geom.max_position_embeddings, D), "matrix"),
+    ]
+    for i in range(geom.num_layers):
+        p = f"{t}encoder.layers.{i}."
+        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
+        for n in ("q", "k", "v", "out"):
+            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
+        specs += [
+            (p + "layer_norm2.weight", (D,), "gamma"),
+            (p + "layer_norm2.bias", (D,), "bias"),
+            (p + "mlp.fc1.weight", (F, D), "matrix"),
+            (p + "mlp.fc1.bias", (F,), "bias"),
+            (p + "mlp.fc2.weight", (D, F), "matrix"),
+            (p + "mlp.fc2.bias", (D,), "bias"),
+        ]
+    specs += [(t + "final_layer_norm.weight", (D,), "gamma"), (t + "final_layer_norm.bias", (D,), "bias"),
+              (t + "head.weight", (geom.projection_size, D), "matrix"), (t + "head.bias", (geom.projection_size,), "bias")]
+    return specs
+
+
+SIGLIP_LOGIT_KEYS = ("logit_scale", "logit_bias")
+
+
+def make_siglip_text_weights(seed: int = 5, geom: SiglipTextGeometry = SIGLIP_TEXT_B, std: float = 0.02, logits=(np.log(10.0), -10.0)) -> dict[str, np.ndarray]:
+    """Seeded synthetic weights of a SigLIP text tower, f32 arrays holding bf16-representable values: the generator and the
+    LayerNorm spread (1 + 0.25 z, 0.1 z) of `make_clip_weights` on `siglip_text_tensor_specs`.  `logits`: (logit_scale,
+    logit_bias) as f32 arrays of shape (1,) beside the tensors (SiglipModel initialises them to log 10 and -10); None: left out."""
+    out: dict[str, np.ndarray] = {}
+    for tid, (name, shape, kind) in enumerate(siglip_text_tensor_specs(geom)):
+        n = int(np.prod(shape))
+        z = irwin_hall_normal(seed, tid, n)
+        if kind == "gamma":
+            z = np.float32(1.0) + z * np.float32(0.25)
+        elif kind == "bias" and "layer_norm" in name:
+            z = z * np.float32(0.1)
+        else:
+            z = z * np.float32(std)
+        out[name] = round_to_bf16(z).reshape(shape)
+    if logits is not None:
+        out["logit_scale"] = round_to_bf16(np.array([logits[0]], dtype=np.float32))
+        out["logit_bias"] = round_to_bf16(np.array([logits[1]], dtype=np.float32))
+    return out
+
+
+def infer_siglip_text_geometry(w: dict, eps: float = 1e-6, pad_token_id: int = 1) -> SiglipTextGeometry:
+    """The geometry of a `siglip_text_tensor_specs` weight dict, read off its tensor shapes; heads of 64."""
+    V, D = (int(v) for v in np.shape(w["text_model.embeddings.token_embedding.weight"]))
+    T = int(np.shape(w["text_model.embeddings.position_embedding.weight"])[0])
+    layers = 0
+    while f"text_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError("the weight dict holds no 'text_model.encoder.layers.0.mlp.fc1.weight'")
+    F = int(np.shape(w["text_model.encoder.layers.0.mlp.fc1.weight"])[0])
+    P = int(np.shape(w["text_model.head.weight"])[0])
+    return SiglipTextGeometry(hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F, vocab_size=V, max_position_embeddings=T,
+                              pad_token_id=int(pad_token_id), projection_size=P, layer_norm_eps=float(eps))
+
+
+def siglip_text_flops_per_sequence(geom: SiglipTextGeometry = SIGLIP_TEXT_B) -> int:
+    """`clip_text_flops_per_sequence` without a mask: all T * T (query, key) pairs, 64 rows, then the head on the pooled row."""
+    D, F, L, T = geom.hidden_size, geom.intermediate_size, geom.num_layers, geom.max_position_embeddings
+    return L * (2 * T * D * (4 * D + 2 * F) + 4 * T * T * D) + 2 * D * geom.projection_size
+
+
+def siglip_token_ids(n: int, vocab: int, pad: int = 1, seed: int = 0, lengths=None) -> np.ndarray:
+    """int32 [n, 64] right-padded sequences as SigLIP's tokenizer writes them under padding="max_length": sequence i holds
+    lengths[i] hashed ids, none of them `pad`, then `pad` in every position behind.  `lengths` defaults to hashed values in 1..64."""
+    T = SIGLIP_TEXT_TOKENS
+    if lengths is None:
+        lengths = 1 + (counter_u64(seed, 0x7200, n) % np.uint64(T)).astype(np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.shape[0] != n or (n and (lengths.min() < 0 or lengths.max() > T)):
+        raise ValueError(f"lengths must hold {n} values in 0..{T}")
+    out = np.full((n, T), pad, dtype=np.int32)
+    for i in range(n):
+        body = (counter_u64(seed, 0x7201, T, i) % np.uint64(vocab - 1)).astype(np.int64)
+        body += body >= pad  # 0..vocab-1 without pad
+        out[i, : lengths[i]] = body[: lengths[i]]
+    return out
+
+
 def synthetic_token_ids(n: int, vocab: int, eos: int, seed: int = 0, lengths=None) -> np.ndarray:
     """int32 [n, 77] BOS-free, right-padded sequences: sequence i holds lengths[i] - 1 hashed ids, none of them `eos`, then
     `eos` at position lengths[i] - 1 and in every position behind it (the padding CLIP's tokenizer writes).  `lengths`
