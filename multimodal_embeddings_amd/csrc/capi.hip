@@ -162,7 +162,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     int r;
     if (t50) {
         // patch 32: the patch-embed GEMM leaves f32 [n * 49, D] in the qkv buffer (dead until layer 0; 196 D n bytes of its
-        // 300 D n), embed_rows_t50 adds bias and position rows, rounds once and writes the [CLS] rows in the same launch
+        // 300 D n), embed_rows adds bias and position rows, rounds once and writes the [CLS] rows in the same launch
         g.A = patches;
         g.W = c->patch_w;
         g.M = n * c->geom.np();
@@ -172,7 +172,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         g.ldf = D;
         if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_embed_rows_t50((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
+        HIP_TRY(c, launch_embed_rows((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, T, D, s));
     } else if (sig) {
         // no class token: patch row m IS token row m, but EPI_PATCH (and its interior-tile form) maps rows past the [CLS]
         // rows at compile time.  As at patch 32 the GEMM leaves f32 [n * 196, D] in the dead qkv buffer (784 D n of its
@@ -186,7 +186,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         g.ldf = D;
         if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_embed_rows_t196((const float*)c->qkv.p, c->patch_b, c->pos, c->x.p, n, D, s));
+        HIP_TRY(c, launch_embed_rows((const float*)c->qkv.p, c->patch_b, c->pos, nullptr, c->x.p, n, T, D, s));
     } else {
         g.A = patches;
         g.W = c->patch_w;
@@ -350,8 +350,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         if ((r = ensure(c, c->projf, (size_t)c->chunk * E * sizeof(float)))) return r;
         {
             Timed t(c, s, KC_POOL);
-            if (t50) HIP_TRY(c, launch_pool_ln_t50(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
-            else HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, c->pooled.p, s));
+            HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, T, pool_token, D, c->ln_eps, c->pooled.p, s));
         }
         g = GemmArgs{};
         g.A = c->pooled.p; g.W = c->proj_w; g.M = n; g.N = E; g.K = D;
@@ -363,8 +362,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     }
     {
         Timed t(c, s, KC_POOL);
-        if (t50) HIP_TRY(c, launch_pool_t50(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
-        else HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
+        HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
     }
     return MME_OK;
 }
@@ -1457,7 +1455,7 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
         case 2: HIP_TRY(c, launch_ln_stats_canonical(a->x, a->row0, a->row1, a->d, a->eps, a->stats, s, a->stride)); break;
         case 3: HIP_TRY(c, launch_ln_finish(a->part, a->part_rows, a->rows, a->d, a->eps, a->stats, s)); break;
         case 4: HIP_TRY(c, launch_cls_rows(a->x, a->cls, a->pos, a->B, a->d, s)); break;
-        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, VIT_T, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
@@ -1522,7 +1520,7 @@ int mme_clip_apply(mme_ctx* c, int op, const mme_clip_apply_args* a, void* strea
     HIP_TRY(c, hipSetDevice(c->device));
     switch (op) {
         case 2: HIP_TRY(c, launch_pre_ln(a->x, a->gamma, a->beta, a->rows, a->d, a->eps, a->stats, s)); break;
-        case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->B, a->tok, a->d, a->eps, a->y, s)); break;
+        case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->B, VIT_T, a->tok, a->d, a->eps, a->y, s)); break;
         default: HIP_TRY(c, launch_l2_rows(a->xf, a->rows, a->p, a->y_f32, a->y_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -1561,10 +1559,10 @@ int mme_vit32_apply(mme_ctx* c, int op, const mme_vit32_apply_args* a, void* str
     hipStream_t s = (hipStream_t)stream;
     switch (op) {
         case 0: HIP_TRY(c, launch_retile_p32(a->src, a->dst, a->n, s)); break;
-        case 1: HIP_TRY(c, launch_embed_rows_t50(a->acc, a->bias, a->pos, a->cls, a->x, a->n, a->d, s)); break;
+        case 1: HIP_TRY(c, launch_embed_rows(a->acc, a->bias, a->pos, a->cls, a->x, a->n, 50, a->d, s)); break;
         case 2: HIP_TRY(c, launch_attention_t50(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
-        case 3: HIP_TRY(c, launch_pool_ln_t50(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->y, s)); break;
-        default: HIP_TRY(c, launch_pool_t50(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+        case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->n, 50, a->tok, a->d, a->eps, a->y, s)); break;
+        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->n, 50, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
@@ -1596,7 +1594,7 @@ int mme_siglip_apply(mme_ctx* c, int op, const mme_siglip_apply_args* a, void* s
     if (bad) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d needs %s", op, bad);
     HIP_TRY(c, hipSetDevice(c->device));
     switch (op) {
-        case 2: HIP_TRY(c, launch_embed_rows_t196(a->acc, a->bias, a->pos, a->x, a->n, a->d, s)); break;
+        case 2: HIP_TRY(c, launch_embed_rows(a->acc, a->bias, a->pos, nullptr, a->x, a->n, 196, a->d, s)); break;
         case 3: HIP_TRY(c, launch_map_pool(a->kv, a->q, a->out, a->n, a->heads, s)); break;
         default: HIP_TRY(c, launch_l2_rows_bf16(a->x, a->n, a->d, a->emb_f32, a->emb_bf16, s)); break;
     }

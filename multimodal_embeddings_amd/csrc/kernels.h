@@ -70,10 +70,14 @@ hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta
 // summation order: bit-identical to launch_ln_stats_canonical on x afterwards (CLIP's pre_layrnorm, the statistics source
 // of the pass's first folded LayerNorm)
 hipError_t launch_pre_ln(void* x, const float* gamma, const float* beta, int64_t rows, int d, float eps, float* stats, hipStream_t s);
-// LayerNorm of row b*197+tok of d values -> bf16 [B, d] (launch_pool without its L2 step: CLIP's post_layernorm)
-hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s);
-// f32 [rows, p] -> x / max(||x||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024
+// LayerNorm of row b*tokens+tok of d values -> bf16 [B, d] (launch_pool without its L2 step: CLIP's post_layernorm);
+// tokens = 197 or 50, 0 <= tok < tokens, else hipErrorInvalidValue
+hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps, void* y, hipStream_t s);
+// x / max(||x||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024.  x: f32 [rows, p]; bf16 [rows, p], widened;
+// or acc f32 [rows, p] + bias [p] (the rows of a GEMM under EPI_F32), the sum formed once in f32
 hipError_t launch_l2_rows(const float* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
+hipError_t launch_l2_rows_bf16(const void* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
+hipError_t launch_bias_l2_rows(const float* acc, const float* bias, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
 // per-row LayerNorm statistics of bf16 rows of d: stats[row] = (mean, rstd)
 hipError_t launch_ln_stats(const void* x, int64_t rows, int d, float eps, float* stats, hipStream_t s);
 // the same statistics in the CANONICAL summation order shared with the EPI_BIAS_RES_STATS epilogue, for rows
@@ -86,9 +90,13 @@ hipError_t launch_ln_finish(const float* part, int64_t part_rows, int64_t rows, 
 bool gemm_runs_256(const GemmArgs& g, int variant);
 // x[b*197 + 0, :] = bf16(cls + pos[0]), rows of d
 hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, int d, hipStream_t s);
-// final LayerNorm on row b*197+tok of d values, L2 normalise, write f32 and/or bf16 [B, d]
-hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps,
+// final LayerNorm on row b*tokens+tok of d values, L2 normalise, write f32 and/or bf16 [B, d]; tokens and tok as launch_pool_ln
+hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps,
                        float* emb_f32, void* emb_bf16, hipStream_t s);
+// behind a patch-embed GEMM under EPI_F32 (acc f32 [n * patches, d]), one rounding per value: with a class token (cls
+// non-null, tokens = 50, patches = 49) x[b*tokens + 1 + p] = bf16((acc + bias) + pos[1 + p]) and x[b*tokens] = bf16(cls + pos[0]);
+// without one (cls null, tokens = patches = 196) x[b*tokens + p] = bf16((acc + bias) + pos[p]).  Any other pair is hipErrorInvalidValue
+hipError_t launch_embed_rows(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int tokens, int d, hipStream_t s);
 // f32 [rows,d] -> L2-normalised bf16 [rows,d]
 hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, hipStream_t s);
 // fused multi-head attention, T=197, dh=64, `heads` = 6, 12 or 16 (one instantiation each; anything else is
@@ -277,42 +285,31 @@ hipError_t launch_attention_tiles(const void* qkv, void* out, const int32_t* nti
 hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s, int tokens = 77);
 // causal attention, T = 77, dh = 64, heads = 8, 12 or 16: qkv [n*77, 3*64*heads] (Q pre-scaled by dh^-0.5 log2 e) -> out [n*77, 64*heads]
 hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads, hipStream_t s);
-// LayerNorm of row b*77 + eos_pos[b] (DEVICE int32 [n], each 0..76) -> y bf16 [n, d] and / or y_f32 [n, d]
+// LayerNorm (launch_pool_ln's) of row b*tokens + eos_pos[b] (DEVICE int32 [n], each 0..tokens-1) -> y bf16 [n, d] and / or y_f32 [n, d]
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
                                    float* y_f32, hipStream_t s, int tokens = 77);
-// ---- SigLIP text tower (text_tower.hip, attention_short.hip): 64 tokens, no mask, last-token pooling and a head with bias.
-// launch_text_token_rows / launch_text_eos_pool_ln take tokens = 64 (77 or 64, else hipErrorInvalidValue): x rows b*64 + t,
-// pos f32 [64, d], eos_pos 0..63 (the tower pools position 63 of every sequence)
+// ---- SigLIP text tower (text_tower.hip, attention_short.hip): 64 tokens, no mask, last-token pooling and a head with bias
+// (launch_bias_l2_rows).  launch_text_token_rows / launch_text_eos_pool_ln take tokens = 64 (77 or 64, else
+// hipErrorInvalidValue): pos f32 [64, d]; the tower pools position 63 of every sequence
 // attention without a mask, T = 64, dh = 64, heads = 8, 12 or 16: qkv [n*64, 3*64*heads] (Q pre-scaled) -> out [n*64, 64*heads],
 // exact row maximum; only_block = 0 or 1: that query block of 32 only
 hipError_t launch_attention_t64(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
-// acc f32 [rows, p] (the head's GEMM under EPI_F32) + bias [p] -> y / max(||y||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024
-hipError_t launch_bias_l2_rows(const float* acc, const float* bias, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
 // out[i] = 1 / (1 + exp(-(cos[i] * scale + bias))), i < count; out may be cos
 hipError_t launch_siglip_scores(const float* cos, float* out, int64_t count, float scale, float bias, hipStream_t s);
 
-// ---- ViT/32 @224 image towers (patch32.hip, attention_short.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64
+// ---- ViT/32 @224 image towers (patch32.hip, attention_short.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64; the
+// row launchers above with tokens = 50
 // K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-32 matrix [n * 49, 3072] in conv order (c, ky, kx): a pure copy
 hipError_t launch_retile_p32(const void* patches16, void* patches32, int n, hipStream_t s);
-// acc f32 [n * 49, d] (the patch-embed GEMM under EPI_F32) -> x[b*50 + 1 + p] = bf16((acc + bias) + pos[1 + p]),
-// x[b*50] = bf16(cls + pos[0]); d = 384, 768 or 1024
-hipError_t launch_embed_rows_t50(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int d, hipStream_t s);
 // attention, T = 50, dh = 64, heads = 6, 12 or 16: qkv [n*50, 3*64*heads] (Q pre-scaled) -> out [n*50, 64*heads], exact row
 // maximum; only_block = 0 or 1: that query block of 32 only
 hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
-// launch_pool_ln / launch_pool on row b*50 + tok (0 <= tok <= 49)
-hipError_t launch_pool_ln_t50(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s);
-hipError_t launch_pool_t50(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
-                           hipStream_t s);
 
-// ---- SigLIP ViT/16 @224 image towers (siglip.hip; attention: launch_attention with tokens = 196): 196 tokens, no class token
-// acc f32 [n * 196, d] (the patch-embed GEMM under EPI_F32) -> x[b*196 + p] = bf16((acc + bias) + pos[p]); d = 384, 768 or 1024
-hipError_t launch_embed_rows_t196(const float* acc, const float* bias, const float* pos, void* x, int n, int d, hipStream_t s);
+// ---- SigLIP ViT/16 @224 image towers (siglip.hip; attention: launch_attention with tokens = 196; launch_embed_rows without a
+// class row; launch_l2_rows_bf16 behind the head): 196 tokens, no class token
 // attention pooling: kv bf16 [n*196, 2*64*heads] (K | V), q f32 [64*heads] (pre-scaled by dh^-0.5 log2 e, the same for every
 // crop) -> out bf16 [n, 64*heads]; exact maximum, f32 sums, one rounding; heads = 6, 12 or 16
 hipError_t launch_map_pool(const void* kv, const float* q, void* out, int n, int heads, hipStream_t s);
-// launch_l2_rows on bf16 rows: x bf16 [rows, p] -> x / max(||x||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024
-hipError_t launch_l2_rows_bf16(const void* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s);
 
 // ---- device-side weight preparation (weight_prep.hip).  dt = MME_DT_* (include/mme.h); sources are device addresses,
 // 16-byte aligned, of elements of that type.

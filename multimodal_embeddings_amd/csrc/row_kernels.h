@@ -1,0 +1,109 @@
+// Device-side pieces of the row kernels (rowops.hip, text_tower.hip): one 64-lane wave owns one row of D values.  Every
+// tower's LayerNorm row, pooled row and L2 step is built from these, so they cannot drift apart: the two-pass f32
+// LayerNorm (mean, then centred variance -- the form torch's LayerNorm uses, transformers modeling_vit.py:261-262,348) and
+// torch.nn.functional.normalize's x / max(||x||_2, 1e-12) are each written here once.
+#pragma once
+#include "common.h"
+
+// a row of D values over 64 lanes: NT accesses of V consecutive values per lane, access t at column t * 64 V + lane * V.
+// 768 = 3 x 4 values per lane, 1024 = 4 x 4, 512 = 2 x 4 (the text width), 384 = 3 x 2 (4-byte accesses: 384 is no multiple
+// of the 256 values a wave covers with 8-byte ones)
+template <int D> struct RowShape {
+    static_assert(D == 384 || D == 512 || D == 768 || D == 1024, "row kernels: widths 384, 512, 768 and 1024");
+    static constexpr int V = (D % 256) == 0 ? 4 : 2;
+    static constexpr int NT = D / (64 * V);
+    typedef __attribute__((ext_vector_type(V))) __bf16 bvec;
+    typedef __attribute__((ext_vector_type(V))) float fvec;
+};
+
+// bf16 row -> v[]: v[t * V + j] is column t * 64 V + lane * V + j
+template <int D> __device__ __forceinline__ void row_load(const bf16_t* xr, int lane, float (&v)[D / 64]) {
+    typedef RowShape<D> RS;
+#pragma unroll
+    for (int t = 0; t < RS::NT; ++t) {
+        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * RS::V + lane * RS::V);
+#pragma unroll
+        for (int j = 0; j < RS::V; ++j) v[t * RS::V + j] = (float)p[j];
+    }
+}
+
+// (mean, rstd) of the row in v[], which stays as it is: two wave reductions, the sums over v[0..] ascending
+template <int D> __device__ __forceinline__ float2 row_stats(const float (&v)[D / 64], float eps) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < D / 64; ++j) s += v[j];
+    const float mean = wave_sum(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < D / 64; ++j) {
+        const float d = v[j] - mean;
+        q += d * d;
+    }
+    return make_float2(mean, rsqrtf(wave_sum(q) * (1.0f / D) + eps));
+}
+
+// LayerNorm of the bf16 row xr: v[] leaves normalised, scaled and shifted, in f32
+template <int D>
+__device__ __forceinline__ void ln_row(const bf16_t* xr, const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int lane,
+                                       float (&v)[D / 64]) {
+    typedef RowShape<D> RS;
+    row_load<D>(xr, lane, v);
+    const float2 st = row_stats<D>(v, eps);
+#pragma unroll
+    for (int t = 0; t < RS::NT; ++t) {
+        const int c = t * 64 * RS::V + lane * RS::V;
+        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
+        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
+#pragma unroll
+        for (int j = 0; j < RS::V; ++j) v[t * RS::V + j] = (v[t * RS::V + j] - st.x) * st.y * gv[j] + bv[j];
+    }
+}
+
+// v[] -> bf16 row, one rounding to nearest even per value
+template <int D> __device__ __forceinline__ void row_store_bf16(bf16_t* yr, int lane, const float (&v)[D / 64]) {
+    typedef RowShape<D> RS;
+#pragma unroll
+    for (int t = 0; t < RS::NT; ++t) {
+        typename RS::bvec o;
+#pragma unroll
+        for (int j = 0; j < RS::V; ++j) o[j] = (bf16_t)v[t * RS::V + j];
+        *(typename RS::bvec*)(yr + t * 64 * RS::V + lane * RS::V) = o;
+    }
+}
+
+// The L2 step: v / max(||v||_2, 1e-12) -> the row at element `off` of yf (f32) and / or yb (bf16; either may be null), the
+// bf16 value the rounding of the f32 one.  n2 sums over v[0..] ascending.  A row narrower than D (`cols`, a multiple of 64,
+// RowShape<1024> only) holds zeros at the columns >= cols, and nothing is stored there.
+template <int D>
+__device__ __forceinline__ void row_l2_store(const float (&v)[D / 64], int lane, float* yf, bf16_t* yb, int64_t off, int cols = D) {
+    typedef RowShape<D> RS;
+    float n2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < D / 64; ++j) n2 += v[j] * v[j];
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
+#pragma unroll
+    for (int t = 0; t < RS::NT; ++t) {
+        const int c = t * 64 * RS::V + lane * RS::V;
+        if (c >= cols) continue;
+        typename RS::fvec o;
+        typename RS::bvec ob;
+#pragma unroll
+        for (int j = 0; j < RS::V; ++j) {
+            o[j] = v[t * RS::V + j] * inv;
+            ob[j] = (bf16_t)o[j];
+        }
+        if (yf) *(typename RS::fvec*)(yf + off + c) = o;
+        if (yb) *(typename RS::bvec*)(yb + off + c) = ob;
+    }
+}
+
+// launches the instantiation of a row kernel for width d; a width without one is an error, never another kernel.  The
+// launchers admit the widths of their path first (common.h: vit_width_built 384 / 768 / 1024, text_width_built 512 / 768 / 1024).
+#define ROW_KERNEL_BY_WIDTH(d, kernel, grid, s, ...)                                                          \
+    switch (d) {                                                                                              \
+        case 384: hipLaunchKernelGGL(kernel<384>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
+        case 512: hipLaunchKernelGGL(kernel<512>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
+        case 768: hipLaunchKernelGGL(kernel<768>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
+        case 1024: hipLaunchKernelGGL(kernel<1024>, grid, dim3(256), 0, s, __VA_ARGS__); break;               \
+        default: return hipErrorInvalidValue;                                                                 \
+    }

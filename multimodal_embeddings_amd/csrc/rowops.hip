@@ -1,26 +1,15 @@
-// Row-wise HBM-bound kernels of the ViT forward: LayerNorm (K3), [CLS] row initialisation,
-// and final-LayerNorm + pooling + L2 normalisation (K8).
+// Row-wise HBM-bound kernels of the image towers' forward and of the heads every tower ends in: LayerNorm (K3), class rows,
+// the rows behind an f32 patch-embed GEMM, the pooled row's LayerNorm with and without the L2 step (K8), the L2 step alone.
 //
-// One 64-lane wave owns one D-wide row: 3 x 8-byte (bf16x4) loads per lane at D = 768, statistics
-// in f32 registers, two wave reductions (mean, then centred variance -- the same two-pass
-// form torch's LayerNorm uses, transformers modeling_vit.py:261-262,348), 8-byte stores.
-// Instantiated per supported width (RowShape): 768 = 3 x 4 values per lane (the ViT-B/16 code as it always was),
-// 1024 = 4 x 4, 384 = 3 x 2 (4-byte accesses: 384 is no multiple of the 256 values a wave covers with 8-byte ones).
+// One 64-lane wave owns one D-wide row: 3 x 8-byte (bf16x4) loads per lane at D = 768, statistics in f32 registers, 8-byte
+// stores.  Instantiated per supported width; the layout of a row over the lanes, the two-pass LayerNorm of a row and the L2
+// step are row_kernels.h's.
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
+#include "row_kernels.h"
 
 namespace {
-
-// a row of D values over 64 lanes: NT accesses of V consecutive values per lane, access t at column t * 64 V + lane * V
-template <int D> struct RowShape {
-    static_assert(D == 384 || D == 768 || D == 1024, "row kernels: widths 384, 768 and 1024");
-    static constexpr int V = (D % 256) == 0 ? 4 : 2;
-    static constexpr int NT = D / (64 * V);
-    static constexpr int PER_LANE = D / 64;
-    typedef __attribute__((ext_vector_type(V))) __bf16 bvec;
-    typedef __attribute__((ext_vector_type(V))) float fvec;
-};
 
 template <int D>
 __global__ __launch_bounds__(256) void layernorm_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
@@ -29,38 +18,9 @@ __global__ __launch_bounds__(256) void layernorm_rows(const bf16_t* __restrict__
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const bf16_t* xr = x + row * D;
-    typedef RowShape<D> RS;
-    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
-    float v[NV];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        v[j] -= mean;
-        q += v[j] * v[j];
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-    bf16_t* yr = y + row * D;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = t * 64 * V + lane * V;
-        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
-        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
-        typename RS::bvec o;
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(v[t * V + j] * rstd * gv[j] + bv[j]);
-        *(typename RS::bvec*)(yr + c) = o;
-    }
+    float v[D / 64];
+    ln_row<D>(x + row * D, gamma, beta, eps, lane, v);
+    row_store_bf16<D>(y + row * D, lane, v);
 }
 
 // LayerNorm statistics only (mean, rstd) of bf16 rows of D: the normalisation itself is
@@ -72,28 +32,10 @@ __global__ __launch_bounds__(256) void ln_stats_rows(const bf16_t* __restrict__ 
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const bf16_t* xr = x + row * D;
-    typedef RowShape<D> RS;
-    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
-    float v[NV];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const float d = v[j] - mean;
-        q += d * d;
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-    if (lane == 0) *(float2*)(stats + 2 * row) = make_float2(mean, rstd);
+    float v[D / 64];
+    row_load<D>(x + row * D, lane, v);
+    const float2 st = row_stats<D>(v, eps);
+    if (lane == 0) *(float2*)(stats + 2 * row) = st;
 }
 
 // The same statistics in the canonical order of gemm_epilogue.h (ln_accumulate / ln_finish_row): one wave per
@@ -167,64 +109,58 @@ __global__ __launch_bounds__(256) void cls_rows(bf16_t* __restrict__ x, const fl
     }
 }
 
+// The rows behind a patch-embed GEMM that ran with the f32 epilogue (acc [n * patches, D]), one rounding per value:
+// x[b * TOKENS + first + p] = bf16((acc[b * patches + p] + bias) + pos[first + p]) -- the f32 order of the patch-embed
+// epilogue of the 197-token path -- where first = 1 with a class token, whose row is x[b * TOKENS] = bf16(cls + pos[0]),
+// and first = 0 without one (cls == nullptr); patches = TOKENS - first.
+template <int N> struct Const {};  // a compile-time integer among a kernel's arguments: kernel<D> deduces it
+template <int D, int TOKENS>
+__global__ __launch_bounds__(256) void embed_rows(const float* __restrict__ acc, const float* __restrict__ bias, const float* __restrict__ pos,
+                                                  const float* __restrict__ cls, bf16_t* __restrict__ x, int64_t rows, Const<TOKENS>) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t b = row / TOKENS;
+    const int t = (int)(row - b * TOKENS);
+    const int first = cls ? 1 : 0;
+    const bool class_row = cls && t == 0;
+    typedef RowShape<D> RS;
+    constexpr int V = RS::V, NT = RS::NT;
+    bf16_t* xr = x + row * D;
+    const float* pr = pos + (int64_t)t * D;
+    const float* ar = acc + (b * (TOKENS - first) + (class_row ? 0 : t - first)) * D;  // read for patch rows only
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        const int c = k * 64 * V + lane * V;
+        const typename RS::fvec p = *(const typename RS::fvec*)(pr + c);
+        typename RS::bvec o;
+        if (class_row) {
+            const typename RS::fvec a = *(const typename RS::fvec*)(cls + c);
+#pragma unroll
+            for (int j = 0; j < V; ++j) o[j] = (bf16_t)(a[j] + p[j]);
+        } else {
+            const typename RS::fvec a = *(const typename RS::fvec*)(ar + c);
+            const typename RS::fvec bv = *(const typename RS::fvec*)(bias + c);
+#pragma unroll
+            for (int j = 0; j < V; ++j) o[j] = (bf16_t)((a[j] + bv[j]) + p[j]);
+        }
+        *(typename RS::bvec*)(xr + c) = o;
+    }
+}
+
 // K8: restates last_pooling (deprecated_package/embedder.py:17-34) for one fixed token
-// index per sequence, after the final LayerNorm of that row only (the other 196 rows of
-// the last hidden state are never read by the reference's pooling).
+// index per sequence, after the final LayerNorm of that row only (the other rows of
+// the last hidden state are never read by the reference's pooling): row b * tokens + tok.
 template <int D>
 __global__ __launch_bounds__(256) void pool_ln_l2(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
-                                                  const float* __restrict__ beta, int B, int tok, float eps,
+                                                  const float* __restrict__ beta, int B, int tokens, int tok, float eps,
                                                   float* __restrict__ emb_f32, bf16_t* __restrict__ emb_bf16) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
-    const bf16_t* xr = x + ((int64_t)b * VIT_T + tok) * D;
-    typedef RowShape<D> RS;
-    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
-    float v[NV];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        v[j] -= mean;
-        q += v[j] * v[j];
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-    float n2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = t * 64 * V + lane * V;
-        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
-        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            v[t * V + j] = v[t * V + j] * rstd * gv[j] + bv[j];
-            n2 += v[t * V + j] * v[t * V + j];
-        }
-    }
-    // torch.nn.functional.normalize: x / max(||x||_2, 1e-12)
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = t * 64 * V + lane * V;
-        typename RS::fvec o;
-        typename RS::bvec ob;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            o[j] = v[t * V + j] * inv;
-            ob[j] = (bf16_t)o[j];
-        }
-        if (emb_f32) *(typename RS::fvec*)(emb_f32 + (int64_t)b * D + c) = o;
-        if (emb_bf16) *(typename RS::bvec*)(emb_bf16 + (int64_t)b * D + c) = ob;
-    }
+    float v[D / 64];
+    ln_row<D>(x + ((int64_t)b * tokens + tok) * D, gamma, beta, eps, lane, v);
+    row_l2_store<D>(v, lane, emb_f32, emb_bf16, (int64_t)b * D);
 }
 
 // f32 rows of any width d (d % 4 == 0) -> L2-normalised bf16 rows (one wave per row).  The
@@ -265,38 +201,11 @@ __global__ __launch_bounds__(256) void pre_ln_rows(bf16_t* __restrict__ x, const
     const int64_t row = (int64_t)blockIdx.x * 4 + wave;
     if (row >= rows) return;  // wave-uniform: no workgroup barrier below
     bf16_t* xr = x + row * D;
-    typedef RowShape<D> RS;
-    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
-    float v[NV];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        v[j] -= mean;
-        q += v[j] * v[j];
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
     bf16_t* lr = rowbuf[wave];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = t * 64 * V + lane * V;
-        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
-        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
-        typename RS::bvec o;
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(v[t * V + j] * rstd * gv[j] + bv[j]);
-        *(typename RS::bvec*)(xr + c) = o;
-        *(typename RS::bvec*)(lr + c) = o;
-    }
+    float v[D / 64];
+    ln_row<D>(xr, gamma, beta, eps, lane, v);
+    row_store_bf16<D>(xr, lane, v);
+    row_store_bf16<D>(lr, lane, v);
     // the wave reads what its own lanes wrote: LDS operations of one wave complete in order
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -330,81 +239,61 @@ __global__ __launch_bounds__(256) void pre_ln_rows(bf16_t* __restrict__ x, const
 }
 
 // CLIP's post_layernorm on the pooled row (modeling_clip.py, CLIPVisionTransformer.forward: pooled_output =
-// self.post_layernorm(last_hidden_state[:, 0, :])): pool_ln_l2's LayerNorm of row b * 197 + tok, rounded to bf16 [B, D]
+// self.post_layernorm(last_hidden_state[:, 0, :])): pool_ln_l2's LayerNorm of row b * tokens + tok, rounded to bf16 [B, D]
 // for the projection GEMM -- no L2 step, the projected vector is what gets normalised.
 template <int D>
 __global__ __launch_bounds__(256) void pool_ln_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
-                                                    const float* __restrict__ beta, int B, int tok, float eps, bf16_t* __restrict__ y) {
+                                                    const float* __restrict__ beta, int B, int tokens, int tok, float eps, bf16_t* __restrict__ y) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
-    const bf16_t* xr = x + ((int64_t)b * VIT_T + tok) * D;
-    typedef RowShape<D> RS;
-    constexpr int V = RS::V, NT = RS::NT, NV = RS::PER_LANE;
-    float v[NV];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * V + lane * V);
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[t * V + j] = (float)p[j];
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s += v[j];
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        v[j] -= mean;
-        q += v[j] * v[j];
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = t * 64 * V + lane * V;
-        const typename RS::fvec gv = *(const typename RS::fvec*)(gamma + c);
-        const typename RS::fvec bv = *(const typename RS::fvec*)(beta + c);
-        typename RS::bvec o;
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = (bf16_t)(v[t * V + j] * rstd * gv[j] + bv[j]);
-        *(typename RS::bvec*)(y + (int64_t)b * D + c) = o;
-    }
+    float v[D / 64];
+    ln_row<D>(x + ((int64_t)b * tokens + tok) * D, gamma, beta, eps, lane, v);
+    row_store_bf16<D>(y + (int64_t)b * D, lane, v);
 }
 
-// The L2 step of pool_ln_l2 on its own, for the projected rows of a CLIP tower (modeling_clip.py, CLIPModel.
-// get_image_features callers normalise image_embeds: x / ||x||; here torch.nn.functional.normalize's x / max(||x||, 1e-12)
-// as everywhere in this engine): f32 [rows, p] -> f32 and / or bf16.  One wave per row, p % 64 == 0, p <= 1024: a lane
-// holds columns 4 lane + 256 k .. + 3.
-__global__ __launch_bounds__(256) void l2_rows(const float* __restrict__ x, int64_t rows, int p, float* __restrict__ y_f32,
-                                               bf16_t* __restrict__ y_bf16) {
+// The L2 step of pool_ln_l2 on its own, for rows of any width p (p % 64 == 0, p <= 1024): the projected rows of a CLIP
+// tower (modeling_clip.py, CLIPModel.get_image_features callers normalise image_embeds: x / ||x||; here
+// torch.nn.functional.normalize's x / max(||x||, 1e-12) as everywhere in this engine), the output of SigLIP's pooling head,
+// the head of a SigLIP text tower -> f32 and / or bf16 [rows, p].  One wave per row in the layout of RowShape<1024>, zeros
+// at the columns >= p.  `load(i, c)`: the four f32 values of a row at column c, i = row * p + c.
+struct LoadF32 {  // f32 rows
+    const float* x;
+    __device__ f32x4 operator()(int64_t i, int) const { return *(const f32x4*)(x + i); }
+};
+struct LoadBf16 {  // bf16 rows, widened
+    const bf16_t* x;
+    __device__ f32x4 operator()(int64_t i, int) const {
+        const bf16x4 b = *(const bf16x4*)(x + i);
+        return f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
+    }
+};
+struct LoadF32Bias {  // acc + bias[c], formed once in f32 (the rows of an EPI_F32 GEMM whose layer has a bias)
+    const float* acc;
+    const float* bias;
+    __device__ f32x4 operator()(int64_t i, int c) const { return *(const f32x4*)(acc + i) + *(const f32x4*)(bias + c); }
+};
+template <class Load>
+__global__ __launch_bounds__(256) void l2_rows(Load load, int64_t rows, int p, float* __restrict__ y_f32, bf16_t* __restrict__ y_bf16) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + row * p;
-    f32x4 v[4];
-    float n2 = 0.f;
+    float v[16];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int c = lane * 4 + k * 256;
-        v[k] = c < p ? *(const f32x4*)(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const f32x4 a = c < p ? load(row * p + c, c) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) n2 += v[k][j] * v[k][j];
+        for (int j = 0; j < 4; ++j) v[k * 4 + j] = a[j];
     }
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + k * 256;
-        if (c >= p) continue;
-        f32x4 o;
-        bf16x4 ob;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = v[k][j] * inv;
-            ob[j] = (bf16_t)o[j];
-        }
-        if (y_f32) *(f32x4*)(y_f32 + row * p + c) = o;
-        if (y_bf16) *(bf16x4*)(y_bf16 + row * p + c) = ob;
-    }
+    row_l2_store<1024>(v, lane, y_f32, y_bf16, row * p, p);
+}
+
+template <class Load> hipError_t launch_l2(Load load, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
+    if (p < 64 || (p % 64) != 0 || p > 1024) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(l2_rows<Load>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, load, rows, p, y_f32, (bf16_t*)y_bf16);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -414,15 +303,6 @@ hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, h
     hipLaunchKernelGGL(normalise_rows_f32, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, (bf16_t*)y);
     return hipGetLastError();
 }
-
-// the instantiation of a row kernel for width d (384, 768, 1024); any other width is an error, never another kernel
-#define ROW_KERNEL_BY_WIDTH(d, kernel, grid, s, ...)                                                          \
-    switch (d) {                                                                                              \
-        case 384: hipLaunchKernelGGL(kernel<384>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
-        case 768: hipLaunchKernelGGL(kernel<768>, grid, dim3(256), 0, s, __VA_ARGS__); break;                 \
-        case 1024: hipLaunchKernelGGL(kernel<1024>, grid, dim3(256), 0, s, __VA_ARGS__); break;               \
-        default: return hipErrorInvalidValue;                                                                 \
-    }
 
 hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int d, float eps, hipStream_t s) {
     if (!vit_width_built(d)) return hipErrorInvalidValue;
@@ -460,11 +340,27 @@ hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, i
     return hipGetLastError();
 }
 
-hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32,
+hipError_t launch_embed_rows(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int tokens, int d, hipStream_t s) {
+    if (!vit_width_built(d) || tokens != (cls ? 50 : 196)) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    const int64_t rows = (int64_t)n * tokens;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (cls) {
+        ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<50>{})
+    } else {
+        ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<196>{})
+    }
+    return hipGetLastError();
+}
+
+// the token layouts of the image path whose pooled row the final LayerNorm reads
+static bool pool_row_ok(int tokens, int tok) { return (tokens == VIT_T || tokens == 50) && tok >= 0 && tok < tokens; }
+
+hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps, float* emb_f32,
                        void* emb_bf16, hipStream_t s) {
-    if (!vit_width_built(d)) return hipErrorInvalidValue;
+    if (!vit_width_built(d) || !pool_row_ok(tokens, tok)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
-    ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tok, eps, emb_f32, (bf16_t*)emb_bf16)
+    ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tokens, tok, eps, emb_f32, (bf16_t*)emb_bf16)
     return hipGetLastError();
 }
 
@@ -475,16 +371,19 @@ hipError_t launch_pre_ln(void* x, const float* gamma, const float* beta, int64_t
     return hipGetLastError();
 }
 
-hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, void* y, hipStream_t s) {
-    if (!vit_width_built(d)) return hipErrorInvalidValue;
+hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps, void* y, hipStream_t s) {
+    if (!vit_width_built(d) || !pool_row_ok(tokens, tok)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
-    ROW_KERNEL_BY_WIDTH(d, pool_ln_rows, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tok, eps, (bf16_t*)y)
+    ROW_KERNEL_BY_WIDTH(d, pool_ln_rows, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tokens, tok, eps, (bf16_t*)y)
     return hipGetLastError();
 }
 
 hipError_t launch_l2_rows(const float* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
-    if (p < 64 || (p % 64) != 0 || p > 1024) return hipErrorInvalidValue;
-    if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(l2_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, p, y_f32, (bf16_t*)y_bf16);
-    return hipGetLastError();
+    return launch_l2(LoadF32{x}, rows, p, y_f32, y_bf16, s);
+}
+hipError_t launch_l2_rows_bf16(const void* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
+    return launch_l2(LoadBf16{(const bf16_t*)x}, rows, p, y_f32, y_bf16, s);
+}
+hipError_t launch_bias_l2_rows(const float* acc, const float* bias, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
+    return launch_l2(LoadF32Bias{acc, bias}, rows, p, y_f32, y_bf16, s);
 }

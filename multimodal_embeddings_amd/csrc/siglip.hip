@@ -1,9 +1,7 @@
-// SigLIP ViT/16 @224 image towers (196 tokens, no class token): the two kernels the tower adds beside the 196-token
-// instantiation of the attention kernel (attention.hip) and the tanh-GELU epilogues (gemm_epilogue.h).
+// SigLIP ViT/16 @224 image towers (196 tokens, no class token): the kernel the tower adds beside the 196-token
+// instantiation of the attention kernel (attention.hip), the tanh-GELU epilogues (gemm_epilogue.h) and rowops.hip's
+// launch_embed_rows (tokens = 196, no class row) and launch_l2_rows_bf16.
 //
-//   embed_rows_t196  the patch-embed GEMM runs with the f32 epilogue (acc [n * 196, D]); this kernel writes the residual
-//                    stream with one rounding per value: x[b * 196 + p] = bf16((acc + bias) + pos[p]) -- the f32 order of
-//                    the patch-embed epilogue of the 197-token path.
 //   map_pool         the attention of SiglipMultiheadAttentionPoolingHead: ONE learned query per head attends over the 196
 //                    tokens of a crop.  kv bf16 [n * 196, 2 D] (K | V, the head's in_proj over post_layernorm(x)), q f32 [D]
 //                    (probe . W_q^T + b_q, times dh^-0.5 log2 e: the same for every crop, prepared at load) -> a bf16 [n, D]:
@@ -13,8 +11,6 @@
 //                    contiguous bytes per lane; p goes through 1 KiB of LDS per wave; P.V: lane = (row group g of 4, four
 //                    head dims), so one instruction reads four whole 128-byte V rows, 49 steps, then two cross-lane adds
 //                    ((g0 + g1) + (g2 + g3)).  Nothing at or past row 196 n is read.
-//   l2_rows_bf16     rowops.hip's l2_rows on bf16 rows (the head's output y is the residual stream's type): widened to f32,
-//                    x / max(||x||, 1e-12) in l2_rows' arithmetic, to f32 and / or bf16.
 // 64-bit offsets everywhere.
 #include "common.h"
 #include "kernels.h"
@@ -22,40 +18,6 @@
 namespace {
 
 constexpr int T196 = 196;
-
-// rowops.hip's RowShape: a row of D values over 64 lanes, NT accesses of V consecutive values per lane
-template <int D> struct RowShape196 {
-    static_assert(D == 384 || D == 768 || D == 1024, "row kernels: widths 384, 768 and 1024");
-    static constexpr int V = (D % 256) == 0 ? 4 : 2;
-    static constexpr int NT = D / (64 * V);
-    typedef __attribute__((ext_vector_type(V))) __bf16 bvec;
-    typedef __attribute__((ext_vector_type(V))) float fvec;
-};
-
-template <int D>
-__global__ __launch_bounds__(256) void embed_rows_t196(const float* __restrict__ acc, const float* __restrict__ bias, const float* __restrict__ pos,
-                                                       bf16_t* __restrict__ x, int64_t rows) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int p = (int)(row % T196);
-    typedef RowShape196<D> RS;
-    constexpr int V = RS::V, NT = RS::NT;
-    bf16_t* xr = x + row * D;
-    const float* pr = pos + (int64_t)p * D;
-    const float* ar = acc + row * D;
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-        const int c = k * 64 * V + lane * V;
-        const typename RS::fvec pv = *(const typename RS::fvec*)(pr + c);
-        const typename RS::fvec a = *(const typename RS::fvec*)(ar + c);
-        const typename RS::fvec bv = *(const typename RS::fvec*)(bias + c);
-        typename RS::bvec o;
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = (bf16_t)((a[j] + bv[j]) + pv[j]);
-        *(typename RS::bvec*)(xr + c) = o;
-    }
-}
 
 template <int H>
 __global__ __launch_bounds__(256) void map_pool(const bf16_t* __restrict__ kv, const float* __restrict__ q, bf16_t* __restrict__ out, int64_t items) {
@@ -124,57 +86,7 @@ __global__ __launch_bounds__(256) void map_pool(const bf16_t* __restrict__ kv, c
     if (g == 0) *(bf16x4*)(out + b * D + h * VIT_DH + c4) = o;
 }
 
-__global__ __launch_bounds__(256) void l2_rows_bf16(const bf16_t* __restrict__ x, int64_t rows, int p, float* __restrict__ y_f32,
-                                                    bf16_t* __restrict__ y_bf16) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const bf16_t* xr = x + row * p;
-    f32x4 v[4];
-    float n2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + k * 256;
-        v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c < p) {
-            const bf16x4 b = *(const bf16x4*)(xr + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[k][j] = (float)b[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) n2 += v[k][j] * v[k][j];
-    }
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + k * 256;
-        if (c >= p) continue;
-        f32x4 o;
-        bf16x4 ob;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = v[k][j] * inv;
-            ob[j] = (bf16_t)o[j];
-        }
-        if (y_f32) *(f32x4*)(y_f32 + row * p + c) = o;
-        if (y_bf16) *(bf16x4*)(y_bf16 + row * p + c) = ob;
-    }
-}
-
 }  // namespace
-
-hipError_t launch_embed_rows_t196(const float* acc, const float* bias, const float* pos, void* x, int n, int d, hipStream_t s) {
-    if (!vit_width_built(d)) return hipErrorInvalidValue;
-    if (n <= 0) return hipSuccess;
-    const int64_t rows = (int64_t)n * T196;
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    switch (d) {
-        case 384: hipLaunchKernelGGL(embed_rows_t196<384>, grid, dim3(256), 0, s, acc, bias, pos, (bf16_t*)x, rows); break;
-        case 768: hipLaunchKernelGGL(embed_rows_t196<768>, grid, dim3(256), 0, s, acc, bias, pos, (bf16_t*)x, rows); break;
-        default: hipLaunchKernelGGL(embed_rows_t196<1024>, grid, dim3(256), 0, s, acc, bias, pos, (bf16_t*)x, rows); break;
-    }
-    return hipGetLastError();
-}
 
 hipError_t launch_map_pool(const void* kv, const float* q, void* out, int n, int heads, hipStream_t s) {
     if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;
@@ -186,12 +98,5 @@ hipError_t launch_map_pool(const void* kv, const float* q, void* out, int n, int
         case 12: hipLaunchKernelGGL(map_pool<12>, grid, dim3(256), 0, s, (const bf16_t*)kv, q, (bf16_t*)out, items); break;
         default: hipLaunchKernelGGL(map_pool<16>, grid, dim3(256), 0, s, (const bf16_t*)kv, q, (bf16_t*)out, items); break;
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_l2_rows_bf16(const void* x, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
-    if (p < 64 || (p % 64) != 0 || p > 1024) return hipErrorInvalidValue;
-    if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(l2_rows_bf16, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const bf16_t*)x, rows, p, y_f32, (bf16_t*)y_bf16);
     return hipGetLastError();
 }

@@ -1,12 +1,13 @@
 // Row kernels of the CLIP text tower (transformers models/clip/modeling_clip.py, CLIPTextEmbeddings and the pooling of
 // CLIPTextTransformer.forward): the token rows that open the pass and the LayerNorm of the EOS rows that closes it.
-// One 64-lane wave owns one row of D values, D a multiple of 256 up to 1024 (512, 768, 1024: 8, 12, 16 heads of 64): a lane
-// holds columns 4 lane + 256 k .. + 3.  The sequence length T is a template parameter: 77 (TXT_T, CLIP) or 64 (TXT_T64, the
-// SigLIP text tower: transformers models/siglip/modeling_siglip.py, SiglipTextEmbeddings and SiglipTextTransformer's
-// last_hidden_state[:, -1, :] -- eos_pool_ln_rows with every position 63 -- whose head's bias and the L2 step are bias_l2_rows).
+// One 64-lane wave owns one row of D values, D = 512, 768 or 1024 (8, 12, 16 heads of 64).  The sequence length is 77
+// (TXT_T, CLIP) or 64 (TXT_T64, the SigLIP text tower: transformers models/siglip/modeling_siglip.py, SiglipTextEmbeddings
+// and SiglipTextTransformer's last_hidden_state[:, -1, :] -- eos_pool_ln_rows with every position 63; the head's bias and
+// the L2 step are rowops.hip's launch_bias_l2_rows).
 // siglip_scores is SiglipModel.forward's sigmoid(exp(logit_scale) cos + logit_bias) on a cosine block.
 #include "common.h"
 #include "kernels.h"
+#include "row_kernels.h"
 
 namespace {
 
@@ -32,101 +33,27 @@ __global__ __launch_bounds__(256) void token_rows(const bf16_t* __restrict__ tok
     }
 }
 
-// final_layer_norm of row b * T + eos_pos[b], the two-pass f32 form of pool_ln_rows (rowops.hip), rounded to bf16
-// [n, D] for the projection GEMM and / or left in f32 [n, D] (a tower without text_projection: the L2 step reads that).
-template <int T>
+// final_layer_norm of row b * tokens + eos_pos[b], the LayerNorm of rowops.hip's pool_ln_rows, rounded to bf16 [n, D]
+// for the projection GEMM and / or left in f32 [n, D] (a tower without text_projection: the L2 step reads that).
+template <int D>
 __global__ __launch_bounds__(256) void eos_pool_ln_rows(const bf16_t* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        const int32_t* __restrict__ eos_pos, int n, int D, float eps, bf16_t* __restrict__ y,
+                                                        const int32_t* __restrict__ eos_pos, int n, int tokens, float eps, bf16_t* __restrict__ y,
                                                         float* __restrict__ yf) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n) return;
-    const bf16_t* xr = x + ((int64_t)b * T + eos_pos[b]) * D;
-    const int nk = D >> 8;  // 2, 3 or 4 groups of 256 columns (wave-uniform)
-    float v[4][4];
-    float s = 0.f;
+    typedef RowShape<D> RS;
+    float v[D / 64];
+    ln_row<D>(x + ((int64_t)b * tokens + eos_pos[b]) * D, gamma, beta, eps, lane, v);
+    if (y) row_store_bf16<D>(y + (int64_t)b * D, lane, v);
+    if (yf) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < nk) {
-            const bf16x4 p = *(const bf16x4*)(xr + k * 256 + lane * 4);
+        for (int t = 0; t < RS::NT; ++t) {
+            typename RS::fvec o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[k][j] = (float)p[j];
-                s += v[k][j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[k][j] = 0.f;
+            for (int j = 0; j < RS::V; ++j) o[j] = v[t * RS::V + j];
+            *(typename RS::fvec*)(yf + (int64_t)b * D + t * 64 * RS::V + lane * RS::V) = o;
         }
-    }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < nk) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[k][j] -= mean;
-                q += v[k][j] * v[k][j];
-            }
-        }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < nk) {
-            const int c = k * 256 + lane * 4;
-            const f32x4 gv = *(const f32x4*)(gamma + c);
-            const f32x4 bv = *(const f32x4*)(beta + c);
-            f32x4 o;
-            bf16x4 ob;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                o[j] = v[k][j] * rstd * gv[j] + bv[j];
-                ob[j] = (bf16_t)o[j];
-            }
-            if (y) *(bf16x4*)(y + (int64_t)b * D + c) = ob;
-            if (yf) *(f32x4*)(yf + (int64_t)b * D + c) = o;
-        }
-}
-
-// The head of a SigLIP text tower behind its EPI_F32 GEMM, and the L2 step: y = acc + bias formed once in f32, then
-// y / max(||y||, 1e-12) in l2_rows' arithmetic and reduction order (rowops.hip), to f32 and / or bf16.  One wave per row,
-// p % 64 == 0, p <= 1024: a lane holds columns 4 lane + 256 k .. + 3.
-__global__ __launch_bounds__(256) void bias_l2_rows(const float* __restrict__ acc, const float* __restrict__ bias, int64_t rows, int p,
-                                                    float* __restrict__ y_f32, bf16_t* __restrict__ y_bf16) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* xr = acc + row * p;
-    f32x4 v[4];
-    float n2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + k * 256;
-        v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c < p) {
-            const f32x4 a = *(const f32x4*)(xr + c);
-            const f32x4 bv = *(const f32x4*)(bias + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[k][j] = a[j] + bv[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) n2 += v[k][j] * v[k][j];
-    }
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int c = lane * 4 + k * 256;
-        if (c >= p) continue;
-        f32x4 o;
-        bf16x4 ob;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            o[j] = v[k][j] * inv;
-            ob[j] = (bf16_t)o[j];
-        }
-        if (y_f32) *(f32x4*)(y_f32 + row * p + c) = o;
-        if (y_bf16) *(bf16x4*)(y_bf16 + row * p + c) = ob;
     }
 }
 
@@ -157,17 +84,7 @@ hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const floa
                                    float* y_f32, hipStream_t s, int tokens) {
     if (!text_width_built(d) || (tokens != TXT_T && tokens != TXT_T64)) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
-    if (tokens == TXT_T)
-        hipLaunchKernelGGL(eos_pool_ln_rows<TXT_T>, dim3((n + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, eos_pos, n, d, eps, (bf16_t*)y, y_f32);
-    else
-        hipLaunchKernelGGL(eos_pool_ln_rows<TXT_T64>, dim3((n + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, gamma, beta, eos_pos, n, d, eps, (bf16_t*)y, y_f32);
-    return hipGetLastError();
-}
-
-hipError_t launch_bias_l2_rows(const float* acc, const float* bias, int64_t rows, int p, float* y_f32, void* y_bf16, hipStream_t s) {
-    if (p < 64 || (p % 64) != 0 || p > 1024) return hipErrorInvalidValue;
-    if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(bias_l2_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, acc, bias, rows, p, y_f32, (bf16_t*)y_bf16);
+    ROW_KERNEL_BY_WIDTH(d, eos_pool_ln_rows, dim3((n + 3) / 4), s, (const bf16_t*)x, gamma, beta, eos_pos, n, tokens, eps, (bf16_t*)y, y_f32)
     return hipGetLastError();
 }
 

@@ -17,7 +17,8 @@ What is compared with what, and why the bound is what it is:
   4. Row kernels (ops 0, 1, 4, 5) at d = 384 and 1024 and the GEMM epilogues at the family's shapes, against float64
      with the formulas and bounds of tests/test_gpu_gemm.py (imported from there, so they cannot drift apart).  GELU on
      random data: |got - ref| <= gelu_tol(ref) + 1.13 d_x, where d_x is that file's accumulation bound on the
-     pre-activation and 1.13 > max |gelu'| = 1.1289.
+     pre-activation and 1.13 > max |gelu'| = 1.1289.  The pooled row's LayerNorm and L2 step are one arithmetic in every
+     token layout (197, 50 and the text tower's 77): the same rows through each layout's hook, compared for EQUALITY.
   5. Two contexts of different geometry in one process, called alternately; a second load into a context.
   6. Downstream at d = 1024 and 384: cross_compare within 2e-6 of float64 numpy on the returned bf16 rows (the cosine
      bound of tests/test_gpu_parity.py), region_neighbours decision for decision against the oracle's loop on the
@@ -458,6 +459,45 @@ def test_pool_ln_l2(d, tok):
     assert float(np.abs(got[7].double().cpu().numpy() - bn).max()) <= tol, "zero row: output is not beta / ||beta||"
     other = X.view(B, T, d)[:, tok - 1 if tok else 1].float().cpu().numpy()
     assert int((np.abs(pool_ref(other, gamma, beta, eps, np.float64) - ref) > 4 * tol).sum()) >= B * d // 2, "mutant 'neighbouring token' not separated"
+    eng.close()
+
+
+@pytest.mark.parametrize("d", [384, 768, 1024])
+@pytest.mark.parametrize("tok", [0, 49])
+def test_pooled_row_is_one_arithmetic_in_every_layout(d, tok):
+    """The LayerNorm of a pooled row and its L2 step are written once (csrc/row_kernels.h): the same 5 rows at token `tok`
+    of a 197-token, a 50-token and (text widths) a 77-token stream must leave every pooling hook in the same BITS."""
+    eng = Engine(0)
+    B, eps = 5, 1e-5
+    g = _gen(900 + d + tok)
+    rows = _randn((B, d), g).to(BF16)
+    gm, bt = (1.0 + _randn((d,), g, 0.2)).contiguous(), _randn((d,), g, 0.5)
+
+    def stream(tokens):
+        x = _randn((B, tokens, d), g).to(BF16)
+        x[:, tok] = rows
+        return x.view(B * tokens, d).contiguous()
+
+    x197, x50 = stream(T), stream(50)
+    a32, a16, b32, b16 = Guard(F32, B, d), Guard(BF16, B, d), Guard(F32, B, d), Guard(BF16, B, d)
+    eng.rowop_apply("pool_ln_l2", x=x197, gamma=gm, beta=bt, B=B, tok=tok, d=d, eps=eps, emb_f32=a32.view, emb_bf16=a16.view)
+    eng.vit32_apply("pool_ln_l2", x=x50, gamma=gm, beta=bt, n=B, tok=tok, d=d, eps=eps, emb_f32=b32.view, emb_bf16=b16.view)
+    for buf in (a32, a16, b32, b16):
+        buf.check("pool_ln_l2")
+    assert bool(torch.isfinite(a32.valid).all()) and float(a32.valid.abs().max()) > 0
+    assert_bits(b32.valid_bits(), a32.valid_bits(), f"pool_ln_l2 f32, 50 against 197 tokens, d {d} tok {tok}")
+    assert_bits(b16.valid_bits(), a16.valid_bits(), f"pool_ln_l2 bf16, 50 against 197 tokens, d {d} tok {tok}")
+    y197, y50 = Guard(BF16, B, d), Guard(BF16, B, d)
+    eng.clip_apply("pool_ln", x=x197, gamma=gm, beta=bt, y=y197.view, B=B, tok=tok, d=d, eps=eps)
+    eng.vit32_apply("pool_ln", x=x50, gamma=gm, beta=bt, y=y50.view, n=B, tok=tok, d=d, eps=eps)
+    y197.check("pool_ln")
+    y50.check("pool_ln")
+    assert_bits(y50.valid_bits(), y197.valid_bits(), f"pool_ln, 50 against 197 tokens, d {d} tok {tok}")
+    if d != 384:  # 384 is no text width
+        y77 = Guard(BF16, B, d)
+        eng.text_apply("eos_pool_ln", x=stream(77), gamma=gm, beta=bt, eos_pos=[tok] * B, y=y77.view, n=B, d=d, eps=eps)
+        y77.check("eos_pool_ln")
+        assert_bits(y77.valid_bits(), y197.valid_bits(), f"eos_pool_ln against pool_ln, d {d} tok {tok}")
     eng.close()
 
 

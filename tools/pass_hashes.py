@@ -1,21 +1,30 @@
 #!/usr/bin/env python3
 """sha256 of what every encoder pass writes, per configuration: one JSON line each.
 
-    python tools/pass_hashes.py [--only image|text|tile] > hashes.jsonl
+    python tools/pass_hashes.py [--only image|text|tile|rows] > hashes.jsonl
 
-For a change that moves no arithmetic (the transformer block's launch sequence is host code: csrc/encoder_pass.hip) the
-lines of two libraries must be EQUAL, not close.  Run the tool once per library, each in a fresh process -- another
+For a change that moves no arithmetic (the transformer block's launch sequence is host code: csrc/encoder_pass.hip; the
+row kernels share their device-side pieces: csrc/row_kernels.h) the lines of two libraries must be EQUAL, not close.  Run the tool once per library, each in a fresh process -- another
 build is selected with MME_LIB_PATH and MME_ALLOW_LIB_OVERRIDE=1, as tools/_diag.py does -- and compare the outputs with
 `diff`.  Every tower is two layers deep and seeded (weights.py), every input is seeded; the shapes are the smallest that
 reach every branch of the shared block:
 
   image   ViT-S/16 width (384: no partial planes under ln_mode 2), ViT-B/16 width (768: planes), CLIP-B/16 (pre-LN,
-          QuickGELU, projection), ViT-B/32, CLIP-B/32.  3 crops at patch 16 are 591 rows (two 256-row panels and a ragged
-          tail of 79), 6 crops at patch 32 are 300.  From the defaults one switch at a time: ln_mode, tile order, attention
-          mode, last-layer pruning at the first and the last pool token, GEMM variant, and chunks of 2 over 5 crops.
-  text    CLIP-B's text width with and without projection, 3 sequences; once more than one chunk of 1024.
+          QuickGELU, projection), ViT-B/32, CLIP-B/32, SigLIP-B/16 (196 tokens, tanh-GELU, pooling head).  3 crops at
+          patch 16 are 591 rows (two 256-row panels and a ragged tail of 79), 6 crops at patch 32 are 300.  From the
+          defaults one switch at a time: ln_mode, tile order, attention mode, last-layer pruning at the first and the last
+          pool token, GEMM variant, and chunks of 2 over 5 crops.
+  text    CLIP-B's text width with and without projection, 3 sequences; once more than one chunk of 1024.  The SigLIP
+          text tower (64 tokens, head with bias) on 3 sequences.
   tile    1 local + 1 global layer, one intermediate state, both save-point conventions, ln_mode 1 / 2 x attention mode
           0 / 1 / 2, on a 1-tile and a 4-tile image.
+  rows    every row launcher once through the *_apply hooks, at every width it is built for: LayerNorm, statistics,
+          class rows, pooled LayerNorm with and without the L2 step at the first and the last token of the 197- and the
+          50-token layout, pre-LN, the embed rows of both layouts without a class token and with one (2 crops: the
+          class row of the second is reached), the EOS pooling of both text layouts, the three L2 forms at p = 64 / 320 /
+          1024 (one partly filled column group, a partly filled second one, all four).  5 rows or sequences: two
+          workgroups of four waves, the second with one live wave.  Every output buffer is hashed WITH a sentinel-filled
+          margin behind it, untouched rows included.
 
 Each configuration ends in a device synchronise; the first error ends the run (nothing is caught).  Needs a GPU.
 """
@@ -35,7 +44,7 @@ if ROOT not in sys.path:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--only", choices=("image", "text", "tile"), default=None)
+    ap.add_argument("--only", choices=("image", "text", "tile", "rows"), default=None)
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -70,15 +79,19 @@ def main(argv=None) -> int:
         towers = {
             "vit_s16": dataclasses.replace(W.VIT_S16, **two), "vit_b16": dataclasses.replace(W.VIT_B16, **two),
             "clip_b16": dataclasses.replace(W.CLIP_B16, **two), "vit_b32": dataclasses.replace(W.VIT_B32, **two),
-            "clip_b32": dataclasses.replace(W.CLIP_B32, **two),
+            "clip_b32": dataclasses.replace(W.CLIP_B32, **two), "siglip_b16": dataclasses.replace(W.SIGLIP_B16, **two),
         }
         # (name, setter, values): the first value is the library's default and is restored after the sweep
         switches = [("ln_mode", Engine.set_ln_fusion, (2, 0, 1)), ("tile_order", Engine.set_tile_order, (1, 0, 2)),
                     ("attention_mode", Engine.set_attention_mode, (1, 0, 2)), ("gemm_variant", Engine.set_gemm_variant, (0, 1, 3))]
         for name, geom in towers.items():
-            clip = isinstance(geom, W.CLIPGeometry)
             e = Engine(0)
-            (e.load_clip if clip else e.load_vit)((W.make_clip_weights if clip else W.make_vit_weights)(11, geom), geom=geom)
+            if isinstance(geom, W.SiglipGeometry):
+                e.load_siglip(W.make_siglip_weights(11, geom), geom=geom)
+            elif isinstance(geom, W.CLIPGeometry):
+                e.load_clip(W.make_clip_weights(11, geom), geom=geom)
+            else:
+                e.load_vit(W.make_vit_weights(11, geom), geom=geom)
             n = 3 if geom.patch_size == 16 else 6
             patches = e.preprocess(*pack(list(W.synthetic_crops(n, seed=5))))
             emit(f"{name} defaults", *e.vit_forward(patches))
@@ -103,6 +116,11 @@ def main(argv=None) -> int:
             for n in (3, 1030) if proj else (3,):  # MME_TEXT_CHUNK is 1024: a full chunk and a ragged one
                 emit(f"text projection={proj} n={n}", *e.text_forward(W.synthetic_token_ids(n, geom.vocab_size, geom.eos_token_id, 7)))
             e.close()
+        geom = W.SiglipTextGeometry(num_layers=2, vocab_size=256)
+        e = Engine(0)
+        e.load_siglip_text(W.make_siglip_text_weights(43, geom), geom)
+        emit("siglip_text n=3", *e.text_forward(W.siglip_token_ids(3, geom.vocab_size, geom.pad_token_id, 7)))
+        e.close()
 
     def tile():
         rng = np.random.default_rng(4)
@@ -122,7 +140,80 @@ def main(argv=None) -> int:
                     emit(f"tile save={point} ln_mode={ln} attention_mode={attn}", *e.tile_vit_forward(pv, ids, nt, want_hidden=True))
             e.close()
 
-    for name, fn in (("image", image), ("text", text), ("tile", tile)):
+    def rows():
+        t, dev = torch, "cuda:0"
+        BF, F = t.bfloat16, t.float32
+        rng = np.random.default_rng(17)
+        N, IMG, TXT, PS = 5, (384, 768, 1024), (512, 768, 1024), (64, 320, 1024)
+
+        def f32(*shape, scale=1.0, shift=0.0):
+            return t.from_numpy((shift + scale * rng.standard_normal(shape)).astype(np.float32)).to(dev)
+
+        def bf(*shape):
+            return f32(*shape).to(BF)
+
+        class Out:
+            """a sentinel-filled byte buffer with 256 more bytes behind the tensor the kernel is handed"""
+
+            def __init__(self, dtype, *shape, init=None):
+                nbytes = int(np.prod(shape)) * t.empty((), dtype=dtype).element_size()
+                self.raw = t.full((nbytes + 256,), 0xA5, dtype=t.uint8, device=dev)
+                self.view = self.raw[:nbytes].view(dtype).view(*shape)
+                if init is not None:
+                    self.view.copy_(init)
+
+        e = Engine(0)
+        for d in IMG:
+            x, gamma, beta = bf(N, d), f32(d, scale=0.2, shift=1.0), f32(d, scale=0.5)
+            y, st = Out(BF, N, d), Out(F, N, 2)
+            e.rowop_apply("layernorm", x=x, y=y.view, gamma=gamma, beta=beta, rows=N, d=d, eps=1e-12)
+            emit(f"rows layernorm d={d}", y.raw)
+            e.rowop_apply("ln_stats", x=x, stats=st.view, rows=N, d=d, eps=1e-12)
+            emit(f"rows ln_stats d={d}", st.raw)
+            xs = Out(BF, N * 197, d)
+            e.rowop_apply("cls_rows", x=xs.view, cls=f32(d), pos=f32(197, d), B=N, d=d)
+            emit(f"rows cls_rows d={d}", xs.raw)
+            xp, st = Out(BF, N, d, init=x), Out(F, N, 2)
+            e.clip_apply("pre_ln", x=xp.view, gamma=gamma, beta=beta, stats=st.view, rows=N, d=d, eps=1e-5)
+            emit(f"rows pre_ln d={d}", xp.raw, st.raw)
+            for tokens, pool, pool_l2 in ((197, lambda **kw: e.clip_apply("pool_ln", B=N, **kw), lambda **kw: e.rowop_apply("pool_ln_l2", B=N, **kw)),
+                                          (50, lambda **kw: e.vit32_apply("pool_ln", n=N, **kw), lambda **kw: e.vit32_apply("pool_ln_l2", n=N, **kw))):
+                xt = bf(N * tokens, d)
+                for tok in (0, tokens - 1):
+                    y, e32, e16 = Out(BF, N, d), Out(F, N, d), Out(BF, N, d)
+                    pool(x=xt, gamma=gamma, beta=beta, y=y.view, tok=tok, d=d, eps=1e-5)
+                    emit(f"rows pool_ln tokens={tokens} tok={tok} d={d}", y.raw)
+                    pool_l2(x=xt, gamma=gamma, beta=beta, emb_f32=e32.view, emb_bf16=e16.view, tok=tok, d=d, eps=1e-12)
+                    emit(f"rows pool_ln_l2 tokens={tokens} tok={tok} d={d}", e32.raw, e16.raw)
+            bias = f32(d)
+            xo = Out(BF, 2 * 50, d)
+            e.vit32_apply("embed_rows", acc=f32(2 * 49, d), bias=bias, pos=f32(50, d), cls=f32(d), x=xo.view, n=2, d=d)
+            emit(f"rows embed_rows tokens=50 d={d}", xo.raw)
+            xo = Out(BF, 2 * 196, d)
+            e.siglip_apply("embed_rows", acc=f32(2 * 196, d), bias=bias, pos=f32(196, d), x=xo.view, n=2, d=d)
+            emit(f"rows embed_rows tokens=196 d={d}", xo.raw)
+            e32, e16 = Out(F, N, d), Out(BF, N, d)
+            e.siglip_apply("l2_bf16", x=x, emb_f32=e32.view, emb_bf16=e16.view, n=N, d=d)
+            emit(f"rows l2_bf16 p={d}", e32.raw, e16.raw)
+        for p in PS:
+            xf, bias = f32(N, p), f32(p)
+            y32, y16 = Out(F, N, p), Out(BF, N, p)
+            e.clip_apply("l2", xf=xf, y_f32=y32.view, y_bf16=y16.view, rows=N, p=p)
+            emit(f"rows l2 p={p}", y32.raw, y16.raw)
+            y32, y16 = Out(F, N, p), Out(BF, N, p)
+            e.siglip_text_apply("bias_l2", acc=xf, bias=bias, emb_f32=y32.view, emb_bf16=y16.view, n=N, p=p)
+            emit(f"rows bias_l2 p={p}", y32.raw, y16.raw)
+        for d in TXT:
+            gamma, beta = f32(d, scale=0.2, shift=1.0), f32(d, scale=0.5)
+            y, yf = Out(BF, N, d), Out(F, N, d)
+            e.text_apply("eos_pool_ln", x=bf(N * 77, d), gamma=gamma, beta=beta, eos_pos=[0, 1, 76, 0, 76], y=y.view, y_f32=yf.view, n=N, d=d, eps=1e-5)
+            emit(f"rows eos_pool_ln tokens=77 d={d}", y.raw, yf.raw)
+            y, yf = Out(BF, N, d), Out(F, N, d)
+            e.siglip_text_apply("last_pool_ln", x=bf(N * 64, d), gamma=gamma, beta=beta, y=y.view, y_f32=yf.view, n=N, d=d, eps=1e-6)
+            emit(f"rows last_pool_ln tokens=64 d={d}", y.raw, yf.raw)
+        e.close()
+
+    for name, fn in (("image", image), ("text", text), ("tile", tile), ("rows", rows)):
         if args.only in (None, name):
             fn()
     return 0
