@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "encoder_pass.h"
+#include "resample.h"
 
 namespace {
 
@@ -440,16 +441,22 @@ int run_h_pass(mme_ctx* c, K1Plan& p, const uint8_t* pix, int n, hipStream_t s, 
         HIP_TRY(c, hipMemcpyAsync(c->hwork.p, c->h_work.data(), c->h_work.size() * sizeof(HWork), hipMemcpyHostToDevice, s));
     return MME_OK;
 }
-// resample_tables + the horizontal pass (one launch per class)
-int launch_h_pass(mme_ctx* c, const K1Plan& p, const uint8_t* pix, int n, hipStream_t s, const char* who) {
-    if (p.tab_bytes) HIP_TRY(c, launch_resample_tables((const CropDesc*)c->crops.p, n, (uint8_t*)c->htab.p, s));
+// the tables of every crop + the horizontal pass (one launch per class), for either descriptor: `tables` and `resize_h` are
+// the rule's launchers, `rule` what the error text calls its pass
+template <class Desc, class Tables, class ResizeH>
+int launch_h_pass(mme_ctx* c, const K1Plan& p, const uint8_t* pix, int n, hipStream_t s, const char* who, const char* rule, Tables tables, ResizeH resize_h) {
+    const Desc* crops = (const Desc*)c->crops.p;
+    if (p.tab_bytes) HIP_TRY(c, tables(crops, n, (uint8_t*)c->htab.p, s));
     const HWork* work = (const HWork*)c->hwork.p;
     for (int k = 0; k < 3; ++k) {
-        hipError_t e = launch_resize_h(pix, (uint8_t*)c->tmp.p, (const CropDesc*)c->crops.p, work, p.count[k], p.lds[k], k, (const uint8_t*)c->htab.p, s);
-        if (e != hipSuccess) return fail(c, MME_E_HIP, "%s: horizontal pass, class %d (%s); %d bytes of LDS", who, k, hipGetErrorString(e), p.lds[k]);
+        hipError_t e = resize_h(pix, (uint8_t*)c->tmp.p, crops, work, p.count[k], p.lds[k], k, (const uint8_t*)c->htab.p, s);
+        if (e != hipSuccess) return fail(c, MME_E_HIP, "%s: %shorizontal pass, class %d (%s); %d bytes of LDS", who, rule, k, hipGetErrorString(e), p.lds[k]);
         work += p.count[k];
     }
     return MME_OK;
+}
+int launch_h_pass(mme_ctx* c, const K1Plan& p, const uint8_t* pix, int n, hipStream_t s, const char* who) {
+    return launch_h_pass<CropDesc>(c, p, pix, n, s, who, "", launch_resample_tables, launch_resize_h);
 }
 
 // ---- K1 under MME_RESIZE_CLIP (preprocess_clip.hip) ---------------------------------------------------------------------
@@ -461,22 +468,8 @@ void clip_resized_size(int h, int w, int* nh, int* nw) {
     *nh = h <= w ? VIT_IMG : nl;
     *nw = h <= w ? nl : VIT_IMG;
 }
-// [xmin, xmax) of output coordinate xx (Resample.c precompute_coeffs, BICUBIC: support 2); the device computes the same
-// two expressions in f64 (bicubic_taps_to)
-void clip_window(int in_size, int out_size, int xx, int* xmin, int* xmax) {
-    const double scale = (double)in_size / (double)out_size;
-    const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
-    const double center = (xx + 0.5) * scale;
-    int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
-    *xmin = lo < 0 ? 0 : lo;
-    *xmax = hi > in_size ? in_size : hi;
-}
-// Resample.c's ksize, the upper bound of a window's taps; 1 for an axis that is not filtered
-int clip_ksize(int in_size, int out_size) {
-    if (in_size == out_size) return 1;
-    const double scale = (double)in_size / (double)out_size;
-    return (int)std::ceil(2.0 * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
-}
+// Resample.c's ksize (resample.h), the upper bound of a window's taps; 1 for an axis that is not filtered
+int clip_ksize(int in_size, int out_size) { return in_size == out_size ? 1 : resample_ksize<Bicubic>(in_size, out_size); }
 
 // Sizes against the 8000 x 8000 limit: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145, so gh <= 37 and kv <= 148 (the
 // vertical pass holds 160); a crop's tables take <= 3584 + 37 * 3584 + 224 * 148 * 4 = 268 800 bytes and its scratch
@@ -486,9 +479,9 @@ void plan_clip_crop(K1Plan& p, int i, ClipCropDesc& d) {
     d.top = (d.new_h - VIT_IMG) / 2;
     d.left = (d.new_w - VIT_IMG) / 2;
     if (d.new_h != d.h) {
-        int a, b, y, z;
-        clip_window(d.h, d.new_h, d.top, &a, &b);
-        clip_window(d.h, d.new_h, d.top + VIT_IMG - 1, &y, &z);
+        // the union of the 224 vertical windows: the expressions clip_tables evaluates on the device (resample.h)
+        const Taps first = resample_window<Bicubic>(d.h, d.new_h, d.top), last = resample_window<Bicubic>(d.h, d.new_h, d.top + VIT_IMG - 1);
+        const int a = first.xmin, z = last.xmin + last.n;
         d.r0 = a;
         d.nr = (z > a ? z : a + 1) - a;
     } else {
@@ -520,16 +513,8 @@ int preprocess_chunk_clip(mme_ctx* c, const uint8_t* pix, const int64_t* offs, c
     HIP_TRY(c, hipMemcpyAsync(c->crops.p, c->h_clip_crops.data(), (size_t)n * sizeof(ClipCropDesc), hipMemcpyHostToDevice, s));
     if ((r = run_h_pass(c, plan, pix, n, s, "mme_preprocess"))) return r;
     Timed t(c, s, KC_PRE);
-    const ClipCropDesc* crops = (const ClipCropDesc*)c->crops.p;
-    HIP_TRY(c, launch_clip_tables(crops, n, (uint8_t*)c->htab.p, s));
-    const HWork* work = (const HWork*)c->hwork.p;
-    for (int k = 0; k < 3; ++k) {
-        hipError_t e = launch_clip_resize_h(pix, (uint8_t*)c->tmp.p, crops, work, plan.count[k], plan.lds[k], k, (const uint8_t*)c->htab.p, s);
-        if (e != hipSuccess)
-            return fail(c, MME_E_HIP, "mme_preprocess: BICUBIC horizontal pass, class %d (%s); %d bytes of LDS", k, hipGetErrorString(e), plan.lds[k]);
-        work += plan.count[k];
-    }
-    HIP_TRY(c, launch_clip_v_patchify((const uint8_t*)c->tmp.p, crops, n, c->lut, c->norm_aff, patches, (const uint8_t*)c->htab.p, plan.kv_max, s));
+    if ((r = launch_h_pass<ClipCropDesc>(c, plan, pix, n, s, "mme_preprocess", "BICUBIC ", launch_clip_tables, launch_clip_resize_h))) return r;
+    HIP_TRY(c, launch_clip_v_patchify((const uint8_t*)c->tmp.p, (const ClipCropDesc*)c->crops.p, n, c->lut, c->norm_aff, patches, (const uint8_t*)c->htab.p, plan.kv_max, s));
     return MME_OK;
 }
 

@@ -8,62 +8,26 @@
 
 #include "ctx.h"
 #include "lanczos.h"
-
-#pragma clang fp contract(off)
+#include "resample.h"
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
 constexpr int MAX_IN = 32768, MAX_OUT = 8000, MAX_RATIO = 16;
 
-// Resample.c sinc_filter / lanczos_filter
-inline double sinc_filter(double x) {
-    if (x == 0.0) return 1.0;
-    x = x * M_PI;
-    return sin(x) / x;
-}
-inline double lanczos_filter(double x) {
-    if (-3.0 <= x && x < 3.0) return sinc_filter(x) * sinc_filter(x / 3);
-    return 0.0;
-}
-
 // Resample.c precompute_coeffs: ksize of an axis (box = whole image)
-int axis_ksize(int in_size, int out_size) {
-    const double scale = (double)in_size / (double)out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(3.0 * filterscale) * 2 + 1;
-}
+int axis_ksize(int in_size, int out_size) { return resample_ksize<Lanczos3>(in_size, out_size); }
 
-// precompute_coeffs + normalize_coeffs_8bpc for every output coordinate; put(xx, xmin, n) then k(xx, i, coefficient) for
-// i < ksize (zero from n on).  ww is summed sequentially, then the division, as there.
+// precompute_coeffs + normalize_coeffs_8bpc for every output coordinate (resample.h): bounds(xx, xmin, n) and
+// coeff(xx, i, coefficient) for i < ksize (zero from n on).  The filter values of a coordinate are kept between the
+// summation and the division, so sin is called once per tap.
 template <class Bounds, class Coeff>
 void axis_table(int in_size, int out_size, Bounds bounds, Coeff coeff) {
-    const double scale = (double)in_size / (double)out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 3.0 * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
-    const double ss = 1.0 / filterscale;
+    const int ksize = axis_ksize(in_size, out_size);
     std::vector<double> w((size_t)ksize);
     for (int xx = 0; xx < out_size; ++xx) {
-        const double center = (xx + 0.5) * scale;
-        double ww = 0.0;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        int n = xmax - xmin;
-        if (n > ksize) n = ksize;  // never taken (Resample.c sizes its own rows by ksize): a memory-safety guard
-        for (int x = 0; x < n; ++x) {
-            w[x] = lanczos_filter((x + xmin - center + 0.5) * ss);
-            ww += w[x];
-        }
-        bounds(xx, xmin, n);
-        for (int x = 0; x < n; ++x) {
-            double v = w[x];
-            if (ww != 0.0) v /= ww;
-            coeff(xx, x, v < 0 ? (int)(-0.5 + v * (double)(1 << PRECISION_BITS)) : (int)(0.5 + v * (double)(1 << PRECISION_BITS)));
-        }
-        for (int x = n; x < ksize; ++x) coeff(xx, x, 0);
+        const Taps t = resample_taps<Lanczos3>(in_size, out_size, xx, ksize, [&](int i, int k) { coeff(xx, i, k); }, w.data());
+        bounds(xx, t.xmin, t.n);
+        for (int x = t.n; x < ksize; ++x) coeff(xx, x, 0);
     }
 }
 

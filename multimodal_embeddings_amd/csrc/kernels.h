@@ -128,7 +128,10 @@ __host__ __device__ inline int k1_tmp_pitch(int new_w) { return (new_w * 3 + 15)
 //   width changes:  Taps[new_w] {xmin, n} | pad to 16 | uint4 hk[gh][new_w]   -- coefficients in groups of four taps,
 //                   group-major so that adjacent output columns read adjacent 16-byte words; zero beyond tap n
 //   height changes: Taps[new_h] | pad to 16 | int vk[new_h][kv]               -- zero beyond tap n
-// gh * 4, kv >= 2 * ceil(scale) + 1 = Resample.c's ksize, the upper bound of n.
+// gh * 4, kv >= 2 * ceil(scale) + 1 = Resample.c's ksize, the upper bound of n.  The integer formulas below (k1_h_groups, kv
+// of k1_layout) equal resample_ksize<Triangle> (resample.h) rounded up to a multiple of four: ceil(max(w / new_w, 1)) is the
+// integer ceiling of w / new_w (1 for an enlarged axis in both); they stay integer so that a layout function does not
+// depend on f64.
 // groups of four taps per output column of the horizontal pass
 __host__ __device__ inline int k1_h_groups(int w, int new_w) { return (2 * ((w + new_w - 1) / new_w) + 1 + 3) >> 2; }
 // bytes of LDS the horizontal table of a crop takes beside its band (table padded to whole 1 KiB DMA sweeps)
@@ -156,6 +159,7 @@ constexpr int K1_H_RPT_WIDE = 4;  // ... in the second launch (crops whose table
 hipError_t launch_resample_tables(const CropDesc* crops, int n, uint8_t* tab, hipStream_t s);
 // horizontal pass over `nwork` bands of ONE class (capi: K1Plan): 0 = eight-row items, table in LDS beside the band;
 // 1 = four-row items, table in LDS; 2 = four-row items, table through L1.  lds_bytes = the largest (table +) band.
+// (launch_resize_h and launch_clip_resize_h are the one kernel template of resample.h over the two descriptors.)
 hipError_t launch_resize_h(const uint8_t* pix, uint8_t* tmp, const CropDesc* crops, const HWork* work, int nwork, int lds_bytes,
                            int cls, const uint8_t* tab, hipStream_t s);
 // multi-tile Mllama output: grid_of int32[n,2] (tiles_h, tiles_w); out f32 [n, max_tiles, 3, T, T]
@@ -176,7 +180,7 @@ hipError_t launch_resize_v_patchify(const uint8_t* pix, const uint8_t* tmp, cons
                                     const float* lut /*[3,256]*/, const NormAffine& aff, void* patches, bool any_resize, const uint8_t* tab, int kv_max,
                                     hipStream_t s);
 
-// ---- K1 under MME_RESIZE_CLIP (preprocess_clip.hip): shortest-edge BICUBIC resize + centre crop, only the 224 x 224
+// ---- K1 under MME_RESIZE_CLIP (preprocess_clip.hip, on resample.h): shortest-edge BICUBIC resize + centre crop, only the 224 x 224
 // window of the resized image computed.  What CropDesc cannot carry: the FULL resized sizes, the window's origin and the
 // source rows the horizontal pass filters.
 struct ClipCropDesc {  // one per crop, built on the host by capi (plan_clip_crop)

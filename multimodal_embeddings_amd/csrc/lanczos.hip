@@ -1,9 +1,10 @@
 // The 8000-pixel cap on the device: Image.resize((new_w, new_h), Image.LANCZOS) of an 8-bit RGB image, bit for bit
 // (embedder.py:110-114 -> Pillow libImaging/Resample.c, 8-bit path).
 //
-// The arithmetic is preprocess_clip.hip's with another filter: 22-bit fixed-point coefficients, horizontal pass then
-// vertical pass, each a signed 32-bit sum from 2^21, an arithmetic shift by 22 and a clamp to 0..255.  The tables are made
-// on the host (capi_lanczos.hip: f64, contraction off, libm's sin -- the function Pillow's object code calls) and arrive
+// The arithmetic is resample.h's Signed sums, as the BICUBIC path's, with another filter: 22-bit fixed-point coefficients,
+// horizontal pass then vertical pass, each a signed 32-bit sum from 2^21, an arithmetic shift by 22 and a clamp to 0..255.
+// The tables are made on the host (capi_lanczos.hip on resample.h's resample_taps<Lanczos3>: f64, contraction off, libm's
+// sin -- the function Pillow's object code calls) and arrive
 // here as rows {xmin, n, k[0..ksize)} of ksize + 2 ints per output coordinate (lanczos.h).  Bounds (tests/test_lanczos_cpu.py
 // walks the whole accepted range): |k| < 1.17 * 2^22 < 2^23 and sum |k| < 1.56 * 2^22, so a signed 24-bit multiply of a
 // pixel byte is exact and 255 * sum |k| + 2^21 < 2^31.
@@ -28,41 +29,9 @@
 #include "common.h"
 #include "kernels.h"
 #include "lanczos.h"
+#include "resample.h"
 
 namespace {
-
-constexpr int PRECISION_BITS = 32 - 8 - 2;
-
-struct __attribute__((packed)) U32u {  // a dword at ANY byte address (gfx950 reads unaligned LDS words)
-    uint32_t v;
-};
-
-__device__ __forceinline__ int clip8s(int v) {
-    v >>= PRECISION_BITS;  // arithmetic
-    return min(max(v, 0), 255);
-}
-__device__ __forceinline__ int mad24s(uint32_t pixel, int k, int acc) { return __mul24((int)pixel, k) + acc; }
-// Clamped sums as the bytes of a dword.  The bytes are made opaque before they are combined: see pack2_clip8s of
-// preprocess_clip.hip (hipcc otherwise fuses shift + clamp + pack into v_ashr_pk_u8_i32 and ORs further bytes into its
-// result as if the upper half were zero).
-__device__ __forceinline__ uint32_t pack3_clip8s(int s0, int s1, int s2) {
-    int b0 = clip8s(s0), b1 = clip8s(s1), b2 = clip8s(s2);
-    asm volatile("" : "+v"(b0), "+v"(b1), "+v"(b2));
-    return (uint32_t)b0 | ((uint32_t)b1 << 8) | ((uint32_t)b2 << 16);
-}
-__device__ __forceinline__ uint32_t pack4_clip8s(int s0, int s1, int s2, int s3) {
-    int b0 = clip8s(s0), b1 = clip8s(s1), b2 = clip8s(s2), b3 = clip8s(s3);
-    asm volatile("" : "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
-    return (uint32_t)b0 | ((uint32_t)b1 << 8) | ((uint32_t)b2 << 16) | ((uint32_t)b3 << 24);
-}
-
-// nvec 16-byte words from g (16-byte aligned) to lds, all four waves; lanes past the end re-read the last word, so
-// the bytes written are nvec * 16 rounded up to a whole 1 KiB sweep
-__device__ __forceinline__ void dma_range_to_lds(const uint4* __restrict__ g, char* lds, int nvec, int tid) {
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    for (int i = wave * 64; i < nvec; i += 256) glds16(g + min(i + lane, nvec - 1), lds + (size_t)i * 16);
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 __global__ __launch_bounds__(256) void lanczos_h(const uint8_t* __restrict__ src, int64_t src_pitch, int h, int new_w,
                                                  const int32_t* __restrict__ tab, int stride, uint8_t* __restrict__ tmp, int tmp_pitch,
@@ -114,22 +83,22 @@ __global__ __launch_bounds__(256) void lanczos_h(const uint8_t* __restrict__ src
             const int yy = min(y0 + r, nrows - 1);
             const int lead = (int)((uintptr_t)(s0 + (int64_t)yy * src_pitch) & 15);
             p[r] = band + (size_t)yy * slot + lead + woff;
-            acc[r][0] = acc[r][1] = acc[r][2] = 1 << (PRECISION_BITS - 1);
+            acc[r][0] = acc[r][1] = acc[r][2] = Signed::start;
         }
         for (int i = 0; i < n; ++i) {
             const int k = kc[i];
 #pragma unroll
             for (int r = 0; r < LZ_H_RPT; ++r) {
                 const uint32_t d = ((const U32u*)(p[r] + 3 * i))->v;  // the fourth byte is the next pixel's (or slot tail)
-                acc[r][0] = mad24s(d & 0xff, k, acc[r][0]);
-                acc[r][1] = mad24s((d >> 8) & 0xff, k, acc[r][1]);
-                acc[r][2] = mad24s((d >> 16) & 0xff, k, acc[r][2]);
+                acc[r][0] = Signed::mad(d & 0xff, k, acc[r][0]);
+                acc[r][1] = Signed::mad((d >> 8) & 0xff, k, acc[r][1]);
+                acc[r][2] = Signed::mad((d >> 16) & 0xff, k, acc[r][2]);
             }
         }
         uint8_t* drow = tmp + (int64_t)(row0 + y0) * tmp_pitch;
 #pragma unroll
         for (int r = 0; r < LZ_H_RPT; ++r) {
-            const uint32_t v = pack3_clip8s(acc[r][0], acc[r][1], acc[r][2]);
+            const uint32_t v = Signed::pack(acc[r][0], acc[r][1], acc[r][2]);
             const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xF9 /* quad_perm [1,2,3,3] */, 0xF, 0xF, true);
             const uint32_t out = (v >> sh_own) | (nb << sh_nb);  // (j = 3: a value nobody stores)
             if (store_ok && y0 + r < nrows) *(uint32_t*)(drow + (int64_t)r * tmp_pitch + col_off) = out;
@@ -156,7 +125,7 @@ __global__ __launch_bounds__(256) void lanczos_v(const uint8_t* __restrict__ tmp
     __syncthreads();
     int acc[LZ_TY][4];
 #pragma unroll
-    for (int y = 0; y < LZ_TY; ++y) acc[y][0] = acc[y][1] = acc[y][2] = acc[y][3] = 1 << (PRECISION_BITS - 1);
+    for (int y = 0; y < LZ_TY; ++y) acc[y][0] = acc[y][1] = acc[y][2] = acc[y][3] = Signed::start;
     const uint32_t* win = (const uint32_t*)window + tid;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     for (int c0 = r0; c0 < r1; c0 += LZ_VCH) {
@@ -175,19 +144,12 @@ __global__ __launch_bounds__(256) void lanczos_v(const uint8_t* __restrict__ tmp
                 const int lo = max(xmin, c0), hi = min(xmin + n, c1);
                 const uint32_t* wp = win + (lo - c0) * (LZ_CB / 4);
                 const int32_t* kp = T + y * stride + 2 + (lo - xmin);
-                for (int t = 0; t < hi - lo; ++t) {
-                    const uint32_t d = wp[t * (LZ_CB / 4)];
-                    const int k = kp[t];
-                    acc[y][0] = mad24s(d & 0xff, k, acc[y][0]);
-                    acc[y][1] = mad24s((d >> 8) & 0xff, k, acc[y][1]);
-                    acc[y][2] = mad24s((d >> 16) & 0xff, k, acc[y][2]);
-                    acc[y][3] = mad24s(d >> 24, k, acc[y][3]);
-                }
+                for (int t = 0; t < hi - lo; ++t) mad_bytes4<Signed>(acc[y], wp[t * (LZ_CB / 4)], kp[t]);
             }
         }
     }
 #pragma unroll
-    for (int y = 0; y < LZ_TY; ++y) canvas[y * (LZ_CB / 4) + tid] = pack4_clip8s(acc[y][0], acc[y][1], acc[y][2], acc[y][3]);
+    for (int y = 0; y < LZ_TY; ++y) canvas[y * (LZ_CB / 4) + tid] = Signed::pack(acc[y][0], acc[y][1], acc[y][2], acc[y][3]);
     __syncthreads();
     // the band's bytes [c0b, c0b + nb) of every row, as dwords aligned in dst
     const int nb = min(LZ_CB, row_bytes - c0b);

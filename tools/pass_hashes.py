@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """sha256 of what every encoder pass writes, per configuration: one JSON line each.
 
-    python tools/pass_hashes.py [--only image|text|tile|rows] > hashes.jsonl
+    python tools/pass_hashes.py [--only image|text|tile|rows|resample] > hashes.jsonl
 
 For a change that moves no arithmetic (the transformer block's launch sequence is host code: csrc/encoder_pass.hip; the
-row kernels share their device-side pieces: csrc/row_kernels.h) the lines of two libraries must be EQUAL, not close.  Run the tool once per library, each in a fresh process -- another
+row kernels share their device-side pieces: csrc/row_kernels.h; the three resize paths share Pillow's 8-bit resampling:
+csrc/resample.h) the lines of two libraries must be EQUAL, not close.  Run the tool once per library, each in a fresh process -- another
 build is selected with MME_LIB_PATH and MME_ALLOW_LIB_OVERRIDE=1, as tools/_diag.py does -- and compare the outputs with
 `diff`.  Every tower is two layers deep and seeded (weights.py), every input is seeded; the shapes are the smallest that
 reach every branch of the shared block:
@@ -25,6 +26,13 @@ reach every branch of the shared block:
           1024 (one partly filled column group, a partly filled second one, all four).  5 rows or sequences: two
           workgroups of four waves, the second with one live wave.  Every output buffer is hashed WITH a sentinel-filled
           margin behind it, untouched rows included.
+  resample  every resize path, each run ONE call on a small mixed batch in one fixed seeded order: `preprocess` under the
+          fit_pad and the clip rule, each with a normalisation the patch emitter computes (fma) and one it reads from the
+          table; `preprocess_tiles` (560, 4); `lanczos_resize` in the ordinary and in the vertical-first order (more than
+          100 times as high as wide, getting lower).  The batch: 1 x 1, 20 x 63, 63 x 20, crops that keep their width or
+          their height (300 x 224, 224 x 300, 100 x 224) and, per rule, the shapes whose horizontal pass is of class 1
+          and of class 2 (fit_pad 1400 x 1350 and 17 x 8000, clip 37 x 1000 and 2000 x 3000); 224 x 224 alone runs the
+          RESIZE = false instantiation.  Every output buffer is hashed with its sentinel margin.
 
 Each configuration ends in a device synchronise; the first error ends the run (nothing is caught).  Needs a GPU.
 """
@@ -44,7 +52,7 @@ if ROOT not in sys.path:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--only", choices=("image", "text", "tile", "rows"), default=None)
+    ap.add_argument("--only", choices=("image", "text", "tile", "rows", "resample"), default=None)
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -213,7 +221,49 @@ def main(argv=None) -> int:
             emit(f"rows last_pool_ln tokens=64 d={d}", y.raw, yf.raw)
         e.close()
 
-    for name, fn in (("image", image), ("text", text), ("tile", tile), ("rows", rows)):
+    def resample():
+        t, dev = torch, "cuda:0"
+        rng = np.random.default_rng(23)
+        shapes = [(1, 1), (20, 63), (63, 20), (300, 224), (224, 300), (100, 224), (1400, 1350), (17, 8000), (37, 1000), (2000, 3000)]
+        mixed = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in (shapes[i] for i in rng.permutation(len(shapes)))]
+        alone = [rng.integers(0, 256, (224, 224, 3), dtype=np.uint8)]
+
+        def out(nbytes):
+            return t.full((nbytes + 256,), 0xA5, dtype=t.uint8, device=dev)
+
+        e = Engine(0)
+        # (name, mean, std, the form the patch emitter takes): tests/test_gpu_normalisation.py, "half" and "table_ch0"
+        norms = [("fma", (0.5, 0.5, 0.5), (0.5, 0.5, 0.5), True), ("table", (0.6, 0.892, 0.7415), (0.1993, 0.0298, 0.0224), False)]
+        for rule in ("fit_pad", "clip"):
+            e.set_resize_rule(rule)
+            for norm, mean, std, exact in norms:
+                e.set_normalisation(mean, std)
+                assert e.normalisation_form()[0] == exact, (norm, e.normalisation_form())
+                for batch, arrays in (("mixed", mixed), ("224x224", alone)):
+                    pix, offs, hw = pack(arrays)
+                    offs, hw = e._crop_tables(offs, hw)
+                    raw = out(len(arrays) * 196 * 768 * 2)
+                    e._check(e.lib.mme_preprocess(e.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, len(arrays), raw.data_ptr(), e._stream()),
+                             "mme_preprocess")
+                    emit(f"resample preprocess rule={rule} norm={norm} batch={batch}", raw)
+        e.set_resize_rule("fit_pad")
+        pix, offs, hw = pack(mixed)
+        offs, hw = e._crop_tables(offs, hw)
+        n, tile, max_tiles = len(mixed), 560, 4
+        raw = out(n * max_tiles * 3 * tile * tile * 4)
+        ids, nt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        e._check(e.lib.mme_preprocess_tiles(e.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, tile, max_tiles, raw.data_ptr(), ids.ctypes.data,
+                                            nt.ctypes.data, e._stream()), "mme_preprocess_tiles")
+        emit("resample preprocess_tiles tile=560 max_tiles=4", raw, t.from_numpy(np.concatenate([ids, nt])))
+        # (source h, w, new_h, new_w): an ordinary cap with a ragged last tile on both axes, and the vertical-first order
+        for name, (h, w, nh, nw) in (("ordinary", (700, 1303, 431, 803)), ("vertical_first", (2300, 21, 1237, 13))):
+            src = t.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).to(dev)
+            raw = out(nh * nw * 3)
+            e.lanczos_resize(src, nh, nw, out=raw[: nh * nw * 3])
+            emit(f"resample lanczos_resize {name} {h}x{w}->{nh}x{nw}", raw)
+        e.close()
+
+    for name, fn in (("image", image), ("text", text), ("tile", tile), ("rows", rows), ("resample", resample)):
         if args.only in (None, name):
             fn()
     return 0
