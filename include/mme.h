@@ -144,7 +144,7 @@ typedef struct {
 } mme_clip_weights;
 int mme_load_clip(mme_ctx* ctx, const mme_clip_weights* w);
 int mme_load_clip_as(mme_ctx* ctx, const mme_clip_weights* w, int dtype, void* stream);
-/* out[4] = kind (0 ViT, 1 CLIP, 2 SigLIP), embed_dim (the row width the forward writes), act (0 erf-GELU, 1 QuickGELU, 2 tanh-GELU), proj_dim (0: none)
+/* out[4] = kind (0 ViT, 1 CLIP, 2 SigLIP, 3 DINOv2), embed_dim (the row width the forward writes), act (0 erf-GELU, 1 QuickGELU, 2 tanh-GELU), proj_dim (0: none)
  * of the context's encoder: what the last load brought, {0, 768, 0, 0} before any. */
 int mme_encoder_info(mme_ctx* ctx, int32_t out[4]);
 
@@ -175,6 +175,35 @@ typedef struct {
 } mme_siglip_weights;
 int mme_load_siglip(mme_ctx* ctx, const mme_siglip_weights* w);
 int mme_load_siglip_as(mme_ctx* ctx, const mme_siglip_weights* w, int dtype, void* stream);
+
+/* ---- DINOv2 ViT/14 image towers ------------------------------------------------------------------------------------------
+ * Replaces `Dinov2Model.from_pretrained(dir)(pixel_values 224 x 224).pooler_output`, L2-normalised (transformers
+ * models/dinov2/modeling_dinov2.py; dinov2-small / -base / -large): the third image geometry, patch 14 at 224 pixels, 16 x 16
+ * patches and a class token, 257 tokens, heads of 64.  The tower is the ViT forward (pre-LN blocks, erf-GELU, no LayerNorm
+ * before layer 0, the final `layernorm` on the pooled row only) with these differences:
+ *   - Dinov2Embeddings: a 14 x 14 patch convolution with bias (vit.patch_w [hidden, 588], prepared as bf16 [hidden, 640] with
+ *     zero columns behind), cls_token prepended, then the position table added.  vit.pos_emb is [257, hidden] and ALWAYS host
+ *     f32, under the ..._as form too: a checkpoint's [1 + g * g, hidden] table is interpolated to 16 x 16 by the caller, once,
+ *     with the model's own call (checkpoint.py, interpolate_dinov2_positions).  mask_token is not read.
+ *   - Dinov2Layer: x + lambda1 * attention(norm1(x)), then x + lambda2 * mlp(norm2(x)) (layer_scale1 / layer_scale2, [hidden]
+ *     each: scale[l]).  LayerScale is folded at load: o_w'[n, k] = bf16(f32(lambda1[n] * o_w[n, k])), o_b'[n] =
+ *     f32(lambda1[n] * o_b[n]), the same for fc2 with lambda2; the block then runs as every other tower's.
+ * mme_vit_forward / mme_embed write rows of `hidden`; pool_token 0 (the default) is pooler_output, 256 the last patch token.
+ * mme_preprocess writes bf16 [n * 256, 640] per crop: row PY * 16 + PX, column c * 196 + ky * 14 + kx, columns 588..639 zero.
+ * Validation as for the ViT loader with patch_size 14 only (every other loader keeps refusing 14); a refusal names the
+ * field, the value found and the supported set, and nothing in the context changes.  SwiGLU towers (the giant) and register
+ * tokens are not run.  Prepared buffers (mme_weights_read): the ViT's 6 + 18 L in their order.  A later ViT, CLIP or SigLIP
+ * load on the same context returns it to that form. */
+typedef struct {
+    const float* lambda1;  /* layer_scale1.lambda1, [hidden] */
+    const float* lambda2;  /* layer_scale2.lambda1, [hidden] */
+} mme_dinov2_scale;
+typedef struct {
+    mme_vit_weights vit;            /* patch_size 14; pos_emb [257, hidden], host f32 under both loaders; patch_w [hidden, 588] */
+    const mme_dinov2_scale* scale;  /* [layers] */
+} mme_dinov2_weights;
+int mme_load_dinov2(mme_ctx* ctx, const mme_dinov2_weights* w);
+int mme_load_dinov2_as(mme_ctx* ctx, const mme_dinov2_weights* w, int dtype, void* stream);
 
 /* ---- CLIP text tower ------------------------------------------------------------------------------------------------------
  * Replaces `CLIPTextModelWithProjection.from_pretrained(dir)(input_ids).text_embeds` (or `CLIPTextModel`'s pooler_output
@@ -981,6 +1010,45 @@ typedef struct mme_siglip_apply_args {
     int32_t n, d, heads;
 } mme_siglip_apply_args;
 int mme_siglip_apply(mme_ctx* ctx, int op, const mme_siglip_apply_args* args, void* stream);
+
+/* Diagnostic: ONE launch of a kernel a DINOv2 tower (ViT/14 @224: 256 patches of 14 x 14, 257 tokens) adds, on the caller's
+ * device buffers, synchronous; works on a bare context.  n = crops.
+ *   op 0 retile_patches_p14  src bf16 [n * 196, 768] (what K1 writes) -> dst bf16 [n * 256, 640], conv order (c, ky, kx):
+ *                            dst[b * 256 + PY * 16 + PX][c * 196 + ky * 14 + kx] = src[b * 196 + (y / 16) * 14 + x / 16][c * 256 + (y % 16) * 16 + x % 16]
+ *                            with (y, x) = (14 PY + ky, 14 PX + kx); columns 588..639 are written as zero
+ *      1 embed_rows_t257     acc f32 [n * 256, d] -> x bf16 [n * 257, d]: x[b * 257 + 1 + p] = bf16((acc[b * 256 + p] + bias) + pos[1 + p]),
+ *                            x[b * 257] = bf16(cls + pos[0]); pos f32 [257, d], f32 adds in that order
+ *      2 attn_mid            qkv bf16 [n * 257, 3 * 64 * heads] (Q | K | V, Q pre-scaled by dh^-0.5 log2 e) -> out bf16 [n * 257, 64 * heads];
+ *                            exact row maximum under every attention mode; only_block 0..8: rows 32 b .. 32 b + 31 of every crop only
+ *      3 pool_ln_l2 (257)    LayerNorm of row b * 257 + tok, then x / max(||x||, 1e-12), to emb_f32 and / or emb_bf16 [n, d]
+ *      4 rowscale            w [rows, cols] and factor [rows] of `dtype` -> prepared bf16 [rows, cols] = bf16_rne(f32(factor[r] * w[r, k]))
+ *      5 mul                 w [rows] and factor [rows] of `dtype` -> prepared f32 [rows] = f32(factor[r] * w[r])
+ * Preconditions (else MME_E_ARG, nothing launched): op 0..5; ops 0..3: 0 <= n <= 2^20, every tensor the op reads or writes
+ * non-null and 16-byte aligned (op 3: one of the two outputs may be NULL); op 0: src != dst; ops 1, 3: d == 384, 768 or 1024;
+ * op 2: heads == 6, 12 or 16, only_block in -1..8; op 3: 0 <= tok <= 256; ops 4, 5: dtype an MME_DT_*, 1 <= rows <= 2^24, w / factor /
+ * prepared non-null; op 4: w and prepared 16-byte aligned, cols a multiple of 8 in 8..65536. */
+typedef struct mme_dinov2_apply_args {
+    const uint16_t* src;    /* op 0 */
+    uint16_t* dst;
+    const float* acc;       /* op 1 */
+    const float* bias;
+    const float* pos;
+    const float* cls;
+    uint16_t* x;            /* op 1: out; op 3: in, bf16 rows of d */
+    const uint16_t* qkv;    /* op 2 */
+    uint16_t* out;
+    const float* gamma;     /* op 3 */
+    const float* beta;
+    float* emb_f32;
+    uint16_t* emb_bf16;
+    const void* w;          /* ops 4, 5 */
+    const void* factor;
+    void* prepared;
+    int64_t rows, cols;
+    int32_t n, d, heads, only_block, tok, dtype;
+    float eps;
+} mme_dinov2_apply_args;
+int mme_dinov2_apply(mme_ctx* ctx, int op, const mme_dinov2_apply_args* args, void* stream);
 
 /* Diagnostic: time the attention kernel (K5) on B crops of random activations (avg_ms over iters launches), then run
  * its stamped build once, both in the form mme_set_attention_mode selects (0: the exact kernel; 1 / 2: the fast one,

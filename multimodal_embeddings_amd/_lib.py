@@ -122,6 +122,20 @@ class _SiglipWeights(C.Structure):  # mme_siglip_weights
     _fields_ = [("vit", _Weights), ("probe", C.POINTER(C.c_float)), ("head", _Layer)]
 
 
+class _Dinov2Scale(C.Structure):  # mme_dinov2_scale
+    _fields_ = [("lambda1", C.POINTER(C.c_float)), ("lambda2", C.POINTER(C.c_float))]
+
+
+class _Dinov2Weights(C.Structure):  # mme_dinov2_weights
+    _fields_ = [("vit", _Weights), ("scale", C.POINTER(_Dinov2Scale))]
+
+
+class _Dinov2ApplyArgs(C.Structure):  # mme_dinov2_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "acc", "bias", "pos", "cls", "x", "qkv", "out", "gamma", "beta", "emb_f32", "emb_bf16", "w", "factor",
+                                          "prepared")] + [("rows", C.c_int64), ("cols", C.c_int64)] + [
+        (n, C.c_int32) for n in ("n", "d", "heads", "only_block", "tok", "dtype")] + [("eps", C.c_float)]
+
+
 class _SiglipApplyArgs(C.Structure):  # mme_siglip_apply_args
     _fields_ = [("gemm", C.POINTER(_GemmApplyArgs)), ("ran_256", C.POINTER(C.c_int32))] + [
         (n, C.c_void_p) for n in ("acc", "bias", "pos", "x", "kv", "q", "out", "emb_f32", "emb_bf16")] + [(n, C.c_int32) for n in ("n", "d", "heads")]
@@ -164,6 +178,9 @@ EXPORTS = {
     "mme_encoder_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_clip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_ClipApplyArgs), C.c_void_p]),
     "mme_vit32_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_Vit32ApplyArgs), C.c_void_p]),
+    "mme_load_dinov2": (C.c_int, [C.c_void_p, C.POINTER(_Dinov2Weights)]),
+    "mme_load_dinov2_as": (C.c_int, [C.c_void_p, C.POINTER(_Dinov2Weights), C.c_int, C.c_void_p]),
+    "mme_dinov2_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_Dinov2ApplyArgs), C.c_void_p]),
     "mme_load_siglip": (C.c_int, [C.c_void_p, C.POINTER(_SiglipWeights)]),
     "mme_load_siglip_as": (C.c_int, [C.c_void_p, C.POINTER(_SiglipWeights), C.c_int, C.c_void_p]),
     "mme_siglip_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_SiglipApplyArgs), C.c_void_p]),
@@ -425,13 +442,13 @@ class Engine:
         return ViTGeometry(image_size=g[0], patch_size=g[1], hidden_size=g[2], num_layers=g[3], num_heads=g[4], intermediate_size=g[5])
 
     def encoder_info(self) -> dict:
-        """What the last load brought (mme_encoder_info): {"kind": "vit" | "clip" | "siglip", "embed_dim", "hidden_act", "projection_dim"}."""
+        """What the last load brought (mme_encoder_info): {"kind": "vit" | "clip" | "siglip" | "dinov2", "embed_dim", "hidden_act", "projection_dim"}."""
         from .weights import CLIP_ACTS
 
         o = (C.c_int32 * 4)()
         self._check(self.lib.mme_encoder_info(self.h, o), "mme_encoder_info")
         acts = CLIP_ACTS + ("gelu_pytorch_tanh",)  # the library's act codes: 0, 1 (mme_clip_weights.act), 2 (SigLIP)
-        return {"kind": ("vit", "clip", "siglip")[o[0]], "embed_dim": int(o[1]), "hidden_act": acts[o[2]], "projection_dim": int(o[3]) or None}
+        return {"kind": ("vit", "clip", "siglip", "dinov2")[o[0]], "embed_dim": int(o[1]), "hidden_act": acts[o[2]], "projection_dim": int(o[3]) or None}
 
     @property
     def embed_dim(self) -> int:
@@ -588,6 +605,98 @@ class Engine:
 
         W, layers = self._siglip_struct(ckpt.geometry, arr)
         self._check(self.lib.mme_load_siglip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_siglip_as")
+
+    # ---- DINOv2 image towers (mme_load_dinov2*) ---------------------------------------------------------------
+    @staticmethod
+    def _dinov2_struct(geom, arr, pos):
+        """mme_dinov2_weights (+ the layer and scale arrays, which the caller keeps alive) for `geom` (weights.Dinov2Geometry),
+        tensor pointers from arr(name) over the names of weights.dinov2_tensor_specs; `pos`: pointer to the f32 [257, D] table."""
+        from .weights import dinov2_geometry_problem
+
+        bad = dinov2_geometry_problem(geom)
+        if bad and bad[0] in ("hidden_act", "use_swiglu_ffn", "num_register_tokens", "position_grid"):  # the fields the C struct does not carry
+            raise MmeError(f"{bad[0]} = {bad[1]!r}; supported: {bad[2]}")
+        layers = (_Layer * geom.num_layers)()
+        scales = (_Dinov2Scale * geom.num_layers)()
+        for i in range(geom.num_layers):
+            p = f"encoder.layer.{i}."
+            L = layers[i]
+            L.ln1_g, L.ln1_b = arr(p + "norm1.weight"), arr(p + "norm1.bias")
+            L.q_w, L.q_b = arr(p + "attention.attention.query.weight"), arr(p + "attention.attention.query.bias")
+            L.k_w, L.k_b = arr(p + "attention.attention.key.weight"), arr(p + "attention.attention.key.bias")
+            L.v_w, L.v_b = arr(p + "attention.attention.value.weight"), arr(p + "attention.attention.value.bias")
+            L.o_w, L.o_b = arr(p + "attention.output.dense.weight"), arr(p + "attention.output.dense.bias")
+            L.ln2_g, L.ln2_b = arr(p + "norm2.weight"), arr(p + "norm2.bias")
+            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
+            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
+            scales[i].lambda1, scales[i].lambda2 = arr(p + "layer_scale1.lambda1"), arr(p + "layer_scale2.lambda1")
+        W = _Dinov2Weights()
+        W.vit = _Weights(224, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size, float(geom.layer_norm_eps))
+        W.vit.cls_token = arr("embeddings.cls_token")
+        W.vit.pos_emb = pos
+        W.vit.patch_w = arr("embeddings.patch_embeddings.projection.weight")
+        W.vit.patch_b = arr("embeddings.patch_embeddings.projection.bias")
+        W.vit.lnf_g, W.vit.lnf_b = arr("layernorm.weight"), arr("layernorm.bias")
+        W.vit.layer = layers
+        W.scale = scales
+        return W, (layers, scales)
+
+    def load_dinov2(self, w: dict, geom=None):
+        """`weights.dinov2_tensor_specs` dict of f32 arrays (the state dict of transformers' Dinov2Model) -> this context,
+        replacing what it held.  `geom`: a weights.Dinov2Geometry; by default read off the tensor shapes, eps 1e-6.  The position
+        table (257 rows, or 1 + g * g of a g x g grid) is interpolated to 16 x 16 here, once, as the model does on every forward."""
+        import dataclasses
+
+        from .checkpoint import DINOV2_POSITIONS, interpolate_dinov2_positions
+        from .weights import dinov2_tensor_specs, infer_dinov2_geometry
+
+        try:
+            found = infer_dinov2_geometry(w)
+        except ValueError as e:
+            raise MmeError(f"load_dinov2: {e}") from e
+        geom = found if geom is None else dataclasses.replace(geom, position_grid=found.position_grid)
+        for name, shape, _ in dinov2_tensor_specs(geom) if 0 < geom.num_layers <= 64 else ():
+            if name not in w:
+                raise MmeError(f"load_dinov2: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"load_dinov2: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32)
+            keep.append(a)
+            return _fp(a)
+
+        pos = interpolate_dinov2_positions(self.torch.from_numpy(np.ascontiguousarray(w[DINOV2_POSITIONS], dtype=np.float32))).numpy()
+        keep.append(pos)
+        W, arrays = self._dinov2_struct(geom, arr, _fp(pos))
+        self._check(self.lib.mme_load_dinov2(self.h, C.byref(W)), "mme_load_dinov2")
+
+    def load_dinov2_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "dinov2")` -> this context, prepared on the device from the file's own f32 / bf16 /
+        f16 bytes, bit-identically to `load_dinov2` on the same values.  The position table is the checkpoint object's
+        interpolated f32 table under every dtype.  Replaces what the context held."""
+        if ckpt.encoder != "dinov2":
+            raise MmeError(f"load_dinov2_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        pos = ckpt.extra["position_table"]
+        W, arrays = self._dinov2_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name), C.cast(C.c_void_p(pos.data_ptr()), C.POINTER(C.c_float)))
+        self._check(self.lib.mme_load_dinov2_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_dinov2_as")
+
+    DINOV2_OPS = {"retile": 0, "embed_rows": 1, "attention": 2, "pool_ln_l2": 3, "rowscale": 4, "mul": 5}
+
+    def dinov2_apply(self, op, *, src=None, dst=None, acc=None, bias=None, pos=None, cls=None, x=None, qkv=None, out=None, gamma=None, beta=None,
+                     emb_f32=None, emb_bf16=None, w=None, factor=None, prepared=None, rows: int = 0, cols: int = 0, n: int = 0, d: int = 768,
+                     heads: int = 12, only_block: int = -1, tok: int = 0, dtype: int = 0, eps: float = 1e-6):
+        """ONE launch of a kernel a DINOv2 tower adds (ViT/14 @224: 256 patches, 257 tokens), on the caller's CUDA tensors
+        (mme_dinov2_apply; synchronous, works on a bare context).  op: a name of DINOV2_OPS or its code; `n` = crops; which
+        tensors each op reads is in include/mme.h.  The library validates."""
+        a = _Dinov2ApplyArgs()
+        a.src, a.dst, a.acc, a.bias, a.pos, a.cls, a.x = (self._ptr(t) for t in (src, dst, acc, bias, pos, cls, x))
+        a.qkv, a.out, a.gamma, a.beta, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (qkv, out, gamma, beta, emb_f32, emb_bf16))
+        a.w, a.factor, a.prepared = (self._ptr(t) for t in (w, factor, prepared))
+        a.rows, a.cols = int(rows), int(cols)
+        a.n, a.d, a.heads, a.only_block, a.tok, a.dtype, a.eps = int(n), int(d), int(heads), int(only_block), int(tok), int(dtype), float(eps)
+        self._check(self.lib.mme_dinov2_apply(self.h, int(self.DINOV2_OPS.get(op, op)), C.byref(a), self._stream()), "mme_dinov2_apply")
 
     # ---- CLIP text tower (mme_load_clip_text*): lives beside the image tower of the same context ----------------------------
     @staticmethod
@@ -1276,12 +1385,13 @@ class Engine:
 
     def preprocess(self, pix, offs, hw):
         """pix: uint8 CUDA tensor (concatenated HWC crops, >=16 spare bytes at the end).  -> bf16 patches of the loaded
-        geometry: [n * 196, 768] at patch 16, [n * 49, 3072] at patch 32 (the same bytes per crop)."""
+        geometry: [n * 196, 768] at patch 16, [n * 49, 3072] at patch 32 (the same bytes per crop), [n * 256, 640] at patch 14
+        (588 values of a patch, zero columns behind)."""
         t = self.torch
         offs, hw = self._crop_tables(offs, hw)
         n = len(offs)
         g = self.vit_geometry()
-        patches = t.empty((n * g.num_patches, g.patch_dim), dtype=t.bfloat16, device=pix.device)
+        patches = t.empty((n * g.num_patches, (g.patch_dim + 63) // 64 * 64), dtype=t.bfloat16, device=pix.device)
         self._check(self.lib.mme_preprocess(self.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, patches.data_ptr(), self._stream()), "mme_preprocess")
         return patches
 

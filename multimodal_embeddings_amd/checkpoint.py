@@ -9,13 +9,14 @@ never fetches: `read_checkpoint(path, encoder)` takes a directory that is alread
 -- checks that its configuration is a geometry the library is built for ("vit_b16": exactly ViT-B/16; "vit": any of the
 supported ViT/16 and ViT/32 @224 family, `weights.SUPPORTED_VIT`, read from config.json; "clip": a CLIP image tower of that family,
 `CLIPVisionModel[WithProjection]` or the vision half of a whole `CLIPModel`; "clip_text": a CLIP text tower,
-`CLIPTextModel[WithProjection]` or the text half of a whole `CLIPModel`; "siglip": a SigLIP ViT/16 @224 image tower with its
+`CLIPTextModel[WithProjection]` or the text half of a whole `CLIPModel`; "dinov2": a DINOv2 ViT/14 image tower (`Dinov2Model`:
+257 tokens at 224 pixels, LayerScale; the checkpoint's position table is interpolated to 16 x 16 here, once); "siglip": a SigLIP ViT/16 @224 image tower with its
 attention-pooling head, `SiglipVisionModel` or the vision half of a whole `SiglipModel`; "mllama_tiles": the tile tower), maps the tensor names to the canonical ones
 (`weights.vit_tensor_specs()` / `weights.tile_vit_tensor_specs()`) and returns the tensors IN THE FILE'S OWN DTYPE: a
 bf16 checkpoint stays bf16 on the host, and `Engine.load_vit_checkpoint` / `load_tile_vit_checkpoint` hand the raw
 bytes to the device, where they are converted and folded (csrc/weight_load.hip: DevPrep; kernels in csrc/weight_prep.hip).
 
-    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text|siglip_vit|siglip_text]
+    python -m multimodal_embeddings_amd.checkpoint DIR [--encoder vit_b16|vit|clip|mllama_tiles|clip_text|siglip_vit|siglip_text|dinov2]
 
 prints what a load would find (dtype, geometry, mean / std, tensor count, bytes): the offline "will this load" check.
 """
@@ -30,14 +31,14 @@ from dataclasses import dataclass, field
 
 from . import config
 from ._lib import MmeError
-from .weights import (CLIP_B16, CLIP_TEXT_B, SIGLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, SiglipGeometry, TileViTGeometry, ViTGeometry,
-                      clip_geometry_problem, clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, siglip_geometry_problem,
+from .weights import (CLIP_B16, CLIP_TEXT_B, DINOV2_B14, SIGLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, Dinov2Geometry, SiglipGeometry,
+                      TileViTGeometry, ViTGeometry, dinov2_geometry_problem, dinov2_tensor_specs, clip_geometry_problem, clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, siglip_geometry_problem,
                       siglip_tensor_specs, siglip_text_geometry_problem, siglip_text_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem,
                       vit_tensor_specs)
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip", "siglip_text")
+ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip", "siglip_text", "dinov2")
 # The command line below and RegionEmbedder spell the SigLIP tower "siglip_vit": both have always refused the bare name
 # "siglip" as an unknown encoder and keep doing so; read_checkpoint, Checkpoint.encoder and the Engine say "siglip".
 SIGLIP_ALIAS = "siglip_vit"
@@ -57,6 +58,7 @@ class Checkpoint:
     image_mean: tuple | None = None
     image_std: tuple | None = None
     source: list = field(default_factory=list)  # files read
+    extra: dict = field(default_factory=dict)   # "dinov2": {"position_table": f32 [257, D], the interpolated table the device holds}
 
     @property
     def dtype_id(self) -> int:
@@ -141,6 +143,38 @@ def canonical_siglip_name(key: str):
     if key.startswith(("embeddings.", "encoder.layers.", "post_layernorm.", "head.")):
         return "vision_model." + key
     return key
+
+
+DINOV2_POSITIONS = "embeddings.position_embeddings"
+
+
+def canonical_dinov2_name(key: str):
+    """Checkpoint key -> canonical name (`weights.dinov2_tensor_specs`: the keys of `Dinov2Model`), or None for what the tower
+    does not use: mask_token (read past), a classifier head."""
+    if key.startswith("dinov2."):  # Dinov2ForImageClassification / Dinov2Backbone keep the model under this prefix
+        key = key[7:]
+    if key.startswith("classifier.") or key == "embeddings.mask_token":
+        return None
+    return key
+
+
+def interpolate_dinov2_positions(table):
+    """The checkpoint's position table [1, 1 + g * g, D] (torch, any float type) -> f32 [257, D] for 224 x 224 pixels at patch 14:
+    what `Dinov2Embeddings.interpolate_pos_encoding` returns on every forward of an f32 model, bit for bit, computed once.  A
+    257-row table is taken as it is; else the class row is kept and the g x g patch grid goes through the model's own call,
+    `F.interpolate(f32, size=(16, 16), mode="bicubic", align_corners=False)`.  A patch part that is no square grid is refused."""
+    import torch
+
+    t = table.reshape(-1, table.shape[-1]).to(torch.float32)
+    rows, D = int(t.shape[0]), int(t.shape[1])
+    g = int(round((rows - 1) ** 0.5))
+    if rows < 2 or g * g != rows - 1:
+        raise MmeError(f"tensor {DINOV2_POSITIONS!r} has {rows} rows: the patch part ({rows - 1} rows) is no square grid")
+    if g == 16:
+        return t.contiguous()
+    patch = t[1:].reshape(1, g, g, D).permute(0, 3, 1, 2)
+    patch = torch.nn.functional.interpolate(patch, size=(16, 16), mode="bicubic", align_corners=False)
+    return torch.cat((t[:1], patch.permute(0, 2, 3, 1).reshape(256, D)), dim=0).contiguous()
 
 
 def canonical_siglip_text_name(key: str):
@@ -246,6 +280,35 @@ def _siglip_geometry(cfg: dict, where: str) -> SiglipGeometry:
     return g
 
 
+def _dinov2_geometry(cfg: dict, where: str) -> Dinov2Geometry:
+    """config.json of a DINOv2 checkpoint (Dinov2Config) -> geometry.  `image_size` there (518 for the released models) only
+    sizes the position table, which is read off the tensor; the engine runs 224 pixels.  A field the file leaves out has
+    Dinov2Config's default, except the sizes."""
+    b = DINOV2_B14
+    if "registers" in str(cfg.get("model_type", "")) or cfg.get("num_register_tokens", 0) not in (0, None):
+        raise MmeError(f"{where}: model_type = {cfg.get('model_type')!r}, num_register_tokens = {cfg.get('num_register_tokens', 0)!r}; supported: "
+                       "dinov2 with num_register_tokens = 0 (Dinov2WithRegisters is not run)")
+    for fld in ("patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads"):
+        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
+            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
+    ratio = cfg.get("mlp_ratio", 4)
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or ratio <= 0:
+        raise MmeError(f"{where}: mlp_ratio = {ratio!r}; a positive number is required")
+    F = int(cfg["hidden_size"] * ratio)
+    g = Dinov2Geometry(patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels), hidden_size=cfg["hidden_size"],
+                       num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"], intermediate_size=F,
+                       layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)), hidden_act=cfg.get("hidden_act", b.hidden_act),
+                       use_swiglu_ffn=cfg.get("use_swiglu_ffn", False))
+    bad = dinov2_geometry_problem(g)
+    if bad:
+        if bad[0] == "intermediate_size":
+            raise MmeError(f"{where}: mlp_ratio = {ratio!r} at hidden_size = {g.hidden_size} (an MLP of {F}); supported: mlp_ratio x hidden_size {bad[2]}")
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    _expect(cfg, "qkv_bias", True, where, default=True)
+    return g
+
+
 def _clip_text_geometry(cfg: dict, where: str, projection_dim) -> CLIPTextGeometry:
     """The text configuration of a CLIP checkpoint (CLIPTextConfig) -> geometry.  A field the file leaves out has
     CLIPTextConfig's default (clip-vit-base-patch16's text tower), as transformers reads it."""
@@ -313,7 +376,7 @@ def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
 
 
 RESIZE_RULES = ("fit_pad", "clip")  # _lib.Engine.RESIZE_RULES / MME_RESIZE_* (include/mme.h)
-CLIP_RULE_ENCODERS = ("vit_b16", "vit", "clip", "siglip")  # the single-tile encoders K1's "clip" rule feeds
+CLIP_RULE_ENCODERS = ("vit_b16", "vit", "clip", "siglip", "dinov2")  # the single-tile encoders K1's "clip" rule feeds
 
 
 def check_resize_rule(resize_rule, encoder: str) -> str:
@@ -361,6 +424,14 @@ def _read_preprocessor(path: str, encoder: str, resize_rule: str = "fit_pad"):
         return _mean_std(pc, where)
     resample = pc.get("resample", 2)
     clip_rule = encoder == "clip" and (resample == 3 or pc.get("do_center_crop") or "crop_size" in pc)
+    if encoder == "dinov2":
+        # DINOv2's processor (BitImageProcessor: shortest edge 256, BICUBIC, centre crop 224) is not a rule K1 has
+        if resample != 2 or pc.get("do_center_crop") or "crop_size" in pc:
+            named = [f"{k} = {pc[k]!r}" for k in ("image_processor_type", "resample", "size", "do_center_crop", "crop_size") if k in pc]
+            logger.warning(f"{where}: {', '.join(named) or 'the file'} asks for DINOv2's own preprocessing, a shortest-edge-256 BICUBIC resize and a "
+                           "224 x 224 centre crop; K1 does not run that rule: it keeps the aspect-preserving fit into 224 x 224 with zero padding "
+                           "(or resize_rule='clip' on request) and applies only the checkpoint's image_mean / image_std")
+        return _mean_std(pc, where)
     if encoder == "siglip":
         # SiglipImageProcessor resizes to size x size WITHOUT keeping the aspect (any resample): not a rule K1 has
         if "Siglip" in str(pc.get("image_processor_type", "")) or resample != 2:
@@ -509,6 +580,10 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         geometry = _siglip_geometry(vcfg, where)
         specs = [(n, s) for n, s, _ in siglip_tensor_specs(geometry)]
         canonical = canonical_siglip_name
+    elif encoder == "dinov2":
+        geometry = _dinov2_geometry(cfg, "config.json")
+        canonical = canonical_dinov2_name
+        specs = None  # after the tensors are read: the side of the position grid is the tensor's
     elif encoder == "clip_text":
         where, tcfg = "config.json", cfg
         if "text_config" in cfg:  # a whole CLIP model: projection_dim sits at the top level
@@ -551,6 +626,16 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         elif geometry.projection_dim is None:
             raise MmeError(f"{path}: the checkpoint holds {keys['text_projection.weight']!r} but {where} names no projection_dim")
         specs = [(n, s) for n, s, _ in clip_text_tensor_specs(geometry)]
+    elif encoder == "dinov2":
+        tensors, keys, files = _read_tensors(path, canonical, {n for n, _, _ in dinov2_tensor_specs(geometry)})
+        if DINOV2_POSITIONS in tensors:
+            rows = int(tensors[DINOV2_POSITIONS].shape[-2]) if tensors[DINOV2_POSITIONS].dim() >= 2 else 0
+            grid = int(round(max(rows - 1, 0) ** 0.5))
+            if rows < 2 or grid * grid != rows - 1:
+                raise MmeError(f"{path}: tensor {keys[DINOV2_POSITIONS]!r} has shape {tuple(tensors[DINOV2_POSITIONS].shape)}: the patch part "
+                               f"({rows - 1} rows) is no square grid")
+            geometry = dataclasses.replace(geometry, position_grid=grid)
+        specs = [(n, s) for n, s, _ in dinov2_tensor_specs(geometry)]
     elif encoder == "siglip_text":
         from .weights import SIGLIP_LOGIT_KEYS
 
@@ -578,7 +663,10 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
     if os.path.exists(pre_path) and encoder not in ("clip_text", "siglip_text"):  # a text tower reads no pixels
         mean, std = _read_preprocessor(pre_path, encoder, resize_rule)
         source.append(pre_path)
-    return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source)
+    extra = {}
+    if encoder == "dinov2":
+        extra["position_table"] = interpolate_dinov2_positions(tensors[DINOV2_POSITIONS])
+    return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source, extra=extra)
 
 
 def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = "float32", geometry=None, image_mean=None, image_std=None,
@@ -614,6 +702,14 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
                "dtype": dtype}
         if g.vision_use_head is not True:
             cfg["vision_use_head"] = g.vision_use_head
+    elif encoder == "dinov2":
+        g = geometry or DINOV2_B14
+        rows = int(np.shape(weights[DINOV2_POSITIONS])[-2]) if DINOV2_POSITIONS in weights else g.position_rows
+        ratio = g.intermediate_size / g.hidden_size
+        cfg = {"architectures": ["Dinov2Model"], "model_type": "dinov2", "image_size": g.patch_size * int(round((rows - 1) ** 0.5)),
+               "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers,
+               "num_attention_heads": g.num_heads, "mlp_ratio": int(ratio) if ratio == int(ratio) else ratio, "hidden_act": g.hidden_act,
+               "layer_norm_eps": g.layer_norm_eps, "qkv_bias": True, "use_swiglu_ffn": g.use_swiglu_ffn, "layerscale_value": 1.0, "dtype": dtype}
     elif encoder == "clip_text":
         g = geometry or CLIP_TEXT_B
         cfg = {"architectures": ["CLIPTextModelWithProjection" if g.projection_dim else "CLIPTextModel"], "model_type": "clip_text_model",

@@ -145,6 +145,7 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
 
 int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
     const bool t50 = c->geom.t50();  // patch 32: 50 tokens, its own patch embedding, attention and pooling kernels
+    const bool t257 = c->geom.t257();  // patch 14 (DINOv2): 257 tokens, the retiled K = 640 patch matrix, attention_mid.hip
     const bool sig = c->siglip;      // SigLIP: 196 tokens (no class token), tanh-GELU, the attention-pooling head behind the last block
     const int T = c->geom.tokens();
     const int M = n * T;
@@ -161,9 +162,10 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     P.zigzag = c->zigzag;  // mme_set_tile_order; only this tower alternates the walk (the patch embedding and the tails walk forwards)
     GemmArgs g{};
     int r;
-    if (t50) {
+    if (t50 || t257) {
         // patch 32: the patch-embed GEMM leaves f32 [n * 49, D] in the qkv buffer (dead until layer 0; 196 D n bytes of its
         // 300 D n), embed_rows adds bias and position rows, rounds once and writes the [CLS] rows in the same launch
+        // patch 14: the same with f32 [n * 256, D] (1024 D n bytes of the buffer's 1542 D n) and K = 640
         g.A = patches;
         g.W = c->patch_w;
         g.M = n * c->geom.np();
@@ -173,7 +175,8 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         g.ldf = D;
         if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_embed_rows((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, T, D, s));
+        if (t257) HIP_TRY(c, launch_embed_rows_t257((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
+        else HIP_TRY(c, launch_embed_rows((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, T, D, s));
     } else if (sig) {
         // no class token: patch row m IS token row m, but EPI_PATCH (and its interior-tile form) maps rows past the [CLS]
         // rows at compile time.  As at patch 32 the GEMM leaves f32 [n * 196, D] in the dead qkv buffer (784 D n of its
@@ -205,7 +208,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         if ((r = P.gemm(EPI_PATCH, g))) return r;
     }
     const GemmArgs patch_args = g;
-    if (!t50 && !sig) {
+    if (!t50 && !t257 && !sig) {
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, D, s));
     }
@@ -216,7 +219,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         // in the canonical order: the first folded LayerNorm needs neither planes nor another pass over x
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_pre_ln(c->x.p, c->pre_g, c->pre_b, M, D, c->ln_eps, (float*)c->stats.p, s));
-    } else if (!t50 && !sig && planes && gemm_runs_256(patch_args, c->gemm_variant)) {  // (patch 32, SigLIP: no planes from the f32 epilogue; the canonical pass below gives the same bits)
+    } else if (!t50 && !t257 && !sig && planes && gemm_runs_256(patch_args, c->gemm_variant)) {  // (patch 32, patch 14, SigLIP: no planes from the f32 epilogue; the canonical pass below gives the same bits)
         // first LayerNorm of the pass: the patch-embed epilogue left the partial sums of every token row an INTERIOR tile
         // wrote (patch rows [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th
         // row) and the rows of the ragged last tile take the stand-alone kernel, same canonical order
@@ -254,6 +257,9 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             if (t50) {  // exact kernel only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
                 if (P.zigzag != 2) P.next_dir();
                 HIP_TRY(c, launch_attention_t50(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
+            } else if (t257) {  // as patch 32: exact kernel only, no walk order
+                if (P.zigzag != 2) P.next_dir();
+                HIP_TRY(c, launch_attention_t257(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
             } else {
                 HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
                                             pruned ? pool_token / 32 : -1, P.zigzag == 2 ? true : P.next_dir() != 0, T));
@@ -363,7 +369,8 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
     }
     {
         Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
+        if (t257) HIP_TRY(c, launch_pool_t257(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
+        else HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
     }
     return MME_OK;
 }
@@ -601,7 +608,7 @@ void mme_destroy(mme_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (void* p : c->allocs) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->patches32};
+    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->patches32, &c->patches14};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->lut) (void)hipFree(c->lut);
@@ -625,7 +632,7 @@ int mme_vit_geometry(mme_ctx* c, int32_t out[6]) {
 
 int mme_encoder_info(mme_ctx* c, int32_t out[4]) {
     if (!c || !out) return fail(c, MME_E_ARG, "mme_encoder_info: null argument");
-    out[0] = c->siglip ? 2 : c->clip ? 1 : 0;
+    out[0] = c->dinov2 ? 3 : c->siglip ? 2 : c->clip ? 1 : 0;
     out[1] = embed_dim(c);
     out[2] = c->act;
     out[3] = c->proj_dim;
@@ -715,6 +722,7 @@ int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const 
     if (!qkv || !out || !redone) return fail(c, MME_E_ARG, "mme_attention_apply: null argument");
     if (kind != 0 && kind != 1) return fail(c, MME_E_ARG, "mme_attention_apply: kind %d (0 = ViT/16 at the context's geometry, 1 = tile-ViT)", kind);
     if (kind == 0 && c->geom.t50()) return fail(c, MME_E_ARG, "mme_attention_apply: kind 0 is the 197-token kernel and the context holds a patch-32 tower (50 tokens); mme_vit32_apply op 2 launches its kernel");
+    if (kind == 0 && c->geom.t257()) return fail(c, MME_E_ARG, "mme_attention_apply: kind 0 is the 197-token kernel and the context holds a patch-14 tower (257 tokens); mme_dinov2_apply op 2 launches its kernel");
     const int n_max = kind == 0 ? 1 << 20 : 4096;
     if (n <= 0 || n > n_max) return fail(c, MME_E_ARG, "mme_attention_apply: n = %d outside 1..%d", n, n_max);
     if (kind == 0) {
@@ -773,20 +781,23 @@ int mme_preprocess(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const in
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     // patch 32: K1 writes its patch-16 matrix into the staging buffer of one chunk, the retile kernel permutes it into the
-    // caller's [n * 49, 3072]; the bytes per crop are the same
-    const bool t50 = c->geom.t50();
+    // caller's [n * 49, 3072]; the bytes per crop are the same.  Patch 14: the same into the caller's [n * 256, 640]
+    const bool t50 = c->geom.t50(), t257 = c->geom.t257();
     int r;
-    if (t50 && (r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
+    if ((t50 || t257) && (r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
     // the crop tables of successive chunks reuse one device buffer: chunk so that stays ordered
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
         if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));
-        bf16_t* dst = (bf16_t*)patches + (size_t)s0 * CROP_VALUES;
-        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, t50 ? (bf16_t*)c->patches.p : dst, s);
+        bf16_t* dst = (bf16_t*)patches + (size_t)s0 * c->geom.crop_values();
+        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, t50 || t257 ? (bf16_t*)c->patches.p : dst, s);
         if (r) return r;
         if (t50) {
             Timed t(c, s, KC_PRE);
             HIP_TRY(c, launch_retile_p32(c->patches.p, dst, m, s));
+        } else if (t257) {
+            Timed t(c, s, KC_PRE);
+            HIP_TRY(c, launch_retile_p14(c->patches.p, dst, m, s));
         }
     }
     return MME_OK;
@@ -804,7 +815,7 @@ int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, 
     hipStream_t s = (hipStream_t)stream;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * CROP_VALUES, m, pool_token,
+        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * c->geom.crop_values(), m, pool_token,
                           emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
                           emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
         if (r) return r;
@@ -825,6 +836,8 @@ int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t
     if ((r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
     const bool t50 = c->geom.t50();  // patch 32: K1 -> retile -> pass
     if (t50 && (r = ensure(c, c->patches32, (size_t)c->chunk * CROP_VALUES * 2))) return r;
+    const bool t257 = c->geom.t257();  // patch 14: K1 -> retile -> pass
+    if (t257 && (r = ensure(c, c->patches14, (size_t)c->chunk * c->geom.crop_values() * 2))) return r;
     hipStream_t s = (hipStream_t)stream;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
@@ -834,8 +847,11 @@ int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t
         if (t50) {
             Timed t(c, s, KC_PRE);
             HIP_TRY(c, launch_retile_p32(c->patches.p, c->patches32.p, m, s));
+        } else if (t257) {
+            Timed t(c, s, KC_PRE);
+            HIP_TRY(c, launch_retile_p14(c->patches.p, c->patches14.p, m, s));
         }
-        r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : c->patches.p), m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
+        r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : t257 ? c->patches14.p : c->patches.p), m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
                           emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
         if (r) return r;
     }
@@ -1548,6 +1564,56 @@ int mme_vit32_apply(mme_ctx* c, int op, const mme_vit32_apply_args* a, void* str
         case 2: HIP_TRY(c, launch_attention_t50(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
         case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->n, 50, a->tok, a->d, a->eps, a->y, s)); break;
         default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->n, 50, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+// the kernels a DINOv2 tower (patch 14, 257 tokens) adds, one launch each (tests/test_gpu_dinov2.py)
+int mme_dinov2_apply(mme_ctx* c, int op, const mme_dinov2_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_dinov2_apply: null argument");
+    if (op < 0 || op > 5) return fail(c, MME_E_ARG, "mme_dinov2_apply: op %d outside 0..5", op);
+    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    const char* bad = nullptr;
+    if (op <= 3 && (a->n < 0 || a->n > (1 << 20))) return fail(c, MME_E_ARG, "mme_dinov2_apply: n = %d outside 0..2^20", a->n);
+    if (op == 0) {
+        if (!vec(a->src) || !vec(a->dst)) bad = "src and dst non-null and 16-byte aligned";
+        else if ((const void*)a->src == (const void*)a->dst) bad = "src != dst (the gather is not in place)";
+    } else if (op == 2) {
+        if (a->heads != 6 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_dinov2_apply: op 2 is built for heads == 6, 12 and 16 (heads = %d)", a->heads);
+        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv and out non-null and 16-byte aligned";
+        else if (a->only_block < -1 || a->only_block > 8) bad = "only_block in -1..8";
+    } else if (op == 1 || op == 3) {
+        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_dinov2_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
+        if (op == 1) {
+            if (!vec(a->acc) || !vec(a->bias) || !vec(a->pos) || !vec(a->cls) || !vec(a->x)) bad = "acc, bias, pos, cls, x non-null and 16-byte aligned";
+        } else {
+            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
+            else if (a->tok < 0 || a->tok > 256) bad = "0 <= tok <= 256";
+            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
+            else if (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
+        }
+    } else {
+        if (a->dtype < MME_DT_F32 || a->dtype > MME_DT_F16)
+            return fail(c, MME_E_ARG, "mme_dinov2_apply: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", a->dtype);
+        const size_t esz = a->dtype == MME_DT_F32 ? 4 : 2;
+        if (!a->w || !a->factor || !a->prepared || ((uintptr_t)a->factor % esz)) bad = "w, factor, prepared non-null, factor aligned to its element";
+        else if (a->rows < 1 || a->rows > ((int64_t)1 << 24)) bad = "1 <= rows <= 2^24";
+        else if (op == 4 && (!vec(a->w) || !vec(a->prepared))) bad = "w and prepared 16-byte aligned";
+        else if (op == 4 && (a->cols < 8 || (a->cols % 8) != 0 || a->cols > (1 << 16))) bad = "cols a multiple of 8 in 8..65536";
+        else if (op == 5 && (((uintptr_t)a->w % esz) || !aligned_to(a->prepared, 4))) bad = "w aligned to its element, prepared 4-byte aligned";
+    }
+    if (bad) return fail(c, MME_E_ARG, "mme_dinov2_apply: op %d needs %s", op, bad);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    switch (op) {
+        case 0: HIP_TRY(c, launch_retile_p14(a->src, a->dst, a->n, s)); break;
+        case 1: HIP_TRY(c, launch_embed_rows_t257(a->acc, a->bias, a->pos, a->cls, a->x, a->n, a->d, s)); break;
+        case 2: HIP_TRY(c, launch_attention_t257(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
+        case 3: HIP_TRY(c, launch_pool_t257(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+        case 4: HIP_TRY(c, launch_wp_rowscale(a->dtype, a->w, (size_t)a->rows, (size_t)a->cols, a->factor, a->prepared, s)); break;
+        default: HIP_TRY(c, launch_wp_mul(a->dtype, a->w, a->factor, (size_t)a->rows, (float*)a->prepared, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;

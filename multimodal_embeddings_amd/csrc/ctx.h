@@ -43,15 +43,20 @@ struct LayerDev {
 // <= 8192, 1..64 layers.
 // Patch 16 (197 tokens, the compile-time geometry of common.h) or patch 32 (50 tokens: patch32.hip, attention_short.hip).
 // no_cls: a tower without a class token (SigLIP, patch 16 only): 196 tokens (siglip.hip, attention.hip at T = 196).
+// Patch 14 (DINOv2 only, mme_load_dinov2: validate_vit_weights refuses it for every other loader): 16 x 16 patches, 257
+// tokens (dinov2.hip, attention_mid.hip); the im2col row of 588 is padded to 640, the GEMM's multiple of 64.
 struct VitGeom {
     int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
     int patch = VIT_PATCH;
     bool no_cls = false;
     int grid() const { return VIT_IMG / patch; }
-    int np() const { return grid() * grid(); }             // patches per crop: 196 or 49
-    int tokens() const { return np() + (no_cls ? 0 : 1); } // 197 or 50; 196 without a class token
-    int patch_dim() const { return 3 * patch * patch; }    // 768 or 3072; np() * patch_dim() is 150 528 for both
+    int np() const { return grid() * grid(); }             // patches per crop: 196, 49 or 256
+    int tokens() const { return np() + (no_cls ? 0 : 1); } // 197, 50 or 257; 196 without a class token
+    int patch_elems() const { return 3 * patch * patch; }  // the checkpoint's im2col row: 768, 3072 or 588
+    int patch_dim() const { return (patch_elems() + 63) & ~63; }  // K of the patch-embed GEMM: 768, 3072 or 640
+    size_t crop_values() const { return (size_t)np() * patch_dim(); }  // bf16 values of one crop's patch matrix: 150 528 at patch 16 and 32, 163 840 at patch 14
     bool t50() const { return patch == 32; }
+    bool t257() const { return patch == 14; }
 };
 
 enum KClass { KC_PRE = 0, KC_GEMM = 1, KC_LN = 2, KC_ATTN = 3, KC_POOL = 4, KC_COS = 5, KC_PAGE = 6, KC_CLUSTER = 7, KC_NEIGH = 8, KC_COMM = 9 };
@@ -94,6 +99,7 @@ struct mme_ctx {
     // and whose ln2 / fc1 / fc2 are the head's layernorm and MLP; head_q [D] f32 is the constant query
     // (probe . W_q^T + b_q) dh^-0.5 log2 e.  head.ln1_g / ln1_b are not set (ln_mode 0 normalises with lnf_g / lnf_b).
     bool siglip = false;
+    bool dinov2 = false;  // the last load was a DINOv2 load (mme_encoder_info kind 3): patch 14, LayerScale folded into o_w / o_b / fc2_w / fc2_b
     LayerDev head{};
     float* head_q = nullptr;
     float* lut = nullptr;  // [3,256]
@@ -108,6 +114,7 @@ struct mme_ctx {
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
     DevBuf patches32;      // patch 32: the retiled [chunk * 49, 3072] matrix of mme_embed (`patches` stages K1's patch-16 matrix)
+    DevBuf patches14;      // patch 14: the retiled [chunk * 256, 640] matrix of mme_embed
     DevBuf pooled, projf;  // CLIP tail: bf16 [chunk, hidden] post_layernorm rows, f32 [chunk, proj_dim] projected rows
                            // SigLIP tail: pooled = bf16 [2][chunk, hidden] (map_pool's rows, then the head's residual rows)
     // host staging for crop tables
@@ -203,6 +210,10 @@ struct HostPrep {
     // [rows, cols] -> bf16 [rows, cols_padded], zero columns behind
     int padded(const void* src, int rows, int cols, int cols_padded, bf16_t** dst);
     int zeros(size_t n, float** dst);
+    // bf16 matrix with a per-row f32 factor: dst[n, k] = bf16_rne(f32(factor[n] * src[n, k])); cols a multiple of 8
+    int rowscaled(const void* src, size_t rows, size_t cols, const void* factor, bf16_t** dst);
+    // f32 table dst[i] = f32(factor[i] * src[i])
+    int table_mul(const void* src, const void* factor, size_t n, float** dst);
 };
 
 // The checkpoint's bytes on the device for the duration of one load.  Two walks over the tensors with the same calls:
@@ -248,6 +259,10 @@ struct DevPrep {
     int folded(const WpFoldSrc* srcs, const size_t* rows, int nsrc, size_t cols, const void* gamma, const void* beta, bf16_t** wf, float** cs, float** bf);
     int padded(const void* src, int rows, int cols, int cols_padded, bf16_t** dst);
     int zeros(size_t n, float** dst);
+    // bf16 matrix with a per-row f32 factor: dst[n, k] = bf16_rne(f32(factor[n] * src[n, k])); cols a multiple of 8
+    int rowscaled(const void* src, size_t rows, size_t cols, const void* factor, bf16_t** dst);
+    // f32 table dst[i] = f32(factor[i] * src[i])
+    int table_mul(const void* src, const void* factor, size_t n, float** dst);
 };
 
 struct Timed {

@@ -309,6 +309,19 @@ hipError_t launch_retile_p32(const void* patches16, void* patches32, int n, hipS
 // maximum; only_block = 0 or 1: that query block of 32 only
 hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
 
+// ---- ViT/14 @224 image towers (DINOv2; dinov2.hip, attention_mid.hip): 16 x 16 patches of 14 x 14, 257 tokens, heads of 64
+// K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-14 matrix [n * 256, 640] in conv order (c, ky, kx), columns 588..639
+// zero on every launch: a 2-byte gather
+hipError_t launch_retile_p14(const void* patches16, void* patches14, int n, hipStream_t s);
+// launch_embed_rows at 257 tokens / 256 patches with a class row (cls non-null, else hipErrorInvalidValue)
+hipError_t launch_embed_rows_t257(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int d, hipStream_t s);
+// launch_pool at 257 tokens: 0 <= tok <= 256
+hipError_t launch_pool_t257(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
+                            hipStream_t s);
+// attention, T = 257, dh = 64, heads = 6, 12 or 16: qkv [n*257, 3*64*heads] (Q pre-scaled) -> out [n*257, 64*heads], exact row
+// maximum; only_block = 0..8: that query block of 32 only
+hipError_t launch_attention_t257(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
+
 // ---- SigLIP ViT/16 @224 image towers (siglip.hip; attention: launch_attention with tokens = 196; launch_embed_rows without a
 // class row; launch_l2_rows_bf16 behind the head): 196 tokens, no class token
 // attention pooling: kv bf16 [n*196, 2*64*heads] (K | V), q f32 [64*heads] (pre-scaled by dh^-0.5 log2 e, the same for every
@@ -330,5 +343,9 @@ struct WpFoldSrc {
 };
 // LayerNorm folding of up to three row blocks (rows[i] multiples of 64; cols a multiple of 64, <= 1280):
 // wf bf16 [sum rows, cols], cs / bf f32 [sum rows]; sums over k ascending in f64, a row per thread
+// [rows, cols] (cols a multiple of 8) times a per-row factor: dst bf16 [rows, cols] = bf16_rne(f32(factor[row] * src[row, col]))
+hipError_t launch_wp_rowscale(int dt, const void* src, size_t rows, size_t cols, const void* factor, void* dst_bf16, hipStream_t s);
+// f32 table dst[i] = f32(factor[i] * src[i]), any n
+hipError_t launch_wp_mul(int dt, const void* src, const void* factor, size_t n, float* dst, hipStream_t s);
 hipError_t launch_wp_fold(int dt, const WpFoldSrc* srcs, const size_t* rows, int nsrc, int cols, const void* gamma, const void* beta, void* wf, float* cs,
                           float* bf, hipStream_t s);

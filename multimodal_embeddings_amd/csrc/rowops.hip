@@ -353,6 +353,16 @@ hipError_t launch_embed_rows(const float* acc, const float* bias, const float* p
     return hipGetLastError();
 }
 
+// the same rows at 257 tokens / 256 patches with a class row (ViT/14 @224): a launcher of its own, launch_embed_rows keeps its set
+hipError_t launch_embed_rows_t257(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int d, hipStream_t s) {
+    if (!vit_width_built(d) || !cls) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    const int64_t rows = (int64_t)n * 257;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<257>{})
+    return hipGetLastError();
+}
+
 // the token layouts of the image path whose pooled row the final LayerNorm reads
 static bool pool_row_ok(int tokens, int tok) { return (tokens == VIT_T || tokens == 50) && tok >= 0 && tok < tokens; }
 
@@ -361,6 +371,15 @@ hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int
     if (!vit_width_built(d) || !pool_row_ok(tokens, tok)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
     ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tokens, tok, eps, emb_f32, (bf16_t*)emb_bf16)
+    return hipGetLastError();
+}
+
+// launch_pool at 257 tokens (ViT/14 @224), 0 <= tok <= 256: a launcher of its own, launch_pool keeps its set
+hipError_t launch_pool_t257(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
+                            hipStream_t s) {
+    if (!vit_width_built(d) || tok < 0 || tok > 256) return hipErrorInvalidValue;
+    if (B <= 0) return hipSuccess;
+    ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, 257, tok, eps, emb_f32, (bf16_t*)emb_bf16)
     return hipGetLastError();
 }
 

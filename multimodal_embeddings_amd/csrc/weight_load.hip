@@ -120,6 +120,21 @@ int HostPrep::padded(const void* src, int rows, int cols, int cols_padded, bf16_
     return upload(c, h.data(), h.size(), dst);
 }
 
+int HostPrep::rowscaled(const void* src, size_t rows, size_t cols, const void* factor, bf16_t** dst) {
+    std::vector<uint16_t> h(rows * cols);
+    for (size_t n = 0; n < rows; ++n) {
+        const float f = ((const float*)factor)[n];
+        for (size_t k = 0; k < cols; ++k) h[n * cols + k] = f32_to_bf16_rne(f * ((const float*)src)[n * cols + k]);
+    }
+    return upload(c, h.data(), h.size(), dst);
+}
+
+int HostPrep::table_mul(const void* src, const void* factor, size_t n, float** dst) {
+    std::vector<float> h(n);
+    for (size_t i = 0; i < n; ++i) h[i] = f32_quiet_nan(((const float*)factor)[i] * ((const float*)src)[i]);
+    return upload(c, h.data(), n, dst);
+}
+
 int HostPrep::zeros(size_t n, float** dst) {
     std::vector<float> z(n, 0.f);
     return upload(c, z.data(), n, dst);
@@ -208,6 +223,20 @@ int DevPrep::padded(const void* src, int rows, int cols, int cols_padded, bf16_t
     return MME_OK;
 }
 
+int DevPrep::rowscaled(const void* src, size_t rows, size_t cols, const void* factor, bf16_t** dst) {
+    int r;
+    if ((r = alloc_weight(c, rows * cols, dst))) return r;
+    HIP_TRY(c, launch_wp_rowscale(dt, src, rows, cols, factor, *dst, s));
+    return MME_OK;
+}
+
+int DevPrep::table_mul(const void* src, const void* factor, size_t n, float** dst) {
+    int r;
+    if ((r = alloc_weight(c, n, dst))) return r;
+    HIP_TRY(c, launch_wp_mul(dt, src, factor, n, *dst, s));
+    return MME_OK;
+}
+
 int DevPrep::zeros(size_t n, float** dst) {
     int r;
     if ((r = alloc_weight(c, n, dst))) return r;
@@ -221,12 +250,15 @@ namespace {
 // argument checks of both ViT loaders (the messages of both name the f32 loader): the geometry against the supported
 // set, every tensor pointer.  Touches nothing in the context but its error text.
 // no_cls: a tower without a class token (SigLIP): patch 16 only, cls_token NULL
-int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who = "mme_load_vit", bool bias_free_patch = false, bool no_cls = false) {
+// p14: the DINOv2 loader, patch 14 only; every other loader keeps refusing patch 14
+int validate_vit_weights(mme_ctx* c, const mme_vit_weights* w, const char* who = "mme_load_vit", bool bias_free_patch = false, bool no_cls = false,
+                         bool p14 = false) {
     if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
     // every refusal names the field, the value found and what is supported
     if (w->image_size != VIT_IMG) return fail(c, MME_E_ARG, "%s: image_size = %d; supported: %d", who, w->image_size, VIT_IMG);
     if (no_cls && w->patch_size != 16) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 16", who, w->patch_size);
-    if (w->patch_size != 16 && w->patch_size != 32) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 16, 32", who, w->patch_size);
+    if (p14 && w->patch_size != 14) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 14", who, w->patch_size);
+    if (!p14 && w->patch_size != 16 && w->patch_size != 32) return fail(c, MME_E_ARG, "%s: patch_size = %d; supported: 16, 32", who, w->patch_size);
     if (!vit_width_built(w->hidden)) return fail(c, MME_E_ARG, "%s: hidden = %d; supported: 384, 768, 1024", who, w->hidden);
     if (w->heads * VIT_DH != w->hidden)
         return fail(c, MME_E_ARG, "%s: heads = %d at hidden = %d; supported: heads of %d, heads = hidden / %d = %d", who, w->heads, w->hidden, VIT_DH, VIT_DH,
@@ -265,6 +297,7 @@ int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     c->pre_g = c->pre_b = nullptr;
     c->proj_w = nullptr;
     c->siglip = false;
+    c->dinov2 = false;
     c->head = LayerDev{};
     c->head_q = nullptr;
     return MME_OK;
@@ -276,13 +309,14 @@ void end_vit_load(mme_ctx* c, bool ok) {
 }
 
 // every tensor of the checkpoint with its element count (the order of the staged bytes)
+// pos_on_host: the position table is not staged (DINOv2: the loader's interpolated f32 table, whatever the checkpoint's type)
 template <class Fn>
-void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&& f) {
+void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&& f, bool pos_on_host = false) {
     const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
     const VitGeom vg{w.hidden, w.layers, w.heads, w.mlp, w.patch_size, w.cls_token == nullptr};
     if (w.cls_token) f(w.cls_token, D);  // SigLIP: no class token
-    f(w.pos_emb, (size_t)vg.tokens() * D);
-    f(w.patch_w, D * vg.patch_dim());
+    if (!pos_on_host) f(w.pos_emb, (size_t)vg.tokens() * D);
+    f(w.patch_w, D * vg.patch_elems());
     if (w.patch_b) f(w.patch_b, D);  // CLIP: no bias on the patch projection
     f(w.lnf_g, D);
     f(w.lnf_b, D);
@@ -300,8 +334,11 @@ void each_vit_tensor(mme_vit_weights& w, std::vector<mme_vit_layer>& layer, Fn&&
 
 // The prepared buffers of the ViT/16 encoder, in the order mme_weights_fingerprint reports them: cls, pos, patch_b, lnf_g,
 // lnf_b, patch_w, then 18 per layer.
+// ls (DINOv2 only, [layers]): LayerScale folded into the projection it follows, o_w' = bf16(lambda1 * o_w), o_b' = lambda1 * o_b and
+// the same for fc2 with lambda2 (the block then runs unchanged); the position table is the caller's host f32 under both
+// preparers, and patch_w [D, 588] is padded to [D, 640].  The order and the count of the buffers are the ViT's.
 template <class P>
-int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
+int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w, const mme_dinov2_scale* ls = nullptr) {
     int r;
     const size_t D = (size_t)w.hidden, F = (size_t)w.mlp;
     const size_t rD[3] = {D, D, D}, rF[1] = {F};
@@ -312,11 +349,16 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
         return p.bf16(s, rows, 1, cols, 1.f, false, dst);
     };
     if ((r = w.cls_token ? plain(w.cls_token, D, &c->cls) : p.zeros(D, &c->cls))) return r;  // SigLIP: a zero table, never read
-    if ((r = plain(w.pos_emb, (size_t)vg.tokens() * D, &c->pos))) return r;
+    if (ls) {
+        HostPrep hp{c};
+        if ((r = hp.table(w.pos_emb, (size_t)vg.tokens() * D, 1.f, false, &c->pos))) return r;
+    } else if ((r = plain(w.pos_emb, (size_t)vg.tokens() * D, &c->pos))) return r;
     if ((r = w.patch_b ? plain(w.patch_b, D, &c->patch_b) : p.zeros(D, &c->patch_b))) return r;  // CLIP: a zero table
     if ((r = plain(w.lnf_g, D, &c->lnf_g))) return r;
     if ((r = plain(w.lnf_b, D, &c->lnf_b))) return r;
-    if ((r = plain_bf16(w.patch_w, rD, (size_t)vg.patch_dim(), &c->patch_w))) return r;
+    if (vg.t257()) {
+        if ((r = p.padded(w.patch_w, (int)D, vg.patch_elems(), vg.patch_dim(), &c->patch_w))) return r;
+    } else if ((r = plain_bf16(w.patch_w, rD, (size_t)vg.patch_dim(), &c->patch_w))) return r;
     // The attention kernel takes its scores in log2 units straight from the matrix pipe (attention.hip, PRESCALED):
     // dh^-0.5 * log2(e) is folded into the query projection here, once, BEFORE the rounding to bf16 that the preparation
     // applies anyway -- softmax(q.k / 8) = exp2(q'.k - c) / sum with q' = (W_q' x + b_q'), W_q' = sc W_q, b_q' = sc b_q.
@@ -334,14 +376,14 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w) {
         if ((r = p.table_cat(qkvb, rD, 3, sc, true, &L.qkv_b))) return r;
         const WpFoldSrc fq[3] = {{a.q_w, a.q_b, sc, 1}, {a.k_w, a.k_b, 1.f, 0}, {a.v_w, a.v_b, 1.f, 0}};
         if ((r = p.folded(fq, rD, 3, D, a.ln1_g, a.ln1_b, &L.w.qkv_wf, &L.w.qkv_cs, &L.w.qkv_bf))) return r;
-        if ((r = plain_bf16(a.o_w, rD, D, &L.w.o_w))) return r;
-        if ((r = plain(a.o_b, D, &L.w.o_b))) return r;
+        if ((r = ls ? p.rowscaled(a.o_w, D, D, ls[l].lambda1, &L.w.o_w) : plain_bf16(a.o_w, rD, D, &L.w.o_w))) return r;
+        if ((r = ls ? p.table_mul(a.o_b, ls[l].lambda1, D, &L.w.o_b) : plain(a.o_b, D, &L.w.o_b))) return r;
         if ((r = plain_bf16(a.fc1_w, rF, D, &L.fc1_w))) return r;
         if ((r = plain(a.fc1_b, F, &L.fc1_b))) return r;
         const WpFoldSrc f1[1] = {{a.fc1_w, a.fc1_b, 1.f, 0}};
         if ((r = p.folded(f1, rF, 1, D, a.ln2_g, a.ln2_b, &L.w.fc1_wf, &L.w.fc1_cs, &L.w.fc1_bf))) return r;
-        if ((r = plain_bf16(a.fc2_w, rD, F, &L.w.fc2_w))) return r;
-        if ((r = plain(a.fc2_b, D, &L.w.fc2_b))) return r;
+        if ((r = ls ? p.rowscaled(a.fc2_w, D, F, ls[l].lambda2, &L.w.fc2_w) : plain_bf16(a.fc2_w, rD, F, &L.w.fc2_w))) return r;
+        if ((r = ls ? p.table_mul(a.fc2_b, ls[l].lambda2, D, &L.w.fc2_b) : plain(a.fc2_b, D, &L.w.fc2_b))) return r;
     }
     return MME_OK;
 }
@@ -509,9 +551,56 @@ int load_siglip(mme_ctx* c, const mme_siglip_weights* w, P p) {
     return r;
 }
 
+// ---- DINOv2 image tower: the ViT sequence at patch 14 with LayerScale folded in ---------------------------------------------------
+int validate_dinov2_weights(mme_ctx* c, const mme_dinov2_weights* w) {
+    const char* who = "mme_load_dinov2";
+    if (!c || !w) return fail(c, MME_E_ARG, "%s: null argument", who);
+    int r;
+    if ((r = validate_vit_weights(c, &w->vit, who, false, false, true))) return r;
+    if (!w->scale) return fail(c, MME_E_ARG, "%s: scale is a null pointer", who);
+    for (int l = 0; l < w->vit.layers; ++l)
+        if (!w->scale[l].lambda1 || !w->scale[l].lambda2) return fail(c, MME_E_ARG, "%s: layer %d has a null LayerScale pointer", who, l);
+    return MME_OK;
+}
+
+template <class P>
+int load_dinov2(mme_ctx* c, const mme_dinov2_weights* w, P p) {
+    int r;
+    if ((r = begin_vit_load(c, &w->vit))) return r;
+    std::vector<mme_vit_layer> layer(w->vit.layer, w->vit.layer + w->vit.layers);
+    std::vector<mme_dinov2_scale> scale(w->scale, w->scale + w->vit.layers);
+    mme_vit_weights v = w->vit;
+    v.layer = layer.data();
+    r = p.stage([&](auto& put) {
+        each_vit_tensor(v, layer, put, true);
+        for (mme_dinov2_scale& sc : scale) {
+            put(sc.lambda1, (size_t)v.hidden);
+            put(sc.lambda2, (size_t)v.hidden);
+        }
+    });
+    if (r == MME_OK) r = prepare_vit(c, p, v, scale.data());
+    r = p.finish(r);
+    if (r == MME_OK) c->dinov2 = true;
+    end_vit_load(c, r == MME_OK);
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mme_load_dinov2(mme_ctx* c, const mme_dinov2_weights* w) {
+    int r;
+    if ((r = validate_dinov2_weights(c, w))) return r;
+    return load_dinov2(c, w, HostPrep{c});
+}
+
+int mme_load_dinov2_as(mme_ctx* c, const mme_dinov2_weights* w, int dtype, void* stream) {
+    int r;
+    if ((r = validate_dinov2_weights(c, w))) return r;
+    if ((r = check_load_dtype(c, dtype, "mme_load_dinov2_as"))) return r;
+    return load_dinov2(c, w, DevPrep(c, dtype, stream, "mme_load_dinov2_as"));
+}
 
 int mme_load_siglip(mme_ctx* c, const mme_siglip_weights* w) {
     int r;

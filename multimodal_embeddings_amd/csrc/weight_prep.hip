@@ -5,6 +5,8 @@
 //   convert  dtype -> f32 (exact), optional f32 scale, -> f32 table or -> bf16 (round to nearest even); a NaN leaves quiet;
 //            the parts of a concatenated buffer (Q | K | V) are one launch each into their slice of it
 //   pad      [rows, cols] -> bf16 [rows, cols_padded], zero columns behind
+//   rowscale [rows, cols] times a per-row factor (LayerScale folded into the projection it follows): f32(factor[row] * w), then
+//            -> bf16 (round to nearest even); mul is the same product element by element as an f32 table (the bias)
 //   fold     LayerNorm folding: W' = bf16(w * gamma), colsum = sum_k W', bias' = b + sum_k w * beta; the two sums run over k
 //            ASCENDING in one f64 accumulator per output row (a row per thread; a tree reduction would change the order)
 //   fingerprint  position-dependent 64-bit checksum of a buffer's bytes (integer adds: the reduction order is free)
@@ -142,6 +144,34 @@ __global__ __launch_bounds__(WP_THREADS) void pad_kernel(const void* src, int ro
         o.y = bf16_rne_bits(v[2]) | (bf16_rne_bits(v[3]) << 16);
         *(uint2*)(dst + (size_t)r * colsp + k) = o;
     }
+}
+
+// one element of `dt` -> f32 (exact)
+template <int DT>
+__device__ __forceinline__ float load1(const void* base, size_t elem) {
+    if (DT == MME_DT_F32) return ((const float*)base)[elem];
+    if (DT == MME_DT_BF16) return __uint_as_float((uint32_t)((const uint16_t*)base)[elem] << 16);
+    return (float)((const _Float16*)base)[elem];
+}
+
+// chunks of 8 elements of a [rows, cols] matrix (cols % 8 == 0: a chunk lies in one row), each times its row's factor
+template <int DT>
+__global__ __launch_bounds__(WP_THREADS) void rowscale_kernel(const void* src, unsigned long long chunks, unsigned long long cols, const void* factor,
+                                                              void* dst) {
+    for (unsigned long long c = (unsigned long long)blockIdx.x * WP_THREADS + threadIdx.x; c < chunks; c += (unsigned long long)gridDim.x * WP_THREADS) {
+        float v[8];
+        load8<DT>(src, (size_t)c * 8, v);
+        const float f = load1<DT>(factor, (size_t)(c * 8 / cols));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = f * v[j];  // rounded to f32 here (as HostPrep::rowscaled)
+        ((u32x4*)dst)[c] = pack8_bf16(v);
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(WP_THREADS) void mul_kernel(const void* src, const void* factor, unsigned long long n, float* dst) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * WP_THREADS + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * WP_THREADS)
+        dst[i] = __uint_as_float(quiet_nan_bits(__float_as_uint(load1<DT>(factor, i) * load1<DT>(src, i))));
 }
 
 // ---- fold --------------------------------------------------------------------------------------------------------------
@@ -324,6 +354,30 @@ hipError_t launch_wp_pad(int dt, const void* src, int rows, int cols, int cols_p
     if (dt == MME_DT_F32) pad_kernel<MME_DT_F32><<<grid, WP_THREADS, 0, s>>>(src, rows, cols, cols_padded, (uint16_t*)dst_bf16);
     else if (dt == MME_DT_BF16) pad_kernel<MME_DT_BF16><<<grid, WP_THREADS, 0, s>>>(src, rows, cols, cols_padded, (uint16_t*)dst_bf16);
     else pad_kernel<MME_DT_F16><<<grid, WP_THREADS, 0, s>>>(src, rows, cols, cols_padded, (uint16_t*)dst_bf16);
+    return hipGetLastError();
+}
+
+hipError_t launch_wp_rowscale(int dt, const void* src, size_t rows, size_t cols, const void* factor, void* dst_bf16, hipStream_t s) {
+    const size_t esz = dt == MME_DT_F32 ? 4 : 2;
+    if (dt < MME_DT_F32 || dt > MME_DT_F16 || rows < 1 || cols < 8 || cols % 8 || ((uintptr_t)src & 15) || ((uintptr_t)dst_bf16 & 15) || !factor ||
+        ((uintptr_t)factor % esz))
+        return hipErrorInvalidValue;
+    const unsigned long long chunks = (unsigned long long)rows * cols / 8;
+    const int grid = grid_for(chunks);
+    if (dt == MME_DT_F32) rowscale_kernel<MME_DT_F32><<<grid, WP_THREADS, 0, s>>>(src, chunks, cols, factor, dst_bf16);
+    else if (dt == MME_DT_BF16) rowscale_kernel<MME_DT_BF16><<<grid, WP_THREADS, 0, s>>>(src, chunks, cols, factor, dst_bf16);
+    else rowscale_kernel<MME_DT_F16><<<grid, WP_THREADS, 0, s>>>(src, chunks, cols, factor, dst_bf16);
+    return hipGetLastError();
+}
+
+hipError_t launch_wp_mul(int dt, const void* src, const void* factor, size_t n, float* dst, hipStream_t s) {
+    const size_t esz = dt == MME_DT_F32 ? 4 : 2;
+    if (dt < MME_DT_F32 || dt > MME_DT_F16 || !src || !factor || !dst || ((uintptr_t)src % esz) || ((uintptr_t)factor % esz)) return hipErrorInvalidValue;
+    if (!n) return hipSuccess;
+    const int grid = grid_for(n);
+    if (dt == MME_DT_F32) mul_kernel<MME_DT_F32><<<grid, WP_THREADS, 0, s>>>(src, factor, n, dst);
+    else if (dt == MME_DT_BF16) mul_kernel<MME_DT_BF16><<<grid, WP_THREADS, 0, s>>>(src, factor, n, dst);
+    else mul_kernel<MME_DT_F16><<<grid, WP_THREADS, 0, s>>>(src, factor, n, dst);
     return hipGetLastError();
 }
 

@@ -172,7 +172,10 @@ class RegionEmbedder:
         transformers' names, whose activation `geometry=` names when it is not QuickGELU), "siglip_vit" (a SigLIP ViT/16 @224 image
         tower: 196 tokens, tanh-GELU, the attention-pooling head; a checkpoint directory of SiglipVisionModel or a whole
         SiglipModel, seeded weights at `geometry=` a weights.SiglipGeometry, default SigLIP-B/16, or a `weights=` dict in
-        transformers' names; `pool` must stay at its default, the head pools) or "mllama_tiles".
+        transformers' names; `pool` must stay at its default, the head pools), "dinov2" (a DINOv2 ViT/14 @224 image tower:
+        257 tokens, LayerScale, `pooler_output`; a checkpoint directory of Dinov2Model -- dinov2-small, -base, -large -- whose
+        position table is interpolated to 16 x 16 once at load, seeded weights at `geometry=` a weights.Dinov2Geometry, default
+        weights.DINOV2_B14, or a `weights=` dict in transformers' names; it has no text tower) or "mllama_tiles".
         `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim).
         `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
         fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
@@ -194,10 +197,10 @@ class RegionEmbedder:
         self.torch = torch
         self.model_name = model_name
         self.checkpoint = None
-        if encoder not in ("vit_b16", "vit", "clip", "siglip_vit", "mllama_tiles"):
+        if encoder not in ("vit_b16", "vit", "clip", "siglip_vit", "dinov2", "mllama_tiles"):
             raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16), 'vit' (the ViT/16 family: ViT-S, -B and -L widths), "
-                             "'clip' (a CLIP ViT/16 image tower of that family), 'siglip_vit' (a SigLIP ViT/16 image tower of that family) or "
-                             "'mllama_tiles' (the checkpoint's own vision-tower geometry)")
+                             "'clip' (a CLIP ViT/16 image tower of that family), 'siglip_vit' (a SigLIP ViT/16 image tower of that family), "
+                             "'dinov2' (a DINOv2 ViT/14 image tower) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
         if encoder == "siglip_vit" and pool != "cls":
             raise ValueError(f"pool = {pool!r}: encoder='siglip_vit' pools with the tower's attention-pooling head; supported: the default")
         # this class spells the tower "siglip_vit" (the bare name "siglip" stays a refused encoder here); below it is checkpoint.py's "siglip"
@@ -249,6 +252,8 @@ class RegionEmbedder:
                     e.load_clip_checkpoint(ck)
                 elif encoder == "siglip":
                     e.load_siglip_checkpoint(ck)
+                elif encoder == "dinov2":
+                    e.load_dinov2_checkpoint(ck)
                 else:
                     e.load_vit_checkpoint(ck)
                 if ck.image_mean is not None:
@@ -271,6 +276,12 @@ class RegionEmbedder:
                 w = weights if weights is not None else make_siglip_weights(seed, geometry or SIGLIP_B16)
                 if weights is None and geometry is None:
                     geometry = SIGLIP_B16
+            elif encoder == "dinov2":
+                from .weights import DINOV2_B14, make_dinov2_weights
+
+                w = weights if weights is not None else make_dinov2_weights(seed, geometry or DINOV2_B14)
+                if weights is None and geometry is None:
+                    geometry = DINOV2_B14
             elif encoder == "vit" and geometry is not None:
                 w = weights if weights is not None else make_vit_weights(seed, geometry)
             else:
@@ -284,6 +295,8 @@ class RegionEmbedder:
                     e.load_clip(w, geom=geometry)
                 elif encoder == "siglip":
                     e.load_siglip(w, geom=geometry)
+                elif encoder == "dinov2":
+                    e.load_dinov2(w, geom=geometry)
                 elif encoder == "vit":
                     e.load_vit(w, geom=geometry)
                 else:
@@ -300,7 +313,7 @@ class RegionEmbedder:
                 e.set_chunk(chunk)
         if prune_last_layer is None:  # default: on for the contexts this object created, a caller's engine stays as it is
             prune_last_layer = engine is None
-        if prune_last_layer and encoder in ("vit_b16", "vit", "clip"):
+        if prune_last_layer and encoder in ("vit_b16", "vit", "clip", "dinov2"):
             # only the pooled token's row of the last layer is computed past its attention (mme_set_forward_pruning): callers of
             # this class only ever receive pooled vectors, and those are bit-identical, 6 % sooner.  The benchmark's headline
             # drives the Engine directly and times the whole forward; `prune_last_layer=False` restores that here.
@@ -308,7 +321,7 @@ class RegionEmbedder:
                 e.set_forward_pruning(True)
         if pool not in ("cls", "last"):
             raise ValueError("pool must be 'cls' or 'last'")
-        # the last token: 196 of the 197 at patch 16 (the same at every width), 49 of the 50 at patch 32
+        # the last token: 196 of the 197 at patch 16 (the same at every width), 49 of the 50 at patch 32, 256 of the 257 at patch 14
         # (SigLIP: the library ignores the token, the head pools)
         self.pool_token = 0 if pool == "cls" else (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1)
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
@@ -753,6 +766,8 @@ class RegionEmbedder:
 
         src = getattr(self, "_text_source", False)
         eng = self.engines[0]
+        if getattr(self, "encoder", None) == "dinov2":
+            raise NotImplementedError("text embeddings: a DINOv2 tower is trained on images alone and has no text tower; " + self._NO_TOWER)
         if getattr(self, "encoder", None) == "siglip":  # (a CLIP text tower embeds into another space than a SigLIP image tower)
             return self._load_siglip_text_tower(src, eng)
         if src is False:

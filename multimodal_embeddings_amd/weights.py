@@ -352,6 +352,151 @@ def infer_siglip_geometry(w: dict, eps: float = 1e-6) -> SiglipGeometry:
                           layer_norm_eps=float(eps))
 
 
+# ---- DINOv2 ViT/14 image towers ---------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Dinov2Geometry(ViTGeometry):
+    """A DINOv2 image tower at the engine's third geometry (transformers Dinov2Config): patch 14 at 224 pixels, 16 x 16 patches
+    and a class token (257 tokens), heads of 64, layer_norm_eps 1e-6, erf-GELU, an MLP of `mlp_ratio` x hidden, LayerScale
+    behind the attention and the MLP of every block.  `position_grid` is the side of the checkpoint's patch position grid: 16
+    (a 257-row table, taken as it is) or 37 (`image_size` 518 in config.json, 1370 rows: dinov2-small / -base / -large), which
+    the loader interpolates to 16 x 16 once, on the host.  The embedding is `pooler_output`, `hidden_size` wide.  The defaults
+    are dinov2-base."""
+
+    patch_size: int = 14
+    layer_norm_eps: float = 1e-6
+    hidden_act: str = "gelu"
+    use_swiglu_ffn: bool = False
+    num_register_tokens: int = 0
+    position_grid: int = 16
+
+    @property
+    def patch_dim_padded(self) -> int:
+        return (self.patch_dim + 63) // 64 * 64  # 588 -> 640: K of the patch-embed GEMM
+
+    @property
+    def embed_dim(self) -> int:
+        return self.hidden_size
+
+    @property
+    def position_rows(self) -> int:
+        return 1 + self.position_grid * self.position_grid
+
+
+DINOV2_S14 = Dinov2Geometry(hidden_size=384, num_layers=12, num_heads=6, intermediate_size=1536)
+DINOV2_B14 = Dinov2Geometry()
+DINOV2_L14 = Dinov2Geometry(hidden_size=1024, num_layers=24, num_heads=16, intermediate_size=4096)
+SUPPORTED_DINOV2 = {"patch_size": (14,), "hidden_act": ("gelu",), "use_swiglu_ffn": (False,), "num_register_tokens": (0,)}
+
+
+def dinov2_geometry_problem(geom: Dinov2Geometry):
+    """As `vit_geometry_problem` with patch 14 only and the DINOv2 fields: None, or (field, value found, supported values as text)."""
+    if geom.use_swiglu_ffn is not False:
+        return "use_swiglu_ffn", geom.use_swiglu_ffn, "False (the SwiGLU MLP of dinov2-giant is not run)"
+    if geom.num_register_tokens != 0:
+        return "num_register_tokens", geom.num_register_tokens, "0 (Dinov2WithRegisters is not run)"
+    if geom.patch_size not in SUPPORTED_DINOV2["patch_size"]:
+        return "patch_size", geom.patch_size, "14"
+    for fld in ("image_size", "num_channels", "hidden_size"):
+        if getattr(geom, fld) not in SUPPORTED_VIT[fld]:
+            return fld, getattr(geom, fld), ", ".join(str(v) for v in SUPPORTED_VIT[fld])
+    if geom.num_heads * 64 != geom.hidden_size:
+        return "num_heads", geom.num_heads, f"{geom.hidden_size // 64} at hidden_size {geom.hidden_size} (heads of 64)"
+    F = geom.intermediate_size
+    if F < 64 or F % 64 or F > 8192:
+        return "intermediate_size", F, SUPPORTED_VIT["intermediate_size"]
+    if not 1 <= geom.num_layers <= 64:
+        return "num_layers", geom.num_layers, SUPPORTED_VIT["num_layers"]
+    if geom.hidden_act not in SUPPORTED_DINOV2["hidden_act"]:
+        return "hidden_act", geom.hidden_act, "gelu"
+    if geom.position_grid < 1:
+        return "position_grid", geom.position_grid, "a positive grid side"
+    return None
+
+
+def dinov2_tensor_specs(geom: Dinov2Geometry = DINOV2_B14):
+    """(name, shape, kind) in a fixed order, the state-dict names of transformers' `Dinov2Model`
+    (models/dinov2/modeling_dinov2.py); kind in {matrix, bias, gamma, scale}.  `embeddings.mask_token` is not listed: the
+    forward without masked positions never reads it."""
+    D, F, P = geom.hidden_size, geom.intermediate_size, geom.patch_size
+    specs = [
+        ("embeddings.cls_token", (1, 1, D), "matrix"),
+        ("embeddings.position_embeddings", (1, geom.position_rows, D), "matrix"),
+        ("embeddings.patch_embeddings.projection.weight", (D, geom.num_channels, P, P), "matrix"),
+        ("embeddings.patch_embeddings.projection.bias", (D,), "bias"),
+    ]
+    for i in range(geom.num_layers):
+        p = f"encoder.layer.{i}."
+        specs += [(p + "norm1.weight", (D,), "gamma"), (p + "norm1.bias", (D,), "bias")]
+        for n in ("query", "key", "value"):
+            specs += [(p + f"attention.attention.{n}.weight", (D, D), "matrix"), (p + f"attention.attention.{n}.bias", (D,), "bias")]
+        specs += [
+            (p + "attention.output.dense.weight", (D, D), "matrix"),
+            (p + "attention.output.dense.bias", (D,), "bias"),
+            (p + "layer_scale1.lambda1", (D,), "scale"),
+            (p + "norm2.weight", (D,), "gamma"),
+            (p + "norm2.bias", (D,), "bias"),
+            (p + "mlp.fc1.weight", (F, D), "matrix"),
+            (p + "mlp.fc1.bias", (F,), "bias"),
+            (p + "mlp.fc2.weight", (D, F), "matrix"),
+            (p + "mlp.fc2.bias", (D,), "bias"),
+            (p + "layer_scale2.lambda1", (D,), "scale"),
+        ]
+    specs += [("layernorm.weight", (D,), "gamma"), ("layernorm.bias", (D,), "bias")]
+    return specs
+
+
+def make_dinov2_weights(seed: int = 6, geom: Dinov2Geometry = DINOV2_B14, std: float = 0.02, pos_grid: int | None = None) -> dict[str, np.ndarray]:
+    """Seeded synthetic weights of a DINOv2 tower, f32 arrays holding bf16-representable values: the generator and the
+    LayerNorm spread of `make_clip_weights` on `dinov2_tensor_specs`.  LayerScale's lambda1 is drawn from about [0.05, 2]
+    (1.025 + 0.325 z clipped), far from the constant 1 a dropped or exchanged scale would be, so that the fold at load time
+    is exercised.  `pos_grid` (16 or 37) overrides the geometry's position grid: 37 gives the 1370-row table real
+    checkpoints carry."""
+    import dataclasses
+
+    if pos_grid is not None:
+        geom = dataclasses.replace(geom, position_grid=int(pos_grid))
+    out: dict[str, np.ndarray] = {}
+    for tid, (name, shape, kind) in enumerate(dinov2_tensor_specs(geom)):
+        n = int(np.prod(shape))
+        z = irwin_hall_normal(seed, tid, n)
+        norm = ".norm" in name or "layernorm" in name
+        if kind == "gamma":
+            z = np.float32(1.0) + z * np.float32(0.25)
+        elif kind == "scale":
+            z = np.clip(np.float32(1.025) + z * np.float32(0.325), np.float32(0.05), np.float32(2.0))
+        elif kind == "bias" and norm:
+            z = z * np.float32(0.1)
+        else:
+            z = z * np.float32(std)
+        out[name] = round_to_bf16(z).reshape(shape)
+    return out
+
+
+def dinov2_flops_per_crop(geom: Dinov2Geometry = DINOV2_B14) -> int:
+    """`vit_flops_per_crop`'s count at 257 tokens, the patch embedding at its real K of 588 (the padded columns are zeros)."""
+    D, F, L, T = geom.hidden_size, geom.intermediate_size, geom.num_layers, geom.seq_len
+    return 2 * geom.num_patches * geom.patch_dim * D + L * (2 * T * D * (4 * D + 2 * F) + 4 * T * T * D)
+
+
+def infer_dinov2_geometry(w: dict, eps: float = 1e-6) -> Dinov2Geometry:
+    """The geometry of a `dinov2_tensor_specs` weight dict, read off its tensor shapes; heads of 64, 224 pixels.  A position
+    table whose patch part is no square grid raises, naming the tensor."""
+    pw = np.shape(w["embeddings.patch_embeddings.projection.weight"])
+    D, patch = int(pw[0]), int(pw[-1])
+    rows = int(np.shape(w["embeddings.position_embeddings"])[-2])
+    grid = int(round((rows - 1) ** 0.5))
+    if rows < 2 or grid * grid != rows - 1:
+        raise ValueError(f"tensor 'embeddings.position_embeddings' has {rows} rows: the patch part ({rows - 1} rows) is no square grid")
+    layers = 0
+    while f"encoder.layer.{layers}.mlp.fc1.weight" in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError("the weight dict holds no 'encoder.layer.0.mlp.fc1.weight'")
+    F = int(np.shape(w["encoder.layer.0.mlp.fc1.weight"])[0])
+    return Dinov2Geometry(image_size=224, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
+                          layer_norm_eps=float(eps), position_grid=grid)
+
+
 # ---- CLIP text towers -------------------------------------------------------------------------------------------------
 TEXT_TOKENS = 77  # CLIPTextConfig.max_position_embeddings; fixed at compile time (csrc/common.h TXT_T)
 
