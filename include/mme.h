@@ -859,7 +859,7 @@ int mme_gemm_stamps(mme_ctx* ctx, int M, int N, int K, uint64_t* stamps_host);
  *             8 as 2; the 256 x 256 kernel (*ran_256 = 1) also writes, for every row of an INTERIOR 256-row tile,
  *               ln_part[(0 * N/64 + slice) * ln_part_rows + m] = sum and [(1 * N/64 + slice) * ...] = sum of squares of
  *               the ROUNDED outputs of row m over columns 64 slice .. 64 slice + 63 (f32).  Other rows carry no promise.
- *             (7, the candidate-list epilogue of mme_neighbours, is refused.)
+ *             (7, the candidate-list epilogue of mme_neighbours, is refused here: mme_select_apply op 2 launches it.)
  *   variant   as mme_set_gemm_variant (0 = by shape); K = 64 always runs the 128 x 128 kernel.  reverse_m 0 / 1: the
  *             256 x 256 kernel walks the row panels upwards / downwards (same results).
  * Preconditions (anything else returns MME_E_ARG with a message and launches nothing): M, N >= 1; K >= 64, K % 64 == 0;
@@ -918,6 +918,51 @@ typedef struct mme_rowop_apply_args {
     float eps;
 } mme_rowop_apply_args;
 int mme_rowop_apply(mme_ctx* ctx, int op, const mme_rowop_apply_args* args, void* stream);
+
+/* Diagnostic: ONE launch of a step of K12 (mme_neighbours) on the caller's device buffers, then a stream synchronise; works on
+ * a bare context (tests/test_gpu_select.py compares every output bit with the definition above mme_neighbours).
+ * The selection of ops 0 and 1, for the row with index self = row0 + r over (value, id) pairs: order by value descending, id
+ * ascending; cut at `fetch`; drop id == self unless keep_self; drop id != self with group[id] == group[self] (group may be
+ * NULL; it is indexed by self and by every id met); drop values outside the closed window [min_sim, max_sim]; keep the first
+ * top_n into idx_out / sim_out [nrows, top_n]; pad with (-1, 0.0f).  Values compare as floats (-0 == +0, -inf is a value like
+ * any other); NaN values are outside the contract.
+ *   op 0 topk_rows        launch_topk_rows as mme_neighbours calls it: the pairs of row r are (qsim[r * ld + j], j), j < N.
+ *                         Columns [N, ld) are not read.  run_if: a device int, or NULL; with *run_if == 0 the launch writes nothing
+ *      1 topk_candidates  launch_topk_candidates: the pairs of row r are (cand_val[r * cap + k], cand_idx[r * cap + k]),
+ *                         k < min(len[r], cap), ids distinct within a row; the result does not depend on their order in the list.
+ *                         Slots from min(len[r], cap) on are not read
+ *      2 gemm_topk        launch_gemm(EPI_TOPK, variant 3) as mme_neighbours makes it: acc = A[M, K] . W[N, K]^T (bf16 operands,
+ *                         f32 accumulation); every (m, n) with acc[m, n] >= thr[m * thr_stride], n < N, takes the next slot k of row m
+ *                         (cand_count[m] += 1, counted past cap as well) and, where k < cap, cand_val[m * cap + k] = acc[m, n],
+ *                         cand_idx[m * cap + k] = n, in arbitrary order.  *overflow is set to 1 when some row's count exceeds cap and
+ *                         is not written otherwise.  The caller zeroes cand_count[0 .. M) and *overflow first
+ * Preconditions (else MME_E_ARG with the field and the value in mme_last_error, nothing launched): op 0..2; the pointers the
+ * op reads or writes non-null (group and run_if excepted) and 4-byte aligned; ops 0, 1: 0 <= nrows <= 2^24, row0 >= 0, fetch
+ * and top_n in 1..128; op 0: N >= 1, ld % 4 == 0, N <= ld <= 2^30, qsim 16-byte aligned; op 1: cap % 4 == 0, cap >= 4, cand_val
+ * and cand_idx 16-byte aligned; op 2: 0 <= M <= 2^24, 1 <= N <= 2^20, K a multiple of 64 in 128..65536, cap >= 1,
+ * thr_stride >= 1, A and W 16-byte aligned.  nrows = 0 / M = 0 launch nothing and return MME_OK. */
+typedef struct mme_select_apply_args {
+    const float* qsim;      /* op 0: f32 [nrows, ld] */
+    const int32_t* group;   /* ops 0, 1: optional */
+    int32_t* idx_out;       /* ops 0, 1: [nrows, top_n] */
+    float* sim_out;         /* ops 0, 1: [nrows, top_n] */
+    const int32_t* run_if;  /* op 0: optional device int */
+    float* cand_val;        /* op 1: in [nrows, cap]; op 2: out [M, cap] */
+    int32_t* cand_idx;      /* op 1: in [nrows, cap]; op 2: out [M, cap] */
+    const int32_t* len;     /* op 1: [nrows] */
+    const uint16_t* A;      /* op 2: bf16 [M, K] */
+    const uint16_t* W;      /* op 2: bf16 [N, K] */
+    const float* thr;       /* op 2: row m reads thr[m * thr_stride] */
+    int32_t* cand_count;    /* op 2: [M] */
+    int32_t* overflow;      /* op 2: one int */
+    int64_t ld;             /* op 0 */
+    int32_t N;              /* ops 0, 2 */
+    int32_t nrows, row0, fetch, top_n, keep_self; /* ops 0, 1 */
+    int32_t cap;            /* ops 1, 2 */
+    int32_t M, K, thr_stride; /* op 2 */
+    float min_sim, max_sim; /* ops 0, 1 */
+} mme_select_apply_args;
+int mme_select_apply(mme_ctx* ctx, int op, const mme_select_apply_args* args, void* stream);
 
 /* Diagnostic: ONE launch of a kernel the CLIP tower adds, on the caller's device buffers, synchronous; works on a bare context.
  *   op 0 the GEMM of `gemm` with out = bf16(quick_gelu(acc + bias[n])), quick_gelu(x) = x * sigmoid(1.702 x)

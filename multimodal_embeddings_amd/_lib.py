@@ -107,6 +107,13 @@ class _RowopApplyArgs(C.Structure):  # mme_rowop_apply_args
         ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("eps", C.c_float)]
 
 
+class _SelectApplyArgs(C.Structure):  # mme_select_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("qsim", "group", "idx_out", "sim_out", "run_if", "cand_val", "cand_idx", "len", "A", "W", "thr", "cand_count",
+                                          "overflow")] + [("ld", C.c_int64)] + [
+        (n, C.c_int32) for n in ("N", "nrows", "row0", "fetch", "top_n", "keep_self", "cap", "M", "K", "thr_stride")] + [
+        ("min_sim", C.c_float), ("max_sim", C.c_float)]
+
+
 class _ClipApplyArgs(C.Structure):  # mme_clip_apply_args
     _fields_ = [("gemm", C.POINTER(_GemmApplyArgs))] + [(n, C.c_void_p) for n in ("x", "gamma", "beta", "stats", "y", "xf", "y_f32", "y_bf16")] + [
         ("rows", C.c_int64), ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("p", C.c_int32), ("eps", C.c_float),
@@ -242,6 +249,7 @@ EXPORTS = {
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mme_gemm_apply": (C.c_int, [C.c_void_p, C.POINTER(_GemmApplyArgs), C.POINTER(C.c_int32), C.c_void_p]),
     "mme_rowop_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_RowopApplyArgs), C.c_void_p]),
+    "mme_select_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_SelectApplyArgs), C.c_void_p]),
     "mme_load_tile_vit": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights)]),
     "mme_load_tile_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights), C.c_int, C.c_void_p]),
     "mme_tile_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1209,6 +1217,28 @@ class Engine:
         a.part_floats = 0 if part is None else int(part.numel())
         a.d, a.B, a.tok, a.eps = int(d), int(B), int(tok), float(eps)
         self._check(self.lib.mme_rowop_apply(self.h, int(self.ROWOPS.get(op, op)), C.byref(a), self._stream()), "mme_rowop_apply")
+
+    SELECT_OPS = {"topk_rows": 0, "topk_candidates": 1, "gemm_topk": 2}
+
+    def select_apply(self, op, *, qsim=None, ld=None, N=None, nrows=None, row0: int = 0, group=None, fetch: int = 1, top_n: int = 1,
+                     keep_self: int = 0, min_sim: float = float("-inf"), max_sim: float = float("inf"), idx_out=None, sim_out=None, run_if=None,
+                     cand_val=None, cand_idx=None, len=None, cap: int = 0, A=None, W=None, M=None, K=None, thr=None, thr_stride: int = 1,
+                     cand_count=None, overflow=None):
+        """ONE launch of a step of K12 on the caller's CUDA tensors (mme_select_apply; synchronous, works on a bare context).
+        op: a name of SELECT_OPS or its code; which tensors and sizes each op reads is in include/mme.h.  `ld` defaults to
+        qsim's row pitch, `nrows` to idx_out's rows, M / K to A's shape and N (op 2) to W's rows.  The library validates."""
+        a = _SelectApplyArgs()
+        a.qsim, a.group, a.idx_out, a.sim_out, a.run_if = (self._ptr(t) for t in (qsim, group, idx_out, sim_out, run_if))
+        a.cand_val, a.cand_idx, a.len, a.A, a.W = (self._ptr(t) for t in (cand_val, cand_idx, len, A, W))
+        a.thr, a.cand_count, a.overflow = (self._ptr(t) for t in (thr, cand_count, overflow))
+        a.ld = int((qsim.shape[-1] if qsim is not None else 0) if ld is None else ld)
+        a.N = int((W.shape[0] if W is not None else 0) if N is None else N)
+        a.nrows = int((idx_out.shape[0] if idx_out is not None else 0) if nrows is None else nrows)
+        a.row0, a.fetch, a.top_n, a.keep_self, a.cap = int(row0), int(fetch), int(top_n), int(keep_self), int(cap)
+        a.M = int((A.shape[0] if A is not None else 0) if M is None else M)
+        a.K = int((A.shape[1] if A is not None else 0) if K is None else K)
+        a.thr_stride, a.min_sim, a.max_sim = int(thr_stride), float(min_sim), float(max_sim)
+        self._check(self.lib.mme_select_apply(self.h, int(self.SELECT_OPS.get(op, op)), C.byref(a), self._stream()), "mme_select_apply")
 
     CLIP_OPS = {"gemm_qgelu": 0, "gemm_ln_qgelu": 1, "pre_ln": 2, "pool_ln": 3, "l2": 4}
 

@@ -1338,7 +1338,7 @@ int mme_gemm_apply(mme_ctx* c, const mme_gemm_apply_args* a, int32_t* ran_256, v
     if (!c) return MME_E_ARG;
     if (!a || !ran_256) return fail(c, MME_E_ARG, "mme_gemm_apply: null argument");
     const int epi = a->epilogue;
-    if (epi == EPI_TOPK) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 7 (candidate lists) is not served here; mme_neighbours runs it");
+    if (epi == EPI_TOPK) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue 7 (candidate lists) is not served here; mme_select_apply op 2 launches it");
     if (epi < 0 || epi > EPI_BIAS_RES_STATS) return fail(c, MME_E_ARG, "mme_gemm_apply: epilogue %d outside 0..6, 8", epi);
     if (a->variant < 0 || a->variant > 6) return fail(c, MME_E_ARG, "mme_gemm_apply: variant %d outside 0..6", a->variant);
     if (a->reverse_m != 0 && a->reverse_m != 1) return fail(c, MME_E_ARG, "mme_gemm_apply: reverse_m must be 0 or 1");
@@ -1457,6 +1457,61 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
         case 3: HIP_TRY(c, launch_ln_finish(a->part, a->part_rows, a->rows, a->d, a->eps, a->stats, s)); break;
         case 4: HIP_TRY(c, launch_cls_rows(a->x, a->cls, a->pos, a->B, a->d, s)); break;
         default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->B, VIT_T, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+// the three launches of K12 (mme_neighbours), one at a time on caller-owned buffers (tests/test_gpu_select.py)
+int mme_select_apply(mme_ctx* c, int op, const mme_select_apply_args* a, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "mme_select_apply: null argument");
+    if (op < 0 || op > 2) return fail(c, MME_E_ARG, "mme_select_apply: op %d outside 0..2", op);
+    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    auto word = [](const void* p) { return p && aligned_to(p, 4); };
+    if (op <= 1) {
+        if (a->nrows < 0 || a->nrows > (1 << 24)) return fail(c, MME_E_ARG, "mme_select_apply: nrows = %d outside 0..2^24", a->nrows);
+        if (a->row0 < 0) return fail(c, MME_E_ARG, "mme_select_apply: row0 = %d is negative", a->row0);
+        if (a->fetch < 1 || a->fetch > 128) return fail(c, MME_E_ARG, "mme_select_apply: fetch = %d outside 1..128", a->fetch);
+        if (a->top_n < 1 || a->top_n > 128) return fail(c, MME_E_ARG, "mme_select_apply: top_n = %d outside 1..128", a->top_n);
+        if (!word(a->idx_out) || !word(a->sim_out)) return fail(c, MME_E_ARG, "mme_select_apply: op %d needs idx_out and sim_out non-null and 4-byte aligned", op);
+        if (a->group && !aligned_to(a->group, 4)) return fail(c, MME_E_ARG, "mme_select_apply: group must be 4-byte aligned");
+    }
+    if (op == 0) {
+        if (a->N < 1) return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs N >= 1 (N = %d)", a->N);
+        if ((a->ld % 4) != 0 || a->ld < a->N || a->ld > ((int64_t)1 << 30))
+            return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs ld %% 4 == 0 and N <= ld <= 2^30 (ld = %lld, N = %d)", (long long)a->ld, a->N);
+        if (!vec(a->qsim)) return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs qsim non-null and 16-byte aligned");
+        if (a->run_if && !aligned_to(a->run_if, 4)) return fail(c, MME_E_ARG, "mme_select_apply: run_if must be 4-byte aligned");
+    } else if (op == 1) {
+        if (a->cap < 4 || (a->cap % 4) != 0) return fail(c, MME_E_ARG, "mme_select_apply: op 1 needs cap %% 4 == 0 and cap >= 4 (cap = %d)", a->cap);
+        if (!vec(a->cand_val) || !vec(a->cand_idx) || !word(a->len))
+            return fail(c, MME_E_ARG, "mme_select_apply: op 1 needs cand_val and cand_idx non-null and 16-byte aligned, len non-null and 4-byte aligned");
+    } else {
+        if (a->M < 0 || a->M > (1 << 24)) return fail(c, MME_E_ARG, "mme_select_apply: M = %d outside 0..2^24", a->M);
+        if (a->N < 1 || a->N > (1 << 20)) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs N in 1..2^20 (N = %d)", a->N);
+        if (a->K < 128 || a->K > (1 << 16) || (a->K % 64) != 0)
+            return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs K a multiple of 64 in 128..65536 (K = %d)", a->K);
+        if (a->cap < 1) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs cap >= 1 (cap = %d)", a->cap);
+        if (a->thr_stride < 1) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs thr_stride >= 1 (thr_stride = %d)", a->thr_stride);
+        if (!vec(a->A) || !vec(a->W)) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs A and W non-null and 16-byte aligned");
+        if (!word(a->thr) || !word(a->cand_count) || !word(a->cand_val) || !word(a->cand_idx) || !word(a->overflow))
+            return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs thr, cand_count, cand_val, cand_idx and overflow non-null and 4-byte aligned");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (op == 0) {
+        HIP_TRY(c, launch_topk_rows(a->qsim, a->ld, a->N, a->nrows, a->row0, a->group, a->fetch, a->top_n, a->keep_self, a->min_sim, a->max_sim,
+                                    a->idx_out, a->sim_out, s, a->run_if));
+    } else if (op == 1) {
+        HIP_TRY(c, launch_topk_candidates(a->cand_val, a->cand_idx, a->len, a->cap, a->nrows, a->row0, a->group, a->fetch, a->top_n, a->keep_self,
+                                          a->min_sim, a->max_sim, a->idx_out, a->sim_out, s));
+    } else {
+        GemmArgs g{};
+        g.A = a->A; g.W = a->W; g.M = a->M; g.N = a->N; g.K = a->K;
+        g.thr = a->thr; g.thr_stride = a->thr_stride; g.cand_count = a->cand_count; g.cand_val = a->cand_val; g.cand_idx = a->cand_idx;
+        g.cand_cap = a->cap; g.overflow = a->overflow;
+        HIP_TRY(c, launch_gemm(EPI_TOPK, g, s, 3));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
