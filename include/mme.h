@@ -580,7 +580,9 @@ int mme_attention_apply(mme_ctx* ctx, int kind, const uint16_t* qkv_dev, int n, 
  *   page_dev    uint8 RGB HWC pixels of the page, [H, W, 3]
  *   boxes_host  int32[n,4] (x0, y0, x1, y1) AFTER the reference's int() truncation
  *               (doclayout_detector.py:179); crop i is (y1-y0) x (x1-x0) pixels; parts of a box
- *               outside the page read as 0, as PIL's Image.crop fills them
+ *               outside the page read as 0, as PIL's Image.crop fills them.  A corner may be any
+ *               int32, however far outside the page: sizes and byte columns are formed in 64 bits,
+ *               and a box whose x1 - x0 or y1 - y0 is not in 1..8000 is MME_E_ARG, named by index
  *   pix_dev     destination buffer; offs_host int64[n] byte offset of crop i in it (same
  *               packing rule as mme_preprocess: 16-byte aligned crops, 16 bytes of slack) */
 int mme_crop_boxes(mme_ctx* ctx, const uint8_t* page_dev, int H, int W, const int32_t* boxes_host, int n, uint8_t* pix_dev,
@@ -668,6 +670,13 @@ int mme_preprocess(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* offs_hos
  *   out_dev            float[n, max_tiles, 3, tile, tile]  (`pixel_values`)
  *   aspect_ids_host    int32[n] or NULL: `aspect_ratio_ids` (1-based index into the supported grids, :136-164)
  *   num_tiles_host     int32[n] or NULL: tiles used; `aspect_ratio_mask` = 1 for the first num_tiles slots (:52-81)
+ * Limit: the vertical pass holds the taps of one output row in 160 words of LDS.  Pillow's window of a crop of h rows
+ * that becomes new_h rows is 2 * ceil(h / new_h) + 1 taps (1 when the height does not change); a batch in which some
+ * crop's window exceeds 160 taps -- its height shrinks by a factor above 79, e.g. 8000 x 9 at tile 16, max_tiles 1 -- is
+ * refused whole with MME_E_ARG before anything is launched (the message names the crop, its size, the window and the
+ * limit; out_dev is not written).  At tile 560 with 4 tiles no crop of up to 8000 x 8000 comes near it (the canvas is
+ * chosen for the largest scale, at least 1120 / 8000: a factor of 7.2 at most, 17 taps).  The
+ * horizontal pass sizes its table from the crop and has no such limit.
  * Synchronises the stream once (crop tables are staged from host temporaries). */
 int mme_preprocess_tiles(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* offs_host, const int32_t* hw_host, int n, int tile,
                          int max_tiles, float* out_dev, int32_t* aspect_ids_host, int32_t* num_tiles_host, void* stream);

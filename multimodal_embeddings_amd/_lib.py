@@ -1347,9 +1347,12 @@ class Engine:
             raise MmeError("crop_boxes: page must be a contiguous uint8 [H, W, 3] tensor")
         b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
         n = len(b)
-        hw = np.ascontiguousarray(np.stack([b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]], axis=1).astype(np.int32)) if n else np.zeros((0, 2), np.int32)
-        if n and (hw.min() <= 0 or hw.max() > 8000):
-            raise MmeError("crop_boxes: every box must be 1..8000 pixels wide and high after int() truncation")
+        b64 = b.astype(np.int64)  # corners are any int32: the difference of two needs 33 bits
+        hw64 = np.stack([b64[:, 3] - b64[:, 1], b64[:, 2] - b64[:, 0]], axis=1)
+        if n and (hw64.min() <= 0 or hw64.max() > 8000):
+            i = int(np.flatnonzero(((hw64 <= 0) | (hw64 > 8000)).any(axis=1))[0])
+            raise MmeError(f"crop_boxes: box {i} is {hw64[i, 1]}x{hw64[i, 0]} (w x h); every box must be 1..8000 pixels wide and high after int() truncation")
+        hw = np.ascontiguousarray(hw64.astype(np.int32)) if n else np.zeros((0, 2), np.int32)
         size = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
         offs = np.zeros(n, dtype=np.int64)
         if n > 1:
@@ -1425,13 +1428,18 @@ class Engine:
         self._check(self.lib.mme_preprocess(self.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, patches.data_ptr(), self._stream()), "mme_preprocess")
         return patches
 
-    def preprocess_tiles(self, pix, offs, hw, tile=560, max_tiles=4):
+    def preprocess_tiles(self, pix, offs, hw, tile=560, max_tiles=4, out=None):
         """Mllama multi-tile preprocessing of packed crops -> (pixel_values f32 CUDA [n, max_tiles, 3, tile, tile],
-        aspect_ratio_ids int64[n], aspect_ratio_mask int64[n, max_tiles], num_tiles list[int])."""
+        aspect_ratio_ids int64[n], aspect_ratio_mask int64[n, max_tiles], num_tiles list[int]).  `out`, if given, is the
+        contiguous f32 tensor of that shape on pix's device that receives the pixel values (and is returned).  A crop
+        whose height shrinks by a factor above 79 (a vertical window of more than 160 taps) is refused (include/mme.h)."""
         t = self.torch
         offs, hw = self._crop_tables(offs, hw)
         n = len(offs)
-        out = t.empty((n, max_tiles, 3, tile, tile), dtype=t.float32, device=pix.device)
+        if out is None:
+            out = t.empty((n, max_tiles, 3, tile, tile), dtype=t.float32, device=pix.device)
+        elif out.dtype != t.float32 or not out.is_contiguous() or out.device != pix.device or tuple(out.shape) != (n, max_tiles, 3, tile, tile):
+            raise MmeError(f"preprocess_tiles: `out` must be a contiguous float32 tensor [{n}, {max_tiles}, 3, {tile}, {tile}] on the crops' device")
         ids = np.zeros(n, dtype=np.int32)
         nt = np.zeros(n, dtype=np.int32)
         self._check(self.lib.mme_preprocess_tiles(self.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, int(tile), int(max_tiles),

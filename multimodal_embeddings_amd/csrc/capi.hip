@@ -1060,6 +1060,15 @@ int mme_preprocess_tiles(mme_ctx* c, const uint8_t* pix, const int64_t* offs, co
         d.h = h;
         d.w = w;
         fit_to_tile_canvas(h, w, th * tile, tw * tile, tile, &d.new_h, &d.new_w);
+        // resize_v_tiles holds a row's vertical taps in MAX_TAPS words of LDS; a longer window would be cut short there
+        // (wrong pixels, no error), so such a batch is refused whole, before anything is launched.  The horizontal pass
+        // sizes its table from the crop and has no such limit.
+        if (d.new_h != h) {
+            const int window = resample_ksize<Triangle>(h, d.new_h);
+            if (window > MAX_TAPS)
+                return fail(c, MME_E_ARG, "mme_preprocess_tiles: crop %d is %dx%d (h x w) and becomes %d rows: a vertical window of %d taps; the limit is %d taps",
+                            i, h, w, d.new_h, window, MAX_TAPS);
+        }
         if (aspect_ids_host) {  // 1 + index of (th, tw) in the supported list (image_processing_pil_mllama.py:136-164)
             int idx = 0, found = 0;
             for (int a = 1; a <= max_tiles && !found; ++a)
@@ -1097,9 +1106,11 @@ int mme_crop_boxes(mme_ctx* c, const uint8_t* page, int H, int W, const int32_t*
     hipStream_t s = (hipStream_t)stream;
     c->h_work.clear();
     for (int i = 0; i < n; ++i) {
-        const int w = boxes[4 * i + 2] - boxes[4 * i], h = boxes[4 * i + 3] - boxes[4 * i + 1];
-        if (w <= 0 || h <= 0 || w > 8000 || h > 8000)
-            return fail(c, MME_E_ARG, "mme_crop_boxes: box %d is %dx%d (w x h); supported 1..8000", i, w, h);
+        // corners are any int32: x1 - x0 of two of them needs 33 bits
+        const int64_t w64 = (int64_t)boxes[4 * i + 2] - boxes[4 * i], h64 = (int64_t)boxes[4 * i + 3] - boxes[4 * i + 1];
+        if (w64 <= 0 || h64 <= 0 || w64 > 8000 || h64 > 8000)
+            return fail(c, MME_E_ARG, "mme_crop_boxes: box %d is %lldx%lld (w x h); supported 1..8000", i, (long long)w64, (long long)h64);
+        const int w = (int)w64, h = (int)h64;
         int rows = (32 * 1024) / (w * 3);
         rows = rows < 1 ? 1 : rows;
         for (int r = 0; r < h; r += rows) c->h_work.push_back(HWork{i, r, (h - r) < rows ? (h - r) : rows});

@@ -249,16 +249,19 @@ __global__ __launch_bounds__(256) void crop_boxes(const uint8_t* __restrict__ pa
                                                   const int64_t* __restrict__ offs, const HWork* __restrict__ work,
                                                   uint8_t* __restrict__ pix) {
     const HWork wk = work[blockIdx.x];
-    const int x0 = boxes[4 * wk.crop], y0 = boxes[4 * wk.crop + 1], x1 = boxes[4 * wk.crop + 2];
-    const int row_bytes = (x1 - x0) * 3;
+    // Corners are any int32 (a box may lie anywhere outside the page), so everything formed from one is 64-bit: 3 * x0
+    // leaves 32 bits from |x0| = 715 827 883 on.  The box's own size is 1..8000 (mme_crop_boxes), so the counts fit an int.
+    const int64_t x0 = boxes[4 * wk.crop], y0 = boxes[4 * wk.crop + 1], x1 = boxes[4 * wk.crop + 2];
+    const int row_bytes = (int)((x1 - x0) * 3);
     uint8_t* dst = pix + offs[wk.crop] + (int64_t)wk.row0 * row_bytes;
     const int total = wk.nrows * row_bytes;
+    const int64_t page_row_bytes = (int64_t)W * 3;
     for (int e = threadIdx.x; e < total; e += 256) {
         const int r = e / row_bytes, b = e - r * row_bytes;
-        const int y = y0 + wk.row0 + r;
-        const int xb = x0 * 3 + b;  // byte column inside the page row
+        const int64_t y = y0 + wk.row0 + r;
+        const int64_t xb = x0 * 3 + b;  // byte column inside the page row
         uint8_t v = 0;
-        if (y >= 0 && y < H && xb >= 0 && xb < W * 3) v = page[((int64_t)y * W) * 3 + xb];
+        if (y >= 0 && y < H && xb >= 0 && xb < page_row_bytes) v = page[y * page_row_bytes + xb];
         dst[e] = v;
     }
 }
