@@ -7,9 +7,13 @@ torch is used for device memory and streams only (data_ptr() into the ABI).
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
+
+from .weights import (CLIP_ACTS, dinov2_geometry_problem, infer_dinov2_geometry, infer_vit_geometry, siglip_geometry_problem,
+                      siglip_text_geometry_problem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The product library is the in-tree libmme.so.  Measurement tools load libmme_diag.so (build.py --diag: the only build
@@ -350,6 +354,113 @@ def lanczos_tables(in_size: int, out_size: int):
     return bounds, coeffs
 
 
+# ---- the per-encoder pieces of a weight struct; encoders.ENCODER_TABLE names them, Engine._weights_struct runs them -----------------
+def _fill_layers(layers, names, arr, scales=None):
+    """The tensor pointers of every layer: names(i) maps the fields of layer i (_Layer's; "lambda1" / "lambda2" are
+    _Dinov2Scale's, in scales[i]) to its tensor names."""
+    for i, L in enumerate(layers):
+        for fld, name in names(i).items():
+            setattr(scales[i] if fld.startswith("lambda") else L, fld, arr(name))
+
+
+def _refuse(bad, fields):
+    """Raises for a weights.*_geometry_problem in one of `fields`, those the C struct does not carry: the library could not refuse it."""
+    if bad and bad[0] in fields:
+        raise MmeError(f"{bad[0]} = {bad[1]!r}; supported: {bad[2]}")
+
+
+def _clip_act(geom) -> int:
+    if geom.hidden_act not in CLIP_ACTS:
+        raise MmeError(f"hidden_act = {geom.hidden_act!r}; supported: {', '.join(CLIP_ACTS)}")
+    return CLIP_ACTS.index(geom.hidden_act)
+
+
+def _vit_scalars(W, geom):
+    V = getattr(W, "vit", W)  # the image towers' structs begin with an mme_vit_weights
+    V.image_size, V.patch_size, V.hidden, V.layers, V.heads, V.mlp = (geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers,
+                                                                      geom.num_heads, geom.intermediate_size)
+    V.ln_eps = float(geom.layer_norm_eps)
+
+
+def _clip_scalars(W, geom):
+    _vit_scalars(W, geom)
+    W.proj_dim, W.act = int(geom.projection_dim or 0), _clip_act(geom)
+
+
+def _siglip_scalars(W, geom):
+    _refuse(siglip_geometry_problem(geom), ("hidden_act", "vision_use_head"))
+    _vit_scalars(W, geom)
+
+
+def _siglip_head(W, geom, arr):
+    """The pooling head, as one more _Layer without a first LayerNorm: in_proj_weight [3 D, D] and in_proj_bias [3 D] are
+    split q | k | v by element offset."""
+    h, D, H = "vision_model.head.", geom.hidden_size, W.head
+    H.ln1_g = H.ln1_b = None
+    H.q_w, H.k_w, H.v_w = (arr(h + "attention.in_proj_weight", i * D * D) for i in range(3))
+    H.q_b, H.k_b, H.v_b = (arr(h + "attention.in_proj_bias", i * D) for i in range(3))
+    H.o_w, H.o_b = arr(h + "attention.out_proj.weight"), arr(h + "attention.out_proj.bias")
+    H.ln2_g, H.ln2_b = arr(h + "layernorm.weight"), arr(h + "layernorm.bias")
+    H.fc1_w, H.fc1_b = arr(h + "mlp.fc1.weight"), arr(h + "mlp.fc1.bias")
+    H.fc2_w, H.fc2_b = arr(h + "mlp.fc2.weight"), arr(h + "mlp.fc2.bias")
+
+
+def _dinov2_scalars(W, geom):
+    _refuse(dinov2_geometry_problem(geom), ("hidden_act", "use_swiglu_ffn", "num_register_tokens", "position_grid"))
+    _vit_scalars(W, geom)
+    W.vit.image_size = 224  # whatever the position table was made for
+
+
+def _dinov2_host_geometry(w: dict, geom):
+    """`geom` (None: all of it) with the position grid the tensors have."""
+    try:
+        found = infer_dinov2_geometry(w)
+    except ValueError as e:
+        raise MmeError(f"load_dinov2: {e}") from e
+    return found if geom is None else dataclasses.replace(geom, position_grid=found.position_grid)
+
+
+def _dinov2_special(get, extra):
+    """pos: the f32 [257, D] position table -- a checkpoint object's own (`extra`), else the dict's table interpolated to
+    16 x 16 here, once, as the model does on every forward.  -> (special arguments of the builder, what must stay alive)."""
+    import torch
+
+    from .checkpoint import DINOV2_POSITIONS, interpolate_dinov2_positions
+
+    table = extra["position_table"] if extra is not None else interpolate_dinov2_positions(
+        torch.from_numpy(np.ascontiguousarray(get(DINOV2_POSITIONS), dtype=np.float32)))
+    return {"pos": C.cast(C.c_void_p(table.data_ptr()), C.POINTER(C.c_float))}, table
+
+
+def _clip_text_scalars(W, geom):
+    W.hidden, W.layers, W.heads, W.mlp, W.vocab, W.max_positions = (geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
+                                                                   geom.vocab_size, geom.max_position_embeddings)
+    W.proj_dim, W.act, W.eos_token_id, W.ln_eps = int(geom.projection_dim or 0), _clip_act(geom), int(geom.eos_token_id), float(geom.layer_norm_eps)
+
+
+def _siglip_text_scalars(W, geom, logits=None):
+    """`logits`: (logit_scale, logit_bias) of a whole SiglipModel, or None."""
+    _refuse(siglip_text_geometry_problem(geom), ("hidden_act",))  # the struct has no field for it: the library runs tanh-GELU
+    W.hidden, W.layers, W.heads, W.mlp, W.vocab, W.max_positions = (geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
+                                                                   geom.vocab_size, geom.max_position_embeddings)
+    W.projection_size, W.pad_token_id, W.ln_eps = int(geom.projection_size), int(geom.pad_token_id), float(geom.layer_norm_eps)
+    W.has_logits, W.logit_scale, W.logit_bias = int(logits is not None), float(logits[0]) if logits else 0.0, float(logits[1]) if logits else 0.0
+
+
+def _siglip_logits(get):
+    """(logit_scale, logit_bias) as floats from get(name) -> a one-value array / tensor or None; None when both are absent."""
+    vals = [get(k) for k in ("logit_scale", "logit_bias")]
+    if vals[0] is None and vals[1] is None:
+        return None
+    if vals[0] is None or vals[1] is None:
+        raise MmeError("load_siglip_text: logit_scale and logit_bias come together (a whole SiglipModel) or not at all")
+    return tuple(float(np.asarray(v.float() if hasattr(v, "float") and not isinstance(v, np.ndarray) else v, dtype=np.float32).reshape(-1)[0]) for v in vals)
+
+
+def _siglip_text_special(get, extra):
+    return {"logits": _siglip_logits(get)}, None
+
+
 class Engine:
     """One mme_ctx bound to one GPU.  Methods take torch CUDA tensors / numpy control arrays."""
 
@@ -388,57 +499,92 @@ class Engine:
 
     # ---- weights ---------------------------------------------------------------------------------
     @staticmethod
-    def _vit_struct(geom, arr):
-        """mme_vit_weights (+ its layer array, which the caller keeps alive) for `geom`, tensor pointers from arr(name)."""
-        layers = (_Layer * geom.num_layers)()
-        for i in range(geom.num_layers):
-            p = f"layers.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "layernorm_before.weight"), arr(p + "layernorm_before.bias")
-            L.q_w, L.q_b = arr(p + "attention.q_proj.weight"), arr(p + "attention.q_proj.bias")
-            L.k_w, L.k_b = arr(p + "attention.k_proj.weight"), arr(p + "attention.k_proj.bias")
-            L.v_w, L.v_b = arr(p + "attention.v_proj.weight"), arr(p + "attention.v_proj.bias")
-            L.o_w, L.o_b = arr(p + "attention.o_proj.weight"), arr(p + "attention.o_proj.bias")
-            L.ln2_g, L.ln2_b = arr(p + "layernorm_after.weight"), arr(p + "layernorm_after.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        W = _Weights(geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
-                     float(geom.layer_norm_eps))
-        W.cls_token = arr("embeddings.cls_token")
-        W.pos_emb = arr("embeddings.position_embeddings")
-        W.patch_w = arr("embeddings.patch_embeddings.projection.weight")
-        W.patch_b = arr("embeddings.patch_embeddings.projection.bias")
-        W.lnf_g, W.lnf_b = arr("layernorm.weight"), arr("layernorm.bias")
-        W.layer = layers
-        return W, layers
+    def _weights_struct(kind, geom, arr, pos=None, **special):
+        """The weight struct of encoder `kind` (a key of encoders.ENCODER_TABLE) at `geom` (+ its layer array, with DINOv2's
+        scale array in a pair, which the caller keeps alive).  Tensor pointers come from arr(name, first_element = 0) over the
+        names of the record's tensor_specs; a tensor this geometry does not have (CLIP without a projection) stays null.  `pos`
+        (DINOv2): the pointer of the f32 [257, D] position table; `logits` (SigLIP text): see _siglip_text_scalars; `gate` (the
+        tile tower, which keeps its own builder): scalar gates from gate(name)."""
+        from .encoders import ENCODER_TABLE
+
+        rec = ENCODER_TABLE[kind]
+        if rec.block is None:
+            return Engine._tile_struct(geom, arr, **special)
+        W = rec.struct()
+        rec.scalars(W, geom, **special)
+        layers = (_Layer * max(0, int(geom.num_layers)))()
+        scales = (_Dinov2Scale * len(layers))() if hasattr(W, "scale") else None
+        _fill_layers(layers, rec.layer_names, arr, scales)
+        V = getattr(W, "vit", W)  # mme_vit_weights: the struct itself, or the one an image tower's struct begins with
+        present = {s[0] for s in rec.tensor_specs(dataclasses.replace(geom, num_layers=0))}  # the names outside the layers that this geometry has
+        for fld, name in rec.top.items():
+            ptr = pos if fld == "pos_emb" and pos is not None else arr(name) if name in present else None
+            setattr(W if hasattr(W, fld) else V, fld, ptr)
+        if rec.fill:
+            rec.fill(W, geom, arr)
+        V.layer = layers
+        if scales is None:
+            return W, layers
+        W.scale = scales
+        return W, (layers, scales)
+
+    def _load(self, kind, w: dict, geom=None):
+        """A dict of f32 arrays under the names of the record's tensor_specs -> this context (the text range of it for a text
+        tower), prepared by the host.  `geom` defaults to what the tensor shapes say; every tensor's element count is checked
+        against it here, the geometry itself against the supported set by the library."""
+        from .encoders import ENCODER_TABLE
+
+        rec = ENCODER_TABLE[kind]
+        if rec.host_geometry:
+            geom = rec.host_geometry(w, geom)
+        elif geom is None:
+            geom = rec.infer_geometry(w)
+        for name, shape, _ in rec.tensor_specs(geom) if not rec.library_refuses_depth or 0 < geom.num_layers <= 64 else ():
+            if name not in w:
+                raise MmeError(f"{rec.loader}: tensor {name!r} is missing")
+            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                raise MmeError(f"{rec.loader}: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = {}
+
+        def arr(name, first=0):
+            if name not in keep:
+                keep[name] = np.ascontiguousarray(w[name], dtype=np.float32).reshape(-1)
+            return _fp(keep[name][first:])
+
+        special, held = rec.special(w.get, None) if rec.special else ({}, None)
+        W, arrays = self._weights_struct(kind, geom, arr, **special)
+        self._check(getattr(self.lib, rec.symbol)(self.h, C.byref(W)), rec.symbol)
+
+    @staticmethod
+    def _ckpt_ptr(ckpt, name, first=0):
+        t = ckpt.tensors[name]
+        if not t.is_contiguous() or t.device.type != "cpu":
+            raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
+        return C.cast(C.c_void_p(t.data_ptr() + first * t.element_size()), C.POINTER(C.c_float))  # elements of ckpt.dtype behind the struct's float*
+
+    def _load_checkpoint(self, kind, ckpt):
+        """`checkpoint.read_checkpoint(dir, kind)` -> this context at the checkpoint's geometry: the raw f32 / bf16 / f16 bytes go
+        to the device and are converted, scaled and LayerNorm-folded there, bit-identically to `_load` on the same values."""
+        from .encoders import ENCODER_TABLE
+
+        rec = ENCODER_TABLE[kind]
+        if getattr(ENCODER_TABLE.get(ckpt.encoder), "symbol", None) != rec.symbol:  # "vit_b16" and "vit" share one loader
+            raise MmeError(f"{rec.loader}_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
+        special, held = rec.special(ckpt.tensors.get, ckpt.extra) if rec.special else ({}, None)
+        W, arrays = self._weights_struct(kind, ckpt.geometry, lambda name, first=0: self._ckpt_ptr(ckpt, name, first), **special)
+        self._check(getattr(self.lib, rec.symbol + "_as")(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), rec.symbol + "_as")
 
     def load_vit(self, w: dict, eps: float | None = None, geom=None):
         """Canonical-name dict of f32 arrays (weights.vit_tensor_specs) -> this context, replacing what it held.  The
-        geometry is `geom` (a weights.ViTGeometry) or, by default, read off the tensor shapes (heads of 64); every tensor's
-        shape is checked against it here, the geometry itself against the supported set by the library.  `eps` overrides
+        geometry is `geom` (a weights.ViTGeometry) or, by default, read off the tensor shapes (heads of 64).  `eps` overrides
         the geometry's layer_norm_eps."""
-        import dataclasses
-
-        from .weights import infer_vit_geometry, vit_tensor_specs
-
-        if geom is None:
-            geom = infer_vit_geometry(w)
         if eps is not None:
-            geom = dataclasses.replace(geom, layer_norm_eps=float(eps))
-        for name, shape, _ in vit_tensor_specs(geom):
-            if name not in w:
-                raise MmeError(f"load_vit: tensor {name!r} is missing")
-            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
-                raise MmeError(f"load_vit: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
-        keep = []
+            geom = dataclasses.replace(infer_vit_geometry(w) if geom is None else geom, layer_norm_eps=float(eps))
+        self._load("vit", w, geom)
 
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            keep.append(a)
-            return _fp(a)
-
-        W, layers = self._vit_struct(geom, arr)
-        self._check(self.lib.mme_load_vit(self.h, C.byref(W)), "mme_load_vit")
+    def load_vit_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "vit_b16" | "vit")` -> this context.  Replaces what the context held."""
+        self._load_checkpoint("vit", ckpt)
 
     def vit_geometry(self):
         """The weights.ViTGeometry this context runs (mme_vit_geometry): that of its last load, ViT-B/16 before any.
@@ -451,8 +597,6 @@ class Engine:
 
     def encoder_info(self) -> dict:
         """What the last load brought (mme_encoder_info): {"kind": "vit" | "clip" | "siglip" | "dinov2", "embed_dim", "hidden_act", "projection_dim"}."""
-        from .weights import CLIP_ACTS
-
         o = (C.c_int32 * 4)()
         self._check(self.lib.mme_encoder_info(self.h, o), "mme_encoder_info")
         acts = CLIP_ACTS + ("gelu_pytorch_tanh",)  # the library's act codes: 0, 1 (mme_clip_weights.act), 2 (SigLIP)
@@ -463,232 +607,36 @@ class Engine:
         """Width of the rows `vit_forward` / `embed` return: the hidden size, or a CLIP tower's projection_dim."""
         return self.encoder_info()["embed_dim"]
 
-    # ---- CLIP image towers (mme_load_clip*) -----------------------------------------------------------------
-    @staticmethod
-    def _clip_struct(geom, arr):
-        """mme_clip_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.CLIPGeometry), tensor
-        pointers from arr(name) over the names of weights.clip_tensor_specs."""
-        from .weights import CLIP_ACTS
-
-        v = "vision_model."
-        layers = (_Layer * geom.num_layers)()
-        for i in range(geom.num_layers):
-            p = f"{v}encoder.layers.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
-            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
-            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
-            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
-            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
-            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        W = _ClipWeights()
-        W.vit = _Weights(geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
-                         float(geom.layer_norm_eps))
-        W.vit.cls_token = arr(v + "embeddings.class_embedding")
-        W.vit.pos_emb = arr(v + "embeddings.position_embedding.weight")
-        W.vit.patch_w = arr(v + "embeddings.patch_embedding.weight")
-        W.vit.patch_b = None  # CLIPVisionEmbeddings: bias=False
-        W.vit.lnf_g, W.vit.lnf_b = arr(v + "post_layernorm.weight"), arr(v + "post_layernorm.bias")
-        W.vit.layer = layers
-        W.pre_g, W.pre_b = arr(v + "pre_layrnorm.weight"), arr(v + "pre_layrnorm.bias")
-        W.proj_w = arr("visual_projection.weight") if geom.projection_dim else None
-        W.proj_dim = int(geom.projection_dim or 0)
-        if geom.hidden_act not in CLIP_ACTS:
-            raise MmeError(f"hidden_act = {geom.hidden_act!r}; supported: {', '.join(CLIP_ACTS)}")
-        W.act = CLIP_ACTS.index(geom.hidden_act)
-        return W, layers
-
+    # ---- the other image towers: each load replaces what the context held ----------------------------------------------------
     def load_clip(self, w: dict, geom=None):
         """`weights.clip_tensor_specs` dict of f32 arrays (the state dict of transformers' CLIPVisionModelWithProjection, or
-        of CLIPVisionModel: no visual_projection) -> this context, replacing what it held.  `geom`: a weights.CLIPGeometry;
-        by default read off the tensor shapes, with QuickGELU and eps 1e-5 (clip-vit-base-patch16's)."""
-        from .weights import clip_tensor_specs, infer_clip_geometry
-
-        if geom is None:
-            geom = infer_clip_geometry(w)
-        for name, shape, _ in clip_tensor_specs(geom):
-            if name not in w:
-                raise MmeError(f"load_clip: tensor {name!r} is missing")
-            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
-                raise MmeError(f"load_clip: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
-        keep = []
-
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            keep.append(a)
-            return _fp(a)
-
-        W, layers = self._clip_struct(geom, arr)
-        self._check(self.lib.mme_load_clip(self.h, C.byref(W)), "mme_load_clip")
+        of CLIPVisionModel: no visual_projection).  `geom`: a weights.CLIPGeometry; by default read off the tensor shapes, with
+        QuickGELU and eps 1e-5 (clip-vit-base-patch16's)."""
+        self._load("clip", w, geom)
 
     def load_clip_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "clip")` -> this context, prepared on the device from the file's own f32 / bf16 / f16
-        bytes, bit-identically to `load_clip` on the same values.  Replaces what the context held."""
-        if ckpt.encoder != "clip":
-            raise MmeError(f"load_clip_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        W, layers = self._clip_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
-        self._check(self.lib.mme_load_clip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_clip_as")
-
-    # ---- SigLIP image towers (mme_load_siglip*) ---------------------------------------------------------------
-    @staticmethod
-    def _siglip_struct(geom, arr):
-        """mme_siglip_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.SiglipGeometry), tensor
-        pointers from arr(name, first_element = 0) over the names of weights.siglip_tensor_specs.  in_proj_weight [3 D, D] and
-        in_proj_bias [3 D] are split q | k | v by element offset."""
-        from .weights import siglip_geometry_problem
-
-        bad = siglip_geometry_problem(geom)
-        if bad and bad[0] in ("hidden_act", "vision_use_head"):  # the two fields the C struct does not carry
-            raise MmeError(f"{bad[0]} = {bad[1]!r}; supported: {bad[2]}")
-        v = "vision_model."
-        D = geom.hidden_size
-        layers = (_Layer * geom.num_layers)()
-        for i in range(geom.num_layers):
-            p = f"{v}encoder.layers.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
-            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
-            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
-            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
-            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
-            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        W = _SiglipWeights()
-        W.vit = _Weights(geom.image_size, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
-                         float(geom.layer_norm_eps))
-        W.vit.cls_token = None  # SiglipVisionEmbeddings: no class token
-        W.vit.pos_emb = arr(v + "embeddings.position_embedding.weight")
-        W.vit.patch_w = arr(v + "embeddings.patch_embedding.weight")
-        W.vit.patch_b = arr(v + "embeddings.patch_embedding.bias")
-        W.vit.lnf_g, W.vit.lnf_b = arr(v + "post_layernorm.weight"), arr(v + "post_layernorm.bias")
-        W.vit.layer = layers
-        h = v + "head."
-        W.probe = arr(h + "probe")
-        H = W.head
-        H.ln1_g = H.ln1_b = None
-        H.q_w, H.k_w, H.v_w = (arr(h + "attention.in_proj_weight", i * D * D) for i in range(3))
-        H.q_b, H.k_b, H.v_b = (arr(h + "attention.in_proj_bias", i * D) for i in range(3))
-        H.o_w, H.o_b = arr(h + "attention.out_proj.weight"), arr(h + "attention.out_proj.bias")
-        H.ln2_g, H.ln2_b = arr(h + "layernorm.weight"), arr(h + "layernorm.bias")
-        H.fc1_w, H.fc1_b = arr(h + "mlp.fc1.weight"), arr(h + "mlp.fc1.bias")
-        H.fc2_w, H.fc2_b = arr(h + "mlp.fc2.weight"), arr(h + "mlp.fc2.bias")
-        return W, layers
+        """`checkpoint.read_checkpoint(dir, "clip")`, prepared on the device bit-identically to `load_clip` on the same values."""
+        self._load_checkpoint("clip", ckpt)
 
     def load_siglip(self, w: dict, geom=None):
-        """`weights.siglip_tensor_specs` dict of f32 arrays (the vision state dict of transformers' SiglipModel) -> this
-        context, replacing what it held.  `geom`: a weights.SiglipGeometry; by default read off the tensor shapes, eps 1e-6."""
-        from .weights import infer_siglip_geometry, siglip_tensor_specs
-
-        if geom is None:
-            geom = infer_siglip_geometry(w)
-        for name, shape, _ in siglip_tensor_specs(geom):
-            if name not in w:
-                raise MmeError(f"load_siglip: tensor {name!r} is missing")
-            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
-                raise MmeError(f"load_siglip: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
-        keep = {}
-
-        def arr(name, first=0):
-            if name not in keep:
-                keep[name] = np.ascontiguousarray(w[name], dtype=np.float32).reshape(-1)
-            return _fp(keep[name][first:])
-
-        W, layers = self._siglip_struct(geom, arr)
-        self._check(self.lib.mme_load_siglip(self.h, C.byref(W)), "mme_load_siglip")
+        """`weights.siglip_tensor_specs` dict of f32 arrays (the vision state dict of transformers' SiglipModel).  `geom`: a
+        weights.SiglipGeometry; by default read off the tensor shapes, eps 1e-6."""
+        self._load("siglip", w, geom)
 
     def load_siglip_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "siglip")` -> this context, prepared on the device from the file's own f32 / bf16 /
-        f16 bytes, bit-identically to `load_siglip` on the same values.  Replaces what the context held."""
-        if ckpt.encoder != "siglip":
-            raise MmeError(f"load_siglip_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-
-        def arr(name, first=0):
-            t = ckpt.tensors[name]
-            if not t.is_contiguous() or t.device.type != "cpu":
-                raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
-            return C.cast(C.c_void_p(t.data_ptr() + first * t.element_size()), C.POINTER(C.c_float))
-
-        W, layers = self._siglip_struct(ckpt.geometry, arr)
-        self._check(self.lib.mme_load_siglip_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_siglip_as")
-
-    # ---- DINOv2 image towers (mme_load_dinov2*) ---------------------------------------------------------------
-    @staticmethod
-    def _dinov2_struct(geom, arr, pos):
-        """mme_dinov2_weights (+ the layer and scale arrays, which the caller keeps alive) for `geom` (weights.Dinov2Geometry),
-        tensor pointers from arr(name) over the names of weights.dinov2_tensor_specs; `pos`: pointer to the f32 [257, D] table."""
-        from .weights import dinov2_geometry_problem
-
-        bad = dinov2_geometry_problem(geom)
-        if bad and bad[0] in ("hidden_act", "use_swiglu_ffn", "num_register_tokens", "position_grid"):  # the fields the C struct does not carry
-            raise MmeError(f"{bad[0]} = {bad[1]!r}; supported: {bad[2]}")
-        layers = (_Layer * geom.num_layers)()
-        scales = (_Dinov2Scale * geom.num_layers)()
-        for i in range(geom.num_layers):
-            p = f"encoder.layer.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "norm1.weight"), arr(p + "norm1.bias")
-            L.q_w, L.q_b = arr(p + "attention.attention.query.weight"), arr(p + "attention.attention.query.bias")
-            L.k_w, L.k_b = arr(p + "attention.attention.key.weight"), arr(p + "attention.attention.key.bias")
-            L.v_w, L.v_b = arr(p + "attention.attention.value.weight"), arr(p + "attention.attention.value.bias")
-            L.o_w, L.o_b = arr(p + "attention.output.dense.weight"), arr(p + "attention.output.dense.bias")
-            L.ln2_g, L.ln2_b = arr(p + "norm2.weight"), arr(p + "norm2.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-            scales[i].lambda1, scales[i].lambda2 = arr(p + "layer_scale1.lambda1"), arr(p + "layer_scale2.lambda1")
-        W = _Dinov2Weights()
-        W.vit = _Weights(224, geom.patch_size, geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size, float(geom.layer_norm_eps))
-        W.vit.cls_token = arr("embeddings.cls_token")
-        W.vit.pos_emb = pos
-        W.vit.patch_w = arr("embeddings.patch_embeddings.projection.weight")
-        W.vit.patch_b = arr("embeddings.patch_embeddings.projection.bias")
-        W.vit.lnf_g, W.vit.lnf_b = arr("layernorm.weight"), arr("layernorm.bias")
-        W.vit.layer = layers
-        W.scale = scales
-        return W, (layers, scales)
+        """`checkpoint.read_checkpoint(dir, "siglip")`, prepared on the device bit-identically to `load_siglip` on the same values."""
+        self._load_checkpoint("siglip", ckpt)
 
     def load_dinov2(self, w: dict, geom=None):
-        """`weights.dinov2_tensor_specs` dict of f32 arrays (the state dict of transformers' Dinov2Model) -> this context,
-        replacing what it held.  `geom`: a weights.Dinov2Geometry; by default read off the tensor shapes, eps 1e-6.  The position
-        table (257 rows, or 1 + g * g of a g x g grid) is interpolated to 16 x 16 here, once, as the model does on every forward."""
-        import dataclasses
-
-        from .checkpoint import DINOV2_POSITIONS, interpolate_dinov2_positions
-        from .weights import dinov2_tensor_specs, infer_dinov2_geometry
-
-        try:
-            found = infer_dinov2_geometry(w)
-        except ValueError as e:
-            raise MmeError(f"load_dinov2: {e}") from e
-        geom = found if geom is None else dataclasses.replace(geom, position_grid=found.position_grid)
-        for name, shape, _ in dinov2_tensor_specs(geom) if 0 < geom.num_layers <= 64 else ():
-            if name not in w:
-                raise MmeError(f"load_dinov2: tensor {name!r} is missing")
-            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
-                raise MmeError(f"load_dinov2: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
-        keep = []
-
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            keep.append(a)
-            return _fp(a)
-
-        pos = interpolate_dinov2_positions(self.torch.from_numpy(np.ascontiguousarray(w[DINOV2_POSITIONS], dtype=np.float32))).numpy()
-        keep.append(pos)
-        W, arrays = self._dinov2_struct(geom, arr, _fp(pos))
-        self._check(self.lib.mme_load_dinov2(self.h, C.byref(W)), "mme_load_dinov2")
+        """`weights.dinov2_tensor_specs` dict of f32 arrays (the state dict of transformers' Dinov2Model).  `geom`: a
+        weights.Dinov2Geometry; by default read off the tensor shapes, eps 1e-6.  The position table (257 rows, or 1 + g * g of a
+        g x g grid) is interpolated to 16 x 16 here, once, as the model does on every forward."""
+        self._load("dinov2", w, geom)
 
     def load_dinov2_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "dinov2")` -> this context, prepared on the device from the file's own f32 / bf16 /
-        f16 bytes, bit-identically to `load_dinov2` on the same values.  The position table is the checkpoint object's
-        interpolated f32 table under every dtype.  Replaces what the context held."""
-        if ckpt.encoder != "dinov2":
-            raise MmeError(f"load_dinov2_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        pos = ckpt.extra["position_table"]
-        W, arrays = self._dinov2_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name), C.cast(C.c_void_p(pos.data_ptr()), C.POINTER(C.c_float)))
-        self._check(self.lib.mme_load_dinov2_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_dinov2_as")
+        """`checkpoint.read_checkpoint(dir, "dinov2")`, prepared on the device bit-identically to `load_dinov2` on the same values.
+        The position table is the checkpoint object's interpolated f32 table under every dtype."""
+        self._load_checkpoint("dinov2", ckpt)
 
     DINOV2_OPS = {"retile": 0, "embed_rows": 1, "attention": 2, "pool_ln_l2": 3, "rowscale": 4, "mul": 5}
 
@@ -707,72 +655,19 @@ class Engine:
         self._check(self.lib.mme_dinov2_apply(self.h, int(self.DINOV2_OPS.get(op, op)), C.byref(a), self._stream()), "mme_dinov2_apply")
 
     # ---- CLIP text tower (mme_load_clip_text*): lives beside the image tower of the same context ----------------------------
-    @staticmethod
-    def _clip_text_struct(geom, arr):
-        """mme_clip_text_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.CLIPTextGeometry),
-        tensor pointers from arr(name) over the names of weights.clip_text_tensor_specs."""
-        from .weights import CLIP_ACTS
-
-        t = "text_model."
-        layers = (_Layer * geom.num_layers)()
-        for i in range(geom.num_layers):
-            p = f"{t}encoder.layers.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
-            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
-            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
-            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
-            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
-            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        if geom.hidden_act not in CLIP_ACTS:
-            raise MmeError(f"hidden_act = {geom.hidden_act!r}; supported: {', '.join(CLIP_ACTS)}")
-        W = _ClipTextWeights(geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size, geom.vocab_size,
-                             geom.max_position_embeddings, int(geom.projection_dim or 0), CLIP_ACTS.index(geom.hidden_act), int(geom.eos_token_id),
-                             float(geom.layer_norm_eps))
-        W.token_emb = arr(t + "embeddings.token_embedding.weight")
-        W.pos_emb = arr(t + "embeddings.position_embedding.weight")
-        W.lnf_g, W.lnf_b = arr(t + "final_layer_norm.weight"), arr(t + "final_layer_norm.bias")
-        W.proj_w = arr("text_projection.weight") if geom.projection_dim else None
-        W.layer = layers
-        return W, layers
-
     def load_clip_text(self, w: dict, geom=None):
         """`weights.clip_text_tensor_specs` dict of f32 arrays (the state dict of transformers' CLIPTextModelWithProjection, or
         of CLIPTextModel: no text_projection) -> the text tower of this context, replacing an earlier text tower and nothing
         else.  `geom`: a weights.CLIPTextGeometry; by default read off the tensor shapes (weights.infer_clip_text_geometry)."""
-        from .weights import clip_text_tensor_specs, infer_clip_text_geometry
-
-        if geom is None:
-            geom = infer_clip_text_geometry(w)
-        for name, shape, _ in clip_text_tensor_specs(geom):
-            if name not in w:
-                raise MmeError(f"load_clip_text: tensor {name!r} is missing")
-            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
-                raise MmeError(f"load_clip_text: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
-        keep = []
-
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            keep.append(a)
-            return _fp(a)
-
-        W, layers = self._clip_text_struct(geom, arr)
-        self._check(self.lib.mme_load_clip_text(self.h, C.byref(W)), "mme_load_clip_text")
+        self._load("clip_text", w, geom)
 
     def load_clip_text_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "clip_text")` -> the text tower of this context, prepared on the device from the
-        file's own f32 / bf16 / f16 bytes, bit-identically to `load_clip_text` on the same values."""
-        if ckpt.encoder != "clip_text":
-            raise MmeError(f"load_clip_text_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        W, layers = self._clip_text_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
-        self._check(self.lib.mme_load_clip_text_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_clip_text_as")
+        """`checkpoint.read_checkpoint(dir, "clip_text")` -> the text tower of this context, prepared on the device
+        bit-identically to `load_clip_text` on the same values."""
+        self._load_checkpoint("clip_text", ckpt)
 
     def text_info(self) -> dict:
         """The text tower of this context (mme_text_info); every number 0 and hidden_act None before a text load."""
-        from .weights import CLIP_ACTS
-
         o = (C.c_int32 * 9)()
         self._check(self.lib.mme_text_info(self.h, o), "mme_text_info")
         acts = tuple(CLIP_ACTS) + ("gelu_pytorch_tanh",)  # EncoderPass::act; 2 under a SigLIP text tower, whose last word is pad_token_id
@@ -837,78 +732,16 @@ class Engine:
         self._check(self.lib.mme_text_apply(self.h, int(self.TEXT_OPS.get(op, op)), C.byref(a), self._stream()), "mme_text_apply")
 
     # ---- SigLIP text tower (mme_load_siglip_text*): takes the text range of the context, beside whatever image tower it holds ----
-    @staticmethod
-    def _siglip_text_struct(geom, arr, logits):
-        """mme_siglip_text_weights (+ the layer array, which the caller keeps alive) for `geom` (weights.SiglipTextGeometry),
-        tensor pointers from arr(name) over the names of weights.siglip_text_tensor_specs; `logits` (logit_scale, logit_bias) or None."""
-        from .weights import siglip_text_geometry_problem
-
-        bad = siglip_text_geometry_problem(geom)
-        if bad and bad[0] == "hidden_act":  # the struct has no field for it: the library runs tanh-GELU
-            raise MmeError(f"hidden_act = {bad[1]!r}; supported: {bad[2]}")
-        t = "text_model."
-        layers = (_Layer * max(0, int(geom.num_layers)))()
-        for i in range(len(layers)):
-            p = f"{t}encoder.layers.{i}."
-            L = layers[i]
-            L.ln1_g, L.ln1_b = arr(p + "layer_norm1.weight"), arr(p + "layer_norm1.bias")
-            L.q_w, L.q_b = arr(p + "self_attn.q_proj.weight"), arr(p + "self_attn.q_proj.bias")
-            L.k_w, L.k_b = arr(p + "self_attn.k_proj.weight"), arr(p + "self_attn.k_proj.bias")
-            L.v_w, L.v_b = arr(p + "self_attn.v_proj.weight"), arr(p + "self_attn.v_proj.bias")
-            L.o_w, L.o_b = arr(p + "self_attn.out_proj.weight"), arr(p + "self_attn.out_proj.bias")
-            L.ln2_g, L.ln2_b = arr(p + "layer_norm2.weight"), arr(p + "layer_norm2.bias")
-            L.fc1_w, L.fc1_b = arr(p + "mlp.fc1.weight"), arr(p + "mlp.fc1.bias")
-            L.fc2_w, L.fc2_b = arr(p + "mlp.fc2.weight"), arr(p + "mlp.fc2.bias")
-        W = _SiglipTextWeights(geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size, geom.vocab_size, geom.max_position_embeddings,
-                               int(geom.projection_size), int(geom.pad_token_id), int(logits is not None), float(geom.layer_norm_eps),
-                               float(logits[0]) if logits else 0.0, float(logits[1]) if logits else 0.0)
-        W.token_emb = arr(t + "embeddings.token_embedding.weight")
-        W.pos_emb = arr(t + "embeddings.position_embedding.weight")
-        W.lnf_g, W.lnf_b = arr(t + "final_layer_norm.weight"), arr(t + "final_layer_norm.bias")
-        W.head_w, W.head_b = arr(t + "head.weight"), arr(t + "head.bias")
-        W.layer = layers
-        return W, layers
-
-    @staticmethod
-    def _siglip_logits(get):
-        """(logit_scale, logit_bias) as floats from get(name) -> a one-value array / tensor or None; None when both are absent."""
-        vals = [get(k) for k in ("logit_scale", "logit_bias")]
-        if vals[0] is None and vals[1] is None:
-            return None
-        if vals[0] is None or vals[1] is None:
-            raise MmeError("load_siglip_text: logit_scale and logit_bias come together (a whole SiglipModel) or not at all")
-        return tuple(float(np.asarray(v.float() if hasattr(v, "float") and not isinstance(v, np.ndarray) else v, dtype=np.float32).reshape(-1)[0]) for v in vals)
-
     def load_siglip_text(self, w: dict, geom=None):
         """`weights.siglip_text_tensor_specs` dict of f32 arrays (the text half of transformers' SiglipModel state dict; with
         `logit_scale` / `logit_bias` beside the tensors, `siglip_scores` works) -> the text tower of this context, replacing an
         earlier text tower of either kind and nothing else.  `geom`: a weights.SiglipTextGeometry; by default read off the shapes."""
-        from .weights import infer_siglip_text_geometry, siglip_text_tensor_specs
-
-        if geom is None:
-            geom = infer_siglip_text_geometry(w)
-        for name, shape, _ in siglip_text_tensor_specs(geom) if 0 < geom.num_layers <= 64 else ():
-            if name not in w:
-                raise MmeError(f"load_siglip_text: tensor {name!r} is missing")
-            if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
-                raise MmeError(f"load_siglip_text: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
-        keep = []
-
-        def arr(name):
-            a = np.ascontiguousarray(w[name], dtype=np.float32)
-            keep.append(a)
-            return _fp(a)
-
-        W, layers = self._siglip_text_struct(geom, arr, self._siglip_logits(w.get))
-        self._check(self.lib.mme_load_siglip_text(self.h, C.byref(W)), "mme_load_siglip_text")
+        self._load("siglip_text", w, geom)
 
     def load_siglip_text_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "siglip_text")` -> the text tower of this context, prepared on the device from the
-        file's own f32 / bf16 / f16 bytes, bit-identically to `load_siglip_text` on the same values."""
-        if ckpt.encoder != "siglip_text":
-            raise MmeError(f"load_siglip_text_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        W, layers = self._siglip_text_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name), self._siglip_logits(ckpt.tensors.get))
-        self._check(self.lib.mme_load_siglip_text_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_siglip_text_as")
+        """`checkpoint.read_checkpoint(dir, "siglip_text")` -> the text tower of this context, prepared on the device
+        bit-identically to `load_siglip_text` on the same values."""
+        self._load_checkpoint("siglip_text", ckpt)
 
     def siglip_scores(self, cos, out=None):
         """f32 CUDA cosine block [m, N] (`cosine`) -> sigmoid(exp(logit_scale) cos + logit_bias), f32 [m, N] (mme_siglip_scores):
@@ -997,22 +830,6 @@ class Engine:
         self.tile_features = geom.output_dim
 
     # ---- weights from a checkpoint, in the file's own dtype, prepared on the device (mme_load_*_as) ------------
-    @staticmethod
-    def _ckpt_ptr(ckpt, name):
-        t = ckpt.tensors[name]
-        if not t.is_contiguous() or t.device.type != "cpu":
-            raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
-        return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))  # elements of ckpt.dtype behind the struct's float*
-
-    def load_vit_checkpoint(self, ckpt):
-        """`checkpoint.read_checkpoint(dir, "vit_b16" | "vit")` -> this context, at the checkpoint's geometry: the raw f32 /
-        bf16 / f16 bytes go to the device and are converted, scaled and LayerNorm-folded there, bit-identically to
-        `load_vit` on the same values.  Replaces what the context held."""
-        if ckpt.encoder not in ("vit_b16", "vit"):
-            raise MmeError(f"load_vit_checkpoint: the checkpoint was read for encoder {ckpt.encoder!r}")
-        W, layers = self._vit_struct(ckpt.geometry, lambda name: self._ckpt_ptr(ckpt, name))
-        self._check(self.lib.mme_load_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_vit_as")
-
     def load_tile_vit_checkpoint(self, ckpt, geometry=None):
         """`checkpoint.read_checkpoint(dir, "mllama_tiles")` -> the tile-ViT encoder of this context, prepared on the device.
         `geometry` overrides the checkpoint's (the save point of the intermediate states is not in the file)."""

@@ -31,10 +31,9 @@ from dataclasses import dataclass, field
 
 from . import config
 from ._lib import MmeError
-from .weights import (CLIP_B16, CLIP_TEXT_B, DINOV2_B14, SIGLIP_B16, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry, Dinov2Geometry, SiglipGeometry,
-                      TileViTGeometry, ViTGeometry, dinov2_geometry_problem, dinov2_tensor_specs, clip_geometry_problem, clip_tensor_specs, clip_text_geometry_problem, clip_text_tensor_specs, siglip_geometry_problem,
-                      siglip_tensor_specs, siglip_text_geometry_problem, siglip_text_tensor_specs, tile_vit_tensor_specs, vit_geometry_problem,
-                      vit_tensor_specs)
+from .weights import (CLIP_B16, CLIP_TEXT_B, DINOV2_B14, SIGLIP_B16, SIGLIP_LOGIT_KEYS, SIGLIP_TEXT_B, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry,
+                      Dinov2Geometry, SiglipGeometry, SiglipTextGeometry, TileViTGeometry, ViTGeometry, clip_geometry_problem, clip_text_geometry_problem,
+                      dinov2_geometry_problem, siglip_geometry_problem, siglip_text_geometry_problem, vit_geometry_problem)
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
@@ -213,151 +212,146 @@ def _expect(cfg: dict, fld: str, built, where: str, default=None):
         raise MmeError(f"{where}: {fld} = {found!r}, but this library is built for {fld} = {built!r}")
 
 
-def _vit_geometry(cfg: dict, where: str) -> ViTGeometry:
-    g = VIT_B16
+# Every function below is an `encoders.Encoder.config_geometry`: (config.json as a dict, the directory) -> (geometry, where the
+# tower's fields were found, for the messages).  A whole two-tower model keeps them under vision_config / text_config.
+def _sub_config(cfg: dict, key: str):
+    if key in cfg:
+        return dict(cfg[key]), f"config.json: {key}"
+    return cfg, "config.json"
+
+
+def _ints(cfg: dict, where: str, fields: dict) -> dict:
+    """cfg's value of every field (`fields`: name -> default, None where the file must name it), each an integer or refused."""
+    out = {}
+    for fld, default in fields.items():
+        out[fld] = cfg.get(fld, default)
+        if not isinstance(out[fld], int) or isinstance(out[fld], bool):
+            raise MmeError(f"{where}: {fld} = {out[fld]!r}; an integer is required")
+    return out
+
+
+def _refuse(bad, where: str):
+    """Raises for a `*_geometry_problem` finding, under the name config.json gives the field."""
+    if bad:
+        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
+        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+
+
+def _image_fields(cfg: dict, where: str, b) -> dict:
+    """The ViTGeometry arguments of an image tower's config: the six sizes required as integers, the rest defaulting to b's."""
+    v = _ints(cfg, where, dict.fromkeys(("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size")))
+    return dict(image_size=v["image_size"], patch_size=v["patch_size"], num_channels=cfg.get("num_channels", b.num_channels), hidden_size=v["hidden_size"],
+                num_layers=v["num_hidden_layers"], num_heads=v["num_attention_heads"], intermediate_size=v["intermediate_size"],
+                layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
+
+
+def _text_fields(cfg: dict, where: str, b, token_id: str) -> dict:
+    """The arguments the two text geometries share; a field the file leaves out has b's value, as transformers reads it."""
+    v = _ints(cfg, where, {"hidden_size": b.hidden_size, "num_hidden_layers": b.num_layers, "num_attention_heads": b.num_heads,
+                           "intermediate_size": b.intermediate_size, "vocab_size": b.vocab_size, "max_position_embeddings": b.max_position_embeddings,
+                           token_id: getattr(b, token_id)})
+    return dict(hidden_size=v["hidden_size"], num_layers=v["num_hidden_layers"], num_heads=v["num_attention_heads"], intermediate_size=v["intermediate_size"],
+                vocab_size=v["vocab_size"], max_position_embeddings=v["max_position_embeddings"], hidden_act=cfg.get("hidden_act", b.hidden_act),
+                layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)), **{token_id: v[token_id]})
+
+
+def _vit_geometry(cfg: dict, path: str):
+    g, where = VIT_B16, "config.json"
     for fld, built in (("image_size", g.image_size), ("patch_size", g.patch_size), ("hidden_size", g.hidden_size),
                        ("num_hidden_layers", g.num_layers), ("num_attention_heads", g.num_heads), ("intermediate_size", g.intermediate_size),
                        ("num_channels", g.num_channels)):
         _expect(cfg, fld, built, where, default=built if fld == "num_channels" else None)
     _expect(cfg, "hidden_act", "gelu", where)
     _expect(cfg, "qkv_bias", True, where, default=True)
-    return ViTGeometry(layer_norm_eps=float(cfg.get("layer_norm_eps", g.layer_norm_eps)))
+    return ViTGeometry(layer_norm_eps=float(cfg.get("layer_norm_eps", g.layer_norm_eps))), where
 
 
-def _vit_family_geometry(cfg: dict, where: str) -> ViTGeometry:
+def _vit_family_geometry(cfg: dict, path: str):
     """config.json of any ViT/16 or ViT/32 @224 the engine runs (weights.SUPPORTED_VIT); a field outside the set is refused with the
     field, the value found and the supported values."""
-    b = VIT_B16
-    for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
-        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
-            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
-    g = ViTGeometry(image_size=cfg["image_size"], patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels),
-                    hidden_size=cfg["hidden_size"], num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"],
-                    intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
-    bad = vit_geometry_problem(g)
-    if bad:
-        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
-        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    where = "config.json"
+    g = ViTGeometry(**_image_fields(cfg, where, VIT_B16))
+    _refuse(vit_geometry_problem(g), where)
     _expect(cfg, "hidden_act", "gelu", where)
     _expect(cfg, "qkv_bias", True, where, default=True)
-    return g
+    return g, where
 
 
-def _clip_geometry(cfg: dict, where: str, projection_dim) -> CLIPGeometry:
+def _clip_geometry(cfg: dict, path: str):
     """The vision configuration of a CLIP checkpoint (CLIPVisionConfig) -> geometry; the same supported set as "vit", plus
-    hidden_act and projection_dim.  `projection_dim` is what the file that holds `cfg` says (a whole CLIP config names it
-    at its top level); whether the checkpoint has a visual_projection at all is decided by its tensors."""
-    b = CLIP_B16
-    for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
-        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
-            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
-    g = CLIPGeometry(image_size=cfg["image_size"], patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels),
-                     hidden_size=cfg["hidden_size"], num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"],
-                     intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)),
-                     projection_dim=projection_dim, hidden_act=cfg.get("hidden_act", b.hidden_act))
-    bad = clip_geometry_problem(g)
-    if bad:
-        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
-        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
-    return g
+    hidden_act and projection_dim.  A whole CLIP config names projection_dim at its top level; whether the checkpoint has a
+    visual_projection at all is decided by its tensors (`_optional_projection`)."""
+    vcfg, where = _sub_config(cfg, "vision_config")
+    if vcfg is not cfg and "projection_dim" in cfg:
+        vcfg["projection_dim"] = cfg["projection_dim"]
+    g = CLIPGeometry(**_image_fields(vcfg, where, CLIP_B16), projection_dim=vcfg.get("projection_dim"), hidden_act=vcfg.get("hidden_act", CLIP_B16.hidden_act))
+    _refuse(clip_geometry_problem(g), where)
+    return g, where
 
 
-def _siglip_geometry(cfg: dict, where: str) -> SiglipGeometry:
+def _siglip_geometry(cfg: dict, path: str):
     """The vision configuration of a SigLIP checkpoint (SiglipVisionConfig) -> geometry: patch 16 at 224 pixels, heads of 64,
     `gelu_pytorch_tanh`, the pooling head.  A field the file leaves out has SiglipVisionConfig's default, except the sizes."""
-    b = SIGLIP_B16
-    for fld in ("image_size", "patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size"):
-        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
-            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
-    g = SiglipGeometry(image_size=cfg["image_size"], patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels),
-                       hidden_size=cfg["hidden_size"], num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"],
-                       intermediate_size=cfg["intermediate_size"], layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)),
-                       hidden_act=cfg.get("hidden_act", b.hidden_act), vision_use_head=cfg.get("vision_use_head", True))
-    bad = siglip_geometry_problem(g)
-    if bad:
-        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
-        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
-    return g
+    vcfg, where = _sub_config(cfg, "vision_config")
+    g = SiglipGeometry(**_image_fields(vcfg, where, SIGLIP_B16), hidden_act=vcfg.get("hidden_act", SIGLIP_B16.hidden_act),
+                       vision_use_head=vcfg.get("vision_use_head", True))
+    _refuse(siglip_geometry_problem(g), where)
+    return g, where
 
 
-def _dinov2_geometry(cfg: dict, where: str) -> Dinov2Geometry:
+def _dinov2_geometry(cfg: dict, path: str):
     """config.json of a DINOv2 checkpoint (Dinov2Config) -> geometry.  `image_size` there (518 for the released models) only
     sizes the position table, which is read off the tensor; the engine runs 224 pixels.  A field the file leaves out has
     Dinov2Config's default, except the sizes."""
-    b = DINOV2_B14
+    b, where = DINOV2_B14, "config.json"
     if "registers" in str(cfg.get("model_type", "")) or cfg.get("num_register_tokens", 0) not in (0, None):
         raise MmeError(f"{where}: model_type = {cfg.get('model_type')!r}, num_register_tokens = {cfg.get('num_register_tokens', 0)!r}; supported: "
                        "dinov2 with num_register_tokens = 0 (Dinov2WithRegisters is not run)")
-    for fld in ("patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads"):
-        if not isinstance(cfg.get(fld), int) or isinstance(cfg.get(fld), bool):
-            raise MmeError(f"{where}: {fld} = {cfg.get(fld)!r}; an integer is required")
+    v = _ints(cfg, where, dict.fromkeys(("patch_size", "hidden_size", "num_hidden_layers", "num_attention_heads")))
     ratio = cfg.get("mlp_ratio", 4)
     if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or ratio <= 0:
         raise MmeError(f"{where}: mlp_ratio = {ratio!r}; a positive number is required")
-    F = int(cfg["hidden_size"] * ratio)
-    g = Dinov2Geometry(patch_size=cfg["patch_size"], num_channels=cfg.get("num_channels", b.num_channels), hidden_size=cfg["hidden_size"],
-                       num_layers=cfg["num_hidden_layers"], num_heads=cfg["num_attention_heads"], intermediate_size=F,
+    F = int(v["hidden_size"] * ratio)
+    g = Dinov2Geometry(patch_size=v["patch_size"], num_channels=cfg.get("num_channels", b.num_channels), hidden_size=v["hidden_size"],
+                       num_layers=v["num_hidden_layers"], num_heads=v["num_attention_heads"], intermediate_size=F,
                        layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)), hidden_act=cfg.get("hidden_act", b.hidden_act),
                        use_swiglu_ffn=cfg.get("use_swiglu_ffn", False))
     bad = dinov2_geometry_problem(g)
-    if bad:
-        if bad[0] == "intermediate_size":
-            raise MmeError(f"{where}: mlp_ratio = {ratio!r} at hidden_size = {g.hidden_size} (an MLP of {F}); supported: mlp_ratio x hidden_size {bad[2]}")
-        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
-        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
+    if bad and bad[0] == "intermediate_size":
+        raise MmeError(f"{where}: mlp_ratio = {ratio!r} at hidden_size = {g.hidden_size} (an MLP of {F}); supported: mlp_ratio x hidden_size {bad[2]}")
+    _refuse(bad, where)
     _expect(cfg, "qkv_bias", True, where, default=True)
-    return g
+    return g, where
 
 
-def _clip_text_geometry(cfg: dict, where: str, projection_dim) -> CLIPTextGeometry:
+def _clip_text_geometry(cfg: dict, path: str):
     """The text configuration of a CLIP checkpoint (CLIPTextConfig) -> geometry.  A field the file leaves out has
     CLIPTextConfig's default (clip-vit-base-patch16's text tower), as transformers reads it."""
-    b = CLIP_TEXT_B
-    fields = {"hidden_size": b.hidden_size, "num_hidden_layers": b.num_layers, "num_attention_heads": b.num_heads, "intermediate_size": b.intermediate_size,
-              "vocab_size": b.vocab_size, "max_position_embeddings": b.max_position_embeddings, "eos_token_id": b.eos_token_id}
-    for fld, default in fields.items():
-        v = cfg.get(fld, default)
-        if not isinstance(v, int) or isinstance(v, bool):
-            raise MmeError(f"{where}: {fld} = {v!r}; an integer is required")
-        fields[fld] = v
-    g = CLIPTextGeometry(hidden_size=fields["hidden_size"], num_layers=fields["num_hidden_layers"], num_heads=fields["num_attention_heads"],
-                         intermediate_size=fields["intermediate_size"], vocab_size=fields["vocab_size"],
-                         max_position_embeddings=fields["max_position_embeddings"], eos_token_id=fields["eos_token_id"], projection_dim=projection_dim,
-                         hidden_act=cfg.get("hidden_act", b.hidden_act), layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
-    bad = clip_text_geometry_problem(g)
-    if bad:
-        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
-        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
-    return g
+    tcfg, where = _sub_config(cfg, "text_config")
+    if tcfg is not cfg:  # a whole CLIP model: projection_dim sits at the top level, CLIPConfig's own field and default
+        tcfg["projection_dim"] = cfg.get("projection_dim", CLIP_TEXT_B.projection_dim)
+    g = CLIPTextGeometry(**_text_fields(tcfg, where, CLIP_TEXT_B, "eos_token_id"), projection_dim=tcfg.get("projection_dim"))
+    _refuse(clip_text_geometry_problem(g), where)
+    return g, where
 
 
-def _siglip_text_geometry(cfg: dict, where: str):
+def _siglip_text_geometry(cfg: dict, path: str):
     """The text configuration of a SigLIP checkpoint (SiglipTextConfig) -> geometry.  A field the file leaves out has
     SiglipTextConfig's default (siglip-base-patch16-224's text tower; projection_size: hidden_size), as transformers reads it."""
-    from .weights import SIGLIP_TEXT_B, SiglipTextGeometry
-
-    b = SIGLIP_TEXT_B
-    fields = {"hidden_size": b.hidden_size, "num_hidden_layers": b.num_layers, "num_attention_heads": b.num_heads, "intermediate_size": b.intermediate_size,
-              "vocab_size": b.vocab_size, "max_position_embeddings": b.max_position_embeddings, "pad_token_id": b.pad_token_id}
-    for fld, default in fields.items():
-        v = cfg.get(fld, default)
-        if not isinstance(v, int) or isinstance(v, bool):
-            raise MmeError(f"{where}: {fld} = {v!r}; an integer is required")
-        fields[fld] = v
-    proj = cfg.get("projection_size")
-    g = SiglipTextGeometry(hidden_size=fields["hidden_size"], num_layers=fields["num_hidden_layers"], num_heads=fields["num_attention_heads"],
-                           intermediate_size=fields["intermediate_size"], vocab_size=fields["vocab_size"],
-                           max_position_embeddings=fields["max_position_embeddings"], pad_token_id=fields["pad_token_id"],
-                           projection_size=fields["hidden_size"] if proj is None else proj, hidden_act=cfg.get("hidden_act", b.hidden_act),
-                           layer_norm_eps=float(cfg.get("layer_norm_eps", b.layer_norm_eps)))
-    bad = siglip_text_geometry_problem(g)
-    if bad:
-        names = {"num_layers": "num_hidden_layers", "num_heads": "num_attention_heads"}
-        raise MmeError(f"{where}: {names.get(bad[0], bad[0])} = {bad[1]!r}; supported: {bad[2]}")
-    return g
+    tcfg, where = _sub_config(cfg, "text_config")
+    if tcfg is cfg and cfg.get("model_type") == "siglip_vision_model":
+        raise MmeError(f"{path}: config.json has model_type = 'siglip_vision_model': the directory holds no text tower")
+    if "naflex" in str(cfg.get("model_type", "")).lower() or "naflex" in str(tcfg.get("model_type", "")).lower():
+        raise MmeError(f"{where}: model_type = {cfg.get('model_type')!r}; supported: siglip, siglip_text_model (the NaFlex variants are not run)")
+    fields = _text_fields(tcfg, where, SIGLIP_TEXT_B, "pad_token_id")
+    proj = tcfg.get("projection_size")
+    g = SiglipTextGeometry(**fields, projection_size=fields["hidden_size"] if proj is None else proj)
+    _refuse(siglip_text_geometry_problem(g), where)
+    return g, where
 
 
-def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
+def _tile_geometry(cfg: dict, path: str):
+    cfg, where = _sub_config(cfg, "vision_config")  # a whole Mllama model keeps the tower's fields there
     g = TILE_VIT
     for fld, built in (("image_size", g.image_size), ("patch_size", g.patch_size), ("hidden_size", g.hidden_size),
                        ("attention_heads", g.num_heads), ("intermediate_size", g.intermediate_size), ("max_num_tiles", g.max_num_tiles)):
@@ -372,7 +366,7 @@ def _tile_geometry(cfg: dict, where: str) -> TileViTGeometry:
             raise MmeError(f"{where}: {fld} is missing")
     return TileViTGeometry(num_layers=int(cfg["num_hidden_layers"]), num_global_layers=int(cfg["num_global_layers"]),
                            intermediate_layers=tuple(int(v) for v in cfg["intermediate_layers_indices"]),
-                           norm_eps=float(cfg.get("norm_eps", g.norm_eps)))
+                           norm_eps=float(cfg.get("norm_eps", g.norm_eps))), where
 
 
 RESIZE_RULES = ("fit_pad", "clip")  # _lib.Engine.RESIZE_RULES / MME_RESIZE_* (include/mme.h)
@@ -543,115 +537,68 @@ def _unify_dtype(tensors: dict, keys: dict):
     return {n: (t if t.dtype == major else t.to(major)).contiguous() for n, t in tensors.items()}, names[major]
 
 
+# ---- what only some encoders need once the tensors are read (`encoders.Encoder.after_read`) ---------------------------------
+def _optional_projection(name: str):
+    """CLIP's two towers: a checkpoint without the projection `name` (CLIPVisionModel, CLIPTextModel) embeds with the final
+    LayerNorm's row, whatever config.json says; one with it needs a projection_dim there."""
+    def after_read(geometry, tensors, keys, path, where):
+        if name not in tensors:
+            return dataclasses.replace(geometry, projection_dim=None)
+        if geometry.projection_dim is None:
+            raise MmeError(f"{path}: the checkpoint holds {keys[name]!r} but {where} names no projection_dim")
+        return geometry
+
+    return after_read
+
+
+def _dinov2_position_grid(geometry, tensors, keys, path, where):
+    """The side of the position grid is the tensor's, not config.json's."""
+    if DINOV2_POSITIONS not in tensors:
+        return geometry
+    rows = int(tensors[DINOV2_POSITIONS].shape[-2]) if tensors[DINOV2_POSITIONS].dim() >= 2 else 0
+    grid = int(round(max(rows - 1, 0) ** 0.5))
+    if rows < 2 or grid * grid != rows - 1:
+        raise MmeError(f"{path}: tensor {keys[DINOV2_POSITIONS]!r} has shape {tuple(tensors[DINOV2_POSITIONS].shape)}: the patch part "
+                       f"({rows - 1} rows) is no square grid")
+    return dataclasses.replace(geometry, position_grid=grid)
+
+
+def _siglip_logit_pair(geometry, tensors, keys, path, where):
+    """A SiglipTextModel checkpoint has no logit_scale / logit_bias; a whole SiglipModel stores both as [1], kept beside the tower's tensors."""
+    have = [k for k in SIGLIP_LOGIT_KEYS if k in tensors]
+    if len(have) == 1:
+        raise MmeError(f"{path}: the checkpoint holds {have[0]!r} without the other of {SIGLIP_LOGIT_KEYS}")
+    for k in have:
+        if tensors[k].numel() != 1:
+            raise MmeError(f"{path}: tensor {keys[k]!r} has shape {tuple(tensors[k].shape)}, expected one value")
+        tensors[k] = tensors[k].reshape(1)
+    return geometry
+
+
 def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpoint:
     """Directory -> Checkpoint (see the module docstring).  Raises MmeError naming the file, field or key at fault.
 
     `resize_rule` ("fit_pad", the same as None, or "clip") is the rule K1 will run: under "clip" a preprocessor_config.json
     must describe CLIPImageProcessor's shortest-edge-224 BICUBIC resize and 224 x 224 centre crop exactly, and a directory
     without one gets CLIP's defaults (the engine's mean / std)."""
+    from .encoders import ENCODER_TABLE
+
     path = os.fspath(path)
     if encoder not in ENCODERS:
         raise ValueError(f"encoder must be one of {ENCODERS}")
+    rec = ENCODER_TABLE[encoder]
     resize_rule = check_resize_rule(resize_rule, encoder)
     if not os.path.isdir(path):
         raise MmeError(f"{path!r} is not a local checkpoint directory; this engine never fetches")
     cfg_path = os.path.join(path, "config.json")
     if not os.path.exists(cfg_path):
         raise MmeError(f"{cfg_path} is missing")
-    cfg = _load_json(cfg_path)
-    source = [cfg_path]
-    if encoder in VIT_ENCODERS:
-        geometry = _vit_geometry(cfg, "config.json") if encoder == "vit_b16" else _vit_family_geometry(cfg, "config.json")
-        specs = [(n, s) for n, s, _ in vit_tensor_specs(geometry)]
-        canonical = canonical_vit_name
-    elif encoder == "clip":
-        where, vcfg = "config.json", cfg
-        if "vision_config" in cfg:  # a whole CLIP model: projection_dim sits at the top level
-            vcfg, where = dict(cfg["vision_config"]), "config.json: vision_config"
-            if "projection_dim" in cfg:
-                vcfg["projection_dim"] = cfg["projection_dim"]
-        geometry = _clip_geometry(vcfg, where, vcfg.get("projection_dim"))
-        canonical = canonical_clip_name
-        specs = None  # after the tensors are read: a CLIPVisionModel checkpoint has no visual_projection
-    elif encoder == "siglip":
-        where, vcfg = "config.json", cfg
-        if "vision_config" in cfg:  # a whole SigLIP model
-            vcfg, where = dict(cfg["vision_config"]), "config.json: vision_config"
-        geometry = _siglip_geometry(vcfg, where)
-        specs = [(n, s) for n, s, _ in siglip_tensor_specs(geometry)]
-        canonical = canonical_siglip_name
-    elif encoder == "dinov2":
-        geometry = _dinov2_geometry(cfg, "config.json")
-        canonical = canonical_dinov2_name
-        specs = None  # after the tensors are read: the side of the position grid is the tensor's
-    elif encoder == "clip_text":
-        where, tcfg = "config.json", cfg
-        if "text_config" in cfg:  # a whole CLIP model: projection_dim sits at the top level
-            tcfg, where = dict(cfg["text_config"]), "config.json: text_config"
-            tcfg["projection_dim"] = cfg.get("projection_dim", CLIP_TEXT_B.projection_dim)  # CLIPConfig's own field and default
-        geometry = _clip_text_geometry(tcfg, where, tcfg.get("projection_dim"))
-        canonical = canonical_clip_text_name
-        specs = None  # after the tensors are read: a CLIPTextModel checkpoint has no text_projection
-    elif encoder == "siglip_text":
-        where, tcfg = "config.json", cfg
-        if "text_config" in cfg:  # a whole SigLIP model
-            tcfg, where = dict(cfg["text_config"]), "config.json: text_config"
-        elif cfg.get("model_type") == "siglip_vision_model":
-            raise MmeError(f"{path}: config.json has model_type = 'siglip_vision_model': the directory holds no text tower")
-        if "naflex" in str(cfg.get("model_type", "")).lower() or "naflex" in str(tcfg.get("model_type", "")).lower():
-            raise MmeError(f"{where}: model_type = {cfg.get('model_type')!r}; supported: siglip, siglip_text_model (the NaFlex variants are not run)")
-        geometry = _siglip_text_geometry(tcfg, where)
-        canonical = canonical_siglip_text_name
-        specs = None  # after the tensors are read: a SiglipTextModel checkpoint has no logit_scale / logit_bias
-    else:
-        where = "config.json"
-        if "vision_config" in cfg:  # a whole Mllama model
-            cfg, where = cfg["vision_config"], "config.json: vision_config"
-        geometry = _tile_geometry(cfg, where)
-        specs = [(n, s) for n, s, _, _ in tile_vit_tensor_specs(geometry)]
-        canonical = canonical_tile_name
-    if encoder == "clip":
-        wanted = {n for n, _, _ in clip_tensor_specs(dataclasses.replace(geometry, projection_dim=geometry.projection_dim or 64))}
-        tensors, keys, files = _read_tensors(path, canonical, wanted)
-        if "visual_projection.weight" not in tensors:  # CLIPVisionModel: the embedding is the post_layernorm row
-            geometry = dataclasses.replace(geometry, projection_dim=None)
-        elif geometry.projection_dim is None:
-            raise MmeError(f"{path}: the checkpoint holds {keys['visual_projection.weight']!r} but {where} names no projection_dim")
-        specs = [(n, s) for n, s, _ in clip_tensor_specs(geometry)]
-    elif encoder == "clip_text":
-        wanted = {n for n, _, _ in clip_text_tensor_specs(dataclasses.replace(geometry, projection_dim=geometry.projection_dim or 64))}
-        tensors, keys, files = _read_tensors(path, canonical, wanted)
-        if "text_projection.weight" not in tensors:  # CLIPTextModel: the embedding is the final_layer_norm row at the EOS position
-            geometry = dataclasses.replace(geometry, projection_dim=None)
-        elif geometry.projection_dim is None:
-            raise MmeError(f"{path}: the checkpoint holds {keys['text_projection.weight']!r} but {where} names no projection_dim")
-        specs = [(n, s) for n, s, _ in clip_text_tensor_specs(geometry)]
-    elif encoder == "dinov2":
-        tensors, keys, files = _read_tensors(path, canonical, {n for n, _, _ in dinov2_tensor_specs(geometry)})
-        if DINOV2_POSITIONS in tensors:
-            rows = int(tensors[DINOV2_POSITIONS].shape[-2]) if tensors[DINOV2_POSITIONS].dim() >= 2 else 0
-            grid = int(round(max(rows - 1, 0) ** 0.5))
-            if rows < 2 or grid * grid != rows - 1:
-                raise MmeError(f"{path}: tensor {keys[DINOV2_POSITIONS]!r} has shape {tuple(tensors[DINOV2_POSITIONS].shape)}: the patch part "
-                               f"({rows - 1} rows) is no square grid")
-            geometry = dataclasses.replace(geometry, position_grid=grid)
-        specs = [(n, s) for n, s, _ in dinov2_tensor_specs(geometry)]
-    elif encoder == "siglip_text":
-        from .weights import SIGLIP_LOGIT_KEYS
-
-        specs = [(n, s) for n, s, _ in siglip_text_tensor_specs(geometry)]
-        tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs} | set(SIGLIP_LOGIT_KEYS))
-        have = [k for k in SIGLIP_LOGIT_KEYS if k in tensors]
-        if len(have) == 1:
-            raise MmeError(f"{path}: the checkpoint holds {have[0]!r} without the other of {SIGLIP_LOGIT_KEYS}")
-        for k in have:  # SiglipModel stores them as [1]; kept beside the tower's tensors
-            if tensors[k].numel() != 1:
-                raise MmeError(f"{path}: tensor {keys[k]!r} has shape {tuple(tensors[k].shape)}, expected one value")
-            tensors[k] = tensors[k].reshape(1)
-            specs.append((k, (1,)))
-    else:
-        tensors, keys, files = _read_tensors(path, canonical, {n for n, _ in specs})
-    source += files
+    geometry, where = rec.config_geometry(_load_json(cfg_path), path)
+    tensors, keys, files = _read_tensors(path, rec.canonical_name, {s[0] for s in rec.tensor_specs(geometry)} | set(rec.optional))
+    if rec.after_read:  # what config.json cannot say: which optional tensors the file holds, the side of DINOv2's position grid
+        geometry = rec.after_read(geometry, tensors, keys, path, where)
+    specs = [(s[0], s[1]) for s in rec.tensor_specs(geometry)]
+    specs += [(k, tuple(tensors[k].shape)) for k in rec.optional if k in tensors and k not in dict(specs)]
     for name, shape in specs:
         if name not in tensors:
             raise MmeError(f"{path}: tensor {name!r} is missing from the checkpoint")
@@ -659,14 +606,76 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
             raise MmeError(f"{path}: tensor {keys[name]!r} has shape {tuple(tensors[name].shape)}, expected {tuple(shape)}")
     tensors, dtype = _unify_dtype({n: tensors[n] for n, _ in specs}, keys)
     mean = std = None
+    source = [cfg_path] + files
     pre_path = os.path.join(path, "preprocessor_config.json")
-    if os.path.exists(pre_path) and encoder not in ("clip_text", "siglip_text"):  # a text tower reads no pixels
+    if os.path.exists(pre_path) and not rec.text:  # a text tower reads no pixels
         mean, std = _read_preprocessor(pre_path, encoder, resize_rule)
         source.append(pre_path)
-    extra = {}
-    if encoder == "dinov2":
-        extra["position_table"] = interpolate_dinov2_positions(tensors[DINOV2_POSITIONS])
+    extra = rec.extra(tensors) if rec.extra else {}
     return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source, extra=extra)
+
+
+# ---- config.json of a geometry (`encoders.Encoder.config_json`: geometry, dtype name, the weight dict -> dict) ----------------
+def _vit_config(g, dtype, weights):
+    return {"architectures": ["ViTModel"], "model_type": "vit", "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels,
+            "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
+            "intermediate_size": g.intermediate_size, "hidden_act": "gelu", "qkv_bias": True, "layer_norm_eps": g.layer_norm_eps, "dtype": dtype}
+
+
+def _clip_config(g, dtype, weights):
+    cfg = {"architectures": ["CLIPVisionModelWithProjection" if g.projection_dim else "CLIPVisionModel"], "model_type": "clip_vision_model",
+           "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size,
+           "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
+           "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "dtype": dtype}
+    if g.projection_dim:
+        cfg["projection_dim"] = g.projection_dim
+    return cfg
+
+
+def _siglip_config(g, dtype, weights):
+    cfg = {"architectures": ["SiglipVisionModel"], "model_type": "siglip_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,
+           "num_channels": g.num_channels, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
+           "intermediate_size": g.intermediate_size, "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0,
+           "dtype": dtype}
+    if g.vision_use_head is not True:
+        cfg["vision_use_head"] = g.vision_use_head
+    return cfg
+
+
+def _dinov2_config(g, dtype, weights):
+    import numpy as np
+
+    rows = int(np.shape(weights[DINOV2_POSITIONS])[-2]) if DINOV2_POSITIONS in weights else g.position_rows
+    ratio = g.intermediate_size / g.hidden_size
+    return {"architectures": ["Dinov2Model"], "model_type": "dinov2", "image_size": g.patch_size * int(round((rows - 1) ** 0.5)),
+            "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers,
+            "num_attention_heads": g.num_heads, "mlp_ratio": int(ratio) if ratio == int(ratio) else ratio, "hidden_act": g.hidden_act,
+            "layer_norm_eps": g.layer_norm_eps, "qkv_bias": True, "use_swiglu_ffn": g.use_swiglu_ffn, "layerscale_value": 1.0, "dtype": dtype}
+
+
+def _clip_text_config(g, dtype, weights):
+    cfg = {"architectures": ["CLIPTextModelWithProjection" if g.projection_dim else "CLIPTextModel"], "model_type": "clip_text_model",
+           "vocab_size": g.vocab_size, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
+           "intermediate_size": g.intermediate_size, "max_position_embeddings": g.max_position_embeddings, "hidden_act": g.hidden_act,
+           "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "eos_token_id": g.eos_token_id, "dtype": dtype}
+    if g.projection_dim:
+        cfg["projection_dim"] = g.projection_dim
+    return cfg
+
+
+def _siglip_text_config(g, dtype, weights):
+    return {"architectures": ["SiglipTextModel"], "model_type": "siglip_text_model", "vocab_size": g.vocab_size, "hidden_size": g.hidden_size,
+            "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
+            "max_position_embeddings": g.max_position_embeddings, "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps,
+            "attention_dropout": 0.0, "pad_token_id": g.pad_token_id, "projection_size": g.projection_size, "dtype": dtype}
+
+
+def _tile_config(g, dtype, weights):
+    return {"architectures": ["MllamaVisionModel"], "model_type": "mllama_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,
+            "num_channels": g.num_channels, "hidden_size": g.hidden_size, "attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
+            "hidden_act": "gelu", "max_num_tiles": g.max_num_tiles, "supported_aspect_ratios": SUPPORTED_ASPECT_RATIOS,
+            "num_hidden_layers": g.num_layers, "num_global_layers": g.num_global_layers,
+            "intermediate_layers_indices": list(g.intermediate_layers), "norm_eps": g.norm_eps, "dtype": dtype}
 
 
 def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = "float32", geometry=None, image_mean=None, image_std=None,
@@ -679,64 +688,15 @@ def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = 
     import torch
     from safetensors.torch import save_file
 
+    from .encoders import ENCODER_TABLE
+
     tdt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}[dtype]
     os.makedirs(path, exist_ok=True)
-    if encoder in VIT_ENCODERS:
-        g = geometry or VIT_B16
-        cfg = {"architectures": ["ViTModel"], "model_type": "vit", "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels,
-               "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
-               "intermediate_size": g.intermediate_size, "hidden_act": "gelu", "qkv_bias": True, "layer_norm_eps": g.layer_norm_eps, "dtype": dtype}
-    elif encoder == "clip":
-        g = geometry or CLIP_B16
-        cfg = {"architectures": ["CLIPVisionModelWithProjection" if g.projection_dim else "CLIPVisionModel"], "model_type": "clip_vision_model",
-               "image_size": g.image_size, "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size,
-               "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
-               "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "dtype": dtype}
-        if g.projection_dim:
-            cfg["projection_dim"] = g.projection_dim
-    elif encoder == "siglip":
-        g = geometry or SIGLIP_B16
-        cfg = {"architectures": ["SiglipVisionModel"], "model_type": "siglip_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,
-               "num_channels": g.num_channels, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
-               "intermediate_size": g.intermediate_size, "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0,
-               "dtype": dtype}
-        if g.vision_use_head is not True:
-            cfg["vision_use_head"] = g.vision_use_head
-    elif encoder == "dinov2":
-        g = geometry or DINOV2_B14
-        rows = int(np.shape(weights[DINOV2_POSITIONS])[-2]) if DINOV2_POSITIONS in weights else g.position_rows
-        ratio = g.intermediate_size / g.hidden_size
-        cfg = {"architectures": ["Dinov2Model"], "model_type": "dinov2", "image_size": g.patch_size * int(round((rows - 1) ** 0.5)),
-               "patch_size": g.patch_size, "num_channels": g.num_channels, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers,
-               "num_attention_heads": g.num_heads, "mlp_ratio": int(ratio) if ratio == int(ratio) else ratio, "hidden_act": g.hidden_act,
-               "layer_norm_eps": g.layer_norm_eps, "qkv_bias": True, "use_swiglu_ffn": g.use_swiglu_ffn, "layerscale_value": 1.0, "dtype": dtype}
-    elif encoder == "clip_text":
-        g = geometry or CLIP_TEXT_B
-        cfg = {"architectures": ["CLIPTextModelWithProjection" if g.projection_dim else "CLIPTextModel"], "model_type": "clip_text_model",
-               "vocab_size": g.vocab_size, "hidden_size": g.hidden_size, "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads,
-               "intermediate_size": g.intermediate_size, "max_position_embeddings": g.max_position_embeddings, "hidden_act": g.hidden_act,
-               "layer_norm_eps": g.layer_norm_eps, "attention_dropout": 0.0, "eos_token_id": g.eos_token_id, "dtype": dtype}
-        if g.projection_dim:
-            cfg["projection_dim"] = g.projection_dim
-    elif encoder == "siglip_text":
-        from .weights import SIGLIP_TEXT_B
-
-        g = geometry or SIGLIP_TEXT_B
-        cfg = {"architectures": ["SiglipTextModel"], "model_type": "siglip_text_model", "vocab_size": g.vocab_size, "hidden_size": g.hidden_size,
-               "num_hidden_layers": g.num_layers, "num_attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
-               "max_position_embeddings": g.max_position_embeddings, "hidden_act": g.hidden_act, "layer_norm_eps": g.layer_norm_eps,
-               "attention_dropout": 0.0, "pad_token_id": g.pad_token_id, "projection_size": g.projection_size, "dtype": dtype}
-    elif encoder == "mllama_tiles":
-        g = geometry or TILE_VIT
-        cfg = {"architectures": ["MllamaVisionModel"], "model_type": "mllama_vision_model", "image_size": g.image_size, "patch_size": g.patch_size,
-               "num_channels": g.num_channels, "hidden_size": g.hidden_size, "attention_heads": g.num_heads, "intermediate_size": g.intermediate_size,
-               "hidden_act": "gelu", "max_num_tiles": g.max_num_tiles, "supported_aspect_ratios": SUPPORTED_ASPECT_RATIOS,
-               "num_hidden_layers": g.num_layers, "num_global_layers": g.num_global_layers,
-               "intermediate_layers_indices": list(g.intermediate_layers), "norm_eps": g.norm_eps, "dtype": dtype}
-    else:
+    if encoder not in ENCODER_TABLE:
         raise ValueError(f"encoder must be one of {ENCODERS}")
+    rec = ENCODER_TABLE[encoder]
     with open(os.path.join(path, "config.json"), "w", encoding="utf-8") as f:
-        json.dump(cfg, f, indent=1)
+        json.dump(rec.config_json(geometry or rec.geometry, dtype, weights), f, indent=1)
     save_file({k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(tdt).contiguous() for k, v in weights.items()},
               os.path.join(path, "model.safetensors"), metadata={"format": "pt"})
     if image_mean is not None:

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import config
 from ._lib import Engine, MmeError, lanczos_geometry_ok, lanczos_workspace  # noqa: F401
-from .weights import TILE_VIT, VIT_B16, make_vit_weights
+from .weights import TILE_VIT
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
@@ -193,6 +193,7 @@ class RegionEmbedder:
         import torch
 
         from .checkpoint import check_resize_rule, read_checkpoint, resolve_model_source
+        from .encoders import ENCODER_TABLE
 
         self.torch = torch
         self.model_name = model_name
@@ -238,6 +239,7 @@ class RegionEmbedder:
         self.devices = [f"cuda:{d}" for d in dev_list]
         self.device = torch.device(self.devices[0])
         self.encoder = encoder
+        rec = ENCODER_TABLE[encoder]
         if engine is not None:
             self.engines = [engine]
         elif self.checkpoint is not None:
@@ -245,62 +247,19 @@ class RegionEmbedder:
             self.engines = []
             for d in dev_list:  # read once, loaded into every context
                 e = Engine(d)
-                if encoder == "mllama_tiles":
-                    geom = ck.geometry if geometry is None else geometry
-                    e.load_tile_vit_checkpoint(ck, geom)
-                elif encoder == "clip":
-                    e.load_clip_checkpoint(ck)
-                elif encoder == "siglip":
-                    e.load_siglip_checkpoint(ck)
-                elif encoder == "dinov2":
-                    e.load_dinov2_checkpoint(ck)
-                else:
-                    e.load_vit_checkpoint(ck)
+                # only the tile tower takes a geometry beside its checkpoint: the save point of the intermediate states is not in the file
+                getattr(e, rec.loader + "_checkpoint")(ck, *([geometry] if encoder == "mllama_tiles" else []))
                 if ck.image_mean is not None:
                     e.set_normalisation(ck.image_mean, ck.image_std)
                 self.engines.append(e)
         else:
-            if encoder == "mllama_tiles":
-                from .weights import make_tile_vit_weights
-
-                w = weights if weights is not None else (make_tile_vit_weights(seed + 1, geometry) if geometry else make_tile_vit_weights(seed + 1))
-            elif encoder == "clip":
-                from .weights import CLIP_B16, make_clip_weights
-
-                w = weights if weights is not None else make_clip_weights(seed, geometry or CLIP_B16)
-                if weights is None and geometry is None:
-                    geometry = CLIP_B16
-            elif encoder == "siglip":
-                from .weights import SIGLIP_B16, make_siglip_weights
-
-                w = weights if weights is not None else make_siglip_weights(seed, geometry or SIGLIP_B16)
-                if weights is None and geometry is None:
-                    geometry = SIGLIP_B16
-            elif encoder == "dinov2":
-                from .weights import DINOV2_B14, make_dinov2_weights
-
-                w = weights if weights is not None else make_dinov2_weights(seed, geometry or DINOV2_B14)
-                if weights is None and geometry is None:
-                    geometry = DINOV2_B14
-            elif encoder == "vit" and geometry is not None:
-                w = weights if weights is not None else make_vit_weights(seed, geometry)
-            else:
-                w = weights if weights is not None else make_vit_weights(seed)
+            if geometry is None and (weights is None or rec.infer_geometry is None):  # a caller's dict is sized by its tensors where that can be read
+                geometry = rec.geometry
+            w = weights if weights is not None else rec.make_weights(seed + rec.seed_offset, geometry)
             self.engines = []
             for d in dev_list:  # one context (weights + workspace) per device, as embedder.py:73-82
                 e = Engine(d)
-                if encoder == "mllama_tiles":
-                    e.load_tile_vit(w, geometry)
-                elif encoder == "clip":
-                    e.load_clip(w, geom=geometry)
-                elif encoder == "siglip":
-                    e.load_siglip(w, geom=geometry)
-                elif encoder == "dinov2":
-                    e.load_dinov2(w, geom=geometry)
-                elif encoder == "vit":
-                    e.load_vit(w, geom=geometry)
-                else:
-                    e.load_vit(w, geom=VIT_B16)
+                getattr(e, rec.loader)(w, geom=geometry)
                 self.engines.append(e)
         self.engine = self.engines[0]
         if resize_rule is not None:
@@ -761,40 +720,43 @@ class RegionEmbedder:
                  "dict), or name a checkpoint directory that holds one (a whole CLIPModel); the mmE5 language tower stays out of scope")
 
     def _load_text_tower(self):
-        """Loads the tower `text_tower=` named into the first engine; NotImplementedError when there is none to load."""
+        """Loads the tower `text_tower=` named into the first engine (SigLIP's 64-token tower under encoder='siglip_vit', whose width
+        is checked against the image side; else CLIP's); NotImplementedError when there is none to load."""
         from .checkpoint import read_checkpoint
+        from .encoders import ENCODER_TABLE
 
         src = getattr(self, "_text_source", False)
         eng = self.engines[0]
         if getattr(self, "encoder", None) == "dinov2":
             raise NotImplementedError("text embeddings: a DINOv2 tower is trained on images alone and has no text tower; " + self._NO_TOWER)
-        if getattr(self, "encoder", None) == "siglip":  # (a CLIP text tower embeds into another space than a SigLIP image tower)
-            return self._load_siglip_text_tower(src, eng)
+        # (a CLIP text tower embeds into another space than a SigLIP image tower)
+        siglip = getattr(self, "encoder", None) == "siglip"
+        kind, no_tower = ("siglip_text", self._NO_SIGLIP_TOWER) if siglip else ("clip_text", self._NO_TOWER)
+        rec = ENCODER_TABLE[kind]
         if src is False:
-            raise NotImplementedError(self._NO_TOWER)
+            raise NotImplementedError(no_tower)
         if isinstance(src, dict):
-            eng.load_clip_text(src)
-        elif isinstance(src, (str, os.PathLike)):
-            eng.load_clip_text_checkpoint(read_checkpoint(src, "clip_text"))
-            self._text_dir = os.fspath(src)
-        elif self.checkpoint is not None:  # None or True beside a checkpoint directory: its own text half
+            if siglip:
+                self._check_siglip_text_width(rec.infer_geometry(src).projection_size, "the weight dict")
+            getattr(eng, rec.loader)(src)
+        elif isinstance(src, (str, os.PathLike)) or self.checkpoint is not None:
+            own = not isinstance(src, (str, os.PathLike))  # None or True beside a checkpoint directory: its own text half
+            directory = self.model_name if own else src
             try:
-                ck = read_checkpoint(self.model_name, "clip_text")
+                ck = read_checkpoint(directory, kind)
             except MmeError as e:
-                if src is None:
-                    raise NotImplementedError(f"{self._NO_TOWER} ({e})") from e
+                if own and src is None:  # a vision-only directory
+                    raise NotImplementedError(f"{no_tower} ({e})") from e
                 raise
-            eng.load_clip_text_checkpoint(ck)
-            self._text_dir = os.fspath(self.model_name)
-        elif src is True:  # seeded, in the space the seeded image side embeds into
-            import dataclasses
-
-            from .weights import CLIP_TEXT_B, make_clip_text_weights
-
-            geom = dataclasses.replace(CLIP_TEXT_B, projection_dim=int(self.embed_dim))
-            eng.load_clip_text(make_clip_text_weights(self._seed + 2, geom), geom)
+            if siglip:
+                self._check_siglip_text_width(ck.geometry.projection_size, os.fspath(directory))
+            getattr(eng, rec.loader + "_checkpoint")(ck)
+            self._text_dir = os.fspath(directory)
+        elif src is True:  # seeded, in the space (SigLIP: at the width) of the seeded image side
+            geom = rec.beside(int(self.embed_dim))
+            getattr(eng, rec.loader)(rec.make_weights(self._seed + 2, geom), geom)
         else:
-            raise NotImplementedError(self._NO_TOWER)
+            raise NotImplementedError(no_tower)
         self._text_loaded = True
 
     _NO_SIGLIP_TOWER = ("text embeddings under encoder='siglip_vit' need a SigLIP text tower: construct RegionEmbedder(..., text_tower=True | a "
@@ -804,45 +766,6 @@ class RegionEmbedder:
         if int(projection) != int(self.embed_dim):
             raise MmeError(f"text_tower: {where}: projection_size = {projection}; supported: {self.embed_dim}, the embed_dim of the loaded "
                            "SigLIP image tower (the two towers must embed into one space)")
-
-    def _load_siglip_text_tower(self, src, eng):
-        """The SigLIP branch of `_load_text_tower`: the same sources, the 64-token tower, the width check against the image side."""
-        from .checkpoint import read_checkpoint
-
-        if src is False:
-            raise NotImplementedError(self._NO_SIGLIP_TOWER)
-        if isinstance(src, dict):
-            from .weights import infer_siglip_text_geometry
-
-            self._check_siglip_text_width(infer_siglip_text_geometry(src).projection_size, "the weight dict")
-            eng.load_siglip_text(src)
-        elif isinstance(src, (str, os.PathLike)):
-            ck = read_checkpoint(src, "siglip_text")
-            self._check_siglip_text_width(ck.geometry.projection_size, os.fspath(src))
-            eng.load_siglip_text_checkpoint(ck)
-            self._text_dir = os.fspath(src)
-        elif self.checkpoint is not None:  # None or True beside a checkpoint directory: its own text half
-            try:
-                ck = read_checkpoint(self.model_name, "siglip_text")
-            except MmeError as e:
-                if src is None:  # a vision-only directory
-                    raise NotImplementedError(f"{self._NO_SIGLIP_TOWER} ({e})") from e
-                raise
-            self._check_siglip_text_width(ck.geometry.projection_size, os.fspath(self.model_name))
-            eng.load_siglip_text_checkpoint(ck)
-            self._text_dir = os.fspath(self.model_name)
-        elif src is True:  # seeded, at the width of the image side
-            import dataclasses
-
-            from .weights import SIGLIP_TEXT_B, make_siglip_text_weights
-
-            D = int(self.embed_dim)
-            geom = SIGLIP_TEXT_B if D == SIGLIP_TEXT_B.hidden_size else dataclasses.replace(
-                SIGLIP_TEXT_B, hidden_size=D, num_heads=D // 64, intermediate_size=4 * D, projection_size=D)
-            eng.load_siglip_text(make_siglip_text_weights(self._seed + 2, geom), geom)
-        else:
-            raise NotImplementedError(self._NO_SIGLIP_TOWER)
-        self._text_loaded = True
 
     def _text_layout(self):
         """(tokens per sequence, id that right-pads a short sequence) of the first engine's text tower: 77 and the eos_token_id

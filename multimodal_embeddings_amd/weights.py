@@ -29,6 +29,63 @@ import numpy as np
 
 _MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
+# ---- what every tower's transformer block shares ------------------------------------------------------------------------
+LAYER_FIELDS = ("ln1_g", "ln1_b", "q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "o_w", "o_b", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")  # _lib._Layer
+
+
+def _block_names(ln1: str, ln2: str, q: str, k: str, v: str, o: str):
+    """One spelling of a block: the tensor names (behind the layer's prefix) of LAYER_FIELDS, in that order."""
+    return tuple(f"{m}.{p}" for m in (ln1, q, k, v, o, ln2, "mlp.fc1", "mlp.fc2") for p in ("weight", "bias"))
+
+
+VIT_BLOCK = _block_names("layernorm_before", "layernorm_after", *(f"attention.{n}_proj" for n in "qkvo"))
+CLIP_BLOCK = _block_names("layer_norm1", "layer_norm2", *(f"self_attn.{n}_proj" for n in ("q", "k", "v", "out")))  # CLIP and SigLIP, image and text
+DINOV2_BLOCK = _block_names("norm1", "norm2", *(f"attention.attention.{n}" for n in ("query", "key", "value")), "attention.output.dense")
+
+
+def block_tensor_specs(prefix: str, names, D: int, F: int):
+    """(name, shape, kind) of one block's 16 tensors in LAYER_FIELDS order; `names`: a *_BLOCK spelling."""
+    shapes = {"fc1_w": (F, D), "fc1_b": (F,), "fc2_w": (D, F)}
+    specs = []
+    for fld, name in zip(LAYER_FIELDS, names):
+        kind = "gamma" if fld in ("ln1_g", "ln2_g") else "bias" if fld.endswith("_b") else "matrix"
+        specs.append((prefix + name, shapes.get(fld, (D, D) if kind == "matrix" else (D,)), kind))
+    return specs
+
+
+def _layer_count(w: dict, key: str) -> int:
+    """How many layers a weight dict holds, counted on `key` (a format over the layer index)."""
+    layers = 0
+    while key.format(layers) in w:
+        layers += 1
+    if layers == 0:
+        raise ValueError(f"the weight dict holds no {key.format(0)!r}")
+    return layers
+
+
+def _seeded_weights(specs, seed: int, rule) -> dict[str, np.ndarray]:
+    """The one generator: tensor `tid` of `specs` is bf16_round(rule(name, kind, z)), z = irwin_hall_normal(seed, tid, n)."""
+    out: dict[str, np.ndarray] = {}
+    for tid, (name, shape, kind) in enumerate(specs):
+        out[name] = round_to_bf16(rule(name, kind, irwin_hall_normal(seed, tid, int(np.prod(shape))))).reshape(shape)
+    return out
+
+
+def _spread_rule(std: float, is_norm, unscaled=lambda name: False):
+    """The rule of every tower but the plain ViT: LayerNorm weights 1 + 0.25 z and biases 0.1 z (`is_norm(name)` says which
+    biases are a LayerNorm's), LayerScale's lambda1 1.025 + 0.325 z clipped to [0.05, 2], `unscaled(name)` tensors z itself,
+    everything else std z."""
+    def rule(name, kind, z):
+        if kind == "gamma":
+            return np.float32(1.0) + z * np.float32(0.25)
+        if kind == "scale":
+            return np.clip(np.float32(1.025) + z * np.float32(0.325), np.float32(0.05), np.float32(2.0))
+        if kind == "bias" and is_norm(name):
+            return z * np.float32(0.1)
+        return z if unscaled(name) else z * np.float32(std)
+
+    return rule
+
 
 @dataclass(frozen=True)
 class ViTGeometry:
@@ -108,11 +165,7 @@ def infer_vit_geometry(w: dict, eps: float = 1e-12) -> ViTGeometry:
     patch = int(np.shape(w["embeddings.patch_embeddings.projection.weight"])[-1])
     tokens = int(np.shape(w["embeddings.position_embeddings"])[-2])
     grid = int(round((tokens - 1) ** 0.5))
-    layers = 0
-    while f"layers.{layers}.mlp.fc1.weight" in w:
-        layers += 1
-    if layers == 0:
-        raise ValueError("the weight dict holds no 'layers.0.mlp.fc1.weight'")
+    layers = _layer_count(w, "layers.{}.mlp.fc1.weight")
     F = int(np.shape(w["layers.0.mlp.fc1.weight"])[0])
     return ViTGeometry(image_size=grid * patch, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
                        layer_norm_eps=float(eps))
@@ -167,18 +220,7 @@ def clip_tensor_specs(geom: CLIPGeometry = CLIP_B16):
         (v + "pre_layrnorm.bias", (D,), "bias"),
     ]
     for i in range(geom.num_layers):
-        p = f"{v}encoder.layers.{i}."
-        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
-        for n in ("q", "k", "v", "out"):
-            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
-        specs += [
-            (p + "layer_norm2.weight", (D,), "gamma"),
-            (p + "layer_norm2.bias", (D,), "bias"),
-            (p + "mlp.fc1.weight", (F, D), "matrix"),
-            (p + "mlp.fc1.bias", (F,), "bias"),
-            (p + "mlp.fc2.weight", (D, F), "matrix"),
-            (p + "mlp.fc2.bias", (D,), "bias"),
-        ]
+        specs += block_tensor_specs(f"{v}encoder.layers.{i}.", CLIP_BLOCK, D, F)
     specs += [(v + "post_layernorm.weight", (D,), "gamma"), (v + "post_layernorm.bias", (D,), "bias")]
     if geom.projection_dim:
         specs.append(("visual_projection.weight", (geom.projection_dim, D), "matrix"))
@@ -190,19 +232,7 @@ def make_clip_weights(seed: int = 1, geom: CLIPGeometry = CLIP_B16, std: float =
     `make_vit_weights` on `clip_tensor_specs`.  LayerNorm weights are 1 + 0.25 z and biases 0.1 z (z ~ N(0, 1)): far enough
     from 1 and 0 that a dropped LayerNorm, or two LayerNorms exchanged, moves the embedding by much more than the bf16
     path's error.  Matrices N(0, std), the other biases N(0, std)."""
-    out: dict[str, np.ndarray] = {}
-    for tid, (name, shape, kind) in enumerate(clip_tensor_specs(geom)):
-        n = int(np.prod(shape))
-        z = irwin_hall_normal(seed, tid, n)
-        norm = "layer_norm" in name or "layrnorm" in name or "layernorm" in name
-        if kind == "gamma":
-            z = np.float32(1.0) + z * np.float32(0.25)
-        elif kind == "bias" and norm:
-            z = z * np.float32(0.1)
-        else:
-            z = z * np.float32(std)
-        out[name] = round_to_bf16(z).reshape(shape)
-    return out
+    return _seeded_weights(clip_tensor_specs(geom), seed, _spread_rule(std, lambda name: "layer_norm" in name or "layrnorm" in name or "layernorm" in name))
 
 
 def clip_flops_per_crop(geom: CLIPGeometry = CLIP_B16) -> int:
@@ -217,11 +247,7 @@ def infer_clip_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quick_gel
     D, patch = int(pw[0]), int(pw[-1])
     tokens = int(np.shape(w["vision_model.embeddings.position_embedding.weight"])[0])
     grid = int(round((tokens - 1) ** 0.5))
-    layers = 0
-    while f"vision_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
-        layers += 1
-    if layers == 0:
-        raise ValueError("the weight dict holds no 'vision_model.encoder.layers.0.mlp.fc1.weight'")
+    layers = _layer_count(w, "vision_model.encoder.layers.{}.mlp.fc1.weight")
     F = int(np.shape(w["vision_model.encoder.layers.0.mlp.fc1.weight"])[0])
     P = int(np.shape(w["visual_projection.weight"])[0]) if "visual_projection.weight" in w else None
     return CLIPGeometry(image_size=grid * patch, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
@@ -277,18 +303,7 @@ def siglip_tensor_specs(geom: SiglipGeometry = SIGLIP_B16):
         (v + "embeddings.position_embedding.weight", (geom.seq_len, D), "matrix"),
     ]
     for i in range(geom.num_layers):
-        p = f"{v}encoder.layers.{i}."
-        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
-        for n in ("q", "k", "v", "out"):
-            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
-        specs += [
-            (p + "layer_norm2.weight", (D,), "gamma"),
-            (p + "layer_norm2.bias", (D,), "bias"),
-            (p + "mlp.fc1.weight", (F, D), "matrix"),
-            (p + "mlp.fc1.bias", (F,), "bias"),
-            (p + "mlp.fc2.weight", (D, F), "matrix"),
-            (p + "mlp.fc2.bias", (D,), "bias"),
-        ]
+        specs += block_tensor_specs(f"{v}encoder.layers.{i}.", CLIP_BLOCK, D, F)
     h = v + "head."
     specs += [
         (v + "post_layernorm.weight", (D,), "gamma"),
@@ -312,21 +327,8 @@ def make_siglip_weights(seed: int = 4, geom: SiglipGeometry = SIGLIP_B16, std: f
     """Seeded synthetic weights of a SigLIP image tower, f32 arrays holding bf16-representable values: the generator and the
     LayerNorm spread of `make_clip_weights` on `siglip_tensor_specs`.  The probe is N(0, 1) as transformers initialises it,
     so that the head's scores are spread over the keys instead of near-uniform."""
-    out: dict[str, np.ndarray] = {}
-    for tid, (name, shape, kind) in enumerate(siglip_tensor_specs(geom)):
-        n = int(np.prod(shape))
-        z = irwin_hall_normal(seed, tid, n)
-        norm = "layer_norm" in name or "layernorm" in name
-        if kind == "gamma":
-            z = np.float32(1.0) + z * np.float32(0.25)
-        elif kind == "bias" and norm:
-            z = z * np.float32(0.1)
-        elif name.endswith("head.probe"):
-            pass
-        else:
-            z = z * np.float32(std)
-        out[name] = round_to_bf16(z).reshape(shape)
-    return out
+    return _seeded_weights(siglip_tensor_specs(geom), seed, _spread_rule(std, lambda name: "layer_norm" in name or "layernorm" in name,
+                                                                         unscaled=lambda name: name.endswith("head.probe")))
 
 
 def siglip_flops_per_crop(geom: SiglipGeometry = SIGLIP_B16) -> int:
@@ -342,11 +344,7 @@ def infer_siglip_geometry(w: dict, eps: float = 1e-6) -> SiglipGeometry:
     D, patch = int(pw[0]), int(pw[-1])
     tokens = int(np.shape(w["vision_model.embeddings.position_embedding.weight"])[0])
     grid = int(round(tokens ** 0.5))
-    layers = 0
-    while f"vision_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
-        layers += 1
-    if layers == 0:
-        raise ValueError("the weight dict holds no 'vision_model.encoder.layers.0.mlp.fc1.weight'")
+    layers = _layer_count(w, "vision_model.encoder.layers.{}.mlp.fc1.weight")
     F = int(np.shape(w["vision_model.encoder.layers.0.mlp.fc1.weight"])[0])
     return SiglipGeometry(image_size=grid * patch, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
                           layer_norm_eps=float(eps))
@@ -426,21 +424,8 @@ def dinov2_tensor_specs(geom: Dinov2Geometry = DINOV2_B14):
     ]
     for i in range(geom.num_layers):
         p = f"encoder.layer.{i}."
-        specs += [(p + "norm1.weight", (D,), "gamma"), (p + "norm1.bias", (D,), "bias")]
-        for n in ("query", "key", "value"):
-            specs += [(p + f"attention.attention.{n}.weight", (D, D), "matrix"), (p + f"attention.attention.{n}.bias", (D,), "bias")]
-        specs += [
-            (p + "attention.output.dense.weight", (D, D), "matrix"),
-            (p + "attention.output.dense.bias", (D,), "bias"),
-            (p + "layer_scale1.lambda1", (D,), "scale"),
-            (p + "norm2.weight", (D,), "gamma"),
-            (p + "norm2.bias", (D,), "bias"),
-            (p + "mlp.fc1.weight", (F, D), "matrix"),
-            (p + "mlp.fc1.bias", (F,), "bias"),
-            (p + "mlp.fc2.weight", (D, F), "matrix"),
-            (p + "mlp.fc2.bias", (D,), "bias"),
-            (p + "layer_scale2.lambda1", (D,), "scale"),
-        ]
+        block = block_tensor_specs(p, DINOV2_BLOCK, D, F)  # LayerScale sits behind the attention's output and behind the MLP
+        specs += block[:10] + [(p + "layer_scale1.lambda1", (D,), "scale")] + block[10:] + [(p + "layer_scale2.lambda1", (D,), "scale")]
     specs += [("layernorm.weight", (D,), "gamma"), ("layernorm.bias", (D,), "bias")]
     return specs
 
@@ -455,21 +440,7 @@ def make_dinov2_weights(seed: int = 6, geom: Dinov2Geometry = DINOV2_B14, std: f
 
     if pos_grid is not None:
         geom = dataclasses.replace(geom, position_grid=int(pos_grid))
-    out: dict[str, np.ndarray] = {}
-    for tid, (name, shape, kind) in enumerate(dinov2_tensor_specs(geom)):
-        n = int(np.prod(shape))
-        z = irwin_hall_normal(seed, tid, n)
-        norm = ".norm" in name or "layernorm" in name
-        if kind == "gamma":
-            z = np.float32(1.0) + z * np.float32(0.25)
-        elif kind == "scale":
-            z = np.clip(np.float32(1.025) + z * np.float32(0.325), np.float32(0.05), np.float32(2.0))
-        elif kind == "bias" and norm:
-            z = z * np.float32(0.1)
-        else:
-            z = z * np.float32(std)
-        out[name] = round_to_bf16(z).reshape(shape)
-    return out
+    return _seeded_weights(dinov2_tensor_specs(geom), seed, _spread_rule(std, lambda name: ".norm" in name or "layernorm" in name))
 
 
 def dinov2_flops_per_crop(geom: Dinov2Geometry = DINOV2_B14) -> int:
@@ -487,11 +458,7 @@ def infer_dinov2_geometry(w: dict, eps: float = 1e-6) -> Dinov2Geometry:
     grid = int(round((rows - 1) ** 0.5))
     if rows < 2 or grid * grid != rows - 1:
         raise ValueError(f"tensor 'embeddings.position_embeddings' has {rows} rows: the patch part ({rows - 1} rows) is no square grid")
-    layers = 0
-    while f"encoder.layer.{layers}.mlp.fc1.weight" in w:
-        layers += 1
-    if layers == 0:
-        raise ValueError("the weight dict holds no 'encoder.layer.0.mlp.fc1.weight'")
+    layers = _layer_count(w, "encoder.layer.{}.mlp.fc1.weight")
     F = int(np.shape(w["encoder.layer.0.mlp.fc1.weight"])[0])
     return Dinov2Geometry(image_size=224, patch_size=patch, hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F,
                           layer_norm_eps=float(eps), position_grid=grid)
@@ -565,18 +532,7 @@ def clip_text_tensor_specs(geom: CLIPTextGeometry = CLIP_TEXT_B):
         (t + "embeddings.position_embedding.weight", (geom.max_position_embeddings, D), "matrix"),
     ]
     for i in range(geom.num_layers):
-        p = f"{t}encoder.layers.{i}."
-        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
-        for n in ("q", "k", "v", "out"):
-            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
-        specs += [
-            (p + "layer_norm2.weight", (D,), "gamma"),
-            (p + "layer_norm2.bias", (D,), "bias"),
-            (p + "mlp.fc1.weight", (F, D), "matrix"),
-            (p + "mlp.fc1.bias", (F,), "bias"),
-            (p + "mlp.fc2.weight", (D, F), "matrix"),
-            (p + "mlp.fc2.bias", (D,), "bias"),
-        ]
+        specs += block_tensor_specs(f"{t}encoder.layers.{i}.", CLIP_BLOCK, D, F)
     specs += [(t + "final_layer_norm.weight", (D,), "gamma"), (t + "final_layer_norm.bias", (D,), "bias")]
     if geom.projection_dim:
         specs.append(("text_projection.weight", (geom.projection_dim, D), "matrix"))
@@ -586,18 +542,7 @@ def clip_text_tensor_specs(geom: CLIPTextGeometry = CLIP_TEXT_B):
 def make_clip_text_weights(seed: int = 3, geom: CLIPTextGeometry = CLIP_TEXT_B, std: float = 0.02) -> dict[str, np.ndarray]:
     """Seeded synthetic weights of a CLIP text tower, f32 arrays holding bf16-representable values: the generator and the
     LayerNorm spread (1 + 0.25 z, 0.1 z) of `make_clip_weights` on `clip_text_tensor_specs`."""
-    out: dict[str, np.ndarray] = {}
-    for tid, (name, shape, kind) in enumerate(clip_text_tensor_specs(geom)):
-        n = int(np.prod(shape))
-        z = irwin_hall_normal(seed, tid, n)
-        if kind == "gamma":
-            z = np.float32(1.0) + z * np.float32(0.25)
-        elif kind == "bias" and "layer_norm" in name:
-            z = z * np.float32(0.1)
-        else:
-            z = z * np.float32(std)
-        out[name] = round_to_bf16(z).reshape(shape)
-    return out
+    return _seeded_weights(clip_text_tensor_specs(geom), seed, _spread_rule(std, lambda name: "layer_norm" in name))
 
 
 def infer_clip_text_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quick_gelu", eos_token_id: int | None = None) -> CLIPTextGeometry:
@@ -606,11 +551,7 @@ def infer_clip_text_geometry(w: dict, eps: float = 1e-5, hidden_act: str = "quic
     vocabulary keeps <|endoftext|>)."""
     V, D = (int(v) for v in np.shape(w["text_model.embeddings.token_embedding.weight"]))
     T = int(np.shape(w["text_model.embeddings.position_embedding.weight"])[0])
-    layers = 0
-    while f"text_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
-        layers += 1
-    if layers == 0:
-        raise ValueError("the weight dict holds no 'text_model.encoder.layers.0.mlp.fc1.weight'")
+    layers = _layer_count(w, "text_model.encoder.layers.{}.mlp.fc1.weight")
     F = int(np.shape(w["text_model.encoder.layers.0.mlp.fc1.weight"])[0])
     P = int(np.shape(w["text_projection.weight"])[0]) if "text_projection.weight" in w else None
     return CLIPTextGeometry(hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F, vocab_size=V, max_position_embeddings=T,
@@ -696,18 +637,7 @@ def siglip_text_tensor_specs(geom: SiglipTextGeometry = SIGLIP_TEXT_B):
         (t + "embeddings.position_embedding.weight", (geom.max_position_embeddings, D), "matrix"),
     ]
     for i in range(geom.num_layers):
-        p = f"{t}encoder.layers.{i}."
-        specs += [(p + "layer_norm1.weight", (D,), "gamma"), (p + "layer_norm1.bias", (D,), "bias")]
-        for n in ("q", "k", "v", "out"):
-            specs += [(p + f"self_attn.{n}_proj.weight", (D, D), "matrix"), (p + f"self_attn.{n}_proj.bias", (D,), "bias")]
-        specs += [
-            (p + "layer_norm2.weight", (D,), "gamma"),
-            (p + "layer_norm2.bias", (D,), "bias"),
-            (p + "mlp.fc1.weight", (F, D), "matrix"),
-            (p + "mlp.fc1.bias", (F,), "bias"),
-            (p + "mlp.fc2.weight", (D, F), "matrix"),
-            (p + "mlp.fc2.bias", (D,), "bias"),
-        ]
+        specs += block_tensor_specs(f"{t}encoder.layers.{i}.", CLIP_BLOCK, D, F)
     specs += [(t + "final_layer_norm.weight", (D,), "gamma"), (t + "final_layer_norm.bias", (D,), "bias"),
               (t + "head.weight", (geom.projection_size, D), "matrix"), (t + "head.bias", (geom.projection_size,), "bias")]
     return specs
@@ -720,17 +650,7 @@ def make_siglip_text_weights(seed: int = 5, geom: SiglipTextGeometry = SIGLIP_TE
     """Seeded synthetic weights of a SigLIP text tower, f32 arrays holding bf16-representable values: the generator and the
     LayerNorm spread (1 + 0.25 z, 0.1 z) of `make_clip_weights` on `siglip_text_tensor_specs`.  `logits`: (logit_scale,
     logit_bias) as f32 arrays of shape (1,) beside the tensors (SiglipModel initialises them to log 10 and -10); None: left out."""
-    out: dict[str, np.ndarray] = {}
-    for tid, (name, shape, kind) in enumerate(siglip_text_tensor_specs(geom)):
-        n = int(np.prod(shape))
-        z = irwin_hall_normal(seed, tid, n)
-        if kind == "gamma":
-            z = np.float32(1.0) + z * np.float32(0.25)
-        elif kind == "bias" and "layer_norm" in name:
-            z = z * np.float32(0.1)
-        else:
-            z = z * np.float32(std)
-        out[name] = round_to_bf16(z).reshape(shape)
+    out = _seeded_weights(siglip_text_tensor_specs(geom), seed, _spread_rule(std, lambda name: "layer_norm" in name))
     if logits is not None:
         out["logit_scale"] = round_to_bf16(np.array([logits[0]], dtype=np.float32))
         out["logit_bias"] = round_to_bf16(np.array([logits[1]], dtype=np.float32))
@@ -741,11 +661,7 @@ def infer_siglip_text_geometry(w: dict, eps: float = 1e-6, pad_token_id: int = 1
     """The geometry of a `siglip_text_tensor_specs` weight dict, read off its tensor shapes; heads of 64."""
     V, D = (int(v) for v in np.shape(w["text_model.embeddings.token_embedding.weight"]))
     T = int(np.shape(w["text_model.embeddings.position_embedding.weight"])[0])
-    layers = 0
-    while f"text_model.encoder.layers.{layers}.mlp.fc1.weight" in w:
-        layers += 1
-    if layers == 0:
-        raise ValueError("the weight dict holds no 'text_model.encoder.layers.0.mlp.fc1.weight'")
+    layers = _layer_count(w, "text_model.encoder.layers.{}.mlp.fc1.weight")
     F = int(np.shape(w["text_model.encoder.layers.0.mlp.fc1.weight"])[0])
     P = int(np.shape(w["text_model.head.weight"])[0])
     return SiglipTextGeometry(hidden_size=D, num_layers=layers, num_heads=D // 64, intermediate_size=F, vocab_size=V, max_position_embeddings=T,
@@ -856,25 +772,7 @@ def vit_tensor_specs(geom: ViTGeometry = VIT_B16):
         ("embeddings.patch_embeddings.projection.bias", (D,), "bias"),
     ]
     for i in range(geom.num_layers):
-        p = f"layers.{i}."
-        specs += [
-            (p + "layernorm_before.weight", (D,), "gamma"),
-            (p + "layernorm_before.bias", (D,), "bias"),
-            (p + "attention.q_proj.weight", (D, D), "matrix"),
-            (p + "attention.q_proj.bias", (D,), "bias"),
-            (p + "attention.k_proj.weight", (D, D), "matrix"),
-            (p + "attention.k_proj.bias", (D,), "bias"),
-            (p + "attention.v_proj.weight", (D, D), "matrix"),
-            (p + "attention.v_proj.bias", (D,), "bias"),
-            (p + "attention.o_proj.weight", (D, D), "matrix"),
-            (p + "attention.o_proj.bias", (D,), "bias"),
-            (p + "layernorm_after.weight", (D,), "gamma"),
-            (p + "layernorm_after.bias", (D,), "bias"),
-            (p + "mlp.fc1.weight", (F, D), "matrix"),
-            (p + "mlp.fc1.bias", (F,), "bias"),
-            (p + "mlp.fc2.weight", (D, F), "matrix"),
-            (p + "mlp.fc2.bias", (D,), "bias"),
-        ]
+        specs += block_tensor_specs(f"layers.{i}.", VIT_BLOCK, D, F)
     specs += [("layernorm.weight", (D,), "gamma"), ("layernorm.bias", (D,), "bias")]
     return specs
 
@@ -893,17 +791,13 @@ def make_vit_weights(
     affine path of the kernels carries non-trivial data in the parity tests; the
     arithmetic cost is identical.
     """
-    out: dict[str, np.ndarray] = {}
-    for tid, (name, shape, kind) in enumerate(vit_tensor_specs(geom)):
-        n = int(np.prod(shape))
+    def rule(name, kind, z):
         if kind == "matrix" or trained_like:
-            z = irwin_hall_normal(seed, tid, n) * np.float32(std)
-            if kind == "gamma":
-                z = z + np.float32(1.0)
-        else:
-            z = np.full(n, 1.0 if kind == "gamma" else 0.0, dtype=np.float32)
-        out[name] = round_to_bf16(z).reshape(shape)
-    return out
+            z = z * np.float32(std)
+            return z + np.float32(1.0) if kind == "gamma" else z
+        return np.full(z.shape, 1.0 if kind == "gamma" else 0.0, dtype=np.float32)
+
+    return _seeded_weights(vit_tensor_specs(geom), seed, rule)
 
 
 def synthetic_crops(n: int, seed: int = 0, size: int = 224, start: int = 0) -> np.ndarray:

@@ -686,7 +686,7 @@ def test_load_clip_refusals_keep_the_previous_weights(crops40):
             return a.ctypes.data_as(C.POINTER(C.c_float))
 
         def attempt(change, pattern):
-            W, layers = eng._clip_struct(geom, arr)
+            W, layers = eng._weights_struct("clip", geom, arr)
             change(W)
             rc = eng.lib.mme_load_clip(eng.h, C.byref(W))
             text = eng.lib.mme_last_error(eng.h).decode()

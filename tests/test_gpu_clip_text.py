@@ -543,7 +543,7 @@ def test_refusals_leave_the_context_usable():
         for change, text in ((dict(num_heads=12), "heads = 12 at hidden = 512"), (dict(max_position_embeddings=64), "max_positions = 64; supported: 77"),
                              (dict(projection_dim=96), "proj_dim = 96"), (dict(eos_token_id=T2.vocab_size), "eos_token_id = 256")):
             g = dataclasses.replace(T2, **change)
-            W, layers = Engine._clip_text_struct(g, lambda name: None)  # geometry only: refused before any tensor is read
+            W, layers = Engine._weights_struct("clip_text", g, lambda name: None)  # geometry only: refused before any tensor is read
             assert e.lib.mme_load_clip_text(e.h, C.byref(W)) != 0 and text in e.lib.mme_last_error(e.h).decode(), change
             assert e.weights_fingerprint() == fp and e.text_info()["loaded"] == 1  # a refusal leaves the context unchanged
         # ids: straight at the C ABI, then through Engine.text_forward (which adds no check of its own)

@@ -947,7 +947,7 @@ def test_refusals_leave_the_previous_weights_in_place(crops40):
             return keep[name][first:].ctypes.data_as(C.POINTER(C.c_float))
 
         def refused(change, text):
-            W, layers = eng._siglip_struct(geom, arr)
+            W, layers = eng._weights_struct("siglip", geom, arr)
             change(W)
             rc = eng.lib.mme_load_siglip(eng.h, C.byref(W))
             msg = eng.lib.mme_last_error(eng.h).decode()

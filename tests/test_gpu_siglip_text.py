@@ -595,7 +595,7 @@ def test_refusals_leave_the_context_as_it_was():
                              (dict(num_heads=12), "heads = 12 at hidden = 512"), (dict(projection_size=96), "projection_size = 96"),
                              (dict(pad_token_id=256), "pad_token_id = 256")):
             g = dataclasses.replace(T2, **change)
-            W, layers = Engine._siglip_text_struct(g, lambda name: None, None)  # geometry only: refused before any tensor is read
+            W, layers = Engine._weights_struct("siglip_text", g, lambda name: None, logits=None)  # geometry only: refused before any tensor is read
             assert e.lib.mme_load_siglip_text(e.h, C.byref(W)) != 0 and text in e.lib.mme_last_error(e.h).decode(), change
             assert e.lib.mme_load_siglip_text_as(e.h, C.byref(W), 1, None) != 0 and text in e.lib.mme_last_error(e.h).decode(), change
             assert e.weights_fingerprint() == fp and e.text_geometry()["kind"] == "siglip"

@@ -757,13 +757,13 @@ def test_patch_14_is_refused_and_the_previous_weights_stay(crops40):
             return a.ctypes.data_as(C.POINTER(C.c_float))
 
         for patch in (14, 8, 64):
-            W, layers = eng._clip_struct(geom, arr)
+            W, layers = eng._weights_struct("clip", geom, arr)
             W.vit.patch_size = patch
             rc = eng.lib.mme_load_clip(eng.h, C.byref(W))
             text = eng.lib.mme_last_error(eng.h).decode()
             assert rc == -1 and f"patch_size = {patch}; supported: 16, 32" in text, (rc, text)
             assert eng.weights_fingerprint() == fp and eng.vit_geometry().patch_size == 32
-        W, layers = eng._clip_struct(geom, arr)
+        W, layers = eng._weights_struct("clip", geom, arr)
         W.vit.image_size = 384
         assert eng.lib.mme_load_clip(eng.h, C.byref(W)) == -1 and "image_size = 384; supported: 224" in eng.lib.mme_last_error(eng.h).decode()
         e32, e16 = _uniform(eng, crops40)
