@@ -702,6 +702,22 @@ int mme_vit_forward(mme_ctx* ctx, const uint16_t* patches_dev, int n, int pool_t
 int mme_embed(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* offs_host, const int32_t* hw_host,
               int n, int pool_token, float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
 
+/* ---- patch-token rows of the last block ------------------------------------
+ * mme_vit_forward / mme_embed that also return token rows: tokens_bf16_dev bf16[n, ntok, hidden], row (b, t) = the tower's
+ * final LayerNorm (`layernorm` of a ViT or DINOv2, `post_layernorm` of CLIP and SigLIP) of residual row tok0 + t of crop b,
+ * then x / max(||x||, 1e-12), rounded once to bf16: the bits mme_vit_forward writes to emb_bf16_dev for pool_token =
+ * tok0 + t on a tower without projection.  The width is always `hidden` (CLIP's visual_projection is not applied to token
+ * rows).  The pooled outputs (either may be NULL) are mme_vit_forward's / mme_embed's for pool_token, bit for bit.
+ *   tok0, ntok   0 <= tok0, 1 <= ntok, tok0 + ntok <= tokens (197 / 50 / 196 / 257), else MME_E_ARG; the patch tokens are
+ *                tok0 = 1 where the tower has a class token (ViT, CLIP, DINOv2), 0 for SigLIP
+ * A pass that returns tokens runs the last block unpruned whatever mme_set_forward_pruning says; the setting is left as it
+ * is.  Chunked as mme_vit_forward; element offsets into tokens_bf16_dev are 64-bit (65 536 crops x 196 x 768 = 9.9 G).
+ * Every single-tile image tower, ln mode and GEMM variant; a tile-ViT context and a context without a load are MME_E_STATE. */
+int mme_vit_tokens(mme_ctx* ctx, const uint16_t* patches_dev, int n, int pool_token, int tok0, int ntok, uint16_t* tokens_bf16_dev,
+                   float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
+int mme_embed_tokens(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* offs_host, const int32_t* hw_host, int n, int pool_token,
+                     int tok0, int ntok, uint16_t* tokens_bf16_dev, float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
+
 /* f32 vectors (the reference moves embeddings as Python float lists, embedder.py:132) ->
  * L2-normalised bf16 rows, same normalisation as last_pooling (F.normalize, eps 1e-12).
  * x_dev float[rows,d] (d % 4 == 0, 16-byte aligned rows), y_dev bf16[rows,d]. */

@@ -225,6 +225,9 @@ EXPORTS = {
     "mme_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "mme_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_vit_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_embed_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "mme_normalise_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "mme_cosine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "mme_cosine_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -1284,6 +1287,50 @@ class Engine:
                                        e32.data_ptr() if e32 is not None else None, e16.data_ptr() if e16 is not None else None,
                                        self._stream()), "mme_embed")
         return e32, e16
+
+    def _token_window(self, tok0, ntok):
+        """The default window is the patch tokens: from 1 where the tower has a class token (ViT, CLIP, DINOv2), from 0 for SigLIP."""
+        g = self.vit_geometry()
+        first = 0 if self.encoder_info()["kind"] == "siglip" else 1
+        tok0 = first if tok0 is None else int(tok0)
+        ntok = g.num_patches + first - tok0 if ntok is None else int(ntok)
+        return tok0, ntok, g
+
+    def _token_out(self, out, n, ntok, hidden, device):
+        t = self.torch
+        if out is None:
+            return t.empty((n, max(ntok, 0), hidden), dtype=t.bfloat16, device=device)
+        if out.dtype != t.bfloat16 or not out.is_contiguous() or out.device != device or tuple(out.shape) != (n, ntok, hidden):
+            raise MmeError(f"token rows: `out` must be a contiguous bfloat16 tensor [{n}, {ntok}, {hidden}] on the input's device")
+        return out
+
+    def vit_tokens(self, patches, pool_token: int = 0, tok0=None, ntok=None, out=None, want_f32: bool = True, want_bf16: bool = True):
+        """vit_forward that also returns the final-LayerNorm, L2-normalised token rows tok0 .. tok0 + ntok - 1 of every crop
+        (mme_vit_tokens; default: the patch tokens) -> (tokens bf16 [n, ntok, hidden], emb_f32, emb_bf16)."""
+        t = self.torch
+        tok0, ntok, g = self._token_window(tok0, ntok)
+        n, d = patches.shape[0] // g.num_patches, self.embed_dim
+        tokens = self._token_out(out, n, ntok, g.hidden_size, patches.device)
+        e32 = t.empty((n, d), dtype=t.float32, device=patches.device) if want_f32 else None
+        e16 = t.empty((n, d), dtype=t.bfloat16, device=patches.device) if want_bf16 else None
+        self._check(self.lib.mme_vit_tokens(self.h, patches.data_ptr(), n, int(pool_token), tok0, ntok, tokens.data_ptr(),
+                                            e32.data_ptr() if want_f32 else None, e16.data_ptr() if want_bf16 else None, self._stream()), "mme_vit_tokens")
+        return tokens, e32, e16
+
+    def embed_tokens(self, pix, offs, hw, pool_token: int = 0, tok0=None, ntok=None, out=None, out_f32=None, out_bf16=None, want_f32: bool = True,
+                     want_bf16: bool = True):
+        """embed that also returns the token rows (mme_embed_tokens), as vit_tokens."""
+        t = self.torch
+        offs, hw = self._crop_tables(offs, hw)
+        n = len(offs)
+        tok0, ntok, g = self._token_window(tok0, ntok)
+        tokens = self._token_out(out, n, ntok, g.hidden_size, pix.device)
+        e32 = out_f32 if out_f32 is not None else (t.empty((n, self.embed_dim), dtype=t.float32, device=pix.device) if want_f32 else None)
+        e16 = out_bf16 if out_bf16 is not None else (t.empty((n, self.embed_dim), dtype=t.bfloat16, device=pix.device) if want_bf16 else None)
+        self._check(self.lib.mme_embed_tokens(self.h, pix.data_ptr(), offs.ctypes.data, hw.ctypes.data, n, int(pool_token), tok0, ntok,
+                                              tokens.data_ptr(), e32.data_ptr() if e32 is not None else None,
+                                              e16.data_ptr() if e16 is not None else None, self._stream()), "mme_embed_tokens")
+        return tokens, e32, e16
 
     def normalise_rows(self, x):
         """f32 CUDA tensor [n,d] -> L2-normalised bf16 [n,d]."""

@@ -143,7 +143,10 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
     return MME_OK;
 }
 
-int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s) {
+// tok_out non-null (mme_vit_tokens / mme_embed_tokens): the last block runs unpruned whatever prune_last says, and behind it
+// the final LayerNorm + L2 of rows tok0 .. tok0 + ntok - 1 of every crop go to tok_out bf16 [n, ntok, hidden]
+int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s,
+                  bf16_t* tok_out = nullptr, int tok0 = 0, int ntok = 0) {
     const bool t50 = c->geom.t50();  // patch 32: 50 tokens, its own patch embedding, attention and pooling kernels
     const bool t257 = c->geom.t257();  // patch 14 (DINOv2): 257 tokens, the retiled K = 640 patch matrix, attention_mid.hip
     const bool sig = c->siglip;      // SigLIP: 196 tokens (no class token), tanh-GELU, the attention-pooling head behind the last block
@@ -251,7 +254,7 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
         // (K8 pools token `pool_token`), so the query block that holds it is the only one attended, and the second half of
         // the block runs on the n gathered rows instead of n x 197.  Same kernels, same per-row arithmetic: the
         // embeddings are bit-identical to the full pass (tests/test_gpu_parity.py).
-        const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0 && !sig;  // (SigLIP's head reads every token row)
+        const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0 && !sig && !tok_out;  // (SigLIP's head and a token pass read every token row)
         {
             Timed t(c, s, KC_ATTN);
             if (t50) {  // exact kernel only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
@@ -299,6 +302,10 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, floa
             if ((r = P.gemm(c->act == 2 ? EPI_BIAS_TGELU : c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, g))) return r;
             if ((r = P.residual(c->mlp.p, L.w.fc2_w, L.w.fc2_b, F, M, c->x.p, false))) return r;
         }
+    }
+    if (tok_out) {  // the token rows of the last block, before any tail touches the workspace (none writes x)
+        Timed t(c, s, KC_POOL);
+        HIP_TRY(c, launch_token_rows(c->x.p, c->lnf_g, c->lnf_b, n, T, tok0, ntok, D, c->ln_eps, tok_out, s));
     }
     if (sig) {
         // SiglipMultiheadAttentionPoolingHead: K | V = in_proj(post_layernorm(x)) over every token row, one constant query
@@ -853,6 +860,76 @@ int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t
         }
         r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : t257 ? c->patches14.p : c->patches.p), m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
                           emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
+        if (r) return r;
+    }
+    return MME_OK;
+}
+
+// what mme_vit_tokens / mme_embed_tokens refuse alike
+static int check_token_call(mme_ctx* c, const char* who, int pool_token, int tok0, int ntok, const void* tokens) {
+    if (!c->loaded && c->tv) return fail(c, MME_E_STATE, "%s: encoder tile_vit; supported: the single-tile image towers (vit, clip, siglip, dinov2)", who);
+    if (!c->loaded) return fail(c, MME_E_STATE, "%s: call mme_load_vit first", who);
+    const int T = c->geom.tokens();
+    if (pool_token < 0 || pool_token >= T) return fail(c, MME_E_ARG, "%s: pool_token %d outside 0..%d", who, pool_token, T - 1);
+    if (tok0 < 0 || ntok < 1 || (int64_t)tok0 + ntok > T)
+        return fail(c, MME_E_ARG, "%s: token window tok0 %d, ntok %d; supported tok0 >= 0, ntok >= 1, tok0 + ntok <= %d (the tower's tokens)", who, tok0, ntok, T);
+    if (!tokens) return fail(c, MME_E_ARG, "%s: tokens_bf16_dev is NULL", who);
+    return MME_OK;
+}
+
+int mme_vit_tokens(mme_ctx* c, const uint16_t* patches, int n, int pool_token, int tok0, int ntok, uint16_t* tokens, float* emb_f32,
+                   uint16_t* emb_bf16, void* stream) {
+    if (!c) return MME_E_ARG;
+    int r = check_token_call(c, "mme_vit_tokens", pool_token, tok0, ntok, tokens);
+    if (r) return r;
+    if (n < 0 || (n > 0 && !patches)) return fail(c, MME_E_ARG, "mme_vit_tokens: null patches or n<0");
+    if (n == 0) return MME_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((r = ensure_workspace(c))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t D = (size_t)c->geom.hidden;
+    for (int s0 = 0; s0 < n; s0 += c->chunk) {
+        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
+        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * c->geom.crop_values(), m, pool_token,
+                          emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
+                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s,
+                          (bf16_t*)tokens + (size_t)s0 * (size_t)ntok * D, tok0, ntok);
+        if (r) return r;
+    }
+    return MME_OK;
+}
+
+int mme_embed_tokens(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, int pool_token, int tok0, int ntok,
+                     uint16_t* tokens, float* emb_f32, uint16_t* emb_bf16, void* stream) {
+    if (!c) return MME_E_ARG;
+    int r = check_token_call(c, "mme_embed_tokens", pool_token, tok0, ntok, tokens);
+    if (r) return r;
+    if (n < 0 || (n > 0 && (!pix || !offs || !hw))) return fail(c, MME_E_ARG, "mme_embed_tokens: null argument or n<0");
+    if (n == 0) return MME_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((r = ensure_workspace(c))) return r;
+    if ((r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
+    const bool t50 = c->geom.t50(), t257 = c->geom.t257();  // K1 -> retile -> pass, as mme_embed
+    if (t50 && (r = ensure(c, c->patches32, (size_t)c->chunk * CROP_VALUES * 2))) return r;
+    if (t257 && (r = ensure(c, c->patches14, (size_t)c->chunk * c->geom.crop_values() * 2))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t D = (size_t)c->geom.hidden;
+    for (int s0 = 0; s0 < n; s0 += c->chunk) {
+        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
+        if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));  // crop tables are reused per chunk
+        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)c->patches.p, s);
+        if (r) return r;
+        if (t50) {
+            Timed t(c, s, KC_PRE);
+            HIP_TRY(c, launch_retile_p32(c->patches.p, c->patches32.p, m, s));
+        } else if (t257) {
+            Timed t(c, s, KC_PRE);
+            HIP_TRY(c, launch_retile_p14(c->patches.p, c->patches14.p, m, s));
+        }
+        r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : t257 ? c->patches14.p : c->patches.p), m, pool_token,
+                          emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
+                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s,
+                          (bf16_t*)tokens + (size_t)s0 * (size_t)ntok * D, tok0, ntok);
         if (r) return r;
     }
     return MME_OK;

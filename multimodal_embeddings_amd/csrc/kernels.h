@@ -93,6 +93,10 @@ hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, i
 // final LayerNorm on row b*tokens+tok of d values, L2 normalise, write f32 and/or bf16 [B, d]; tokens and tok as launch_pool_ln
 hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps,
                        float* emb_f32, void* emb_bf16, hipStream_t s);
+// launch_pool over a window of rows per crop: final LayerNorm + L2 of rows b*tokens + tok0 .. + ntok - 1 -> y bf16 [n, ntok, d], each
+// row K8's bf16 output for that pool token bit for bit; tokens = 197, 196, 50 or 257, 0 <= tok0, 1 <= ntok, tok0 + ntok <= tokens
+hipError_t launch_token_rows(const void* x, const float* gamma, const float* beta, int n, int tokens, int tok0, int ntok, int d, float eps, void* y,
+                             hipStream_t s);
 // behind a patch-embed GEMM under EPI_F32 (acc f32 [n * patches, d]), one rounding per value: with a class token (cls
 // non-null, tokens = 50, patches = 49) x[b*tokens + 1 + p] = bf16((acc + bias) + pos[1 + p]) and x[b*tokens] = bf16(cls + pos[0]);
 // without one (cls null, tokens = patches = 196) x[b*tokens + p] = bf16((acc + bias) + pos[p]).  Any other pair is hipErrorInvalidValue

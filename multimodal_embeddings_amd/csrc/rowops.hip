@@ -163,6 +163,23 @@ __global__ __launch_bounds__(256) void pool_ln_l2(const bf16_t* __restrict__ x, 
     row_l2_store<D>(v, lane, emb_f32, emb_bf16, (int64_t)b * D);
 }
 
+// pool_ln_l2 over a window of token rows per crop: row (b, t), t < ntok, is the final LayerNorm and the L2 step of residual
+// row b * tokens + tok0 + t -> bf16 at element (b * ntok + t) * D of y.  ln_row and row_l2_store in K8's order, so a row
+// equals K8's bf16 output for pool_token = tok0 + t bit for bit.  Every offset in 64 bits (65 536 crops x 196 x 768 values).
+template <int D>
+__global__ __launch_bounds__(256) void token_ln_l2(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta, int64_t rows, int tokens, int tok0, int ntok, float eps,
+                                                   bf16_t* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t b = row / ntok;
+    const int t = (int)(row - b * ntok);
+    float v[D / 64];
+    ln_row<D>(x + (b * tokens + tok0 + t) * D, gamma, beta, eps, lane, v);
+    row_l2_store<D>(v, lane, nullptr, y, row * D);
+}
+
 // f32 rows of any width d (d % 4 == 0) -> L2-normalised bf16 rows (one wave per row).  The
 // reference hands vectors around as Python float lists (embedder.py:132); this is the way
 // such vectors enter the bf16 cosine kernel, with the same normalisation as last_pooling.
@@ -380,6 +397,16 @@ hipError_t launch_pool_t257(const void* x, const float* gamma, const float* beta
     if (!vit_width_built(d) || tok < 0 || tok > 256) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
     ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, 257, tok, eps, emb_f32, (bf16_t*)emb_bf16)
+    return hipGetLastError();
+}
+
+hipError_t launch_token_rows(const void* x, const float* gamma, const float* beta, int n, int tokens, int tok0, int ntok, int d, float eps, void* y,
+                             hipStream_t s) {
+    const bool layout = tokens == VIT_T || tokens == VIT_NP || tokens == 50 || tokens == 257;
+    if (!vit_width_built(d) || !layout || tok0 < 0 || ntok < 1 || tok0 + ntok > tokens || !y) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    const int64_t rows = (int64_t)n * ntok;
+    ROW_KERNEL_BY_WIDTH(d, token_ln_l2, dim3((unsigned)((rows + 3) / 4)), s, (const bf16_t*)x, gamma, beta, rows, tokens, tok0, ntok, eps, (bf16_t*)y)
     return hipGetLastError();
 }
 

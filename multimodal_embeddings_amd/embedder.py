@@ -573,7 +573,7 @@ class RegionEmbedder:
                     try:
                         compute.wait_event(pipe["ev_in"][slot])
                         self._run_cap_jobs(engine, pix, jobs)  # this thread, the compute stream: ordered before the pass
-                        e32, _ = engine.embed(pix, offs, hw, self.pool_token, want_bf16=False)
+                        e32 = self._pass(engine, pix, offs, hw, idx)
                         pipe["ev_done"][slot].record(compute)
                     except Exception as e:  # embedder.py:223-224
                         logger.error(f"Error in batch processing: {e}")
@@ -610,6 +610,23 @@ class RegionEmbedder:
             producer.join()
         return results
 
+    def _pass(self, engine, pix, offs, hw, idx):
+        """The device pass of one packed group -> f32 [n, embed_dim].  Under get_patch_embeddings the same pass also returns the
+        patch-token rows (mme_embed_tokens; its pooled rows are mme_embed's bit for bit), which go to rows `idx` of the sink."""
+        sink = getattr(self, "_token_sink", None)
+        if sink is None:
+            e32, _ = engine.embed(pix, offs, hw, self.pool_token, want_bf16=False)
+            return e32
+        t = self.torch
+        tokens, e32, _ = engine.embed_tokens(pix, offs, hw, self.pool_token, want_bf16=False)
+        rows = t.as_tensor(list(idx), dtype=t.int64, device=tokens.device)
+        if sink.device == tokens.device:
+            sink.index_copy_(0, rows, tokens)
+        else:  # another context's share: through that device's stream, then ordered into the sink's
+            t.cuda.current_stream(tokens.device).synchronize()
+            sink.index_copy_(0, rows.to(sink.device), tokens.to(sink.device))
+        return e32
+
     def _embed_list_serial(self, dev_idx, items):
         """The unpipelined form (decode -> pack -> pass -> lists per group), used by the tile-ViT option."""
         engine = self.engines[dev_idx]
@@ -640,7 +657,7 @@ class RegionEmbedder:
                     pv, ids, _, nt = engine.preprocess_tiles(pix, offs, hw, 560, 4)
                     _, e32, _ = engine.tile_vit_forward(pv, ids, nt, want_bf16=False)
                 else:
-                    e32, _ = engine.embed(pix, offs, hw, self.pool_token, want_bf16=False)
+                    e32 = self._pass(engine, pix, offs, hw, [i for i, _ in group])
                 rows = e32.cpu().tolist()
                 results.extend((i, row) for (i, _), row in zip(group, rows))
             except Exception as e:  # embedder.py:223-224
@@ -707,6 +724,40 @@ class RegionEmbedder:
                     arr[i] = row
             return arr, ok
         return embeddings
+
+    def get_patch_embeddings(self, images, out=None, batch_size=config.BATCH_SIZE):
+        """get_image_embeddings that also keeps the patch tokens of every crop: returns (vectors, tokens).
+
+        `vectors` is exactly what get_image_embeddings returns for the same input (float lists, None holes included).  `tokens` is a
+        bfloat16 CUDA tensor [n, ntok, hidden] in input order on the first context's device -- the caller's `out` if given -- whose
+        row (i, t) is the tower's final LayerNorm of patch token t of crop i, L2-normalised: ntok = 196 (ViT/16, CLIP/16, SigLIP), 49
+        (patch 32) or 256 (DINOv2); the class token is left out.  A failed item's block is zeros.
+
+        Size: n * ntok * hidden * 2 bytes -- 301 KB per ViT-B/16 crop, 19.7 GB at 65 536 crops; pass `out` to place it, or call in
+        slices.  Not available for encoder="mllama_tiles" (the tile tower's 4 x 1601 tokens of 1280 are another object)."""
+        if getattr(self, "encoder", "vit_b16") == "mllama_tiles":
+            raise NotImplementedError("get_patch_embeddings: encoder 'mllama_tiles'; supported: the single-tile image towers "
+                                      "(vit, clip, siglip_vit, dinov2)")
+        t = self.torch
+        n = len(images)
+        g = self.engine.vit_geometry()
+        shape = (n, g.num_patches, g.hidden_size)
+        dev = t.device(self.devices[0])
+        if out is None:
+            out = t.zeros(shape, dtype=t.bfloat16, device=dev)
+        else:
+            if out.dtype != t.bfloat16 or not out.is_contiguous() or not out.is_cuda or tuple(out.shape) != shape:
+                raise ValueError(f"get_patch_embeddings: `out` must be a contiguous bfloat16 CUDA tensor {list(shape)}")
+            out.zero_()
+        t.cuda.synchronize(out.device)  # the zeros are in place before any context's stream writes a block
+        self._token_sink = out
+        try:
+            vectors = self.get_image_embeddings(images, batch_size=batch_size)
+        finally:
+            self._token_sink = None
+            for d in self.devices:
+                t.cuda.synchronize(t.device(d))
+        return vectors, out
 
     def embed(self, region):
         """north_star `embed(region) -> vec`: one crop -> float32[embed_dim] (raises on failure)."""
