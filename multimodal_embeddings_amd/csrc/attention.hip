@@ -87,7 +87,7 @@ __device__ __forceinline__ void attn_body(const bf16_t* __restrict__ qkv, bf16_t
     const int n_items = nloc * hpw;
     if (n_items == 0) return;
     // item -> (crop base, head)
-    // rev (share bit 17): walk the blocks from the LAST crop down (zig-zag order of consecutive kernels, capi.hip forward_chunk)
+    // rev (share bit 17): walk the blocks from the LAST crop down (zig-zag order of consecutive kernels, image_tower.hip)
     const bool rev = (share >> 17) & 1;
     auto item_blk = [&](int it) { const int blk = blockIdx.x + (it / hpw) * gridDim.x; return rev ? nblk - 1 - blk : blk; };
     auto item_head = [&](int it) { return (item_blk(it) % hsplit) * hpw + (it - (it / hpw) * hpw); };

@@ -1,4 +1,5 @@
-// C ABI (include/mme.h): context, workspace and the launch sequences (weight loading: weight_load.hip).
+// C ABI (include/mme.h): context, K1 (preprocessing) and the launch sequences that are no encoder pass (the image towers:
+// image_tower.hip; weight loading: weight_load.hip).
 // No exceptions cross the boundary; every failure sets ctx->err and returns a code.
 #include "../../include/mme.h"
 
@@ -47,28 +48,6 @@ int ensure(mme_ctx* c, DevBuf& b, size_t bytes) {
     hipError_t e = hipMalloc(&b.p, bytes);
     if (e != hipSuccess) return fail(c, MME_E_NOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
     b.bytes = bytes;
-    return MME_OK;
-}
-
-// The workspace follows the chunk AND the geometry: a context that was reloaded with a wider encoder regrows it
-// (ensure() never shrinks a buffer, so going back to a narrower one keeps what is there).
-int ensure_workspace(mme_ctx* c) {
-    const int D = c->geom.hidden, F = c->geom.mlp;
-    const int T = c->geom.tokens();  // 197, or 50 at patch 32 (a quarter of the rows; ensure() keeps the larger buffers)
-    if (c->ws_chunk == c->chunk && c->ws_hidden == D && c->ws_mlp == F && c->ws_tokens == T) return MME_OK;
-    const size_t rows = (size_t)c->chunk * T;
-    int r;
-    if ((r = ensure(c, c->x, rows * D * 2))) return r;
-    if ((r = ensure(c, c->hbuf, rows * D * 2))) return r;
-    if ((r = ensure(c, c->qkv, rows * 3 * D * 2))) return r;
-    if ((r = ensure(c, c->att, rows * D * 2))) return r;
-    if ((r = ensure(c, c->mlp, rows * F * 2))) return r;
-    if ((r = ensure(c, c->stats, rows * 2 * sizeof(float)))) return r;
-    if ((r = ensure(c, c->lnpart, rows * 2 * (D / 64) * sizeof(float)))) return r;
-    c->ws_chunk = c->chunk;
-    c->ws_hidden = D;
-    c->ws_mlp = F;
-    c->ws_tokens = T;
     return MME_OK;
 }
 
@@ -143,245 +122,6 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
     return MME_OK;
 }
 
-// tok_out non-null (mme_vit_tokens / mme_embed_tokens): the last block runs unpruned whatever prune_last says, and behind it
-// the final LayerNorm + L2 of rows tok0 .. tok0 + ntok - 1 of every crop go to tok_out bf16 [n, ntok, hidden]
-int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, int pool_token, float* emb_f32, bf16_t* emb_bf16, hipStream_t s,
-                  bf16_t* tok_out = nullptr, int tok0 = 0, int ntok = 0) {
-    const bool t50 = c->geom.t50();  // patch 32: 50 tokens, its own patch embedding, attention and pooling kernels
-    const bool t257 = c->geom.t257();  // patch 14 (DINOv2): 257 tokens, the retiled K = 640 patch matrix, attention_mid.hip
-    const bool sig = c->siglip;      // SigLIP: 196 tokens (no class token), tanh-GELU, the attention-pooling head behind the last block
-    const int T = c->geom.tokens();
-    const int M = n * T;
-    const int D = c->geom.hidden, F = c->geom.mlp, NL = c->geom.layers;  // the geometry of the loaded weights
-    // The epilogues leave the LayerNorm partial planes from their interior-tile code only, and at a width that is no
-    // multiple of the 256-column tile (384) the last column tile of every row panel is no interior tile: its two slices
-    // would be missing.  There mode 2 takes mode 1's statistics pass over x, which sums in the same canonical order:
-    // the same bits, one more read of x per LayerNorm.
-    const bool planes = c->ln_mode == 2 && (D % 256) == 0;
-    EncoderPass P{c, s, D, F, c->ln_eps, c->act, c->x.p, c->qkv.p, c->att.p, c->mlp.p, (float*)c->stats.p};
-    P.lnpart = (float*)c->lnpart.p;  // handed to the residual GEMMs in every mode,
-    P.lnpart_rows = (int64_t)c->ws_chunk * T;
-    P.planes = planes;               // used where the epilogues leave all of them
-    P.zigzag = c->zigzag;  // mme_set_tile_order; only this tower alternates the walk (the patch embedding and the tails walk forwards)
-    GemmArgs g{};
-    int r;
-    if (t50 || t257) {
-        // patch 32: the patch-embed GEMM leaves f32 [n * 49, D] in the qkv buffer (dead until layer 0; 196 D n bytes of its
-        // 300 D n), embed_rows adds bias and position rows, rounds once and writes the [CLS] rows in the same launch
-        // patch 14: the same with f32 [n * 256, D] (1024 D n bytes of the buffer's 1542 D n) and K = 640
-        g.A = patches;
-        g.W = c->patch_w;
-        g.M = n * c->geom.np();
-        g.N = D;
-        g.K = c->geom.patch_dim();
-        g.outf = (float*)c->qkv.p;
-        g.ldf = D;
-        if ((r = P.gemm(EPI_F32, g))) return r;
-        Timed t(c, s, KC_LN);
-        if (t257) HIP_TRY(c, launch_embed_rows_t257((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
-        else HIP_TRY(c, launch_embed_rows((const float*)c->qkv.p, c->patch_b, c->pos, c->cls, c->x.p, n, T, D, s));
-    } else if (sig) {
-        // no class token: patch row m IS token row m, but EPI_PATCH (and its interior-tile form) maps rows past the [CLS]
-        // rows at compile time.  As at patch 32 the GEMM leaves f32 [n * 196, D] in the dead qkv buffer (784 D n of its
-        // 1176 D n bytes) and a row kernel adds bias and position rows in EPI_PATCH's f32 order, one rounding
-        g.A = patches;
-        g.W = c->patch_w;
-        g.M = M;
-        g.N = D;
-        g.K = VIT_PATCH_DIM;
-        g.outf = (float*)c->qkv.p;
-        g.ldf = D;
-        if ((r = P.gemm(EPI_F32, g))) return r;
-        Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_embed_rows((const float*)c->qkv.p, c->patch_b, c->pos, nullptr, c->x.p, n, T, D, s));
-    } else {
-        g.A = patches;
-        g.W = c->patch_w;
-        g.M = n * VIT_NP;
-        g.N = D;
-        g.K = VIT_PATCH_DIM;
-        g.bias = c->patch_b;
-        g.pos = c->pos;
-        g.out = c->x.p;
-        g.ldo = D;
-        if (planes && !c->clip) {  // the 256 x 256 kernel leaves the LayerNorm partial sums of the token rows it writes
-            g.ln_part = P.lnpart;
-            g.ln_part_rows = P.lnpart_rows;
-        }
-        if ((r = P.gemm(EPI_PATCH, g))) return r;
-    }
-    const GemmArgs patch_args = g;
-    if (!t50 && !t257 && !sig) {
-        Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_cls_rows(c->x.p, c->cls, c->pos, n, D, s));
-    }
-    if ((r = reset_attn_guards(c, NL, s))) return r;
-    // The first LayerNorm of the pass.  The statistics of every later one come from the block (EncoderPass::stats_after).
-    if (c->clip) {
-        // CLIP: pre_layrnorm over every token row, in place; the same launch leaves the statistics of the rows it wrote,
-        // in the canonical order: the first folded LayerNorm needs neither planes nor another pass over x
-        Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_pre_ln(c->x.p, c->pre_g, c->pre_b, M, D, c->ln_eps, (float*)c->stats.p, s));
-    } else if (!t50 && !t257 && !sig && planes && gemm_runs_256(patch_args, c->gemm_variant)) {  // (patch 32, patch 14, SigLIP: no planes from the f32 epilogue; the canonical pass below gives the same bits)
-        // first LayerNorm of the pass: the patch-embed epilogue left the partial sums of every token row an INTERIOR tile
-        // wrote (patch rows [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th
-        // row) and the rows of the ragged last tile take the stand-alone kernel, same canonical order
-        const int64_t interior = (int64_t)(patch_args.M / 256) * 256;                      // patch rows
-        const int64_t t_int = interior ? interior - 1 + (interior - 1) / VIT_NP + 2 : 0;   // one past the last token row they map to
-        Timed t(c, s, KC_LN);
-        HIP_TRY(c, launch_ln_finish((const float*)c->lnpart.p, patch_args.ln_part_rows, t_int, D, c->ln_eps, (float*)c->stats.p, s));
-        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, 0, t_int, D, c->ln_eps, (float*)c->stats.p, s, VIT_T));  // [CLS] rows below t_int
-        HIP_TRY(c, launch_ln_stats_canonical(c->x.p, t_int, M, D, c->ln_eps, (float*)c->stats.p, s));
-    } else if (c->ln_mode != 0 && (r = P.stats_from_x(c->x.p, 0, M))) {
-        return r;
-    }
-    for (int l = 0; l < NL; ++l) {
-        const LayerDev& L = c->layer[l];
-        if (c->ln_mode != 0) {  // LN1 folded into the QKV GEMM: x is read once, nothing normalised is written
-            if ((r = P.qkv_ln(L.w, M))) return r;
-        } else {
-            {
-                Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_layernorm(c->x.p, L.ln1_g, L.ln1_b, c->hbuf.p, M, D, c->ln_eps, s));
-            }
-            g = GemmArgs{};
-            g.A = c->hbuf.p; g.W = L.qkv_w; g.M = M; g.N = 3 * D; g.K = D;
-            g.bias = L.qkv_b; g.out = c->qkv.p; g.ldo = 3 * D;
-            g.reverse_m = P.next_dir();
-            if ((r = P.gemm(EPI_BIAS, g))) return r;
-        }
-        // Pruned last layer (mme_set_forward_pruning): after the last attention only ONE token row per crop is ever read
-        // (K8 pools token `pool_token`), so the query block that holds it is the only one attended, and the second half of
-        // the block runs on the n gathered rows instead of n x 197.  Same kernels, same per-row arithmetic: the
-        // embeddings are bit-identical to the full pass (tests/test_gpu_parity.py).
-        const bool pruned = c->prune_last && l + 1 == NL && c->ln_mode != 0 && !sig && !tok_out;  // (SigLIP's head and a token pass read every token row)
-        {
-            Timed t(c, s, KC_ATTN);
-            if (t50) {  // exact kernel only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
-                if (P.zigzag != 2) P.next_dir();
-                HIP_TRY(c, launch_attention_t50(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
-            } else if (t257) {  // as patch 32: exact kernel only, no walk order
-                if (P.zigzag != 2) P.next_dir();
-                HIP_TRY(c, launch_attention_t257(c->qkv.p, c->att.p, n, c->geom.heads, s, pruned ? pool_token / 32 : -1));
-            } else {
-                HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, c->geom.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
-                                            pruned ? pool_token / 32 : -1, P.zigzag == 2 ? true : P.next_dir() != 0, T));
-            }
-        }
-        const bool last = l + 1 == NL;  // no statistics after the last block: the final LayerNorm touches the pooled row only (K8)
-        if (pruned) {
-            bf16_t* att_p = (bf16_t*)c->hbuf.p;          // [n, D] gathered attention rows
-            bf16_t* x_p = att_p + (size_t)n * D;      // [n, D] gathered residual rows (hbuf holds rows x D: n x 197 of them)
-            const size_t rowb = (size_t)D * 2, pitch = (size_t)T * rowb;
-            {
-                Timed t(c, s, KC_POOL);
-                HIP_TRY(c, hipMemcpy2DAsync(att_p, rowb, (const char*)c->att.p + (size_t)pool_token * rowb, pitch, rowb, n, hipMemcpyDeviceToDevice, s));
-                HIP_TRY(c, hipMemcpy2DAsync(x_p, rowb, (const char*)c->x.p + (size_t)pool_token * rowb, pitch, rowb, n, hipMemcpyDeviceToDevice, s));
-            }
-            EncoderPass G = P;    // the same block on the gathered rows:
-            G.lnpart = nullptr;   // n rows are far below one 256-row panel,
-            G.planes = false;     // so no planes, one canonical statistics pass
-            G.zigzag = G.dir = 0; // and no reversal
-            if ((r = G.after_attention(L.w, n, att_p, x_p, false))) return r;
-            {   // back into the residual stream, where the pooling kernel reads the row
-                Timed t(c, s, KC_POOL);
-                HIP_TRY(c, hipMemcpy2DAsync((char*)c->x.p + (size_t)pool_token * rowb, pitch, x_p, rowb, rowb, n, hipMemcpyDeviceToDevice, s));
-            }
-        } else if (c->ln_mode != 0) {
-            if ((r = P.after_attention(L.w, M, c->att.p, c->x.p, !last || sig))) return r;  // SigLIP: post_layernorm, folded into the head's K | V GEMM, reads the statistics
-        } else {  // LayerNorm-kernel mode: the block's residual GEMMs around a LayerNorm launch and the unfolded fc1
-            if ((r = P.residual(c->att.p, L.w.o_w, L.w.o_b, D, M, c->x.p, false))) return r;
-            {
-                Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_layernorm(c->x.p, L.ln2_g, L.ln2_b, c->hbuf.p, M, D, c->ln_eps, s));
-            }
-            g = GemmArgs{};
-            g.A = c->hbuf.p; g.W = L.fc1_w; g.M = M; g.N = F; g.K = D;
-            g.bias = L.fc1_b; g.out = c->mlp.p; g.ldo = F;
-            g.reverse_m = P.next_dir();
-            if ((r = P.gemm(c->act == 2 ? EPI_BIAS_TGELU : c->act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, g))) return r;
-            if ((r = P.residual(c->mlp.p, L.w.fc2_w, L.w.fc2_b, F, M, c->x.p, false))) return r;
-        }
-    }
-    if (tok_out) {  // the token rows of the last block, before any tail touches the workspace (none writes x)
-        Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_token_rows(c->x.p, c->lnf_g, c->lnf_b, n, T, tok0, ntok, D, c->ln_eps, tok_out, s));
-    }
-    if (sig) {
-        // SiglipMultiheadAttentionPoolingHead: K | V = in_proj(post_layernorm(x)) over every token row, one constant query
-        // per head (map_pool), then the second half of a block with the head's weights on n rows: out_proj on a ZEROED
-        // residual (0 + out_proj(a) is out_proj(a) in bf16: the probe is no residual), y = a' + fc2(act(fc1(LN(a')))); L2
-        const LayerDev& Hd = c->head;
-        if ((r = ensure(c, c->pooled, (size_t)2 * c->chunk * D * 2))) return r;
-        bf16_t* a_p = (bf16_t*)c->pooled.p;   // [n, D] pooled attention rows
-        bf16_t* y_p = a_p + (size_t)n * D;    // [n, D] the head's residual rows
-        g = GemmArgs{};
-        g.M = M; g.N = 2 * D; g.K = D; g.out = c->qkv.p; g.ldo = 2 * D;
-        if (c->ln_mode != 0) {
-            g.A = c->x.p; g.W = Hd.w.qkv_wf; g.bias = Hd.w.qkv_bf; g.colsum = Hd.w.qkv_cs; g.ln_stats = (float*)c->stats.p;
-            g.reverse_m = P.next_dir();
-            if ((r = P.gemm(EPI_LN_BIAS, g))) return r;
-        } else {
-            {
-                Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_layernorm(c->x.p, c->lnf_g, c->lnf_b, c->hbuf.p, M, D, c->ln_eps, s));
-            }
-            g.A = c->hbuf.p; g.W = Hd.qkv_w; g.bias = Hd.qkv_b;
-            g.reverse_m = P.next_dir();
-            if ((r = P.gemm(EPI_BIAS, g))) return r;
-        }
-        {
-            Timed t(c, s, KC_POOL);
-            HIP_TRY(c, launch_map_pool(c->qkv.p, c->head_q, a_p, n, c->geom.heads, s));
-            HIP_TRY(c, hipMemsetAsync(y_p, 0, (size_t)n * D * 2, s));
-        }
-        EncoderPass G = P;    // as the pruned last layer: n rows are far below one 256-row panel,
-        G.lnpart = nullptr;   // so no planes, one canonical statistics pass
-        G.planes = false;
-        G.zigzag = G.dir = 0; // and no reversal
-        if (c->ln_mode != 0) {
-            if ((r = G.after_attention(Hd.w, n, a_p, y_p, false))) return r;
-        } else {
-            if ((r = G.residual(a_p, Hd.w.o_w, Hd.w.o_b, D, n, y_p, false))) return r;
-            {
-                Timed t(c, s, KC_LN);
-                HIP_TRY(c, launch_layernorm(y_p, Hd.ln2_g, Hd.ln2_b, c->hbuf.p, n, D, c->ln_eps, s));
-            }
-            g = GemmArgs{};
-            g.A = c->hbuf.p; g.W = Hd.fc1_w; g.M = n; g.N = F; g.K = D;
-            g.bias = Hd.fc1_b; g.out = c->mlp.p; g.ldo = F;
-            if ((r = G.gemm(EPI_BIAS_TGELU, g))) return r;
-            if ((r = G.residual(c->mlp.p, Hd.w.fc2_w, Hd.w.fc2_b, F, n, y_p, false))) return r;
-        }
-        Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_l2_rows_bf16(y_p, n, D, emb_f32, emb_bf16, s));
-        return MME_OK;
-    }
-    if (c->proj_dim) {
-        // CLIP with a projection: post_layernorm of the pooled row, rounded to bf16, times visual_projection, then L2
-        const int E = c->proj_dim;
-        if ((r = ensure(c, c->pooled, (size_t)c->chunk * D * 2))) return r;
-        if ((r = ensure(c, c->projf, (size_t)c->chunk * E * sizeof(float)))) return r;
-        {
-            Timed t(c, s, KC_POOL);
-            HIP_TRY(c, launch_pool_ln(c->x.p, c->lnf_g, c->lnf_b, n, T, pool_token, D, c->ln_eps, c->pooled.p, s));
-        }
-        g = GemmArgs{};
-        g.A = c->pooled.p; g.W = c->proj_w; g.M = n; g.N = E; g.K = D;
-        g.outf = (float*)c->projf.p; g.ldf = E;
-        if ((r = P.gemm(EPI_F32, g))) return r;
-        Timed t(c, s, KC_POOL);
-        HIP_TRY(c, launch_l2_rows((const float*)c->projf.p, n, E, emb_f32, emb_bf16, s));
-        return MME_OK;
-    }
-    {
-        Timed t(c, s, KC_POOL);
-        if (t257) HIP_TRY(c, launch_pool_t257(c->x.p, c->lnf_g, c->lnf_b, n, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
-        else HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, pool_token, D, c->ln_eps, emb_f32, emb_bf16, s));
-    }
-    return MME_OK;
-}
-
 // Mllama single-tile fit (transformers image_processing_pil_mllama.py:246-295, canvas == tile)
 void fit_to_canvas(int h, int w, int* nh, int* nw) {
     const double scale_h = (double)VIT_IMG / h, scale_w = (double)VIT_IMG / w;
@@ -413,8 +153,6 @@ struct K1Plan {
 };
 // LDS budget of classes 0 and 1
 constexpr int kHLds = 32 * 1024;
-// bf16 values of one crop's patch matrix: 196 x 768 = 49 x 3072
-constexpr size_t CROP_VALUES = (size_t)VIT_NP * VIT_PATCH_DIM;
 
 // The bands of crop i's horizontal pass: source rows [first_row, first_row + nrows) of row_bytes each, whose table takes
 // tab_lds bytes of LDS when it rides beside the band.  Picks the class and appends the bands to it.
@@ -532,6 +270,8 @@ int preprocess_chunk_clip(mme_ctx* c, const uint8_t* pix, const int64_t* offs, c
     return MME_OK;
 }
 
+}  // namespace
+
 int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches, hipStream_t s) {
     c->h_crops.resize(n);
     c->h_work.clear();
@@ -566,8 +306,6 @@ int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const 
                                         (const uint8_t*)c->htab.p, plan.kv_max, s));
     return MME_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -778,160 +516,6 @@ int mme_set_chunk(mme_ctx* c, int crops) {
     if (!c) return MME_E_ARG;
     if (crops < 1 || crops > 16384) return fail(c, MME_E_ARG, "mme_set_chunk: %d outside 1..16384", crops);
     c->chunk = crops;
-    return MME_OK;
-}
-
-int mme_preprocess(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, uint16_t* patches, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (n < 0 || (n > 0 && (!pix || !offs || !hw || !patches))) return fail(c, MME_E_ARG, "mme_preprocess: null argument or n<0");
-    if (n == 0) return MME_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    // patch 32: K1 writes its patch-16 matrix into the staging buffer of one chunk, the retile kernel permutes it into the
-    // caller's [n * 49, 3072]; the bytes per crop are the same.  Patch 14: the same into the caller's [n * 256, 640]
-    const bool t50 = c->geom.t50(), t257 = c->geom.t257();
-    int r;
-    if ((t50 || t257) && (r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    // the crop tables of successive chunks reuse one device buffer: chunk so that stays ordered
-    for (int s0 = 0; s0 < n; s0 += c->chunk) {
-        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));
-        bf16_t* dst = (bf16_t*)patches + (size_t)s0 * c->geom.crop_values();
-        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, t50 || t257 ? (bf16_t*)c->patches.p : dst, s);
-        if (r) return r;
-        if (t50) {
-            Timed t(c, s, KC_PRE);
-            HIP_TRY(c, launch_retile_p32(c->patches.p, dst, m, s));
-        } else if (t257) {
-            Timed t(c, s, KC_PRE);
-            HIP_TRY(c, launch_retile_p14(c->patches.p, dst, m, s));
-        }
-    }
-    return MME_OK;
-}
-
-int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, float* emb_f32, uint16_t* emb_bf16, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!c->loaded) return fail(c, MME_E_STATE, "mme_vit_forward: call mme_load_vit first");
-    if (n < 0 || (n > 0 && !patches)) return fail(c, MME_E_ARG, "mme_vit_forward: null patches or n<0");
-    if (pool_token < 0 || pool_token >= c->geom.tokens()) return fail(c, MME_E_ARG, "mme_vit_forward: pool_token %d outside 0..%d", pool_token, c->geom.tokens() - 1);
-    if (n == 0) return MME_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int r = ensure_workspace(c);
-    if (r) return r;
-    hipStream_t s = (hipStream_t)stream;
-    for (int s0 = 0; s0 < n; s0 += c->chunk) {
-        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * c->geom.crop_values(), m, pool_token,
-                          emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
-        if (r) return r;
-    }
-    return MME_OK;
-}
-
-int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, int pool_token, float* emb_f32,
-              uint16_t* emb_bf16, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!c->loaded) return fail(c, MME_E_STATE, "mme_embed: call mme_load_vit first");
-    if (n < 0 || (n > 0 && (!pix || !offs || !hw))) return fail(c, MME_E_ARG, "mme_embed: null argument or n<0");
-    if (pool_token < 0 || pool_token >= c->geom.tokens()) return fail(c, MME_E_ARG, "mme_embed: pool_token %d outside 0..%d", pool_token, c->geom.tokens() - 1);
-    if (n == 0) return MME_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int r = ensure_workspace(c);
-    if (r) return r;
-    if ((r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    const bool t50 = c->geom.t50();  // patch 32: K1 -> retile -> pass
-    if (t50 && (r = ensure(c, c->patches32, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    const bool t257 = c->geom.t257();  // patch 14: K1 -> retile -> pass
-    if (t257 && (r = ensure(c, c->patches14, (size_t)c->chunk * c->geom.crop_values() * 2))) return r;
-    hipStream_t s = (hipStream_t)stream;
-    for (int s0 = 0; s0 < n; s0 += c->chunk) {
-        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));  // crop tables are reused per chunk
-        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)c->patches.p, s);
-        if (r) return r;
-        if (t50) {
-            Timed t(c, s, KC_PRE);
-            HIP_TRY(c, launch_retile_p32(c->patches.p, c->patches32.p, m, s));
-        } else if (t257) {
-            Timed t(c, s, KC_PRE);
-            HIP_TRY(c, launch_retile_p14(c->patches.p, c->patches14.p, m, s));
-        }
-        r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : t257 ? c->patches14.p : c->patches.p), m, pool_token, emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s);
-        if (r) return r;
-    }
-    return MME_OK;
-}
-
-// what mme_vit_tokens / mme_embed_tokens refuse alike
-static int check_token_call(mme_ctx* c, const char* who, int pool_token, int tok0, int ntok, const void* tokens) {
-    if (!c->loaded && c->tv) return fail(c, MME_E_STATE, "%s: encoder tile_vit; supported: the single-tile image towers (vit, clip, siglip, dinov2)", who);
-    if (!c->loaded) return fail(c, MME_E_STATE, "%s: call mme_load_vit first", who);
-    const int T = c->geom.tokens();
-    if (pool_token < 0 || pool_token >= T) return fail(c, MME_E_ARG, "%s: pool_token %d outside 0..%d", who, pool_token, T - 1);
-    if (tok0 < 0 || ntok < 1 || (int64_t)tok0 + ntok > T)
-        return fail(c, MME_E_ARG, "%s: token window tok0 %d, ntok %d; supported tok0 >= 0, ntok >= 1, tok0 + ntok <= %d (the tower's tokens)", who, tok0, ntok, T);
-    if (!tokens) return fail(c, MME_E_ARG, "%s: tokens_bf16_dev is NULL", who);
-    return MME_OK;
-}
-
-int mme_vit_tokens(mme_ctx* c, const uint16_t* patches, int n, int pool_token, int tok0, int ntok, uint16_t* tokens, float* emb_f32,
-                   uint16_t* emb_bf16, void* stream) {
-    if (!c) return MME_E_ARG;
-    int r = check_token_call(c, "mme_vit_tokens", pool_token, tok0, ntok, tokens);
-    if (r) return r;
-    if (n < 0 || (n > 0 && !patches)) return fail(c, MME_E_ARG, "mme_vit_tokens: null patches or n<0");
-    if (n == 0) return MME_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((r = ensure_workspace(c))) return r;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t D = (size_t)c->geom.hidden;
-    for (int s0 = 0; s0 < n; s0 += c->chunk) {
-        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        r = forward_chunk(c, (const bf16_t*)patches + (size_t)s0 * c->geom.crop_values(), m, pool_token,
-                          emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s,
-                          (bf16_t*)tokens + (size_t)s0 * (size_t)ntok * D, tok0, ntok);
-        if (r) return r;
-    }
-    return MME_OK;
-}
-
-int mme_embed_tokens(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, int pool_token, int tok0, int ntok,
-                     uint16_t* tokens, float* emb_f32, uint16_t* emb_bf16, void* stream) {
-    if (!c) return MME_E_ARG;
-    int r = check_token_call(c, "mme_embed_tokens", pool_token, tok0, ntok, tokens);
-    if (r) return r;
-    if (n < 0 || (n > 0 && (!pix || !offs || !hw))) return fail(c, MME_E_ARG, "mme_embed_tokens: null argument or n<0");
-    if (n == 0) return MME_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((r = ensure_workspace(c))) return r;
-    if ((r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    const bool t50 = c->geom.t50(), t257 = c->geom.t257();  // K1 -> retile -> pass, as mme_embed
-    if (t50 && (r = ensure(c, c->patches32, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    if (t257 && (r = ensure(c, c->patches14, (size_t)c->chunk * c->geom.crop_values() * 2))) return r;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t D = (size_t)c->geom.hidden;
-    for (int s0 = 0; s0 < n; s0 += c->chunk) {
-        const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));  // crop tables are reused per chunk
-        r = preprocess_chunk(c, pix, offs + s0, hw + 2 * s0, m, (bf16_t*)c->patches.p, s);
-        if (r) return r;
-        if (t50) {
-            Timed t(c, s, KC_PRE);
-            HIP_TRY(c, launch_retile_p32(c->patches.p, c->patches32.p, m, s));
-        } else if (t257) {
-            Timed t(c, s, KC_PRE);
-            HIP_TRY(c, launch_retile_p14(c->patches.p, c->patches14.p, m, s));
-        }
-        r = forward_chunk(c, (const bf16_t*)(t50 ? c->patches32.p : t257 ? c->patches14.p : c->patches.p), m, pool_token,
-                          emb_f32 ? emb_f32 + (size_t)s0 * embed_dim(c) : nullptr,
-                          emb_bf16 ? (bf16_t*)emb_bf16 + (size_t)s0 * embed_dim(c) : nullptr, s,
-                          (bf16_t*)tokens + (size_t)s0 * (size_t)ntok * D, tok0, ntok);
-        if (r) return r;
-    }
     return MME_OK;
 }
 

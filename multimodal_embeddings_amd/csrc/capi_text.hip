@@ -264,7 +264,7 @@ int text_chunk(mme_ctx* c, TextDev* t, const int32_t* ids_dev, const int32_t* eo
     }
     if ((r = P.stats_from_x(t->x.p, 0, M))) return r;
     for (int l = 0; l < NL; ++l) {
-        if ((r = P.qkv_ln(t->layer[l], M))) return r;
+        if ((r = P.qkv_ln(t->layer[l], M, 3 * D))) return r;
         {
             Timed tm(c, s, KC_ATTN);
             if (t->causal) HIP_TRY(c, launch_attention_causal(t->qkv.p, t->att.p, n, t->heads, s));

@@ -255,7 +255,7 @@ int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* a
                 }
                 if ((r = P.stats_from_x(t->x.p, 0, M))) return r;
             }
-            if ((r = P.qkv_ln(t->layer[l], M))) return r;
+            if ((r = P.qkv_ln(t->layer[l], M, 3 * TD))) return r;
             {
                 Timed tm(c, s, KC_ATTN);
                 HIP_TRY(c, launch_attention_tiles(t->qkv.p, t->att.p, nt_dev, m, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2));

@@ -110,7 +110,7 @@ struct mme_ctx {
     DevBuf attn_guard;      // int[max(64, layers)]: one guard word per layer of a pass (encoder_pass.h, reset_attn_guards)
     DevBuf attn_apply;      // mme_attention_apply: its own guard word (int 0), the tile counts from int 16 on
     bool prune_last = false;  // mme_set_forward_pruning
-    int zigzag = 1;           // EncoderPass::zigzag of forward_chunk: 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
+    int zigzag = 1;           // EncoderPass::zigzag of the image towers (image_tower.hip): 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
     DevBuf patches32;      // patch 32: the retiled [chunk * 49, 3072] matrix of mme_embed (`patches` stages K1's patch-16 matrix)
@@ -160,6 +160,8 @@ inline int embed_dim(const mme_ctx* c) { return c->proj_dim ? c->proj_dim : c->g
     } while (0)
 
 int ensure(mme_ctx* c, DevBuf& b, size_t bytes);
+// K1 (capi.hip) of n <= chunk crops under the context's resize rule -> patches bf16 [n * 196, 768], the patch-16 matrix
+int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches, hipStream_t s);
 // f32 -> bf16, round to nearest even, NaN kept quiet (bf16_rne_bits of weight_prep.hip is its device form, bit for bit)
 inline uint16_t f32_to_bf16_rne(float f) {
     uint32_t u;

@@ -1,5 +1,5 @@
-// One pre-LN transformer block as every encoder of the library runs it (encoder_pass.hip): the image towers (capi.hip,
-// forward_chunk), the CLIP text tower (capi_text.hip) and the tile-ViT (capi_tilevit.hip) differ in the settings of
+// One pre-LN transformer block as every encoder of the library runs it (encoder_pass.hip): the image towers
+// (image_tower.hip), the text towers (capi_text.hip) and the tile-ViT (capi_tilevit.hip) differ in the settings of
 // EncoderPass and in the attention launch they put between the block's two halves, not in the sequence.
 #pragma once
 #include "ctx.h"
@@ -14,6 +14,10 @@ struct EncoderPass {
     // workspace: residual stream, Q | K | V, attention output, MLP hidden (bf16); (mean, rstd) per row
     void *x, *qkv, *att, *mlp;
     float* stats;
+    // Non-null selects the LayerNorm-kernel form of the two halves (ln_mode 0, image towers only): the buffer [rows, D]
+    // the normalised rows are written to.  Null: every LayerNorm is folded into the GEMM that consumes it.
+    void* hbuf = nullptr;
+    bool unfolded() const { return hbuf != nullptr; }
     // Partial (sum, sum of squares) planes [2][D/64][lnpart_rows] that the residual GEMMs are handed (null: none).
     // `planes` says whether they are USED: the GEMMs that write x then run EPI_BIAS_RES_STATS and the statistics of the
     // rows their interior tiles wrote are finished from the planes (96 bytes per row at D = 768) instead of read from x.
@@ -29,6 +33,15 @@ struct EncoderPass {
         if (zigzag == 1) dir ^= 1;
         return dir;
     }
+    // The same pass on a handful of gathered rows (a pruned last layer, SigLIP's head): far below one 256-row panel,
+    // so no planes and one canonical statistics pass, and no reversal
+    EncoderPass on_few_rows() const {
+        EncoderPass g = *this;
+        g.lnpart = nullptr;
+        g.planes = false;
+        g.zigzag = g.dir = 0;
+        return g;
+    }
 
     // one launch in one KC_GEMM scope
     int gemm(int epilogue, const GemmArgs& g);
@@ -40,14 +53,21 @@ struct EncoderPass {
     int stats_after(const GemmArgs& producer, int64_t rows);
     // out = xr + a . w^T + bias on `rows` rows (o_proj, fc2), in place on xr; `stats_next`: a folded LayerNorm reads xr next
     int residual(const void* a, const bf16_t* w, const float* bias, int K, int rows, void* xr, bool stats_next);
-    // first half: qkv = LN1(x) . qkv_w^T + b with the LayerNorm folded in (statistics of x are in `stats`)
-    int qkv_ln(const BlockW& w, int rows);
+    // first half, folded: qkv [rows, N] = LN1(x) . qkv_w^T + b (statistics of x are in `stats`); N = 3 D, or 2 D for the
+    // K | V projection of SigLIP's head
+    int qkv_ln(const BlockW& w, int rows, int N);
     // fc1 with LN2 folded in and the activation: mlp = act(LN2(xr) . fc1_w^T + b)
     int fc1_ln(const BlockW& w, int rows, const void* xr);
     // second half, after the tower's attention launch: o_proj + residual, statistics, fc1, fc2 + residual, and the
     // statistics again when `stats_next` (the next block's QKV GEMM reads them).  `a` [rows, D] is the attention output
     // and `xr` [rows, D] the residual rows: the pass's own buffers, or the gathered rows of a pruned last layer
     int after_attention(const BlockW& w, int rows, const void* a, void* xr, bool stats_next);
+    // The two halves of an image-tower layer in the form the pass runs.  Folded: qkv_ln / after_attention on L.w.
+    // Unfolded: a LayerNorm launch (gamma, beta -> hbuf) in front of EPI_BIAS into qkv; o_proj + residual, a LayerNorm
+    // launch (ln2), fc1 with its activation, fc2 + residual -- no statistics, `stats_next` is not consulted.
+    int layernorm(const void* xr, const float* gamma, const float* beta, int rows);  // xr -> hbuf, one KC_LN scope
+    int first_half(const LayerDev& L, const float* gamma, const float* beta, int rows, int N);
+    int second_half(const LayerDev& L, int rows, const void* a, void* xr, bool stats_next);
 };
 
 // one guard word per layer for the fast attention forms (attention.hip, attention_tiles.hip), zeroed per pass -- in

@@ -37,10 +37,10 @@ int EncoderPass::residual(const void* a, const bf16_t* w, const float* bias, int
     return stats_next ? stats_after(g, rows) : MME_OK;
 }
 
-int EncoderPass::qkv_ln(const BlockW& w, int rows) {
+int EncoderPass::qkv_ln(const BlockW& w, int rows, int N) {
     GemmArgs g{};
-    g.A = x; g.W = w.qkv_wf; g.M = rows; g.N = 3 * D; g.K = D;
-    g.bias = w.qkv_bf; g.colsum = w.qkv_cs; g.ln_stats = stats; g.out = qkv; g.ldo = 3 * D;
+    g.A = x; g.W = w.qkv_wf; g.M = rows; g.N = N; g.K = D;
+    g.bias = w.qkv_bf; g.colsum = w.qkv_cs; g.ln_stats = stats; g.out = qkv; g.ldo = N;
     g.reverse_m = next_dir();
     return gemm(EPI_LN_BIAS, g);
 }
@@ -58,6 +58,36 @@ int EncoderPass::after_attention(const BlockW& w, int rows, const void* a, void*
     if ((r = residual(a, w.o_w, w.o_b, D, rows, xr, true))) return r;
     if ((r = fc1_ln(w, rows, xr))) return r;
     return residual(mlp, w.fc2_w, w.fc2_b, F, rows, xr, stats_next);
+}
+
+int EncoderPass::layernorm(const void* xr, const float* gamma, const float* beta, int rows) {
+    Timed t(c, s, KC_LN);
+    HIP_TRY(c, launch_layernorm(xr, gamma, beta, hbuf, rows, D, eps, s));
+    return MME_OK;
+}
+
+int EncoderPass::first_half(const LayerDev& L, const float* gamma, const float* beta, int rows, int N) {
+    if (!unfolded()) return qkv_ln(L.w, rows, N);
+    int r;
+    if ((r = layernorm(x, gamma, beta, rows))) return r;
+    GemmArgs g{};
+    g.A = hbuf; g.W = L.qkv_w; g.M = rows; g.N = N; g.K = D;
+    g.bias = L.qkv_b; g.out = qkv; g.ldo = N;
+    g.reverse_m = next_dir();
+    return gemm(EPI_BIAS, g);
+}
+
+int EncoderPass::second_half(const LayerDev& L, int rows, const void* a, void* xr, bool stats_next) {
+    if (!unfolded()) return after_attention(L.w, rows, a, xr, stats_next);
+    int r;
+    if ((r = residual(a, L.w.o_w, L.w.o_b, D, rows, xr, false))) return r;
+    if ((r = layernorm(xr, L.ln2_g, L.ln2_b, rows))) return r;
+    GemmArgs g{};
+    g.A = hbuf; g.W = L.fc1_w; g.M = rows; g.N = F; g.K = D;
+    g.bias = L.fc1_b; g.out = mlp; g.ldo = F;
+    g.reverse_m = next_dir();
+    if ((r = gemm(act == 2 ? EPI_BIAS_TGELU : act ? EPI_BIAS_QGELU : EPI_BIAS_GELU, g))) return r;
+    return residual(mlp, L.w.fc2_w, L.w.fc2_b, F, rows, xr, false);
 }
 
 int reset_attn_guards(mme_ctx* c, int layers, hipStream_t s) {

@@ -293,7 +293,7 @@ def expected_planes(out_bits, rows_idx, what):
 
 
 def t_int_formula(M):
-    """forward_chunk's t_int: one past the last token row an interior patch tile covered"""
+    """stem's t_int (csrc/image_tower.hip): one past the last token row an interior patch tile covered"""
     interior = M // 256 * 256
     return interior - 1 + (interior - 1) // NP + 2 if interior else 0
 

@@ -47,16 +47,34 @@ def patches_of(e, n):
     return e.preprocess(torch.from_numpy(crops.reshape(-1)).to("cuda:0"), offs, hw)
 
 
-@pytest.mark.parametrize("name", ["vit_b16", "vit_b32", "clip_b16"])
+IMAGE_TOWERS = {
+    "vit_b16": (W.VIT_B16, Engine.load_vit, W.make_vit_weights), "vit_b32": (W.VIT_B32, Engine.load_vit, W.make_vit_weights),
+    "clip_b16": (W.CLIP_B16, Engine.load_clip, W.make_clip_weights), "siglip_b16": (W.SIGLIP_B16, Engine.load_siglip, W.make_siglip_weights),
+    "dinov2_b14": (W.DINOV2_B14, Engine.load_dinov2, W.make_dinov2_weights),
+}
+
+
+@pytest.mark.parametrize("name", list(IMAGE_TOWERS))
 def test_image_pass(name):
-    """3 crops at patch 16 are 591 rows, 6 at patch 32 are 300: two 256-row panels and a ragged tail, one chunk"""
-    geom = dataclasses.replace({"vit_b16": W.VIT_B16, "vit_b32": W.VIT_B32, "clip_b16": W.CLIP_B16}[name], num_layers=NL)
-    clip = name == "clip_b16"
+    """3 crops at patch 16 are 591 rows (588 without a class token), 6 at patch 32 are 300: two 256-row panels and a ragged
+    tail; 3 at patch 14 are 771: three panels and a ragged 3.  One chunk.
+
+    SigLIP, modes 0 and 1: gemm = patch embedding + 4 per block + the head's K | V, out_proj, fc1, fc2; layernorm = the
+    token rows + two per block + two for the head (mode 0: its two LayerNorm launches; mode 1: the first statistics pass
+    and the one behind out_proj, every block being followed by a folded LayerNorm); pool = map_pool with the zeroed
+    residual, then L2.  DINOv2: vit_b16's closed form (the token rows in place of the [CLS] rows).  Both closed forms
+    were read off the sequence and then confirmed by the counts of the library before the image pass was split into
+    stem, blocks and tail."""
+    base, load, make = IMAGE_TOWERS[name]
+    geom = dataclasses.replace(base, num_layers=NL)
+    clip, sig = name == "clip_b16", name == "siglip_b16"
     e = Engine(0)
     try:
-        (e.load_clip if clip else e.load_vit)((W.make_clip_weights if clip else W.make_vit_weights)(11, geom), geom=geom)
-        patches = patches_of(e, 3 if geom.patch_size == 16 else 6)
+        load(e, make(11, geom), geom=geom)
+        patches = patches_of(e, 6 if geom.patch_size == 32 else 3)
         want = {"preprocess": 0, "gemm": 1 + 4 * NL + (1 if clip else 0), "layernorm": 2 * NL + 1, "attention": NL, "pool": 2 if clip else 1}
+        if sig:
+            want = {"preprocess": 0, "gemm": 4 * NL + 5, "layernorm": 2 * NL + 3, "attention": NL, "pool": 2}
         got = {}
         for mode in (1, 2) if clip else (0, 1, 2):
             e.set_ln_fusion(mode)
@@ -72,6 +90,10 @@ def test_image_pass(name):
             pruned, out = counted(e, lambda: e.vit_forward(patches))
             assert pruned == dict(want, pool=3)
             assert torch.equal(out[0], got[1][1][0])
+            # a token pass with pruning on runs the last block unpruned: no gather, no scatter, one more pool scope (the token rows)
+            tokens, out = counted(e, lambda: e.vit_tokens(patches))
+            assert tokens == dict(want, pool=2)
+            assert torch.equal(out[1], got[1][1][0]) and torch.equal(out[2], got[1][1][1])
     finally:
         e.close()
 

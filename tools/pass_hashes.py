@@ -11,10 +11,14 @@ build is selected with MME_LIB_PATH and MME_ALLOW_LIB_OVERRIDE=1, as tools/_diag
 reach every branch of the shared block:
 
   image   ViT-S/16 width (384: no partial planes under ln_mode 2), ViT-B/16 width (768: planes), CLIP-B/16 (pre-LN,
-          QuickGELU, projection), ViT-B/32, CLIP-B/32, SigLIP-B/16 (196 tokens, tanh-GELU, pooling head).  3 crops at
-          patch 16 are 591 rows (two 256-row panels and a ragged tail of 79), 6 crops at patch 32 are 300.  From the
-          defaults one switch at a time: ln_mode, tile order, attention mode, last-layer pruning at the first and the last
-          pool token, GEMM variant, and chunks of 2 over 5 crops.
+          QuickGELU, projection), ViT-B/32, CLIP-B/32, SigLIP-B/16 (196 tokens, tanh-GELU, pooling head), DINOv2-B/14
+          (257 tokens).  3 crops at patch 16 are 591 rows (two 256-row panels and a ragged tail of 79), 6 crops at patch
+          32 are 300, 3 crops at patch 14 are 771 (three panels and a ragged 3).  From the defaults one switch at a time:
+          ln_mode, tile order, attention mode, last-layer pruning at the first and the last pool token, GEMM variant, and
+          chunks of 2 over 5 crops.  The token rows (`vit_tokens`) at the defaults, with pruning on (the token pass runs
+          the last block unpruned) and in chunks of 2 over 5 crops (three chunks, the last ragged: the token pointer's
+          offset per chunk).  The pixel path (`embed`, `embed_tokens`) in chunks of 2 over 5 crops for one tower per
+          retile form: vit_b16 (none), vit_b32, dinov2_b14.
   text    CLIP-B's text width with and without projection, 3 sequences; once more than one chunk of 1024.  The SigLIP
           text tower (64 tokens, head with bias) on 3 sequences.
   tile    1 local + 1 global layer, one intermediate state, both save-point conventions, ln_mode 1 / 2 x attention mode
@@ -88,6 +92,7 @@ def main(argv=None) -> int:
             "vit_s16": dataclasses.replace(W.VIT_S16, **two), "vit_b16": dataclasses.replace(W.VIT_B16, **two),
             "clip_b16": dataclasses.replace(W.CLIP_B16, **two), "vit_b32": dataclasses.replace(W.VIT_B32, **two),
             "clip_b32": dataclasses.replace(W.CLIP_B32, **two), "siglip_b16": dataclasses.replace(W.SIGLIP_B16, **two),
+            "dinov2_b14": dataclasses.replace(W.DINOV2_B14, **two),
         }
         # (name, setter, values): the first value is the library's default and is restored after the sweep
         switches = [("ln_mode", Engine.set_ln_fusion, (2, 0, 1)), ("tile_order", Engine.set_tile_order, (1, 0, 2)),
@@ -96,11 +101,13 @@ def main(argv=None) -> int:
             e = Engine(0)
             if isinstance(geom, W.SiglipGeometry):
                 e.load_siglip(W.make_siglip_weights(11, geom), geom=geom)
+            elif isinstance(geom, W.Dinov2Geometry):
+                e.load_dinov2(W.make_dinov2_weights(11, geom), geom=geom)
             elif isinstance(geom, W.CLIPGeometry):
                 e.load_clip(W.make_clip_weights(11, geom), geom=geom)
             else:
                 e.load_vit(W.make_vit_weights(11, geom), geom=geom)
-            n = 3 if geom.patch_size == 16 else 6
+            n = 6 if geom.patch_size == 32 else 3
             patches = e.preprocess(*pack(list(W.synthetic_crops(n, seed=5))))
             emit(f"{name} defaults", *e.vit_forward(patches))
             for sw, setter, values in switches:
@@ -111,9 +118,17 @@ def main(argv=None) -> int:
             e.set_forward_pruning(True)
             for tok in (0, geom.seq_len - 1):
                 emit(f"{name} pruned pool_token={tok}", *e.vit_forward(patches, pool_token=tok))
+            emit(f"{name} tokens pruned", *e.vit_tokens(patches))
             e.set_forward_pruning(False)
+            emit(f"{name} tokens defaults", *e.vit_tokens(patches))
             e.set_chunk(2)
-            emit(f"{name} chunk=2 n=5", *e.vit_forward(e.preprocess(*pack(list(W.synthetic_crops(5, seed=6))))))
+            five = pack(list(W.synthetic_crops(5, seed=6)))
+            patches = e.preprocess(*five)
+            emit(f"{name} chunk=2 n=5", *e.vit_forward(patches))
+            emit(f"{name} tokens chunk=2 n=5", *e.vit_tokens(patches))
+            if name in ("vit_b16", "vit_b32", "dinov2_b14"):  # the pixel path, one tower per retile form
+                emit(f"{name} embed chunk=2 n=5", *e.embed(*five))
+                emit(f"{name} embed_tokens chunk=2 n=5", *e.embed_tokens(*five))
             e.close()
 
     def text():
