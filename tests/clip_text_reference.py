@@ -14,7 +14,8 @@ models/clip/modeling_clip.py.  What each step restates:
     CLIPTextModelWithProjection text_embeds = text_projection(pooled_output)  (Linear, bias=False)
 
 `tests/golden/make_clip_text_golden.py` records what the two transformers classes return on seeded weights and ids
-(tests/golden/clip_text_cases.npz); tests/test_clip_text_cpu.py holds this restatement to those rows.  `causal_attention_f64`
+(tests/golden/clip_text_cases.npz); tests/test_clip_text_cpu.py holds this restatement to those rows.  `mutant=` switches on one of the
+wrong towers of tests/tower_mutants.py; with None the arithmetic is the restatement's.  `causal_attention_f64`
 is the float64 attention the kernel test and the mutant test share, with the tolerance's scale A = sum p |v| / sum p.
 """
 from __future__ import annotations
@@ -22,8 +23,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from clip_reference import ACT, _t, layer_norm, one_minus_cos  # noqa: F401  (re-exported)
-from multimodal_embeddings_amd.weights import CLIP_TEXT_B, CLIPTextGeometry
+from clip_reference import ACT, _t, block, block_getter, has, layer_norm, one_minus_cos, position_rows, stored  # noqa: F401  (re-exported)
+from multimodal_embeddings_amd.weights import CLIP_BLOCK, CLIP_TEXT_B, CLIPTextGeometry
 
 T = 77
 
@@ -38,50 +39,52 @@ def eos_positions(ids: np.ndarray, eos_token_id: int) -> np.ndarray:
 
 
 @torch.no_grad()
-def clip_text_hidden_states(ids, w: dict, geom: CLIPTextGeometry = CLIP_TEXT_B, dtype=torch.float64) -> torch.Tensor:
-    """ids [n, 77] -> the encoder's output [n, 77, D] (before final_layer_norm), arithmetic in `dtype`"""
+def clip_text_hidden_states(ids, w: dict, geom: CLIPTextGeometry = CLIP_TEXT_B, dtype=torch.float64, mutant=None) -> torch.Tensor:
+    """ids [n, 77] -> the encoder's output [n, 77, D] (before final_layer_norm), arithmetic in `dtype`.
+    `mutant`: the switches of clip_reference.py, and "no_causal_mask"."""
     ids = torch.as_tensor(np.asarray(ids, dtype=np.int64))
-    n = ids.shape[0]
     D, H = geom.hidden_size, geom.num_heads
     dh = D // H
     t = "text_model."
-    x = _t(w, t + "embeddings.token_embedding.weight", dtype)[ids] + _t(w, t + "embeddings.position_embedding.weight", dtype).reshape(1, T, D)
-    mask = torch.full((T, T), float("-inf"), dtype=dtype).triu(1)
+    x = _t(w, t + "embeddings.token_embedding.weight", dtype)[ids] + position_rows(_t(w, t + "embeddings.position_embedding.weight", dtype), mutant).reshape(1, T, D)
+    x = stored(x, mutant)
+    mask = None if has(mutant, "no_causal_mask") else torch.full((T, T), float("-inf"), dtype=dtype).triu(1)
     act = ACT[geom.hidden_act]
+    if has(mutant, "other_gelu"):
+        act = ACT["gelu" if geom.hidden_act == "quick_gelu" else "quick_gelu"]
     for i in range(geom.num_layers):
-        p = f"{t}encoder.layers.{i}."
-        lin = lambda v, name: v @ _t(w, p + name + ".weight", dtype).T + _t(w, p + name + ".bias", dtype)  # noqa: E731
-        h = layer_norm(x, _t(w, p + "layer_norm1.weight", dtype), _t(w, p + "layer_norm1.bias", dtype), geom.layer_norm_eps)
-        q, k, val = (lin(h, f"self_attn.{m}_proj").view(n, T, H, dh).transpose(1, 2) for m in "qkv")
-        s = torch.softmax((q @ k.transpose(2, 3)) * (dh ** -0.5) + mask, dim=-1)
-        x = x + lin((s @ val).transpose(1, 2).reshape(n, T, D), "self_attn.out_proj")
-        h = layer_norm(x, _t(w, p + "layer_norm2.weight", dtype), _t(w, p + "layer_norm2.bias", dtype), geom.layer_norm_eps)
-        x = x + lin(act(lin(h, "mlp.fc1")), "mlp.fc2")
+        x = block(x, block_getter(w, f"{t}encoder.layers.{i}.", CLIP_BLOCK, dtype), H, dh, geom.layer_norm_eps, act, mutant, mask)
     return x
 
 
 @torch.no_grad()
-def clip_text_forward(ids, w: dict, geom: CLIPTextGeometry = CLIP_TEXT_B, dtype=torch.float64, batch: int = 16):
+def clip_text_forward(ids, w: dict, geom: CLIPTextGeometry = CLIP_TEXT_B, dtype=torch.float64, batch: int = 16, mutant=None):
     """-> (pooler_output [n, D], text_embeds [n, P] or None without a projection), numpy in `dtype`, not normalised: what
-    CLIPTextModel / CLIPTextModelWithProjection return."""
+    CLIPTextModel / CLIPTextModelWithProjection return.  Mutants of this step: "pooled_last" (position 76),
+    "pooled_before_eos", "no_final_ln"."""
     ids = np.asarray(ids)
     pos = eos_positions(ids, geom.eos_token_id)
     assert (pos >= 0).all(), "a sequence holds no eos_token_id"
+    if has(mutant, "pooled_last"):
+        pos = np.full_like(pos, T - 1)
+    if has(mutant, "pooled_before_eos"):
+        pos = np.maximum(pos - 1, 0)
     t = "text_model."
     pooled, proj = [], []
     for s in range(0, ids.shape[0], batch):
-        hs = clip_text_hidden_states(ids[s : s + batch], w, geom, dtype)
+        hs = clip_text_hidden_states(ids[s : s + batch], w, geom, dtype, mutant)
         rows = hs[torch.arange(hs.shape[0]), torch.as_tensor(pos[s : s + batch])]
-        po = layer_norm(rows, _t(w, t + "final_layer_norm.weight", dtype), _t(w, t + "final_layer_norm.bias", dtype), geom.layer_norm_eps)
+        po = rows if has(mutant, "no_final_ln") else layer_norm(rows, _t(w, t + "final_layer_norm.weight", dtype),
+                                                                _t(w, t + "final_layer_norm.bias", dtype), geom.layer_norm_eps)
         pooled.append(po)
         if geom.projection_dim:
             proj.append(po @ _t(w, "text_projection.weight", dtype).T)
     return torch.cat(pooled).numpy(), (torch.cat(proj).numpy() if proj else None)
 
 
-def clip_text_embed(ids, w: dict, geom: CLIPTextGeometry = CLIP_TEXT_B, dtype=torch.float64) -> np.ndarray:
+def clip_text_embed(ids, w: dict, geom: CLIPTextGeometry = CLIP_TEXT_B, dtype=torch.float64, mutant=None) -> np.ndarray:
     """The engine's contract: text_embeds (pooler_output without a projection), x / max(||x||, 1e-12)"""
-    pooled, proj = clip_text_forward(ids, w, geom, dtype)
+    pooled, proj = clip_text_forward(ids, w, geom, dtype, mutant=mutant)
     e = proj if proj is not None else pooled
     return e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), 1e-12)
 

@@ -12,14 +12,17 @@
 
 `tests/golden/make_dinov2_golden.py` records what `Dinov2Model` itself returns on seeded weights and inputs
 (tests/golden/dinov2_cases.npz); tests/test_dinov2_cpu.py holds this restatement to those rows.  The GPU tests compare the
-engine with this restatement.  `mutate=` names the two wrong models the sharpness tests ask for.
+engine with this restatement.  `mutate=` names the two wrong models tests/test_gpu_dinov2.py asks for; `mutant=` switches on one
+of the wrong towers of tests/tower_mutants.py (clip_reference.py holds the shared pieces); with neither the arithmetic is the restatement's.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from multimodal_embeddings_amd.weights import DINOV2_B14, Dinov2Geometry
+from clip_reference import block, block_getter, final_rows, has, neighbour, patch_rows, position_rows, stored
+from multimodal_embeddings_amd.weights import DINOV2_B14, DINOV2_BLOCK, Dinov2Geometry
+from siglip_reference import gelu_tanh
 
 POS = "embeddings.position_embeddings"
 
@@ -57,47 +60,73 @@ def position_table(w: dict, dtype=torch.float32) -> torch.Tensor:
 
 
 @torch.no_grad()
-def dinov2_hidden_states(pixel_values, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float32, mutate: str | None = None) -> torch.Tensor:
+def dinov2_hidden_states(pixel_values, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float32, mutate: str | None = None,
+                         mutant=None) -> torch.Tensor:
     """pixel_values [n, 3, 224, 224] -> the encoder's output [n, 257, D] (before the final layernorm), arithmetic in `dtype`.
-    mutate: "swap_pos" exchanges the position rows 1 and 2, "no_layer_scale2" leaves layer_scale2 out of every block."""
+    mutate: "swap_pos" exchanges the position rows 1 and 2, "no_layer_scale2" leaves layer_scale2 out of every block.
+    mutant: the switches of clip_reference.py, and of this tower "no_layer_scale" (both scales left out), "ls_exchanged"
+    (lambda2 behind the attention, lambda1 behind the MLP), "cls_pos_from_grid" (the class token gets the first row of the
+    interpolated patch grid instead of the table's class row), "other_gelu" (tanh-GELU)."""
     x = torch.as_tensor(np.asarray(pixel_values)).to(dtype)
     n = x.shape[0]
     D, H, dh = geom.hidden_size, geom.num_heads, geom.head_dim
-    x = patchify(x, geom.patch_size) @ _t(w, "embeddings.patch_embeddings.projection.weight", dtype).reshape(D, -1).T
+    x = patch_rows(x, geom.patch_size, mutant) @ _t(w, "embeddings.patch_embeddings.projection.weight", dtype).reshape(D, -1).T
     x = x + _t(w, "embeddings.patch_embeddings.projection.bias", dtype)
     x = torch.cat((_t(w, "embeddings.cls_token", dtype).reshape(1, 1, D).expand(n, 1, D), x), dim=1)
     pos = position_table(w, dtype)
     if mutate == "swap_pos":
         pos = pos.clone()
         pos[[1, 2]] = pos[[2, 1]]
-    x = x + pos.reshape(1, 257, D)
+    if has(mutant, "cls_pos_from_grid"):
+        pos = pos.clone()
+        pos[0] = pos[1]
+    x = stored(x + position_rows(pos, mutant).reshape(1, 257, D), mutant)
+    act = gelu_tanh if has(mutant, "other_gelu") else gelu
     for i in range(geom.num_layers):
         p = f"encoder.layer.{i}."
-        lin = lambda t, name: t @ _t(w, p + name + ".weight", dtype).T + _t(w, p + name + ".bias", dtype)  # noqa: E731
-        h = layer_norm(x, _t(w, p + "norm1.weight", dtype), _t(w, p + "norm1.bias", dtype), geom.layer_norm_eps)
-        q, k, val = (lin(h, f"attention.attention.{m}").view(n, -1, H, dh).transpose(1, 2) for m in ("query", "key", "value"))
-        s = torch.softmax((q @ k.transpose(2, 3)) * (dh ** -0.5), dim=-1)
-        x = x + lin((s @ val).transpose(1, 2).reshape(n, -1, D), "attention.output.dense") * _t(w, p + "layer_scale1.lambda1", dtype)
-        h = layer_norm(x, _t(w, p + "norm2.weight", dtype), _t(w, p + "norm2.bias", dtype), geom.layer_norm_eps)
-        m = lin(gelu(lin(h, "mlp.fc1")), "mlp.fc2")
-        x = x + (m if mutate == "no_layer_scale2" else m * _t(w, p + "layer_scale2.lambda1", dtype))
+        s1, s2 = _t(w, p + "layer_scale1.lambda1", dtype), _t(w, p + "layer_scale2.lambda1", dtype)
+        if has(mutant, "ls_exchanged"):
+            s1, s2 = s2, s1
+        if has(mutant, "no_layer_scale"):
+            s1 = s2 = None
+        if mutate == "no_layer_scale2":
+            s2 = None
+        x = block(x, block_getter(w, p, DINOV2_BLOCK, dtype), H, dh, geom.layer_norm_eps, act, mutant, scale1=s1, scale2=s2)
     return x
+
+
+def _final_ln(w, dtype):
+    return _t(w, "layernorm.weight", dtype), _t(w, "layernorm.bias", dtype)
+
+
+@torch.no_grad()
+def dinov2_pool(hs, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float32, token: int = 0, mutant=None) -> torch.Tensor:
+    """The encoder's output [n, 257, D] -> layernorm(row `token`) [n, D]"""
+    if has(mutant, "neighbour_pooled"):
+        token = neighbour(token, 257)
+    return hs[:, token] if has(mutant, "no_final_ln") else layer_norm(hs[:, token], *_final_ln(w, dtype), geom.layer_norm_eps)
 
 
 @torch.no_grad()
 def dinov2_forward(pixel_values, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float32, batch: int = 8, token: int = 0,
-                   mutate: str | None = None) -> np.ndarray:
-    """-> layernorm(row `token`) [n, D], numpy in `dtype`, not normalised: token 0 is what Dinov2Model returns as pooler_output"""
+                   mutate: str | None = None, mutant=None) -> np.ndarray:
+    """-> layernorm(row `token`) [n, D], numpy in `dtype`, not normalised: token 0 is what Dinov2Model returns as pooler_output.
+    Mutants of this step: "neighbour_pooled", "no_final_ln"."""
     pv = np.asarray(pixel_values)
-    g, b = _t(w, "layernorm.weight", dtype), _t(w, "layernorm.bias", dtype)
-    out = [layer_norm(dinov2_hidden_states(pv[s : s + batch], w, geom, dtype, mutate)[:, token], g, b, geom.layer_norm_eps)
+    out = [dinov2_pool(dinov2_hidden_states(pv[s : s + batch], w, geom, dtype, mutate, mutant), w, geom, dtype, token, mutant)
            for s in range(0, pv.shape[0], batch)]
     return torch.cat(out).numpy()
 
 
-def dinov2_embed(pixel_values, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float32, token: int = 0) -> np.ndarray:
+@torch.no_grad()
+def dinov2_token_rows(pixel_values, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float64, mutant=None) -> np.ndarray:
+    """-> [n, 257, D]: every token row behind the final layernorm, L2-normalised: what Engine.vit_tokens returns"""
+    return final_rows(dinov2_hidden_states(pixel_values, w, geom, dtype, None, mutant), *_final_ln(w, dtype), geom.layer_norm_eps, mutant).numpy()
+
+
+def dinov2_embed(pixel_values, w: dict, geom: Dinov2Geometry = DINOV2_B14, dtype=torch.float32, token: int = 0, mutant=None) -> np.ndarray:
     """The engine's contract: the pooled row, x / max(||x||, 1e-12)"""
-    e = dinov2_forward(pixel_values, w, geom, dtype, token=token)
+    e = dinov2_forward(pixel_values, w, geom, dtype, token=token, mutant=mutant)
     return e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), 1e-12)
 
 

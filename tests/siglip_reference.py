@@ -11,7 +11,8 @@
 
 `tests/golden/make_siglip_golden.py` records what `SiglipVisionModel` itself returns on seeded weights and inputs
 (tests/golden/siglip_cases.npz); tests/test_siglip_cpu.py holds this restatement to those rows.  The GPU tests compare the
-engine with this restatement.  `gelu_tanh_sigmoid` is the form the GEMM epilogue evaluates (csrc/gemm_epilogue.h).
+engine with this restatement.  `gelu_tanh_sigmoid` is the form the GEMM epilogue evaluates (csrc/gemm_epilogue.h).  `mutant=` switches
+on one of the wrong towers of tests/tower_mutants.py (clip_reference.py holds the shared pieces); with None the arithmetic is the restatement's.
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ import math
 import numpy as np
 import torch
 
-from multimodal_embeddings_amd.weights import SIGLIP_B16, SiglipGeometry
+from clip_reference import block, block_getter, final_rows, gelu_erf, has, patch_rows, position_rows, stored
+from multimodal_embeddings_amd.weights import CLIP_BLOCK, SIGLIP_B16, SiglipGeometry
 
 V = "vision_model."
 C0 = 2.0 * math.sqrt(2.0 / math.pi)
@@ -54,56 +56,64 @@ def patchify(pixel_values: torch.Tensor, patch: int = 16) -> torch.Tensor:
 
 
 @torch.no_grad()
-def siglip_hidden_states(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32) -> torch.Tensor:
-    """pixel_values [n, 3, 224, 224] -> the encoder's output [n, 196, D] (before post_layernorm), arithmetic in `dtype`"""
+def siglip_hidden_states(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32, mutant=None) -> torch.Tensor:
+    """pixel_values [n, 3, 224, 224] -> the encoder's output [n, 196, D] (before post_layernorm), arithmetic in `dtype`.
+    `mutant`: the switches of clip_reference.py ("other_gelu": erf-GELU)."""
     x = torch.as_tensor(np.asarray(pixel_values)).to(dtype)
-    n = x.shape[0]
     D, H, dh = geom.hidden_size, geom.num_heads, geom.head_dim
-    x = patchify(x, geom.patch_size) @ _t(w, V + "embeddings.patch_embedding.weight", dtype).reshape(D, -1).T + _t(w, V + "embeddings.patch_embedding.bias", dtype)
-    x = x + _t(w, V + "embeddings.position_embedding.weight", dtype).reshape(1, geom.seq_len, D)
+    x = patch_rows(x, geom.patch_size, mutant) @ _t(w, V + "embeddings.patch_embedding.weight", dtype).reshape(D, -1).T + _t(w, V + "embeddings.patch_embedding.bias", dtype)
+    x = stored(x + position_rows(_t(w, V + "embeddings.position_embedding.weight", dtype), mutant).reshape(1, geom.seq_len, D), mutant)
+    act = gelu_erf if has(mutant, "other_gelu") else gelu_tanh
     for i in range(geom.num_layers):
-        p = f"{V}encoder.layers.{i}."
-        lin = lambda t, name: t @ _t(w, p + name + ".weight", dtype).T + _t(w, p + name + ".bias", dtype)  # noqa: E731
-        h = layer_norm(x, _t(w, p + "layer_norm1.weight", dtype), _t(w, p + "layer_norm1.bias", dtype), geom.layer_norm_eps)
-        q, k, val = (lin(h, f"self_attn.{m}_proj").view(n, -1, H, dh).transpose(1, 2) for m in "qkv")
-        s = torch.softmax((q @ k.transpose(2, 3)) * (dh ** -0.5), dim=-1)
-        x = x + lin((s @ val).transpose(1, 2).reshape(n, -1, D), "self_attn.out_proj")
-        h = layer_norm(x, _t(w, p + "layer_norm2.weight", dtype), _t(w, p + "layer_norm2.bias", dtype), geom.layer_norm_eps)
-        x = x + lin(gelu_tanh(lin(h, "mlp.fc1")), "mlp.fc2")
+        x = block(x, block_getter(w, f"{V}encoder.layers.{i}.", CLIP_BLOCK, dtype), H, dh, geom.layer_norm_eps, act, mutant)
     return x
 
 
+def _post_ln(w, dtype):
+    return _t(w, V + "post_layernorm.weight", dtype), _t(w, V + "post_layernorm.bias", dtype)
+
+
 @torch.no_grad()
-def siglip_head(hs: torch.Tensor, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32) -> torch.Tensor:
-    """The encoder's output [n, 196, D] -> pooler_output [n, D]: post_layernorm, then the attention-pooling head"""
+def siglip_head(hs: torch.Tensor, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32, mutant=None) -> torch.Tensor:
+    """The encoder's output [n, 196, D] -> pooler_output [n, D]: post_layernorm, then the attention-pooling head.
+    Mutants of this step: "no_final_ln" / "kv_without_post_ln" (K | V read the encoder's output), "probe_unscaled" (no dh^-0.5),
+    "mean_pooled_head" (uniform scores), "no_head_mlp_residual", and "other_gelu"."""
     n = hs.shape[0]
     D, H, dh = geom.hidden_size, geom.num_heads, geom.head_dim
-    h = layer_norm(hs, _t(w, V + "post_layernorm.weight", dtype), _t(w, V + "post_layernorm.bias", dtype), geom.layer_norm_eps)
+    h = hs if has(mutant, "no_final_ln") or has(mutant, "kv_without_post_ln") else layer_norm(hs, *_post_ln(w, dtype), geom.layer_norm_eps)
     p = V + "head."
     wi, bi = _t(w, p + "attention.in_proj_weight", dtype), _t(w, p + "attention.in_proj_bias", dtype)
     probe = _t(w, p + "probe", dtype).reshape(1, D)
     q = (probe @ wi[:D].T + bi[:D]).view(1, 1, H, dh).transpose(1, 2)                 # [1, H, 1, dh], the same for every crop
     k = (h @ wi[D : 2 * D].T + bi[D : 2 * D]).view(n, -1, H, dh).transpose(1, 2)      # [n, H, 196, dh]
     val = (h @ wi[2 * D :].T + bi[2 * D :]).view(n, -1, H, dh).transpose(1, 2)
-    s = torch.softmax((q @ k.transpose(2, 3)) * (dh ** -0.5), dim=-1)                  # [n, H, 1, 196]
+    s = (q @ k.transpose(2, 3)) * (1.0 if has(mutant, "probe_unscaled") else dh ** -0.5)
+    s = torch.softmax(torch.zeros_like(s) if has(mutant, "mean_pooled_head") else s, dim=-1)  # [n, H, 1, 196]
     a = (s @ val).transpose(1, 2).reshape(n, D)
     a = a @ _t(w, p + "attention.out_proj.weight", dtype).T + _t(w, p + "attention.out_proj.bias", dtype)
     m = layer_norm(a, _t(w, p + "layernorm.weight", dtype), _t(w, p + "layernorm.bias", dtype), geom.layer_norm_eps)
-    m = gelu_tanh(m @ _t(w, p + "mlp.fc1.weight", dtype).T + _t(w, p + "mlp.fc1.bias", dtype))
-    return a + (m @ _t(w, p + "mlp.fc2.weight", dtype).T + _t(w, p + "mlp.fc2.bias", dtype))
+    m = (gelu_erf if has(mutant, "other_gelu") else gelu_tanh)(m @ _t(w, p + "mlp.fc1.weight", dtype).T + _t(w, p + "mlp.fc1.bias", dtype))
+    m = m @ _t(w, p + "mlp.fc2.weight", dtype).T + _t(w, p + "mlp.fc2.bias", dtype)
+    return m if has(mutant, "no_head_mlp_residual") else a + m
 
 
 @torch.no_grad()
-def siglip_forward(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32, batch: int = 8) -> np.ndarray:
+def siglip_forward(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32, batch: int = 8, mutant=None) -> np.ndarray:
     """-> pooler_output [n, D], numpy in `dtype`, not normalised: what SiglipVisionModel returns"""
     pv = np.asarray(pixel_values)
-    out = [siglip_head(siglip_hidden_states(pv[s : s + batch], w, geom, dtype), w, geom, dtype) for s in range(0, pv.shape[0], batch)]
+    out = [siglip_head(siglip_hidden_states(pv[s : s + batch], w, geom, dtype, mutant), w, geom, dtype, mutant) for s in range(0, pv.shape[0], batch)]
     return torch.cat(out).numpy()
 
 
-def siglip_embed(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32) -> np.ndarray:
+@torch.no_grad()
+def siglip_token_rows(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float64, mutant=None) -> np.ndarray:
+    """-> [n, 196, D]: every token row behind post_layernorm, L2-normalised: what Engine.vit_tokens returns"""
+    return final_rows(siglip_hidden_states(pixel_values, w, geom, dtype, mutant), *_post_ln(w, dtype), geom.layer_norm_eps, mutant).numpy()
+
+
+def siglip_embed(pixel_values, w: dict, geom: SiglipGeometry = SIGLIP_B16, dtype=torch.float32, mutant=None) -> np.ndarray:
     """The engine's contract: pooler_output, x / max(||x||, 1e-12)"""
-    e = siglip_forward(pixel_values, w, geom, dtype)
+    e = siglip_forward(pixel_values, w, geom, dtype, mutant=mutant)
     return e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), 1e-12)
 
 

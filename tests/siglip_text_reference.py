@@ -13,7 +13,7 @@ models/siglip/modeling_siglip.py.  What each step restates:
 
 `tests/golden/make_siglip_text_golden.py` records what SiglipTextModel / SiglipModel return on seeded weights and ids
 (tests/golden/siglip_text_cases.npz); tests/test_siglip_text_cpu.py holds this restatement to those rows.  The keyword switches
-of `siglip_text_forward` (`pool_pos`, `causal`, `head_bias`) exist for the mutant tests.  `attention_f64` is the float64 attention
+of `siglip_text_forward` (`pool_pos`, `causal`, `head_bias`) exist for the mutant tests, as does `mutant=` (tests/tower_mutants.py).  `attention_f64` is the float64 attention
 the kernel test uses, with the tolerance's scale A = sum p |v| / sum p.
 """
 from __future__ import annotations
@@ -21,8 +21,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from clip_reference import _t, layer_norm, one_minus_cos  # noqa: F401  (re-exported)
-from multimodal_embeddings_amd.weights import SIGLIP_TEXT_B, SiglipTextGeometry
+from clip_reference import _t, block, block_getter, gelu_erf, has, layer_norm, one_minus_cos, position_rows, stored  # noqa: F401  (re-exported)
+from multimodal_embeddings_amd.weights import CLIP_BLOCK, SIGLIP_TEXT_B, SiglipTextGeometry
 
 T = 64
 
@@ -32,37 +32,41 @@ def gelu_tanh(x):
 
 
 @torch.no_grad()
-def siglip_text_hidden_states(ids, w: dict, geom: SiglipTextGeometry = SIGLIP_TEXT_B, dtype=torch.float64, causal: bool = False) -> torch.Tensor:
-    """ids [n, 64] -> the encoder's output [n, 64, D] (before final_layer_norm), arithmetic in `dtype`; `causal`: the mutant"""
+def siglip_text_hidden_states(ids, w: dict, geom: SiglipTextGeometry = SIGLIP_TEXT_B, dtype=torch.float64, causal: bool = False,
+                              mutant=None) -> torch.Tensor:
+    """ids [n, 64] -> the encoder's output [n, 64, D] (before final_layer_norm), arithmetic in `dtype`; `causal`: the mutant.
+    `mutant`: the switches of clip_reference.py, "padding_masked" (no key at a pad_token_id position is attended) and
+    "other_gelu" (erf-GELU)."""
     ids = torch.as_tensor(np.asarray(ids, dtype=np.int64))
-    n = ids.shape[0]
     D, H = geom.hidden_size, geom.num_heads
     dh = D // H
     t = "text_model."
-    x = _t(w, t + "embeddings.token_embedding.weight", dtype)[ids] + _t(w, t + "embeddings.position_embedding.weight", dtype).reshape(1, T, D)
+    x = _t(w, t + "embeddings.token_embedding.weight", dtype)[ids] + position_rows(_t(w, t + "embeddings.position_embedding.weight", dtype), mutant).reshape(1, T, D)
+    x = stored(x, mutant)
     mask = torch.full((T, T), float("-inf"), dtype=dtype).triu(1) if causal else torch.zeros((T, T), dtype=dtype)
+    if has(mutant, "padding_masked"):
+        mask = mask + torch.where(ids == geom.pad_token_id, float("-inf"), 0.0).to(dtype).reshape(-1, 1, 1, T)
+    act = gelu_erf if has(mutant, "other_gelu") else gelu_tanh
     for i in range(geom.num_layers):
-        p = f"{t}encoder.layers.{i}."
-        lin = lambda v, name: v @ _t(w, p + name + ".weight", dtype).T + _t(w, p + name + ".bias", dtype)  # noqa: E731
-        h = layer_norm(x, _t(w, p + "layer_norm1.weight", dtype), _t(w, p + "layer_norm1.bias", dtype), geom.layer_norm_eps)
-        q, k, val = (lin(h, f"self_attn.{m}_proj").view(n, T, H, dh).transpose(1, 2) for m in "qkv")
-        s = torch.softmax((q @ k.transpose(2, 3)) * (dh ** -0.5) + mask, dim=-1)
-        x = x + lin((s @ val).transpose(1, 2).reshape(n, T, D), "self_attn.out_proj")
-        h = layer_norm(x, _t(w, p + "layer_norm2.weight", dtype), _t(w, p + "layer_norm2.bias", dtype), geom.layer_norm_eps)
-        x = x + lin(gelu_tanh(lin(h, "mlp.fc1")), "mlp.fc2")
+        x = block(x, block_getter(w, f"{t}encoder.layers.{i}.", CLIP_BLOCK, dtype), H, dh, geom.layer_norm_eps, act, mutant, mask)
     return x
 
 
 @torch.no_grad()
 def siglip_text_forward(ids, w: dict, geom: SiglipTextGeometry = SIGLIP_TEXT_B, dtype=torch.float64, batch: int = 16, *, pool_pos: int = T - 1,
-                        causal: bool = False, head_bias: bool = True) -> np.ndarray:
-    """-> pooler_output [n, P], numpy in `dtype`, not normalised: what SiglipTextModel returns.  The keywords are the mutants."""
+                        causal: bool = False, head_bias: bool = True, mutant=None) -> np.ndarray:
+    """-> pooler_output [n, P], numpy in `dtype`, not normalised: what SiglipTextModel returns.  The keywords are the mutants;
+    `mutant` names them too: "pooled_62", "no_head_bias", "no_final_ln"."""
     ids = np.asarray(ids)
     t = "text_model."
+    if has(mutant, "pooled_62"):
+        pool_pos = T - 2
+    head_bias = head_bias and not has(mutant, "no_head_bias")
     out = []
     for s in range(0, ids.shape[0], batch):
-        hs = siglip_text_hidden_states(ids[s : s + batch], w, geom, dtype, causal)
-        po = layer_norm(hs[:, pool_pos], _t(w, t + "final_layer_norm.weight", dtype), _t(w, t + "final_layer_norm.bias", dtype), geom.layer_norm_eps)
+        hs = siglip_text_hidden_states(ids[s : s + batch], w, geom, dtype, causal, mutant)
+        po = hs[:, pool_pos] if has(mutant, "no_final_ln") else layer_norm(hs[:, pool_pos], _t(w, t + "final_layer_norm.weight", dtype),
+                                                                          _t(w, t + "final_layer_norm.bias", dtype), geom.layer_norm_eps)
         y = po @ _t(w, t + "head.weight", dtype).T
         out.append(y + _t(w, t + "head.bias", dtype) if head_bias else y)
     return torch.cat(out).numpy()

@@ -24,6 +24,8 @@ transformers itself returned (tests/golden/clip_cases.npz); bit identities; relo
     rounding ulp_bf16(ref)/2 is added.
 (5) max(1 - cos) <= 1e-3 against the float32 restatement: the project's bound for the bf16 path against an f32 restatement
     (tests/test_gpu_vit_family.py).  Measured values: DESIGN.md 4.7.
+    What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, the other activation):
+    tests/test_gpu_tower_sharpness.py.
 """
 import dataclasses
 import json

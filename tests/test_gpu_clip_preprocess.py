@@ -6,6 +6,8 @@ of tests/clip_preprocess_reference.py (itself pinned to Pillow and transformers 
 (2) the rule as state of a context; (3) mme_embed == mme_preprocess -> mme_vit_forward; (4) RegionEmbedder end to end against
 the f32 restatement of the tower fed the restated pixels, max(1 - cos) <= 1e-3 (the project's bound for this tower), and the
 rule is live: the default rule's vectors differ by more than that; (5) refusals.
+What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, the other activation):
+tests/test_gpu_tower_sharpness.py.
 """
 import dataclasses
 import json

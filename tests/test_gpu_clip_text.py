@@ -13,6 +13,8 @@ Tolerances, none fitted:
 (4) prepared buffers: the definitions and bounds of tests/test_gpu_weight_prep.py.
 (5) parity: max(1 - cos) <= 1e-3 against the recorded transformers rows, the project's bound for the CLIP image tower.
     Measured on one MI355X: B 4.4e-5, L2 2.0e-5, H2 2.0e-5, B2n 1.4e-5, V1 1.3e-5.
+    What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, the other activation):
+    tests/test_gpu_tower_sharpness.py.
 A GPU fault in one test ends the module's GPU work: the tests after it fail without launching anything.
 """
 import ctypes as C

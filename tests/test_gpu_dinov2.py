@@ -8,7 +8,8 @@
     plausible kernel bug written as a change of the reference's scores) must leave 4 x the tolerance on the planted rows;
 (3) the prepared buffers: device and host preparer equal, LayerScale folded as the float64 product rounded once;
 (4) the whole path against the f32 restatement of tests/dinov2_reference.py and against what transformers' Dinov2Model
-    returned (tests/golden/dinov2_cases.npz), max(1 - cos) <= 1e-3, the project's bound for the bf16 path;
+    returned (tests/golden/dinov2_cases.npz), max(1 - cos) <= 1e-3, the project's bound for the bf16 path (what that bound cannot see
+    on std 0.02 weights -- uniform attention, Q and K exchanged, a dropped key -- is held by tests/test_gpu_tower_sharpness.py);
 (5) bit identities: ln_mode 1 = 2, every GEMM variant, pruned = unpruned, chunking, tile order, embed = preprocess + forward,
     checkpoint directory = weight dict.  ln_mode 0 (the LayerNorm kernel in front of unfolded weights) rounds at other
     points than the folded modes by construction, as for every other tower; it is held to the restatement;

@@ -15,6 +15,8 @@ against the float32 restatement of tests/siglip_reference.py and the rows transf
     (2^-9 |ref|), the f32 scores, exponentials and sums over 196 terms are orders below; the bound of (1) covers it with room.
 (5) l2_rows_bf16 against float64 with the rule of the pool forms (8 x a float32 restatement's own deviation, at least 2^-22).
 (6) end to end: max(1 - cos) <= 1e-3, the project's standing bound for the bf16 path.  Measured values: DESIGN.md 4.15.
+    What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, the other activation):
+    tests/test_gpu_tower_sharpness.py.
 """
 import ctypes as C
 import dataclasses

@@ -26,6 +26,8 @@ Tolerances, none fitted:
     the last term for results below the smallest normal f32, which the exp's overflow (z < -88.7: e = inf, p = 0) or a
     flushed reciprocal may return as 0.  Checked at |z| in {0, 1, 20, 100}, both signs.
 (6) parity: max(1 - cos) <= 1e-3 against the recorded transformers rows, the project's bound for every tower.
+    What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, the other activation):
+    tests/test_gpu_tower_sharpness.py.
 A GPU fault in one test ends the module's GPU work: the tests after it fail without launching anything.
 """
 import ctypes as C

@@ -7,7 +7,8 @@ One-layer seeded towers at hidden 384 (MLP 64, as TINY of tests/test_gpu_dinov2.
     pruning setting is what it was afterwards: a plain forward still launches the pruned sequence;
 (c) mme_embed_tokens = mme_preprocess + mme_vit_tokens, bit for bit; a one-row window at the last token; sentinel items stay;
 (d) every token row against transformers' last_hidden_state (tests/golden/tokens_<tower>.npz, CLIP behind its post_layernorm),
-    L2-normalised in float64: max(1 - cos) <= 1e-3, the project's bound for the bf16 path;
+    L2-normalised in float64: max(1 - cos) <= 1e-3, the project's bound for the bf16 path (what that bound cannot see on
+    std 0.02 weights -- uniform attention, Q and K exchanged, a dropped key -- is held by tests/test_gpu_tower_sharpness.py);
 (e) the refusals, by message;
 (f) RegionEmbedder.get_patch_embeddings: the vectors of get_image_embeddings, the token blocks of mme_embed_tokens in input
     order, zeros for an item that failed, the caller's `out`.

@@ -14,6 +14,8 @@ identities; coexistence with patch-16 towers and the text tower on one context; 
     for the 197-token forms: 8 x the deviation of a float32 numpy restatement measured in the test, never below 2^-22 of
     the largest value, plus ulp_bf16(ref) / 2 where the kernel writes bf16.
 (4) end to end: max(1 - cos) <= 1e-3, the project's standing bound for the bf16 path.  Measured values: DESIGN.md 4.10.
+    What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, the other activation):
+    tests/test_gpu_tower_sharpness.py.
 """
 import ctypes as C
 import dataclasses

@@ -5,6 +5,8 @@ What is compared with what, and why the bound is what it is:
      synthetic crops plus the 24 bundled variable-size crops of tests/test_gpu_parity.py: max(1 - cos) <= 1e-3, the
      project's bound for this comparison (bf16 MFMA path against an f32 oracle; ViT-B/16 measures 4.8e-5), with that
      file's centred check against the trivial pass.  The worst value per geometry is printed (`pytest -s`).
+     What that bound cannot see on std 0.02 weights (uniform attention, Q and K exchanged, a dropped key, tanh- for
+     erf-GELU) and what holds it: tests/test_gpu_tower_sharpness.py.
   2. Bit equalities, on 3-layer ViT-S and ViT-L: everything that is the same arithmetic in another order of launches,
      tiles or loaders is compared for EQUALITY (checkpoint directory in f32 / bf16 / f16 against the host loader, the
      fingerprints of the prepared buffers, LayerNorm fusion 1 against 2 under every GEMM variant, pruning, the forced
