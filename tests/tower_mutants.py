@@ -9,6 +9,8 @@ What the two sharpness tests share (tests/test_tower_sharpness_cpu.py, tests/tes
   * MUTANTS: per kind of tower, label -> the name the restatements switch on (`mutant=` in tests/*_reference.py).
   * outputs(): every output the GPU test compares, from one pass of the float64 (or emulated) restatement.
   * distance(): per crop or sequence, the maximum over its outputs and their rows of 1 - cos, in float64.
+  * TILE_*: the tile tower's case, a registry of its own at the end of this file (tests/test_tile_tower_sharpness_cpu.py,
+    tests/test_gpu_tile_tower_sharpness.py), under the same three bounds.
 
 The bounds: an engine within BOUND = 1e-3 of the restatement (the project's bound) is, by the triangle inequality on angles
 (1 - cos = 2 sin^2(angle / 2): a factor 4 in 1 - cos is a factor 2 in angle), more than 1e-3 from anything that is MUTANT_FAR
@@ -28,6 +30,7 @@ import clip_text_reference as ctr
 import dinov2_reference as dr
 import siglip_reference as sr
 import siglip_text_reference as strf
+import tile_reference as tr
 import vit_reference as vr
 from multimodal_embeddings_amd import weights as W
 
@@ -200,3 +203,77 @@ def distance(got: dict, want: dict) -> np.ndarray:
     """The metric: per crop or sequence, the maximum of 1 - cos over every row of every output, [n] in float64"""
     assert got.keys() == want.keys()
     return np.max([one_minus_cos(got[k], want[k]).max(axis=1) for k in want], axis=0)
+
+
+# ---- the tile tower (tests/test_tile_tower_sharpness_cpu.py, tests/test_gpu_tile_tower_sharpness.py) -------------------------
+# A registry of its own beside TOWERS and MUTANTS: one image is one sequence of 6432 tokens with an aspect-ratio id and a tile
+# count, and a forward of the restatement (tests/tile_reference.py) takes seconds, so the cases are three images, not ten towers.
+# The smallest tower with a local layer, a gated global layer and an intermediate feature (token counts and widths are fixed
+# at compile time in the engine: nothing smaller exists)
+TILE_GEOM = dataclasses.replace(W.TILE_VIT, num_layers=1, num_global_layers=1, intermediate_layers=(0,))
+TILE_SEED = 31
+# (name suffix, factor, offset); a gate is SET by factor 0.  What each line is for (the mutants named; measured values in
+# tests/test_tile_tower_sharpness_cpu.py).  The seeded gates are pi / 4 twice: "gate_attn / gate_ffn exchanged" is the same tower.
+TILE_RECIPE = MLP + (
+    # scores x 16 (the weights are N(0, 0.02) at width 1280), the factor of the peaked-attention test of tests/test_gpu_tilevit.py.
+    # At x 2.5 (scores x 6.25) "one key of 6432 dropped" is 2.8e-3 and "a tile's 7 padding tokens taken as real" 1.3e-3, at
+    # x 3.5 7.0e-3 and 3.7e-3; at x 5 the bf16 emulation leaves its bound (2.9e-4)
+    ("q_proj.weight", 4.0, 0.0), ("k_proj.weight", 4.0, 0.0),
+    # two different gates, one of them where g and tanh g are apart (1.5 against 0.905): "exchanged", "without its tanh"
+    ("gate_attn", 0.0, 1.5), ("gate_ffn", 0.0, 0.3),
+    # the post-tile embedding at the size of the LayerNorm output it is added to (N(0, 0.02) x tanh(-0.5) is 1 % of it): "left
+    # out" 6e-5 and "added before layernorm_post" 2e-6 without it
+    ("post_tile_positional_embedding.embedding.weight", 50.0, 0.0),
+    # layernorm_post with a spread: gamma 1 + N(0, 0.5), beta N(0, 0.5).  The global layer normalises its input again, so a
+    # layernorm_post of gamma near 1 and beta near 0 is nearly invisible: "layernorm_post left out" 9e-4 without it
+    ("layernorm_post.weight", 25.0, -24.0), ("layernorm_post.bias", 25.0, 0.0),
+    # ln1 apart from ln2, gamma 1 + N(0, 0.2): "ln1 / ln2 parameters exchanged" 1.1e-3 without it
+    ("input_layernorm.weight", 10.0, -9.0),
+)
+TILE_IMAGES = ((300, 200, 3), (400, 900, 3), (1000, 1100, 3))  # 1, 2 and 4 tiles; aspect-ratio ids 1, 2 and 6
+TILE_MUTANTS = {
+    **ATTENTION,
+    "padding keys masked for every query": "pad_keys_masked", "(padding, padding) mask dropped": "no_pad_mask",
+    "each tile attends only itself": "tile_local", "global gates ignored": "gates_ignored",
+    "gate used without its tanh": "gate_without_tanh", "gate_attn / gate_ffn exchanged": "gates_exchanged",
+    "pre-tile embedding added to the class row too": "pre_on_class", "(1 - tanh g) factor dropped": "no_one_minus_gate",
+    "tile-embedding rows rolled by one tile": "tile_emb_rolled", "post-tile embedding left out": "no_post_emb",
+    "post-tile embedding added before layernorm_post": "post_emb_before_ln", "layernorm_pre left out": "no_ln_pre",
+    "layernorm_post left out": "no_ln_post", "ln1 / ln2 parameters exchanged": "ln_exchanged",
+    "residual around the MLP dropped": "no_mlp_residual", "the class row of tile 1 pooled for tile 0": "pooled_tile_1",
+    "a tile's 7 padding tokens taken as real": "pad_tokens_real", "one key of 6432 dropped": "key_dropped",
+}
+# recorded and not asserted (tests/test_tile_tower_sharpness_cpu.py says which levers were tried and what holds the property)
+TILE_RECORDED_ONLY = {"tanh-GELU for erf-GELU": "other_gelu"}
+
+
+def tile_weights(sharp: bool = True, recipe=TILE_RECIPE) -> dict:
+    """The sharp weights of the tile case; sharp=False: `make_tile_vit_weights` of the same seed as the tile tests use them"""
+    w = dict(W.make_tile_vit_weights(TILE_SEED, TILE_GEOM))
+    if sharp:
+        for name in w:
+            for suffix, factor, offset in recipe:
+                if name.endswith(suffix):
+                    w[name] = W.round_to_bf16(w[name] * np.float32(factor) + np.float32(offset)).reshape(w[name].shape)
+        assert all(float(v[0]) != 0.0 for name, v in w.items() if name.endswith("gate") or ".gate_" in name)
+    return w
+
+
+def tile_images() -> list:
+    """Three synthetic uint8 images that the Mllama preprocessing turns into 1, 2 and 4 tiles"""
+    rng = np.random.default_rng(TILE_SEED)
+    return [rng.integers(0, 256, s, dtype=np.uint8) for s in TILE_IMAGES]
+
+
+def tile_inputs() -> list:
+    """Per image (pixel values f32 [4, 3, 560, 560], aspect-ratio id, tile count) from the oracle's tile preprocessing, which
+    `mme_preprocess_tiles` equals bit for bit (tests/test_gpu_tiles.py)"""
+    from oracle import preprocess as opre
+
+    return [opre.preprocess_tiles(a)[:3] for a in tile_images()]
+
+
+def tile_distance(got: dict, want: dict) -> float:
+    """The metric of one image: the maximum of 1 - cos over every row of all four tiles of every output, in float64"""
+    assert got.keys() == want.keys()
+    return float(max(one_minus_cos(got[k], want[k]).max() for k in want))
