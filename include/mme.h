@@ -856,6 +856,68 @@ int mme_duplicates_merge(mme_ctx* ctx, const mme_dup_state* dst, const mme_dup_s
 int mme_duplicates_finish(mme_ctx* ctx, const mme_dup_state* state, int N, int32_t* labels_dev, int32_t* best_idx_dev,
                           float* best_sim_dev, int64_t* summary_dev, void* stream);
 
+/* ---- K15: spherical k-means over the vector table -------------------------------
+ * Partitions the rows of the L2-normalised bf16 table emb_dev[N, d] into k clusters by cosine to a unit centroid.
+ *   assign   label[i] = argmax_j s_ij, s_ij the f32-accumulated cosine of row i and centroid j (K9's GEMM); sim[i] = that
+ *            value.  The order of the scores is total: a NaN is below every number, -0.0 below +0.0, among bit-equal scores
+ *            the lowest j wins.  Against the float64 dot product s64 of the same bf16 rows, with delta = 2 * d * 2^-24
+ *            (K14's bound): s64[label] >= max_j s64 - 2 delta and |sim - s64[label]| <= delta.
+ *   update   sums[j, :] = the bf16 rows with label j, widened to f64 and added in ascending row index; counts[j] their number;
+ *            for counts[j] > 0: n2 = sum_c sums[j, c]^2 (ascending c), centroids[j, c] = sums[j, c] / max(sqrt(n2), 1e-12),
+ *            rounded once from f64 to bf16, nearest even.  An empty cluster keeps its centroid row; its sums are 0.  No
+ *            floating-point atomics: bit-identical run to run.
+ * mme_kmeans: the start centroids are the rows init_rows_host[0..k) of emb (k distinct rows), or, with NULL, what
+ * state.centroids holds.  Assign against the start; then up to max_iter iterations of { update; assign; step end }, where
+ * the step end counts the iteration, records the rows whose label changed, and stops the loop on the device once an
+ * iteration moved no row (converged = 1; that iteration is counted).  So labels and sim always describe the returned
+ * centroids; sums and counts are those of the last update (the labels the returned centroids were computed from; not
+ * written with max_iter = 0, which is "assign rows to given centroids").  Everything is enqueued on `stream`; the call
+ * never waits for the device (the cosine blocks and the update's scratch go through the K12 workspace, in row chunks when
+ * [N, k] f32 exceeds it; init_rows_host goes up in one asynchronous copy of k int32 and may be reused on return).
+ *   info  int64[4]: iterations run, rows moved by the last iteration, converged (0 / 1), clusters that were empty in the
+ *         last update;  objective  f64[1]: the sum of sim in a fixed order.
+ * MME_E_ARG, with the field and the value in mme_last_error, nothing enqueued, the context usable: N < 1, d % 64 != 0, k
+ * outside 1..min(N, 65536), max_iter outside 0..1000, an init row outside 0..N-1 or listed twice, a null pointer.
+ * Profiling classes: the GEMM counts as "cosine", everything else as "cluster". */
+typedef struct mme_kmeans_state {   /* caller-owned device memory */
+    uint16_t* centroids;   /* bf16 [k, d]  in: the start (unless init_rows is given); out: final */
+    double*   sums;        /* [k, d] */
+    int32_t*  counts;      /* [k] */
+    int32_t*  labels;      /* [N] */
+    float*    sim;         /* [N] cosine of each row to its centroid */
+    int64_t*  info;        /* [4] iterations run, rows moved by the last iteration, converged (0/1), empty clusters */
+    double*   objective;   /* [1] sum of sim */
+} mme_kmeans_state;
+int mme_kmeans(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, int k, const int32_t* init_rows_host, int max_iter,
+               const mme_kmeans_state* state, void* stream);
+
+/* Diagnostic: ONE step of K15 on the caller's device tensors (synchronous; works on a bare context), so that each can be
+ * compared with a float64 restatement directly (tests/test_gpu_kmeans.py).
+ *   op 0 ARGMAX  qsim f32 [N, ld] (ld % 4 == 0, ld >= k, 16-byte aligned), k valid columns -> labels[N], sim[N];
+ *                *moved += the rows whose label differs from the labels[row] found there
+ *   op 1 ASSIGN  emb bf16 [N, d] against centroids bf16 [k, d]: the GEMM into the workspace in chunks of chunk_rows rows (0 =
+ *                by size), ARGMAX after each; outputs as op 0
+ *   op 2 UPDATE  emb, labels (a label outside 0..k-1 belongs to no cluster) -> sums f64 [k, d], counts[k], centroids
+ * run_if (optional, int32 on the device): the launches return at once unless *run_if != 0.
+ * Preconditions (else MME_E_ARG with the field and the value in mme_last_error, nothing launched): op 0..2; N in 1..2^24;
+ * k in 1..65536; ops 1, 2: d a multiple of 64 in 64..65536; the pointers the op uses non-null and aligned as stated. */
+enum { MME_KMEANS_ARGMAX = 0, MME_KMEANS_ASSIGN = 1, MME_KMEANS_UPDATE = 2 };
+typedef struct mme_kmeans_apply_args {
+    const float* qsim;       /* op 0 */
+    int64_t ld;              /* op 0 */
+    const uint16_t* emb;     /* ops 1, 2 */
+    uint16_t* centroids;     /* op 1: in; op 2: out */
+    int32_t N, d, k;
+    int32_t chunk_rows;      /* op 1 */
+    int32_t* labels;         /* ops 0, 1: in (previous) and out; op 2: in */
+    float* sim;              /* ops 0, 1 */
+    int64_t* moved;          /* ops 0, 1 */
+    const int32_t* run_if;
+    double* sums;            /* op 2 */
+    int32_t* counts;         /* op 2 */
+} mme_kmeans_apply_args;
+int mme_kmeans_apply(mme_ctx* ctx, int op, const mme_kmeans_apply_args* args, void* stream);
+
 /* Diagnostic: time one MFMA GEMM shape on random bf16 data (allocates its own operands;
  * synchronous).  epilogue 0 bias, 1 bias+GELU, 2 bias+residual, 3 patch-embed, 4 f32 out;
  * variant as mme_set_gemm_variant. */

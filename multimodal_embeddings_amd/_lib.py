@@ -175,6 +175,18 @@ class _DupState(C.Structure):  # mme_dup_state
     ]
 
 
+class _KmeansState(C.Structure):  # mme_kmeans_state
+    _fields_ = [(f, C.c_void_p) for f in ("centroids", "sums", "counts", "labels", "sim", "info", "objective")]
+
+
+class _KmeansApplyArgs(C.Structure):  # mme_kmeans_apply_args
+    _fields_ = [
+        ("qsim", C.c_void_p), ("ld", C.c_int64), ("emb", C.c_void_p), ("centroids", C.c_void_p), ("N", C.c_int32), ("d", C.c_int32),
+        ("k", C.c_int32), ("chunk_rows", C.c_int32), ("labels", C.c_void_p), ("sim", C.c_void_p), ("moved", C.c_void_p),
+        ("run_if", C.c_void_p), ("sums", C.c_void_p), ("counts", C.c_void_p),
+    ]
+
+
 EXPORTS = {
     "mme_abi_version": (C.c_int, []),
     "mme_is_diag_build": (C.c_int, []),
@@ -252,6 +264,8 @@ EXPORTS = {
                                       C.POINTER(_DupState), C.c_void_p]),
     "mme_duplicates_merge": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.POINTER(_DupState), C.c_int, C.c_void_p]),
     "mme_duplicates_finish": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_KmeansState), C.c_void_p]),
+    "mme_kmeans_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_KmeansApplyArgs), C.c_void_p]),
     "mme_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mme_gemm_apply": (C.c_int, [C.c_void_p, C.POINTER(_GemmApplyArgs), C.POINTER(C.c_int32), C.c_void_p]),
@@ -462,6 +476,18 @@ def _siglip_logits(get):
 
 def _siglip_text_special(get, extra):
     return {"logits": _siglip_logits(get)}, None
+
+
+class KmeansResult:
+    """What Engine.kmeans returns, CUDA tensors: labels int32 [N], sim float32 [N], centroids bfloat16 [k, d], counts int32 [k],
+    sums float64 [k, d], info int64 [4] (iterations, rows moved by the last one, converged, empty clusters), objective
+    float64 [1] (the sum of sim)."""
+
+    __slots__ = ("labels", "sim", "centroids", "counts", "sums", "info", "objective")
+
+    def __init__(self, **kw):
+        for f in self.__slots__:
+            setattr(self, f, kw[f])
 
 
 class Engine:
@@ -1518,6 +1544,60 @@ class Engine:
         row0, nrows = (0, None) if rows is None else rows
         self.duplicates_scan(state, emb, group, page_of, min_sim=min_sim, row0=row0, nrows=nrows)
         return self.duplicates_finish(state)
+
+    # ---- K15 spherical k-means (mme.h, mme_kmeans*) ----
+    def kmeans(self, emb_bf16, k, init_rows=None, centroids=None, max_iter=100):
+        """Spherical k-means of the L2-normalised bf16 rows emb_bf16[N, d] into k clusters (mme_kmeans; enqueues and returns).
+        The start is `init_rows` (k distinct rows of emb) or `centroids` (bf16 [k, d], copied), exactly one of them.
+        max_iter = 0 assigns the rows to the given centroids.  -> KmeansResult of CUDA tensors; counts and sums are those
+        of the last update (zero with max_iter = 0).  The library validates N, d, k, max_iter and the rows."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != dev:
+            raise MmeError("kmeans: emb must be a 2-D bfloat16 tensor on this engine's device")
+        if (init_rows is None) == (centroids is None):
+            raise MmeError("kmeans: give exactly one of init_rows and centroids")
+        N, d = e.shape
+        k = int(k)
+        rows = None
+        if init_rows is not None:
+            rows = np.ascontiguousarray(np.asarray(init_rows).reshape(-1), dtype=np.int32)
+            if rows.size != k:
+                raise MmeError(f"kmeans: init_rows has {rows.size} rows, k = {k}")
+            cen = t.zeros((max(k, 1), d), dtype=t.bfloat16, device=dev)
+        else:
+            if centroids.dtype != t.bfloat16 or centroids.dim() != 2 or tuple(centroids.shape) != (k, d):
+                raise MmeError(f"kmeans: centroids must be a bfloat16 tensor [k = {k}, d = {d}], got {centroids.dtype} {tuple(centroids.shape)}")
+            cen = centroids.to(dev).contiguous().clone()
+        res = KmeansResult(labels=t.empty(max(N, 1), dtype=t.int32, device=dev)[:N], sim=t.empty(max(N, 1), dtype=t.float32, device=dev)[:N],
+                           centroids=cen[:k], counts=t.zeros(max(k, 1), dtype=t.int32, device=dev)[:k],
+                           sums=t.zeros((max(k, 1), d), dtype=t.float64, device=dev)[:k], info=t.zeros(4, dtype=t.int64, device=dev),
+                           objective=t.zeros(1, dtype=t.float64, device=dev))
+        st = _KmeansState()
+        for f in ("centroids", "sums", "counts", "labels", "sim", "info", "objective"):
+            setattr(st, f, int(getattr(res, f).data_ptr()))
+        self._check(self.lib.mme_kmeans(self.h, e.data_ptr(), N, d, k, None if rows is None else rows.ctypes.data, int(max_iter), C.byref(st),
+                                        self._stream()), "mme_kmeans")
+        return res
+
+    KMEANS_OPS = {"argmax": 0, "assign": 1, "update": 2}
+
+    def kmeans_apply(self, op, *, qsim=None, ld=None, emb=None, centroids=None, N=None, d=None, k=None, chunk_rows: int = 0, labels=None, sim=None,
+                     moved=None, run_if=None, sums=None, counts=None):
+        """ONE step of K15 on the caller's CUDA tensors (mme_kmeans_apply; synchronous, works on a bare context).  op: a name
+        of KMEANS_OPS or its code; which tensors each op reads and writes is in include/mme.h.  `ld` defaults to qsim's row
+        pitch, N to the rows of qsim / emb, d to emb's width and k to the rows of centroids.  The library validates."""
+        a = _KmeansApplyArgs()
+        a.qsim, a.emb, a.centroids, a.labels, a.sim = (self._ptr(x) for x in (qsim, emb, centroids, labels, sim))
+        a.moved, a.run_if, a.sums, a.counts = (self._ptr(x) for x in (moved, run_if, sums, counts))
+        a.ld = int((qsim.stride(0) if qsim is not None else 0) if ld is None else ld)
+        src = qsim if qsim is not None else emb
+        a.N = int((src.shape[0] if src is not None else 0) if N is None else N)
+        a.d = int((emb.shape[1] if emb is not None else 0) if d is None else d)
+        a.k = int((centroids.shape[0] if centroids is not None else 0) if k is None else k)
+        a.chunk_rows = int(chunk_rows)
+        self._check(self.lib.mme_kmeans_apply(self.h, int(self.KMEANS_OPS.get(op, op)), C.byref(a), self._stream()), "mme_kmeans_apply")
 
     def gemm_bench(self, M, N, K, epilogue=0, variant=0, iters=10):
         """(avg ms, TFLOP/s) for one GEMM shape on random data."""

@@ -219,3 +219,165 @@ def create_duplicate_report(collection, threshold, output_path=None, **kwargs):
         with open(output_path, "w") as fh:
             json.dump(result, fh, indent=1)
     return result
+
+
+# ---- K15: k groups of look-alike regions (spherical k-means) ---------------------------------------------
+
+def cluster_table(labels, sim, ids, metadatas, *, n_clusters=None, iterations=None, converged=None, objective=None, max_members=None):
+    """The JSON-ready report from K15's arrays; a pure function of its arguments (no GPU).
+
+    labels[i] = the cluster of row i, sim[i] = its cosine to that cluster's centroid; ids / metadatas are the rows'.  Returns
+      {"n_regions", "n_clusters", "n_empty", "iterations", "converged", "objective",
+       "clusters": [{"cluster", "size", "cohesion": mean sim or None, "medoid": id of the member with the largest sim (the lowest
+                     row among equals) or None, "pages": [page names, sorted],
+                     "members": [{"id", "parent_image", "type", "area_percentage", "score"}, ... by score descending, then row]},
+                    ... cluster 0 .. n_clusters - 1; an empty cluster is listed with size 0, never renumbered]}
+    n_clusters defaults to max(labels) + 1; max_members keeps only the best members of each list (size and cohesion stay whole)."""
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    sim = np.asarray(sim, dtype=np.float64).reshape(-1)
+    n = len(ids)
+    if not (len(labels) == len(sim) == len(metadatas) == n):
+        raise ValueError("cluster_table: labels, sim, ids and metadatas must have one entry per row")
+    k = (int(labels.max()) + 1 if n else 0) if n_clusters is None else int(n_clusters)
+    if n and (labels.min() < 0 or labels.max() >= k):
+        raise ValueError(f"cluster_table: labels must lie in 0..{k - 1}")
+    members = [[] for _ in range(k)]
+    for r in range(n):
+        members[int(labels[r])].append(r)
+    clusters = []
+    for j, rows in enumerate(members):
+        rows = sorted(rows, key=lambda r: (-sim[r], r))  # a NaN score would not sort: K15 gives none on unit rows
+        out_rows = []
+        for r in rows:
+            m = metadatas[r] or {}
+            out_rows.append({"id": ids[r], "parent_image": os.path.basename(_parent_of(m)), "type": m.get("region_type", "unknown"),
+                             "area_percentage": m.get("area_percentage", 0), "score": float(sim[r])})
+        clusters.append({"cluster": j, "size": len(rows), "cohesion": float(np.mean(sim[rows])) if rows else None,
+                         "medoid": ids[rows[0]] if rows else None,
+                         "pages": sorted({m["parent_image"] for m in out_rows if m["parent_image"]}),
+                         "members": out_rows if max_members is None else out_rows[: int(max_members)]})
+    return {"n_regions": n, "n_clusters": k, "n_empty": sum(1 for c in clusters if c["size"] == 0),
+            "iterations": None if iterations is None else int(iterations), "converged": None if converged is None else bool(converged),
+            "objective": None if objective is None else float(objective), "clusters": clusters}
+
+
+def kmeans_init_rows(emb, k, init="k-means++", seed=0):
+    """k distinct start rows of the unit rows emb [N, d] (a torch tensor on any device), sorted, as int32 numpy.
+
+    init = "k-means++": the first row uniform, each further row with probability proportional to 1 - (its largest cosine to the
+    rows chosen so far), from a torch.Generator on emb's device seeded with `seed` (plain torch: k matrix-vector products);
+    "random": numpy.random.default_rng(seed).choice without replacement; an int array: those rows (checked, not sorted)."""
+    import torch
+
+    n, k = int(emb.shape[0]), int(k)
+    if k < 1 or k > n:
+        raise ValueError(f"n_clusters = {k} must lie in 1..{n} (the number of rows)")
+    if not isinstance(init, str):
+        rows = np.asarray(init)
+        if rows.ndim != 1 or rows.size != k or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError(f"init rows must be a 1-D integer array of n_clusters = {k} rows")
+        if rows.min() < 0 or rows.max() >= n:
+            raise ValueError(f"init rows must lie in 0..{n - 1}")
+        if len(np.unique(rows)) != k:
+            raise ValueError("init rows must be distinct")
+        return rows.astype(np.int32)
+    if init == "random":
+        return np.sort(np.random.default_rng(int(seed)).choice(n, size=k, replace=False)).astype(np.int32)
+    if init != "k-means++":
+        raise ValueError("init must be 'k-means++', 'random' or an integer array of rows")
+    g = torch.Generator(device=emb.device).manual_seed(int(seed))
+    x = emb.to(torch.float32)
+    chosen = torch.zeros(n, dtype=torch.bool, device=emb.device)
+    first = int(torch.randint(0, n, (1,), generator=g, device=emb.device).item())
+    rows = [first]
+    chosen[first] = True
+    dist = (1.0 - x @ x[first]).clamp_(min=0.0)
+    for _ in range(1, k):
+        w = dist.masked_fill(chosen, 0.0)
+        if float(w.sum().item()) <= 0.0:  # every row left is a copy of a chosen one: take the lowest
+            nxt = int(torch.nonzero(~chosen)[0].item())
+        else:
+            nxt = int(torch.multinomial(w, 1, generator=g).item())
+        rows.append(nxt)
+        chosen[nxt] = True
+        dist = torch.minimum(dist, (1.0 - x @ x[nxt]).clamp_(min=0.0))
+    return np.sort(np.asarray(rows)).astype(np.int32)
+
+
+def _region_rows(collection, where):
+    all_entries = collection.get(include=["metadatas", "embeddings", "documents"], where=where)
+    have = [r for r, e in enumerate((all_entries or {}).get("embeddings") or []) if e is not None and len(e) > 0]
+    return all_entries, have
+
+
+def cluster_regions(collection, n_clusters, *, where={"is_region": {"$eq": True}}, init="k-means++", seed=0, n_init=1, max_iter=100,
+                    engine: Engine | None = None, max_members=None):
+    """n_clusters groups of look-alike regions: spherical k-means (kernel K15) over the unit bf16 vectors of the rows `where`
+    selects (rows without an embedding left out).  Returns cluster_table's dict; kmeans_regions also returns the arrays
+    (the centroids among them, which assign_regions takes).
+
+    init: kmeans_init_rows' forms; run r of n_init uses seed + r, and the run with the largest objective (the sum of the
+    rows' cosines to their centroids) is kept, the first among equals."""
+    table, _ = kmeans_regions(collection, n_clusters, where=where, init=init, seed=seed, n_init=n_init, max_iter=max_iter, engine=engine,
+                              max_members=max_members)
+    return table
+
+
+def kmeans_regions(collection, n_clusters, *, where={"is_region": {"$eq": True}}, init="k-means++", seed=0, n_init=1, max_iter=100,
+                   engine: Engine | None = None, max_members=None):
+    """cluster_regions, returning (table, arrays): arrays = {"ids", "labels", "sim", "centroids" (bf16 CUDA tensor), "counts",
+    "objectives" (one per run), "best_run"} or None without regions."""
+    if int(n_init) < 1:
+        raise ValueError(f"n_init = {n_init} must be at least 1")
+    if int(max_iter) < 0 or int(max_iter) > 1000:
+        raise ValueError(f"max_iter = {max_iter} must lie in 0..1000")
+    all_entries, have = _region_rows(collection, where)
+    if not have:
+        logger.warning("No regions found in the database. Make sure regions have been processed first.")
+        return cluster_table([], [], [], [], n_clusters=0), None
+    ids = [all_entries["ids"][r] for r in have]
+    metas = [all_entries["metadatas"][r] for r in have]
+    if int(n_clusters) < 1 or int(n_clusters) > len(ids):
+        raise ValueError(f"n_clusters = {n_clusters} must lie in 1..{len(ids)} (the number of regions)")
+    engine = engine or default_engine()
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
+    best, objectives, best_run = None, [], 0
+    for run in range(int(n_init)):
+        rows = kmeans_init_rows(emb, n_clusters, init, int(seed) + run)
+        res = engine.kmeans(emb, int(n_clusters), init_rows=rows, max_iter=int(max_iter))
+        obj = float(res.objective.item())
+        objectives.append(obj)
+        if best is None or obj > objectives[best_run]:
+            best, best_run = res, run
+    info = best.info.cpu().numpy()
+    labels, sim = best.labels.cpu().numpy(), best.sim.cpu().numpy()
+    table = cluster_table(labels, sim, ids, metas, n_clusters=int(n_clusters), iterations=int(info[0]), converged=bool(info[2]),
+                          objective=objectives[best_run], max_members=max_members)
+    return table, {"ids": ids, "labels": labels, "sim": sim, "centroids": best.centroids, "counts": best.counts.cpu().numpy(),
+                   "objectives": objectives, "best_run": best_run}
+
+
+def assign_regions(centroids, embeddings, *, engine: Engine | None = None):
+    """Which existing cluster does each new vector belong to: (labels int32 [n], sim float32 [n]) numpy arrays, the cluster whose
+    centroid (bf16 [k, d] tensor, as kmeans_regions returns) has the largest cosine with the row and that cosine.  K15 with
+    max_iter = 0: the centroids are not changed.  mme_kmeans wants at least k rows, so fewer are padded with copies of the
+    first row, whose results are dropped."""
+    engine = engine or default_engine()
+    emb = to_unit_bf16(embeddings, engine)
+    n, k = int(emb.shape[0]), int(centroids.shape[0])
+    if n == 0:
+        return np.empty(0, dtype=np.int32), np.empty(0, dtype=np.float32)
+    if n < k:
+        emb = engine.torch.cat([emb, emb[:1].expand(k - n, -1)]).contiguous()
+    res = engine.kmeans(emb, k, centroids=centroids, max_iter=0)
+    return res.labels[:n].cpu().numpy(), res.sim[:n].cpu().numpy()
+
+
+def create_region_cluster_report(collection, n_clusters, output_path=None, **kwargs):
+    """cluster_regions, written as one JSON document when `output_path` is given (as create_duplicate_report)."""
+    result = cluster_regions(collection, n_clusters, **kwargs)
+    if output_path:
+        os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+        with open(output_path, "w") as fh:
+            json.dump(result, fh, indent=1)
+    return result
