@@ -918,6 +918,42 @@ typedef struct mme_kmeans_apply_args {
 } mme_kmeans_apply_args;
 int mme_kmeans_apply(mme_ctx* ctx, int op, const mme_kmeans_apply_args* args, void* stream);
 
+/* ---- K16: the silhouette of a partition of the vector table ----------------------
+ * How well labels_dev[N] (a label outside 0..k-1 belongs to no cluster) partition the bf16 rows emb_dev[N, d] under the
+ * distance 1 - x_i . x_j of the stored rows, widened exactly to f64 -- without the N x N matrix: the distances from row i to
+ * the members of cluster c add up to n_c - x_i . S_c.
+ *   S_c, n_c   sums and counts of K15's update on these labels (same adds, same order)
+ *   g_ic = sum_t x_it S_ct,  q_i = sum_t x_it^2     in f64, each one chain of fused multiply-adds in ascending t
+ *   row i with c = label[i]:  n_c == 1: s_i = 0.  Otherwise
+ *       a_i = ((n_c - g_ic) - (1 - q_i)) / (n_c - 1)        the row's own distance 1 - q_i left out
+ *       b_i = min over c' != c with n_c' > 0 of 1 - g_ic' / n_c'      (+inf when there is none)
+ *       s_i = (b_i - a_i) / max(a_i, b_i), a NaN quotient becoming 0
+ *     each formula with exactly the operations written, in that order.  A row of no cluster: s_i = NaN, not counted.
+ *   sample   f64 [N] s_i; may be NULL
+ *   cluster  f64 [k] the mean s_i of each cluster's rows (NaN for an empty cluster)
+ *   score    f64 [1] the mean over the counted rows; NaN when fewer than two clusters have members or no row is counted
+ *   info     int64 [2] rows counted, clusters with members
+ *   sums     f64 [k, d], counts int32 [k]: S_c and n_c, as mme_kmeans_state's
+ * The means add in a fixed order (per cluster, then over the clusters); no floating-point atomics: every output is
+ * bit-identical run to run.  Everything is enqueued on `stream`; scratch comes from the K12 workspace.
+ * MME_E_ARG, with the field and the value in mme_last_error, nothing enqueued, the context usable: N < 2, d % 64 != 0, k
+ * outside 2..min(N, 65536), a null pointer other than sample.  Profiling class: "cluster". */
+typedef struct mme_silhouette_out {   /* caller-owned device memory */
+    double*  sample;    /* [N] or NULL */
+    double*  cluster;   /* [k] */
+    double*  score;     /* [1] */
+    int64_t* info;      /* [2] rows counted, clusters with members */
+    double*  sums;      /* [k, d] */
+    int32_t* counts;    /* [k] */
+} mme_silhouette_out;
+int mme_silhouette(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* labels_dev, int k,
+                   const mme_silhouette_out* out, void* stream);
+
+/* Diagnostic: the rows kernel of K16 alone, on the caller's sums f64 [k, d] and counts int32 [k] -> sample f64 [N]
+ * (enqueues; the same shape checks as mme_silhouette, every pointer non-null, emb and sums 16-byte aligned). */
+int mme_silhouette_rows(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* labels_dev, int k,
+                        const double* sums_dev, const int32_t* counts_dev, double* sample_dev, void* stream);
+
 /* Diagnostic: time one MFMA GEMM shape on random bf16 data (allocates its own operands;
  * synchronous).  epilogue 0 bias, 1 bias+GELU, 2 bias+residual, 3 patch-embed, 4 f32 out;
  * variant as mme_set_gemm_variant. */

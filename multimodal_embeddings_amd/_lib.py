@@ -187,6 +187,10 @@ class _KmeansApplyArgs(C.Structure):  # mme_kmeans_apply_args
     ]
 
 
+class _SilhouetteOut(C.Structure):  # mme_silhouette_out
+    _fields_ = [(f, C.c_void_p) for f in ("sample", "cluster", "score", "info", "sums", "counts")]
+
+
 EXPORTS = {
     "mme_abi_version": (C.c_int, []),
     "mme_is_diag_build": (C.c_int, []),
@@ -266,6 +270,8 @@ EXPORTS = {
     "mme_duplicates_finish": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_KmeansState), C.c_void_p]),
     "mme_kmeans_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_KmeansApplyArgs), C.c_void_p]),
+    "mme_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_SilhouetteOut), C.c_void_p]),
+    "mme_silhouette_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mme_gemm_apply": (C.c_int, [C.c_void_p, C.POINTER(_GemmApplyArgs), C.POINTER(C.c_int32), C.c_void_p]),
@@ -484,6 +490,18 @@ class KmeansResult:
     float64 [1] (the sum of sim)."""
 
     __slots__ = ("labels", "sim", "centroids", "counts", "sums", "info", "objective")
+
+    def __init__(self, **kw):
+        for f in self.__slots__:
+            setattr(self, f, kw[f])
+
+
+class SilhouetteResult:
+    """What Engine.silhouette returns, CUDA tensors: score float64 [1] (NaN with fewer than two clusters with members), cluster
+    float64 [k] (each cluster's mean, NaN for an empty one), info int64 [2] (rows counted, clusters with members), sums float64
+    [k, d] and counts int32 [k] (as K15's update leaves them), samples float64 [N] or None."""
+
+    __slots__ = ("score", "cluster", "info", "sums", "counts", "samples")
 
     def __init__(self, **kw):
         for f in self.__slots__:
@@ -1598,6 +1616,39 @@ class Engine:
         a.k = int((centroids.shape[0] if centroids is not None else 0) if k is None else k)
         a.chunk_rows = int(chunk_rows)
         self._check(self.lib.mme_kmeans_apply(self.h, int(self.KMEANS_OPS.get(op, op)), C.byref(a), self._stream()), "mme_kmeans_apply")
+
+    # ---- K16 silhouette of a partition (mme.h, mme_silhouette) ----
+    def silhouette(self, emb_bf16, labels, k, samples=False):
+        """The silhouette of the partition `labels` (int32 [N]; a label outside 0..k-1 belongs to no cluster) of the bf16 rows
+        emb_bf16[N, d] under the distance 1 - x_i . x_j (mme_silhouette; enqueues and returns).  -> SilhouetteResult of CUDA
+        tensors, `samples` only when asked for.  The library validates N, d and k."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != dev:
+            raise MmeError("silhouette: emb must be a 2-D bfloat16 tensor on this engine's device")
+        N, d = e.shape
+        k = int(k)
+        if not hasattr(labels, "dtype") or labels.dtype != t.int32 or labels.dim() != 1 or labels.shape[0] != N or labels.device != dev:
+            raise MmeError(f"silhouette: labels must be an int32 tensor [N = {N}] on this engine's device")
+        lab = labels.contiguous()
+        kk = max(k, 1)
+        res = SilhouetteResult(score=t.zeros(1, dtype=t.float64, device=dev), cluster=t.zeros(kk, dtype=t.float64, device=dev)[:k],
+                               info=t.zeros(2, dtype=t.int64, device=dev), sums=t.zeros((kk, d), dtype=t.float64, device=dev)[:k],
+                               counts=t.zeros(kk, dtype=t.int32, device=dev)[:k],
+                               samples=t.zeros(max(N, 1), dtype=t.float64, device=dev)[:N] if samples else None)
+        out = _SilhouetteOut()
+        for f, v in (("sample", res.samples), ("cluster", res.cluster), ("score", res.score), ("info", res.info), ("sums", res.sums), ("counts", res.counts)):
+            setattr(out, f, None if v is None else int(v.data_ptr()))
+        self._check(self.lib.mme_silhouette(self.h, e.data_ptr(), N, d, lab.data_ptr(), k, C.byref(out), self._stream()), "mme_silhouette")
+        return res
+
+    def silhouette_rows(self, emb_bf16, labels, sums, counts, sample):
+        """The rows kernel of K16 alone on the caller's CUDA tensors (mme_silhouette_rows; enqueues): sample float64 [N] from
+        sums float64 [k, d] and counts int32 [k].  The library validates."""
+        N, d = emb_bf16.shape
+        self._check(self.lib.mme_silhouette_rows(self.h, self._ptr(emb_bf16), int(N), int(d), self._ptr(labels), int(counts.shape[0]), self._ptr(sums),
+                                                 self._ptr(counts), self._ptr(sample), self._stream()), "mme_silhouette_rows")
 
     def gemm_bench(self, M, N, K, epilogue=0, variant=0, iters=10):
         """(avg ms, TFLOP/s) for one GEMM shape on random data."""

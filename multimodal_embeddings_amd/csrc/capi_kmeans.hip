@@ -1,6 +1,7 @@
 // C ABI of K15 (include/mme.h, mme_kmeans*): argument checks and the host pass -- the cosine of a chunk of rows against the
 // centroids through the GEMM into the K12 workspace, kmeans_argmax_rows over it; the update's scratch sits in front of
 // that block.  Everything is enqueued at once: the iterations past convergence are switched off on the device.
+// At the end, K16 (mme_silhouette*): the update on given labels, silhouette_rows and the reductions (silhouette.hip).
 #include <algorithm>
 #include <cstdlib>
 
@@ -190,5 +191,77 @@ int mme_kmeans_apply(mme_ctx* c, int op, const mme_kmeans_apply_args* a, void* s
         }
     }
     HIP_TRY(c, hipStreamSynchronize(s));
+    return MME_OK;
+}
+
+// ---- K16: the silhouette of a partition (silhouette.hip) ----
+
+namespace {
+
+int check_silhouette_shape(mme_ctx* c, const char* who, int N, int d, int k) {
+    if (N < 2) return fail(c, MME_E_ARG, "%s: N = %d; at least two rows are required", who, N);
+    if (d <= 0 || (d % 64) != 0) return fail(c, MME_E_ARG, "%s: d = %d; d %% 64 == 0 is required", who, d);
+    if (k < 2 || k > 65536 || k > N) return fail(c, MME_E_ARG, "%s: k = %d is outside 2..min(N, 65536) (N = %d)", who, k, N);
+    return MME_OK;
+}
+
+}  // namespace
+
+int mme_silhouette(mme_ctx* c, const uint16_t* emb, int N, int d, const int32_t* labels, int k, const mme_silhouette_out* out, void* stream) {
+    if (!c) return MME_E_ARG;
+    const char* who = "mme_silhouette";
+    int r;
+    if (!out) return fail(c, MME_E_ARG, "%s: out is null", who);
+    if ((r = check_silhouette_shape(c, who, N, d, k))) return r;
+    if (!emb) return fail(c, MME_E_ARG, "%s: emb is null", who);
+    if (!labels) return fail(c, MME_E_ARG, "%s: labels is null", who);
+    if (!out->cluster) return fail(c, MME_E_ARG, "%s: out.cluster is null", who);
+    if (!out->score) return fail(c, MME_E_ARG, "%s: out.score is null", who);
+    if (!out->info) return fail(c, MME_E_ARG, "%s: out.info is null", who);
+    if (!out->sums) return fail(c, MME_E_ARG, "%s: out.sums is null", who);
+    if (!out->counts) return fail(c, MME_E_ARG, "%s: out.counts is null", who);
+    if (!aligned_to(emb, 16)) return fail(c, MME_E_ARG, "%s: emb must be 16-byte aligned", who);
+    if (!aligned_to(out->sums, 16)) return fail(c, MME_E_ARG, "%s: out.sums must be 16-byte aligned", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the head of the K12 workspace: the update's scratch, the centroids the update writes (the caller's are not ours to
+    // change), the samples when the caller wants none, and the clusters' sums
+    KmeansScratch sc{};
+    kmeans_plan(N, k, &sc.chunk, &sc.nchunks);
+    size_t total = 0;
+    auto carve = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_rank = carve((size_t)N * 4), o_order = carve((size_t)N * 4), o_start = carve((size_t)k * 4);
+    const size_t o_cnt = carve((size_t)sc.nchunks * k * 4), o_cen = carve((size_t)k * d * 2);
+    const size_t o_samp = carve(out->sample ? 0 : (size_t)N * 8), o_csum = carve((size_t)k * 8);
+    if ((r = ensure(c, c->neigh_ws, total))) return r;
+    char* ws = (char*)c->neigh_ws.p;
+    sc.rank = (int32_t*)(ws + o_rank);
+    sc.order = (int32_t*)(ws + o_order);
+    sc.start = (int32_t*)(ws + o_start);
+    sc.cnt = (int32_t*)(ws + o_cnt);
+    double* sample = out->sample ? out->sample : (double*)(ws + o_samp);
+    Timed t(c, s, KC_CLUSTER);
+    HIP_TRY(c, launch_kmeans_update(emb, labels, N, d, k, out->sums, out->counts, (uint16_t*)(ws + o_cen), sc, nullptr, s));
+    HIP_TRY(c, launch_silhouette_rows(emb, N, d, labels, k, out->sums, out->counts, sample, s));
+    HIP_TRY(c, launch_silhouette_reduce(sample, sc.order, sc.start, out->counts, k, (double*)(ws + o_csum), out->cluster, out->score,
+                                        (long long*)out->info, s));
+    return MME_OK;
+}
+
+int mme_silhouette_rows(mme_ctx* c, const uint16_t* emb, int N, int d, const int32_t* labels, int k, const double* sums, const int32_t* counts,
+                        double* sample, void* stream) {
+    if (!c) return MME_E_ARG;
+    const char* who = "mme_silhouette_rows";
+    int r;
+    if ((r = check_silhouette_shape(c, who, N, d, k))) return r;
+    if (!emb || !aligned_to(emb, 16)) return fail(c, MME_E_ARG, "%s: emb must be non-null and 16-byte aligned", who);
+    if (!labels) return fail(c, MME_E_ARG, "%s: labels is null", who);
+    if (!sums || !aligned_to(sums, 16)) return fail(c, MME_E_ARG, "%s: sums must be non-null and 16-byte aligned", who);
+    if (!counts) return fail(c, MME_E_ARG, "%s: counts is null", who);
+    if (!sample) return fail(c, MME_E_ARG, "%s: sample is null", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    Timed t(c, s, KC_CLUSTER);
+    HIP_TRY(c, launch_silhouette_rows(emb, N, d, labels, k, sums, counts, sample, s));
     return MME_OK;
 }

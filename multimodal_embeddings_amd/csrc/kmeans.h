@@ -36,3 +36,13 @@ hipError_t launch_kmeans_step_end(int* ctrl, long long* moved, const float* sim,
 hipError_t launch_kmeans_fill_labels(int32_t* labels, int N, hipStream_t s);
 // dst[j, :] = src[rows[j], :], bf16 rows of d (d % 8 == 0), j < k
 hipError_t launch_kmeans_gather_rows(const uint16_t* src, const int32_t* rows, int k, int d, uint16_t* dst, hipStream_t s);
+
+// K16, the silhouette of a partition (silhouette.hip).  sample[i] (f64 [N]) from the bf16 rows, their labels (outside 0..k-1:
+// NaN), and sums / counts as launch_kmeans_update leaves them; d % 64 == 0, emb and sums 16-byte aligned.
+hipError_t launch_silhouette_rows(const uint16_t* emb, int N, int d, const int32_t* label, int k, const double* sums, const int32_t* counts,
+                                  double* sample, hipStream_t s);
+// csum[j] = the samples of cluster j added in a fixed order over order[start[j] .. + counts[j]), cluster[j] = csum[j] / counts[j]
+// (NaN for an empty one); info = {rows counted, clusters with members}; score = the sum of csum over those rows, NaN with
+// fewer than two clusters with members.
+hipError_t launch_silhouette_reduce(const double* sample, const int32_t* order, const int32_t* start, const int32_t* counts, int k, double* csum,
+                                    double* cluster, double* score, long long* info, hipStream_t s);

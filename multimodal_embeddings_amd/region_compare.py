@@ -310,23 +310,59 @@ def _region_rows(collection, where):
     return all_entries, have
 
 
+def pick_n_clusters(scores):
+    """The number of clusters from {k: silhouette score or None}: the page side's rule (oracle/cluster.py, cluster_images).  k
+    ascending, the best score starting at -1 and the answer at the first k; a k is taken only when its score is strictly
+    above the best so far, and a k without a score (None or NaN) is skipped.  Pure: no GPU."""
+    ks = sorted(int(k) for k in scores)
+    if not ks:
+        raise ValueError("pick_n_clusters: no k to choose from")
+    best_score, best_k = -1, ks[0]
+    by_int = {int(k): v for k, v in scores.items()}
+    for k in ks:
+        v = by_int[k]
+        if v is None or v != v:
+            continue
+        if v > best_score:
+            best_score, best_k = v, k
+    return best_k
+
+
+def _clip_k_range(k_range, n):
+    ks = sorted({int(k) for k in k_range if 2 <= int(k) <= n})
+    if not ks:
+        raise ValueError(f"k_range holds no k in 2..{n} (the number of regions)")
+    return ks
+
+
+def _score_or_none(v):
+    v = float(v)
+    return None if v != v else v
+
+
 def cluster_regions(collection, n_clusters, *, where={"is_region": {"$eq": True}}, init="k-means++", seed=0, n_init=1, max_iter=100,
-                    engine: Engine | None = None, max_members=None):
+                    engine: Engine | None = None, max_members=None, k_range=range(2, 11), silhouette=False):
     """n_clusters groups of look-alike regions: spherical k-means (kernel K15) over the unit bf16 vectors of the rows `where`
     selects (rows without an embedding left out).  Returns cluster_table's dict; kmeans_regions also returns the arrays
     (the centroids among them, which assign_regions takes).
 
     init: kmeans_init_rows' forms; run r of n_init uses seed + r, and the run with the largest objective (the sum of the
-    rows' cosines to their centroids) is kept, the first among equals."""
+    rows' cosines to their centroids) is kept, the first among equals.
+
+    n_clusters = None (given explicitly: the argument keeps no default) chooses it: every k of k_range (clipped to 2..the number of regions) gets such a run and one silhouette
+    (kernel K16) of the run kept; pick_n_clusters decides, and the table of that k comes back with "k_scores" ({k: score or
+    None}), "silhouette" (the picked k's score) and a "silhouette" entry in each cluster (its mean, None for an empty one).
+    With a given n_clusters those keys appear only under silhouette=True."""
     table, _ = kmeans_regions(collection, n_clusters, where=where, init=init, seed=seed, n_init=n_init, max_iter=max_iter, engine=engine,
-                              max_members=max_members)
+                              max_members=max_members, k_range=k_range, silhouette=silhouette)
     return table
 
 
 def kmeans_regions(collection, n_clusters, *, where={"is_region": {"$eq": True}}, init="k-means++", seed=0, n_init=1, max_iter=100,
-                   engine: Engine | None = None, max_members=None):
+                   engine: Engine | None = None, max_members=None, k_range=range(2, 11), silhouette=False, silhouette_samples=False):
     """cluster_regions, returning (table, arrays): arrays = {"ids", "labels", "sim", "centroids" (bf16 CUDA tensor), "counts",
-    "objectives" (one per run), "best_run"} or None without regions."""
+    "objectives" (one per run), "best_run"} or None without regions; with n_clusters = None also "by_k" ({k: {"labels",
+    "objectives", "best_run", "silhouette"}}), and under silhouette_samples=True "silhouette_samples" (float64 [n])."""
     if int(n_init) < 1:
         raise ValueError(f"n_init = {n_init} must be at least 1")
     if int(max_iter) < 0 or int(max_iter) > 1000:
@@ -337,24 +373,76 @@ def kmeans_regions(collection, n_clusters, *, where={"is_region": {"$eq": True}}
         return cluster_table([], [], [], [], n_clusters=0), None
     ids = [all_entries["ids"][r] for r in have]
     metas = [all_entries["metadatas"][r] for r in have]
-    if int(n_clusters) < 1 or int(n_clusters) > len(ids):
-        raise ValueError(f"n_clusters = {n_clusters} must lie in 1..{len(ids)} (the number of regions)")
+    choose = n_clusters is None
+    if choose:
+        ks = _clip_k_range(k_range, len(ids))
+    else:
+        if int(n_clusters) < 1 or int(n_clusters) > len(ids):
+            raise ValueError(f"n_clusters = {n_clusters} must lie in 1..{len(ids)} (the number of regions)")
+        ks = [int(n_clusters)]
     engine = engine or default_engine()
-    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
-    best, objectives, best_run = None, [], 0
-    for run in range(int(n_init)):
-        rows = kmeans_init_rows(emb, n_clusters, init, int(seed) + run)
-        res = engine.kmeans(emb, int(n_clusters), init_rows=rows, max_iter=int(max_iter))
-        obj = float(res.objective.item())
-        objectives.append(obj)
-        if best is None or obj > objectives[best_run]:
-            best, best_run = res, run
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)  # one upload for every k
+    want_sil = choose or bool(silhouette) or bool(silhouette_samples)
+    runs = {}
+    for k in ks:
+        best, objectives, best_run = None, [], 0
+        for run in range(int(n_init)):
+            rows = kmeans_init_rows(emb, k, init, int(seed) + run)
+            res = engine.kmeans(emb, k, init_rows=rows, max_iter=int(max_iter))
+            obj = float(res.objective.item())
+            objectives.append(obj)
+            if best is None or obj > objectives[best_run]:
+                best, best_run = res, run
+        sil = engine.silhouette(emb, best.labels, k, samples=bool(silhouette_samples)) if want_sil else None
+        runs[k] = (best, objectives, best_run, sil)
+    k_scores = {k: _score_or_none(r[3].score.item()) for k, r in runs.items()} if want_sil else None
+    k = pick_n_clusters(k_scores) if choose else ks[0]
+    best, objectives, best_run, sil = runs[k]
     info = best.info.cpu().numpy()
     labels, sim = best.labels.cpu().numpy(), best.sim.cpu().numpy()
-    table = cluster_table(labels, sim, ids, metas, n_clusters=int(n_clusters), iterations=int(info[0]), converged=bool(info[2]),
+    table = cluster_table(labels, sim, ids, metas, n_clusters=k, iterations=int(info[0]), converged=bool(info[2]),
                           objective=objectives[best_run], max_members=max_members)
-    return table, {"ids": ids, "labels": labels, "sim": sim, "centroids": best.centroids, "counts": best.counts.cpu().numpy(),
-                   "objectives": objectives, "best_run": best_run}
+    arrays = {"ids": ids, "labels": labels, "sim": sim, "centroids": best.centroids, "counts": best.counts.cpu().numpy(),
+              "objectives": objectives, "best_run": best_run}
+    if want_sil:
+        table["k_scores"] = k_scores
+        table["silhouette"] = k_scores[k]
+        for c, v in zip(table["clusters"], sil.cluster.cpu().numpy()):
+            c["silhouette"] = _score_or_none(v)
+        if silhouette_samples:
+            arrays["silhouette_samples"] = sil.samples.cpu().numpy()
+    if choose:
+        arrays["by_k"] = {kk: {"labels": r[0].labels.cpu().numpy(), "objectives": r[1], "best_run": r[2], "silhouette": k_scores[kk]}
+                          for kk, r in runs.items()}
+    return table, arrays
+
+
+def silhouette_regions(collection, labels, *, where={"is_region": {"$eq": True}}, engine: Engine | None = None):
+    """The silhouette (kernel K16) of labels the caller already has -- assign_regions' output, say -- one per row `where` selects
+    (rows without an embedding left out), in the collection's order; a negative label belongs to no cluster.  Returns
+    {"n_regions", "n_clusters", "silhouette", "clusters": [{"cluster", "size", "silhouette": mean or None}], "samples": [per
+    row, None for a row of no cluster]}.  ValueError when fewer than two clusters have members."""
+    all_entries, have = _region_rows(collection, where)
+    labels = np.asarray(labels).reshape(-1)
+    if len(labels) != len(have):
+        raise ValueError(f"silhouette_regions: {len(labels)} labels for {len(have)} regions")
+    if not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("silhouette_regions: labels must be integers")
+    n = len(have)
+    k = max(int(labels.max()) + 1 if n else 0, 2)
+    members = len(np.unique(labels[labels >= 0]))
+    if members < 2 or n < 2:
+        raise ValueError(f"silhouette_regions: {members} cluster(s) have members; a silhouette needs at least two")
+    engine = engine or default_engine()
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
+    lab = engine.torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(emb.device)
+    res = engine.silhouette(emb, lab, k, samples=True)
+    if int(res.info[1].item()) < 2:
+        raise ValueError(f"silhouette_regions: {int(res.info[1].item())} cluster(s) have members; a silhouette needs at least two")
+    counts = res.counts.cpu().numpy()
+    return {"n_regions": n, "n_clusters": k, "silhouette": _score_or_none(res.score.item()),
+            "clusters": [{"cluster": j, "size": int(counts[j]), "silhouette": _score_or_none(v)} for j, v in enumerate(res.cluster.cpu().numpy())],
+            "samples": [_score_or_none(v) for v in res.samples.cpu().numpy()]}
 
 
 def assign_regions(centroids, embeddings, *, engine: Engine | None = None):
@@ -374,7 +462,8 @@ def assign_regions(centroids, embeddings, *, engine: Engine | None = None):
 
 
 def create_region_cluster_report(collection, n_clusters, output_path=None, **kwargs):
-    """cluster_regions, written as one JSON document when `output_path` is given (as create_duplicate_report)."""
+    """cluster_regions (its keywords passed through: n_clusters = None chooses k over k_range by silhouette), written as one
+    JSON document when `output_path` is given (as create_duplicate_report)."""
     result = cluster_regions(collection, n_clusters, **kwargs)
     if output_path:
         os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
