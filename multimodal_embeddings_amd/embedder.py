@@ -30,6 +30,7 @@ import numpy as np
 
 from . import config
 from ._lib import Engine, MmeError, lanczos_geometry_ok, lanczos_workspace  # noqa: F401
+from .staging import ResultRing, Stage, _Null, current_stream, new_event, new_stream, on, packed_layout  # noqa: F401
 from .weights import TILE_VIT
 
 logger = logging.getLogger("multimodal_embeddings_amd")
@@ -137,17 +138,39 @@ def _load_for_device(item):
     return _load_rgb(image)
 
 
-class _Null:
-    """Stream / event stand-in where there is no device (host-logic tests): every ordering call is a no-op."""
+def _load_item(pair):
+    """(index, item) -> (index, decoded item | None): an item that cannot be read is logged and becomes a hole."""
+    i, item = pair
+    try:
+        return i, _load_for_device(item)  # looked up per call: tools swap the loader at module level
+    except Exception as e:  # embedder.py:135-137
+        logger.error(f"Error processing image {item if isinstance(item, (str, os.PathLike)) else type(item)}: {e}")
+        return i, None
 
-    def wait_event(self, *_):
-        pass
 
-    def record(self, *_):
-        pass
-
-    def synchronize(self):
-        pass
+def _decoded_groups(items, step, group_bytes):
+    """The front end of both embed paths: [(index, item)] in parts of `step` items, each decoded and cut into groups of at
+    most `group_bytes` of pixels.  Yields per part (indices that failed to load, [[(index, decoded item)]])."""
+    for g0 in range(0, len(items), step):
+        part = items[g0 : g0 + step]
+        # PNG decode is the slow part of a call and Pillow releases the GIL while decoding
+        if len(part) > 4 and not all(isinstance(it, np.ndarray) for _, it in part):
+            with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1, len(part))) as pool:
+                loaded = list(pool.map(_load_item, part))
+        else:
+            loaded = [_load_item(pr) for pr in part]
+        groups, group, nbytes = [], [], 0
+        for i, a in loaded:
+            if a is None:
+                continue
+            if group and nbytes + a.nbytes > group_bytes:
+                groups.append(group)
+                group, nbytes = [], 0
+            group.append((i, a))
+            nbytes += a.nbytes
+        if group:
+            groups.append(group)
+        yield [i for i, a in loaded if a is None], groups
 
 
 class RegionEmbedder:
@@ -285,7 +308,6 @@ class RegionEmbedder:
         self.pool_token = 0 if pool == "cls" else (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1)
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
         self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
-        self._group_crops = 16 * config.BATCH_SIZE
         self._seed = seed
         self._tokenizer = tokenizer
         self._text_source = text_tower  # None: look in model_name on first use; False: never
@@ -301,41 +323,12 @@ class RegionEmbedder:
         device = self.device if device is None else device
         n = len(arrays)
         hw = np.array([a.shape[:2] for a in arrays], dtype=np.int32).reshape(n, 2)
-        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
-        offs = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            offs[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
-        total = int(offs[-1] + sizes[-1]) + 16 if n else 16
+        offs, sizes, total = packed_layout(hw)
         host = t.empty(total, dtype=t.uint8, pin_memory=t.cuda.is_available())
         hv = host.numpy()
         for a, o, s in zip(arrays, offs, sizes):
             hv[o : o + s] = a.reshape(-1)
         return host.to(device, non_blocking=True), offs, hw
-
-    def _pack_mixed(self, arrays, device):
-        """`pack` for a list that may hold device crops (uint8 CUDA tensors [h, w, 3], the capped oversized items of the serial
-        path) beside host arrays: the host arrays travel as `pack` sends them, the device crops are copied into their places."""
-        t = self.torch
-        if not any(isinstance(a, t.Tensor) for a in arrays):
-            return self.pack(arrays, device)
-        hosts = [a if not isinstance(a, t.Tensor) else np.empty((0,) + tuple(a.shape[1:]), dtype=np.uint8) for a in arrays]
-        n = len(arrays)
-        hw = np.array([a.shape[:2] for a in arrays], dtype=np.int32).reshape(n, 2)
-        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
-        offs = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            offs[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
-        total = int(offs[-1] + sizes[-1]) + 16
-        host = t.empty(total, dtype=t.uint8, pin_memory=t.cuda.is_available())
-        hv = host.numpy()
-        for a, o, s in zip(hosts, offs, sizes):
-            if a.shape[0]:
-                hv[o : o + s] = a.reshape(-1)
-        pix = host.to(device, non_blocking=True)
-        for a, o, s in zip(arrays, offs, sizes):
-            if isinstance(a, t.Tensor):
-                pix[int(o) : int(o + s)].copy_(a.reshape(-1))
-        return pix, offs, hw
 
     def embed_packed(self, pix, offs, hw, want_f32=True, want_bf16=True):
         """Packed crops already in HBM -> (f32 [n, embed_dim], bf16 [n, embed_dim]) CUDA tensors."""
@@ -364,47 +357,30 @@ class RegionEmbedder:
 
     # -- reference surface ------------------------------------------------------------------------
     def _pipe_state(self, dev_idx):
-        """Per-context staging of the host <-> device pipeline of `_embed_list`: two slots, each a pinned input buffer, its
-        device twin and a pinned result buffer (grown on demand, kept), two copy streams (the H2D and D2H engines run
-        side by side) and the events that order them against the compute stream."""
+        """Per-context staging of the host <-> device pipeline of `_embed_list`: two slots, each a pinned input buffer and its
+        device twin (grown on demand, kept), a copy stream for the H2D, the result ring with the D2H stream (the two copy
+        engines run side by side) and the events that order them against the compute stream.  The host-logic tests drive
+        the pipeline with a stand-in engine and no device: streams and events are then staging's no-ops."""
         st = self.__dict__.setdefault("_pipes", {})  # atomic: contexts are driven from one thread each, concurrently
         if dev_idx not in st:
-            t = self.torch
-            dev = t.device(self.devices[dev_idx])
-            if dev.type != "cuda":  # the host-logic tests drive this pipeline with a stand-in engine and no device
-                mk_stream = mk_event = _Null
-            else:
-                mk_stream, mk_event = (lambda: t.cuda.Stream(dev)), t.cuda.Event
-            with self._on(dev):
+            dev = self.torch.device(self.devices[dev_idx])
+            with on(dev):
                 st[dev_idx] = {
-                    "in_stream": mk_stream(), "out_stream": mk_stream(), "compute": None if dev.type == "cuda" else _Null(),
-                    "pin": [None, None], "dev": [None, None], "out": [None, None], "pinned": dev.type == "cuda",
+                    "in_stream": new_stream(dev), "ring": ResultRing(dev, 256),
+                    "pin": [None, None], "dev": [None, None], "pinned": dev.type == "cuda",
                     "used": [False, False],  # a slot's events mean something once it has been staged, in ANY earlier call
-                    "ev_in": [mk_event(), mk_event()], "ev_done": [mk_event(), mk_event()], "ev_out": [mk_event(), mk_event()],
+                    "ev_in": [new_event(dev), new_event(dev)], "ev_done": [new_event(dev), new_event(dev)],
                 }
         return st[dev_idx]
 
-    def _on(self, dev, stream=None):
-        """Context manager: `dev` current (and `stream` current on it); nothing to do without a device."""
-        import contextlib
-
-        t = self.torch
-        if dev.type != "cuda":
-            return contextlib.nullcontext()
-        return t.cuda.stream(stream) if stream is not None else t.cuda.device(dev)
-
     def _stage_group(self, pipe, slot, arrays, device):
-        """Pack decoded crops into the slot's pinned buffer (16-byte aligned, as `pack`) and start their H2D copy on the
+        """Pack decoded crops into the slot's pinned buffer (`packed_layout`, as `pack`) and start their H2D copy on the
         input stream.  Returns (device pixels, offs, hw, cap jobs).  The slot's previous occupants are out of the way: the caller
         acquired the slot after the consumer recorded `ev_done[slot]` (the pass that read the device twin)."""
         t = self.torch
         n = len(arrays)
         hw = np.array([a.shape[:2] for a in arrays], dtype=np.int32).reshape(n, 2)
-        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
-        offs = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            offs[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
-        total = int(offs[-1] + sizes[-1]) + 16
+        offs, sizes, total = packed_layout(hw)
         # An oversized item (_Oversized): `offs` / `hw` point at its CAPPED image, a hole the consumer thread fills on the
         # device; its raw pixels ride behind the crops (host and device buffer), its workspace behind those (device only).
         jobs, srcs = [], []  # jobs: (raw offset, h, w, new_h, new_w, capped offset, workspace offset, workspace bytes)
@@ -447,7 +423,7 @@ class RegionEmbedder:
                 list(pool.map(lambda ab: copy_range(*ab), zip(bounds[:-1], bounds[1:])))
         else:
             copy_range(0, n)
-        with self._on(device, pipe["in_stream"]):
+        with on(device, pipe["in_stream"]):
             if not first_use:
                 pipe["in_stream"].wait_event(pipe["ev_done"][slot])  # the pass that read the device twin has run
             pipe["dev"][slot][:total].copy_(pipe["pin"][slot][:total], non_blocking=True)
@@ -462,158 +438,83 @@ class RegionEmbedder:
         for at, h, w, nh, nw, dst, work, work_bytes in jobs:
             engine.lanczos_resize(pix[at : at + h * w * 3].view(h, w, 3), nh, nw, out=pix[dst : dst + nh * nw * 3], work=pix[work : work + work_bytes])
 
-    def _embed_list(self, dev_idx, items):
-        """One context's share of a call: [(index, item)] -> [(index, list[float] | None)] (embedder.py:86-139).
+    def _embed_list(self, dev_idx, items, step, as_array=False, sink=None):
+        """One context's share of a call: [(index, item)] -> [(index, list[float] | None)] (embedder.py:86-139); float32
+        ndarray rows under `as_array`; `sink`: see `_pass`.
 
-        The items go through in bounded groups -- at most 16 x batch_size crops and GROUP_BYTES of packed pixels per
+        The items go through in bounded groups -- at most `step` (16 x batch_size) crops and GROUP_BYTES of packed pixels per
         `mme_embed` call -- each decoded, packed and embedded inside its own try/except: a failure (an unreadable
         file, an out-of-memory MmeError) voids only what it touched.
 
         The reference runs open -> processor -> forward -> `.cpu().tolist()` strictly in series per image
         (embedder.py:104-137).  Here the host side of group g + 1 (decode on a thread pool, packing into a pinned
         buffer, H2D on a copy stream) runs on a producer thread UNDER the device pass of group g, and the D2H of group
-        g plus the float lists of group g - 1 behind it: two staging slots, three streams, events between them."""
-        if getattr(self, "encoder", "vit_b16") == "mllama_tiles":
-            return self._embed_list_serial(dev_idx, items)
-        import queue
-        import threading
-
-        t = self.torch
+        g plus the float lists of group g - 1 behind it: two staging slots, three streams, events between them
+        (staging.Stage and staging.ResultRing)."""
+        if self.encoder == "mllama_tiles":
+            return self._embed_list_serial(dev_idx, items, step)
         engine = self.engines[dev_idx]
-        device = t.device(self.devices[dev_idx])
+        device = self.torch.device(self.devices[dev_idx])
         pipe = self._pipe_state(dev_idx)
         results = []
-        step = max(1, int(self._group_crops))
-        ready = queue.Queue(maxsize=2)
-        slot_free = [threading.Semaphore(1), threading.Semaphore(1)]
-        stop = threading.Event()
 
-        def load(pair):
-            i, item = pair
-            try:
-                return i, _load_for_device(item)
-            except Exception as e:  # embedder.py:135-137
-                logger.error(f"Error processing image {item if isinstance(item, (str, os.PathLike)) else type(item)}: {e}")
-                return i, None
-
-        def produce():
+        def produce(stage):  # decode, host copies and H2D on the input stream: no engine call on this thread
             g = 0
-            try:
-                with self._on(device):
-                    for g0 in range(0, len(items), step):
-                        part = items[g0 : g0 + step]
-                        # PNG decode is the slow part of a call and Pillow releases the GIL while decoding
-                        if len(part) > 4 and not all(isinstance(it, np.ndarray) for _, it in part):
-                            with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1, len(part))) as pool:
-                                loaded = list(pool.map(load, part))
-                        else:
-                            loaded = [load(pr) for pr in part]
-                        failed = [i for i, a in loaded if a is None]
-                        groups, group, nbytes = [], [], 0
-                        for i, a in loaded:
-                            if a is None:
-                                continue
-                            if group and nbytes + a.nbytes > self.GROUP_BYTES:
-                                groups.append(group)
-                                group, nbytes = [], 0
-                            group.append((i, a))
-                            nbytes += a.nbytes
-                        if group:
-                            groups.append(group)
-                        if failed:
-                            ready.put(("failed", failed))
-                        for group in groups:
-                            slot = g & 1
-                            while not slot_free[slot].acquire(timeout=0.1):
-                                if stop.is_set():
-                                    return
-                            try:
-                                staged = self._stage_group(pipe, slot, [a for _, a in group], device)
-                                ready.put(("group", slot, [i for i, _ in group], staged))
-                            except Exception as e:  # embedder.py:223-224
-                                logger.error(f"Error in batch processing: {e}")
-                                slot_free[slot].release()
-                                ready.put(("failed", [i for i, _ in group]))
-                                continue
-                            g += 1
-            except BaseException as e:  # never leave the consumer waiting
-                logger.error(f"Error in batch processing: {e}")
-            finally:
-                ready.put(("end",))
+            with on(device):
+                for failed, groups in _decoded_groups(items, step, self.GROUP_BYTES):
+                    if failed:
+                        stage.put(("failed", failed))
+                    for group in groups:
+                        slot = g & 1
+                        if not stage.acquire(slot):
+                            return
+                        try:
+                            staged = self._stage_group(pipe, slot, [a for _, a in group], device)
+                        except Exception as e:  # embedder.py:223-224
+                            logger.error(f"Error in batch processing: {e}")
+                            stage.release(slot)
+                            stage.put(("failed", [i for i, _ in group]))
+                            continue
+                        stage.put(("group", slot, [i for i, _ in group], staged))
+                        g += 1
 
-        pending = None  # (slot, indices, n, device result kept alive) whose D2H is in flight
-
-        def finalize(p):
-            slot, idx, n, _keep = p
-            pipe["ev_out"][slot].synchronize()
-            if getattr(self, "_rows_as_array", False):
-                rows = list(pipe["out"][slot][:n].numpy().copy())  # float32 row views (get_image_embeddings(as_array=True))
+        def finalize(idx, rows):
+            if as_array:
+                rows = list(rows.copy())  # float32 rows (get_image_embeddings(as_array=True))
             else:
                 # embedder.py:132 `.cpu().tolist()`.  In slices: one tolist() of a whole group holds the GIL for tens of
                 # milliseconds, during which the producer thread cannot even start its next (GIL-free) buffer copy
-                buf, rows = pipe["out"][slot], []
-                for c0 in range(0, n, 64):
-                    rows.extend(buf[c0 : min(n, c0 + 64)].tolist())
+                rows = [row for c0 in range(0, len(rows), 64) for row in rows[c0 : c0 + 64].tolist()]
             results.extend(zip(idx, rows))
 
-        producer = threading.Thread(target=produce, name=f"mme-stage-{dev_idx}", daemon=True)
-        producer.start()
-        try:
-            with self._on(device):
-                compute = pipe["compute"] or t.cuda.current_stream(device)
-                while True:
-                    msg = ready.get()
-                    if msg[0] == "end":
-                        break
-                    if msg[0] == "failed":
-                        results.extend((i, None) for i in msg[1])
-                        continue
-                    _, slot, idx, (pix, offs, hw, jobs) = msg
-                    n = len(idx)
-                    try:
-                        compute.wait_event(pipe["ev_in"][slot])
-                        self._run_cap_jobs(engine, pix, jobs)  # this thread, the compute stream: ordered before the pass
-                        e32 = self._pass(engine, pix, offs, hw, idx)
-                        pipe["ev_done"][slot].record(compute)
-                    except Exception as e:  # embedder.py:223-224
-                        logger.error(f"Error in batch processing: {e}")
-                        pipe["ev_done"][slot].record(compute)
-                        slot_free[slot].release()
-                        results.extend((i, None) for i in idx)
-                        continue
-                    slot_free[slot].release()  # the producer may refill the slot: its H2D waits for ev_done on the device
-                    if pending is not None and pending[0] == slot:
-                        finalize(pending)  # the result buffer of this slot is about to be reused
-                        pending = None
-                    if pipe["out"][slot] is None or pipe["out"][slot].shape[0] < n or pipe["out"][slot].shape[1] != e32.shape[1]:
-                        pipe["out"][slot] = t.empty((max(n, 256), e32.shape[1]), dtype=t.float32, pin_memory=pipe["pinned"])
-                    with self._on(device, pipe["out_stream"]):
-                        pipe["out_stream"].wait_event(pipe["ev_done"][slot])
-                        pipe["out"][slot][:n].copy_(e32, non_blocking=True)
-                        pipe["ev_out"][slot].record(pipe["out_stream"])
-                    if pending is not None:
-                        finalize(pending)  # float lists of the previous group, under this group's device pass
-                    pending = (slot, idx, n, e32)
-                if pending is not None:
-                    finalize(pending)
-        except BaseException:
-            if device.type == "cuda":  # leave nothing in flight on the staging buffers the next call will reuse
-                t.cuda.synchronize(device)
-            raise
-        finally:
-            stop.set()
-            while producer.is_alive():  # drain so that a blocked put() returns
+        ring = pipe["ring"]
+        ring.start(finalize)
+        with Stage(f"mme-stage-{dev_idx}", produce, 2, device, logger) as stage, on(device):
+            compute = current_stream(device)
+            for msg in iter(stage.get, None):
+                if msg[0] == "failed":
+                    results.extend((i, None) for i in msg[1])
+                    continue
+                _, slot, idx, (pix, offs, hw, jobs) = msg
                 try:
-                    ready.get(timeout=0.05)
-                except queue.Empty:
-                    pass
-            producer.join()
+                    compute.wait_event(pipe["ev_in"][slot])
+                    self._run_cap_jobs(engine, pix, jobs)  # this thread, the compute stream: ordered before the pass
+                    e32 = self._pass(engine, pix, offs, hw, idx, sink)
+                except Exception as e:  # embedder.py:223-224
+                    logger.error(f"Error in batch processing: {e}")
+                    e32 = None
+                pipe["ev_done"][slot].record(compute)
+                stage.release(slot)  # the producer may refill the slot: its H2D waits for ev_done on the device
+                if e32 is None:
+                    results.extend((i, None) for i in idx)
+                else:  # D2H behind the pass; the float lists of the previous group under this group's device pass
+                    ring.submit(e32, pipe["ev_done"][slot], idx)
+            ring.finish()
         return results
 
-    def _pass(self, engine, pix, offs, hw, idx):
-        """The device pass of one packed group -> f32 [n, embed_dim].  Under get_patch_embeddings the same pass also returns the
-        patch-token rows (mme_embed_tokens; its pooled rows are mme_embed's bit for bit), which go to rows `idx` of the sink."""
-        sink = getattr(self, "_token_sink", None)
+    def _pass(self, engine, pix, offs, hw, idx, sink=None):
+        """The device pass of one packed group -> f32 [n, embed_dim].  With a `sink` (get_patch_embeddings) the same pass also returns
+        the patch-token rows (mme_embed_tokens; its pooled rows are mme_embed's bit for bit), which go to rows `idx` of the sink."""
         if sink is None:
             e32, _ = engine.embed(pix, offs, hw, self.pool_token, want_bf16=False)
             return e32
@@ -627,64 +528,33 @@ class RegionEmbedder:
             sink.index_copy_(0, rows.to(sink.device), tokens.to(sink.device))
         return e32
 
-    def _embed_list_serial(self, dev_idx, items):
-        """The unpipelined form (decode -> pack -> pass -> lists per group), used by the tile-ViT option."""
+    def _embed_list_serial(self, dev_idx, items, step):
+        """The unpipelined form of `_embed_list` for the tile-ViT option: decode -> stage -> cap -> pass -> lists per group of at
+        most TILE_GROUP_CROPS crops, all on the calling thread, through the first staging slot of the context."""
         engine = self.engines[dev_idx]
         device = self.torch.device(self.devices[dev_idx])
+        pipe = self._pipe_state(dev_idx)
         results = []
-
-        def load(pair):
-            i, item = pair
-            try:
-                return i, _load_for_device(item)
-            except Exception as e:  # embedder.py:135-137
-                logger.error(f"Error processing image {item if isinstance(item, (str, os.PathLike)) else type(item)}: {e}")
-                return i, None
-
-        def cap(a):  # an oversized RGB item is shrunk on the device, by this thread, before it is packed with the others
-            if not isinstance(a, _Oversized):
-                return a
-            with self._on(device):
-                raw = self.torch.from_numpy(a.raw).to(device)
-                return engine.lanczos_resize(raw, a.new_h, a.new_w)
-
-        def run(group):
-            if not group:
-                return
-            try:
-                pix, offs, hw = self._pack_mixed([cap(a) for _, a in group], device)
-                if getattr(self, "encoder", "vit_b16") == "mllama_tiles":  # processor (K1 multi-tile) + vision tower, class token of tile 0 (7680-d)
-                    pv, ids, _, nt = engine.preprocess_tiles(pix, offs, hw, 560, 4)
-                    _, e32, _ = engine.tile_vit_forward(pv, ids, nt, want_bf16=False)
-                else:
-                    e32 = self._pass(engine, pix, offs, hw, [i for i, _ in group])
-                rows = e32.cpu().tolist()
-                results.extend((i, row) for (i, _), row in zip(group, rows))
-            except Exception as e:  # embedder.py:223-224
-                logger.error(f"Error in batch processing: {e}")
-                results.extend((i, None) for i, _ in group)
-
-        step = max(1, int(self._group_crops))
-        if getattr(self, "encoder", "vit_b16") == "mllama_tiles":
-            step = min(step, self.TILE_GROUP_CROPS)
-        for g0 in range(0, len(items), step):
-            part = items[g0 : g0 + step]
-            if len(part) > 4:
-                with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1, len(part))) as pool:
-                    loaded = list(pool.map(load, part))
-            else:
-                loaded = [load(pr) for pr in part]
-            group, nbytes = [], 0
-            for i, a in loaded:
-                if a is None:
-                    results.append((i, None))
-                    continue
-                if group and nbytes + a.nbytes > self.GROUP_BYTES:
-                    run(group)
-                    group, nbytes = [], 0
-                group.append((i, a))
-                nbytes += a.nbytes
-            run(group)
+        with on(device):
+            compute = current_stream(device)
+            for failed, groups in _decoded_groups(items, min(step, self.TILE_GROUP_CROPS), self.GROUP_BYTES):
+                results.extend((i, None) for i in failed)
+                for group in groups:
+                    idx = [i for i, _ in group]
+                    try:
+                        pix, offs, hw, jobs = self._stage_group(pipe, 0, [a for _, a in group], device)
+                        try:
+                            compute.wait_event(pipe["ev_in"][0])
+                            self._run_cap_jobs(engine, pix, jobs)
+                            # processor (K1 multi-tile) + vision tower, class token of tile 0 (7680-d)
+                            pv, ids, _, nt = engine.preprocess_tiles(pix, offs, hw, 560, 4)
+                            _, e32, _ = engine.tile_vit_forward(pv, ids, nt, want_bf16=False)
+                        finally:
+                            pipe["ev_done"][0].record(compute)  # the next group's H2D into the slot waits for this
+                        results.extend(zip(idx, e32.cpu().tolist()))
+                    except Exception as e:  # embedder.py:223-224
+                        logger.error(f"Error in batch processing: {e}")
+                        results.extend((i, None) for i in idx)
         return results
 
     def get_image_embeddings(self, image_paths, is_query=False, batch_size=config.BATCH_SIZE, *, as_array=False):
@@ -697,10 +567,13 @@ class RegionEmbedder:
         thread (:208-224); a single query image takes the first context without the pool (:158-185).
         `batch_size` keeps the reference's meaning "images per GPU per batch", except that a device pass here
         carries 16 of the reference's one-image forwards per unit of it (256 crops at the default 16)."""
+        return self._embed_all(image_paths, is_query, batch_size, bool(as_array), None)
+
+    def _embed_all(self, image_paths, is_query, batch_size, as_array, sink):
+        """get_image_embeddings; with a `sink` the passes also leave their patch tokens there (get_patch_embeddings, `_pass`)."""
         if not image_paths:
             return (np.zeros((0, getattr(self, "embed_dim", config.EMBED_DIM)), dtype=np.float32), np.zeros(0, dtype=bool)) if as_array else []
-        self._rows_as_array = bool(as_array) and getattr(self, "encoder", "vit_b16") != "mllama_tiles"
-        self._group_crops = 16 * max(1, int(batch_size))
+        step = 16 * max(1, int(batch_size))
         embeddings = [None] * len(image_paths)
         n_dev = len(self.engines)
         if n_dev == 1 or (len(image_paths) == 1 and is_query):
@@ -708,10 +581,10 @@ class RegionEmbedder:
         else:
             shares = [[(i, p) for i, p in enumerate(image_paths) if i % n_dev == d] for d in range(n_dev)]
         if len(shares) == 1:
-            done = [self._embed_list(0, shares[0])]
+            done = [self._embed_list(0, shares[0], step, as_array, sink)]
         else:
             with ThreadPoolExecutor(max_workers=n_dev) as pool:
-                done = list(pool.map(lambda d: self._embed_list(d, shares[d]), range(n_dev)))
+                done = list(pool.map(lambda d: self._embed_list(d, shares[d], step, as_array, sink), range(n_dev)))
         for part in done:
             for i, row in part:
                 embeddings[i] = row
@@ -735,7 +608,7 @@ class RegionEmbedder:
 
         Size: n * ntok * hidden * 2 bytes -- 301 KB per ViT-B/16 crop, 19.7 GB at 65 536 crops; pass `out` to place it, or call in
         slices.  Not available for encoder="mllama_tiles" (the tile tower's 4 x 1601 tokens of 1280 are another object)."""
-        if getattr(self, "encoder", "vit_b16") == "mllama_tiles":
+        if self.encoder == "mllama_tiles":
             raise NotImplementedError("get_patch_embeddings: encoder 'mllama_tiles'; supported: the single-tile image towers "
                                       "(vit, clip, siglip_vit, dinov2)")
         t = self.torch
@@ -750,11 +623,9 @@ class RegionEmbedder:
                 raise ValueError(f"get_patch_embeddings: `out` must be a contiguous bfloat16 CUDA tensor {list(shape)}")
             out.zero_()
         t.cuda.synchronize(out.device)  # the zeros are in place before any context's stream writes a block
-        self._token_sink = out
         try:
-            vectors = self.get_image_embeddings(images, batch_size=batch_size)
+            vectors = self._embed_all(images, False, batch_size, False, out)
         finally:
-            self._token_sink = None
             for d in self.devices:
                 t.cuda.synchronize(t.device(d))
         return vectors, out
@@ -778,10 +649,10 @@ class RegionEmbedder:
 
         src = getattr(self, "_text_source", False)
         eng = self.engines[0]
-        if getattr(self, "encoder", None) == "dinov2":
+        if self.encoder == "dinov2":
             raise NotImplementedError("text embeddings: a DINOv2 tower is trained on images alone and has no text tower; " + self._NO_TOWER)
         # (a CLIP text tower embeds into another space than a SigLIP image tower)
-        siglip = getattr(self, "encoder", None) == "siglip"
+        siglip = self.encoder == "siglip"
         kind, no_tower = ("siglip_text", self._NO_SIGLIP_TOWER) if siglip else ("clip_text", self._NO_TOWER)
         rec = ENCODER_TABLE[kind]
         if src is False:

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import config
 from ._lib import MmeError
+from .staging import ResultRing, Stage, current_stream, new_event, new_stream, on, packed_bytes
 
 logger = logging.getLogger(__name__)
 
@@ -213,19 +214,14 @@ class RegionProcessor:
 
     def _wave_pipe(self):
         """Staging of `process_regions`, created once per processor: a copy stream for the page uploads, a result stream,
-        WAVE_SLOTS device arenas holding the pages of a wave, one packed-crop buffer, two pinned result buffers and the
-        events that order them."""
+        WAVE_SLOTS device arenas holding the pages of a wave, one packed-crop buffer, the result ring (staging.ResultRing)
+        and the events that order them."""
         if getattr(self, "_pipe", None) is None:
-            from .embedder import _Null
-
-            t = self.embedder.torch
-            dev = t.device(self.embedder.device)
-            cuda = dev.type == "cuda"
-            mk_stream, mk_event = ((lambda: t.cuda.Stream(dev)), t.cuda.Event) if cuda else (_Null, _Null)
+            dev = self.embedder.torch.device(self.embedder.device)
             ns = max(2, int(self.WAVE_SLOTS))
-            self._pipe = {"dev": dev, "cuda": cuda, "in_stream": mk_stream(), "out_stream": mk_stream(),
-                          "arena": [None] * ns, "ev_cut": [mk_event() for _ in range(ns)], "slot_used": [False] * ns,
-                          "pix": None, "out": [None, None], "ev_pass": [mk_event(), mk_event()], "ev_out": [mk_event(), mk_event()]}
+            self._pipe = {"dev": dev, "in_stream": new_stream(dev), "ring": ResultRing(dev, 2048),
+                          "arena": [None] * ns, "ev_cut": [new_event(dev) for _ in range(ns)], "slot_used": [False] * ns,
+                          "pix": None, "ev_pass": [new_event(dev), new_event(dev)]}
         return self._pipe
 
     def process_regions(self, image_paths, force_recompute=False, *, regions_by_path=None, pages=None, as_lists=True):
@@ -244,6 +240,8 @@ class RegionProcessor:
             a gap between the encoder's persistent kernels, page after page -- copies the rows back on a third stream
             and hands the rows of the previous wave to the store -- per page, in page order, in the reference's chunks
             of REGION_BATCH_SIZE -- while the device works on the current one.
+        The producer thread, its slots and queue and the one-behind result buffers are staging.Stage and staging.ResultRing,
+        shared with `RegionEmbedder._embed_list`; every engine call is made on this thread.
         The contract per page is unchanged: an unreadable page is logged and skipped (`validate_image`, :43-45), a page
         without regions is skipped with the reference's warning (:50-52), a page whose boxes cannot be cut fails alone and
         a failed device pass voids exactly the pages it carried ("Error in batch processing"), a failed upsert voids its
@@ -254,22 +252,17 @@ class RegionProcessor:
         The passes run on the embedder's FIRST context (one GPU): the deployment shape is one process per GPU, each with its
         share of the pages (`dist.shard_range` / `shard_pages`); an embedder that holds several contexts in one process fans
         `get_image_embeddings` out over them, not this method."""
-        import contextlib
-        import queue
-        import threading
         import time as _time
         from concurrent.futures import ThreadPoolExecutor
 
         from .embedder import _load_rgb
 
         t = self.embedder.torch
-        engine = self.embedder.engine
         pipe = self._wave_pipe()
-        dev, cuda = pipe["dev"], pipe["cuda"]
+        dev = pipe["dev"]
         ns = len(pipe["arena"])
         total_images = len(image_paths)
         logger.info(f"Processing regions for {total_images} images")
-        on = (lambda stream: t.cuda.stream(stream)) if cuda else (lambda stream: contextlib.nullcontext())
         trace = getattr(self, "trace", None)  # tools: a dict of accumulated seconds per stage of the two threads
 
         def tick(key, t0):
@@ -286,22 +279,17 @@ class RegionProcessor:
                 logger.error(f"Invalid image file {path}: {e}")
                 return None
 
-        ready = queue.Queue(maxsize=ns)
-        slot_free = [threading.Semaphore(1) for _ in range(ns)]
-        stop = threading.Event()
-
-        def produce():
+        def produce(stage):  # decode, page rows and H2D on the input stream: no engine call on this thread
             wave_no = 0
             cur = None  # open wave: {"slot", "pages": [(path, ids, metas, good, boxes, arena offset, shape)], "crops", "crop_bytes", "page_bytes"}
 
             def open_wave():
                 nonlocal cur
                 slot = wave_no % ns
-                while not slot_free[slot].acquire(timeout=0.1):
-                    if stop.is_set():
-                        return False
+                if not stage.acquire(slot):
+                    return False
                 if pipe["slot_used"][slot]:
-                    with on(pipe["in_stream"]):
+                    with on(dev, pipe["in_stream"]):
                         pipe["in_stream"].wait_event(pipe["ev_cut"][slot])  # the K0 launches that read this arena have run
                 pipe["slot_used"][slot] = True
                 cur = {"slot": slot, "pages": [], "crops": 0, "crop_bytes": 0, "page_bytes": 0}
@@ -312,10 +300,10 @@ class RegionProcessor:
                 if cur is None:
                     return
                 if cur["pages"]:
-                    ready.put(("wave", cur))  # every upload of the wave has completed: the copies below are blocking
+                    stage.put(cur)  # every upload of the wave has completed: the copies below are blocking
                     wave_no += 1
                 else:
-                    slot_free[cur["slot"]].release()
+                    stage.release(cur["slot"])
                 cur = None
 
             def upload(arr, slot, at):
@@ -330,104 +318,92 @@ class RegionProcessor:
                     grown = t.empty(max(at + nb, self.WAVE_PAGE_BYTES // 2, 1 << 24), dtype=t.uint8, device=dev)
                     if arena is not None:
                         if at:  # pages of this wave already sit in the old arena
-                            with on(pipe["in_stream"]):
+                            with on(dev, pipe["in_stream"]):
                                 grown[:at].copy_(arena[:at])
                                 pipe["in_stream"].synchronize()
                         pipe["ev_cut"][slot].synchronize()  # nothing reads the old arena any more
                     pipe["arena"][slot] = arena = grown
-                with on(pipe["in_stream"]):
+                with on(dev, pipe["in_stream"]):
                     arena[at : at + nb].copy_(t.from_numpy(arr.reshape(-1)))
                 return nb
 
-            try:
-                with ThreadPoolExecutor(max_workers=self.DECODE_AHEAD) as pool:
-                    futures = {k: pool.submit(decode, image_paths[k]) for k in range(min(self.DECODE_AHEAD, total_images))}
-                    for idx, image_path in enumerate(image_paths):
-                        if stop.is_set():
-                            return
-                        tk = _time.perf_counter()
-                        arr = futures.pop(idx).result()
-                        tk = tick("producer: wait for decode", tk)
-                        if idx + self.DECODE_AHEAD < total_images:
-                            futures[idx + self.DECODE_AHEAD] = pool.submit(decode, image_paths[idx + self.DECODE_AHEAD])
-                        if (idx + 1) % 5 == 0 or idx == total_images - 1:
-                            logger.info(f"Region processing progress: {idx + 1}/{total_images} images")
-                        if arr is None:
-                            logger.error(f"Skipping invalid image: {image_path}")  # :43-45
-                            continue
-                        image_filename = os.path.basename(image_path)
-                        try:
-                            regions = regions_by_path.get(image_path) if regions_by_path is not None else self.detector.detect_regions(image_path, force_recompute)
-                        except Exception as e:  # noqa: BLE001
-                            logger.error(f"Error detecting regions in {image_filename}: {e}")
-                            regions = None
-                        if regions is None or not regions.get("boxes"):
-                            logger.warning(f"No regions detected in {image_filename}")  # :50-52
-                            continue
-                        ids, metas, boxes, good = self._page_rows(image_path, regions)
-                        tk = tick("producer: rows", tk)
-                        if not good:
-                            continue
-                        b = boxes[good]
-                        try:  # an oversized box inside the page takes its capped size (embedder.py:110-114); any other fails the page
-                            side = self._crop_sizes(b, int(arr.shape[0]), int(arr.shape[1]))
-                        except MmeError as e:
-                            logger.error(f"Error in batch processing: {image_filename}: {e}")
-                            continue
-                        nbytes = int(((side[:, 0].astype(np.int64) * side[:, 1] * 3 + 15) // 16 * 16).sum())
-                        if cur is not None and cur["pages"] and (cur["crop_bytes"] + nbytes > self.WAVE_BYTES
-                                                                 or cur["page_bytes"] + arr.nbytes > self.WAVE_PAGE_BYTES):
-                            close_wave()
-                        if cur is None and not open_wave():
-                            return
-                        tk = tick("producer: wait for a wave slot", tk)
-                        try:
-                            at = (cur["page_bytes"] + 255) // 256 * 256
-                            nb = upload(arr, cur["slot"], at)
-                        except (OSError, ValueError, RuntimeError) as e:
-                            logger.error(f"Error in batch processing: {e}")  # this page's regions fail, the wave goes on
-                            continue
-                        tk = tick("producer: page H2D", tk)
-                        cur["pages"].append((image_path, ids, metas, good, b, at, arr.shape))
-                        cur["page_bytes"] = at + nb
-                        cur["crop_bytes"] += nbytes
-                        cur["crops"] += len(good)
-                        if cur["crops"] >= self.WAVE_CROPS:
-                            close_wave()
-                    close_wave()
-            except BaseException as e:  # never leave the consumer waiting
-                logger.error(f"Error in batch processing: {e}")
-                if cur is not None:
-                    slot_free[cur["slot"]].release()
-            finally:
-                ready.put(("end",))
+            with ThreadPoolExecutor(max_workers=self.DECODE_AHEAD) as pool:
+                futures = {k: pool.submit(decode, image_paths[k]) for k in range(min(self.DECODE_AHEAD, total_images))}
+                for idx, image_path in enumerate(image_paths):
+                    if stage.stop.is_set():
+                        return
+                    tk = _time.perf_counter()
+                    arr = futures.pop(idx).result()
+                    tk = tick("producer: wait for decode", tk)
+                    if idx + self.DECODE_AHEAD < total_images:
+                        futures[idx + self.DECODE_AHEAD] = pool.submit(decode, image_paths[idx + self.DECODE_AHEAD])
+                    if (idx + 1) % 5 == 0 or idx == total_images - 1:
+                        logger.info(f"Region processing progress: {idx + 1}/{total_images} images")
+                    if arr is None:
+                        logger.error(f"Skipping invalid image: {image_path}")  # :43-45
+                        continue
+                    image_filename = os.path.basename(image_path)
+                    try:
+                        regions = regions_by_path.get(image_path) if regions_by_path is not None else self.detector.detect_regions(image_path, force_recompute)
+                    except Exception as e:  # noqa: BLE001
+                        logger.error(f"Error detecting regions in {image_filename}: {e}")
+                        regions = None
+                    if regions is None or not regions.get("boxes"):
+                        logger.warning(f"No regions detected in {image_filename}")  # :50-52
+                        continue
+                    ids, metas, boxes, good = self._page_rows(image_path, regions)
+                    tk = tick("producer: rows", tk)
+                    if not good:
+                        continue
+                    b = boxes[good]
+                    try:  # an oversized box inside the page takes its capped size (embedder.py:110-114); any other fails the page
+                        side = self._crop_sizes(b, int(arr.shape[0]), int(arr.shape[1]))
+                    except MmeError as e:
+                        logger.error(f"Error in batch processing: {image_filename}: {e}")
+                        continue
+                    nbytes = packed_bytes(side)
+                    if cur is not None and cur["pages"] and (cur["crop_bytes"] + nbytes > self.WAVE_BYTES
+                                                             or cur["page_bytes"] + arr.nbytes > self.WAVE_PAGE_BYTES):
+                        close_wave()
+                    if cur is None and not open_wave():
+                        return
+                    tk = tick("producer: wait for a wave slot", tk)
+                    try:
+                        at = (cur["page_bytes"] + 255) // 256 * 256
+                        nb = upload(arr, cur["slot"], at)
+                    except (OSError, ValueError, RuntimeError) as e:
+                        logger.error(f"Error in batch processing: {e}")  # this page's regions fail, the wave goes on
+                        continue
+                    tk = tick("producer: page H2D", tk)
+                    cur["pages"].append((image_path, ids, metas, good, b, at, arr.shape))
+                    cur["page_bytes"] = at + nb
+                    cur["crop_bytes"] += nbytes
+                    cur["crops"] += len(good)
+                    if cur["crops"] >= self.WAVE_CROPS:
+                        close_wave()
+                close_wave()
 
         total = 0
-        pending = None  # (result slot, wave, n rows, device rows kept alive) whose D2H is in flight
         n_pass = 0
 
-        def finalize(p):
+        def finalize(wave, rows):
             nonlocal total
-            rs, wave, n, _keep = p
-            pipe["ev_out"][rs].synchronize()
-            rows = pipe["out"][rs][:n].numpy()
             r0 = 0
             for path, ids, metas, good, *_ in wave["pages"]:
                 emb = rows[r0: r0 + len(good)]
                 r0 += len(good)
                 total += self._upsert_page(os.path.basename(path), ids, metas, good, emb.tolist() if as_lists else list(emb.copy()))
 
-        producer = threading.Thread(target=produce, name="mme-region-stage", daemon=True)
-        producer.start()
-        try:
-            compute = t.cuda.current_stream(dev) if cuda else pipe["in_stream"]
+        ring = pipe["ring"]
+        ring.start(finalize)
+        with Stage("mme-region-stage", produce, ns, dev, logger) as stage:
+            compute = current_stream(dev)
             while True:
                 tk = _time.perf_counter()
-                msg = ready.get()
+                wave = stage.get()
                 tk = tick("consumer: wait for a staged wave", tk)
-                if msg[0] == "end":
+                if wave is None:
                     break
-                wave = msg[1]
                 slot = wave["slot"]
                 try:
                     need = wave["crop_bytes"] + 16
@@ -444,55 +420,30 @@ class RegionProcessor:
                             continue
                         offs_all.append(offs)
                         hw_all.append(hw)
-                        base = int(offs[-1]) + (int(hw[-1, 0]) * int(hw[-1, 1]) * 3 + 15) // 16 * 16
+                        base += packed_bytes(hw)
                         kept.append(page)
                     wave["pages"] = kept
                     pipe["ev_cut"][slot].record(compute)
-                    slot_free[slot].release()  # the producer may refill the arena: its copies wait for ev_cut on the device
+                    stage.release(slot)  # the producer may refill the arena: its copies wait for ev_cut on the device
                     slot = None
                     tk = tick("consumer: crop_boxes calls", tk)
                     if not kept:
                         continue
-                    n = sum(len(o) for o in offs_all)
                     e32, _ = self.embedder.embed_packed(pipe["pix"], np.concatenate(offs_all), np.concatenate(hw_all), want_bf16=False)
                     tk = tick("consumer: embed call", tk)
                 except (MmeError, OSError, ValueError, RuntimeError) as e:
                     if slot is not None:
                         pipe["ev_cut"][slot].record(compute)
-                        slot_free[slot].release()
+                        stage.release(slot)
                     for path, *_ in wave["pages"]:
                         logger.error(f"Error in batch processing: {e}")  # embedder.py:223-224, once per page the pass carried
                     continue
-                rs = n_pass & 1
+                ev_pass = pipe["ev_pass"][n_pass & 1]
                 n_pass += 1
-                pipe["ev_pass"][rs].record(compute)
-                if pending is not None and pending[0] == rs:
-                    finalize(pending)  # the result buffer is about to be reused
-                    pending = None
-                if pipe["out"][rs] is None or pipe["out"][rs].shape[0] < n or pipe["out"][rs].shape[1] != e32.shape[1]:
-                    pipe["out"][rs] = t.empty((max(n, 2048), e32.shape[1]), dtype=t.float32, pin_memory=cuda)
-                with on(pipe["out_stream"]):
-                    pipe["out_stream"].wait_event(pipe["ev_pass"][rs])
-                    pipe["out"][rs][:n].copy_(e32, non_blocking=True)
-                    pipe["ev_out"][rs].record(pipe["out_stream"])
+                ev_pass.record(compute)
                 tk = _time.perf_counter()
-                if pending is not None:
-                    finalize(pending)  # the previous wave's rows go to the store under this wave's device pass
+                ring.submit(e32, ev_pass, wave)  # the previous wave's rows go to the store under this wave's device pass
                 tick("consumer: rows of the previous wave to the store", tk)
-                pending = (rs, wave, n, e32)
-            if pending is not None:
-                finalize(pending)
-        except BaseException:
-            if cuda:
-                t.cuda.synchronize(dev)
-            raise
-        finally:
-            stop.set()
-            while producer.is_alive():  # drain so that a blocked put() returns
-                try:
-                    ready.get(timeout=0.05)
-                except queue.Empty:
-                    pass
-            producer.join()
+            ring.finish()
         logger.info(f"Completed region processing: {total} regions processed in {total_images} images")
         return total

@@ -157,7 +157,7 @@ def test_get_image_embeddings_contract_without_gpu_work(monkeypatch):
 
     def make(n_dev, fail_on=None):
         emb = E.RegionEmbedder.__new__(E.RegionEmbedder)
-        emb.torch, emb.pool_token, emb._group_crops = torch, 0, 256
+        emb.torch, emb.pool_token, emb.encoder = torch, 0, "vit_b16"
         emb.devices = ["cpu"] * n_dev
         emb.device = torch.device("cpu")
         emb.engines = [FakeEngine(d, fail_on) for d in range(n_dev)]
@@ -585,10 +585,15 @@ def test_process_regions_wave_logic_without_a_device():
     from multimodal_embeddings_amd._lib import MmeError
     from multimodal_embeddings_amd.region_processor import RegionProcessor
 
+    import threading
+
+    engine_threads = set()  # every engine call belongs to the thread that called process_regions
+
     class FakeEngine:
         device = 0
 
         def crop_boxes(self, page, boxes, out=None, base=0):
+            engine_threads.add(threading.get_ident())
             b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
             hw = np.stack([b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]], axis=1).astype(np.int32)
             if hw.max() > 100:
@@ -611,6 +616,7 @@ def test_process_regions_wave_logic_without_a_device():
         fail_pass = None
 
         def embed_packed(self, pix, offs, hw, want_bf16=False):
+            engine_threads.add(threading.get_ident())
             self.passes.append(len(offs))
             if self.fail_pass is not None and len(self.passes) - 1 == self.fail_pass:
                 raise MmeError("out of memory (simulated)")
@@ -675,3 +681,4 @@ def test_process_regions_wave_logic_without_a_device():
     # one wave for everything when the threshold is large; a byte cap closes waves too
     n3, emb3, _ = run(wave=10_000)
     assert n3 == n and emb3.passes == [276]
+    assert engine_threads == {threading.get_ident()}  # crop_boxes and the passes ran on the calling thread, never the producer's
