@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+from .staging import packed_layout
 from .weights import (CLIP_ACTS, dinov2_geometry_problem, infer_dinov2_geometry, infer_vit_geometry, siglip_geometry_problem,
                       siglip_text_geometry_problem)
 
@@ -1045,20 +1046,27 @@ class Engine:
     def _ptr(t):
         return None if t is None else int(t.data_ptr())
 
+    def _gemm_args(self, A, W, M, N, K, variant, reverse_m, bias, out, ldo, ln_stats, colsum):
+        """The operands every GEMM hook takes (gemm_apply, and the GEMM ops of clip_apply / siglip_apply) as mme_gemm_apply_args:
+        M, N, K default to the operands' shapes, ldo to N."""
+        g = _GemmApplyArgs()
+        g.variant, g.reverse_m = int(variant), int(reverse_m)
+        g.M = int(A.shape[0] if M is None else M)
+        g.N = int(W.shape[0] if N is None else N)
+        g.K = int(A.shape[1] if K is None else K)
+        g.A, g.W, g.bias, g.out, g.ln_stats, g.colsum = (self._ptr(t) for t in (A, W, bias, out, ln_stats, colsum))
+        g.ldo = int(g.N if ldo is None else ldo)
+        return g
+
     def gemm_apply(self, epilogue: int, A, W, *, M=None, N=None, K=None, variant: int = 0, reverse_m: int = 0, bias=None, out=None, ldo=None,
                    res=None, pos=None, outf=None, ldf=None, ln_stats=None, colsum=None, ln_part=None, ln_part_rows: int = 0) -> bool:
         """ONE GEMM launch with one epilogue on the caller's CUDA tensors (mme_gemm_apply; synchronous): A bf16 [M, K],
         W bf16 [N, K]; the other tensors as include/mme.h describes them, `out` / `res` / `outf` possibly views into larger
         buffers with row pitch `ldo` / `ldf` (default N).  M, N, K default to the operands' shapes.  -> True when the
         256 x 256 kernel ran.  Nothing is checked here: the library validates every argument and raises MmeError."""
-        a = _GemmApplyArgs()
-        a.epilogue, a.variant, a.reverse_m = int(epilogue), int(variant), int(reverse_m)
-        a.M = int(A.shape[0] if M is None else M)
-        a.N = int(W.shape[0] if N is None else N)
-        a.K = int(A.shape[1] if K is None else K)
-        a.A, a.W, a.bias, a.out, a.res, a.pos = (self._ptr(t) for t in (A, W, bias, out, res, pos))
-        a.outf, a.ln_stats, a.colsum, a.ln_part = (self._ptr(t) for t in (outf, ln_stats, colsum, ln_part))
-        a.ldo = int(a.N if ldo is None else ldo)
+        a = self._gemm_args(A, W, M, N, K, variant, reverse_m, bias, out, ldo, ln_stats, colsum)
+        a.epilogue = int(epilogue)
+        a.res, a.pos, a.outf, a.ln_part = (self._ptr(t) for t in (res, pos, outf, ln_part))
         a.ldf = int(a.N if ldf is None else ldf)
         a.pos_rows = 0 if pos is None else int(pos.shape[0])
         a.ln_part_rows = int(ln_part_rows)
@@ -1117,13 +1125,7 @@ class Engine:
         a = _ClipApplyArgs()
         g = None
         if A is not None or W is not None:
-            g = _GemmApplyArgs()
-            g.variant, g.reverse_m = int(variant), int(reverse_m)
-            g.M = int(A.shape[0] if M is None else M)
-            g.N = int(W.shape[0] if N is None else N)
-            g.K = int(A.shape[1] if K is None else K)
-            g.A, g.W, g.bias, g.out, g.ln_stats, g.colsum = (self._ptr(t) for t in (A, W, bias, out, ln_stats, colsum))
-            g.ldo = int(g.N if ldo is None else ldo)
+            g = self._gemm_args(A, W, M, N, K, variant, reverse_m, bias, out, ldo, ln_stats, colsum)
             a.gemm = C.pointer(g)
         a.x, a.gamma, a.beta, a.stats, a.y, a.xf, a.y_f32, a.y_bf16 = (self._ptr(t) for t in (x, gamma, beta, stats, y, xf, y_f32, y_bf16))
         a.rows, a.d, a.B, a.tok, a.p, a.eps = int(rows), int(d), int(B), int(tok), int(p), float(eps)
@@ -1145,13 +1147,7 @@ class Engine:
         a = _SiglipApplyArgs()
         g = None
         if A is not None or W is not None:
-            g = _GemmApplyArgs()
-            g.variant, g.reverse_m = int(variant), int(reverse_m)
-            g.M = int(A.shape[0] if M is None else M)
-            g.N = int(W.shape[0] if N is None else N)
-            g.K = int(A.shape[1] if K is None else K)
-            g.A, g.W, g.bias, g.out, g.ln_stats, g.colsum = (self._ptr(t) for t in (A, W, bias, out, ln_stats, colsum))
-            g.ldo = int(g.N if ldo is None else ldo)
+            g = self._gemm_args(A, W, M, N, K, variant, reverse_m, bias, out, ldo, ln_stats, colsum)
             a.gemm = C.pointer(g)
         a.acc, a.bias, a.pos, a.x, a.kv, a.q, a.out, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (acc, bias, pos, x, kv, q, out, emb_f32, emb_bf16))
         a.n, a.d, a.heads = int(n), int(d), int(heads)
@@ -1217,17 +1213,13 @@ class Engine:
             i = int(np.flatnonzero(((hw64 <= 0) | (hw64 > 8000)).any(axis=1))[0])
             raise MmeError(f"crop_boxes: box {i} is {hw64[i, 1]}x{hw64[i, 0]} (w x h); every box must be 1..8000 pixels wide and high after int() truncation")
         hw = np.ascontiguousarray(hw64.astype(np.int32)) if n else np.zeros((0, 2), np.int32)
-        size = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
-        offs = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            offs[1:] = np.cumsum((size[:-1] + 15) // 16 * 16)
-        total = int(offs[-1] + size[-1]) if n else 0
+        offs, _, total = packed_layout(hw)  # `total` counts the 16 bytes behind the last crop
         if out is not None:
-            if out.dtype != t.uint8 or not out.is_contiguous() or out.device != page.device or base % 16 or base < 0 or base + total + 16 > out.numel():
+            if out.dtype != t.uint8 or not out.is_contiguous() or out.device != page.device or base % 16 or base < 0 or base + total > out.numel():
                 raise MmeError("crop_boxes: `out` must be a contiguous uint8 buffer on the page's device with room for the crops (+16 B) from a 16-byte aligned `base`")
             pix, offs = out, offs + int(base)
         else:
-            pix = t.empty(total + 16, dtype=t.uint8, device=page.device)
+            pix = t.empty(total, dtype=t.uint8, device=page.device)
         self._check(self.lib.mme_crop_boxes(self.h, page.data_ptr(), int(page.shape[0]), int(page.shape[1]), b.ctypes.data, n,
                                             pix.data_ptr(), offs.ctypes.data, self._stream()), "mme_crop_boxes")
         return pix, offs, hw

@@ -475,7 +475,9 @@ hipError_t launch_attention_heads(const void* qkv, void* out, int B, hipStream_t
 
 hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard, bool force_redo, int only_block, bool reverse,
                             int tokens) {
-    if (only_block < -1 || only_block > 6 || (tokens != VIT_T && tokens != 196)) return hipErrorInvalidValue;
+    static_assert(count_attn(ATTN_LONG) == 2 && attn_row(ATTN_LONG, VIT_T) && attn_row(ATTN_LONG, 196), "attention: the layouts of this family are 197 and 196 tokens");
+    const TokenLayout* L = find_layout(tokens);
+    if (!L || L->attn != ATTN_LONG || !L->takes_block(only_block)) return hipErrorInvalidValue;
     return with_heads(heads, [&](auto h) {
         constexpr int H = decltype(h)::value;
         return tokens == VIT_T ? launch_attention_heads<H, VIT_T>(qkv, out, B, s, guard, force_redo, only_block, reverse)

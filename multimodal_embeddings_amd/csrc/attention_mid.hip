@@ -148,10 +148,10 @@ __global__ __launch_bounds__(64 * MID_WAVES, 2) void attn_mid(const bf16_t* __re
 
 }  // namespace
 
-hipError_t launch_attention_t257(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block) {
-    if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 384, 768, 1024
-    if (only_block < -1 || only_block >= MID_NT) return hipErrorInvalidValue;
-    if (n <= 0) return hipSuccess;
+static_assert(count_attn(ATTN_MID) == 1 && attn_row(ATTN_MID, MID_T), "attn_mid: the one layout of this family is MID_T tokens");
+
+// behind launch_attention_exact (attention_short.hip), which has checked heads and only_block against the layout and n > 0
+hipError_t launch_attn_mid(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block) {
     const int64_t items = (int64_t)n * heads;
     if (items > 0x7fffffff) return hipErrorInvalidValue;
     if (hipError_t e = ensure_dynamic_lds((const void*)attn_mid, MID_LDS); e != hipSuccess) return e;

@@ -25,7 +25,7 @@
 //   * Q arrives pre-multiplied by dh^-0.5 log2 e (folded into W_q / b_q at load, as for attention.hip): P = exp2(s - max).
 //   * only_block >= 0 (not CAUSAL): only that query block is computed and stored (the pruned last layer); the other wave
 //     still brings its share of K and V.  The computed block is bit-identical to the full launch: a wave's arithmetic does
-//     not depend on the other wave's.  The causal kernel takes the argument and ignores it.
+//     not depend on the other wave's.  The causal kernel takes the argument and ignores it (its launcher passes -1).
 // Rounding points are attention.hip's two: P to bf16 before P.V, the output (O / sum, sum over the f32 P) to bf16.
 // Query 0 of a causal item sees one key: P = 1, sum = 1, the output is V[0] bit for bit.
 #include "attention_common.h"
@@ -144,37 +144,23 @@ __global__ __launch_bounds__(64 * ((T + 31) / 32)) void attn_short(const bf16_t*
     }
 }
 
-enum ShortKind { SHORT_T77_CAUSAL, SHORT_T50, SHORT_T64 };
-
-hipError_t launch_short(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block, ShortKind kind) {
-    if (n <= 0) return hipSuccess;
-    const int64_t items = (int64_t)n * heads;
-    if (items > 0x7fffffff) return hipErrorInvalidValue;
-    const int grid = items < 1024 ? (int)items : 1024;  // persistent: up to four workgroups per CU walk the items
-    if (kind == SHORT_T77_CAUSAL)
-        hipLaunchKernelGGL((attn_short<TXT_T, true>), dim3(grid), dim3(192), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
-    else if (kind == SHORT_T50)
-        hipLaunchKernelGGL((attn_short<50, false>), dim3(grid), dim3(128), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
-    else
-        hipLaunchKernelGGL((attn_short<TXT_T64, false>), dim3(grid), dim3(128), 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block);
-    return hipGetLastError();
-}
+static_assert(count_attn(ATTN_SHORT) == 3 && attn_row(ATTN_SHORT, TXT_T, true) && attn_row(ATTN_SHORT, 50) && attn_row(ATTN_SHORT, TXT_T64),
+              "attn_short: instantiate the kernel for every layout of this family");
 
 }  // namespace
 
-hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads, hipStream_t s) {
-    if (heads != 8 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 512, 768, 1024
-    return launch_short(qkv, out, n, heads, s, -1, SHORT_T77_CAUSAL);
-}
-
-hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block) {
-    if (heads != 6 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 384, 768, 1024
-    if (only_block < -1 || only_block > 1) return hipErrorInvalidValue;
-    return launch_short(qkv, out, n, heads, s, only_block, SHORT_T50);
-}
-
-hipError_t launch_attention_t64(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block) {
-    if (heads != 8 && heads != 12 && heads != 16) return hipErrorInvalidValue;  // widths 512, 768, 1024
-    if (only_block < -1 || only_block > 1) return hipErrorInvalidValue;
-    return launch_short(qkv, out, n, heads, s, only_block, SHORT_T64);
+hipError_t launch_attention_exact(const void* qkv, void* out, int n, int tokens, bool causal, int heads, hipStream_t s, int only_block) {
+    const TokenLayout* L = find_layout(tokens, causal);
+    if (!L || L->attn == ATTN_LONG || !L->has_heads(heads) || !L->takes_block(only_block)) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    if (L->attn == ATTN_MID) return launch_attn_mid(qkv, out, n, heads, s, only_block);
+    const int64_t items = (int64_t)n * heads;
+    if (items > 0x7fffffff) return hipErrorInvalidValue;
+    const int grid = items < 1024 ? (int)items : 1024;  // persistent: up to four workgroups per CU walk the items
+    const dim3 waves(64 * L->blocks);  // a wave per query block
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), waves, 0, s, (const bf16_t*)qkv, (bf16_t*)out, (int)items, heads, only_block); };
+    if (tokens == TXT_T) go(attn_short<TXT_T, true>);
+    else if (tokens == 50) go(attn_short<50, false>);
+    else go(attn_short<TXT_T64, false>);
+    return hipGetLastError();
 }

@@ -353,7 +353,7 @@ void mme_destroy(mme_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (void* p : c->allocs) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->patches32, &c->patches14};
+    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->retiled};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->lut) (void)hipFree(c->lut);
@@ -466,12 +466,13 @@ int mme_attention_apply(mme_ctx* c, int kind, const uint16_t* qkv, int n, const 
     if (!c) return MME_E_ARG;
     if (!qkv || !out || !redone) return fail(c, MME_E_ARG, "mme_attention_apply: null argument");
     if (kind != 0 && kind != 1) return fail(c, MME_E_ARG, "mme_attention_apply: kind %d (0 = ViT/16 at the context's geometry, 1 = tile-ViT)", kind);
-    if (kind == 0 && c->geom.t50()) return fail(c, MME_E_ARG, "mme_attention_apply: kind 0 is the 197-token kernel and the context holds a patch-32 tower (50 tokens); mme_vit32_apply op 2 launches its kernel");
-    if (kind == 0 && c->geom.t257()) return fail(c, MME_E_ARG, "mme_attention_apply: kind 0 is the 197-token kernel and the context holds a patch-14 tower (257 tokens); mme_dinov2_apply op 2 launches its kernel");
+    const TokenLayout& L = c->geom.layout();
+    if (kind == 0 && L.attn != ATTN_LONG)
+        return fail(c, MME_E_ARG, "mme_attention_apply: kind 0 is the 197-token kernel and the context holds a patch-%d tower (%d tokens); %s op 2 launches its kernel", L.patch, L.tokens, L.patch == 32 ? "mme_vit32_apply" : "mme_dinov2_apply");
     const int n_max = kind == 0 ? 1 << 20 : 4096;
     if (n <= 0 || n > n_max) return fail(c, MME_E_ARG, "mme_attention_apply: n = %d outside 1..%d", n, n_max);
     if (kind == 0) {
-        if (only_block < -1 || only_block > 6) return fail(c, MME_E_ARG, "mme_attention_apply: only_block %d outside -1..6", only_block);
+        if (!L.takes_block(only_block)) return fail(c, MME_E_ARG, "mme_attention_apply: only_block %d outside -1..%d", only_block, L.blocks - 1);
         if (reverse != 0 && reverse != 1) return fail(c, MME_E_ARG, "mme_attention_apply: reverse must be 0 or 1");
     } else {
         if (only_block != -1 || reverse != 0) return fail(c, MME_E_ARG, "mme_attention_apply: kind 1 takes only_block = -1 and reverse = 0");
@@ -1080,26 +1081,24 @@ int mme_gemm_apply(mme_ctx* c, const mme_gemm_apply_args* a, int32_t* ran_256, v
 }
 
 int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_rowop_apply: null argument");
-    if (op < 0 || op > 5) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d outside 0..5", op);
+    if (int r = hook_args(c, "mme_rowop_apply", a, op, 5)) return r;
     const bool fixed_d = op == 0 || op == 1 || op == 4 || op == 5;
     if (fixed_d && !vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
     if (!fixed_d && (a->d <= 0 || (a->d % 64) != 0 || a->d > 2048)) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d needs d %% 64 == 0, d <= 2048 (d = %d)", op, a->d);
-    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
     const bool stats_ok = a->stats && aligned_to(a->stats, 8);
     const char* bad = nullptr;
+    const HookCheck h{c, "mme_rowop_apply", op};
     switch (op) {
         case 0:
-            if (!vec(a->x) || !vec(a->y) || !vec(a->gamma) || !vec(a->beta)) bad = "x, y, gamma, beta non-null and 16-byte aligned";
+            if (!vec16(a->x) || !vec16(a->y) || !vec16(a->gamma) || !vec16(a->beta)) bad = "x, y, gamma, beta non-null and 16-byte aligned";
             else if (a->rows < 0) bad = "rows >= 0";
             break;
         case 1:
-            if (!vec(a->x) || !stats_ok) bad = "x non-null and 16-byte aligned, stats non-null and 8-byte aligned";
+            if (!vec16(a->x) || !stats_ok) bad = "x non-null and 16-byte aligned, stats non-null and 8-byte aligned";
             else if (a->rows < 0) bad = "rows >= 0";
             break;
         case 2:
-            if (!vec(a->x) || !stats_ok) bad = "x non-null and 16-byte aligned, stats non-null and 8-byte aligned";
+            if (!vec16(a->x) || !stats_ok) bad = "x non-null and 16-byte aligned, stats non-null and 8-byte aligned";
             else if (a->row0 < 0 || a->row1 < a->row0 || a->stride < 1) bad = "0 <= row0 <= row1 and stride >= 1";
             break;
         case 3:
@@ -1108,15 +1107,14 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
             else if (a->part_rows > ((int64_t)1 << 32) || a->part_floats < 2 * (int64_t)(a->d / 64) * a->part_rows) bad = "part_floats >= 2 * d/64 * part_rows";
             break;
         case 4:
-            if (!vec(a->x) || !vec(a->cls) || !vec(a->pos)) bad = "x, cls, pos non-null and 16-byte aligned";
+            if (!vec16(a->x) || !vec16(a->cls) || !vec16(a->pos)) bad = "x, cls, pos non-null and 16-byte aligned";
             else if (a->B < 0) bad = "B >= 0";
             break;
         default:
-            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
-            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
-            else if (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
-            else if (a->B < 0) bad = "B >= 0";
-            else if (a->tok < 0 || a->tok >= VIT_T) bad = "0 <= tok <= 196";
+            if (int r = h.ln_in(a->x, a->gamma, a->beta)) return r;
+            if (int r = h.out_pair(a->emb_f32, a->emb_bf16, "emb_f32", "emb_bf16")) return r;
+            if (a->B < 0) bad = "B >= 0";
+            else if (int r = h.tok(*find_layout(VIT_T), a->tok)) return r;
             break;
     }
     if (bad) return fail(c, MME_E_ARG, "mme_rowop_apply: op %d needs %s", op, bad);
@@ -1136,10 +1134,7 @@ int mme_rowop_apply(mme_ctx* c, int op, const mme_rowop_apply_args* a, void* str
 
 // the three launches of K12 (mme_neighbours), one at a time on caller-owned buffers (tests/test_gpu_select.py)
 int mme_select_apply(mme_ctx* c, int op, const mme_select_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_select_apply: null argument");
-    if (op < 0 || op > 2) return fail(c, MME_E_ARG, "mme_select_apply: op %d outside 0..2", op);
-    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    if (int r = hook_args(c, "mme_select_apply", a, op, 2)) return r;
     auto word = [](const void* p) { return p && aligned_to(p, 4); };
     if (op <= 1) {
         if (a->nrows < 0 || a->nrows > (1 << 24)) return fail(c, MME_E_ARG, "mme_select_apply: nrows = %d outside 0..2^24", a->nrows);
@@ -1153,11 +1148,11 @@ int mme_select_apply(mme_ctx* c, int op, const mme_select_apply_args* a, void* s
         if (a->N < 1) return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs N >= 1 (N = %d)", a->N);
         if ((a->ld % 4) != 0 || a->ld < a->N || a->ld > ((int64_t)1 << 30))
             return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs ld %% 4 == 0 and N <= ld <= 2^30 (ld = %lld, N = %d)", (long long)a->ld, a->N);
-        if (!vec(a->qsim)) return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs qsim non-null and 16-byte aligned");
+        if (!vec16(a->qsim)) return fail(c, MME_E_ARG, "mme_select_apply: op 0 needs qsim non-null and 16-byte aligned");
         if (a->run_if && !aligned_to(a->run_if, 4)) return fail(c, MME_E_ARG, "mme_select_apply: run_if must be 4-byte aligned");
     } else if (op == 1) {
         if (a->cap < 4 || (a->cap % 4) != 0) return fail(c, MME_E_ARG, "mme_select_apply: op 1 needs cap %% 4 == 0 and cap >= 4 (cap = %d)", a->cap);
-        if (!vec(a->cand_val) || !vec(a->cand_idx) || !word(a->len))
+        if (!vec16(a->cand_val) || !vec16(a->cand_idx) || !word(a->len))
             return fail(c, MME_E_ARG, "mme_select_apply: op 1 needs cand_val and cand_idx non-null and 16-byte aligned, len non-null and 4-byte aligned");
     } else {
         if (a->M < 0 || a->M > (1 << 24)) return fail(c, MME_E_ARG, "mme_select_apply: M = %d outside 0..2^24", a->M);
@@ -1166,7 +1161,7 @@ int mme_select_apply(mme_ctx* c, int op, const mme_select_apply_args* a, void* s
             return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs K a multiple of 64 in 128..65536 (K = %d)", a->K);
         if (a->cap < 1) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs cap >= 1 (cap = %d)", a->cap);
         if (a->thr_stride < 1) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs thr_stride >= 1 (thr_stride = %d)", a->thr_stride);
-        if (!vec(a->A) || !vec(a->W)) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs A and W non-null and 16-byte aligned");
+        if (!vec16(a->A) || !vec16(a->W)) return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs A and W non-null and 16-byte aligned");
         if (!word(a->thr) || !word(a->cand_count) || !word(a->cand_val) || !word(a->cand_idx) || !word(a->overflow))
             return fail(c, MME_E_ARG, "mme_select_apply: op 2 needs thr, cand_count, cand_val, cand_idx and overflow non-null and 4-byte aligned");
     }
@@ -1222,29 +1217,26 @@ static int act_gemm_apply(mme_ctx* c, const char* who, int op, int epi, const mm
 
 // the kernels a CLIP tower adds, one launch each (tests/test_gpu_clip.py)
 int mme_clip_apply(mme_ctx* c, int op, const mme_clip_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_clip_apply: null argument");
-    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_clip_apply: op %d outside 0..4", op);
+    if (int r = hook_args(c, "mme_clip_apply", a, op, 4)) return r;
     hipStream_t s = (hipStream_t)stream;
     if (op <= 1) return act_gemm_apply(c, "mme_clip_apply", op, op == 0 ? EPI_BIAS_QGELU : EPI_LN_BIAS_QGELU, a->gemm, a->ran_256, s);
-    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    const HookCheck h{c, "mme_clip_apply", op};
     const char* bad = nullptr;
+    int r;
     if (op == 2 || op == 3) {
-        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_clip_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
-        if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
-        else if (op == 2 && (!a->stats || !aligned_to(a->stats, 8))) bad = "stats non-null and 8-byte aligned";
+        if ((r = h.width(a->d)) || (r = h.ln_in(a->x, a->gamma, a->beta))) return r;
+        if (op == 2 && (!a->stats || !aligned_to(a->stats, 8))) bad = "stats non-null and 8-byte aligned";
         else if (op == 2 && a->rows < 0) bad = "rows >= 0";
-        else if (op == 3 && !vec(a->y)) bad = "y non-null and 16-byte aligned";
+        else if (op == 3 && !vec16(a->y)) bad = "y non-null and 16-byte aligned";
         else if (op == 3 && a->B < 0) bad = "B >= 0";
-        else if (op == 3 && (a->tok < 0 || a->tok >= VIT_T)) bad = "0 <= tok <= 196";
+        else if (op == 3 && (r = h.tok(*find_layout(VIT_T), a->tok))) return r;
     } else {
         if (a->p < 64 || (a->p % 64) != 0 || a->p > 1024) return fail(c, MME_E_ARG, "mme_clip_apply: op 4 needs p %% 64 == 0, 64 <= p <= 1024 (p = %d)", a->p);
-        if (!vec(a->xf)) bad = "xf non-null and 16-byte aligned";
-        else if (!a->y_f32 && !a->y_bf16) bad = "y_f32 or y_bf16";
-        else if (!aligned_to(a->y_f32, 16) || !aligned_to(a->y_bf16, 16)) bad = "y_f32 and y_bf16 16-byte aligned";
+        if (!vec16(a->xf)) bad = "xf non-null and 16-byte aligned";
+        else if ((r = h.out_pair(a->y_f32, a->y_bf16, "y_f32", "y_bf16"))) return r;
         else if (a->rows < 0) bad = "rows >= 0";
     }
-    if (bad) return fail(c, MME_E_ARG, "mme_clip_apply: op %d needs %s", op, bad);
+    if (bad) return h.needs(bad);
     HIP_TRY(c, hipSetDevice(c->device));
     switch (op) {
         case 2: HIP_TRY(c, launch_pre_ln(a->x, a->gamma, a->beta, a->rows, a->d, a->eps, a->stats, s)); break;
@@ -1255,124 +1247,102 @@ int mme_clip_apply(mme_ctx* c, int op, const mme_clip_apply_args* a, void* strea
     return MME_OK;
 }
 
-// the kernels a patch-32 tower adds, one launch each (tests/test_gpu_vit32.py)
-int mme_vit32_apply(mme_ctx* c, int op, const mme_vit32_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_vit32_apply: null argument");
-    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_vit32_apply: op %d outside 0..4", op);
-    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
-    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "mme_vit32_apply: n = %d outside 0..2^20", a->n);
-    const char* bad = nullptr;
-    if (op == 0) {
-        if (!vec(a->src) || !vec(a->dst)) bad = "src and dst non-null and 16-byte aligned";
-        else if (a->src == a->dst) bad = "src != dst (the permutation is not in place)";
-    } else if (op == 2) {
-        if (a->heads != 6 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_vit32_apply: op 2 is built for heads == 6, 12 and 16 (heads = %d)", a->heads);
-        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv and out non-null and 16-byte aligned";
-        else if (a->only_block < -1 || a->only_block > 1) bad = "only_block in -1..1";
-    } else {
-        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_vit32_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
-        if (op == 1) {
-            if (!vec(a->acc) || !vec(a->bias) || !vec(a->pos) || !vec(a->cls) || !vec(a->x)) bad = "acc, bias, pos, cls, x non-null and 16-byte aligned";
-        } else {
-            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
-            else if (a->tok < 0 || a->tok > 49) bad = "0 <= tok <= 49";
-            else if (op == 3 && !vec(a->y)) bad = "y non-null and 16-byte aligned";
-            else if (op == 4 && !a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
-            else if (op == 4 && (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16))) bad = "emb_f32 and emb_bf16 16-byte aligned";
-        }
+}  // extern "C"
+
+// The four steps a patch tower outside the 197-token path adds -- retile, embed rows, exact attention, the pooled
+// LayerNorm without (y) or with (emb_f32 / emb_bf16) the L2 step -- one launch each at layout L: the ops mme_vit32_apply and
+// mme_dinov2_apply have in common.  A is either hook's args struct; y is passed beside it (DINOv2 has no such op).
+enum PatchStep { STEP_RETILE, STEP_EMBED_ROWS, STEP_ATTENTION, STEP_POOL_LN, STEP_POOL_LN_L2 };
+template <class A>
+static int patch_tower_apply(mme_ctx* c, const char* who, const TokenLayout& L, int op, PatchStep step, const A* a, uint16_t* y, const char* retile_how,
+                             void* stream) {
+    const HookCheck h{c, who, op};
+    int r = h.crops(a->n);
+    if (r) return r;
+    switch (step) {
+        case STEP_RETILE:  // retile_how: the kernel's kind of copy ("permutation", "gather")
+            if (!vec16(a->src) || !vec16(a->dst)) return h.needs("src and dst non-null and 16-byte aligned");
+            if ((const void*)a->src == (const void*)a->dst) return fail(c, MME_E_ARG, "%s: op %d needs src != dst (the %s is not in place)", who, op, retile_how);
+            break;
+        case STEP_EMBED_ROWS: r = h.embed_rows(L, a->d, a->acc, a->bias, a->pos, a->cls, a->x); break;
+        case STEP_ATTENTION:
+            if ((r = h.heads(L, a->heads))) return r;
+            if (!vec16(a->qkv) || !vec16(a->out)) return h.needs("qkv and out non-null and 16-byte aligned");
+            if (!L.takes_block(a->only_block)) return fail(c, MME_E_ARG, "%s: op %d needs only_block in -1..%d", who, op, L.blocks - 1);
+            break;
+        default:
+            if ((r = h.width(a->d)) || (r = h.ln_in(a->x, a->gamma, a->beta)) || (r = h.tok(L, a->tok))) return r;
+            if (step == STEP_POOL_LN) r = vec16(y) ? MME_OK : h.needs("y non-null and 16-byte aligned");
+            else r = h.out_pair(a->emb_f32, a->emb_bf16, "emb_f32", "emb_bf16");
+            break;
     }
-    if (bad) return fail(c, MME_E_ARG, "mme_vit32_apply: op %d needs %s", op, bad);
+    if (r) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    switch (op) {
-        case 0: HIP_TRY(c, launch_retile_p32(a->src, a->dst, a->n, s)); break;
-        case 1: HIP_TRY(c, launch_embed_rows(a->acc, a->bias, a->pos, a->cls, a->x, a->n, 50, a->d, s)); break;
-        case 2: HIP_TRY(c, launch_attention_t50(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
-        case 3: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->n, 50, a->tok, a->d, a->eps, a->y, s)); break;
-        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->n, 50, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
+    switch (step) {
+        case STEP_RETILE: HIP_TRY(c, launch_retile(L.patch, a->src, a->dst, a->n, s)); break;
+        case STEP_EMBED_ROWS: HIP_TRY(c, launch_embed_rows(a->acc, a->bias, a->pos, a->cls, a->x, a->n, L.tokens, a->d, s)); break;
+        case STEP_ATTENTION: HIP_TRY(c, launch_attention_exact(a->qkv, a->out, a->n, L.tokens, L.causal, a->heads, s, a->only_block)); break;
+        case STEP_POOL_LN: HIP_TRY(c, launch_pool_ln(a->x, a->gamma, a->beta, a->n, L.tokens, a->tok, a->d, a->eps, y, s)); break;
+        default: HIP_TRY(c, launch_pool(a->x, a->gamma, a->beta, a->n, L.tokens, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
 }
 
-// the kernels a DINOv2 tower (patch 14, 257 tokens) adds, one launch each (tests/test_gpu_dinov2.py)
+extern "C" {
+
+// the kernels a patch-32 tower adds, one launch each (tests/test_gpu_vit32.py): the op codes are the steps
+int mme_vit32_apply(mme_ctx* c, int op, const mme_vit32_apply_args* a, void* stream) {
+    if (int r = hook_args(c, "mme_vit32_apply", a, op, 4)) return r;
+    return patch_tower_apply(c, "mme_vit32_apply", *find_layout(50), op, (PatchStep)op, a, a->y, "permutation", stream);
+}
+
+// the kernels a DINOv2 tower (patch 14, 257 tokens) adds, one launch each (tests/test_gpu_dinov2.py): ops 0..2 are the steps,
+// op 3 the pooled LayerNorm with the L2 step; rowscale and mul (ops 4, 5) are the loader's own
 int mme_dinov2_apply(mme_ctx* c, int op, const mme_dinov2_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_dinov2_apply: null argument");
-    if (op < 0 || op > 5) return fail(c, MME_E_ARG, "mme_dinov2_apply: op %d outside 0..5", op);
-    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
+    if (int r = hook_args(c, "mme_dinov2_apply", a, op, 5)) return r;
+    if (op <= 3) return patch_tower_apply(c, "mme_dinov2_apply", *find_layout(257), op, op == 3 ? STEP_POOL_LN_L2 : (PatchStep)op, a, nullptr, "gather", stream);
+    if (a->dtype < MME_DT_F32 || a->dtype > MME_DT_F16)
+        return fail(c, MME_E_ARG, "mme_dinov2_apply: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", a->dtype);
+    const size_t esz = a->dtype == MME_DT_F32 ? 4 : 2;
     const char* bad = nullptr;
-    if (op <= 3 && (a->n < 0 || a->n > (1 << 20))) return fail(c, MME_E_ARG, "mme_dinov2_apply: n = %d outside 0..2^20", a->n);
-    if (op == 0) {
-        if (!vec(a->src) || !vec(a->dst)) bad = "src and dst non-null and 16-byte aligned";
-        else if ((const void*)a->src == (const void*)a->dst) bad = "src != dst (the gather is not in place)";
-    } else if (op == 2) {
-        if (a->heads != 6 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_dinov2_apply: op 2 is built for heads == 6, 12 and 16 (heads = %d)", a->heads);
-        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv and out non-null and 16-byte aligned";
-        else if (a->only_block < -1 || a->only_block > 8) bad = "only_block in -1..8";
-    } else if (op == 1 || op == 3) {
-        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_dinov2_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
-        if (op == 1) {
-            if (!vec(a->acc) || !vec(a->bias) || !vec(a->pos) || !vec(a->cls) || !vec(a->x)) bad = "acc, bias, pos, cls, x non-null and 16-byte aligned";
-        } else {
-            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
-            else if (a->tok < 0 || a->tok > 256) bad = "0 <= tok <= 256";
-            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
-            else if (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
-        }
-    } else {
-        if (a->dtype < MME_DT_F32 || a->dtype > MME_DT_F16)
-            return fail(c, MME_E_ARG, "mme_dinov2_apply: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", a->dtype);
-        const size_t esz = a->dtype == MME_DT_F32 ? 4 : 2;
-        if (!a->w || !a->factor || !a->prepared || ((uintptr_t)a->factor % esz)) bad = "w, factor, prepared non-null, factor aligned to its element";
-        else if (a->rows < 1 || a->rows > ((int64_t)1 << 24)) bad = "1 <= rows <= 2^24";
-        else if (op == 4 && (!vec(a->w) || !vec(a->prepared))) bad = "w and prepared 16-byte aligned";
-        else if (op == 4 && (a->cols < 8 || (a->cols % 8) != 0 || a->cols > (1 << 16))) bad = "cols a multiple of 8 in 8..65536";
-        else if (op == 5 && (((uintptr_t)a->w % esz) || !aligned_to(a->prepared, 4))) bad = "w aligned to its element, prepared 4-byte aligned";
-    }
+    if (!a->w || !a->factor || !a->prepared || ((uintptr_t)a->factor % esz)) bad = "w, factor, prepared non-null, factor aligned to its element";
+    else if (a->rows < 1 || a->rows > ((int64_t)1 << 24)) bad = "1 <= rows <= 2^24";
+    else if (op == 4 && (!vec16(a->w) || !vec16(a->prepared))) bad = "w and prepared 16-byte aligned";
+    else if (op == 4 && (a->cols < 8 || (a->cols % 8) != 0 || a->cols > (1 << 16))) bad = "cols a multiple of 8 in 8..65536";
+    else if (op == 5 && (((uintptr_t)a->w % esz) || !aligned_to(a->prepared, 4))) bad = "w aligned to its element, prepared 4-byte aligned";
     if (bad) return fail(c, MME_E_ARG, "mme_dinov2_apply: op %d needs %s", op, bad);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    switch (op) {
-        case 0: HIP_TRY(c, launch_retile_p14(a->src, a->dst, a->n, s)); break;
-        case 1: HIP_TRY(c, launch_embed_rows_t257(a->acc, a->bias, a->pos, a->cls, a->x, a->n, a->d, s)); break;
-        case 2: HIP_TRY(c, launch_attention_t257(a->qkv, a->out, a->n, a->heads, s, a->only_block)); break;
-        case 3: HIP_TRY(c, launch_pool_t257(a->x, a->gamma, a->beta, a->n, a->tok, a->d, a->eps, a->emb_f32, a->emb_bf16, s)); break;
-        case 4: HIP_TRY(c, launch_wp_rowscale(a->dtype, a->w, (size_t)a->rows, (size_t)a->cols, a->factor, a->prepared, s)); break;
-        default: HIP_TRY(c, launch_wp_mul(a->dtype, a->w, a->factor, (size_t)a->rows, (float*)a->prepared, s)); break;
-    }
+    if (op == 4) HIP_TRY(c, launch_wp_rowscale(a->dtype, a->w, (size_t)a->rows, (size_t)a->cols, a->factor, a->prepared, s));
+    else HIP_TRY(c, launch_wp_mul(a->dtype, a->w, a->factor, (size_t)a->rows, (float*)a->prepared, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
 }
 
 // the kernels a SigLIP tower adds, one launch each (tests/test_gpu_siglip.py)
 int mme_siglip_apply(mme_ctx* c, int op, const mme_siglip_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_siglip_apply: null argument");
-    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d outside 0..4", op);
+    if (int r = hook_args(c, "mme_siglip_apply", a, op, 4)) return r;
     hipStream_t s = (hipStream_t)stream;
     if (op <= 1) return act_gemm_apply(c, "mme_siglip_apply", op, op == 0 ? EPI_BIAS_TGELU : EPI_LN_BIAS_TGELU, a->gemm, a->ran_256, s);
-    auto vec = [](const void* p) { return p && aligned_to(p, 16); };
-    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "mme_siglip_apply: n = %d outside 0..2^20", a->n);
-    const char* bad = nullptr;
+    const HookCheck h{c, "mme_siglip_apply", op};
+    const TokenLayout& L = *find_layout(196);
+    int r;
+    if ((r = h.crops(a->n))) return r;
     if (op == 3) {
-        if (a->heads != 6 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_siglip_apply: op 3 is built for heads == 6, 12 and 16 (heads = %d)", a->heads);
-        if (!vec(a->kv) || !vec(a->q) || !vec(a->out)) bad = "kv, q and out non-null and 16-byte aligned";
+        if ((r = h.heads(L, a->heads))) return r;
+        if (!vec16(a->kv) || !vec16(a->q) || !vec16(a->out)) return h.needs("kv, q and out non-null and 16-byte aligned");
+    } else if (op == 2) {
+        if ((r = h.embed_rows(L, a->d, a->acc, a->bias, a->pos, nullptr, a->x))) return r;
     } else {
-        if (!vit_width_built(a->d)) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", op, a->d);
-        if (op == 2) {
-            if (!vec(a->acc) || !vec(a->bias) || !vec(a->pos) || !vec(a->x)) bad = "acc, bias, pos, x non-null and 16-byte aligned";
-        } else {
-            if (!vec(a->x)) bad = "x non-null and 16-byte aligned";
-            else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
-            else if (!aligned_to(a->emb_f32, 16) || !aligned_to(a->emb_bf16, 16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
-        }
+        if ((r = h.width(a->d))) return r;
+        if (!vec16(a->x)) return h.needs("x non-null and 16-byte aligned");
+        if ((r = h.out_pair(a->emb_f32, a->emb_bf16, "emb_f32", "emb_bf16"))) return r;
     }
-    if (bad) return fail(c, MME_E_ARG, "mme_siglip_apply: op %d needs %s", op, bad);
     HIP_TRY(c, hipSetDevice(c->device));
     switch (op) {
-        case 2: HIP_TRY(c, launch_embed_rows(a->acc, a->bias, a->pos, nullptr, a->x, a->n, 196, a->d, s)); break;
+        case 2: HIP_TRY(c, launch_embed_rows(a->acc, a->bias, a->pos, nullptr, a->x, a->n, L.tokens, a->d, s)); break;
         case 3: HIP_TRY(c, launch_map_pool(a->kv, a->q, a->out, a->n, a->heads, s)); break;
         default: HIP_TRY(c, launch_l2_rows_bf16(a->x, a->n, a->d, a->emb_f32, a->emb_bf16, s)); break;
     }

@@ -267,8 +267,7 @@ int text_chunk(mme_ctx* c, TextDev* t, const int32_t* ids_dev, const int32_t* eo
         if ((r = P.qkv_ln(t->layer[l], M, 3 * D))) return r;
         {
             Timed tm(c, s, KC_ATTN);
-            if (t->causal) HIP_TRY(c, launch_attention_causal(t->qkv.p, t->att.p, n, t->heads, s));
-            else HIP_TRY(c, launch_attention_t64(t->qkv.p, t->att.p, n, t->heads, s));
+            HIP_TRY(c, launch_attention_exact(t->qkv.p, t->att.p, n, T, t->causal, t->heads, s));
         }
         // no statistics after the last block: final_layer_norm touches the pooled rows only
         if ((r = P.after_attention(t->layer[l], M, t->att.p, t->x.p, l + 1 < NL))) return r;
@@ -289,8 +288,6 @@ int text_chunk(mme_ctx* c, TextDev* t, const int32_t* ids_dev, const int32_t* eo
     else HIP_TRY(c, launch_l2_rows((const float*)t->projf.p, n, E ? E : D, emb_f32, emb_bf16, s));
     return MME_OK;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -397,115 +394,97 @@ int mme_text_forward(mme_ctx* c, const int32_t* ids_host, int n, float* emb_f32,
     return MME_OK;
 }
 
-// the kernels the text tower adds, one launch each (tests/test_gpu_clip_text.py)
-int mme_text_apply(mme_ctx* c, int op, const mme_text_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_text_apply: null argument");
-    if (op < 0 || op > 2) return fail(c, MME_E_ARG, "mme_text_apply: op %d outside 0..2", op);
-    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "mme_text_apply: n = %d outside 0..2^20", a->n);
-    auto vec = [](const void* p) { return p && aligned16(p); };
+}  // extern "C"
+
+namespace {
+
+// Ops 0..2 of mme_text_apply and mme_siglip_text_apply -- token rows, exact attention, the pooled LayerNorm -- one launch
+// each at the text layout L.  What differs: the vocabulary cap, whether attention takes only_block, and the pooled
+// positions, the caller's (eos_pos_host, CLIP) or tokens - 1 for every sequence (null: SigLIP).  A is either hook's args struct.
+template <class A>
+int text_steps_apply(mme_ctx* c, const char* who, const TokenLayout& L, int op, const A* a, int vocab_cap, int only_block, const int32_t* eos_pos_host,
+                     bool pool_last, void* stream) {
+    const HookCheck h{c, who, op};
     const char* bad = nullptr;
-    if (op != 1 && !text_width_built(a->d)) return fail(c, MME_E_ARG, "mme_text_apply: op %d is built for d == 512, d == 768 and d == 1024 (d = %d)", op, a->d);
+    const int n = a->n, T = L.tokens;
+    if (int r = h.crops(n)) return r;
+    if (op != 1 && !text_width_built(a->d)) return fail(c, MME_E_ARG, "%s: op %d is built for d == 512, d == 768 and d == 1024 (d = %d)", who, op, a->d);
     if (op == 0) {
-        if (!vec(a->tok) || !vec(a->pos) || !vec(a->x) || !a->ids_host) bad = "tok, pos, x non-null and 16-byte aligned, ids_host non-null";
-        else if (a->vocab < 1 || a->vocab > TXT_MAX_VOCAB) bad = "1 <= vocab <= 65536";
+        if (!vec16(a->tok) || !vec16(a->pos) || !vec16(a->x) || !a->ids_host) bad = "tok, pos, x non-null and 16-byte aligned, ids_host non-null";
+        else if (a->vocab < 1 || a->vocab > vocab_cap) return fail(c, MME_E_ARG, "%s: op %d needs 1 <= vocab <= %d", who, op, vocab_cap);
     } else if (op == 1) {
-        if (a->heads != 8 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "mme_text_apply: op 1 is built for heads == 8, 12 and 16 (heads = %d)", a->heads);
-        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv, out non-null and 16-byte aligned";
+        if (int r = h.heads(L, a->heads)) return r;
+        if (!L.takes_block(only_block)) return fail(c, MME_E_ARG, "%s: op 1: only_block = %d outside -1..%d", who, only_block, L.blocks - 1);
+        if (!vec16(a->qkv) || !vec16(a->out)) bad = "qkv, out non-null and 16-byte aligned";
     } else {
-        if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta) || !a->eos_pos_host) bad = "x, gamma, beta non-null and 16-byte aligned, eos_pos_host non-null";
-        else if (!a->y && !a->y_f32) bad = "y or y_f32";
-        else if (!aligned16(a->y) || !aligned16(a->y_f32)) bad = "y and y_f32 16-byte aligned";
+        if (!vec16(a->x) || !vec16(a->gamma) || !vec16(a->beta) || (!pool_last && !eos_pos_host))
+            bad = pool_last ? "x, gamma, beta non-null and 16-byte aligned" : "x, gamma, beta non-null and 16-byte aligned, eos_pos_host non-null";
+        else if (int r = h.out_pair(a->y, a->y_f32, "y", "y_f32")) return r;
     }
-    if (bad) return fail(c, MME_E_ARG, "mme_text_apply: op %d needs %s", op, bad);
-    const int n = a->n;
+    if (bad) return h.needs(bad);
     if (op == 0)
-        for (size_t i = 0; i < (size_t)n * TXT_T; ++i)
+        for (size_t i = 0; i < (size_t)n * T; ++i)
             if (a->ids_host[i] < 0 || a->ids_host[i] >= a->vocab)
-                return fail(c, MME_E_ARG, "mme_text_apply: op 0: ids_host[%zu] = %d outside 0..vocab-1 = 0..%d", i, a->ids_host[i], a->vocab - 1);
-    if (op == 2)
+                return fail(c, MME_E_ARG, "%s: op 0: ids_host[%zu] = %d outside 0..vocab-1 = 0..%d", who, i, a->ids_host[i], a->vocab - 1);
+    if (op == 2 && !pool_last)
         for (int b = 0; b < n; ++b)
-            if (a->eos_pos_host[b] < 0 || a->eos_pos_host[b] >= TXT_T)
-                return fail(c, MME_E_ARG, "mme_text_apply: op 2: eos_pos_host[%d] = %d outside 0..%d", b, a->eos_pos_host[b], TXT_T - 1);
+            if (eos_pos_host[b] < 0 || eos_pos_host[b] >= T)
+                return fail(c, MME_E_ARG, "%s: op 2: eos_pos_host[%d] = %d outside 0..%d", who, b, eos_pos_host[b], T - 1);
     if (n == 0) return MME_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int r;
-    if (op != 1) {
-        if ((r = text_dev(c, "mme_text_apply"))) return r;
-        const size_t bytes = (op == 0 ? (size_t)n * TXT_T : (size_t)n) * sizeof(int32_t);
+    if (op != 1) {  // the ids, or the position to pool of every sequence
+        if ((r = text_dev(c, who))) return r;
+        std::vector<int32_t> last;
+        if (op == 2 && pool_last) last.assign((size_t)n, T - 1);
+        const size_t bytes = (op == 0 ? (size_t)n * T : (size_t)n) * sizeof(int32_t);
         if ((r = ensure(c, c->text->apply_ints, bytes))) return r;
-        HIP_TRY(c, hipMemcpyAsync(c->text->apply_ints.p, op == 0 ? a->ids_host : a->eos_pos_host, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->text->apply_ints.p, op == 0 ? a->ids_host : pool_last ? last.data() : eos_pos_host, bytes, hipMemcpyHostToDevice, s));
+        if (pool_last) HIP_TRY(c, hipStreamSynchronize(s));  // `last` is a local
     }
+    const int32_t* ints = op != 1 ? (const int32_t*)c->text->apply_ints.p : nullptr;
     switch (op) {
-        case 0: HIP_TRY(c, launch_text_token_rows(a->tok, a->pos, (const int32_t*)c->text->apply_ints.p, a->x, n, a->d, s)); break;
-        case 1: HIP_TRY(c, launch_attention_causal(a->qkv, a->out, n, a->heads, s)); break;
-        default:
-            HIP_TRY(c, launch_text_eos_pool_ln(a->x, a->gamma, a->beta, (const int32_t*)c->text->apply_ints.p, n, a->d, a->eps, a->y, a->y_f32, s));
-            break;
+        case 0: HIP_TRY(c, launch_text_token_rows(a->tok, a->pos, ints, a->x, n, a->d, s, T)); break;
+        case 1: HIP_TRY(c, launch_attention_exact(a->qkv, a->out, n, T, L.causal, a->heads, s, only_block)); break;
+        default: HIP_TRY(c, launch_text_eos_pool_ln(a->x, a->gamma, a->beta, ints, n, a->d, a->eps, a->y, a->y_f32, s, T)); break;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+// the kernels the text tower adds, one launch each (tests/test_gpu_clip_text.py)
+int mme_text_apply(mme_ctx* c, int op, const mme_text_apply_args* a, void* stream) {
+    if (int r = hook_args(c, "mme_text_apply", a, op, 2)) return r;
+    return text_steps_apply(c, "mme_text_apply", *find_layout(TXT_T), op, a, TXT_MAX_VOCAB, -1, a->eos_pos_host, false, stream);
+}
+
 // the kernels the SigLIP text tower adds, one launch each (tests/test_gpu_siglip_text.py)
 int mme_siglip_text_apply(mme_ctx* c, int op, const mme_siglip_text_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
     const char* who = "mme_siglip_text_apply";
-    if (!a) return fail(c, MME_E_ARG, "%s: null argument", who);
-    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "%s: op %d outside 0..4", who, op);
-    if (a->n < 0 || a->n > (1 << 20)) return fail(c, MME_E_ARG, "%s: n = %d outside 0..2^20", who, a->n);
-    auto vec = [](const void* p) { return p && aligned16(p); };
+    if (int r = hook_args(c, who, a, op, 4)) return r;
+    if (op <= 2) return text_steps_apply(c, who, *find_layout(TXT_T64), op, a, TXT_MAX_VOCAB_SIGLIP, a->only_block, nullptr, true, stream);
+    const HookCheck h{c, who, op};
     const char* bad = nullptr;
-    if ((op == 0 || op == 2) && !text_width_built(a->d)) return fail(c, MME_E_ARG, "%s: op %d is built for d == 512, d == 768 and d == 1024 (d = %d)", who, op, a->d);
-    if (op == 0) {
-        if (!vec(a->tok) || !vec(a->pos) || !vec(a->x) || !a->ids_host) bad = "tok, pos, x non-null and 16-byte aligned, ids_host non-null";
-        else if (a->vocab < 1 || a->vocab > TXT_MAX_VOCAB_SIGLIP) bad = "1 <= vocab <= 262144";
-    } else if (op == 1) {
-        if (a->heads != 8 && a->heads != 12 && a->heads != 16) return fail(c, MME_E_ARG, "%s: op 1 is built for heads == 8, 12 and 16 (heads = %d)", who, a->heads);
-        if (a->only_block < -1 || a->only_block > 1) return fail(c, MME_E_ARG, "%s: op 1: only_block = %d outside -1..1", who, a->only_block);
-        if (!vec(a->qkv) || !vec(a->out)) bad = "qkv, out non-null and 16-byte aligned";
-    } else if (op == 2) {
-        if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta)) bad = "x, gamma, beta non-null and 16-byte aligned";
-        else if (!a->y && !a->y_f32) bad = "y or y_f32";
-        else if (!aligned16(a->y) || !aligned16(a->y_f32)) bad = "y and y_f32 16-byte aligned";
-    } else if (op == 3) {
+    if (int r = h.crops(a->n)) return r;
+    if (op == 3) {
         if (a->p < 64 || (a->p % 64) != 0 || a->p > 1024) return fail(c, MME_E_ARG, "%s: op 3: p = %d; supported: a multiple of 64 up to 1024", who, a->p);
-        if (!vec(a->acc) || !vec(a->bias)) bad = "acc, bias non-null and 16-byte aligned";
-        else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
-        else if (!aligned16(a->emb_f32) || !aligned16(a->emb_bf16)) bad = "emb_f32 and emb_bf16 16-byte aligned";
+        if (!vec16(a->acc) || !vec16(a->bias)) bad = "acc, bias non-null and 16-byte aligned";
+        else if (int r = h.out_pair(a->emb_f32, a->emb_bf16, "emb_f32", "emb_bf16")) return r;
     } else {
         if (a->count < 0) return fail(c, MME_E_ARG, "%s: op 4: count = %lld", who, (long long)a->count);
         if (!a->cos || !a->scores || ((uintptr_t)a->cos & 3) || ((uintptr_t)a->scores & 3)) bad = "cos, scores non-null and 4-byte aligned";
     }
     if (bad) return fail(c, MME_E_ARG, "%s: op %d needs %s", who, op, bad);
-    const int n = a->n;
-    if (op == 0)
-        for (size_t i = 0; i < (size_t)n * TXT_T64; ++i)
-            if (a->ids_host[i] < 0 || a->ids_host[i] >= a->vocab)
-                return fail(c, MME_E_ARG, "%s: op 0: ids_host[%zu] = %d outside 0..vocab-1 = 0..%d", who, i, a->ids_host[i], a->vocab - 1);
-    if (op == 4 ? a->count == 0 : n == 0) return MME_OK;
+    if (op == 4 ? a->count == 0 : a->n == 0) return MME_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    int r;
-    if (op == 0 || op == 2) {  // the ids, or position 63 of every sequence
-        if ((r = text_dev(c, who))) return r;
-        std::vector<int32_t> last;
-        if (op == 2) last.assign((size_t)n, TXT_T64 - 1);
-        const size_t bytes = (op == 0 ? (size_t)n * TXT_T64 : (size_t)n) * sizeof(int32_t);
-        if ((r = ensure(c, c->text->apply_ints, bytes))) return r;
-        HIP_TRY(c, hipMemcpyAsync(c->text->apply_ints.p, op == 0 ? a->ids_host : last.data(), bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipStreamSynchronize(s));  // `last` is a local
-    }
-    switch (op) {
-        case 0: HIP_TRY(c, launch_text_token_rows(a->tok, a->pos, (const int32_t*)c->text->apply_ints.p, a->x, n, a->d, s, TXT_T64)); break;
-        case 1: HIP_TRY(c, launch_attention_t64(a->qkv, a->out, n, a->heads, s, a->only_block)); break;
-        case 2:
-            HIP_TRY(c, launch_text_eos_pool_ln(a->x, a->gamma, a->beta, (const int32_t*)c->text->apply_ints.p, n, a->d, a->eps, a->y, a->y_f32, s, TXT_T64));
-            break;
-        case 3: HIP_TRY(c, launch_bias_l2_rows(a->acc, a->bias, n, a->p, a->emb_f32, a->emb_bf16, s)); break;
-        default: HIP_TRY(c, launch_siglip_scores(a->cos, a->scores, a->count, expf(a->logit_scale), a->logit_bias, s)); break;
-    }
+    if (op == 3) HIP_TRY(c, launch_bias_l2_rows(a->acc, a->bias, a->n, a->p, a->emb_f32, a->emb_bf16, s));
+    else HIP_TRY(c, launch_siglip_scores(a->cos, a->scores, a->count, expf(a->logit_scale), a->logit_bias, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
 }

@@ -283,33 +283,30 @@ int mme_tile_vit_forward(mme_ctx* c, const float* pixel_values, const int32_t* a
 // ---- single launches of the row kernels on caller-owned buffers (tests/test_gpu_tile_rows.py): as mme_rowop_apply, every
 // assumption of the kernels is checked here, so that a bad argument is an MME_E_ARG and never a launch
 int mme_tile_rowop_apply(mme_ctx* c, int op, const mme_tile_rowop_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_tile_rowop_apply: null argument");
-    if (op < 0 || op > 4) return fail(c, MME_E_ARG, "mme_tile_rowop_apply: op %d outside 0..4", op);
-    auto vec = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
+    if (int r = hook_args(c, "mme_tile_rowop_apply", a, op, 4)) return r;
     const int64_t count_max = 0x7fffffff;
     const int64_t count = op == 0 ? a->npatch : op == 3 ? a->out_rows : op == 4 ? (int64_t)a->n : a->rows;
     const char* bad = nullptr;
     int64_t last_row = 0;  // ops 3, 4: the last row of x and of every state the launch reads
     switch (op) {
         case 0:
-            if (!vec(a->pv) || !vec(a->patches)) bad = "pv, patches non-null and 16-byte aligned";
+            if (!vec16(a->pv) || !vec16(a->patches)) bad = "pv, patches non-null and 16-byte aligned";
             else if (count < 0 || count > count_max) bad = "0 <= npatch <= 2^31 - 1";
             break;
         case 1:
-            if (!vec(a->pemb) || !vec(a->cls) || !vec(a->pre) || !vec(a->pos) || !vec(a->tilepos) || !vec(a->gamma) || !vec(a->beta) || !vec(a->x))
+            if (!vec16(a->pemb) || !vec16(a->cls) || !vec16(a->pre) || !vec16(a->pos) || !vec16(a->tilepos) || !vec16(a->gamma) || !vec16(a->beta) || !vec16(a->x))
                 bad = "pemb, cls, pre, pos, tilepos, gamma, beta, x non-null and 16-byte aligned";
             break;
         case 2:
-            if (!vec(a->x) || !vec(a->gamma) || !vec(a->beta) || !vec(a->post)) bad = "x, gamma, beta, post non-null and 16-byte aligned";
+            if (!vec16(a->x) || !vec16(a->gamma) || !vec16(a->beta) || !vec16(a->post)) bad = "x, gamma, beta, post non-null and 16-byte aligned";
             break;
         case 3:
-            if (!vec(a->x) || !vec(a->hidden)) bad = "x, hidden non-null and 16-byte aligned";
+            if (!vec16(a->x) || !vec16(a->hidden)) bad = "x, hidden non-null and 16-byte aligned";
             else if (count < 0 || count > count_max) bad = "0 <= out_rows <= 2^31 - 1";
             else if (count > 0) last_row = (count - 1) / TTOK * TTOKP + (count - 1) % TTOK;
             break;
         default:
-            if (!vec(a->x)) bad = "x non-null and 16-byte aligned";
+            if (!vec16(a->x)) bad = "x non-null and 16-byte aligned";
             else if (!a->emb_f32 && !a->emb_bf16) bad = "emb_f32 or emb_bf16";
             else if (((uintptr_t)a->emb_f32 & 15) || ((uintptr_t)a->emb_bf16 & 15)) bad = "emb_f32 and emb_bf16 16-byte aligned";
             else if (count < 0) bad = "n >= 0";
@@ -324,7 +321,7 @@ int mme_tile_rowop_apply(mme_ctx* c, int op, const mme_tile_rowop_apply_args* a,
     if (!bad && (op == 3 || op == 4)) {
         if (a->ni < 0 || a->ni > TMAXI) bad = "ni in 0..8";
         else if ((a->ni == 0) != (a->inter == nullptr)) bad = "inter null exactly when ni == 0";
-        else if (a->inter && !vec(a->inter)) bad = "inter 16-byte aligned";
+        else if (a->inter && !vec16(a->inter)) bad = "inter 16-byte aligned";
         else if (a->ni > 1 && (a->inter_stride < (last_row + 1) * TD || a->inter_stride > ((int64_t)1 << 40)))
             bad = "inter_stride >= the elements of one state ((last source row + 1) * 1280) and <= 2^40";
     }

@@ -53,6 +53,7 @@ constexpr int TXT_MAX_VOCAB = 65536;
 constexpr int TXT_T64 = 64;                  // SigLIP text towers: 64 positions
 constexpr int TXT_MAX_VOCAB_SIGLIP = 262144;  // SigLIP 32000, SigLIP 2 256000
 constexpr bool text_width_built(int d) { return d == 512 || d == 768 || d == 1024; }
+#include "layouts.h"  // the table of token layouts: one row for each of the sequence lengths above and below
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 

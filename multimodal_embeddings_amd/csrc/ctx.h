@@ -39,24 +39,20 @@ struct LayerDev {
 };
 
 // The ViT @224 geometry a context runs: that of the weights it was loaded with, ViT-B/16 before any load.
-// Supported set (validate_vit_weights, weight_load.hip): image 224, patch 16 or 32, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
-// <= 8192, 1..64 layers.
-// Patch 16 (197 tokens, the compile-time geometry of common.h) or patch 32 (50 tokens: patch32.hip, attention_short.hip).
-// no_cls: a tower without a class token (SigLIP, patch 16 only): 196 tokens (siglip.hip, attention.hip at T = 196).
-// Patch 14 (DINOv2 only, mme_load_dinov2: validate_vit_weights refuses it for every other loader): 16 x 16 patches, 257
-// tokens (dinov2.hip, attention_mid.hip); the im2col row of 588 is padded to 640, the GEMM's multiple of 64.
+// Supported set (validate_vit_weights, weight_load.hip): image 224, heads of 64, hidden 384 / 768 / 1024, mlp % 64 == 0 and
+// <= 8192, 1..64 layers, and a patch size and class token that make an image layout of layouts.h: patch 16 (197 tokens; 196
+// under no_cls: SigLIP), patch 32 (50), patch 14 (257; DINOv2 only; the im2col row of 588 is padded to 640, a multiple of 64).
+// What a layout is -- its kernels, heads, query blocks, pooled row -- is read from layout(), never spelled out per tower.
 struct VitGeom {
     int hidden = VIT_D, layers = VIT_L, heads = VIT_H, mlp = VIT_F;
     int patch = VIT_PATCH;
     bool no_cls = false;
-    int grid() const { return VIT_IMG / patch; }
-    int np() const { return grid() * grid(); }             // patches per crop: 196, 49 or 256
+    int np() const { return (VIT_IMG / patch) * (VIT_IMG / patch); }  // patches per crop: 196, 49 or 256
     int tokens() const { return np() + (no_cls ? 0 : 1); } // 197, 50 or 257; 196 without a class token
+    const TokenLayout& layout() const { return *find_layout(tokens()); }  // the loaders admit no other geometry
     int patch_elems() const { return 3 * patch * patch; }  // the checkpoint's im2col row: 768, 3072 or 588
-    int patch_dim() const { return (patch_elems() + 63) & ~63; }  // K of the patch-embed GEMM: 768, 3072 or 640
+    int patch_dim() const { return (patch_elems() + 63) & ~63; }  // K of the patch-embed GEMM: 768, 3072 or 640 (the row's patch_dim)
     size_t crop_values() const { return (size_t)np() * patch_dim(); }  // bf16 values of one crop's patch matrix: 150 528 at patch 16 and 32, 163 840 at patch 14
-    bool t50() const { return patch == 32; }
-    bool t257() const { return patch == 14; }
 };
 
 enum KClass { KC_PRE = 0, KC_GEMM = 1, KC_LN = 2, KC_ATTN = 3, KC_POOL = 4, KC_COS = 5, KC_PAGE = 6, KC_CLUSTER = 7, KC_NEIGH = 8, KC_COMM = 9 };
@@ -113,8 +109,7 @@ struct mme_ctx {
     int zigzag = 1;           // EncoderPass::zigzag of the image towers (image_tower.hip): 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
-    DevBuf patches32;      // patch 32: the retiled [chunk * 49, 3072] matrix of mme_embed (`patches` stages K1's patch-16 matrix)
-    DevBuf patches14;      // patch 14: the retiled [chunk * 256, 640] matrix of mme_embed
+    DevBuf retiled;        // patch 32 / 14: the retiled [chunk * 49, 3072] / [chunk * 256, 640] matrix of mme_embed (`patches` stages K1's patch-16 matrix)
     DevBuf pooled, projf;  // CLIP tail: bf16 [chunk, hidden] post_layernorm rows, f32 [chunk, proj_dim] projected rows
                            // SigLIP tail: pooled = bf16 [2][chunk, hidden] (map_pool's rows, then the head's residual rows)
     // host staging for crop tables
@@ -160,6 +155,40 @@ inline int embed_dim(const mme_ctx* c) { return c->proj_dim ? c->proj_dim : c->g
     } while (0)
 
 int ensure(mme_ctx* c, DevBuf& b, size_t bytes);
+
+// ---- The checks the single-launch *_apply hooks share, each written once.  who: the hook; op: its op code; L: the layout the
+// hook runs (layouts.h).  A refusal is MME_E_ARG in the hook's own words, 0 is "go on".
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool vec16(const void* p) { return p && aligned16(p); }
+struct HookCheck {
+    mme_ctx* c;
+    const char* who;
+    int op;
+    int needs(const char* what) const { return fail(c, MME_E_ARG, "%s: op %d needs %s", who, op, what); }
+    int crops(int n) const { return n < 0 || n > (1 << 20) ? fail(c, MME_E_ARG, "%s: n = %d outside 0..2^20", who, n) : MME_OK; }
+    int width(int d) const { return vit_width_built(d) ? MME_OK : fail(c, MME_E_ARG, "%s: op %d is built for d == 384, d == 768 and d == 1024 (d = %d)", who, op, d); }
+    int heads(const TokenLayout& L, int h) const { return L.has_heads(h) ? MME_OK : fail(c, MME_E_ARG, "%s: op %d is built for heads == %d, %d and %d (heads = %d)", who, op, L.heads[0], L.heads[1], L.heads[2], h); }
+    // embed rows: the width, then every tensor (cls among them exactly when the layout has a class row)
+    int embed_rows(const TokenLayout& L, int d, const void* acc, const void* bias, const void* pos, const void* cls, const void* x) const {
+        if (int r = width(d)) return r;
+        if (vec16(acc) && vec16(bias) && vec16(pos) && (!L.cls || vec16(cls)) && vec16(x)) return MME_OK;
+        return needs(L.cls ? "acc, bias, pos, cls, x non-null and 16-byte aligned" : "acc, bias, pos, x non-null and 16-byte aligned");
+    }
+    // the pooled LayerNorm: its input, its token, and the two outputs (named nf, nb) of the form with the L2 step
+    int ln_in(const void* x, const void* gamma, const void* beta) const { return vec16(x) && vec16(gamma) && vec16(beta) ? MME_OK : needs("x, gamma, beta non-null and 16-byte aligned"); }
+    int tok(const TokenLayout& L, int t) const { return t < 0 || t >= L.tokens ? fail(c, MME_E_ARG, "%s: op %d needs 0 <= tok <= %d", who, op, L.tokens - 1) : MME_OK; }
+    int out_pair(const void* f32, const void* bf16, const char* nf, const char* nb) const {
+        if (!f32 && !bf16) return fail(c, MME_E_ARG, "%s: op %d needs %s or %s", who, op, nf, nb);
+        return aligned16(f32) && aligned16(bf16) ? MME_OK : fail(c, MME_E_ARG, "%s: op %d needs %s and %s 16-byte aligned", who, op, nf, nb);
+    }
+};
+// what every hook refuses first: no context, no args struct, an op code outside 0..last
+inline int hook_args(mme_ctx* c, const char* who, const void* a, int op, int last) {
+    if (!c) return MME_E_ARG;
+    if (!a) return fail(c, MME_E_ARG, "%s: null argument", who);
+    return op < 0 || op > last ? fail(c, MME_E_ARG, "%s: op %d outside 0..%d", who, op, last) : MME_OK;
+}
+
 // K1 (capi.hip) of n <= chunk crops under the context's resize rule -> patches bf16 [n * 196, 768], the patch-16 matrix
 int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches, hipStream_t s);
 // f32 -> bf16, round to nearest even, NaN kept quiet (bf16_rne_bits of weight_prep.hip is its device form, bit for bit)

@@ -11,8 +11,8 @@
 //                       of the padded weight, and 0 * NaN of a stale buffer would still be NaN).  A run of 14 kx values
 //                       straddles the 16-value runs of the source, so this is a 2-byte gather; a thread forms eight
 //                       destination values and writes 16 bytes, consecutive lanes consecutive bytes.  About 0.6 MB per crop.
-// The rows behind the patch-embed GEMM and the pooled row are rowops.hip's (launch_embed_rows_t257, launch_pool_t257).
-// 64-bit offsets everywhere.
+// The rows behind the patch-embed GEMM and the pooled row are rowops.hip's (launch_embed_rows, launch_pool with tokens = 257).
+// 64-bit offsets everywhere.  retile_to_p14 is launch_retile's (patch32.hip) at patch 14.
 #include "common.h"
 #include "kernels.h"
 
@@ -22,6 +22,7 @@ constexpr int NP256 = 256, GRID16 = 16, P14 = 14;
 constexpr int P14_K = 3 * P14 * P14;  // 588
 constexpr int P14_KP = 640;           // padded K of the patch-embed GEMM
 constexpr int64_t P14_PIECES_PER_CROP = (int64_t)NP256 * P14_KP / 8;  // 16-byte pieces of one crop: 20 480
+static_assert(find_layout(257)->patch == P14 && find_layout(257)->patches == NP256 && find_layout(257)->patch_dim == P14_KP, "layouts.h");
 
 __global__ __launch_bounds__(256) void retile_patches_p14(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int64_t pieces) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void retile_patches_p14(const uint16_t* __rest
 
 }  // namespace
 
-hipError_t launch_retile_p14(const void* patches16, void* patches14, int n, hipStream_t s) {
+hipError_t retile_to_p14(const void* patches16, void* patches14, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const int64_t pieces = (int64_t)n * P14_PIECES_PER_CROP, blocks = (pieces + 255) / 256;
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;

@@ -51,7 +51,7 @@ int stem(EncoderPass& P, const bf16_t* patches, int n) {
     // compile time.  Every other tower (patch 32, patch 14; SigLIP, whose patch row m IS token row m) leaves f32
     // [n * np, D] in the qkv buffer, dead until layer 0, and a row kernel adds bias and position rows in EPI_PATCH's f32
     // order, rounds once and writes the [CLS] rows, where there are any, in the same launch.
-    const bool fused = G.patch == 16 && !G.no_cls;
+    const bool fused = !G.layout().embed_rows;
     GemmArgs g{};
     g.A = patches; g.W = c->patch_w; g.M = n * G.np(); g.N = D; g.K = G.patch_dim();
     int r;
@@ -68,8 +68,7 @@ int stem(EncoderPass& P, const bf16_t* patches, int n) {
         g.outf = (float*)c->qkv.p; g.ldf = D;
         if ((r = P.gemm(EPI_F32, g))) return r;
         Timed t(c, s, KC_LN);
-        if (G.t257()) HIP_TRY(c, launch_embed_rows_t257(g.outf, c->patch_b, c->pos, c->cls, c->x.p, n, D, s));
-        else HIP_TRY(c, launch_embed_rows(g.outf, c->patch_b, c->pos, G.no_cls ? nullptr : c->cls, c->x.p, n, G.tokens(), D, s));
+        HIP_TRY(c, launch_embed_rows(g.outf, c->patch_b, c->pos, G.no_cls ? nullptr : c->cls, c->x.p, n, G.tokens(), D, s));
     }
     if ((r = reset_attn_guards(c, G.layers, s))) return r;
     if (c->clip) {
@@ -130,10 +129,9 @@ int blocks(EncoderPass& P, int n, const PassOut& o) {
         const int only_block = pruned ? o.pool_token / 32 : -1;
         {
             Timed t(c, s, KC_ATTN);
-            if (G.t50() || G.t257()) {  // exact kernels only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
+            if (G.layout().attn != ATTN_LONG) {  // exact kernels only: the guard words stay zero; the walk order is not taken (next_dir keeps the GEMMs' alternation)
                 if (P.zigzag != 2) P.next_dir();
-                if (G.t50()) HIP_TRY(c, launch_attention_t50(c->qkv.p, c->att.p, n, G.heads, s, only_block));
-                else HIP_TRY(c, launch_attention_t257(c->qkv.p, c->att.p, n, G.heads, s, only_block));
+                HIP_TRY(c, launch_attention_exact(c->qkv.p, c->att.p, n, T, false, G.heads, s, only_block));
             } else {
                 HIP_TRY(c, launch_attention(c->qkv.p, c->att.p, n, G.heads, s, c->attn_mode ? (int*)c->attn_guard.p + l : nullptr, c->attn_mode == 2,
                                             only_block, P.zigzag == 2 ? true : P.next_dir() != 0, T));
@@ -203,8 +201,7 @@ int tail(EncoderPass& P, int n, const PassOut& o) {
     if (c->siglip) return siglip_head(P, n, o);
     if (c->proj_dim) return clip_projection(P, n, o);
     Timed t(c, s, KC_POOL);
-    if (c->geom.t257()) HIP_TRY(c, launch_pool_t257(c->x.p, c->lnf_g, c->lnf_b, n, o.pool_token, D, c->ln_eps, o.emb_f32, o.emb_bf16, s));
-    else HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, o.pool_token, D, c->ln_eps, o.emb_f32, o.emb_bf16, s));
+    HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, o.pool_token, D, c->ln_eps, o.emb_f32, o.emb_bf16, s));
     return MME_OK;
 }
 
@@ -232,23 +229,21 @@ int forward_chunk(mme_ctx* c, const bf16_t* patches, int n, const PassOut& o, hi
 // patch-16 matrix into the staging buffer of one chunk (c->patches) and the retile kernel permutes it into dst
 // [m * 49, 3072] (the same bytes per crop) or [m * 256, 640].
 int patches_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int m, bf16_t* dst, hipStream_t s) {
-    const bool t50 = c->geom.t50(), t257 = c->geom.t257();
+    const bool retile = c->geom.patch != VIT_PATCH;
     int r;
-    if ((r = preprocess_chunk(c, pix, offs, hw, m, t50 || t257 ? (bf16_t*)c->patches.p : dst, s))) return r;
-    if (!t50 && !t257) return MME_OK;
+    if ((r = preprocess_chunk(c, pix, offs, hw, m, retile ? (bf16_t*)c->patches.p : dst, s))) return r;
+    if (!retile) return MME_OK;
     Timed t(c, s, KC_PRE);
-    if (t50) HIP_TRY(c, launch_retile_p32(c->patches.p, dst, m, s));
-    else HIP_TRY(c, launch_retile_p14(c->patches.p, dst, m, s));
+    HIP_TRY(c, launch_retile(c->geom.patch, c->patches.p, dst, m, s));
     return MME_OK;
 }
 
-// The buffers of the pixel path (mme_embed, mme_embed_tokens): the workspace, K1's staging buffer, the retiled matrix
+// The buffers of the pixel path (mme_embed, mme_embed_tokens): the workspace, K1's staging buffer, the retiled matrix (ensure() only grows it)
 int ensure_pixel_path(mme_ctx* c) {
     int r;
     if ((r = ensure_workspace(c))) return r;
     if ((r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    if (c->geom.t50() && (r = ensure(c, c->patches32, (size_t)c->chunk * CROP_VALUES * 2))) return r;
-    if (c->geom.t257() && (r = ensure(c, c->patches14, (size_t)c->chunk * c->geom.crop_values() * 2))) return r;
+    if (c->geom.patch != VIT_PATCH && (r = ensure(c, c->retiled, (size_t)c->chunk * c->geom.crop_values() * 2))) return r;
     return MME_OK;
 }
 
@@ -256,7 +251,7 @@ int ensure_pixel_path(mme_ctx* c) {
 // chunk is preprocessed first (K1 -> retile -> pass), behind a synchronise: the crop tables of successive chunks reuse
 // one device buffer.
 int forward_chunks(mme_ctx* c, const bf16_t* patches, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, const PassOut& all, hipStream_t s) {
-    bf16_t* staged = (bf16_t*)(c->geom.t50() ? c->patches32.p : c->geom.t257() ? c->patches14.p : c->patches.p);
+    bf16_t* staged = (bf16_t*)(c->geom.patch != VIT_PATCH ? c->retiled.p : c->patches.p);
     const size_t E = embed_dim(c), tok_values = (size_t)all.ntok * c->geom.hidden;
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
@@ -297,7 +292,7 @@ int mme_preprocess(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const in
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int r;
-    if ((c->geom.t50() || c->geom.t257()) && (r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
+    if (c->geom.patch != VIT_PATCH && (r = ensure(c, c->patches, (size_t)c->chunk * CROP_VALUES * 2))) return r;
     // the crop tables of successive chunks reuse one device buffer: chunk so that stays ordered
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;

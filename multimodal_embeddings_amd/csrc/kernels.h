@@ -70,8 +70,10 @@ hipError_t launch_layernorm(const void* x, const float* gamma, const float* beta
 // summation order: bit-identical to launch_ln_stats_canonical on x afterwards (CLIP's pre_layrnorm, the statistics source
 // of the pass's first folded LayerNorm)
 hipError_t launch_pre_ln(void* x, const float* gamma, const float* beta, int64_t rows, int d, float eps, float* stats, hipStream_t s);
+// The launchers that take `tokens` look the layout up in the table of layouts.h and refuse (hipErrorInvalidValue) a count
+// that is no row, or a row without the operation.
 // LayerNorm of row b*tokens+tok of d values -> bf16 [B, d] (launch_pool without its L2 step: CLIP's post_layernorm);
-// tokens = 197 or 50, 0 <= tok < tokens, else hipErrorInvalidValue
+// tokens: an image layout with a pooled row (197, 50, 257), 0 <= tok < tokens
 hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps, void* y, hipStream_t s);
 // x / max(||x||, 1e-12) as f32 and/or bf16 [rows, p]; p % 64 == 0, p <= 1024.  x: f32 [rows, p]; bf16 [rows, p], widened;
 // or acc f32 [rows, p] + bias [p] (the rows of a GEMM under EPI_F32), the sum formed once in f32
@@ -94,22 +96,22 @@ hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, i
 hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps,
                        float* emb_f32, void* emb_bf16, hipStream_t s);
 // launch_pool over a window of rows per crop: final LayerNorm + L2 of rows b*tokens + tok0 .. + ntok - 1 -> y bf16 [n, ntok, d], each
-// row K8's bf16 output for that pool token bit for bit; tokens = 197, 196, 50 or 257, 0 <= tok0, 1 <= ntok, tok0 + ntok <= tokens
+// row K8's bf16 output for that pool token bit for bit; tokens: any image layout, 0 <= tok0, 1 <= ntok, tok0 + ntok <= tokens
 hipError_t launch_token_rows(const void* x, const float* gamma, const float* beta, int n, int tokens, int tok0, int ntok, int d, float eps, void* y,
                              hipStream_t s);
 // behind a patch-embed GEMM under EPI_F32 (acc f32 [n * patches, d]), one rounding per value: with a class token (cls
-// non-null, tokens = 50, patches = 49) x[b*tokens + 1 + p] = bf16((acc + bias) + pos[1 + p]) and x[b*tokens] = bf16(cls + pos[0]);
-// without one (cls null, tokens = patches = 196) x[b*tokens + p] = bf16((acc + bias) + pos[p]).  Any other pair is hipErrorInvalidValue
+// non-null; tokens = 50 or 257) x[b*tokens + 1 + p] = bf16((acc + bias) + pos[1 + p]) and x[b*tokens] = bf16(cls + pos[0]);
+// without one (cls null; tokens = patches = 196) x[b*tokens + p] = bf16((acc + bias) + pos[p]).  tokens: an image layout whose
+// row sets embed_rows, cls non-null exactly when it has a class row
 hipError_t launch_embed_rows(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int tokens, int d, hipStream_t s);
 // f32 [rows,d] -> L2-normalised bf16 [rows,d]
 hipError_t launch_normalise_rows(const float* x, int64_t rows, int d, void* y, hipStream_t s);
-// fused multi-head attention, T=197, dh=64, `heads` = 6, 12 or 16 (one instantiation each; anything else is
-// hipErrorInvalidValue); qkv [B*197, 3*64*heads] -> out [B*197, 64*heads]
+// fused multi-head attention of the layouts of attention.hip (197 tokens, or 196: towers without a class token), dh=64, `heads` = 6, 12
+// or 16 (one instantiation each); qkv [B*tokens, 3*64*heads] -> out [B*tokens, 64*heads].  Anything else is hipErrorInvalidValue
 // guard: device int, zero before the launch; non-null selects the FAST kernel + the conditional exact re-run (attention.hip)
 // force_redo: the fast kernel raises the guard for every row (test of the re-run path)
 // only_block >= 0: compute and store that query block of 32 only (0..6)
 // reverse: walk the crops from the last one down (same results; zig-zag order of consecutive kernels, EncoderPass::zigzag)
-// tokens: 197, or 196 (towers without a class token: qkv [B*196, ...] -> out [B*196, ...]); anything else is hipErrorInvalidValue
 hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStream_t s, int* guard = nullptr, bool force_redo = false,
                             int only_block = -1, bool reverse = false, int tokens = 197);
 // diagnostic: stamped build of the fast or the exact form, stamps uint64[B][8][8]
@@ -286,45 +288,29 @@ hipError_t launch_tile_output(const void* x, const void* inter, int ni, int64_t 
 hipError_t launch_tile_pool(const void* x, const void* inter, int ni, int64_t inter_stride, int n, float* emb_f32, void* emb_bf16, hipStream_t s);
 hipError_t launch_attention_tiles(const void* qkv, void* out, const int32_t* ntiles_dev, int n, hipStream_t s, int* guard = nullptr, bool force_redo = false);
 
-// ---- CLIP text tower (text_tower.hip, attention_short.hip): 77 tokens, heads of 64, d = 512, 768 or 1024 (else
-// hipErrorInvalidValue)
-// x[b*77 + t, :] = bf16(f32(tok[ids[b*77 + t], :]) + pos[t, :]); tok bf16 [vocab, d], pos f32 [77, d], ids DEVICE int32 [n*77], each
+// ---- the text towers (text_tower.hip, attention_short.hip): 77 tokens under a causal mask (CLIP) or 64 without a mask (SigLIP:
+// last-token pooling and a head with bias, launch_bias_l2_rows); heads of 64, d = 512, 768 or 1024 (else hipErrorInvalidValue).
+// tokens: a text layout of the table
+// x[b*T + t, :] = bf16(f32(tok[ids[b*T + t], :]) + pos[t, :]); tok bf16 [vocab, d], pos f32 [T, d], ids DEVICE int32 [n*T], each
 // 0 <= id < vocab (the caller validates them on the host)
 hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s, int tokens = 77);
-// causal attention, T = 77, dh = 64, heads = 8, 12 or 16: qkv [n*77, 3*64*heads] (Q pre-scaled by dh^-0.5 log2 e) -> out [n*77, 64*heads]
-hipError_t launch_attention_causal(const void* qkv, void* out, int n, int heads, hipStream_t s);
-// LayerNorm (launch_pool_ln's) of row b*tokens + eos_pos[b] (DEVICE int32 [n], each 0..tokens-1) -> y bf16 [n, d] and / or y_f32 [n, d]
+// LayerNorm (launch_pool_ln's) of row b*tokens + eos_pos[b] (DEVICE int32 [n], each 0..tokens-1) -> y bf16 [n, d] and / or y_f32 [n, d];
+// the SigLIP tower pools position 63 of every sequence
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
                                    float* y_f32, hipStream_t s, int tokens = 77);
-// ---- SigLIP text tower (text_tower.hip, attention_short.hip): 64 tokens, no mask, last-token pooling and a head with bias
-// (launch_bias_l2_rows).  launch_text_token_rows / launch_text_eos_pool_ln take tokens = 64 (77 or 64, else
-// hipErrorInvalidValue): pos f32 [64, d]; the tower pools position 63 of every sequence
-// attention without a mask, T = 64, dh = 64, heads = 8, 12 or 16: qkv [n*64, 3*64*heads] (Q pre-scaled) -> out [n*64, 64*heads],
-// exact row maximum; only_block = 0 or 1: that query block of 32 only
-hipError_t launch_attention_t64(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
 // out[i] = 1 / (1 + exp(-(cos[i] * scale + bias))), i < count; out may be cos
 hipError_t launch_siglip_scores(const float* cos, float* out, int64_t count, float scale, float bias, hipStream_t s);
 
-// ---- ViT/32 @224 image towers (patch32.hip, attention_short.hip): 7 x 7 patches of 32 x 32, 50 tokens, heads of 64; the
-// row launchers above with tokens = 50
-// K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-32 matrix [n * 49, 3072] in conv order (c, ky, kx): a pure copy
-hipError_t launch_retile_p32(const void* patches16, void* patches32, int n, hipStream_t s);
-// attention, T = 50, dh = 64, heads = 6, 12 or 16: qkv [n*50, 3*64*heads] (Q pre-scaled) -> out [n*50, 64*heads], exact row
-// maximum; only_block = 0 or 1: that query block of 32 only
-hipError_t launch_attention_t50(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
+// ---- exact attention of the layouts outside attention.hip (attn_short<T, CAUSAL>: 77 causal, 50, 64; attn_mid: 257): dh = 64,
+// qkv [n*T, 3*64*heads] (Q pre-scaled by dh^-0.5 log2 e) -> out [n*T, 64*heads], exact row maximum.  heads: the layout's set;
+// only_block = -1, or a query block of 32 below the layout's `blocks` (that block only; the causal layout takes -1 only)
+hipError_t launch_attention_exact(const void* qkv, void* out, int n, int tokens, bool causal, int heads, hipStream_t s, int only_block = -1);
+hipError_t launch_attn_mid(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block);  // attention_mid.hip, behind it: checked arguments, n > 0
 
-// ---- ViT/14 @224 image towers (DINOv2; dinov2.hip, attention_mid.hip): 16 x 16 patches of 14 x 14, 257 tokens, heads of 64
-// K1's bf16 patch-16 matrix [n * 196, 768] -> the patch-14 matrix [n * 256, 640] in conv order (c, ky, kx), columns 588..639
-// zero on every launch: a 2-byte gather
-hipError_t launch_retile_p14(const void* patches16, void* patches14, int n, hipStream_t s);
-// launch_embed_rows at 257 tokens / 256 patches with a class row (cls non-null, else hipErrorInvalidValue)
-hipError_t launch_embed_rows_t257(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int d, hipStream_t s);
-// launch_pool at 257 tokens: 0 <= tok <= 256
-hipError_t launch_pool_t257(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
-                            hipStream_t s);
-// attention, T = 257, dh = 64, heads = 6, 12 or 16: qkv [n*257, 3*64*heads] (Q pre-scaled) -> out [n*257, 64*heads], exact row
-// maximum; only_block = 0..8: that query block of 32 only
-hipError_t launch_attention_t257(const void* qkv, void* out, int n, int heads, hipStream_t s, int only_block = -1);
+// ---- K1's bf16 patch-16 matrix [n * 196, 768] -> the patch matrix of another patch size in conv order (c, ky, kx):
+// patch 32 (patch32.hip): [n * 49, 3072], a pure copy; patch 14 (dinov2.hip): [n * 256, 640], a 2-byte gather, columns 588..639
+// zero on every launch.  Any other patch is hipErrorInvalidValue
+hipError_t launch_retile(int patch, const void* patches16, void* dst, int n, hipStream_t s);
 
 // ---- SigLIP ViT/16 @224 image towers (siglip.hip; attention: launch_attention with tokens = 196; launch_embed_rows without a
 // class row; launch_l2_rows_bf16 behind the head): 196 tokens, no class token

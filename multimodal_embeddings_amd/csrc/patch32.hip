@@ -8,7 +8,7 @@
 //                         source row      b * 196 + (2 PY + KY / 16) * 14 + 2 PX + KX / 16, column c * 256 + (KY % 16) * 16 + KX % 16
 //                       A pure copy in 16-byte pieces (half a run per thread, consecutive lanes write consecutive bytes).
 // The rows behind the patch-embed GEMM and the pooled row are rowops.hip's (launch_embed_rows, launch_pool_ln, launch_pool
-// with tokens = 50).  64-bit offsets everywhere.
+// with tokens = 50).  64-bit offsets everywhere.  launch_retile, the one launcher of both retile kernels, is at the end.
 #include "common.h"
 #include "kernels.h"
 
@@ -17,6 +17,7 @@ namespace {
 constexpr int NP49 = 49, GRID7 = 7;
 constexpr int P32_DIM = 3 * 32 * 32;            // 3072
 constexpr int64_t PIECES_PER_CROP = NP49 * P32_DIM / 8;  // 16-byte pieces of one crop: 18 816
+static_assert(find_layout(50)->patch == 32 && find_layout(50)->patches == NP49 && find_layout(50)->patch_dim == P32_DIM, "layouts.h");
 
 __global__ __launch_bounds__(256) void retile_patches_p32(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int64_t pieces) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -35,10 +36,13 @@ __global__ __launch_bounds__(256) void retile_patches_p32(const bf16_t* __restri
 
 }  // namespace
 
-hipError_t launch_retile_p32(const void* patches16, void* patches32, int n, hipStream_t s) {
+hipError_t retile_to_p14(const void* patches16, void* patches14, int n, hipStream_t s);  // dinov2.hip
+hipError_t launch_retile(int patch, const void* patches16, void* dst, int n, hipStream_t s) {
+    if (patch == 14) return retile_to_p14(patches16, dst, n, s);
+    if (patch != 32) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     const int64_t pieces = (int64_t)n * PIECES_PER_CROP, blocks = (pieces + 255) / 256;
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(retile_patches_p32, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)patches16, (bf16_t*)patches32, pieces);
+    hipLaunchKernelGGL(retile_patches_p32, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)patches16, (bf16_t*)dst, pieces);
     return hipGetLastError();
 }

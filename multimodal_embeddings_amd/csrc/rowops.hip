@@ -357,53 +357,43 @@ hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, i
     return hipGetLastError();
 }
 
+static_assert(count_layouts([](const TokenLayout& L) { return L.embed_rows; }) == 3 && find_layout(50)->embed_rows && find_layout(196)->embed_rows &&
+                  find_layout(257)->embed_rows, "embed_rows: instantiate the kernel for every layout whose row sets embed_rows");
+
 hipError_t launch_embed_rows(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int tokens, int d, hipStream_t s) {
-    if (!vit_width_built(d) || tokens != (cls ? 50 : 196)) return hipErrorInvalidValue;
+    const TokenLayout* L = find_layout(tokens);
+    if (!vit_width_built(d) || !L || !L->embed_rows || L->cls != (cls != nullptr)) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     const int64_t rows = (int64_t)n * tokens;
     const dim3 grid((unsigned)((rows + 3) / 4));
-    if (cls) {
+    if (tokens == 50) {
         ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<50>{})
-    } else {
+    } else if (tokens == 196) {
         ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<196>{})
+    } else {
+        ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<257>{})
     }
     return hipGetLastError();
 }
 
-// the same rows at 257 tokens / 256 patches with a class row (ViT/14 @224): a launcher of its own, launch_embed_rows keeps its set
-hipError_t launch_embed_rows_t257(const float* acc, const float* bias, const float* pos, const float* cls, void* x, int n, int d, hipStream_t s) {
-    if (!vit_width_built(d) || !cls) return hipErrorInvalidValue;
-    if (n <= 0) return hipSuccess;
-    const int64_t rows = (int64_t)n * 257;
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    ROW_KERNEL_BY_WIDTH(d, embed_rows, grid, s, acc, bias, pos, cls, (bf16_t*)x, rows, Const<257>{})
-    return hipGetLastError();
+// an image layout with a pooled row, and a row of it
+static bool pooled_row(int tokens, int tok) {
+    const TokenLayout* L = find_layout(tokens);
+    return L && L->image() && L->pooled && tok >= 0 && tok < tokens;
 }
-
-// the token layouts of the image path whose pooled row the final LayerNorm reads
-static bool pool_row_ok(int tokens, int tok) { return (tokens == VIT_T || tokens == 50) && tok >= 0 && tok < tokens; }
 
 hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps, float* emb_f32,
                        void* emb_bf16, hipStream_t s) {
-    if (!vit_width_built(d) || !pool_row_ok(tokens, tok)) return hipErrorInvalidValue;
+    if (!vit_width_built(d) || !pooled_row(tokens, tok)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
     ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tokens, tok, eps, emb_f32, (bf16_t*)emb_bf16)
     return hipGetLastError();
 }
 
-// launch_pool at 257 tokens (ViT/14 @224), 0 <= tok <= 256: a launcher of its own, launch_pool keeps its set
-hipError_t launch_pool_t257(const void* x, const float* gamma, const float* beta, int B, int tok, int d, float eps, float* emb_f32, void* emb_bf16,
-                            hipStream_t s) {
-    if (!vit_width_built(d) || tok < 0 || tok > 256) return hipErrorInvalidValue;
-    if (B <= 0) return hipSuccess;
-    ROW_KERNEL_BY_WIDTH(d, pool_ln_l2, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, 257, tok, eps, emb_f32, (bf16_t*)emb_bf16)
-    return hipGetLastError();
-}
-
 hipError_t launch_token_rows(const void* x, const float* gamma, const float* beta, int n, int tokens, int tok0, int ntok, int d, float eps, void* y,
                              hipStream_t s) {
-    const bool layout = tokens == VIT_T || tokens == VIT_NP || tokens == 50 || tokens == 257;
-    if (!vit_width_built(d) || !layout || tok0 < 0 || ntok < 1 || tok0 + ntok > tokens || !y) return hipErrorInvalidValue;
+    const TokenLayout* L = find_layout(tokens);
+    if (!vit_width_built(d) || !L || !L->image() || tok0 < 0 || ntok < 1 || tok0 + ntok > tokens || !y) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     const int64_t rows = (int64_t)n * ntok;
     ROW_KERNEL_BY_WIDTH(d, token_ln_l2, dim3((unsigned)((rows + 3) / 4)), s, (const bf16_t*)x, gamma, beta, rows, tokens, tok0, ntok, eps, (bf16_t*)y)
@@ -418,7 +408,7 @@ hipError_t launch_pre_ln(void* x, const float* gamma, const float* beta, int64_t
 }
 
 hipError_t launch_pool_ln(const void* x, const float* gamma, const float* beta, int B, int tokens, int tok, int d, float eps, void* y, hipStream_t s) {
-    if (!vit_width_built(d) || !pool_row_ok(tokens, tok)) return hipErrorInvalidValue;
+    if (!vit_width_built(d) || !pooled_row(tokens, tok)) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
     ROW_KERNEL_BY_WIDTH(d, pool_ln_rows, dim3((B + 3) / 4), s, (const bf16_t*)x, gamma, beta, B, tokens, tok, eps, (bf16_t*)y)
     return hipGetLastError();

@@ -70,8 +70,12 @@ __global__ __launch_bounds__(256) void siglip_scores(const float* __restrict__ c
 
 }  // namespace
 
+constexpr bool text_layout(const TokenLayout& L) { return !L.image(); }  // the layouts token_rows is instantiated for:
+static_assert(count_layouts(text_layout) == 2 && text_layout(*find_layout(TXT_T)) && text_layout(*find_layout(TXT_T64)), "token_rows: one instantiation per text layout");
+
 hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32_t* ids, void* x, int n, int d, hipStream_t s, int tokens) {
-    if (!text_width_built(d) || (tokens != TXT_T && tokens != TXT_T64)) return hipErrorInvalidValue;
+    const TokenLayout* L = find_layout(tokens);
+    if (!text_width_built(d) || !L || !text_layout(*L)) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     const int64_t rows = (int64_t)n * tokens;
     const dim3 grid((unsigned)((rows + 3) / 4));
@@ -82,7 +86,8 @@ hipError_t launch_text_token_rows(const void* tok, const float* pos, const int32
 
 hipError_t launch_text_eos_pool_ln(const void* x, const float* gamma, const float* beta, const int32_t* eos_pos, int n, int d, float eps, void* y,
                                    float* y_f32, hipStream_t s, int tokens) {
-    if (!text_width_built(d) || (tokens != TXT_T && tokens != TXT_T64)) return hipErrorInvalidValue;
+    const TokenLayout* L = find_layout(tokens);
+    if (!text_width_built(d) || !L || !text_layout(*L) || !L->pooled) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
     ROW_KERNEL_BY_WIDTH(d, eos_pool_ln_rows, dim3((n + 3) / 4), s, (const bf16_t*)x, gamma, beta, eos_pos, n, tokens, eps, (bf16_t*)y, y_f32)
     return hipGetLastError();

@@ -356,7 +356,7 @@ int prepare_vit(mme_ctx* c, P& p, const mme_vit_weights& w, const mme_dinov2_sca
     if ((r = w.patch_b ? plain(w.patch_b, D, &c->patch_b) : p.zeros(D, &c->patch_b))) return r;  // CLIP: a zero table
     if ((r = plain(w.lnf_g, D, &c->lnf_g))) return r;
     if ((r = plain(w.lnf_b, D, &c->lnf_b))) return r;
-    if (vg.t257()) {
+    if (vg.patch_elems() != vg.patch_dim()) {  // patch 14: 588 -> 640
         if ((r = p.padded(w.patch_w, (int)D, vg.patch_elems(), vg.patch_dim(), &c->patch_w))) return r;
     } else if ((r = plain_bf16(w.patch_w, rD, (size_t)vg.patch_dim(), &c->patch_w))) return r;
     // The attention kernel takes its scores in log2 units straight from the matrix pipe (attention.hip, PRESCALED):

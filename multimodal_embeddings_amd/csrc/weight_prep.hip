@@ -453,12 +453,9 @@ int64_t mme_weights_read(mme_ctx* c, int index, int64_t cap_bytes, void* dst_hos
 // mme_rowop_apply, every assumption of the launchers and kernels is checked here, so that a bad argument is an MME_E_ARG
 // and never a launch
 int mme_weight_prep_apply(mme_ctx* c, int op, const mme_weight_prep_apply_args* a, void* stream) {
-    if (!c) return MME_E_ARG;
-    if (!a) return fail(c, MME_E_ARG, "mme_weight_prep_apply: null argument");
-    if (op < 0 || op > 2) return fail(c, MME_E_ARG, "mme_weight_prep_apply: op %d outside 0..2", op);
+    if (int r = hook_args(c, "mme_weight_prep_apply", a, op, 2)) return r;
     if (a->dtype < MME_DT_F32 || a->dtype > MME_DT_F16)
         return fail(c, MME_E_ARG, "mme_weight_prep_apply: dtype %d (MME_DT_F32 = 0, MME_DT_BF16 = 1, MME_DT_F16 = 2)", a->dtype);
-    auto vec = [](const void* p) { return p && ((uintptr_t)p & 15) == 0; };
     const size_t esz = a->dtype == MME_DT_F32 ? 4 : 2;
     const char* bad = nullptr;
     WpFoldSrc srcs[3] = {};
@@ -466,20 +463,20 @@ int mme_weight_prep_apply(mme_ctx* c, int op, const mme_weight_prep_apply_args* 
     switch (op) {
         case 0:
             if (a->count < 0 || a->count > ((int64_t)1 << 40) || (a->count % 8) != 0) bad = "0 <= count <= 2^40, count % 8 == 0";
-            else if (!vec(a->src) || !vec(a->dst)) bad = "src, dst non-null and 16-byte aligned";
+            else if (!vec16(a->src) || !vec16(a->dst)) bad = "src, dst non-null and 16-byte aligned";
             break;
         case 1:
             if (a->rows < 1 || a->cols < 4 || (a->cols % 4) != 0 || (a->cols_padded % 4) != 0 || a->cols_padded < a->cols)
                 bad = "rows >= 1, cols >= 4, cols % 4 == 0, cols_padded % 4 == 0, cols_padded >= cols";
-            else if (!vec(a->src) || !vec(a->dst)) bad = "src, dst non-null and 16-byte aligned";
+            else if (!vec16(a->src) || !vec16(a->dst)) bad = "src, dst non-null and 16-byte aligned";
             break;
         default:
             if (a->nsrc < 1 || a->nsrc > 3) bad = "nsrc in 1..3";
             else if (a->cols < FOLD_KT || (a->cols % FOLD_KT) != 0 || a->cols > FOLD_MAXK) bad = "cols a multiple of 64, 64 <= cols <= 1280";
-            else if (!vec(a->gamma) || !vec(a->beta) || !vec(a->wf) || !vec(a->cs) || !vec(a->bf)) bad = "gamma, beta, wf, cs, bf non-null and 16-byte aligned";
+            else if (!vec16(a->gamma) || !vec16(a->beta) || !vec16(a->wf) || !vec16(a->cs) || !vec16(a->bf)) bad = "gamma, beta, wf, cs, bf non-null and 16-byte aligned";
             for (int i = 0; !bad && i < a->nsrc; ++i) {
                 if (a->src_rows[i] < FOLD_ROWS || (a->src_rows[i] % FOLD_ROWS) != 0 || a->src_rows[i] > (1 << 24)) bad = "every rows[i] a non-zero multiple of 64, <= 2^24";
-                else if (!vec(a->w[i])) bad = "every w[i] non-null and 16-byte aligned";
+                else if (!vec16(a->w[i])) bad = "every w[i] non-null and 16-byte aligned";
                 else if ((uintptr_t)a->b[i] % esz) bad = "every b[i] null or aligned to its element";
                 srcs[i] = WpFoldSrc{a->w[i], a->b[i], a->src_scale[i], a->src_scaled[i] ? 1 : 0};
                 rows[i] = (size_t)a->src_rows[i];

@@ -25,8 +25,8 @@ reach every branch of the shared block:
           0 / 1 / 2, on a 1-tile and a 4-tile image.
   rows    every row launcher once through the *_apply hooks, at every width it is built for: LayerNorm, statistics,
           class rows, pooled LayerNorm with and without the L2 step at the first and the last token of the 197- and the
-          50-token layout, pre-LN, the embed rows of both layouts without a class token and with one (2 crops: the
-          class row of the second is reached), the EOS pooling of both text layouts, the three L2 forms at p = 64 / 320 /
+          50-token layout and with it of the 257-token layout, pre-LN, the embed rows of the 196-token layout (no class
+          token) and of the 50- and the 257-token layout (2 crops: the class row of the second is reached), the EOS pooling of both text layouts, the three L2 forms at p = 64 / 320 /
           1024 (one partly filled column group, a partly filled second one, all four).  5 rows or sequences: two
           workgroups of four waves, the second with one live wave.  Every output buffer is hashed WITH a sentinel-filled
           margin behind it, untouched rows included.
@@ -208,7 +208,15 @@ def main(argv=None) -> int:
                     emit(f"rows pool_ln tokens={tokens} tok={tok} d={d}", y.raw)
                     pool_l2(x=xt, gamma=gamma, beta=beta, emb_f32=e32.view, emb_bf16=e16.view, tok=tok, d=d, eps=1e-12)
                     emit(f"rows pool_ln_l2 tokens={tokens} tok={tok} d={d}", e32.raw, e16.raw)
+            xt = bf(N * 257, d)  # the 257-token layout has no pool_ln hook: the form with the L2 step only
+            for tok in (0, 256):
+                e32, e16 = Out(F, N, d), Out(BF, N, d)
+                e.dinov2_apply("pool_ln_l2", x=xt, gamma=gamma, beta=beta, emb_f32=e32.view, emb_bf16=e16.view, n=N, tok=tok, d=d, eps=1e-12)
+                emit(f"rows pool_ln_l2 tokens=257 tok={tok} d={d}", e32.raw, e16.raw)
             bias = f32(d)
+            xo = Out(BF, 2 * 257, d)
+            e.dinov2_apply("embed_rows", acc=f32(2 * 256, d), bias=bias, pos=f32(257, d), cls=f32(d), x=xo.view, n=2, d=d)
+            emit(f"rows embed_rows tokens=257 d={d}", xo.raw)
             xo = Out(BF, 2 * 50, d)
             e.vit32_apply("embed_rows", acc=f32(2 * 49, d), bias=bias, pos=f32(50, d), cls=f32(d), x=xo.view, n=2, d=d)
             emit(f"rows embed_rows tokens=50 d={d}", xo.raw)
