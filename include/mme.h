@@ -13,6 +13,19 @@
  *   - "dev" pointers are device (HBM) pointers owned by the caller, "host" pointers are
  *     ordinary host memory; all launches are asynchronous on `stream` (a hipStream_t
  *     passed as void*; NULL = the default stream) unless the name ends in _sync;
+ *   - ordering (held by tests/test_gpu_streams.py for every entry point): every step a result depends on -- kernels, memsets,
+ *     copies, the first-call initialisation of context state -- is enqueued on `stream` and on no other, so outputs are
+ *     complete once `stream` has reached the end of the call, whatever the null stream or any other stream is doing.  The
+ *     context's scratch (crop descriptors, band lists, resampling tables, the cosine workspace K12 / K14 / K15 / K16 share, the
+ *     guard words, the staging vectors on the host) is SHARED between calls: calls on one context must be ordered with respect
+ *     to one another -- issued on the same stream, or on different streams with an event dependency from each call to the
+ *     next.  Two calls back to back on one stream need no host synchronisation between them.  Calls on two streams with no
+ *     dependency between them need two contexts;
+ *   - caller HOST arrays (crop offsets and sizes, boxes, token ids, page offsets, init_rows, tile counts, aspect-ratio ids)
+ *     are read before the call returns: the caller may overwrite or free them on return, while the device work is pending.
+ *     Host OUTPUT arrays are complete on return (such entry points wait for `stream` and say so);
+ *   - an entry point may make the host wait where its text says so, and when scratch has to grow: growing a buffer that
+ *     already exists waits for the whole device before the old one is freed.  Steady-state calls of one shape do not wait;
  *   - bf16 = 16-bit brain float stored as uint16_t.
  */
 #ifndef MME_H
