@@ -493,14 +493,45 @@ int mme_normalisation_form(mme_ctx* ctx, int32_t* exact, float a[3], float b[3])
  *     pass), then the centre crop top = (new_h - 224) / 2, left = (new_w - 224) / 2 (image_processing_backends.py:
  *     602-617 PilBackend.center_crop -> image_transforms.py:445 center_crop).  No padding ever; the uint8 window is
  *     bit-equal to Pillow's, only the window is computed.  Normalisation and the patch layout are the same as under rule 0.
- * A batch of 224 x 224 crops only is the identity under both rules and takes the same kernels.
+ *   MME_RESIZE_SPEC (2): a rule with parameters, what a checkpoint's preprocessor_config.json asks for; made current by
+ *     mme_set_resize_spec below and by nothing else: mme_set_resize_rule(2) is refused.  Rule 1 is the spec
+ *     {MME_RESIZE_MODE_SHORTEST_EDGE, 224, 0, 3}, run by the same kernels.
+ * A batch of 224 x 224 crops only is the identity under rules 0 and 1 and takes the same kernels.
  * Any other value is MME_E_ARG; mme_last_error names the value and the supported set.
  * The rule is a property of how the caller wants pixels made, like mme_set_normalisation: no weight load
  * (mme_load_vit*, mme_load_clip*, mme_load_tile_vit*) resets or changes it.  Crops stay limited to 1..8000 per side. */
-enum { MME_RESIZE_FIT_PAD = 0, MME_RESIZE_CLIP = 1 };
+enum { MME_RESIZE_FIT_PAD = 0, MME_RESIZE_CLIP = 1, MME_RESIZE_SPEC = 2 };
 int mme_set_resize_rule(mme_ctx* ctx, int rule);
 /* *rule = the current rule (read-only, no device work). */
 int mme_resize_rule(mme_ctx* ctx, int32_t* rule);
+
+/* The rule as a spec: what the Pillow backends of transformers' image processors do before rescale and normalise
+ * (image_processing_backends.py PilBackend.resize -> center_crop).
+ *   1. The WHOLE crop is resized with Pillow's 8-bit filter `resample` (2 BILINEAR, 3 BICUBIC; libImaging/Resample.c) to
+ *      MME_RESIZE_MODE_EXACT:          height x width, the aspect not kept (ViTImageProcessor, SiglipImageProcessor: 224 x 224;
+ *                                      DeiT-style processors: 256 x 256);
+ *      MME_RESIZE_MODE_SHORTEST_EDGE:  the short edge becomes `height`, the long edge int(height * long / short) in f64, in
+ *                                      that order of operations (BitImageProcessor as DINOv2 directories configure it: 256;
+ *                                      CLIPImageProcessor: 224).  `width` must be 0.
+ *      An axis whose size does not change is not filtered.
+ *   2. The centre window 224 x 224 of the resized image: top = (new_h - 224) / 2, left = (new_w - 224) / 2 (the origin for an
+ *      exact 224 x 224 target).  Only that window is ever computed; its uint8 pixels are bit-equal to Pillow's.
+ * Supported: height (and, in exact mode, width) 224..512; resample 2 or 3.  Anything else is MME_E_ARG, mme_last_error names
+ * the field, its value and the supported set, and the context keeps the rule it had.  On success mme_resize_rule reports
+ * MME_RESIZE_SPEC until mme_set_resize_rule(0 | 1) leaves the spec again.  Like the two fixed rules: no weight load touches
+ * it, mme_preprocess_tiles ignores it, crops stay 1..8000 per side.  A batch of 224 x 224 crops only is the identity under
+ * exact 224 x 224 and under shortest edge 224, and under no other spec (shortest edge 256 resizes it to 256 x 256 and crops).
+ * mme_get_resize_spec: *out = the current spec; MME_E_STATE unless a spec is the current rule.  (A C function cannot carry the
+ * name of the struct's typedef, hence `get`.) */
+enum { MME_RESIZE_MODE_SHORTEST_EDGE = 0, MME_RESIZE_MODE_EXACT = 1 };
+typedef struct mme_resize_spec {
+    int32_t mode;     /* MME_RESIZE_MODE_SHORTEST_EDGE = 0, MME_RESIZE_MODE_EXACT = 1 */
+    int32_t height;   /* EXACT: height of the resized image; SHORTEST_EDGE: the edge */
+    int32_t width;    /* EXACT: width of the resized image; SHORTEST_EDGE: 0 */
+    int32_t resample; /* Pillow's numbers: 2 BILINEAR, 3 BICUBIC */
+} mme_resize_spec;
+int mme_set_resize_spec(mme_ctx* ctx, const mme_resize_spec* spec);
+int mme_get_resize_spec(mme_ctx* ctx, mme_resize_spec* out);
 
 /* Rows of the internal activation workspace = crops per encoder pass (default 4096: one pass
  * for the headline batch; 11.6 GiB of workspace at ViT-B/16; larger passes lose less to tile quantisation).

@@ -188,6 +188,10 @@ class _KmeansApplyArgs(C.Structure):  # mme_kmeans_apply_args
     ]
 
 
+class _ResizeSpec(C.Structure):  # mme_resize_spec
+    _fields_ = [(f, C.c_int32) for f in ("mode", "height", "width", "resample")]
+
+
 class _SilhouetteOut(C.Structure):  # mme_silhouette_out
     _fields_ = [(f, C.c_void_p) for f in ("sample", "cluster", "score", "info", "sums", "counts")]
 
@@ -229,6 +233,8 @@ EXPORTS = {
     "mme_normalisation_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mme_set_resize_rule": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_resize_rule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_set_resize_spec": (C.c_int, [C.c_void_p, C.POINTER(_ResizeSpec)]),
+    "mme_get_resize_spec": (C.c_int, [C.c_void_p, C.POINTER(_ResizeSpec)]),
     "mme_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_gemm_variant": (C.c_int, [C.c_void_p, C.c_int]),
     "mme_set_ln_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -291,6 +297,37 @@ EXPORTS = {
     "mme_profile_reset": (C.c_int, [C.c_void_p]),
     "mme_profile_read_sync": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
 }
+
+RESIZE_SPEC_RULE = 2  # MME_RESIZE_SPEC: a rule with parameters, so not one of Engine.RESIZE_RULES' names
+RESIZE_MODES = {"shortest_edge": 0, "exact": 1}  # MME_RESIZE_MODE_*
+RESIZE_MODES_BY_NUMBER = {v: k for k, v in RESIZE_MODES.items()}
+
+
+@dataclasses.dataclass(frozen=True)
+class ResizeSpec:
+    """mme_resize_spec: how a crop becomes 224 x 224 pixels the way a checkpoint's image processor makes them.  The whole crop
+    is resized with Pillow's `resample` (2 BILINEAR, 3 BICUBIC) -- mode "exact": to height x width, the aspect not kept; mode
+    "shortest_edge": the short edge to `height`, the long edge to int(height * long / short), `width` 0 -- and the 224 x 224
+    centre window of the result is taken.  `ResizeSpec.of("shortest_edge", 256, 3)` is DINOv2's, `.of("exact", 224, 3)` SigLIP's,
+    `.of("exact", 224, 2)` ViT's."""
+    mode: str
+    height: int
+    width: int
+    resample: int
+
+    @classmethod
+    def of(cls, mode, size, resample):
+        if mode == "exact":
+            h, w = (size, size) if isinstance(size, int) else tuple(size)
+            return cls("exact", h, w, resample)
+        return cls(mode, size, 0, resample)
+
+    @property
+    def mode_number(self):
+        if self.mode not in RESIZE_MODES and not isinstance(self.mode, int):
+            raise MmeError(f"ResizeSpec mode = {self.mode!r}; supported {sorted(RESIZE_MODES)}")
+        return RESIZE_MODES.get(self.mode, self.mode)
+
 
 _lib = None
 
@@ -976,9 +1013,33 @@ class Engine:
 
     @property
     def resize_rule(self) -> str:
+        """"fit_pad", "clip", or "spec" while a `ResizeSpec` is the rule (`resize_spec`)."""
         v = C.c_int32(-1)
         self._check(self.lib.mme_resize_rule(self.h, C.byref(v)), "mme_resize_rule")
-        return {n: k for k, n in self.RESIZE_RULES.items()}[v.value]
+        return {RESIZE_SPEC_RULE: "spec", **{n: k for k, n in self.RESIZE_RULES.items()}}[v.value]
+
+    def set_resize_spec(self, mode, size=None, resample=None):
+        """Make a spec the rule of `preprocess` / `embed` (mme_set_resize_spec): resize the whole crop with Pillow's filter
+        `resample` (2 BILINEAR, 3 BICUBIC) to `size`, then take the 224 x 224 centre window.  `mode` "shortest_edge" with
+        `size` the edge, or "exact" with `size` = (height, width) or one int for both.  A `ResizeSpec` may be passed alone.
+        The library refuses what it does not run (edges outside 224..512, other filters) and the rule then stays as it was."""
+        spec = mode if isinstance(mode, ResizeSpec) else ResizeSpec.of(mode, size, resample)
+        try:
+            raw = _ResizeSpec(int(spec.mode_number), int(spec.height), int(spec.width), int(spec.resample))
+        except (TypeError, ValueError) as e:
+            raise MmeError(f"{spec!r}: mode, size and resample must be integers ({e})") from None
+        self._check(self.lib.mme_set_resize_spec(self.h, C.byref(raw)), "mme_set_resize_spec")
+
+    @property
+    def resize_spec(self):
+        """The `ResizeSpec` that is the current rule, or None under "fit_pad" and "clip"."""
+        v = C.c_int32(-1)
+        self._check(self.lib.mme_resize_rule(self.h, C.byref(v)), "mme_resize_rule")
+        if v.value != RESIZE_SPEC_RULE:
+            return None
+        raw = _ResizeSpec()
+        self._check(self.lib.mme_get_resize_spec(self.h, C.byref(raw)), "mme_get_resize_spec")
+        return ResizeSpec(RESIZE_MODES_BY_NUMBER.get(raw.mode, raw.mode), raw.height, raw.width, raw.resample)
 
     def set_gemm_variant(self, variant: int):
         self._check(self.lib.mme_set_gemm_variant(self.h, int(variant)), "mme_set_gemm_variant")

@@ -30,7 +30,7 @@ import re
 from dataclasses import dataclass, field
 
 from . import config
-from ._lib import MmeError
+from ._lib import MmeError, ResizeSpec
 from .weights import (CLIP_B16, CLIP_TEXT_B, DINOV2_B14, SIGLIP_B16, SIGLIP_LOGIT_KEYS, SIGLIP_TEXT_B, TILE_VIT, VIT_B16, CLIPGeometry, CLIPTextGeometry,
                       Dinov2Geometry, SiglipGeometry, SiglipTextGeometry, TileViTGeometry, ViTGeometry, clip_geometry_problem, clip_text_geometry_problem,
                       dinov2_geometry_problem, siglip_geometry_problem, siglip_text_geometry_problem, vit_geometry_problem)
@@ -56,6 +56,7 @@ class Checkpoint:
     geometry: object         # ViTGeometry | TileViTGeometry
     image_mean: tuple | None = None
     image_std: tuple | None = None
+    resize_spec: object = None  # the ResizeSpec of preprocessor_config.json, read under resize_rule = "checkpoint" only
     source: list = field(default_factory=list)  # files read
     extra: dict = field(default_factory=dict)   # "dinov2": {"position_table": f32 [257, D], the interpolated table the device holds}
 
@@ -373,11 +374,18 @@ RESIZE_RULES = ("fit_pad", "clip")  # _lib.Engine.RESIZE_RULES / MME_RESIZE_* (i
 CLIP_RULE_ENCODERS = ("vit_b16", "vit", "clip", "siglip", "dinov2")  # the single-tile encoders K1's "clip" rule feeds
 
 
-def check_resize_rule(resize_rule, encoder: str) -> str:
-    """None -> "fit_pad"; raises for an unknown rule and for "clip" with the tile encoder."""
+def check_resize_rule(resize_rule, encoder: str):
+    """None -> "fit_pad"; "checkpoint" and a ResizeSpec pass as they are; raises for an unknown rule and for "clip",
+    "checkpoint" or a ResizeSpec with the tile encoder."""
     rule = "fit_pad" if resize_rule is None else resize_rule
+    if isinstance(rule, ResizeSpec) or rule == "checkpoint":
+        if encoder not in CLIP_RULE_ENCODERS:
+            raise MmeError(f"resize_rule = {resize_rule!r} (a resize of the whole crop + centre crop to 224 x 224) feeds the single-tile encoders "
+                           f"{CLIP_RULE_ENCODERS} only; encoder = {encoder!r} has its own multi-tile preprocessing")
+        return rule
     if rule not in RESIZE_RULES:
-        raise MmeError(f"resize_rule = {resize_rule!r}; supported {RESIZE_RULES} (None means 'fit_pad')")
+        raise MmeError(f"resize_rule = {resize_rule!r}; supported {RESIZE_RULES} (None means 'fit_pad'), 'checkpoint' (what the directory's "
+                       "preprocessor_config.json asks for) and a ResizeSpec")
     if rule == "clip" and encoder not in CLIP_RULE_ENCODERS:
         raise MmeError(f"resize_rule = 'clip' (shortest-edge BICUBIC resize + centre crop to 224 x 224) feeds the single-tile encoders "
                        f"{CLIP_RULE_ENCODERS} only; encoder = {encoder!r} has its own multi-tile preprocessing")
@@ -401,8 +409,75 @@ def _check_clip_rule_fields(pc: dict, where: str):
         raise MmeError(f"{where}: crop_size = {crop!r}; resize_rule = 'clip' supports crop_size = 224 x 224 ({{'height': 224, 'width': 224}} or 224) only")
 
 
-def _read_preprocessor(path: str, encoder: str, resize_rule: str = "fit_pad"):
-    """preprocessor_config.json -> (mean, std) or (None, None); raises for what K1 cannot honour under `resize_rule`."""
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+SPEC_EDGES = (224, 512)  # mme_set_resize_spec: edge, height and width of the resized image
+
+
+def resize_spec_of(preprocessor_config: dict, where: str = "preprocessor_config.json") -> ResizeSpec:
+    """The ResizeSpec a preprocessor_config.json (the dict) asks for: what the Pillow backend of its image processor does
+    before rescale and normalise -- resize the whole crop (`size`, `resample`), then `center_crop`.  Raises MmeError naming
+    the field, its value and the supported set for everything K1 does not run.  `where` names the file in the messages."""
+    pc = preprocessor_config
+    kind = str(pc.get("image_processor_type", ""))
+    if "Mllama" in kind or "max_image_tiles" in pc:
+        raise MmeError(f"{where}: image_processor_type = {kind!r}; a Mllama processor tiles the image, which no resize spec describes: supported "
+                       "encoder='mllama_tiles' (its own preprocessing) or the default fit-and-pad rule")
+    if "max_num_patches" in pc:
+        raise MmeError(f"{where}: max_num_patches = {pc['max_num_patches']!r}; a SigLIP 2 NaFlex processor keeps the aspect on a variable patch grid: "
+                       "supported fixed-resolution processors only (size + resample, no max_num_patches)")
+    if pc.get("do_resize", True) is False:
+        raise MmeError(f"{where}: do_resize = False; a resize spec always resizes (supported: do_resize = True)")
+    if pc.get("do_pad"):
+        raise MmeError(f"{where}: do_pad = {pc['do_pad']!r}; supported: no padding (do_pad absent or False)")
+    if pc.get("do_rescale", True) is not True:
+        raise MmeError(f"{where}: do_rescale = {pc.get('do_rescale')!r}; K1 always rescales by 1/255 (supported: do_rescale = True)")
+    rf = pc.get("rescale_factor", 1.0 / 255.0)
+    if not isinstance(rf, (int, float)) or isinstance(rf, bool) or abs(float(rf) - 1.0 / 255.0) > 1e-9:
+        raise MmeError(f"{where}: rescale_factor = {rf!r}; supported 1/255 = {1.0 / 255.0!r}")
+    resample = pc.get("resample")
+    if not _is_int(resample) or resample not in (2, 3):
+        raise MmeError(f"{where}: resample = {resample!r}; supported 2 (Pillow BILINEAR) and 3 (Pillow BICUBIC)")
+    size = pc.get("size")
+    lo, hi = SPEC_EDGES
+    if _is_int(size) or (isinstance(size, dict) and set(size) == {"shortest_edge"} and _is_int(size["shortest_edge"])):
+        edge = size if _is_int(size) else size["shortest_edge"]
+        mode, height, width = "shortest_edge", edge, 0
+        ok = lo <= edge <= hi
+    elif isinstance(size, dict) and set(size) == {"height", "width"} and _is_int(size["height"]) and _is_int(size["width"]):
+        mode, height, width = "exact", size["height"], size["width"]
+        ok = lo <= height <= hi and lo <= width <= hi
+    else:
+        ok = False
+    if not ok:
+        raise MmeError(f"{where}: size = {size!r}; supported {{'shortest_edge': S}}, the bare int S or {{'height': H, 'width': W}} with S, H, W in {lo}..{hi}")
+    crop_on = pc.get("do_center_crop", False)
+    if crop_on is True:
+        crop = pc.get("crop_size")
+        if not (crop == {"height": 224, "width": 224} or (_is_int(crop) and crop == 224)):
+            raise MmeError(f"{where}: crop_size = {crop!r}; supported 224 x 224 ({{'height': 224, 'width': 224}} or 224)")
+    elif crop_on not in (False, None):
+        raise MmeError(f"{where}: do_center_crop = {crop_on!r}; supported True and False")
+    elif mode == "shortest_edge":
+        raise MmeError(f"{where}: do_center_crop = {pc.get('do_center_crop')!r} with size = {size!r}; a shortest-edge resize leaves no 224 x 224 image: "
+                       "supported do_center_crop = True with crop_size 224 x 224")
+    elif (height, width) != (224, 224):
+        raise MmeError(f"{where}: do_center_crop = {pc.get('do_center_crop')!r} with size = {size!r}; without a centre crop the resized image is the "
+                       "canvas: supported size 224 x 224, or do_center_crop = True with crop_size 224 x 224")
+    return ResizeSpec(mode, height, width, resample)
+
+
+def _read_preprocessor(path: str, encoder: str, resize_rule="fit_pad"):
+    """preprocessor_config.json -> (mean, std, spec): mean / std or None / None; spec is the file's ResizeSpec under
+    resize_rule = "checkpoint", else None.  Raises for what K1 cannot honour under `resize_rule`."""
+    spec = resize_spec_of(_load_json(path), os.path.basename(path)) if resize_rule == "checkpoint" else None  # its refusals speak of the spec
+    mean, std = _read_mean_std(path, encoder, resize_rule)
+    return mean, std, spec
+
+
+def _read_mean_std(path: str, encoder: str, resize_rule):
     global _warned_resize_rule
     pc = _load_json(path)
     where = os.path.basename(path)
@@ -416,6 +491,8 @@ def _read_preprocessor(path: str, encoder: str, resize_rule: str = "fit_pad"):
     if resize_rule == "clip":
         _check_clip_rule_fields(pc, where)
         return _mean_std(pc, where)
+    if resize_rule == "checkpoint" or isinstance(resize_rule, ResizeSpec):  # the caller's rule, not the fit-and-pad one: nothing to warn of
+        return _mean_std(pc, where)
     resample = pc.get("resample", 2)
     clip_rule = encoder == "clip" and (resample == 3 or pc.get("do_center_crop") or "crop_size" in pc)
     if encoder == "dinov2":
@@ -423,16 +500,16 @@ def _read_preprocessor(path: str, encoder: str, resize_rule: str = "fit_pad"):
         if resample != 2 or pc.get("do_center_crop") or "crop_size" in pc:
             named = [f"{k} = {pc[k]!r}" for k in ("image_processor_type", "resample", "size", "do_center_crop", "crop_size") if k in pc]
             logger.warning(f"{where}: {', '.join(named) or 'the file'} asks for DINOv2's own preprocessing, a shortest-edge-256 BICUBIC resize and a "
-                           "224 x 224 centre crop; K1 does not run that rule: it keeps the aspect-preserving fit into 224 x 224 with zero padding "
-                           "(or resize_rule='clip' on request) and applies only the checkpoint's image_mean / image_std")
+                           "224 x 224 centre crop; K1 does not run that rule by default: it keeps the aspect-preserving fit into 224 x 224 with zero padding "
+                           "(resize_rule='checkpoint' runs the file's own rule, 'clip' CLIP's) and applies only the checkpoint's image_mean / image_std")
         return _mean_std(pc, where)
     if encoder == "siglip":
         # SiglipImageProcessor resizes to size x size WITHOUT keeping the aspect (any resample): not a rule K1 has
         if "Siglip" in str(pc.get("image_processor_type", "")) or resample != 2:
             named = [f"{k} = {pc[k]!r}" for k in ("image_processor_type", "resample", "size") if k in pc]
             logger.warning(f"{where}: {', '.join(named) or 'the file'} asks for SigLIP's own preprocessing, a plain resize to 224 x 224 that does not keep the "
-                           "aspect ratio; K1 does not run that rule: it keeps the aspect-preserving fit into 224 x 224 with zero padding "
-                           "(or resize_rule='clip' on request) and applies only the checkpoint's image_mean / image_std")
+                           "aspect ratio; K1 does not run that rule by default: it keeps the aspect-preserving fit into 224 x 224 with zero padding "
+                           "(resize_rule='checkpoint' runs the file's own rule, 'clip' CLIP's) and applies only the checkpoint's image_mean / image_std")
         return _mean_std(pc, where)
     if resample != 2 and not (encoder == "clip" and resample == 3):
         raise MmeError(f"{where}: resample = {resample!r}; K1 resizes with Pillow BILINEAR (resample = 2) only")
@@ -578,9 +655,10 @@ def _siglip_logit_pair(geometry, tensors, keys, path, where):
 def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpoint:
     """Directory -> Checkpoint (see the module docstring).  Raises MmeError naming the file, field or key at fault.
 
-    `resize_rule` ("fit_pad", the same as None, or "clip") is the rule K1 will run: under "clip" a preprocessor_config.json
-    must describe CLIPImageProcessor's shortest-edge-224 BICUBIC resize and 224 x 224 centre crop exactly, and a directory
-    without one gets CLIP's defaults (the engine's mean / std)."""
+    `resize_rule` ("fit_pad", the same as None, "clip", "checkpoint" or a ResizeSpec) is the rule K1 will run: under "clip" a
+    preprocessor_config.json must describe CLIPImageProcessor's shortest-edge-224 BICUBIC resize and 224 x 224 centre crop
+    exactly, and a directory without one gets CLIP's defaults (the engine's mean / std).  Under "checkpoint" the file must
+    exist; `resize_spec_of` derives the rule from it (`Checkpoint.resize_spec`) before any tensor is read."""
     from .encoders import ENCODER_TABLE
 
     path = os.fspath(path)
@@ -593,6 +671,11 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
     cfg_path = os.path.join(path, "config.json")
     if not os.path.exists(cfg_path):
         raise MmeError(f"{cfg_path} is missing")
+    pre_path = os.path.join(path, "preprocessor_config.json")
+    if resize_rule == "checkpoint":  # refused before anything is loaded
+        if not os.path.exists(pre_path):
+            raise MmeError(f"{pre_path} is missing: resize_rule = 'checkpoint' reads the rule from it (pass a ResizeSpec to name one yourself)")
+        resize_spec_of(_load_json(pre_path), os.path.basename(pre_path))
     geometry, where = rec.config_geometry(_load_json(cfg_path), path)
     tensors, keys, files = _read_tensors(path, rec.canonical_name, {s[0] for s in rec.tensor_specs(geometry)} | set(rec.optional))
     if rec.after_read:  # what config.json cannot say: which optional tensors the file holds, the side of DINOv2's position grid
@@ -605,14 +688,14 @@ def read_checkpoint(path, encoder: str = "vit_b16", resize_rule=None) -> Checkpo
         if tuple(tensors[name].shape) != tuple(shape):
             raise MmeError(f"{path}: tensor {keys[name]!r} has shape {tuple(tensors[name].shape)}, expected {tuple(shape)}")
     tensors, dtype = _unify_dtype({n: tensors[n] for n, _ in specs}, keys)
-    mean = std = None
+    mean = std = spec = None
     source = [cfg_path] + files
-    pre_path = os.path.join(path, "preprocessor_config.json")
     if os.path.exists(pre_path) and not rec.text:  # a text tower reads no pixels
-        mean, std = _read_preprocessor(pre_path, encoder, resize_rule)
+        mean, std, spec = _read_preprocessor(pre_path, encoder, resize_rule)
         source.append(pre_path)
     extra = rec.extra(tensors) if rec.extra else {}
-    return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, source=source, extra=extra)
+    return Checkpoint(encoder=encoder, tensors=tensors, dtype=dtype, geometry=geometry, image_mean=mean, image_std=std, resize_spec=spec, source=source,
+                      extra=extra)
 
 
 # ---- config.json of a geometry (`encoders.Encoder.config_json`: geometry, dtype name, the weight dict -> dict) ----------------
@@ -715,8 +798,9 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m multimodal_embeddings_amd.checkpoint", description="what a load of this checkpoint directory would find")
     ap.add_argument("directory")
     ap.add_argument("--encoder", choices=CLI_ENCODERS, default="vit_b16")
-    ap.add_argument("--resize-rule", choices=RESIZE_RULES, default="fit_pad",
-                    help="the rule K1 would run: 'clip' checks preprocessor_config.json against the shortest-edge BICUBIC resize + centre crop")
+    ap.add_argument("--resize-rule", choices=RESIZE_RULES + ("checkpoint",), default="fit_pad",
+                    help="the rule K1 would run: 'clip' checks preprocessor_config.json against the shortest-edge BICUBIC resize + centre crop; "
+                         "'checkpoint' derives the rule from that file and prints it")
     a = ap.parse_args(argv)
     try:
         ck = read_checkpoint(a.directory, "siglip" if a.encoder == SIGLIP_ALIAS else a.encoder, a.resize_rule)
@@ -728,6 +812,8 @@ def main(argv=None) -> int:
     print(f"geometry    {ck.geometry}")
     print(f"image_mean  {ck.image_mean}")
     print(f"image_std   {ck.image_std}")
+    if ck.resize_spec is not None:
+        print(f"resize_spec {ck.resize_spec}")
     print(f"tensors     {len(ck.tensors)}")
     print(f"bytes       {ck.nbytes}")
     for f in ck.source:

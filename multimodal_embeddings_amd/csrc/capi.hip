@@ -211,28 +211,50 @@ int launch_h_pass(mme_ctx* c, const K1Plan& p, const uint8_t* pix, int n, hipStr
     return launch_h_pass<CropDesc>(c, p, pix, n, s, who, "", launch_resample_tables, launch_resize_h);
 }
 
-// ---- K1 under MME_RESIZE_CLIP (preprocess_clip.hip) ---------------------------------------------------------------------
-// transformers image_transforms.py get_resize_output_image_size, size = {"shortest_edge": 224}, default_to_square = False:
-// the short edge gets 224, the long edge int(224 * long / short) -- the Python float expression in that order, in f64
-void clip_resized_size(int h, int w, int* nh, int* nw) {
+// ---- K1 under MME_RESIZE_CLIP and MME_RESIZE_SPEC (preprocess_clip.hip) ---------------------------------------------------
+// One path serves both: rule 1 is the spec below, what CLIPImageProcessorPil does.
+constexpr mme_resize_spec kClipSpec = {MME_RESIZE_MODE_SHORTEST_EDGE, VIT_IMG, 0, 3};
+// the spec mme_preprocess runs under the context's rule; null under the fit-and-pad rule
+const mme_resize_spec* spec_of(const mme_ctx* c) {
+    return c->resize_rule == MME_RESIZE_SPEC ? &c->resize_spec : (c->resize_rule == MME_RESIZE_CLIP ? &kClipSpec : nullptr);
+}
+// a 224 x 224 crop is resized to 224 x 224, i.e. not filtered on either axis, and its centre window is the crop
+bool spec_keeps_canvas(const mme_resize_spec& sp) {
+    return sp.mode == MME_RESIZE_MODE_EXACT ? (sp.height == VIT_IMG && sp.width == VIT_IMG) : sp.height == VIT_IMG;
+}
+// The size of the whole resized image.  EXACT: the spec's.  SHORTEST_EDGE S: transformers image_transforms.py
+// get_resize_output_image_size, size = {"shortest_edge": S}, default_to_square = False: the short edge gets S, the long
+// edge int(S * long / short) -- the Python float expression in that order, in f64
+void spec_resized_size(const mme_resize_spec& sp, int h, int w, int* nh, int* nw) {
+    if (sp.mode == MME_RESIZE_MODE_EXACT) {
+        *nh = sp.height;
+        *nw = sp.width;
+        return;
+    }
     const int sh = h <= w ? h : w, lg = h <= w ? w : h;
-    const int nl = (int)((double)(VIT_IMG * (int64_t)lg) / (double)sh);
-    *nh = h <= w ? VIT_IMG : nl;
-    *nw = h <= w ? nl : VIT_IMG;
+    const int nl = (int)((double)(sp.height * (int64_t)lg) / (double)sh);
+    *nh = h <= w ? sp.height : nl;
+    *nw = h <= w ? nl : sp.height;
 }
 // Resample.c's ksize (resample.h), the upper bound of a window's taps; 1 for an axis that is not filtered
-int clip_ksize(int in_size, int out_size) { return in_size == out_size ? 1 : resample_ksize<Bicubic>(in_size, out_size); }
+template <class Filter>
+int axis_ksize(int in_size, int out_size) {
+    return in_size == out_size ? 1 : resample_ksize<Filter>(in_size, out_size);
+}
 
-// Sizes against the 8000 x 8000 limit: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145, so gh <= 37 and kv <= 148 (the
-// vertical pass holds 160); a crop's tables take <= 3584 + 37 * 3584 + 224 * 148 * 4 = 268 800 bytes and its scratch
-// image <= 8000 * 672 = 5 376 000 bytes, both summed in size_t.  The widest class-2 band is 4 * 24000 bytes of LDS.
-void plan_clip_crop(K1Plan& p, int i, ClipCropDesc& d) {
-    clip_resized_size(d.h, d.w, &d.new_h, &d.new_w);
+// Sizes against the 8000 x 8000 limit, resized edges >= 224: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145 (BICUBIC; 73 for
+// BILINEAR), so gh <= 37 and kv <= 148 (the vertical pass holds 160); a crop's tables take <= 3584 + 37 * 3584 + 224 * 148 * 4
+// = 268 800 bytes and its scratch image <= 8000 * 672 = 5 376 000 bytes (nr <= h), both summed in size_t.  The widest
+// class-2 band is 4 * 24000 bytes of LDS.  Filter = the spec's (Triangle for resample 2, Bicubic for 3).
+template <class Filter>
+void plan_spec_crop(K1Plan& p, int i, ClipCropDesc& d, const mme_resize_spec& sp) {
+    spec_resized_size(sp, d.h, d.w, &d.new_h, &d.new_w);
     d.top = (d.new_h - VIT_IMG) / 2;
     d.left = (d.new_w - VIT_IMG) / 2;
     if (d.new_h != d.h) {
-        // the union of the 224 vertical windows: the expressions clip_tables evaluates on the device (resample.h)
-        const Taps first = resample_window<Bicubic>(d.h, d.new_h, d.top), last = resample_window<Bicubic>(d.h, d.new_h, d.top + VIT_IMG - 1);
+        // the union of the 224 vertical windows: the expressions clip_tables evaluates on the device (resample.h); the
+        // whole source height when the window is the whole resized image (an exact 224 target)
+        const Taps first = resample_window<Filter>(d.h, d.new_h, d.top), last = resample_window<Filter>(d.h, d.new_h, d.top + VIT_IMG - 1);
         const int a = first.xmin, z = last.xmin + last.n;
         d.r0 = a;
         d.nr = (z > a ? z : a + 1) - a;
@@ -240,8 +262,8 @@ void plan_clip_crop(K1Plan& p, int i, ClipCropDesc& d) {
         d.r0 = d.top;
         d.nr = VIT_IMG;
     }
-    d.gh = (clip_ksize(d.w, d.new_w) + 3) >> 2;
-    d.kv = (clip_ksize(d.h, d.new_h) + 3) & ~3;
+    d.gh = (axis_ksize<Filter>(d.w, d.new_w) + 3) >> 2;
+    d.kv = (axis_ksize<Filter>(d.h, d.new_h) + 3) & ~3;
     if (d.kv > p.kv_max) p.kv_max = d.kv;
     d.tab_off = (int64_t)p.tab_bytes;
     p.tab_bytes += (size_t)clip_layout(d.gh, d.kv).bytes;
@@ -250,22 +272,29 @@ void plan_clip_crop(K1Plan& p, int i, ClipCropDesc& d) {
     plan_bands(p, i, d.w * 3, clip_h_table_lds(d.gh), d.r0, d.nr);
 }
 
-int preprocess_chunk_clip(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches, hipStream_t s) {
+int preprocess_chunk_spec(mme_ctx* c, const mme_resize_spec& sp, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches,
+                          hipStream_t s) {
     c->h_clip_crops.resize(n);
     K1Plan plan;
+    const bool bilinear = sp.resample == 2;
     for (int i = 0; i < n; ++i) {
         ClipCropDesc& d = c->h_clip_crops[i];
         d.src_off = offs[i];
         d.h = hw[2 * i];
         d.w = hw[2 * i + 1];
-        plan_clip_crop(plan, i, d);
+        if (bilinear)
+            plan_spec_crop<Triangle>(plan, i, d, sp);
+        else
+            plan_spec_crop<Bicubic>(plan, i, d, sp);
     }
     int r;
     if ((r = ensure(c, c->crops, (size_t)n * sizeof(ClipCropDesc)))) return r;
     HIP_TRY(c, hipMemcpyAsync(c->crops.p, c->h_clip_crops.data(), (size_t)n * sizeof(ClipCropDesc), hipMemcpyHostToDevice, s));
     if ((r = run_h_pass(c, plan, pix, n, s, "mme_preprocess"))) return r;
     Timed t(c, s, KC_PRE);
-    if ((r = launch_h_pass<ClipCropDesc>(c, plan, pix, n, s, "mme_preprocess", "BICUBIC ", launch_clip_tables, launch_clip_resize_h))) return r;
+    const int resample = sp.resample;
+    auto tables = [resample](const ClipCropDesc* crops, int m, uint8_t* tab, hipStream_t st) { return launch_clip_tables(crops, m, tab, resample, st); };
+    if ((r = launch_h_pass<ClipCropDesc>(c, plan, pix, n, s, "mme_preprocess", bilinear ? "BILINEAR " : "BICUBIC ", tables, launch_clip_resize_h))) return r;
     HIP_TRY(c, launch_clip_v_patchify((const uint8_t*)c->tmp.p, (const ClipCropDesc*)c->crops.p, n, c->lut, c->norm_aff, patches, (const uint8_t*)c->htab.p, plan.kv_max, s));
     return MME_OK;
 }
@@ -283,8 +312,11 @@ int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const 
             return fail(c, MME_E_ARG, "crop %d has size %dx%d (h x w); supported 1..8000 (embedder.py:110-114 caps at 8000)", i, h, w);
         if (h != VIT_IMG || w != VIT_IMG) any_resize = true;
     }
-    // a batch of 224 x 224 crops is the identity under both rules: the lean instantiation below, today's bits and time
-    if (c->resize_rule == MME_RESIZE_CLIP && any_resize) return preprocess_chunk_clip(c, pix, offs, hw, n, patches, s);
+    // a batch of 224 x 224 crops is the identity under the fit-and-pad rule and under every spec that resizes such a crop to
+    // 224 x 224 (CLIP's among them): the lean instantiation below, today's bits and time.  Under any other spec (shortest
+    // edge 256: resized to 256 x 256 and cropped) it is filtered like every other batch.
+    if (const mme_resize_spec* sp = spec_of(c); sp && (any_resize || !spec_keeps_canvas(*sp)))
+        return preprocess_chunk_spec(c, *sp, pix, offs, hw, n, patches, s);
     for (int i = 0; i < n; ++i) {
         const int h = hw[2 * i], w = hw[2 * i + 1];
         CropDesc& d = c->h_crops[i];
@@ -397,8 +429,37 @@ int mme_set_resize_rule(mme_ctx* c, int rule) {
     if (!c) return MME_E_ARG;
     if (rule != MME_RESIZE_FIT_PAD && rule != MME_RESIZE_CLIP)
         return fail(c, MME_E_ARG, "mme_set_resize_rule: rule %d; supported %d (MME_RESIZE_FIT_PAD: fit into 224 x 224, BILINEAR, zero pad) and %d "
-                                  "(MME_RESIZE_CLIP: shortest edge 224, BICUBIC, centre crop)", rule, MME_RESIZE_FIT_PAD, MME_RESIZE_CLIP);
+                                  "(MME_RESIZE_CLIP: shortest edge 224, BICUBIC, centre crop); %d (MME_RESIZE_SPEC) has parameters and is set by "
+                                  "mme_set_resize_spec", rule, MME_RESIZE_FIT_PAD, MME_RESIZE_CLIP, MME_RESIZE_SPEC);
     c->resize_rule = rule;
+    return MME_OK;
+}
+
+int mme_set_resize_spec(mme_ctx* c, const mme_resize_spec* spec) {
+    if (!c) return MME_E_ARG;
+    if (!spec) return fail(c, MME_E_ARG, "mme_set_resize_spec: spec is NULL; supported: a pointer to an mme_resize_spec");
+    const mme_resize_spec sp = *spec;
+    const bool exact = sp.mode == MME_RESIZE_MODE_EXACT;
+    if (sp.mode != MME_RESIZE_MODE_SHORTEST_EDGE && !exact)
+        return fail(c, MME_E_ARG, "mme_set_resize_spec: mode = %d; supported %d (MME_RESIZE_MODE_SHORTEST_EDGE) and %d (MME_RESIZE_MODE_EXACT)", sp.mode,
+                    MME_RESIZE_MODE_SHORTEST_EDGE, MME_RESIZE_MODE_EXACT);
+    if (sp.height < VIT_IMG || sp.height > 512)
+        return fail(c, MME_E_ARG, "mme_set_resize_spec: height = %d (%s); supported 224..512", sp.height, exact ? "the height of the resized image" : "the shortest edge");
+    if (exact ? (sp.width < VIT_IMG || sp.width > 512) : sp.width != 0)
+        return fail(c, MME_E_ARG, "mme_set_resize_spec: width = %d; supported %s", sp.width, exact ? "224..512" : "0 under MME_RESIZE_MODE_SHORTEST_EDGE (height is the edge)");
+    if (sp.resample != 2 && sp.resample != 3)
+        return fail(c, MME_E_ARG, "mme_set_resize_spec: resample = %d; supported 2 (Pillow BILINEAR) and 3 (Pillow BICUBIC)", sp.resample);
+    c->resize_spec = sp;
+    c->resize_rule = MME_RESIZE_SPEC;
+    return MME_OK;
+}
+
+int mme_get_resize_spec(mme_ctx* c, mme_resize_spec* out) {
+    if (!c || !out) return fail(c, MME_E_ARG, "mme_get_resize_spec: null argument");
+    if (c->resize_rule != MME_RESIZE_SPEC)
+        return fail(c, MME_E_STATE, "mme_get_resize_spec: the current rule is %d, not %d (MME_RESIZE_SPEC); mme_set_resize_spec makes a spec the rule", c->resize_rule,
+                    MME_RESIZE_SPEC);
+    *out = c->resize_spec;
     return MME_OK;
 }
 

@@ -101,6 +101,7 @@ struct mme_ctx {
     float* lut = nullptr;  // [3,256]
     NormAffine norm_aff{};  // the same mapping as one fma per value where that is bit-exact after the bf16 rounding (set_lut)
     int resize_rule = MME_RESIZE_FIT_PAD;  // mme_set_resize_rule: how mme_preprocess / mme_embed make 224 x 224 pixels; no load changes it
+    mme_resize_spec resize_spec{};  // mme_set_resize_spec: the rule's parameters while resize_rule == MME_RESIZE_SPEC
     // workspace (sized for `chunk` crops)
     int ws_chunk = 0, ws_hidden = 0, ws_mlp = 0, ws_tokens = 0;  // what the workspace below was sized for
     DevBuf attn_guard;      // int[max(64, layers)]: one guard word per layer of a pass (encoder_pass.h, reset_attn_guards)

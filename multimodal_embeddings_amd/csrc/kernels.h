@@ -186,15 +186,16 @@ hipError_t launch_resize_v_patchify(const uint8_t* pix, const uint8_t* tmp, cons
                                     const float* lut /*[3,256]*/, const NormAffine& aff, void* patches, bool any_resize, const uint8_t* tab, int kv_max,
                                     hipStream_t s);
 
-// ---- K1 under MME_RESIZE_CLIP (preprocess_clip.hip, on resample.h): shortest-edge BICUBIC resize + centre crop, only the 224 x 224
-// window of the resized image computed.  What CropDesc cannot carry: the FULL resized sizes, the window's origin and the
+// ---- K1 under MME_RESIZE_CLIP and MME_RESIZE_SPEC (preprocess_clip.hip, on resample.h): a resize of the whole crop (CLIP's:
+// shortest edge 224, BICUBIC; a spec's: mme_resize_spec) + centre crop, only the 224 x 224 window of the resized image
+// computed.  What CropDesc cannot carry: the FULL resized sizes, the window's origin and the
 // source rows the horizontal pass filters.
 struct ClipCropDesc {  // one per crop, built on the host by capi (plan_clip_crop)
     int64_t src_off;       // byte offset into pix
     int64_t tmp_off;       // byte offset (16-aligned) of this crop's scratch image: nr rows of 672 bytes
     int64_t tab_off;       // byte offset (16-aligned) of this crop's tables (ClipLayout)
     int32_t h, w;          // source size
-    int32_t new_h, new_w;  // size of the whole resized image: 224 on the short edge, int(224 * long / short) on the other
+    int32_t new_h, new_w;  // size of the whole resized image (CLIP: 224 on the short edge, int(224 * long / short) on the other)
     int32_t top, left;     // origin of the centre-crop window in the resized image
     int32_t r0, nr;        // source rows [r0, r0 + nr): the union of the 224 vertical windows (rows top.. when the height is kept)
     int32_t gh, kv;        // groups of four taps per output column; ints per vertical coefficient row (a multiple of 4)
@@ -216,7 +217,8 @@ __host__ __device__ inline ClipLayout clip_layout(int gh, int kv) {
 }
 // bytes of LDS the horizontal table takes beside a band (padded to whole 1 KiB DMA sweeps)
 __host__ __device__ inline int clip_h_table_lds(int gh) { return (224 * 8 + gh * 224 * 16 + 1023) & ~1023; }
-hipError_t launch_clip_tables(const ClipCropDesc* crops, int n, uint8_t* tab, hipStream_t s);
+// `resample`: Pillow's number of the filter, 2 (BILINEAR: Triangle) or 3 (BICUBIC)
+hipError_t launch_clip_tables(const ClipCropDesc* crops, int n, uint8_t* tab, int resample, hipStream_t s);
 // horizontal pass over `nwork` bands of one class, as launch_resize_h: 0 = eight-row items, table in LDS; 1 = four-row
 // items, table in LDS; 2 = four-row items, table through L1.  HWork::row0 is a SOURCE row (>= r0).
 hipError_t launch_clip_resize_h(const uint8_t* pix, uint8_t* tmp, const ClipCropDesc* crops, const HWork* work, int nwork, int lds_bytes,

@@ -1,5 +1,8 @@
-// K1 under MME_RESIZE_CLIP: batched variable-size crop -> CLIP's own shortest-edge BICUBIC resize -> centre crop
-// 224 x 224 -> normalise -> patchify (bf16 patch matrix [n*196, 768] in conv order (c, ky, kx)).
+// K1 under MME_RESIZE_CLIP and MME_RESIZE_SPEC: batched variable-size crop -> a Pillow resize of the whole crop (to a shortest
+// edge or to an exact size, BICUBIC or BILINEAR: mme_resize_spec) -> centre crop 224 x 224 -> normalise -> patchify (bf16
+// patch matrix [n*196, 768] in conv order (c, ky, kx)).  CLIP's rule is the instance {shortest edge, 224, BICUBIC}, which
+// the text below describes; the descriptor (ClipCropDesc) carries the geometry of any spec, and the filter is the template
+// argument of clip_tables, the only kernel that evaluates it.
 //
 // Restates, bit for bit on the uint8 side, transformers CLIPImageProcessorPil (image_transforms.py
 // get_resize_output_image_size with size = {"shortest_edge": 224}; image_processing_backends.py PilBackend.resize and
@@ -15,7 +18,8 @@
 // The kernels are preprocess.hip's over another arithmetic (resample.h): the horizontal kernel template, the vertical
 // chunk loop and the patch emitter, here with Signed sums, since the unsigned v_mad_u32_u24 sums and upper-only clamp of the
 // fit-and-pad rule hold for the non-negative triangle weights only.  Here weights are signed: |k| <= 4 715 487 < 2^23 and
-// sum |k| <= 1.25 * 2^22.  With 224 fixed output columns the scratch pitch is 672 bytes for every crop and the
+// sum |k| <= 1.2636 * 2^22 over every spec; a spec's BILINEAR weights are non-negative and the same
+// sums are exact for them.  With 224 fixed output columns the scratch pitch is 672 bytes for every crop and the
 // vertical pass has ONE form: an unfiltered axis gets one-tap windows of weight 2^22, which copy exactly
 // (((p << 22) + 2^21) >> 22 == p), so the column offset of e.g. a 224 x 300 crop rides through the horizontal pass.
 //   clip_tables      one workgroup per crop: both window tables (ClipLayout, kernels.h).
@@ -51,6 +55,7 @@ struct ClipCrop {
 // i.e. source rows minus r0.  The host computed r0 and nr from the same two window expressions, so every window lies in
 // [0, nr) as computed; the clamp below is a memory-safety guard for the vertical pass's reads, never an adjustment (were it
 // taken, coefficient and row would no longer match and the bit-equality tests would show wrong pixels).
+template <class Filter>
 __global__ __launch_bounds__(256) void clip_tables(const ClipCropDesc* __restrict__ crops, uint8_t* __restrict__ tab) {
     const ClipCropDesc c = crops[blockIdx.x];
     const ClipLayout L = clip_layout(c.gh, c.kv);
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(256) void clip_tables(const ClipCropDesc* __restric
             auto put = [&](int i, int k) { hk[((i >> 2) * OUT + x) * 4 + (i & 3)] = k; };
             Taps t;
             if (c.new_w != c.w) {
-                t = resample_taps<Bicubic>(c.w, c.new_w, c.left + x, c.gh * 4, put);
+                t = resample_taps<Filter>(c.w, c.new_w, c.left + x, c.gh * 4, put);
             } else {
                 t = Taps{c.left + x, 1};
                 put(0, 1 << PRECISION_BITS);
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(256) void clip_tables(const ClipCropDesc* __restric
             int* row = (int*)(base + L.vk_off) + y * c.kv;
             Taps t;
             if (c.new_h != c.h) {
-                t = resample_taps<Bicubic>(c.h, c.new_h, c.top + y, c.kv, [&](int i, int k) { row[i] = k; });
+                t = resample_taps<Filter>(c.h, c.new_h, c.top + y, c.kv, [&](int i, int k) { row[i] = k; });
             } else {
                 t = Taps{c.top + y, 1};
                 row[0] = 1 << PRECISION_BITS;
@@ -144,9 +149,10 @@ __global__ __launch_bounds__(512, 6) void clip_v_patchify(const uint8_t* __restr
 
 }  // namespace
 
-hipError_t launch_clip_tables(const ClipCropDesc* crops, int n, uint8_t* tab, hipStream_t s) {
+hipError_t launch_clip_tables(const ClipCropDesc* crops, int n, uint8_t* tab, int resample, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(clip_tables, dim3(n), dim3(256), 0, s, crops, tab);
+    if (resample != 2 && resample != 3) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resample == 2 ? clip_tables<Triangle> : clip_tables<Bicubic>, dim3(n), dim3(256), 0, s, crops, tab);
     return hipGetLastError();
 }
 

@@ -29,7 +29,7 @@ import os
 import numpy as np
 
 from . import config
-from ._lib import Engine, MmeError, lanczos_geometry_ok, lanczos_workspace  # noqa: F401
+from ._lib import Engine, MmeError, ResizeSpec, lanczos_geometry_ok, lanczos_workspace  # noqa: F401
 from .staging import ResultRing, Stage, _Null, current_stream, new_event, new_stream, on, packed_layout  # noqa: F401
 from .weights import TILE_VIT
 
@@ -203,7 +203,11 @@ class RegionEmbedder:
         `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
         fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
         encoders only; a checkpoint's preprocessor_config.json must then describe exactly that rule).  It is set on every
-        engine of this object; None leaves a caller's `engine=` as it is.
+        engine of this object; None leaves a caller's `engine=` as it is.  "checkpoint" reads the rule the model was trained
+        under from the directory's preprocessor_config.json (checkpoint.resize_spec_of: ViT's and SigLIP's exact 224 x 224
+        resize, DINOv2's shortest-edge-256 BICUBIC resize + centre crop, ...; a missing file or a rule K1 does not run is an
+        error) and a `ResizeSpec` names such a rule directly; `self.resize_rule` is then "spec" and `self.resize_spec` the spec.
+        Neither is ever a default.
         `text_tower`: the text tower behind `get_text_embeddings` (CLIP's; SigLIP's under encoder="siglip_vit"), in the FIRST engine only.  None: nothing is loaded
         now; the first `get_text_embeddings` loads it if `model_name` is a checkpoint directory that holds one.  True: load
         now (from that directory, or seeded CLIP_TEXT_B-shaped weights projecting to this object's `embed_dim` beside a seeded
@@ -237,6 +241,9 @@ class RegionEmbedder:
         source = "weights" if engine is not None else resolve_model_source(model_name, weights, allow_synthetic)
         if source == "checkpoint":
             self.checkpoint = read_checkpoint(model_name, encoder, resize_rule)
+        elif self.resize_rule == "checkpoint":
+            raise MmeError(f"resize_rule = 'checkpoint' reads preprocessor_config.json of a checkpoint directory; model_name = {model_name!r} is "
+                           "none, or weights= / engine= was given (supported: a local checkpoint directory, or a ResizeSpec that names the rule)")
         if engine is not None:
             dev_list = [engine.device]
         elif devices is not None:  # explicit device indices (may repeat: several contexts on one GPU)
@@ -285,11 +292,16 @@ class RegionEmbedder:
                 getattr(e, rec.loader)(w, geom=geometry)
                 self.engines.append(e)
         self.engine = self.engines[0]
-        if resize_rule is not None:
+        if self.resize_rule == "checkpoint":
+            self.resize_rule = self.checkpoint.resize_spec
+        if isinstance(self.resize_rule, ResizeSpec):
+            for e in self.engines:
+                e.set_resize_spec(self.resize_rule)
+        elif resize_rule is not None:
             for e in self.engines:
                 e.set_resize_rule(self.resize_rule)
-        else:  # a caller's engine keeps its rule; this object reports it
-            self.resize_rule = self.engine.resize_rule
+        # a caller's engine keeps its rule under None; this object reports what the engine runs
+        self.resize_rule, self.resize_spec = self.engine.resize_rule, self.engine.resize_spec
         if chunk:
             for e in self.engines:
                 e.set_chunk(chunk)

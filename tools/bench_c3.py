@@ -6,7 +6,8 @@ GB/s and whole-path crops/s, and checks a sample against the oracle bit-for-bit 
 
 `--resize-rule fit_pad|clip` runs all of that under one rule of mme_set_resize_rule (default fit_pad).  `--resize-rule both`
 alternates K1 under the two rules in one process on the same crops -- two warm-ups each, then five timed runs of each,
-interleaved, one line per run -- and then times one mme_embed step of seeded CLIP-B/16 under each rule.
+interleaved, one line per run -- and then times one mme_embed step of seeded CLIP-B/16 under each rule.  `--resize-rule specs`
+does the same over the two rules and the four specs of mme_set_resize_spec that real checkpoints ask for (SPECS below).
 """
 import argparse
 import os
@@ -17,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from multimodal_embeddings_amd._lib import Engine
+from multimodal_embeddings_amd._lib import Engine, ResizeSpec
 from multimodal_embeddings_amd.weights import make_vit_weights, round_to_bf16
 
 
@@ -29,29 +30,44 @@ def k1_ms(eng, pix, offs, hw):
     return eng.profile_read()["preprocess"][0]
 
 
-def both_rules(pix, offs, hw, n):
+SPECS = {  # the rules real checkpoints ask for (tests/resize_spec_reference.py)
+    "exact224_bicubic": ResizeSpec("exact", 224, 224, 3),
+    "exact224_bilinear": ResizeSpec("exact", 224, 224, 2),
+    "edge256_bicubic": ResizeSpec("shortest_edge", 256, 0, 3),
+    "exact256_bicubic": ResizeSpec("exact", 256, 256, 3),
+}
+
+
+def set_rule(eng, rule):
+    if rule in SPECS:
+        eng.set_resize_spec(SPECS[rule])
+    else:
+        eng.set_resize_rule(rule)
+
+
+def both_rules(pix, offs, hw, n, rules=("fit_pad", "clip")):
     from multimodal_embeddings_amd.weights import make_clip_weights
 
     eng = Engine(0)
     eng.load_clip(make_clip_weights(1))
-    rules = ("fit_pad", "clip")
     for _ in range(2):
         for rule in rules:
-            eng.set_resize_rule(rule)
+            set_rule(eng, rule)
             k1_ms(eng, pix, offs, hw)
     ms = {r: [] for r in rules}
     for i in range(5):
         for rule in rules:
-            eng.set_resize_rule(rule)
+            set_rule(eng, rule)
             ms[rule].append(k1_ms(eng, pix, offs, hw))
             print(f"C3 K1 run {i} rule {rule}: kernels {ms[rule][-1]:.3f} ms")
     eng.profile(False)
     for rule in rules:
         v = ms[rule]
         print(f"C3 K1 rule {rule}: min {min(v):.3f} median {sorted(v)[2]:.3f} max {max(v):.3f} ms over 5 runs")
-    print(f"C3 K1 ratio clip / fit_pad (medians): {sorted(ms['clip'])[2] / sorted(ms['fit_pad'])[2]:.2f}")
+    for rule in rules[1:]:
+        print(f"C3 K1 ratio {rule} / fit_pad (medians): {sorted(ms[rule])[2] / sorted(ms['fit_pad'])[2]:.2f}")
     for rule in rules:
-        eng.set_resize_rule(rule)
+        set_rule(eng, rule)
         for _ in range(2):
             eng.embed(pix, offs, hw)
         torch.cuda.synchronize()
@@ -64,7 +80,7 @@ def both_rules(pix, offs, hw, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--resize-rule", choices=("fit_pad", "clip", "both"), default="fit_pad")
+    ap.add_argument("--resize-rule", choices=("fit_pad", "clip", "both", "specs"), default="fit_pad")
     rule = ap.parse_args().resize_rule
     n = 4096
     sizes = np.load(os.path.join(os.path.dirname(__file__), "..", "tests", "golden", "bundled_crop_sizes_hw.npy"))
@@ -77,6 +93,8 @@ def main():
     pix = torch.randint(0, 256, (total,), dtype=torch.uint8, device="cuda", generator=g)
     if rule == "both":
         return both_rules(pix, offs, hw, n)
+    if rule == "specs":
+        return both_rules(pix, offs, hw, n, ("fit_pad", "clip") + tuple(SPECS))
     eng = Engine(0)
     eng.load_vit(make_vit_weights(seed=1))
     eng.set_resize_rule(rule)
