@@ -762,6 +762,48 @@ int mme_vit_tokens(mme_ctx* ctx, const uint16_t* patches_dev, int n, int pool_to
 int mme_embed_tokens(mme_ctx* ctx, const uint8_t* pix_dev, const int64_t* offs_host, const int32_t* hw_host, int n, int pool_token,
                      int tok0, int ntok, uint16_t* tokens_bf16_dev, float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
 
+/* ---- mean pooling over the patches a crop covers ---------------------------
+ * For a vit or dinov2 tower (class token, T = 1 + g * g tokens, g = 224 / patch), x the residual stream behind the last
+ * block and y_t = LayerNorm(x[b * T + t]) * gamma + beta with the final LayerNorm's weights, in f32 (K8's arithmetic): crop b
+ * has a covered grid (R, C), 1 <= R, C <= g, S_b = {1 + r * g + c : r < R, c < C}, P = R * C, and
+ *     m = (sum_{t in S_b} y_t) / P                                              in f32
+ *     MME_POOL_MEAN      m / max(||m||, 1e-12)                                  embed_dim = hidden
+ *     MME_POOL_CLS_MEAN  v = [y_0 | m], v / max(||v||, 1e-12), one norm over    embed_dim = 2 * hidden
+ *                        all 2 * hidden values (transformers' Dinov2ForImageClassification feature, L2-normalised)
+ * and the bf16 output is the single rounding of the f32 output.  The summation order is a fixed function of (R, C) alone --
+ * not of n, the chunk or any setting: with the covered tokens numbered j = r * C + c, partial sum p_w, w = 0..3, adds the
+ * rows j = w, w + 4, w + 8, ... in ascending j starting from its first row; m = (((p_0 + p_1) + p_2) + p_3) * (1.0f / P), over
+ * the partial sums that have a row.  So the grid (1, 1) gives mme_vit_forward's row for pool_token = 1 bit for bit.
+ * The covered grid: under the fit-and-pad rule the resized crop sits top-left in the 224 x 224 canvas and the rest is padding
+ * (half of all newspaper regions cover under a third of the patches), so R = ceil(new_h / patch), C = ceil(new_w / patch) of
+ * the rule's own new_h x new_w: a patch counts when it holds at least one pixel of the crop.  Under MME_RESIZE_CLIP and every
+ * MME_RESIZE_SPEC the canvas is full: (g, g).
+ *
+ * mme_set_pooling: MME_POOL_TOKEN (the default: one token row, pool_token, every bit as before), MME_POOL_MEAN,
+ * MME_POOL_CLS_MEAN.  The mean modes need a vit or dinov2 tower loaded; with a CLIP or SigLIP tower (the projection and the
+ * head pool for themselves), the tile tower or no tower they are MME_E_STATE, any other mode number MME_E_ARG.  Every image
+ * tower load sets the mode back to MME_POOL_TOKEN: mme_load_vit / _clip / _siglip / _dinov2 and their _as forms, and
+ * mme_load_tile_vit too -- a ViT or DINOv2 tower loaded before it stays loaded and usable, so the mean modes can be set again
+ * afterwards.  A text-tower load (mme_load_clip_text, mme_load_siglip_text) replaces the text tower and nothing of the image
+ * side: it leaves the mode as it is.  Under the mean modes pool_token is checked and ignored, the last block
+ * runs unpruned whatever mme_set_forward_pruning says (the setting is left as it is), mme_encoder_info reports the mode's
+ * embed_dim, mme_vit_forward and mme_vit_tokens pool whole grids, and mme_embed and mme_embed_tokens pool the grids of
+ * mme_pool_grids.  Token rows are not affected. */
+enum { MME_POOL_TOKEN = 0, MME_POOL_MEAN = 1, MME_POOL_CLS_MEAN = 2 };
+int mme_set_pooling(mme_ctx* ctx, int mode);
+int mme_pooling(mme_ctx* ctx, int32_t* mode);
+/* The fit-and-pad covered grid of one h x w crop at `patch`: out_rc = (R, C).  A host function, no context and no GPU (errors:
+ * mme_last_error(NULL)).  h, w outside 1..8000 or patch not 14, 16 or 32: MME_E_ARG. */
+int mme_pool_grid(int h, int w, int patch, int32_t out_rc[2]);
+/* The grids the pixel path of THIS context uses (its patch size and resize rule) for n crops of hw_host int32 [n, 2] (h, w):
+ * grids_host int32 [n, 2].  Host only. */
+int mme_pool_grids(mme_ctx* ctx, const int32_t* hw_host, int n, int32_t* grids_host);
+/* mme_vit_forward under a mean mode with the covered grid of every crop: grids_host int32 [n, 2] (R, C), NULL = whole grids.
+ * An entry outside 1..g is MME_E_ARG and nothing is launched; MME_POOL_TOKEN is MME_E_STATE.  The grids are copied to a
+ * context-owned device buffer once per call, on `stream`. */
+int mme_vit_forward_grids(mme_ctx* ctx, const uint16_t* patches_dev, int n, const int32_t* grids_host, float* emb_f32_dev,
+                          uint16_t* emb_bf16_dev, void* stream);
+
 /* f32 vectors (the reference moves embeddings as Python float lists, embedder.py:132) ->
  * L2-normalised bf16 rows, same normalisation as last_pooling (F.normalize, eps 1e-12).
  * x_dev float[rows,d] (d % 4 == 0, 16-byte aligned rows), y_dev bf16[rows,d]. */
@@ -1085,6 +1127,26 @@ typedef struct mme_rowop_apply_args {
     float eps;
 } mme_rowop_apply_args;
 int mme_rowop_apply(mme_ctx* ctx, int op, const mme_rowop_apply_args* args, void* stream);
+
+/* Diagnostic: ONE launch of the mean-pooling kernel (pooling.hip; the definition is above mme_set_pooling) on the caller's
+ * device buffers, synchronous; works on a bare context.  x bf16 [B * tokens, d]; the patch rows of crop b are first + r * g + c.
+ *   op 0 mean      -> emb_f32 / emb_bf16 [B, d]
+ *      1 cls+mean  -> [B, 2 d], row b * tokens the class row
+ * grids: DEVICE int32 [B, 2] (R, C), or NULL for whole grids; the caller guarantees 1 <= R, C <= g (the kernel clamps).
+ * Preconditions (else MME_E_ARG, nothing launched): x, gamma, beta non-null and 16-byte aligned; emb_f32 or emb_bf16 non-null,
+ * both 16-byte aligned; grids 8-byte aligned; d == 384, 768 or 1024; 0 <= B <= 2^20; 1 <= g <= 16; first 0 or 1 (op 1: 1);
+ * tokens == first + g * g. */
+typedef struct mme_pool_apply_args {
+    const uint16_t* x;
+    const float* gamma;
+    const float* beta;
+    const int32_t* grids;
+    float* emb_f32;
+    uint16_t* emb_bf16;
+    int32_t B, tokens, g, first, d;
+    float eps;
+} mme_pool_apply_args;
+int mme_pool_apply(mme_ctx* ctx, int op, const mme_pool_apply_args* args, void* stream);
 
 /* Diagnostic: ONE launch of a step of K12 (mme_neighbours) on the caller's device buffers, then a stream synchronise; works on
  * a bare context (tests/test_gpu_select.py compares every output bit with the definition above mme_neighbours).

@@ -112,6 +112,11 @@ class _RowopApplyArgs(C.Structure):  # mme_rowop_apply_args
         ("d", C.c_int32), ("B", C.c_int32), ("tok", C.c_int32), ("eps", C.c_float)]
 
 
+class _PoolApplyArgs(C.Structure):  # mme_pool_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("x", "gamma", "beta", "grids", "emb_f32", "emb_bf16")] + [
+        (n, C.c_int32) for n in ("B", "tokens", "g", "first", "d")] + [("eps", C.c_float)]
+
+
 class _SelectApplyArgs(C.Structure):  # mme_select_apply_args
     _fields_ = [(n, C.c_void_p) for n in ("qsim", "group", "idx_out", "sim_out", "run_if", "cand_val", "cand_idx", "len", "A", "W", "thr", "cand_count",
                                           "overflow")] + [("ld", C.c_int64)] + [
@@ -251,6 +256,12 @@ EXPORTS = {
     "mme_vit_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_embed_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "mme_set_pooling": (C.c_int, [C.c_void_p, C.c_int]),
+    "mme_pooling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_pool_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "mme_pool_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mme_vit_forward_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_pool_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_PoolApplyArgs), C.c_void_p]),
     "mme_normalise_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "mme_cosine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "mme_cosine_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -689,7 +700,7 @@ class Engine:
 
     @property
     def embed_dim(self) -> int:
-        """Width of the rows `vit_forward` / `embed` return: the hidden size, or a CLIP tower's projection_dim."""
+        """Width of the rows `vit_forward` / `embed` return: the hidden size (twice that under pooling "cls+mean"), or a CLIP tower's projection_dim."""
         return self.encoder_info()["embed_dim"]
 
     # ---- the other image towers: each load replaces what the context held ----------------------------------------------------
@@ -1063,6 +1074,51 @@ class Engine:
         bit-identical embeddings, 6 % less work; off by default (see mme.h)."""
         self._check(self.lib.mme_set_forward_pruning(self.h, int(bool(on))), "mme_set_forward_pruning")
 
+    POOLINGS = {"token": 0, "mean": 1, "cls+mean": 2}  # MME_POOL_*
+
+    def set_pooling(self, mode):
+        """"token" / 0 (default: the row `pool_token` names), "mean" / 1 (the mean of the final-LayerNorm patch rows the crop
+        covers, L2-normalised) or "cls+mean" / 2 ([class row | mean], one L2 norm, embed_dim = 2 * hidden); the mean modes need
+        a vit or dinov2 tower loaded, and every load goes back to "token" (mme_set_pooling, include/mme.h)."""
+        self._check(self.lib.mme_set_pooling(self.h, int(self.POOLINGS.get(mode, mode))), "mme_set_pooling")
+
+    @property
+    def pooling(self) -> str:
+        m = C.c_int32(-1)
+        self._check(self.lib.mme_pooling(self.h, C.byref(m)), "mme_pooling")
+        return {v: k for k, v in self.POOLINGS.items()}[m.value]
+
+    @staticmethod
+    def pool_grid(h: int, w: int, patch: int = 16):
+        """(R, C): the patches an h x w crop covers under the fit-and-pad rule (mme_pool_grid; a host function, no GPU needed)."""
+        lib = load_library()
+        rc = (C.c_int32 * 2)()
+        if lib.mme_pool_grid(int(h), int(w), int(patch), rc) != 0:
+            raise MmeError(f"mme_pool_grid failed: {lib.mme_last_error(None).decode()}")
+        return int(rc[0]), int(rc[1])
+
+    def pool_grids(self, hw) -> np.ndarray:
+        """int32 [n, 2]: the covered grids the pixel path of this context uses for crops of sizes hw [n, 2] (mme_pool_grids)."""
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros_like(hw)
+        self._check(self.lib.mme_pool_grids(self.h, hw.ctypes.data, len(hw), out.ctypes.data), "mme_pool_grids")
+        return out
+
+    POOL_OPS = {"mean": 0, "cls+mean": 1}
+
+    def pool_apply(self, op, *, x=None, gamma=None, beta=None, grids=None, emb_f32=None, emb_bf16=None, B: int = 0, tokens: int = 197, g: int = 14,
+                   first: int = 1, d: int = 768, eps: float = 1e-12):
+        """ONE launch of the mean-pooling kernel on the caller's CUDA tensors (mme_pool_apply; synchronous).  `grids`: an int32
+        CUDA tensor [B, 2] (R, C) or None for whole grids; the library cannot read device memory, so the entries are checked
+        here (1..g each, else MmeError and nothing is launched).  Everything else the library validates."""
+        if grids is not None and grids.numel() and (int(grids.min()) < 1 or int(grids.max()) > int(g)):
+            bad = self.torch.nonzero((grids < 1) | (grids > int(g)))[0].tolist()
+            raise MmeError(f"pool_apply: grids[{bad[0]}][{bad[1]}] = {int(grids[bad[0], bad[1]])}; supported 1..{int(g)}")
+        a = _PoolApplyArgs()
+        a.x, a.gamma, a.beta, a.grids, a.emb_f32, a.emb_bf16 = (self._ptr(t) for t in (x, gamma, beta, grids, emb_f32, emb_bf16))
+        a.B, a.tokens, a.g, a.first, a.d, a.eps = int(B), int(tokens), int(g), int(first), int(d), float(eps)
+        self._check(self.lib.mme_pool_apply(self.h, int(self.POOL_OPS.get(op, op)), C.byref(a), self._stream()), "mme_pool_apply")
+
     def attention_redone(self, count: int = 12):
         """Layers of the LAST encoder pass whose attention launch raised the fast form's guard (list of `count` ints:
         `vit_geometry().num_layers` for the ViT forward -- 12 for ViT-B/16 --, the tower's layer count after `tile_vit_forward`)."""
@@ -1364,12 +1420,21 @@ class Engine:
         mask = (np.arange(max_tiles)[None, :] < nt[:, None]).astype(np.int64)
         return out, ids.astype(np.int64), mask, nt.tolist()
 
-    def vit_forward(self, patches, pool_token: int = 0, want_f32: bool = True, want_bf16: bool = True):
+    def vit_forward(self, patches, pool_token: int = 0, want_f32: bool = True, want_bf16: bool = True, grids=None):
+        """`grids`: under pooling "mean" / "cls+mean", a host int32 array [n, 2] of covered grids (R, C) (mme_vit_forward_grids;
+        pool_token is not used); without it the mean modes pool whole grids."""
         t = self.torch
         g = self.vit_geometry()
         n, d = patches.shape[0] // g.num_patches, self.embed_dim
         e32 = t.empty((n, d), dtype=t.float32, device=patches.device) if want_f32 else None
         e16 = t.empty((n, d), dtype=t.bfloat16, device=patches.device) if want_bf16 else None
+        if grids is not None:
+            grids = np.ascontiguousarray(grids, dtype=np.int32).reshape(-1, 2)
+            if len(grids) != n:
+                raise ValueError(f"grids holds {len(grids)} rows for {n} crops")
+            self._check(self.lib.mme_vit_forward_grids(self.h, patches.data_ptr(), n, grids.ctypes.data, e32.data_ptr() if want_f32 else None,
+                                                       e16.data_ptr() if want_bf16 else None, self._stream()), "mme_vit_forward_grids")
+            return e32, e16
         self._check(self.lib.mme_vit_forward(self.h, patches.data_ptr(), n, int(pool_token), e32.data_ptr() if want_f32 else None,
                                              e16.data_ptr() if want_bf16 else None, self._stream()), "mme_vit_forward")
         return e32, e16

@@ -339,6 +339,22 @@ int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const 
     return MME_OK;
 }
 
+int pool_grids_host(mme_ctx* c, const char* who, const int32_t* hw, int n, int32_t* out) {
+    const int patch = c->geom.patch, g = VIT_IMG / patch;
+    // every spec resizes to at least 224 on both axes and takes the centre window: the canvas is full (so is a 224 x 224 crop's,
+    // which the fit-and-pad rule leaves as it is)
+    const bool full = spec_of(c) != nullptr;
+    for (int i = 0; i < n; ++i) {
+        const int h = hw[2 * i], w = hw[2 * i + 1];
+        if (h <= 0 || w <= 0 || h > 8000 || w > 8000) return fail(c, MME_E_ARG, "%s: crop %d has size %dx%d (h x w); supported 1..8000", who, i, h, w);
+        int nh = VIT_IMG, nw = VIT_IMG;
+        if (!full) fit_to_canvas(h, w, &nh, &nw);
+        out[2 * i] = full ? g : (nh + patch - 1) / patch;
+        out[2 * i + 1] = full ? g : (nw + patch - 1) / patch;
+    }
+    return MME_OK;
+}
+
 extern "C" {
 
 int mme_abi_version(void) { return MME_ABI_VERSION; }
@@ -385,7 +401,7 @@ void mme_destroy(mme_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     for (void* p : c->allocs) (void)hipFree(p);
-    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->retiled};
+    DevBuf* bufs[] = {&c->x, &c->hbuf, &c->qkv, &c->att, &c->mlp, &c->patches, &c->tmp, &c->htab, &c->crops, &c->hwork, &c->page_ws, &c->cluster_ws, &c->stats, &c->lnpart, &c->neigh_ws, &c->zero_bias, &c->attn_guard, &c->attn_apply, &c->pooled, &c->projf, &c->retiled, &c->pool_grids};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->lut) (void)hipFree(c->lut);
@@ -571,6 +587,65 @@ int mme_set_tile_order(mme_ctx* c, int mode) {
 int mme_set_forward_pruning(mme_ctx* c, int on) {
     if (!c) return MME_E_ARG;
     c->prune_last = on != 0;
+    return MME_OK;
+}
+
+// ---- pooling over the covered patch tokens -------------------------------------------------------------------
+int mme_set_pooling(mme_ctx* c, int mode) {
+    if (!c) return MME_E_ARG;
+    if (mode < MME_POOL_TOKEN || mode > MME_POOL_CLS_MEAN)
+        return fail(c, MME_E_ARG, "mme_set_pooling: mode = %d; supported %d (MME_POOL_TOKEN), %d (MME_POOL_MEAN) and %d (MME_POOL_CLS_MEAN)", mode, MME_POOL_TOKEN,
+                    MME_POOL_MEAN, MME_POOL_CLS_MEAN);
+    if (mode != MME_POOL_TOKEN) {
+        const char* enc = !c->loaded ? (c->tv ? "tile_vit" : "none loaded") : c->siglip ? "siglip" : c->clip ? "clip" : nullptr;
+        if (enc)
+            return fail(c, MME_E_STATE, "mme_set_pooling: mode = %d with encoder %s; supported: modes %d and %d with a vit or dinov2 tower loaded (CLIP's "
+                                        "projection and SigLIP's head pool for themselves), mode %d everywhere", mode, enc, MME_POOL_MEAN, MME_POOL_CLS_MEAN, MME_POOL_TOKEN);
+    }
+    c->pool_mode = mode;
+    return MME_OK;
+}
+
+int mme_pooling(mme_ctx* c, int32_t* mode) {
+    if (!c || !mode) return fail(c, MME_E_ARG, "mme_pooling: null argument");
+    *mode = c->pool_mode;
+    return MME_OK;
+}
+
+int mme_pool_grid(int h, int w, int patch, int32_t out_rc[2]) {
+    if (!out_rc) return fail(nullptr, MME_E_ARG, "mme_pool_grid: out_rc is NULL");
+    if (h < 1 || h > 8000 || w < 1 || w > 8000) return fail(nullptr, MME_E_ARG, "mme_pool_grid: crop size %dx%d (h x w); supported 1..8000", h, w);
+    if (patch != 14 && patch != 16 && patch != 32) return fail(nullptr, MME_E_ARG, "mme_pool_grid: patch = %d; supported 14, 16 and 32", patch);
+    int nh, nw;
+    fit_to_canvas(h, w, &nh, &nw);
+    out_rc[0] = (nh + patch - 1) / patch;  // a patch counts when it holds at least one pixel of the resized crop
+    out_rc[1] = (nw + patch - 1) / patch;
+    return MME_OK;
+}
+
+int mme_pool_grids(mme_ctx* c, const int32_t* hw, int n, int32_t* grids) {
+    if (!c) return MME_E_ARG;
+    if (n < 0 || (n > 0 && (!hw || !grids))) return fail(c, MME_E_ARG, "mme_pool_grids: null argument or n<0");
+    return pool_grids_host(c, "mme_pool_grids", hw, n, grids);
+}
+
+int mme_pool_apply(mme_ctx* c, int op, const mme_pool_apply_args* a, void* stream) {
+    if (int r = hook_args(c, "mme_pool_apply", a, op, 1)) return r;
+    const HookCheck h{c, "mme_pool_apply", op};
+    if (int r = h.width(a->d)) return r;
+    if (int r = h.ln_in(a->x, a->gamma, a->beta)) return r;
+    if (int r = h.out_pair(a->emb_f32, a->emb_bf16, "emb_f32", "emb_bf16")) return r;
+    if (a->grids && ((uintptr_t)a->grids & 7) != 0) return h.needs("grids 8-byte aligned (device int32 [B, 2]) or NULL");
+    if (a->B < 0 || a->B > (1 << 20)) return fail(c, MME_E_ARG, "mme_pool_apply: B = %d outside 0..2^20", a->B);
+    if (a->g < 1 || a->g > 16) return fail(c, MME_E_ARG, "mme_pool_apply: g = %d; supported 1..16", a->g);
+    if (a->first != 0 && a->first != 1) return fail(c, MME_E_ARG, "mme_pool_apply: first = %d; supported 0 and 1", a->first);
+    if (op == 1 && a->first != 1) return fail(c, MME_E_ARG, "mme_pool_apply: op 1 (cls+mean) needs first == 1: row 0 is the class row (first = %d)", a->first);
+    if (a->tokens != a->first + a->g * a->g)
+        return fail(c, MME_E_ARG, "mme_pool_apply: tokens = %d; supported first + g * g = %d", a->tokens, a->first + a->g * a->g);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(c, launch_pool_mean(a->x, a->gamma, a->beta, a->grids, a->B, a->tokens, a->g, a->first, op == 1, a->d, a->eps, a->emb_f32, a->emb_bf16, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
     return MME_OK;
 }
 

@@ -73,6 +73,7 @@ int new_tile_dev(mme_ctx* c, const mme_tile_vit_weights* w) {
     TileVitDev* t = new (std::nothrow) TileVitDev();
     if (!t) return fail(c, MME_E_NOMEM, "mme_load_tile_vit: out of host memory");
     c->tv = t;
+    c->pool_mode = MME_POOL_TOKEN;  // as every image-tower load
     t->layers = w->layers;
     t->global_layers = w->global_layers;
     t->ni = w->n_intermediate;

@@ -107,6 +107,9 @@ struct mme_ctx {
     DevBuf attn_guard;      // int[max(64, layers)]: one guard word per layer of a pass (encoder_pass.h, reset_attn_guards)
     DevBuf attn_apply;      // mme_attention_apply: its own guard word (int 0), the tile counts from int 16 on
     bool prune_last = false;  // mme_set_forward_pruning
+    int pool_mode = MME_POOL_TOKEN;  // mme_set_pooling; every load sets it back to MME_POOL_TOKEN
+    DevBuf pool_grids;               // int32 [n, 2]: the covered grids of a call (mme_vit_forward_grids) or of a chunk (the pixel path)
+    std::vector<int32_t> h_pool_grids;  // host staging of a chunk's grids
     int zigzag = 1;           // EncoderPass::zigzag of the image towers (image_tower.hip): 1 = consecutive kernels walk the rows in opposite directions, 2 = attention only
     int attn_mode = 1;      // mme_set_attention_mode: 0 exact, 1 fast (guarded), 2 fast with the guard forced (tests)
     DevBuf x, hbuf, qkv, att, mlp, stats, lnpart, patches, tmp, htab, crops, hwork, page_ws, cluster_ws, neigh_ws, zero_bias;
@@ -146,8 +149,12 @@ inline void release_alloc_range(mme_ctx* c, size_t& lo, size_t& hi, size_t& othe
 }
 
 int fail(mme_ctx* c, int code, const char* fmt, ...);
-// width of the rows mme_vit_forward / mme_embed write
-inline int embed_dim(const mme_ctx* c) { return c->proj_dim ? c->proj_dim : c->geom.hidden; }
+// width of the rows mme_vit_forward / mme_embed write ([y_0 | m] under MME_POOL_CLS_MEAN, which only a tower without projection takes)
+inline int embed_dim(const mme_ctx* c) { return c->proj_dim ? c->proj_dim : (c->pool_mode == MME_POOL_CLS_MEAN ? 2 : 1) * c->geom.hidden; }
+// The covered grids (R, C) of n crops under the context's patch size and resize rule -> out int32 [n, 2] (capi.hip, mme_pool_grids):
+// the fit-and-pad rule covers ceil(new / patch) patches per axis, every rule that fills the canvas all of them.  A crop outside
+// 1..8000 is MME_E_ARG in `who`'s name.
+int pool_grids_host(mme_ctx* c, const char* who, const int32_t* hw, int n, int32_t* out);
 
 #define HIP_TRY(c, expr)                                                                            \
     do {                                                                                            \

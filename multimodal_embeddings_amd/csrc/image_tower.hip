@@ -38,6 +38,11 @@ struct PassOut {
     // tokens bf16 [n, ntok, hidden], and the last block runs unpruned whatever prune_last says
     bf16_t* tokens = nullptr;
     int tok0 = 0, ntok = 0;
+    // mme_set_pooling (forward_chunks fills both in): under MME_POOL_MEAN / MME_POOL_CLS_MEAN the tail averages the patch rows of
+    // every crop's covered grid -- grids: DEVICE int32 [n, 2] of the chunk, null = whole grids -- pool_token is not read, and
+    // the last block runs unpruned as for a token pass
+    int pool_mode = MME_POOL_TOKEN;
+    const int32_t* grids = nullptr;
 };
 
 // Patch embedding and token rows into x, the guard reset, and the first LayerNorm statistics of the pass (those of every
@@ -124,8 +129,8 @@ int blocks(EncoderPass& P, int n, const PassOut& o) {
         const LayerDev& L = c->layer[l];
         const bool last = l + 1 == G.layers;
         if ((r = P.first_half(L, L.ln1_g, L.ln1_b, M, 3 * P.D))) return r;
-        // (the unfolded form, SigLIP's head and a token pass read every token row)
-        const bool pruned = c->prune_last && last && !P.unfolded() && !c->siglip && !o.tokens;
+        // (the unfolded form, SigLIP's head, a token pass and mean pooling read every token row)
+        const bool pruned = c->prune_last && last && !P.unfolded() && !c->siglip && !o.tokens && o.pool_mode == MME_POOL_TOKEN;
         const int only_block = pruned ? o.pool_token / 32 : -1;
         {
             Timed t(c, s, KC_ATTN);
@@ -201,7 +206,11 @@ int tail(EncoderPass& P, int n, const PassOut& o) {
     if (c->siglip) return siglip_head(P, n, o);
     if (c->proj_dim) return clip_projection(P, n, o);
     Timed t(c, s, KC_POOL);
-    HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, o.pool_token, D, c->ln_eps, o.emb_f32, o.emb_bf16, s));
+    if (o.pool_mode != MME_POOL_TOKEN)
+        HIP_TRY(c, launch_pool_mean(c->x.p, c->lnf_g, c->lnf_b, o.grids, n, T, VIT_IMG / c->geom.patch, 1, o.pool_mode == MME_POOL_CLS_MEAN, D, c->ln_eps,
+                                    o.emb_f32, o.emb_bf16, s));
+    else
+        HIP_TRY(c, launch_pool(c->x.p, c->lnf_g, c->lnf_b, n, T, o.pool_token, D, c->ln_eps, o.emb_f32, o.emb_bf16, s));
     return MME_OK;
 }
 
@@ -249,18 +258,34 @@ int ensure_pixel_path(mme_ctx* c) {
 
 // The chunk loop of the four forward entry points.  pix null: `patches` holds the n crops' patch matrices.  Else every
 // chunk is preprocessed first (K1 -> retile -> pass), behind a synchronise: the crop tables of successive chunks reuse
-// one device buffer.
-int forward_chunks(mme_ctx* c, const bf16_t* patches, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, const PassOut& all, hipStream_t s) {
+// one device buffer.  Under mme_set_pooling's mean modes the covered grids go to the device in c->pool_grids: those of a patch
+// call (`grids`: host int32 [n, 2], validated by the caller; null = whole grids, nothing is copied) once, those of the pixel
+// path (pool_grids_host over the chunk's crop sizes) per chunk behind the same synchronise.
+int forward_chunks(mme_ctx* c, const bf16_t* patches, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, PassOut all, hipStream_t s,
+                   const int32_t* grids = nullptr) {
     bf16_t* staged = (bf16_t*)(c->geom.patch != VIT_PATCH ? c->retiled.p : c->patches.p);
     const size_t E = embed_dim(c), tok_values = (size_t)all.ntok * c->geom.hidden;
+    all.pool_mode = c->pool_mode;
+    const bool mean = all.pool_mode != MME_POOL_TOKEN;
+    int r;
+    if (mean && (pix || grids)) {
+        if ((r = ensure(c, c->pool_grids, (size_t)(pix && n > c->chunk ? c->chunk : n) * 2 * sizeof(int32_t)))) return r;
+        if (!pix) HIP_TRY(c, hipMemcpyAsync(c->pool_grids.p, grids, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
     for (int s0 = 0; s0 < n; s0 += c->chunk) {
         const int m = n - s0 < c->chunk ? n - s0 : c->chunk;
-        int r;
         if (pix) {
             if (s0 > 0) HIP_TRY(c, hipStreamSynchronize(s));
             if ((r = patches_chunk(c, pix, offs + s0, hw + 2 * s0, m, staged, s))) return r;
+            if (mean) {
+                c->h_pool_grids.resize((size_t)2 * m);
+                if ((r = pool_grids_host(c, "mme_embed", hw + 2 * s0, m, c->h_pool_grids.data()))) return r;
+                // a pageable-host copy, staged before the call returns: the vector is free for the next chunk
+                HIP_TRY(c, hipMemcpyAsync(c->pool_grids.p, c->h_pool_grids.data(), (size_t)m * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            }
         }
         PassOut o = all;
+        if (mean && (pix || grids)) o.grids = (const int32_t*)c->pool_grids.p + (pix ? 0 : (size_t)2 * s0);
         if (o.emb_f32) o.emb_f32 += s0 * E;
         if (o.emb_bf16) o.emb_bf16 += s0 * E;
         if (o.tokens) o.tokens += s0 * tok_values;
@@ -312,6 +337,24 @@ int mme_vit_forward(mme_ctx* c, const uint16_t* patches, int n, int pool_token, 
     int r = ensure_workspace(c);
     if (r) return r;
     return forward_chunks(c, (const bf16_t*)patches, nullptr, nullptr, nullptr, n, PassOut{pool_token, emb_f32, (bf16_t*)emb_bf16}, (hipStream_t)stream);
+}
+
+int mme_vit_forward_grids(mme_ctx* c, const uint16_t* patches, int n, const int32_t* grids, float* emb_f32, uint16_t* emb_bf16, void* stream) {
+    if (!c) return MME_E_ARG;
+    if (!c->loaded) return fail(c, MME_E_STATE, "mme_vit_forward_grids: call mme_load_vit first");
+    if (c->pool_mode == MME_POOL_TOKEN)
+        return fail(c, MME_E_STATE, "mme_vit_forward_grids: pooling mode %d (MME_POOL_TOKEN); supported: %d (MME_POOL_MEAN) and %d (MME_POOL_CLS_MEAN), see mme_set_pooling",
+                    MME_POOL_TOKEN, MME_POOL_MEAN, MME_POOL_CLS_MEAN);
+    if (n < 0 || (n > 0 && !patches)) return fail(c, MME_E_ARG, "mme_vit_forward_grids: null patches or n<0");
+    const int g = VIT_IMG / c->geom.patch;
+    for (int i = 0; grids && i < 2 * n; ++i)
+        if (grids[i] < 1 || grids[i] > g)
+            return fail(c, MME_E_ARG, "mme_vit_forward_grids: grids[%d][%d] = %d; supported 1..%d (the %d x %d patch grid)", i / 2, i % 2, grids[i], g, g, g);
+    if (n == 0) return MME_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int r = ensure_workspace(c);
+    if (r) return r;
+    return forward_chunks(c, (const bf16_t*)patches, nullptr, nullptr, nullptr, n, PassOut{0, emb_f32, (bf16_t*)emb_bf16}, (hipStream_t)stream, grids);
 }
 
 int mme_embed(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, int pool_token, float* emb_f32,

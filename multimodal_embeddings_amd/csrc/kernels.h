@@ -99,6 +99,13 @@ hipError_t launch_pool(const void* x, const float* gamma, const float* beta, int
 // row K8's bf16 output for that pool token bit for bit; tokens: any image layout, 0 <= tok0, 1 <= ntok, tok0 + ntok <= tokens
 hipError_t launch_token_rows(const void* x, const float* gamma, const float* beta, int n, int tokens, int tok0, int ntok, int d, float eps, void* y,
                              hipStream_t s);
+// Mean pooling over the covered patch tokens (pooling.hip): the final LayerNorm of the rows first + r * g + c,
+// r < R, c < C, of crop b, their f32 mean m in the fixed order of pooling.hip, then m / max(||m||, 1e-12) -> [B, d], or under
+// cls_mean [y_0 | m] / max(||.||, 1e-12) -> [B, 2 d] (f32 and / or bf16).  grids: DEVICE int32 [B, 2] (R, C), each 1..g (the
+// caller validates; the kernel clamps), or null: (g, g) for every crop.  tokens == first + g * g, g <= 16, first 0 or 1 (1 under
+// cls_mean), d as launch_pool; else hipErrorInvalidValue
+hipError_t launch_pool_mean(const void* x, const float* gamma, const float* beta, const int32_t* grids, int B, int tokens, int g, int first,
+                            bool cls_mean, int d, float eps, float* emb_f32, void* emb_bf16, hipStream_t s);
 // behind a patch-embed GEMM under EPI_F32 (acc f32 [n * patches, d]), one rounding per value: with a class token (cls
 // non-null; tokens = 50 or 257) x[b*tokens + 1 + p] = bf16((acc + bias) + pos[1 + p]) and x[b*tokens] = bf16(cls + pos[0]);
 // without one (cls null; tokens = patches = 196) x[b*tokens + p] = bf16((acc + bias) + pos[p]).  tokens: an image layout whose

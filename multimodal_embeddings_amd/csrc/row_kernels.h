@@ -16,15 +16,28 @@ template <int D> struct RowShape {
     typedef __attribute__((ext_vector_type(V))) float fvec;
 };
 
-// bf16 row -> v[]: v[t * V + j] is column t * 64 V + lane * V + j
-template <int D> __device__ __forceinline__ void row_load(const bf16_t* xr, int lane, float (&v)[D / 64]) {
+// the bf16 row as its lanes load it, not yet widened: NT independent loads (a kernel that wants several rows in flight issues
+// these for all of them before it widens the first)
+template <int D> __device__ __forceinline__ void row_load_raw(const bf16_t* xr, int lane, typename RowShape<D>::bvec (&p)[RowShape<D>::NT]) {
+    typedef RowShape<D> RS;
+#pragma unroll
+    for (int t = 0; t < RS::NT; ++t) p[t] = *(const typename RS::bvec*)(xr + t * 64 * RS::V + lane * RS::V);
+}
+// p[] -> v[]: v[t * V + j] is column t * 64 V + lane * V + j
+template <int D> __device__ __forceinline__ void row_widen(const typename RowShape<D>::bvec (&p)[RowShape<D>::NT], float (&v)[D / 64]) {
     typedef RowShape<D> RS;
 #pragma unroll
     for (int t = 0; t < RS::NT; ++t) {
-        const typename RS::bvec p = *(const typename RS::bvec*)(xr + t * 64 * RS::V + lane * RS::V);
 #pragma unroll
-        for (int j = 0; j < RS::V; ++j) v[t * RS::V + j] = (float)p[j];
+        for (int j = 0; j < RS::V; ++j) v[t * RS::V + j] = (float)p[t][j];
     }
+}
+
+// bf16 row -> v[]: v[t * V + j] is column t * 64 V + lane * V + j
+template <int D> __device__ __forceinline__ void row_load(const bf16_t* xr, int lane, float (&v)[D / 64]) {
+    typename RowShape<D>::bvec p[RowShape<D>::NT];
+    row_load_raw<D>(xr, lane, p);
+    row_widen<D>(p, v);
 }
 
 // (mean, rstd) of the row in v[], which stays as it is: two wave reductions, the sums over v[0..] ascending
@@ -42,12 +55,10 @@ template <int D> __device__ __forceinline__ float2 row_stats(const float (&v)[D 
     return make_float2(mean, rsqrtf(wave_sum(q) * (1.0f / D) + eps));
 }
 
-// LayerNorm of the bf16 row xr: v[] leaves normalised, scaled and shifted, in f32
+// LayerNorm of the row already in v[] (row_load's layout): v[] leaves normalised, scaled and shifted, in f32
 template <int D>
-__device__ __forceinline__ void ln_row(const bf16_t* xr, const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int lane,
-                                       float (&v)[D / 64]) {
+__device__ __forceinline__ void ln_apply(const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int lane, float (&v)[D / 64]) {
     typedef RowShape<D> RS;
-    row_load<D>(xr, lane, v);
     const float2 st = row_stats<D>(v, eps);
 #pragma unroll
     for (int t = 0; t < RS::NT; ++t) {
@@ -57,6 +68,14 @@ __device__ __forceinline__ void ln_row(const bf16_t* xr, const float* __restrict
 #pragma unroll
         for (int j = 0; j < RS::V; ++j) v[t * RS::V + j] = (v[t * RS::V + j] - st.x) * st.y * gv[j] + bv[j];
     }
+}
+
+// LayerNorm of the bf16 row xr: v[] leaves normalised, scaled and shifted, in f32
+template <int D>
+__device__ __forceinline__ void ln_row(const bf16_t* xr, const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int lane,
+                                       float (&v)[D / 64]) {
+    row_load<D>(xr, lane, v);
+    ln_apply<D>(gamma, beta, eps, lane, v);
 }
 
 // v[] -> bf16 row, one rounding to nearest even per value
@@ -71,16 +90,22 @@ template <int D> __device__ __forceinline__ void row_store_bf16(bf16_t* yr, int 
     }
 }
 
-// The L2 step: v / max(||v||_2, 1e-12) -> the row at element `off` of yf (f32) and / or yb (bf16; either may be null), the
-// bf16 value the rounding of the f32 one.  n2 sums over v[0..] ascending.  A row narrower than D (`cols`, a multiple of 64,
-// RowShape<1024> only) holds zeros at the columns >= cols, and nothing is stored there.
-template <int D>
-__device__ __forceinline__ void row_l2_store(const float (&v)[D / 64], int lane, float* yf, bf16_t* yb, int64_t off, int cols = D) {
-    typedef RowShape<D> RS;
+// this lane's share of ||v||^2, summed over v[0..] ascending
+template <int D> __device__ __forceinline__ float row_sumsq(const float (&v)[D / 64]) {
     float n2 = 0.f;
 #pragma unroll
     for (int j = 0; j < D / 64; ++j) n2 += v[j] * v[j];
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), 1e-12f);
+    return n2;
+}
+
+// 1 / max(||v||_2, 1e-12) from the wave's sum of squares
+__device__ __forceinline__ float l2_inverse(float n2) { return 1.0f / fmaxf(sqrtf(n2), 1e-12f); }
+
+// v * inv -> the row at element `off` of yf (f32) and / or yb (bf16; either may be null), the bf16 value the rounding of the
+// f32 one.  A row narrower than D (`cols`, a multiple of 64, RowShape<1024> only): nothing is stored at the columns >= cols.
+template <int D>
+__device__ __forceinline__ void row_scale_store(const float (&v)[D / 64], float inv, int lane, float* yf, bf16_t* yb, int64_t off, int cols = D) {
+    typedef RowShape<D> RS;
 #pragma unroll
     for (int t = 0; t < RS::NT; ++t) {
         const int c = t * 64 * RS::V + lane * RS::V;
@@ -95,6 +120,13 @@ __device__ __forceinline__ void row_l2_store(const float (&v)[D / 64], int lane,
         if (yf) *(typename RS::fvec*)(yf + off + c) = o;
         if (yb) *(typename RS::bvec*)(yb + off + c) = ob;
     }
+}
+
+// The L2 step: v / max(||v||_2, 1e-12) -> the row at element `off` of yf / yb (row_scale_store).  n2 sums over v[0..]
+// ascending.  A row narrower than D holds zeros at the columns >= cols.
+template <int D>
+__device__ __forceinline__ void row_l2_store(const float (&v)[D / 64], int lane, float* yf, bf16_t* yb, int64_t off, int cols = D) {
+    row_scale_store<D>(v, l2_inverse(wave_sum(row_sumsq<D>(v))), lane, yf, yb, off, cols);
 }
 
 // launches the instantiation of a row kernel for width d; a width without one is an error, never another kernel.  The

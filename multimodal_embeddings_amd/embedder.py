@@ -200,6 +200,10 @@ class RegionEmbedder:
         position table is interpolated to 16 x 16 once at load, seeded weights at `geometry=` a weights.Dinov2Geometry, default
         weights.DINOV2_B14, or a `weights=` dict in transformers' names; it has no text tower) or "mllama_tiles".
         `self.embed_dim` is the width of the vectors this object returns (a CLIP tower's projection_dim).
+        `pool`: "cls" or "last" return one token row; "mean" (encoder "vit" and "dinov2") returns the L2-normalised mean of the
+        final-LayerNorm patch rows the crop covers on the 224 x 224 canvas -- under the fit-and-pad rule most of a column's or a
+        strip's canvas is padding, which stays out of the mean -- and "cls+mean" the class row and that mean side by side under
+        one L2 norm (`embed_dim` = 2 x hidden; transformers' Dinov2ForImageClassification feature).  DESIGN.md 4.26.
         `resize_rule`: how K1 makes the 224 x 224 pixels of a crop.  None and "fit_pad" are the aspect-preserving BILINEAR
         fit with zero padding; "clip" is CLIPImageProcessor's shortest-edge-224 BICUBIC resize + centre crop (the single-tile
         encoders only; a checkpoint's preprocessor_config.json must then describe exactly that rule).  It is set on every
@@ -231,6 +235,9 @@ class RegionEmbedder:
                              "'dinov2' (a DINOv2 ViT/14 image tower) or 'mllama_tiles' (the checkpoint's own vision-tower geometry)")
         if encoder == "siglip_vit" and pool != "cls":
             raise ValueError(f"pool = {pool!r}: encoder='siglip_vit' pools with the tower's attention-pooling head; supported: the default")
+        if pool in ("mean", "cls+mean") and encoder not in ("vit", "dinov2"):
+            raise ValueError(f"pool = {pool!r}: encoder={encoder!r} pools one token row, or for itself (CLIP's projection, the tile tower's features); "
+                             "supported: 'mean' and 'cls+mean' with encoder='vit' and encoder='dinov2'")
         # this class spells the tower "siglip_vit" (the bare name "siglip" stays a refused encoder here); below it is checkpoint.py's "siglip"
         if encoder == "siglip_vit":
             encoder = "siglip"
@@ -313,11 +320,16 @@ class RegionEmbedder:
             # drives the Engine directly and times the whole forward; `prune_last_layer=False` restores that here.
             for e in self.engines:
                 e.set_forward_pruning(True)
-        if pool not in ("cls", "last"):
-            raise ValueError("pool must be 'cls' or 'last'")
+        if pool not in ("cls", "last", "mean", "cls+mean"):
+            raise ValueError("pool must be 'cls' or 'last' (one token row), or 'mean' or 'cls+mean' (the mean of the patch rows a crop covers; "
+                             "encoder='vit' and 'dinov2')")
+        self.pool = pool
+        if pool in ("mean", "cls+mean"):
+            for e in self.engines:  # every context pools alike: the covered patches of each crop, [class row | mean] under "cls+mean"
+                e.set_pooling(pool)
         # the last token: 196 of the 197 at patch 16 (the same at every width), 49 of the 50 at patch 32, 256 of the 257 at patch 14
-        # (SigLIP: the library ignores the token, the head pools)
-        self.pool_token = 0 if pool == "cls" else (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1)
+        # (SigLIP: the library ignores the token, the head pools; so do the mean modes)
+        self.pool_token = (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1) if pool == "last" else 0
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
         self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
         self._seed = seed
