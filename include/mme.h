@@ -627,8 +627,8 @@ int mme_attention_apply(mme_ctx* ctx, int kind, const uint16_t* qkv_dev, int n, 
  *               outside the page read as 0, as PIL's Image.crop fills them.  A corner may be any
  *               int32, however far outside the page: sizes and byte columns are formed in 64 bits,
  *               and a box whose x1 - x0 or y1 - y0 is not in 1..8000 is MME_E_ARG, named by index
- *   pix_dev     destination buffer; offs_host int64[n] byte offset of crop i in it (same
- *               packing rule as mme_preprocess: 16-byte aligned crops, 16 bytes of slack) */
+ *   pix_dev     destination buffer; offs_host int64[n] byte offset of crop i in it (the packing
+ *               rule of mme_preprocess: any byte offsets, 16 bytes of slack behind the last pixel) */
 int mme_crop_boxes(mme_ctx* ctx, const uint8_t* page_dev, int H, int W, const int32_t* boxes_host, int n, uint8_t* pix_dev,
                    const int64_t* offs_host, void* stream);
 
@@ -694,7 +694,13 @@ int mme_nms_boxes(mme_ctx* ctx, const double* boxes, const double* scores, const
  * (768 = 3 * 16 * 16, the patch row: the same at every hidden size).
  *   pix_dev     uint8 RGB HWC pixels of all crops, concatenated; the allocation must
  *               extend at least 16 bytes past the last pixel (rows are read in words)
- *   offs_host   int64[n]   byte offset of crop i inside pix_dev
+ *   offs_host   int64[n]   byte offset of crop i inside pix_dev.  THE ALIGNMENT RULE, for mme_preprocess, mme_embed,
+ *                          mme_preprocess_tiles and mme_crop_boxes alike: an offset may be ANY byte offset >= 0 and crops
+ *                          may follow one another without a gap; the result is the same bit for bit wherever a crop
+ *                          starts (tests/test_gpu_k1_extremes.py runs every rule at offsets 1, 2, 3, 5, 7, 9, 11, 13
+ *                          and 15 mod 16).  The only requirement is the 16 bytes of allocation behind the last pixel,
+ *                          above.  Starting crops at multiples of 16 is a matter of speed (the band fetch then has no
+ *                          lead, and 224 x 224 crops take the 16-byte copy), not of correctness.
  *   hw_host     int32[n,2] (height, width) of crop i  (int()-truncated bbox size,
  *                          doclayout_detector.py:179)
  *   patches_dev bf16[n*196, 768]; under a patch-32 context (mme_vit_geometry: patch_size 32) bf16[n*49, 3072], the same
@@ -795,6 +801,51 @@ int mme_pooling(mme_ctx* ctx, int32_t* mode);
 /* The fit-and-pad covered grid of one h x w crop at `patch`: out_rc = (R, C).  A host function, no context and no GPU (errors:
  * mme_last_error(NULL)).  h, w outside 1..8000 or patch not 14, 16 or 32: MME_E_ARG. */
 int mme_pool_grid(int h, int w, int patch, int32_t out_rc[2]);
+
+/* ---- K1's plan, seen from the host ---------------------------------------------------------------------------------------
+ * What mme_preprocess / mme_embed (rule kind 0: fit-and-pad; kind 1: a resize spec -- MME_RESIZE_CLIP is the spec {shortest
+ * edge, 224, 0, BICUBIC}) and mme_preprocess_tiles (kind 2) decide on the host for a batch of n crops of sizes hw_host int32
+ * [n, 2] (h, w): one record per crop, computed by the very functions those entry points plan with.  A host function: no
+ * context and no GPU (errors: mme_last_error(NULL)).  Nothing is launched and nothing allocated on a device.
+ * MME_E_ARG: a null pointer, n < 0, a kind outside 0..2, a spec mme_set_resize_spec refuses, a (tile, max_tiles)
+ * mme_preprocess_tiles refuses.  A crop the entry point would refuse the BATCH for is no error here: its record says so
+ * (`refused`), every other field of that record that could be computed is filled in, and planning goes on behind it as if
+ * the crop were absent (it takes no table and no scratch bytes).
+ * totals, if not NULL: [0] table bytes, [1] scratch bytes, [2] bands of the horizontal pass over all three classes,
+ * [3] the largest kv of the batch.
+ * bands_host, if not NULL: int32 [bands_cap, 4] receives the band list itself, (crop, first source row, rows, class) per band
+ * in the order the entry point copies it to the device (class 0 | 1 | 2); MME_E_ARG when the batch has more than bands_cap
+ * bands.  With NULL the bands are counted and not listed, which makes a record cost well under a microsecond. */
+enum { MME_K1_RULE_FIT_PAD = 0, MME_K1_RULE_SPEC = 1, MME_K1_RULE_TILES = 2 };
+enum {
+    MME_K1_OK = 0,
+    MME_K1_REFUSED_SIZE = 1,      /* h or w outside 1..8000 */
+    MME_K1_REFUSED_TILE_TAPS = 2, /* tiles: the vertical window exceeds 160 taps (kv holds the window's taps) */
+    MME_K1_REFUSED_H_LDS = 3,     /* the horizontal launch of this crop's class would ask for more than 160 KiB of LDS */
+    MME_K1_REFUSED_V_TAPS = 4     /* fit-and-pad, spec: kv exceeds the 160 taps the vertical pass holds */
+};
+typedef struct mme_k1_rule {
+    int32_t kind;         /* MME_K1_RULE_* */
+    mme_resize_spec spec; /* kind 1 */
+    int32_t tile, max_tiles; /* kind 2 */
+} mme_k1_rule;
+typedef struct mme_k1_record {
+    int32_t new_h, new_w; /* the resized size (kind 1: of the WHOLE resized image) */
+    int32_t top, left;    /* kind 1: origin of the 224 x 224 centre window in the resized image; else 0 */
+    int32_t r0, nr;       /* kind 1: the source rows [r0, r0 + nr) the horizontal pass filters; else 0, h */
+    int32_t th, tw;       /* kind 2: the tile grid; else 1, 1 */
+    int32_t h_pass, v_pass; /* 1 when that axis is filtered (its size changes) */
+    int32_t gh, kv;       /* capacities of the tables: groups of four horizontal taps; vertical taps (a multiple of 4) */
+    int32_t h_class;      /* class of the horizontal pass: 0 eight-row, 1 four-row, 2 table through L1; -1: no bands */
+    int32_t band_rows, n_bands; /* source rows per band and bands; 0, 0 without bands */
+    int32_t h_lds;        /* dynamic LDS bytes the horizontal launch of h_class asks for if this crop is its widest; 0 without bands */
+    int32_t v_lds;        /* dynamic LDS bytes of the vertical kernel if this crop's kv is the batch's largest; 0 for tiles (static LDS) */
+    int32_t refused;      /* MME_K1_OK or why the entry point refuses the batch because of this crop */
+    int64_t tab_off, tab_bytes; /* this crop's tables in the table buffer */
+    int64_t tmp_off, tmp_bytes; /* this crop's scratch image (0 bytes without a horizontal pass under kinds 0 and 2) */
+} mme_k1_record;
+int mme_k1_plan(const mme_k1_rule* rule, const int32_t* hw_host, int n, mme_k1_record* out, int64_t totals[4], int32_t* bands_host,
+                int64_t bands_cap);
 /* The grids the pixel path of THIS context uses (its patch size and resize rule) for n crops of hw_host int32 [n, 2] (h, w):
  * grids_host int32 [n, 2].  Host only. */
 int mme_pool_grids(mme_ctx* ctx, const int32_t* hw_host, int n, int32_t* grids_host);

@@ -197,6 +197,18 @@ class _ResizeSpec(C.Structure):  # mme_resize_spec
     _fields_ = [(f, C.c_int32) for f in ("mode", "height", "width", "resample")]
 
 
+class _K1Rule(C.Structure):  # mme_k1_rule
+    _fields_ = [("kind", C.c_int32), ("spec", _ResizeSpec), ("tile", C.c_int32), ("max_tiles", C.c_int32)]
+
+
+K1_RECORD_INT32 = ("new_h", "new_w", "top", "left", "r0", "nr", "th", "tw", "h_pass", "v_pass", "gh", "kv", "h_class", "band_rows", "n_bands", "h_lds", "v_lds",
+                   "refused")
+K1_RECORD_INT64 = ("tab_off", "tab_bytes", "tmp_off", "tmp_bytes")
+# mme_k1_record as a numpy record: 18 int32 then 4 int64 (72 bytes in: the int64 fields are naturally aligned)
+K1_RECORD = np.dtype([(f, np.int32) for f in K1_RECORD_INT32] + [(f, np.int64) for f in K1_RECORD_INT64], align=True)
+K1_REFUSALS = {0: None, 1: "size", 2: "tile_taps", 3: "h_lds", 4: "v_taps"}  # MME_K1_REFUSED_*
+
+
 class _SilhouetteOut(C.Structure):  # mme_silhouette_out
     _fields_ = [(f, C.c_void_p) for f in ("sample", "cluster", "score", "info", "sums", "counts")]
 
@@ -260,6 +272,7 @@ EXPORTS = {
     "mme_pooling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mme_pool_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "mme_pool_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mme_k1_plan": (C.c_int, [C.POINTER(_K1Rule), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "mme_vit_forward_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_pool_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_PoolApplyArgs), C.c_void_p]),
     "mme_normalise_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
@@ -1096,6 +1109,35 @@ class Engine:
         if lib.mme_pool_grid(int(h), int(w), int(patch), rc) != 0:
             raise MmeError(f"mme_pool_grid failed: {lib.mme_last_error(None).decode()}")
         return int(rc[0]), int(rc[1])
+
+    @staticmethod
+    def k1_plan(rule, hw, *, tile: int = 560, max_tiles: int = 4, bands: bool = False):
+        """(records, totals): what K1 plans on the host for crops of sizes hw [n, 2] (h, w) under `rule` -- "fit_pad", "clip", a
+        `ResizeSpec`, or "tiles" with (tile, max_tiles) (mme_k1_plan; a host function, no GPU needed).  records: a numpy record
+        array of K1_RECORD, one per crop; totals: int64 [4] = table bytes, scratch bytes, bands, largest kv.  bands=True: a third
+        value, int32 [bands, 4] = (crop, first source row, rows, class) of every band of the horizontal pass in launch order."""
+        lib = load_library()
+        raw = _K1Rule()
+        if rule == "fit_pad":
+            raw.kind = 0
+        elif rule == "tiles":
+            raw.kind, raw.tile, raw.max_tiles = 2, int(tile), int(max_tiles)
+        else:
+            spec = ResizeSpec("shortest_edge", 224, 0, 3) if rule == "clip" else rule
+            if not isinstance(spec, ResizeSpec):
+                raise MmeError(f"k1_plan rule = {rule!r}; supported 'fit_pad', 'clip', 'tiles' and a ResizeSpec")
+            raw.kind, raw.spec = 1, _ResizeSpec(int(spec.mode_number), int(spec.height), int(spec.width), int(spec.resample))
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(hw), dtype=K1_RECORD)
+        totals = np.zeros(4, dtype=np.int64)
+        if lib.mme_k1_plan(C.byref(raw), hw.ctypes.data, len(hw), out.ctypes.data, totals.ctypes.data, None, 0) != 0:
+            raise MmeError(f"mme_k1_plan failed: {lib.mme_last_error(None).decode()}")
+        if not bands:
+            return out, totals
+        listed = np.zeros((int(totals[2]), 4), dtype=np.int32)
+        if lib.mme_k1_plan(C.byref(raw), hw.ctypes.data, len(hw), out.ctypes.data, totals.ctypes.data, listed.ctypes.data, len(listed)) != 0:
+            raise MmeError(f"mme_k1_plan failed: {lib.mme_last_error(None).decode()}")
+        return out, totals, listed
 
     def pool_grids(self, hw) -> np.ndarray:
         """int32 [n, 2]: the covered grids the pixel path of this context uses for crops of sizes hw [n, 2] (mme_pool_grids)."""

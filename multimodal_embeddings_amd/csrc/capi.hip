@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "encoder_pass.h"
+#include "k1_plan.h"
 #include "resample.h"
 
 namespace {
@@ -122,62 +123,6 @@ int set_lut(mme_ctx* c, const float mean[3], const float stdv[3]) {
     return MME_OK;
 }
 
-// Mllama single-tile fit (transformers image_processing_pil_mllama.py:246-295, canvas == tile)
-void fit_to_canvas(int h, int w, int* nh, int* nw) {
-    const double scale_h = (double)VIT_IMG / h, scale_w = (double)VIT_IMG / w;
-    if (scale_w < scale_h) {
-        *nw = VIT_IMG;
-        int v = (int)std::floor(h * scale_w);
-        if (v == 0) v = 1;
-        *nh = v < VIT_IMG ? v : VIT_IMG;
-    } else {
-        *nh = VIT_IMG;
-        int v = (int)std::floor(w * scale_h);
-        if (v == 0) v = 1;
-        *nw = v < VIT_IMG ? v : VIT_IMG;
-    }
-}
-
-// K1 plan shared by the two preprocessing entry points: scratch image + resampling tables of every crop and the bands of
-// the horizontal pass.  A band is a whole number of row groups (the rows one work item filters).  Three classes, one
-// launch each:
-//   0  table + eight rows fit kHLds bytes of LDS: eight-row items, table in LDS beside the band (five workgroups per CU at 32 KiB)
-//   1  table + four rows fit: four-row items, table in LDS
-//   2  wider crops: one four-row group per band, the table read through L1, LDS sized for the widest of them
-struct K1Plan {
-    size_t tmp_bytes = 0, tab_bytes = 0;
-    std::vector<HWork> work[3];
-    int lds[3] = {16, 16, 16};  // largest (table +) band per class
-    int count[3] = {0, 0, 0};
-    int kv_max = 0;  // largest K1Layout::kv of the batch (LDS of the vertical pass)
-};
-// LDS budget of classes 0 and 1
-constexpr int kHLds = 32 * 1024;
-
-// The bands of crop i's horizontal pass: source rows [first_row, first_row + nrows) of row_bytes each, whose table takes
-// tab_lds bytes of LDS when it rides beside the band.  Picks the class and appends the bands to it.
-void plan_bands(K1Plan& p, int i, int row_bytes, int tab_lds, int first_row, int nrows) {
-    const int fit = tab_lds < kHLds ? (kHLds - tab_lds) / row_bytes : 0;  // rows that fit beside the table
-    const int cls = fit >= K1_H_RPT ? 0 : (fit >= K1_H_RPT_WIDE ? 1 : 2);
-    int rows = cls == 0 ? (fit & ~(K1_H_RPT - 1)) : K1_H_RPT_WIDE;
-    if (rows > 64) rows = 64;
-    for (int r = 0; r < nrows; r += rows) p.work[cls].push_back(HWork{i, first_row + r, (nrows - r) < rows ? (nrows - r) : rows});
-    const int bb = (rows < nrows ? rows : nrows) * row_bytes + (cls < 2 ? tab_lds : 0);
-    if (bb > p.lds[cls]) p.lds[cls] = bb;
-}
-
-void plan_crop(mme_ctx* c, K1Plan& p, int i, CropDesc& d) {
-    d.tmp_off = 0;
-    d.tab_off = (int64_t)p.tab_bytes;
-    const K1Layout lay = k1_layout(d.h, d.w, d.new_h, d.new_w);
-    p.tab_bytes += (size_t)lay.bytes;
-    if (lay.kv > p.kv_max) p.kv_max = lay.kv;
-    if (d.new_w == d.w) return;
-    d.tmp_off = (int64_t)p.tmp_bytes;
-    p.tmp_bytes += (size_t)d.h * k1_tmp_pitch(d.new_w);
-    plan_bands(p, i, d.w * 3, k1_h_table_lds(d.w, d.new_w), 0, d.h);
-}
-
 // copies the band lists to the device (class 0 | class 1 | class 2)
 int run_h_pass(mme_ctx* c, K1Plan& p, const uint8_t* pix, int n, hipStream_t s, const char* who) {
     c->h_work.clear();
@@ -211,65 +156,10 @@ int launch_h_pass(mme_ctx* c, const K1Plan& p, const uint8_t* pix, int n, hipStr
     return launch_h_pass<CropDesc>(c, p, pix, n, s, who, "", launch_resample_tables, launch_resize_h);
 }
 
-// ---- K1 under MME_RESIZE_CLIP and MME_RESIZE_SPEC (preprocess_clip.hip) ---------------------------------------------------
-// One path serves both: rule 1 is the spec below, what CLIPImageProcessorPil does.
-constexpr mme_resize_spec kClipSpec = {MME_RESIZE_MODE_SHORTEST_EDGE, VIT_IMG, 0, 3};
+// ---- K1 under MME_RESIZE_CLIP and MME_RESIZE_SPEC (preprocess_clip.hip): kClipSpec and the plan are k1_plan.h's ---------------
 // the spec mme_preprocess runs under the context's rule; null under the fit-and-pad rule
 const mme_resize_spec* spec_of(const mme_ctx* c) {
     return c->resize_rule == MME_RESIZE_SPEC ? &c->resize_spec : (c->resize_rule == MME_RESIZE_CLIP ? &kClipSpec : nullptr);
-}
-// a 224 x 224 crop is resized to 224 x 224, i.e. not filtered on either axis, and its centre window is the crop
-bool spec_keeps_canvas(const mme_resize_spec& sp) {
-    return sp.mode == MME_RESIZE_MODE_EXACT ? (sp.height == VIT_IMG && sp.width == VIT_IMG) : sp.height == VIT_IMG;
-}
-// The size of the whole resized image.  EXACT: the spec's.  SHORTEST_EDGE S: transformers image_transforms.py
-// get_resize_output_image_size, size = {"shortest_edge": S}, default_to_square = False: the short edge gets S, the long
-// edge int(S * long / short) -- the Python float expression in that order, in f64
-void spec_resized_size(const mme_resize_spec& sp, int h, int w, int* nh, int* nw) {
-    if (sp.mode == MME_RESIZE_MODE_EXACT) {
-        *nh = sp.height;
-        *nw = sp.width;
-        return;
-    }
-    const int sh = h <= w ? h : w, lg = h <= w ? w : h;
-    const int nl = (int)((double)(sp.height * (int64_t)lg) / (double)sh);
-    *nh = h <= w ? sp.height : nl;
-    *nw = h <= w ? nl : sp.height;
-}
-// Resample.c's ksize (resample.h), the upper bound of a window's taps; 1 for an axis that is not filtered
-template <class Filter>
-int axis_ksize(int in_size, int out_size) {
-    return in_size == out_size ? 1 : resample_ksize<Filter>(in_size, out_size);
-}
-
-// Sizes against the 8000 x 8000 limit, resized edges >= 224: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145 (BICUBIC; 73 for
-// BILINEAR), so gh <= 37 and kv <= 148 (the vertical pass holds 160); a crop's tables take <= 3584 + 37 * 3584 + 224 * 148 * 4
-// = 268 800 bytes and its scratch image <= 8000 * 672 = 5 376 000 bytes (nr <= h), both summed in size_t.  The widest
-// class-2 band is 4 * 24000 bytes of LDS.  Filter = the spec's (Triangle for resample 2, Bicubic for 3).
-template <class Filter>
-void plan_spec_crop(K1Plan& p, int i, ClipCropDesc& d, const mme_resize_spec& sp) {
-    spec_resized_size(sp, d.h, d.w, &d.new_h, &d.new_w);
-    d.top = (d.new_h - VIT_IMG) / 2;
-    d.left = (d.new_w - VIT_IMG) / 2;
-    if (d.new_h != d.h) {
-        // the union of the 224 vertical windows: the expressions clip_tables evaluates on the device (resample.h); the
-        // whole source height when the window is the whole resized image (an exact 224 target)
-        const Taps first = resample_window<Filter>(d.h, d.new_h, d.top), last = resample_window<Filter>(d.h, d.new_h, d.top + VIT_IMG - 1);
-        const int a = first.xmin, z = last.xmin + last.n;
-        d.r0 = a;
-        d.nr = (z > a ? z : a + 1) - a;
-    } else {
-        d.r0 = d.top;
-        d.nr = VIT_IMG;
-    }
-    d.gh = (axis_ksize<Filter>(d.w, d.new_w) + 3) >> 2;
-    d.kv = (axis_ksize<Filter>(d.h, d.new_h) + 3) & ~3;
-    if (d.kv > p.kv_max) p.kv_max = d.kv;
-    d.tab_off = (int64_t)p.tab_bytes;
-    p.tab_bytes += (size_t)clip_layout(d.gh, d.kv).bytes;
-    d.tmp_off = (int64_t)p.tmp_bytes;
-    p.tmp_bytes += (size_t)d.nr * (VIT_IMG * 3);
-    plan_bands(p, i, d.w * 3, clip_h_table_lds(d.gh), d.r0, d.nr);
 }
 
 int preprocess_chunk_spec(mme_ctx* c, const mme_resize_spec& sp, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, bf16_t* patches,
@@ -282,10 +172,7 @@ int preprocess_chunk_spec(mme_ctx* c, const mme_resize_spec& sp, const uint8_t* 
         d.src_off = offs[i];
         d.h = hw[2 * i];
         d.w = hw[2 * i + 1];
-        if (bilinear)
-            plan_spec_crop<Triangle>(plan, i, d, sp);
-        else
-            plan_spec_crop<Bicubic>(plan, i, d, sp);
+        plan_spec_crop(plan, i, d, sp);
     }
     int r;
     if ((r = ensure(c, c->crops, (size_t)n * sizeof(ClipCropDesc)))) return r;
@@ -324,7 +211,7 @@ int preprocess_chunk(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const 
         d.h = h;
         d.w = w;
         fit_to_canvas(h, w, &d.new_h, &d.new_w);
-        plan_crop(c, plan, i, d);
+        plan_crop(plan, i, d);
     }
     int r;
     if ((r = ensure(c, c->crops, (size_t)n * sizeof(CropDesc)))) return r;
@@ -623,6 +510,38 @@ int mme_pool_grid(int h, int w, int patch, int32_t out_rc[2]) {
     return MME_OK;
 }
 
+int mme_k1_plan(const mme_k1_rule* rule, const int32_t* hw, int n, mme_k1_record* out, int64_t totals[4], int32_t* bands, int64_t bands_cap) {
+    if (!rule || n < 0 || (n > 0 && (!hw || !out))) return fail(nullptr, MME_E_ARG, "mme_k1_plan: null argument or n < 0");
+    if (rule->kind < MME_K1_RULE_FIT_PAD || rule->kind > MME_K1_RULE_TILES)
+        return fail(nullptr, MME_E_ARG, "mme_k1_plan: rule kind = %d; supported 0 (fit-and-pad), 1 (resize spec) and 2 (tiles)", rule->kind);
+    if (rule->kind == MME_K1_RULE_SPEC && !spec_admitted(rule->spec))
+        return fail(nullptr, MME_E_ARG, "mme_k1_plan: spec {mode %d, height %d, width %d, resample %d} is none mme_set_resize_spec admits", rule->spec.mode,
+                    rule->spec.height, rule->spec.width, rule->spec.resample);
+    if (rule->kind == MME_K1_RULE_TILES && !tiles_admitted(rule->tile, rule->max_tiles))
+        return fail(nullptr, MME_E_ARG, "mme_k1_plan: need tile in 8..1024 (multiple of 8), max_tiles in 1..16; got %d, %d", rule->tile, rule->max_tiles);
+    K1Plan plan;
+    plan.list_bands = bands != nullptr;
+    k1_plan_records(*rule, hw, n, out, plan);
+    if (totals) {
+        totals[0] = (int64_t)plan.tab_bytes;
+        totals[1] = (int64_t)plan.tmp_bytes;
+        totals[2] = (int64_t)plan.nbands;
+        totals[3] = plan.kv_max;
+    }
+    if (bands) {
+        if ((int64_t)plan.nbands > bands_cap)
+            return fail(nullptr, MME_E_ARG, "mme_k1_plan: the batch has %zu bands, bands_host holds %lld", plan.nbands, (long long)bands_cap);
+        for (int k = 0; k < 3; ++k)  // the order run_h_pass copies them in
+            for (const HWork& wk : plan.work[k]) {
+                *bands++ = wk.crop;
+                *bands++ = wk.row0;
+                *bands++ = wk.nrows;
+                *bands++ = k;
+            }
+    }
+    return MME_OK;
+}
+
 int mme_pool_grids(mme_ctx* c, const int32_t* hw, int n, int32_t* grids) {
     if (!c) return MME_E_ARG;
     if (n < 0 || (n > 0 && (!hw || !grids))) return fail(c, MME_E_ARG, "mme_pool_grids: null argument or n<0");
@@ -776,67 +695,11 @@ int mme_cluster_pages(mme_ctx* c, const double* S, int P, int n_clusters, int mo
     return MME_OK;
 }
 
-// ---- Mllama tile canvas (transformers image_processing_pil_mllama.py:216-355), f64 like numpy ----
-static void optimal_tile_grid(int h, int w, int max_tiles, int tile, int* th, int* tw) {
-    // supported grids (a, b), a outer / b inner (:216-243), treated as (tiles_h, tiles_w) (:329-332)
-    int ga[64], gb[64], ng = 0;
-    double sc[64];
-    for (int a = 1; a <= max_tiles; ++a)
-        for (int b = 1; b <= max_tiles; ++b)
-            if (a * b <= max_tiles && ng < 64) {
-                const double sh = (double)(a * tile) / (double)h, sw = (double)(b * tile) / (double)w;
-                ga[ng] = a;
-                gb[ng] = b;
-                sc[ng++] = sw > sh ? sh : sw;  // np.where(scale_w > scale_h, scale_h, scale_w)
-            }
-    bool any_up = false;
-    double sel = 0.0;
-    for (int i = 0; i < ng; ++i)
-        if (sc[i] >= 1.0 && (!any_up || sc[i] < sel)) {  // smallest upscaling factor (:337-339)
-            sel = sc[i];
-            any_up = true;
-        }
-    if (!any_up) {
-        bool first = true;
-        for (int i = 0; i < ng; ++i)
-            if (first || sc[i] > sel) {  // largest downscaling factor (:340-343)
-                sel = sc[i];
-                first = false;
-            }
-    }
-    long best_area = -1;
-    for (int i = 0; i < ng; ++i)
-        if (sc[i] == sel) {  // ties: smallest canvas area, first in list order (:346-353)
-            const long area = (long)(ga[i] * tile) * (long)(gb[i] * tile);
-            if (best_area < 0 || area < best_area) {
-                best_area = area;
-                *th = ga[i];
-                *tw = gb[i];
-            }
-        }
-}
-
-static void fit_to_tile_canvas(int h, int w, int canvas_h, int canvas_w, int tile, int* nh, int* nw) {
-    const int target_w = w < tile ? tile : (w > canvas_w ? canvas_w : w);
-    const int target_h = h < tile ? tile : (h > canvas_h ? canvas_h : h);
-    const double scale_h = (double)target_h / (double)h, scale_w = (double)target_w / (double)w;
-    if (scale_w < scale_h) {
-        *nw = target_w;
-        int v = (int)std::floor((double)h * scale_w);
-        if (v == 0) v = 1;
-        *nh = v < target_h ? v : target_h;
-    } else {
-        *nh = target_h;
-        int v = (int)std::floor((double)w * scale_h);
-        if (v == 0) v = 1;
-        *nw = v < target_w ? v : target_w;
-    }
-}
-
+// ---- Mllama tile canvas: the grid and the fit are k1_plan.h's ----
 int mme_preprocess_tiles(mme_ctx* c, const uint8_t* pix, const int64_t* offs, const int32_t* hw, int n, int tile, int max_tiles,
                          float* out, int32_t* aspect_ids_host, int32_t* num_tiles_host, void* stream) {
     if (!c) return MME_E_ARG;
-    if (n < 0 || tile < 8 || tile > 1024 || (tile % 8) != 0 || max_tiles < 1 || max_tiles > 16)
+    if (n < 0 || !tiles_admitted(tile, max_tiles))
         return fail(c, MME_E_ARG, "mme_preprocess_tiles: need n >= 0, tile in 8..1024 (multiple of 8), max_tiles in 1..16");
     if (n == 0) return MME_OK;
     if (!pix || !offs || !hw || !out) return fail(c, MME_E_ARG, "mme_preprocess_tiles: null pointer");
@@ -849,24 +712,16 @@ int mme_preprocess_tiles(mme_ctx* c, const uint8_t* pix, const int64_t* offs, co
     for (int i = 0; i < n; ++i) {
         const int h = hw[2 * i], w = hw[2 * i + 1];
         if (h <= 0 || w <= 0 || h > 8000 || w > 8000) return fail(c, MME_E_ARG, "crop %d has size %dx%d (h x w); supported 1..8000", i, h, w);
-        int th = 1, tw = 1;
-        optimal_tile_grid(h, w, max_tiles, tile, &th, &tw);
-        grid[2 * i] = th;
-        grid[2 * i + 1] = tw;
         CropDesc& d = c->h_crops[i];
         d.src_off = offs[i];
         d.h = h;
         d.w = w;
-        fit_to_tile_canvas(h, w, th * tile, tw * tile, tile, &d.new_h, &d.new_w);
-        // resize_v_tiles holds a row's vertical taps in MAX_TAPS words of LDS; a longer window would be cut short there
-        // (wrong pixels, no error), so such a batch is refused whole, before anything is launched.  The horizontal pass
-        // sizes its table from the crop and has no such limit.
-        if (d.new_h != h) {
-            const int window = resample_ksize<Triangle>(h, d.new_h);
-            if (window > MAX_TAPS)
-                return fail(c, MME_E_ARG, "mme_preprocess_tiles: crop %d is %dx%d (h x w) and becomes %d rows: a vertical window of %d taps; the limit is %d taps",
-                            i, h, w, d.new_h, window, MAX_TAPS);
-        }
+        int th, tw;
+        if (const int window = tile_crop_size(d, tile, max_tiles, &th, &tw))
+            return fail(c, MME_E_ARG, "mme_preprocess_tiles: crop %d is %dx%d (h x w) and becomes %d rows: a vertical window of %d taps; the limit is %d taps",
+                        i, h, w, d.new_h, window, MAX_TAPS);
+        grid[2 * i] = th;
+        grid[2 * i + 1] = tw;
         if (aspect_ids_host) {  // 1 + index of (th, tw) in the supported list (image_processing_pil_mllama.py:136-164)
             int idx = 0, found = 0;
             for (int a = 1; a <= max_tiles && !found; ++a)
@@ -878,7 +733,7 @@ int mme_preprocess_tiles(mme_ctx* c, const uint8_t* pix, const int64_t* offs, co
             aspect_ids_host[i] = found;
         }
         if (num_tiles_host) num_tiles_host[i] = th * tw;
-        plan_crop(c, plan, i, d);
+        plan_crop(plan, i, d);
     }
     int r;
     const size_t desc_bytes = ((size_t)n * sizeof(CropDesc) + 15) & ~(size_t)15;

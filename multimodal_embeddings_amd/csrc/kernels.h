@@ -124,7 +124,7 @@ hipError_t launch_attention(const void* qkv, void* out, int B, int heads, hipStr
 // diagnostic: stamped build of the fast or the exact form, stamps uint64[B][8][8]
 hipError_t launch_attention_stamped(const void* qkv, void* out, int B, int heads, bool fast, unsigned long long* stamps, hipStream_t s);
 
-struct CropDesc {  // one per crop, built on the host by capi
+struct CropDesc {  // one per crop, built on the host (k1_plan.h: plan_crop)
     int64_t src_off;   // byte offset into pix
     int64_t tmp_off;   // byte offset (16-aligned) into the horizontal-pass scratch (if the width changes)
     int64_t tab_off;   // byte offset (16-aligned) of this crop's resampling tables in the table buffer (K1Layout)
@@ -145,6 +145,8 @@ __host__ __device__ inline int k1_tmp_pitch(int new_w) { return (new_w * 3 + 15)
 // of k1_layout) equal resample_ksize<Triangle> (resample.h) rounded up to a multiple of four: ceil(max(w / new_w, 1)) is the
 // integer ceiling of w / new_w (1 for an enlarged axis in both); they stay integer so that a layout function does not
 // depend on f64.
+// Held over every admitted size (1..8000 x 1..8000) by tests/test_k1_plan_cpu.py, which also finds the attained maxima: under
+// fit-and-pad ksize <= 143, gh <= 36, kv <= 144 (a 70 x 7841 crop becomes one row), and a window's true length never exceeds ksize.
 // groups of four taps per output column of the horizontal pass
 __host__ __device__ inline int k1_h_groups(int w, int new_w) { return (2 * ((w + new_w - 1) / new_w) + 1 + 3) >> 2; }
 // bytes of LDS the horizontal table of a crop takes beside its band (table padded to whole 1 KiB DMA sweeps)
@@ -170,7 +172,7 @@ constexpr int K1_H_RPT = 8;       // source rows one item of the horizontal pass
 constexpr int K1_H_RPT_WIDE = 4;  // ... in the second launch (crops whose table + eight rows do not fit the LDS budget)
 // both tap tables of every crop, once per crop (f64 on the device exactly as Resample.c computes them on the host)
 hipError_t launch_resample_tables(const CropDesc* crops, int n, uint8_t* tab, hipStream_t s);
-// horizontal pass over `nwork` bands of ONE class (capi: K1Plan): 0 = eight-row items, table in LDS beside the band;
+// horizontal pass over `nwork` bands of ONE class (k1_plan.h: K1Plan): 0 = eight-row items, table in LDS beside the band;
 // 1 = four-row items, table in LDS; 2 = four-row items, table through L1.  lds_bytes = the largest (table +) band.
 // (launch_resize_h and launch_clip_resize_h are the one kernel template of resample.h over the two descriptors.)
 hipError_t launch_resize_h(const uint8_t* pix, uint8_t* tmp, const CropDesc* crops, const HWork* work, int nwork, int lds_bytes,
@@ -197,7 +199,7 @@ hipError_t launch_resize_v_patchify(const uint8_t* pix, const uint8_t* tmp, cons
 // shortest edge 224, BICUBIC; a spec's: mme_resize_spec) + centre crop, only the 224 x 224 window of the resized image
 // computed.  What CropDesc cannot carry: the FULL resized sizes, the window's origin and the
 // source rows the horizontal pass filters.
-struct ClipCropDesc {  // one per crop, built on the host by capi (plan_clip_crop)
+struct ClipCropDesc {  // one per crop, built on the host (k1_plan.h: plan_spec_crop)
     int64_t src_off;       // byte offset into pix
     int64_t tmp_off;       // byte offset (16-aligned) of this crop's scratch image: nr rows of 672 bytes
     int64_t tab_off;       // byte offset (16-aligned) of this crop's tables (ClipLayout)

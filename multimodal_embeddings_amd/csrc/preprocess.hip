@@ -300,12 +300,12 @@ hipError_t launch_resize_v_patchify(const uint8_t* pix, const uint8_t* tmp, cons
     if (n <= 0) return hipSuccess;
     // the LDS window (16 KiB per chunk) is only needed when some crop is resized or partially fills the canvas; the
     // all-224x224 batch keeps the small footprint (more workgroups per CU for a pure stream)
-    constexpr int window = 16 * 1024;
-    const int kvs = kv_max < 4 ? 4 : ((kv_max + 3) & ~3);
+    constexpr int window = K1_V_WINDOW;
+    const int kvs = k1_v_stride(kv_max);
     if (kvs > MAX_TAPS) return hipErrorInvalidValue;
     const int kk_bytes = VIT_PATCH * kvs * (int)sizeof(int);
     if (any_resize) {
-        const int smem = kk_bytes + window + DMA_SLACK;
+        const int smem = k1_v_lds_request(kvs);
         if (hipError_t e = ensure_dynamic_lds((const void*)resize_v_patchify<true>, smem); e != hipSuccess) return e;
         hipLaunchKernelGGL(resize_v_patchify<true>, dim3(n * VIT_GRID), dim3(512), smem, s, pix, tmp, crops, lut, (bf16_t*)patches, tab, window, kvs, aff);
     } else {

@@ -164,10 +164,10 @@ hipError_t launch_clip_resize_h(const uint8_t* pix, uint8_t* tmp, const ClipCrop
 hipError_t launch_clip_v_patchify(const uint8_t* tmp, const ClipCropDesc* crops, int n, const float* lut, const NormAffine& aff, void* patches,
                                   const uint8_t* tab, int kv_max, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    constexpr int window = 16 * 1024;
-    const int kvs = kv_max < 4 ? 4 : ((kv_max + 3) & ~3);
+    constexpr int window = K1_V_WINDOW;
+    const int kvs = k1_v_stride(kv_max);
     if (kvs > MAX_TAPS) return hipErrorInvalidValue;
-    const int smem = VIT_PATCH * kvs * (int)sizeof(int) + window + DMA_SLACK;
+    const int smem = k1_v_lds_request(kvs);
     if (hipError_t e = ensure_dynamic_lds((const void*)clip_v_patchify, smem); e != hipSuccess) return e;
     hipLaunchKernelGGL(clip_v_patchify, dim3(n * VIT_GRID), dim3(512), smem, s, tmp, crops, lut, (bf16_t*)patches, tab, window, kvs, aff);
     return hipGetLastError();

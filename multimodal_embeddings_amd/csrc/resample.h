@@ -16,7 +16,7 @@
 #include "kernels.h"
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
-constexpr int MAX_TAPS = 160;  // taps a vertical window of K1 may hold: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145 (BICUBIC)
+constexpr int MAX_TAPS = 160;  // taps a vertical window of K1 may hold: ksize <= 2 * ceil(2 * 8000 / 224) + 1 = 145 (BICUBIC; attained: k1_plan.h)
 
 struct Taps {
     int xmin, n;
@@ -140,6 +140,15 @@ __device__ __forceinline__ void dma_range_to_lds(const uint4* __restrict__ g, ch
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     for (int i = wave * 64; i < nvec; i += NT) glds16(g + min(i + lane, nvec - 1), lds + (size_t)i * 16);
 }
+// The dynamic LDS K1's launches ask for, from one text for the launchers and for the host's view of the plan (mme_k1_plan).
+// Horizontal pass: lds_bytes = (padded table +) one band; + alignment lead (<= 15) + vector rounding (<= 15) + the last tap
+// group's over-read (<= 9 bytes, zero weights) + the DMA sweep's slack.  A launch above K1_LDS_LIMIT is refused.
+constexpr int K1_LDS_LIMIT = 160 * 1024;
+inline size_t k1_h_lds_request(int lds_bytes) { return (size_t)lds_bytes + 64 + DMA_SLACK; }
+// Vertical pass + patchify: kk[16][kvs] | window | slack; kvs = the batch's largest kv, at least 4; refused above MAX_TAPS
+constexpr int K1_V_WINDOW = 16 * 1024;
+inline int k1_v_stride(int kv_max) { return kv_max < 4 ? 4 : ((kv_max + 3) & ~3); }
+inline int k1_v_lds_request(int kvs) { return VIT_PATCH * kvs * (int)sizeof(int) + K1_V_WINDOW + DMA_SLACK; }
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // The fixed-point sum of a pass: from 2^21, pixel byte x 22-bit coefficient, shift by 22, clamp to a byte.  pack() makes
@@ -348,16 +357,14 @@ __global__ __launch_bounds__(256) void resize_h(const uint8_t* __restrict__ pix,
     }
 }
 
-// `nwork` bands of ONE class (capi: K1Plan): 0 = eight-row items, table in LDS beside the band; 1 = four-row items, table in
+// `nwork` bands of ONE class (k1_plan.h: K1Plan): 0 = eight-row items, table in LDS beside the band; 1 = four-row items, table in
 // LDS; 2 = four-row items, table through L1.  lds_bytes = the largest (table +) band.
 template <class Crop>
 hipError_t launch_resize_h_of(const uint8_t* pix, uint8_t* tmp, const typename Crop::Desc* crops, const HWork* work, int nwork, int lds_bytes,
                               int cls, const uint8_t* tab, hipStream_t s) {
     if (nwork <= 0) return hipSuccess;
-    // lds_bytes = (padded table +) one band; + alignment lead (<= 15) + vector rounding (<= 15) + the last tap group's
-    // over-read (<= 9 bytes, zero weights) + the DMA sweep's slack
-    const size_t smem = (size_t)lds_bytes + 64 + DMA_SLACK;
-    if (smem > 160 * 1024 || cls < 0 || cls > 2) return hipErrorInvalidValue;
+    const size_t smem = k1_h_lds_request(lds_bytes);
+    if (smem > K1_LDS_LIMIT || cls < 0 || cls > 2) return hipErrorInvalidValue;
     auto* fn = cls == 0 ? resize_h<Crop, true, K1_H_RPT> : (cls == 1 ? resize_h<Crop, true, K1_H_RPT_WIDE> : resize_h<Crop, false, K1_H_RPT_WIDE>);
     if (hipError_t e = ensure_dynamic_lds((const void*)fn, (int)smem); e != hipSuccess) return e;
     hipLaunchKernelGGL(fn, dim3(nwork), dim3(256), smem, s, pix, tmp, crops, work, tab);
