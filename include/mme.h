@@ -1091,6 +1091,43 @@ int mme_silhouette(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const in
 int mme_silhouette_rows(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* labels_dev, int k,
                         const double* sums_dev, const int32_t* counts_dev, double* sample_dev, void* stream);
 
+/* ---- K17: centre, reduce and whiten the vector table -------------------------------
+ * A PCA basis fitted on the table itself: the device computes the moments and applies the projection, the host solves the
+ * d x d eigenproblem in float64 (region_compare.projection_from_moments; not a hot path).
+ *
+ * Moments (K17a), mme_moments: emb_dev bf16 [N, d], any finite values.  With B = MME_MOMENTS_BLOCK (part of the definition,
+ * not of the grid) and block b covering the rows b B .. min(N, (b + 1) B) - 1:
+ *     p_b[c]    = sum_i x[i, c]             P_b[a, c] = sum_i x[i, a] x[i, c]
+ *   every value widened from bf16 to f64, each sum starting from +0.0 and taking its rows in ascending i, one f64 addition per
+ *   row (the product of two bf16 values is exact in f64: an fma and a multiply-then-add give the same bits);
+ *     sum  = ((0 + p_0) + p_1) + ...        gram = ((0 + P_0) + P_1) + ...
+ *   in ascending block order.  gram is symmetric bit for bit (the upper triangle of 64 x 64 tiles is computed and mirrored).
+ *   No floating-point atomics: the result is bit-identical run to run and equal to the float64 restatement
+ *   (tests/projection_reference.py).  The per-block partials go through the K12 workspace, in groups of blocks when they do
+ *   not all fit; a group continues where the one before stopped, so the grouping changes no bit.
+ *   sum_dev f64 [d], gram_dev f64 [d, d].
+ * Projection (K17b), mme_project:  y[i, j] = sum_c (f32(x[i, c]) - mean[c]) * w[j, c],  j < m, in f32 throughout (one rounding
+ *   for the difference, fused multiply-adds over c in an order the kernel chooses).  Against y64, the same expression in
+ *   float64 from the same f32 mean and w:  |y - y64| <= (d + 2) 2^-24 sum_c |x[i, c] - mean[c]| |w[j, c]|.
+ *   mean_dev f32 [d] and w_dev f32 [m, d] are the host's float64 mean and components rounded once to f32.  Outputs, at least one:
+ *     y_f32_dev   [N, ld_y], ld_y >= m and ld_y % 4 == 0; the columns m .. ld_y - 1 are not written
+ *     y_bf16_dev  [N, m], only with m % 64 == 0: the f32 rows L2-normalised exactly as mme_normalise_rows does it, bit for bit
+ * Both are asynchronous on `stream` and never wait for the device (except that a workspace that has to grow is reallocated
+ * behind a device synchronise, as everywhere); both work on a bare context.  Profiling class: "cluster".
+ * MME_E_ARG, with the field and the value in mme_last_error, nothing enqueued, the context usable: N outside 1..2^24; d not a
+ * multiple of 64, or outside 64..1024 for the moments (64..65536 for the projection); m outside 1..d; y_bf16_dev with
+ * m % 64 != 0; both outputs null; y_f32_dev with ld_y < m or ld_y % 4 != 0; a null or misaligned pointer (16 bytes; 8 for
+ * sum_dev and gram_dev). */
+#define MME_MOMENTS_BLOCK 1024
+int mme_moments(mme_ctx* ctx, const uint16_t* emb_dev, int64_t N, int d, double* sum_dev, double* gram_dev, void* stream);
+int mme_project(mme_ctx* ctx, const uint16_t* emb_dev, int64_t N, int d, const float* mean_dev, const float* w_dev, int m,
+                float* y_f32_dev, int64_t ld_y, uint16_t* y_bf16_dev, void* stream);
+
+/* Diagnostic: K17a with group_blocks row blocks per workspace group (0 = what the workspace holds, 1..65535 otherwise), then a
+ * stream synchronise -- so that a test can make the groups run on a small table; the bits are those of the product call. */
+int mme_moments_apply(mme_ctx* ctx, const uint16_t* emb_dev, int64_t N, int d, int group_blocks, double* sum_dev, double* gram_dev,
+                      void* stream);
+
 /* Diagnostic: time one MFMA GEMM shape on random bf16 data (allocates its own operands;
  * synchronous).  epilogue 0 bias, 1 bias+GELU, 2 bias+residual, 3 patch-embed, 4 f32 out;
  * variant as mme_set_gemm_variant. */

@@ -303,6 +303,9 @@ EXPORTS = {
     "mme_kmeans_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_KmeansApplyArgs), C.c_void_p]),
     "mme_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_SilhouetteOut), C.c_void_p]),
     "mme_silhouette_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mme_moments_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mme_gemm_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mme_gemm_apply": (C.c_int, [C.c_void_p, C.POINTER(_GemmApplyArgs), C.POINTER(C.c_int32), C.c_void_p]),
@@ -1809,6 +1812,68 @@ class Engine:
         N, d = emb_bf16.shape
         self._check(self.lib.mme_silhouette_rows(self.h, self._ptr(emb_bf16), int(N), int(d), self._ptr(labels), int(counts.shape[0]), self._ptr(sums),
                                                  self._ptr(counts), self._ptr(sample), self._stream()), "mme_silhouette_rows")
+
+    # ---- K17 moments and projection of the vector table (mme.h, mme_moments / mme_project) ----
+    MOMENTS_BLOCK = 1024  # MME_MOMENTS_BLOCK
+
+    def moments(self, emb_bf16, group_blocks=None):
+        """(sum float64 [d], gram float64 [d, d]) of the bf16 rows emb_bf16[N, d], CUDA tensors, in the fixed order of mme.h
+        (mme_moments; enqueues and returns).  `group_blocks` (diagnostic, mme_moments_apply; synchronous): that many row
+        blocks per workspace group.  The library validates N and d."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != dev:
+            raise MmeError("moments: emb must be a 2-D bfloat16 tensor on this engine's device")
+        N, d = e.shape
+        s = t.empty(max(d, 1), dtype=t.float64, device=dev)[:d]
+        g = t.empty((max(d, 1), max(d, 1)), dtype=t.float64, device=dev)[:d, :d]
+        if group_blocks is None:
+            self._check(self.lib.mme_moments(self.h, e.data_ptr(), N, d, s.data_ptr(), g.data_ptr(), self._stream()), "mme_moments")
+        else:
+            self._check(self.lib.mme_moments_apply(self.h, e.data_ptr(), N, d, int(group_blocks), s.data_ptr(), g.data_ptr(), self._stream()),
+                        "mme_moments_apply")
+        return s, g
+
+    def _f32_table(self, x, what):
+        """A float32 CUDA tensor of a mean / component table: a tensor on the device as it is (float32 required), anything else
+        (numpy, lists; float64 is rounded once) uploaded on the current stream."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        if t.is_tensor(x) and x.device == dev:
+            if x.dtype != t.float32:
+                raise MmeError(f"project: {what} on the device must be float32, got {x.dtype}")
+            return x.contiguous()
+        host = t.from_numpy(np.ascontiguousarray(np.asarray(x.cpu() if t.is_tensor(x) else x, dtype=np.float64).astype(np.float32)))
+        return host.to(dev)
+
+    def project(self, emb_bf16, mean, components, *, normalise=True, f32=False, out_f32=None):
+        """The rows emb_bf16[N, d] centred by `mean` [d] and projected onto the rows of `components` [m, d] in f32 (mme_project;
+        enqueues and returns).  normalise=True: the L2-normalised bf16 rows [N, m] (m % 64 == 0); f32=True, or normalise=False:
+        the f32 coordinates [N, m]; both: the pair (bf16, f32).  `out_f32`: a float32 CUDA tensor [N, m] whose row pitch may
+        exceed m (a multiple of 4; the columns behind m are not written).  The library validates the shapes."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != dev:
+            raise MmeError("project: emb must be a 2-D bfloat16 tensor on this engine's device")
+        N, d = e.shape
+        mu, w = self._f32_table(mean, "mean").reshape(-1), self._f32_table(components, "components")
+        if w.dim() != 2 or w.shape[1] != d or mu.shape[0] != d:
+            raise MmeError(f"project: mean must be [d = {d}] and components [m, d = {d}], got {tuple(mu.shape)} and {tuple(w.shape)}")
+        m = w.shape[0]
+        want_f32 = bool(f32) or not normalise or out_f32 is not None
+        y32 = None
+        if want_f32:
+            y32 = out_f32 if out_f32 is not None else t.empty((max(N, 1), (m + 3) // 4 * 4), dtype=t.float32, device=dev)[:N, :m]
+            if y32.dtype != t.float32 or y32.dim() != 2 or tuple(y32.shape) != (N, m) or y32.stride(1) != 1 or y32.device != dev:
+                raise MmeError(f"project: out_f32 must be a float32 tensor [N = {N}, m = {m}] with unit column stride on this engine's device")
+        y16 = t.empty((max(N, 1), m), dtype=t.bfloat16, device=dev)[:N] if normalise else None
+        self._check(self.lib.mme_project(self.h, e.data_ptr(), N, d, mu.data_ptr(), w.data_ptr(), m, self._ptr(y32),
+                                         int(y32.stride(0)) if y32 is not None else 0, self._ptr(y16), self._stream()), "mme_project")
+        if normalise and want_f32:
+            return y16, y32
+        return y16 if normalise else y32
 
     def gemm_bench(self, M, N, K, epilogue=0, variant=0, iters=10):
         """(avg ms, TFLOP/s) for one GEMM shape on random data."""

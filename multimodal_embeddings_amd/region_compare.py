@@ -11,6 +11,7 @@ different pages" over all regions at once (kernel K14, `mme_duplicates_*`), and 
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import logging
 import os
@@ -470,3 +471,119 @@ def create_region_cluster_report(collection, n_clusters, output_path=None, **kwa
         with open(output_path, "w") as fh:
             json.dump(result, fh, indent=1)
     return result
+
+
+# ---- K17: centre, reduce and whiten the vector table -----------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class Projection:
+    """A mean and a PCA basis fitted on a vector table (fit_projection / projection_from_moments), float64 numpy arrays:
+    mean [d]; components [m, d], the rows W_j that `transform` applies (v_j, or v_j / sqrt(lambda_j + eps) when whitened);
+    eigenvalues [d], all of them, descending; explained_variance_ratio [d] (each eigenvalue's share of their sum, a negative
+    rounding residue counted as 0); n_rows the rows fitted on; whiten, eps as given."""
+    mean: np.ndarray
+    components: np.ndarray
+    eigenvalues: np.ndarray
+    explained_variance_ratio: np.ndarray
+    n_rows: int
+    whiten: bool
+    eps: float
+
+    @property
+    def n_components(self) -> int:
+        return int(self.components.shape[0])
+
+    def transform(self, vectors, *, normalise=True, engine: Engine | None = None):
+        """W . (x - mean) of every row of `vectors` (lists of floats, numpy or CUDA tensors [N, d]; rounded to unit bf16 rows the
+        way the collection's vectors are; an image vector and a text query vector alike), kernel K17b in f32.  normalise=True:
+        the L2-normalised bf16 CUDA rows [N, m] that K9..K16 take (n_components % 64 == 0); normalise=False: the float32 CUDA
+        coordinates [N, m] for any m (2 for a map)."""
+        m = self.n_components
+        if normalise and m % 64 != 0:
+            raise ValueError(f"transform: n_components = {m} with normalise=True; supported: a multiple of 64 (normalise=False returns "
+                             "float32 coordinates for any n_components)")
+        engine = engine or default_engine()
+        rows = to_unit_bf16(vectors, engine)
+        if rows.shape[1] != self.mean.shape[0]:
+            raise ValueError(f"transform: vectors have d = {rows.shape[1]}; supported: d = {self.mean.shape[0]} (what the projection was fitted on)")
+        return engine.project(rows, self.mean, self.components, normalise=bool(normalise))
+
+
+def projection_from_moments(sum, gram, n, n_components, *, whiten=False, eps=0.0, rank_tol=1e-10) -> Projection:
+    """The host half of the fit, float64 numpy, no device: from sum [d] = the column sums and gram [d, d] = X^T X of n rows
+    (Engine.moments) the mean mu = sum / n, the covariance C = gram / n - mu mu^T (symmetrised), its eigenpairs by
+    numpy.linalg.eigh in descending order, every eigenvector signed so that its entry of largest magnitude (the lowest index
+    among equals) is positive, and the first n_components of them as rows -- divided by sqrt(lambda_j + eps) under whiten.
+    ValueError with the field, the value and the supported set: n < 2, n_components outside 1..d or beyond the numerical rank
+    (the number of lambda_j > rank_tol * lambda_0)."""
+    s = np.asarray(sum, dtype=np.float64).reshape(-1)
+    G = np.asarray(gram, dtype=np.float64)
+    d = s.shape[0]
+    if G.shape != (d, d):
+        raise ValueError(f"projection_from_moments: gram has shape {G.shape}; supported: [d, d] = [{d}, {d}] (sum has {d} columns)")
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"projection_from_moments: n = {n}; supported: at least 2 rows")
+    m = int(n_components)
+    if m < 1 or m > d:
+        raise ValueError(f"projection_from_moments: n_components = {m}; supported 1..d (d = {d})")
+    if not float(eps) >= 0.0:
+        raise ValueError(f"projection_from_moments: eps = {eps}; supported: eps >= 0")
+    mu = s / n
+    C = G / n - np.outer(mu, mu)
+    C = (C + C.T) / 2
+    lam, V = np.linalg.eigh(C)
+    lam, V = lam[::-1].copy(), V[:, ::-1].T.copy()  # descending; rows are eigenvectors
+    big = np.argmax(np.abs(V), axis=1)  # the first among equals
+    V *= np.where(V[np.arange(d), big] < 0, -1.0, 1.0)[:, None]
+    rank = int(np.count_nonzero(lam > float(rank_tol) * lam[0])) if lam[0] > 0 else 0
+    if m > rank:
+        raise ValueError(f"projection_from_moments: n_components = {m}; supported 1..{rank} (the numerical rank of the covariance of {n} rows: "
+                         f"eigenvalues above rank_tol = {rank_tol} times the largest)")
+    W = V[:m] / np.sqrt(lam[:m] + float(eps))[:, None] if whiten else V[:m].copy()
+    pos = np.maximum(lam, 0.0)
+    return Projection(mean=mu, components=np.ascontiguousarray(W), eigenvalues=lam, explained_variance_ratio=pos / pos.sum(), n_rows=n,
+                      whiten=bool(whiten), eps=float(eps))
+
+
+def fit_projection(source, n_components, *, whiten=False, eps=0.0, rank_tol=1e-10, where={"is_region": {"$eq": True}},
+                   engine: Engine | None = None) -> Projection:
+    """A Projection fitted on `source`: a RegionCollection (the rows `where` selects, rows without an embedding left out) or an
+    array / tensor [N, d].  The vectors become unit bf16 rows as everywhere (to_unit_bf16), kernel K17a computes their column
+    sums and second moments in float64 in a fixed order, and projection_from_moments does the rest on the host.  Exact and
+    reproducible: the same table gives the same Projection bit for bit."""
+    engine = engine or default_engine()
+    if hasattr(source, "get") and hasattr(source, "upsert"):
+        all_entries, have = _region_rows(source, where)
+        if len(have) < 2:
+            raise ValueError(f"fit_projection: N = {len(have)} regions with an embedding; supported: at least 2 rows")
+        source = [all_entries["embeddings"][r] for r in have]
+    rows = to_unit_bf16(source, engine)
+    if rows.shape[0] < 2:
+        raise ValueError(f"fit_projection: N = {rows.shape[0]}; supported: at least 2 rows")
+    s, g = engine.moments(rows)
+    return projection_from_moments(s.cpu().numpy(), g.cpu().numpy(), rows.shape[0], n_components, whiten=whiten, eps=eps, rank_tol=rank_tol)
+
+
+def project_collection(collection, projection: Projection, engine: Engine | None = None, *, transform=None):
+    """A new RegionCollection with the same ids, documents and metadatas in the same order and the projected, L2-normalised
+    vectors (Projection.transform; a row without an embedding stays without one).  Its collection-level metadata gains
+    {"projection": {"n_components", "whiten", "n_rows"}}.  The source is not changed.  `transform`: what turns the list of
+    vectors into the projected rows (array-like [n, m]) in place of projection.transform -- a device-free stand-in."""
+    from .weighted_region_clustering import RegionCollection
+
+    rows = collection.get(include=["metadatas", "embeddings", "documents"])
+    emb = list(rows.get("embeddings") if rows.get("embeddings") is not None else [])
+    have = [r for r, e in enumerate(emb) if e is not None and len(e) > 0]
+    out = [None] * len(rows["ids"])
+    if have:
+        vecs = [emb[r] for r in have]
+        y = transform(vecs) if transform is not None else projection.transform(vecs, normalise=True, engine=engine or getattr(collection, "engine", None))
+        y = y.float().cpu().numpy() if hasattr(y, "cpu") else np.asarray(y, dtype=np.float32)
+        for r, v in zip(have, y):
+            out[r] = v
+    new = RegionCollection(metric=getattr(collection, "metric", "cosine"), engine=engine or getattr(collection, "engine", None))
+    new.metadata = {**getattr(collection, "metadata", {}), "projection": {"n_components": projection.n_components, "whiten": bool(projection.whiten),
+                                                                         "n_rows": int(projection.n_rows)}}
+    new.upsert(ids=list(rows["ids"]), embeddings=out, documents=list(rows.get("documents") or [None] * len(rows["ids"])),
+               metadatas=list(rows["metadatas"]))
+    return new

@@ -104,3 +104,29 @@ class ProgressLog:
 
     def __len__(self):
         return len(self._done)
+
+
+_PROJECTION_ARRAYS = ("mean", "components", "eigenvalues", "explained_variance_ratio")
+
+
+def _npz_path(path):
+    path = os.fspath(path)
+    return path if path.endswith(".npz") else path + ".npz"
+
+
+def save_projection(projection, path):
+    """A region_compare.Projection as one `.npz` (the suffix is added when missing): the four float64 arrays as they are, and
+    n_rows, whiten, eps as scalars.  load_projection gives every bit back."""
+    path = _npz_path(path)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, **{f: np.asarray(getattr(projection, f), dtype=np.float64) for f in _PROJECTION_ARRAYS},
+             n_rows=np.int64(projection.n_rows), whiten=np.bool_(projection.whiten), eps=np.float64(projection.eps))
+    return path
+
+
+def load_projection(path):
+    """Inverse of `save_projection`."""
+    from .region_compare import Projection
+
+    with np.load(_npz_path(path)) as z:
+        return Projection(**{f: z[f] for f in _PROJECTION_ARRAYS}, n_rows=int(z["n_rows"]), whiten=bool(z["whiten"]), eps=float(z["eps"]))
