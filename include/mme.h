@@ -993,6 +993,62 @@ int mme_duplicates_merge(mme_ctx* ctx, const mme_dup_state* dst, const mme_dup_s
 int mme_duplicates_finish(mme_ctx* ctx, const mme_dup_state* state, int N, int32_t* labels_dev, int32_t* best_idx_dev,
                           float* best_sim_dev, int64_t* summary_dev, void* stream);
 
+/* ---- K18: density clusters of regions, DBSCAN over the vector table -------------
+ * Adds to the reference: region_compare.py ranks regions (:160-353) and weighted_region_clustering.py clusters PAGES
+ * (:476-543); neither has a region-level clustering.  K14 above is single linkage at a threshold, K15 needs k and places
+ * every row; this answers "which regions belong to a recurring kind of thing, how many kinds, which to none".  The state,
+ * the row-range calls and the refusals have K14's shape (mme_duplicates_* above).
+ *
+ * j is a NEIGHBOUR of i when i != j, group_dev[i] != group_dev[j] (NULL = every pair is admissible) and the f32-accumulated
+ * cosine of the bf16 rows is >= min_sim; against the float64 dot product with delta = 2 * d * 2^-24 as K14: s64 >= min_sim
+ * + delta is a neighbour, s64 < min_sim - delta is none, in between either.  count[i] = neighbours of i (self not counted).
+ * i is CORE when count[i] + 1 >= min_samples (the row itself counts, as in scikit-learn).  A CLUSTER is a connected
+ * component of the core rows under "neighbours"; its id is its smallest core row.  A non-core row with a core neighbour is
+ * a BORDER row of the cluster of its most similar core neighbour (the lower index among bit-equal f32 values); every other
+ * row is NOISE.  Integer adds, maxima of packed keys and a canonical union-find only: bit-identical from run to run.
+ *
+ * The state is caller-owned device memory; all calls enqueue on `stream` and never wait for the device (the cosine blocks
+ * go through the K12 workspace, which grows on first use).
+ *   count     int32[N]   neighbours of the row: an OUTPUT as it stands after the count calls
+ *   parent    int32[N]   union-find forest over the core rows, parent[i] <= i
+ *   border    uint64[N]  best core neighbour of a non-core row as a packed key (mme_density_finish unpacks it)
+ *   counters  uint64[2]  [0] neighbour pairs the count calls found, [1] neighbour pairs the link calls saw
+ * mme_density_init    parent[i] = i, everything else zero.
+ * mme_density_count   the pairs (i, j) with row0 <= i < row0 + nrows and i < j < N, ACCUMULATED into count and counters[0]:
+ *                     calls over disjoint row ranges that cover [0, N) are one count, in any order (nrows = 0 does nothing).
+ * mme_density_link    the same pairs again, with the same row-range meaning (the ranges may be split differently): two core
+ *                     rows are united, a core row is offered to a non-core neighbour's border key.  THE CALLER ORDERS IT
+ *                     BEHIND EVERY COUNT CALL of the table (stream order on one stream suffices): a link pass that runs on
+ *                     counts that are not final links rows that are not core yet wrongly, and nothing detects it.  emb_dev,
+ *                     group_dev and min_sim must be those of the count calls; after link calls that cover [0, N)
+ *                     counters[1] == counters[0].
+ * mme_density_finish  (min_samples as in the link calls)
+ *                     labels_dev int32[N]: the cluster id (its smallest core row) of a core or border row, -1 for noise;
+ *                     kind_dev int32[N]: 2 core, 1 border, 0 noise;
+ *                     border_idx_dev int32[N] / border_sim_dev float[N]: a border row's best core neighbour, (-1, 0) for
+ *                     every other row;
+ *                     summary_dev int64[6]: neighbour pairs found, clusters, core rows, border rows, noise rows, rows of
+ *                     the largest cluster (0 without one).  The state is not changed.
+ * At min_samples = 1 every row is core and labels equal K14's; at 2 there is no border row and the clusters are K14's groups
+ * of >= 2 rows.  There is no merge entry and no multi-GPU form: counts add over row shards, but the link pass needs the
+ * summed counts first.
+ * MME_E_ARG, with the entry point, the field and the value in mme_last_error, nothing enqueued, state and context usable: a
+ * null pointer, d % 64 != 0, a NaN min_sim, min_samples < 1, rows outside [0, N].
+ * Profiling classes: the GEMM counts as "cosine", den_count and den_link as "neighbours", finish as "cluster". */
+typedef struct mme_density_state {
+    int32_t* count;
+    int32_t* parent;
+    uint64_t* border;
+    uint64_t* counters;
+} mme_density_state;
+int mme_density_init(mme_ctx* ctx, const mme_density_state* state, int N, void* stream);
+int mme_density_count(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* group_dev, float min_sim, int row0, int nrows,
+                      const mme_density_state* state, void* stream);
+int mme_density_link(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* group_dev, float min_sim, int min_samples,
+                     int row0, int nrows, const mme_density_state* state, void* stream);
+int mme_density_finish(mme_ctx* ctx, const mme_density_state* state, int N, int min_samples, int32_t* labels_dev, int32_t* kind_dev,
+                       int32_t* border_idx_dev, float* border_sim_dev, int64_t* summary_dev, void* stream);
+
 /* ---- K15: spherical k-means over the vector table -------------------------------
  * Partitions the rows of the L2-normalised bf16 table emb_dev[N, d] into k clusters by cosine to a unit centroid.
  *   assign   label[i] = argmax_j s_ij, s_ij the f32-accumulated cosine of row i and centroid j (K9's GEMM); sim[i] = that

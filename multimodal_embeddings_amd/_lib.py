@@ -181,6 +181,10 @@ class _DupState(C.Structure):  # mme_dup_state
     ]
 
 
+class _DensityState(C.Structure):  # mme_density_state
+    _fields_ = [(f, C.c_void_p) for f in ("count", "parent", "border", "counters")]
+
+
 class _KmeansState(C.Structure):  # mme_kmeans_state
     _fields_ = [(f, C.c_void_p) for f in ("centroids", "sums", "counts", "labels", "sim", "info", "objective")]
 
@@ -299,6 +303,12 @@ EXPORTS = {
                                       C.POINTER(_DupState), C.c_void_p]),
     "mme_duplicates_merge": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.POINTER(_DupState), C.c_int, C.c_void_p]),
     "mme_duplicates_finish": (C.c_int, [C.c_void_p, C.POINTER(_DupState), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mme_density_init": (C.c_int, [C.c_void_p, C.POINTER(_DensityState), C.c_int, C.c_void_p]),
+    "mme_density_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(_DensityState), C.c_void_p]),
+    "mme_density_link": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(_DensityState),
+                                   C.c_void_p]),
+    "mme_density_finish": (C.c_int, [C.c_void_p, C.POINTER(_DensityState), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "mme_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_KmeansState), C.c_void_p]),
     "mme_kmeans_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_KmeansApplyArgs), C.c_void_p]),
     "mme_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_SilhouetteOut), C.c_void_p]),
@@ -1647,7 +1657,7 @@ class Engine:
         st.edge_cap, st.P = int(state.get("edge_cap", 0)), int(state.get("pages", 0))
         return st
 
-    def _i32_rows(self, v, N, what):
+    def _i32_rows(self, v, N, what, who="duplicates"):
         """optional int32 [N] control vector (CUDA tensor or array) on this engine's device"""
         if v is None:
             return None
@@ -1655,7 +1665,7 @@ class Engine:
         g = v if isinstance(v, t.Tensor) else t.from_numpy(np.ascontiguousarray(v, dtype=np.int32))
         g = g.to(device=t.device(f"cuda:{self.device}"), dtype=t.int32).contiguous()
         if g.numel() != N:
-            raise MmeError(f"duplicates: {what} must have one id per row")
+            raise MmeError(f"{who}: {what} must have one id per row")
         return g
 
     def duplicates_init(self, N, pages=0, edge_cap=0):
@@ -1725,6 +1735,77 @@ class Engine:
         row0, nrows = (0, None) if rows is None else rows
         self.duplicates_scan(state, emb, group, page_of, min_sim=min_sim, row0=row0, nrows=nrows)
         return self.duplicates_finish(state)
+
+    # ---- K18 density clusters (mme.h, mme_density_*) ----
+    def _density_struct(self, state):
+        st = _DensityState()
+        for f in ("count", "parent", "border", "counters"):
+            setattr(st, f, self._ptr(state.get(f)))
+        return st
+
+    def density_init(self, N):
+        """A fresh state for N rows: a dict of CUDA tensors `count`, `parent` int32 [N], `border` int64 [N] (packed keys),
+        `counters` int64 [2] (neighbour pairs the count calls found, pairs the link calls saw); plus `N`."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        N = int(N)
+        state = {"N": N, "count": t.empty(max(N, 1), dtype=t.int32, device=dev), "parent": t.empty(max(N, 1), dtype=t.int32, device=dev),
+                 "border": t.empty(max(N, 1), dtype=t.int64, device=dev), "counters": t.empty(2, dtype=t.int64, device=dev)}
+        self._check(self.lib.mme_density_init(self.h, C.byref(self._density_struct(state)), N, self._stream()), "mme_density_init")
+        return state
+
+    def _density_table(self, state, emb_bf16, group):
+        t = self.torch
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != t.device(f"cuda:{self.device}"):
+            raise MmeError("density: emb must be a 2-D bfloat16 tensor on this engine's device")
+        if e.shape[0] != state["N"]:
+            raise MmeError(f"density: the state was made for {state['N']} rows, emb has {e.shape[0]}")
+        g = self._i32_rows(group, e.shape[0], "group", who="density")
+        return e, g
+
+    def density_count(self, state, emb_bf16, group=None, *, min_sim, row0=0, nrows=None):
+        """Counts the neighbour pairs (i, j), row0 <= i < row0 + nrows, i < j < N, into `state`.  Calls over disjoint row
+        ranges that cover [0, N) are one count, in any order."""
+        e, g = self._density_table(state, emb_bf16, group)
+        N, d = e.shape
+        nrows = N - row0 if nrows is None else int(nrows)
+        self._check(self.lib.mme_density_count(self.h, e.data_ptr(), N, d, self._ptr(g), float(min_sim), int(row0), nrows,
+                                               C.byref(self._density_struct(state)), self._stream()), "mme_density_count")
+
+    def density_link(self, state, emb_bf16, group=None, *, min_sim, min_samples, row0=0, nrows=None):
+        """Links the same pairs: unions of two core rows, border offers of one.  Call it only after the count calls have
+        covered every row (on the same stream), with the same emb, group and min_sim."""
+        e, g = self._density_table(state, emb_bf16, group)
+        N, d = e.shape
+        nrows = N - row0 if nrows is None else int(nrows)
+        self._check(self.lib.mme_density_link(self.h, e.data_ptr(), N, d, self._ptr(g), float(min_sim), int(min_samples), int(row0), nrows,
+                                              C.byref(self._density_struct(state)), self._stream()), "mme_density_link")
+
+    def density_finish(self, state, *, min_samples):
+        """The outputs by name, CUDA tensors: labels (the cluster's smallest core row, -1 for noise), kind (2 core, 1 border,
+        0 noise), count, border_idx int32 [N], border_sim float32 [N], summary int64 [6] (neighbour pairs, clusters, core,
+        border, noise rows, rows of the largest cluster) and counters int64 [2].  count and counters are the state's own."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        N = state["N"]
+        out = {"labels": t.empty(N, dtype=t.int32, device=dev), "kind": t.empty(N, dtype=t.int32, device=dev),
+               "border_idx": t.empty(N, dtype=t.int32, device=dev), "border_sim": t.empty(N, dtype=t.float32, device=dev),
+               "summary": t.empty(6, dtype=t.int64, device=dev)}
+        ptr = lambda k: self._ptr(out[k]) if N else None  # noqa: E731
+        self._check(self.lib.mme_density_finish(self.h, C.byref(self._density_struct(state)), N, int(min_samples), ptr("labels"), ptr("kind"),
+                                                ptr("border_idx"), ptr("border_sim"), out["summary"].data_ptr(), self._stream()), "mme_density_finish")
+        out["count"] = state["count"][:N]
+        out["counters"] = state["counters"]
+        return out
+
+    def density_clusters(self, emb, min_sim, min_samples, group=None):
+        """DBSCAN of the L2-normalised bf16 rows emb[N, d] in one call: init, count, link, finish, all enqueued on the current
+        stream.  See density_finish for what comes back."""
+        state = self.density_init(emb.shape[0])
+        self.density_count(state, emb, group, min_sim=min_sim)
+        self.density_link(state, emb, group, min_sim=min_sim, min_samples=min_samples)
+        return self.density_finish(state, min_samples=min_samples)
 
     # ---- K15 spherical k-means (mme.h, mme_kmeans*) ----
     def kmeans(self, emb_bf16, k, init_rows=None, centroids=None, max_iter=100):

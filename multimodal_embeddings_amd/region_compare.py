@@ -222,6 +222,144 @@ def create_duplicate_report(collection, threshold, output_path=None, **kwargs):
     return result
 
 
+# ---- K18: density clusters of regions (DBSCAN) -------------------------------------------------------------
+
+_KIND_NAMES = {2: "core", 1: "border", 0: "noise"}
+
+
+def density_table(labels, kind, count, border_idx, border_sim, ids, metadatas, *, threshold, min_samples, min_size=1, max_members=None):
+    """The JSON-ready report from K18's arrays; a pure function of its arguments (no GPU).
+
+    labels[i] = the cluster of row i (any id, K18 gives the cluster's smallest core row) or -1 for noise, kind[i] = 2 core,
+    1 border, 0 noise, count[i] = the row's neighbours, (border_idx, border_sim)[i] = a border row's best core neighbour;
+    ids / metadatas are the rows'.  Returns
+      {"threshold", "min_samples", "n_regions",
+       "clusters": [{"cluster", "size", "n_core", "n_border", "pages": [page names, sorted],
+                     "members": [{"id", "parent_image", "box", "kind": "core" | "border", "count",
+                                  "best_core": {"id", "score"} (border members only)}, ... in row order]},
+                    ... by size descending, then by first member (the lowest row), numbered 0..k-1 in that order],
+       "noise": {"count", "ids"},
+       "summary": {"n_clusters", "n_core", "n_border", "n_noise", "largest_cluster"}}
+    Clusters of fewer than `min_size` rows are left out of "clusters" (they are the tail of the order, so the numbers of the
+    others stay; the summary counts all); max_members keeps only the first members of each list (the counts stay whole)."""
+    labels, kind, count, border_idx = (np.asarray(v).astype(np.int64).reshape(-1) for v in (labels, kind, count, border_idx))
+    border_sim = np.asarray(border_sim, dtype=np.float64).reshape(-1)
+    n = len(ids)
+    if not (len(labels) == len(kind) == len(count) == len(border_idx) == len(border_sim) == len(metadatas) == n):
+        raise ValueError("density_table: labels, kind, count, border_idx, border_sim, ids and metadatas must have one entry per row")
+    if n and not np.isin(kind, (0, 1, 2)).all():
+        raise ValueError("density_table: kind must be 0 (noise), 1 (border) or 2 (core)")
+    if n and ((labels < 0) != (kind == 0)).any():
+        raise ValueError("density_table: exactly the noise rows (kind 0) must have the label -1")
+    members = {}
+    for r in range(n):
+        if kind[r] != 0:
+            members.setdefault(int(labels[r]), []).append(r)
+    order = sorted(members.values(), key=lambda rows: (-len(rows), rows[0]))
+    clusters = []
+    for number, rows in enumerate(order):
+        if len(rows) < max(1, int(min_size)):
+            continue
+        out_rows = []
+        for r in rows:
+            m = metadatas[r] or {}
+            row = {"id": ids[r], "parent_image": os.path.basename(_parent_of(m)), "box": _box_of(m), "kind": _KIND_NAMES[int(kind[r])],
+                   "count": int(count[r])}
+            if kind[r] == 1:
+                row["best_core"] = {"id": ids[int(border_idx[r])], "score": float(border_sim[r])}
+            out_rows.append(row)
+        n_core = int(sum(1 for r in rows if kind[r] == 2))
+        clusters.append({"cluster": number, "size": len(rows), "n_core": n_core, "n_border": len(rows) - n_core,
+                         "pages": sorted({m["parent_image"] for m in out_rows if m["parent_image"]}),
+                         "members": out_rows if max_members is None else out_rows[: int(max_members)]})
+    noise = [ids[r] for r in range(n) if kind[r] == 0]
+    return {"threshold": None if threshold is None else float(threshold), "min_samples": int(min_samples), "n_regions": n, "clusters": clusters,
+            "noise": {"count": len(noise), "ids": noise},
+            "summary": {"n_clusters": len(order), "n_core": int((kind == 2).sum()), "n_border": int((kind == 1).sum()), "n_noise": len(noise),
+                        "largest_cluster": len(order[0]) if order else 0}}
+
+
+def density_clusters(collection, threshold, min_samples, *, exclude="none", prefix_length=config.PREFIX_LENGTH,
+                     where={"is_region": {"$eq": True}}, min_size=1, engine: Engine | None = None):
+    """Density clusters (DBSCAN, kernel K18) of the regions `where` selects, rows without an embedding left out: a region is
+    core when at least `min_samples` regions, itself included, have a cosine >= `threshold` with it; clusters are the
+    connected components of the core regions, a non-core region next to a core one is a border member of its most similar
+    core neighbour's cluster, every other region is noise.  Returns density_table's dict.
+
+    `threshold` and `min_samples` have no defaults: the right values belong to the encoder and the archive
+    (kth_neighbour_similarity gives the curve to read a threshold from).  exclude: duplicate_inputs' rules for the pairs that
+    never count; the default "none" counts every pair -- a page with twelve look-alike columns is density too."""
+    if int(min_samples) < 1:
+        raise ValueError(f"density_clusters: min_samples = {min_samples}; supported: at least 1")
+    all_entries, have = _region_rows(collection, where)
+    if not have:
+        logger.warning("No regions found in the database. Make sure regions have been processed first.")
+        return density_table([], [], [], [], [], [], [], threshold=threshold, min_samples=min_samples, min_size=min_size)
+    ids = [all_entries["ids"][r] for r in have]
+    metas = [all_entries["metadatas"][r] for r in have]
+    engine = engine or default_engine()
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
+    group, _, _ = duplicate_inputs(metas, exclude, prefix_length)
+    res = engine.density_clusters(emb, float(threshold), int(min_samples), group)
+    host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in res.items()}
+    return density_table(host["labels"], host["kind"], host["count"], host["border_idx"], host["border_sim"], ids, metas, threshold=threshold,
+                         min_samples=min_samples, min_size=min_size)
+
+
+def create_density_report(collection, threshold, min_samples, output_path=None, **kwargs):
+    """density_clusters, written as one JSON document when `output_path` is given (as create_duplicate_report)."""
+    result = density_clusters(collection, threshold, min_samples, **kwargs)
+    if output_path:
+        os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+        with open(output_path, "w") as fh:
+            json.dump(result, fh, indent=1)
+    return result
+
+
+K12_LIST_LIMIT = 128  # mme_neighbours: fetch and top_n lie in 1..128
+
+
+def kth_neighbour_similarity(collection, k, *, exclude="none", where={"is_region": {"$eq": True}}, engine: Engine | None = None):
+    """The cosine of every region's k-th most similar admissible region, as a float32 array sorted descending: the curve whose
+    knee is the usual way to choose density_clusters' threshold for min_samples = k + 1.  One pass of K12 (Engine.neighbours)
+    over the rows `where` selects, rows without an embedding left out; exclude: duplicate_inputs' rules.  A row with fewer than
+    k admissible rows has no such value and is left out.
+
+    K12's lists hold at most `fetch` = 128 rows, the row itself and the rows `exclude` drops among them.  ValueError names the
+    limit when k does not fit (k <= 127 under "none", k <= 128 otherwise), or when a row's 128 nearest rows hold fewer than k
+    admissible ones although the table has them."""
+    k = int(k)
+    if exclude not in ("parent", "prefix", "none"):
+        raise ValueError("exclude must be 'parent', 'prefix' or 'none'")
+    most = K12_LIST_LIMIT - 1 if exclude == "none" else K12_LIST_LIMIT
+    if k < 1 or k > most:
+        raise ValueError(f"kth_neighbour_similarity: k = {k}; supported 1..{most} under exclude = {exclude!r} (K12's lists hold fetch <= "
+                         f"{K12_LIST_LIMIT} rows, the row itself among them, and top_n <= {K12_LIST_LIMIT})")
+    all_entries, have = _region_rows(collection, where)
+    if not have:
+        return np.empty(0, dtype=np.float32)
+    metas = [all_entries["metadatas"][r] for r in have]
+    n = len(have)
+    engine = engine or default_engine()
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
+    group, _, _ = duplicate_inputs(metas, exclude)
+    fetch = min(k + 1, K12_LIST_LIMIT) if group is None else K12_LIST_LIMIT
+    idx, sim = engine.neighbours(emb, group, fetch=fetch, top_n=k)
+    idx = idx.cpu().numpy() if hasattr(idx, "cpu") else np.asarray(idx)
+    sim = sim.cpu().numpy() if hasattr(sim, "cpu") else np.asarray(sim)
+    found = idx[:, k - 1] >= 0
+    if group is None:
+        admissible = np.full(n, n - 1)
+    else:
+        _, inverse, size = np.unique(group, return_inverse=True, return_counts=True)
+        admissible = n - size[inverse]
+    short = ~found & (admissible >= k)
+    if short.any():
+        raise ValueError(f"kth_neighbour_similarity: {int(short.sum())} rows have fewer than k = {k} admissible rows among their fetch = "
+                         f"{K12_LIST_LIMIT} nearest (K12's limit on the list length) under exclude = {exclude!r}")
+    return np.sort(sim[found, k - 1].astype(np.float32))[::-1].copy()
+
+
 # ---- K15: k groups of look-alike regions (spherical k-means; DESIGN.md 4.22) ---------------------------------------------
 
 def cluster_table(labels, sim, ids, metadatas, *, n_clusters=None, iterations=None, converged=None, objective=None, max_members=None):
