@@ -1049,6 +1049,69 @@ int mme_density_link(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const 
 int mme_density_finish(mme_ctx* ctx, const mme_density_state* state, int N, int min_samples, int32_t* labels_dev, int32_t* kind_dev,
                        int32_t* border_idx_dev, float* border_sim_dev, int64_t* summary_dev, void* stream);
 
+/* ---- K19: cluster hierarchy of regions, the mutual-reachability spanning tree ----
+ * K18 above answers one threshold per run of two passes.  This computes, once, the spanning forest from whose N - 1 edges
+ * the host derives the DBSCAN* clusters at EVERY threshold, HDBSCAN's threshold-free clusters and a dendrogram
+ * (region_compare.cut_hierarchy / hierarchy_clusters / linkage_of), with no further GPU work.
+ *
+ * Input: K14's table, emb_dev bf16 [N, d], unit rows, d % 64 == 0; group_dev int32[N] or NULL with K14's meaning (a pair is
+ * ADMISSIBLE when i != j and the groups differ); min_samples >= 1.
+ * s(i, j) is the f32 the cosine GEMM writes for row i against row j; against the float64 dot product delta = 2 * d * 2^-24
+ * as K14.  s(i, j) and s(j, i) are the same bits.
+ * CORE SIMILARITY  core[i] = the (min_samples - 1)-th largest s(i, j) over the admissible j (the row itself counts towards
+ *   min_samples, as in K18 and scikit-learn); +1.5 at min_samples = 1 (above every cosine); -2.0 when the row has fewer than
+ *   min_samples - 1 admissible partners (below every cosine, finite).  The selection is exact for every min_samples.
+ * WEIGHT  m(i, j) = min(core[i], core[j], s(i, j)) for an admissible pair.
+ * THE TREE  the spanning forest of the admissible graph that is maximal under the strict total order on edges: m descending,
+ *   then lo = min(i, j) ascending, then hi = max(i, j) ascending.  The order is strict, so the edge set is unique: it equals
+ *   Kruskal's over the same f32 weights and is bit-identical from run to run.  (Mutual reachability ties in bulk -- every edge
+ *   from a row to one of its closer neighbours weighs core[i] -- so the order is the centre of the definition.)
+ *
+ * The state is caller-owned device memory:
+ *   core         float[N4]   N4 = N rounded up to 4, 16-byte aligned: an OUTPUT after the core calls
+ *   comp         int32[N4]   16-byte aligned: the smallest row of the row's component
+ *   row_key      uint64[N]   a row's best outgoing edge of the current round as a packed key
+ *   parent       int32[N]    union-find forest, parent[i] <= i
+ *   comp_weight  uint32[N]   per component scratch
+ *   comp_edge    uint64[N]   per component scratch
+ *   edges        int32[N - 1, 2]  (lo, hi), and weights float[N - 1]: the first counters[0] entries are valid; the order in
+ *                which one round's edges land is not specified (the SET is; sort by the order above for one order)
+ *   counters     uint64[3]   edges emitted, rounds run, components left
+ * mme_hierarchy_init   one-row components, no edge, counters = {0, 0, N}.
+ * mme_hierarchy_core   core[i] for row0 <= i < row0 + nrows; calls over row ranges that cover [0, N) fill core, in any order.
+ * mme_hierarchy_scan   one round's scan of the rows row0 <= i < row0 + nrows against every row: row_key[i] = the best edge
+ *                      from i to another component.  Calls over disjoint row ranges that cover [0, N) are one round's scan,
+ *                      in any order, as mme_density_count.
+ * mme_hierarchy_merge  ends the round: every component's maximal edge is emitted (once, when both ends chose it), the
+ *                      components are united, comp is renewed, the keys cleared, counters updated.
+ * THE CALLER ORDERS the core calls of the whole table BEFORE THE FIRST SCAN, and EVERY SCAN OF A ROUND BEFORE ITS MERGE, and
+ * the merge before the next round's scans (stream order on one stream suffices): a scan on core values or components that are
+ * not final chooses wrong edges, and nothing detects it.  emb_dev and group_dev must be the same in every call.  The
+ * number of rounds depends on the data: repeat { scans; merge } until a round emits no edge (counters[0] stays) or
+ * counters[0] == N - 1; at most ceil(log2 N) rounds emit edges.  Reading counters[0] back is the caller's one wait per round.
+ * All calls enqueue on `stream` and never wait for the device (the cosine blocks go through the K12 workspace, which grows
+ * on first use).  No merge of states across GPUs: a sharded form needs row_key merged by maximum per round.
+ * MME_E_ARG, with the entry point, the field and the value in mme_last_error, nothing enqueued, state and context usable: a
+ * null pointer, core or comp not 16-byte aligned, d % 64 != 0, min_samples < 1, rows outside [0, N].
+ * Profiling classes: the GEMM counts as "cosine", hier_core and hier_scan as "neighbours", merge as "cluster". */
+typedef struct mme_hierarchy_state {
+    float* core;
+    int32_t* comp;
+    uint64_t* row_key;
+    int32_t* parent;
+    uint32_t* comp_weight;
+    uint64_t* comp_edge;
+    int32_t* edges;
+    float* weights;
+    uint64_t* counters;
+} mme_hierarchy_state;
+int mme_hierarchy_init(mme_ctx* ctx, const mme_hierarchy_state* state, int N, void* stream);
+int mme_hierarchy_core(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* group_dev, int min_samples, int row0, int nrows,
+                       const mme_hierarchy_state* state, void* stream);
+int mme_hierarchy_scan(mme_ctx* ctx, const uint16_t* emb_dev, int N, int d, const int32_t* group_dev, int row0, int nrows,
+                       const mme_hierarchy_state* state, void* stream);
+int mme_hierarchy_merge(mme_ctx* ctx, const mme_hierarchy_state* state, int N, void* stream);
+
 /* ---- K15: spherical k-means over the vector table -------------------------------
  * Partitions the rows of the L2-normalised bf16 table emb_dev[N, d] into k clusters by cosine to a unit centroid.
  *   assign   label[i] = argmax_j s_ij, s_ij the f32-accumulated cosine of row i and centroid j (K9's GEMM); sim[i] = that

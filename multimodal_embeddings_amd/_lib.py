@@ -185,6 +185,13 @@ class _DensityState(C.Structure):  # mme_density_state
     _fields_ = [(f, C.c_void_p) for f in ("count", "parent", "border", "counters")]
 
 
+_HIERARCHY_FIELDS = ("core", "comp", "row_key", "parent", "comp_weight", "comp_edge", "edges", "weights", "counters")
+
+
+class _HierarchyState(C.Structure):  # mme_hierarchy_state
+    _fields_ = [(f, C.c_void_p) for f in _HIERARCHY_FIELDS]
+
+
 class _KmeansState(C.Structure):  # mme_kmeans_state
     _fields_ = [(f, C.c_void_p) for f in ("centroids", "sums", "counts", "labels", "sim", "info", "objective")]
 
@@ -309,6 +316,10 @@ EXPORTS = {
                                    C.c_void_p]),
     "mme_density_finish": (C.c_int, [C.c_void_p, C.POINTER(_DensityState), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "mme_hierarchy_init": (C.c_int, [C.c_void_p, C.POINTER(_HierarchyState), C.c_int, C.c_void_p]),
+    "mme_hierarchy_core": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(_HierarchyState), C.c_void_p]),
+    "mme_hierarchy_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_HierarchyState), C.c_void_p]),
+    "mme_hierarchy_merge": (C.c_int, [C.c_void_p, C.POINTER(_HierarchyState), C.c_int, C.c_void_p]),
     "mme_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_KmeansState), C.c_void_p]),
     "mme_kmeans_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_KmeansApplyArgs), C.c_void_p]),
     "mme_silhouette": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(_SilhouetteOut), C.c_void_p]),
@@ -1806,6 +1817,101 @@ class Engine:
         self.density_count(state, emb, group, min_sim=min_sim)
         self.density_link(state, emb, group, min_sim=min_sim, min_samples=min_samples)
         return self.density_finish(state, min_samples=min_samples)
+
+    # ---- K19 cluster hierarchy (mme.h, mme_hierarchy_*) ----
+    def _hierarchy_struct(self, state):
+        st = _HierarchyState()
+        for f in _HIERARCHY_FIELDS:
+            setattr(st, f, self._ptr(state.get(f)))
+        return st
+
+    def hierarchy_init(self, N):
+        """A fresh state for N rows: a dict of CUDA tensors `core` float32 and `comp` int32 [N rounded up to 4], `row_key`,
+        `comp_edge` int64 [N] (packed keys), `parent`, `comp_weight` int32 [N], `edges` int32 [N - 1, 2], `weights` float32
+        [N - 1], `counters` int64 [3] (edges emitted, rounds run, components left); plus `N`."""
+        t = self.torch
+        dev = t.device(f"cuda:{self.device}")
+        N = int(N)
+        n1, n4 = max(N, 1), max((N + 3) & ~3, 4)
+        state = {"N": N, "core": t.empty(n4, dtype=t.float32, device=dev), "comp": t.empty(n4, dtype=t.int32, device=dev),
+                 "row_key": t.empty(n1, dtype=t.int64, device=dev), "parent": t.empty(n1, dtype=t.int32, device=dev),
+                 "comp_weight": t.empty(n1, dtype=t.int32, device=dev), "comp_edge": t.empty(n1, dtype=t.int64, device=dev),
+                 "edges": t.zeros((max(N - 1, 1), 2), dtype=t.int32, device=dev), "weights": t.zeros(max(N - 1, 1), dtype=t.float32, device=dev),
+                 "counters": t.empty(3, dtype=t.int64, device=dev)}
+        self._check(self.lib.mme_hierarchy_init(self.h, C.byref(self._hierarchy_struct(state)), N, self._stream()), "mme_hierarchy_init")
+        return state
+
+    def _hierarchy_table(self, state, emb_bf16, group):
+        t = self.torch
+        e = emb_bf16.contiguous()
+        if e.dtype != t.bfloat16 or e.dim() != 2 or e.device != t.device(f"cuda:{self.device}"):
+            raise MmeError("hierarchy: emb must be a 2-D bfloat16 tensor on this engine's device")
+        if e.shape[0] != state["N"]:
+            raise MmeError(f"hierarchy: the state was made for {state['N']} rows, emb has {e.shape[0]}")
+        return e, self._i32_rows(group, e.shape[0], "group", who="hierarchy")
+
+    def hierarchy_core(self, state, emb_bf16, group=None, *, min_samples, row0=0, nrows=None):
+        """core[i], row0 <= i < row0 + nrows: the (min_samples - 1)-th largest admissible cosine of the row.  Calls over row
+        ranges that cover [0, N) fill `core`, in any order; all of them come before the first hierarchy_scan."""
+        e, g = self._hierarchy_table(state, emb_bf16, group)
+        N, d = e.shape
+        nrows = N - row0 if nrows is None else int(nrows)
+        self._check(self.lib.mme_hierarchy_core(self.h, e.data_ptr(), N, d, self._ptr(g), int(min_samples), int(row0), nrows,
+                                                C.byref(self._hierarchy_struct(state)), self._stream()), "mme_hierarchy_core")
+
+    def hierarchy_scan(self, state, emb_bf16, group=None, *, row0=0, nrows=None):
+        """One round's scan of the rows row0 <= i < row0 + nrows against every row.  Calls over disjoint row ranges that cover
+        [0, N) are one round's scan, in any order; then hierarchy_merge ends the round."""
+        e, g = self._hierarchy_table(state, emb_bf16, group)
+        N, d = e.shape
+        nrows = N - row0 if nrows is None else int(nrows)
+        self._check(self.lib.mme_hierarchy_scan(self.h, e.data_ptr(), N, d, self._ptr(g), int(row0), nrows,
+                                                C.byref(self._hierarchy_struct(state)), self._stream()), "mme_hierarchy_scan")
+
+    def hierarchy_merge(self, state):
+        """Ends a round: emits every component's maximal edge, unites, renews `comp`, updates `counters`.  Enqueues only."""
+        self._check(self.lib.mme_hierarchy_merge(self.h, C.byref(self._hierarchy_struct(state)), state["N"], self._stream()), "mme_hierarchy_merge")
+
+    def hierarchy_rounds(self, state, scan):
+        """The round loop: `scan()` enqueues one round's scans, then the merge; repeated until the forest is whole or a round
+        emits no edge.  The number of rounds depends on the data, so the edge counter (8 bytes) is read back once per round:
+        the one synchronisation per round.  -> (edges emitted, rounds run)."""
+        N = state["N"]
+        edges, rounds = 0, 0
+        while edges < N - 1 and rounds <= max(N - 1, 1).bit_length():  # at most ceil(log2 N) rounds emit edges
+            scan()
+            self.hierarchy_merge(state)
+            rounds += 1
+            now = int(state["counters"][0].item())
+            if now == edges:
+                break
+            edges = now
+        return edges, rounds
+
+    def hierarchy_sorted(self, state, n_edges):
+        """(edges int32 [E, 2], weights float32 [E]) of the state, as copies sorted by the order of the tree: weight descending
+        (on the order-preserving image of the f32), then lo, then hi ascending."""
+        t = self.torch
+        e, w = state["edges"][:n_edges], state["weights"][:n_edges]
+        if n_edges == 0:
+            return e.clone(), w.clone()
+        pair = (e[:, 0].to(t.int64) << 32) | e[:, 1].to(t.int64)
+        order = t.sort(pair, stable=True)[1]
+        u = w.view(t.int32).to(t.int64) & 0xFFFFFFFF
+        image = t.where((u & 0x80000000) != 0, ~u & 0xFFFFFFFF, u | 0x80000000)
+        order = order[t.sort(image[order], descending=True, stable=True)[1]]
+        return e[order].contiguous(), w[order].contiguous()
+
+    def hierarchy(self, emb, min_samples, group=None):
+        """The mutual-reachability spanning forest of the L2-normalised bf16 rows emb[N, d] in one call: init, core, then rounds
+        of scan and merge on the current stream (hierarchy_rounds: one 8-byte read-back per round).  -> dict of CUDA tensors
+        `edges` int32 [E, 2] (lo, hi) and `weights` float32 [E], sorted by weight descending, then lo, then hi; `core` float32
+        [N]; and the ints `rounds` and `components` (E = N - components)."""
+        state = self.hierarchy_init(emb.shape[0])
+        self.hierarchy_core(state, emb, group, min_samples=min_samples)
+        n_edges, rounds = self.hierarchy_rounds(state, lambda: self.hierarchy_scan(state, emb, group))
+        edges, weights = self.hierarchy_sorted(state, n_edges)
+        return {"edges": edges, "weights": weights, "core": state["core"][:state["N"]], "rounds": rounds, "components": state["N"] - n_edges}
 
     # ---- K15 spherical k-means (mme.h, mme_kmeans*) ----
     def kmeans(self, emb_bf16, k, init_rows=None, centroids=None, max_iter=100):

@@ -316,6 +316,315 @@ def create_density_report(collection, threshold, min_samples, output_path=None, 
     return result
 
 
+# ---- K19: the cluster hierarchy of regions (mutual-reachability spanning tree) -----------------------------
+# Everything below is a pure function of the tree's edge list: no GPU, no further pass over the table.
+
+
+def _tree_arrays(edges, weights, n=None):
+    """(edges int64 [E, 2] as (lo, hi), weights float64 [E], n) sorted by the order of the tree: weight descending, then lo,
+    then hi ascending"""
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if len(e) != len(w):
+        raise ValueError("hierarchy: edges and weights must have one entry per edge")
+    e = np.stack([e.min(1), e.max(1)], axis=1) if len(e) else e
+    n = (int(e.max()) + 1 if len(e) else 0) if n is None else int(n)
+    if len(e) and (e.min() < 0 or e.max() >= n or (e[:, 0] == e[:, 1]).any()):
+        raise ValueError(f"hierarchy: edges must join two different rows of 0..{n - 1}")
+    order = np.lexsort((e[:, 1], e[:, 0], -w))
+    return e[order], w[order], n
+
+
+def _find(top, x):
+    r = x
+    while top[r] != r:
+        r = top[r]
+    while top[x] != r:
+        top[x], x = r, top[x]
+    return r
+
+
+def cut_hierarchy(edges, weights, core, threshold):
+    """The DBSCAN* clusters at `threshold` from the tree of Engine.hierarchy: (labels, kind), int32 [N].  The rows with core[i]
+    >= threshold are core (kind 2); the clusters are the components of the edges with weight >= threshold, which join core rows
+    only; a cluster's id is its smallest member; every other row is noise (label -1, kind 0).  These are K18's core rows and
+    K18's clusters on them at min_sim = threshold, with K18's border rows as noise."""
+    core = np.asarray(core, dtype=np.float64).reshape(-1)
+    n = len(core)
+    e, w, _ = _tree_arrays(edges, weights, n)
+    is_core = core >= threshold
+    top = list(range(n))
+    for (a, b), keep in zip(e.tolist(), (w >= threshold).tolist()):
+        if not keep:
+            break  # sorted by weight descending
+        ra, rb = _find(top, a), _find(top, b)
+        if ra != rb:
+            top[max(ra, rb)] = min(ra, rb)  # the root is the smallest member
+    labels = np.fromiter((_find(top, r) for r in range(n)), dtype=np.int32, count=n)
+    labels = np.where(is_core, labels, -1).astype(np.int32)
+    return labels, np.where(is_core, 2, 0).astype(np.int32)
+
+
+def _single_linkage(e, w, n):
+    """The dendrogram of the sorted tree: (left, right, dist, size), one entry per merge, node ids as scipy's (rows 0..n-1, merge
+    t is node n + t).  Distance = max(0, 1 - weight); equal weights merge in the order of the tree.  The components of a forest
+    are joined at distance +inf, in the order of their smallest members."""
+    top = list(range(2 * n - 1))
+    size = [1] * n + [0] * (n - 1)
+    left, right, dist = [], [], []
+    pairs = e.tolist()
+    ds = np.maximum(0.0, 1.0 - w).tolist()
+    if len(pairs) > n - 1:
+        raise ValueError("hierarchy: the edges close a cycle")
+
+    def merge(a, b, dt):
+        node = n + len(left)
+        top[a] = top[b] = node
+        size[node] = size[a] + size[b]
+        left.append(a)
+        right.append(b)
+        dist.append(dt)
+        return node
+
+    for (x, y), dt in zip(pairs, ds):
+        a, b = _find(top, x), _find(top, y)
+        if a == b:
+            raise ValueError("hierarchy: the edges close a cycle")
+        merge(a, b, dt)
+    if len(pairs) < n - 1:
+        roots, seen = [], set()  # in the order of their smallest members
+        for r in range(n):
+            f = _find(top, r)
+            if f not in seen:
+                seen.add(f)
+                roots.append(f)
+        joined = roots[0]
+        for f in roots[1:]:
+            joined = merge(joined, f, float("inf"))
+    return left, right, dist, size
+
+
+def linkage_of(edges, weights):
+    """The tree as a scipy linkage matrix, float64 [N - 1, 4] (node, node, distance = max(0, 1 - weight), rows below), for
+    scipy.cluster.hierarchy.dendrogram / fcluster: what the reference draws for pages (weighted_region_clustering.py:297-339),
+    for regions.  Needs a spanning tree (N - 1 edges); with min_samples = 1 it is the single-linkage dendrogram of the
+    cosine distance."""
+    e, w, n = _tree_arrays(edges, weights, None)
+    n = max(n, len(e) + 1)
+    if len(e) != n - 1:
+        raise ValueError(f"linkage_of: {len(e)} edges over {n} rows are a forest, not a tree")
+    left, right, dist, size = _single_linkage(e, w, n)
+    z = np.empty((n - 1, 4), dtype=np.float64)
+    z[:, 0], z[:, 1] = np.minimum(left, right), np.maximum(left, right)
+    z[:, 2], z[:, 3] = dist, size[n:]
+    return z
+
+
+def hierarchy_clusters(edges, weights, core, min_cluster_size, *, allow_single_cluster=False):
+    """HDBSCAN's threshold-free clusters from the tree of Engine.hierarchy: the condensed tree and the excess-of-mass selection
+    as scikit-learn's HDBSCAN does them (cluster_selection_method="eom", no epsilon), with distance = max(0, 1 - weight) and
+    lambda = 1 / distance.  Equal-weight merges are processed in the order of the tree (weight descending, lo, hi).  Returns
+      {"labels": int32 [N], a cluster's id is its smallest member, -1 for noise,
+       "persistence": {cluster id: the cluster's stability, sum over its rows of (lambda_row - lambda_birth)},
+       "strength": float64 [N], lambda_row / lambda_max of the row's cluster (1 for a row that never leaves it, 0 for noise)}.
+    `core` gives the number of rows (rows without an edge are noise)."""
+    n = len(np.asarray(core).reshape(-1))
+    mcs = int(min_cluster_size)
+    if mcs < 2:
+        raise ValueError(f"hierarchy_clusters: min_cluster_size = {min_cluster_size}; supported: at least 2")
+    labels = np.full(n, -1, dtype=np.int32)
+    strength = np.zeros(n, dtype=np.float64)
+    if n < 2:
+        return {"labels": labels, "persistence": {}, "strength": strength}
+    e, w, _ = _tree_arrays(edges, weights, n)
+    left, right, dist, size = _single_linkage(e, w, n)
+
+    def rows_below(node):
+        out, stack = [], [node]
+        while stack:
+            x = stack.pop()
+            if x < n:
+                out.append(x)
+            else:
+                stack.append(right[x - n])
+                stack.append(left[x - n])
+        return out
+
+    # the condensed tree, breadth first, so that a cluster's number is above its parent's: cluster 0 is the root
+    c_parent, c_birth = [-1], [0.0]
+    own = [[]]       # (row, lambda) of the rows that leave the cluster itself
+    children = [[]]  # the two clusters it splits into
+    queue = [(2 * n - 2, 0)]
+    for node, c in queue:  # grows while it is walked
+        while True:
+            l, r, d = left[node - n], right[node - n], dist[node - n]
+            lam = 1.0 / d if d > 0.0 else float("inf")
+            big_l, big_r = size[l] >= mcs, size[r] >= mcs
+            if big_l and big_r:
+                for side in (l, r):
+                    c_parent.append(c)
+                    c_birth.append(lam)
+                    own.append([])
+                    children.append([])
+                    children[c].append(len(c_parent) - 1)
+                    queue.append((side, len(c_parent) - 1))
+                break
+            for side, big in ((l, big_l), (r, big_r)):
+                if not big:
+                    own[c].extend((x, lam) for x in rows_below(side))
+            if not big_l and not big_r:
+                break
+            node = l if big_l else r  # the cluster goes on in its big side
+    k = len(c_parent)
+    c_size = [0] * k
+    for c in range(k - 1, -1, -1):
+        c_size[c] += len(own[c])
+        if c:
+            c_size[c_parent[c]] += c_size[c]
+
+    def excess(lam, birth):
+        return 0.0 if lam == birth else lam - birth  # inf - inf: rows that leave at the distance they joined at
+
+    stability = [sum(excess(lam, c_birth[c]) for _, lam in own[c]) + sum(excess(c_birth[ch], c_birth[c]) * c_size[ch] for ch in children[c])
+                 for c in range(k)]
+    selected = [True] * k
+    if not allow_single_cluster:
+        selected[0] = False
+    for c in range(k - 1, -1 if allow_single_cluster else 0, -1):
+        below = sum(stability[ch] for ch in children[c])
+        if below > stability[c]:
+            selected[c] = False
+            stability[c] = below
+        else:
+            stack = list(children[c])
+            while stack:
+                x = stack.pop()
+                selected[x] = False
+                stack.extend(children[x])
+    chosen = [c for c in range(k) if selected[c]]
+    owner = [-1] * k  # the selected cluster a cluster's rows belong to
+    for c in range(k):
+        owner[c] = c if selected[c] else (owner[c_parent[c]] if c else -1)
+    only_root = chosen == [0]
+    # the largest lambda at which a row or a sub-cluster leaves the cluster itself (scikit-learn's lambda_max: a row of a
+    # sub-cluster that was not selected has strength 1)
+    deaths = [max([lam for _, lam in own[c]] + [c_birth[ch] for ch in children[c]] + [0.0]) for c in range(k)]
+    root_threshold = deaths[0]
+    members = {}
+    for c in range(k):
+        o = owner[c]
+        if o < 0:
+            continue
+        for x, lam in own[c]:
+            if only_root and lam < root_threshold:
+                continue  # scikit-learn: with the root alone selected, a row belongs to it only from the root's last split on
+            members.setdefault(o, []).append((x, lam))
+    persistence = {}
+    for o, rows in members.items():
+        ident = min(x for x, _ in rows)
+        persistence[int(ident)] = float(stability[o])
+        top = deaths[o]
+        for x, lam in rows:
+            labels[x] = ident
+            strength[x] = 1.0 if top == 0.0 or lam == float("inf") else min(lam, top) / top
+    return {"labels": labels, "persistence": persistence, "strength": strength}
+
+
+@dataclasses.dataclass
+class RegionHierarchy:
+    """The cluster hierarchy of a set of regions (region_hierarchy): the tree's edge list and the rows' ids.  edges int32
+    [E, 2] (lo, hi) and weights float32 [E] sorted by weight descending, then lo, then hi; core float32 [N]."""
+    edges: np.ndarray
+    weights: np.ndarray
+    core: np.ndarray
+    min_samples: int
+    ids: list
+    metadatas: list | None = None
+    rounds: int = 0
+    components: int = 1
+
+    def cut(self, threshold, *, min_size=1, max_members=None):
+        """The DBSCAN* clusters at `threshold` as density_table's dict (cut_hierarchy: K18's core rows and clusters at that
+        threshold, its border rows among the noise; a member has no "count", which the tree does not hold)."""
+        labels, kind = cut_hierarchy(self.edges, self.weights, self.core, threshold)
+        n = len(self.ids)
+        metas = self.metadatas if self.metadatas is not None else [None] * n
+        table = density_table(labels, kind, np.zeros(n, dtype=np.int64), np.full(n, -1), np.zeros(n), self.ids, metas, threshold=threshold,
+                              min_samples=self.min_samples, min_size=min_size, max_members=max_members)
+        for c in table["clusters"]:
+            for m in c["members"]:
+                del m["count"]
+        return table
+
+    def clusters(self, min_cluster_size, *, allow_single_cluster=False):
+        """hierarchy_clusters over the tree, by id: {"min_cluster_size", "n_regions", "clusters": [{"cluster", "size",
+        "persistence", "members": [{"id", "strength"}, ... in row order]}, ... by size descending, then first member], "noise":
+        {"count", "ids"}, "labels": int32 [N] (a cluster's smallest row, -1 noise)}."""
+        res = hierarchy_clusters(self.edges, self.weights, self.core, min_cluster_size, allow_single_cluster=allow_single_cluster)
+        members = {}
+        for r, lab in enumerate(res["labels"].tolist()):
+            if lab >= 0:
+                members.setdefault(lab, []).append(r)
+        out = []
+        for number, (lab, rows) in enumerate(sorted(members.items(), key=lambda kv: (-len(kv[1]), kv[0]))):
+            out.append({"cluster": number, "size": len(rows), "persistence": res["persistence"][lab],
+                        "members": [{"id": self.ids[r], "strength": float(res["strength"][r])} for r in rows]})
+        noise = [self.ids[r] for r in np.flatnonzero(res["labels"] < 0).tolist()]
+        return {"min_cluster_size": int(min_cluster_size), "n_regions": len(self.ids), "clusters": out,
+                "noise": {"count": len(noise), "ids": noise}, "labels": res["labels"]}
+
+    def linkage(self):
+        """linkage_of over the tree: the scipy linkage matrix of the regions' dendrogram (label its leaves with `ids`)."""
+        return linkage_of(self.edges, self.weights)
+
+
+def region_hierarchy(collection, min_samples, *, exclude="none", prefix_length=config.PREFIX_LENGTH, where={"is_region": {"$eq": True}},
+                     engine: Engine | None = None):
+    """The cluster hierarchy (kernel K19, Engine.hierarchy) of the regions `where` selects, rows without an embedding left out:
+    the spanning tree of the mutual-reachability graph, computed once on the GPU.  -> RegionHierarchy, whose .cut(threshold)
+    gives the DBSCAN* clusters at ANY threshold, .clusters(min_cluster_size) HDBSCAN's threshold-free ones and .linkage() the
+    dendrogram, all on the host.
+
+    `min_samples` has no default: the right value belongs to the archive.  exclude: duplicate_inputs' rules for the pairs that
+    never count, as density_clusters."""
+    if int(min_samples) < 1:
+        raise ValueError(f"region_hierarchy: min_samples = {min_samples}; supported: at least 1")
+    all_entries, have = _region_rows(collection, where)
+    if not have:
+        logger.warning("No regions found in the database. Make sure regions have been processed first.")
+        return RegionHierarchy(np.zeros((0, 2), dtype=np.int32), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.float32), int(min_samples), [], [],
+                               0, 0)
+    ids = [all_entries["ids"][r] for r in have]
+    metas = [all_entries["metadatas"][r] for r in have]
+    engine = engine or default_engine()
+    emb = to_unit_bf16([all_entries["embeddings"][r] for r in have], engine)
+    group, _, _ = duplicate_inputs(metas, exclude, prefix_length)
+    res = engine.hierarchy(emb, int(min_samples), group)
+    host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in res.items()}
+    return RegionHierarchy(host["edges"].astype(np.int32), host["weights"].astype(np.float32), host["core"].astype(np.float32), int(min_samples), ids,
+                           metas, int(res["rounds"]), int(res["components"]))
+
+
+def create_hierarchy_report(collection, min_samples, output_path=None, *, thresholds=(), min_cluster_size=None, **kwargs):
+    """region_hierarchy, written as one JSON document when `output_path` is given (as create_density_report): the tree by id
+    ({"a", "b", "weight"} per edge, in the tree's order), every row's core similarity, the cut at each of `thresholds` and,
+    with `min_cluster_size`, the threshold-free clusters."""
+    h = region_hierarchy(collection, min_samples, **kwargs)
+    result = {"min_samples": int(min_samples), "n_regions": len(h.ids), "rounds": h.rounds, "components": h.components,
+              "edges": [{"a": h.ids[a], "b": h.ids[b], "weight": float(w)} for (a, b), w in zip(h.edges.tolist(), h.weights.tolist())],
+              "core": {i: float(c) for i, c in zip(h.ids, h.core.tolist())},
+              "cuts": [h.cut(t) for t in thresholds]}
+    if min_cluster_size is not None:
+        clusters = h.clusters(min_cluster_size)
+        clusters["labels"] = clusters["labels"].tolist()
+        result["clusters"] = clusters
+    if output_path:
+        os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+        with open(output_path, "w") as fh:
+            json.dump(result, fh, indent=1)
+    return result
+
+
 K12_LIST_LIMIT = 128  # mme_neighbours: fetch and top_n lie in 1..128
 
 

@@ -130,3 +130,24 @@ def load_projection(path):
 
     with np.load(_npz_path(path)) as z:
         return Projection(**{f: z[f] for f in _PROJECTION_ARRAYS}, n_rows=int(z["n_rows"]), whiten=bool(z["whiten"]), eps=float(z["eps"]))
+
+
+def save_hierarchy(hierarchy, path):
+    """A region_compare.RegionHierarchy as one `.npz` (the suffix is added when missing): edges int32, weights and core float32
+    as they are, the ids as a string array, and min_samples, rounds, components as scalars.  The rows' metadata is not kept.
+    load_hierarchy gives every bit of the arrays back."""
+    path = _npz_path(path)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, edges=np.asarray(hierarchy.edges, dtype=np.int32).reshape(-1, 2), weights=np.asarray(hierarchy.weights, dtype=np.float32),
+             core=np.asarray(hierarchy.core, dtype=np.float32), ids=np.asarray(list(hierarchy.ids), dtype=np.str_),
+             min_samples=np.int64(hierarchy.min_samples), rounds=np.int64(hierarchy.rounds), components=np.int64(hierarchy.components))
+    return path
+
+
+def load_hierarchy(path):
+    """Inverse of `save_hierarchy` (metadatas = None)."""
+    from .region_compare import RegionHierarchy
+
+    with np.load(_npz_path(path)) as z:
+        return RegionHierarchy(z["edges"], z["weights"], z["core"], int(z["min_samples"]), [str(i) for i in z["ids"]], None, int(z["rounds"]),
+                               int(z["components"]))
