@@ -543,8 +543,11 @@ int mme_set_chunk(mme_ctx* ctx, int crops_per_pass);
 /* Tuning / test knob: which MFMA GEMM tiling serves K2/K4/K6/K7/K9.  0 = by shape (default),
  * 1 = 128x128 tiles, 3 = 256x256 ping-pong kernel with a 3-deep activation ring, 4 = variant 3 with
  * 4 of a lane's 16 output stores deferred into the next tile's first K-tile (the default for large
- * problems).  2 is accepted and means 3; 5 and 6 are accepted and mean 4.  Results are bit-identical
- * across variants (same MFMA instruction, same K order per output element). */
+ * problems), 6 = the 384x256 kernel (eight waves, wave tile 192x64, two K-tiles of LDS: 17 % fewer operand
+ * bytes per FLOP, no deferred stores) for the epilogues it is built for (0, 1, 2, 5, 6, 8) and variant 4
+ * for the others.  0 takes 6 for the (N, K) shapes on which it measured faster (QKV, fc1, fc2 of ViT-B at
+ * 16 or more tiles per workgroup), else 4.  2 is accepted and means 3; 5 is accepted and means 4.  Results
+ * are bit-identical across variants (same MFMA instruction, same K order per output element). */
 int mme_set_gemm_variant(mme_ctx* ctx, int variant);
 
 /* LayerNorm folding: LN1 / LN2 are folded into the QKV / fc1 GEMMs
@@ -1272,7 +1275,8 @@ int mme_gemm_stamps(mme_ctx* ctx, int M, int N, int K, uint64_t* stamps_host);
  *             4 outf[m * ldf + n] = acc (f32)
  *             5 out = bf16(rstd[m] * (acc - mean[m] * colsum[n]) + bias[n]), (mean, rstd) = ln_stats[2m], [2m + 1]
  *             6 as 5, then gelu
- *             8 as 2; the 256 x 256 kernel (*ran_256 = 1) also writes, for every row of an INTERIOR 256-row tile,
+ *             8 as 2; a large-tile kernel (*ran_256 = 1) also writes, for every row of an INTERIOR row tile (256 rows;
+ *               384 rows under variant 6, or under variant 0 where it takes that kernel),
  *               ln_part[(0 * N/64 + slice) * ln_part_rows + m] = sum and [(1 * N/64 + slice) * ...] = sum of squares of
  *               the ROUNDED outputs of row m over columns 64 slice .. 64 slice + 63 (f32).  Other rows carry no promise.
  *             (7, the candidate-list epilogue of mme_neighbours, is refused here: mme_select_apply op 2 launches it.)
@@ -1283,7 +1287,8 @@ int mme_gemm_stamps(mme_ctx* ctx, int M, int N, int K, uint64_t* stamps_host);
  * res 16-byte aligned and either == out or not overlapping it; pos 16-byte aligned with pos_rows >= 197; outf with
  * ldf >= N, 16-byte aligned when ldf % 4 == 0 (4-byte otherwise); ln_stats 8-byte, colsum 16-byte aligned; planes:
  * N % 64 == 0, ln_part_rows >= M (epilogue 8) or >= M / 196 * 197 (epilogue 3), ln_part_floats >= 2 * N/64 * ln_part_rows.
- * *ran_256 = 1 when the 256 x 256 kernel ran (and, for epilogue 8, the planes were written), 0 for the 128 x 128 one. */
+ * *ran_256 = 1 when a large-tile kernel ran (256 x 256 or 384 x 256; for epilogue 8, the planes were written), 0 for the
+ * 128 x 128 one. */
 typedef struct mme_gemm_apply_args {
     int32_t epilogue, variant, reverse_m;
     int32_t M, N, K;

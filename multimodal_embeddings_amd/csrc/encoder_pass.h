@@ -47,9 +47,10 @@ struct EncoderPass {
     int gemm(int epilogue, const GemmArgs& g);
     // statistics of rows [row0, rows) of `xr` in the canonical summation order: one read of those rows
     int stats_from_x(const void* xr, int64_t row0, int64_t rows);
-    // statistics of the `rows` rows `producer` wrote (producer.out): rows [0, floor(rows / 256) * 256) are finished from
-    // the planes when they are used and the launch ran the 256 x 256 kernel (the only one that leaves them), the ragged
-    // tail -- or, otherwise, every row -- takes stats_from_x, which sums in the same order: the same bits either way
+    // statistics of the `rows` rows `producer` wrote (producer.out): the rows of the interior row tiles of the kernel that
+    // ran (gemm_interior_rows: 256- or 384-row tiles) are finished from the planes when they are used and the launch ran a
+    // large-tile kernel (the only ones that leave them), the ragged tail -- or, otherwise, every row -- takes
+    // stats_from_x, which sums in the same order: the same bits either way
     int stats_after(const GemmArgs& producer, int64_t rows);
     // out = xr + a . w^T + bias on `rows` rows (o_proj, fc2), in place on xr; `stats_next`: a folded LayerNorm reads xr next
     int residual(const void* a, const bf16_t* w, const float* bias, int K, int rows, void* xr, bool stats_next);

@@ -14,8 +14,8 @@ int EncoderPass::stats_from_x(const void* xr, int64_t row0, int64_t rows) {
 }
 
 int EncoderPass::stats_after(const GemmArgs& producer, int64_t rows) {
-    if (!planes || !gemm_runs_256(producer, c->gemm_variant)) return stats_from_x(producer.out, 0, rows);
-    const int64_t interior = rows / 256 * 256;
+    const int64_t interior = planes ? gemm_interior_rows(EPI_BIAS_RES_STATS, producer, c->gemm_variant) : 0;
+    if (interior == 0) return stats_from_x(producer.out, 0, rows);
     {
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_ln_finish(lnpart, lnpart_rows, interior, D, eps, stats, s));

@@ -120,31 +120,52 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_128(GemmArgs g) {
 }  // namespace
 
 hipError_t launch_gemm256r(int epilogue, const GemmArgs& g, hipStream_t s, bool defer);
+hipError_t launch_gemm384r(int epilogue, const GemmArgs& g, hipStream_t s);
+bool gemm384r_has(int epilogue);
 
 // variant: 0 = choose by shape, 1 = 128x128 tiles, 3 = 256x256 ping-pong kernel with a 3-deep activation ring (all 160 KiB
-// of LDS), 4 = variant 3 with 4 of a lane's 16 stores deferred into the next tile's first K-tile.  Accepted for old
-// callers: 2 means 3 (the 2-slot-ring kernel it named was folded into gemm256r.hip); 5 and 6 mean 4 (their deeper
-// deferrals, 8 and 6 stores, measured slower than 4)
-static int resolve_variant(const GemmArgs& g, int variant) {
+// of LDS), 4 = variant 3 with 4 of a lane's 16 stores deferred into the next tile's first K-tile, 6 = the 384x256 kernel
+// (gemm384r.hip) for the epilogues it is instantiated for, else 4.  Accepted for old callers: 2 means 3 (the 2-slot-ring
+// kernel it named was folded into gemm256r.hip); 5 means 4 (its deeper deferral, 8 stores, measured slower than 4)
+// The (N, K) shapes on which the 384 x 256 kernel beat variant 4 by more than variant 4's own round-to-round spread
+// (tools/gemm_bench.py, 806 912 rows, arms interleaved; figures: DESIGN 6): QKV, fc1 and fc2 of ViT-B.  o_proj (768 x 768)
+// lost there (its epilogue is a third of the launch and this kernel defers no stores) and stays on variant 4, as does every
+// shape not measured.  Measured at 24+ tiles per workgroup only: below 16 the last, partly filled round of 384-row tiles
+// would cost more than the kernel gains, so shorter launches stay on variant 4 too.
+static bool prefers_384(int epilogue, const GemmArgs& g) {
+    if (!gemm384r_has(epilogue) || (g.N % 256) != 0) return false;
+    if ((int64_t)((g.M + 383) / 384) * (g.N / 256) < 16 * 256) return false;
+    return (g.N == 2304 && g.K == 768) || (g.N == 3072 && g.K == 768) || (g.N == 768 && g.K == 3072);
+}
+
+static int resolve_variant(int epilogue, const GemmArgs& g, int variant) {
     if (variant == 0) {
         const int64_t tiles256 = (int64_t)((g.M + 255) / 256) * ((g.N + 255) / 256);
         // 128 tiles: measured on whole embed calls of 16..256 crops (tools/bench_small.py): with the threshold at 256, calls
         // of 64 / 96 crops ran their 150- / 225-tile GEMMs on the 128 x 128 kernel and took 11 % / 9 % longer (that kernel
         // also leaves no LayerNorm partial sums: one more pass over x per LayerNorm)
-        variant = tiles256 >= 128 ? 4 : 1;
+        variant = tiles256 >= 128 ? (prefers_384(epilogue, g) ? 6 : 4) : 1;
     }
     if (variant == 2) variant = 3;
-    if (variant == 5 || variant == 6) variant = 4;
-    if (g.K < 128) variant = 1;  // the 256 kernel streams two K-tiles ahead
+    if (variant == 5) variant = 4;
+    if (variant == 6 && !gemm384r_has(epilogue)) variant = 4;
+    if (g.K < 128) variant = 1;  // the large-tile kernels stream two K-tiles ahead
     return variant;
 }
 
-bool gemm_runs_256(const GemmArgs& g, int variant) { return resolve_variant(g, variant) != 1; }
+bool gemm_runs_256(const GemmArgs& g, int variant) { return resolve_variant(EPI_BIAS, g, variant) != 1; }  // (whatever the epilogue)
+
+int64_t gemm_interior_rows(int epilogue, const GemmArgs& g, int variant) {
+    const int v = resolve_variant(epilogue, g, variant);
+    const int tm = v == 1 ? 0 : v == 6 ? 384 : 256;
+    return tm ? (int64_t)(g.M / tm) * tm : 0;
+}
 
 hipError_t launch_gemm(int epilogue, const GemmArgs& g, hipStream_t s, int variant) {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     const bool automatic = variant == 0;
-    variant = resolve_variant(g, variant);
+    variant = resolve_variant(epilogue, g, variant);
+    if (variant == 6) return launch_gemm384r(epilogue, g, s);
     if (variant == 3 || variant == 4) {
         // f32 out (K9): the deferred row block LOSES there -- interleaved A/B on the [8192 x 65536] block, 20 launches per arm,
         // four rounds: 0.911 ms without, 1.00 ms with (tools/k9_ab.py; the mid-round figure that favoured it had measured the

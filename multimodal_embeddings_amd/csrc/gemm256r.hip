@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_tiles.h"
 #include "kernels.h"
 
 namespace {
@@ -407,15 +408,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_256r(GemmArgs g, int tile
 #undef K_TILE
 }
 
-// column-group width of the tile order: the group's weight rows (gn x 256 x K bf16) should stay resident in one
-// XCD's 4 MiB L2 next to the streaming A panels and output lines; never split below 3 tiles
-// (PMC, fc1 4096 crops: L2-miss fetch 15.4 GB at gn = 12 -> 6.2 GB at gn = 6, same time)
-int column_group(int K, int tiles_n) {
-    int gn = (int)((2400 * 1024) / ((size_t)TN * K * 2));
-    if (gn < 3) gn = 3;
-    return gn > tiles_n ? tiles_n : gn;
-}
-
 template <int EPI, int NDEF, bool STAMP = false>
 hipError_t launch256r(const GemmArgs& g, hipStream_t s, unsigned long long* stamps = nullptr) {
     if (hipError_t e = ensure_dynamic_lds((const void*)gemm_bf16_tn_256r<EPI, STAMP, NDEF>, LDS_BYTES); e != hipSuccess) return e;
@@ -423,7 +415,7 @@ hipError_t launch256r(const GemmArgs& g, hipStream_t s, unsigned long long* stam
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < 256 ? ntiles : 256;  // one workgroup per CU
     hipLaunchKernelGGL((gemm_bf16_tn_256r<EPI, STAMP, NDEF>), dim3(grid), dim3(512), LDS_BYTES, s, g, tiles_m, tiles_n,
-                       column_group(g.K, tiles_n), stamps);
+                       gemm_column_group(g.K, tiles_n), stamps);
     return hipGetLastError();
 }
 

@@ -176,28 +176,34 @@ __device__ __forceinline__ f32x4 unpack_bf16x4(uint2 u) {
 // column (within the wave's 64) of this lane's 16-byte piece for the tile pair (jp, jp+1)
 __device__ __forceinline__ int row16_col(int jp, int fq) { return ((fq & 1) ? (jp + 1) * 16 : jp * 16) + (fq >> 1) * 8; }
 
-// Interior-tile epilogue of one wave tile (128 x 64 as acc[8][4] of 16x16 MFMA tiles; row
-// mw + 16 i + fr, columns nw + 16 j + 4 fq ..) for the bias / GELU / residual / LayerNorm-folded
-// epilogues.  All loads are issued first, `between()` runs next (the GEMM kernels request their
+// Interior-tile epilogue of one wave tile (16 NI x 64 as acc[NI][4] of 16x16 MFMA tiles, NI = 8 for the 256 x 256 kernel and
+// 12 for the 384 x 256 one; row mw + 16 i + fr, columns nw + 16 j + 4 fq ..) for the bias / GELU / residual /
+// LayerNorm-folded epilogues.  All loads are issued first, `between()` runs next (the GEMM kernels request their
 // next LDS-DMA there: vmcnt retires in order and counts stores, so a load issued after a store
-// would wait for it), then 16 fire-and-forget 16-byte stores, which are afterwards exactly the
-// 16 youngest vector-memory operations of the wave.  Straight-line code: a branch would make the
+// would wait for it), then 2 NI fire-and-forget 16-byte stores, which are afterwards exactly the
+// 2 NI youngest vector-memory operations of the wave.  Straight-line code: a branch would make the
 // compiler re-insert vmcnt(0) at every join.
-// NDEF > 0: the last NDEF / 2 row blocks of the wave tile (i >= 8 - NDEF / 2) are not stored but returned packed in pend[];
+// NI = 12 leaves no registers for all per-row loads at once (192 accumulators; the residual alone is 96 VGPRs): the rows
+// go in batches of four row blocks (two with a residual), and the loads of batch b + 1 are ISSUED before the stores of batch b, whose
+// packed results wait in the registers its accumulators left (the rule of epilogue_wave_patch_128x64).  Per element the
+// arithmetic and its order are those of NI = 8: the two forms agree bit for bit.
+// NDEF > 0 (NI = 8): the last NDEF / 2 row blocks of the wave tile (i >= 8 - NDEF / 2) are not stored but returned packed in pend[];
 // the caller issues them later (gemm256r.hip, variant 4).
-template <int EPI, int NDEF = 0, class Between>
-__device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&acc)[8][4], int mw, int nw, int fr, int fq,
+template <int EPI, int NDEF = 0, int NI, class Between>
+__device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&acc)[NI][4], int mw, int nw, int fr, int fq,
                                                      Between&& between, uint4* pend = nullptr) {
     static_assert(EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RES || EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU ||
                       EPI == EPI_BIAS_RES_STATS || EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_BIAS_TGELU ||
                       EPI == EPI_LN_BIAS_TGELU,
                   "epilogue_wave_128x64: unsupported epilogue");
+    static_assert(NI == 8 || (NI == 12 && NDEF == 0), "epilogue_wave_128x64: 8 row blocks, or 12 without deferred stores");
     constexpr bool RES = EPI == EPI_BIAS_RES || EPI == EPI_BIAS_RES_STATS;
     constexpr bool STATS = EPI == EPI_BIAS_RES_STATS;
     constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_LN_BIAS_TGELU;
     constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_LN_BIAS_GELU;
     constexpr bool QGELU = EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU;
     constexpr bool TGELU = EPI == EPI_BIAS_TGELU || EPI == EPI_LN_BIAS_TGELU;
+    constexpr int BATCH = NI == 8 ? 8 : RES ? 2 : 4;  // row blocks whose per-row loads are in registers together
     // wave-uniform row bases (SGPR pairs) + 32-bit lane offsets: saddr addressing
     const int64_t tile_off = (int64_t)mw * g.ldo + nw;
     const int lo0 = fr * (int)g.ldo + row16_col(0, fq), lo1 = fr * (int)g.ldo + row16_col(2, fq);
@@ -209,103 +215,130 @@ __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&
         bv[j] = *(const f32x4*)(g.bias + nw + fq * 4 + j * 16);
         if (LN) sv[j] = *(const f32x4*)(g.colsum + nw + fq * 4 + j * 16);
     }
-    float2 st[LN ? 8 : 1];
-    if (LN) {
+    float2 st[LN ? NI : 1];
+    uint4 rv[RES ? NI : 1][2];
+    auto load_rows = [&](int i0) {
+        if (LN) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) st[i] = *(const float2*)(g.ln_stats + 2 * (int64_t)(mw + i * 16 + fr));
-    }
-    uint4 rv[RES ? 8 : 1][2];
-    if (RES) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            rv[i][0] = *(const uint4*)(resb + (int64_t)i * 16 * g.ldo + lo0);
-            rv[i][1] = *(const uint4*)(resb + (int64_t)i * 16 * g.ldo + lo1);
+            for (int i = i0; i < i0 + BATCH; ++i) st[i] = *(const float2*)(g.ln_stats + 2 * (int64_t)(mw + i * 16 + fr));
         }
-    }
+        if (RES) {
+#pragma unroll
+            for (int i = i0; i < i0 + BATCH; ++i) {
+                rv[i][0] = *(const uint4*)(resb + (int64_t)i * 16 * g.ldo + lo0);
+                rv[i][1] = *(const uint4*)(resb + (int64_t)i * 16 * g.ldo + lo1);
+            }
+        }
+    };
+    load_rows(0);
     asm volatile("" ::: "memory");
     between();
     asm volatile("" ::: "memory");
-    float psum[STATS ? 8 : 1], psq[STATS ? 8 : 1];
+    float psum[STATS ? NI : 1], psq[STATS ? NI : 1];
     if (STATS) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) psum[i] = psq[i] = 0.f;
+        for (int i = 0; i < NI; ++i) psum[i] = psq[i] = 0.f;
     }
+    // the packed 16 bytes of row block i, column tiles (jp, jp + 1)
+    auto compute = [&](int i, int jp) {
+        f32x4 v0, v1;
+        if (LN) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+            for (int r = 0; r < 4; ++r) {
+                v0[r] = fmaf(st[i].y, fmaf(-st[i].x, sv[jp][r], acc[i][jp][r]), bv[jp][r]);
+                v1[r] = fmaf(st[i].y, fmaf(-st[i].x, sv[jp + 1][r], acc[i][jp + 1][r]), bv[jp + 1][r]);
+            }
+        } else {
+            v0 = acc[i][jp] + bv[jp];
+            v1 = acc[i][jp + 1] + bv[jp + 1];
+        }
+        if (GELU) {
 #pragma unroll
-        for (int jp = 0; jp < 4; jp += 2) {
-            f32x4 v0, v1;
-            if (LN) {
+            for (int r = 0; r < 4; ++r) {
+                v0[r] = gelu_erf(v0[r]);
+                v1[r] = gelu_erf(v1[r]);
+            }
+        }
+        if (QGELU) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v0[r] = fmaf(st[i].y, fmaf(-st[i].x, sv[jp][r], acc[i][jp][r]), bv[jp][r]);
-                    v1[r] = fmaf(st[i].y, fmaf(-st[i].x, sv[jp + 1][r], acc[i][jp + 1][r]), bv[jp + 1][r]);
+            for (int r = 0; r < 4; ++r) {
+                v0[r] = quick_gelu(v0[r]);
+                v1[r] = quick_gelu(v1[r]);
+            }
+        }
+        if (TGELU) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v0[r] = gelu_tanh(v0[r]);
+                v1[r] = gelu_tanh(v1[r]);
+            }
+        }
+        if (RES) {
+            uint2 rp, rq;
+            row16_to_pair(rv[i][jp >> 1], rp, rq);
+            v0 += unpack_bf16x4(rp);
+            v1 += unpack_bf16x4(rq);
+        }
+        const uint2 pk0 = pack_bf16x4(v0), pk1 = pack_bf16x4(v1);
+        if (STATS) {  // canonical order: column tiles j ascending, the two packed pairs of a tile in order
+            ln_accumulate(pk0, psum[i], psq[i]);
+            ln_accumulate(pk1, psum[i], psq[i]);
+        }
+        return pair_to_row16(pk0, pk1);
+    };
+    if constexpr (BATCH == NI) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+#pragma unroll
+            for (int jp = 0; jp < 4; jp += 2) {
+                const uint4 packed = compute(i, jp);
+                if (NDEF > 0 && i >= 8 - NDEF / 2) {
+                    pend[(i - (8 - NDEF / 2)) * 2 + (jp >> 1)] = packed;
+                } else {
+                    *(uint4*)(outb + (int64_t)i * 16 * g.ldo + (jp ? lo1 : lo0)) = packed;
                 }
-            } else {
-                v0 = acc[i][jp] + bv[jp];
-                v1 = acc[i][jp + 1] + bv[jp + 1];
             }
-            if (GELU) {
+        }
+    } else {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v0[r] = gelu_erf(v0[r]);
-                    v1[r] = gelu_erf(v1[r]);
-                }
-            }
-            if (QGELU) {
+        for (int i0 = 0; i0 < NI; i0 += BATCH) {
+            uint4 packed[BATCH][2];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v0[r] = quick_gelu(v0[r]);
-                    v1[r] = quick_gelu(v1[r]);
-                }
+            for (int i = 0; i < BATCH; ++i) {
+                packed[i][0] = compute(i0 + i, 0);
+                packed[i][1] = compute(i0 + i, 2);
             }
-            if (TGELU) {
+            if (i0 + BATCH < NI) load_rows(i0 + BATCH);  // BEFORE this batch's stores
+            asm volatile("" ::: "memory");
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v0[r] = gelu_tanh(v0[r]);
-                    v1[r] = gelu_tanh(v1[r]);
-                }
+            for (int i = 0; i < BATCH; ++i) {
+                *(uint4*)(outb + (int64_t)(i0 + i) * 16 * g.ldo + lo0) = packed[i][0];
+                *(uint4*)(outb + (int64_t)(i0 + i) * 16 * g.ldo + lo1) = packed[i][1];
             }
-            if (RES) {
-                uint2 rp, rq;
-                row16_to_pair(rv[i][jp >> 1], rp, rq);
-                v0 += unpack_bf16x4(rp);
-                v1 += unpack_bf16x4(rq);
-            }
-            const uint2 pk0 = pack_bf16x4(v0), pk1 = pack_bf16x4(v1);
-            if (STATS) {  // canonical order: column tiles j ascending, the two packed pairs of a tile in order
-                ln_accumulate(pk0, psum[i], psq[i]);
-                ln_accumulate(pk1, psum[i], psq[i]);
-            }
-            const uint4 packed = pair_to_row16(pk0, pk1);
-            if (NDEF > 0 && i >= 8 - NDEF / 2) {
-                pend[(i - (8 - NDEF / 2)) * 2 + (jp >> 1)] = packed;
-            } else {
-                *(uint4*)(outb + (int64_t)i * 16 * g.ldo + (jp ? lo1 : lo0)) = packed;
-            }
+            asm volatile("" ::: "memory");
         }
     }
     if (STATS) {
-        // 16 per-lane partials (8 row blocks x {sum, sum of squares}) over this lane's 16 columns of the wave's
+        // 2 NI per-lane partials (NI row blocks x {sum, sum of squares}) over this lane's 16 columns of the wave's
         // 64-column slice -> totals over the four lanes (fq = 0..3) that share a row, as ((fq0 + fq1) + (fq2 + fq3)).
-        // Two swap levels reduce all 16 at once: v_permlane16_swap leaves the pair sums of quantity a in the even
+        // Two swap levels reduce them all at once: v_permlane16_swap leaves the pair sums of quantity a in the even
         // 16-lane rows and those of b in the odd rows, v_permlane32_swap then pairs the lane halves.
-        float t[8];
+        float t[NI];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {  // row block k: rows 0 / 2 of the result pair psum over fq, rows 1 / 3 psq
+        for (int k = 0; k < NI; ++k) {  // row block k: rows 0 / 2 of the result pair psum over fq, rows 1 / 3 psq
             const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(psum[k]), __float_as_uint(psq[k]), false, false);
             t[k] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);  // even rows: psum[k] over (fq, fq + 1); odd rows: psq[k]
         }
-        float u[4];
+        float u[NI / 2];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < NI / 2; ++k) {
             const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(t[2 * k]), __float_as_uint(t[2 * k + 1]), false, false);
             u[k] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);  // lanes 0..31: row block 2k; lanes 32..63: row block 2k + 1
         }
         // lane (fq, fr): fq & 1 selects the plane (0 sum, 1 sum of squares), fq >> 1 the row block 2k + (fq >> 1)
         float* plane = g.ln_part + ((int64_t)(fq & 1) * (g.N >> 6) + (nw >> 6)) * g.ln_part_rows + mw + (fq >> 1) * 16 + fr;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) plane[k * 32] = u[k];
+        for (int k = 0; k < NI / 2; ++k) plane[k * 32] = u[k];
     }
 }
 

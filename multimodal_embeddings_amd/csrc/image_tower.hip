@@ -85,7 +85,7 @@ int stem(EncoderPass& P, const bf16_t* patches, int n) {
         // the patch-embed epilogue left the partial sums of every token row an INTERIOR tile wrote (patch rows
         // [0, interior) -> token rows up to t_int); the [CLS] rows (written by cls_rows, every 197th row) and the rows
         // of the ragged last tile take the stand-alone kernel, same canonical order
-        const int64_t interior = (int64_t)(g.M / 256) * 256;                               // patch rows
+        const int64_t interior = gemm_interior_rows(EPI_PATCH, g, c->gemm_variant);        // patch rows
         const int64_t t_int = interior ? interior - 1 + (interior - 1) / VIT_NP + 2 : 0;   // one past the last token row they map to
         Timed t(c, s, KC_LN);
         HIP_TRY(c, launch_ln_finish(P.lnpart, P.lnpart_rows, t_int, D, c->ln_eps, P.stats, s));

@@ -88,8 +88,11 @@ hipError_t launch_ln_stats(const void* x, int64_t rows, int d, float eps, float*
 hipError_t launch_ln_stats_canonical(const void* x, int64_t row0, int64_t row1, int d, float eps, float* stats, hipStream_t s, int64_t stride = 1);
 // finishes rows [0, rows) from the partial planes an EPI_BIAS_RES_STATS GEMM left: part [2][d/64][part_rows]
 hipError_t launch_ln_finish(const float* part, int64_t part_rows, int64_t rows, int d, float eps, float* stats, hipStream_t s);
-// true when launch_gemm(variant) runs the 256 x 256 kernel (whose fast-path epilogue writes the partial planes)
+// true when launch_gemm(variant) runs a large-tile kernel (256 x 256 or 384 x 256), whose fast-path epilogue writes the partial planes
 bool gemm_runs_256(const GemmArgs& g, int variant);
+// rows [0, this) lie in the interior row tiles of the kernel launch_gemm(epilogue, g, s, variant) runs (256- or 384-row
+// tiles; 0 for the 128 x 128 kernel): the rows whose partial planes an EPI_BIAS_RES_STATS / EPI_PATCH launch leaves
+int64_t gemm_interior_rows(int epilogue, const GemmArgs& g, int variant);
 // x[b*197 + 0, :] = bf16(cls + pos[0]), rows of d
 hipError_t launch_cls_rows(void* x, const float* cls, const float* pos, int B, int d, hipStream_t s);
 // final LayerNorm on row b*tokens+tok of d values, L2 normalise, write f32 and/or bf16 [B, d]; tokens and tok as launch_pool_ln
