@@ -298,11 +298,18 @@ def t_int_formula(M):
     return interior - 1 + (interior - 1) // NP + 2 if interior else 0
 
 
-def check_planes(epi, planes, out_bits, M, N, ran, what):
+def row_tile(epi, variant):
+    """Row-tile height of the large-tile kernel an explicit `variant` resolves to (include/mme.h): 384 under variant 6 for the
+    epilogues the 384 x 256 kernel is built for (0, 1, 2, 5, 6, 8), else 256 (epilogues 3 and 4 resolve to variant 4)."""
+    return 384 if variant == 6 and epi in (0, 1, 2, 5, 6, 8) else 256
+
+
+def check_planes(epi, planes, out_bits, M, N, ran, what, tm=256):
+    """`tm`: the row-tile height of the kernel that ran (row_tile): the planes are promised for the rows of its interior row tiles"""
     if not ran:
         assert bool(torch.isnan(planes).all()), f"{what}: the 128 x 128 kernel wrote partial-sum planes"
         return
-    interior = M // 256 * 256
+    interior = M // tm * tm
     m = torch.arange(interior, device=DEV)
     rows_idx = token_rows(interior) if epi == 3 else m
     if N % 256 == 0 and interior:
@@ -321,7 +328,8 @@ def check_planes(epi, planes, out_bits, M, N, ran, what):
                 assert torch.equal((~torch.isnan(planes[k, s])).nonzero().flatten(), rows_idx), f"{what}: plane {k} slice {s} covers other rows"
 
 
-# (epilogue, M, N, K, options).  Properties covered -- kernel: variants 1, 3, 4 always, 0 and reverse_m where listed;
+# (epilogue, M, N, K, options).  Properties covered -- kernel: variants 1, 3, 4, 6 always (6 is the 384 x 256 kernel for epilogues
+# 0, 2, 5, 8 and variant 4 for 3 and 4; its planes cover 384-row interior tiles), 0 and reverse_m where listed;
 # M: 1, 127, 128, 129, 255, 256, 257, ragged last row tiles, 256 and 257 tiles (the persistent loop's has_next boundary at a
 # grid of 256), 288 tiles (every workgroup defers into a following tile and flushes a last one); N: 768, 1280, 2304, 3072,
 # 3840, 5120, N % 256 != 0 (260, 320, 1028, 261), N < 128; K: 64 (128 x 128 kernel whatever the variant), 128, 192, 640, 768,
@@ -370,7 +378,7 @@ def test_exact_bit_for_bit(eng, case):
     planes_on = opt.get("planes", epi == 8)
     # epilogue 8 always takes a plane buffer; "planes": False only says that N % 256 != 0 leaves no complete row to compare
     give_planes = epi == 8 or (epi == 3 and planes_on)
-    runs = [(1, 0), (3, 0), (4, 0)] + opt.get("extra", [])
+    runs = [(1, 0), (3, 0), (4, 0), (6, 0)] + opt.get("extra", [])
     for variant, rev in runs:
         w = f"{what} variant {variant} reverse {rev}"
         out, planes, ran = launch(eng, epi, d["A"], d["W"], variant, reverse_m=rev, bias=d.get("bias"), res=d.get("res"),
@@ -379,7 +387,7 @@ def test_exact_bit_for_bit(eng, case):
         got = out.view(torch.int32 if epi == 4 else torch.int16)
         assert_bits(got, want, w)
         if give_planes:
-            check_planes(epi, planes, want, M, N, ran, w)
+            check_planes(epi, planes, want, M, N, ran, w, tm=row_tile(epi, variant))
     # ---- sharpness: each mutant is a change of the reference that this case's comparison would see
     if opt.get("swap"):  # the two 8-column blocks a permlane16_swap pair exchanges: columns 32q + 8..15 <-> 32q + 16..23
         c = torch.arange(N, device=DEV)

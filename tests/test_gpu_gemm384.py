@@ -18,6 +18,10 @@ and everything outside variant 6's interior must still hold the sentinel.  At M 
 
 Last, a five-crop embed (985 token rows: two interior 384-row tiles and a ragged 217) under variants 3 and 6 with the
 LayerNorm statistics from one pass over x (ln_fusion 1) and from the planes (ln_fusion 2): four embeddings equal in bits.
+
+Everything beyond two tiles per workgroup is in tests/test_gpu_gemm384_stream.py: three and four tiles per workgroup, an odd
+number of K-tiles across a tile boundary, several column groups, a ragged tile prefetched from an interior one and the
+reverse, float64 exact references, the automatic choice (variant 0) at its threshold and the product configuration end to end.
 """
 import os
 import sys

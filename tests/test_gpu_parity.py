@@ -160,7 +160,7 @@ def test_ln_fusion_on_off_agree(engine, golden_dir):
     pixb, offsb, hwb = _pack(list(crops))
     engine.set_ln_fusion(1)
     ref, _ = engine.embed(pixb, offsb, hwb)
-    for variant in (0, 1, 3, 4):
+    for variant in (0, 1, 3, 4, 6):
         engine.set_gemm_variant(variant)
         for mode in (2, 1):
             engine.set_ln_fusion(mode)

@@ -555,7 +555,7 @@ def test_forward_settings_are_bit_identical(crops40, key):
         eng.set_ln_fusion(1)
         ref, _ = _uniform(eng, crops)
         assert bool(torch.isfinite(ref).all()) and tuple(ref.shape) == (300, width)
-        for variant in (0, 1, 3, 4):
+        for variant in (0, 1, 3, 4, 6):
             eng.set_gemm_variant(variant)
             for mode in (2, 1):
                 eng.set_ln_fusion(mode)
