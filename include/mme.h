@@ -1651,6 +1651,113 @@ typedef struct mme_tile_rowop_apply_args {
 } mme_tile_rowop_apply_args;
 int mme_tile_rowop_apply(mme_ctx* ctx, int op, const mme_tile_rowop_apply_args* args, void* stream);
 
+/* ---- Mllama language tower with cross-attention ---------------------------
+ * Replaces the language side of `MllamaForConditionalGeneration.from_pretrained(...)` / `model(**inputs)` and `last_pooling`
+ * (deprecated_package/embedder.py:17-34, 102-129, 228-254): transformers `multi_modal_projector` + `MllamaTextModel`
+ * (models/mllama/modeling_mllama.py) -- embed_tokens, rotary positions 0..S-1, self-attention layers (RMSNorm, bias-free
+ * q/k/v, rotate_half RoPE, causal GQA attention, o_proj, RMSNorm, down(silu(gate) * up)) and, at the indices of
+ * cross_attention_layers, cross-attention layers (q_norm / k_norm per head, no RoPE, not causal, tanh gates, the per-row tile
+ * mask of _prepare_cross_attention_mask), the final norm -- then the row at len - 1, L2-normalised.  Without vision rows
+ * the cross layers are skipped entirely (the text-only path of get_text_embeddings).
+ *
+ * Supported geometry (else MME_E_ARG naming the field, the value found and the supported set; nothing in the context
+ * changes): head_dim 128, hidden = heads * 128, heads <= 64, heads / kv_heads in {1, 2, 4, 8}; intermediate % 64 == 0 and
+ * <= 16384; 1..64 layers, cross layer indices strictly increasing (an index at or beyond `layers` is ignored); vocab + 8 <=
+ * 2^18 rows of embed_tokens; vision_dim % 64 == 0 and <= 8192; hidden_act 0 (silu); rope_type 0 ("default") or 1 ("llama3");
+ * image_token_id in 0..vocab + 7.  Sequences of 1..128 tokens.
+ *
+ * Every tensor is row-major f32 (mme_load_mllama_lm) or elements of `dtype` (mme_load_mllama_lm_as, prepared on the device
+ * to the same bits).  The tower lives beside the context's other towers (the tile tower among them); a second load replaces
+ * it.  Prepared buffers, in the order mme_weights_fingerprint reports them: embed_tokens bf16 [vocab + 8, hidden], norm f32,
+ * projector weight bf16 [hidden, vision_dim], projector bias f32, zeros f32, the rotary cos and sin tables f32 [128, 64]
+ * (built on the host), then per layer -- self: input_layernorm f32, q | k | v bf16 [(heads + 2 kv_heads) 128, hidden], o_proj
+ * bf16, post_attention_layernorm f32, gate | up bf16 [2 intermediate, hidden], down bf16 -- cross: input_layernorm, q_proj
+ * bf16, q_norm f32 [128], k_norm f32 [128], k | v bf16 [2 kv_heads 128, hidden], o_proj * tanh(attn_gate) bf16,
+ * post_attention_layernorm, gate | up, down * tanh(mlp_gate) bf16 (tanh on the host, the factor applied in f32 before the
+ * rounding to bf16). */
+typedef struct mme_mllama_lm_layer {
+    int32_t cross;            /* 1: a cross-attention layer (q_norm, k_norm and the gates are read) */
+    float attn_gate, mlp_gate; /* cross_attn_attn_gate, cross_attn_mlp_gate: the raw scalars */
+    const float *ln1, *ln2;   /* input_layernorm.weight, post_attention_layernorm.weight [hidden] */
+    const float *q_w, *k_w, *v_w, *o_w; /* [heads 128, hidden], [kv_heads 128, hidden] x 2, [hidden, heads 128] */
+    const float *q_norm, *k_norm;       /* [128] each, cross layers only */
+    const float *gate_w, *up_w, *down_w; /* [intermediate, hidden] x 2, [hidden, intermediate] */
+} mme_mllama_lm_layer;
+
+typedef struct mme_mllama_lm_weights {
+    int32_t hidden, heads, kv_heads, intermediate, layers;
+    int32_t vocab;            /* text_config.vocab_size; embed_tokens has vocab + 8 rows */
+    int32_t vision_dim;       /* vision_config.vision_output_dim */
+    int32_t image_token_id;   /* image_token_index: the id of <|image|> */
+    int32_t hidden_act;       /* 0 silu */
+    int32_t rope_type;        /* 0 "default", 1 "llama3" */
+    int32_t rope_original_max; /* llama3: original_max_position_embeddings */
+    float rms_eps, rope_theta, rope_factor, rope_low_freq_factor, rope_high_freq_factor;
+    const float *embed_tokens, *norm, *proj_w, *proj_b;
+    const mme_mllama_lm_layer* layer; /* [layers] */
+} mme_mllama_lm_weights;
+
+int mme_load_mllama_lm(mme_ctx* ctx, const mme_mllama_lm_weights* w);
+int mme_load_mllama_lm_as(mme_ctx* ctx, const mme_mllama_lm_weights* w, int dtype, void* stream);
+/* out: loaded (0 / 1), hidden, heads, kv_heads, intermediate, layers, cross layers, vocab, vision_dim, image_token_id,
+ * rope_type, index in mme_weights_fingerprint's order of the tower's first prepared buffer; all zero before a load */
+int mme_mllama_lm_info(mme_ctx* ctx, int32_t out[12]);
+
+/* ids_host int32 [n, S], len_host int32 [n] (attended tokens of each sequence, 1..S: right padding only; under the causal
+ * mask nothing behind len - 1 reaches that row, so the padded ids only have to be valid ids).
+ * vision_bf16_dev: bf16 [n, tiles, tokens, vision_dim], the vision model's last_hidden_state (padding tiles included), or
+ * NULL: the text-only path (tiles, tokens, num_tiles_host and xmask_host are not read).  tiles 1..4, tokens 1..1601.
+ * xmask_host uint8 [n, S]: the tiles each row attends, as bits (bit t: tile t; below 1 << tiles).  A row with no bit attends
+ * EVERY key (padding tiles included) and its cross layers' MLP term is zero, as transformers computes it.  NULL: the
+ * processor's rule -- rows from the first image_token_id on attend tiles [0, num_tiles_host[i]), rows before it none.
+ * With vision rows every sequence must hold image_token_id (else MME_E_ARG).
+ * emb_f32_dev f32 [n, hidden] and / or emb_bf16_dev bf16 [n, hidden]: the final norm of row len - 1, L2-normalised.
+ * Sequences are processed mme_set_chunk (<= 64) at a time; asynchronous on `stream` apart from the staging of the ids. */
+int mme_mllama_lm_forward(mme_ctx* ctx, const int32_t* ids_host, const int32_t* len_host, int n, int S, const uint16_t* vision_bf16_dev, int tiles,
+                          int tokens, const int32_t* num_tiles_host, const uint8_t* xmask_host, float* emb_f32_dev, uint16_t* emb_bf16_dev, void* stream);
+
+/* pixel_values -> tile tower -> projector -> language tower, mme_set_chunk (<= 64) images at a time: the first three
+ * arguments as mme_tile_vit_forward (both towers loaded, vision_dim == the tile tower's 1280 * (1 + n_intermediate)), the
+ * rest as mme_mllama_lm_forward.  The vision states reach the projector as bf16 [chunk, 4, 1601, vision_dim], gathered from
+ * the tile tower's own bf16 buffers: the f32 `hidden` tensor of mme_tile_vit_forward is never written.  Bit-identical to
+ * mme_tile_vit_forward's hidden (rounded to bf16, which is exact) handed to mme_mllama_lm_forward. */
+int mme_mllama_embed(mme_ctx* ctx, const float* pixel_values_dev, const int32_t* aspect_ids_host, const int32_t* num_tiles_host, int n,
+                     const int32_t* ids_host, const int32_t* len_host, int S, const uint8_t* xmask_host, float* emb_f32_dev, uint16_t* emb_bf16_dev,
+                     void* stream);
+
+/* Diagnostic: ONE launch of a kernel of the language tower (mllama_lm.hip) on the caller's device buffers, synchronous; works
+ * on a bare context (tests/test_gpu_mllama_lm.py compares every output element with float64).  bf16 rows; heads are 128 wide.
+ *   op 0 gather      x[r] = tok[ids_host[r]], r < rows; tok [vocab, d]
+ *      1 rmsnorm     y[r] = bf16(w * (x[r] * rsqrt(mean(x[r]^2) + eps))), rows of d
+ *      2 headnorm    in place: the `heads` heads from column col0 on of every row of ld values, each normalised with w [128]
+ *      3 rope        in place: rotate_half RoPE on the first `heads` heads of every row of ld values, position r % S;
+ *                    cos / sin f32 [128, 64]
+ *      4 silu_mul    y [rows, d] = bf16(silu(x[:, :d]) * x[:, d:]), x [rows, 2 d]; rowzero (DEVICE uint8 [rows] or NULL): zero rows
+ *      5 pool        row b * S + len_host[b] - 1 of x [n S, d]: w * (x * rstd) in f32, L2 -> emb_f32 / emb_bf16 [n, d]
+ *      6 self_attn   x = qkv [n S, (heads + 2 kv_heads) 128] -> y [n S, heads 128], causal, rows at or behind len_host[b] zero
+ *      7 cross_attn  x = q [n S, heads 128], kv [n tiles tokens, 2 kv_heads 128], xmask_host uint8 [n S] -> y [n S, heads 128]
+ * Preconditions (else MME_E_ARG with a message, nothing launched): pointers non-null and 16-byte aligned; d % 8 == 0 (ops 0, 1,
+ * 4), 8..16384; 1 <= S <= 128; heads / kv_heads in {1, 2, 4, 8} (ops 6, 7); ids inside 0..vocab-1; len in 1..S; mask bits
+ * below 1 << tiles; ld and col0 cover the heads. */
+typedef struct mme_mllama_apply_args {
+    const uint16_t* tok;      /* op 0 */
+    const int32_t* ids_host;  /* op 0 */
+    const int32_t* len_host;  /* ops 5, 6 */
+    const uint8_t* xmask_host; /* op 7 */
+    uint16_t* x;              /* input (in place for ops 2, 3; output of op 0) */
+    uint16_t* y;              /* output of ops 1, 4, 6, 7 */
+    const uint16_t* kv;       /* op 7 */
+    const float* w;           /* ops 1, 2, 5 */
+    const float *cos, *sin;   /* op 3 */
+    const uint8_t* rowzero;   /* op 4 */
+    float* emb_f32;           /* op 5 */
+    uint16_t* emb_bf16;
+    int64_t rows, ld;
+    int32_t n, S, d, heads, kv_heads, col0, vocab, tiles, tokens;
+    float eps;
+} mme_mllama_apply_args;
+int mme_mllama_apply(mme_ctx* ctx, int op, const mme_mllama_apply_args* args, void* stream);
+
 /* ---- multi-GPU: the ONE exchange step of the path ------------------------------------------
  * Replaces the hand-back of per-device results through Python lists by the reference's thread pool
  * (deprecated_package/embedder.py:208-224): every rank embeds its contiguous block of the corpus and the

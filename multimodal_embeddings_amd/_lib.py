@@ -97,6 +97,24 @@ class _TileWeights(C.Structure):
     ]
 
 
+class _MllamaLMLayer(C.Structure):  # mme_mllama_lm_layer
+    _fields_ = [("cross", C.c_int32), ("attn_gate", C.c_float), ("mlp_gate", C.c_float)] + [
+        (n, C.POINTER(C.c_float)) for n in ("ln1", "ln2", "q_w", "k_w", "v_w", "o_w", "q_norm", "k_norm", "gate_w", "up_w", "down_w")]
+
+
+class _MllamaLMWeights(C.Structure):  # mme_mllama_lm_weights
+    _fields_ = [(n, C.c_int32) for n in ("hidden", "heads", "kv_heads", "intermediate", "layers", "vocab", "vision_dim", "image_token_id", "hidden_act",
+                                         "rope_type", "rope_original_max")] + [
+        (n, C.c_float) for n in ("rms_eps", "rope_theta", "rope_factor", "rope_low_freq_factor", "rope_high_freq_factor")] + [
+        (n, C.POINTER(C.c_float)) for n in ("embed_tokens", "norm", "proj_w", "proj_b")] + [("layer", C.POINTER(_MllamaLMLayer))]
+
+
+class _MllamaApplyArgs(C.Structure):  # mme_mllama_apply_args
+    _fields_ = [(n, C.c_void_p) for n in ("tok", "ids_host", "len_host", "xmask_host", "x", "y", "kv", "w", "cos", "sin", "rowzero", "emb_f32", "emb_bf16")] + [
+        ("rows", C.c_int64), ("ld", C.c_int64)] + [(n, C.c_int32) for n in ("n", "S", "d", "heads", "kv_heads", "col0", "vocab", "tiles", "tokens")] + [
+        ("eps", C.c_float)]
+
+
 class _GemmApplyArgs(C.Structure):  # mme_gemm_apply_args
     _fields_ = [
         ("epilogue", C.c_int32), ("variant", C.c_int32), ("reverse_m", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
@@ -336,6 +354,14 @@ EXPORTS = {
     "mme_load_tile_vit_as": (C.c_int, [C.c_void_p, C.POINTER(_TileWeights), C.c_int, C.c_void_p]),
     "mme_tile_vit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mme_tile_rowop_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_TileRowopApplyArgs), C.c_void_p]),
+    "mme_load_mllama_lm": (C.c_int, [C.c_void_p, C.POINTER(_MllamaLMWeights)]),
+    "mme_load_mllama_lm_as": (C.c_int, [C.c_void_p, C.POINTER(_MllamaLMWeights), C.c_int, C.c_void_p]),
+    "mme_mllama_lm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mme_mllama_lm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "mme_mllama_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "mme_mllama_apply": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_MllamaApplyArgs), C.c_void_p]),
     "mme_comm_unique_id": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mme_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mme_comm_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -541,6 +567,15 @@ def _dinov2_special(get, extra):
     return {"pos": C.cast(C.c_void_p(table.data_ptr()), C.POINTER(C.c_float))}, table
 
 
+def _mllama_lm_special(get, extra):
+    """The gates of the cross layers travel as numbers: gate(name) reads the checkpoint's (or the dict's) one-element tensor."""
+    def gate(name):
+        t = get(name)
+        return float(t.float().reshape(-1)[0]) if hasattr(t, "float") else float(np.asarray(t).reshape(-1)[0])
+
+    return {"gate": gate}, None
+
+
 def _clip_text_scalars(W, geom):
     W.hidden, W.layers, W.heads, W.mlp, W.vocab, W.max_positions = (geom.hidden_size, geom.num_layers, geom.num_heads, geom.intermediate_size,
                                                                    geom.vocab_size, geom.max_position_embeddings)
@@ -641,8 +676,8 @@ class Engine:
         from .encoders import ENCODER_TABLE
 
         rec = ENCODER_TABLE[kind]
-        if rec.block is None:
-            return Engine._tile_struct(geom, arr, **special)
+        if rec.block is None:  # the two Mllama towers keep their own builders
+            return (Engine._mllama_lm_struct if kind == "mllama_text" else Engine._tile_struct)(geom, arr, **special)
         W = rec.struct()
         rec.scalars(W, geom, **special)
         layers = (_Layer * max(0, int(geom.num_layers)))()
@@ -974,6 +1009,176 @@ class Engine:
         W, layers = self._tile_struct(geom, arr, gate)
         self._check(self.lib.mme_load_tile_vit_as(self.h, C.byref(W), int(ckpt.dtype_id), self._stream()), "mme_load_tile_vit_as")
         self.tile_features = geom.output_dim
+
+    # ---- Mllama language tower (mme_load_mllama_lm*): lives beside the tile tower of the same context ----------------------
+    @staticmethod
+    def _mllama_lm_struct(geom, arr, gate=None):
+        """mme_mllama_lm_weights (+ its layer array, which the caller keeps alive) for a weights.MllamaLMGeometry: tensor
+        pointers from arr(name), the scalar gates from gate(name) -- by default the first f32 behind arr(name) --; names as
+        weights.mllama_lm_tensor_specs."""
+        from .weights import MLLAMA_ROPE_TYPES
+
+        if gate is None:
+            def gate(name):
+                p = arr(name)
+                return float(p[0]) if p else 0.0
+
+        n_layers = max(0, int(geom.num_layers))
+        cross = set(geom.cross_layers)
+        layers = (_MllamaLMLayer * n_layers)()
+        for i in range(n_layers):
+            p = f"language_model.layers.{i}."
+            a = p + ("cross_attn." if i in cross else "self_attn.")
+            X = layers[i]
+            X.cross = int(i in cross)
+            X.ln1, X.ln2 = arr(p + "input_layernorm.weight"), arr(p + "post_attention_layernorm.weight")
+            X.q_w, X.k_w, X.v_w, X.o_w = (arr(a + f"{n}_proj.weight") for n in "qkvo")
+            if i in cross:
+                X.q_norm, X.k_norm = arr(a + "q_norm.weight"), arr(a + "k_norm.weight")
+                X.attn_gate, X.mlp_gate = gate(p + "cross_attn_attn_gate"), gate(p + "cross_attn_mlp_gate")
+            X.gate_w, X.up_w, X.down_w = (arr(p + f"mlp.{n}_proj.weight") for n in ("gate", "up", "down"))
+        W = _MllamaLMWeights()
+        W.hidden, W.heads, W.kv_heads, W.intermediate, W.layers = geom.hidden_size, geom.num_heads, geom.num_kv_heads, geom.intermediate_size, geom.num_layers
+        W.vocab, W.vision_dim, W.image_token_id = geom.vocab_size, geom.vision_output_dim, geom.image_token_id
+        W.hidden_act = 0 if geom.hidden_act == "silu" else -1
+        W.rope_type = MLLAMA_ROPE_TYPES.index(geom.rope_type) if geom.rope_type in MLLAMA_ROPE_TYPES else -1
+        W.rope_original_max = int(geom.rope_original_max)
+        W.rms_eps, W.rope_theta, W.rope_factor = float(geom.rms_norm_eps), float(geom.rope_theta), float(geom.rope_factor)
+        W.rope_low_freq_factor, W.rope_high_freq_factor = float(geom.rope_low_freq_factor), float(geom.rope_high_freq_factor)
+        W.embed_tokens, W.norm = arr("language_model.embed_tokens.weight"), arr("language_model.norm.weight")
+        W.proj_w, W.proj_b = arr("multi_modal_projector.weight"), arr("multi_modal_projector.bias")
+        W.layer = layers
+        return W, layers
+
+    def load_mllama_lm(self, w: dict, geom=None):
+        """`weights.mllama_lm_tensor_specs` dict of f32 arrays (the language model and projector of transformers'
+        MllamaForConditionalGeneration, names without `model.`) -> the language tower of this context; the context's other
+        towers stay.  `geom`: a weights.MllamaLMGeometry; by default read off the tensor shapes."""
+        from .weights import infer_mllama_lm_geometry, mllama_lm_tensor_specs
+
+        geom = geom or infer_mllama_lm_geometry(w)
+        if 0 < geom.num_layers <= 64:
+            for name, shape, _, _ in mllama_lm_tensor_specs(geom):
+                if name not in w:
+                    raise MmeError(f"load_mllama_lm: tensor {name!r} is missing")
+                if int(np.prod(np.shape(w[name]))) != int(np.prod(shape)):
+                    raise MmeError(f"load_mllama_lm: tensor {name!r} has shape {tuple(np.shape(w[name]))}, expected {tuple(shape)}")
+        keep = []
+
+        def arr(name):
+            a = np.ascontiguousarray(w[name], dtype=np.float32).reshape(-1)
+            keep.append(a)
+            return _fp(a)
+
+        W, layers = self._mllama_lm_struct(geom, arr, lambda name: float(np.asarray(w[name]).reshape(-1)[0]))
+        self._check(self.lib.mme_load_mllama_lm(self.h, C.byref(W)), "mme_load_mllama_lm")
+
+    def load_mllama_lm_tensors(self, tensors: dict, geom, dtype_id: int):
+        """Contiguous host torch tensors of ONE dtype (MME_DT_* code `dtype_id`) under the canonical names -> the language tower,
+        prepared on the device bit-identically to `load_mllama_lm` on the same values (mme_load_mllama_lm_as)."""
+        def arr(name):
+            t = tensors[name]
+            if not t.is_contiguous() or t.device.type != "cpu":
+                raise MmeError(f"checkpoint tensor {name!r} must be a contiguous host tensor")
+            return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_float))
+
+        W, layers = self._mllama_lm_struct(geom, arr, lambda name: float(tensors[name].float().reshape(-1)[0]))
+        self._check(self.lib.mme_load_mllama_lm_as(self.h, C.byref(W), int(dtype_id), self._stream()), "mme_load_mllama_lm_as")
+
+    def load_mllama_lm_checkpoint(self, ckpt):
+        """`checkpoint.read_checkpoint(dir, "mllama_text")` -> the language tower of this context, prepared on the device
+        bit-identically to `load_mllama_lm` on the same values."""
+        self._load_checkpoint("mllama_text", ckpt)
+
+    def mllama_lm_info(self) -> dict:
+        """The loaded language tower's geometry as the library holds it (mme_mllama_lm_info); `loaded` False before a load."""
+        out = (C.c_int32 * 12)()
+        self._check(self.lib.mme_mllama_lm_info(self.h, out), "mme_mllama_lm_info")
+        keys = ("loaded", "hidden_size", "num_heads", "num_kv_heads", "intermediate_size", "num_layers", "num_cross_layers", "vocab_size",
+                "vision_output_dim", "image_token_id", "rope_type", "first_buffer")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["loaded"] = bool(d["loaded"])
+        return d
+
+    @staticmethod
+    def _mllama_sequences(ids, lengths, xmask):
+        ids = np.ascontiguousarray(np.asarray(ids), dtype=np.int32)
+        if ids.ndim != 2:
+            raise MmeError("the ids must be int32 [n, S]")
+        n, S = ids.shape
+        lens = np.full(n, S, dtype=np.int32) if lengths is None else np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int32)
+        if lens.shape[0] != n:
+            raise MmeError(f"{lens.shape[0]} lengths for {n} sequences")
+        xm = None
+        if xmask is not None:
+            xm = np.ascontiguousarray(np.asarray(xmask), dtype=np.uint8)
+            if xm.shape != (n, S):
+                raise MmeError(f"xmask must be uint8 [n, S] = {(n, S)}, got {xm.shape}")
+        return ids, lens, xm, n, S
+
+    def mllama_lm_forward(self, ids, lengths=None, vision=None, num_tiles=None, xmask=None, want_f32: bool = True, want_bf16: bool = True):
+        """ids int32 [n, S] (+ attended lengths [n], right padding; default S) -> (emb f32 [n, hidden] | None, emb bf16 | None).
+        vision: bf16 CUDA [n, tiles, tokens, vision_dim], the vision model's last_hidden_state, or None for the text-only path;
+        num_tiles [n] and / or xmask uint8 [n, S] (attended tiles as bits) as mme_mllama_lm_forward reads them."""
+        t = self.torch
+        ids, lens, xm, n, S = self._mllama_sequences(ids, lengths, xmask)
+        D = self.mllama_lm_info()["hidden_size"]
+        dev = t.device("cuda", self.device)
+        tiles = tokens = 0
+        nt = None
+        if vision is not None:
+            if vision.dtype != t.bfloat16 or vision.dim() != 4 or vision.shape[0] != n or not vision.is_cuda:
+                raise MmeError("mllama_lm_forward: vision must be a bf16 CUDA tensor [n, tiles, tokens, vision_dim]")
+            vision = vision.contiguous()
+            tiles, tokens = int(vision.shape[1]), int(vision.shape[2])
+            if num_tiles is not None:
+                nt = np.ascontiguousarray(np.asarray(num_tiles).reshape(-1), dtype=np.int32)
+        e32 = t.empty((n, D), dtype=t.float32, device=dev) if want_f32 else None
+        e16 = t.empty((n, D), dtype=t.bfloat16, device=dev) if want_bf16 else None
+        self._check(self.lib.mme_mllama_lm_forward(self.h, ids.ctypes.data, lens.ctypes.data, n, S, self._ptr(vision), tiles, tokens,
+                                                   nt.ctypes.data if nt is not None else None, xm.ctypes.data if xm is not None else None,
+                                                   self._ptr(e32), self._ptr(e16), self._stream()), "mme_mllama_lm_forward")
+        return e32, e16
+
+    def mllama_embed(self, pixel_values, aspect_ratio_ids, num_tiles, ids, lengths=None, xmask=None, want_f32: bool = True, want_bf16: bool = True):
+        """pixel_values f32 CUDA [n, 4, 3, 560, 560] (+ ids / tile counts, as `preprocess_tiles` returns them) and the prompt ids
+        int32 [n, S] -> the tile tower, the projector and the language tower -> (emb f32 [n, hidden] | None, emb bf16 | None)."""
+        t = self.torch
+        pv = pixel_values.contiguous()
+        if pv.dtype != t.float32 or tuple(pv.shape[1:]) != (4, 3, 560, 560):
+            raise MmeError("mllama_embed: pixel_values must be f32 [n, 4, 3, 560, 560]")
+        ids, lens, xm, n, S = self._mllama_sequences(ids, lengths, xmask)
+        if pv.shape[0] != n:
+            raise MmeError(f"mllama_embed: {pv.shape[0]} images for {n} sequences")
+        aid = np.ascontiguousarray(np.asarray(aspect_ratio_ids).reshape(-1), dtype=np.int32)
+        nt = np.ascontiguousarray(np.asarray(num_tiles).reshape(-1), dtype=np.int32)
+        D = self.mllama_lm_info()["hidden_size"]
+        e32 = t.empty((n, D), dtype=t.float32, device=pv.device) if want_f32 else None
+        e16 = t.empty((n, D), dtype=t.bfloat16, device=pv.device) if want_bf16 else None
+        self._check(self.lib.mme_mllama_embed(self.h, pv.data_ptr(), aid.ctypes.data, nt.ctypes.data, n, ids.ctypes.data, lens.ctypes.data, S,
+                                              xm.ctypes.data if xm is not None else None, self._ptr(e32), self._ptr(e16), self._stream()), "mme_mllama_embed")
+        return e32, e16
+
+    MLLAMA_OPS = {"gather": 0, "rmsnorm": 1, "headnorm": 2, "rope": 3, "silu_mul": 4, "pool": 5, "self_attn": 6, "cross_attn": 7}
+
+    def mllama_apply(self, op, *, tok=None, ids=None, lengths=None, xmask=None, x=None, y=None, kv=None, w=None, cos=None, sin=None, rowzero=None,
+                     emb_f32=None, emb_bf16=None, rows: int = 0, ld: int = 0, n: int = 0, S: int = 0, d: int = 0, heads: int = 0, kv_heads: int = 0,
+                     col0: int = 0, vocab: int = 0, tiles: int = 0, tokens: int = 0, eps: float = 1e-5):
+        """ONE launch of a kernel of the language tower on the caller's CUDA tensors (mme_mllama_apply; synchronous).  op: a name
+        of MLLAMA_OPS or its code; ids / lengths (int32) and xmask (uint8) are host arrays.  The library validates."""
+        a = _MllamaApplyArgs()
+        keep = []
+        for fld, v, dt in (("ids_host", ids, np.int32), ("len_host", lengths, np.int32), ("xmask_host", xmask, np.uint8)):
+            if v is not None:
+                h = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=dt)
+                keep.append(h)
+                setattr(a, fld, h.ctypes.data)
+        a.tok, a.x, a.y, a.kv, a.w, a.cos, a.sin, a.rowzero, a.emb_f32, a.emb_bf16 = (
+            self._ptr(t) for t in (tok, x, y, kv, w, cos, sin, rowzero, emb_f32, emb_bf16))
+        a.rows, a.ld = int(rows), int(ld)
+        a.n, a.S, a.d, a.heads, a.kv_heads, a.col0, a.vocab, a.tiles, a.tokens = (int(v) for v in (n, S, d, heads, kv_heads, col0, vocab, tiles, tokens))
+        a.eps = float(eps)
+        self._check(self.lib.mme_mllama_apply(self.h, int(self.MLLAMA_OPS.get(op, op)), C.byref(a), self._stream()), "mme_mllama_apply")
 
     def weights_fingerprint(self) -> tuple:
         """One 64-bit checksum per prepared weight buffer of this context, in creation order (mme_weights_fingerprint):

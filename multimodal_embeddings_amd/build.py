@@ -21,8 +21,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(PKG, "libmme.so")
-SOURCES = ["gemm.hip", "gemm256r.hip", "gemm384r.hip", "rowops.hip", "attention.hip", "preprocess.hip", "preprocess_clip.hip", "page_reduce.hip", "cluster.hip", "neighbours.hip", "launch_state.hip", "comm.hip", "nms.hip", "attention_tiles.hip", "tilevit.hip", "weight_prep.hip", "weight_load.hip", "encoder_pass.hip", "capi.hip", "image_tower.hip", "capi_tilevit.hip", "text_tower.hip", "attention_short.hip", "capi_text.hip", "patch32.hip", "siglip.hip", "dinov2.hip", "attention_mid.hip", "duplicates.hip", "capi_duplicates.hip", "lanczos.hip", "capi_lanczos.hip", "kmeans.hip", "capi_kmeans.hip", "silhouette.hip", "pooling.hip", "projection.hip", "capi_projection.hip", "density.hip", "capi_density.hip", "hierarchy.hip", "capi_hierarchy.hip"]
-HEADERS = ["common.h", "layouts.h", "kernels.h", "row_kernels.h", "attention_common.h", "gemm_epilogue.h", "gemm_tiles.h", "ctx.h", "encoder_pass.h", "duplicates.h", "kmeans.h", "lanczos.h", "resample.h", "k1_plan.h", "projection.h", "union_find.h", "density.h", "hierarchy.h", os.path.join("..", "..", "include", "mme.h")]
+SOURCES = ["gemm.hip", "gemm256r.hip", "gemm384r.hip", "rowops.hip", "attention.hip", "preprocess.hip", "preprocess_clip.hip", "page_reduce.hip", "cluster.hip", "neighbours.hip", "launch_state.hip", "comm.hip", "nms.hip", "attention_tiles.hip", "tilevit.hip", "weight_prep.hip", "weight_load.hip", "encoder_pass.hip", "capi.hip", "image_tower.hip", "capi_tilevit.hip", "text_tower.hip", "attention_short.hip", "capi_text.hip", "patch32.hip", "siglip.hip", "dinov2.hip", "attention_mid.hip", "duplicates.hip", "capi_duplicates.hip", "lanczos.hip", "capi_lanczos.hip", "kmeans.hip", "capi_kmeans.hip", "silhouette.hip", "pooling.hip", "projection.hip", "capi_projection.hip", "density.hip", "capi_density.hip", "hierarchy.hip", "capi_hierarchy.hip", "mllama_lm.hip", "capi_mllama.hip"]
+HEADERS = ["common.h", "layouts.h", "kernels.h", "row_kernels.h", "attention_common.h", "gemm_epilogue.h", "gemm_tiles.h", "ctx.h", "encoder_pass.h", "duplicates.h", "kmeans.h", "lanczos.h", "resample.h", "k1_plan.h", "projection.h", "union_find.h", "density.h", "hierarchy.h", "mllama_lm.h", os.path.join("..", "..", "include", "mme.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

@@ -37,7 +37,7 @@ from .weights import (CLIP_B16, CLIP_TEXT_B, DINOV2_B14, SIGLIP_B16, SIGLIP_LOGI
 
 logger = logging.getLogger("multimodal_embeddings_amd")
 
-ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip", "siglip_text", "dinov2")
+ENCODERS = ("vit_b16", "vit", "clip", "mllama_tiles", "clip_text", "siglip", "siglip_text", "dinov2", "mllama_text")
 # The command line below and RegionEmbedder spell the SigLIP tower "siglip_vit": both have always refused the bare name
 # "siglip" as an unknown encoder and keep doing so; read_checkpoint, Checkpoint.encoder and the Engine say "siglip".
 SIGLIP_ALIAS = "siglip_vit"
@@ -196,6 +196,22 @@ def canonical_tile_name(key: str):
     if key.startswith(("model.", "language_model.", "multi_modal_projector.", "lm_head.")):
         return None
     return key
+
+
+def canonical_mllama_lm_name(key: str):
+    """Checkpoint key -> canonical name (weights.mllama_lm_tensor_specs: `language_model.…`, `multi_modal_projector.…`), or None for
+    a key outside the language tower and the projector.  transformers 5 spells the tensors `model.language_model.…` and
+    `model.multi_modal_projector.…`; checkpoints saved by 4.4x (mmE5's) `language_model.model.…` and `multi_modal_projector.…`.
+    `lm_head` is not read."""
+    if key.startswith("model."):
+        key = key[len("model."):]
+    if key.startswith("language_model.model."):
+        return "language_model." + key[len("language_model.model."):]
+    if key.startswith("language_model.lm_head.") or key.startswith("lm_head."):
+        return None
+    if key.startswith(("language_model.", "multi_modal_projector.")):
+        return key
+    return None
 
 
 # ---- configuration ------------------------------------------------------------------------------------------------------
@@ -368,6 +384,39 @@ def _tile_geometry(cfg: dict, path: str):
     return TileViTGeometry(num_layers=int(cfg["num_hidden_layers"]), num_global_layers=int(cfg["num_global_layers"]),
                            intermediate_layers=tuple(int(v) for v in cfg["intermediate_layers_indices"]),
                            norm_eps=float(cfg.get("norm_eps", g.norm_eps))), where
+
+
+def _mllama_lm_geometry(cfg: dict, path: str):
+    """text_config of a whole Mllama model (+ vision_config.vision_output_dim and image_token_index) -> MllamaLMGeometry.  The
+    rotary parameters are `rope_parameters` (transformers 5) or `rope_scaling` + `rope_theta` (4.4x)."""
+    from .weights import MLLAMA_LM_11B, MllamaLMGeometry, mllama_lm_geometry_problem
+
+    b = MLLAMA_LM_11B
+    if "text_config" not in cfg:
+        raise MmeError("config.json: text_config is missing (supported: the config of a whole MllamaForConditionalGeneration)")
+    t, where = dict(cfg["text_config"]), "config.json: text_config"
+    v = _ints(t, where, {"hidden_size": b.hidden_size, "num_attention_heads": b.num_heads, "num_key_value_heads": b.num_kv_heads,
+                         "intermediate_size": b.intermediate_size, "num_hidden_layers": b.num_layers, "vocab_size": b.vocab_size})
+    rope = dict(t.get("rope_parameters") or t.get("rope_scaling") or {})
+    rope_type = rope.get("rope_type", rope.get("type", "default"))
+    theta = rope.get("rope_theta", t.get("rope_theta", b.rope_theta))
+    vision = _ints(dict(cfg.get("vision_config") or {}), "config.json: vision_config", {"vision_output_dim": b.vision_output_dim})
+    top = _ints(cfg, "config.json", {"image_token_index": v["vocab_size"]})
+    cross = t.get("cross_attention_layers", list(b.cross_attention_layers))
+    if not isinstance(cross, (list, tuple)) or not all(isinstance(i, int) and not isinstance(i, bool) for i in cross):
+        raise MmeError(f"{where}: cross_attention_layers = {cross!r}; a list of integers is required")
+    g = MllamaLMGeometry(hidden_size=v["hidden_size"], num_heads=v["num_attention_heads"], num_kv_heads=v["num_key_value_heads"],
+                         intermediate_size=v["intermediate_size"], num_layers=v["num_hidden_layers"], cross_attention_layers=tuple(cross),
+                         vocab_size=v["vocab_size"], vision_output_dim=vision["vision_output_dim"], image_token_id=top["image_token_index"],
+                         rms_norm_eps=float(t.get("rms_norm_eps", b.rms_norm_eps)), hidden_act=t.get("hidden_act", b.hidden_act), rope_type=rope_type,
+                         rope_theta=float(theta), rope_factor=float(rope.get("factor", b.rope_factor)),
+                         rope_low_freq_factor=float(rope.get("low_freq_factor", b.rope_low_freq_factor)),
+                         rope_high_freq_factor=float(rope.get("high_freq_factor", b.rope_high_freq_factor)),
+                         rope_original_max=int(rope.get("original_max_position_embeddings", b.rope_original_max)))
+    bad = mllama_lm_geometry_problem(g)
+    if bad:
+        raise MmeError(f"{where}: {bad}")
+    return g, where
 
 
 RESIZE_RULES = ("fit_pad", "clip")  # _lib.Engine.RESIZE_RULES / MME_RESIZE_* (include/mme.h)
@@ -759,6 +808,19 @@ def _tile_config(g, dtype, weights):
             "hidden_act": "gelu", "max_num_tiles": g.max_num_tiles, "supported_aspect_ratios": SUPPORTED_ASPECT_RATIOS,
             "num_hidden_layers": g.num_layers, "num_global_layers": g.num_global_layers,
             "intermediate_layers_indices": list(g.intermediate_layers), "norm_eps": g.norm_eps, "dtype": dtype}
+
+
+def _mllama_lm_config(g, dtype, weights):
+    rope = {"rope_type": g.rope_type, "rope_theta": g.rope_theta}
+    if g.rope_type == "llama3":
+        rope.update({"factor": g.rope_factor, "low_freq_factor": g.rope_low_freq_factor, "high_freq_factor": g.rope_high_freq_factor,
+                     "original_max_position_embeddings": g.rope_original_max})
+    return {"architectures": ["MllamaForConditionalGeneration"], "model_type": "mllama", "image_token_index": g.image_token_id, "dtype": dtype,
+            "text_config": {"model_type": "mllama_text_model", "hidden_size": g.hidden_size, "num_attention_heads": g.num_heads,
+                            "num_key_value_heads": g.num_kv_heads, "intermediate_size": g.intermediate_size, "num_hidden_layers": g.num_layers,
+                            "cross_attention_layers": list(g.cross_layers), "vocab_size": g.vocab_size, "rms_norm_eps": g.rms_norm_eps,
+                            "hidden_act": g.hidden_act, "rope_parameters": rope},
+            "vision_config": {"vision_output_dim": g.vision_output_dim}}
 
 
 def save_checkpoint(path, weights: dict, encoder: str = "vit_b16", dtype: str = "float32", geometry=None, image_mean=None, image_std=None,

@@ -294,6 +294,7 @@ void mme_destroy(mme_ctx* c) {
     if (c->lut) (void)hipFree(c->lut);
     tile_vit_free(c);
     text_free(c);
+    mllama_free(c);
     for (auto& ev : c->events) {
         (void)hipEventDestroy(ev.a);
         (void)hipEventDestroy(ev.b);

@@ -198,7 +198,7 @@ int load_text(mme_ctx* c, const TextW* w, P p, const char* who) {
     TextDev* t = c->text;
     t->loaded = false;
     if (c->text_alloc_hi > c->text_alloc_lo) HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
-    release_alloc_range(c, c->text_alloc_lo, c->text_alloc_hi, c->vit_alloc_lo, c->vit_alloc_hi);
+    release_alloc_range(c, c->text_alloc_lo, c->text_alloc_hi);
     t->hidden = w->hidden; t->layers = w->layers; t->heads = w->heads; t->mlp = w->mlp; t->vocab = w->vocab;
     t->proj_dim = w->proj_dim; t->act = w->act; t->eos = w->eos; t->eps = w->ln_eps;
     t->kind = w->kind; t->tokens = w->tokens; t->causal = w->kind == TEXT_CLIP; t->pool_last = w->kind == TEXT_SIGLIP; t->pad = w->eos;

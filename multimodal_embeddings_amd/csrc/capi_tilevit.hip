@@ -38,6 +38,16 @@ void tile_vit_free(mme_ctx* c) {
     c->tv = nullptr;
 }
 
+int tile_vit_states(mme_ctx* c, const char* who, const void** x, const void** inter, int* ni, int64_t* inter_stride) {
+    if (!c->tv) return fail(c, MME_E_STATE, "%s: call mme_load_tile_vit first", who);
+    const TileVitDev* t = c->tv;
+    *x = t->x.p;
+    *inter = t->ni ? t->inter.p : nullptr;
+    *ni = t->ni;
+    *inter_stride = (int64_t)t->ws_images * TT * TD;
+    return MME_OK;
+}
+
 namespace {
 
 int validate_tile_weights(mme_ctx* c, const mme_tile_vit_weights* w) {

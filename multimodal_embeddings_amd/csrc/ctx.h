@@ -64,6 +64,7 @@ struct EventPair {
 
 struct TileVitDev;  // capi_tilevit.hip
 struct TextDev;     // capi_text.hip
+struct MllamaDev;   // capi_mllama.hip
 
 struct mme_ctx {
     int device = 0;
@@ -129,21 +130,26 @@ struct mme_ctx {
     // CLIP text tower (capi_text.hip): coexists with the image tower; allocs[text_alloc_lo, text_alloc_hi) are its weights
     TextDev* text = nullptr;
     size_t text_alloc_lo = 0, text_alloc_hi = 0;
+    // Mllama language tower (capi_mllama.hip): coexists with every other tower; allocs[mllama_alloc_lo, mllama_alloc_hi) are its weights
+    MllamaDev* mllama = nullptr;
+    size_t mllama_alloc_lo = 0, mllama_alloc_hi = 0;
 };
 
-// Frees allocs[lo, hi) (the caller has drained the device) and takes them out of the tables; `other_lo / other_hi`, the
-// range of the tower that stays, moves down with its buffers when it sits behind.  Afterwards lo == hi == allocs.size():
-// the buffers the load creates next are the new range.
-inline void release_alloc_range(mme_ctx* c, size_t& lo, size_t& hi, size_t& other_lo, size_t& other_hi) {
-    const size_t n = hi - lo;
+// Frees allocs[lo, hi) (the caller has drained the device) and takes them out of the tables; every other tower's range (the
+// ViT's, the text tower's, the Mllama language tower's) moves down with its buffers when it sits behind.  Afterwards
+// lo == hi == allocs.size(): the buffers the load creates next are the new range.
+inline void release_alloc_range(mme_ctx* c, size_t& lo, size_t& hi) {
+    const size_t n = hi - lo, end = hi;
     if (n) {
         for (size_t i = lo; i < hi; ++i) (void)hipFree(c->allocs[i]);
         c->allocs.erase(c->allocs.begin() + lo, c->allocs.begin() + hi);
         c->alloc_bytes.erase(c->alloc_bytes.begin() + lo, c->alloc_bytes.begin() + hi);
-        if (other_lo >= hi) {
-            other_lo -= n;
-            other_hi -= n;
-        }
+        size_t* ranges[3][2] = {{&c->vit_alloc_lo, &c->vit_alloc_hi}, {&c->text_alloc_lo, &c->text_alloc_hi}, {&c->mllama_alloc_lo, &c->mllama_alloc_hi}};
+        for (auto& r : ranges)
+            if (r[0] != &lo && *r[0] >= end) {
+                *r[0] -= n;
+                *r[1] -= n;
+            }
     }
     lo = hi = c->allocs.size();
 }
@@ -217,6 +223,10 @@ inline float f32_quiet_nan(float f) {
 }
 void tile_vit_free(mme_ctx* c);
 void text_free(mme_ctx* c);  // the text tower's record and workspace (its weights are in c->allocs)
+void mllama_free(mme_ctx* c);  // the Mllama language tower's record and workspace (its weights are in c->allocs)
+// the tile tower's states after a pass of <= 64 images (capi_tilevit.hip): x and the ni intermediate states, bf16 rows of 1280
+// padded to 1608 per tile; MME_E_STATE in `who`'s name without a tile tower
+int tile_vit_states(mme_ctx* c, const char* who, const void** x, const void** inter, int* ni, int64_t* inter_stride);
 
 // ---- weight loading (weight_load.hip) ---------------------------------------------------------------------------------
 // Each encoder's load is ONE sequence of prepared buffers (prepare_vit in weight_load.hip, prepare_tile in

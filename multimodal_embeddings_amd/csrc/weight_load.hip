@@ -287,7 +287,7 @@ int begin_vit_load(mme_ctx* c, const mme_vit_weights* w) {
     c->pool_mode = MME_POOL_TOKEN;  // mme_set_pooling holds until the next load
     if (c->vit_alloc_hi > c->vit_alloc_lo) HIP_TRY(c, hipDeviceSynchronize());  // a pass in flight still reads them
     // exactly the image tower's buffers; a text tower loaded behind them keeps its own, its range moves down with them
-    release_alloc_range(c, c->vit_alloc_lo, c->vit_alloc_hi, c->text_alloc_lo, c->text_alloc_hi);
+    release_alloc_range(c, c->vit_alloc_lo, c->vit_alloc_hi);
     c->geom = VitGeom{w->hidden, w->layers, w->heads, w->mlp, w->patch_size, w->cls_token == nullptr};  // no class token: SigLIP only (validated)
     c->ln_eps = w->ln_eps;
     c->layer.assign((size_t)w->layers, LayerDev{});

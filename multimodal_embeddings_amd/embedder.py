@@ -182,7 +182,7 @@ class RegionEmbedder:
     def __init__(self, model_name=config.DEFAULT_MODEL_NAME, device=None, gpu_count=None, *, weights=None,
                  seed: int = 1, pool: str = "cls", chunk: int | None = None, engine: Engine | None = None, devices=None,
                  encoder: str = "vit_b16", geometry=None, prune_last_layer: bool | None = None, allow_synthetic: bool = True,
-                 resize_rule: str | None = None, text_tower=None, tokenizer=None):
+                 resize_rule: str | None = None, text_tower=None, tokenizer=None, lm_geometry=None, prompt_ids=None):
         """`model_name`: a LOCAL checkpoint directory (config.json + model.safetensors | shards | pytorch_model.bin, optionally
         preprocessor_config.json) is read once (checkpoint.read_checkpoint), loaded into every context in the file's own dtype
         and its image_mean / image_std applied; `self.checkpoint` keeps it.  Any other name is never fetched: the encoder runs
@@ -220,7 +220,15 @@ class RegionEmbedder:
         a SiglipTextModel directory): True beside seeded or caller's image weights seeds a tower of the image tower's width
         (SIGLIP_TEXT_B at 768); its projection must equal `embed_dim`.  None beside seeded or vision-only weights loads nothing.
         `tokenizer`: a callable str -> list[int] or a transformers tokenizer; by default transformers' CLIPTokenizer is read
-        from the tower's directory on first use (local files only).  Token ids need no tokenizer."""
+        from the tower's directory on first use (local files only).  Token ids need no tokenizer.
+        encoder="mllama": the tile tower of "mllama_tiles" AND the Mllama language tower with cross-attention in
+        every context: images are embedded through both under the prompt `prompt_ids` (token ids, the image token among them;
+        by default `MLLAMA_PROMPT`, the reference's prompt, through `tokenizer=`), texts through the language tower
+        alone; `embed_dim` is the text hidden size.  Seeded weights take `geometry=` (a weights.TileViTGeometry) and
+        `lm_geometry=` (a weights.MllamaLMGeometry whose vision_output_dim is the tile tower's output width; default
+        weights.MLLAMA_LM_11B); a checkpoint directory of MllamaForConditionalGeneration (mmE5's) brings both towers, the
+        projector and, where it holds tokenizer files, the tokenizer (local files only).  A str prompt or query needs a
+        tokenizer; without one only token ids are taken."""
         import torch
 
         from .checkpoint import check_resize_rule, read_checkpoint, resolve_model_source
@@ -229,6 +237,11 @@ class RegionEmbedder:
         self.torch = torch
         self.model_name = model_name
         self.checkpoint = None
+        self.mllama_lm = encoder == "mllama"
+        if self.mllama_lm:  # the image side is the tile tower; the language tower is loaded beside it below
+            encoder = "mllama_tiles"
+        elif lm_geometry is not None or prompt_ids is not None:
+            raise ValueError("lm_geometry= and prompt_ids= belong to encoder='mllama'")
         if encoder not in ("vit_b16", "vit", "clip", "siglip_vit", "dinov2", "mllama_tiles"):
             raise ValueError("encoder must be 'vit_b16' (BASELINE.json's re-scoped ViT-B/16), 'vit' (the ViT/16 family: ViT-S, -B and -L widths), "
                              "'clip' (a CLIP ViT/16 image tower of that family), 'siglip_vit' (a SigLIP ViT/16 image tower of that family), "
@@ -332,13 +345,91 @@ class RegionEmbedder:
         self.pool_token = (196 if encoder == "mllama_tiles" else self.engine.vit_geometry().seq_len - 1) if pool == "last" else 0
         # width of the returned vectors: the ViT's hidden size, the tile tower's concatenated features
         self.embed_dim = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)) if encoder == "mllama_tiles" else int(self.engine.embed_dim)
-        self._seed = seed
         self._tokenizer = tokenizer
+        if self.mllama_lm:  # may replace self._tokenizer by the directory's own
+            self._load_mllama_lm(engine is None, weights, seed, lm_geometry, prompt_ids, tokenizer)
+        self._seed = seed
         self._text_source = text_tower  # None: look in model_name on first use; False: never
         self._text_dir = None           # where a default tokenizer is looked for
         self._text_loaded = False
         if text_tower is not None and text_tower is not False:
             self._load_text_tower()
+
+    MLLAMA_PROMPT = "<|image|><|begin_of_text|> Represent the given image."  # the reference's prompt (embedder.py:108); the tokenizer puts its BOS in front
+
+    def _load_mllama_lm(self, own_engines, weights, seed, lm_geometry, prompt_ids, tokenizer):
+        """The language tower of encoder='mllama' into every context this object made (a caller's engine brings its own), the
+        prompt of the image path as ids, and `embed_dim` = the text hidden size."""
+        from .weights import MLLAMA_LM_11B, make_mllama_lm_weights
+
+        self._tokenizer = tokenizer
+        if own_engines and self.checkpoint is not None:  # one directory holds both towers and the projector
+            from .checkpoint import read_checkpoint
+
+            self.lm_checkpoint = read_checkpoint(self.model_name, "mllama_text")
+            if self.lm_checkpoint.geometry.vision_output_dim != int(getattr(self.engine, "tile_features", TILE_VIT.output_dim)):
+                raise MmeError(f"{self.model_name}: vision_output_dim = {self.lm_checkpoint.geometry.vision_output_dim}, but the tile tower puts out "
+                               f"{self.engine.tile_features} features")
+            for e in self.engines:
+                e.load_mllama_lm_checkpoint(self.lm_checkpoint)
+            if tokenizer is None and any(os.path.exists(os.path.join(self.model_name, f)) for f in ("tokenizer.json", "tokenizer.model")):
+                from transformers import AutoTokenizer  # the directory's own tokenizer files, never fetched
+
+                self._tokenizer = AutoTokenizer.from_pretrained(self.model_name, local_files_only=True)
+        elif own_engines:
+            geom = lm_geometry or MLLAMA_LM_11B
+            features = int(getattr(self.engine, "tile_features", TILE_VIT.output_dim))
+            if geom.vision_output_dim != features:
+                raise ValueError(f"lm_geometry.vision_output_dim = {geom.vision_output_dim}; supported: the tile tower's output width {features}")
+            w = make_mllama_lm_weights(seed + 6, geom)
+            for e in self.engines:
+                e.load_mllama_lm(w, geom)
+        info = self.engine.mllama_lm_info()
+        if not info["loaded"]:
+            raise MmeError("encoder='mllama': the engine holds no language tower (Engine.load_mllama_lm)")
+        self._mllama_info = info
+        self.embed_dim = int(info["hidden_size"])
+        if prompt_ids is None:  # the reference's prompt, which only a tokenizer can turn into ids
+            prompt_ids = self.MLLAMA_PROMPT
+        self.prompt_ids = self._mllama_ids(prompt_ids, "prompt_ids")
+        if info["image_token_id"] not in self.prompt_ids:
+            raise ValueError(f"prompt_ids hold no image token (id {info['image_token_id']}): the image path needs one")
+
+    def _mllama_ids(self, item, what):
+        """A str through `tokenizer=`, or a 1-D sequence of token ids -> list[int], checked against the tower's table and 128 positions."""
+        if isinstance(item, str):
+            tok = getattr(self, "_tokenizer", None)
+            if tok is None:
+                raise ValueError(f"{what}: a str needs tokenizer= (a callable str -> list[int] or a transformers tokenizer); without one pass "
+                                 "prompt_ids= / token ids")
+            out = tok(item)
+            item = out["input_ids"] if isinstance(out, dict) or hasattr(out, "input_ids") else out
+        a = np.asarray(item)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or not 1 <= a.shape[0] <= 128:
+            raise MmeError(f"{what}: token ids must be a 1-D integer sequence of 1..128 ids, got {a.dtype} {tuple(a.shape)}")
+        rows = self._mllama_info["vocab_size"] + 8
+        if a.min() < 0 or a.max() >= rows:
+            raise MmeError(f"{what}: ids outside 0..{rows - 1}")
+        return [int(v) for v in a]
+
+    def _mllama_text(self, text):
+        single = isinstance(text, str)
+        if not single:
+            a = text if isinstance(text, np.ndarray) else None
+            if a is None and isinstance(text, (list, tuple)) and len(text) and not isinstance(text[0], (str, list, tuple, np.ndarray)):
+                a = np.asarray(text)
+            single = a is not None and a.ndim == 1
+        items = [text] if single else list(text)
+        if not items:
+            return []
+        rows = [self._mllama_ids(it, "get_text_embeddings") for it in items]
+        S = max(len(r) for r in rows)
+        ids = np.zeros((len(rows), S), dtype=np.int32)  # right padding: under the causal mask it reaches no attended row
+        for i, r in enumerate(rows):
+            ids[i, : len(r)] = r
+        e32, _ = self.engines[0].mllama_lm_forward(ids, np.array([len(r) for r in rows], dtype=np.int32), want_bf16=False)
+        out = [[float(v) for v in r] for r in e32.cpu().numpy()]
+        return out[0] if single else out
 
     # -- device-resident API -------------------------------------------------------------------
     def pack(self, arrays, device=None):
@@ -572,7 +663,10 @@ class RegionEmbedder:
                             self._run_cap_jobs(engine, pix, jobs)
                             # processor (K1 multi-tile) + vision tower, class token of tile 0 (7680-d)
                             pv, ids, _, nt = engine.preprocess_tiles(pix, offs, hw, 560, 4)
-                            _, e32, _ = engine.tile_vit_forward(pv, ids, nt, want_bf16=False)
+                            if getattr(self, "mllama_lm", False):  # ... + projector + language tower under the prompt: the reference's 4096-d vector
+                                e32, _ = engine.mllama_embed(pv, ids, nt, np.tile(np.asarray(self.prompt_ids, dtype=np.int32), (len(idx), 1)), want_bf16=False)
+                            else:
+                                _, e32, _ = engine.tile_vit_forward(pv, ids, nt, want_bf16=False)
                         finally:
                             pipe["ev_done"][0].record(compute)  # the next group's H2D into the slot waits for this
                         results.extend(zip(idx, e32.cpu().tolist()))
@@ -782,6 +876,8 @@ class RegionEmbedder:
         a 2-D int array -> a list of such vectors.  Raises on failure, as the reference's does (embedder.py:228-254).
         NotImplementedError without a text tower."""
         engines = getattr(self, "engines", None)
+        if engines and getattr(self, "mllama_lm", False):  # the language tower without an image: the cross layers are skipped
+            return self._mllama_text(text)
         if not engines or getattr(self, "_text_source", False) is False:
             raise NotImplementedError(self._NO_TOWER)
         if not getattr(self, "_text_loaded", False):

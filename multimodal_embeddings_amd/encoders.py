@@ -117,5 +117,11 @@ ENCODER_TABLE = {
         top=_VIT_TOP, scalars=_lib._dinov2_scalars, after_read=ck._dinov2_position_grid,
         extra=lambda tensors: {"position_table": ck.interpolate_dinov2_positions(tensors[ck.DINOV2_POSITIONS])},
         host_geometry=_lib._dinov2_host_geometry, special=_lib._dinov2_special, library_refuses_depth=True),
+    # the Mllama language tower and projector: its own builder (Engine._mllama_lm_struct), as the tile tower; beside that tower in one directory
+    "mllama_text": Encoder(
+        geometry=wt.MLLAMA_LM_11B, tensor_specs=wt.mllama_lm_tensor_specs, make_weights=wt.make_mllama_lm_weights,
+        infer_geometry=wt.infer_mllama_lm_geometry, canonical_name=ck.canonical_mllama_lm_name, config_geometry=ck._mllama_lm_geometry,
+        config_json=ck._mllama_lm_config, struct=_lib._MllamaLMWeights, symbol="mme_load_mllama_lm", text=True, special=_lib._mllama_lm_special,
+        seed_offset=6),
 }
 assert tuple(ENCODER_TABLE) == ck.ENCODERS

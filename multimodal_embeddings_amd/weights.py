@@ -969,3 +969,176 @@ def make_tile_vit_weights(seed: int = 2, geom: TileViTGeometry = TILE_VIT, threa
     with ThreadPoolExecutor(max_workers=max(1, threads)) as ex:
         list(ex.map(fill, jobs))
     return out
+
+
+# ---- the reference's language tower: Mllama text model with cross-attention -----------------------
+MLLAMA_MAX_SEQ = 128  # positions of the library's rotary table (csrc/mllama_lm.h MLLAMA_MAX_S)
+MLLAMA_ROPE_TYPES = ("default", "llama3")  # include/mme.h mme_mllama_lm_weights.rope_type: the index
+
+
+@dataclass(frozen=True)
+class MllamaLMGeometry:
+    """`MllamaTextConfig` + the projector's input width, as intfloat/mmE5-mllama-11b-instruct configures them: 4096-d, 32 heads
+    of 128 over 8 KV heads, MLP 14336, 40 layers of which 3, 8, ..., 38 cross-attend the image, llama3 rotary frequencies.
+    `cross_attention_layers` may name indices at or beyond `num_layers` (a stack cut short keeps the tuple): they are ignored."""
+
+    hidden_size: int = 4096
+    num_heads: int = 32
+    num_kv_heads: int = 8
+    intermediate_size: int = 14336
+    num_layers: int = 40
+    cross_attention_layers: tuple = (3, 8, 13, 18, 23, 28, 33, 38)
+    vocab_size: int = 128256
+    vision_output_dim: int = 7680
+    image_token_id: int = 128256
+    rms_norm_eps: float = 1e-5
+    hidden_act: str = "silu"
+    rope_type: str = "llama3"
+    rope_theta: float = 500000.0
+    rope_factor: float = 8.0
+    rope_low_freq_factor: float = 1.0
+    rope_high_freq_factor: float = 4.0
+    rope_original_max: int = 8192
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden_size // self.num_heads
+
+    @property
+    def embed_rows(self) -> int:  # embed_tokens holds vocab_size + 8 rows (<|image|> among the extra ones)
+        return self.vocab_size + 8
+
+    @property
+    def cross_layers(self) -> tuple:
+        return tuple(int(i) for i in self.cross_attention_layers if 0 <= int(i) < self.num_layers)
+
+
+MLLAMA_LM_11B = MllamaLMGeometry()
+SUPPORTED_MLLAMA_LM = {"head_dim": (128,), "heads / kv_heads": (1, 2, 4, 8), "intermediate_size": "a multiple of 64 up to 16384", "num_layers": "1..64",
+                       "vocab_size": "vocab_size + 8 <= 2^18", "vision_output_dim": "a multiple of 64 up to 8192", "hidden_act": ("silu",),
+                       "rope_type": MLLAMA_ROPE_TYPES}
+
+
+def mllama_lm_geometry_problem(geom: MllamaLMGeometry):
+    """None, or why the library refuses `geom` (the text names the field, the value found and the supported set)."""
+    if geom.num_heads < 1 or geom.num_heads > 64 or geom.hidden_size != geom.num_heads * 128:
+        return f"hidden_size = {geom.hidden_size} at num_heads = {geom.num_heads}; supported: 1..64 heads of 128"
+    if geom.num_kv_heads < 1 or geom.num_heads % geom.num_kv_heads or geom.num_heads // geom.num_kv_heads not in (1, 2, 4, 8):
+        return f"num_kv_heads = {geom.num_kv_heads} at num_heads = {geom.num_heads}; supported: heads / kv_heads in (1, 2, 4, 8)"
+    if geom.intermediate_size < 64 or geom.intermediate_size % 64 or geom.intermediate_size > 16384:
+        return f"intermediate_size = {geom.intermediate_size}; supported: a multiple of 64 up to 16384"
+    if not 1 <= geom.num_layers <= 64:
+        return f"num_layers = {geom.num_layers}; supported: 1..64"
+    cross = tuple(geom.cross_attention_layers)
+    if any(b <= a for a, b in zip(cross, cross[1:])) or any(i < 0 for i in cross):
+        return f"cross_attention_layers = {cross}; supported: strictly increasing, non-negative"
+    if geom.vocab_size < 1 or geom.vocab_size + 8 > 1 << 18:
+        return f"vocab_size = {geom.vocab_size}; supported: vocab_size + 8 <= 2^18"
+    if geom.vision_output_dim < 64 or geom.vision_output_dim % 64 or geom.vision_output_dim > 8192:
+        return f"vision_output_dim = {geom.vision_output_dim}; supported: a multiple of 64 up to 8192"
+    if not 0 <= geom.image_token_id < geom.embed_rows:
+        return f"image_token_id = {geom.image_token_id}; supported: 0..vocab_size + 7"
+    if geom.hidden_act != "silu":
+        return f"hidden_act = {geom.hidden_act!r}; supported: 'silu'"
+    if geom.rope_type not in MLLAMA_ROPE_TYPES:
+        return f"rope_type = {geom.rope_type!r}; supported: {MLLAMA_ROPE_TYPES}"
+    return None
+
+
+def mllama_lm_tensor_specs(geom: MllamaLMGeometry = MLLAMA_LM_11B):
+    """(name, shape, kind, scale) in a fixed order: the names of transformers 5.15's `MllamaForConditionalGeneration` state dict
+    without the leading `model.`.  The scales give attention logits and residual branches of order one at every width."""
+    D, KV, I = geom.hidden_size, geom.num_kv_heads * 128, geom.intermediate_size
+    qk, lin, down = 1.3 * D ** -0.5, D ** -0.5, I ** -0.5
+    specs = [
+        ("language_model.embed_tokens.weight", (geom.embed_rows, D), "matrix", 1.0),
+        ("language_model.norm.weight", (D,), "gamma", 0.25),
+        ("multi_modal_projector.weight", (D, geom.vision_output_dim), "matrix", geom.vision_output_dim ** -0.5),
+        ("multi_modal_projector.bias", (D,), "matrix", 0.5),
+    ]
+    cross = set(geom.cross_layers)
+    for i in range(geom.num_layers):
+        p = f"language_model.layers.{i}."
+        specs += [(p + "input_layernorm.weight", (D,), "gamma", 0.25), (p + "post_attention_layernorm.weight", (D,), "gamma", 0.25)]
+        if i in cross:
+            a = p + "cross_attn."
+            # q / k three times the unit scale: without q_norm / k_norm the logits would be three times as large
+            specs += [(a + "q_proj.weight", (D, D), "matrix", 3 * lin), (a + "k_proj.weight", (KV, D), "matrix", 3 * lin), (a + "v_proj.weight", (KV, D), "matrix", lin),
+                      (a + "o_proj.weight", (D, D), "matrix", lin), (a + "q_norm.weight", (128,), "gamma", 0.25), (a + "k_norm.weight", (128,), "gamma", 0.25),
+                      (p + "cross_attn_attn_gate", (1,), "gate", 0.9), (p + "cross_attn_mlp_gate", (1,), "gate", -1.5)]
+        else:
+            a = p + "self_attn."
+            specs += [(a + "q_proj.weight", (D, D), "matrix", qk), (a + "k_proj.weight", (KV, D), "matrix", qk), (a + "v_proj.weight", (KV, D), "matrix", lin),
+                      (a + "o_proj.weight", (D, D), "matrix", lin)]
+        specs += [(p + "mlp.gate_proj.weight", (I, D), "matrix", lin), (p + "mlp.up_proj.weight", (I, D), "matrix", lin),
+                  (p + "mlp.down_proj.weight", (D, I), "matrix", down)]
+    return specs
+
+
+def make_mllama_lm_weights(seed: int = 7, geometry: MllamaLMGeometry = MLLAMA_LM_11B, threads: int = 8) -> dict[str, np.ndarray]:
+    """Seeded synthetic weights of the language tower and the projector, f32 arrays of bf16-representable values, from the
+    counter-based generator of `make_tile_vit_weights`.  The gates are NON-ZERO (a checkpoint's are; a zero gate would switch
+    the cross layers off) and the norm weights are 1 + N(0, 0.25), so that a dropped norm weight or gate changes the output."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    out: dict[str, np.ndarray] = {}
+    jobs = []
+    step = 1 << 22
+    for tid, (name, shape, kind, scale) in enumerate(mllama_lm_tensor_specs(geometry)):
+        n = int(np.prod(shape))
+        if kind == "gate":
+            out[name] = round_to_bf16(np.full(n, scale, dtype=np.float32)).reshape(shape)
+            continue
+        buf = np.empty(n, dtype=np.float32)
+        out[name] = buf.reshape(shape)
+        jobs += [(buf, tid, o, min(step, n - o), scale, kind) for o in range(0, n, step)]
+
+    def fill(job):
+        buf, tid, o, m, scale, kind = job
+        z = hashed_normal4(seed, tid, m, start=o) * np.float32(scale)
+        if kind == "gamma":
+            z += np.float32(1.0)
+        buf[o : o + m] = round_to_bf16(z)
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as ex:
+        list(ex.map(fill, jobs))
+    return out
+
+
+def infer_mllama_lm_geometry(w: dict, **config) -> MllamaLMGeometry:
+    """The geometry the tensor shapes of a canonical-name dict say; what no shape says (the rotary parameters, eps, the image
+    token, which default to the 11B checkpoint's except image_token_id = vocab_size) comes from `config`."""
+    rows, D = np.shape(w["language_model.embed_tokens.weight"])
+    layers = _layer_count(w, "language_model.layers.{}.input_layernorm.weight")
+    cross = tuple(i for i in range(layers) if f"language_model.layers.{i}.cross_attn.q_proj.weight" in w)
+    some = f"language_model.layers.{cross[0]}.cross_attn." if cross else "language_model.layers.0.self_attn."
+    kv = int(np.shape(w[some + "k_proj.weight"])[0])
+    vocab = int(rows) - 8
+    fields = dict(hidden_size=int(D), num_heads=int(D) // 128, num_kv_heads=kv // 128, num_layers=layers, cross_attention_layers=cross, vocab_size=vocab,
+                  intermediate_size=int(np.shape(w["language_model.layers.0.mlp.gate_proj.weight"])[0]),
+                  vision_output_dim=int(np.shape(w["multi_modal_projector.weight"])[1]), image_token_id=vocab)
+    fields.update(config)
+    return MllamaLMGeometry(**fields)
+
+
+def mllama_rope_inv_freq(geom: MllamaLMGeometry) -> np.ndarray:
+    """transformers' rotary inverse frequencies f32 [64] for `geom` (modeling_rope_utils.py: the default rule, and llama3's
+    three bands: wavelengths under original_max / high_freq_factor kept, over original_max / low_freq_factor divided by
+    `factor`, between the two interpolated), in f32 arithmetic as torch forms them."""
+    f32 = np.float32
+    inv = (f32(1.0) / np.power(f32(geom.rope_theta), np.arange(0, 128, 2, dtype=np.int64).astype(f32) / f32(128))).astype(f32)
+    if geom.rope_type == "default":
+        return inv
+    orig, low, high, factor = f32(geom.rope_original_max), f32(geom.rope_low_freq_factor), f32(geom.rope_high_freq_factor), f32(geom.rope_factor)
+    wavelen = f32(2.0 * np.pi) / inv
+    inv_l = np.where(wavelen > orig / low, inv / factor, inv).astype(f32)
+    smooth = (orig / wavelen - low) / (high - low)
+    smoothed = ((f32(1.0) - smooth) * inv_l / factor + smooth * inv_l).astype(f32)
+    medium = ~(wavelen < orig / high) & ~(wavelen > orig / low)
+    return np.where(medium, smoothed, inv_l).astype(f32)
+
+
+def mllama_rope_tables(geom: MllamaLMGeometry, positions: int = MLLAMA_MAX_SEQ):
+    """(cos, sin) f32 [positions, 64]: the angle position * inv_freq formed in f32, as the library's host code builds its table."""
+    ang = (np.arange(positions, dtype=np.float32)[:, None] * mllama_rope_inv_freq(geom)[None, :]).astype(np.float32)
+    return np.cos(ang.astype(np.float64)).astype(np.float32), np.sin(ang.astype(np.float64)).astype(np.float32)
