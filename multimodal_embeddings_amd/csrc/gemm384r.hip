@@ -35,6 +35,24 @@
 // retired by that tile's first phase-5 wait, five phases after the epilogue; K-tile 0 of the next tile was complete before
 // the epilogue began.  The first tile's prologue establishes the same state.  Without a K-tile t+2 (the workgroup's last
 // two K-tiles) phase 5 waits vmcnt(0).
+//
+// Epilogue operands (folded-LayerNorm epilogues 5 and 6, interior tiles).  bias and colsum depend on the column tile and
+// ln_stats on the row panel, none on the K loop, so a wave requests them in compact form, one value per lane, in phase 3 of
+// K-tile nk - 2 (the one phase without an LDS-DMA request): five loads into 8 VGPRs,
+//     bias[n0 + 64 wn + lane]   colsum[n0 + 64 wn + lane]   ln_stats[m0 + 192 wm + 64 k + lane], k = 0..2   (float2)
+// (their two lane offsets, 4 lane and 8 lane, live across the K loop as well: 10 VGPRs in all).
+// In the issue order above they stand between B_hi(t+1) and B_lo(t+2), so the SAME phase-5 wait of that K-tile -- vmcnt(4),
+// or vmcnt(0) without a K-tile t+2 -- retires them, two phases later; no wait count changes and the whole last K-tile lies
+// between that wait and their first use.  With nk = 2 K-tile 0 is that K-tile (the prologue's requests are all older).  They
+// are inline-asm loads: the compiler places no wait of its own for them, and the fast path of the epilogue holds no
+// s_waitcnt vmcnt at all.  The epilogue hands every lane its columns and rows by ds_bpermute_b32 (gemm_epilogue.h,
+// epilogue_wave_192x64_ln).  Edge tiles skip the loads: their guarded path loads per element as before.
+// HAZARD of that form: to the compiler the eight destination registers are defined AT the asm statement.  Should it ever
+// split their live ranges and copy or spill one between the load and the phase-5 wait, the copy would read a register whose
+// data has not landed.  Nothing in the source forbids that; the compile gate does: profiles/gemm384_resources.txt records,
+// for <5> and <6>, that between the five loads and the counted wait no instruction other than the loads names a destination
+// register (today they are touched by the loads and by the epilogue's ds_bpermute_b32 alone).  Re-check it with every change
+// to this file or to the compiler.
 #include <type_traits>
 
 #include "common.h"
@@ -56,6 +74,7 @@ constexpr int NI = 12;                   // row blocks of a wave tile
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_384r(GemmArgs g, int tiles_m, int tiles_n, int gn) {
     static_assert(epi_has_fast_path<EPI>(), "the 384-row kernel is built for the 16-byte fast-path epilogues");
+    constexpr bool LN_EARLY = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -136,6 +155,25 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_384r(GemmArgs g, int tile
         if (wm == 1) S_BARRIER();  // group 1 runs one barrier behind group 0
 
         bf16x8 fa[4], fb[4];
+        // the folded-LayerNorm epilogue's operands of this tile, one value per lane (see "Epilogue operands" above)
+        [[maybe_unused]] float e_bias, e_colsum;
+        [[maybe_unused]] ln_f32x2 e_st[3];
+        [[maybe_unused]] const bool fast_ln = LN_EARLY && n0 + TN <= g.N && m0 + TM <= g.M;
+
+        auto epi_fetch = [&](int t) {
+            if constexpr (LN_EARLY) {
+                if (t == nk - 2 && fast_ln) {  // retired by this K-tile's phase-5 wait; an edge tile loads in its guarded path
+                    const float* cb = g.bias + n0 + wn * 64;
+                    const float* cs = g.colsum + n0 + wn * 64;
+                    const float* rp = g.ln_stats + 2 * (int64_t)(m0 + wm * 192);
+                    asm volatile("global_load_dword %0, %1, %2" : "=v"(e_bias) : "v"(lane * 4), "s"(cb) : "memory");
+                    asm volatile("global_load_dword %0, %1, %2" : "=v"(e_colsum) : "v"(lane * 4), "s"(cs) : "memory");
+                    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(e_st[0]) : "v"(lane * 8), "s"(rp) : "memory");
+                    asm volatile("global_load_dwordx2 %0, %1, %2 offset:512" : "=v"(e_st[1]) : "v"(lane * 8), "s"(rp) : "memory");
+                    asm volatile("global_load_dwordx2 %0, %1, %2 offset:1024" : "=v"(e_st[2]) : "v"(lane * 8), "s"(rp) : "memory");
+                }
+            }
+        };
 
 #define READ_B(ks)                                                                                                        \
     _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                         \
@@ -184,6 +222,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_384r(GemmArgs g, int tile
             READ_B(1)
             __builtin_amdgcn_sched_barrier(0);
             READ_A(1, 0)
+            epi_fetch(t);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // B's last reads have returned: phase 4 refills B_lo
             S_BARRIER();
             MFMA_THIRD(0)
@@ -214,7 +253,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_384r(GemmArgs g, int tile
         const int fr_e = lane_e & 15, fq_e = lane_e >> 4;
         const bool fast = n0 + TN <= g.N && m0 + TM <= g.M;
         if (fast) {
-            epilogue_wave_128x64<EPI>(g, acc, m0 + wm * 192, n0 + wn * 64, fr_e, fq_e, [] {});
+            if constexpr (LN_EARLY) {
+                epilogue_wave_192x64_ln<EPI>(g, acc, m0 + wm * 192, n0 + wn * 64, fr_e, fq_e, e_bias, e_colsum, e_st);
+            } else {
+                epilogue_wave_128x64<EPI>(g, acc, m0 + wm * 192, n0 + wn * 64, fr_e, fq_e, [] {});
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < NI; ++i) {

@@ -183,10 +183,12 @@ __device__ __forceinline__ int row16_col(int jp, int fq) { return ((fq & 1) ? (j
 // would wait for it), then 2 NI fire-and-forget 16-byte stores, which are afterwards exactly the
 // 2 NI youngest vector-memory operations of the wave.  Straight-line code: a branch would make the
 // compiler re-insert vmcnt(0) at every join.
-// NI = 12 leaves no registers for all per-row loads at once (192 accumulators; the residual alone is 96 VGPRs): the rows
-// go in batches of four row blocks (two with a residual), and the loads of batch b + 1 are ISSUED before the stores of batch b, whose
-// packed results wait in the registers its accumulators left (the rule of epilogue_wave_patch_128x64).  Per element the
-// arithmetic and its order are those of NI = 8: the two forms agree bit for bit.
+// NI = 12 leaves no registers for all per-row loads at once (192 accumulators; the residual alone is 96 VGPRs): with a
+// residual (epilogues 2, 8) the rows go in batches of two row blocks, and the loads of batch b + 1 are ISSUED before the
+// stores of batch b, whose packed results wait in the registers its accumulators left (the rule of
+// epilogue_wave_patch_128x64).  Epilogues 0 and 1 have no per-row loads; their rows go in batches of four row blocks, packed
+// and then stored.  Per element the arithmetic and its order are those of NI = 8: the two forms agree bit for bit.  NI = 12
+// with folded LayerNorm does not come here (static_assert): its operands arrive in registers, epilogue_wave_192x64_ln below.
 // NDEF > 0 (NI = 8): the last NDEF / 2 row blocks of the wave tile (i >= 8 - NDEF / 2) are not stored but returned packed in pend[];
 // the caller issues them later (gemm256r.hip, variant 4).
 template <int EPI, int NDEF = 0, int NI, class Between>
@@ -200,6 +202,7 @@ __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&
     constexpr bool RES = EPI == EPI_BIAS_RES || EPI == EPI_BIAS_RES_STATS;
     constexpr bool STATS = EPI == EPI_BIAS_RES_STATS;
     constexpr bool LN = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU || EPI == EPI_LN_BIAS_QGELU || EPI == EPI_LN_BIAS_TGELU;
+    static_assert(NI == 8 || !LN, "epilogue_wave_128x64: 12 row blocks with folded LayerNorm go through epilogue_wave_192x64_ln");
     constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_LN_BIAS_GELU;
     constexpr bool QGELU = EPI == EPI_BIAS_QGELU || EPI == EPI_LN_BIAS_QGELU;
     constexpr bool TGELU = EPI == EPI_BIAS_TGELU || EPI == EPI_LN_BIAS_TGELU;
@@ -339,6 +342,83 @@ __device__ __forceinline__ void epilogue_wave_128x64(const GemmArgs& g, f32x4 (&
         float* plane = g.ln_part + ((int64_t)(fq & 1) * (g.N >> 6) + (nw >> 6)) * g.ln_part_rows + mw + (fq >> 1) * 16 + fr;
 #pragma unroll
         for (int k = 0; k < NI / 2; ++k) plane[k * 32] = u[k];
+    }
+}
+
+// Interior-tile epilogue of one 192 x 64 wave tile (acc[12][4], the 384 x 256 kernel) for the folded-LayerNorm forms, with
+// its operands ALREADY IN REGISTERS in compact form, one value per lane (the kernel requested them under its K loop):
+//   bias_l = bias[nw + lane]   colsum_l = colsum[nw + lane]   st_l[k] = (mean, rstd) of row mw + 64 k + lane, k = 0..2
+// Lane (fq, fr) needs columns 16 j + 4 fq + r and rows 16 i + fr: ds_bpermute_b32 fetches them from the lanes that hold them
+// (no LDS allocation; the LDS pipe is idle here), 32 moves for the columns and 24 for the rows, the rows two row blocks
+// ahead of their use.  No load, no wait on a store: compute, pack and 24 fire-and-forget 16-byte stores.
+// Store order: the two 16-byte stores of a row block (the two halves of the 128-byte line each row owns) are issued
+// back to back, as epilogue_wave_128x64 issues them.  With all left halves first and the right halves twelve stores later
+// the same kernel measured 3-4 % SLOWER per launch than with the loads in the epilogue (gemm384_attempts_not_kept.txt).
+// Registers: 192 accumulators + 32 for bias and colsum of all four column tiles do not fit beside the compact operands,
+// so only the first column-tile pair is materialised at first; row blocks 0 and 1 store their left halves, the second pair
+// goes into the 16 registers that frees, and from then on every row block stores both halves together (22 of 24 adjacent).
+// Per element the arithmetic and its order are those of epilogue_wave_128x64: the two agree bit for bit.
+typedef float ln_f32x2 __attribute__((ext_vector_type(2)));
+template <int EPI>
+__device__ __forceinline__ void epilogue_wave_192x64_ln(const GemmArgs& g, f32x4 (&acc)[12][4], int mw, int nw, int fr, int fq, float bias_l,
+                                                        float colsum_l, const ln_f32x2 (&st_l)[3]) {
+    static_assert(EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_GELU, "epilogue_wave_192x64_ln: folded LayerNorm, plain or with erf-GELU");
+    constexpr bool GELU = EPI == EPI_LN_BIAS_GELU;
+    bf16_t* outb = (bf16_t*)g.out + ((int64_t)mw * g.ldo + nw);
+    const int lo_r = fr * (int)g.ldo;
+    const int ca = fq * 16, ra = fr * 4;  // byte addresses of the source lanes 4 fq (+ 16 j + r) and fr (+ 16 i)
+    auto from_lane = [](int addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v))); };
+    ln_f32x2 st[12];  // (mean, rstd) as one register pair: v_pk_fma_f32 selects the half
+    f32x4 bv[4], sv[4];
+    auto cols = [&](int jp) {
+#pragma unroll
+        for (int j = jp; j < jp + 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bv[j][r] = from_lane(ca + j * 64 + r * 4, bias_l);
+                sv[j][r] = from_lane(ca + j * 64 + r * 4, colsum_l);
+            }
+    };
+    auto compute = [&](int i, int jp) {
+        f32x4 v0, v1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            v0[r] = fmaf(st[i].y, fmaf(-st[i].x, sv[jp][r], acc[i][jp][r]), bv[jp][r]);
+            v1[r] = fmaf(st[i].y, fmaf(-st[i].x, sv[jp + 1][r], acc[i][jp + 1][r]), bv[jp + 1][r]);
+        }
+        if (GELU) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v0[r] = gelu_erf(v0[r]);
+                v1[r] = gelu_erf(v1[r]);
+            }
+        }
+        return pair_to_row16(pack_bf16x4(v0), pack_bf16x4(v1));
+    };
+    auto row = [&](int i) {
+        st[i].x = from_lane(ra + (i & 3) * 64, st_l[i >> 2].x);
+        st[i].y = from_lane(ra + (i & 3) * 64, st_l[i >> 2].y);
+    };
+    auto emit = [&](int i, int jp) { *(uint4*)(outb + (int64_t)i * 16 * g.ldo + lo_r + row16_col(jp, fq)) = compute(i, jp); };
+    cols(0);
+    row(0);
+    row(1);
+    row(2);
+    row(3);
+    __builtin_amdgcn_sched_barrier(0);
+    emit(0, 0);
+    emit(1, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    cols(2);  // into the registers the first 32 accumulators have left
+    __builtin_amdgcn_sched_barrier(0);
+    emit(0, 2);
+    emit(1, 2);
+#pragma unroll
+    for (int i = 2; i < 12; ++i) {
+        if (i + 2 < 12) row(i + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        emit(i, 0);
+        emit(i, 2);
     }
 }
 
